@@ -19,6 +19,9 @@ Prints ONE JSON line (last line of stdout) on rank 0.  Two ways to drive N GPUs,
 
 Every N renders one frame at a time (frames_in_flight 1: a step's time is a frame's latency); --pipeline (one GPU, diagnostic)
 keeps two frames in flight on two streams.
+
+--dump-outputs DIR writes the frame of the last timed step as DIR/frame.npy; every input is seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import argparse
 import json
@@ -44,6 +47,41 @@ HBM_PEAK_GBS = 8000.0    # MI355X_MICROARCH.md: 8.0 TB/s spec
 
 COUNT_KEYS = ("rays", "node_visits", "tri_tests", "samples", "launches", "rays_primary", "rays_shadow", "rays_bounce", "dom_rays",
               "dom_node_visits", "dom_tri_tests")
+
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all
+
+
+def frame_from_device(d_img, H, W):
+    """[H,W,3] float64 host copy of a frame in device memory (a blocking copy, outside the timed region)"""
+    import ctypes as C
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hip_rt
+    img = np.zeros((H, W, 3))
+    hip_rt.check(hip_rt.hip().hipMemcpy(img.ctypes.data_as(C.c_void_p), C.c_void_p(d_img), img.nbytes, 2))
+    return img
+
+
+def dump_outputs(directory, outputs):
+    """--dump-outputs: every array as DIR/<name>.npy in float64.  One larger than its share of the limit is replaced by a fixed sample of
+    its rows (pixels of a frame), drawn with seed 0: DIR/<name>_sample.npy and the flat row indices as DIR/<name>_sample_index.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    budget = DUMP_LIMIT_BYTES // max(1, len(outputs))
+    written = []
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes <= budget:
+            files = {name: a}
+        else:
+            rows = a.reshape(-1, a.shape[-1])
+            k = budget // (rows.shape[1] * 8 + 8)
+            idx = np.sort(np.random.default_rng(0).choice(rows.shape[0], size=k, replace=False))
+            files = {name + "_sample": rows[idx], name + "_sample_index": idx.astype(np.float64)}
+        for f, v in files.items():
+            np.save(os.path.join(directory, f + ".npy"), v)
+            written.append(f + ".npy")
+    return written
 
 
 def committed_profile(name_glob, build_id, kernel=None):
@@ -257,10 +295,11 @@ def run_capi(args):
         dev.collect_stats(st)
         add_stats(tot, st)
         extra["frames_in_flight"] = nbuf
-        if args.save_png:
+        if args.save_png or args.dump_outputs:
             frame_host = np.zeros((H, W, 3))
             bufs[turn[0]].to_host_async(frame_host, streams[turn[0]].h)
             sync()
+        outputs = {"frame": frame_host} if args.dump_outputs else None
         n_ranks_timed = 1
     else:
         t_dev = time.perf_counter()
@@ -281,8 +320,9 @@ def run_capi(args):
         md.collect_stats()                            # (discard what the untimed frames left)
         t0 = time.perf_counter()
         for _ in range(args.steps):                   # every call returns with the frame complete in GPU 0's HBM: all streams synchronised
-            md.render_device(args.spp, args.seed, args.tile_w, args.tile_h, flags=M.RENDER_KEEP_STATS)
+            d_img = md.render_device(args.spp, args.seed, args.tile_w, args.tile_h, flags=M.RENDER_KEEP_STATS)
         elapsed = time.perf_counter() - t0
+        outputs = {"frame": frame_from_device(d_img, H, W)} if args.dump_outputs else None     # (the last step's frame)
         md.collect_stats(st)                          # counters and the event pairs recorded inside the timed region, read after it
         add_stats(tot, st)
         render_ms, gather_ms, comm_ranks = md.last_timing()
@@ -293,7 +333,7 @@ def run_capi(args):
         n_ranks_timed = n
     # ms_trace of a multi-GPU frame is the slowest rank's; launches are summed over ranks
     return {"elapsed": elapsed, "tot": tot, "world": n, "scene": scene, "scene_dir": scene_dir, "frame": frame_host, "extra": extra,
-            "build_id": M.build_id(), "launch_ranks": n_ranks_timed, "M": M, "engine": scene.trace_engine()}
+            "build_id": M.build_id(), "launch_ranks": n_ranks_timed, "M": M, "engine": scene.trace_engine(), "outputs": outputs}
 
 
 def run_procs(args):
@@ -352,7 +392,7 @@ def run_procs(args):
     for i, k in enumerate(COUNT_KEYS):
         tot[k] = float(sm[i])
     frame_host = None
-    if args.save_png and rank == 0:
+    if (args.save_png or args.dump_outputs) and rank == 0:
         frame_host = np.zeros((H, W, 3))
         frame_buf.to_host_async(frame_host, stream.h)
         stream.synchronize()
@@ -364,7 +404,8 @@ def run_procs(args):
     extra = {"launcher": "procs: one process per GPU, mcpt_render_device per rank, gather over an RCCL communicator of the processes (mcpt_comm_*); no torch in the process",
              "hip_runtime": M.hip_runtime_path(), "rccl_ranks": comm_ranks, "gather": "rccl", "frames_in_flight": 1}
     return {"elapsed": elapsed, "tot": tot, "world": world, "scene": scene, "scene_dir": scene_dir, "frame": frame_host, "extra": extra,
-            "build_id": M.build_id(), "launch_ranks": world, "M": M, "engine": scene.trace_engine()}
+            "build_id": M.build_id(), "launch_ranks": world, "M": M, "engine": scene.trace_engine(),
+            "outputs": {"frame": frame_host} if args.dump_outputs else None}
 
 
 def run_torch(args):
@@ -432,7 +473,7 @@ def run_torch(args):
         tot["ms_trace"] = float(mx[1])
         for i, k in enumerate(COUNT_KEYS):
             tot[k] = float(sm[2 + i])
-    frame_host = frame.cpu().numpy() if (args.save_png and rank == 0 and frame is not None) else None
+    frame_host = frame.cpu().numpy() if ((args.save_png or args.dump_outputs) and rank == 0 and frame is not None) else None
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -442,7 +483,8 @@ def run_torch(args):
              "hip_runtime": M.hip_runtime_path(), "hip_versions": "compiled %d, runtime %d (mismatch allowed explicitly)" % M.hip_runtime_info()[:2],
              "frames_in_flight": 1}
     return {"elapsed": elapsed, "tot": tot, "world": world, "scene": scene, "scene_dir": scene_dir, "frame": frame_host, "extra": extra,
-            "build_id": M.build_id(), "launch_ranks": world, "M": M, "engine": scene.trace_engine()}
+            "build_id": M.build_id(), "launch_ranks": world, "M": M, "engine": scene.trace_engine(),
+            "outputs": {"frame": frame_host} if args.dump_outputs else None}
 
 
 def main():
@@ -469,7 +511,12 @@ def main():
     ap.add_argument("--sim-rank", type=int, default=0, help="with --sim-world: which rank's tiles")
     ap.add_argument("--tile-w", type=int, default=0, help="tile width of the rank partition (0: the library's default, 32)")
     ap.add_argument("--tile-h", type=int, default=0, help="tile height of the rank partition (0: the library's default, 8)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frame the last of them computed as DIR/frame.npy (float64 [H,W,3]; above 64 MB "
+                         "a fixed seeded sample of its pixels)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # ONE JSON line on stdout: libraries that print banners to file descriptor 1 (RCCL's version block, Gloo's connection chatter)
     # are sent to stderr for the length of the run; the line itself goes to the real stdout at the end.
@@ -483,7 +530,7 @@ def main():
     res = run_torch(args) if launcher == "torch" else (run_procs(args) if launcher == "procs" else run_capi(args))
     M = res["M"]
     tot, elapsed, world, scene_dir, scene = res["tot"], res["elapsed"], res["world"], res["scene_dir"], res["scene"]
-    steps = max(1, args.steps)
+    steps = args.steps
     sec_per_frame = elapsed / steps
     rays = float(tot["rays"])
     value = rays / elapsed / 1e6
@@ -561,6 +608,8 @@ def main():
                      "note": "launches of k_wf_trace, timed with HIP events on the launching stream"},
     }
     out.update(res["extra"])
+    if args.dump_outputs:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, res["outputs"])}
     if args.save_png and res["frame"] is not None:
         M.write_png(args.save_png, M.imshow_rgb8(res["frame"]))
     if world == 1 and not args.no_cpu_baseline and scene_dir is not None and args.scene != "interior":

@@ -49,9 +49,17 @@ def _worker(rank, world, port, tmp):
 
 @pytest.mark.parametrize("world", [2])
 def test_gather_assembles_the_frame(world, tmp_path):
-    import torch.multiprocessing as mp
+    # the standard library's spawn, not torch.multiprocessing: torch is imported by the workers only, never by this process (a whole-suite
+    # run on a GPU machine goes on to the GPU tests in it)
+    import multiprocessing as mp
     port = 29500 + (os.getpid() % 2000)
-    mp.spawn(_worker, args=(world, port, str(tmp_path)), nprocs=world, join=True)
+    ctx = mp.get_context("spawn")
+    procs = [ctx.Process(target=_worker, args=(r, world, port, str(tmp_path))) for r in range(world)]
+    for p_ in procs:
+        p_.start()
+    for p_ in procs:
+        p_.join(300)
+    assert [p_.exitcode for p_ in procs] == [0] * world
     frame = np.load(tmp_path / "frame.npy")
     full = np.load(tmp_path / "full.npy")
     assert np.array_equal(frame.view(np.uint64), full.view(np.uint64))

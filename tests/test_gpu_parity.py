@@ -937,6 +937,41 @@ def test_one_process_per_gpu_without_torch(mcpt, tmp_path):
         pg.close()
 
 
+def test_bench_dumps_the_frame_of_its_last_step(mcpt, tmp_path):
+    """bench.py --dump-outputs DIR: the frame the timed path returned in its last step, as DIR/frame.npy in float64 -- the same bits
+    whatever the number of steps, and the frame a one-GPU render of the same scene files returns."""
+    import importlib.util
+    import json
+    import shutil
+    import subprocess
+    import sys
+    frames = []
+    for steps, warmup in ((2, 1), (1, 0)):
+        d = tmp_path / ("dump%d" % steps)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--width", "320",
+                              "--height", "180", "--spp", "8", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                             capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert out.returncode == 0, out.stderr[-2000:]
+        line = json.loads([ln for ln in out.stdout.splitlines() if ln.strip()][-1])
+        assert line["steps"] == steps and line["dumped_outputs"]["files"] == ["frame.npy"]
+        f = np.load(str(d / "frame.npy"))
+        assert f.dtype == np.float64 and f.shape == (180, 320, 3) and f.max() > 0
+        frames.append(f)
+    assert np.array_equal(_bits(frames[0]), _bits(frames[1]))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    scene_dir = bench.write_scene_dir("cornell-box", 320, 180)
+    sc = mcpt.Scene(scene_dir, "cornell-box")
+    dev = mcpt.Device(sc, 0)
+    try:
+        assert np.array_equal(_bits(frames[0]), _bits(dev.generateImg(8, seed=0)))
+    finally:
+        dev.close()
+        sc.close()
+        shutil.rmtree(scene_dir, ignore_errors=True)
+
+
 def test_bench_refuses_more_gpus_than_visible_and_quotes_only_profiles_of_the_loaded_build(mcpt, tmp_path):
     """`python bench.py --gpus N` without a launcher needs N visible GPUs (exit code 2, nothing on stdout).  Counters quoted from
     profiles/ must come from the build that is loaded: committed_profile() matches the file's build_id against mcpt_build_id()."""

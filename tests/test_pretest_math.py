@@ -173,3 +173,34 @@ def test_bench_quotes_only_profiles_of_the_loaded_build(tmp_path):
         assert j is None and "no committed profile" in why
     finally:
         bench.ROOT = old
+
+
+def test_bench_dump_outputs_stays_within_its_limit(tmp_path, monkeypatch):
+    """bench.dump_outputs: arrays within the limit are written whole in float64; a larger one is replaced by the same seeded sample of its
+    rows on every call, with the row indices beside it, and the files stay within the limit."""
+    import bench
+    rng = np.random.default_rng(3)
+    small = rng.random((9, 16, 3)).astype(F)
+    assert bench.dump_outputs(str(tmp_path / "a"), {"frame": small}) == ["frame.npy"]
+    got = np.load(str(tmp_path / "a" / "frame.npy"))
+    assert got.dtype == np.float64 and np.array_equal(got, small.astype(np.float64))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 4096)
+    big = rng.random((40, 64, 3))
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), {"frame": big}) == ["frame_sample.npy", "frame_sample_index.npy"]
+    b, c = tmp_path / "b", tmp_path / "c"
+    assert sum(f.stat().st_size - 128 for f in b.iterdir()) <= 4096     # (a .npy header is 128 bytes)
+    val, idx = np.load(str(b / "frame_sample.npy")), np.load(str(b / "frame_sample_index.npy"))
+    assert val.dtype == np.float64 and idx.dtype == np.float64 and len(idx) == len(val) > 0 and len(np.unique(idx)) == len(idx)
+    assert np.array_equal(val, big.reshape(-1, 3)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(str(c / "frame_sample_index.npy"))) and np.array_equal(val, np.load(str(c / "frame_sample.npy")))
+
+
+def test_bench_refuses_fewer_than_one_step():
+    """--steps is the number of timed steps: zero or fewer is refused before anything runs, not rounded up."""
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 2 and not out.stdout.strip() and "--steps" in out.stderr
