@@ -227,6 +227,43 @@ int  mcpt_sample_radiance(mcpt_device*, uint64_t seed, const int32_t* pix, const
 /* number of pixels owned by (rank, world) under the tile partition, and their indices (row*W+col, ascending) */
 int64_t mcpt_owned_pixels(const mcpt_scene*, const mcpt_render_params*, int32_t* pixels /* may be NULL */);
 
+/* ---- progressive frames (since the progressive-rendering change; no reference counterpart) ---- */
+/* A frame of N = params->spp samples per pixel rendered in passes: mcpt_progressive_step(h, n) renders samples [done, min(done + n, N)) of
+ * every pixel the handle owns (params->rank / world / tile_w / tile_h as mcpt_render; MCPT_RENDER_MEGAKERNEL honoured; MCPT_RENDER_PIPELINE
+ * and MCPT_RENDER_KEEP_STATS refused with MCPT_ERR_ARG).  Every (pixel, sample) owns its RNG key and the passes continue the frame's
+ * sequential float fold, so at done == N the image is mcpt_render's frame bit for bit, whatever the pass sizes were.  Beside the fold the
+ * handle keeps, per pixel and channel, sum x and sum x^2 of the sample radiance in fp64 (k order).
+ *   step   : n <= 0, or a step after done == N, returns MCPT_ERR_ARG; synchronous (the pass is finished when it returns).
+ *   image  : host H*W*3 doubles; pixels the handle does not own keep the caller's values.  img = the current estimate: at done == N the
+ *            float-folded frame itself, at done < N the fp64 mean sum_x / done (NOT the float fold, which is only complete at N; the two
+ *            differ in the last float bits).  stderr_img (may be NULL; img may be NULL if stderr_img is not) = the standard error of that
+ *            mean, sqrt(s^2 / done) with s^2 the unbiased sample variance (clamped at 0), per channel; 0 while done < 2.
+ *            _device: the same into device buffers on `stream`, asynchronous.
+ *   noise  : over the owned pixels whose primary ray hit, after `done` samples: sum_se2 = sum over pixels and channels of stderr^2,
+ *            sum_mean2 = sum of mean^2, pixels = their number; rel_error = sqrt(sum_se2 / sum_mean2) (a relative RMS standard error),
+ *            abs_rms = sqrt(sum_se2 / (3 pixels)).  Deterministic: the same bits on any MI355X and for any pass sizes that reach `done`.
+ *            done < 2: rel_error = abs_rms = +inf and the sums 0.
+ *   next_pass : the schedule render_scene uses (a pure function).  The first pass is min(N, 8); each later one doubles the samples done,
+ *            min(N - done, done).  remaining_s = +inf: no time budget; otherwise a later pass is capped at floor(remaining_s / s_per_sample)
+ *            (seconds per sample per pixel of the last pass), and 0 -- stop -- is returned when that cap is < 1 or remaining_s <= 0.  Also 0
+ *            when done >= N.
+ * A handle shares ownership of its device (as a device does of its scene): the device goes with the last of mcpt_device_free and the
+ * mcpt_progressive_free of the handles created on it.  Without a HIP device create returns MCPT_ERR_NO_DEVICE. */
+typedef struct mcpt_progressive mcpt_progressive;
+typedef struct {
+    int32_t done, spp;
+    int64_t pixels;
+    double rel_error, abs_rms, sum_se2, sum_mean2;
+} mcpt_noise;
+int  mcpt_progressive_create(mcpt_device*, const mcpt_render_params*, mcpt_progressive** out);
+int  mcpt_progressive_step(mcpt_progressive*, int32_t n, mcpt_stats* stats /* may be NULL */);
+int  mcpt_progressive_done(const mcpt_progressive*);
+int  mcpt_progressive_noise(mcpt_progressive*, mcpt_noise* out);
+int  mcpt_progressive_image(mcpt_progressive*, double* img, double* stderr_img);
+int  mcpt_progressive_image_device(mcpt_progressive*, double* d_img, double* d_stderr, void* stream);
+int  mcpt_progressive_next_pass(int32_t spp, int32_t done, double remaining_s, double s_per_sample);
+void mcpt_progressive_free(mcpt_progressive*);
+
 /* ---- integrator over several GPUs of one node (no reference counterpart: generateImg is single-process OpenMP) ---- */
 /* The frame is cut into tiles dealt to the GPUs exactly as mcpt_render_params.rank/world describe (rank r = devices[r]); the scene
  * is resident on every GPU; one host thread per GPU renders its tiles; at the end of the frame every rank's pixels travel as one
@@ -296,6 +333,7 @@ int  mcpt_decode_jpeg(const char* file, int32_t* width, int32_t* height, uint8_t
 int  mcpt_render_scene(const char* path, const char* filename, int32_t spp);
 #define MCPT_OUT_PNG_DEFLATE  1      /* the .png is deflate-compressed (same pixels; the reference's svpng stores them raw) */
 #define MCPT_OUT_PFM          2      /* also write <prefix>-SPP<N>.pfm: the linear fp32 radiance before imshow's clamp */
+#define MCPT_OUT_ERROR_PFM    4      /* also write <prefix>-SPP<N>.err.pfm: the per-pixel standard error (mcpt_progressive_image) as fp32 */
 typedef struct {
     uint64_t seed;
     int32_t  device;            /* HIP ordinal */
@@ -313,6 +351,13 @@ typedef struct {
     int32_t  num_devices;       /* > 0: devices[0..num_devices); -1: every visible GPU */
     int32_t  gather;            /* MCPT_GATHER_* */
     const int32_t* devices;     /* NULL with num_devices > 0: ordinals 0..num_devices-1 */
+    /* since the progressive-rendering change (mcpt_render_scene_opts only).  When noise_target > 0, time_budget_s > 0 or MCPT_OUT_ERROR_PFM
+     * is set, the frame is rendered progressively (mcpt_progressive_*, the passes of mcpt_progressive_next_pass): it stops after the
+     * first pass whose rel_error <= noise_target, or when the time budget (seconds, counted from the first pass) allows no further pass,
+     * or at N.  A frame stopped at k < N samples is written as <prefix>-SPP<k>.png (the estimate of mcpt_progressive_image); at N it is
+     * the plain call's frame, byte for byte.  With a checkpoint or num_devices != 0 these return MCPT_ERR_ARG. */
+    double   noise_target;      /* 0 = none */
+    double   time_budget_s;     /* 0 = none */
 } mcpt_render_scene_options;
 /* The struct has grown with MCPT_VERSION and carries no size field.  mcpt_render_scene_ex -- the only entry point through version
  * 102 -- reads the struct as it stood at 102, i.e. every field above: what a caller sets through it (load_flags, checkpoint,

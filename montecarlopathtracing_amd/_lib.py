@@ -61,7 +61,17 @@ class RenderSceneOptions(C.Structure):
                 ("quiet", C.c_int32), ("output_prefix", C.c_char_p),
                 ("load_flags", C.c_int32), ("output_flags", C.c_int32), ("checkpoint", C.c_char_p),
                 ("checkpoint_parts", C.c_int32), ("reserved", C.c_int32),
-                ("num_devices", C.c_int32), ("gather", C.c_int32), ("devices", C.POINTER(C.c_int32))]
+                ("num_devices", C.c_int32), ("gather", C.c_int32), ("devices", C.POINTER(C.c_int32)),
+                ("noise_target", C.c_double), ("time_budget_s", C.c_double)]
+
+
+class Noise(C.Structure):
+    """mcpt_noise: the frame summary of a progressive frame after `done` of `spp` samples"""
+    _fields_ = [("done", C.c_int32), ("spp", C.c_int32), ("pixels", C.c_int64), ("rel_error", C.c_double), ("abs_rms", C.c_double),
+                ("sum_se2", C.c_double), ("sum_mean2", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 # every symbol include/mcpt.h declares
@@ -77,6 +87,8 @@ EXPORTS = [
     "mcpt_render", "mcpt_render_device", "mcpt_device_collect_stats", "mcpt_sample_radiance", "mcpt_owned_pixels",
     "mcpt_quantize_rgb8", "mcpt_write_png", "mcpt_png_encode", "mcpt_png_encode_deflate", "mcpt_write_png_deflate", "mcpt_write_pfm",
     "mcpt_checkpoint_save", "mcpt_checkpoint_load", "mcpt_decode_jpeg",
+    "mcpt_progressive_create", "mcpt_progressive_step", "mcpt_progressive_done", "mcpt_progressive_noise", "mcpt_progressive_image",
+    "mcpt_progressive_image_device", "mcpt_progressive_next_pass", "mcpt_progressive_free",
     "mcpt_multi_create", "mcpt_multi_num_devices", "mcpt_multi_render", "mcpt_multi_render_device", "mcpt_multi_last_timing", "mcpt_multi_collect_stats", "mcpt_multi_free",
     "mcpt_comm_unique_id", "mcpt_comm_create", "mcpt_comm_size", "mcpt_comm_gather_frame", "mcpt_comm_allreduce", "mcpt_comm_free",
     "mcpt_render_scene", "mcpt_render_scene_ex", "mcpt_render_scene_opts",
@@ -153,6 +165,15 @@ def lib():
     L.mcpt_checkpoint_save.argtypes = [C.c_char_p, P, D, C.c_int32, C.c_uint64, C.c_int32, U8]
     L.mcpt_checkpoint_load.argtypes = [C.c_char_p, P, D, C.c_int32, C.c_uint64, C.c_int32, U8]
     L.mcpt_decode_jpeg.argtypes = [C.c_char_p, I32, I32, U8, C.c_int64]
+    L.mcpt_progressive_create.argtypes = [P, C.POINTER(RenderParams), C.POINTER(P)]
+    L.mcpt_progressive_step.argtypes = [P, C.c_int32, C.POINTER(Stats)]
+    L.mcpt_progressive_done.argtypes = [P]
+    L.mcpt_progressive_noise.argtypes = [P, C.POINTER(Noise)]
+    L.mcpt_progressive_image.argtypes = [P, D, D]
+    L.mcpt_progressive_image_device.argtypes = [P, P, P, P]
+    L.mcpt_progressive_next_pass.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double]
+    L.mcpt_progressive_free.argtypes = [P]
+    L.mcpt_progressive_free.restype = None
     L.mcpt_multi_create.argtypes = [P, I32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(P)]
     L.mcpt_multi_num_devices.argtypes = [P]
     L.mcpt_multi_render.argtypes = [P, C.POINTER(RenderParams), D, C.POINTER(Stats)]

@@ -5,14 +5,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import McptError, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
+from ._lib import McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
 RENDER_DEFAULT, RENDER_MEGAKERNEL = 0, 2
 RENDER_KEEP_STATS, RENDER_PIPELINE = 4, 8
 LOAD_STANDARD_OBJ, LOAD_MTLLIB, LOAD_MORTON_BOUNDS = 1, 2, 4
-OUT_PNG_DEFLATE, OUT_PFM = 1, 2
+OUT_PNG_DEFLATE, OUT_PFM, OUT_ERROR_PFM = 1, 2, 4
 BUILD_HOST, BUILD_DEVICE, BUILD_DEVICE_FAST, BUILD_DEVICE_SAH = 0, 1, 2, 3
 SCENE_DEFER_BUILD = 1
 GATHER_PEER, GATHER_RCCL = 0, 1
@@ -281,6 +281,68 @@ class Device:
         check(lib().mcpt_sample_radiance(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), pix.shape[0], _p(rgb, C.c_double)))
         return rgb
 
+    def progressive(self, spp, seed=0, rank=0, world=1, tile_w=0, tile_h=0, flags=0):
+        """A frame of `spp` samples per pixel rendered in passes (mcpt_progressive_*): see Progressive."""
+        return Progressive(self, spp, seed, rank, world, tile_w, tile_h, flags)
+
+
+class Progressive:
+    """A progressive frame on a Device.  step(n) renders the next n samples of every owned pixel; at done == spp, image() is generateImg's
+    frame bit for bit.  Before that, image() is the fp64 mean of the samples done (not the float fold) and stderr() its standard error."""
+
+    def __init__(self, device, spp, seed=0, rank=0, world=1, tile_w=0, tile_h=0, flags=0):
+        self.device, self.spp = device, spp
+        self._h = C.c_void_p()
+        rp = RenderParams(spp, seed, rank, world, tile_w, tile_h, flags)
+        check(lib().mcpt_progressive_create(device._h, C.byref(rp), C.byref(self._h)))
+
+    def step(self, n, stats=None):
+        check(lib().mcpt_progressive_step(self._h, n, C.byref(stats) if stats is not None else None))
+        return self.done
+
+    @property
+    def done(self):
+        rc = lib().mcpt_progressive_done(self._h)
+        if rc < 0:
+            check(rc)
+        return rc
+
+    def noise(self):
+        """Noise: rel_error, abs_rms, sum_se2, sum_mean2, pixels (owned hit pixels), done, spp"""
+        o = Noise()
+        check(lib().mcpt_progressive_noise(self._h, C.byref(o)))
+        return o
+
+    def image(self, img=None):
+        """the current estimate as [H,W,3] float64 (pixels not owned: left as in img, else 0)"""
+        if img is None:
+            img = np.zeros((self.device.height, self.device.width, 3))
+        check(lib().mcpt_progressive_image(self._h, _p(img, C.c_double), None))
+        return img
+
+    def stderr(self, err=None):
+        """the per-pixel, per-channel standard error of image() as [H,W,3] float64 (0 while done < 2)"""
+        if err is None:
+            err = np.zeros((self.device.height, self.device.width, 3))
+        check(lib().mcpt_progressive_image(self._h, None, _p(err, C.c_double)))
+        return err
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().mcpt_progressive_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def progressive_next_pass(spp, done, remaining_s=float("inf"), s_per_sample=0.0):
+    """render_scene's pass schedule (mcpt_progressive_next_pass): samples of the next pass, 0 = stop"""
+    return lib().mcpt_progressive_next_pass(spp, done, remaining_s, s_per_sample)
+
 
 class MultiDevice:
     """generateImg on several GPUs of the node behind one call (mcpt_multi_*): one host thread per GPU inside the library, tiles
@@ -416,9 +478,11 @@ def morton_code(x, y, z):
 
 
 def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, height=0, quiet=True, output_prefix=None, stats=None,
-                 load_flags=0, output_flags=0, checkpoint=None, checkpoint_parts=0, devices=None, gather=GATHER_PEER):
+                 load_flags=0, output_flags=0, checkpoint=None, checkpoint_parts=0, devices=None, gather=GATHER_PEER, noise_target=0.0,
+                 time_budget_s=0.0):
     """render_scene(path, filename, N) of MTPC/MTPC.cpp:35; writes <prefix>-SPP<N>.png (default ../result/<filename>).
-    devices: list of GPU ordinals, or -1 for every visible GPU (the frame is then rendered by mcpt_multi_*)."""
+    devices: list of GPU ordinals, or -1 for every visible GPU (the frame is then rendered by mcpt_multi_*).
+    noise_target / time_budget_s / OUT_ERROR_PFM: a progressive frame that may stop at k < N samples (<prefix>-SPP<k>.png)."""
     dev_arr, ndev = None, 0
     if devices == -1:
         ndev = -1
@@ -427,7 +491,7 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
         dev_arr, ndev = _p(keep, C.c_int32), keep.shape[0]
     o = RenderSceneOptions(seed, device, width, height, int(quiet), output_prefix.encode() if output_prefix else None,
                            load_flags, output_flags, checkpoint.encode() if checkpoint else None, checkpoint_parts, 0,
-                           ndev, gather, dev_arr)
+                           ndev, gather, dev_arr, noise_target, time_budget_s)
     check(lib().mcpt_render_scene_opts(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o),
                                        C.byref(stats) if stats is not None else None))
     return True

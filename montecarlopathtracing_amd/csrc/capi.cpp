@@ -168,6 +168,9 @@ struct mcpt_device {
     unsigned int slow_cap = 1u << 20;
     LaunchCfg cfg;                                  // this GPU's resident grids and knobs
     long long finish_threshold = 500000;            // paths left at which the finishing pass takes over (MCPT_FINISH_PATHS; sweep: flat from 2e5 to 1e6)
+    // Shared ownership, as a device holds its scene: the caller's handle and every progressive frame created on the device hold one
+    // reference each; the device goes with the last of mcpt_device_free / mcpt_progressive_free.
+    std::atomic<int> refs{1};
 };
 
 extern "C" {
@@ -559,7 +562,7 @@ int64_t mcpt_owned_pixels(const mcpt_scene* h, const mcpt_render_params* p, int3
 // ------------------------------------------------------------------------------------------------ device
 void mcpt_device_free(mcpt_device* d)
 {
-    if (!d) return;
+    if (!d || d->refs.fetch_sub(1) != 1) return;
     (void)hipSetDevice(d->ordinal);
     (void)hipDeviceSynchronize();          // frames of a sequence may still be in flight on the caller's streams
     void* ptrs[] = {d->nodes, d->tris, d->shade, d->materials, d->lights, d->light_tris, d->light_cdf, d->texels, d->fast_nodes, d->fast_tris, d->fast_pre, d->cw_nodes, d->d_order,
@@ -1018,6 +1021,9 @@ static void counters_to_stats(const DCounters& c, mcpt_stats* s, bool print_diag
                                  "  ray o %.17g %.17g %.17g d %.17g %.17g %.17g\n",
                          g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13], g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21]);
         }
+#ifdef MCPT_PRE_CHECK
+        std::fprintf(stderr, "KERNARG CHECK: %llu of %llu trace launches read another WfArgs through the kernarg segment\n", c.pad[21], c.pad[22]);
+#endif
         if (c.pad[13]) std::fprintf(stderr, "finish diag: longest wave %llu steps, %.0f us alive, %.0f us of it in the ray walks (100 MHz ticks; maxima over waves and launches)\n",
                                     c.pad[13], double(c.pad[14]) / 100.0, double(c.pad[15]) / 100.0);
         const double lt = double(c.pad[16] + c.pad[17] + c.pad[18]);
@@ -1101,13 +1107,29 @@ static int prepare_partition(mcpt_device* d, const mcpt_render_params* p, hipStr
     return MCPT_OK;
 }
 
+// Which camera samples of every owned pixel a render call covers and where they are folded.  A frame: samples [0, N) through
+// k_fold_samples (mom == null).  A progressive pass (mcpt_progressive_step): samples [k0, k0 + n) of a frame of N through
+// k_fold_progressive, which continues the image's fold and the moments in mom.  n is the layout stride of the pass (WfArgs::spp):
+// chunks are sized from it.
+struct SampleRange {
+    int k0, n, N;
+    double* mom;
+    uint8_t* hit;
+};
+
+static void fold_range(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, int first, int n_slots, double* d_img, hipStream_t st)
+{
+    if (r.mom) launch_fold_progressive(f.rad, d->pixels, f.hits, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, st);
+    else launch_fold_samples(f.rad, d->pixels, f.hits, first, n_slots, r.n, d_img, st);
+}
+
 // megakernel path: one lane per camera sample, the whole path in one kernel (kept for A/B runs and as a second
 // implementation the wavefront path is checked against)
-static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const mcpt_render_params* p, double* d_img, bool timed, hipStream_t st,
-                             double& ms_trace, int& launches)
+static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, const mcpt_render_params* p, double* d_img, bool timed,
+                             hipStream_t st, double& ms_trace, int& launches)
 {
     const int64_t npx = d->n_pixels;
-    const int spp = p->spp;
+    const int spp = r.n;
     const size_t per_pixel = size_t(spp) * 3 * sizeof(double);
     int64_t chunk = int64_t(std::max<size_t>(d->sample_budget_bytes / per_pixel, 64));
     chunk = std::min<int64_t>(chunk, npx);
@@ -1120,7 +1142,7 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const mc
     for (int64_t first = 0; first < npx; first += chunk) {
         const int n_slots = int(std::min<int64_t>(chunk, npx - first));
         if (timed) HIP_TRY(hipEventRecord(d->ev[2], st));
-        launch_shade_samples(d->ds, p->seed, d->dirs, d->pixels, f.hits, int(first), n_slots, spp, f.rad, f.ctr, st);
+        launch_shade_samples(d->ds, p->seed, d->dirs, d->pixels, f.hits, int(first), n_slots, spp, r.k0, f.rad, f.ctr, st);
         HIP_TRY(hipGetLastError());
         if (timed) {
             HIP_TRY(hipEventRecord(d->ev[3], st));
@@ -1130,7 +1152,7 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const mc
             ms_trace += ms;
         }
         launches++;
-        launch_fold_samples(f.rad, d->pixels, f.hits, int(first), n_slots, spp, d_img, st);
+        fold_range(d, f, r, int(first), n_slots, d_img, st);
         HIP_TRY(hipGetLastError());
     }
     return MCPT_OK;
@@ -1139,11 +1161,11 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const mc
 // wavefront path (wavefront.hpp): per chunk, lockstep iterations of logic + trace over compacted path state in HBM.
 // timed: event pairs around the trace launches, summed here (one stream synchronisation at the end); keep: the pairs are recorded
 // and left in d->ev_pool for mcpt_device_collect_stats -- the frame ends without the host waiting for it.
-static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const mcpt_render_params* p, double* d_img, bool timed, bool keep, hipStream_t st,
-                            double& ms_trace, int& launches)
+static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, const mcpt_render_params* p, double* d_img, bool timed,
+                            bool keep, hipStream_t st, double& ms_trace, int& launches)
 {
     const int64_t npx = d->n_pixels;
-    const int spp = p->spp;
+    const int spp = r.n;
     const int nl = d->ds.num_lights;
     const bool fast = d->trace_mode == MCPT_TRACE_FAST;
     const size_t bpp = wf_bytes_per_path(nl);
@@ -1190,7 +1212,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const mcp
     WfArgs a{};
     WfState A, B;
     if (!wf_carve(f.wf_ws, f.wf_ws_bytes, cap, nl, A, B, a.rays)) return fail(MCPT_ERR_NOMEM, "wavefront workspace too small");
-    a.cap = cap; a.nl = nl; a.spp = spp; a.seed = p->seed; a.pixels = d->pixels; a.hit_slots = f.hit_slots; a.surf = f.surf; a.alive_base = f.alive_base; a.hits = f.hits;
+    a.cap = cap; a.nl = nl; a.spp = spp; a.sample_base = r.k0; a.seed = p->seed; a.pixels = d->pixels; a.hit_slots = f.hit_slots; a.surf = f.surf; a.alive_base = f.alive_base; a.hits = f.hits;
     a.dirs = d->dirs; a.rad = f.rad; a.counts = f.wf_counts; a.ctr = f.ctr; a.tris = d->tris; a.materials = d->materials; a.queue = fast ? f.queue : nullptr;
     a.finish_below = fast ? unsigned(std::min<long long>(std::max<long long>(d->finish_threshold, 0), 1ll << 30)) : 0u;
     // Iterations are enqueued without waiting for their counts: every kernel reads its input count from the device slot the
@@ -1265,7 +1287,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const mcp
             launch_wf_logic(d->ds, a, n_upper, false, st, d->cfg);
             HIP_TRY(hipGetLastError());
         }
-        launch_fold_samples(f.rad, d->pixels, f.hits, int(first), n_slots, spp, d_img, st);
+        fold_range(d, f, r, int(first), n_slots, d_img, st);
         HIP_TRY(hipGetLastError());
     }
     if (timed && !keep) {
@@ -1280,7 +1302,8 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const mcp
     return MCPT_OK;
 }
 
-static int render_device_impl(mcpt_device* d, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, hipStream_t st, int& slot_used);
+static int render_device_impl(mcpt_device* d, const SampleRange& r, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, hipStream_t st,
+                              int& slot_used);
 
 int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, void* stream)
 {
@@ -1290,7 +1313,8 @@ int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_im
     // a frame that fails half-way must not leave half-recorded event pairs behind: mcpt_device_collect_stats would trip over them
     const size_t ev_used0 = d->ev_used, frame_ev_used0 = d->frame_ev_used;
     int slot_used = -1;
-    const int rc = render_device_impl(d, p, d_img, stats, static_cast<hipStream_t>(stream), slot_used);
+    const SampleRange whole{0, p->spp, p->spp, nullptr, nullptr};
+    const int rc = render_device_impl(d, whole, p, d_img, stats, static_cast<hipStream_t>(stream), slot_used);
     if (rc != MCPT_OK) {
         d->ev_used = ev_used0; d->frame_ev_used = frame_ev_used0;
         if (slot_used >= 0) d->slot[slot_used].keeping = false;      // its counters hold part of a frame: cleared by the next one
@@ -1298,7 +1322,8 @@ int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_im
     return rc;
 }
 
-static int render_device_impl(mcpt_device* d, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, hipStream_t st, int& slot_used)
+static int render_device_impl(mcpt_device* d, const SampleRange& r, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, hipStream_t st,
+                              int& slot_used)
 {
     const bool keep = (p->flags & MCPT_RENDER_KEEP_STATS) != 0 && !(p->flags & MCPT_RENDER_MEGAKERNEL);
     const bool timed = stats != nullptr && !keep;
@@ -1336,12 +1361,12 @@ static int render_device_impl(mcpt_device* d, const mcpt_render_params* p, doubl
     HIP_TRY(hipGetLastError());
     double ms_trace = 0;
     int launches = 0;
-    if (p->flags & MCPT_RENDER_MEGAKERNEL) rc = render_megakernel(d, f, p, d_img, timed, st, ms_trace, launches);
-    else rc = render_wavefront(d, f, p, d_img, timed, keep, st, ms_trace, launches);
+    if (p->flags & MCPT_RENDER_MEGAKERNEL) rc = render_megakernel(d, f, r, p, d_img, timed, st, ms_trace, launches);
+    else rc = render_wavefront(d, f, r, p, d_img, timed, keep, st, ms_trace, launches);
     if (rc) return rc;
     if (keep) {
         HIP_TRY(hipEventRecord(fe->second, st));
-        d->kept_samples += uint64_t(npx) * uint64_t(p->spp); d->kept_primary += uint64_t(npx); d->kept_launches += launches;
+        d->kept_samples += uint64_t(npx) * uint64_t(r.n); d->kept_primary += uint64_t(npx); d->kept_launches += launches;
     } else HIP_TRY(hipEventRecord(d->ev[1], st));
     HIP_TRY(hipEventRecord(f.done, st));
     f.used = true;
@@ -1353,7 +1378,7 @@ static int render_device_impl(mcpt_device* d, const mcpt_render_params* p, doubl
         float ms = 0;
         HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
         stats->ms_total = ms; stats->ms_trace = ms_trace; stats->launches = launches;
-        stats->samples = uint64_t(npx) * uint64_t(p->spp);      // camera samples covered (a primary miss is a finished sample)
+        stats->samples = uint64_t(npx) * uint64_t(r.n);         // camera samples covered (a primary miss is a finished sample)
         stats->rays_primary = uint64_t(npx);
     }
     return MCPT_OK;
@@ -1442,6 +1467,155 @@ int mcpt_sample_radiance(mcpt_device* d, uint64_t seed, const int32_t* pix, cons
     cleanup();
     if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
     return MCPT_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ progressive frames
+// A frame of N samples per pixel rendered in passes of consecutive sample ranges.  Every (pixel, sample) owns its RNG key, so a pass
+// of samples [k0, k1) computes the same radiance as the one-shot frame does for them, and k_fold_progressive continues the frame's float
+// fold where the last pass left it: at done == N the image is mcpt_render's frame bit for bit.
+struct mcpt_progressive {
+    mcpt_device* d = nullptr;          // holds a reference (mcpt_device::refs)
+    mcpt_render_params p{};            // p.spp = N
+    int done = 0;
+    bool broken = false;               // a step failed half-way: the image and the moments hold part of a pass
+    int32_t* pixels = nullptr; int64_t n_pixels = 0;   // the owned pixels of (rank, world)
+    double* img = nullptr;             // W*H*3: the float fold of samples [0, done) (pixels not owned stay 0)
+    double* mom = nullptr;             // W*H*2*3: sum x, sum x*x per channel
+    uint8_t* hit = nullptr;            // W*H: the pixel's primary ray hit
+    double* partials = nullptr;        // noise_ranges() x 3
+    double* sums = nullptr;            // 4 doubles: sum se2, sum mean^2, hit pixels, 0
+    double* h_sums = nullptr;          // pinned copy of sums (the pass's one 32-byte read-back)
+};
+
+void mcpt_progressive_free(mcpt_progressive* h)
+{
+    if (!h) return;
+    (void)hipSetDevice(h->d->ordinal);
+    (void)hipStreamSynchronize(h->d->stream);
+    for (void* q : {static_cast<void*>(h->pixels), static_cast<void*>(h->img), static_cast<void*>(h->mom), static_cast<void*>(h->hit),
+                    static_cast<void*>(h->partials), static_cast<void*>(h->sums)})
+        if (q) (void)hipFree(q);
+    if (h->h_sums) (void)hipHostFree(h->h_sums);
+    mcpt_device_free(h->d);
+    delete h;
+}
+
+int mcpt_progressive_create(mcpt_device* d, const mcpt_render_params* p, mcpt_progressive** out)
+{
+    if (!out || !p) return fail(MCPT_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (mcpt_device_count() <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (p->spp <= 0) return fail(MCPT_ERR_ARG, "spp must be positive");
+    if (p->flags & (MCPT_RENDER_PIPELINE | MCPT_RENDER_KEEP_STATS))
+        return fail(MCPT_ERR_ARG, "a progressive frame takes neither MCPT_RENDER_PIPELINE nor MCPT_RENDER_KEEP_STATS");
+    int tw, th, rank, world;
+    tile_shape(p, tw, th, rank, world);
+    if (rank < 0 || rank >= world) return fail(MCPT_ERR_ARG, "rank outside world");
+    HIP_TRY(hipSetDevice(d->ordinal));
+    std::vector<int32_t> v;
+    owned_pixel_list(d->width, d->height, tw, th, rank, world, v);
+    const size_t px = size_t(d->width) * d->height;
+    auto* h = new mcpt_progressive;
+    h->d = d; d->refs.fetch_add(1);
+    h->p = *p;
+    h->n_pixels = int64_t(v.size());
+    int rc = upload(v, &h->pixels);
+    hipError_t e = hipSuccess;
+    if (rc == MCPT_OK) {
+        auto alloc = [&](void** q, size_t bytes) { if (e == hipSuccess) e = hipMalloc(q, std::max<size_t>(bytes, 8)); if (e == hipSuccess) e = hipMemset(*q, 0, std::max<size_t>(bytes, 8)); };
+        alloc(reinterpret_cast<void**>(&h->img), px * 3 * sizeof(double));
+        alloc(reinterpret_cast<void**>(&h->mom), px * 6 * sizeof(double));
+        alloc(reinterpret_cast<void**>(&h->hit), px);
+        alloc(reinterpret_cast<void**>(&h->partials), size_t(kNoiseRanges) * 3 * sizeof(double));
+        alloc(reinterpret_cast<void**>(&h->sums), 4 * sizeof(double));
+        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_sums), 4 * sizeof(double), hipHostMallocDefault);
+        if (e != hipSuccess) rc = fail(MCPT_ERR_HIP, std::string("progressive frame buffers: ") + hipGetErrorString(e));
+    }
+    if (rc != MCPT_OK) { mcpt_progressive_free(h); return rc; }
+    *out = h;
+    return MCPT_OK;
+}
+
+int mcpt_progressive_step(mcpt_progressive* h, int32_t n, mcpt_stats* stats)
+{
+    if (!h || n <= 0) return fail(MCPT_ERR_ARG, "bad argument");
+    if (h->done >= h->p.spp) return fail(MCPT_ERR_ARG, "the progressive frame is complete");
+    if (h->broken) return fail(MCPT_ERR_ARG, "an earlier step of this progressive frame failed");
+    mcpt_device* d = h->d;
+    HIP_TRY(hipSetDevice(d->ordinal));
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    mcpt_render_params q = h->p;
+    q.spp = std::min(n, h->p.spp - h->done);
+    const SampleRange r{h->done, q.spp, h->p.spp, h->mom, h->hit};
+    const size_t ev_used0 = d->ev_used;
+    int slot_used = -1;
+    int rc = render_device_impl(d, r, &q, h->img, stats, d->stream, slot_used);
+    const hipError_t e = hipStreamSynchronize(d->stream);
+    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    if (rc != MCPT_OK) { d->ev_used = ev_used0; h->broken = true; return rc; }
+    h->done += q.spp;
+    return MCPT_OK;
+}
+
+int mcpt_progressive_done(const mcpt_progressive* h) { return h ? h->done : fail(MCPT_ERR_ARG, "null handle"); }
+
+int mcpt_progressive_noise(mcpt_progressive* h, mcpt_noise* o)
+{
+    if (!h || !o) return fail(MCPT_ERR_ARG, "null argument");
+    std::memset(o, 0, sizeof *o);
+    o->done = h->done; o->spp = h->p.spp;
+    if (h->done < 2) { o->rel_error = o->abs_rms = INFINITY; return MCPT_OK; }     // no variance estimate from fewer than two samples
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    hipStream_t st = h->d->stream;
+    launch_noise_reduce(h->pixels, h->n_pixels, h->mom, h->hit, h->done, h->partials, h->sums, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h->h_sums, h->sums, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    o->sum_se2 = h->h_sums[0]; o->sum_mean2 = h->h_sums[1]; o->pixels = int64_t(h->h_sums[2]);
+    o->rel_error = o->sum_mean2 > 0 ? std::sqrt(o->sum_se2 / o->sum_mean2) : (o->sum_se2 > 0 ? INFINITY : 0.0);
+    o->abs_rms = o->pixels > 0 ? std::sqrt(o->sum_se2 / (3.0 * double(o->pixels))) : 0.0;
+    return MCPT_OK;
+}
+
+int mcpt_progressive_image_device(mcpt_progressive* h, double* d_img, double* d_stderr, void* stream)
+{
+    if (!h || (!d_img && !d_stderr)) return fail(MCPT_ERR_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    launch_progressive_image(h->pixels, h->n_pixels, h->img, h->mom, h->done, h->p.spp, d_img, d_stderr, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MCPT_OK;
+}
+
+int mcpt_progressive_image(mcpt_progressive* h, double* img, double* stderr_img)
+{
+    if (!h || (!img && !stderr_img)) return fail(MCPT_ERR_ARG, "bad argument");
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    const size_t bytes = size_t(h->d->width) * h->d->height * 3 * sizeof(double);
+    double *d_est = nullptr, *d_err = nullptr;
+    // pageable host buffers: blocking copies either side; pixels this rank does not own keep the caller's values
+    hipError_t e = hipSuccess;
+    if (img) { e = hipMalloc(reinterpret_cast<void**>(&d_est), bytes); if (e == hipSuccess) e = hipMemcpy(d_est, img, bytes, hipMemcpyHostToDevice); }
+    if (e == hipSuccess && stderr_img) { e = hipMalloc(reinterpret_cast<void**>(&d_err), bytes); if (e == hipSuccess) e = hipMemcpy(d_err, stderr_img, bytes, hipMemcpyHostToDevice); }
+    int rc = e == hipSuccess ? mcpt_progressive_image_device(h, d_est, d_err, h->d->stream) : fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    e = hipStreamSynchronize(h->d->stream);
+    if (rc == MCPT_OK && e == hipSuccess && img) e = hipMemcpy(img, d_est, bytes, hipMemcpyDeviceToHost);
+    if (rc == MCPT_OK && e == hipSuccess && stderr_img) e = hipMemcpy(stderr_img, d_err, bytes, hipMemcpyDeviceToHost);
+    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    (void)hipFree(d_est); (void)hipFree(d_err);
+    return rc;
+}
+
+int mcpt_progressive_next_pass(int32_t spp, int32_t done, double remaining_s, double s_per_sample)
+{
+    if (spp <= 0 || done < 0 || done >= spp) return 0;
+    if (done == 0) return std::min(spp, 8);                  // the first pass: no rate measured yet, and a frame needs one pass
+    const int n = std::min(spp - done, done);               // each later pass doubles the samples done
+    if (std::isinf(remaining_s) && remaining_s > 0) return n;     // no time budget
+    if (!(remaining_s > 0)) return 0;                        // the budget is spent
+    if (!(s_per_sample > 0)) return n;                        // no rate to go by
+    const double cap = std::floor(remaining_s / s_per_sample);
+    return cap < 1.0 ? 0 : int(std::min<double>(n, cap));
 }
 
 // ------------------------------------------------------------------------------------------------ output
@@ -1571,6 +1745,52 @@ int mcpt_decode_jpeg(const char* file, int32_t* width, int32_t* height, uint8_t*
 // of it: a caller that sets load_flags, a checkpoint or num_devices through it gets what it asked for, not a silently different
 // render -- so a caller compiled against a 100 / 101 header must hand over a zero-extended struct of that size.  Fields added after
 // 102 are reached through mcpt_render_scene_opts only, which takes the caller's sizeof and reads exactly that many bytes.
+// render_scene's progressive frame: passes of mcpt_progressive_next_pass's schedule until the relative error reaches o.noise_target (checked
+// after every pass), the time budget runs out (measured from the first pass on, the rate of the last pass deciding the next one's size) or
+// every sample is in.  Without a time budget the pass boundaries depend on nothing but N, so the stopping point is reproducible.
+static int render_scene_progressive(mcpt_device* dev, const mcpt_render_params& rp, const mcpt_render_scene_options& o, bool talk, std::vector<double>& img,
+                                    std::vector<double>* err, int& rendered, mcpt_stats& local)
+{
+    using clk = std::chrono::steady_clock;
+    mcpt_progressive* pr = nullptr;
+    int rc = mcpt_progressive_create(dev, &rp, &pr);
+    if (rc) return rc;
+    const auto t0 = clk::now();
+    double rate = 0.0;
+    mcpt_noise nz{};
+    nz.rel_error = INFINITY;
+    bool measured = false;
+    for (;;) {
+        const double remaining = o.time_budget_s > 0 ? o.time_budget_s - std::chrono::duration<double>(clk::now() - t0).count() : INFINITY;
+        const int n = mcpt_progressive_next_pass(rp.spp, pr->done, remaining, rate);
+        if (n <= 0) break;
+        const auto ts = clk::now();
+        mcpt_stats one{};
+        if ((rc = mcpt_progressive_step(pr, n, &one))) break;
+        rate = std::chrono::duration<double>(clk::now() - ts).count() / n;
+        local.rays_primary += one.rays_primary; local.rays_shadow += one.rays_shadow; local.rays_bounce += one.rays_bounce;
+        local.node_visits += one.node_visits; local.tri_tests += one.tri_tests; local.shade_calls += one.shade_calls;
+        local.samples += one.samples; local.shadow_skipped += one.shadow_skipped; local.ms_trace += one.ms_trace;
+        local.ms_total += one.ms_total; local.launches += one.launches;
+        local.max_depth = std::max(local.max_depth, one.max_depth);
+        measured = false;
+        if (o.noise_target > 0) {
+            if ((rc = mcpt_progressive_noise(pr, &nz))) break;
+            measured = true;
+            if (nz.rel_error <= o.noise_target) break;
+        }
+    }
+    if (rc == MCPT_OK && talk && !measured) rc = mcpt_progressive_noise(pr, &nz);
+    if (rc == MCPT_OK) {
+        rendered = pr->done;
+        if (err) err->assign(img.size(), 0.0);
+        rc = mcpt_progressive_image(pr, img.data(), err ? err->data() : nullptr);
+    }
+    if (rc == MCPT_OK && talk) std::printf("progressive: %d of %d samples per pixel, relative error %.4g\n", pr->done, rp.spp, nz.rel_error);
+    mcpt_progressive_free(pr);
+    return rc;
+}
+
 static constexpr int64_t kOptionsBytesV102 = int64_t(offsetof(mcpt_render_scene_options, devices) + sizeof(const int32_t*));
 int mcpt_render_scene_ex(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, mcpt_stats* stats)
 {
@@ -1583,6 +1803,12 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
     mcpt_render_scene_options o{};
     if (opt) std::memcpy(&o, opt, std::min<size_t>(size_t(opt_bytes), sizeof o));
     const bool talk = !o.quiet;
+    // a noise target, a time budget or the error image: the frame goes through a progressive handle (one GPU, no checkpoint)
+    const bool progressive = o.noise_target > 0 || o.time_budget_s > 0 || (o.output_flags & MCPT_OUT_ERROR_PFM);
+    if (o.noise_target < 0 || o.time_budget_s < 0 || std::isnan(o.noise_target) || std::isnan(o.time_budget_s))
+        return fail(MCPT_ERR_ARG, "noise_target and time_budget_s must be >= 0");
+    if (progressive && (o.checkpoint || o.num_devices != 0))
+        return fail(MCPT_ERR_ARG, "a noise target, a time budget or MCPT_OUT_ERROR_PFM renders on one GPU without a checkpoint");
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     mcpt_scene* sc = nullptr;
@@ -1612,7 +1838,11 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
     mcpt_render_params rp{};
     rp.spp = spp; rp.seed = o.seed; rp.world = 1;
     mcpt_stats local{};
-    if (!o.checkpoint) {
+    int rendered = spp;                                  // samples per pixel the written frame holds
+    std::vector<double> err_img;
+    if (progressive) {
+        rc = render_scene_progressive(dev, rp, o, talk, img, (o.output_flags & MCPT_OUT_ERROR_PFM) ? &err_img : nullptr, rendered, local);
+    } else if (!o.checkpoint) {
         rc = many ? mcpt_multi_render(multi, &rp, img.data(), &local) : mcpt_render(dev, &rp, img.data(), &local);
     } else {
         // the frame in `parts` tile partitions, saved after each; partitions a matching checkpoint already holds are skipped
@@ -1647,10 +1877,11 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
         std::vector<uint8_t> rgb(img.size());
         mcpt_quantize_rgb8(img.data(), int64_t(img.size()), rgb.data());
         const std::string prefix = o.output_prefix ? std::string(o.output_prefix) : std::string("../result/") + filename;
-        const std::string stem = prefix + "-SPP" + std::to_string(spp);                 // imshow, MTPC.cpp:17-20
+        const std::string stem = prefix + "-SPP" + std::to_string(rendered);            // imshow, MTPC.cpp:17-20 (a progressive frame stopped early: its own count)
         rc = (o.output_flags & MCPT_OUT_PNG_DEFLATE) ? mcpt_write_png_deflate((stem + ".png").c_str(), rgb.data(), s.width, s.height)
                                                       : mcpt_write_png((stem + ".png").c_str(), rgb.data(), s.width, s.height);
         if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_PFM)) rc = mcpt_write_pfm((stem + ".pfm").c_str(), img.data(), s.width, s.height);
+        if (rc == MCPT_OK && !err_img.empty()) rc = mcpt_write_pfm((stem + ".err.pfm").c_str(), err_img.data(), s.width, s.height);
     }
     if (stats) *stats = local;
     if (dev) mcpt_device_free(dev);

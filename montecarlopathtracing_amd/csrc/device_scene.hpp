@@ -131,7 +131,8 @@ struct DCounters {
                                   // [5..9] lanes that claimed, [10] sleeps, [11] steps that claimed nothing, [12..16] wave cycles per class,
                                   // [17] cycles voting / claiming / sleeping, [18] wave lifetimes, [19] waves
     unsigned long long pad[24];   // diagnostics: [0..11] trace engine (MCPT_TRACE_DIAG builds), [12] rays k_wf_trace handed to the exact walk,
-                                  // [13..15] finishing kernel, [16..19] logic kernel
+                                  // [13..15] finishing kernel, [16..19] logic kernel,
+                                  // [20] pre-test self-check, [21..22] kernarg self-check (MCPT_PRE_CHECK: trace launches whose kernarg WfArgs differ / checked)
 };
 
 }  // namespace mcpt

@@ -177,10 +177,11 @@ __global__ void __launch_bounds__(256) k_primary_hits_reference(DScene S, const 
 }
 
 // One lane per camera sample.  Samples of one pixel are consecutive lanes, so a wave starts from one shared
-// primary hit (coherent first vertex and shadow rays).  Radiance goes to rad[(slot*spp + k)*3].
+// primary hit (coherent first vertex and shadow rays).  Radiance goes to rad[(slot*spp + k)*3]; lane k of a slot renders camera
+// sample sample_base + k (a whole frame: 0).
 __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long long seed, const double* __restrict__ dirs,
                                                        const int32_t* __restrict__ pixels, const PrimaryHit* __restrict__ hits,
-                                                       int first_slot, long long n_samples, int spp, double* __restrict__ rad, DCounters* ctr)
+                                                       int first_slot, long long n_samples, int spp, int sample_base, double* __restrict__ rad, DCounters* ctr)
 {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     LaneStats ls;
@@ -192,7 +193,7 @@ __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long l
         ls.samples = 1;
         double r[3] = {0, 0, 0};
         if (ph.leaf >= 0) {
-            RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix; key.sample = (uint32_t)k;
+            RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix; key.sample = (uint32_t)(sample_base + k);
             Hit h; h.leaf = ph.leaf; h.t = ph.t; h.p = mk(ph.p[0], ph.p[1], ph.p[2]);
             shade_path(S, key, ld3(dirs + (size_t)pix * 3), h, r, ls);
         }
@@ -238,6 +239,110 @@ __global__ void k_fold_samples(const double* __restrict__ rad, const int32_t* __
         for (int k = 0; k < spp; k++) acc = (float)((double)acc + src[(size_t)k * 3] / spp);
     const int pix = pixels ? pixels[slot] : slot;
     img[(size_t)pix * 3 + c] = (double)acc;
+}
+
+// ---- progressive frames (mcpt_progressive_*): samples [k0, k0 + n) of a frame of N per pass
+// The fold of k_fold_samples continued from where the previous pass left it: acc starts from the float the fp64 image holds (exactly a
+// float), so once every pass is in, img is k_fold_samples' frame bit for bit whatever the pass boundaries were.  Beside it the pixel's
+// first and second moments of the radiance, in fp64 in k order: mom[pix][0][c] = sum x, mom[pix][1][c] = sum x*x (no contraction:
+// the library is built with -ffp-contract=off).  hit[pix] records whether the pixel's primary ray hit (k_noise_reduce counts only those).
+// One lane per (slot, channel).
+__global__ void k_fold_progressive(const double* __restrict__ rad, const int32_t* __restrict__ pixels, const PrimaryHit* __restrict__ hits,
+                                   int first_slot, int n_slots, int n, int k0, int N, double* __restrict__ img, double* __restrict__ mom,
+                                   uint8_t* __restrict__ hit)
+{
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)n_slots * 3) return;
+    const int s = (int)(gid / 3), c = (int)(gid % 3);
+    const int slot = first_slot + s;
+    const int pix = pixels ? pixels[slot] : slot;
+    const bool h = hits[slot].leaf >= 0;
+    if (c == 0) hit[pix] = h ? 1 : 0;
+    if (!h) { img[(size_t)pix * 3 + c] = 0.0; return; }    // a primary miss adds nothing (pathTracing.cpp:311); its moments stay 0
+    const double* src = rad + (size_t)s * n * 3 + c;
+    double* m = mom + (size_t)pix * 6 + c;
+    float acc = k0 > 0 ? (float)img[(size_t)pix * 3 + c] : 0.0f;
+    double s1 = k0 > 0 ? m[0] : 0.0, s2 = k0 > 0 ? m[3] : 0.0;
+    for (int k = 0; k < n; k++) {
+        const double x = src[(size_t)k * 3];
+        acc = (float)((double)acc + x / N);
+        s1 += x;
+        s2 += x * x;
+    }
+    img[(size_t)pix * 3 + c] = (double)acc;
+    m[0] = s1; m[3] = s2;
+}
+
+// Squared standard error of the mean of one channel after k samples (k >= 2): the unbiased sample variance over k.  The difference of
+// the moments can come out a rounding below zero for a pixel whose samples are all equal: clamped to 0.
+__device__ __forceinline__ double progressive_se2(double s1, double s2, int k)
+{
+    const double var = (s2 - s1 * s1 / k) / (k - 1);
+    return (var > 0.0 ? var : 0.0) / k;
+}
+
+// Frame summary (k_noise_reduce + k_noise_final): over the owned hit pixels, sum se2 and sum mean^2 of every channel and the pixel count.
+// Deterministic and independent of the device: the pixel list is cut into `ranges` contiguous ranges (a number fixed by the pixel count,
+// not by the grid), block r reduces range r -- thread t takes the range's pixels t, t + 256, ... in order, the waves reduce with a fixed
+// __shfl_xor butterfly, wave 0 adds the four wave sums in order -- and one block adds the ranges' partials the same way.  No atomics.
+__device__ __forceinline__ double wave_sum_fixed(double v)
+{
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+__device__ __forceinline__ void block_sum3(double v[3], double* out)
+{
+    __shared__ double part[4][3];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int i = 0; i < 3; i++) v[i] = wave_sum_fixed(v[i]);
+    if (lane == 0) for (int i = 0; i < 3; i++) part[w][i] = v[i];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int i = 0; i < 3; i++) out[i] = ((part[0][i] + part[1][i]) + part[2][i]) + part[3][i];
+}
+__global__ void __launch_bounds__(256) k_noise_reduce(const int32_t* __restrict__ pixels, long long n_pixels, long long per_range,
+                                                      const double* __restrict__ mom, const uint8_t* __restrict__ hit, int done,
+                                                      double* __restrict__ partials)
+{
+    const long long lo = (long long)blockIdx.x * per_range;
+    const long long hi = lo + per_range < n_pixels ? lo + per_range : n_pixels;
+    double v[3] = {0.0, 0.0, 0.0};
+    for (long long i = lo + threadIdx.x; i < hi; i += 256) {
+        const int pix = pixels ? pixels[i] : (int)i;
+        if (!hit[pix]) continue;
+        const double* m = mom + (size_t)pix * 6;
+        for (int c = 0; c < 3; c++) {
+            const double mean = m[c] / done;
+            v[0] += progressive_se2(m[c], m[3 + c], done);
+            v[1] += mean * mean;
+        }
+        v[2] += 1.0;
+    }
+    block_sum3(v, partials + (size_t)blockIdx.x * 3);
+}
+__global__ void __launch_bounds__(256) k_noise_final(const double* __restrict__ partials, int ranges, double* __restrict__ out)
+{
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int r = threadIdx.x; r < ranges; r += 256)
+        for (int i = 0; i < 3; i++) v[i] += partials[(size_t)r * 3 + i];
+    block_sum3(v, out);
+    if (threadIdx.x == 0) out[3] = 0.0;
+}
+
+// Current estimate and (est_err != null) the standard error of every owned pixel after `done` of N samples.  done == N: the float fold
+// itself (the frame mcpt_render computes); done < N: the fp64 mean s1 / done, which is not the float fold.  Error: sqrt(se2), 0 for
+// done < 2.  One lane per (owned pixel, channel); other pixels are not touched.
+__global__ void k_progressive_image(const int32_t* __restrict__ pixels, long long n_pixels, const double* __restrict__ img,
+                                    const double* __restrict__ mom, int done, int N, double* __restrict__ est, double* __restrict__ est_err)
+{
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= n_pixels * 3) return;
+    const int c = (int)(gid % 3);
+    const int pix = pixels ? pixels[gid / 3] : (int)(gid / 3);
+    const size_t i = (size_t)pix * 3 + c;
+    const double* m = mom + (size_t)pix * 6 + c;
+    if (est) est[i] = done == N ? img[i] : (done > 0 ? m[0] / done : 0.0);
+    if (est_err) est_err[i] = done >= 2 ? sqrt(progressive_se2(m[0], m[3], done)) : 0.0;
 }
 
 // End-of-frame exchange of the multi-GPU entry (multi_device.cpp): a rank's pixels leave its frame as one compact buffer
@@ -337,11 +442,11 @@ void launch_primary_hits(const DScene& S, bool fast, const double* d_dirs, const
     launch_persistent(S, src, n_pixels, queue, slow_list, slow_cap, ctr, st, cfg.primary_grid, cfg.primary_grid_short, cfg);
 }
 void launch_shade_samples(const DScene& S, unsigned long long seed, const double* d_dirs, const int32_t* d_pixels,
-                          const PrimaryHit* d_hits, int first_slot, int n_slots, int spp, double* d_rad, DCounters* ctr, hipStream_t st)
+                          const PrimaryHit* d_hits, int first_slot, int n_slots, int spp, int sample_base, double* d_rad, DCounters* ctr, hipStream_t st)
 {
     const long long n = (long long)n_slots * spp;
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_shade_samples, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, d_rad, ctr);
+    hipLaunchKernelGGL(k_shade_samples, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
 }
 void launch_sample_radiance(const DScene& S, unsigned long long seed, const double* d_dirs, const int32_t* d_pix, const int32_t* d_k,
                             long long n, double* d_rgb, DCounters* ctr, hipStream_t st)
@@ -354,6 +459,29 @@ void launch_fold_samples(const double* d_rad, const int32_t* d_pixels, const Pri
 {
     if (n_slots <= 0) return;
     hipLaunchKernelGGL(k_fold_samples, dim3(blocks_for((long long)n_slots * 3, 256)), dim3(256), 0, st, d_rad, d_pixels, d_hits, first_slot, n_slots, spp, d_img);
+}
+
+void launch_fold_progressive(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int n, int k0, int N,
+                             double* d_img, double* d_mom, uint8_t* d_hit, hipStream_t st)
+{
+    if (n_slots <= 0) return;
+    hipLaunchKernelGGL(k_fold_progressive, dim3(blocks_for((long long)n_slots * 3, 256)), dim3(256), 0, st, d_rad, d_pixels, d_hits, first_slot, n_slots, n, k0, N,
+                       d_img, d_mom, d_hit);
+}
+int noise_ranges(long long n_pixels) { return (int)std::min<long long>(kNoiseRanges, std::max<long long>(1, (n_pixels + 255) / 256)); }
+void launch_noise_reduce(const int32_t* d_pixels, long long n_pixels, const double* d_mom, const uint8_t* d_hit, int done, double* d_partials,
+                         double* d_out, hipStream_t st)
+{
+    const int ranges = noise_ranges(n_pixels);
+    const long long per_range = (n_pixels + ranges - 1) / ranges;
+    hipLaunchKernelGGL(k_noise_reduce, dim3(ranges), dim3(256), 0, st, d_pixels, n_pixels, per_range, d_mom, d_hit, done, d_partials);
+    hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(256), 0, st, d_partials, ranges, d_out);
+}
+void launch_progressive_image(const int32_t* d_pixels, long long n_pixels, const double* d_img, const double* d_mom, int done, int N, double* d_est,
+                              double* d_err, hipStream_t st)
+{
+    if (n_pixels <= 0) return;
+    hipLaunchKernelGGL(k_progressive_image, dim3(blocks_for(n_pixels * 3, 256)), dim3(256), 0, st, d_pixels, n_pixels, d_img, d_mom, done, N, d_est, d_err);
 }
 
 }  // namespace mcpt

@@ -44,10 +44,20 @@ void launch_primary_dirs(const DCamera& cam, double* d_dirs, hipStream_t st);
 void launch_primary_hits(const DScene& S, bool fast, const double* d_dirs, const int32_t* d_pixels, int n_pixels, PrimaryHit* d_hits,
                          DCounters* ctr, TraceQueue* queue, long long* slow_list, unsigned int slow_cap, hipStream_t st, const LaunchCfg& cfg);
 void launch_shade_samples(const DScene& S, unsigned long long seed, const double* d_dirs, const int32_t* d_pixels,
-                          const PrimaryHit* d_hits, int first_slot, int n_slots, int spp, double* d_rad, DCounters* ctr, hipStream_t st);
+                          const PrimaryHit* d_hits, int first_slot, int n_slots, int spp, int sample_base, double* d_rad, DCounters* ctr, hipStream_t st);
 void launch_sample_radiance(const DScene& S, unsigned long long seed, const double* d_dirs, const int32_t* d_pix, const int32_t* d_k,
                             long long n, double* d_rgb, DCounters* ctr, hipStream_t st);
 void launch_fold_samples(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int spp,
                          double* d_img, hipStream_t st);
+// progressive frames: fold of samples [k0, k0 + n) of a frame of N into d_img, moments into d_mom ([W*H][2][3]), primary hit flags into d_hit
+void launch_fold_progressive(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int n, int k0, int N,
+                             double* d_img, double* d_mom, uint8_t* d_hit, hipStream_t st);
+// frame summary after `done` samples (done >= 2): d_out[0..3] = sum se2, sum mean^2, hit pixels, 0; d_partials holds noise_ranges() x 3 doubles
+constexpr int kNoiseRanges = 1024;
+int noise_ranges(long long n_pixels);
+void launch_noise_reduce(const int32_t* d_pixels, long long n_pixels, const double* d_mom, const uint8_t* d_hit, int done, double* d_partials,
+                         double* d_out, hipStream_t st);
+void launch_progressive_image(const int32_t* d_pixels, long long n_pixels, const double* d_img, const double* d_mom, int done, int N, double* d_est,
+                              double* d_err, hipStream_t st);
 
 }  // namespace mcpt

@@ -688,7 +688,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                     RngKey key;
                     key.k0 = (uint32_t)a.seed; key.k1 = (uint32_t)(a.seed >> 32);
                     const int slot = a.first_slot + id / a.spp;
-                    key.pixel = (uint32_t)(a.pixels ? a.pixels[slot] : slot); key.sample = (uint32_t)(id % a.spp);
+                    key.pixel = (uint32_t)(a.pixels ? a.pixels[slot] : slot); key.sample = (uint32_t)(a.sample_base + id % a.spp);
                     int sample_mat = -1;
                     for (int l = 0; l < nl; l++) {
                         V3 direction, cc;

@@ -57,6 +57,22 @@ __device__ __forceinline__ WfArgsKernarg wf_kernarg_args()
     return (WfArgsKernarg)((kbytes)__builtin_amdgcn_kernarg_segment_ptr() + off);
 }
 
+// MCPT_PRE_CHECK builds: the kernarg segment seen through wf_kernarg_args() must hold the launch's own WfArgs.  One lane per launch compares
+// a few fields with the by-value copy and counts the launches checked (DCounters::pad[22]) and those that differ (pad[21], must stay 0) --
+// a counter, not a trap: the frame goes on and the host reports the count.
+__device__ __forceinline__ void wf_kernarg_check(const WfArgs& a)
+{
+#ifdef MCPT_PRE_CHECK
+    if (blockIdx.x == 0 && threadIdx.x == 0 && a.ctr) {
+        const WfArgsKernarg k = wf_kernarg_args();
+        if (k->cap != a.cap || k->spp != a.spp || k->sample_base != a.sample_base) atomicAdd(&a.ctr->pad[21], 1ull);
+        atomicAdd(&a.ctr->pad[22], 1ull);
+    }
+#else
+    (void)a;
+#endif
+}
+
 // persistent fast walk
 __device__ __forceinline__ long long wf_chunk(long long total, int min_chunk, int max_chunk)
 {
@@ -71,6 +87,7 @@ __device__ __forceinline__ long long wf_chunk(long long total, int min_chunk, in
 template <int STACK, int WAVES>
 __global__ void __launch_bounds__(256, WAVES) k_wf_trace(DScene S, WfArgs a, TraceQueue* queue, long long* slow_list, unsigned int slow_cap, int min_chunk, int max_chunk)
 {
+    wf_kernarg_check(a);
     const long long n_paths = a.counts->n_next;
     if (n_paths <= (long long)a.finish_below) return;                  // nothing left, or k_wf_finish has taken the paths
     const long long chunk = wf_chunk(n_paths * (a.nl + 1), min_chunk, max_chunk);
@@ -106,6 +123,7 @@ __global__ void __launch_bounds__(256, WAVES) k_wf_trace(DScene S, WfArgs a, Tra
 template <int NW, int KT, int SCAP>
 __global__ void __launch_bounds__(NW * 64, 1) k_wf_trace_pool(DScene S, WfArgs a, TraceQueue* queue, long long* slow_list, unsigned int slow_cap, int min_chunk, int max_chunk)
 {
+    wf_kernarg_check(a);
     const long long n_paths = a.counts->n_next;
     if (n_paths <= (long long)a.finish_below) return;
     const long long chunk = wf_chunk(n_paths * (a.nl + 1), min_chunk, max_chunk);

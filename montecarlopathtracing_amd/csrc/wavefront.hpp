@@ -97,6 +97,9 @@ struct WfArgs {
     unsigned int finish_below;
     TraceQueue* queue;          // the frame slot's queue words: k_wf_logic clears them for the trace launch that follows it (a fill dispatch per
                                 // iteration, ~13 us with its gap, is a percent of a rank's share of the frame)
+    int sample_base;            // sample index of the pass's first sample: sample k of a slot is camera sample sample_base + k (progressive
+                                // passes render samples [sample_base, sample_base + spp) of a frame; a whole frame passes 0).  Kept last:
+                                // wf_kernarg_args()'s offset of the struct is unchanged by it
 };
 
 size_t wf_bytes_per_path(int nl);

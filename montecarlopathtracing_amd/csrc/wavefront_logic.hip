@@ -70,7 +70,7 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
     key.k0 = (uint32_t)a.seed; key.k1 = (uint32_t)(a.seed >> 32);
     if (FIRST) key.pixel = (uint32_t)pix_first;
     else { const int slot = a.first_slot + id / a.spp; key.pixel = (uint32_t)(a.pixels ? a.pixels[slot] : slot); }
-    key.sample = (uint32_t)(id % a.spp);
+    key.sample = (uint32_t)(a.sample_base + id % a.spp);
 
     {
         V3 nd = mk(0, 0, 0), wgt = mk(1, 1, 1);
@@ -370,7 +370,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
                 if (a.depth > 0) L = ldc(a.out.L, cap, j);
                 p = src.vertex(j);
                 const int slot = a.first_slot + id / a.spp;
-                key.pixel = (uint32_t)(a.pixels ? a.pixels[slot] : slot); key.sample = (uint32_t)(id % a.spp);
+                key.pixel = (uint32_t)(a.pixels ? a.pixels[slot] : slot); key.sample = (uint32_t)(a.sample_base + id % a.spp);
             }
         }
         if (!__ballot(mode != M_IDLE)) {
