@@ -264,6 +264,39 @@ int  mcpt_progressive_image_device(mcpt_progressive*, double* d_img, double* d_s
 int  mcpt_progressive_next_pass(int32_t spp, int32_t done, double remaining_s, double s_per_sample);
 void mcpt_progressive_free(mcpt_progressive*);
 
+/* ---- adaptive frames (since the adaptive-sampling change): a progressive frame whose pixels stop on their own error estimate ---- */
+/* mcpt_progressive_create_adaptive makes a progressive handle (step / done / noise / image / free as above) that keeps an active pixel
+ * list, initially the owned list.  step(n) renders samples [done, min(done + n, N)) of the active pixels only, then decides on the GPU,
+ * from each pixel's own moments, which of them continue; the list stays in ascending pixel order.  With k = done after the step, pixel p
+ * stops when
+ *     its primary ray missed (its value is +0.0 for any sample count), or
+ *     k >= min_spp  and  se2 < rel2 * m2 + abs2,   where, in fp64 without contraction,
+ *         rel2 = rel_target * rel_target,  abs2 = abs_target * abs_target,
+ *         se2 = ((se2_0 + se2_1) + se2_2),  m2 = ((m_0 * m_0 + m_1 * m_1) + m_2 * m_2),
+ *         m_c = s1_c / k,  se2_c = v_c / k with v_c = max((s2_c - s1_c * s1_c / k) / (k - 1), 0)   (the squared standard error above).
+ * Pixels only ever leave the list, so all active pixels share the count `done` and a pixel that stopped at k holds exactly the uniform
+ * frame's samples [0, k): its estimate and error are those of a uniform handle at done == k, bit for bit, and a pixel that reaches N
+ * holds the one-shot frame's value.  With rel_target = abs_target = 0 only misses stop, and the frame is mcpt_render's bit for bit.
+ * Stopping on the pixel's own variance estimate biases the estimate slightly (a pixel whose first samples happen to agree stops early);
+ * targets of 0 remove the bias.  noise and image use every pixel's own count n_p: the estimate is the float fold at n_p == N, else
+ * s1 / n_p; the error sqrt(se2(n_p)); noise sums over the owned hit pixels as above, each with its own n_p (done reports the last pass
+ * boundary).  min_spp must be >= 2 (a value above N is taken as N), the targets finite and >= 0; MCPT_RENDER_PIPELINE and
+ * MCPT_RENDER_KEEP_STATS are refused.  A step once the active list is empty, or at done == N, returns MCPT_ERR_ARG.
+ *   active         : the pixels the next step renders; 0 when the frame is complete (an empty list, or done == N).
+ *   active_pixels  : writes those pixels, ascending, to `pixels` (may be NULL) and returns their number (< 0: MCPT_ERR_*).
+ *   sample_counts  : W*H int32: the samples each owned pixel holds (other entries are left as they are).
+ * On a uniform handle (mcpt_progressive_create) active is the owned count until done == N, active_pixels the owned list, and every owned
+ * pixel's count is done. */
+typedef struct {
+    double  rel_target, abs_target;
+    int32_t min_spp;
+    int32_t reserved;
+} mcpt_adaptive_params;
+int     mcpt_progressive_create_adaptive(mcpt_device*, const mcpt_render_params*, const mcpt_adaptive_params*, mcpt_progressive** out);
+int64_t mcpt_progressive_active(const mcpt_progressive*);
+int64_t mcpt_progressive_active_pixels(mcpt_progressive*, int32_t* pixels);
+int     mcpt_progressive_sample_counts(mcpt_progressive*, int32_t* counts);
+
 /* ---- integrator over several GPUs of one node (no reference counterpart: generateImg is single-process OpenMP) ---- */
 /* The frame is cut into tiles dealt to the GPUs exactly as mcpt_render_params.rank/world describe (rank r = devices[r]); the scene
  * is resident on every GPU; one host thread per GPU renders its tiles; at the end of the frame every rank's pixels travel as one
@@ -334,6 +367,7 @@ int  mcpt_render_scene(const char* path, const char* filename, int32_t spp);
 #define MCPT_OUT_PNG_DEFLATE  1      /* the .png is deflate-compressed (same pixels; the reference's svpng stores them raw) */
 #define MCPT_OUT_PFM          2      /* also write <prefix>-SPP<N>.pfm: the linear fp32 radiance before imshow's clamp */
 #define MCPT_OUT_ERROR_PFM    4      /* also write <prefix>-SPP<N>.err.pfm: the per-pixel standard error (mcpt_progressive_image) as fp32 */
+#define MCPT_OUT_SPP_PFM      8      /* also write <prefix>-SPP<N>.spp.pfm: the samples each pixel holds (mcpt_progressive_sample_counts) */
 typedef struct {
     uint64_t seed;
     int32_t  device;            /* HIP ordinal */
@@ -358,6 +392,15 @@ typedef struct {
      * the plain call's frame, byte for byte.  With a checkpoint or num_devices != 0 these return MCPT_ERR_ARG. */
     double   noise_target;      /* 0 = none */
     double   time_budget_s;     /* 0 = none */
+    /* since the adaptive-sampling change (mcpt_render_scene_opts only).  adaptive_min_spp > 0: an adaptive frame
+     * (mcpt_progressive_create_adaptive with rel_target = noise_target, abs_target, min_spp = adaptive_min_spp).  Its first pass is
+     * min(N, adaptive_min_spp) samples, later ones follow mcpt_progressive_next_pass's doubling; it stops when no pixel is active, at N, or
+     * on the time budget -- the seconds per sample of the last pass scaled by (next active count / last active count); the fixed cost of a
+     * pass is not modelled.  The PNG is named after the largest count any pixel reached.  With a checkpoint or num_devices != 0:
+     * MCPT_ERR_ARG. */
+    int32_t  adaptive_min_spp;  /* 0 = off */
+    int32_t  reserved2;
+    double   abs_target;        /* adaptive frames: the absolute term of the stopping rule */
 } mcpt_render_scene_options;
 /* The struct has grown with MCPT_VERSION and carries no size field.  mcpt_render_scene_ex -- the only entry point through version
  * 102 -- reads the struct as it stood at 102, i.e. every field above: what a caller sets through it (load_flags, checkpoint,

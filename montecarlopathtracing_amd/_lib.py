@@ -62,7 +62,13 @@ class RenderSceneOptions(C.Structure):
                 ("load_flags", C.c_int32), ("output_flags", C.c_int32), ("checkpoint", C.c_char_p),
                 ("checkpoint_parts", C.c_int32), ("reserved", C.c_int32),
                 ("num_devices", C.c_int32), ("gather", C.c_int32), ("devices", C.POINTER(C.c_int32)),
-                ("noise_target", C.c_double), ("time_budget_s", C.c_double)]
+                ("noise_target", C.c_double), ("time_budget_s", C.c_double),
+                ("adaptive_min_spp", C.c_int32), ("reserved2", C.c_int32), ("abs_target", C.c_double)]
+
+
+class AdaptiveParams(C.Structure):
+    """mcpt_adaptive_params: the per-pixel stopping rule of an adaptive frame (mcpt_progressive_create_adaptive)"""
+    _fields_ = [("rel_target", C.c_double), ("abs_target", C.c_double), ("min_spp", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Noise(C.Structure):
@@ -89,6 +95,7 @@ EXPORTS = [
     "mcpt_checkpoint_save", "mcpt_checkpoint_load", "mcpt_decode_jpeg",
     "mcpt_progressive_create", "mcpt_progressive_step", "mcpt_progressive_done", "mcpt_progressive_noise", "mcpt_progressive_image",
     "mcpt_progressive_image_device", "mcpt_progressive_next_pass", "mcpt_progressive_free",
+    "mcpt_progressive_create_adaptive", "mcpt_progressive_active", "mcpt_progressive_active_pixels", "mcpt_progressive_sample_counts",
     "mcpt_multi_create", "mcpt_multi_num_devices", "mcpt_multi_render", "mcpt_multi_render_device", "mcpt_multi_last_timing", "mcpt_multi_collect_stats", "mcpt_multi_free",
     "mcpt_comm_unique_id", "mcpt_comm_create", "mcpt_comm_size", "mcpt_comm_gather_frame", "mcpt_comm_allreduce", "mcpt_comm_free",
     "mcpt_render_scene", "mcpt_render_scene_ex", "mcpt_render_scene_opts",
@@ -174,6 +181,12 @@ def lib():
     L.mcpt_progressive_next_pass.argtypes = [C.c_int32, C.c_int32, C.c_double, C.c_double]
     L.mcpt_progressive_free.argtypes = [P]
     L.mcpt_progressive_free.restype = None
+    L.mcpt_progressive_create_adaptive.argtypes = [P, C.POINTER(RenderParams), C.POINTER(AdaptiveParams), C.POINTER(P)]
+    L.mcpt_progressive_active.argtypes = [P]
+    L.mcpt_progressive_active.restype = C.c_int64
+    L.mcpt_progressive_active_pixels.argtypes = [P, I32]
+    L.mcpt_progressive_active_pixels.restype = C.c_int64
+    L.mcpt_progressive_sample_counts.argtypes = [P, I32]
     L.mcpt_multi_create.argtypes = [P, I32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(P)]
     L.mcpt_multi_num_devices.argtypes = [P]
     L.mcpt_multi_render.argtypes = [P, C.POINTER(RenderParams), D, C.POINTER(Stats)]

@@ -5,14 +5,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
+from ._lib import AdaptiveParams, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
 RENDER_DEFAULT, RENDER_MEGAKERNEL = 0, 2
 RENDER_KEEP_STATS, RENDER_PIPELINE = 4, 8
 LOAD_STANDARD_OBJ, LOAD_MTLLIB, LOAD_MORTON_BOUNDS = 1, 2, 4
-OUT_PNG_DEFLATE, OUT_PFM, OUT_ERROR_PFM = 1, 2, 4
+OUT_PNG_DEFLATE, OUT_PFM, OUT_ERROR_PFM, OUT_SPP_PFM = 1, 2, 4, 8
 BUILD_HOST, BUILD_DEVICE, BUILD_DEVICE_FAST, BUILD_DEVICE_SAH = 0, 1, 2, 3
 SCENE_DEFER_BUILD = 1
 GATHER_PEER, GATHER_RCCL = 0, 1
@@ -285,16 +285,25 @@ class Device:
         """A frame of `spp` samples per pixel rendered in passes (mcpt_progressive_*): see Progressive."""
         return Progressive(self, spp, seed, rank, world, tile_w, tile_h, flags)
 
+    def adaptive(self, spp, rel_target, abs_target=0.0, min_spp=16, seed=0, rank=0, world=1, tile_w=0, tile_h=0, flags=0):
+        """An adaptive frame (mcpt_progressive_create_adaptive): a Progressive whose pixels stop on their own error estimate."""
+        return Progressive(self, spp, seed, rank, world, tile_w, tile_h, flags, adaptive=AdaptiveParams(rel_target, abs_target, min_spp, 0))
+
 
 class Progressive:
     """A progressive frame on a Device.  step(n) renders the next n samples of every owned pixel; at done == spp, image() is generateImg's
-    frame bit for bit.  Before that, image() is the fp64 mean of the samples done (not the float fold) and stderr() its standard error."""
+    frame bit for bit.  Before that, image() is the fp64 mean of the samples done (not the float fold) and stderr() its standard error.
+    An adaptive frame (Device.adaptive) renders only the active pixels; image() and stderr() then use every pixel's own count
+    (sample_counts())."""
 
-    def __init__(self, device, spp, seed=0, rank=0, world=1, tile_w=0, tile_h=0, flags=0):
+    def __init__(self, device, spp, seed=0, rank=0, world=1, tile_w=0, tile_h=0, flags=0, adaptive=None):
         self.device, self.spp = device, spp
         self._h = C.c_void_p()
         rp = RenderParams(spp, seed, rank, world, tile_w, tile_h, flags)
-        check(lib().mcpt_progressive_create(device._h, C.byref(rp), C.byref(self._h)))
+        if adaptive is None:
+            check(lib().mcpt_progressive_create(device._h, C.byref(rp), C.byref(self._h)))
+        else:
+            check(lib().mcpt_progressive_create_adaptive(device._h, C.byref(rp), C.byref(adaptive), C.byref(self._h)))
 
     def step(self, n, stats=None):
         check(lib().mcpt_progressive_step(self._h, n, C.byref(stats) if stats is not None else None))
@@ -306,6 +315,29 @@ class Progressive:
         if rc < 0:
             check(rc)
         return rc
+
+    @property
+    def active(self):
+        """pixels the next step renders (0: the frame is complete)"""
+        n = lib().mcpt_progressive_active(self._h)
+        if n < 0:
+            check(n)
+        return n
+
+    def active_pixels(self):
+        """the active pixel list, ascending, as int32"""
+        out = np.zeros(self.active, dtype=np.int32)
+        n = lib().mcpt_progressive_active_pixels(self._h, _p(out, C.c_int32))
+        if n < 0:
+            check(n)
+        return out[:n]
+
+    def sample_counts(self, counts=None):
+        """the samples every owned pixel holds, as [H,W] int32 (pixels not owned: left as in counts, else 0)"""
+        if counts is None:
+            counts = np.zeros((self.device.height, self.device.width), dtype=np.int32)
+        check(lib().mcpt_progressive_sample_counts(self._h, _p(counts, C.c_int32)))
+        return counts
 
     def noise(self):
         """Noise: rel_error, abs_rms, sum_se2, sum_mean2, pixels (owned hit pixels), done, spp"""
@@ -479,10 +511,11 @@ def morton_code(x, y, z):
 
 def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, height=0, quiet=True, output_prefix=None, stats=None,
                  load_flags=0, output_flags=0, checkpoint=None, checkpoint_parts=0, devices=None, gather=GATHER_PEER, noise_target=0.0,
-                 time_budget_s=0.0):
+                 time_budget_s=0.0, adaptive_min_spp=0, abs_target=0.0):
     """render_scene(path, filename, N) of MTPC/MTPC.cpp:35; writes <prefix>-SPP<N>.png (default ../result/<filename>).
     devices: list of GPU ordinals, or -1 for every visible GPU (the frame is then rendered by mcpt_multi_*).
-    noise_target / time_budget_s / OUT_ERROR_PFM: a progressive frame that may stop at k < N samples (<prefix>-SPP<k>.png)."""
+    noise_target / time_budget_s / OUT_ERROR_PFM: a progressive frame that may stop at k < N samples (<prefix>-SPP<k>.png).
+    adaptive_min_spp > 0: an adaptive frame, noise_target and abs_target its per-pixel targets (OUT_SPP_PFM: the sample-count map)."""
     dev_arr, ndev = None, 0
     if devices == -1:
         ndev = -1
@@ -491,7 +524,7 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
         dev_arr, ndev = _p(keep, C.c_int32), keep.shape[0]
     o = RenderSceneOptions(seed, device, width, height, int(quiet), output_prefix.encode() if output_prefix else None,
                            load_flags, output_flags, checkpoint.encode() if checkpoint else None, checkpoint_parts, 0,
-                           ndev, gather, dev_arr, noise_target, time_budget_s)
+                           ndev, gather, dev_arr, noise_target, time_budget_s, adaptive_min_spp, 0, abs_target)
     check(lib().mcpt_render_scene_opts(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o),
                                        C.byref(stats) if stats is not None else None))
     return True

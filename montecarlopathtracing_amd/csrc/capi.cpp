@@ -1117,18 +1117,25 @@ struct SampleRange {
     uint8_t* hit;
 };
 
-static void fold_range(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, int first, int n_slots, double* d_img, hipStream_t st)
+// The pixels a render call covers, on the device: the partition's owned list (mcpt_render*, uniform progressive passes) or an adaptive
+// frame's active list.  Slot s of the call renders pixel pixels[s].
+struct PixelList {
+    const int32_t* pixels;
+    int64_t n;
+};
+
+static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, int first, int n_slots, double* d_img, hipStream_t st)
 {
-    if (r.mom) launch_fold_progressive(f.rad, d->pixels, f.hits, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, st);
-    else launch_fold_samples(f.rad, d->pixels, f.hits, first, n_slots, r.n, d_img, st);
+    if (r.mom) launch_fold_progressive(f.rad, L.pixels, f.hits, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, st);
+    else launch_fold_samples(f.rad, L.pixels, f.hits, first, n_slots, r.n, d_img, st);
 }
 
 // megakernel path: one lane per camera sample, the whole path in one kernel (kept for A/B runs and as a second
 // implementation the wavefront path is checked against)
-static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, const mcpt_render_params* p, double* d_img, bool timed,
-                             hipStream_t st, double& ms_trace, int& launches)
+static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, const mcpt_render_params* p,
+                             double* d_img, bool timed, hipStream_t st, double& ms_trace, int& launches)
 {
-    const int64_t npx = d->n_pixels;
+    const int64_t npx = L.n;
     const int spp = r.n;
     const size_t per_pixel = size_t(spp) * 3 * sizeof(double);
     int64_t chunk = int64_t(std::max<size_t>(d->sample_budget_bytes / per_pixel, 64));
@@ -1142,7 +1149,7 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const Sa
     for (int64_t first = 0; first < npx; first += chunk) {
         const int n_slots = int(std::min<int64_t>(chunk, npx - first));
         if (timed) HIP_TRY(hipEventRecord(d->ev[2], st));
-        launch_shade_samples(d->ds, p->seed, d->dirs, d->pixels, f.hits, int(first), n_slots, spp, r.k0, f.rad, f.ctr, st);
+        launch_shade_samples(d->ds, p->seed, d->dirs, L.pixels, f.hits, int(first), n_slots, spp, r.k0, f.rad, f.ctr, st);
         HIP_TRY(hipGetLastError());
         if (timed) {
             HIP_TRY(hipEventRecord(d->ev[3], st));
@@ -1152,7 +1159,7 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const Sa
             ms_trace += ms;
         }
         launches++;
-        fold_range(d, f, r, int(first), n_slots, d_img, st);
+        fold_range(f, r, L, int(first), n_slots, d_img, st);
         HIP_TRY(hipGetLastError());
     }
     return MCPT_OK;
@@ -1161,10 +1168,10 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const Sa
 // wavefront path (wavefront.hpp): per chunk, lockstep iterations of logic + trace over compacted path state in HBM.
 // timed: event pairs around the trace launches, summed here (one stream synchronisation at the end); keep: the pairs are recorded
 // and left in d->ev_pool for mcpt_device_collect_stats -- the frame ends without the host waiting for it.
-static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, const mcpt_render_params* p, double* d_img, bool timed,
-                            bool keep, hipStream_t st, double& ms_trace, int& launches)
+static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, const mcpt_render_params* p,
+                            double* d_img, bool timed, bool keep, hipStream_t st, double& ms_trace, int& launches)
 {
-    const int64_t npx = d->n_pixels;
+    const int64_t npx = L.n;
     const int spp = r.n;
     const int nl = d->ds.num_lights;
     const bool fast = d->trace_mode == MCPT_TRACE_FAST;
@@ -1212,7 +1219,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
     WfArgs a{};
     WfState A, B;
     if (!wf_carve(f.wf_ws, f.wf_ws_bytes, cap, nl, A, B, a.rays)) return fail(MCPT_ERR_NOMEM, "wavefront workspace too small");
-    a.cap = cap; a.nl = nl; a.spp = spp; a.sample_base = r.k0; a.seed = p->seed; a.pixels = d->pixels; a.hit_slots = f.hit_slots; a.surf = f.surf; a.alive_base = f.alive_base; a.hits = f.hits;
+    a.cap = cap; a.nl = nl; a.spp = spp; a.sample_base = r.k0; a.seed = p->seed; a.pixels = L.pixels; a.hit_slots = f.hit_slots; a.surf = f.surf; a.alive_base = f.alive_base; a.hits = f.hits;
     a.dirs = d->dirs; a.rad = f.rad; a.counts = f.wf_counts; a.ctr = f.ctr; a.tris = d->tris; a.materials = d->materials; a.queue = fast ? f.queue : nullptr;
     a.finish_below = fast ? unsigned(std::min<long long>(std::max<long long>(d->finish_threshold, 0), 1ll << 30)) : 0u;
     // Iterations are enqueued without waiting for their counts: every kernel reads its input count from the device slot the
@@ -1287,7 +1294,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
             launch_wf_logic(d->ds, a, n_upper, false, st, d->cfg);
             HIP_TRY(hipGetLastError());
         }
-        fold_range(d, f, r, int(first), n_slots, d_img, st);
+        fold_range(f, r, L, int(first), n_slots, d_img, st);
         HIP_TRY(hipGetLastError());
     }
     if (timed && !keep) {
@@ -1302,8 +1309,8 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
     return MCPT_OK;
 }
 
-static int render_device_impl(mcpt_device* d, const SampleRange& r, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, hipStream_t st,
-                              int& slot_used);
+static int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelList& L, const mcpt_render_params* p, double* d_img, mcpt_stats* stats,
+                              hipStream_t st, int& slot_used);
 
 int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, void* stream)
 {
@@ -1314,7 +1321,8 @@ int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_im
     const size_t ev_used0 = d->ev_used, frame_ev_used0 = d->frame_ev_used;
     int slot_used = -1;
     const SampleRange whole{0, p->spp, p->spp, nullptr, nullptr};
-    const int rc = render_device_impl(d, whole, p, d_img, stats, static_cast<hipStream_t>(stream), slot_used);
+    int rc = prepare_partition(d, p, static_cast<hipStream_t>(stream));
+    if (rc == MCPT_OK) rc = render_device_impl(d, whole, PixelList{d->pixels, d->n_pixels}, p, d_img, stats, static_cast<hipStream_t>(stream), slot_used);
     if (rc != MCPT_OK) {
         d->ev_used = ev_used0; d->frame_ev_used = frame_ev_used0;
         if (slot_used >= 0) d->slot[slot_used].keeping = false;      // its counters hold part of a frame: cleared by the next one
@@ -1322,8 +1330,8 @@ int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_im
     return rc;
 }
 
-static int render_device_impl(mcpt_device* d, const SampleRange& r, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, hipStream_t st,
-                              int& slot_used)
+static int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelList& L, const mcpt_render_params* p, double* d_img, mcpt_stats* stats,
+                              hipStream_t st, int& slot_used)
 {
     const bool keep = (p->flags & MCPT_RENDER_KEEP_STATS) != 0 && !(p->flags & MCPT_RENDER_MEGAKERNEL);
     const bool timed = stats != nullptr && !keep;
@@ -1339,9 +1347,7 @@ static int render_device_impl(mcpt_device* d, const SampleRange& r, const mcpt_r
     if (f.used) HIP_TRY(hipStreamWaitEvent(st, f.done, 0));
     int rc = ensure_dirs(d, st);
     if (rc) return rc;
-    rc = prepare_partition(d, p, st);
-    if (rc) return rc;
-    const int64_t npx = d->n_pixels;
+    const int64_t npx = L.n;
     if (npx == 0) return MCPT_OK;
     if ((rc = grow(&f.hits, &f.hits_cap, npx))) return rc;
     if (!keep || !f.keeping) HIP_TRY(hipMemsetAsync(f.ctr, 0, sizeof(DCounters), st));    // kept statistics accumulate until they are collected
@@ -1357,12 +1363,12 @@ static int render_device_impl(mcpt_device* d, const SampleRange& r, const mcpt_r
         fe = &d->frame_ev[d->frame_ev_used++];
         HIP_TRY(hipEventRecord(fe->first, st));
     } else HIP_TRY(hipEventRecord(d->ev[0], st));
-    launch_primary_hits(d->ds, d->trace_mode == MCPT_TRACE_FAST, d->dirs, d->pixels, int(npx), f.hits, f.ctr, f.queue, f.slow_list, d->slow_cap, st, d->cfg);
+    launch_primary_hits(d->ds, d->trace_mode == MCPT_TRACE_FAST, d->dirs, L.pixels, int(npx), f.hits, f.ctr, f.queue, f.slow_list, d->slow_cap, st, d->cfg);
     HIP_TRY(hipGetLastError());
     double ms_trace = 0;
     int launches = 0;
-    if (p->flags & MCPT_RENDER_MEGAKERNEL) rc = render_megakernel(d, f, r, p, d_img, timed, st, ms_trace, launches);
-    else rc = render_wavefront(d, f, r, p, d_img, timed, keep, st, ms_trace, launches);
+    if (p->flags & MCPT_RENDER_MEGAKERNEL) rc = render_megakernel(d, f, r, L, p, d_img, timed, st, ms_trace, launches);
+    else rc = render_wavefront(d, f, r, L, p, d_img, timed, keep, st, ms_trace, launches);
     if (rc) return rc;
     if (keep) {
         HIP_TRY(hipEventRecord(fe->second, st));
@@ -1485,6 +1491,20 @@ struct mcpt_progressive {
     double* partials = nullptr;        // noise_ranges() x 3
     double* sums = nullptr;            // 4 doubles: sum se2, sum mean^2, hit pixels, 0
     double* h_sums = nullptr;          // pinned copy of sums (the pass's one 32-byte read-back)
+    std::vector<int32_t> owned;        // host copy of `pixels`
+    // adaptive frames (mcpt_progressive_create_adaptive): the active list, double-buffered -- a pass renders active[cur][0..n_active) and
+    // the selection writes the pixels that continue to active[cur ^ 1]
+    bool adaptive = false;
+    double rel2 = 0.0, abs2 = 0.0;     // rel_target^2, abs_target^2
+    int min_spp = 0;
+    int32_t* active[2] = {nullptr, nullptr};
+    int cur = 0;
+    int64_t n_active = 0;
+    int32_t* cnt = nullptr;            // W*H: the samples each pixel holds (written for the listed pixels after every pass)
+    unsigned long long* masks = nullptr;                 // 4 * adaptive_blocks(n_pixels): the keep ballots of the selection
+    int32_t* block_counts = nullptr; int32_t* block_offsets = nullptr;   // adaptive_blocks(n_pixels) each
+    int32_t* total = nullptr;          // the next list's length
+    int32_t* h_total = nullptr;        // pinned copy of total (the pass's 4-byte read-back)
 };
 
 void mcpt_progressive_free(mcpt_progressive* h)
@@ -1493,20 +1513,19 @@ void mcpt_progressive_free(mcpt_progressive* h)
     (void)hipSetDevice(h->d->ordinal);
     (void)hipStreamSynchronize(h->d->stream);
     for (void* q : {static_cast<void*>(h->pixels), static_cast<void*>(h->img), static_cast<void*>(h->mom), static_cast<void*>(h->hit),
-                    static_cast<void*>(h->partials), static_cast<void*>(h->sums)})
+                    static_cast<void*>(h->partials), static_cast<void*>(h->sums), static_cast<void*>(h->active[0]), static_cast<void*>(h->active[1]),
+                    static_cast<void*>(h->cnt), static_cast<void*>(h->masks), static_cast<void*>(h->block_counts),
+                    static_cast<void*>(h->block_offsets), static_cast<void*>(h->total)})
         if (q) (void)hipFree(q);
     if (h->h_sums) (void)hipHostFree(h->h_sums);
+    if (h->h_total) (void)hipHostFree(h->h_total);
     mcpt_device_free(h->d);
     delete h;
 }
 
-int mcpt_progressive_create(mcpt_device* d, const mcpt_render_params* p, mcpt_progressive** out)
+// ap == null: a uniform frame; otherwise an adaptive one (arguments checked by the caller)
+static int progressive_create(mcpt_device* d, const mcpt_render_params* p, const mcpt_adaptive_params* ap, mcpt_progressive** out)
 {
-    if (!out || !p) return fail(MCPT_ERR_ARG, "null argument");
-    *out = nullptr;
-    if (mcpt_device_count() <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
-    if (p->spp <= 0) return fail(MCPT_ERR_ARG, "spp must be positive");
     if (p->flags & (MCPT_RENDER_PIPELINE | MCPT_RENDER_KEEP_STATS))
         return fail(MCPT_ERR_ARG, "a progressive frame takes neither MCPT_RENDER_PIPELINE nor MCPT_RENDER_KEEP_STATS");
     int tw, th, rank, world;
@@ -1530,11 +1549,52 @@ int mcpt_progressive_create(mcpt_device* d, const mcpt_render_params* p, mcpt_pr
         alloc(reinterpret_cast<void**>(&h->partials), size_t(kNoiseRanges) * 3 * sizeof(double));
         alloc(reinterpret_cast<void**>(&h->sums), 4 * sizeof(double));
         if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_sums), 4 * sizeof(double), hipHostMallocDefault);
+        if (ap) {
+            const size_t blocks = size_t(adaptive_blocks(int(v.size())));
+            alloc(reinterpret_cast<void**>(&h->active[0]), v.size() * sizeof(int32_t));
+            alloc(reinterpret_cast<void**>(&h->active[1]), v.size() * sizeof(int32_t));
+            alloc(reinterpret_cast<void**>(&h->cnt), px * sizeof(int32_t));
+            alloc(reinterpret_cast<void**>(&h->masks), blocks * 4 * sizeof(unsigned long long));
+            alloc(reinterpret_cast<void**>(&h->block_counts), blocks * sizeof(int32_t));
+            alloc(reinterpret_cast<void**>(&h->block_offsets), blocks * sizeof(int32_t));
+            alloc(reinterpret_cast<void**>(&h->total), sizeof(int32_t));
+            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_total), sizeof(int32_t), hipHostMallocDefault);
+            if (e == hipSuccess && !v.empty()) e = hipMemcpy(h->active[0], h->pixels, v.size() * sizeof(int32_t), hipMemcpyDeviceToDevice);
+            h->adaptive = true;
+            h->rel2 = ap->rel_target * ap->rel_target;
+            h->abs2 = ap->abs_target * ap->abs_target;
+            h->min_spp = std::min(ap->min_spp, p->spp);
+            h->n_active = h->n_pixels;
+        }
         if (e != hipSuccess) rc = fail(MCPT_ERR_HIP, std::string("progressive frame buffers: ") + hipGetErrorString(e));
     }
     if (rc != MCPT_OK) { mcpt_progressive_free(h); return rc; }
+    h->owned = std::move(v);
     *out = h;
     return MCPT_OK;
+}
+
+int mcpt_progressive_create(mcpt_device* d, const mcpt_render_params* p, mcpt_progressive** out)
+{
+    if (!out || !p) return fail(MCPT_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (mcpt_device_count() <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (p->spp <= 0) return fail(MCPT_ERR_ARG, "spp must be positive");
+    return progressive_create(d, p, nullptr, out);
+}
+
+int mcpt_progressive_create_adaptive(mcpt_device* d, const mcpt_render_params* p, const mcpt_adaptive_params* ap, mcpt_progressive** out)
+{
+    if (!out || !p || !ap) return fail(MCPT_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!(std::isfinite(ap->rel_target) && ap->rel_target >= 0.0 && std::isfinite(ap->abs_target) && ap->abs_target >= 0.0))
+        return fail(MCPT_ERR_ARG, "rel_target and abs_target must be finite and >= 0");
+    if (ap->min_spp < 2) return fail(MCPT_ERR_ARG, "min_spp must be >= 2 (a standard error needs two samples)");
+    if (p->spp <= 0) return fail(MCPT_ERR_ARG, "spp must be positive");
+    if (mcpt_device_count() <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    return progressive_create(d, p, ap, out);
 }
 
 int mcpt_progressive_step(mcpt_progressive* h, int32_t n, mcpt_stats* stats)
@@ -1542,19 +1602,61 @@ int mcpt_progressive_step(mcpt_progressive* h, int32_t n, mcpt_stats* stats)
     if (!h || n <= 0) return fail(MCPT_ERR_ARG, "bad argument");
     if (h->done >= h->p.spp) return fail(MCPT_ERR_ARG, "the progressive frame is complete");
     if (h->broken) return fail(MCPT_ERR_ARG, "an earlier step of this progressive frame failed");
+    if (h->adaptive && h->n_active == 0) return fail(MCPT_ERR_ARG, "the adaptive frame is complete: no pixel is active");
     mcpt_device* d = h->d;
     HIP_TRY(hipSetDevice(d->ordinal));
     if (stats) std::memset(stats, 0, sizeof *stats);
     mcpt_render_params q = h->p;
     q.spp = std::min(n, h->p.spp - h->done);
     const SampleRange r{h->done, q.spp, h->p.spp, h->mom, h->hit};
+    const PixelList L = h->adaptive ? PixelList{h->active[h->cur], h->n_active} : PixelList{h->pixels, h->n_pixels};
     const size_t ev_used0 = d->ev_used;
     int slot_used = -1;
-    int rc = render_device_impl(d, r, &q, h->img, stats, d->stream, slot_used);
+    int rc = render_device_impl(d, r, L, &q, h->img, stats, d->stream, slot_used);
+    if (rc == MCPT_OK && h->adaptive) {
+        // which pixels continue: decided on the device; the host reads back the new list's length only
+        launch_adaptive_select(L.pixels, int(L.n), h->mom, h->hit, h->done + q.spp, h->min_spp, h->rel2, h->abs2, h->cnt, h->masks,
+                               h->block_counts, h->block_offsets, h->total, h->active[h->cur ^ 1], d->stream);
+        hipError_t le = hipGetLastError();
+        if (le == hipSuccess) le = hipMemcpyAsync(h->h_total, h->total, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream);
+        if (le != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(le));
+    }
     const hipError_t e = hipStreamSynchronize(d->stream);
     if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
     if (rc != MCPT_OK) { d->ev_used = ev_used0; h->broken = true; return rc; }
     h->done += q.spp;
+    if (h->adaptive) { h->n_active = *h->h_total; h->cur ^= 1; }
+    return MCPT_OK;
+}
+
+int64_t mcpt_progressive_active(const mcpt_progressive* h)
+{
+    if (!h) return fail(MCPT_ERR_ARG, "null handle");
+    if (h->done >= h->p.spp) return 0;
+    return h->adaptive ? h->n_active : h->n_pixels;
+}
+
+int64_t mcpt_progressive_active_pixels(mcpt_progressive* h, int32_t* pixels)
+{
+    const int64_t n = mcpt_progressive_active(h);
+    if (n <= 0 || !pixels) return n;
+    if (!h->adaptive) { std::memcpy(pixels, h->owned.data(), size_t(n) * sizeof(int32_t)); return n; }
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    HIP_TRY(hipMemcpy(pixels, h->active[h->cur], size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return n;
+}
+
+int mcpt_progressive_sample_counts(mcpt_progressive* h, int32_t* counts)
+{
+    if (!h || !counts) return fail(MCPT_ERR_ARG, "null argument");
+    if (!h->adaptive) {
+        for (int32_t pix : h->owned) counts[pix] = h->done;
+        return MCPT_OK;
+    }
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    std::vector<int32_t> all(size_t(h->d->width) * h->d->height);
+    HIP_TRY(hipMemcpy(all.data(), h->cnt, all.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    for (int32_t pix : h->owned) counts[pix] = all[size_t(pix)];
     return MCPT_OK;
 }
 
@@ -1568,7 +1670,7 @@ int mcpt_progressive_noise(mcpt_progressive* h, mcpt_noise* o)
     if (h->done < 2) { o->rel_error = o->abs_rms = INFINITY; return MCPT_OK; }     // no variance estimate from fewer than two samples
     HIP_TRY(hipSetDevice(h->d->ordinal));
     hipStream_t st = h->d->stream;
-    launch_noise_reduce(h->pixels, h->n_pixels, h->mom, h->hit, h->done, h->partials, h->sums, st);
+    launch_noise_reduce(h->pixels, h->n_pixels, h->mom, h->hit, h->done, h->cnt, h->partials, h->sums, st);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(h->h_sums, h->sums, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1582,7 +1684,7 @@ int mcpt_progressive_image_device(mcpt_progressive* h, double* d_img, double* d_
 {
     if (!h || (!d_img && !d_stderr)) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->d->ordinal));
-    launch_progressive_image(h->pixels, h->n_pixels, h->img, h->mom, h->done, h->p.spp, d_img, d_stderr, static_cast<hipStream_t>(stream));
+    launch_progressive_image(h->pixels, h->n_pixels, h->img, h->mom, h->done, h->cnt, h->p.spp, d_img, d_stderr, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MCPT_OK;
 }
@@ -1748,12 +1850,17 @@ int mcpt_decode_jpeg(const char* file, int32_t* width, int32_t* height, uint8_t*
 // render_scene's progressive frame: passes of mcpt_progressive_next_pass's schedule until the relative error reaches o.noise_target (checked
 // after every pass), the time budget runs out (measured from the first pass on, the rate of the last pass deciding the next one's size) or
 // every sample is in.  Without a time budget the pass boundaries depend on nothing but N, so the stopping point is reproducible.
+// An adaptive frame (o.adaptive_min_spp > 0): the first pass is min(N, adaptive_min_spp), the frame ends when no pixel is active, and the
+// time budget scales the last pass's seconds per sample by the share of pixels the next pass renders (the fixed cost of a pass is not
+// modelled).  counts (may be null) receives the samples of every pixel.
 static int render_scene_progressive(mcpt_device* dev, const mcpt_render_params& rp, const mcpt_render_scene_options& o, bool talk, std::vector<double>& img,
-                                    std::vector<double>* err, int& rendered, mcpt_stats& local)
+                                    std::vector<double>* err, std::vector<int32_t>* counts, int& rendered, mcpt_stats& local)
 {
     using clk = std::chrono::steady_clock;
+    const bool adaptive = o.adaptive_min_spp > 0;
     mcpt_progressive* pr = nullptr;
-    int rc = mcpt_progressive_create(dev, &rp, &pr);
+    mcpt_adaptive_params ap{o.noise_target, o.abs_target, o.adaptive_min_spp, 0};
+    int rc = adaptive ? mcpt_progressive_create_adaptive(dev, &rp, &ap, &pr) : mcpt_progressive_create(dev, &rp, &pr);
     if (rc) return rc;
     const auto t0 = clk::now();
     double rate = 0.0;
@@ -1762,19 +1869,22 @@ static int render_scene_progressive(mcpt_device* dev, const mcpt_render_params& 
     bool measured = false;
     for (;;) {
         const double remaining = o.time_budget_s > 0 ? o.time_budget_s - std::chrono::duration<double>(clk::now() - t0).count() : INFINITY;
-        const int n = mcpt_progressive_next_pass(rp.spp, pr->done, remaining, rate);
-        if (n <= 0) break;
+        int n = mcpt_progressive_next_pass(rp.spp, pr->done, remaining, rate);
+        if (adaptive && pr->done == 0) n = std::min(rp.spp, o.adaptive_min_spp);
+        if (n <= 0 || (adaptive && mcpt_progressive_active(pr) == 0)) break;
         const auto ts = clk::now();
+        const int64_t listed = mcpt_progressive_active(pr);
         mcpt_stats one{};
         if ((rc = mcpt_progressive_step(pr, n, &one))) break;
         rate = std::chrono::duration<double>(clk::now() - ts).count() / n;
+        if (adaptive) rate = listed > 0 ? rate * double(mcpt_progressive_active(pr)) / double(listed) : 0.0;
         local.rays_primary += one.rays_primary; local.rays_shadow += one.rays_shadow; local.rays_bounce += one.rays_bounce;
         local.node_visits += one.node_visits; local.tri_tests += one.tri_tests; local.shade_calls += one.shade_calls;
         local.samples += one.samples; local.shadow_skipped += one.shadow_skipped; local.ms_trace += one.ms_trace;
         local.ms_total += one.ms_total; local.launches += one.launches;
         local.max_depth = std::max(local.max_depth, one.max_depth);
         measured = false;
-        if (o.noise_target > 0) {
+        if (o.noise_target > 0 && !adaptive) {
             if ((rc = mcpt_progressive_noise(pr, &nz))) break;
             measured = true;
             if (nz.rel_error <= o.noise_target) break;
@@ -1785,6 +1895,10 @@ static int render_scene_progressive(mcpt_device* dev, const mcpt_render_params& 
         rendered = pr->done;
         if (err) err->assign(img.size(), 0.0);
         rc = mcpt_progressive_image(pr, img.data(), err ? err->data() : nullptr);
+    }
+    if (rc == MCPT_OK && counts) {
+        counts->assign(img.size() / 3, 0);
+        rc = mcpt_progressive_sample_counts(pr, counts->data());
     }
     if (rc == MCPT_OK && talk) std::printf("progressive: %d of %d samples per pixel, relative error %.4g\n", pr->done, rp.spp, nz.rel_error);
     mcpt_progressive_free(pr);
@@ -1804,11 +1918,14 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
     if (opt) std::memcpy(&o, opt, std::min<size_t>(size_t(opt_bytes), sizeof o));
     const bool talk = !o.quiet;
     // a noise target, a time budget or the error image: the frame goes through a progressive handle (one GPU, no checkpoint)
-    const bool progressive = o.noise_target > 0 || o.time_budget_s > 0 || (o.output_flags & MCPT_OUT_ERROR_PFM);
+    const bool adaptive = o.adaptive_min_spp > 0;
+    const bool progressive = o.noise_target > 0 || o.time_budget_s > 0 || (o.output_flags & MCPT_OUT_ERROR_PFM) || adaptive;
     if (o.noise_target < 0 || o.time_budget_s < 0 || std::isnan(o.noise_target) || std::isnan(o.time_budget_s))
         return fail(MCPT_ERR_ARG, "noise_target and time_budget_s must be >= 0");
+    if (o.adaptive_min_spp < 0 || o.adaptive_min_spp == 1 || (adaptive && (!(std::isfinite(o.abs_target) && o.abs_target >= 0.0) || std::isinf(o.noise_target))))
+        return fail(MCPT_ERR_ARG, "adaptive_min_spp must be 0 or >= 2, the targets finite and >= 0");
     if (progressive && (o.checkpoint || o.num_devices != 0))
-        return fail(MCPT_ERR_ARG, "a noise target, a time budget or MCPT_OUT_ERROR_PFM renders on one GPU without a checkpoint");
+        return fail(MCPT_ERR_ARG, "a noise target, a time budget, an adaptive frame or MCPT_OUT_ERROR_PFM renders on one GPU without a checkpoint");
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     mcpt_scene* sc = nullptr;
@@ -1840,8 +1957,10 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
     mcpt_stats local{};
     int rendered = spp;                                  // samples per pixel the written frame holds
     std::vector<double> err_img;
+    std::vector<int32_t> counts;                         // adaptive frames: the samples of every pixel
     if (progressive) {
-        rc = render_scene_progressive(dev, rp, o, talk, img, (o.output_flags & MCPT_OUT_ERROR_PFM) ? &err_img : nullptr, rendered, local);
+        rc = render_scene_progressive(dev, rp, o, talk, img, (o.output_flags & MCPT_OUT_ERROR_PFM) ? &err_img : nullptr, adaptive ? &counts : nullptr,
+                                      rendered, local);
     } else if (!o.checkpoint) {
         rc = many ? mcpt_multi_render(multi, &rp, img.data(), &local) : mcpt_render(dev, &rp, img.data(), &local);
     } else {
@@ -1882,6 +2001,12 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
                                                       : mcpt_write_png((stem + ".png").c_str(), rgb.data(), s.width, s.height);
         if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_PFM)) rc = mcpt_write_pfm((stem + ".pfm").c_str(), img.data(), s.width, s.height);
         if (rc == MCPT_OK && !err_img.empty()) rc = mcpt_write_pfm((stem + ".err.pfm").c_str(), err_img.data(), s.width, s.height);
+        if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_SPP_PFM)) {
+            // the sample-count map, the count in every channel: `rendered` everywhere unless the frame was adaptive
+            std::vector<double> spp_img(img.size(), double(rendered));
+            for (size_t i = 0; i < counts.size(); i++) spp_img[3 * i] = spp_img[3 * i + 1] = spp_img[3 * i + 2] = double(counts[i]);
+            rc = mcpt_write_pfm((stem + ".spp.pfm").c_str(), spp_img.data(), s.width, s.height);
+        }
     }
     if (stats) *stats = local;
     if (dev) mcpt_device_free(dev);

@@ -300,9 +300,11 @@ __device__ __forceinline__ void block_sum3(double v[3], double* out)
     if (threadIdx.x == 0)
         for (int i = 0; i < 3; i++) out[i] = ((part[0][i] + part[1][i]) + part[2][i]) + part[3][i];
 }
+// PER_PIXEL (adaptive frames): every pixel with its own sample count cnt[pix] instead of `done`.
+template <bool PER_PIXEL>
 __global__ void __launch_bounds__(256) k_noise_reduce(const int32_t* __restrict__ pixels, long long n_pixels, long long per_range,
                                                       const double* __restrict__ mom, const uint8_t* __restrict__ hit, int done,
-                                                      double* __restrict__ partials)
+                                                      const int32_t* __restrict__ cnt, double* __restrict__ partials)
 {
     const long long lo = (long long)blockIdx.x * per_range;
     const long long hi = lo + per_range < n_pixels ? lo + per_range : n_pixels;
@@ -311,9 +313,10 @@ __global__ void __launch_bounds__(256) k_noise_reduce(const int32_t* __restrict_
         const int pix = pixels ? pixels[i] : (int)i;
         if (!hit[pix]) continue;
         const double* m = mom + (size_t)pix * 6;
+        const int k = PER_PIXEL ? cnt[pix] : done;
         for (int c = 0; c < 3; c++) {
-            const double mean = m[c] / done;
-            v[0] += progressive_se2(m[c], m[3 + c], done);
+            const double mean = m[c] / k;
+            v[0] += progressive_se2(m[c], m[3 + c], k);
             v[1] += mean * mean;
         }
         v[2] += 1.0;
@@ -331,9 +334,12 @@ __global__ void __launch_bounds__(256) k_noise_final(const double* __restrict__ 
 
 // Current estimate and (est_err != null) the standard error of every owned pixel after `done` of N samples.  done == N: the float fold
 // itself (the frame mcpt_render computes); done < N: the fp64 mean s1 / done, which is not the float fold.  Error: sqrt(se2), 0 for
-// done < 2.  One lane per (owned pixel, channel); other pixels are not touched.
+// done < 2.  One lane per (owned pixel, channel); other pixels are not touched.  PER_PIXEL (adaptive frames): the pixel's own count
+// cnt[pix] in place of `done`.
+template <bool PER_PIXEL>
 __global__ void k_progressive_image(const int32_t* __restrict__ pixels, long long n_pixels, const double* __restrict__ img,
-                                    const double* __restrict__ mom, int done, int N, double* __restrict__ est, double* __restrict__ est_err)
+                                    const double* __restrict__ mom, int done, const int32_t* __restrict__ cnt, int N, double* __restrict__ est,
+                                    double* __restrict__ est_err)
 {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= n_pixels * 3) return;
@@ -341,8 +347,92 @@ __global__ void k_progressive_image(const int32_t* __restrict__ pixels, long lon
     const int pix = pixels ? pixels[gid / 3] : (int)(gid / 3);
     const size_t i = (size_t)pix * 3 + c;
     const double* m = mom + (size_t)pix * 6 + c;
-    if (est) est[i] = done == N ? img[i] : (done > 0 ? m[0] / done : 0.0);
-    if (est_err) est_err[i] = done >= 2 ? sqrt(progressive_se2(m[0], m[3], done)) : 0.0;
+    const int k = PER_PIXEL ? cnt[pix] : done;
+    if (est) est[i] = k == N ? img[i] : (k > 0 ? m[0] / k : 0.0);
+    if (est_err) est_err[i] = k >= 2 ? sqrt(progressive_se2(m[0], m[3], k)) : 0.0;
+}
+
+// ---- adaptive frames: which pixels of the active list continue after a pass of k samples, and the next list (order kept)
+// Three kernels, no atomics.  select: one lane per list entry, 256-lane blocks of four waves; each wave stores the __ballot of its keep
+// flags (masks[wave]) and the block stores its count; every listed pixel's count becomes k.  scan: one workgroup turns the block counts
+// into exclusive offsets and writes the total.  scatter: a kept lane's position is its block's offset, the popcounts of the waves before
+// it in the block and the set bits of its wave's mask below it (v_mbcnt).  An order-preserving compaction has one correct output, so the
+// list is deterministic.  The rule (mcpt.h, mcpt_progressive_create_adaptive) reads the pixel's own moments only; fp64, no contraction
+// (-ffp-contract=off), channels summed in order 0, 1, 2.
+__global__ void __launch_bounds__(256) k_adaptive_select(const int32_t* __restrict__ list, int n, const double* __restrict__ mom,
+                                                         const uint8_t* __restrict__ hit, int k, int min_spp, double rel2, double abs2,
+                                                         int32_t* __restrict__ cnt, unsigned long long* __restrict__ masks,
+                                                         int32_t* __restrict__ block_counts)
+{
+    __shared__ int wave_count[4];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    bool keep = false;
+    if (i < n) {
+        const int pix = list[i];
+        cnt[pix] = k;
+        if (hit[pix]) {
+            keep = k < min_spp;
+            if (!keep) {
+                const double* m = mom + (size_t)pix * 6;
+                double se2 = 0.0, m2 = 0.0;
+                for (int c = 0; c < 3; c++) {
+                    const double mean = m[c] / k;
+                    se2 += progressive_se2(m[c], m[3 + c], k);
+                    m2 += mean * mean;
+                }
+                keep = !(se2 < rel2 * m2 + abs2);
+            }
+        }
+    }
+    const unsigned long long mask = __ballot(keep);
+    if (lane == 0) {
+        masks[(size_t)blockIdx.x * 4 + w] = mask;
+        wave_count[w] = __popcll(mask);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) block_counts[blockIdx.x] = ((wave_count[0] + wave_count[1]) + wave_count[2]) + wave_count[3];
+}
+
+// Exclusive scan of n block counts into offsets, in chunks of 256 with a running carry; *total = the sum.  One workgroup of 256.
+__global__ void __launch_bounds__(256) k_adaptive_scan(const int32_t* __restrict__ counts, int n, int32_t* __restrict__ offsets,
+                                                       int32_t* __restrict__ total)
+{
+    __shared__ int wave_sum[4];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int carry = 0;
+    for (int base = 0; base < n; base += 256) {
+        const int i = base + threadIdx.x;
+        const int v = i < n ? counts[i] : 0;
+        int x = v;                                              // inclusive scan within the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const int y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wave_sum[w] = x;
+        __syncthreads();
+        int before = carry;
+        for (int j = 0; j < w; j++) before += wave_sum[j];
+        if (i < n) offsets[i] = before + x - v;
+        carry += ((wave_sum[0] + wave_sum[1]) + wave_sum[2]) + wave_sum[3];
+        __syncthreads();                                        // wave_sum is rewritten by the next chunk
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+__global__ void __launch_bounds__(256) k_adaptive_scatter(const int32_t* __restrict__ list, int n, const unsigned long long* __restrict__ masks,
+                                                          const int32_t* __restrict__ offsets, int32_t* __restrict__ out)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const unsigned long long* bm = masks + (size_t)blockIdx.x * 4;
+    const unsigned long long mask = bm[w];
+    if (!((mask >> lane) & 1ull)) return;
+    int pos = offsets[blockIdx.x];
+    for (int j = 0; j < w; j++) pos += __popcll(bm[j]);
+    pos += (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)mask, 0u));
+    out[pos] = list[i];
 }
 
 // End-of-frame exchange of the multi-GPU entry (multi_device.cpp): a rank's pixels leave its frame as one compact buffer
@@ -469,19 +559,33 @@ void launch_fold_progressive(const double* d_rad, const int32_t* d_pixels, const
                        d_img, d_mom, d_hit);
 }
 int noise_ranges(long long n_pixels) { return (int)std::min<long long>(kNoiseRanges, std::max<long long>(1, (n_pixels + 255) / 256)); }
-void launch_noise_reduce(const int32_t* d_pixels, long long n_pixels, const double* d_mom, const uint8_t* d_hit, int done, double* d_partials,
-                         double* d_out, hipStream_t st)
+void launch_noise_reduce(const int32_t* d_pixels, long long n_pixels, const double* d_mom, const uint8_t* d_hit, int done, const int32_t* d_cnt,
+                         double* d_partials, double* d_out, hipStream_t st)
 {
     const int ranges = noise_ranges(n_pixels);
     const long long per_range = (n_pixels + ranges - 1) / ranges;
-    hipLaunchKernelGGL(k_noise_reduce, dim3(ranges), dim3(256), 0, st, d_pixels, n_pixels, per_range, d_mom, d_hit, done, d_partials);
+    if (d_cnt) hipLaunchKernelGGL(k_noise_reduce<true>, dim3(ranges), dim3(256), 0, st, d_pixels, n_pixels, per_range, d_mom, d_hit, done, d_cnt, d_partials);
+    else hipLaunchKernelGGL(k_noise_reduce<false>, dim3(ranges), dim3(256), 0, st, d_pixels, n_pixels, per_range, d_mom, d_hit, done, d_cnt, d_partials);
     hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(256), 0, st, d_partials, ranges, d_out);
 }
-void launch_progressive_image(const int32_t* d_pixels, long long n_pixels, const double* d_img, const double* d_mom, int done, int N, double* d_est,
-                              double* d_err, hipStream_t st)
+void launch_progressive_image(const int32_t* d_pixels, long long n_pixels, const double* d_img, const double* d_mom, int done, const int32_t* d_cnt,
+                              int N, double* d_est, double* d_err, hipStream_t st)
 {
     if (n_pixels <= 0) return;
-    hipLaunchKernelGGL(k_progressive_image, dim3(blocks_for(n_pixels * 3, 256)), dim3(256), 0, st, d_pixels, n_pixels, d_img, d_mom, done, N, d_est, d_err);
+    const dim3 grid(blocks_for(n_pixels * 3, 256));
+    if (d_cnt) hipLaunchKernelGGL(k_progressive_image<true>, grid, dim3(256), 0, st, d_pixels, n_pixels, d_img, d_mom, done, d_cnt, N, d_est, d_err);
+    else hipLaunchKernelGGL(k_progressive_image<false>, grid, dim3(256), 0, st, d_pixels, n_pixels, d_img, d_mom, done, d_cnt, N, d_est, d_err);
+}
+int adaptive_blocks(int n) { return (n + 255) / 256; }
+void launch_adaptive_select(const int32_t* d_list, int n, const double* d_mom, const uint8_t* d_hit, int k, int min_spp, double rel2, double abs2,
+                            int32_t* d_cnt, unsigned long long* d_masks, int32_t* d_block_counts, int32_t* d_block_offsets, int32_t* d_total,
+                            int32_t* d_out, hipStream_t st)
+{
+    const int blocks = adaptive_blocks(n);
+    if (blocks == 0) { (void)hipMemsetAsync(d_total, 0, sizeof(int32_t), st); return; }
+    hipLaunchKernelGGL(k_adaptive_select, dim3(blocks), dim3(256), 0, st, d_list, n, d_mom, d_hit, k, min_spp, rel2, abs2, d_cnt, d_masks, d_block_counts);
+    hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(256), 0, st, d_block_counts, blocks, d_block_offsets, d_total);
+    hipLaunchKernelGGL(k_adaptive_scatter, dim3(blocks), dim3(256), 0, st, d_list, n, d_masks, d_block_offsets, d_out);
 }
 
 }  // namespace mcpt

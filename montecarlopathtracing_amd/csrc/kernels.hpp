@@ -55,9 +55,16 @@ void launch_fold_progressive(const double* d_rad, const int32_t* d_pixels, const
 // frame summary after `done` samples (done >= 2): d_out[0..3] = sum se2, sum mean^2, hit pixels, 0; d_partials holds noise_ranges() x 3 doubles
 constexpr int kNoiseRanges = 1024;
 int noise_ranges(long long n_pixels);
-void launch_noise_reduce(const int32_t* d_pixels, long long n_pixels, const double* d_mom, const uint8_t* d_hit, int done, double* d_partials,
-                         double* d_out, hipStream_t st);
-void launch_progressive_image(const int32_t* d_pixels, long long n_pixels, const double* d_img, const double* d_mom, int done, int N, double* d_est,
-                              double* d_err, hipStream_t st);
+// d_cnt == null: every pixel holds `done` samples; otherwise pixel p holds d_cnt[p] (adaptive frames)
+void launch_noise_reduce(const int32_t* d_pixels, long long n_pixels, const double* d_mom, const uint8_t* d_hit, int done, const int32_t* d_cnt,
+                         double* d_partials, double* d_out, hipStream_t st);
+void launch_progressive_image(const int32_t* d_pixels, long long n_pixels, const double* d_img, const double* d_mom, int done, const int32_t* d_cnt,
+                              int N, double* d_est, double* d_err, hipStream_t st);
+// adaptive frames: after a pass of k samples over d_list[0..n), d_cnt[p] = k for every listed p, and the pixels that continue go to d_out
+// in list order, their number to *d_total.  d_masks holds 4 * adaptive_blocks(n) words, d_block_counts / d_block_offsets adaptive_blocks(n).
+int adaptive_blocks(int n);
+void launch_adaptive_select(const int32_t* d_list, int n, const double* d_mom, const uint8_t* d_hit, int k, int min_spp, double rel2, double abs2,
+                            int32_t* d_cnt, unsigned long long* d_masks, int32_t* d_block_counts, int32_t* d_block_offsets, int32_t* d_total,
+                            int32_t* d_out, hipStream_t st);
 
 }  // namespace mcpt
