@@ -297,6 +297,55 @@ int64_t mcpt_progressive_active(const mcpt_progressive*);
 int64_t mcpt_progressive_active_pixels(mcpt_progressive*, int32_t* pixels);
 int     mcpt_progressive_sample_counts(mcpt_progressive*, int32_t* counts);
 
+/* ---- first-hit AOVs and the denoiser (since the denoising change): a better image from a progressive frame's estimate ---- */
+/* mcpt_progressive_aovs: auxiliary outputs of every owned pixel's primary hit, W*H int32 / doubles (normal, albedo: W*H*3), each pointer
+ * may be NULL; other pixels are left as they are.  They do not depend on the samples: computed once, on the handle's first aovs or denoise
+ * call (the primary rays of the owned pixels traced on the device's stream), kept with the handle and freed with it.
+ *   material : the material of the hit triangle, -1 for a miss.
+ *   depth    : the hit's ray parameter t (the primary direction is a unit vector); 0 on a miss.
+ *   normal   : the interpolated shading normal exactly as the integrator forms it at a vertex (barycentric blend of the vertex normals),
+ *              not normalised; 0 on a miss and on an emitter.
+ *   albedo   : the diffuse colour Kd exactly as shading forms it, the texel / 255 (the .mtl's map_Kd) included; 0 on a miss and an emitter.
+ * mcpt_progressive_denoise: an edge-avoiding a-trous wavelet filter (the spatial filter of SVGF) of the estimate, guided by the AOVs and
+ * the per-pixel variance.  Host: W*H*3 doubles, pixels not owned keep the caller's values; _device: into a device buffer on `stream`,
+ * asynchronous.  It works on uniform, adaptive and partitioned (rank / world) handles, reads the handle's state and never writes it.
+ * THE DENOISED IMAGE IS BIASED: it trades variance for a bias towards the neighbours' values; the estimate and stderr of
+ * mcpt_progressive_image are unchanged and stay unbiased.  Returns MCPT_ERR_ARG for done < 2, iterations outside 0..10, a sigma that is
+ * negative or not finite, a non-zero reserved field.  params == NULL or all fields 0: the defaults.  Otherwise iterations is K as given
+ * (0: no filtering) and a sigma of 0 is its default.  The filter, in fp64 without contraction, every sum in the order written:
+ *   inputs   : per owned pixel p the estimate c_p (mcpt_progressive_image), the squared standard error se2_c of every channel from the
+ *              moments (as mcpt_progressive_image, with the pixel's own count on an adaptive handle; 0 below two samples), the AOVs.
+ *   surface  : p is a surface pixel when it is owned, material_p >= 0 and the material is not an emitter.  Every other pixel (not owned,
+ *              miss, emitter) is output bit for bit as the estimate and is never a neighbour.
+ *   demodulate: a_c = max(albedo_c, 0.01), e_c = c_c / a_c; lum(e) = (0.2126 e_0 + 0.7152 e_1) + 0.0722 e_2;
+ *              v_p = sum_c ((w_c * w_c) * se2_c) / (a_c * a_c), w = (0.2126, 0.7152, 0.0722), channels in order.
+ *   n^_p     : the normal AOV divided by its length sqrt((n_x n_x + n_y n_y) + n_z n_z); a zero normal stays 0.
+ *   iteration i = 0 .. K-1, step s = 2^i, from (e, v) to (e', v'):
+ *     g_p  = sum k_q v_q / sum k_q over the 3 x 3 window q = p + (dx, dy), dx, dy in -1..1 row-major, q inside the frame, a surface
+ *            pixel with material_q == material_p; k_q = b[dx] b[dy], b = (1/4, 1/2, 1/4).
+ *     taps : q = p + s (dx, dy) for dy, dx in -2..2, row-major; a tap counts when q is inside the frame, a surface pixel and
+ *            material_q == material_p.
+ *     w_pq = ((h[dx] h[dy]) N_pq) exp(-D_pq - L_pq),   h = (1/16, 1/4, 3/8, 1/4, 1/16),
+ *            N_pq = max(0, (n^_p.x n^_q.x + n^_p.y n^_q.y) + n^_p.z n^_q.z)^128 by seven squarings, 1 at the centre tap,
+ *            D_pq = |t_q - t_p| / (((sigma_z t_p) s) max(|dx|, |dy|)), 0 at the centre tap,
+ *            L_pq = |lum(e_q) - lum(e_p)| / (sigma_l sqrt(g_p) + 1e-10).
+ *     e'_p = (sum w_pq e_q) / sum w_pq per channel,  v'_p = (sum (w_pq w_pq) v_q) / (sum w_pq * sum w_pq).
+ *   output   : a_c e_c after K iterations; K = 0: the estimate itself, bit for bit.
+ * Defaults: K = MCPT_DENOISE_ITERATIONS, sigma_l = MCPT_DENOISE_SIGMA_L, sigma_z = MCPT_DENOISE_SIGMA_Z.  Every output is one GPU lane's
+ * fixed-order sum: the same bits on any MI355X, on every call, for any pass schedule that reaches the same state. */
+#define MCPT_DENOISE_ITERATIONS      5
+#define MCPT_DENOISE_MAX_ITERATIONS  10
+#define MCPT_DENOISE_SIGMA_L         2.0
+#define MCPT_DENOISE_SIGMA_Z         0.05
+typedef struct {
+    int32_t iterations;         /* K (0 with both sigmas 0: the defaults) */
+    int32_t reserved;           /* must be 0 */
+    double  sigma_l, sigma_z;   /* 0 = the default */
+} mcpt_denoise_params;
+int mcpt_progressive_aovs(mcpt_progressive*, int32_t* material, double* depth, double* normal, double* albedo);
+int mcpt_progressive_denoise(mcpt_progressive*, const mcpt_denoise_params*, double* img);
+int mcpt_progressive_denoise_device(mcpt_progressive*, const mcpt_denoise_params*, double* d_img, void* stream);
+
 /* ---- integrator over several GPUs of one node (no reference counterpart: generateImg is single-process OpenMP) ---- */
 /* The frame is cut into tiles dealt to the GPUs exactly as mcpt_render_params.rank/world describe (rank r = devices[r]); the scene
  * is resident on every GPU; one host thread per GPU renders its tiles; at the end of the frame every rank's pixels travel as one
@@ -368,6 +417,10 @@ int  mcpt_render_scene(const char* path, const char* filename, int32_t spp);
 #define MCPT_OUT_PFM          2      /* also write <prefix>-SPP<N>.pfm: the linear fp32 radiance before imshow's clamp */
 #define MCPT_OUT_ERROR_PFM    4      /* also write <prefix>-SPP<N>.err.pfm: the per-pixel standard error (mcpt_progressive_image) as fp32 */
 #define MCPT_OUT_SPP_PFM      8      /* also write <prefix>-SPP<N>.spp.pfm: the samples each pixel holds (mcpt_progressive_sample_counts) */
+#define MCPT_OUT_DENOISED    16      /* also write <prefix>-SPP<N>.denoised.png (and .denoised.pfm with MCPT_OUT_PFM): mcpt_progressive_denoise
+                                        with the defaults; needs N >= 2 */
+#define MCPT_OUT_AOV_PFM     32      /* also write <prefix>-SPP<N>.albedo.pfm, .normal.pfm, .depth.pfm and .material.pfm (mcpt_progressive_aovs;
+                                        depth and material -- as a float, -1 for a miss -- in all three channels) as fp32 */
 typedef struct {
     uint64_t seed;
     int32_t  device;            /* HIP ordinal */
@@ -389,7 +442,9 @@ typedef struct {
      * is set, the frame is rendered progressively (mcpt_progressive_*, the passes of mcpt_progressive_next_pass): it stops after the
      * first pass whose rel_error <= noise_target, or when the time budget (seconds, counted from the first pass) allows no further pass,
      * or at N.  A frame stopped at k < N samples is written as <prefix>-SPP<k>.png (the estimate of mcpt_progressive_image); at N it is
-     * the plain call's frame, byte for byte.  With a checkpoint or num_devices != 0 these return MCPT_ERR_ARG. */
+     * the plain call's frame, byte for byte.  With a checkpoint or num_devices != 0 these return MCPT_ERR_ARG.  MCPT_OUT_DENOISED and
+     * MCPT_OUT_AOV_PFM (since the denoising change) also make the frame progressive, under the same conditions; the plain .png stays
+     * byte for byte what it is without them. */
     double   noise_target;      /* 0 = none */
     double   time_budget_s;     /* 0 = none */
     /* since the adaptive-sampling change (mcpt_render_scene_opts only).  adaptive_min_spp > 0: an adaptive frame

@@ -71,6 +71,11 @@ class AdaptiveParams(C.Structure):
     _fields_ = [("rel_target", C.c_double), ("abs_target", C.c_double), ("min_spp", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DenoiseParams(C.Structure):
+    """mcpt_denoise_params: the a-trous filter of mcpt_progressive_denoise (0 = the default)"""
+    _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("sigma_l", C.c_double), ("sigma_z", C.c_double)]
+
+
 class Noise(C.Structure):
     """mcpt_noise: the frame summary of a progressive frame after `done` of `spp` samples"""
     _fields_ = [("done", C.c_int32), ("spp", C.c_int32), ("pixels", C.c_int64), ("rel_error", C.c_double), ("abs_rms", C.c_double),
@@ -96,6 +101,7 @@ EXPORTS = [
     "mcpt_progressive_create", "mcpt_progressive_step", "mcpt_progressive_done", "mcpt_progressive_noise", "mcpt_progressive_image",
     "mcpt_progressive_image_device", "mcpt_progressive_next_pass", "mcpt_progressive_free",
     "mcpt_progressive_create_adaptive", "mcpt_progressive_active", "mcpt_progressive_active_pixels", "mcpt_progressive_sample_counts",
+    "mcpt_progressive_aovs", "mcpt_progressive_denoise", "mcpt_progressive_denoise_device",
     "mcpt_multi_create", "mcpt_multi_num_devices", "mcpt_multi_render", "mcpt_multi_render_device", "mcpt_multi_last_timing", "mcpt_multi_collect_stats", "mcpt_multi_free",
     "mcpt_comm_unique_id", "mcpt_comm_create", "mcpt_comm_size", "mcpt_comm_gather_frame", "mcpt_comm_allreduce", "mcpt_comm_free",
     "mcpt_render_scene", "mcpt_render_scene_ex", "mcpt_render_scene_opts",
@@ -187,6 +193,9 @@ def lib():
     L.mcpt_progressive_active_pixels.argtypes = [P, I32]
     L.mcpt_progressive_active_pixels.restype = C.c_int64
     L.mcpt_progressive_sample_counts.argtypes = [P, I32]
+    L.mcpt_progressive_aovs.argtypes = [P, I32, D, D, D]
+    L.mcpt_progressive_denoise.argtypes = [P, C.POINTER(DenoiseParams), D]
+    L.mcpt_progressive_denoise_device.argtypes = [P, C.POINTER(DenoiseParams), P, P]
     L.mcpt_multi_create.argtypes = [P, I32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(P)]
     L.mcpt_multi_num_devices.argtypes = [P]
     L.mcpt_multi_render.argtypes = [P, C.POINTER(RenderParams), D, C.POINTER(Stats)]

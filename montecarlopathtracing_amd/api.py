@@ -5,14 +5,14 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
+from ._lib import AdaptiveParams, DenoiseParams, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
 RENDER_DEFAULT, RENDER_MEGAKERNEL = 0, 2
 RENDER_KEEP_STATS, RENDER_PIPELINE = 4, 8
 LOAD_STANDARD_OBJ, LOAD_MTLLIB, LOAD_MORTON_BOUNDS = 1, 2, 4
-OUT_PNG_DEFLATE, OUT_PFM, OUT_ERROR_PFM, OUT_SPP_PFM = 1, 2, 4, 8
+OUT_PNG_DEFLATE, OUT_PFM, OUT_ERROR_PFM, OUT_SPP_PFM, OUT_DENOISED, OUT_AOV_PFM = 1, 2, 4, 8, 16, 32
 BUILD_HOST, BUILD_DEVICE, BUILD_DEVICE_FAST, BUILD_DEVICE_SAH = 0, 1, 2, 3
 SCENE_DEFER_BUILD = 1
 GATHER_PEER, GATHER_RCCL = 0, 1
@@ -359,6 +359,26 @@ class Progressive:
         check(lib().mcpt_progressive_image(self._h, None, _p(err, C.c_double)))
         return err
 
+    def aovs(self):
+        """the first-hit AOVs of the owned pixels (mcpt_progressive_aovs): a dict of numpy arrays, material [H,W] int32 (-1: a miss),
+        depth [H,W], normal [H,W,3] (not normalised) and albedo [H,W,3] float64.  Pixels not owned: material -1, the rest 0."""
+        h, w = self.device.height, self.device.width
+        out = {"material": np.full((h, w), -1, dtype=np.int32), "depth": np.zeros((h, w)), "normal": np.zeros((h, w, 3)),
+               "albedo": np.zeros((h, w, 3))}
+        check(lib().mcpt_progressive_aovs(self._h, _p(out["material"], C.c_int32), _p(out["depth"], C.c_double),
+                                          _p(out["normal"], C.c_double), _p(out["albedo"], C.c_double)))
+        return out
+
+    def denoise(self, iterations=0, sigma_l=0.0, sigma_z=0.0, img=None):
+        """the a-trous denoised estimate as [H,W,3] float64 (mcpt_progressive_denoise; pixels not owned: left as in img, else 0).  All
+        three 0: the defaults; otherwise iterations is taken as given (0: the estimate) and a sigma of 0 is its default.  Biased, unlike
+        image(); needs done >= 2."""
+        if img is None:
+            img = np.zeros((self.device.height, self.device.width, 3))
+        dp = DenoiseParams(iterations, 0, sigma_l, sigma_z)
+        check(lib().mcpt_progressive_denoise(self._h, C.byref(dp), _p(img, C.c_double)))
+        return img
+
     def close(self):
         if getattr(self, "_h", None):
             lib().mcpt_progressive_free(self._h)
@@ -515,7 +535,8 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
     """render_scene(path, filename, N) of MTPC/MTPC.cpp:35; writes <prefix>-SPP<N>.png (default ../result/<filename>).
     devices: list of GPU ordinals, or -1 for every visible GPU (the frame is then rendered by mcpt_multi_*).
     noise_target / time_budget_s / OUT_ERROR_PFM: a progressive frame that may stop at k < N samples (<prefix>-SPP<k>.png).
-    adaptive_min_spp > 0: an adaptive frame, noise_target and abs_target its per-pixel targets (OUT_SPP_PFM: the sample-count map)."""
+    adaptive_min_spp > 0: an adaptive frame, noise_target and abs_target its per-pixel targets (OUT_SPP_PFM: the sample-count map).
+    OUT_DENOISED / OUT_AOV_PFM: also the denoised frame (.denoised.png, .denoised.pfm with OUT_PFM) / the first-hit AOVs as .pfm files."""
     dev_arr, ndev = None, 0
     if devices == -1:
         ndev = -1

@@ -21,6 +21,7 @@
 
 #include "accel_build.hpp"
 #include "build_kernels.hpp"
+#include "denoise.hpp"
 #include "jpeg_decoder.hpp"
 #include "kernels.hpp"
 #include "knobs.hpp"
@@ -1505,6 +1506,12 @@ struct mcpt_progressive {
     int32_t* block_counts = nullptr; int32_t* block_offsets = nullptr;   // adaptive_blocks(n_pixels) each
     int32_t* total = nullptr;          // the next list's length
     int32_t* h_total = nullptr;        // pinned copy of total (the pass's 4-byte read-back)
+    // first-hit AOVs (W*H[*3], owned pixels written; computed on the first mcpt_progressive_aovs / _denoise call: they do not depend on
+    // the samples) and the guide record the denoiser's taps read
+    bool aov_ready = false;
+    int32_t* aov_mat = nullptr; double* aov_depth = nullptr; double* aov_normal = nullptr; double* aov_albedo = nullptr;
+    DenoiseGuide* guide = nullptr;
+    DenoisePix* dn_buf[2] = {nullptr, nullptr};   // the denoiser's ping-pong buffers (W*H each), allocated on its first call
 };
 
 void mcpt_progressive_free(mcpt_progressive* h)
@@ -1515,7 +1522,9 @@ void mcpt_progressive_free(mcpt_progressive* h)
     for (void* q : {static_cast<void*>(h->pixels), static_cast<void*>(h->img), static_cast<void*>(h->mom), static_cast<void*>(h->hit),
                     static_cast<void*>(h->partials), static_cast<void*>(h->sums), static_cast<void*>(h->active[0]), static_cast<void*>(h->active[1]),
                     static_cast<void*>(h->cnt), static_cast<void*>(h->masks), static_cast<void*>(h->block_counts),
-                    static_cast<void*>(h->block_offsets), static_cast<void*>(h->total)})
+                    static_cast<void*>(h->block_offsets), static_cast<void*>(h->total), static_cast<void*>(h->aov_mat),
+                    static_cast<void*>(h->aov_depth), static_cast<void*>(h->aov_normal), static_cast<void*>(h->aov_albedo),
+                    static_cast<void*>(h->guide), static_cast<void*>(h->dn_buf[0]), static_cast<void*>(h->dn_buf[1])})
         if (q) (void)hipFree(q);
     if (h->h_sums) (void)hipHostFree(h->h_sums);
     if (h->h_total) (void)hipHostFree(h->h_total);
@@ -1708,6 +1717,121 @@ int mcpt_progressive_image(mcpt_progressive* h, double* img, double* stderr_img)
     return rc;
 }
 
+// First-hit AOVs of the owned pixels: the primary hits of the owned list traced again on the device's stream and closest-hit workspace
+// (launch_primary_hits, as a render call traces them), then k_primary_aov.  Once per handle.
+static int ensure_aovs(mcpt_progressive* h)
+{
+    if (h->aov_ready) return MCPT_OK;
+    mcpt_device* d = h->d;
+    hipStream_t st = d->stream;
+    int rc = ensure_dirs(d, st);
+    if (rc) return rc;
+    const size_t px = size_t(d->width) * d->height;
+    PrimaryHit* hits = nullptr;
+    hipError_t e = hipSuccess;
+    auto alloc = [&](void** q, size_t bytes) { if (e == hipSuccess && !*q) e = hipMalloc(q, std::max<size_t>(bytes, 8)); };
+    alloc(reinterpret_cast<void**>(&hits), size_t(h->n_pixels) * sizeof(PrimaryHit));
+    alloc(reinterpret_cast<void**>(&h->aov_mat), px * sizeof(int32_t));
+    alloc(reinterpret_cast<void**>(&h->aov_depth), px * sizeof(double));
+    alloc(reinterpret_cast<void**>(&h->aov_normal), px * 3 * sizeof(double));
+    alloc(reinterpret_cast<void**>(&h->aov_albedo), px * 3 * sizeof(double));
+    alloc(reinterpret_cast<void**>(&h->guide), px * sizeof(DenoiseGuide));
+    // pixels not owned: material -1 everywhere in the guide (all bits set), so that no tap reads them
+    if (e == hipSuccess) e = hipMemsetAsync(h->guide, 0xff, px * sizeof(DenoiseGuide), st);
+    if (e == hipSuccess) {
+        launch_primary_hits(d->ds, d->trace_mode == MCPT_TRACE_FAST, d->dirs, h->pixels, int(h->n_pixels), hits, d->aux_ctr, d->aux_queue,
+                            d->aux_slow_list, d->slow_cap, st, d->cfg);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        launch_primary_aov(d->ds, h->pixels, int(h->n_pixels), hits, h->aov_mat, h->aov_depth, h->aov_normal, h->aov_albedo, h->guide, st);
+        e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (hits) (void)hipFree(hits);
+    if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("first-hit AOVs: ") + hipGetErrorString(e));
+    h->aov_ready = true;
+    return MCPT_OK;
+}
+
+int mcpt_progressive_aovs(mcpt_progressive* h, int32_t* material, double* depth, double* normal, double* albedo)
+{
+    if (!h) return fail(MCPT_ERR_ARG, "null handle");
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    int rc = ensure_aovs(h);
+    if (rc) return rc;
+    const size_t px = size_t(h->d->width) * h->d->height;
+    // the device arrays whole, then the owned pixels into the caller's (pixels not owned keep the caller's values)
+    auto fetch = [&](const void* src, void* dst, size_t per_pixel) -> int {
+        if (!dst) return MCPT_OK;
+        std::vector<uint8_t> all(px * per_pixel);
+        HIP_TRY(hipMemcpy(all.data(), src, all.size(), hipMemcpyDeviceToHost));
+        for (int32_t pix : h->owned) std::memcpy(static_cast<uint8_t*>(dst) + size_t(pix) * per_pixel, all.data() + size_t(pix) * per_pixel, per_pixel);
+        return MCPT_OK;
+    };
+    if ((rc = fetch(h->aov_mat, material, sizeof(int32_t)))) return rc;
+    if ((rc = fetch(h->aov_depth, depth, sizeof(double)))) return rc;
+    if ((rc = fetch(h->aov_normal, normal, 3 * sizeof(double)))) return rc;
+    return fetch(h->aov_albedo, albedo, 3 * sizeof(double));
+}
+
+static int denoise_args(const mcpt_progressive* h, const mcpt_denoise_params* dp, int& iterations, double& sigma_l, double& sigma_z)
+{
+    if (!h) return fail(MCPT_ERR_ARG, "null handle");
+    const mcpt_denoise_params z{};
+    const mcpt_denoise_params& q = dp ? *dp : z;
+    if (q.reserved != 0) return fail(MCPT_ERR_ARG, "mcpt_denoise_params.reserved must be 0");
+    if (q.iterations < 0 || q.iterations > MCPT_DENOISE_MAX_ITERATIONS) return fail(MCPT_ERR_ARG, "denoise iterations outside 0..10");
+    if (!(std::isfinite(q.sigma_l) && q.sigma_l >= 0.0 && std::isfinite(q.sigma_z) && q.sigma_z >= 0.0))
+        return fail(MCPT_ERR_ARG, "denoise sigmas must be finite and >= 0 (0: the default)");
+    if (h->done < 2) return fail(MCPT_ERR_ARG, "denoising needs a variance estimate: at least two samples done");
+    const bool defaults = q.iterations == 0 && q.sigma_l == 0.0 && q.sigma_z == 0.0;     // a zero struct: the defaults
+    iterations = defaults ? MCPT_DENOISE_ITERATIONS : q.iterations;
+    sigma_l = q.sigma_l > 0.0 ? q.sigma_l : MCPT_DENOISE_SIGMA_L;
+    sigma_z = q.sigma_z > 0.0 ? q.sigma_z : MCPT_DENOISE_SIGMA_Z;
+    return MCPT_OK;
+}
+
+int mcpt_progressive_denoise_device(mcpt_progressive* h, const mcpt_denoise_params* dp, double* d_img, void* stream)
+{
+    int iterations = 0;
+    double sigma_l = 0.0, sigma_z = 0.0;
+    int rc = denoise_args(h, dp, iterations, sigma_l, sigma_z);
+    if (rc) return rc;
+    if (!d_img) return fail(MCPT_ERR_ARG, "null image");
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    if ((rc = ensure_aovs(h))) return rc;
+    const size_t px = size_t(h->d->width) * h->d->height;
+    for (auto& b : h->dn_buf)
+        if (!b) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b), std::max<size_t>(px, 1) * sizeof(DenoisePix)));
+    launch_denoise(h->pixels, h->n_pixels, h->d->width, h->d->height, h->img, h->mom, h->done, h->cnt, h->p.spp, h->aov_albedo, h->guide,
+                   iterations, sigma_l, sigma_z, h->dn_buf[0], h->dn_buf[1], d_img, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MCPT_OK;
+}
+
+int mcpt_progressive_denoise(mcpt_progressive* h, const mcpt_denoise_params* dp, double* img)
+{
+    int iterations = 0;
+    double sigma_l = 0.0, sigma_z = 0.0;
+    int rc = denoise_args(h, dp, iterations, sigma_l, sigma_z);
+    if (rc) return rc;
+    if (!img) return fail(MCPT_ERR_ARG, "null image");
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    const size_t bytes = size_t(h->d->width) * h->d->height * 3 * sizeof(double);
+    double* d_out = nullptr;
+    // pageable host buffer: blocking copies either side; pixels this rank does not own keep the caller's values
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_out), bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_out, img, bytes, hipMemcpyHostToDevice);
+    rc = e == hipSuccess ? mcpt_progressive_denoise_device(h, dp, d_out, h->d->stream) : fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    e = hipStreamSynchronize(h->d->stream);
+    if (rc == MCPT_OK && e == hipSuccess) e = hipMemcpy(img, d_out, bytes, hipMemcpyDeviceToHost);
+    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    (void)hipFree(d_out);
+    return rc;
+}
+
 int mcpt_progressive_next_pass(int32_t spp, int32_t done, double remaining_s, double s_per_sample)
 {
     if (spp <= 0 || done < 0 || done >= spp) return 0;
@@ -1852,9 +1976,12 @@ int mcpt_decode_jpeg(const char* file, int32_t* width, int32_t* height, uint8_t*
 // every sample is in.  Without a time budget the pass boundaries depend on nothing but N, so the stopping point is reproducible.
 // An adaptive frame (o.adaptive_min_spp > 0): the first pass is min(N, adaptive_min_spp), the frame ends when no pixel is active, and the
 // time budget scales the last pass's seconds per sample by the share of pixels the next pass renders (the fixed cost of a pass is not
-// modelled).  counts (may be null) receives the samples of every pixel.
+// modelled).  counts (may be null) receives the samples of every pixel; denoised (may be null) mcpt_progressive_denoise's image with the
+// defaults; aovs (may be null) the AOV images, every one as W*H*3 doubles (albedo, normal, depth, material: the scalars in all channels).
+struct SceneAovs { std::vector<double> albedo, normal, depth, material; };
 static int render_scene_progressive(mcpt_device* dev, const mcpt_render_params& rp, const mcpt_render_scene_options& o, bool talk, std::vector<double>& img,
-                                    std::vector<double>* err, std::vector<int32_t>* counts, int& rendered, mcpt_stats& local)
+                                    std::vector<double>* err, std::vector<int32_t>* counts, std::vector<double>* denoised, SceneAovs* aovs,
+                                    int& rendered, mcpt_stats& local)
 {
     using clk = std::chrono::steady_clock;
     const bool adaptive = o.adaptive_min_spp > 0;
@@ -1900,6 +2027,22 @@ static int render_scene_progressive(mcpt_device* dev, const mcpt_render_params& 
         counts->assign(img.size() / 3, 0);
         rc = mcpt_progressive_sample_counts(pr, counts->data());
     }
+    if (rc == MCPT_OK && denoised) {
+        denoised->assign(img.size(), 0.0);
+        rc = mcpt_progressive_denoise(pr, nullptr, denoised->data());
+    }
+    if (rc == MCPT_OK && aovs) {
+        const size_t px = img.size() / 3;
+        std::vector<int32_t> mat(px, -1);
+        std::vector<double> depth(px, 0.0);
+        aovs->albedo.assign(img.size(), 0.0);
+        aovs->normal.assign(img.size(), 0.0);
+        rc = mcpt_progressive_aovs(pr, mat.data(), depth.data(), aovs->normal.data(), aovs->albedo.data());
+        aovs->depth.resize(img.size());
+        aovs->material.resize(img.size());
+        for (size_t i = 0; i < px; i++)
+            for (size_t c = 0; c < 3; c++) { aovs->depth[3 * i + c] = depth[i]; aovs->material[3 * i + c] = double(mat[i]); }
+    }
     if (rc == MCPT_OK && talk) std::printf("progressive: %d of %d samples per pixel, relative error %.4g\n", pr->done, rp.spp, nz.rel_error);
     mcpt_progressive_free(pr);
     return rc;
@@ -1919,13 +2062,16 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
     const bool talk = !o.quiet;
     // a noise target, a time budget or the error image: the frame goes through a progressive handle (one GPU, no checkpoint)
     const bool adaptive = o.adaptive_min_spp > 0;
-    const bool progressive = o.noise_target > 0 || o.time_budget_s > 0 || (o.output_flags & MCPT_OUT_ERROR_PFM) || adaptive;
+    const bool progressive = o.noise_target > 0 || o.time_budget_s > 0 || (o.output_flags & (MCPT_OUT_ERROR_PFM | MCPT_OUT_DENOISED | MCPT_OUT_AOV_PFM)) ||
+                             adaptive;
     if (o.noise_target < 0 || o.time_budget_s < 0 || std::isnan(o.noise_target) || std::isnan(o.time_budget_s))
         return fail(MCPT_ERR_ARG, "noise_target and time_budget_s must be >= 0");
     if (o.adaptive_min_spp < 0 || o.adaptive_min_spp == 1 || (adaptive && (!(std::isfinite(o.abs_target) && o.abs_target >= 0.0) || std::isinf(o.noise_target))))
         return fail(MCPT_ERR_ARG, "adaptive_min_spp must be 0 or >= 2, the targets finite and >= 0");
     if (progressive && (o.checkpoint || o.num_devices != 0))
-        return fail(MCPT_ERR_ARG, "a noise target, a time budget, an adaptive frame or MCPT_OUT_ERROR_PFM renders on one GPU without a checkpoint");
+        return fail(MCPT_ERR_ARG, "a noise target, a time budget, an adaptive frame, MCPT_OUT_ERROR_PFM, MCPT_OUT_DENOISED or MCPT_OUT_AOV_PFM renders "
+                                  "on one GPU without a checkpoint");
+    if ((o.output_flags & MCPT_OUT_DENOISED) && spp < 2) return fail(MCPT_ERR_ARG, "MCPT_OUT_DENOISED needs N >= 2 (a variance estimate)");
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     mcpt_scene* sc = nullptr;
@@ -1958,8 +2104,11 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
     int rendered = spp;                                  // samples per pixel the written frame holds
     std::vector<double> err_img;
     std::vector<int32_t> counts;                         // adaptive frames: the samples of every pixel
+    std::vector<double> denoised;
+    SceneAovs aovs;
     if (progressive) {
         rc = render_scene_progressive(dev, rp, o, talk, img, (o.output_flags & MCPT_OUT_ERROR_PFM) ? &err_img : nullptr, adaptive ? &counts : nullptr,
+                                      (o.output_flags & MCPT_OUT_DENOISED) ? &denoised : nullptr, (o.output_flags & MCPT_OUT_AOV_PFM) ? &aovs : nullptr,
                                       rendered, local);
     } else if (!o.checkpoint) {
         rc = many ? mcpt_multi_render(multi, &rp, img.data(), &local) : mcpt_render(dev, &rp, img.data(), &local);
@@ -2006,6 +2155,19 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
             std::vector<double> spp_img(img.size(), double(rendered));
             for (size_t i = 0; i < counts.size(); i++) spp_img[3 * i] = spp_img[3 * i + 1] = spp_img[3 * i + 2] = double(counts[i]);
             rc = mcpt_write_pfm((stem + ".spp.pfm").c_str(), spp_img.data(), s.width, s.height);
+        }
+        if (rc == MCPT_OK && !denoised.empty()) {
+            mcpt_quantize_rgb8(denoised.data(), int64_t(denoised.size()), rgb.data());
+            const std::string dn = stem + ".denoised";
+            rc = (o.output_flags & MCPT_OUT_PNG_DEFLATE) ? mcpt_write_png_deflate((dn + ".png").c_str(), rgb.data(), s.width, s.height)
+                                                          : mcpt_write_png((dn + ".png").c_str(), rgb.data(), s.width, s.height);
+            if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_PFM)) rc = mcpt_write_pfm((dn + ".pfm").c_str(), denoised.data(), s.width, s.height);
+        }
+        if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_AOV_PFM)) {
+            const std::pair<const char*, const std::vector<double>*> files[] = {
+                {".albedo.pfm", &aovs.albedo}, {".normal.pfm", &aovs.normal}, {".depth.pfm", &aovs.depth}, {".material.pfm", &aovs.material}};
+            for (const auto& f : files)
+                if (rc == MCPT_OK) rc = mcpt_write_pfm((stem + f.first).c_str(), f.second->data(), s.width, s.height);
         }
     }
     if (stats) *stats = local;

@@ -50,6 +50,15 @@ __device__ __forceinline__ double dmax3(double p1, double p2, double p3)
     else return p3;
 }
 
+// ------------------------------------------------------------------------------------------------ progressive frames
+// Squared standard error of the mean of one channel after k samples (k >= 2): the unbiased sample variance over k.  The difference of
+// the moments can come out a rounding below zero for a pixel whose samples are all equal: clamped to 0.
+__device__ __forceinline__ double progressive_se2(double s1, double s2, int k)
+{
+    const double var = (s2 - s1 * s1 / k) / (k - 1);
+    return (var > 0.0 ? var : 0.0) / k;
+}
+
 // ------------------------------------------------------------------------------------------------ RNG seam (D1)
 // Philox4x32-10, counter (pixel, sample, depth<<16 | block, 'MCPT'), key = seed.  A path vertex numbers its uniforms by slot
 // (light l: 4l..4l+3, then RR, FRESNEL, LOBE, PHI, THETA); slot s is word s & 3 of block s >> 2 and a word w becomes

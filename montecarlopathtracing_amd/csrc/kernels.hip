@@ -273,14 +273,6 @@ __global__ void k_fold_progressive(const double* __restrict__ rad, const int32_t
     m[0] = s1; m[3] = s2;
 }
 
-// Squared standard error of the mean of one channel after k samples (k >= 2): the unbiased sample variance over k.  The difference of
-// the moments can come out a rounding below zero for a pixel whose samples are all equal: clamped to 0.
-__device__ __forceinline__ double progressive_se2(double s1, double s2, int k)
-{
-    const double var = (s2 - s1 * s1 / k) / (k - 1);
-    return (var > 0.0 ? var : 0.0) / k;
-}
-
 // Frame summary (k_noise_reduce + k_noise_final): over the owned hit pixels, sum se2 and sum mean^2 of every channel and the pixel count.
 // Deterministic and independent of the device: the pixel list is cut into `ranges` contiguous ranges (a number fixed by the pixel count,
 // not by the grid), block r reduces range r -- thread t takes the range's pixels t, t + 256, ... in order, the waves reduce with a fixed
