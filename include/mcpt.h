@@ -189,6 +189,24 @@ int  mcpt_device_create(const mcpt_scene*, int32_t device_ordinal, mcpt_device**
 int  mcpt_device_create_ex(const mcpt_scene*, int32_t device_ordinal, int32_t build_mode, mcpt_device** out);
 int  mcpt_device_get_bvh_nodes(mcpt_device*, double* box6 /* Nr*6, may be NULL */, int32_t* leaf_face /* Nr, may be NULL */);
 int  mcpt_device_get_leaf_order(mcpt_device*, int32_t* leaf_to_face);
+/* Read-only view of the culling hierarchy the fast walk of a device walks (tests check its structure).  Two-call pattern: with
+ * nodes and tri_faces NULL only *info is filled.  nodes[n_nodes] = the raw 64-byte compressed 4-wide records as the device holds
+ * them (root = 0; per axis plane = p + q * 2^e, q in 0..255; child >= 0: node, MCPT_FAST_EMPTY: none, else a leaf
+ * -1 - ((first << 4) | (count - 1)) over tri_faces[first .. first+count)); tri_faces[n_tris] = .obj face of each triangle slot. */
+#define MCPT_FAST_BUILT_HOST        0   /* host SAH builder (MCPT_BUILD_HOST, MCPT_BUILD_DEVICE) */
+#define MCPT_FAST_BUILT_DEVICE_FAST 1   /* MCPT_BUILD_DEVICE_FAST: Morton clusters on the GPU */
+#define MCPT_FAST_BUILT_DEVICE_PLOC 2   /* MCPT_BUILD_DEVICE_SAH: clusters grown by PLOC on the GPU */
+#define MCPT_FAST_BUILT_PLOC_FELL_BACK 3 /* MCPT_BUILD_DEVICE_SAH that left too many clusters: built as MCPT_BUILD_DEVICE_FAST */
+typedef struct {
+    int32_t n_nodes, n_tris;
+    int32_t enabled;            /* 0: the fast walk is off on this device (coordinates or stack need out of range) */
+    int32_t cw_stack_need;      /* worst-case walk stack entries the builder recorded */
+    int32_t max_depth;          /* inner levels the builder recorded */
+    int32_t builder;            /* MCPT_FAST_BUILT_* */
+    int32_t clusters;           /* MCPT_FAST_BUILT_DEVICE_PLOC: clusters grown on the GPU; otherwise 0 */
+    int32_t reserved;
+} mcpt_fast_info;
+int  mcpt_device_fast_hierarchy(const mcpt_device*, mcpt_fast_info* info, void* nodes, int32_t* tri_faces);
 void mcpt_device_free(mcpt_device*);
 /* Which walk the closest-hit queries use.  Both return identical results (tests/test_gpu_parity.py).
  *   MCPT_TRACE_FAST (default): SAH hierarchy over the reference's leaf boxes, conservative culling, distance pruning,

@@ -76,6 +76,11 @@ class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("sigma_l", C.c_double), ("sigma_z", C.c_double)]
 
 
+class FastInfo(C.Structure):
+    """mcpt_fast_info: shape and origin of the culling hierarchy a device's fast walk walks (mcpt_device_fast_hierarchy)"""
+    _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_tris", "enabled", "cw_stack_need", "max_depth", "builder", "clusters", "reserved")]
+
+
 class Noise(C.Structure):
     """mcpt_noise: the frame summary of a progressive frame after `done` of `spp` samples"""
     _fields_ = [("done", C.c_int32), ("spp", C.c_int32), ("pixels", C.c_int64), ("rel_error", C.c_double), ("abs_rms", C.c_double),
@@ -92,7 +97,7 @@ EXPORTS = [
     "mcpt_scene_load", "mcpt_scene_load_ex", "mcpt_scene_create", "mcpt_scene_free", "mcpt_scene_set_resolution", "mcpt_scene_get_info", "mcpt_scene_get_faces",
     "mcpt_scene_get_leaf_order", "mcpt_scene_get_bvh_nodes", "mcpt_scene_find_index", "mcpt_scene_get_material",
     "mcpt_scene_get_light", "mcpt_morton_code", "mcpt_scene_fast_bvh_stats",
-    "mcpt_device_create", "mcpt_device_create_ex", "mcpt_device_get_bvh_nodes", "mcpt_device_get_leaf_order", "mcpt_device_free",
+    "mcpt_device_create", "mcpt_device_create_ex", "mcpt_device_get_bvh_nodes", "mcpt_device_get_leaf_order", "mcpt_device_fast_hierarchy", "mcpt_device_free",
     "mcpt_device_set_trace_mode", "mcpt_scene_trace_engine",
     "mcpt_trace_closest", "mcpt_trace_closest_device",
     "mcpt_render", "mcpt_render_device", "mcpt_device_collect_stats", "mcpt_sample_radiance", "mcpt_owned_pixels",
@@ -155,6 +160,7 @@ def lib():
     L.mcpt_device_create_ex.argtypes = [P, C.c_int32, C.c_int32, C.POINTER(P)]
     L.mcpt_device_get_bvh_nodes.argtypes = [P, D, I32]
     L.mcpt_device_get_leaf_order.argtypes = [P, I32]
+    L.mcpt_device_fast_hierarchy.argtypes = [P, C.POINTER(FastInfo), P, I32]
     L.mcpt_device_free.argtypes = [P]
     L.mcpt_device_free.restype = None
     L.mcpt_device_set_trace_mode.argtypes = [P, C.c_int32]

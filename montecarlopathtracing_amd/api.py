@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, DenoiseParams, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
+from ._lib import AdaptiveParams, DenoiseParams, FastInfo, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -14,6 +14,8 @@ RENDER_KEEP_STATS, RENDER_PIPELINE = 4, 8
 LOAD_STANDARD_OBJ, LOAD_MTLLIB, LOAD_MORTON_BOUNDS = 1, 2, 4
 OUT_PNG_DEFLATE, OUT_PFM, OUT_ERROR_PFM, OUT_SPP_PFM, OUT_DENOISED, OUT_AOV_PFM = 1, 2, 4, 8, 16, 32
 BUILD_HOST, BUILD_DEVICE, BUILD_DEVICE_FAST, BUILD_DEVICE_SAH = 0, 1, 2, 3
+# mcpt_fast_info.builder: which builder made the culling hierarchy a device walks
+FAST_BUILT_HOST, FAST_BUILT_DEVICE_FAST, FAST_BUILT_DEVICE_PLOC, FAST_BUILT_PLOC_FELL_BACK = 0, 1, 2, 3
 SCENE_DEFER_BUILD = 1
 GATHER_PEER, GATHER_RCCL = 0, 1
 
@@ -237,6 +239,16 @@ class Device:
         o = np.zeros(self.scene.info.num_faces, dtype=np.int32)
         check(lib().mcpt_device_get_leaf_order(self._h, _p(o, C.c_int32)))
         return o
+
+    def fast_hierarchy(self):
+        """(FastInfo, nodes [n_nodes] uint8 records of 64 bytes, tri_faces [n_tris]): the culling hierarchy the fast walk walks, read
+        back from HBM (mcpt_device_fast_hierarchy; tests/fast_bvh_ref.py decodes and checks it)."""
+        info = FastInfo()
+        check(lib().mcpt_device_fast_hierarchy(self._h, C.byref(info), None, None))
+        nodes = np.zeros((info.n_nodes, 64), dtype=np.uint8)
+        faces = np.zeros(info.n_tris, dtype=np.int32)
+        check(lib().mcpt_device_fast_hierarchy(self._h, C.byref(info), nodes.ctypes.data_as(C.c_void_p), _p(faces, C.c_int32)))
+        return info, nodes, faces
 
     def set_trace_mode(self, mode):
         """TRACE_FAST (default) or TRACE_REFERENCE: which walk answers closest-hit queries (same results)."""

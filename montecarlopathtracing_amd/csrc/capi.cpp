@@ -118,7 +118,9 @@ struct mcpt_device {
     DNode* nodes = nullptr; DTri* tris = nullptr; DTriShade* shade = nullptr; DMaterial* materials = nullptr;
     DLight* lights = nullptr; DLightTri* light_tris = nullptr; double* light_cdf = nullptr; uint8_t* texels = nullptr;
     FastNode* fast_nodes = nullptr; DTri* fast_tris = nullptr; CwNode* cw_nodes = nullptr; DTriPre* fast_pre = nullptr;
-    size_t n_cw_nodes = 0;          // nodes in cw_nodes when the hierarchy was built on the device
+    size_t n_cw_nodes = 0;          // nodes in cw_nodes
+    size_t n_fast_tris = 0;         // triangle slots in fast_tris
+    mcpt_fast_info fast_info{};     // what mcpt_device_fast_hierarchy reports (builder, clusters, recorded depth and stack need)
     int trace_mode = MCPT_TRACE_FAST;
     int32_t* d_order = nullptr;            // leaf -> .obj face (device build keeps it for read-back)
     mcpt_bvh_info bi{};
@@ -783,6 +785,8 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
             if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy (clustering): ") + hipGetErrorString(e));
             lap("clusters on the GPU");
             if (talk) std::fprintf(stderr, "device create: %d clusters in %d rounds, %d nodes below them, stack need below a cluster root %d\n", n_top, rounds, n_cw, lower_need);
+            d->fast_info.builder = MCPT_FAST_BUILT_DEVICE_PLOC;
+            d->fast_info.clusters = n_top;
             fb.scene_absmax = amax;
             if (n_top == 1) {
                 d->cw_nodes = d_lower;
@@ -815,6 +819,7 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
         if (build_mode != MCPT_BUILD_DEVICE_SAH || ploc_fell_back) {
         hipError_t e = device_build_fast(d->tris, t, blo, bhi, kPerLeaf, kClusterLevels, &d_lower, &d->fast_tris, &n_cw, &levels, &n_top, &top_boxes, &amax, d->stream);
         if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy: ") + hipGetErrorString(e));
+        d->fast_info.builder = ploc_fell_back ? MCPT_FAST_BUILT_PLOC_FELL_BACK : MCPT_FAST_BUILT_DEVICE_FAST;
         fb.scene_absmax = amax;
         if (n_top == 1) {                        // small scene: the GPU's tree is the whole tree
             d->cw_nodes = d_lower;
@@ -848,7 +853,10 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
         if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
         (void)hipFree(d_slots);
         if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("fast triangle gather: ") + hipGetErrorString(e));
+        d->n_cw_nodes = fb_ro.cw.size();
+        d->fast_info.builder = MCPT_FAST_BUILT_HOST;
     }
+    d->n_fast_tris = fast_on_device ? size_t(t) : fb_ro.leaf_tris.size();
     // The pre-test pays where the walk is bound by instruction issue, i.e. where nodes and triangles come out of L1 / L2 / the 256-MB
     // Infinity Cache (cornell-box: 7.38 -> 7.25 ms per k_wf_trace launch; veach-mis and the 204 k-triangle interior alike).  On the
     // 10 M-triangle scene the walk waits for memory, and a second dependent fetch per leaf (48-B record, then the 128-B record of a
@@ -912,10 +920,14 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
     S.fast.stack_limit = kFastShortStack;
     {
         // (any prefix of the node array may be mirrored; the host builder puts the top of the tree there)
-        const size_t n_cw_total = fast_on_device ? d->n_cw_nodes : fb_ro.cw.size();
-        S.fast.cached = int32_t(std::min<size_t>(n_cw_total, size_t(kFastTopNodes)));
+        S.fast.cached = int32_t(std::min<size_t>(d->n_cw_nodes, size_t(kFastTopNodes)));
         if (K.node_cache >= 0 && K.node_cache < S.fast.cached) S.fast.cached = K.node_cache;
     }
+    d->fast_info.n_nodes = int32_t(d->n_cw_nodes);
+    d->fast_info.n_tris = int32_t(d->n_fast_tris);
+    d->fast_info.enabled = S.fast.enabled;
+    d->fast_info.cw_stack_need = fb_ro.cw_stack_need;
+    d->fast_info.max_depth = fb_ro.max_depth;
     if (!K.short_kernel) S.fast.stack_limit = kFastMaxDepth;
     S.fast.stack_cap = S.fast.stack_limit;
     if (K.test_stack_cap >= 4 && K.test_stack_cap < S.fast.stack_cap) S.fast.stack_cap = K.test_stack_cap;
@@ -962,6 +974,22 @@ int mcpt_device_get_leaf_order(mcpt_device* d, int32_t* leaf_to_face)
     if (!d || !leaf_to_face) return fail(MCPT_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(d->ordinal));
     HIP_TRY(hipMemcpy(leaf_to_face, d->d_order, size_t(d->bi.t) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
+
+int mcpt_device_fast_hierarchy(const mcpt_device* d, mcpt_fast_info* info, void* nodes, int32_t* tri_faces)
+{
+    static_assert(sizeof(CwNode) == 64, "mcpt.h documents 64-byte node records");
+    if (!d || !info) return fail(MCPT_ERR_ARG, "null argument");
+    *info = d->fast_info;
+    if (!nodes && !tri_faces) return MCPT_OK;
+    HIP_TRY(hipSetDevice(d->ordinal));
+    if (nodes && d->n_cw_nodes) HIP_TRY(hipMemcpy(nodes, d->cw_nodes, d->n_cw_nodes * sizeof(CwNode), hipMemcpyDeviceToHost));
+    if (tri_faces && d->n_fast_tris) {
+        std::vector<DTri> tris(d->n_fast_tris);
+        HIP_TRY(hipMemcpy(tris.data(), d->fast_tris, d->n_fast_tris * sizeof(DTri), hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < tris.size(); k++) tri_faces[k] = tris[k].face;
+    }
     return MCPT_OK;
 }
 
