@@ -118,9 +118,7 @@ struct mcpt_device {
     DNode* nodes = nullptr; DTri* tris = nullptr; DTriShade* shade = nullptr; DMaterial* materials = nullptr;
     DLight* lights = nullptr; DLightTri* light_tris = nullptr; double* light_cdf = nullptr; uint8_t* texels = nullptr;
     FastNode* fast_nodes = nullptr; DTri* fast_tris = nullptr; CwNode* cw_nodes = nullptr; DTriPre* fast_pre = nullptr;
-    size_t n_cw_nodes = 0;          // nodes in cw_nodes
-    size_t n_fast_tris = 0;         // triangle slots in fast_tris
-    mcpt_fast_info fast_info{};     // what mcpt_device_fast_hierarchy reports (builder, clusters, recorded depth and stack need)
+    mcpt_fast_info fast_info{};     // what mcpt_device_fast_hierarchy reports (node and triangle slot counts, builder, clusters, depth, stack need)
     int trace_mode = MCPT_TRACE_FAST;
     int32_t* d_order = nullptr;            // leaf -> .obj face (device build keeps it for read-back)
     mcpt_bvh_info bi{};
@@ -593,63 +591,41 @@ int mcpt_device_create(const mcpt_scene* h, int32_t ordinal, mcpt_device** out)
     return mcpt_device_create_ex(h, ordinal, (h && !h->s.accel_built) ? MCPT_BUILD_DEVICE : MCPT_BUILD_HOST, out);
 }
 
-int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mode, mcpt_device** out)
-{
-    if (!h || !out) return fail(MCPT_ERR_ARG, "null argument");
-    *out = nullptr;
-    if (build_mode != MCPT_BUILD_HOST && build_mode != MCPT_BUILD_DEVICE && build_mode != MCPT_BUILD_DEVICE_FAST && build_mode != MCPT_BUILD_DEVICE_SAH)
-        return fail(MCPT_ERR_ARG, "bad build mode");
-    const Scene& s = h->s;
-    if (build_mode == MCPT_BUILD_HOST && !s.accel_built) return fail(MCPT_ERR_ARG, "scene has no host build; use MCPT_BUILD_DEVICE");
-    int ndev = mcpt_device_count();
-    if (ndev <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
-    if (const int gate = runtime_gate()) return gate;          // kernels of one hipcc on another release's runtime: refused
-    if (ordinal < 0 || ordinal >= ndev) return fail(MCPT_ERR_NO_DEVICE, "device ordinal out of range");
-    HIP_TRY(hipSetDevice(ordinal));
-    std::unique_ptr<mcpt_device, void (*)(mcpt_device*)> d(new mcpt_device, mcpt_device_free);
-    d->ordinal = ordinal;
-    d->knobs = read_knobs();
-    const Knobs& K = d->knobs;
-    HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    for (auto& e : d->ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipStreamCreateWithFlags(&d->look_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&d->look_ev, hipEventDisableTiming));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d->h_look), 64, hipHostMallocDefault));
+// ------------------------------------------------------------------------------------------------ device creation, stage by stage
+// Each stage writes into d and returns an MCPT_* code.  Whatever it allocates is in a d-> field by the time it returns, so the
+// caller's mcpt_device_free releases it when a later stage fails; temporaries are freed where they are made.
 
-    const int t = int(s.faces.size());
-    const mcpt_bvh_info bi = bvh_shape(t);
-    d->bi = bi;
+// MCPT_PRINT_DIAG on a large scene: how far device creation has come, and when
+struct CreateClock {
+    bool talk; std::chrono::steady_clock::time_point t0;
+    void lap(const char* what) const { if (talk) std::fprintf(stderr, "device create: %s at %.2f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()); }
+};
+static void put3(double* o, const Vec3& v) { o[0] = v.x; o[1] = v.y; o[2] = v.z; }
+
+// The reference's structures in HBM -- uploaded from the host build (MCPT_BUILD_HOST) or built on the GPU (the other modes) -- and
+// the leaf order (leaf -> .obj face) either way
+static int create_reference(mcpt_device* d, const Scene& s, int32_t build_mode, const CreateClock& clock, std::vector<int32_t>& order)
+{
+    const mcpt_bvh_info& bi = d->bi;
+    const int t = bi.t;
     int rc;
-    const bool talk = K.print_diag && t >= (1 << 17);
-    const auto t_create = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (talk) std::fprintf(stderr, "device create: %s at %.2f s\n", what, std::chrono::duration<double>(std::chrono::steady_clock::now() - t_create).count());
-    };
-    std::vector<int32_t> order;                     // leaf -> .obj face
-    const bool fast_on_device = build_mode == MCPT_BUILD_DEVICE_FAST || build_mode == MCPT_BUILD_DEVICE_SAH;
     if (build_mode == MCPT_BUILD_HOST) {
-        std::vector<DNode> nodes(bi.Nr);
+        std::vector<DNode> nodes(bi.Nr);             // (records filled in place: the vectors zero them first)
         for (int i = 0; i < bi.Nr; i++) {
             const NodeBox& b = s.nodes[i];
-            DNode n{};
+            DNode& n = nodes[i];
             n.mn[0] = b.min_x; n.mn[1] = b.min_y; n.mn[2] = b.min_z; n.mx[0] = b.max_x; n.mx[1] = b.max_y; n.mx[2] = b.max_z;
-            nodes[i] = n;
         }
         std::vector<DTri> tris(t);
         std::vector<DTriShade> shade(t);
         for (int k = 0; k < t; k++) {
             const FaceRec& f = s.faces[s.order[k]];
-            DTri q{};
-            DTriShade a{};
-            const Vec3* vs[3] = {&f.v[0], &f.v[1], &f.v[2]};
-            double* dst[3] = {q.v1, q.v2, q.v3};
-            for (int c = 0; c < 3; c++) { dst[c][0] = vs[c]->x; dst[c][1] = vs[c]->y; dst[c][2] = vs[c]->z; }
-            q.n[0] = f.nrm.x; q.n[1] = f.nrm.y; q.n[2] = f.nrm.z;
+            DTri& q = tris[k];
+            DTriShade& a = shade[k];
+            double *v[3] = {q.v1, q.v2, q.v3}, *vn[3] = {a.vn1, a.vn2, a.vn3}, *vt[3] = {a.vt1, a.vt2, a.vt3};
+            for (int c = 0; c < 3; c++) { put3(v[c], f.v[c]); put3(vn[c], f.vn[c]); vt[c][0] = f.vt[c][0]; vt[c][1] = f.vt[c][1]; }
+            put3(q.n, f.nrm);
             q.material = f.material; q.face = s.order[k]; q.leaf = k;
-            double* nd[3] = {a.vn1, a.vn2, a.vn3};
-            for (int c = 0; c < 3; c++) { nd[c][0] = f.vn[c].x; nd[c][1] = f.vn[c].y; nd[c][2] = f.vn[c].z; }
-            a.vt1[0] = f.vt[0][0]; a.vt1[1] = f.vt[0][1]; a.vt2[0] = f.vt[1][0]; a.vt2[1] = f.vt[1][1]; a.vt3[0] = f.vt[2][0]; a.vt3[1] = f.vt[2][1];
-            tris[k] = q; shade[k] = a;
         }
         order = s.order;
         if ((rc = upload(nodes, &d->nodes)) || (rc = upload(tris, &d->tris)) || (rc = upload(shade, &d->shade)) || (rc = upload(order, &d->d_order)))
@@ -663,15 +639,14 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
         for (long long i = ib; i < ie; i++) {
             const FaceRec& f = s.faces[size_t(i)];
             for (int c = 0; c < 3; c++) {
-                v9[size_t(i) * 9 + c * 3] = f.v[c].x; v9[size_t(i) * 9 + c * 3 + 1] = f.v[c].y; v9[size_t(i) * 9 + c * 3 + 2] = f.v[c].z;
-                vn9[size_t(i) * 9 + c * 3] = f.vn[c].x; vn9[size_t(i) * 9 + c * 3 + 1] = f.vn[c].y; vn9[size_t(i) * 9 + c * 3 + 2] = f.vn[c].z;
+                put3(&v9[size_t(i) * 9 + c * 3], f.v[c]); put3(&vn9[size_t(i) * 9 + c * 3], f.vn[c]);
                 vt6[size_t(i) * 6 + c * 2] = f.vt[c][0]; vt6[size_t(i) * 6 + c * 2 + 1] = f.vt[c][1];
             }
-            nrm3[size_t(i) * 3] = f.nrm.x; nrm3[size_t(i) * 3 + 1] = f.nrm.y; nrm3[size_t(i) * 3 + 2] = f.nrm.z;
+            put3(&nrm3[size_t(i) * 3], f.nrm);
             mat[size_t(i)] = f.material;
         }
         });
-        lap("faces staged");
+        clock.lap("faces staged");
         double *d_v9 = nullptr, *d_vn9 = nullptr, *d_vt6 = nullptr, *d_nrm3 = nullptr;
         int32_t* d_mat = nullptr;
         auto drop = [&]() { (void)hipFree(d_v9); (void)hipFree(d_vn9); (void)hipFree(d_vt6); (void)hipFree(d_nrm3); (void)hipFree(d_mat); };
@@ -690,18 +665,22 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
         drop();
         if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build: ") + hipGetErrorString(e));
     }
+    clock.lap("reference structures in HBM");
+    return MCPT_OK;
+}
 
-    lap("reference structures in HBM");
+// materials and their texels, lights, light triangles and their CDF
+static int create_materials_and_lights(mcpt_device* d, const Scene& s)
+{
     std::vector<uint8_t> texels;
     std::vector<DMaterial> mats(s.materials.size());
     for (size_t i = 0; i < s.materials.size(); i++) {
         const MaterialRec& m = s.materials[i];
-        DMaterial dm{};
-        dm.kd[0] = m.kd.x; dm.kd[1] = m.kd.y; dm.kd[2] = m.kd.z; dm.ks[0] = m.ks.x; dm.ks[1] = m.ks.y; dm.ks[2] = m.ks.z;
+        DMaterial& dm = mats[i];
+        put3(dm.kd, m.kd); put3(dm.ks, m.ks);
         dm.Ns = m.Ns; dm.Ni = m.Ni; dm.has_map = m.has_map; dm.map_w = m.map_w; dm.map_h = m.map_h; dm.light = m.light;
         dm.tex_offset = int64_t(texels.size());
         texels.insert(texels.end(), m.bgr.begin(), m.bgr.end());
-        mats[i] = dm;
     }
     std::vector<DLight> lights(s.lights.size());
     std::vector<DLightTri> ltris;
@@ -709,179 +688,178 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
     for (size_t i = 0; i < s.lights.size(); i++) {
         const LightRec& l = s.lights[i];
         const MaterialRec& m = s.materials[l.material];
-        DLight dl{};
-        dl.radiance[0] = l.radiance.x; dl.radiance[1] = l.radiance.y; dl.radiance[2] = l.radiance.z;
+        DLight& dl = lights[i];
+        put3(dl.radiance, l.radiance);
         dl.total_area = l.total_area; dl.material = l.material; dl.ntri = int32_t(m.faces.size());
         dl.first = int32_t(ltris.size()); dl.cdf_sorted = l.cdf_sorted ? 1 : 0;
         for (size_t j = 0; j < m.faces.size(); j++) {
             const FaceRec& f = s.faces[m.faces[j]];
             DLightTri q{};
-            double* pv[3] = {q.v1, q.v2, q.v3};
-            double* pn[3] = {q.vn1, q.vn2, q.vn3};
-            for (int c = 0; c < 3; c++) {
-                pv[c][0] = f.v[c].x; pv[c][1] = f.v[c].y; pv[c][2] = f.v[c].z;
-                pn[c][0] = f.vn[c].x; pn[c][1] = f.vn[c].y; pn[c][2] = f.vn[c].z;
-            }
+            double *v[3] = {q.v1, q.v2, q.v3}, *vn[3] = {q.vn1, q.vn2, q.vn3};
+            for (int c = 0; c < 3; c++) { put3(v[c], f.v[c]); put3(vn[c], f.vn[c]); }
             ltris.push_back(q);
             lcdf.push_back(l.cdf[j]);
         }
-        lights[i] = dl;
     }
-    if ((rc = upload(mats, &d->materials)) || (rc = upload(lights, &d->lights)) || (rc = upload(ltris, &d->light_tris)) ||
-        (rc = upload(lcdf, &d->light_cdf)) || (rc = upload(texels, &d->texels)))
+    int rc;
+    if ((rc = upload(mats, &d->materials)) || (rc = upload(lights, &d->lights)) || (rc = upload(ltris, &d->light_tris)) || (rc = upload(lcdf, &d->light_cdf)))
         return rc;
+    return upload(texels, &d->texels);
+}
 
-    // result-identical fast structure: SAH hierarchy built on the host from the leaf order (accel_build.cpp), permuted triangle
-    // copy gathered on the GPU -- or, MCPT_BUILD_DEVICE_FAST, a 4-wide tree over the Morton order built on the GPU in place
-    std::shared_ptr<const FastBvh> fb_host;
-    if (!fast_on_device) { fb_host = shared_fast_bvh(h, order, K); lap("culling hierarchy on the host"); }
-    FastBvh fb_dev;                              // MCPT_BUILD_DEVICE_FAST: shape figures of the hierarchy built on this GPU
-    const FastBvh& fb_ro = fast_on_device ? fb_dev : *fb_host;
-    FastBvh& fb = fb_dev;
-    bool coords_ok = true;                       // every coordinate zero or within [1e-150, 1e150]
-    for (const FaceRec& f : s.faces)
-        for (int c = 0; c < 3; c++)
-            for (double v : {f.v[c].x, f.v[c].y, f.v[c].z}) {
-                const double a = std::fabs(v);
-                if (!(a == 0.0 || (a >= 1e-150 && a <= 1e150))) coords_ok = false;
+// The whole hierarchy from the n_lower nodes a GPU builder left in d_lower.  n_top == 1: they are the whole tree.  Otherwise they
+// are a forest of n_top clusters: the host's SAH tree over the clusters' boxes goes in front of them, and d_lower is freed.
+// roots[c] = lower node of cluster c's root, < 0: the cluster is one leaf and this is its reference; null: cluster c's root is
+// lower node c.  lower_need / lower_depth = stack entries / inner levels a walk below a cluster root may take.
+static int stitch_clusters(mcpt_device* d, CwNode* d_lower, int n_lower, int n_top, const std::vector<double>& top_boxes, const int32_t* roots,
+                           int lower_need, int lower_depth)
+{
+    mcpt_fast_info& fi = d->fast_info;
+    if (n_top == 1) {                        // small scene: the GPU's tree is the whole tree
+        d->cw_nodes = d_lower;
+        fi.n_nodes = n_lower; fi.max_depth = lower_depth; fi.cw_stack_need = lower_need;
+        return MCPT_OK;
+    }
+    FastBvh up;
+    build_fast_upper(top_boxes.data(), n_top, lower_need, up);
+    const int n_up = int(up.cw.size());
+    for (CwNode& nd : up.cw)
+        for (int c = 0; c < 4; c++)
+            if (nd.child[c] < 0 && nd.child[c] != kFastEmpty) {            // cluster -> its root node, or its triangles if it is one leaf
+                const int cluster = -1 - nd.child[c];
+                const int32_t r = roots ? roots[cluster] : cluster;
+                nd.child[c] = r >= 0 ? n_up + r : r;
             }
-    if (fast_on_device) {
-        int n_cw = 0, levels = 0;
-        double amax = 0;
-        double blo[3] = {1e300, 1e300, 1e300}, bhi[3] = {-1e300, -1e300, -1e300};
-        for (const FaceRec& f : s.faces)
-            for (int c = 0; c < 3; c++) {
-                const double q[3] = {f.v[c].x, f.v[c].y, f.v[c].z};
-                for (int a = 0; a < 3; a++) { if (q[a] < blo[a]) blo[a] = q[a]; if (q[a] > bhi[a]) bhi[a] = q[a]; }
-            }
-        // Clusters of Morton-consecutive triangles on the GPU (by default one compressed node over four single-triangle leaves:
-        // every triangle keeps its own quantised box), a SAH tree over the clusters' boxes on the host.  Sweep on MI355X
-        // (MCPT_CLUSTER_LEAF x MCPT_CLUSTER_LEVELS, ms per frame synthetic 10 M SPP 16 / cornell-box): 1x1 87 / 143, 1x2 93 / 161,
-        // 1x3 103 / 182, 2x1 116 / 177, 4x2 163 / 238; the host's full SAH tree: 56 / 110.
-        const int kPerLeaf = K.cluster_leaf, kClusterLevels = K.cluster_levels;
-        CwNode* d_lower = nullptr;
-        int n_top = 0;
-        std::vector<double> top_boxes;
-        bool ploc_fell_back = false;
-        if (build_mode == MCPT_BUILD_DEVICE_SAH) {
-            // clusters grown by locally-ordered clustering on the GPU (build_kernels.hip: device_build_ploc), the host's SAH tree over them
-            const int kCluster = K.ploc_cluster, kHeightEnv = K.ploc_height;
-            // how tall a cluster may grow: what the walk's stack leaves once the tree over the expected number of clusters has its levels
-            int kHeight = kHeightEnv;
-            if (!kHeight) {
-                const long long est = std::max<long long>(1, 2ll * t / kCluster);
-                int lv = 1;
-                while ((1ll << lv) < est) lv++;
-                kHeight = std::max(6, std::min(20, 35 - 5 - lv));
-            }
-            const int kRadius = K.ploc_radius, kLeaf = K.ploc_leaf ? K.ploc_leaf : kFastDefaultLeaf, kBudget = K.ploc_budget;
-            const double kAreaDen = K.ploc_area, kCt = K.ploc_ct, kCl = K.ploc_cl;
-            std::vector<int32_t> top_roots;
-            int lower_need = 0, rounds = 0;
-            hipError_t e = device_build_ploc(d->tris, t, blo, bhi, kCluster, kHeight, kRadius, kLeaf, kAreaDen > 0 ? 1.0 / kAreaDen : 0.0, kCt, kCl, kBudget, &d_lower, &d->fast_tris, &n_cw, &n_top, &top_boxes,
-                                             &top_roots, &lower_need, &amax, &rounds, d->stream);
-            if (e == hipErrorNotSupported) ploc_fell_back = true;
-            else {
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d->cw_nodes), size_t(n_up + n_lower) * sizeof(CwNode));
+    if (e == hipSuccess) e = hipMemcpy(d->cw_nodes, up.cw.data(), size_t(n_up) * sizeof(CwNode), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpyAsync(d->cw_nodes + n_up, d_lower, size_t(n_lower) * sizeof(CwNode), hipMemcpyDeviceToDevice, d->stream);
+    if (e == hipSuccess) e = device_offset_children(d->cw_nodes + n_up, n_lower, n_up, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    (void)hipFree(d_lower);
+    if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy: ") + hipGetErrorString(e));
+    fi.n_nodes = int32_t(n_up + n_lower); fi.max_depth = up.max_depth + lower_depth;
+    fi.cw_stack_need = up.cw_stack_need;     // includes lower_need
+    return MCPT_OK;
+}
+
+// MCPT_BUILD_DEVICE_FAST / MCPT_BUILD_DEVICE_SAH: the lower part of the hierarchy built on the GPU in place over the leaf-ordered
+// triangles, the host's tree over its clusters.  PLOC (MCPT_BUILD_DEVICE_SAH) that leaves too many clusters falls back to Morton.
+static int build_hierarchy_on_device(mcpt_device* d, const double lo[3], const double hi[3], bool ploc, const CreateClock& clock, double* absmax)
+{
+    const Knobs& K = d->knobs;
+    const int t = d->bi.t;
+    d->fast_info.n_tris = t;
+    CwNode* d_lower = nullptr;
+    int n_lower = 0, n_top = 0;
+    std::vector<double> top_boxes;
+    if (ploc) {
+        // clusters grown by locally-ordered clustering on the GPU (build_kernels.hip: device_build_ploc), the host's SAH tree over them;
+        // how tall a cluster may grow: what the walk's stack leaves once the tree over the expected number of clusters has its levels
+        int height = K.ploc_height;
+        if (!height) {
+            const long long est = std::max<long long>(1, 2ll * t / K.ploc_cluster);
+            int lv = 1;
+            while ((1ll << lv) < est) lv++;
+            height = std::max(6, std::min(20, 35 - 5 - lv));
+        }
+        std::vector<int32_t> top_roots;
+        int lower_need = 0, rounds = 0;
+        const hipError_t e = device_build_ploc(d->tris, t, lo, hi, K.ploc_cluster, height, K.ploc_radius, K.ploc_leaf ? K.ploc_leaf : kFastDefaultLeaf,
+                                               K.ploc_area > 0 ? 1.0 / K.ploc_area : 0.0, K.ploc_ct, K.ploc_cl, K.ploc_budget, &d_lower, &d->fast_tris, &n_lower,
+                                               &n_top, &top_boxes, &top_roots, &lower_need, absmax, &rounds, d->stream);
+        if (e != hipErrorNotSupported) {
             if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy (clustering): ") + hipGetErrorString(e));
-            lap("clusters on the GPU");
-            if (talk) std::fprintf(stderr, "device create: %d clusters in %d rounds, %d nodes below them, stack need below a cluster root %d\n", n_top, rounds, n_cw, lower_need);
+            clock.lap("clusters on the GPU");
+            if (clock.talk) std::fprintf(stderr, "device create: %d clusters in %d rounds, %d nodes below them, stack need below a cluster root %d\n", n_top, rounds, n_lower, lower_need);
             d->fast_info.builder = MCPT_FAST_BUILT_DEVICE_PLOC;
             d->fast_info.clusters = n_top;
-            fb.scene_absmax = amax;
-            if (n_top == 1) {
-                d->cw_nodes = d_lower;
-                d->n_cw_nodes = size_t(n_cw);
-                fb.max_depth = lower_need;
-                fb.cw_stack_need = lower_need;
-            } else {
-                FastBvh up;
-                build_fast_upper(top_boxes.data(), n_top, lower_need, up);
-                const int n_up = int(up.cw.size());
-                for (CwNode& nd : up.cw)
-                    for (int c = 0; c < 4; c++)
-                        if (nd.child[c] < 0 && nd.child[c] != kFastEmpty) {            // cluster -> its root node, or its triangles if it is one leaf
-                            const int32_t r = top_roots[size_t(-1 - nd.child[c])];
-                            nd.child[c] = r >= 0 ? n_up + r : r;
-                        }
-                e = hipMalloc(reinterpret_cast<void**>(&d->cw_nodes), size_t(n_up + n_cw) * sizeof(CwNode));
-                if (e == hipSuccess) e = hipMemcpy(d->cw_nodes, up.cw.data(), size_t(n_up) * sizeof(CwNode), hipMemcpyHostToDevice);
-                if (e == hipSuccess) e = hipMemcpyAsync(d->cw_nodes + n_up, d_lower, size_t(n_cw) * sizeof(CwNode), hipMemcpyDeviceToDevice, d->stream);
-                if (e == hipSuccess) e = device_offset_children(d->cw_nodes + n_up, n_cw, n_up, d->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-                (void)hipFree(d_lower);
-                if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy: ") + hipGetErrorString(e));
-                d->n_cw_nodes = size_t(n_up) + size_t(n_cw);
-                fb.max_depth = up.max_depth + lower_need;
-                fb.cw_stack_need = up.cw_stack_need;             // includes lower_need
+            return stitch_clusters(d, d_lower, n_lower, n_top, top_boxes, top_roots.data(), lower_need, lower_need);
+        }
+    }
+    // Clusters of Morton-consecutive triangles on the GPU (by default one compressed node over four single-triangle leaves:
+    // every triangle keeps its own quantised box), a SAH tree over the clusters' boxes on the host.  Sweep on MI355X
+    // (MCPT_CLUSTER_LEAF x MCPT_CLUSTER_LEVELS, ms per frame synthetic 10 M SPP 16 / cornell-box): 1x1 87 / 143, 1x2 93 / 161,
+    // 1x3 103 / 182, 2x1 116 / 177, 4x2 163 / 238; the host's full SAH tree: 56 / 110.
+    int levels = 0;
+    const hipError_t e = device_build_fast(d->tris, t, lo, hi, K.cluster_leaf, K.cluster_levels, &d_lower, &d->fast_tris, &n_lower, &levels, &n_top, &top_boxes,
+                                           absmax, d->stream);
+    if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy: ") + hipGetErrorString(e));
+    d->fast_info.builder = ploc ? MCPT_FAST_BUILT_PLOC_FELL_BACK : MCPT_FAST_BUILT_DEVICE_FAST;
+    return stitch_clusters(d, d_lower, n_lower, n_top, top_boxes, nullptr, 3 * levels, levels);   // three siblings pushed per level on the way down
+}
+
+// The fast walk's culling hierarchy: fills d->cw_nodes, d->fast_tris and d->fast_info; *absmax = largest |coordinate| of the scene
+static int create_hierarchy(mcpt_device* d, const mcpt_scene* h, int32_t build_mode, const std::vector<int32_t>& order, const CreateClock& clock, double* absmax)
+{
+    // one pass over the faces: the scene's bounds, which the GPU builders sort on (a NaN coordinate passes neither comparison), and
+    // whether every coordinate is zero or within [1e-150, 1e150], as the fast walk needs (NaN and infinities are not)
+    bool coords_ok = true;
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    for (const FaceRec& f : h->s.faces)
+        for (int c = 0; c < 3; c++) {
+            const double q[3] = {f.v[c].x, f.v[c].y, f.v[c].z};
+            for (int a = 0; a < 3; a++) {
+                const double m = std::fabs(q[a]);
+                if (!(m == 0.0 || (m >= 1e-150 && m <= 1e150))) coords_ok = false;
+                if (q[a] < lo[a]) lo[a] = q[a];
+                if (q[a] > hi[a]) hi[a] = q[a];
             }
-            }
         }
-        if (build_mode != MCPT_BUILD_DEVICE_SAH || ploc_fell_back) {
-        hipError_t e = device_build_fast(d->tris, t, blo, bhi, kPerLeaf, kClusterLevels, &d_lower, &d->fast_tris, &n_cw, &levels, &n_top, &top_boxes, &amax, d->stream);
-        if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy: ") + hipGetErrorString(e));
-        d->fast_info.builder = ploc_fell_back ? MCPT_FAST_BUILT_PLOC_FELL_BACK : MCPT_FAST_BUILT_DEVICE_FAST;
-        fb.scene_absmax = amax;
-        if (n_top == 1) {                        // small scene: the GPU's tree is the whole tree
-            d->cw_nodes = d_lower;
-            d->n_cw_nodes = size_t(n_cw);
-            fb.max_depth = levels;
-            fb.cw_stack_need = 3 * levels;       // three siblings pushed per level on the way down
-        } else {
-            FastBvh up;
-            build_fast_upper(top_boxes.data(), n_top, 3 * levels, up);
-            const int n_up = int(up.cw.size());
-            for (CwNode& nd : up.cw)
-                for (int c = 0; c < 4; c++)
-                    if (nd.child[c] < 0 && nd.child[c] != kFastEmpty) nd.child[c] = n_up + (-1 - nd.child[c]);   // cluster -> its root node
-            e = hipMalloc(reinterpret_cast<void**>(&d->cw_nodes), size_t(n_up + n_cw) * sizeof(CwNode));
-            if (e == hipSuccess) e = hipMemcpy(d->cw_nodes, up.cw.data(), size_t(n_up) * sizeof(CwNode), hipMemcpyHostToDevice);
-            if (e == hipSuccess) e = hipMemcpyAsync(d->cw_nodes + n_up, d_lower, size_t(n_cw) * sizeof(CwNode), hipMemcpyDeviceToDevice, d->stream);
-            if (e == hipSuccess) e = device_offset_children(d->cw_nodes + n_up, n_cw, n_up, d->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-            (void)hipFree(d_lower);
-            if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy: ") + hipGetErrorString(e));
-            d->n_cw_nodes = size_t(n_up) + size_t(n_cw);
-            fb.max_depth = up.max_depth + levels;
-            fb.cw_stack_need = up.cw_stack_need;             // includes the clusters' 3 * levels
-        }
-        }
+    mcpt_fast_info& fi = d->fast_info;
+    if (build_mode == MCPT_BUILD_DEVICE_FAST || build_mode == MCPT_BUILD_DEVICE_SAH) {
+        if (const int rc = build_hierarchy_on_device(d, lo, hi, build_mode == MCPT_BUILD_DEVICE_SAH, clock, absmax)) return rc;
     } else {
+        // the SAH hierarchy built on the host from the leaf order (accel_build.cpp, shared by every device of the scene), its
+        // permuted triangle copy gathered on the GPU
+        const std::shared_ptr<const FastBvh> fb = shared_fast_bvh(h, order, d->knobs);
+        clock.lap("culling hierarchy on the host");
         int32_t* d_slots = nullptr;
-        if ((rc = upload(fb_ro.cw, &d->cw_nodes)) || (rc = upload(fb_ro.leaf_tris, &d_slots))) { (void)hipFree(d_slots); return rc; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d->fast_tris), std::max<size_t>(fb_ro.leaf_tris.size(), 1) * sizeof(DTri));
-        if (e == hipSuccess) e = device_gather_tris(d->tris, d_slots, int(fb_ro.leaf_tris.size()), d->fast_tris, d->stream);
+        int rc;
+        if ((rc = upload(fb->cw, &d->cw_nodes)) || (rc = upload(fb->leaf_tris, &d_slots))) { (void)hipFree(d_slots); return rc; }
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d->fast_tris), std::max<size_t>(fb->leaf_tris.size(), 1) * sizeof(DTri));
+        if (e == hipSuccess) e = device_gather_tris(d->tris, d_slots, int(fb->leaf_tris.size()), d->fast_tris, d->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
         (void)hipFree(d_slots);
         if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("fast triangle gather: ") + hipGetErrorString(e));
-        d->n_cw_nodes = fb_ro.cw.size();
-        d->fast_info.builder = MCPT_FAST_BUILT_HOST;
+        fi.builder = MCPT_FAST_BUILT_HOST;
+        fi.n_nodes = int32_t(fb->cw.size()); fi.n_tris = int32_t(fb->leaf_tris.size());
+        fi.max_depth = fb->max_depth; fi.cw_stack_need = fb->cw_stack_need;
+        *absmax = fb->scene_absmax;
     }
-    d->n_fast_tris = fast_on_device ? size_t(t) : fb_ro.leaf_tris.size();
-    // The pre-test pays where the walk is bound by instruction issue, i.e. where nodes and triangles come out of L1 / L2 / the 256-MB
-    // Infinity Cache (cornell-box: 7.38 -> 7.25 ms per k_wf_trace launch; veach-mis and the 204 k-triangle interior alike).  On the
-    // 10 M-triangle scene the walk waits for memory, and a second dependent fetch per leaf (48-B record, then the 128-B record of a
-    // survivor) costs more than the skipped arithmetic saves: 6.90 vs 6.44 ms per launch.  So: records only for scenes of at most
-    // MCPT_PRE_TEST_MAX_TRIS triangles (default 2^20: ~200 B per triangle of nodes, records and triangles stay cache-resident).
-    const long long pre_max = K.pre_test_max_tris;
-    if (t <= pre_max) {
-        // fp32 records of the triangle phase's pre-test, one per slot of the fast triangle array
-        const int n_slots = fast_on_device ? t : int(fb_ro.leaf_tris.size());
-        // (four records of padding: the pre-test reads its triangles in rounds of up to four slots, used or not)
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d->fast_pre), (size_t(n_slots) + 4) * sizeof(DTriPre));
-        if (e == hipSuccess) e = hipMemsetAsync(d->fast_pre + n_slots, 0, 4 * sizeof(DTriPre), d->stream);
-        if (e == hipSuccess) e = device_build_pre(d->fast_tris, n_slots, fb_ro.scene_absmax, d->fast_pre, d->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-        if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("pre-test records: ") + hipGetErrorString(e));
-    }
-    lap("culling hierarchy in HBM");
+    fi.enabled = (coords_ok && fi.max_depth < kFastMaxDepth && fi.cw_stack_need < kFastMaxDepth && *absmax >= 1e-15 && *absmax <= 1e15) ? 1 : 0;
+    return MCPT_OK;
+}
+
+// The pre-test pays where the walk is bound by instruction issue, i.e. where nodes and triangles come out of L1 / L2 / the 256-MB
+// Infinity Cache (cornell-box: 7.38 -> 7.25 ms per k_wf_trace launch; veach-mis and the 204 k-triangle interior alike).  On the
+// 10 M-triangle scene the walk waits for memory, and a second dependent fetch per leaf (48-B record, then the 128-B record of a
+// survivor) costs more than the skipped arithmetic saves: 6.90 vs 6.44 ms per launch.  So: records only for scenes of at most
+// MCPT_PRE_TEST_MAX_TRIS triangles (default 2^20: ~200 B per triangle of nodes, records and triangles stay cache-resident).
+static int create_pre_test(mcpt_device* d, double absmax)
+{
+    if (d->bi.t > d->knobs.pre_test_max_tris) return MCPT_OK;
+    // fp32 records of the triangle phase's pre-test, one per slot of the fast triangle array
+    const int n_slots = d->fast_info.n_tris;
+    // (four records of padding: the pre-test reads its triangles in rounds of up to four slots, used or not)
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d->fast_pre), (size_t(n_slots) + 4) * sizeof(DTriPre));
+    if (e == hipSuccess) e = hipMemsetAsync(d->fast_pre + n_slots, 0, 4 * sizeof(DTriPre), d->stream);
+    if (e == hipSuccess) e = device_build_pre(d->fast_tris, n_slots, absmax, d->fast_pre, d->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("pre-test records: ") + hipGetErrorString(e));
+    return MCPT_OK;
+}
+
+// engine choice, frame slots, auxiliary buffers of the closest-hit entry points, finishing threshold and workspace budget
+static int create_workspaces(mcpt_device* d, const Scene& s)
+{
+    const Knobs& K = d->knobs;
     if (K.slow_list) d->slow_cap = unsigned(K.slow_list);   // tests shrink it to force the overflow path
     init_launch_cfg(d->cfg, K.logic_grid, K.trace_block_rays, K.trace_min_chunk, K.trace_max_chunk);
-    d->cfg.trace_pool = trace_engine_for(t, K) == MCPT_ENGINE_POOL ? 1 : 0;
+    d->cfg.trace_pool = trace_engine_for(d->bi.t, K) == MCPT_ENGINE_POOL ? 1 : 0;
     // the pool engine keeps the stack entries of a ray beyond those it has in LDS in an area behind the deferred-ray list of the launch
     const size_t spill_bytes = d->cfg.trace_pool ? pool_spill_bytes(d->cfg.cus) : 0;
     // ... and finishes a frame's last paths in path mode (MCPT_FINISH_ENGINE=lane: the one-lane-per-path kernel, for A/B runs)
-    d->cfg.finish_pool = d->cfg.trace_pool;
-    if (K.finish_engine == 0) d->cfg.finish_pool = 0;
+    d->cfg.finish_pool = K.finish_engine == 0 ? 0 : d->cfg.trace_pool;
     const size_t path_bytes = d->cfg.finish_pool ? finish_pool_bytes(d->cfg.cus, int(s.lights.size())) : 0;     // (0: a path's rays do not fit a lane's slots)
     if (!path_bytes) d->cfg.finish_pool = 0;
     for (auto& f : d->slot) {
@@ -900,45 +878,75 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
     // paths left at which the finishing pass takes over: the pool form holds the wavefront kernels' pace further up (sweep on one eighth of
     // the headline frame, ms: 250 k 14.2, 500 k 13.3, 1 M 13.1, 2 M 13.0, 4 M 13.5, 8 M 14.8; whole frame 81.0 / 80.3 at 500 k / 2 M), the
     // one-lane-per-path form is flat from 2e5 to 1e6
-    d->finish_threshold = path_bytes ? 1500000 : 500000;
-    if (K.finish_paths >= 0) d->finish_threshold = K.finish_paths;
+    d->finish_threshold = K.finish_paths >= 0 ? K.finish_paths : path_bytes ? 1500000 : 500000;
     if (K.workspace_gb > 0) d->wf_budget_bytes = size_t(K.workspace_gb * double(size_t(1) << 30));
+    return MCPT_OK;
+}
 
+// the kernels' view of the scene (DScene), the camera and the primary directions' buffer
+static int create_dscene(mcpt_device* d, const Scene& s, double absmax)
+{
+    const Knobs& K = d->knobs;
+    const mcpt_bvh_info& bi = d->bi;
     DScene& S = d->ds;
     S.nodes = d->nodes; S.tris = d->tris; S.shade = d->shade; S.materials = d->materials; S.lights = d->lights;
     S.light_tris = d->light_tris; S.light_cdf = d->light_cdf; S.texels = d->texels;
-    S.t = t; S.Lv = bi.Lv; S.Level = bi.Level; S.Nr = bi.Nr;
+    S.t = bi.t; S.Lv = bi.Lv; S.Level = bi.Level; S.Nr = bi.Nr;
     S.num_lights = int32_t(s.lights.size()); S.num_materials = int32_t(s.materials.size());
     S.area0 = s.area0;
-    S.fast.cw = d->cw_nodes; S.fast.nodes = nullptr; S.fast.tris = d->fast_tris; S.fast.pre = d->fast_pre; S.fast.absmax = fb_ro.scene_absmax;
-    S.fast.enabled = (coords_ok && fb_ro.max_depth < kFastMaxDepth && fb_ro.cw_stack_need < kFastMaxDepth && fb_ro.scene_absmax >= 1e-15 &&
-                      fb_ro.scene_absmax <= 1e15) ? 1 : 0;
+    S.fast.cw = d->cw_nodes; S.fast.nodes = nullptr; S.fast.tris = d->fast_tris; S.fast.pre = d->fast_pre; S.fast.absmax = absmax;
+    S.fast.enabled = d->fast_info.enabled;
     // Which shape of the trace engine walks it (wavefront.hip): by default the short-stack one at 4 waves per SIMD -- the hierarchy may
     // need up to kFastMaxDepth - 1 entries in the worst case, but a ray that would push past entry 27 is simply handed to the one-lane
     // walk (deep stack), and on every scene measured none does (10 M triangles: 0 of 1.5e8 rays).  MCPT_SHORT_KERNEL=0: the deep-stack
     // engine at 3 waves per SIMD.
-    S.fast.stack_limit = kFastShortStack;
-    {
-        // (any prefix of the node array may be mirrored; the host builder puts the top of the tree there)
-        S.fast.cached = int32_t(std::min<size_t>(d->n_cw_nodes, size_t(kFastTopNodes)));
-        if (K.node_cache >= 0 && K.node_cache < S.fast.cached) S.fast.cached = K.node_cache;
-    }
-    d->fast_info.n_nodes = int32_t(d->n_cw_nodes);
-    d->fast_info.n_tris = int32_t(d->n_fast_tris);
-    d->fast_info.enabled = S.fast.enabled;
-    d->fast_info.cw_stack_need = fb_ro.cw_stack_need;
-    d->fast_info.max_depth = fb_ro.max_depth;
-    if (!K.short_kernel) S.fast.stack_limit = kFastMaxDepth;
+    S.fast.stack_limit = K.short_kernel ? kFastShortStack : kFastMaxDepth;
     S.fast.stack_cap = S.fast.stack_limit;
     if (K.test_stack_cap >= 4 && K.test_stack_cap < S.fast.stack_cap) S.fast.stack_cap = K.test_stack_cap;
+    // (any prefix of the node array may be mirrored; the host builder puts the top of the tree there)
+    S.fast.cached = int32_t(std::min<size_t>(size_t(d->fast_info.n_nodes), size_t(kFastTopNodes)));
+    if (K.node_cache >= 0 && K.node_cache < S.fast.cached) S.fast.cached = K.node_cache;
     const CameraFrame cf = camera_frame(s);
-    S.cam.eye[0] = cf.eye.x; S.cam.eye[1] = cf.eye.y; S.cam.eye[2] = cf.eye.z;
-    S.cam.start_point[0] = cf.start_point.x; S.cam.start_point[1] = cf.start_point.y; S.cam.start_point[2] = cf.start_point.z;
-    S.cam.pdx[0] = cf.screen_pdx.x; S.cam.pdx[1] = cf.screen_pdx.y; S.cam.pdx[2] = cf.screen_pdx.z;
-    S.cam.pdy[0] = cf.screen_pdy.x; S.cam.pdy[1] = cf.screen_pdy.y; S.cam.pdy[2] = cf.screen_pdy.z;
+    put3(S.cam.eye, cf.eye); put3(S.cam.start_point, cf.start_point); put3(S.cam.pdx, cf.screen_pdx); put3(S.cam.pdy, cf.screen_pdy);
     S.cam.width = s.width; S.cam.height = s.height;
     d->width = s.width; d->height = s.height;
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->dirs), size_t(s.width) * s.height * 3 * sizeof(double)));
+    return MCPT_OK;
+}
+
+int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mode, mcpt_device** out)
+{
+    if (!h || !out) return fail(MCPT_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (build_mode != MCPT_BUILD_HOST && build_mode != MCPT_BUILD_DEVICE && build_mode != MCPT_BUILD_DEVICE_FAST && build_mode != MCPT_BUILD_DEVICE_SAH)
+        return fail(MCPT_ERR_ARG, "bad build mode");
+    const Scene& s = h->s;
+    if (build_mode == MCPT_BUILD_HOST && !s.accel_built) return fail(MCPT_ERR_ARG, "scene has no host build; use MCPT_BUILD_DEVICE");
+    int ndev = mcpt_device_count();
+    if (ndev <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
+    if (const int gate = runtime_gate()) return gate;          // kernels of one hipcc on another release's runtime: refused
+    if (ordinal < 0 || ordinal >= ndev) return fail(MCPT_ERR_NO_DEVICE, "device ordinal out of range");
+    HIP_TRY(hipSetDevice(ordinal));
+    std::unique_ptr<mcpt_device, void (*)(mcpt_device*)> d(new mcpt_device, mcpt_device_free);
+    d->ordinal = ordinal;
+    d->knobs = read_knobs();
+    HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
+    for (auto& e : d->ev) HIP_TRY(hipEventCreate(&e));
+    HIP_TRY(hipStreamCreateWithFlags(&d->look_stream, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&d->look_ev, hipEventDisableTiming));
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d->h_look), 64, hipHostMallocDefault));
+
+    const int t = int(s.faces.size());
+    d->bi = bvh_shape(t);
+    const CreateClock clock{d->knobs.print_diag && t >= (1 << 17), std::chrono::steady_clock::now()};
+    std::vector<int32_t> order;                     // leaf -> .obj face
+    double absmax = 0;                              // largest |coordinate| of the scene, as the hierarchy's builder found it
+    int rc;
+    if ((rc = create_reference(d.get(), s, build_mode, clock, order)) || (rc = create_materials_and_lights(d.get(), s)) ||
+        (rc = create_hierarchy(d.get(), h, build_mode, order, clock, &absmax)) || (rc = create_pre_test(d.get(), absmax)))
+        return rc;
+    clock.lap("culling hierarchy in HBM");
+    if ((rc = create_workspaces(d.get(), s)) || (rc = create_dscene(d.get(), s, absmax))) return rc;
     h->devices_created.fetch_add(1);
     h->refs.fetch_add(1);
     d->scene = h;
@@ -984,10 +992,11 @@ int mcpt_device_fast_hierarchy(const mcpt_device* d, mcpt_fast_info* info, void*
     *info = d->fast_info;
     if (!nodes && !tri_faces) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
-    if (nodes && d->n_cw_nodes) HIP_TRY(hipMemcpy(nodes, d->cw_nodes, d->n_cw_nodes * sizeof(CwNode), hipMemcpyDeviceToHost));
-    if (tri_faces && d->n_fast_tris) {
-        std::vector<DTri> tris(d->n_fast_tris);
-        HIP_TRY(hipMemcpy(tris.data(), d->fast_tris, d->n_fast_tris * sizeof(DTri), hipMemcpyDeviceToHost));
+    const size_t n_nodes = size_t(d->fast_info.n_nodes), n_tris = size_t(d->fast_info.n_tris);
+    if (nodes && n_nodes) HIP_TRY(hipMemcpy(nodes, d->cw_nodes, n_nodes * sizeof(CwNode), hipMemcpyDeviceToHost));
+    if (tri_faces && n_tris) {
+        std::vector<DTri> tris(n_tris);
+        HIP_TRY(hipMemcpy(tris.data(), d->fast_tris, n_tris * sizeof(DTri), hipMemcpyDeviceToHost));
         for (size_t k = 0; k < tris.size(); k++) tri_faces[k] = tris[k].face;
     }
     return MCPT_OK;
