@@ -364,6 +364,39 @@ int mcpt_progressive_aovs(mcpt_progressive*, int32_t* material, double* depth, d
 int mcpt_progressive_denoise(mcpt_progressive*, const mcpt_denoise_params*, double* img);
 int mcpt_progressive_denoise_device(mcpt_progressive*, const mcpt_denoise_params*, double* d_img, void* stream);
 
+/* ---- camera lens (since the lens change; the reference has a pinhole and one primary ray per pixel) ---- */
+/* The reference traces one primary ray per pixel, through the pixel's corner, and gives it to all N samples (pathTracing.cpp:297-308), so
+ * every frame is aliased and nothing is out of focus.  A lens set on a device gives every camera sample (pixel, k) a camera ray of its own.
+ *   uniforms : u0..u3 = words 0..3 of the Philox block with counter (pixel, k, 0xFFFF << 16 | 0, 'MCPT') and key = seed, each (w + 0.5) * 2^-32
+ *              (the RNG seam of the path vertices at a depth no vertex has: uniform(seed, pixel, k, depth 0xFFFF, slot 0..3)).
+ *   q        : pos(i,j), the reference's running-sum corner of pixel (i,j) (start_point - pdy*i, then + pdx once per column, the bits of the
+ *              primary rays).  With MCPT_LENS_JITTER q = (pos(i,j) + pdx*u0) - pdy*u1: a uniform point of the pixel square whose top-left
+ *              corner is the reference's point -- so a jittered image sits half a pixel right of and below the reference's corner-sampled one.
+ *   pinhole  : aperture == 0: origin eye, direction normalize(q - eye).  Without jitter this is the reference's primary ray, bit for bit.
+ *   thin lens: aperture > 0, l = |look_at - eye|, F = focus_distance (F <= 0: l).  Focal point f = eye + (q - eye) * (F / l); lens point
+ *              o = (eye + x^ * (r cos phi)) + y^ * (r sin phi), r = aperture * sqrt(u2), phi = (2 pi) * u3 with the full-precision pi;
+ *              x^ = screen_x_dir, y^ = the normalised up (the basis of the reference's image plane, pathTracing.cpp:285-288, not necessarily
+ *              orthogonal to the view); the ray leaves o with direction normalize(f - o).  In focus is the reference's image plane scaled
+ *              about the eye until it passes through the point at distance F along the eye -> look_at axis.
+ *   shading  : unchanged.  The first vertex is shaded at depth 0 under the same rules and keys (a camera ray that reaches an emitter returns
+ *              the light's radiance unweighted); a camera ray that misses gives a sample of radiance 0.  fp64, no contraction.
+ * A lens is ACTIVE when it has a flag or aperture > 0.  Then mcpt_render*, MCPT_RENDER_MEGAKERNEL / PIPELINE / KEEP_STATS, partitions,
+ * mcpt_sample_radiance, mcpt_multi_* and progressive / adaptive handles trace a camera ray per sample, and rays_primary counts those rays.
+ * A progressive handle takes the device's lens when it is created (a later set_lens leaves it as it is).  Per pixel the handle counts the
+ * samples whose camera ray hit something; "the pixel's primary ray missed" (noise sums, the adaptive rule's immediate stop, the zero pixels
+ * of the fold) then means: that count is 0.  With a pinhole the count is 0 or `done`, which is the rule above.  AOVs stay those of the
+ * pixel's unjittered pinhole ray, and the denoiser's pass-through rule is unchanged (guides for depth of field are not modelled).
+ * MCPT_LENS_PER_SAMPLE alone traces a camera ray per sample although all rays of a pixel coincide: the same frame, bit for bit, through the
+ * per-sample route (an A/B and test seam).  Errors (MCPT_ERR_ARG): unknown flag bits, reserved != 0, aperture negative or not finite,
+ * focus_distance not finite.  With a NULL device and valid arguments: MCPT_ERR_NO_DEVICE without a GPU, as the other entry points. */
+#define MCPT_LENS_JITTER      1   /* uniform over the pixel square (antialiasing) */
+#define MCPT_LENS_PER_SAMPLE  2   /* trace a camera ray per sample even when all of a pixel's rays coincide (A/B and test seam) */
+typedef struct { int32_t flags; int32_t reserved; double aperture; double focus_distance; } mcpt_lens;
+int mcpt_device_set_lens(mcpt_device*, const mcpt_lens*);   /* NULL = the reference pinhole */
+int mcpt_device_get_lens(const mcpt_device*, mcpt_lens*);
+/* test seam: the camera rays of samples (pix[i], k[i]) under the device's lens (active or not) -> rays6[n*6] = origin xyz, direction xyz */
+int mcpt_camera_rays(mcpt_device*, uint64_t seed, const int32_t* pix, const int32_t* k, int64_t n, double* rays6);
+
 /* ---- integrator over several GPUs of one node (no reference counterpart: generateImg is single-process OpenMP) ---- */
 /* The frame is cut into tiles dealt to the GPUs exactly as mcpt_render_params.rank/world describe (rank r = devices[r]); the scene
  * is resident on every GPU; one host thread per GPU renders its tiles; at the end of the frame every rank's pixels travel as one
@@ -389,6 +422,7 @@ int  mcpt_multi_collect_stats(mcpt_multi*, mcpt_stats* stats);
  * number of ranks the RCCL communicator reports (0 with MCPT_GATHER_PEER).  Any pointer may be NULL. */
 int  mcpt_multi_last_timing(const mcpt_multi*, double* render_ms, double* gather_ms, int32_t* comm_ranks);
 void mcpt_multi_free(mcpt_multi*);
+int  mcpt_multi_set_lens(mcpt_multi*, const mcpt_lens*);     /* every device of the group (NULL: the pinhole) */
 
 /* ---- one process per GPU (since 105; no reference counterpart) ---- */
 /* The same exchange between the PROCESSES of a launch: every rank is a process that drives one GPU through mcpt_device_* (params->rank /
@@ -482,6 +516,11 @@ typedef struct {
  * it and reads exactly that many bytes: the entry point for any field added after 102, and the safe one for older headers. */
 int  mcpt_render_scene_ex(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, mcpt_stats* stats);
 int  mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, int64_t options_bytes, mcpt_stats* stats);
+/* mcpt_render_scene_opts under a lens (NULL: the pinhole, = mcpt_render_scene_opts), on the device or on every GPU of the options.  An invalid
+ * lens is refused before anything is read or written.  A checkpoint's frame identity includes the lens when it is active: a lens frame never
+ * resumes from a pinhole frame's checkpoint nor the reverse, and a pinhole frame's identity is what it was before lenses existed. */
+int  mcpt_render_scene_lens(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, int64_t options_bytes,
+                            const mcpt_lens*, mcpt_stats* stats);
 
 #ifdef __cplusplus
 }

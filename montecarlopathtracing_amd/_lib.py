@@ -76,6 +76,11 @@ class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("sigma_l", C.c_double), ("sigma_z", C.c_double)]
 
 
+class Lens(C.Structure):
+    """mcpt_lens: pixel-area jitter and a thin-lens aperture (mcpt_device_set_lens); all zero = the reference's pinhole"""
+    _fields_ = [("flags", C.c_int32), ("reserved", C.c_int32), ("aperture", C.c_double), ("focus_distance", C.c_double)]
+
+
 class FastInfo(C.Structure):
     """mcpt_fast_info: shape and origin of the culling hierarchy a device's fast walk walks (mcpt_device_fast_hierarchy)"""
     _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_tris", "enabled", "cw_stack_need", "max_depth", "builder", "clusters", "reserved")]
@@ -110,6 +115,7 @@ EXPORTS = [
     "mcpt_multi_create", "mcpt_multi_num_devices", "mcpt_multi_render", "mcpt_multi_render_device", "mcpt_multi_last_timing", "mcpt_multi_collect_stats", "mcpt_multi_free",
     "mcpt_comm_unique_id", "mcpt_comm_create", "mcpt_comm_size", "mcpt_comm_gather_frame", "mcpt_comm_allreduce", "mcpt_comm_free",
     "mcpt_render_scene", "mcpt_render_scene_ex", "mcpt_render_scene_opts",
+    "mcpt_device_set_lens", "mcpt_device_get_lens", "mcpt_camera_rays", "mcpt_multi_set_lens", "mcpt_render_scene_lens",
 ]
 
 
@@ -220,6 +226,12 @@ def lib():
     L.mcpt_render_scene.argtypes = [C.c_char_p, C.c_char_p, C.c_int32]
     L.mcpt_render_scene_ex.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.POINTER(Stats)]
     L.mcpt_render_scene_opts.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Stats)]
+    L.mcpt_device_set_lens.argtypes = [P, C.POINTER(Lens)]
+    L.mcpt_device_get_lens.argtypes = [P, C.POINTER(Lens)]
+    L.mcpt_camera_rays.argtypes = [P, C.c_uint64, I32, I32, C.c_int64, D]
+    L.mcpt_multi_set_lens.argtypes = [P, C.POINTER(Lens)]
+    L.mcpt_render_scene_lens.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens),
+                                         C.POINTER(Stats)]
     _lib = L
     return L
 

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, DenoiseParams, FastInfo, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
+from ._lib import AdaptiveParams, DenoiseParams, FastInfo, Lens, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -18,10 +18,23 @@ BUILD_HOST, BUILD_DEVICE, BUILD_DEVICE_FAST, BUILD_DEVICE_SAH = 0, 1, 2, 3
 FAST_BUILT_HOST, FAST_BUILT_DEVICE_FAST, FAST_BUILT_DEVICE_PLOC, FAST_BUILT_PLOC_FELL_BACK = 0, 1, 2, 3
 SCENE_DEFER_BUILD = 1
 GATHER_PEER, GATHER_RCCL = 0, 1
+LENS_JITTER, LENS_PER_SAMPLE = 1, 2
 
 
 def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
+
+
+def make_lens(aperture=0.0, focus_distance=0.0, jitter=False, per_sample=False):
+    """An mcpt_lens: jitter = uniform over the pixel square, aperture > 0 = a thin lens of that radius focused at focus_distance
+    (<= 0: at look_at), per_sample = a camera ray per sample even for the pinhole (mcpt.h: camera lens)."""
+    return Lens((LENS_JITTER if jitter else 0) | (LENS_PER_SAMPLE if per_sample else 0), 0, float(aperture), float(focus_distance))
+
+
+def _as_lens(lens):
+    if lens is None or isinstance(lens, Lens):
+        return lens
+    return make_lens(**lens)
 
 
 def build_id():
@@ -293,6 +306,26 @@ class Device:
         check(lib().mcpt_sample_radiance(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), pix.shape[0], _p(rgb, C.c_double)))
         return rgb
 
+    def set_lens(self, aperture=0.0, focus_distance=0.0, jitter=False, per_sample=False):
+        """The camera lens of every later frame, sample_radiance, camera_rays and progressive handle created after it (mcpt_device_set_lens);
+        no arguments: the reference's pinhole."""
+        check(lib().mcpt_device_set_lens(self._h, C.byref(make_lens(aperture, focus_distance, jitter, per_sample))))
+
+    def lens(self):
+        """the device's lens as a dict of set_lens's arguments"""
+        l = Lens()
+        check(lib().mcpt_device_get_lens(self._h, C.byref(l)))
+        return {"aperture": l.aperture, "focus_distance": l.focus_distance, "jitter": bool(l.flags & LENS_JITTER),
+                "per_sample": bool(l.flags & LENS_PER_SAMPLE)}
+
+    def camera_rays(self, seed, pix, k):
+        """camera rays of samples (pix[i], k[i]) under the device's lens: (n, 6) = origin, direction"""
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        rays = np.zeros((pix.shape[0], 6))
+        check(lib().mcpt_camera_rays(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), pix.shape[0], _p(rays, C.c_double)))
+        return rays
+
     def progressive(self, spp, seed=0, rank=0, world=1, tile_w=0, tile_h=0, flags=0):
         """A frame of `spp` samples per pixel rendered in passes (mcpt_progressive_*): see Progressive."""
         return Progressive(self, spp, seed, rank, world, tile_w, tile_h, flags)
@@ -428,6 +461,10 @@ class MultiDevice:
     def num_devices(self):
         return lib().mcpt_multi_num_devices(self._h)
 
+    def set_lens(self, aperture=0.0, focus_distance=0.0, jitter=False, per_sample=False):
+        """the same lens on every device of the group (Device.set_lens)"""
+        check(lib().mcpt_multi_set_lens(self._h, C.byref(make_lens(aperture, focus_distance, jitter, per_sample))))
+
     def generateImg(self, spp, seed=0, tile_w=0, tile_h=0, flags=0, stats=None):
         img = np.zeros((self.height, self.width, 3))
         rp = RenderParams(spp, seed, 0, 1, tile_w, tile_h, flags)
@@ -543,12 +580,13 @@ def morton_code(x, y, z):
 
 def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, height=0, quiet=True, output_prefix=None, stats=None,
                  load_flags=0, output_flags=0, checkpoint=None, checkpoint_parts=0, devices=None, gather=GATHER_PEER, noise_target=0.0,
-                 time_budget_s=0.0, adaptive_min_spp=0, abs_target=0.0):
+                 time_budget_s=0.0, adaptive_min_spp=0, abs_target=0.0, lens=None):
     """render_scene(path, filename, N) of MTPC/MTPC.cpp:35; writes <prefix>-SPP<N>.png (default ../result/<filename>).
     devices: list of GPU ordinals, or -1 for every visible GPU (the frame is then rendered by mcpt_multi_*).
     noise_target / time_budget_s / OUT_ERROR_PFM: a progressive frame that may stop at k < N samples (<prefix>-SPP<k>.png).
     adaptive_min_spp > 0: an adaptive frame, noise_target and abs_target its per-pixel targets (OUT_SPP_PFM: the sample-count map).
-    OUT_DENOISED / OUT_AOV_PFM: also the denoised frame (.denoised.png, .denoised.pfm with OUT_PFM) / the first-hit AOVs as .pfm files."""
+    OUT_DENOISED / OUT_AOV_PFM: also the denoised frame (.denoised.png, .denoised.pfm with OUT_PFM) / the first-hit AOVs as .pfm files.
+    lens: None (the pinhole), a Lens or a dict of Device.set_lens's arguments; rendered through mcpt_render_scene_lens."""
     dev_arr, ndev = None, 0
     if devices == -1:
         ndev = -1
@@ -558,6 +596,9 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
     o = RenderSceneOptions(seed, device, width, height, int(quiet), output_prefix.encode() if output_prefix else None,
                            load_flags, output_flags, checkpoint.encode() if checkpoint else None, checkpoint_parts, 0,
                            ndev, gather, dev_arr, noise_target, time_budget_s, adaptive_min_spp, 0, abs_target)
-    check(lib().mcpt_render_scene_opts(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o),
-                                       C.byref(stats) if stats is not None else None))
+    st = C.byref(stats) if stats is not None else None
+    if lens is None:
+        check(lib().mcpt_render_scene_opts(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o), st))
+    else:
+        check(lib().mcpt_render_scene_lens(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o), C.byref(_as_lens(lens)), st))
     return True

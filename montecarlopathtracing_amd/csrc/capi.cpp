@@ -126,6 +126,8 @@ struct mcpt_device {
     int width = 0, height = 0;
     double* dirs = nullptr;                // W*H*3 primary directions
     bool dirs_ready = false;
+    mcpt_lens lens{};                      // mcpt_device_set_lens (all zero: the reference's pinhole)
+    double* pos = nullptr;                 // W*H*3 image-plane points pos(i,j), made on the first frame under an active lens
     // render workspace
     int32_t* pixels = nullptr; int64_t n_pixels = 0; int part_key[4] = {-1, -1, -1, -1};
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -148,6 +150,7 @@ struct mcpt_device {
         void* wf_ws = nullptr; size_t wf_ws_bytes = 0;
         int32_t* hit_slots = nullptr; int64_t hit_slots_cap = 0;
         PrimarySurface* surf = nullptr; int64_t surf_cap = 0;   // first-vertex record per hit pixel of the chunk
+        uint8_t* cam_hit = nullptr; int64_t cam_hit_cap = 0;     // per-sample route of a lens: did the sample's camera ray hit (per chunk sample)
         unsigned int* alive_base = nullptr; int64_t alive_base_cap = 0;   // shaded pixels before each group of 64 hit slots
         WfCounts* wf_counts = nullptr;                  // MCPT_WF_COUNT_SLOTS slots
         TraceQueue* queue = nullptr;                    // persistent trace kernels: chunk queue head + deferred-ray list
@@ -567,10 +570,10 @@ void mcpt_device_free(mcpt_device* d)
     (void)hipSetDevice(d->ordinal);
     (void)hipDeviceSynchronize();          // frames of a sequence may still be in flight on the caller's streams
     void* ptrs[] = {d->nodes, d->tris, d->shade, d->materials, d->lights, d->light_tris, d->light_cdf, d->texels, d->fast_nodes, d->fast_tris, d->fast_pre, d->cw_nodes, d->d_order,
-                    d->dirs, d->pixels};
+                    d->dirs, d->pixels, d->pos};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& f : d->slot) {
-        void* q[] = {f.hits, f.rad, f.wf_ws, f.hit_slots, f.surf, f.alive_base, f.wf_counts, f.queue, f.slow_list, f.path_area, f.ctr};
+        void* q[] = {f.hits, f.rad, f.wf_ws, f.hit_slots, f.surf, f.alive_base, f.wf_counts, f.queue, f.slow_list, f.path_area, f.ctr, f.cam_hit};
         for (void* p : q) if (p) (void)hipFree(p);
         if (f.done) (void)hipEventDestroy(f.done);
     }
@@ -1020,6 +1023,47 @@ static int ensure_dirs(mcpt_device* d, hipStream_t st)
     return MCPT_OK;
 }
 
+// ---- lenses (mcpt.h: camera lens)
+static bool lens_active(const mcpt_lens& l) { return l.flags != 0 || l.aperture > 0.0; }
+static int lens_check(const mcpt_lens* l)
+{
+    if (!l) return MCPT_OK;
+    if (l->flags & ~(MCPT_LENS_JITTER | MCPT_LENS_PER_SAMPLE)) return fail(MCPT_ERR_ARG, "unknown lens flag");
+    if (l->reserved != 0) return fail(MCPT_ERR_ARG, "mcpt_lens.reserved must be 0");
+    if (!(std::isfinite(l->aperture) && l->aperture >= 0.0)) return fail(MCPT_ERR_ARG, "the aperture must be finite and >= 0");
+    if (!std::isfinite(l->focus_distance)) return fail(MCPT_ERR_ARG, "the focus distance must be finite");
+    return MCPT_OK;
+}
+static int ensure_pos(mcpt_device* d, hipStream_t st)
+{
+    if (!d->pos) {
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->pos), std::max<size_t>(size_t(d->width) * d->height * 3 * sizeof(double), 8)));
+        launch_primary_pos(d->ds.cam, d->pos, st);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return MCPT_OK;
+}
+// what the kernels need of a lens: the device's camera frame (capi: create_dscene), x^ = screen_x_dir and y^ = the normalised up as
+// camera_frame forms them, F / l
+static DLens lens_for(const mcpt_device* d, const mcpt_lens& l)
+{
+    DLens c{};
+    const Scene& s = d->scene->s;
+    const Vec3 up = normalized(s.up), dir = s.look_at - s.eye;
+    const Vec3 x = normalized(cross(dir, up));
+    const double len = norm(dir);
+    const double F = l.focus_distance > 0.0 ? l.focus_distance : len;
+    c.pos = d->pos;
+    for (int i = 0; i < 3; i++) { c.eye[i] = d->ds.cam.eye[i]; c.pdx[i] = d->ds.cam.pdx[i]; c.pdy[i] = d->ds.cam.pdy[i]; }
+    c.xhat[0] = x.x; c.xhat[1] = x.y; c.xhat[2] = x.z;
+    c.yhat[0] = up.x; c.yhat[1] = up.y; c.yhat[2] = up.z;
+    c.aperture = l.aperture;
+    c.focus_scale = F / len;
+    c.flags = l.flags;
+    return c;
+}
+
 static void counters_to_stats(const DCounters& c, mcpt_stats* s, bool print_diag)
 {
     s->rays_primary = c.rays_primary; s->rays_shadow = c.rays_shadow; s->rays_bounce = c.rays_bounce;
@@ -1153,6 +1197,8 @@ struct SampleRange {
     int k0, n, N;
     double* mom;
     uint8_t* hit;
+    const mcpt_lens* lens;      // the lens of the call (the device's, or the one a progressive handle took); null: the pinhole
+    int32_t* hitcnt;            // progressive passes under an active lens: per pixel, the samples whose camera ray hit
 };
 
 // The pixels a render call covers, on the device: the partition's owned list (mcpt_render*, uniform progressive passes) or an adaptive
@@ -1162,20 +1208,21 @@ struct PixelList {
     int64_t n;
 };
 
-static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, int first, int n_slots, double* d_img, hipStream_t st)
+static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, int first, int n_slots, double* d_img, bool lensed, hipStream_t st)
 {
-    if (r.mom) launch_fold_progressive(f.rad, L.pixels, f.hits, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, st);
+    if (lensed) launch_fold_lens(f.rad, f.cam_hit, L.pixels, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, r.hitcnt, st);
+    else if (r.mom) launch_fold_progressive(f.rad, L.pixels, f.hits, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, st);
     else launch_fold_samples(f.rad, L.pixels, f.hits, first, n_slots, r.n, d_img, st);
 }
 
 // megakernel path: one lane per camera sample, the whole path in one kernel (kept for A/B runs and as a second
 // implementation the wavefront path is checked against)
 static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, const mcpt_render_params* p,
-                             double* d_img, bool timed, hipStream_t st, double& ms_trace, int& launches)
+                             double* d_img, bool timed, const DLens* lens, hipStream_t st, double& ms_trace, int& launches)
 {
     const int64_t npx = L.n;
     const int spp = r.n;
-    const size_t per_pixel = size_t(spp) * 3 * sizeof(double);
+    const size_t per_pixel = size_t(spp) * 3 * sizeof(double) + (lens ? size_t(spp) : 0);   // (+ the hit flag of every sample under a lens)
     int64_t chunk = int64_t(std::max<size_t>(d->sample_budget_bytes / per_pixel, 64));
     chunk = std::min<int64_t>(chunk, npx);
     if (f.rad_cap < size_t(chunk) * per_pixel) {
@@ -1184,10 +1231,12 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const Sa
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f.rad), size_t(chunk) * per_pixel));
         f.rad_cap = size_t(chunk) * per_pixel;
     }
+    if (lens) { int rc = grow(&f.cam_hit, &f.cam_hit_cap, chunk * spp); if (rc) return rc; }
     for (int64_t first = 0; first < npx; first += chunk) {
         const int n_slots = int(std::min<int64_t>(chunk, npx - first));
         if (timed) HIP_TRY(hipEventRecord(d->ev[2], st));
-        launch_shade_samples(d->ds, p->seed, d->dirs, L.pixels, f.hits, int(first), n_slots, spp, r.k0, f.rad, f.ctr, st);
+        if (lens) launch_shade_samples_lens(d->ds, *lens, p->seed, L.pixels, int(first), n_slots, spp, r.k0, f.rad, f.cam_hit, f.ctr, st);
+        else launch_shade_samples(d->ds, p->seed, d->dirs, L.pixels, f.hits, int(first), n_slots, spp, r.k0, f.rad, f.ctr, st);
         HIP_TRY(hipGetLastError());
         if (timed) {
             HIP_TRY(hipEventRecord(d->ev[3], st));
@@ -1197,7 +1246,7 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const Sa
             ms_trace += ms;
         }
         launches++;
-        fold_range(f, r, L, int(first), n_slots, d_img, st);
+        fold_range(f, r, L, int(first), n_slots, d_img, lens != nullptr, st);
         HIP_TRY(hipGetLastError());
     }
     return MCPT_OK;
@@ -1206,8 +1255,10 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const Sa
 // wavefront path (wavefront.hpp): per chunk, lockstep iterations of logic + trace over compacted path state in HBM.
 // timed: event pairs around the trace launches, summed here (one stream synchronisation at the end); keep: the pairs are recorded
 // and left in d->ev_pool for mcpt_device_collect_stats -- the frame ends without the host waiting for it.
+// lens (non-null: an active lens): the per-sample route -- per chunk a camera pass (the camera as vertex -1 of every sample) and a trace
+// launch of its rays, then the logic passes from depth 0 on, every vertex in the path state (WfArgs::hits == null)
 static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, const mcpt_render_params* p,
-                            double* d_img, bool timed, bool keep, hipStream_t st, double& ms_trace, int& launches)
+                            double* d_img, bool timed, bool keep, const DLens* lens, hipStream_t st, double& ms_trace, int& launches)
 {
     const int64_t npx = L.n;
     const int spp = r.n;
@@ -1230,7 +1281,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
         }
         budget = d->wf_auto_budget;
     }
-    int64_t cap = int64_t((budget - overhead) / (bpp + 24));      // + 24 B radiance per sample
+    int64_t cap = int64_t((budget - overhead) / (bpp + 24 + (lens ? 1 : 0)));      // + 24 B radiance per sample (+ its hit flag under a lens)
     cap = std::min<int64_t>(cap, npx * int64_t(spp));
     cap = std::min<int64_t>(cap, (int64_t(1) << 31) - 4096);                 // 32-bit compaction counter / sample ids
     int64_t chunk_slots = std::max<int64_t>(cap / spp, 1);
@@ -1250,16 +1301,21 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f.rad), rad_need));
         f.rad_cap = rad_need;
     }
-    int rc = grow(&f.hit_slots, &f.hit_slots_cap, chunk_slots);
-    if (rc) return rc;
-    if ((rc = grow(&f.surf, &f.surf_cap, chunk_slots))) return rc;
-    if ((rc = grow(&f.alive_base, &f.alive_base_cap, chunk_slots / 64 + 2))) return rc;
+    int rc = MCPT_OK;
+    if (lens) {
+        if ((rc = grow(&f.cam_hit, &f.cam_hit_cap, cap))) return rc;
+    } else {
+        if ((rc = grow(&f.hit_slots, &f.hit_slots_cap, chunk_slots))) return rc;
+        if ((rc = grow(&f.surf, &f.surf_cap, chunk_slots))) return rc;
+        if ((rc = grow(&f.alive_base, &f.alive_base_cap, chunk_slots / 64 + 2))) return rc;
+    }
     WfArgs a{};
     WfState A, B;
     if (!wf_carve(f.wf_ws, f.wf_ws_bytes, cap, nl, A, B, a.rays)) return fail(MCPT_ERR_NOMEM, "wavefront workspace too small");
     a.cap = cap; a.nl = nl; a.spp = spp; a.sample_base = r.k0; a.seed = p->seed; a.pixels = L.pixels; a.hit_slots = f.hit_slots; a.surf = f.surf; a.alive_base = f.alive_base; a.hits = f.hits;
     a.dirs = d->dirs; a.rad = f.rad; a.counts = f.wf_counts; a.ctr = f.ctr; a.tris = d->tris; a.materials = d->materials; a.queue = fast ? f.queue : nullptr;
     a.finish_below = fast ? unsigned(std::min<long long>(std::max<long long>(d->finish_threshold, 0), 1ll << 30)) : 0u;
+    if (lens) { a.hits = nullptr; a.cam_hit = f.cam_hit; }
     // Iterations are enqueued without waiting for their counts: every kernel reads its input count from the device slot the
     // previous one wrote.  The host looks at a count only every few iterations (to stop, and to size the next grids).
     const size_t ev_first = d->ev_used;
@@ -1277,21 +1333,42 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
     for (int64_t first = 0; first < npx; first += chunk_slots) {
         const int n_slots = int(std::min<int64_t>(chunk_slots, npx - first));
         HIP_TRY(hipMemsetAsync(f.wf_counts, 0, sizeof(WfCounts) * MCPT_WF_COUNT_SLOTS, st));
-        launch_hit_slots(f.hits, int(first), n_slots, f.hit_slots, &f.wf_counts[0].n_next, st);
-        HIP_TRY(hipGetLastError());
         long long n_upper = (long long)n_slots * spp;        // upper bound of the live paths, refined at every look
         double n_grid = double(n_upper);                     // grid-sizing estimate between looks (kernels stride, any grid is correct)
         a.first_slot = int(first);
         a.in = A; a.out = B;
         a.counts_in = &f.wf_counts[0];
-        launch_primary_surface(d->ds, a, f.surf, f.alive_base, &f.wf_counts[0].pad[2], n_slots, st);      // what the samples of a pixel share at their first vertex
-        HIP_TRY(hipGetLastError());
+        if (lens) {
+            // the camera as vertex -1: its state into a.out, the count into slot 0, its rays traced as a bounce (depth -1: from a.out.p)
+            WfArgs ac = a;
+            ac.depth = -1; ac.counts = &f.wf_counts[0]; ac.count_mul = 1u; ac.finish_below = 0u;
+            launch_camera_pass(*lens, ac, n_upper, st);
+            HIP_TRY(hipGetLastError());
+            ac.nl = 0;          // the trace launch sees the bounce slot only (l == nl): no empty shadow-ray slots to walk past
+            std::pair<hipEvent_t, hipEvent_t>* pr = nullptr;
+            if (timed || keep) { if ((rc = next_pair(pr))) return rc; HIP_TRY(hipEventRecord(pr->first, st)); }
+            launch_wf_trace(d->ds, ac, n_upper, fast, f.queue, f.slow_list, d->slow_cap, st, d->cfg);
+            HIP_TRY(hipGetLastError());
+            if (timed || keep) HIP_TRY(hipEventRecord(pr->second, st));
+            launches++;
+            std::swap(a.in, a.out);
+        } else {
+            launch_hit_slots(f.hits, int(first), n_slots, f.hit_slots, &f.wf_counts[0].n_next, st);
+            HIP_TRY(hipGetLastError());
+            launch_primary_surface(d->ds, a, f.surf, f.alive_base, &f.wf_counts[0].pad[2], n_slots, st);      // what the samples of a pixel share at their first vertex
+            HIP_TRY(hipGetLastError());
+        }
         for (int depth = 0; depth < MCPT_MAX_DEPTH && n_upper > 0; depth++) {
             a.depth = depth;
-            a.counts_in = &f.wf_counts[depth]; a.count_mul = depth == 0 ? unsigned(spp) : 1u;
+            a.counts_in = &f.wf_counts[depth]; a.count_mul = depth == 0 && !lens ? unsigned(spp) : 1u;
             a.counts = &f.wf_counts[depth + 1];
             const long long n_launch = std::max<long long>(1, (long long)n_grid);
-            launch_wf_logic(d->ds, a, n_launch, depth == 0, st, d->cfg);
+            // the per-sample route's depth 0 resolves the camera rays: nothing went to the finishing kernel before it, and its pool form
+            // (which reads a pixel's PrimaryHit at depth 0) does not adopt its paths
+            const bool cam0 = lens && depth == 0;
+            char* const area = cam0 ? nullptr : f.path_area;
+            if (cam0) { WfArgs al = a; al.finish_below = 0u; launch_wf_logic(d->ds, al, n_launch, false, st, d->cfg); }
+            else launch_wf_logic(d->ds, a, n_launch, depth == 0, st, d->cfg);
             HIP_TRY(hipGetLastError());
             // The host looks at this pass's count every few iterations, and at every iteration once the hand-over to the finishing
             // kernel is near.  The look waits for this logic pass only (event + side stream): when it finds the hand-over, the
@@ -1304,7 +1381,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
                 HIP_TRY(hipStreamSynchronize(d->look_stream));
                 const unsigned int n_now = *d->h_look;
                 if (n_now <= a.finish_below) {
-                    if (n_now > 0) { launch_wf_finish(d->ds, a, (long long)n_now, st, d->cfg, f.path_area, f.slow_list, d->slow_cap); HIP_TRY(hipGetLastError()); }
+                    if (n_now > 0) { launch_wf_finish(d->ds, a, (long long)n_now, st, d->cfg, area, f.slow_list, d->slow_cap); HIP_TRY(hipGetLastError()); }
                     n_upper = 0;
                     break;
                 }
@@ -1312,7 +1389,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
                 n_grid = double(n_now);
             } else if (a.finish_below) {
                 // few paths left (decided on the device from this pass's count): one lane per path runs them to the end
-                launch_wf_finish(d->ds, a, std::min<long long>(n_launch, (long long)a.finish_below), st, d->cfg, f.path_area, f.slow_list, d->slow_cap);
+                launch_wf_finish(d->ds, a, std::min<long long>(n_launch, (long long)a.finish_below), st, d->cfg, area, f.slow_list, d->slow_cap);
                 HIP_TRY(hipGetLastError());
             }
             const long long n_trace = look ? (long long)n_grid : n_launch;
@@ -1332,7 +1409,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
             launch_wf_logic(d->ds, a, n_upper, false, st, d->cfg);
             HIP_TRY(hipGetLastError());
         }
-        fold_range(f, r, L, int(first), n_slots, d_img, st);
+        fold_range(f, r, L, int(first), n_slots, d_img, lens != nullptr, st);
         HIP_TRY(hipGetLastError());
     }
     if (timed && !keep) {
@@ -1358,7 +1435,7 @@ int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_im
     // a frame that fails half-way must not leave half-recorded event pairs behind: mcpt_device_collect_stats would trip over them
     const size_t ev_used0 = d->ev_used, frame_ev_used0 = d->frame_ev_used;
     int slot_used = -1;
-    const SampleRange whole{0, p->spp, p->spp, nullptr, nullptr};
+    const SampleRange whole{0, p->spp, p->spp, nullptr, nullptr, &d->lens, nullptr};
     int rc = prepare_partition(d, p, static_cast<hipStream_t>(stream));
     if (rc == MCPT_OK) rc = render_device_impl(d, whole, PixelList{d->pixels, d->n_pixels}, p, d_img, stats, static_cast<hipStream_t>(stream), slot_used);
     if (rc != MCPT_OK) {
@@ -1385,8 +1462,12 @@ static int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelL
     if (f.used) HIP_TRY(hipStreamWaitEvent(st, f.done, 0));
     int rc = ensure_dirs(d, st);
     if (rc) return rc;
+    const bool lensed = r.lens && lens_active(*r.lens);
+    if (lensed && (rc = ensure_pos(d, st))) return rc;
+    const DLens dl = lensed ? lens_for(d, *r.lens) : DLens{};
     const int64_t npx = L.n;
     if (npx == 0) return MCPT_OK;
+    const uint64_t primary_rays = uint64_t(npx) * (lensed ? uint64_t(r.n) : 1u);
     if ((rc = grow(&f.hits, &f.hits_cap, npx))) return rc;
     if (!keep || !f.keeping) HIP_TRY(hipMemsetAsync(f.ctr, 0, sizeof(DCounters), st));    // kept statistics accumulate until they are collected
     f.keeping = keep;
@@ -1401,16 +1482,18 @@ static int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelL
         fe = &d->frame_ev[d->frame_ev_used++];
         HIP_TRY(hipEventRecord(fe->first, st));
     } else HIP_TRY(hipEventRecord(d->ev[0], st));
-    launch_primary_hits(d->ds, d->trace_mode == MCPT_TRACE_FAST, d->dirs, L.pixels, int(npx), f.hits, f.ctr, f.queue, f.slow_list, d->slow_cap, st, d->cfg);
-    HIP_TRY(hipGetLastError());
+    if (!lensed) {          // (a lens traces its camera rays per sample, in the render path)
+        launch_primary_hits(d->ds, d->trace_mode == MCPT_TRACE_FAST, d->dirs, L.pixels, int(npx), f.hits, f.ctr, f.queue, f.slow_list, d->slow_cap, st, d->cfg);
+        HIP_TRY(hipGetLastError());
+    }
     double ms_trace = 0;
     int launches = 0;
-    if (p->flags & MCPT_RENDER_MEGAKERNEL) rc = render_megakernel(d, f, r, L, p, d_img, timed, st, ms_trace, launches);
-    else rc = render_wavefront(d, f, r, L, p, d_img, timed, keep, st, ms_trace, launches);
+    if (p->flags & MCPT_RENDER_MEGAKERNEL) rc = render_megakernel(d, f, r, L, p, d_img, timed, lensed ? &dl : nullptr, st, ms_trace, launches);
+    else rc = render_wavefront(d, f, r, L, p, d_img, timed, keep, lensed ? &dl : nullptr, st, ms_trace, launches);
     if (rc) return rc;
     if (keep) {
         HIP_TRY(hipEventRecord(fe->second, st));
-        d->kept_samples += uint64_t(npx) * uint64_t(r.n); d->kept_primary += uint64_t(npx); d->kept_launches += launches;
+        d->kept_samples += uint64_t(npx) * uint64_t(r.n); d->kept_primary += primary_rays; d->kept_launches += launches;
     } else HIP_TRY(hipEventRecord(d->ev[1], st));
     HIP_TRY(hipEventRecord(f.done, st));
     f.used = true;
@@ -1423,7 +1506,7 @@ static int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelL
         HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
         stats->ms_total = ms; stats->ms_trace = ms_trace; stats->launches = launches;
         stats->samples = uint64_t(npx) * uint64_t(r.n);         // camera samples covered (a primary miss is a finished sample)
-        stats->rays_primary = uint64_t(npx);
+        stats->rays_primary = primary_rays;
     }
     return MCPT_OK;
 }
@@ -1503,12 +1586,62 @@ int mcpt_sample_radiance(mcpt_device* d, uint64_t seed, const int32_t* pix, cons
     if (e == hipSuccess) e = hipMemcpy(d_pix, pix, size_t(n) * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_k, k, size_t(n) * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        launch_sample_radiance(d->ds, seed, d->dirs, d_pix, d_k, n, d_rgb, d->aux_ctr, d->stream);
+        if (lens_active(d->lens)) {
+            if ((rc = ensure_pos(d, d->stream))) { cleanup(); return rc; }
+            launch_sample_radiance_lens(d->ds, lens_for(d, d->lens), seed, d_pix, d_k, n, d_rgb, d->aux_ctr, d->stream);
+        } else launch_sample_radiance(d->ds, seed, d->dirs, d_pix, d_k, n, d_rgb, d->aux_ctr, d->stream);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
     if (e == hipSuccess) e = hipMemcpy(rgb, d_rgb, size_t(n) * 24, hipMemcpyDeviceToHost);
     cleanup();
+    if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    return MCPT_OK;
+}
+
+int mcpt_device_set_lens(mcpt_device* d, const mcpt_lens* l)
+{
+    if (int rc = lens_check(l)) return rc;
+    if (mcpt_device_count() <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    d->lens = l ? *l : mcpt_lens{};
+    return MCPT_OK;
+}
+
+int mcpt_device_get_lens(const mcpt_device* d, mcpt_lens* out)
+{
+    if (!out) return fail(MCPT_ERR_ARG, "null argument");
+    if (mcpt_device_count() <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    *out = d->lens;
+    return MCPT_OK;
+}
+
+int mcpt_camera_rays(mcpt_device* d, uint64_t seed, const int32_t* pix, const int32_t* k, int64_t n, double* rays6)
+{
+    if (!pix || !k || !rays6 || n < 0) return fail(MCPT_ERR_ARG, "bad argument");
+    if (mcpt_device_count() <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (n == 0) return MCPT_OK;
+    for (int64_t i = 0; i < n; i++)
+        if (pix[i] < 0 || pix[i] >= d->width * d->height) return fail(MCPT_ERR_ARG, "pixel index out of range");
+    HIP_TRY(hipSetDevice(d->ordinal));
+    int rc = ensure_pos(d, d->stream);
+    if (rc) return rc;
+    int32_t *d_pix = nullptr, *d_k = nullptr;
+    double* d_rays = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_pix), size_t(n) * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_k), size_t(n) * 4);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_rays), size_t(n) * 48);
+    if (e == hipSuccess) e = hipMemcpy(d_pix, pix, size_t(n) * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_k, k, size_t(n) * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        launch_camera_rays(lens_for(d, d->lens), seed, d_pix, d_k, n, d_rays, d->stream);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    if (e == hipSuccess) e = hipMemcpy(rays6, d_rays, size_t(n) * 48, hipMemcpyDeviceToHost);
+    (void)hipFree(d_pix); (void)hipFree(d_k); (void)hipFree(d_rays);
     if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
     return MCPT_OK;
 }
@@ -1549,6 +1682,8 @@ struct mcpt_progressive {
     int32_t* aov_mat = nullptr; double* aov_depth = nullptr; double* aov_normal = nullptr; double* aov_albedo = nullptr;
     DenoiseGuide* guide = nullptr;
     DenoisePix* dn_buf[2] = {nullptr, nullptr};   // the denoiser's ping-pong buffers (W*H each), allocated on its first call
+    mcpt_lens lens{};                  // the device's lens when the handle was created
+    int32_t* hitcnt = nullptr;         // W*H, under an active lens: the samples so far whose camera ray hit (hit = hitcnt > 0)
 };
 
 void mcpt_progressive_free(mcpt_progressive* h)
@@ -1561,7 +1696,7 @@ void mcpt_progressive_free(mcpt_progressive* h)
                     static_cast<void*>(h->cnt), static_cast<void*>(h->masks), static_cast<void*>(h->block_counts),
                     static_cast<void*>(h->block_offsets), static_cast<void*>(h->total), static_cast<void*>(h->aov_mat),
                     static_cast<void*>(h->aov_depth), static_cast<void*>(h->aov_normal), static_cast<void*>(h->aov_albedo),
-                    static_cast<void*>(h->guide), static_cast<void*>(h->dn_buf[0]), static_cast<void*>(h->dn_buf[1])})
+                    static_cast<void*>(h->guide), static_cast<void*>(h->dn_buf[0]), static_cast<void*>(h->dn_buf[1]), static_cast<void*>(h->hitcnt)})
         if (q) (void)hipFree(q);
     if (h->h_sums) (void)hipHostFree(h->h_sums);
     if (h->h_total) (void)hipHostFree(h->h_total);
@@ -1584,6 +1719,7 @@ static int progressive_create(mcpt_device* d, const mcpt_render_params* p, const
     auto* h = new mcpt_progressive;
     h->d = d; d->refs.fetch_add(1);
     h->p = *p;
+    h->lens = d->lens;
     h->n_pixels = int64_t(v.size());
     int rc = upload(v, &h->pixels);
     hipError_t e = hipSuccess;
@@ -1592,6 +1728,7 @@ static int progressive_create(mcpt_device* d, const mcpt_render_params* p, const
         alloc(reinterpret_cast<void**>(&h->img), px * 3 * sizeof(double));
         alloc(reinterpret_cast<void**>(&h->mom), px * 6 * sizeof(double));
         alloc(reinterpret_cast<void**>(&h->hit), px);
+        if (lens_active(h->lens)) alloc(reinterpret_cast<void**>(&h->hitcnt), px * sizeof(int32_t));
         alloc(reinterpret_cast<void**>(&h->partials), size_t(kNoiseRanges) * 3 * sizeof(double));
         alloc(reinterpret_cast<void**>(&h->sums), 4 * sizeof(double));
         if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_sums), 4 * sizeof(double), hipHostMallocDefault);
@@ -1654,7 +1791,7 @@ int mcpt_progressive_step(mcpt_progressive* h, int32_t n, mcpt_stats* stats)
     if (stats) std::memset(stats, 0, sizeof *stats);
     mcpt_render_params q = h->p;
     q.spp = std::min(n, h->p.spp - h->done);
-    const SampleRange r{h->done, q.spp, h->p.spp, h->mom, h->hit};
+    const SampleRange r{h->done, q.spp, h->p.spp, h->mom, h->hit, &h->lens, h->hitcnt};
     const PixelList L = h->adaptive ? PixelList{h->active[h->cur], h->n_active} : PixelList{h->pixels, h->n_pixels};
     const size_t ev_used0 = d->ev_used;
     int slot_used = -1;
@@ -1971,6 +2108,20 @@ static uint64_t scene_tag(const Scene& s)
     return h;
 }
 
+// The identity of a frame rendered under a lens: the scene's tag with the lens mixed in -- only when the lens is active, so that a pinhole
+// frame keeps its tag (and existing checkpoint files stay valid) and the two never resume from each other's files.
+static uint64_t frame_tag(const Scene& s, const mcpt_lens* l)
+{
+    uint64_t h = scene_tag(s);
+    if (!l || !lens_active(*l)) return h;
+    auto mix = [&](const void* p, size_t n) { const unsigned char* b = static_cast<const unsigned char*>(p); for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; } };
+    const char tag[] = "lens";
+    const int64_t flags = l->flags;
+    const double focus = l->focus_distance > 0.0 ? l->focus_distance : 0.0;     // (every F <= 0 is the same lens)
+    mix(tag, 4); mix(&flags, sizeof flags); mix(&l->aperture, sizeof(double)); mix(&focus, sizeof focus);
+    return h;
+}
+
 int mcpt_checkpoint_save(const char* file, const mcpt_scene* h, const double* img, int32_t spp, uint64_t seed, int32_t parts, const uint8_t* done)
 {
     if (!file || !h || !img || !done || spp <= 0 || parts <= 0 || parts > 65536) return fail(MCPT_ERR_ARG, "bad argument");
@@ -2093,7 +2244,14 @@ int mcpt_render_scene_ex(const char* path, const char* filename, int32_t spp, co
 
 int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes, mcpt_stats* stats)
 {
+    return mcpt_render_scene_lens(path, filename, spp, opt, opt_bytes, nullptr, stats);
+}
+
+int mcpt_render_scene_lens(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
+                           const mcpt_lens* lens, mcpt_stats* stats)
+{
     if (!path || !filename || spp <= 0 || opt_bytes < 0 || (opt_bytes > 0 && !opt)) return fail(MCPT_ERR_ARG, "bad argument");
+    if (int lrc = lens_check(lens)) return lrc;
     mcpt_render_scene_options o{};
     if (opt) std::memcpy(&o, opt, std::min<size_t>(size_t(opt_bytes), sizeof o));
     const bool talk = !o.quiet;
@@ -2126,7 +2284,8 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
     const bool many = o.num_devices > 0 || o.num_devices == -1;
     if (many) rc = mcpt_multi_create(sc, o.num_devices > 0 ? o.devices : nullptr, o.num_devices > 0 ? o.num_devices : 0, MCPT_BUILD_HOST, o.gather, &multi);
     else rc = mcpt_device_create(sc, o.device, &dev);
-    if (rc) { mcpt_scene_free(sc); return rc; }
+    if (rc == MCPT_OK && lens) rc = many ? mcpt_multi_set_lens(multi, lens) : mcpt_device_set_lens(dev, lens);
+    if (rc) { if (dev) mcpt_device_free(dev); if (multi) mcpt_multi_free(multi); mcpt_scene_free(sc); return rc; }
     if (talk && many) std::printf("rendering on %d GPUs\n", mcpt_multi_num_devices(multi));
     if (many && o.checkpoint) {
         mcpt_multi_free(multi); mcpt_scene_free(sc);
@@ -2153,7 +2312,9 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
         // the frame in `parts` tile partitions, saved after each; partitions a matching checkpoint already holds are skipped
         const int parts = o.checkpoint_parts > 0 ? o.checkpoint_parts : 8;
         std::vector<uint8_t> done(size_t(parts), 0);
-        const int lrc = mcpt_checkpoint_load(o.checkpoint, sc, img.data(), spp, o.seed, parts, done.data());
+        const uint64_t tag = frame_tag(s, lens);
+        std::string cerr;
+        const int lrc = checkpoint_load(o.checkpoint, img.data(), s.width, s.height, spp, o.seed, tag, parts, done.data(), cerr);
         if (lrc != MCPT_OK) { std::fill(img.begin(), img.end(), 0.0); std::fill(done.begin(), done.end(), uint8_t(0)); }
         if (talk && lrc == MCPT_OK) {
             int have = 0;
@@ -2173,7 +2334,8 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
             local.ms_total += one.ms_total; local.launches += one.launches;
             local.max_depth = std::max(local.max_depth, one.max_depth);
             done[size_t(part)] = 1;
-            rc = mcpt_checkpoint_save(o.checkpoint, sc, img.data(), spp, o.seed, parts, done.data());
+            rc = checkpoint_save(o.checkpoint, img.data(), s.width, s.height, spp, o.seed, tag, parts, done.data(), cerr);
+            if (rc) rc = fail(rc, cerr);
         }
     }
     const auto t2 = clk::now();

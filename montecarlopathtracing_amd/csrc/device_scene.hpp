@@ -105,6 +105,16 @@ struct DCamera {                                   // generateImg's frame, pathT
     int32_t width, height;
 };
 
+// What a kernel needs of the lens: the device's camera frame and the lens itself, formed on the host (capi.cpp: lens_for); camera.hpp: camera_ray.
+struct DLens {
+    const double* pos;          // [W*H][3] pos(i,j): the reference's running-sum corner of every pixel (k_primary_pos)
+    double eye[3], pdx[3], pdy[3];
+    double xhat[3], yhat[3];    // screen_x_dir and the normalised up: the basis of the reference's image plane
+    double aperture;            // lens radius; 0 = pinhole
+    double focus_scale;         // F / l (F <= 0 given: 1)
+    int32_t flags, pad;
+};
+
 struct DScene {
     const DNode* nodes;
     const DTri* tris;

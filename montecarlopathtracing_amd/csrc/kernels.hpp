@@ -49,6 +49,18 @@ void launch_sample_radiance(const DScene& S, unsigned long long seed, const doub
                             long long n, double* d_rgb, DCounters* ctr, hipStream_t st);
 void launch_fold_samples(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int spp,
                          double* d_img, hipStream_t st);
+// ---- lenses (camera.hip).  d_pos: the W*H image-plane points of the camera (DLens::pos).  d_flags[slot * spp + k] (chunk-local): 1 when
+// the camera ray of that sample hit something.
+void launch_primary_pos(const DCamera& cam, double* d_pos, hipStream_t st);
+void launch_camera_rays(const DLens& lens, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, long long n, double* d_rays6, hipStream_t st);
+void launch_shade_samples_lens(const DScene& S, const DLens& lens, unsigned long long seed, const int32_t* d_pixels, int first_slot, int n_slots, int spp,
+                               int sample_base, double* d_rad, uint8_t* d_flags, DCounters* ctr, hipStream_t st);
+void launch_sample_radiance_lens(const DScene& S, const DLens& lens, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, long long n,
+                                 double* d_rgb, DCounters* ctr, hipStream_t st);
+// the folds of k_fold_samples / k_fold_progressive for the per-sample route (a camera ray that missed has radiance 0: it adds nothing);
+// progressive: d_hitcnt[pix] += the hits of the pass, d_hit[pix] = d_hitcnt[pix] > 0
+void launch_fold_lens(const double* d_rad, const uint8_t* d_flags, const int32_t* d_pixels, int first_slot, int n_slots, int n, int k0, int N,
+                      double* d_img, double* d_mom, uint8_t* d_hit, int32_t* d_hitcnt, hipStream_t st);
 // progressive frames: fold of samples [k0, k0 + n) of a frame of N into d_img, moments into d_mom ([W*H][2][3]), primary hit flags into d_hit
 void launch_fold_progressive(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int n, int k0, int N,
                              double* d_img, double* d_mom, uint8_t* d_hit, hipStream_t st);

@@ -222,6 +222,22 @@ void mcpt_multi_free(mcpt_multi* m)
 
 int mcpt_multi_num_devices(const mcpt_multi* m) { return m ? int(m->ranks.size()) : 0; }
 
+// the same lens on every GPU of the group (mcpt_device_set_lens checks it; the first refusal leaves every device as it was)
+int mcpt_multi_set_lens(mcpt_multi* m, const mcpt_lens* lens)
+{
+    mcpt_lens prev{};
+    if (m && !m->ranks.empty()) (void)mcpt_device_get_lens(m->ranks[0].dev, &prev);
+    if (!m) return mcpt_device_set_lens(nullptr, lens);       // the device entry point's checks and refusal of a null handle
+    for (Rank& r : m->ranks) {
+        const int rc = mcpt_device_set_lens(r.dev, lens);
+        if (rc != MCPT_OK) {
+            for (Rank& q : m->ranks) (void)mcpt_device_set_lens(q.dev, &prev);
+            return rc;
+        }
+    }
+    return MCPT_OK;
+}
+
 int mcpt_multi_create(const mcpt_scene* scene, const int32_t* devices, int32_t num_devices, int32_t build_mode, int32_t gather, mcpt_multi** out)
 {
     if (!scene || !out) return fail(MCPT_ERR_ARG, "null argument");

@@ -98,8 +98,12 @@ struct WfArgs {
     TraceQueue* queue;          // the frame slot's queue words: k_wf_logic clears them for the trace launch that follows it (a fill dispatch per
                                 // iteration, ~13 us with its gap, is a percent of a rank's share of the frame)
     int sample_base;            // sample index of the pass's first sample: sample k of a slot is camera sample sample_base + k (progressive
-                                // passes render samples [sample_base, sample_base + spp) of a frame; a whole frame passes 0).  Kept last:
-                                // wf_kernarg_args()'s offset of the struct is unchanged by it
+                                // passes render samples [sample_base, sample_base + spp) of a frame; a whole frame passes 0).  Kept
+                                // behind the older fields: wf_kernarg_args()'s offset of the struct is unchanged by it
+    // The per-sample route of a lens (k_camera_pass): hits == null says so -- every vertex, the first one included, then lives in the path
+    // state (out.p) instead of a pixel's PrimaryHit -- and the first logic pass records here, per chunk-local sample id, whether the
+    // sample's camera ray hit something (1) or not (0).  Null in the per-pixel route.
+    uint8_t* cam_hit;
 };
 
 size_t wf_bytes_per_path(int nl);
@@ -123,5 +127,9 @@ void launch_primary_surface(const DScene& S, const WfArgs& a, PrimarySurface* su
                             hipStream_t st);
 void launch_hit_slots(const PrimaryHit* hits, int first_slot, int n_slots, int32_t* hit_slots, unsigned int* count, hipStream_t st);
 void launch_zero_rad(double* rad, long long n_doubles, hipStream_t st);
+// The per-sample route of a lens (camera.hip): the camera as a vertex -1 of every (slot, k) of the chunk.  Its bounce ray is the camera ray
+// (from the lens point, MCPT_BT_NO_OFFSET), T = 1, no shadow rays; a.out receives the state, a.counts->n_next = n_samples.  The trace
+// launch that follows reads it with a.depth = -1; the logic pass of depth 0 then forms every sample's first vertex from its own hit.
+void launch_camera_pass(const DLens& lens, const WfArgs& a, long long n_samples, hipStream_t st);
 
 }  // namespace mcpt

@@ -232,7 +232,8 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                             if (depth > ls.depth) ls.depth = depth;
                             // (is the surface an emitter: the trace kernel said so with the leaf, MCPT_HIT_EMITTER)
                             if (hl[u] & MCPT_HIT_EMITTER) {                              // emitter: pathTracing.cpp:141-144
-                                if ((bt[u] & 7) != RT_DIFFUSE) {
+                                if (depth == 0) L[u] = ld3(S.lights[S.materials[S.tris[hl[u] & MCPT_HIT_LEAF_MASK].material].light].radiance);   // a camera ray (per-sample route): unweighted
+                                else if ((bt[u] & 7) != RT_DIFFUSE) {
                                     const DMaterial* m = S.materials + S.tris[hl[u] & MCPT_HIT_LEAF_MASK].material;
                                     if (folded) T[u] = sldc(a.in.T, cap, pos[u]);
                                     const V3 rad = ld3(S.lights[m->light].radiance);
@@ -240,6 +241,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                                 }
                             } else alive[u] = true;
                         }
+                        if (depth == 0 && a.cam_hit) a.cam_hit[id[u]] = hl[u] >= 0 ? 1 : 0;
                         if (!alive[u]) { sst(a.rad + (size_t)id[u] * 3, L[u].x); sst(a.rad + (size_t)id[u] * 3 + 1, L[u].y); sst(a.rad + (size_t)id[u] * 3 + 2, L[u].z); }
                     }
                 }
@@ -287,12 +289,13 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 const int id = sld(a.in.id + i);
                 const int bt = sld(a.in.btype + i);
                 V3 T = mk(1, 1, 1);
-                if (depth > 1 || folded) T = sldc(a.in.T, cap, i);
-                if (!folded) { const V3 wgt = sldc(a.in.w, cap, i); T = mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR); }
+                if (depth > 1 || (folded && depth > 0)) T = sldc(a.in.T, cap, i);      // (depth 0, the per-sample route: a camera ray, T = 1)
+                if (!folded && depth > 0) { const V3 wgt = sldc(a.in.w, cap, i); T = mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR); }
                 const V3 bd = sldc(a.in.bdir, cap, i);
-                // the vertex the bounce ray left from: the pixel's primary hit after the first pass, in.p afterwards
+                // the vertex the bounce ray left from: the pixel's primary hit after the first pass, in.p afterwards (and always in the
+                // per-sample route of a lens, hits == null: depth 0 resolves the camera rays, left from the lens points in in.p)
                 V3 pv;
-                if (depth == 1) { const PrimaryHit* ph = a.hits + (a.first_slot + id / a.spp); pv = mk(ph->p[0], ph->p[1], ph->p[2]); }
+                if (depth == 1 && a.hits) { const PrimaryHit* ph = a.hits + (a.first_slot + id / a.spp); pv = mk(ph->p[0], ph->p[1], ph->p[2]); }
                 else pv = sldc(a.in.p, cap, i);
                 // the hit point of the bounce ray, as the reference's test formed it when the trace kernel accepted the triangle
                 // (sceneManagement.cpp:318-320: t = ((v1 - o) . n) / (n . d), p = o + d t; same operands, same operations)

@@ -19,10 +19,11 @@ struct WfRaySource {
         l = 0; j = q;
         while (j >= n_paths) { j -= n_paths; l++; }
     }
-    // the vertex the rays of path j leave from: after the first pass every sample of a pixel still sits on its primary hit
+    // the vertex the rays of path j leave from: after the first pass every sample of a pixel still sits on its primary hit (the per-sample
+    // route of a lens, hits == null: in the state like every later vertex)
     __device__ __forceinline__ V3 vertex(long long j) const
     {
-        if (a.depth == 0) {
+        if (a.depth == 0 && a.hits) {
             const PrimaryHit* ph = a.hits + (a.first_slot + a.out.id[j] / a.spp);
             return mk(ph->p[0], ph->p[1], ph->p[2]);
         }
@@ -104,7 +105,7 @@ struct WfRaySourceK {
         const bool bounce = l == nl;
         const int flag = bounce ? wf_sld(wf_glob(A->out.btype) + j) : wf_sld(wf_glob(A->out.expect) + ((long long)l * cap + j));
         V3 p;
-        if (A->depth == 0) {
+        if (A->depth == 0 && A->hits) {
             const auto* ph = wf_glob(A->hits) + (A->first_slot + wf_glob(A->out.id)[j] / A->spp);
             p = mk(ph->p[0], ph->p[1], ph->p[2]);
         } else {

@@ -11,7 +11,7 @@ mkdir -p variants/obj_$name
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 base="-O3 -std=c++17 -fPIC -ffp-contract=off -pthread -Wall -Wno-unused-function -Wno-unused-result $flags"
 logic_flags="${LOGIC_FLAGS--mllvm -disable-machine-licm}"      # as the Makefile's LOGICFLAGS (LOGIC_FLAGS= in the environment: none)
-for f in kernels wavefront build_kernels denoise; do
+for f in kernels wavefront build_kernels denoise camera; do
   $HIPCC $base $hip_only --offload-arch=gfx950 -c -o variants/obj_$name/$f.o $f.hip &
 done
 $HIPCC $base $hip_only $logic_flags --offload-arch=gfx950 -c -o variants/obj_$name/wavefront_logic.o wavefront_logic.hip &
