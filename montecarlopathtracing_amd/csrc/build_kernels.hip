@@ -223,80 +223,75 @@ hipError_t device_offset_children(CwNode* nodes, int n, int off, hipStream_t st)
     return hipGetLastError();
 }
 
-hipError_t device_build_fast(const DTri* leaf_tris, int t, const double lo[3], const double hi[3], int per_leaf, int max_levels, CwNode** cw, DTri** fast_tris,
+#define BK_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
+
+hipError_t device_build_fast(const DTri* leaf_tris, int t, const double lo[3], const double hi[3], int per_leaf, int max_levels, DevBuf<CwNode>& cw, DevBuf<DTri>& fast_tris,
                              int* n_nodes, int* levels, int* n_top, std::vector<double>* top_boxes, double* absmax, hipStream_t st)
 {
-    *cw = nullptr; *fast_tris = nullptr; *n_nodes = 0; *levels = 0; *n_top = 0; *absmax = 0;
+    cw.reset(); fast_tris.reset(); *n_nodes = 0; *levels = 0; *n_top = 0; *absmax = 0;
     if (t <= 0 || t > (1 << 27)) return hipErrorInvalidValue;                  // leaf references hold first << 4
     // ---- order: sort (63-bit Morton code, leaf index), gather the triangle records into that order
-    DTri* tris = nullptr;
+    DevBuf<DTri> tris;
     {
-        unsigned long long *keys = nullptr, *keys_out = nullptr;
-        int32_t *idx = nullptr, *idx_out = nullptr;
-        void* tmp = nullptr;
+        DevBuf<unsigned long long> keys, keys_out;
+        DevBuf<int32_t> idx, idx_out;
+        DevBuf<char> tmp;
         size_t tmp_bytes = 0;
-        auto drop = [&]() { (void)hipFree(keys); (void)hipFree(keys_out); (void)hipFree(idx); (void)hipFree(idx_out); (void)hipFree(tmp); };
-        hipError_t rc = hipMalloc(reinterpret_cast<void**>(&keys), size_t(t) * 8);
-        if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&keys_out), size_t(t) * 8);
-        if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&idx), size_t(t) * 4);
-        if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&idx_out), size_t(t) * 4);
-        if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&tris), size_t(t) * sizeof(DTri));
-        if (rc != hipSuccess) { drop(); (void)hipFree(tris); return rc; }
+        BK_TRY(keys.alloc(size_t(t)));
+        BK_TRY(keys_out.alloc(size_t(t)));
+        BK_TRY(idx.alloc(size_t(t)));
+        BK_TRY(idx_out.alloc(size_t(t)));
+        BK_TRY(tris.alloc(size_t(t)));
         FastDomain dom;
         for (int a = 0; a < 3; a++) { dom.lo[a] = lo[a]; const double ext = hi[a] - lo[a]; dom.inv[a] = ext > 0 ? 1.0 / ext : 0.0; }
-        hipLaunchKernelGGL(k_fast_keys, dim3((t + 255) / 256), dim3(256), 0, st, leaf_tris, t, dom, keys, idx);
-        rc = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_out, idx, idx_out, t, 0, 63, st);
-        if (rc == hipSuccess) rc = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1);
-        if (rc == hipSuccess) rc = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, idx, idx_out, t, 0, 63, st);
-        if (rc == hipSuccess) { hipLaunchKernelGGL(k_gather_tris, dim3((t + 255) / 256), dim3(256), 0, st, leaf_tris, idx_out, t, tris); rc = hipGetLastError(); }
-        if (rc == hipSuccess) rc = hipStreamSynchronize(st);
-        drop();
-        if (rc != hipSuccess) { (void)hipFree(tris); return rc; }
+        hipLaunchKernelGGL(k_fast_keys, dim3((t + 255) / 256), dim3(256), 0, st, leaf_tris, t, dom, keys.get(), idx.get());
+        BK_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.get(), keys_out.get(), idx.get(), idx_out.get(), t, 0, 63, st));
+        BK_TRY(tmp.alloc(tmp_bytes));
+        BK_TRY(rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, keys.get(), keys_out.get(), idx.get(), idx_out.get(), t, 0, 63, st));
+        hipLaunchKernelGGL(k_gather_tris, dim3((t + 255) / 256), dim3(256), 0, st, leaf_tris, idx_out.get(), t, tris.get());
+        BK_TRY(hipGetLastError());
+        BK_TRY(hipStreamSynchronize(st));
     }
     const int groups = (t + per_leaf - 1) / per_leaf;
     int size[16], L = 0;                                                       // size[d] = nodes of inner level d, bottom first
     for (int n = groups;;) { n = (n + 3) / 4; size[L++] = n; if (n == 1 || L == max_levels) break; }   // stops below the root: a forest
     int total = 0;
     for (int d = 0; d < L; d++) total += size[d];
-    FBox *a = nullptr, *b = nullptr;
-    unsigned long long* am = nullptr;
-    CwNode* nodes = nullptr;
-    auto cleanup = [&]() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(am); };
-    hipError_t rc = hipMalloc(reinterpret_cast<void**>(&a), size_t(groups) * sizeof(FBox));
-    if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&b), size_t(size[0]) * sizeof(FBox));
-    if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&am), sizeof(unsigned long long));
-    if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&nodes), size_t(total) * sizeof(CwNode));
-    if (rc == hipSuccess) rc = hipMemsetAsync(am, 0, sizeof(unsigned long long), st);
-    if (rc != hipSuccess) { cleanup(); (void)hipFree(nodes); (void)hipFree(tris); return rc; }
-    hipLaunchKernelGGL(k_fast_leaf_boxes, dim3((groups + 255) / 256), dim3(256), 0, st, tris, t, per_leaf, groups, a, am);
+    DevBuf<FBox> a, b;
+    DevBuf<unsigned long long> am;
+    DevBuf<CwNode> nodes;
+    BK_TRY(a.alloc(size_t(groups)));
+    BK_TRY(b.alloc(size_t(size[0])));
+    BK_TRY(am.alloc(1));
+    BK_TRY(nodes.alloc(size_t(total)));
+    BK_TRY(hipMemsetAsync(am.get(), 0, sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_fast_leaf_boxes, dim3((groups + 255) / 256), dim3(256), 0, st, tris.get(), t, per_leaf, groups, a.get(), am.get());
     // root = node 0: level bases run top-down while the levels are built bottom-up
     int n_children = groups;
     for (int d = 0; d < L; d++) {
         int base = 0, child_base = 0;
         for (int u = L - 1; u > d; u--) base += size[u];
         child_base = base + size[d];                                           // the level below follows this one
-        hipLaunchKernelGGL(k_fast_level, dim3((size[d] + 255) / 256), dim3(256), 0, st, a, n_children, child_base, d == 0 ? per_leaf : 0, t, b, nodes, base,
-                           size[d]);
-        FBox* tmp = a; a = b; b = tmp;                                         // b (size[0] entries) is large enough for every later level
+        hipLaunchKernelGGL(k_fast_level, dim3((size[d] + 255) / 256), dim3(256), 0, st, a.get(), n_children, child_base, d == 0 ? per_leaf : 0, t, b.get(),
+                           nodes.get(), base, size[d]);
+        std::swap(a, b);                                                       // b (size[0] entries) is large enough for every later level
         n_children = size[d];
     }
     unsigned long long bits = 0;
-    rc = hipGetLastError();
+    BK_TRY(hipGetLastError());
     // (pageable host memory -- a stack word, a vector -- is only ever touched by blocking copies after the stream has drained: an
     // asynchronous copy into it goes through the runtime's pin-on-the-fly / staging paths, and an early return would leave a DMA
     // pending into a dead frame)
-    if (rc == hipSuccess) rc = hipStreamSynchronize(st);
-    if (rc == hipSuccess) rc = hipMemcpy(&bits, am, sizeof bits, hipMemcpyDeviceToHost);
+    BK_TRY(hipStreamSynchronize(st));
+    BK_TRY(hipMemcpy(&bits, am.get(), sizeof bits, hipMemcpyDeviceToHost));
     // exact boxes of the top level built here (nodes 0 .. size[L-1]-1): what the host's builder sees of each cluster; after the
     // last swap they are in `a`
-    if (rc == hipSuccess && top_boxes) {
+    if (top_boxes) {
         top_boxes->resize(size_t(size[L - 1]) * 6);
-        rc = hipMemcpy(top_boxes->data(), a, size_t(size[L - 1]) * sizeof(FBox), hipMemcpyDeviceToHost);
+        BK_TRY(hipMemcpy(top_boxes->data(), a.get(), size_t(size[L - 1]) * sizeof(FBox), hipMemcpyDeviceToHost));
     }
-    cleanup();
-    if (rc != hipSuccess) { (void)hipFree(nodes); (void)hipFree(tris); return rc; }
     double v; std::memcpy(&v, &bits, sizeof v);
-    *cw = nodes; *fast_tris = tris; *n_nodes = total; *levels = L; *n_top = size[L - 1]; *absmax = v;
+    cw = std::move(nodes); fast_tris = std::move(tris); *n_nodes = total; *levels = L; *n_top = size[L - 1]; *absmax = v;
     return hipSuccess;
 }
 
@@ -551,92 +546,91 @@ __global__ void k_ploc_collapse(const int32_t* __restrict__ done, int n_clusters
 }
 
 hipError_t device_build_ploc(const DTri* leaf_tris, int t, const double lo[3], const double hi[3], int max_cluster, int max_height, int radius, int max_leaf,
-                             double area_fraction, double cost_tri, double cost_leaf, int collapse_budget, CwNode** cw, DTri** fast_tris, int* n_nodes, int* n_top, std::vector<double>* top_boxes, std::vector<int32_t>* top_roots,
+                             double area_fraction, double cost_tri, double cost_leaf, int collapse_budget, DevBuf<CwNode>& cw, DevBuf<DTri>& fast_tris, int* n_nodes, int* n_top, std::vector<double>* top_boxes, std::vector<int32_t>* top_roots,
                              int* lower_need, double* absmax, int* rounds, hipStream_t st)
 {
-    *cw = nullptr; *fast_tris = nullptr; *n_nodes = 0; *n_top = 0; *absmax = 0; *lower_need = 0;
+    cw.reset(); fast_tris.reset(); *n_nodes = 0; *n_top = 0; *absmax = 0; *lower_need = 0;
     if (rounds) *rounds = 0;
     if (t <= 0 || t > (1 << 27)) return hipErrorInvalidValue;
-    std::vector<void*> owned;
-    auto drop = [&]() { for (void* q : owned) (void)hipFree(q); owned.clear(); };
-    auto take = [&](void** ptr, size_t bytes) { const hipError_t e = hipMalloc(ptr, bytes ? bytes : 1); if (e == hipSuccess) owned.push_back(*ptr); return e; };
-#define PL_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { drop(); return e_; } } while (0)
     // ---- Morton order of the triangle records
-    DTri* tris = nullptr;
-    unsigned long long *keys = nullptr, *keys_out = nullptr;
-    int32_t *idx = nullptr, *idx_out = nullptr;
-    void* tmp = nullptr;
+    DevBuf<DTri> tris;
+    DevBuf<unsigned long long> keys, keys_out;
+    DevBuf<int32_t> idx, idx_out;
+    DevBuf<char> tmp;
     size_t tmp_bytes = 0;
-    PL_TRY(take(reinterpret_cast<void**>(&keys), size_t(t) * 8));
-    PL_TRY(take(reinterpret_cast<void**>(&keys_out), size_t(t) * 8));
-    PL_TRY(take(reinterpret_cast<void**>(&idx), size_t(t) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&idx_out), size_t(t) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&tris), size_t(t) * sizeof(DTri)));
+    BK_TRY(keys.alloc(size_t(t)));
+    BK_TRY(keys_out.alloc(size_t(t)));
+    BK_TRY(idx.alloc(size_t(t)));
+    BK_TRY(idx_out.alloc(size_t(t)));
+    BK_TRY(tris.alloc(size_t(t)));
     FastDomain dom;
     for (int a = 0; a < 3; a++) { dom.lo[a] = lo[a]; const double ext = hi[a] - lo[a]; dom.inv[a] = ext > 0 ? 1.0 / ext : 0.0; }
-    hipLaunchKernelGGL(k_fast_keys, dim3((t + 255) / 256), dim3(256), 0, st, leaf_tris, t, dom, keys, idx);
-    PL_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_out, idx, idx_out, t, 0, 63, st));
-    PL_TRY(take(&tmp, tmp_bytes));
-    PL_TRY(rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, idx, idx_out, t, 0, 63, st));
-    hipLaunchKernelGGL(k_gather_tris, dim3((t + 255) / 256), dim3(256), 0, st, leaf_tris, idx_out, t, tris);
+    hipLaunchKernelGGL(k_fast_keys, dim3((t + 255) / 256), dim3(256), 0, st, leaf_tris, t, dom, keys.get(), idx.get());
+    BK_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.get(), keys_out.get(), idx.get(), idx_out.get(), t, 0, 63, st));
+    BK_TRY(tmp.alloc(tmp_bytes));
+    BK_TRY(rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, keys.get(), keys_out.get(), idx.get(), idx_out.get(), t, 0, 63, st));
+    hipLaunchKernelGGL(k_gather_tris, dim3((t + 255) / 256), dim3(256), 0, st, leaf_tris, idx_out.get(), t, tris.get());
     // ---- clustering
-    PlocArrays A;
-    unsigned long long* am = nullptr;
-    int32_t *cid = nullptr, *cid2 = nullptr, *nn = nullptr, *done = nullptr, *counters = nullptr;
-    PL_TRY(take(reinterpret_cast<void**>(&A.box), size_t(2) * t * sizeof(FBox)));
-    PL_TRY(take(reinterpret_cast<void**>(&A.left), size_t(2) * t * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&A.right), size_t(2) * t * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&A.cnt), size_t(2) * t * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&A.hgt), size_t(2) * t * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&A.cost), size_t(2) * t * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&A.leaf), size_t(2) * t * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&A.first), size_t(2) * t * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&cid), size_t(t) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&cid2), size_t(t) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&nn), size_t(t) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&done), size_t(t) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&counters), 16 * 4));          // [0] inner nodes, [1] selected (active), [2] selected (done), [3] stack need
-    PL_TRY(take(reinterpret_cast<void**>(&am), 8));
-    PL_TRY(hipMemsetAsync(counters, 0, 16 * 4, st));
-    PL_TRY(hipMemsetAsync(am, 0, 8, st));
-    hipLaunchKernelGGL(k_fast_leaf_boxes, dim3((t + 255) / 256), dim3(256), 0, st, tris, t, 1, t, A.box, am);
-    hipLaunchKernelGGL(k_ploc_init, dim3((t + 255) / 256), dim3(256), 0, st, t, cid, A, (float)cost_tri, (float)cost_leaf);
+    const size_t n2 = size_t(2) * t;
+    DevBuf<FBox> box;
+    DevBuf<int32_t> left, right, cnt, hgt, leaf, first;
+    DevBuf<float> cost;
+    DevBuf<unsigned long long> am;
+    DevBuf<int32_t> cid, cid2, nn, done, counters;
+    BK_TRY(box.alloc(n2));
+    BK_TRY(left.alloc(n2));
+    BK_TRY(right.alloc(n2));
+    BK_TRY(cnt.alloc(n2));
+    BK_TRY(hgt.alloc(n2));
+    BK_TRY(cost.alloc(n2));
+    BK_TRY(leaf.alloc(n2));
+    BK_TRY(first.alloc(n2));
+    const PlocArrays A{box.get(), left.get(), right.get(), cnt.get(), hgt.get(), cost.get(), leaf.get(), first.get()};
+    BK_TRY(cid.alloc(size_t(t)));
+    BK_TRY(cid2.alloc(size_t(t)));
+    BK_TRY(nn.alloc(size_t(t)));
+    BK_TRY(done.alloc(size_t(t)));
+    BK_TRY(counters.alloc(16));          // [0] inner nodes, [1] selected (active), [2] selected (done), [3] stack need
+    BK_TRY(am.alloc(1));
+    BK_TRY(hipMemsetAsync(counters.get(), 0, 16 * 4, st));
+    BK_TRY(hipMemsetAsync(am.get(), 0, 8, st));
+    hipLaunchKernelGGL(k_fast_leaf_boxes, dim3((t + 255) / 256), dim3(256), 0, st, tris.get(), t, 1, t, A.box, am.get());
+    hipLaunchKernelGGL(k_ploc_init, dim3((t + 255) / 256), dim3(256), 0, st, t, cid.get(), A, (float)cost_tri, (float)cost_leaf);
     const double sx = hi[0] - lo[0], sy = hi[1] - lo[1], sz = hi[2] - lo[2];
     const float max_area = area_fraction > 0 ? (float)((sx * sy + sy * sz + sz * sx) * area_fraction) : __builtin_inff();
     size_t sel_bytes = 0;
-    PL_TRY(rocprim::select(nullptr, sel_bytes, cid, cid2, counters + 1, size_t(t), PlocIsActive(), st));
-    void* sel_tmp = nullptr;
-    PL_TRY(take(&sel_tmp, sel_bytes));
+    BK_TRY(rocprim::select(nullptr, sel_bytes, cid.get(), cid2.get(), counters.get() + 1, size_t(t), PlocIsActive(), st));
+    DevBuf<char> sel_tmp;
+    BK_TRY(sel_tmp.alloc(sel_bytes));
     int n_active = t, n_done = 0, n_rounds = 0;
     while (n_active > 0) {
         const unsigned g = unsigned((n_active + 255) / 256);
-        hipLaunchKernelGGL(k_ploc_nn, dim3(g), dim3(256), 0, st, cid, n_active, A, radius, max_cluster, max_height, max_area, nn);
-        hipLaunchKernelGGL(k_ploc_merge, dim3(g), dim3(256), 0, st, cid, n_active, nn, A, t, counters, max_leaf, (float)cost_tri, 1.0f, (float)cost_leaf);
-        hipLaunchKernelGGL(k_ploc_clear_partner, dim3(g), dim3(256), 0, st, cid, n_active, nn);
+        hipLaunchKernelGGL(k_ploc_nn, dim3(g), dim3(256), 0, st, cid.get(), n_active, A, radius, max_cluster, max_height, max_area, nn.get());
+        hipLaunchKernelGGL(k_ploc_merge, dim3(g), dim3(256), 0, st, cid.get(), n_active, nn.get(), A, t, counters.get(), max_leaf, (float)cost_tri, 1.0f, (float)cost_leaf);
+        hipLaunchKernelGGL(k_ploc_clear_partner, dim3(g), dim3(256), 0, st, cid.get(), n_active, nn.get());
         size_t b1 = sel_bytes;
-        PL_TRY(rocprim::select(sel_tmp, b1, cid, done + n_done, counters + 2, size_t(n_active), PlocIsDone(), st));
+        BK_TRY(rocprim::select(sel_tmp.get(), b1, cid.get(), done.get() + n_done, counters.get() + 2, size_t(n_active), PlocIsDone(), st));
         size_t b2 = sel_bytes;
-        PL_TRY(rocprim::select(sel_tmp, b2, cid, cid2, counters + 1, size_t(n_active), PlocIsActive(), st));
+        BK_TRY(rocprim::select(sel_tmp.get(), b2, cid.get(), cid2.get(), counters.get() + 1, size_t(n_active), PlocIsActive(), st));
         int32_t h[2] = {0, 0};
-        PL_TRY(hipStreamSynchronize(st));
-        PL_TRY(hipMemcpy(h, counters + 1, 8, hipMemcpyDeviceToHost));       // blocking: h is a stack array
+        BK_TRY(hipStreamSynchronize(st));
+        BK_TRY(hipMemcpy(h, counters.get() + 1, 8, hipMemcpyDeviceToHost));       // blocking: h is a stack array
         n_active = h[0]; n_done += h[1];
-        int32_t* sw = cid; cid = cid2; cid2 = sw;
-        if (++n_rounds > 4096) { drop(); return hipErrorUnknown; }      // (every round finishes or merges at least one cluster)
+        std::swap(cid, cid2);
+        if (++n_rounds > 4096) return hipErrorUnknown;      // (every round finishes or merges at least one cluster)
     }
     if (rounds) *rounds = n_rounds;
     // ---- collapse the clusters
     const int nc = n_done;
-    int32_t *tri_cnt = nullptr, *tri_base = nullptr, *node_cnt = nullptr, *node_base = nullptr, *perm = nullptr;
-    FBox* d_top = nullptr;
-    int32_t* d_refs = nullptr;
-    PL_TRY(take(reinterpret_cast<void**>(&tri_cnt), size_t(nc) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&tri_base), size_t(nc) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&node_cnt), size_t(nc) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&node_base), size_t(nc) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&perm), size_t(t) * 4));
-    PL_TRY(take(reinterpret_cast<void**>(&d_top), size_t(nc) * sizeof(FBox)));
-    PL_TRY(take(reinterpret_cast<void**>(&d_refs), size_t(nc) * 4));
+    DevBuf<int32_t> tri_cnt, tri_base, node_cnt, node_base, perm, d_refs;
+    DevBuf<FBox> d_top;
+    BK_TRY(tri_cnt.alloc(size_t(nc)));
+    BK_TRY(tri_base.alloc(size_t(nc)));
+    BK_TRY(node_cnt.alloc(size_t(nc)));
+    BK_TRY(node_base.alloc(size_t(nc)));
+    BK_TRY(perm.alloc(size_t(t)));
+    BK_TRY(d_top.alloc(size_t(nc)));
+    BK_TRY(d_refs.alloc(size_t(nc)));
     const unsigned gc = unsigned((nc + 127) / 128);
     // Stack entries a walk may hold below a cluster root: at least the height the clusters were grown to (then the collapse can always
     // proceed); more lets it open more children per node, which shortens every walk -- as long as the tree over the nc clusters, which
@@ -648,68 +642,61 @@ hipError_t device_build_ploc(const DTri* leaf_tris, int t, const double lo[3], c
     if (collapse_budget > 0) budget = collapse_budget < max_height ? max_height : collapse_budget;
     // (a scene that left far more clusters than a scene of its size should -- everything too large or too far apart to merge -- leaves
     // no room for the tree above them: the caller takes another builder)
-    if (nc > 1 && budget + levels_above + 2 > 35) { drop(); return hipErrorNotSupported; }
-    hipLaunchKernelGGL(k_ploc_cluster_counts, dim3((nc + 255) / 256), dim3(256), 0, st, done, nc, A.cnt, tri_cnt);
-    hipLaunchKernelGGL(k_ploc_collapse<false>, dim3(gc), dim3(128), 0, st, done, nc, A, t, max_leaf, budget, nullptr, nullptr, node_cnt, nullptr, nullptr, nullptr, nullptr, nullptr);
+    if (nc > 1 && budget + levels_above + 2 > 35) return hipErrorNotSupported;
+    hipLaunchKernelGGL(k_ploc_cluster_counts, dim3((nc + 255) / 256), dim3(256), 0, st, done.get(), nc, A.cnt, tri_cnt.get());
+    hipLaunchKernelGGL(k_ploc_collapse<false>, dim3(gc), dim3(128), 0, st, done.get(), nc, A, t, max_leaf, budget, nullptr, nullptr, node_cnt.get(), nullptr, nullptr, nullptr, nullptr, nullptr);
     size_t scan_bytes = 0;
-    PL_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, tri_cnt, tri_base, int32_t(0), size_t(nc), rocprim::plus<int32_t>(), st));
-    void* scan_tmp = nullptr;
-    PL_TRY(take(&scan_tmp, scan_bytes));
+    BK_TRY(rocprim::exclusive_scan(nullptr, scan_bytes, tri_cnt.get(), tri_base.get(), int32_t(0), size_t(nc), rocprim::plus<int32_t>(), st));
+    DevBuf<char> scan_tmp;
+    BK_TRY(scan_tmp.alloc(scan_bytes));
     size_t sb = scan_bytes;
-    PL_TRY(rocprim::exclusive_scan(scan_tmp, sb, tri_cnt, tri_base, int32_t(0), size_t(nc), rocprim::plus<int32_t>(), st));
+    BK_TRY(rocprim::exclusive_scan(scan_tmp.get(), sb, tri_cnt.get(), tri_base.get(), int32_t(0), size_t(nc), rocprim::plus<int32_t>(), st));
     sb = scan_bytes;
-    PL_TRY(rocprim::exclusive_scan(scan_tmp, sb, node_cnt, node_base, int32_t(0), size_t(nc), rocprim::plus<int32_t>(), st));
+    BK_TRY(rocprim::exclusive_scan(scan_tmp.get(), sb, node_cnt.get(), node_base.get(), int32_t(0), size_t(nc), rocprim::plus<int32_t>(), st));
     int32_t last[2] = {0, 0};
-    PL_TRY(hipStreamSynchronize(st));
-    PL_TRY(hipMemcpy(&last[0], node_base + (nc - 1), 4, hipMemcpyDeviceToHost));
-    PL_TRY(hipMemcpy(&last[1], node_cnt + (nc - 1), 4, hipMemcpyDeviceToHost));
+    BK_TRY(hipStreamSynchronize(st));
+    BK_TRY(hipMemcpy(&last[0], node_base.get() + (nc - 1), 4, hipMemcpyDeviceToHost));
+    BK_TRY(hipMemcpy(&last[1], node_cnt.get() + (nc - 1), 4, hipMemcpyDeviceToHost));
     const int total = last[0] + last[1];
-    CwNode* nodes = nullptr;
-    DTri* out_tris = nullptr;
-    hipError_t rc = hipMalloc(reinterpret_cast<void**>(&nodes), size_t(total > 0 ? total : 1) * sizeof(CwNode));
-    if (rc == hipSuccess) rc = hipMalloc(reinterpret_cast<void**>(&out_tris), size_t(t) * sizeof(DTri));
-    if (rc != hipSuccess) { (void)hipFree(nodes); (void)hipFree(out_tris); drop(); return rc; }
-    hipLaunchKernelGGL(k_ploc_collapse<true>, dim3(gc), dim3(128), 0, st, done, nc, A, t, max_leaf, budget, node_base, tri_base, nullptr, nodes, perm, d_top, d_refs, counters + 3);
-    hipLaunchKernelGGL(k_gather_tris, dim3((t + 255) / 256), dim3(256), 0, st, tris, perm, t, out_tris);
+    DevBuf<CwNode> nodes;
+    DevBuf<DTri> out_tris;
+    BK_TRY(nodes.alloc(size_t(total > 0 ? total : 1)));
+    BK_TRY(out_tris.alloc(size_t(t)));
+    hipLaunchKernelGGL(k_ploc_collapse<true>, dim3(gc), dim3(128), 0, st, done.get(), nc, A, t, max_leaf, budget, node_base.get(), tri_base.get(), nullptr, nodes.get(),
+                       perm.get(), d_top.get(), d_refs.get(), counters.get() + 3);
+    hipLaunchKernelGGL(k_gather_tris, dim3((t + 255) / 256), dim3(256), 0, st, tris.get(), perm.get(), t, out_tris.get());
     unsigned long long bits = 0;
     int32_t need = 0;
-    rc = hipGetLastError();
-    if (rc == hipSuccess) rc = hipStreamSynchronize(st);
-    if (rc == hipSuccess) rc = hipMemcpy(&bits, am, 8, hipMemcpyDeviceToHost);
-    if (rc == hipSuccess) rc = hipMemcpy(&need, counters + 3, 4, hipMemcpyDeviceToHost);
-    if (rc == hipSuccess && top_boxes) { top_boxes->resize(size_t(nc) * 6); rc = hipMemcpy(top_boxes->data(), d_top, size_t(nc) * sizeof(FBox), hipMemcpyDeviceToHost); }
-    if (rc == hipSuccess && top_roots) { top_roots->resize(size_t(nc)); rc = hipMemcpy(top_roots->data(), d_refs, size_t(nc) * 4, hipMemcpyDeviceToHost); }
-    drop();
-    if (rc != hipSuccess) { (void)hipFree(nodes); (void)hipFree(out_tris); return rc; }
+    BK_TRY(hipGetLastError());
+    BK_TRY(hipStreamSynchronize(st));
+    BK_TRY(hipMemcpy(&bits, am.get(), 8, hipMemcpyDeviceToHost));
+    BK_TRY(hipMemcpy(&need, counters.get() + 3, 4, hipMemcpyDeviceToHost));
+    if (top_boxes) { top_boxes->resize(size_t(nc) * 6); BK_TRY(hipMemcpy(top_boxes->data(), d_top.get(), size_t(nc) * sizeof(FBox), hipMemcpyDeviceToHost)); }
+    if (top_roots) { top_roots->resize(size_t(nc)); BK_TRY(hipMemcpy(top_roots->data(), d_refs.get(), size_t(nc) * 4, hipMemcpyDeviceToHost)); }
     double v; std::memcpy(&v, &bits, sizeof v);
-    *cw = nodes; *fast_tris = out_tris; *n_nodes = total; *n_top = nc; *absmax = v; *lower_need = need;
+    cw = std::move(nodes); fast_tris = std::move(out_tris); *n_nodes = total; *n_top = nc; *absmax = v; *lower_need = need;
     return hipSuccess;
-#undef PL_TRY
 }
 
-
-#define BK_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return e_; } while (0)
 
 hipError_t device_build_reference(const BuildInputs& in, const mcpt_bvh_info& bi, DNode* nodes, DTri* tris, DTriShade* shade,
                                   int32_t* d_order, hipStream_t st)
 {
     const int t = in.t;
-    uint32_t *keys = nullptr, *keys_out = nullptr;
-    int32_t* idx = nullptr;
-    void* tmp = nullptr;
+    DevBuf<uint32_t> keys, keys_out;
+    DevBuf<int32_t> idx;
+    DevBuf<char> tmp;
     size_t tmp_bytes = 0;
-    hipError_t rc = hipSuccess;
-    auto cleanup = [&]() { (void)hipFree(keys); (void)hipFree(keys_out); (void)hipFree(idx); (void)hipFree(tmp); };
-    if ((rc = hipMalloc(reinterpret_cast<void**>(&keys), size_t(t) * 4)) != hipSuccess || (rc = hipMalloc(reinterpret_cast<void**>(&keys_out), size_t(t) * 4)) != hipSuccess ||
-        (rc = hipMalloc(reinterpret_cast<void**>(&idx), size_t(t) * 4)) != hipSuccess) { cleanup(); return rc; }
+    BK_TRY(keys.alloc(size_t(t)));
+    BK_TRY(keys_out.alloc(size_t(t)));
+    BK_TRY(idx.alloc(size_t(t)));
     MortonDomain dom;
     for (int a = 0; a < 3; a++) { dom.lo[a] = in.morton_lo[a]; dom.span[a] = in.morton_span[a]; }
-    hipLaunchKernelGGL(k_morton_keys, dim3((t + 255) / 256), dim3(256), 0, st, in.v9, t, dom, keys, idx);
+    hipLaunchKernelGGL(k_morton_keys, dim3((t + 255) / 256), dim3(256), 0, st, in.v9, t, dom, keys.get(), idx.get());
     // stable LSD radix sort of (key, face index) on the 30 key bits: equal keys keep .obj order (D2)
-    rc = rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys, keys_out, idx, d_order, t, 0, 30, st);
-    if (rc == hipSuccess) rc = hipMalloc(&tmp, tmp_bytes ? tmp_bytes : 1);
-    if (rc == hipSuccess) rc = rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_out, idx, d_order, t, 0, 30, st);
-    if (rc != hipSuccess) { cleanup(); return rc; }
+    BK_TRY(rocprim::radix_sort_pairs(nullptr, tmp_bytes, keys.get(), keys_out.get(), idx.get(), d_order, t, 0, 30, st));
+    BK_TRY(tmp.alloc(tmp_bytes));
+    BK_TRY(rocprim::radix_sort_pairs(tmp.get(), tmp_bytes, keys.get(), keys_out.get(), idx.get(), d_order, t, 0, 30, st));
     const int leaf0 = ((1 << bi.Level) - 1) - (2 * (bi.Lv >> 1) - __builtin_popcount(unsigned(bi.Lv >> 1)));   // findIndex(2^Level - 1, Level)
     hipLaunchKernelGGL(k_fill_leaves, dim3((t + 255) / 256), dim3(256), 0, st, in.v9, in.vn9, in.vt6, in.nrm3, in.material, d_order, t, tris, shade,
                        nodes + leaf0);
@@ -717,10 +704,8 @@ hipError_t device_build_reference(const BuildInputs& in, const mcpt_bvh_info& bi
         const int count = (1 << l) - (bi.Lv >> (bi.Level - l));
         if (count > 0) hipLaunchKernelGGL(k_build_level, dim3((count + 255) / 256), dim3(256), 0, st, nodes, bi.Lv, bi.Level, l);
     }
-    rc = hipGetLastError();
-    if (rc == hipSuccess) rc = hipStreamSynchronize(st);
-    cleanup();
-    return rc;
+    BK_TRY(hipGetLastError());
+    return hipStreamSynchronize(st);
 }
 
 // fp32 records of the triangle phase's pre-test (device_scene.hpp: DTriPre, trace_fast.hpp: tri_pre_reject), one per slot of the

@@ -6,6 +6,7 @@
 
 #include "../../include/mcpt.h"
 #include "device_scene.hpp"
+#include "hip_owned.hpp"
 
 namespace mcpt {
 
@@ -27,8 +28,8 @@ hipError_t device_build_reference(const BuildInputs& in, const mcpt_bvh_info& bi
 // high, written as the compressed nodes the walk kernels read.  With t <= 4^(max_levels+1) that is the whole tree (n_top = 1);
 // otherwise it is a forest of n_top clusters (nodes 0 .. n_top-1 are their roots, top_boxes their exact boxes, lo[3] hi[3] each)
 // for the host to put a SAH tree over (accel_build.cpp: build_fast_upper).  Only ever used to cull (trace_fast.hpp), so its
-// shape cannot change a result.  *cw and *fast_tris are hipMalloc'ed here; the walk needs 3 stack entries per level.
-hipError_t device_build_fast(const DTri* leaf_tris, int t, const double lo[3], const double hi[3], int per_leaf, int max_levels, CwNode** cw, DTri** fast_tris,
+// shape cannot change a result.  cw and fast_tris receive the buffers built here; the walk needs 3 stack entries per level.
+hipError_t device_build_fast(const DTri* leaf_tris, int t, const double lo[3], const double hi[3], int per_leaf, int max_levels, DevBuf<CwNode>& cw, DevBuf<DTri>& fast_tris,
                              int* n_nodes, int* levels, int* n_top, std::vector<double>* top_boxes, double* absmax, hipStream_t st);
 // MCPT_BUILD_DEVICE_SAH: the lower part grown on the device by parallel locally-ordered clustering into subtrees of at most max_cluster
 // triangles and max_height binary levels, each collapsed into compressed 4-wide nodes (leaves of up to max_leaf triangles where the
@@ -38,7 +39,7 @@ hipError_t device_build_fast(const DTri* leaf_tris, int t, const double lo[3], c
 // root can hold.  rounds = clustering rounds it took.
 hipError_t device_build_ploc(const DTri* leaf_tris, int t, const double lo[3], const double hi[3], int max_cluster, int max_height, int radius, int max_leaf,
                              double area_fraction /* of the scene box's area a cluster's box may have; 0: no limit */, double cost_tri, double cost_leaf,
-                             int collapse_budget /* stack entries below a cluster root; 0: chosen from the number of clusters */, CwNode** cw, DTri** fast_tris, int* n_nodes, int* n_top, std::vector<double>* top_boxes, std::vector<int32_t>* top_roots,
+                             int collapse_budget /* stack entries below a cluster root; 0: chosen from the number of clusters */, DevBuf<CwNode>& cw, DevBuf<DTri>& fast_tris, int* n_nodes, int* n_top, std::vector<double>* top_boxes, std::vector<int32_t>* top_roots,
                              int* lower_need, double* absmax, int* rounds, hipStream_t st);
 hipError_t device_offset_children(CwNode* nodes, int n, int off, hipStream_t st);     // child >= 0 -> child + off
 hipError_t device_gather_tris(const DTri* tris, const int32_t* d_slots, int n, DTri* out, hipStream_t st);

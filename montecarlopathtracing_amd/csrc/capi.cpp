@@ -22,6 +22,7 @@
 #include "accel_build.hpp"
 #include "build_kernels.hpp"
 #include "denoise.hpp"
+#include "hip_owned.hpp"
 #include "jpeg_decoder.hpp"
 #include "kernels.hpp"
 #include "knobs.hpp"
@@ -32,39 +33,20 @@ using namespace mcpt;
 
 namespace {
 thread_local std::string g_error;
-int fail(int code, const std::string& msg) { g_error = msg; return code; }
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess)                                                                           \
-            return fail(MCPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));              \
-    } while (0)
-
-template <class T, class A>
-int upload(const std::vector<T, A>& h, T** d)
-{
-    *d = nullptr;
-    const size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(d), bytes));
-    if (!h.empty()) HIP_TRY(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return MCPT_OK;
-}
-template <class T>
-int grow(T** ptr, int64_t* cap, int64_t need)
-{
-    if (*cap >= need) return MCPT_OK;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr; *cap = 0;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(ptr), size_t(need) * sizeof(T)));
-    *cap = need;
-    return MCPT_OK;
-}
-
 }  // namespace
 
-// the calling thread's error message, for the other translation units of the library (multi_device.cpp)
-namespace mcpt { int set_error(int code, const std::string& msg) { return fail(code, msg); } }
+// the calling thread's error message, for every translation unit of the library (hip_owned.hpp: fail, HIP_TRY)
+namespace mcpt { int set_error(int code, const std::string& msg) { g_error = msg; return code; } }
+
+// a device buffer of at least 8 bytes, unless b holds one already; alloc_zeroed: cleared as well
+template <class T>
+static hipError_t alloc_once(DevBuf<T>& b, size_t bytes) { return b ? hipSuccess : b.alloc_bytes(std::max<size_t>(bytes, 8)); }
+template <class T>
+static hipError_t alloc_zeroed(DevBuf<T>& b, size_t bytes)
+{
+    const hipError_t e = alloc_once(b, bytes);
+    return e == hipSuccess ? hipMemset(b.get(), 0, std::max<size_t>(bytes, 8)) : e;
+}
 
 struct mcpt_scene {
     Scene s;
@@ -109,64 +91,78 @@ static std::shared_ptr<const FastBvh> shared_fast_bvh(const mcpt_scene* h, const
     return h->fast_cached;
 }
 
+// start/stop events around a launch or a frame; next_pair: the next unused pair of a pool, created on first use
+using EventPair = std::pair<Event, Event>;
+static int next_pair(std::vector<EventPair>& pool, size_t& used, EventPair*& out)
+{
+    if (used == pool.size()) {
+        EventPair q;
+        HIP_TRY(create(q.first, hipEventCreate));
+        HIP_TRY(create(q.second, hipEventCreate));
+        pool.push_back(std::move(q));
+    }
+    out = &pool[used++];
+    return MCPT_OK;
+}
+
 struct mcpt_device {
     int ordinal = 0;
     Knobs knobs;                           // the environment as it was when this device was created (knobs.hpp)
     DScene ds{};
-    hipStream_t stream = nullptr;          // library stream for the host-pointer entry points
+    Stream stream;                         // library stream for the host-pointer entry points
     // scene arrays
-    DNode* nodes = nullptr; DTri* tris = nullptr; DTriShade* shade = nullptr; DMaterial* materials = nullptr;
-    DLight* lights = nullptr; DLightTri* light_tris = nullptr; double* light_cdf = nullptr; uint8_t* texels = nullptr;
-    FastNode* fast_nodes = nullptr; DTri* fast_tris = nullptr; CwNode* cw_nodes = nullptr; DTriPre* fast_pre = nullptr;
+    DevBuf<DNode> nodes; DevBuf<DTri> tris; DevBuf<DTriShade> shade; DevBuf<DMaterial> materials;
+    DevBuf<DLight> lights; DevBuf<DLightTri> light_tris; DevBuf<double> light_cdf; DevBuf<uint8_t> texels;
+    DevBuf<DTri> fast_tris; DevBuf<CwNode> cw_nodes; DevBuf<DTriPre> fast_pre;
     mcpt_fast_info fast_info{};     // what mcpt_device_fast_hierarchy reports (node and triangle slot counts, builder, clusters, depth, stack need)
     int trace_mode = MCPT_TRACE_FAST;
-    int32_t* d_order = nullptr;            // leaf -> .obj face (device build keeps it for read-back)
+    DevBuf<int32_t> d_order;               // leaf -> .obj face (device build keeps it for read-back)
     mcpt_bvh_info bi{};
     // frame state
     int width = 0, height = 0;
-    double* dirs = nullptr;                // W*H*3 primary directions
+    DevBuf<double> dirs;                   // W*H*3 primary directions
     bool dirs_ready = false;
     mcpt_lens lens{};                      // mcpt_device_set_lens (all zero: the reference's pinhole)
-    double* pos = nullptr;                 // W*H*3 image-plane points pos(i,j), made on the first frame under an active lens
+    DevBuf<double> pos;                    // W*H*3 image-plane points pos(i,j), made on the first frame under an active lens
     // render workspace
-    int32_t* pixels = nullptr; int64_t n_pixels = 0; int part_key[4] = {-1, -1, -1, -1};
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    hipStream_t look_stream = nullptr;     // the host's looks at a path count travel here, so that they wait for the logic pass that wrote
-    hipEvent_t look_ev = nullptr;          // the count and for nothing enqueued after it (the finishing kernel above all)
-    unsigned int* h_look = nullptr;        // pinned host word the looks land in (never a pageable stack address: an async copy into
+    DevBuf<int32_t> pixels; int64_t n_pixels = 0; int part_key[4] = {-1, -1, -1, -1};
+    Event ev[4];
+    Stream look_stream;                    // the host's looks at a path count travel here, so that they wait for the logic pass that wrote
+    Event look_ev;                         // the count and for nothing enqueued after it (the finishing kernel above all)
+    HostBuf<unsigned int> h_look;          // pinned host word the looks land in (never a pageable stack address: an async copy into
                                            // pageable memory goes through the runtime's pin-on-the-fly / staging paths)
     const mcpt_scene* scene = nullptr;     // the handle this device was created from (devices_created is given back in mcpt_device_free)
     // closest-hit and test entry points (mcpt_trace_closest*, mcpt_sample_radiance) have counters, queue words and a deferred-ray
     // list of their own: a frame in flight on another stream keeps using its frame slot's
-    DCounters* aux_ctr = nullptr; TraceQueue* aux_queue = nullptr; long long* aux_slow_list = nullptr;
+    DevBuf<DCounters> aux_ctr; DevBuf<TraceQueue> aux_queue; DevBuf<long long> aux_slow_list;
     size_t sample_budget_bytes = size_t(4) << 30;   // megakernel path: radiance staging buffer per chunk
     size_t wf_budget_bytes = 0;                     // path state + rays per frame slot; 0 = a share of the free HBM (MCPT_WORKSPACE_GB overrides)
     size_t wf_auto_budget = 0;                      // that share, asked for once (hipMemGetInfo costs a few hundred microseconds)
     // Everything a frame in flight owns.  Two slots: with MCPT_RENDER_PIPELINE consecutive frames alternate between them, so the
     // latency-bound tail of one frame (the finishing kernel's last long paths, the fold) overlaps the head of the next on another stream.
     struct FrameSlot {
-        PrimaryHit* hits = nullptr; int64_t hits_cap = 0;
-        double* rad = nullptr; size_t rad_cap = 0;
-        void* wf_ws = nullptr; size_t wf_ws_bytes = 0;
-        int32_t* hit_slots = nullptr; int64_t hit_slots_cap = 0;
-        PrimarySurface* surf = nullptr; int64_t surf_cap = 0;   // first-vertex record per hit pixel of the chunk
-        uint8_t* cam_hit = nullptr; int64_t cam_hit_cap = 0;     // per-sample route of a lens: did the sample's camera ray hit (per chunk sample)
-        unsigned int* alive_base = nullptr; int64_t alive_base_cap = 0;   // shaded pixels before each group of 64 hit slots
-        WfCounts* wf_counts = nullptr;                  // MCPT_WF_COUNT_SLOTS slots
-        TraceQueue* queue = nullptr;                    // persistent trace kernels: chunk queue head + deferred-ray list
-        long long* slow_list = nullptr;
-        char* path_area = nullptr;                      // records and exact-walk stacks of the pool form of the finishing pass (finish_pool_bytes)
-        DCounters* ctr = nullptr;
-        hipEvent_t done = nullptr;                      // recorded after the slot's last kernel of a frame
+        DevBuf<PrimaryHit> hits;
+        DevBuf<double> rad;                             // sized in bytes (a lens adds a hit flag per sample)
+        DevBuf<char> wf_ws;
+        DevBuf<int32_t> hit_slots;
+        DevBuf<PrimarySurface> surf;                    // first-vertex record per hit pixel of the chunk
+        DevBuf<uint8_t> cam_hit;                        // per-sample route of a lens: did the sample's camera ray hit (per chunk sample)
+        DevBuf<unsigned int> alive_base;                // shaded pixels before each group of 64 hit slots
+        DevBuf<WfCounts> wf_counts;                     // MCPT_WF_COUNT_SLOTS slots
+        DevBuf<TraceQueue> queue;                       // persistent trace kernels: chunk queue head + deferred-ray list
+        DevBuf<long long> slow_list;
+        DevBuf<char> path_area;                         // records and exact-walk stacks of the pool form of the finishing pass (finish_pool_bytes)
+        DevBuf<DCounters> ctr;
+        Event done;                                     // recorded after the slot's last kernel of a frame
         bool used = false;
         bool keeping = false;                           // ctr holds kept statistics of earlier frames (must not be cleared)
     } slot[2];
     int next_slot = 0;
     bool pipelined = false;                         // set by the first MCPT_RENDER_PIPELINE frame (sizes the workspace budget)
     // statistics kept on the device side until mcpt_device_collect_stats (MCPT_RENDER_KEEP_STATS)
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pool;   // start/stop pairs around trace launches
+    std::vector<EventPair> ev_pool;                 // start/stop pairs around trace launches
     size_t ev_used = 0;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> frame_ev;  // start/stop of every kept frame
+    std::vector<EventPair> frame_ev;                // start/stop of every kept frame
     size_t frame_ev_used = 0;
     uint64_t kept_samples = 0, kept_primary = 0; int kept_launches = 0;
     unsigned int slow_cap = 1u << 20;
@@ -569,24 +565,8 @@ void mcpt_device_free(mcpt_device* d)
     if (!d || d->refs.fetch_sub(1) != 1) return;
     (void)hipSetDevice(d->ordinal);
     (void)hipDeviceSynchronize();          // frames of a sequence may still be in flight on the caller's streams
-    void* ptrs[] = {d->nodes, d->tris, d->shade, d->materials, d->lights, d->light_tris, d->light_cdf, d->texels, d->fast_nodes, d->fast_tris, d->fast_pre, d->cw_nodes, d->d_order,
-                    d->dirs, d->pixels, d->pos};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (auto& f : d->slot) {
-        void* q[] = {f.hits, f.rad, f.wf_ws, f.hit_slots, f.surf, f.alive_base, f.wf_counts, f.queue, f.slow_list, f.path_area, f.ctr, f.cam_hit};
-        for (void* p : q) if (p) (void)hipFree(p);
-        if (f.done) (void)hipEventDestroy(f.done);
-    }
-    for (hipEvent_t e : d->ev) if (e) (void)hipEventDestroy(e);
-    for (auto& pr : d->ev_pool) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    for (auto& pr : d->frame_ev) { (void)hipEventDestroy(pr.first); (void)hipEventDestroy(pr.second); }
-    for (void* p : {static_cast<void*>(d->aux_ctr), static_cast<void*>(d->aux_queue), static_cast<void*>(d->aux_slow_list)}) if (p) (void)hipFree(p);
-    if (d->h_look) (void)hipHostFree(d->h_look);
-    if (d->look_stream) (void)hipStreamDestroy(d->look_stream);
-    if (d->look_ev) (void)hipEventDestroy(d->look_ev);
-    if (d->stream) (void)hipStreamDestroy(d->stream);
     if (d->scene) { d->scene->devices_created.fetch_sub(1); scene_release(d->scene); }
-    delete d;
+    delete d;                              // (its buffers, events and streams with it)
 }
 
 int mcpt_device_create(const mcpt_scene* h, int32_t ordinal, mcpt_device** out)
@@ -611,7 +591,6 @@ static int create_reference(mcpt_device* d, const Scene& s, int32_t build_mode, 
 {
     const mcpt_bvh_info& bi = d->bi;
     const int t = bi.t;
-    int rc;
     if (build_mode == MCPT_BUILD_HOST) {
         std::vector<DNode> nodes(bi.Nr);             // (records filled in place: the vectors zero them first)
         for (int i = 0; i < bi.Nr; i++) {
@@ -631,8 +610,10 @@ static int create_reference(mcpt_device* d, const Scene& s, int32_t build_mode, 
             q.material = f.material; q.face = s.order[k]; q.leaf = k;
         }
         order = s.order;
-        if ((rc = upload(nodes, &d->nodes)) || (rc = upload(tris, &d->tris)) || (rc = upload(shade, &d->shade)) || (rc = upload(order, &d->d_order)))
-            return rc;
+        HIP_TRY(d->nodes.upload(nodes));
+        HIP_TRY(d->tris.upload(tris));
+        HIP_TRY(d->shade.upload(shade));
+        HIP_TRY(d->d_order.upload(order));
     } else {
         // faces in .obj order -> HBM, then Morton keys, stable sort, leaf records and the level-by-level union on the GPU
         // (no zero fill: 2.2 GB at 10 M triangles, every element is written below)
@@ -650,22 +631,24 @@ static int create_reference(mcpt_device* d, const Scene& s, int32_t build_mode, 
         }
         });
         clock.lap("faces staged");
-        double *d_v9 = nullptr, *d_vn9 = nullptr, *d_vt6 = nullptr, *d_nrm3 = nullptr;
-        int32_t* d_mat = nullptr;
-        auto drop = [&]() { (void)hipFree(d_v9); (void)hipFree(d_vn9); (void)hipFree(d_vt6); (void)hipFree(d_nrm3); (void)hipFree(d_mat); };
-        if ((rc = upload(v9, &d_v9)) || (rc = upload(vn9, &d_vn9)) || (rc = upload(vt6, &d_vt6)) || (rc = upload(nrm3, &d_nrm3)) || (rc = upload(mat, &d_mat))) { drop(); return rc; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d->nodes), size_t(bi.Nr) * sizeof(DNode));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d->tris), size_t(t) * sizeof(DTri));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d->shade), size_t(t) * sizeof(DTriShade));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d->d_order), size_t(t) * sizeof(int32_t));
+        DevBuf<double> d_v9, d_vn9, d_vt6, d_nrm3;
+        DevBuf<int32_t> d_mat;
+        HIP_TRY(d_v9.upload(v9));
+        HIP_TRY(d_vn9.upload(vn9));
+        HIP_TRY(d_vt6.upload(vt6));
+        HIP_TRY(d_nrm3.upload(nrm3));
+        HIP_TRY(d_mat.upload(mat));
+        hipError_t e = d->nodes.alloc(size_t(bi.Nr));
+        if (e == hipSuccess) e = d->tris.alloc(size_t(t));
+        if (e == hipSuccess) e = d->shade.alloc(size_t(t));
+        if (e == hipSuccess) e = d->d_order.alloc(size_t(t));
         if (e == hipSuccess) {
-            BuildInputs in{d_v9, d_vn9, d_vt6, d_nrm3, d_mat, t, {s.morton_lo[0], s.morton_lo[1], s.morton_lo[2]},
+            BuildInputs in{d_v9.get(), d_vn9.get(), d_vt6.get(), d_nrm3.get(), d_mat.get(), t, {s.morton_lo[0], s.morton_lo[1], s.morton_lo[2]},
                            {s.morton_span[0], s.morton_span[1], s.morton_span[2]}};
-            e = device_build_reference(in, bi, d->nodes, d->tris, d->shade, d->d_order, d->stream);
+            e = device_build_reference(in, bi, d->nodes.get(), d->tris.get(), d->shade.get(), d->d_order.get(), d->stream.get());
         }
         order.resize(t);
-        if (e == hipSuccess) e = hipMemcpy(order.data(), d->d_order, size_t(t) * sizeof(int32_t), hipMemcpyDeviceToHost);
-        drop();
+        if (e == hipSuccess) e = hipMemcpy(order.data(), d->d_order.get(), size_t(t) * sizeof(int32_t), hipMemcpyDeviceToHost);
         if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build: ") + hipGetErrorString(e));
     }
     clock.lap("reference structures in HBM");
@@ -704,22 +687,24 @@ static int create_materials_and_lights(mcpt_device* d, const Scene& s)
             lcdf.push_back(l.cdf[j]);
         }
     }
-    int rc;
-    if ((rc = upload(mats, &d->materials)) || (rc = upload(lights, &d->lights)) || (rc = upload(ltris, &d->light_tris)) || (rc = upload(lcdf, &d->light_cdf)))
-        return rc;
-    return upload(texels, &d->texels);
+    HIP_TRY(d->materials.upload(mats));
+    HIP_TRY(d->lights.upload(lights));
+    HIP_TRY(d->light_tris.upload(ltris));
+    HIP_TRY(d->light_cdf.upload(lcdf));
+    HIP_TRY(d->texels.upload(texels));
+    return MCPT_OK;
 }
 
 // The whole hierarchy from the n_lower nodes a GPU builder left in d_lower.  n_top == 1: they are the whole tree.  Otherwise they
-// are a forest of n_top clusters: the host's SAH tree over the clusters' boxes goes in front of them, and d_lower is freed.
+// are a forest of n_top clusters: the host's SAH tree over the clusters' boxes goes in front of them, and d_lower goes.
 // roots[c] = lower node of cluster c's root, < 0: the cluster is one leaf and this is its reference; null: cluster c's root is
 // lower node c.  lower_need / lower_depth = stack entries / inner levels a walk below a cluster root may take.
-static int stitch_clusters(mcpt_device* d, CwNode* d_lower, int n_lower, int n_top, const std::vector<double>& top_boxes, const int32_t* roots,
+static int stitch_clusters(mcpt_device* d, DevBuf<CwNode> d_lower, int n_lower, int n_top, const std::vector<double>& top_boxes, const int32_t* roots,
                            int lower_need, int lower_depth)
 {
     mcpt_fast_info& fi = d->fast_info;
     if (n_top == 1) {                        // small scene: the GPU's tree is the whole tree
-        d->cw_nodes = d_lower;
+        d->cw_nodes = std::move(d_lower);
         fi.n_nodes = n_lower; fi.max_depth = lower_depth; fi.cw_stack_need = lower_need;
         return MCPT_OK;
     }
@@ -733,12 +718,12 @@ static int stitch_clusters(mcpt_device* d, CwNode* d_lower, int n_lower, int n_t
                 const int32_t r = roots ? roots[cluster] : cluster;
                 nd.child[c] = r >= 0 ? n_up + r : r;
             }
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d->cw_nodes), size_t(n_up + n_lower) * sizeof(CwNode));
-    if (e == hipSuccess) e = hipMemcpy(d->cw_nodes, up.cw.data(), size_t(n_up) * sizeof(CwNode), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpyAsync(d->cw_nodes + n_up, d_lower, size_t(n_lower) * sizeof(CwNode), hipMemcpyDeviceToDevice, d->stream);
-    if (e == hipSuccess) e = device_offset_children(d->cw_nodes + n_up, n_lower, n_up, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-    (void)hipFree(d_lower);
+    hipError_t e = d->cw_nodes.alloc(size_t(n_up + n_lower));
+    CwNode* const cw = d->cw_nodes.get();
+    if (e == hipSuccess) e = hipMemcpy(cw, up.cw.data(), size_t(n_up) * sizeof(CwNode), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpyAsync(cw + n_up, d_lower.get(), size_t(n_lower) * sizeof(CwNode), hipMemcpyDeviceToDevice, d->stream.get());
+    if (e == hipSuccess) e = device_offset_children(cw + n_up, n_lower, n_up, d->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream.get());
     if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy: ") + hipGetErrorString(e));
     fi.n_nodes = int32_t(n_up + n_lower); fi.max_depth = up.max_depth + lower_depth;
     fi.cw_stack_need = up.cw_stack_need;     // includes lower_need
@@ -752,7 +737,7 @@ static int build_hierarchy_on_device(mcpt_device* d, const double lo[3], const d
     const Knobs& K = d->knobs;
     const int t = d->bi.t;
     d->fast_info.n_tris = t;
-    CwNode* d_lower = nullptr;
+    DevBuf<CwNode> d_lower;
     int n_lower = 0, n_top = 0;
     std::vector<double> top_boxes;
     if (ploc) {
@@ -767,16 +752,16 @@ static int build_hierarchy_on_device(mcpt_device* d, const double lo[3], const d
         }
         std::vector<int32_t> top_roots;
         int lower_need = 0, rounds = 0;
-        const hipError_t e = device_build_ploc(d->tris, t, lo, hi, K.ploc_cluster, height, K.ploc_radius, K.ploc_leaf ? K.ploc_leaf : kFastDefaultLeaf,
-                                               K.ploc_area > 0 ? 1.0 / K.ploc_area : 0.0, K.ploc_ct, K.ploc_cl, K.ploc_budget, &d_lower, &d->fast_tris, &n_lower,
-                                               &n_top, &top_boxes, &top_roots, &lower_need, absmax, &rounds, d->stream);
+        const hipError_t e = device_build_ploc(d->tris.get(), t, lo, hi, K.ploc_cluster, height, K.ploc_radius, K.ploc_leaf ? K.ploc_leaf : kFastDefaultLeaf,
+                                               K.ploc_area > 0 ? 1.0 / K.ploc_area : 0.0, K.ploc_ct, K.ploc_cl, K.ploc_budget, d_lower, d->fast_tris, &n_lower,
+                                               &n_top, &top_boxes, &top_roots, &lower_need, absmax, &rounds, d->stream.get());
         if (e != hipErrorNotSupported) {
             if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy (clustering): ") + hipGetErrorString(e));
             clock.lap("clusters on the GPU");
             if (clock.talk) std::fprintf(stderr, "device create: %d clusters in %d rounds, %d nodes below them, stack need below a cluster root %d\n", n_top, rounds, n_lower, lower_need);
             d->fast_info.builder = MCPT_FAST_BUILT_DEVICE_PLOC;
             d->fast_info.clusters = n_top;
-            return stitch_clusters(d, d_lower, n_lower, n_top, top_boxes, top_roots.data(), lower_need, lower_need);
+            return stitch_clusters(d, std::move(d_lower), n_lower, n_top, top_boxes, top_roots.data(), lower_need, lower_need);
         }
     }
     // Clusters of Morton-consecutive triangles on the GPU (by default one compressed node over four single-triangle leaves:
@@ -784,11 +769,11 @@ static int build_hierarchy_on_device(mcpt_device* d, const double lo[3], const d
     // (MCPT_CLUSTER_LEAF x MCPT_CLUSTER_LEVELS, ms per frame synthetic 10 M SPP 16 / cornell-box): 1x1 87 / 143, 1x2 93 / 161,
     // 1x3 103 / 182, 2x1 116 / 177, 4x2 163 / 238; the host's full SAH tree: 56 / 110.
     int levels = 0;
-    const hipError_t e = device_build_fast(d->tris, t, lo, hi, K.cluster_leaf, K.cluster_levels, &d_lower, &d->fast_tris, &n_lower, &levels, &n_top, &top_boxes,
-                                           absmax, d->stream);
+    const hipError_t e = device_build_fast(d->tris.get(), t, lo, hi, K.cluster_leaf, K.cluster_levels, d_lower, d->fast_tris, &n_lower, &levels, &n_top, &top_boxes,
+                                           absmax, d->stream.get());
     if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("device build of the fast hierarchy: ") + hipGetErrorString(e));
     d->fast_info.builder = ploc ? MCPT_FAST_BUILT_PLOC_FELL_BACK : MCPT_FAST_BUILT_DEVICE_FAST;
-    return stitch_clusters(d, d_lower, n_lower, n_top, top_boxes, nullptr, 3 * levels, levels);   // three siblings pushed per level on the way down
+    return stitch_clusters(d, std::move(d_lower), n_lower, n_top, top_boxes, nullptr, 3 * levels, levels);   // three siblings pushed per level on the way down
 }
 
 // The fast walk's culling hierarchy: fills d->cw_nodes, d->fast_tris and d->fast_info; *absmax = largest |coordinate| of the scene
@@ -816,13 +801,12 @@ static int create_hierarchy(mcpt_device* d, const mcpt_scene* h, int32_t build_m
         // permuted triangle copy gathered on the GPU
         const std::shared_ptr<const FastBvh> fb = shared_fast_bvh(h, order, d->knobs);
         clock.lap("culling hierarchy on the host");
-        int32_t* d_slots = nullptr;
-        int rc;
-        if ((rc = upload(fb->cw, &d->cw_nodes)) || (rc = upload(fb->leaf_tris, &d_slots))) { (void)hipFree(d_slots); return rc; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&d->fast_tris), std::max<size_t>(fb->leaf_tris.size(), 1) * sizeof(DTri));
-        if (e == hipSuccess) e = device_gather_tris(d->tris, d_slots, int(fb->leaf_tris.size()), d->fast_tris, d->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-        (void)hipFree(d_slots);
+        DevBuf<int32_t> d_slots;
+        HIP_TRY(d->cw_nodes.upload(fb->cw));
+        HIP_TRY(d_slots.upload(fb->leaf_tris));
+        hipError_t e = d->fast_tris.alloc(fb->leaf_tris.size());
+        if (e == hipSuccess) e = device_gather_tris(d->tris.get(), d_slots.get(), int(fb->leaf_tris.size()), d->fast_tris.get(), d->stream.get());
+        if (e == hipSuccess) e = hipStreamSynchronize(d->stream.get());
         if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("fast triangle gather: ") + hipGetErrorString(e));
         fi.builder = MCPT_FAST_BUILT_HOST;
         fi.n_nodes = int32_t(fb->cw.size()); fi.n_tris = int32_t(fb->leaf_tris.size());
@@ -844,10 +828,10 @@ static int create_pre_test(mcpt_device* d, double absmax)
     // fp32 records of the triangle phase's pre-test, one per slot of the fast triangle array
     const int n_slots = d->fast_info.n_tris;
     // (four records of padding: the pre-test reads its triangles in rounds of up to four slots, used or not)
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d->fast_pre), (size_t(n_slots) + 4) * sizeof(DTriPre));
-    if (e == hipSuccess) e = hipMemsetAsync(d->fast_pre + n_slots, 0, 4 * sizeof(DTriPre), d->stream);
-    if (e == hipSuccess) e = device_build_pre(d->fast_tris, n_slots, absmax, d->fast_pre, d->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+    hipError_t e = d->fast_pre.alloc(size_t(n_slots) + 4);
+    if (e == hipSuccess) e = hipMemsetAsync(d->fast_pre.get() + n_slots, 0, 4 * sizeof(DTriPre), d->stream.get());
+    if (e == hipSuccess) e = device_build_pre(d->fast_tris.get(), n_slots, absmax, d->fast_pre.get(), d->stream.get());
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream.get());
     if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("pre-test records: ") + hipGetErrorString(e));
     return MCPT_OK;
 }
@@ -866,18 +850,18 @@ static int create_workspaces(mcpt_device* d, const Scene& s)
     const size_t path_bytes = d->cfg.finish_pool ? finish_pool_bytes(d->cfg.cus, int(s.lights.size())) : 0;     // (0: a path's rays do not fit a lane's slots)
     if (!path_bytes) d->cfg.finish_pool = 0;
     for (auto& f : d->slot) {
-        if (path_bytes) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f.path_area), path_bytes));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f.ctr), sizeof(DCounters)));
-        HIP_TRY(hipMemset(f.ctr, 0, sizeof(DCounters)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f.wf_counts), sizeof(WfCounts) * MCPT_WF_COUNT_SLOTS));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f.queue), sizeof(TraceQueue)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f.slow_list), size_t(d->slow_cap) * sizeof(long long) + spill_bytes));
-        HIP_TRY(hipEventCreateWithFlags(&f.done, hipEventDisableTiming));
+        if (path_bytes) HIP_TRY(f.path_area.alloc(path_bytes));
+        HIP_TRY(f.ctr.alloc(1));
+        HIP_TRY(hipMemset(f.ctr.get(), 0, sizeof(DCounters)));
+        HIP_TRY(f.wf_counts.alloc(MCPT_WF_COUNT_SLOTS));
+        HIP_TRY(f.queue.alloc(1));
+        HIP_TRY(f.slow_list.alloc_bytes(size_t(d->slow_cap) * sizeof(long long) + spill_bytes));     // (the pool engine's spill area behind the list)
+        HIP_TRY(create(f.done, hipEventCreateWithFlags, hipEventDisableTiming));
     }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->aux_ctr), sizeof(DCounters)));
-    HIP_TRY(hipMemset(d->aux_ctr, 0, sizeof(DCounters)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->aux_queue), sizeof(TraceQueue)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->aux_slow_list), size_t(d->slow_cap) * sizeof(long long) + spill_bytes));
+    HIP_TRY(d->aux_ctr.alloc(1));
+    HIP_TRY(hipMemset(d->aux_ctr.get(), 0, sizeof(DCounters)));
+    HIP_TRY(d->aux_queue.alloc(1));
+    HIP_TRY(d->aux_slow_list.alloc_bytes(size_t(d->slow_cap) * sizeof(long long) + spill_bytes));
     // paths left at which the finishing pass takes over: the pool form holds the wavefront kernels' pace further up (sweep on one eighth of
     // the headline frame, ms: 250 k 14.2, 500 k 13.3, 1 M 13.1, 2 M 13.0, 4 M 13.5, 8 M 14.8; whole frame 81.0 / 80.3 at 500 k / 2 M), the
     // one-lane-per-path form is flat from 2e5 to 1e6
@@ -892,12 +876,12 @@ static int create_dscene(mcpt_device* d, const Scene& s, double absmax)
     const Knobs& K = d->knobs;
     const mcpt_bvh_info& bi = d->bi;
     DScene& S = d->ds;
-    S.nodes = d->nodes; S.tris = d->tris; S.shade = d->shade; S.materials = d->materials; S.lights = d->lights;
-    S.light_tris = d->light_tris; S.light_cdf = d->light_cdf; S.texels = d->texels;
+    S.nodes = d->nodes.get(); S.tris = d->tris.get(); S.shade = d->shade.get(); S.materials = d->materials.get(); S.lights = d->lights.get();
+    S.light_tris = d->light_tris.get(); S.light_cdf = d->light_cdf.get(); S.texels = d->texels.get();
     S.t = bi.t; S.Lv = bi.Lv; S.Level = bi.Level; S.Nr = bi.Nr;
     S.num_lights = int32_t(s.lights.size()); S.num_materials = int32_t(s.materials.size());
     S.area0 = s.area0;
-    S.fast.cw = d->cw_nodes; S.fast.nodes = nullptr; S.fast.tris = d->fast_tris; S.fast.pre = d->fast_pre; S.fast.absmax = absmax;
+    S.fast.cw = d->cw_nodes.get(); S.fast.nodes = nullptr; S.fast.tris = d->fast_tris.get(); S.fast.pre = d->fast_pre.get(); S.fast.absmax = absmax;
     S.fast.enabled = d->fast_info.enabled;
     // Which shape of the trace engine walks it (wavefront.hip): by default the short-stack one at 4 waves per SIMD -- the hierarchy may
     // need up to kFastMaxDepth - 1 entries in the worst case, but a ray that would push past entry 27 is simply handed to the one-lane
@@ -913,7 +897,7 @@ static int create_dscene(mcpt_device* d, const Scene& s, double absmax)
     put3(S.cam.eye, cf.eye); put3(S.cam.start_point, cf.start_point); put3(S.cam.pdx, cf.screen_pdx); put3(S.cam.pdy, cf.screen_pdy);
     S.cam.width = s.width; S.cam.height = s.height;
     d->width = s.width; d->height = s.height;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->dirs), size_t(s.width) * s.height * 3 * sizeof(double)));
+    HIP_TRY(d->dirs.alloc(size_t(s.width) * s.height * 3));
     return MCPT_OK;
 }
 
@@ -933,11 +917,11 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
     std::unique_ptr<mcpt_device, void (*)(mcpt_device*)> d(new mcpt_device, mcpt_device_free);
     d->ordinal = ordinal;
     d->knobs = read_knobs();
-    HIP_TRY(hipStreamCreateWithFlags(&d->stream, hipStreamNonBlocking));
-    for (auto& e : d->ev) HIP_TRY(hipEventCreate(&e));
-    HIP_TRY(hipStreamCreateWithFlags(&d->look_stream, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&d->look_ev, hipEventDisableTiming));
-    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&d->h_look), 64, hipHostMallocDefault));
+    HIP_TRY(create(d->stream, hipStreamCreateWithFlags, hipStreamNonBlocking));
+    for (auto& e : d->ev) HIP_TRY(create(e, hipEventCreate));
+    HIP_TRY(create(d->look_stream, hipStreamCreateWithFlags, hipStreamNonBlocking));
+    HIP_TRY(create(d->look_ev, hipEventCreateWithFlags, hipEventDisableTiming));
+    HIP_TRY(d->h_look.alloc_bytes(64));
 
     const int t = int(s.faces.size());
     d->bi = bvh_shape(t);
@@ -965,7 +949,7 @@ int mcpt_device_get_bvh_nodes(mcpt_device* d, double* box6, int32_t* leaf_face)
     const mcpt_bvh_info& bi = d->bi;
     if (box6) {
         std::vector<DNode> nodes(bi.Nr);
-        HIP_TRY(hipMemcpy(nodes.data(), d->nodes, size_t(bi.Nr) * sizeof(DNode), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(nodes.data(), d->nodes.get(), size_t(bi.Nr) * sizeof(DNode), hipMemcpyDeviceToHost));
         for (int i = 0; i < bi.Nr; i++) {
             double* o = box6 + size_t(i) * 6;
             o[0] = nodes[i].mx[0]; o[1] = nodes[i].mx[1]; o[2] = nodes[i].mx[2]; o[3] = nodes[i].mn[0]; o[4] = nodes[i].mn[1]; o[5] = nodes[i].mn[2];
@@ -973,7 +957,7 @@ int mcpt_device_get_bvh_nodes(mcpt_device* d, double* box6, int32_t* leaf_face)
     }
     if (leaf_face) {
         std::vector<int32_t> order(bi.t);
-        HIP_TRY(hipMemcpy(order.data(), d->d_order, size_t(bi.t) * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(order.data(), d->d_order.get(), size_t(bi.t) * sizeof(int32_t), hipMemcpyDeviceToHost));
         const int leaf0 = find_index(bi, (1 << bi.Level) - 1, bi.Level);
         for (int i = 0; i < bi.Nr; i++) leaf_face[i] = (i >= leaf0 && i < leaf0 + bi.t) ? order[i - leaf0] : -1;
     }
@@ -984,7 +968,7 @@ int mcpt_device_get_leaf_order(mcpt_device* d, int32_t* leaf_to_face)
 {
     if (!d || !leaf_to_face) return fail(MCPT_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(d->ordinal));
-    HIP_TRY(hipMemcpy(leaf_to_face, d->d_order, size_t(d->bi.t) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(leaf_to_face, d->d_order.get(), size_t(d->bi.t) * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
 
@@ -996,10 +980,10 @@ int mcpt_device_fast_hierarchy(const mcpt_device* d, mcpt_fast_info* info, void*
     if (!nodes && !tri_faces) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
     const size_t n_nodes = size_t(d->fast_info.n_nodes), n_tris = size_t(d->fast_info.n_tris);
-    if (nodes && n_nodes) HIP_TRY(hipMemcpy(nodes, d->cw_nodes, n_nodes * sizeof(CwNode), hipMemcpyDeviceToHost));
+    if (nodes && n_nodes) HIP_TRY(hipMemcpy(nodes, d->cw_nodes.get(), n_nodes * sizeof(CwNode), hipMemcpyDeviceToHost));
     if (tri_faces && n_tris) {
         std::vector<DTri> tris(n_tris);
-        HIP_TRY(hipMemcpy(tris.data(), d->fast_tris, n_tris * sizeof(DTri), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(tris.data(), d->fast_tris.get(), n_tris * sizeof(DTri), hipMemcpyDeviceToHost));
         for (size_t k = 0; k < tris.size(); k++) tri_faces[k] = tris[k].face;
     }
     return MCPT_OK;
@@ -1015,7 +999,7 @@ int mcpt_device_set_trace_mode(mcpt_device* d, int32_t mode)
 static int ensure_dirs(mcpt_device* d, hipStream_t st)
 {
     if (!d->dirs_ready) {
-        launch_primary_dirs(d->ds.cam, d->dirs, st);
+        launch_primary_dirs(d->ds.cam, d->dirs.get(), st);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
         d->dirs_ready = true;
@@ -1037,8 +1021,8 @@ static int lens_check(const mcpt_lens* l)
 static int ensure_pos(mcpt_device* d, hipStream_t st)
 {
     if (!d->pos) {
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->pos), std::max<size_t>(size_t(d->width) * d->height * 3 * sizeof(double), 8)));
-        launch_primary_pos(d->ds.cam, d->pos, st);
+        HIP_TRY(d->pos.alloc_bytes(std::max<size_t>(size_t(d->width) * d->height * 3 * sizeof(double), 8)));
+        launch_primary_pos(d->ds.cam, d->pos.get(), st);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(st));
     }
@@ -1054,7 +1038,7 @@ static DLens lens_for(const mcpt_device* d, const mcpt_lens& l)
     const Vec3 x = normalized(cross(dir, up));
     const double len = norm(dir);
     const double F = l.focus_distance > 0.0 ? l.focus_distance : len;
-    c.pos = d->pos;
+    c.pos = d->pos.get();
     for (int i = 0; i < 3; i++) { c.eye[i] = d->ds.cam.eye[i]; c.pdx[i] = d->ds.cam.pdx[i]; c.pdy[i] = d->ds.cam.pdy[i]; }
     c.xhat[0] = x.x; c.xhat[1] = x.y; c.xhat[2] = x.z;
     c.yhat[0] = up.x; c.yhat[1] = up.y; c.yhat[2] = up.z;
@@ -1122,7 +1106,7 @@ int mcpt_trace_closest_device(mcpt_device* d, const double* d_rays, int64_t n, i
     if (!d || (n > 0 && !d_rays) || n < 0) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(d->ordinal));
     if (!d_face || !d_t || !d_p) return fail(MCPT_ERR_ARG, "d_face, d_t and d_p are required by the device form");
-    launch_trace_closest(d->ds, d->trace_mode == MCPT_TRACE_FAST, d_rays, n, d_face, d_t, d_p, d_pn, d->aux_ctr, d->aux_queue, d->aux_slow_list, d->slow_cap,
+    launch_trace_closest(d->ds, d->trace_mode == MCPT_TRACE_FAST, d_rays, n, d_face, d_t, d_p, d_pn, d->aux_ctr.get(), d->aux_queue.get(), d->aux_slow_list.get(), d->slow_cap,
                          static_cast<hipStream_t>(stream), d->cfg);
     HIP_TRY(hipGetLastError());
     return MCPT_OK;
@@ -1134,37 +1118,35 @@ int mcpt_trace_closest(mcpt_device* d, const double* rays, int64_t n, int32_t* f
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n == 0) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
-    double *d_rays = nullptr, *d_t = nullptr, *d_p = nullptr, *d_pn = nullptr;
-    int32_t* d_face = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_rays); (void)hipFree(d_t); (void)hipFree(d_p); (void)hipFree(d_pn); (void)hipFree(d_face); };
-#define TRY_OR_CLEAN(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(MCPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-    TRY_OR_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_rays), size_t(n) * 6 * sizeof(double)));
-    TRY_OR_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_face), size_t(n) * sizeof(int32_t)));
-    TRY_OR_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_t), size_t(n) * sizeof(double)));
-    TRY_OR_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_p), size_t(n) * 3 * sizeof(double)));
-    TRY_OR_CLEAN(hipMalloc(reinterpret_cast<void**>(&d_pn), size_t(n) * 3 * sizeof(double)));
+    DevBuf<double> d_rays, d_t, d_p, d_pn;
+    DevBuf<int32_t> d_face;
+    HIP_TRY(d_rays.alloc(size_t(n) * 6));
+    HIP_TRY(d_face.alloc(size_t(n)));
+    HIP_TRY(d_t.alloc(size_t(n)));
+    HIP_TRY(d_p.alloc(size_t(n) * 3));
+    HIP_TRY(d_pn.alloc(size_t(n) * 3));
+    hipStream_t st = d->stream.get();
     // host buffers are pageable: blocking copies (the runtime stages them), ordered around the kernels by stream synchronisation
-    TRY_OR_CLEAN(hipMemcpy(d_rays, rays, size_t(n) * 6 * sizeof(double), hipMemcpyHostToDevice));
-    TRY_OR_CLEAN(hipMemsetAsync(d->aux_ctr, 0, sizeof(DCounters), d->stream));
-    TRY_OR_CLEAN(hipEventRecord(d->ev[0], d->stream));
-    launch_trace_closest(d->ds, d->trace_mode == MCPT_TRACE_FAST, d_rays, n, d_face, d_t, d_p, d_pn, d->aux_ctr, d->aux_queue, d->aux_slow_list, d->slow_cap, d->stream, d->cfg);
-    TRY_OR_CLEAN(hipGetLastError());
-    TRY_OR_CLEAN(hipEventRecord(d->ev[1], d->stream));
-    TRY_OR_CLEAN(hipStreamSynchronize(d->stream));
-    if (face) TRY_OR_CLEAN(hipMemcpy(face, d_face, size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (t) TRY_OR_CLEAN(hipMemcpy(t, d_t, size_t(n) * sizeof(double), hipMemcpyDeviceToHost));
-    if (p) TRY_OR_CLEAN(hipMemcpy(p, d_p, size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (pn) TRY_OR_CLEAN(hipMemcpy(pn, d_pn, size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(d_rays.get(), rays, size_t(n) * 6 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemsetAsync(d->aux_ctr.get(), 0, sizeof(DCounters), st));
+    HIP_TRY(hipEventRecord(d->ev[0].get(), st));
+    launch_trace_closest(d->ds, d->trace_mode == MCPT_TRACE_FAST, d_rays.get(), n, d_face.get(), d_t.get(), d_p.get(), d_pn.get(), d->aux_ctr.get(),
+                         d->aux_queue.get(), d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(d->ev[1].get(), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (face) HIP_TRY(hipMemcpy(face, d_face.get(), size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (t) HIP_TRY(hipMemcpy(t, d_t.get(), size_t(n) * sizeof(double), hipMemcpyDeviceToHost));
+    if (p) HIP_TRY(hipMemcpy(p, d_p.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (pn) HIP_TRY(hipMemcpy(pn, d_pn.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost));
     DCounters c{};
-    TRY_OR_CLEAN(hipMemcpy(&c, d->aux_ctr, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&c, d->aux_ctr.get(), sizeof c, hipMemcpyDeviceToHost));
     if (stats) {
         counters_to_stats(c, stats, d->knobs.print_diag != 0);
         float ms = 0;
-        (void)hipEventElapsedTime(&ms, d->ev[0], d->ev[1]);
+        (void)hipEventElapsedTime(&ms, d->ev[0].get(), d->ev[1].get());
         stats->ms_trace = ms; stats->ms_total = ms; stats->launches = 1;
     }
-    cleanup();
-#undef TRY_OR_CLEAN
     return MCPT_OK;
 }
 
@@ -1178,12 +1160,8 @@ static int prepare_partition(mcpt_device* d, const mcpt_render_params* p, hipStr
     if (std::memcmp(key, d->part_key, sizeof key) == 0 && d->pixels) return MCPT_OK;
     std::vector<int32_t> v;
     owned_pixel_list(d->width, d->height, tw, th, rank, world, v);
-    if (d->pixels) {
-        HIP_TRY(hipDeviceSynchronize());       // a frame of the previous partition may still be in flight (MCPT_RENDER_KEEP_STATS / PIPELINE)
-        (void)hipFree(d->pixels); d->pixels = nullptr;
-    }
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d->pixels), std::max<size_t>(v.size(), 1) * sizeof(int32_t)));
-    if (!v.empty()) HIP_TRY(hipMemcpy(d->pixels, v.data(), v.size() * sizeof(int32_t), hipMemcpyHostToDevice));   // blocking: v is pageable
+    if (d->pixels) HIP_TRY(hipDeviceSynchronize());       // a frame of the previous partition may still be in flight (MCPT_RENDER_KEEP_STATS / PIPELINE)
+    HIP_TRY(d->pixels.upload(v));                          // (blocking copy: v is pageable)
     d->n_pixels = int64_t(v.size());
     std::memcpy(d->part_key, key, sizeof key);
     return MCPT_OK;
@@ -1210,9 +1188,9 @@ struct PixelList {
 
 static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, int first, int n_slots, double* d_img, bool lensed, hipStream_t st)
 {
-    if (lensed) launch_fold_lens(f.rad, f.cam_hit, L.pixels, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, r.hitcnt, st);
-    else if (r.mom) launch_fold_progressive(f.rad, L.pixels, f.hits, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, st);
-    else launch_fold_samples(f.rad, L.pixels, f.hits, first, n_slots, r.n, d_img, st);
+    if (lensed) launch_fold_lens(f.rad.get(), f.cam_hit.get(), L.pixels, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, r.hitcnt, st);
+    else if (r.mom) launch_fold_progressive(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, st);
+    else launch_fold_samples(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, d_img, st);
 }
 
 // megakernel path: one lane per camera sample, the whole path in one kernel (kept for A/B runs and as a second
@@ -1225,24 +1203,19 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const Sa
     const size_t per_pixel = size_t(spp) * 3 * sizeof(double) + (lens ? size_t(spp) : 0);   // (+ the hit flag of every sample under a lens)
     int64_t chunk = int64_t(std::max<size_t>(d->sample_budget_bytes / per_pixel, 64));
     chunk = std::min<int64_t>(chunk, npx);
-    if (f.rad_cap < size_t(chunk) * per_pixel) {
-        if (f.rad) (void)hipFree(f.rad);
-        f.rad = nullptr; f.rad_cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f.rad), size_t(chunk) * per_pixel));
-        f.rad_cap = size_t(chunk) * per_pixel;
-    }
-    if (lens) { int rc = grow(&f.cam_hit, &f.cam_hit_cap, chunk * spp); if (rc) return rc; }
+    HIP_TRY(f.rad.grow_bytes(size_t(chunk) * per_pixel));
+    if (lens) HIP_TRY(f.cam_hit.grow(size_t(chunk * spp)));
     for (int64_t first = 0; first < npx; first += chunk) {
         const int n_slots = int(std::min<int64_t>(chunk, npx - first));
-        if (timed) HIP_TRY(hipEventRecord(d->ev[2], st));
-        if (lens) launch_shade_samples_lens(d->ds, *lens, p->seed, L.pixels, int(first), n_slots, spp, r.k0, f.rad, f.cam_hit, f.ctr, st);
-        else launch_shade_samples(d->ds, p->seed, d->dirs, L.pixels, f.hits, int(first), n_slots, spp, r.k0, f.rad, f.ctr, st);
+        if (timed) HIP_TRY(hipEventRecord(d->ev[2].get(), st));
+        if (lens) launch_shade_samples_lens(d->ds, *lens, p->seed, L.pixels, int(first), n_slots, spp, r.k0, f.rad.get(), f.cam_hit.get(), f.ctr.get(), st);
+        else launch_shade_samples(d->ds, p->seed, d->dirs.get(), L.pixels, f.hits.get(), int(first), n_slots, spp, r.k0, f.rad.get(), f.ctr.get(), st);
         HIP_TRY(hipGetLastError());
         if (timed) {
-            HIP_TRY(hipEventRecord(d->ev[3], st));
-            HIP_TRY(hipEventSynchronize(d->ev[3]));
+            HIP_TRY(hipEventRecord(d->ev[3].get(), st));
+            HIP_TRY(hipEventSynchronize(d->ev[3].get()));
             float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, d->ev[2], d->ev[3]));
+            HIP_TRY(hipEventElapsedTime(&ms, d->ev[2].get(), d->ev[3].get()));
             ms_trace += ms;
         }
         launches++;
@@ -1276,7 +1249,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
             size_t free_b = 0, total_b = 0;
             HIP_TRY(hipMemGetInfo(&free_b, &total_b));
             size_t mine = 0;
-            for (const auto& q : d->slot) mine += q.wf_ws_bytes + q.rad_cap;
+            for (const auto& q : d->slot) mine += q.wf_ws.bytes() + q.rad.bytes();
             d->wf_auto_budget = std::max<size_t>((free_b + mine) / (d->pipelined ? 3 : 2), size_t(1) << 30);
         }
         budget = d->wf_auto_budget;
@@ -1288,51 +1261,31 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
     chunk_slots = std::min<int64_t>(chunk_slots, npx);
     cap = chunk_slots * spp;
     const size_t ws_need = size_t(cap) * bpp + overhead;
-    if (f.wf_ws_bytes < ws_need) {
-        if (f.wf_ws) (void)hipFree(f.wf_ws);
-        f.wf_ws = nullptr; f.wf_ws_bytes = 0;
-        HIP_TRY(hipMalloc(&f.wf_ws, ws_need));
-        f.wf_ws_bytes = ws_need;
-    }
-    const size_t rad_need = size_t(cap) * 3 * sizeof(double);
-    if (f.rad_cap < rad_need) {
-        if (f.rad) (void)hipFree(f.rad);
-        f.rad = nullptr; f.rad_cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&f.rad), rad_need));
-        f.rad_cap = rad_need;
+    HIP_TRY(f.wf_ws.grow_bytes(ws_need));
+    HIP_TRY(f.rad.grow_bytes(size_t(cap) * 3 * sizeof(double)));
+    if (lens) {
+        HIP_TRY(f.cam_hit.grow(size_t(cap)));
+    } else {
+        HIP_TRY(f.hit_slots.grow(size_t(chunk_slots)));
+        HIP_TRY(f.surf.grow(size_t(chunk_slots)));
+        HIP_TRY(f.alive_base.grow(size_t(chunk_slots / 64 + 2)));
     }
     int rc = MCPT_OK;
-    if (lens) {
-        if ((rc = grow(&f.cam_hit, &f.cam_hit_cap, cap))) return rc;
-    } else {
-        if ((rc = grow(&f.hit_slots, &f.hit_slots_cap, chunk_slots))) return rc;
-        if ((rc = grow(&f.surf, &f.surf_cap, chunk_slots))) return rc;
-        if ((rc = grow(&f.alive_base, &f.alive_base_cap, chunk_slots / 64 + 2))) return rc;
-    }
     WfArgs a{};
     WfState A, B;
-    if (!wf_carve(f.wf_ws, f.wf_ws_bytes, cap, nl, A, B, a.rays)) return fail(MCPT_ERR_NOMEM, "wavefront workspace too small");
-    a.cap = cap; a.nl = nl; a.spp = spp; a.sample_base = r.k0; a.seed = p->seed; a.pixels = L.pixels; a.hit_slots = f.hit_slots; a.surf = f.surf; a.alive_base = f.alive_base; a.hits = f.hits;
-    a.dirs = d->dirs; a.rad = f.rad; a.counts = f.wf_counts; a.ctr = f.ctr; a.tris = d->tris; a.materials = d->materials; a.queue = fast ? f.queue : nullptr;
+    if (!wf_carve(f.wf_ws.get(), f.wf_ws.bytes(), cap, nl, A, B, a.rays)) return fail(MCPT_ERR_NOMEM, "wavefront workspace too small");
+    a.cap = cap; a.nl = nl; a.spp = spp; a.sample_base = r.k0; a.seed = p->seed; a.pixels = L.pixels; a.hit_slots = f.hit_slots.get(); a.surf = f.surf.get(); a.alive_base = f.alive_base.get();
+    a.hits = f.hits.get(); a.dirs = d->dirs.get(); a.rad = f.rad.get(); a.counts = f.wf_counts.get(); a.ctr = f.ctr.get(); a.tris = d->tris.get();
+    a.materials = d->materials.get(); a.queue = fast ? f.queue.get() : nullptr;
     a.finish_below = fast ? unsigned(std::min<long long>(std::max<long long>(d->finish_threshold, 0), 1ll << 30)) : 0u;
-    if (lens) { a.hits = nullptr; a.cam_hit = f.cam_hit; }
+    if (lens) { a.hits = nullptr; a.cam_hit = f.cam_hit.get(); }
     // Iterations are enqueued without waiting for their counts: every kernel reads its input count from the device slot the
     // previous one wrote.  The host looks at a count only every few iterations (to stop, and to size the next grids).
     const size_t ev_first = d->ev_used;
-    auto next_pair = [&](std::pair<hipEvent_t, hipEvent_t>*& out) -> int {
-        if (d->ev_used == d->ev_pool.size()) {
-            hipEvent_t e0, e1;
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            d->ev_pool.emplace_back(e0, e1);
-        }
-        out = &d->ev_pool[d->ev_used++];
-        return MCPT_OK;
-    };
     const int kSyncEvery = 4;
     for (int64_t first = 0; first < npx; first += chunk_slots) {
         const int n_slots = int(std::min<int64_t>(chunk_slots, npx - first));
-        HIP_TRY(hipMemsetAsync(f.wf_counts, 0, sizeof(WfCounts) * MCPT_WF_COUNT_SLOTS, st));
+        HIP_TRY(hipMemsetAsync(f.wf_counts.get(), 0, sizeof(WfCounts) * MCPT_WF_COUNT_SLOTS, st));
         long long n_upper = (long long)n_slots * spp;        // upper bound of the live paths, refined at every look
         double n_grid = double(n_upper);                     // grid-sizing estimate between looks (kernels stride, any grid is correct)
         a.first_slot = int(first);
@@ -1345,17 +1298,17 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
             launch_camera_pass(*lens, ac, n_upper, st);
             HIP_TRY(hipGetLastError());
             ac.nl = 0;          // the trace launch sees the bounce slot only (l == nl): no empty shadow-ray slots to walk past
-            std::pair<hipEvent_t, hipEvent_t>* pr = nullptr;
-            if (timed || keep) { if ((rc = next_pair(pr))) return rc; HIP_TRY(hipEventRecord(pr->first, st)); }
-            launch_wf_trace(d->ds, ac, n_upper, fast, f.queue, f.slow_list, d->slow_cap, st, d->cfg);
+            EventPair* pr = nullptr;
+            if (timed || keep) { if ((rc = next_pair(d->ev_pool, d->ev_used, pr))) return rc; HIP_TRY(hipEventRecord(pr->first.get(), st)); }
+            launch_wf_trace(d->ds, ac, n_upper, fast, f.queue.get(), f.slow_list.get(), d->slow_cap, st, d->cfg);
             HIP_TRY(hipGetLastError());
-            if (timed || keep) HIP_TRY(hipEventRecord(pr->second, st));
+            if (timed || keep) HIP_TRY(hipEventRecord(pr->second.get(), st));
             launches++;
             std::swap(a.in, a.out);
         } else {
-            launch_hit_slots(f.hits, int(first), n_slots, f.hit_slots, &f.wf_counts[0].n_next, st);
+            launch_hit_slots(f.hits.get(), int(first), n_slots, f.hit_slots.get(), &f.wf_counts[0].n_next, st);
             HIP_TRY(hipGetLastError());
-            launch_primary_surface(d->ds, a, f.surf, f.alive_base, &f.wf_counts[0].pad[2], n_slots, st);      // what the samples of a pixel share at their first vertex
+            launch_primary_surface(d->ds, a, f.surf.get(), f.alive_base.get(), &f.wf_counts[0].pad[2], n_slots, st);      // what the samples of a pixel share at their first vertex
             HIP_TRY(hipGetLastError());
         }
         for (int depth = 0; depth < MCPT_MAX_DEPTH && n_upper > 0; depth++) {
@@ -1366,7 +1319,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
             // the per-sample route's depth 0 resolves the camera rays: nothing went to the finishing kernel before it, and its pool form
             // (which reads a pixel's PrimaryHit at depth 0) does not adopt its paths
             const bool cam0 = lens && depth == 0;
-            char* const area = cam0 ? nullptr : f.path_area;
+            char* const area = cam0 ? nullptr : f.path_area.get();
             if (cam0) { WfArgs al = a; al.finish_below = 0u; launch_wf_logic(d->ds, al, n_launch, false, st, d->cfg); }
             else launch_wf_logic(d->ds, a, n_launch, depth == 0, st, d->cfg);
             HIP_TRY(hipGetLastError());
@@ -1375,13 +1328,13 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
             // finishing kernel is launched and the call returns while it runs -- the next frame's head can overlap it.
             const bool look = (depth + 1) % kSyncEvery == 0 || (a.finish_below && n_grid * 0.6 <= 6.0 * double(a.finish_below));
             if (look) {
-                HIP_TRY(hipEventRecord(d->look_ev, st));
-                HIP_TRY(hipStreamWaitEvent(d->look_stream, d->look_ev, 0));
-                HIP_TRY(hipMemcpyAsync(d->h_look, &f.wf_counts[depth + 1].n_next, sizeof(unsigned int), hipMemcpyDeviceToHost, d->look_stream));
-                HIP_TRY(hipStreamSynchronize(d->look_stream));
-                const unsigned int n_now = *d->h_look;
+                HIP_TRY(hipEventRecord(d->look_ev.get(), st));
+                HIP_TRY(hipStreamWaitEvent(d->look_stream.get(), d->look_ev.get(), 0));
+                HIP_TRY(hipMemcpyAsync(d->h_look.get(), &f.wf_counts[depth + 1].n_next, sizeof(unsigned int), hipMemcpyDeviceToHost, d->look_stream.get()));
+                HIP_TRY(hipStreamSynchronize(d->look_stream.get()));
+                const unsigned int n_now = d->h_look[0];
                 if (n_now <= a.finish_below) {
-                    if (n_now > 0) { launch_wf_finish(d->ds, a, (long long)n_now, st, d->cfg, area, f.slow_list, d->slow_cap); HIP_TRY(hipGetLastError()); }
+                    if (n_now > 0) { launch_wf_finish(d->ds, a, (long long)n_now, st, d->cfg, area, f.slow_list.get(), d->slow_cap); HIP_TRY(hipGetLastError()); }
                     n_upper = 0;
                     break;
                 }
@@ -1389,15 +1342,15 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
                 n_grid = double(n_now);
             } else if (a.finish_below) {
                 // few paths left (decided on the device from this pass's count): one lane per path runs them to the end
-                launch_wf_finish(d->ds, a, std::min<long long>(n_launch, (long long)a.finish_below), st, d->cfg, area, f.slow_list, d->slow_cap);
+                launch_wf_finish(d->ds, a, std::min<long long>(n_launch, (long long)a.finish_below), st, d->cfg, area, f.slow_list.get(), d->slow_cap);
                 HIP_TRY(hipGetLastError());
             }
             const long long n_trace = look ? (long long)n_grid : n_launch;
-            std::pair<hipEvent_t, hipEvent_t>* pr = nullptr;
-            if (timed || keep) { if ((rc = next_pair(pr))) return rc; HIP_TRY(hipEventRecord(pr->first, st)); }
-            launch_wf_trace(d->ds, a, n_trace, fast, f.queue, f.slow_list, d->slow_cap, st, d->cfg);
+            EventPair* pr = nullptr;
+            if (timed || keep) { if ((rc = next_pair(d->ev_pool, d->ev_used, pr))) return rc; HIP_TRY(hipEventRecord(pr->first.get(), st)); }
+            launch_wf_trace(d->ds, a, n_trace, fast, f.queue.get(), f.slow_list.get(), d->slow_cap, st, d->cfg);
             HIP_TRY(hipGetLastError());
-            if (timed || keep) HIP_TRY(hipEventRecord(pr->second, st));
+            if (timed || keep) HIP_TRY(hipEventRecord(pr->second.get(), st));
             launches++;
             std::swap(a.in, a.out);
             if (!look) n_grid *= 0.75;   // paths die at >= 40 % per bounce (Russian roulette 0.6)
@@ -1416,7 +1369,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
         HIP_TRY(hipStreamSynchronize(st));
         for (size_t i = ev_first; i < d->ev_used; i++) {
             float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, d->ev_pool[i].first, d->ev_pool[i].second));
+            HIP_TRY(hipEventElapsedTime(&ms, d->ev_pool[i].first.get(), d->ev_pool[i].second.get()));
             ms_trace += ms;
         }
         d->ev_used = ev_first;
@@ -1437,7 +1390,7 @@ int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_im
     int slot_used = -1;
     const SampleRange whole{0, p->spp, p->spp, nullptr, nullptr, &d->lens, nullptr};
     int rc = prepare_partition(d, p, static_cast<hipStream_t>(stream));
-    if (rc == MCPT_OK) rc = render_device_impl(d, whole, PixelList{d->pixels, d->n_pixels}, p, d_img, stats, static_cast<hipStream_t>(stream), slot_used);
+    if (rc == MCPT_OK) rc = render_device_impl(d, whole, PixelList{d->pixels.get(), d->n_pixels}, p, d_img, stats, static_cast<hipStream_t>(stream), slot_used);
     if (rc != MCPT_OK) {
         d->ev_used = ev_used0; d->frame_ev_used = frame_ev_used0;
         if (slot_used >= 0) d->slot[slot_used].keeping = false;      // its counters hold part of a frame: cleared by the next one
@@ -1454,12 +1407,12 @@ static int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelL
     if ((p->flags & MCPT_RENDER_PIPELINE) && !d->pipelined) {
         HIP_TRY(hipDeviceSynchronize());
         d->pipelined = true; d->wf_auto_budget = 0;                  // the budget now has to hold two frames
-        for (auto& q : d->slot) { if (q.wf_ws) (void)hipFree(q.wf_ws); q.wf_ws = nullptr; q.wf_ws_bytes = 0; }
+        for (auto& q : d->slot) q.wf_ws.reset();
     }
     const int si = (p->flags & MCPT_RENDER_PIPELINE) ? (d->next_slot ^= 1) : 0;
     slot_used = si;
     mcpt_device::FrameSlot& f = d->slot[si];
-    if (f.used) HIP_TRY(hipStreamWaitEvent(st, f.done, 0));
+    if (f.used) HIP_TRY(hipStreamWaitEvent(st, f.done.get(), 0));
     int rc = ensure_dirs(d, st);
     if (rc) return rc;
     const bool lensed = r.lens && lens_active(*r.lens);
@@ -1468,22 +1421,16 @@ static int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelL
     const int64_t npx = L.n;
     if (npx == 0) return MCPT_OK;
     const uint64_t primary_rays = uint64_t(npx) * (lensed ? uint64_t(r.n) : 1u);
-    if ((rc = grow(&f.hits, &f.hits_cap, npx))) return rc;
-    if (!keep || !f.keeping) HIP_TRY(hipMemsetAsync(f.ctr, 0, sizeof(DCounters), st));    // kept statistics accumulate until they are collected
+    HIP_TRY(f.hits.grow(size_t(npx)));
+    if (!keep || !f.keeping) HIP_TRY(hipMemsetAsync(f.ctr.get(), 0, sizeof(DCounters), st));    // kept statistics accumulate until they are collected
     f.keeping = keep;
-    std::pair<hipEvent_t, hipEvent_t>* fe = nullptr;
+    EventPair* fe = nullptr;
     if (keep) {
-        if (d->frame_ev_used == d->frame_ev.size()) {
-            hipEvent_t e0, e1;
-            HIP_TRY(hipEventCreate(&e0));
-            HIP_TRY(hipEventCreate(&e1));
-            d->frame_ev.emplace_back(e0, e1);
-        }
-        fe = &d->frame_ev[d->frame_ev_used++];
-        HIP_TRY(hipEventRecord(fe->first, st));
-    } else HIP_TRY(hipEventRecord(d->ev[0], st));
+        if ((rc = next_pair(d->frame_ev, d->frame_ev_used, fe))) return rc;
+        HIP_TRY(hipEventRecord(fe->first.get(), st));
+    } else HIP_TRY(hipEventRecord(d->ev[0].get(), st));
     if (!lensed) {          // (a lens traces its camera rays per sample, in the render path)
-        launch_primary_hits(d->ds, d->trace_mode == MCPT_TRACE_FAST, d->dirs, L.pixels, int(npx), f.hits, f.ctr, f.queue, f.slow_list, d->slow_cap, st, d->cfg);
+        launch_primary_hits(d->ds, d->trace_mode == MCPT_TRACE_FAST, d->dirs.get(), L.pixels, int(npx), f.hits.get(), f.ctr.get(), f.queue.get(), f.slow_list.get(), d->slow_cap, st, d->cfg);
         HIP_TRY(hipGetLastError());
     }
     double ms_trace = 0;
@@ -1492,18 +1439,18 @@ static int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelL
     else rc = render_wavefront(d, f, r, L, p, d_img, timed, keep, lensed ? &dl : nullptr, st, ms_trace, launches);
     if (rc) return rc;
     if (keep) {
-        HIP_TRY(hipEventRecord(fe->second, st));
+        HIP_TRY(hipEventRecord(fe->second.get(), st));
         d->kept_samples += uint64_t(npx) * uint64_t(r.n); d->kept_primary += primary_rays; d->kept_launches += launches;
-    } else HIP_TRY(hipEventRecord(d->ev[1], st));
-    HIP_TRY(hipEventRecord(f.done, st));
+    } else HIP_TRY(hipEventRecord(d->ev[1].get(), st));
+    HIP_TRY(hipEventRecord(f.done.get(), st));
     f.used = true;
     if (timed) {
         DCounters c{};
         HIP_TRY(hipStreamSynchronize(st));
-        HIP_TRY(hipMemcpy(&c, f.ctr, sizeof c, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&c, f.ctr.get(), sizeof c, hipMemcpyDeviceToHost));
         counters_to_stats(c, stats, d->knobs.print_diag != 0);
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, d->ev[0], d->ev[1]));
+        HIP_TRY(hipEventElapsedTime(&ms, d->ev[0].get(), d->ev[1].get()));
         stats->ms_total = ms; stats->ms_trace = ms_trace; stats->launches = launches;
         stats->samples = uint64_t(npx) * uint64_t(r.n);         // camera samples covered (a primary miss is a finished sample)
         stats->rays_primary = primary_rays;
@@ -1523,8 +1470,8 @@ int mcpt_device_collect_stats(mcpt_device* d, mcpt_stats* stats)
     DCounters sum{};
     for (auto& f : d->slot) {
         DCounters c{};
-        HIP_TRY(hipMemcpy(&c, f.ctr, sizeof c, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemset(f.ctr, 0, sizeof(DCounters)));
+        HIP_TRY(hipMemcpy(&c, f.ctr.get(), sizeof c, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemset(f.ctr.get(), 0, sizeof(DCounters)));
         unsigned long long* a = reinterpret_cast<unsigned long long*>(&sum);
         const unsigned long long* b = reinterpret_cast<const unsigned long long*>(&c);
         for (size_t i = 0; i < sizeof(DCounters) / sizeof(unsigned long long); i++) a[i] += b[i];
@@ -1535,12 +1482,12 @@ int mcpt_device_collect_stats(mcpt_device* d, mcpt_stats* stats)
     hipError_t bad = hipSuccess;
     for (size_t i = 0; i < d->ev_used; i++) {
         float ms = 0;
-        const hipError_t e = hipEventElapsedTime(&ms, d->ev_pool[i].first, d->ev_pool[i].second);
+        const hipError_t e = hipEventElapsedTime(&ms, d->ev_pool[i].first.get(), d->ev_pool[i].second.get());
         if (e == hipSuccess) stats->ms_trace += ms; else bad = e;
     }
     for (size_t i = 0; i < d->frame_ev_used; i++) {
         float ms = 0;
-        const hipError_t e = hipEventElapsedTime(&ms, d->frame_ev[i].first, d->frame_ev[i].second);
+        const hipError_t e = hipEventElapsedTime(&ms, d->frame_ev[i].first.get(), d->frame_ev[i].second.get());
         if (e == hipSuccess) stats->ms_total += ms; else bad = e;
     }
     stats->launches = d->kept_launches; stats->samples = d->kept_samples; stats->rays_primary = d->kept_primary;
@@ -1555,16 +1502,15 @@ int mcpt_render(mcpt_device* d, const mcpt_render_params* p, double* img, mcpt_s
     if (!d || !p || !img) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(d->ordinal));
     const size_t bytes = size_t(d->width) * d->height * 3 * sizeof(double);
-    double* d_img = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_img), bytes));
+    DevBuf<double> d_img;
+    HIP_TRY(d_img.alloc_bytes(bytes));
     // The caller's frame is pageable host memory: blocking copies on either side of the frame, which itself is ordered on d->stream.
-    hipError_t e = hipMemcpy(d_img, img, bytes, hipMemcpyHostToDevice);   // untouched pixels keep the caller's values
-    int rc = e == hipSuccess ? mcpt_render_device(d, p, d_img, stats, d->stream) : fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    hipError_t e = hipMemcpy(d_img.get(), img, bytes, hipMemcpyHostToDevice);   // untouched pixels keep the caller's values
+    int rc = e == hipSuccess ? mcpt_render_device(d, p, d_img.get(), stats, d->stream.get()) : fail(MCPT_ERR_HIP, hipGetErrorString(e));
     // also on failure: nothing of this frame may still be running when d_img goes
-    e = hipStreamSynchronize(d->stream);
-    if (rc == MCPT_OK && e == hipSuccess) e = hipMemcpy(img, d_img, bytes, hipMemcpyDeviceToHost);
+    e = hipStreamSynchronize(d->stream.get());
+    if (rc == MCPT_OK && e == hipSuccess) e = hipMemcpy(img, d_img.get(), bytes, hipMemcpyDeviceToHost);
     if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    (void)hipFree(d_img);
     return rc;
 }
 
@@ -1575,26 +1521,25 @@ int mcpt_sample_radiance(mcpt_device* d, uint64_t seed, const int32_t* pix, cons
     for (int64_t i = 0; i < n; i++)
         if (pix[i] < 0 || pix[i] >= d->width * d->height) return fail(MCPT_ERR_ARG, "pixel index out of range");
     HIP_TRY(hipSetDevice(d->ordinal));
-    int rc = ensure_dirs(d, d->stream);
+    int rc = ensure_dirs(d, d->stream.get());
     if (rc) return rc;
-    int32_t *d_pix = nullptr, *d_k = nullptr;
-    double* d_rgb = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_pix); (void)hipFree(d_k); (void)hipFree(d_rgb); };
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_pix), size_t(n) * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_k), size_t(n) * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_rgb), size_t(n) * 24);
-    if (e == hipSuccess) e = hipMemcpy(d_pix, pix, size_t(n) * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_k, k, size_t(n) * 4, hipMemcpyHostToDevice);
+    hipStream_t st = d->stream.get();
+    DevBuf<int32_t> d_pix, d_k;
+    DevBuf<double> d_rgb;
+    hipError_t e = d_pix.alloc(size_t(n));
+    if (e == hipSuccess) e = d_k.alloc(size_t(n));
+    if (e == hipSuccess) e = d_rgb.alloc(size_t(n) * 3);
+    if (e == hipSuccess) e = hipMemcpy(d_pix.get(), pix, size_t(n) * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_k.get(), k, size_t(n) * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         if (lens_active(d->lens)) {
-            if ((rc = ensure_pos(d, d->stream))) { cleanup(); return rc; }
-            launch_sample_radiance_lens(d->ds, lens_for(d, d->lens), seed, d_pix, d_k, n, d_rgb, d->aux_ctr, d->stream);
-        } else launch_sample_radiance(d->ds, seed, d->dirs, d_pix, d_k, n, d_rgb, d->aux_ctr, d->stream);
+            if ((rc = ensure_pos(d, st))) return rc;
+            launch_sample_radiance_lens(d->ds, lens_for(d, d->lens), seed, d_pix.get(), d_k.get(), n, d_rgb.get(), d->aux_ctr.get(), st);
+        } else launch_sample_radiance(d->ds, seed, d->dirs.get(), d_pix.get(), d_k.get(), n, d_rgb.get(), d->aux_ctr.get(), st);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-    if (e == hipSuccess) e = hipMemcpy(rgb, d_rgb, size_t(n) * 24, hipMemcpyDeviceToHost);
-    cleanup();
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = hipMemcpy(rgb, d_rgb.get(), size_t(n) * 24, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
     return MCPT_OK;
 }
@@ -1626,22 +1571,21 @@ int mcpt_camera_rays(mcpt_device* d, uint64_t seed, const int32_t* pix, const in
     for (int64_t i = 0; i < n; i++)
         if (pix[i] < 0 || pix[i] >= d->width * d->height) return fail(MCPT_ERR_ARG, "pixel index out of range");
     HIP_TRY(hipSetDevice(d->ordinal));
-    int rc = ensure_pos(d, d->stream);
+    int rc = ensure_pos(d, d->stream.get());
     if (rc) return rc;
-    int32_t *d_pix = nullptr, *d_k = nullptr;
-    double* d_rays = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_pix), size_t(n) * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_k), size_t(n) * 4);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_rays), size_t(n) * 48);
-    if (e == hipSuccess) e = hipMemcpy(d_pix, pix, size_t(n) * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_k, k, size_t(n) * 4, hipMemcpyHostToDevice);
+    DevBuf<int32_t> d_pix, d_k;
+    DevBuf<double> d_rays;
+    hipError_t e = d_pix.alloc(size_t(n));
+    if (e == hipSuccess) e = d_k.alloc(size_t(n));
+    if (e == hipSuccess) e = d_rays.alloc(size_t(n) * 6);
+    if (e == hipSuccess) e = hipMemcpy(d_pix.get(), pix, size_t(n) * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_k.get(), k, size_t(n) * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        launch_camera_rays(lens_for(d, d->lens), seed, d_pix, d_k, n, d_rays, d->stream);
+        launch_camera_rays(lens_for(d, d->lens), seed, d_pix.get(), d_k.get(), n, d_rays.get(), d->stream.get());
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-    if (e == hipSuccess) e = hipMemcpy(rays6, d_rays, size_t(n) * 48, hipMemcpyDeviceToHost);
-    (void)hipFree(d_pix); (void)hipFree(d_k); (void)hipFree(d_rays);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->stream.get());
+    if (e == hipSuccess) e = hipMemcpy(rays6, d_rays.get(), size_t(n) * 48, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
     return MCPT_OK;
 }
@@ -1655,53 +1599,45 @@ struct mcpt_progressive {
     mcpt_render_params p{};            // p.spp = N
     int done = 0;
     bool broken = false;               // a step failed half-way: the image and the moments hold part of a pass
-    int32_t* pixels = nullptr; int64_t n_pixels = 0;   // the owned pixels of (rank, world)
-    double* img = nullptr;             // W*H*3: the float fold of samples [0, done) (pixels not owned stay 0)
-    double* mom = nullptr;             // W*H*2*3: sum x, sum x*x per channel
-    uint8_t* hit = nullptr;            // W*H: the pixel's primary ray hit
-    double* partials = nullptr;        // noise_ranges() x 3
-    double* sums = nullptr;            // 4 doubles: sum se2, sum mean^2, hit pixels, 0
-    double* h_sums = nullptr;          // pinned copy of sums (the pass's one 32-byte read-back)
+    DevBuf<int32_t> pixels; int64_t n_pixels = 0;      // the owned pixels of (rank, world)
+    DevBuf<double> img;                // W*H*3: the float fold of samples [0, done) (pixels not owned stay 0)
+    DevBuf<double> mom;                // W*H*2*3: sum x, sum x*x per channel
+    DevBuf<uint8_t> hit;               // W*H: the pixel's primary ray hit
+    DevBuf<double> partials;           // noise_ranges() x 3
+    DevBuf<double> sums;               // 4 doubles: sum se2, sum mean^2, hit pixels, 0
+    HostBuf<double> h_sums;            // pinned copy of sums (the pass's one 32-byte read-back)
     std::vector<int32_t> owned;        // host copy of `pixels`
     // adaptive frames (mcpt_progressive_create_adaptive): the active list, double-buffered -- a pass renders active[cur][0..n_active) and
     // the selection writes the pixels that continue to active[cur ^ 1]
     bool adaptive = false;
     double rel2 = 0.0, abs2 = 0.0;     // rel_target^2, abs_target^2
     int min_spp = 0;
-    int32_t* active[2] = {nullptr, nullptr};
+    DevBuf<int32_t> active[2];
     int cur = 0;
     int64_t n_active = 0;
-    int32_t* cnt = nullptr;            // W*H: the samples each pixel holds (written for the listed pixels after every pass)
-    unsigned long long* masks = nullptr;                 // 4 * adaptive_blocks(n_pixels): the keep ballots of the selection
-    int32_t* block_counts = nullptr; int32_t* block_offsets = nullptr;   // adaptive_blocks(n_pixels) each
-    int32_t* total = nullptr;          // the next list's length
-    int32_t* h_total = nullptr;        // pinned copy of total (the pass's 4-byte read-back)
+    DevBuf<int32_t> cnt;               // W*H: the samples each pixel holds (written for the listed pixels after every pass)
+    DevBuf<unsigned long long> masks;  // 4 * adaptive_blocks(n_pixels): the keep ballots of the selection
+    DevBuf<int32_t> block_counts, block_offsets;   // adaptive_blocks(n_pixels) each
+    DevBuf<int32_t> total;             // the next list's length
+    HostBuf<int32_t> h_total;          // pinned copy of total (the pass's 4-byte read-back)
     // first-hit AOVs (W*H[*3], owned pixels written; computed on the first mcpt_progressive_aovs / _denoise call: they do not depend on
     // the samples) and the guide record the denoiser's taps read
     bool aov_ready = false;
-    int32_t* aov_mat = nullptr; double* aov_depth = nullptr; double* aov_normal = nullptr; double* aov_albedo = nullptr;
-    DenoiseGuide* guide = nullptr;
-    DenoisePix* dn_buf[2] = {nullptr, nullptr};   // the denoiser's ping-pong buffers (W*H each), allocated on its first call
+    DevBuf<int32_t> aov_mat; DevBuf<double> aov_depth, aov_normal, aov_albedo;
+    DevBuf<DenoiseGuide> guide;
+    DevBuf<DenoisePix> dn_buf[2];      // the denoiser's ping-pong buffers (W*H each), allocated on its first call
     mcpt_lens lens{};                  // the device's lens when the handle was created
-    int32_t* hitcnt = nullptr;         // W*H, under an active lens: the samples so far whose camera ray hit (hit = hitcnt > 0)
+    DevBuf<int32_t> hitcnt;            // W*H, under an active lens: the samples so far whose camera ray hit (hit = hitcnt > 0)
 };
 
 void mcpt_progressive_free(mcpt_progressive* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->d->ordinal);
-    (void)hipStreamSynchronize(h->d->stream);
-    for (void* q : {static_cast<void*>(h->pixels), static_cast<void*>(h->img), static_cast<void*>(h->mom), static_cast<void*>(h->hit),
-                    static_cast<void*>(h->partials), static_cast<void*>(h->sums), static_cast<void*>(h->active[0]), static_cast<void*>(h->active[1]),
-                    static_cast<void*>(h->cnt), static_cast<void*>(h->masks), static_cast<void*>(h->block_counts),
-                    static_cast<void*>(h->block_offsets), static_cast<void*>(h->total), static_cast<void*>(h->aov_mat),
-                    static_cast<void*>(h->aov_depth), static_cast<void*>(h->aov_normal), static_cast<void*>(h->aov_albedo),
-                    static_cast<void*>(h->guide), static_cast<void*>(h->dn_buf[0]), static_cast<void*>(h->dn_buf[1]), static_cast<void*>(h->hitcnt)})
-        if (q) (void)hipFree(q);
-    if (h->h_sums) (void)hipHostFree(h->h_sums);
-    if (h->h_total) (void)hipHostFree(h->h_total);
-    mcpt_device_free(h->d);
-    delete h;
+    (void)hipStreamSynchronize(h->d->stream.get());
+    mcpt_device* d = h->d;
+    delete h;                          // its buffers go before the device reference
+    mcpt_device_free(d);
 }
 
 // ap == null: a uniform frame; otherwise an adaptive one (arguments checked by the caller)
@@ -1716,44 +1652,38 @@ static int progressive_create(mcpt_device* d, const mcpt_render_params* p, const
     std::vector<int32_t> v;
     owned_pixel_list(d->width, d->height, tw, th, rank, world, v);
     const size_t px = size_t(d->width) * d->height;
-    auto* h = new mcpt_progressive;
+    std::unique_ptr<mcpt_progressive, void (*)(mcpt_progressive*)> h(new mcpt_progressive, mcpt_progressive_free);
     h->d = d; d->refs.fetch_add(1);
     h->p = *p;
     h->lens = d->lens;
     h->n_pixels = int64_t(v.size());
-    int rc = upload(v, &h->pixels);
-    hipError_t e = hipSuccess;
-    if (rc == MCPT_OK) {
-        auto alloc = [&](void** q, size_t bytes) { if (e == hipSuccess) e = hipMalloc(q, std::max<size_t>(bytes, 8)); if (e == hipSuccess) e = hipMemset(*q, 0, std::max<size_t>(bytes, 8)); };
-        alloc(reinterpret_cast<void**>(&h->img), px * 3 * sizeof(double));
-        alloc(reinterpret_cast<void**>(&h->mom), px * 6 * sizeof(double));
-        alloc(reinterpret_cast<void**>(&h->hit), px);
-        if (lens_active(h->lens)) alloc(reinterpret_cast<void**>(&h->hitcnt), px * sizeof(int32_t));
-        alloc(reinterpret_cast<void**>(&h->partials), size_t(kNoiseRanges) * 3 * sizeof(double));
-        alloc(reinterpret_cast<void**>(&h->sums), 4 * sizeof(double));
-        if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_sums), 4 * sizeof(double), hipHostMallocDefault);
-        if (ap) {
-            const size_t blocks = size_t(adaptive_blocks(int(v.size())));
-            alloc(reinterpret_cast<void**>(&h->active[0]), v.size() * sizeof(int32_t));
-            alloc(reinterpret_cast<void**>(&h->active[1]), v.size() * sizeof(int32_t));
-            alloc(reinterpret_cast<void**>(&h->cnt), px * sizeof(int32_t));
-            alloc(reinterpret_cast<void**>(&h->masks), blocks * 4 * sizeof(unsigned long long));
-            alloc(reinterpret_cast<void**>(&h->block_counts), blocks * sizeof(int32_t));
-            alloc(reinterpret_cast<void**>(&h->block_offsets), blocks * sizeof(int32_t));
-            alloc(reinterpret_cast<void**>(&h->total), sizeof(int32_t));
-            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&h->h_total), sizeof(int32_t), hipHostMallocDefault);
-            if (e == hipSuccess && !v.empty()) e = hipMemcpy(h->active[0], h->pixels, v.size() * sizeof(int32_t), hipMemcpyDeviceToDevice);
-            h->adaptive = true;
-            h->rel2 = ap->rel_target * ap->rel_target;
-            h->abs2 = ap->abs_target * ap->abs_target;
-            h->min_spp = std::min(ap->min_spp, p->spp);
-            h->n_active = h->n_pixels;
-        }
-        if (e != hipSuccess) rc = fail(MCPT_ERR_HIP, std::string("progressive frame buffers: ") + hipGetErrorString(e));
+    HIP_TRY(h->pixels.upload(v));
+    HIP_TRY(alloc_zeroed(h->img, px * 3 * sizeof(double)));
+    HIP_TRY(alloc_zeroed(h->mom, px * 6 * sizeof(double)));
+    HIP_TRY(alloc_zeroed(h->hit, px));
+    if (lens_active(h->lens)) HIP_TRY(alloc_zeroed(h->hitcnt, px * sizeof(int32_t)));
+    HIP_TRY(alloc_zeroed(h->partials, size_t(kNoiseRanges) * 3 * sizeof(double)));
+    HIP_TRY(alloc_zeroed(h->sums, 4 * sizeof(double)));
+    HIP_TRY(h->h_sums.alloc(4));
+    if (ap) {
+        const size_t blocks = size_t(adaptive_blocks(int(v.size())));
+        HIP_TRY(alloc_zeroed(h->active[0], v.size() * sizeof(int32_t)));
+        HIP_TRY(alloc_zeroed(h->active[1], v.size() * sizeof(int32_t)));
+        HIP_TRY(alloc_zeroed(h->cnt, px * sizeof(int32_t)));
+        HIP_TRY(alloc_zeroed(h->masks, blocks * 4 * sizeof(unsigned long long)));
+        HIP_TRY(alloc_zeroed(h->block_counts, blocks * sizeof(int32_t)));
+        HIP_TRY(alloc_zeroed(h->block_offsets, blocks * sizeof(int32_t)));
+        HIP_TRY(alloc_zeroed(h->total, sizeof(int32_t)));
+        HIP_TRY(h->h_total.alloc(1));
+        if (!v.empty()) HIP_TRY(hipMemcpy(h->active[0].get(), h->pixels.get(), v.size() * sizeof(int32_t), hipMemcpyDeviceToDevice));
+        h->adaptive = true;
+        h->rel2 = ap->rel_target * ap->rel_target;
+        h->abs2 = ap->abs_target * ap->abs_target;
+        h->min_spp = std::min(ap->min_spp, p->spp);
+        h->n_active = h->n_pixels;
     }
-    if (rc != MCPT_OK) { mcpt_progressive_free(h); return rc; }
     h->owned = std::move(v);
-    *out = h;
+    *out = h.release();
     return MCPT_OK;
 }
 
@@ -1791,24 +1721,24 @@ int mcpt_progressive_step(mcpt_progressive* h, int32_t n, mcpt_stats* stats)
     if (stats) std::memset(stats, 0, sizeof *stats);
     mcpt_render_params q = h->p;
     q.spp = std::min(n, h->p.spp - h->done);
-    const SampleRange r{h->done, q.spp, h->p.spp, h->mom, h->hit, &h->lens, h->hitcnt};
-    const PixelList L = h->adaptive ? PixelList{h->active[h->cur], h->n_active} : PixelList{h->pixels, h->n_pixels};
+    const SampleRange r{h->done, q.spp, h->p.spp, h->mom.get(), h->hit.get(), &h->lens, h->hitcnt.get()};
+    const PixelList L = h->adaptive ? PixelList{h->active[h->cur].get(), h->n_active} : PixelList{h->pixels.get(), h->n_pixels};
     const size_t ev_used0 = d->ev_used;
     int slot_used = -1;
-    int rc = render_device_impl(d, r, L, &q, h->img, stats, d->stream, slot_used);
+    int rc = render_device_impl(d, r, L, &q, h->img.get(), stats, d->stream.get(), slot_used);
     if (rc == MCPT_OK && h->adaptive) {
         // which pixels continue: decided on the device; the host reads back the new list's length only
-        launch_adaptive_select(L.pixels, int(L.n), h->mom, h->hit, h->done + q.spp, h->min_spp, h->rel2, h->abs2, h->cnt, h->masks,
-                               h->block_counts, h->block_offsets, h->total, h->active[h->cur ^ 1], d->stream);
+        launch_adaptive_select(L.pixels, int(L.n), h->mom.get(), h->hit.get(), h->done + q.spp, h->min_spp, h->rel2, h->abs2, h->cnt.get(), h->masks.get(),
+                               h->block_counts.get(), h->block_offsets.get(), h->total.get(), h->active[h->cur ^ 1].get(), d->stream.get());
         hipError_t le = hipGetLastError();
-        if (le == hipSuccess) le = hipMemcpyAsync(h->h_total, h->total, sizeof(int32_t), hipMemcpyDeviceToHost, d->stream);
+        if (le == hipSuccess) le = hipMemcpyAsync(h->h_total.get(), h->total.get(), sizeof(int32_t), hipMemcpyDeviceToHost, d->stream.get());
         if (le != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(le));
     }
-    const hipError_t e = hipStreamSynchronize(d->stream);
+    const hipError_t e = hipStreamSynchronize(d->stream.get());
     if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
     if (rc != MCPT_OK) { d->ev_used = ev_used0; h->broken = true; return rc; }
     h->done += q.spp;
-    if (h->adaptive) { h->n_active = *h->h_total; h->cur ^= 1; }
+    if (h->adaptive) { h->n_active = h->h_total[0]; h->cur ^= 1; }
     return MCPT_OK;
 }
 
@@ -1825,7 +1755,7 @@ int64_t mcpt_progressive_active_pixels(mcpt_progressive* h, int32_t* pixels)
     if (n <= 0 || !pixels) return n;
     if (!h->adaptive) { std::memcpy(pixels, h->owned.data(), size_t(n) * sizeof(int32_t)); return n; }
     HIP_TRY(hipSetDevice(h->d->ordinal));
-    HIP_TRY(hipMemcpy(pixels, h->active[h->cur], size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pixels, h->active[h->cur].get(), size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
     return n;
 }
 
@@ -1838,7 +1768,7 @@ int mcpt_progressive_sample_counts(mcpt_progressive* h, int32_t* counts)
     }
     HIP_TRY(hipSetDevice(h->d->ordinal));
     std::vector<int32_t> all(size_t(h->d->width) * h->d->height);
-    HIP_TRY(hipMemcpy(all.data(), h->cnt, all.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(all.data(), h->cnt.get(), all.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     for (int32_t pix : h->owned) counts[pix] = all[size_t(pix)];
     return MCPT_OK;
 }
@@ -1852,10 +1782,10 @@ int mcpt_progressive_noise(mcpt_progressive* h, mcpt_noise* o)
     o->done = h->done; o->spp = h->p.spp;
     if (h->done < 2) { o->rel_error = o->abs_rms = INFINITY; return MCPT_OK; }     // no variance estimate from fewer than two samples
     HIP_TRY(hipSetDevice(h->d->ordinal));
-    hipStream_t st = h->d->stream;
-    launch_noise_reduce(h->pixels, h->n_pixels, h->mom, h->hit, h->done, h->cnt, h->partials, h->sums, st);
+    hipStream_t st = h->d->stream.get();
+    launch_noise_reduce(h->pixels.get(), h->n_pixels, h->mom.get(), h->hit.get(), h->done, h->cnt.get(), h->partials.get(), h->sums.get(), st);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(h->h_sums, h->sums, 4 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h->h_sums.get(), h->sums.get(), 4 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     o->sum_se2 = h->h_sums[0]; o->sum_mean2 = h->h_sums[1]; o->pixels = int64_t(h->h_sums[2]);
     o->rel_error = o->sum_mean2 > 0 ? std::sqrt(o->sum_se2 / o->sum_mean2) : (o->sum_se2 > 0 ? INFINITY : 0.0);
@@ -1867,7 +1797,7 @@ int mcpt_progressive_image_device(mcpt_progressive* h, double* d_img, double* d_
 {
     if (!h || (!d_img && !d_stderr)) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->d->ordinal));
-    launch_progressive_image(h->pixels, h->n_pixels, h->img, h->mom, h->done, h->cnt, h->p.spp, d_img, d_stderr, static_cast<hipStream_t>(stream));
+    launch_progressive_image(h->pixels.get(), h->n_pixels, h->img.get(), h->mom.get(), h->done, h->cnt.get(), h->p.spp, d_img, d_stderr, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MCPT_OK;
 }
@@ -1877,17 +1807,16 @@ int mcpt_progressive_image(mcpt_progressive* h, double* img, double* stderr_img)
     if (!h || (!img && !stderr_img)) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->d->ordinal));
     const size_t bytes = size_t(h->d->width) * h->d->height * 3 * sizeof(double);
-    double *d_est = nullptr, *d_err = nullptr;
+    DevBuf<double> d_est, d_err;
     // pageable host buffers: blocking copies either side; pixels this rank does not own keep the caller's values
     hipError_t e = hipSuccess;
-    if (img) { e = hipMalloc(reinterpret_cast<void**>(&d_est), bytes); if (e == hipSuccess) e = hipMemcpy(d_est, img, bytes, hipMemcpyHostToDevice); }
-    if (e == hipSuccess && stderr_img) { e = hipMalloc(reinterpret_cast<void**>(&d_err), bytes); if (e == hipSuccess) e = hipMemcpy(d_err, stderr_img, bytes, hipMemcpyHostToDevice); }
-    int rc = e == hipSuccess ? mcpt_progressive_image_device(h, d_est, d_err, h->d->stream) : fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    e = hipStreamSynchronize(h->d->stream);
-    if (rc == MCPT_OK && e == hipSuccess && img) e = hipMemcpy(img, d_est, bytes, hipMemcpyDeviceToHost);
-    if (rc == MCPT_OK && e == hipSuccess && stderr_img) e = hipMemcpy(stderr_img, d_err, bytes, hipMemcpyDeviceToHost);
+    if (img) { e = d_est.alloc_bytes(bytes); if (e == hipSuccess) e = hipMemcpy(d_est.get(), img, bytes, hipMemcpyHostToDevice); }
+    if (e == hipSuccess && stderr_img) { e = d_err.alloc_bytes(bytes); if (e == hipSuccess) e = hipMemcpy(d_err.get(), stderr_img, bytes, hipMemcpyHostToDevice); }
+    int rc = e == hipSuccess ? mcpt_progressive_image_device(h, d_est.get(), d_err.get(), h->d->stream.get()) : fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    e = hipStreamSynchronize(h->d->stream.get());
+    if (rc == MCPT_OK && e == hipSuccess && img) e = hipMemcpy(img, d_est.get(), bytes, hipMemcpyDeviceToHost);
+    if (rc == MCPT_OK && e == hipSuccess && stderr_img) e = hipMemcpy(stderr_img, d_err.get(), bytes, hipMemcpyDeviceToHost);
     if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    (void)hipFree(d_est); (void)hipFree(d_err);
     return rc;
 }
 
@@ -1897,33 +1826,30 @@ static int ensure_aovs(mcpt_progressive* h)
 {
     if (h->aov_ready) return MCPT_OK;
     mcpt_device* d = h->d;
-    hipStream_t st = d->stream;
+    hipStream_t st = d->stream.get();
     int rc = ensure_dirs(d, st);
     if (rc) return rc;
     const size_t px = size_t(d->width) * d->height;
-    PrimaryHit* hits = nullptr;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](void** q, size_t bytes) { if (e == hipSuccess && !*q) e = hipMalloc(q, std::max<size_t>(bytes, 8)); };
-    alloc(reinterpret_cast<void**>(&hits), size_t(h->n_pixels) * sizeof(PrimaryHit));
-    alloc(reinterpret_cast<void**>(&h->aov_mat), px * sizeof(int32_t));
-    alloc(reinterpret_cast<void**>(&h->aov_depth), px * sizeof(double));
-    alloc(reinterpret_cast<void**>(&h->aov_normal), px * 3 * sizeof(double));
-    alloc(reinterpret_cast<void**>(&h->aov_albedo), px * 3 * sizeof(double));
-    alloc(reinterpret_cast<void**>(&h->guide), px * sizeof(DenoiseGuide));
+    DevBuf<PrimaryHit> hits;
+    hipError_t e = alloc_once(hits, size_t(h->n_pixels) * sizeof(PrimaryHit));
+    if (e == hipSuccess) e = alloc_once(h->aov_mat, px * sizeof(int32_t));
+    if (e == hipSuccess) e = alloc_once(h->aov_depth, px * sizeof(double));
+    if (e == hipSuccess) e = alloc_once(h->aov_normal, px * 3 * sizeof(double));
+    if (e == hipSuccess) e = alloc_once(h->aov_albedo, px * 3 * sizeof(double));
+    if (e == hipSuccess) e = alloc_once(h->guide, px * sizeof(DenoiseGuide));
     // pixels not owned: material -1 everywhere in the guide (all bits set), so that no tap reads them
-    if (e == hipSuccess) e = hipMemsetAsync(h->guide, 0xff, px * sizeof(DenoiseGuide), st);
+    if (e == hipSuccess) e = hipMemsetAsync(h->guide.get(), 0xff, px * sizeof(DenoiseGuide), st);
     if (e == hipSuccess) {
-        launch_primary_hits(d->ds, d->trace_mode == MCPT_TRACE_FAST, d->dirs, h->pixels, int(h->n_pixels), hits, d->aux_ctr, d->aux_queue,
-                            d->aux_slow_list, d->slow_cap, st, d->cfg);
+        launch_primary_hits(d->ds, d->trace_mode == MCPT_TRACE_FAST, d->dirs.get(), h->pixels.get(), int(h->n_pixels), hits.get(), d->aux_ctr.get(), d->aux_queue.get(),
+                            d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
         e = hipGetLastError();
     }
     if (e == hipSuccess) {
-        launch_primary_aov(d->ds, h->pixels, int(h->n_pixels), hits, h->aov_mat, h->aov_depth, h->aov_normal, h->aov_albedo, h->guide, st);
+        launch_primary_aov(d->ds, h->pixels.get(), int(h->n_pixels), hits.get(), h->aov_mat.get(), h->aov_depth.get(), h->aov_normal.get(), h->aov_albedo.get(), h->guide.get(), st);
         e = hipGetLastError();
     }
     const hipError_t es = hipStreamSynchronize(st);
     if (e == hipSuccess) e = es;
-    if (hits) (void)hipFree(hits);
     if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("first-hit AOVs: ") + hipGetErrorString(e));
     h->aov_ready = true;
     return MCPT_OK;
@@ -1944,10 +1870,10 @@ int mcpt_progressive_aovs(mcpt_progressive* h, int32_t* material, double* depth,
         for (int32_t pix : h->owned) std::memcpy(static_cast<uint8_t*>(dst) + size_t(pix) * per_pixel, all.data() + size_t(pix) * per_pixel, per_pixel);
         return MCPT_OK;
     };
-    if ((rc = fetch(h->aov_mat, material, sizeof(int32_t)))) return rc;
-    if ((rc = fetch(h->aov_depth, depth, sizeof(double)))) return rc;
-    if ((rc = fetch(h->aov_normal, normal, 3 * sizeof(double)))) return rc;
-    return fetch(h->aov_albedo, albedo, 3 * sizeof(double));
+    if ((rc = fetch(h->aov_mat.get(), material, sizeof(int32_t)))) return rc;
+    if ((rc = fetch(h->aov_depth.get(), depth, sizeof(double)))) return rc;
+    if ((rc = fetch(h->aov_normal.get(), normal, 3 * sizeof(double)))) return rc;
+    return fetch(h->aov_albedo.get(), albedo, 3 * sizeof(double));
 }
 
 static int denoise_args(const mcpt_progressive* h, const mcpt_denoise_params* dp, int& iterations, double& sigma_l, double& sigma_z)
@@ -1978,9 +1904,9 @@ int mcpt_progressive_denoise_device(mcpt_progressive* h, const mcpt_denoise_para
     if ((rc = ensure_aovs(h))) return rc;
     const size_t px = size_t(h->d->width) * h->d->height;
     for (auto& b : h->dn_buf)
-        if (!b) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b), std::max<size_t>(px, 1) * sizeof(DenoisePix)));
-    launch_denoise(h->pixels, h->n_pixels, h->d->width, h->d->height, h->img, h->mom, h->done, h->cnt, h->p.spp, h->aov_albedo, h->guide,
-                   iterations, sigma_l, sigma_z, h->dn_buf[0], h->dn_buf[1], d_img, static_cast<hipStream_t>(stream));
+        if (!b) HIP_TRY(b.alloc(px));
+    launch_denoise(h->pixels.get(), h->n_pixels, h->d->width, h->d->height, h->img.get(), h->mom.get(), h->done, h->cnt.get(), h->p.spp, h->aov_albedo.get(), h->guide.get(),
+                   iterations, sigma_l, sigma_z, h->dn_buf[0].get(), h->dn_buf[1].get(), d_img, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MCPT_OK;
 }
@@ -1994,15 +1920,14 @@ int mcpt_progressive_denoise(mcpt_progressive* h, const mcpt_denoise_params* dp,
     if (!img) return fail(MCPT_ERR_ARG, "null image");
     HIP_TRY(hipSetDevice(h->d->ordinal));
     const size_t bytes = size_t(h->d->width) * h->d->height * 3 * sizeof(double);
-    double* d_out = nullptr;
+    DevBuf<double> d_out;
     // pageable host buffer: blocking copies either side; pixels this rank does not own keep the caller's values
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_out), bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_out, img, bytes, hipMemcpyHostToDevice);
-    rc = e == hipSuccess ? mcpt_progressive_denoise_device(h, dp, d_out, h->d->stream) : fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    e = hipStreamSynchronize(h->d->stream);
-    if (rc == MCPT_OK && e == hipSuccess) e = hipMemcpy(img, d_out, bytes, hipMemcpyDeviceToHost);
+    hipError_t e = d_out.alloc_bytes(bytes);
+    if (e == hipSuccess) e = hipMemcpy(d_out.get(), img, bytes, hipMemcpyHostToDevice);
+    rc = e == hipSuccess ? mcpt_progressive_denoise_device(h, dp, d_out.get(), h->d->stream.get()) : fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    e = hipStreamSynchronize(h->d->stream.get());
+    if (rc == MCPT_OK && e == hipSuccess) e = hipMemcpy(img, d_out.get(), bytes, hipMemcpyDeviceToHost);
     if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    (void)hipFree(d_out);
     return rc;
 }
 

@@ -19,10 +19,11 @@
 #include <vector>
 
 #include "../../include/mcpt.h"
+#include "hip_owned.hpp"
 #include "kernels.hpp"
 
-namespace mcpt { int set_error(int code, const std::string& msg); }
-static int fail(int code, const std::string& msg) { return mcpt::set_error(code, msg); }
+using mcpt::DevBuf;
+using mcpt::Event;
 
 namespace {
 
@@ -57,21 +58,22 @@ struct RcclApi {
     }
 };
 
+// A rank's buffers live on two GPUs: free_lists and mcpt_multi_free release each group with reset() while its device is current.
 struct Rank {
     int ordinal = 0;
     mcpt_device* dev = nullptr;
-    hipStream_t stream = nullptr;
-    double* d_frame = nullptr;          // this rank's full-size frame (only its own pixels are written); rank 0's is THE frame
-    int32_t* d_pixels = nullptr;        // its pixel list, on its GPU
-    double* d_compact = nullptr;        // [n][3] on its GPU
+    mcpt::Stream stream;
+    DevBuf<double> d_frame;             // this rank's full-size frame (only its own pixels are written); rank 0's is THE frame
+    DevBuf<int32_t> d_pixels;           // its pixel list, on its GPU
+    DevBuf<double> d_compact;           // [n][3] on its GPU
     int64_t n = 0;
     // on devices[0]:
-    double* d_stage = nullptr;          // [n][3] where the compact buffer lands
-    int32_t* d_pixels0 = nullptr;       // the same pixel list on devices[0]
+    DevBuf<double> d_stage;             // [n][3] where the compact buffer lands
+    DevBuf<int32_t> d_pixels0;          // the same pixel list on devices[0]
     mcpt_stats stats{};
     int rc = MCPT_OK;
     std::string err;
-    hipEvent_t ev_start = nullptr, ev_rendered = nullptr;   // on the rank's stream: before its render / after its render (timing report)
+    Event ev_start, ev_rendered;        // on the rank's stream: before its render / after its render (timing report)
     float render_ms = 0;
 };
 
@@ -139,27 +141,21 @@ struct mcpt_multi {
     std::vector<Rank> ranks;
     RcclApi rccl;
     std::vector<ncclComm_t> comms;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev_gather = nullptr;   // on devices[0]'s stream: frame start, frame end, its own render done
+    Event ev0, ev1, ev_gather;          // on devices[0]'s stream: frame start, frame end, its own render done
     float gather_ms = 0;                // last frame: from rank 0's render being done to the last unpack (what the exchange adds)
     Workers workers;
 };
-
-#define HIP_OR_FAIL(expr)                                                                               \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(MCPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 static void free_lists(mcpt_multi* m)
 {
     for (Rank& r : m->ranks) {
         (void)hipSetDevice(r.ordinal);
-        if (r.d_pixels) (void)hipFree(r.d_pixels);
-        if (r.d_compact) (void)hipFree(r.d_compact);
+        r.d_pixels.reset();
+        r.d_compact.reset();
         (void)hipSetDevice(m->ranks[0].ordinal);
-        if (r.d_stage) (void)hipFree(r.d_stage);
-        if (r.d_pixels0) (void)hipFree(r.d_pixels0);
-        r.d_pixels = r.d_pixels0 = nullptr; r.d_compact = r.d_stage = nullptr; r.n = 0;
+        r.d_stage.reset();
+        r.d_pixels0.reset();
+        r.n = 0;
     }
 }
 
@@ -180,16 +176,13 @@ static int prepare_lists(mcpt_multi* m, const mcpt_render_params* p)
         std::vector<int32_t> pix(size_t(std::max<int64_t>(n, 1)));
         if (n > 0 && mcpt_owned_pixels(m->scene, &q, pix.data()) != n) return fail(MCPT_ERR_ARG, "pixel partition changed between two calls");
         R.n = n;
-        const size_t lb = pix.size() * sizeof(int32_t), cb = pix.size() * 3 * sizeof(double);
-        HIP_OR_FAIL(hipSetDevice(R.ordinal));
-        HIP_OR_FAIL(hipMalloc(reinterpret_cast<void**>(&R.d_pixels), lb));
-        HIP_OR_FAIL(hipMemcpy(R.d_pixels, pix.data(), lb, hipMemcpyHostToDevice));
+        HIP_TRY(hipSetDevice(R.ordinal));
+        HIP_TRY(R.d_pixels.upload(pix));
         if (r > 0) {
-            HIP_OR_FAIL(hipMalloc(reinterpret_cast<void**>(&R.d_compact), cb));
-            HIP_OR_FAIL(hipSetDevice(m->ranks[0].ordinal));
-            HIP_OR_FAIL(hipMalloc(reinterpret_cast<void**>(&R.d_stage), cb));
-            HIP_OR_FAIL(hipMalloc(reinterpret_cast<void**>(&R.d_pixels0), lb));
-            HIP_OR_FAIL(hipMemcpy(R.d_pixels0, pix.data(), lb, hipMemcpyHostToDevice));
+            HIP_TRY(R.d_compact.alloc(pix.size() * 3));
+            HIP_TRY(hipSetDevice(m->ranks[0].ordinal));
+            HIP_TRY(R.d_stage.alloc(pix.size() * 3));
+            HIP_TRY(R.d_pixels0.upload(pix));
         }
     }
     std::memcpy(m->part_key, key, sizeof key);
@@ -207,15 +200,15 @@ void mcpt_multi_free(mcpt_multi* m)
         if (m->comms[i] && m->rccl.CommDestroy) { (void)hipSetDevice(m->ranks[i].ordinal); (void)m->rccl.CommDestroy(m->comms[i]); }
     for (Rank& r : m->ranks) {
         (void)hipSetDevice(r.ordinal);
-        if (r.d_frame) (void)hipFree(r.d_frame);
-        if (r.ev_start) (void)hipEventDestroy(r.ev_start);
-        if (r.ev_rendered) (void)hipEventDestroy(r.ev_rendered);
-        if (r.stream) (void)hipStreamDestroy(r.stream);
+        r.d_frame.reset();
+        r.ev_start.reset();
+        r.ev_rendered.reset();
+        r.stream.reset();
         if (r.dev) mcpt_device_free(r.dev);
     }
-    if (m->ev0) (void)hipEventDestroy(m->ev0);
-    if (m->ev1) (void)hipEventDestroy(m->ev1);
-    if (m->ev_gather) (void)hipEventDestroy(m->ev_gather);
+    m->ev0.reset();
+    m->ev1.reset();
+    m->ev_gather.reset();
     if (m->rccl.lib) dlclose(m->rccl.lib);
     delete m;
 }
@@ -269,11 +262,11 @@ int mcpt_multi_create(const mcpt_scene* scene, const int32_t* devices, int32_t n
         R.rc = mcpt_device_create_ex(scene, R.ordinal, build_mode, &R.dev);
         if (R.rc) { R.err = mcpt_last_error(); return; }
         hipError_t e = hipSetDevice(R.ordinal);
-        if (e == hipSuccess) e = hipStreamCreateWithFlags(&R.stream, hipStreamNonBlocking);
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&R.d_frame), frame_bytes);
-        if (e == hipSuccess) e = hipMemset(R.d_frame, 0, frame_bytes);
-        if (e == hipSuccess) e = hipEventCreate(&R.ev_start);
-        if (e == hipSuccess) e = hipEventCreate(&R.ev_rendered);
+        if (e == hipSuccess) e = create(R.stream, hipStreamCreateWithFlags, hipStreamNonBlocking);
+        if (e == hipSuccess) e = R.d_frame.alloc_bytes(frame_bytes);
+        if (e == hipSuccess) e = hipMemset(R.d_frame.get(), 0, frame_bytes);
+        if (e == hipSuccess) e = create(R.ev_start, hipEventCreate);
+        if (e == hipSuccess) e = create(R.ev_rendered, hipEventCreate);
         if (e != hipSuccess) { R.rc = MCPT_ERR_HIP; R.err = std::string("multi-device setup: ") + hipGetErrorString(e); }
     };
     {
@@ -294,10 +287,10 @@ int mcpt_multi_create(const mcpt_scene* scene, const int32_t* devices, int32_t n
             if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
         }
     }
-    HIP_OR_FAIL(hipSetDevice(m->ranks[0].ordinal));
-    HIP_OR_FAIL(hipEventCreate(&m->ev0));
-    HIP_OR_FAIL(hipEventCreate(&m->ev1));
-    HIP_OR_FAIL(hipEventCreate(&m->ev_gather));
+    HIP_TRY(hipSetDevice(m->ranks[0].ordinal));
+    HIP_TRY(create(m->ev0, hipEventCreate));
+    HIP_TRY(create(m->ev1, hipEventCreate));
+    HIP_TRY(create(m->ev_gather, hipEventCreate));
     m->workers.start(int(m->ranks.size()));
     if (gather == MCPT_GATHER_RCCL) {
         std::string err;
@@ -320,8 +313,8 @@ int mcpt_multi_render_device(mcpt_multi* m, const mcpt_render_params* p, double*
     if (rc) return rc;
     const int world = int(m->ranks.size());
     Rank& R0 = m->ranks[0];
-    HIP_OR_FAIL(hipSetDevice(R0.ordinal));
-    HIP_OR_FAIL(hipEventRecord(m->ev0, R0.stream));
+    HIP_TRY(hipSetDevice(R0.ordinal));
+    HIP_TRY(hipEventRecord(m->ev0.get(), R0.stream.get()));
     const bool rccl = m->gather == MCPT_GATHER_RCCL && world > 1;
     const bool keep = (p->flags & MCPT_RENDER_KEEP_STATS) != 0 && !(p->flags & MCPT_RENDER_MEGAKERNEL);
     // one thread per GPU: render the rank's tiles, pack them, (peer mode) send them to devices[0]
@@ -331,23 +324,23 @@ int mcpt_multi_render_device(mcpt_multi* m, const mcpt_render_params* p, double*
         q.rank = r; q.world = world;
         R.rc = MCPT_OK; R.err.clear();
         hipError_t e = hipSetDevice(R.ordinal);
-        if (e == hipSuccess) e = hipEventRecord(R.ev_start, R.stream);
+        if (e == hipSuccess) e = hipEventRecord(R.ev_start.get(), R.stream.get());
         if (e != hipSuccess) { R.rc = MCPT_ERR_HIP; R.err = std::string("multi-device render: ") + hipGetErrorString(e); return; }
         // MCPT_RENDER_KEEP_STATS: the ranks' statistics stay on their devices (no read-back, no event queries inside the frame) until
         // mcpt_multi_collect_stats; one frame at a time all the same (MCPT_RENDER_PIPELINE is not passed on)
         q.flags &= ~MCPT_RENDER_PIPELINE;
-        R.rc = mcpt_render_device(R.dev, &q, R.d_frame, keep ? nullptr : &R.stats, R.stream);
+        R.rc = mcpt_render_device(R.dev, &q, R.d_frame.get(), keep ? nullptr : &R.stats, R.stream.get());
         if (R.rc) { R.err = mcpt_last_error(); return; }
         e = hipSetDevice(R.ordinal);
-        if (e == hipSuccess) e = hipEventRecord(R.ev_rendered, R.stream);
-        if (e == hipSuccess && r == 0) e = hipEventRecord(m->ev_gather, R.stream);
+        if (e == hipSuccess) e = hipEventRecord(R.ev_rendered.get(), R.stream.get());
+        if (e == hipSuccess && r == 0) e = hipEventRecord(m->ev_gather.get(), R.stream.get());
         if (e == hipSuccess && r > 0 && R.n > 0) {
-            mcpt::launch_pack_pixels(R.d_frame, R.d_pixels, R.n, R.d_compact, R.stream);
+            mcpt::launch_pack_pixels(R.d_frame.get(), R.d_pixels.get(), R.n, R.d_compact.get(), R.stream.get());
             e = hipGetLastError();
             if (e == hipSuccess && !rccl)
-                e = hipMemcpyPeerAsync(R.d_stage, R0.ordinal, R.d_compact, R.ordinal, size_t(R.n) * 3 * sizeof(double), R.stream);
+                e = hipMemcpyPeerAsync(R.d_stage.get(), R0.ordinal, R.d_compact.get(), R.ordinal, size_t(R.n) * 3 * sizeof(double), R.stream.get());
         }
-        if (e == hipSuccess && !rccl) e = hipStreamSynchronize(R.stream);
+        if (e == hipSuccess && !rccl) e = hipStreamSynchronize(R.stream.get());
         if (e != hipSuccess) { R.rc = MCPT_ERR_HIP; R.err = std::string("multi-device render: ") + hipGetErrorString(e); }
     };
     m->workers.run(work);
@@ -359,22 +352,22 @@ int mcpt_multi_render_device(mcpt_multi* m, const mcpt_render_params* p, double*
         for (int r = 1; r < world && nr == ncclSuccess; r++) {
             Rank& R = m->ranks[size_t(r)];
             if (R.n <= 0) continue;
-            nr = m->rccl.Send(R.d_compact, size_t(R.n) * 3, ncclDouble, 0, m->comms[size_t(r)], R.stream);
-            if (nr == ncclSuccess) nr = m->rccl.Recv(R.d_stage, size_t(R.n) * 3, ncclDouble, r, m->comms[0], R0.stream);
+            nr = m->rccl.Send(R.d_compact.get(), size_t(R.n) * 3, ncclDouble, 0, m->comms[size_t(r)], R.stream.get());
+            if (nr == ncclSuccess) nr = m->rccl.Recv(R.d_stage.get(), size_t(R.n) * 3, ncclDouble, r, m->comms[0], R0.stream.get());
         }
         const ncclResult_t ge = m->rccl.GroupEnd();
         if (nr == ncclSuccess) nr = ge;
         if (nr != ncclSuccess) return fail(MCPT_ERR_HIP, std::string("RCCL gather: ") + m->rccl.GetErrorString(nr));
-        for (int r = 1; r < world; r++) { HIP_OR_FAIL(hipSetDevice(m->ranks[size_t(r)].ordinal)); HIP_OR_FAIL(hipStreamSynchronize(m->ranks[size_t(r)].stream)); }
+        for (int r = 1; r < world; r++) { HIP_TRY(hipSetDevice(m->ranks[size_t(r)].ordinal)); HIP_TRY(hipStreamSynchronize(m->ranks[size_t(r)].stream.get())); }
     }
-    HIP_OR_FAIL(hipSetDevice(R0.ordinal));
+    HIP_TRY(hipSetDevice(R0.ordinal));
     for (int r = 1; r < world; r++) {
         Rank& R = m->ranks[size_t(r)];
-        mcpt::launch_unpack_pixels(R.d_stage, R.d_pixels0, R.n, R0.d_frame, R0.stream);
-        HIP_OR_FAIL(hipGetLastError());
+        mcpt::launch_unpack_pixels(R.d_stage.get(), R.d_pixels0.get(), R.n, R0.d_frame.get(), R0.stream.get());
+        HIP_TRY(hipGetLastError());
     }
-    HIP_OR_FAIL(hipEventRecord(m->ev1, R0.stream));
-    HIP_OR_FAIL(hipStreamSynchronize(R0.stream));
+    HIP_TRY(hipEventRecord(m->ev1.get(), R0.stream.get()));
+    HIP_TRY(hipStreamSynchronize(R0.stream.get()));
     if (stats && !keep) {
         for (const Rank& R : m->ranks) {
             const mcpt_stats& s = R.stats;
@@ -387,19 +380,19 @@ int mcpt_multi_render_device(mcpt_multi* m, const mcpt_render_params* p, double*
             stats->max_depth = std::max(stats->max_depth, s.max_depth);
         }
         float ms = 0;
-        (void)hipEventElapsedTime(&ms, m->ev0, m->ev1);      // rank 0's stream from before its render to after the last unpack
+        (void)hipEventElapsedTime(&ms, m->ev0.get(), m->ev1.get());      // rank 0's stream from before its render to after the last unpack
         stats->ms_total = ms;
     }
     m->gather_ms = 0;
-    (void)hipEventElapsedTime(&m->gather_ms, m->ev_gather, m->ev1);
+    (void)hipEventElapsedTime(&m->gather_ms, m->ev_gather.get(), m->ev1.get());
     for (Rank& R : m->ranks) {
         R.render_ms = 0;
         (void)hipSetDevice(R.ordinal);
-        if (hipEventSynchronize(R.ev_rendered) == hipSuccess) (void)hipEventElapsedTime(&R.render_ms, R.ev_start, R.ev_rendered);
+        if (hipEventSynchronize(R.ev_rendered.get()) == hipSuccess) (void)hipEventElapsedTime(&R.render_ms, R.ev_start.get(), R.ev_rendered.get());
     }
     (void)hipGetLastError();
     (void)hipSetDevice(R0.ordinal);
-    *d_img = R0.d_frame;
+    *d_img = R0.d_frame.get();
     return MCPT_OK;
 }
 
@@ -446,8 +439,8 @@ int mcpt_multi_render(mcpt_multi* m, const mcpt_render_params* p, double* img, m
     double* d = nullptr;
     const int rc = mcpt_multi_render_device(m, p, &d, stats);
     if (rc) return rc;
-    HIP_OR_FAIL(hipSetDevice(m->ranks[0].ordinal));
-    HIP_OR_FAIL(hipMemcpy(img, d, size_t(m->width) * m->height * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipSetDevice(m->ranks[0].ordinal));
+    HIP_TRY(hipMemcpy(img, d, size_t(m->width) * m->height * 3 * sizeof(double), hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
 

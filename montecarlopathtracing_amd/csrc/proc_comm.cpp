@@ -15,10 +15,10 @@
 #include <vector>
 
 #include "../../include/mcpt.h"
+#include "hip_owned.hpp"
 #include "kernels.hpp"
 
-namespace mcpt { int set_error(int code, const std::string& msg); }
-static int fail(int code, const std::string& msg) { return mcpt::set_error(code, msg); }
+using mcpt::DevBuf;
 
 namespace {
 
@@ -67,24 +67,19 @@ struct mcpt_comm {
     Rccl rccl;
     ncclComm_t comm = nullptr;
     int ordinal = 0, rank = 0, world = 1;
-    hipStream_t stream = nullptr;               // the exchange's own stream
-    hipEvent_t ev = nullptr;
+    mcpt::Stream stream;                        // the exchange's own stream
+    mcpt::Event ev;
     // pixel lists of the partition the buffers were made for
     int key[2] = {-1, -1};
     int64_t n_own = 0;
-    int32_t* d_pixels_own = nullptr;            // this rank's pixels
-    double* d_compact = nullptr;                // [n_own][3]
+    DevBuf<int32_t> d_pixels_own;               // this rank's pixels
+    DevBuf<double> d_compact;                   // [n_own][3]
     std::vector<int64_t> n_of;                  // rank 0: pixels of every rank
-    std::vector<int32_t*> d_pixels_of;          // rank 0: their lists, on this GPU
-    std::vector<double*> d_stage_of;            // rank 0: where their buffers land
-    double* d_red = nullptr;                    // all-reduce scratch (64 doubles)
+    std::vector<DevBuf<int32_t>> d_pixels_of;   // rank 0: their lists, on this GPU
+    std::vector<DevBuf<double>> d_stage_of;     // rank 0: where their buffers land
+    DevBuf<double> d_red;                       // all-reduce scratch (64 doubles)
 };
 
-#define HIP_OR_FAIL(expr)                                                                               \
-    do {                                                                                                \
-        hipError_t e_ = (expr);                                                                         \
-        if (e_ != hipSuccess) return fail(MCPT_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 #define NCCL_OR_FAIL(c, expr)                                                                           \
     do {                                                                                                \
         ncclResult_t r_ = (expr);                                                                       \
@@ -93,11 +88,7 @@ struct mcpt_comm {
 
 static void free_lists(mcpt_comm* c)
 {
-    if (c->d_pixels_own) (void)hipFree(c->d_pixels_own);
-    if (c->d_compact) (void)hipFree(c->d_compact);
-    for (int32_t* p : c->d_pixels_of) if (p) (void)hipFree(p);
-    for (double* p : c->d_stage_of) if (p) (void)hipFree(p);
-    c->d_pixels_own = nullptr; c->d_compact = nullptr; c->d_pixels_of.clear(); c->d_stage_of.clear(); c->n_of.clear();
+    c->d_pixels_own.reset(); c->d_compact.reset(); c->d_pixels_of.clear(); c->d_stage_of.clear(); c->n_of.clear();
     c->key[0] = c->key[1] = -1; c->n_own = 0;
 }
 
@@ -119,18 +110,16 @@ static int prepare_lists(mcpt_comm* c, const mcpt_scene* scene, const mcpt_rende
     int64_t n = list_of(c->rank, pix);
     if (n < 0) return int(n);
     c->n_own = n;
-    HIP_OR_FAIL(hipMalloc(reinterpret_cast<void**>(&c->d_pixels_own), pix.size() * sizeof(int32_t)));
-    HIP_OR_FAIL(hipMemcpy(c->d_pixels_own, pix.data(), pix.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_OR_FAIL(hipMalloc(reinterpret_cast<void**>(&c->d_compact), pix.size() * 3 * sizeof(double)));
+    HIP_TRY(c->d_pixels_own.upload(pix));
+    HIP_TRY(c->d_compact.alloc(pix.size() * 3));
     if (c->rank == 0) {
-        c->n_of.assign(size_t(c->world), 0); c->d_pixels_of.assign(size_t(c->world), nullptr); c->d_stage_of.assign(size_t(c->world), nullptr);
+        c->n_of.assign(size_t(c->world), 0); c->d_pixels_of.resize(size_t(c->world)); c->d_stage_of.resize(size_t(c->world));
         for (int r = 1; r < c->world; r++) {
             n = list_of(r, pix);
             if (n < 0) return int(n);
             c->n_of[size_t(r)] = n;
-            HIP_OR_FAIL(hipMalloc(reinterpret_cast<void**>(&c->d_pixels_of[size_t(r)]), pix.size() * sizeof(int32_t)));
-            HIP_OR_FAIL(hipMemcpy(c->d_pixels_of[size_t(r)], pix.data(), pix.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-            HIP_OR_FAIL(hipMalloc(reinterpret_cast<void**>(&c->d_stage_of[size_t(r)]), pix.size() * 3 * sizeof(double)));
+            HIP_TRY(c->d_pixels_of[size_t(r)].upload(pix));
+            HIP_TRY(c->d_stage_of[size_t(r)].alloc(pix.size() * 3));
         }
     }
     std::memcpy(c->key, key, sizeof key);
@@ -156,13 +145,11 @@ void mcpt_comm_free(mcpt_comm* c)
 {
     if (!c) return;
     (void)hipSetDevice(c->ordinal);
-    if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->stream) (void)hipStreamSynchronize(c->stream.get());
     free_lists(c);
-    if (c->d_red) (void)hipFree(c->d_red);
+    c->d_red.reset();
     if (c->comm && c->rccl.CommDestroy) (void)c->rccl.CommDestroy(c->comm);
-    if (c->ev) (void)hipEventDestroy(c->ev);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    delete c;                                   // (the event and the stream with it)
 }
 
 int mcpt_comm_create(int32_t ordinal, int32_t rank, int32_t world, const uint8_t* id, int64_t id_bytes, mcpt_comm** out)
@@ -176,10 +163,10 @@ int mcpt_comm_create(int32_t ordinal, int32_t rank, int32_t world, const uint8_t
     c->ordinal = ordinal; c->rank = rank; c->world = world;
     std::string err;
     if (!c->rccl.load(err)) return fail(MCPT_ERR_IO, err);
-    HIP_OR_FAIL(hipSetDevice(ordinal));
-    HIP_OR_FAIL(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIP_OR_FAIL(hipEventCreateWithFlags(&c->ev, hipEventDisableTiming));
-    HIP_OR_FAIL(hipMalloc(reinterpret_cast<void**>(&c->d_red), 64 * sizeof(double)));
+    HIP_TRY(hipSetDevice(ordinal));
+    HIP_TRY(create(c->stream, hipStreamCreateWithFlags, hipStreamNonBlocking));
+    HIP_TRY(create(c->ev, hipEventCreateWithFlags, hipEventDisableTiming));
+    HIP_TRY(c->d_red.alloc(64));
     ncclUniqueId u;
     std::memcpy(&u, id, sizeof u);
     NCCL_OR_FAIL(c, c->rccl.CommInitRank(&c->comm, world, u, rank));
@@ -201,32 +188,32 @@ int mcpt_comm_size(const mcpt_comm* c)
 int mcpt_comm_gather_frame(mcpt_comm* c, const mcpt_scene* scene, const mcpt_render_params* p, double* d_frame, void* stream)
 {
     if (!c || !scene || !p || !d_frame) return fail(MCPT_ERR_ARG, "null argument");
-    HIP_OR_FAIL(hipSetDevice(c->ordinal));
+    HIP_TRY(hipSetDevice(c->ordinal));
     if (c->world == 1) return MCPT_OK;
     int rc = prepare_lists(c, scene, p);
     if (rc) return rc;
-    HIP_OR_FAIL(hipEventRecord(c->ev, static_cast<hipStream_t>(stream)));
-    HIP_OR_FAIL(hipStreamWaitEvent(c->stream, c->ev, 0));
+    HIP_TRY(hipEventRecord(c->ev.get(), static_cast<hipStream_t>(stream)));
+    HIP_TRY(hipStreamWaitEvent(c->stream.get(), c->ev.get(), 0));
     if (c->rank > 0) {
         if (c->n_own > 0) {
-            mcpt::launch_pack_pixels(d_frame, c->d_pixels_own, c->n_own, c->d_compact, c->stream);
-            HIP_OR_FAIL(hipGetLastError());
+            mcpt::launch_pack_pixels(d_frame, c->d_pixels_own.get(), c->n_own, c->d_compact.get(), c->stream.get());
+            HIP_TRY(hipGetLastError());
         }
         NCCL_OR_FAIL(c, c->rccl.GroupStart());
-        if (c->n_own > 0) NCCL_OR_FAIL(c, c->rccl.Send(c->d_compact, size_t(c->n_own) * 3, ncclDouble, 0, c->comm, c->stream));
+        if (c->n_own > 0) NCCL_OR_FAIL(c, c->rccl.Send(c->d_compact.get(), size_t(c->n_own) * 3, ncclDouble, 0, c->comm, c->stream.get()));
         NCCL_OR_FAIL(c, c->rccl.GroupEnd());
     } else {
         NCCL_OR_FAIL(c, c->rccl.GroupStart());
         for (int r = 1; r < c->world; r++)
-            if (c->n_of[size_t(r)] > 0) NCCL_OR_FAIL(c, c->rccl.Recv(c->d_stage_of[size_t(r)], size_t(c->n_of[size_t(r)]) * 3, ncclDouble, r, c->comm, c->stream));
+            if (c->n_of[size_t(r)] > 0) NCCL_OR_FAIL(c, c->rccl.Recv(c->d_stage_of[size_t(r)].get(), size_t(c->n_of[size_t(r)]) * 3, ncclDouble, r, c->comm, c->stream.get()));
         NCCL_OR_FAIL(c, c->rccl.GroupEnd());
         for (int r = 1; r < c->world; r++)
             if (c->n_of[size_t(r)] > 0) {
-                mcpt::launch_unpack_pixels(c->d_stage_of[size_t(r)], c->d_pixels_of[size_t(r)], c->n_of[size_t(r)], d_frame, c->stream);
-                HIP_OR_FAIL(hipGetLastError());
+                mcpt::launch_unpack_pixels(c->d_stage_of[size_t(r)].get(), c->d_pixels_of[size_t(r)].get(), c->n_of[size_t(r)], d_frame, c->stream.get());
+                HIP_TRY(hipGetLastError());
             }
     }
-    HIP_OR_FAIL(hipStreamSynchronize(c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
     return MCPT_OK;
 }
 
@@ -234,14 +221,14 @@ int mcpt_comm_gather_frame(mcpt_comm* c, const mcpt_scene* scene, const mcpt_ren
 int mcpt_comm_allreduce(mcpt_comm* c, double* v, int32_t n, int32_t op)
 {
     if (!c || n < 0 || n > 64 || (n > 0 && !v) || (op != 0 && op != 1)) return fail(MCPT_ERR_ARG, "bad argument");
-    HIP_OR_FAIL(hipSetDevice(c->ordinal));
+    HIP_TRY(hipSetDevice(c->ordinal));
     double buf[64] = {0};
     const int m = n > 0 ? n : 1;
     if (n > 0) std::memcpy(buf, v, size_t(n) * sizeof(double));
-    HIP_OR_FAIL(hipMemcpy(c->d_red, buf, size_t(m) * sizeof(double), hipMemcpyHostToDevice));          // blocking: buf is pageable
-    NCCL_OR_FAIL(c, c->rccl.AllReduce(c->d_red, c->d_red, size_t(m), ncclDouble, op == 0 ? ncclSum : ncclMax, c->comm, c->stream));
-    HIP_OR_FAIL(hipStreamSynchronize(c->stream));
-    HIP_OR_FAIL(hipMemcpy(buf, c->d_red, size_t(m) * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c->d_red.get(), buf, size_t(m) * sizeof(double), hipMemcpyHostToDevice));          // blocking: buf is pageable
+    NCCL_OR_FAIL(c, c->rccl.AllReduce(c->d_red.get(), c->d_red.get(), size_t(m), ncclDouble, op == 0 ? ncclSum : ncclMax, c->comm, c->stream.get()));
+    HIP_TRY(hipStreamSynchronize(c->stream.get()));
+    HIP_TRY(hipMemcpy(buf, c->d_red.get(), size_t(m) * sizeof(double), hipMemcpyDeviceToHost));
     if (n > 0) std::memcpy(v, buf, size_t(n) * sizeof(double));
     return MCPT_OK;
 }
