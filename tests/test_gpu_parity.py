@@ -222,6 +222,8 @@ def test_sample_radiance(pair, oracle, mcpt, engine):
             on_surface[i] = st.rays_on_surface > 0
         return o, on_surface
     o, on_surface = _cached(name, "samples", from_oracle)
+    # a NaN compares false with everything: without this a NaN sample would count as "not flipped"
+    assert np.array_equal(np.isnan(g), np.isnan(o)), "NaN masks differ on %d samples" % int((np.isnan(g) != np.isnan(o)).any(axis=1).sum())
     scale = np.maximum(np.abs(o).max(axis=1), 1e-12)
     err = np.abs(g - o).max(axis=1) / scale
     flip = err > REL_TOL
@@ -251,6 +253,7 @@ def test_image_matches_oracle(pair, oracle, mcpt, pipeline, engine):
     st = mcpt.Stats()
     img = dev.generateImg(spp, seed=3, stats=st, flags=mcpt.RENDER_MEGAKERNEL if pipeline == "megakernel" else 0)
     assert img.shape == ref.shape
+    assert np.array_equal(np.isnan(img), np.isnan(ref)), "NaN masks differ on %d channels" % int((np.isnan(img) != np.isnan(ref)).sum())
     scale = np.maximum(np.abs(ref), 1e-6)
     rel = np.abs(img - ref) / scale
     bad = int((rel > 1e-6).sum())      # float accumulator: 1 ulp of fp32 ~ 6e-8
@@ -326,6 +329,7 @@ def test_wavefront_iterations_against_megakernel_and_oracle(pair, oracle, mcpt, 
         if mode == "fast" and finish_paths == "0":
             assert st.dom_rays > 0.9 * (st.rays_shadow + st.rays_bounce)     # ... and its rays went through k_wf_trace
         ref = osc.render(spp, seed=3)
+        assert np.array_equal(np.isnan(a), np.isnan(ref)), "NaN masks differ on %d channels" % int((np.isnan(a) != np.isnan(ref)).sum())
         rel = np.abs(a - ref) / np.maximum(np.abs(ref), 1e-6)
         bad = int((rel > 1e-6).sum())
         assert bad <= max(3, int(a.size * spp * FLIP_BUDGET[name])), "%d pixel channels differ from the oracle" % bad
