@@ -105,7 +105,7 @@ struct DCamera {                                   // generateImg's frame, pathT
     int32_t width, height;
 };
 
-// What a kernel needs of the lens: the device's camera frame and the lens itself, formed on the host (capi.cpp: lens_for); camera.hpp: camera_ray.
+// What a kernel needs of the lens: the device's camera frame and the lens itself, formed on the host (render.cpp: lens_for); camera.hpp: camera_ray.
 struct DLens {
     const double* pos;          // [W*H][3] pos(i,j): the reference's running-sum corner of every pixel (k_primary_pos)
     double eye[3], pdx[3], pdy[3];

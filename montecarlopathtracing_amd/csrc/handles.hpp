@@ -1,0 +1,166 @@
+// The C API's scene and device handles and the few host steps more than one of its files needs.  Host only: no .hip file includes it.
+//   capi.cpp          error state, version, device count, the HIP runtime check
+//   scene_api.cpp     scene handles, the tile partition, the trace engine of a scene, the shared culling hierarchy
+//   device.cpp        device creation stage by stage, hierarchy queries, closest hit
+//   render.cpp        lenses, the integrator (megakernel and wavefront), mcpt_render*, statistics, (pixel, sample) queries
+//   progressive.cpp   progressive frames, AOVs, the denoiser
+//   render_scene.cpp  output writers, checkpoints, render_scene
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <atomic>
+#include <cstdint>
+#include <functional>
+#include <memory>
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "accel_build.hpp"
+#include "hip_owned.hpp"
+#include "kernels.hpp"
+#include "knobs.hpp"
+#include "scene.hpp"
+#include "wavefront.hpp"
+
+struct mcpt_scene {
+    mcpt::Scene s;
+    // The fast walk's culling hierarchy depends on the scene and the leaf order only: built once, shared by every device
+    // created from this scene (one SAH build for the 8 GPUs of a node, not 8).
+    mutable std::atomic<int> devices_created{0};      // mcpt_scene_set_resolution is refused once a device holds the camera
+    // Shared ownership: the caller's handle and every device created from the scene hold one reference each; the scene goes with the
+    // last of mcpt_scene_free / mcpt_device_free, in whichever order they come (a device keeps using the handle: the shared culling
+    // hierarchy, the counter above).
+    mutable std::atomic<int> refs{1};
+    mutable std::mutex fast_mu;
+    mutable std::shared_ptr<const mcpt::FastBvh> fast_cached;
+    mutable std::vector<int32_t> fast_order;
+    mutable int fast_leaf = 0;
+    mutable double fast_ct = 0;
+};
+
+// start/stop events around a launch or a frame
+using EventPair = std::pair<mcpt::Event, mcpt::Event>;
+
+struct mcpt_device {
+    int ordinal = 0;
+    mcpt::Knobs knobs;                     // the environment as it was when this device was created (knobs.hpp)
+    mcpt::DScene ds{};
+    mcpt::Stream stream;                   // library stream for the host-pointer entry points
+    // scene arrays
+    mcpt::DevBuf<mcpt::DNode> nodes; mcpt::DevBuf<mcpt::DTri> tris; mcpt::DevBuf<mcpt::DTriShade> shade; mcpt::DevBuf<mcpt::DMaterial> materials;
+    mcpt::DevBuf<mcpt::DLight> lights; mcpt::DevBuf<mcpt::DLightTri> light_tris; mcpt::DevBuf<double> light_cdf; mcpt::DevBuf<uint8_t> texels;
+    mcpt::DevBuf<mcpt::DTri> fast_tris; mcpt::DevBuf<mcpt::CwNode> cw_nodes; mcpt::DevBuf<mcpt::DTriPre> fast_pre;
+    mcpt_fast_info fast_info{};     // what mcpt_device_fast_hierarchy reports (node and triangle slot counts, builder, clusters, depth, stack need)
+    int trace_mode = MCPT_TRACE_FAST;
+    mcpt::DevBuf<int32_t> d_order;         // leaf -> .obj face (device build keeps it for read-back)
+    mcpt_bvh_info bi{};
+    // frame state
+    int width = 0, height = 0;
+    mcpt::DevBuf<double> dirs;             // W*H*3 primary directions
+    bool dirs_ready = false;
+    mcpt_lens lens{};                      // mcpt_device_set_lens (all zero: the reference's pinhole)
+    mcpt::DevBuf<double> pos;              // W*H*3 image-plane points pos(i,j), made on the first frame under an active lens
+    // render workspace
+    mcpt::DevBuf<int32_t> pixels; int64_t n_pixels = 0; int part_key[4] = {-1, -1, -1, -1};
+    mcpt::Event ev[4];
+    mcpt::Stream look_stream;              // the host's looks at a path count travel here, so that they wait for the logic pass that wrote
+    mcpt::Event look_ev;                   // the count and for nothing enqueued after it (the finishing kernel above all)
+    mcpt::HostBuf<unsigned int> h_look;    // pinned host word the looks land in (never a pageable stack address: an async copy into
+                                           // pageable memory goes through the runtime's pin-on-the-fly / staging paths)
+    const mcpt_scene* scene = nullptr;     // the handle this device was created from (devices_created is given back in mcpt_device_free)
+    // closest-hit and test entry points (mcpt_trace_closest*, mcpt_sample_radiance) have counters, queue words and a deferred-ray
+    // list of their own: a frame in flight on another stream keeps using its frame slot's
+    mcpt::DevBuf<mcpt::DCounters> aux_ctr; mcpt::DevBuf<mcpt::TraceQueue> aux_queue; mcpt::DevBuf<long long> aux_slow_list;
+    size_t sample_budget_bytes = size_t(4) << 30;   // megakernel path: radiance staging buffer per chunk
+    size_t wf_budget_bytes = 0;                     // path state + rays per frame slot; 0 = a share of the free HBM (MCPT_WORKSPACE_GB overrides)
+    size_t wf_auto_budget = 0;                      // that share, asked for once (hipMemGetInfo costs a few hundred microseconds)
+    // Everything a frame in flight owns.  Two slots: with MCPT_RENDER_PIPELINE consecutive frames alternate between them, so the
+    // latency-bound tail of one frame (the finishing kernel's last long paths, the fold) overlaps the head of the next on another stream.
+    struct FrameSlot {
+        mcpt::DevBuf<mcpt::PrimaryHit> hits;
+        mcpt::DevBuf<double> rad;                       // sized in bytes (a lens adds a hit flag per sample)
+        mcpt::DevBuf<char> wf_ws;
+        mcpt::DevBuf<int32_t> hit_slots;
+        mcpt::DevBuf<mcpt::PrimarySurface> surf;        // first-vertex record per hit pixel of the chunk
+        mcpt::DevBuf<uint8_t> cam_hit;                  // per-sample route of a lens: did the sample's camera ray hit (per chunk sample)
+        mcpt::DevBuf<unsigned int> alive_base;          // shaded pixels before each group of 64 hit slots
+        mcpt::DevBuf<mcpt::WfCounts> wf_counts;         // MCPT_WF_COUNT_SLOTS slots
+        mcpt::DevBuf<mcpt::TraceQueue> queue;           // persistent trace kernels: chunk queue head + deferred-ray list
+        mcpt::DevBuf<long long> slow_list;
+        mcpt::DevBuf<char> path_area;                   // records and exact-walk stacks of the pool form of the finishing pass (finish_pool_bytes)
+        mcpt::DevBuf<mcpt::DCounters> ctr;
+        mcpt::Event done;                               // recorded after the slot's last kernel of a frame
+        bool used = false;
+        bool keeping = false;                           // ctr holds kept statistics of earlier frames (must not be cleared)
+    } slot[2];
+    int next_slot = 0;
+    bool pipelined = false;                         // set by the first MCPT_RENDER_PIPELINE frame (sizes the workspace budget)
+    // statistics kept on the device side until mcpt_device_collect_stats (MCPT_RENDER_KEEP_STATS)
+    std::vector<EventPair> ev_pool;                 // start/stop pairs around trace launches
+    size_t ev_used = 0;
+    std::vector<EventPair> frame_ev;                // start/stop of every kept frame
+    size_t frame_ev_used = 0;
+    uint64_t kept_samples = 0, kept_primary = 0; int kept_launches = 0;
+    unsigned int slow_cap = 1u << 20;
+    mcpt::LaunchCfg cfg;                            // this GPU's resident grids and knobs
+    long long finish_threshold = 500000;            // paths left at which the finishing pass takes over (MCPT_FINISH_PATHS; sweep: flat from 2e5 to 1e6)
+    // Shared ownership, as a device holds its scene: the caller's handle and every progressive frame created on the device hold one
+    // reference each; the device goes with the last of mcpt_device_free / mcpt_progressive_free.
+    std::atomic<int> refs{1};
+};
+
+// The helpers below are the library's own: none of them is exported from libmcpt.so.
+#pragma GCC visibility push(hidden)
+
+// ---- capi.cpp
+int runtime_gate();                                 // what mcpt_device_create asks before it touches a device
+// MCPT_ERR_NO_DEVICE unless a HIP device is visible (libmcpt has no CPU fallback); *visible: how many are
+int require_device(int* visible = nullptr);
+
+// ---- scene_api.cpp
+void scene_release(const mcpt_scene* s);            // drops one reference to s
+int trace_engine_for(long long t, const mcpt::Knobs& k);
+// the culling hierarchy of h for the leaf order `order`, built on the first request and shared by every device of the scene
+std::shared_ptr<const mcpt::FastBvh> shared_fast_bvh(const mcpt_scene* h, const std::vector<int32_t>& order, const mcpt::Knobs& k);
+// p's tile partition (tiles of tile_w x tile_h, default 32 x 8, dealt over world ranks); MCPT_ERR_ARG when the rank is outside the world
+struct TileShape { int tw, th, rank, world; };
+int tile_shape(const mcpt_render_params* p, TileShape& t);
+// the pixels (y * W + x, in scan order) that p's rank owns in a W x H frame; MCPT_ERR_ARG as tile_shape
+int owned_pixels(int W, int H, const mcpt_render_params* p, std::vector<int32_t>& out);
+
+// ---- render.cpp
+inline bool lens_active(const mcpt_lens& l) { return l.flags != 0 || l.aperture > 0.0; }
+int lens_check(const mcpt_lens* l);
+int ensure_dirs(mcpt_device* d, hipStream_t st);    // the primary directions, made on first use
+void counters_to_stats(const mcpt::DCounters& c, mcpt_stats* s, bool print_diag);
+// a += b for every counter of b (max_depth: the larger); ms_trace and ms_total are the caller's to combine
+void add_counts(mcpt_stats& a, const mcpt_stats& b);
+// Runs run(d_img, d_img2) on device copies of the caller's pageable host frames (`bytes` each; a null frame stays null): each is copied
+// in first, so that pixels the call does not write keep the caller's values, and out again on success.  The stream is synchronised
+// in between, on failure as well: nothing enqueued may still use a copy when it goes.
+int with_device_frames(hipStream_t st, size_t bytes, double* img, double* img2, const std::function<int(double*, double*)>& run);
+
+// Which camera samples of every owned pixel a render call covers and where they are folded.  A frame: samples [0, N) through
+// k_fold_samples (mom == null).  A progressive pass (mcpt_progressive_step): samples [k0, k0 + n) of a frame of N through
+// k_fold_progressive, which continues the image's fold and the moments in mom.  n is the layout stride of the pass (WfArgs::spp):
+// chunks are sized from it.
+struct SampleRange {
+    int k0, n, N;
+    double* mom;
+    uint8_t* hit;
+    const mcpt_lens* lens;      // the lens of the call (the device's, or the one a progressive handle took); null: the pinhole
+    int32_t* hitcnt;            // progressive passes under an active lens: per pixel, the samples whose camera ray hit
+};
+
+// The pixels a render call covers, on the device: the partition's owned list (mcpt_render*, uniform progressive passes) or an adaptive
+// frame's active list.  Slot s of the call renders pixel pixels[s].
+struct PixelList {
+    const int32_t* pixels;
+    int64_t n;
+};
+
+int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelList& L, const mcpt_render_params* p, double* d_img, mcpt_stats* stats,
+                       hipStream_t st, int& slot_used);
+
+#pragma GCC visibility pop

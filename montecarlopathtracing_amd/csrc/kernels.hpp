@@ -1,4 +1,4 @@
-// Launch interface between the C-ABI layer (capi.cpp) and the HIP kernels (kernels.hip).
+// Launch interface between the C-ABI layer (the host files handles.hpp lists) and the HIP kernels (kernels.hip).
 #pragma once
 #include <hip/hip_runtime_api.h>
 

@@ -2,9 +2,9 @@
 // tiles dealt by mcpt_render_params.rank/world, end-of-frame exchange of compact pixel buffers into the first GPU's HBM over
 // xGMI -- hipMemcpyPeerAsync by default, RCCL send/recv on request.  The reference has nothing like it (one OpenMP process,
 // MTPC/pathTracing.cpp:303); this is what lets render_scene(path, filename, N) of MTPC/MTPC.cpp:35 use the whole node without
-// a Python launcher.  Built only on the library's public entry points plus two pack/unpack kernels.
+// a Python launcher.  Built on the library's public entry points, two pack/unpack kernels and the partition and statistics helpers of
+// handles.hpp.
 #include <hip/hip_runtime_api.h>
-#include <rccl/rccl.h>          // types only: the library itself is loaded with dlopen when MCPT_GATHER_RCCL is asked for
 
 #include <dlfcn.h>
 
@@ -18,45 +18,13 @@
 #include <thread>
 #include <vector>
 
-#include "../../include/mcpt.h"
-#include "hip_owned.hpp"
-#include "kernels.hpp"
+#include "handles.hpp"
+#include "rccl_loader.hpp"          // loaded when MCPT_GATHER_RCCL is asked for
 
 using mcpt::DevBuf;
 using mcpt::Event;
 
 namespace {
-
-struct RcclApi {
-    void* lib = nullptr;
-    ncclResult_t (*CommInitAll)(ncclComm_t*, int, const int*) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-    bool load(std::string& err)
-    {
-        for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-            if (lib) break;
-        }
-        if (!lib) { err = std::string("cannot load librccl: ") + dlerror(); return false; }
-        auto sym = [&](const char* n) { return dlsym(lib, n); };
-        CommInitAll = reinterpret_cast<decltype(CommInitAll)>(sym("ncclCommInitAll"));
-        CommDestroy = reinterpret_cast<decltype(CommDestroy)>(sym("ncclCommDestroy"));
-        CommCount = reinterpret_cast<decltype(CommCount)>(sym("ncclCommCount"));
-        GroupStart = reinterpret_cast<decltype(GroupStart)>(sym("ncclGroupStart"));
-        GroupEnd = reinterpret_cast<decltype(GroupEnd)>(sym("ncclGroupEnd"));
-        Send = reinterpret_cast<decltype(Send)>(sym("ncclSend"));
-        Recv = reinterpret_cast<decltype(Recv)>(sym("ncclRecv"));
-        GetErrorString = reinterpret_cast<decltype(GetErrorString)>(sym("ncclGetErrorString"));
-        if (!CommInitAll || !CommDestroy || !GroupStart || !GroupEnd || !Send || !Recv || !GetErrorString) { err = "librccl lacks an expected symbol"; return false; }
-        return true;
-    }
-};
 
 // A rank's buffers live on two GPUs: free_lists and mcpt_multi_free release each group with reset() while its device is current.
 struct Rank {
@@ -139,7 +107,7 @@ struct mcpt_multi {
     int gather = MCPT_GATHER_PEER;
     int part_key[2] = {-1, -1};         // tile shape the pixel lists were made for ({-1,-1}: none)
     std::vector<Rank> ranks;
-    RcclApi rccl;
+    Rccl rccl;
     std::vector<ncclComm_t> comms;
     Event ev0, ev1, ev_gather;          // on devices[0]'s stream: frame start, frame end, its own render done
     float gather_ms = 0;                // last frame: from rank 0's render being done to the last unpack (what the exchange adds)
@@ -171,11 +139,10 @@ static int prepare_lists(mcpt_multi* m, const mcpt_render_params* p)
         Rank& R = m->ranks[size_t(r)];
         mcpt_render_params q = *p;
         q.rank = r; q.world = world;
-        const int64_t n = mcpt_owned_pixels(m->scene, &q, nullptr);
-        if (n < 0) return int(n);
-        std::vector<int32_t> pix(size_t(std::max<int64_t>(n, 1)));
-        if (n > 0 && mcpt_owned_pixels(m->scene, &q, pix.data()) != n) return fail(MCPT_ERR_ARG, "pixel partition changed between two calls");
-        R.n = n;
+        std::vector<int32_t> pix;
+        if (const int rc = owned_pixels(m->width, m->height, &q, pix)) return rc;
+        R.n = int64_t(pix.size());
+        if (pix.empty()) pix.push_back(0);          // (a rank without pixels still gets buffers of one entry)
         HIP_TRY(hipSetDevice(R.ordinal));
         HIP_TRY(R.d_pixels.upload(pix));
         if (r > 0) {
@@ -236,8 +203,8 @@ int mcpt_multi_create(const mcpt_scene* scene, const int32_t* devices, int32_t n
     if (!scene || !out) return fail(MCPT_ERR_ARG, "null argument");
     *out = nullptr;
     if (gather != MCPT_GATHER_PEER && gather != MCPT_GATHER_RCCL) return fail(MCPT_ERR_ARG, "unknown gather mode");
-    const int visible = mcpt_device_count();
-    if (visible <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
+    int visible = 0;
+    if (const int rc = require_device(&visible)) return rc;
     std::vector<int32_t> ord;
     if (!devices || num_devices <= 0) {
         const int n = num_devices > 0 ? num_devices : visible;
@@ -294,7 +261,8 @@ int mcpt_multi_create(const mcpt_scene* scene, const int32_t* devices, int32_t n
     m->workers.start(int(m->ranks.size()));
     if (gather == MCPT_GATHER_RCCL) {
         std::string err;
-        if (!m->rccl.load(err)) return fail(MCPT_ERR_IO, err);
+        const auto needed = [](const Rccl& r) { return r.CommInitAll && r.CommDestroy && r.GroupStart && r.GroupEnd && r.Send && r.Recv && r.GetErrorString; };
+        if (!m->rccl.load(err, needed)) return fail(MCPT_ERR_IO, err);
         m->comms.assign(ord.size(), nullptr);
         std::vector<int> devlist(ord.begin(), ord.end());
         const ncclResult_t r = m->rccl.CommInitAll(m->comms.data(), int(devlist.size()), devlist.data());
@@ -370,14 +338,8 @@ int mcpt_multi_render_device(mcpt_multi* m, const mcpt_render_params* p, double*
     HIP_TRY(hipStreamSynchronize(R0.stream.get()));
     if (stats && !keep) {
         for (const Rank& R : m->ranks) {
-            const mcpt_stats& s = R.stats;
-            stats->rays_primary += s.rays_primary; stats->rays_shadow += s.rays_shadow; stats->rays_bounce += s.rays_bounce;
-            stats->node_visits += s.node_visits; stats->tri_tests += s.tri_tests; stats->shade_calls += s.shade_calls;
-            stats->samples += s.samples; stats->shadow_skipped += s.shadow_skipped;
-            stats->dom_rays += s.dom_rays; stats->dom_node_visits += s.dom_node_visits; stats->dom_tri_tests += s.dom_tri_tests;
-            stats->launches += s.launches;
-            stats->ms_trace = std::max(stats->ms_trace, s.ms_trace);
-            stats->max_depth = std::max(stats->max_depth, s.max_depth);
+            add_counts(*stats, R.stats);
+            stats->ms_trace = std::max(stats->ms_trace, R.stats.ms_trace);
         }
         float ms = 0;
         (void)hipEventElapsedTime(&ms, m->ev0.get(), m->ev1.get());      // rank 0's stream from before its render to after the last unpack
@@ -421,14 +383,9 @@ int mcpt_multi_collect_stats(mcpt_multi* m, mcpt_stats* stats)
         mcpt_stats s{};
         const int rc = mcpt_device_collect_stats(R.dev, &s);
         if (rc) return rc;
-        stats->rays_primary += s.rays_primary; stats->rays_shadow += s.rays_shadow; stats->rays_bounce += s.rays_bounce;
-        stats->node_visits += s.node_visits; stats->tri_tests += s.tri_tests; stats->shade_calls += s.shade_calls;
-        stats->samples += s.samples; stats->shadow_skipped += s.shadow_skipped;
-        stats->dom_rays += s.dom_rays; stats->dom_node_visits += s.dom_node_visits; stats->dom_tri_tests += s.dom_tri_tests;
-        stats->launches += s.launches;
+        add_counts(*stats, s);
         stats->ms_trace = std::max(stats->ms_trace, s.ms_trace);
         stats->ms_total = std::max(stats->ms_total, s.ms_total);
-        stats->max_depth = std::max(stats->max_depth, s.max_depth);
     }
     return MCPT_OK;
 }

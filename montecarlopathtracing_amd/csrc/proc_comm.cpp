@@ -5,63 +5,16 @@
 // runs the runtime the library was compiled against and /opt/rocm's own librccl.  The reference has nothing like it (one OpenMP process,
 // MTPC/pathTracing.cpp:303); the in-process form of the same exchange is multi_device.cpp.
 #include <hip/hip_runtime_api.h>
-#include <rccl/rccl.h>          // types only: librccl is loaded with dlopen
-
-#include <dlfcn.h>
 
 #include <cstring>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "../../include/mcpt.h"
-#include "hip_owned.hpp"
-#include "kernels.hpp"
+#include "handles.hpp"
+#include "rccl_loader.hpp"
 
 using mcpt::DevBuf;
-
-namespace {
-
-struct Rccl {
-    void* lib = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*CommCount)(const ncclComm_t, int*) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    ncclResult_t (*Send)(const void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*Recv)(void*, size_t, ncclDataType_t, int, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-    bool load(std::string& err)
-    {
-        if (lib) return true;
-        for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-            lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
-            if (lib) break;
-        }
-        if (!lib) { err = std::string("cannot load librccl: ") + dlerror(); return false; }
-        auto sym = [&](const char* n) { return dlsym(lib, n); };
-        GetUniqueId = reinterpret_cast<decltype(GetUniqueId)>(sym("ncclGetUniqueId"));
-        CommInitRank = reinterpret_cast<decltype(CommInitRank)>(sym("ncclCommInitRank"));
-        CommDestroy = reinterpret_cast<decltype(CommDestroy)>(sym("ncclCommDestroy"));
-        CommCount = reinterpret_cast<decltype(CommCount)>(sym("ncclCommCount"));
-        GroupStart = reinterpret_cast<decltype(GroupStart)>(sym("ncclGroupStart"));
-        GroupEnd = reinterpret_cast<decltype(GroupEnd)>(sym("ncclGroupEnd"));
-        Send = reinterpret_cast<decltype(Send)>(sym("ncclSend"));
-        Recv = reinterpret_cast<decltype(Recv)>(sym("ncclRecv"));
-        AllReduce = reinterpret_cast<decltype(AllReduce)>(sym("ncclAllReduce"));
-        GetErrorString = reinterpret_cast<decltype(GetErrorString)>(sym("ncclGetErrorString"));
-        if (!GetUniqueId || !CommInitRank || !CommDestroy || !GroupStart || !GroupEnd || !Send || !Recv || !AllReduce || !GetErrorString) {
-            err = "librccl lacks an expected symbol";
-            return false;
-        }
-        return true;
-    }
-};
-
-}  // namespace
 
 struct mcpt_comm {
     Rccl rccl;
@@ -78,6 +31,11 @@ struct mcpt_comm {
     std::vector<DevBuf<int32_t>> d_pixels_of;   // rank 0: their lists, on this GPU
     std::vector<DevBuf<double>> d_stage_of;     // rank 0: where their buffers land
     DevBuf<double> d_red;                       // all-reduce scratch (64 doubles)
+};
+
+// the entry points of librccl a process communicator uses
+static const auto comm_needs = [](const Rccl& r) {
+    return r.GetUniqueId && r.CommInitRank && r.CommDestroy && r.GroupStart && r.GroupEnd && r.Send && r.Recv && r.AllReduce && r.GetErrorString;
 };
 
 #define NCCL_OR_FAIL(c, expr)                                                                           \
@@ -97,13 +55,13 @@ static int prepare_lists(mcpt_comm* c, const mcpt_scene* scene, const mcpt_rende
     const int key[2] = {p->tile_w, p->tile_h};
     if (c->d_pixels_own && std::memcmp(key, c->key, sizeof key) == 0) return MCPT_OK;
     free_lists(c);
+    // rank r's pixels (a rank without pixels still gets buffers of one entry)
     auto list_of = [&](int r, std::vector<int32_t>& pix) -> int64_t {
         mcpt_render_params q = *p;
         q.rank = r; q.world = c->world;
-        const int64_t n = mcpt_owned_pixels(scene, &q, nullptr);
-        if (n < 0) return n;
-        pix.assign(size_t(n > 0 ? n : 1), 0);
-        if (n > 0 && mcpt_owned_pixels(scene, &q, pix.data()) != n) return fail(MCPT_ERR_ARG, "pixel partition changed between two calls");
+        if (const int rc = owned_pixels(scene->s.width, scene->s.height, &q, pix)) return rc;
+        const int64_t n = int64_t(pix.size());
+        if (pix.empty()) pix.push_back(0);
         return n;
     };
     std::vector<int32_t> pix;
@@ -133,7 +91,7 @@ int mcpt_comm_unique_id(uint8_t* id, int64_t cap)
     if (!id || cap < int64_t(sizeof(ncclUniqueId))) return fail(MCPT_ERR_ARG, "the id buffer needs 128 bytes");
     Rccl r;
     std::string err;
-    if (!r.load(err)) return fail(MCPT_ERR_IO, err);
+    if (!r.load(err, comm_needs)) return fail(MCPT_ERR_IO, err);
     ncclUniqueId u;
     const ncclResult_t rc = r.GetUniqueId(&u);
     if (rc != ncclSuccess) return fail(MCPT_ERR_HIP, std::string("ncclGetUniqueId: ") + r.GetErrorString(rc));
@@ -156,13 +114,13 @@ int mcpt_comm_create(int32_t ordinal, int32_t rank, int32_t world, const uint8_t
 {
     if (!out || !id || world < 1 || rank < 0 || rank >= world || id_bytes != int64_t(sizeof(ncclUniqueId))) return fail(MCPT_ERR_ARG, "bad argument");
     *out = nullptr;
-    const int visible = mcpt_device_count();
-    if (visible <= 0) return fail(MCPT_ERR_NO_DEVICE, "no HIP device available (libmcpt has no CPU fallback)");
+    int visible = 0;
+    if (const int rc = require_device(&visible)) return rc;
     if (ordinal < 0 || ordinal >= visible) return fail(MCPT_ERR_NO_DEVICE, "device ordinal out of range");
     std::unique_ptr<mcpt_comm, void (*)(mcpt_comm*)> c(new mcpt_comm, mcpt_comm_free);
     c->ordinal = ordinal; c->rank = rank; c->world = world;
     std::string err;
-    if (!c->rccl.load(err)) return fail(MCPT_ERR_IO, err);
+    if (!c->rccl.load(err, comm_needs)) return fail(MCPT_ERR_IO, err);
     HIP_TRY(hipSetDevice(ordinal));
     HIP_TRY(create(c->stream, hipStreamCreateWithFlags, hipStreamNonBlocking));
     HIP_TRY(create(c->ev, hipEventCreateWithFlags, hipEventDisableTiming));

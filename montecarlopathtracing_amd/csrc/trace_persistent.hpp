@@ -304,7 +304,7 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
                 unsigned int surv = 0;
 #if MCPT_PRE_TEST
                 w.tris += tri_m;
-                if (!pre) surv = (1u << tri_m) - 1u;       // scenes for which the pre-test is switched off (capi.cpp: too large for the caches)
+                if (!pre) surv = (1u << tri_m) - 1u;       // scenes for which the pre-test is switched off (device.cpp: too large for the caches)
                 else {
                 const PreRay pr = make_pre_ray(F, r, rf.o, margin_f);
                 // MCPT_PRE_UNROLL triangles per round: their records are requested together, so a round costs one memory latency

@@ -239,7 +239,7 @@ void init_launch_cfg(LaunchCfg& cfg, unsigned forced_logic_grid, long long trace
     cfg.min_chunk = min_chunk >= 64 ? min_chunk / 64 * 64 : 256;
     cfg.max_chunk = max_chunk >= 64 ? max_chunk / 64 * 64 : 2048;
     if (cfg.max_chunk < cfg.min_chunk) cfg.max_chunk = cfg.min_chunk;
-    cfg.trace_pool = 0;             // (mcpt_device_create picks the engine from the scene: capi.cpp: trace_engine_for)
+    cfg.trace_pool = 0;             // (mcpt_device_create picks the engine from the scene: scene_api.cpp: trace_engine_for)
     init_launch_cfg_closest(cfg);
 }
 

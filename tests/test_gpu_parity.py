@@ -593,7 +593,7 @@ def test_morton_bounds_scene_same_answers(mcpt, oracle):
         d.close()
 
 
-def test_render_scene_outputs_and_resume(mcpt, tmp_path):
+def test_render_scene_outputs_and_resume(mcpt, tmp_path, monkeypatch):
     """render_scene with the output options: compressed PNG = the same pixels as the reference-format PNG, the PFM = the
     linear frame, and a frame resumed from a checkpoint that holds 3 of 5 partitions = the uninterrupted frame, bit for bit."""
     from PIL import Image
@@ -619,11 +619,20 @@ def test_render_scene_outputs_and_resume(mcpt, tmp_path):
     ck = out + "frame.ckp"
     mcpt.checkpoint_save(ck, sc, part, 6, 9, np.array([1, 0, 1, 1, 0], dtype=np.uint8))
     st = mcpt.Stats()
+    # (no finishing pass from here on: every bounce goes through k_wf_trace, whose share dom_* counts -- a frame this small is otherwise
+    # handed to the finishing pass after its first vertex; the frame is the same either way)
+    monkeypatch.setenv("MCPT_FINISH_PATHS", "0")
     mcpt.render_scene(SCENES, "cornell-box", 6, output_prefix=out + "resumed", checkpoint=ck, checkpoint_parts=5, stats=st, **kw)
     assert open(out + "resumed-SPP6.png", "rb").read() == open(out + "plain-SPP6.png", "rb").read()
     img, done = mcpt.checkpoint_load(ck, sc, 6, 9, 5)
     assert done.all() and np.array_equal(_bits(img), _bits(full))
     assert 0 < st.samples < 80 * 60 * 6              # only the two missing partitions were rendered
+    assert st.dom_rays > 0                           # ... and their statistics keep the trace kernel's share
+    # a progressive frame (a noise target no pass reaches: every sample) reports that share as well
+    sp = mcpt.Stats()
+    mcpt.render_scene(SCENES, "cornell-box", 6, output_prefix=out + "prog", noise_target=1e-12, stats=sp, **kw)
+    assert open(out + "prog-SPP6.png", "rb").read() == open(out + "plain-SPP6.png", "rb").read()
+    assert sp.samples == 80 * 60 * 6 and sp.dom_rays > 0
     # a checkpoint of another frame (different seed) is ignored, not trusted
     mcpt.render_scene(SCENES, "cornell-box", 6, output_prefix=out + "other", checkpoint=ck, checkpoint_parts=5,
                       **dict(kw, seed=10))
