@@ -37,14 +37,14 @@ const Row kRows[] = {
     {"MCPT_SHORT_KERNEL", "1", "0: the voting engine's deep-stack form (36 entries, 3 waves per SIMD) instead of the 27-entry form at 4"},
     {"MCPT_LOGIC_GRID", "resident size", "blocks of the logic kernel's grid"},
     {"MCPT_TRACE_BLOCK_RAYS", "2048", "a block of the trace engines is started per this many rays"},
-    {"MCPT_TRACE_MIN_CHUNK", "256", "ray slots per queue claim, lower bound"},
-    {"MCPT_TRACE_MAX_CHUNK", "2048", "ray slots per queue claim, upper bound"},
+    {"MCPT_TRACE_MIN_CHUNK", "256", "ray slots per queue claim, lower bound (the pool engine's launches and k_wf_trace; not the voting engine's closest-hit and primary launches, which take persistent_chunk)"},
+    {"MCPT_TRACE_MAX_CHUNK", "2048", "ray slots per queue claim, upper bound (the same launches)"},
     {"MCPT_WORKSPACE_GB", "a share of the free HBM", "path-state workspace per frame slot, GiB"},
     {"MCPT_FAST_STACK_LIMIT", "36", "stack entries the culling hierarchy is built to need at most (8..36)"},
     {"MCPT_FAST_LEAF", "4", "most triangles in a leaf of the host-built hierarchy (1..8)"},
     {"MCPT_FAST_CT", "1.6", "SAH cost of a leaf triangle relative to a node"},
     {"MCPT_BUILD_SERIAL", "0", "1: the host SAH builder on one thread (the threaded build gives the same tree)"},
-    {"MCPT_NODE_CACHE", "engine default", "nodes of the top of the tree the engines may mirror in LDS"},
+    {"MCPT_NODE_CACHE", "engine default", "nodes of the top of the tree the engines may mirror in LDS; no effect unless compiled with MCPT_POOL_CACHE_N > 0"},
     {"MCPT_CLUSTER_LEAF", "1", "MCPT_BUILD_DEVICE_FAST: triangles per leaf of a Morton cluster (1..8)"},
     {"MCPT_CLUSTER_LEVELS", "1", "MCPT_BUILD_DEVICE_FAST: levels of 4-wide nodes built on the GPU (1..5)"},
     {"MCPT_PLOC_CLUSTER", "4096", "MCPT_BUILD_DEVICE_SAH: most triangles in a cluster grown on the GPU"},
