@@ -397,6 +397,43 @@ int mcpt_device_get_lens(const mcpt_device*, mcpt_lens*);
 /* test seam: the camera rays of samples (pix[i], k[i]) under the device's lens (active or not) -> rays6[n*6] = origin xyz, direction xyz */
 int mcpt_camera_rays(mcpt_device*, uint64_t seed, const int32_t* pix, const int32_t* k, int64_t n, double* rays6);
 
+/* ---- environment light (since the environment change; the reference lights a scene with its emissive triangles only) ---- */
+/* An ENVIRONMENT is a latitude-longitude RGB radiance map of W x H texels (W, H >= 1), top row first, every texel finite and >= 0; scale > 0
+ * multiplies the radiance.  A 1x1 map is a constant sky.  Without one, a ray that leaves the scene brings 0, as in the reference.
+ *   frame: world +Y is up.  Row i covers cos(theta) in [c[i+1], c[i]], c[i] = cos(pi i / H) in fp64 on the host, c[0] = 1, c[H] = -1;
+ *     column j covers phi in [2 pi j / W, 2 pi (j+1) / W); a direction is (sin(theta) cos(phi), cos(theta), sin(theta) sin(phi)).
+ *   lookup Le(d), nearest texel: phi = atan2(d.z, d.x) (+ 2 pi if negative), j = min(W-1, floor((phi * W) / (2 pi))); i = the row with
+ *     c[i+1] < y <= c[i] (the last row also takes y = -1), y = d.y clamped to [-1, 1], found by binary search in c; Le(d) = scale * texel(i, j).
+ *   sampling tables (host, fp64): w_ij = lum_ij * omega_ij, lum = (0.2126 r + 0.7152 g) + 0.0722 b, omega_ij = ((c[i] - c[i+1]) * 2 pi) / W;
+ *     per row the running sums of w_ij left to right (the conditional CDF), over the rows the running sums of each row's last entry (the
+ *     marginal CDF); Z = the marginal's last entry.  Z == 0: the environment is INACTIVE and everything is as without one.
+ *   a draw from uniforms u0..u3: row i = first i with u0 * Z < marg[i], column j = first j with u1 * rowsum_i < cond[i][j] (binary
+ *     searches); cos(theta) = c[i] + (c[i+1] - c[i]) * u2, sin(theta) = sqrt(max(0, 1 - cos^2)), phi = (2 pi (j + u3)) / W;
+ *     pdf = lum_ij / Z per unit solid angle (constant over the texel: no Jacobian).  A 1x1 map draws uniformly over the sphere.
+ *   light sample at a vertex p with normal pn and diffuse colour kd, after the scene's lights, from Philox block nl + 2 of the vertex's
+ *     depth (nl = the scene's lights; every other draw is unchanged): direction d, k = d . pn; !(k > 0): no shadow ray.  Otherwise a shadow
+ *     ray from p + 0.01 d along d that must leave the scene, contributing c = (kd * Le) * (((k / |pn|) / pi) / pdf) per channel.
+ *   rays that leave the scene: a camera ray brings Le(d), unweighted; a SPECULAR or TRANSMISSION bounce ray adds T' * Le(d), T' = T * w / 0.6
+ *     the throughput the next vertex would have had; a DIFFUSE bounce ray adds nothing (light sampling covers the diffuse lobe, as for
+ *     emitters, pathTracing.cpp:247-261).  A pixel whose primary ray missed folds Le(primary direction) for each of its N samples through
+ *     the frame's float fold; it keeps a standard error of 0 and stays out of the noise sums and an adaptive frame's active list.
+ * Every pipeline (wavefront, MCPT_RENDER_MEGAKERNEL, lenses, partitions, progressive and adaptive handles) renders the same frame under it.
+ * A progressive handle takes the device's environment when it is created.  AOVs and the denoiser treat a missed pixel as before. */
+typedef struct { int32_t width, height; const float* rgb; double scale; int32_t flags, reserved; } mcpt_environment;
+/* NULL clears it; the device copies the texels.  MCPT_ERR_ARG: a size < 1, a texel that is NaN, inf or < 0, scale not finite or <= 0, flags or
+ * reserved != 0. */
+int mcpt_device_set_environment(mcpt_device*, const mcpt_environment*);
+/* width = height = 0 when there is none; Z = 0 when it is inactive.  Any pointer may be NULL. */
+int mcpt_device_get_environment(const mcpt_device*, int32_t* width, int32_t* height, double* scale, double* Z);
+/* test seams: rgb[n*3] = Le(dirs[i]) under the device's environment; the draw of vertex `depth` of camera samples (pix[i], k[i]) ->
+ * dirs[n*3], pdf[n], rgb[n*3] (the radiance of the drawn texel).  MCPT_ERR_ARG without an active environment. */
+int mcpt_environment_eval(mcpt_device*, const double* dirs, int64_t n, double* rgb);
+int mcpt_environment_sample(mcpt_device*, uint64_t seed, const int32_t* pix, const int32_t* k, int32_t depth, int64_t n, double* dirs, double* pdf,
+                            double* rgb);
+/* a PFM file (the format mcpt_write_pfm writes; 'PF' colour only) -> its size and, when rgb is not NULL, w*h*3 floats top row first (cap:
+ * floats rgb holds; too few: MCPT_ERR_ARG).  MCPT_ERR_IO: no file; MCPT_ERR_PARSE: not a colour PFM. */
+int mcpt_read_pfm(const char* file, int32_t* width, int32_t* height, float* rgb, int64_t cap);
+
 /* ---- integrator over several GPUs of one node (no reference counterpart: generateImg is single-process OpenMP) ---- */
 /* The frame is cut into tiles dealt to the GPUs exactly as mcpt_render_params.rank/world describe (rank r = devices[r]); the scene
  * is resident on every GPU; one host thread per GPU renders its tiles; at the end of the frame every rank's pixels travel as one
@@ -423,6 +460,7 @@ int  mcpt_multi_collect_stats(mcpt_multi*, mcpt_stats* stats);
 int  mcpt_multi_last_timing(const mcpt_multi*, double* render_ms, double* gather_ms, int32_t* comm_ranks);
 void mcpt_multi_free(mcpt_multi*);
 int  mcpt_multi_set_lens(mcpt_multi*, const mcpt_lens*);     /* every device of the group (NULL: the pinhole) */
+int  mcpt_multi_set_environment(mcpt_multi*, const mcpt_environment*);   /* every device of the group (NULL: none) */
 
 /* ---- one process per GPU (since 105; no reference counterpart) ---- */
 /* The same exchange between the PROCESSES of a launch: every rank is a process that drives one GPU through mcpt_device_* (params->rank /
@@ -521,6 +559,13 @@ int  mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp,
  * resumes from a pinhole frame's checkpoint nor the reverse, and a pinhole frame's identity is what it was before lenses existed. */
 int  mcpt_render_scene_lens(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, int64_t options_bytes,
                             const mcpt_lens*, mcpt_stats* stats);
+/* mcpt_render_scene_lens under an environment light: environment_pfm (NULL: none, = mcpt_render_scene_lens) is a colour PFM read with
+ * mcpt_read_pfm, environment_scale its mcpt_environment.scale; on the device or on every GPU of the options.  A map that cannot be read
+ * (MCPT_ERR_IO / MCPT_ERR_PARSE) or is invalid (MCPT_ERR_ARG) is refused before anything else is read or written.  A checkpoint's frame
+ * identity includes the environment when it is active (its size, scale and texels): such a frame never resumes from a checkpoint of a frame
+ * without it nor the reverse, and a frame without one (or with an inactive one) keeps the identity it had before environments existed. */
+int  mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, int64_t options_bytes,
+                           const mcpt_lens*, const char* environment_pfm, double environment_scale, mcpt_stats* stats);
 
 #ifdef __cplusplus
 }

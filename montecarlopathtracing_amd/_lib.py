@@ -81,6 +81,12 @@ class Lens(C.Structure):
     _fields_ = [("flags", C.c_int32), ("reserved", C.c_int32), ("aperture", C.c_double), ("focus_distance", C.c_double)]
 
 
+class Environment(C.Structure):
+    """mcpt_environment (mcpt.h: environment light)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("rgb", C.POINTER(C.c_float)), ("scale", C.c_double), ("flags", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class FastInfo(C.Structure):
     """mcpt_fast_info: shape and origin of the culling hierarchy a device's fast walk walks (mcpt_device_fast_hierarchy)"""
     _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_tris", "enabled", "cw_stack_need", "max_depth", "builder", "clusters", "reserved")]
@@ -116,6 +122,8 @@ EXPORTS = [
     "mcpt_comm_unique_id", "mcpt_comm_create", "mcpt_comm_size", "mcpt_comm_gather_frame", "mcpt_comm_allreduce", "mcpt_comm_free",
     "mcpt_render_scene", "mcpt_render_scene_ex", "mcpt_render_scene_opts",
     "mcpt_device_set_lens", "mcpt_device_get_lens", "mcpt_camera_rays", "mcpt_multi_set_lens", "mcpt_render_scene_lens",
+    "mcpt_device_set_environment", "mcpt_device_get_environment", "mcpt_environment_eval", "mcpt_environment_sample", "mcpt_read_pfm",
+    "mcpt_multi_set_environment", "mcpt_render_scene_env",
 ]
 
 
@@ -232,6 +240,15 @@ def lib():
     L.mcpt_multi_set_lens.argtypes = [P, C.POINTER(Lens)]
     L.mcpt_render_scene_lens.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens),
                                          C.POINTER(Stats)]
+    F32 = C.POINTER(C.c_float)
+    L.mcpt_device_set_environment.argtypes = [P, C.POINTER(Environment)]
+    L.mcpt_device_get_environment.argtypes = [P, I32, I32, D, D]
+    L.mcpt_environment_eval.argtypes = [P, D, C.c_int64, D]
+    L.mcpt_environment_sample.argtypes = [P, C.c_uint64, I32, I32, C.c_int32, C.c_int64, D, D, D]
+    L.mcpt_read_pfm.argtypes = [C.c_char_p, I32, I32, F32, C.c_int64]
+    L.mcpt_multi_set_environment.argtypes = [P, C.POINTER(Environment)]
+    L.mcpt_render_scene_env.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens), C.c_char_p,
+                                        C.c_double, C.POINTER(Stats)]
     _lib = L
     return L
 

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, DenoiseParams, FastInfo, Lens, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
+from ._lib import AdaptiveParams, DenoiseParams, Environment, FastInfo, Lens, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -29,6 +29,19 @@ def make_lens(aperture=0.0, focus_distance=0.0, jitter=False, per_sample=False):
     """An mcpt_lens: jitter = uniform over the pixel square, aperture > 0 = a thin lens of that radius focused at focus_distance
     (<= 0: at look_at), per_sample = a camera ray per sample even for the pinhole (mcpt.h: camera lens)."""
     return Lens((LENS_JITTER if jitter else 0) | (LENS_PER_SAMPLE if per_sample else 0), 0, float(aperture), float(focus_distance))
+
+
+def make_environment(rgb, scale=1.0):
+    """An mcpt_environment and the float32 texels it points to (keep both alive while it is used): rgb = an (H, W, 3) radiance map, top
+    row first, or an (r, g, b) constant sky (a 1x1 map)."""
+    a = np.asarray(rgb, dtype=np.float64)
+    if a.ndim == 1:
+        a = a.reshape(1, 1, 3)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("an environment is an (H, W, 3) array or an (r, g, b) triple")
+    tex = np.ascontiguousarray(a, dtype=np.float32)
+    e = Environment(tex.shape[1], tex.shape[0], _p(tex, C.c_float), float(scale), 0, 0)
+    return e, tex
 
 
 def _as_lens(lens):
@@ -326,6 +339,42 @@ class Device:
         check(lib().mcpt_camera_rays(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), pix.shape[0], _p(rays, C.c_double)))
         return rays
 
+    def set_environment(self, rgb=None, scale=1.0):
+        """The environment light of every later frame, sample_radiance and progressive handle created after it (mcpt_device_set_environment):
+        rgb = an (H, W, 3) lat-long radiance map (top row first) or an (r, g, b) constant sky; None clears it."""
+        if rgb is None:
+            check(lib().mcpt_device_set_environment(self._h, None))
+            return
+        e, tex = make_environment(rgb, scale)
+        check(lib().mcpt_device_set_environment(self._h, C.byref(e)))
+        del tex
+
+    @property
+    def environment(self):
+        """the device's environment: None, or a dict of width, height, scale and Z (Z == 0: inactive)"""
+        w, h, s, z = C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
+        check(lib().mcpt_device_get_environment(self._h, C.byref(w), C.byref(h), C.byref(s), C.byref(z)))
+        if w.value == 0:
+            return None
+        return {"width": w.value, "height": h.value, "scale": s.value, "Z": z.value}
+
+    def environment_eval(self, dirs):
+        """Le(dirs[i]) under the device's (active) environment: (n, 3)"""
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        rgb = np.zeros((dirs.shape[0], 3))
+        check(lib().mcpt_environment_eval(self._h, _p(dirs, C.c_double), dirs.shape[0], _p(rgb, C.c_double)))
+        return rgb
+
+    def environment_sample(self, seed, pix, k, depth):
+        """the environment's draw at vertex `depth` of camera samples (pix[i], k[i]): directions (n, 3), pdf (n,), radiance (n, 3)"""
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        n = pix.shape[0]
+        dirs, pdf, rgb = np.zeros((n, 3)), np.zeros(n), np.zeros((n, 3))
+        check(lib().mcpt_environment_sample(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), int(depth), n, _p(dirs, C.c_double),
+                                            _p(pdf, C.c_double), _p(rgb, C.c_double)))
+        return dirs, pdf, rgb
+
     def progressive(self, spp, seed=0, rank=0, world=1, tile_w=0, tile_h=0, flags=0):
         """A frame of `spp` samples per pixel rendered in passes (mcpt_progressive_*): see Progressive."""
         return Progressive(self, spp, seed, rank, world, tile_w, tile_h, flags)
@@ -465,6 +514,15 @@ class MultiDevice:
         """the same lens on every device of the group (Device.set_lens)"""
         check(lib().mcpt_multi_set_lens(self._h, C.byref(make_lens(aperture, focus_distance, jitter, per_sample))))
 
+    def set_environment(self, rgb=None, scale=1.0):
+        """the same environment on every device of the group (Device.set_environment)"""
+        if rgb is None:
+            check(lib().mcpt_multi_set_environment(self._h, None))
+            return
+        e, tex = make_environment(rgb, scale)
+        check(lib().mcpt_multi_set_environment(self._h, C.byref(e)))
+        del tex
+
     def generateImg(self, spp, seed=0, tile_w=0, tile_h=0, flags=0, stats=None):
         img = np.zeros((self.height, self.width, 3))
         rp = RenderParams(spp, seed, 0, 1, tile_w, tile_h, flags)
@@ -542,6 +600,15 @@ def png_bytes_deflate(rgb8):
     return out[:n].tobytes()
 
 
+def read_pfm(file):
+    """A colour PFM (as write_pfm writes it) -> float32 [H, W, 3], top row first."""
+    w, h = C.c_int32(), C.c_int32()
+    check(lib().mcpt_read_pfm(file.encode(), C.byref(w), C.byref(h), None, 0))
+    out = np.zeros((h.value, w.value, 3), dtype=np.float32)
+    check(lib().mcpt_read_pfm(file.encode(), C.byref(w), C.byref(h), _p(out, C.c_float), out.size))
+    return out
+
+
 def write_pfm(file, img):
     """Linear radiance [H,W,3] as a little-endian fp32 Portable Float Map."""
     img = np.ascontiguousarray(img, dtype=np.float64)
@@ -580,13 +647,14 @@ def morton_code(x, y, z):
 
 def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, height=0, quiet=True, output_prefix=None, stats=None,
                  load_flags=0, output_flags=0, checkpoint=None, checkpoint_parts=0, devices=None, gather=GATHER_PEER, noise_target=0.0,
-                 time_budget_s=0.0, adaptive_min_spp=0, abs_target=0.0, lens=None):
+                 time_budget_s=0.0, adaptive_min_spp=0, abs_target=0.0, lens=None, environment=None, environment_scale=1.0):
     """render_scene(path, filename, N) of MTPC/MTPC.cpp:35; writes <prefix>-SPP<N>.png (default ../result/<filename>).
     devices: list of GPU ordinals, or -1 for every visible GPU (the frame is then rendered by mcpt_multi_*).
     noise_target / time_budget_s / OUT_ERROR_PFM: a progressive frame that may stop at k < N samples (<prefix>-SPP<k>.png).
     adaptive_min_spp > 0: an adaptive frame, noise_target and abs_target its per-pixel targets (OUT_SPP_PFM: the sample-count map).
     OUT_DENOISED / OUT_AOV_PFM: also the denoised frame (.denoised.png, .denoised.pfm with OUT_PFM) / the first-hit AOVs as .pfm files.
-    lens: None (the pinhole), a Lens or a dict of Device.set_lens's arguments; rendered through mcpt_render_scene_lens."""
+    lens: None (the pinhole), a Lens or a dict of Device.set_lens's arguments; rendered through mcpt_render_scene_lens.
+    environment: None, or the path of a colour PFM lat-long map (environment_scale: its scale); rendered through mcpt_render_scene_env."""
     dev_arr, ndev = None, 0
     if devices == -1:
         ndev = -1
@@ -597,7 +665,10 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
                            load_flags, output_flags, checkpoint.encode() if checkpoint else None, checkpoint_parts, 0,
                            ndev, gather, dev_arr, noise_target, time_budget_s, adaptive_min_spp, 0, abs_target)
     st = C.byref(stats) if stats is not None else None
-    if lens is None:
+    if environment is not None:
+        check(lib().mcpt_render_scene_env(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o),
+                                          C.byref(_as_lens(lens)) if lens is not None else None, environment.encode(), float(environment_scale), st))
+    elif lens is None:
         check(lib().mcpt_render_scene_opts(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o), st))
     else:
         check(lib().mcpt_render_scene_lens(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o), C.byref(_as_lens(lens)), st))

@@ -39,7 +39,9 @@ __global__ void __launch_bounds__(256) k_camera_rays(DLens lens, unsigned long l
 }
 
 // The megakernel with a lens: one lane per camera sample traces its own camera ray (reference-shaped walk) and shades the path from its
-// hit, as k_shade_samples does from the pixel's shared one.  Lane (slot, k) -> rad[(slot*spp + k)*3], flags[slot*spp + k].
+// hit, as k_shade_samples does from the pixel's shared one.  Lane (slot, k) -> rad[(slot*spp + k)*3], flags[slot*spp + k].  ENV: an active
+// environment (a camera ray that misses gives Le of its direction).
+template <bool ENV>
 __global__ void __launch_bounds__(256) k_shade_samples_lens(DScene S, DLens lens, unsigned long long seed, const int32_t* __restrict__ pixels,
                                                             int first_slot, long long n_samples, int spp, int sample_base, double* __restrict__ rad,
                                                             uint8_t* __restrict__ flags, DCounters* ctr)
@@ -58,8 +60,8 @@ __global__ void __launch_bounds__(256) k_shade_samples_lens(DScene S, DLens lens
         double out[3] = {0, 0, 0};
         if (ok) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix; key.sample = (uint32_t)k;
-            shade_path(S, key, r.d, h, out, ls);
-        }
+            shade_path<ENV>(S, key, r.d, h, out, ls);
+        } else if (ENV) env_camera_miss(S, r.d, out);
         rad[gid * 3] = out[0]; rad[gid * 3 + 1] = out[1]; rad[gid * 3 + 2] = out[2];
         flags[gid] = ok ? 1 : 0;
     }
@@ -67,6 +69,7 @@ __global__ void __launch_bounds__(256) k_shade_samples_lens(DScene S, DLens lens
 }
 
 // mcpt_sample_radiance with a lens: arbitrary (pixel, k) pairs
+template <bool ENV>
 __global__ void __launch_bounds__(256) k_sample_radiance_lens(DScene S, DLens lens, unsigned long long seed, const int32_t* __restrict__ pix,
                                                               const int32_t* __restrict__ ks, long long n, double* __restrict__ rgb, DCounters* ctr)
 {
@@ -80,8 +83,8 @@ __global__ void __launch_bounds__(256) k_sample_radiance_lens(DScene S, DLens le
         ls.primary = 1; ls.samples = 1;
         if (trace_closest(S, r, h, w)) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix[gid]; key.sample = (uint32_t)ks[gid];
-            shade_path(S, key, r.d, h, out, ls);
-        }
+            shade_path<ENV>(S, key, r.d, h, out, ls);
+        } else if (ENV) env_camera_miss(S, r.d, out);
         ls.nodes += w.nodes; ls.tris += w.tris;
         rgb[gid * 3] = out[0]; rgb[gid * 3 + 1] = out[1]; rgb[gid * 3 + 2] = out[2];
     }
@@ -117,8 +120,9 @@ __global__ void __launch_bounds__(256) k_camera_pass(DLens lens, WfArgs a, long 
 // k_fold_samples / k_fold_progressive for the per-sample route.  A camera ray that missed gives radiance +0.0, which leaves the fold and
 // the moments as they are, so a pixel none of whose rays of the pass hit is not read at all: it keeps +0.0 and zero moments from its first
 // pass on -- what the per-pixel route writes for a missed pixel.  PROG: the pixel's count of hit samples continues (one
-// lane per pixel writes it: c == 0), hit[pix] = count > 0.  One lane per (slot, channel).
-template <bool PROG>
+// lane per pixel writes it: c == 0), hit[pix] = count > 0.  One lane per (slot, channel).  ENV: a camera ray that missed has radiance Le
+// of its direction, so every pixel folds all its samples into the image and both moments, whether or not any of them hit.
+template <bool PROG, bool ENV>
 __global__ void k_fold_lens(const double* __restrict__ rad, const uint8_t* __restrict__ flags, const int32_t* __restrict__ pixels, int first_slot,
                             int n_slots, int n, int k0, int N, double* __restrict__ img, double* __restrict__ mom, uint8_t* __restrict__ hit,
                             int32_t* __restrict__ hitcnt)
@@ -135,7 +139,7 @@ __global__ void k_fold_lens(const double* __restrict__ rad, const uint8_t* __res
     const size_t i = (size_t)pix * 3 + c;
     if (!PROG) {
         float acc = 0.0f;
-        if (h > 0)
+        if (h > 0 || ENV)
             for (int k = 0; k < n; k++) acc = (float)((double)acc + src[(size_t)k * 3] / n);
         img[i] = (double)acc;
         return;
@@ -146,7 +150,7 @@ __global__ void k_fold_lens(const double* __restrict__ rad, const uint8_t* __res
         hit[pix] = total > 0 ? 1 : 0;
     }
     double* m = mom + (size_t)pix * 6 + c;
-    if (h == 0) {                                    // nothing to add: the image and the moments stay (+0.0 from the first pass on)
+    if (h == 0 && !ENV) {                            // nothing to add: the image and the moments stay (+0.0 from the first pass on)
         if (k0 == 0) { img[i] = 0.0; m[0] = 0.0; m[3] = 0.0; }
         return;
     }
@@ -179,26 +183,36 @@ void launch_shade_samples_lens(const DScene& S, const DLens& lens, unsigned long
 {
     const long long n = (long long)n_slots * spp;
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_shade_samples_lens, dim3(blocks_of(n, 256)), dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad,
-                       d_flags, ctr);
+    if (env_on(S.env))
+        hipLaunchKernelGGL(k_shade_samples_lens<true>, dim3(blocks_of(n, 256)), dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad,
+                           d_flags, ctr);
+    else
+        hipLaunchKernelGGL(k_shade_samples_lens<false>, dim3(blocks_of(n, 256)), dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad,
+                           d_flags, ctr);
 }
 void launch_sample_radiance_lens(const DScene& S, const DLens& lens, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, long long n,
                                  double* d_rgb, DCounters* ctr, hipStream_t st)
 {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_sample_radiance_lens, dim3(blocks_of(n, 256)), dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr);
+    if (env_on(S.env)) hipLaunchKernelGGL(k_sample_radiance_lens<true>, dim3(blocks_of(n, 256)), dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr);
+    else hipLaunchKernelGGL(k_sample_radiance_lens<false>, dim3(blocks_of(n, 256)), dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr);
 }
 void launch_camera_pass(const DLens& lens, const WfArgs& a, long long n_samples, hipStream_t st)
 {
     hipLaunchKernelGGL(k_camera_pass, dim3(blocks_of(n_samples > 0 ? n_samples : 1, 256)), dim3(256), 0, st, lens, a, n_samples);
 }
 void launch_fold_lens(const double* d_rad, const uint8_t* d_flags, const int32_t* d_pixels, int first_slot, int n_slots, int n, int k0, int N,
-                      double* d_img, double* d_mom, uint8_t* d_hit, int32_t* d_hitcnt, hipStream_t st)
+                      double* d_img, double* d_mom, uint8_t* d_hit, int32_t* d_hitcnt, bool env, hipStream_t st)
 {
     if (n_slots <= 0) return;
     const dim3 grid(blocks_of((long long)n_slots * 3, 256));
-    if (d_mom) hipLaunchKernelGGL(k_fold_lens<true>, grid, dim3(256), 0, st, d_rad, d_flags, d_pixels, first_slot, n_slots, n, k0, N, d_img, d_mom, d_hit, d_hitcnt);
-    else hipLaunchKernelGGL(k_fold_lens<false>, grid, dim3(256), 0, st, d_rad, d_flags, d_pixels, first_slot, n_slots, n, k0, N, d_img, d_mom, d_hit, d_hitcnt);
+    if (env) {
+        if (d_mom) hipLaunchKernelGGL((k_fold_lens<true, true>), grid, dim3(256), 0, st, d_rad, d_flags, d_pixels, first_slot, n_slots, n, k0, N, d_img, d_mom, d_hit, d_hitcnt);
+        else hipLaunchKernelGGL((k_fold_lens<false, true>), grid, dim3(256), 0, st, d_rad, d_flags, d_pixels, first_slot, n_slots, n, k0, N, d_img, d_mom, d_hit, d_hitcnt);
+        return;
+    }
+    if (d_mom) hipLaunchKernelGGL((k_fold_lens<true, false>), grid, dim3(256), 0, st, d_rad, d_flags, d_pixels, first_slot, n_slots, n, k0, N, d_img, d_mom, d_hit, d_hitcnt);
+    else hipLaunchKernelGGL((k_fold_lens<false, false>), grid, dim3(256), 0, st, d_rad, d_flags, d_pixels, first_slot, n_slots, n, k0, N, d_img, d_mom, d_hit, d_hitcnt);
 }
 
 }  // namespace mcpt

@@ -115,6 +115,17 @@ struct DLens {
     int32_t flags, pad;
 };
 
+// The environment light of a frame (env.hpp; tables built by environment.cpp).  All zero: none -- or an inactive one, Z == 0 -- and the
+// kernels are the instantiations without it.
+struct DEnv {
+    const float* rgb;           // [H][W][3] texels, top row first
+    const double* c;            // [H + 1] row borders: c[i] = cos(pi i / H), c[0] = 1, c[H] = -1
+    const double* marg;         // [H] marginal CDF over rows: running sums of the rows' weights, marg[H-1] = Z
+    const double* cond;         // [H][W] per row: running sums of w_ij = lum_ij * omega_ij
+    int32_t W, H;
+    double scale, Z;
+};
+
 struct DScene {
     const DNode* nodes;
     const DTri* tris;
@@ -128,7 +139,13 @@ struct DScene {
     int32_t t, Lv, Level, Nr, num_lights, num_materials;
     double area0;                                  // range of the frozen static u1 (Q1)
     DCamera cam;
+    DEnv env;                                      // rgb == null: no (active) environment
 };
+
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool env_on(const DEnv& e) { return e.rgb != nullptr; }
 
 // device-side counters (one cache line)
 struct DCounters {

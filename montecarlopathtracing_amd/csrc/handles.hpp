@@ -42,6 +42,19 @@ struct mcpt_scene {
 // start/stop events around a launch or a frame
 using EventPair = std::pair<mcpt::Event, mcpt::Event>;
 
+namespace mcpt {
+// An environment as a device holds it (environment.cpp): the caller's texels and the sampling tables, on the GPU.  Shared: a progressive
+// handle keeps the one it was created under alive after the device's is replaced.  denv is all zero when the map is inactive (Z == 0).
+struct EnvData {
+    int32_t W = 0, H = 0;
+    double scale = 1.0, Z = 0.0;
+    std::vector<float> rgb;                 // the caller's texels (the checkpoint identity mixes them in)
+    DevBuf<float> d_rgb;
+    DevBuf<double> d_c, d_marg, d_cond;
+    DEnv denv{};
+};
+}  // namespace mcpt
+
 struct mcpt_device {
     int ordinal = 0;
     mcpt::Knobs knobs;                     // the environment as it was when this device was created (knobs.hpp)
@@ -61,6 +74,7 @@ struct mcpt_device {
     bool dirs_ready = false;
     mcpt_lens lens{};                      // mcpt_device_set_lens (all zero: the reference's pinhole)
     mcpt::DevBuf<double> pos;              // W*H*3 image-plane points pos(i,j), made on the first frame under an active lens
+    std::shared_ptr<const mcpt::EnvData> env;   // mcpt_device_set_environment (null: none); ds.env is its denv
     // render workspace
     mcpt::DevBuf<int32_t> pixels; int64_t n_pixels = 0; int part_key[4] = {-1, -1, -1, -1};
     mcpt::Event ev[4];
@@ -129,6 +143,10 @@ int tile_shape(const mcpt_render_params* p, TileShape& t);
 // the pixels (y * W + x, in scan order) that p's rank owns in a W x H frame; MCPT_ERR_ARG as tile_shape
 int owned_pixels(int W, int H, const mcpt_render_params* p, std::vector<int32_t>& out);
 
+// ---- environment.cpp
+int env_check(const mcpt_environment* e);
+int env_make(const mcpt_environment* e, std::shared_ptr<mcpt::EnvData>& out);   // tables + upload on the current device (e valid)
+
 // ---- render.cpp
 inline bool lens_active(const mcpt_lens& l) { return l.flags != 0 || l.aperture > 0.0; }
 int lens_check(const mcpt_lens* l);
@@ -151,6 +169,7 @@ struct SampleRange {
     uint8_t* hit;
     const mcpt_lens* lens;      // the lens of the call (the device's, or the one a progressive handle took); null: the pinhole
     int32_t* hitcnt;            // progressive passes under an active lens: per pixel, the samples whose camera ray hit
+    const mcpt::EnvData* env;   // the environment of the call (the device's, or the one a progressive handle took); null: none
 };
 
 // The pixels a render call covers, on the device: the partition's owned list (mcpt_render*, uniform progressive passes) or an adaptive

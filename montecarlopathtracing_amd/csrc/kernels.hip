@@ -178,7 +178,8 @@ __global__ void __launch_bounds__(256) k_primary_hits_reference(DScene S, const 
 
 // One lane per camera sample.  Samples of one pixel are consecutive lanes, so a wave starts from one shared
 // primary hit (coherent first vertex and shadow rays).  Radiance goes to rad[(slot*spp + k)*3]; lane k of a slot renders camera
-// sample sample_base + k (a whole frame: 0).
+// sample sample_base + k (a whole frame: 0).  ENV: S.env is active (a pixel whose primary ray missed is folded from Le, not from rad).
+template <bool ENV>
 __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long long seed, const double* __restrict__ dirs,
                                                        const int32_t* __restrict__ pixels, const PrimaryHit* __restrict__ hits,
                                                        int first_slot, long long n_samples, int spp, int sample_base, double* __restrict__ rad, DCounters* ctr)
@@ -195,7 +196,7 @@ __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long l
         if (ph.leaf >= 0) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix; key.sample = (uint32_t)(sample_base + k);
             Hit h; h.leaf = ph.leaf; h.t = ph.t; h.p = mk(ph.p[0], ph.p[1], ph.p[2]);
-            shade_path(S, key, ld3(dirs + (size_t)pix * 3), h, r, ls);
+            shade_path<ENV>(S, key, ld3(dirs + (size_t)pix * 3), h, r, ls);
         }
         rad[gid * 3] = r[0]; rad[gid * 3 + 1] = r[1]; rad[gid * 3 + 2] = r[2];
     }
@@ -203,6 +204,7 @@ __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long l
 }
 
 // mcpt_sample_radiance: arbitrary (pixel, k) pairs, primary ray traced per sample.
+template <bool ENV>
 __global__ void __launch_bounds__(256) k_sample_radiance(DScene S, unsigned long long seed, const double* __restrict__ dirs,
                                                          const int32_t* __restrict__ pix, const int32_t* __restrict__ ks, long long n,
                                                          double* __restrict__ rgb, DCounters* ctr)
@@ -216,8 +218,8 @@ __global__ void __launch_bounds__(256) k_sample_radiance(DScene S, unsigned long
         ls.primary = 1; ls.samples = 1;
         if (trace_closest(S, r, h, w)) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix[gid]; key.sample = (uint32_t)ks[gid];
-            shade_path(S, key, r.d, h, out, ls);
-        }
+            shade_path<ENV>(S, key, r.d, h, out, ls);
+        } else if (ENV) env_camera_miss(S, r.d, out);
         ls.nodes += w.nodes; ls.tris += w.tris;
         rgb[gid * 3] = out[0]; rgb[gid * 3 + 1] = out[1]; rgb[gid * 3 + 2] = out[2];
     }
@@ -225,9 +227,11 @@ __global__ void __launch_bounds__(256) k_sample_radiance(DScene S, unsigned long
 }
 
 // Per pixel: acc(float) += radiance/N for k = 0..N-1 in order (pathTracing.cpp:301,316-318 with D3), widened
-// to double for image::img (sceneManagement.h:221).  One lane per (pixel, channel).
+// to double for image::img (sceneManagement.h:221).  One lane per (pixel, channel).  ENV: a pixel whose primary ray missed folds
+// Le(primary direction) for each of its samples, through the same float fold.
+template <bool ENV>
 __global__ void k_fold_samples(const double* __restrict__ rad, const int32_t* __restrict__ pixels, const PrimaryHit* __restrict__ hits,
-                               int first_slot, int n_slots, int spp, double* __restrict__ img)
+                               int first_slot, int n_slots, int spp, double* __restrict__ img, DEnv env, const double* __restrict__ dirs)
 {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)n_slots * 3) return;
@@ -237,6 +241,11 @@ __global__ void k_fold_samples(const double* __restrict__ rad, const int32_t* __
     float acc = 0.0f;
     if (hits[slot].leaf >= 0)            // a primary miss adds nothing (pathTracing.cpp:311)
         for (int k = 0; k < spp; k++) acc = (float)((double)acc + src[(size_t)k * 3] / spp);
+    else if (ENV) {                      // ... but the environment's radiance
+        const V3 le = env_eval(env, ld3(dirs + (size_t)(pixels ? pixels[slot] : slot) * 3));
+        const double x = c == 0 ? le.x : (c == 1 ? le.y : le.z);
+        for (int k = 0; k < spp; k++) acc = (float)((double)acc + x / spp);
+    }
     const int pix = pixels ? pixels[slot] : slot;
     img[(size_t)pix * 3 + c] = (double)acc;
 }
@@ -246,10 +255,11 @@ __global__ void k_fold_samples(const double* __restrict__ rad, const int32_t* __
 // float), so once every pass is in, img is k_fold_samples' frame bit for bit whatever the pass boundaries were.  Beside it the pixel's
 // first and second moments of the radiance, in fp64 in k order: mom[pix][0][c] = sum x, mom[pix][1][c] = sum x*x (no contraction:
 // the library is built with -ffp-contract=off).  hit[pix] records whether the pixel's primary ray hit (k_noise_reduce counts only those).
-// One lane per (slot, channel).
+// One lane per (slot, channel).  ENV: a missed pixel's image continues the fold of Le(primary direction), its first moment the sum.
+template <bool ENV>
 __global__ void k_fold_progressive(const double* __restrict__ rad, const int32_t* __restrict__ pixels, const PrimaryHit* __restrict__ hits,
                                    int first_slot, int n_slots, int n, int k0, int N, double* __restrict__ img, double* __restrict__ mom,
-                                   uint8_t* __restrict__ hit)
+                                   uint8_t* __restrict__ hit, DEnv env, const double* __restrict__ dirs)
 {
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= (long long)n_slots * 3) return;
@@ -258,7 +268,20 @@ __global__ void k_fold_progressive(const double* __restrict__ rad, const int32_t
     const int pix = pixels ? pixels[slot] : slot;
     const bool h = hits[slot].leaf >= 0;
     if (c == 0) hit[pix] = h ? 1 : 0;
-    if (!h) { img[(size_t)pix * 3 + c] = 0.0; return; }    // a primary miss adds nothing (pathTracing.cpp:311); its moments stay 0
+    if (!h) {                                               // a primary miss adds nothing (pathTracing.cpp:311); its moments stay 0
+        if (ENV) {                                          // every sample of the pixel is Le(primary direction): the image holds the whole
+            const V3 le = env_eval(env, ld3(dirs + (size_t)pix * 3));      // frame's fold from the first pass on (mcpt_progressive_image shows it
+            const double x = c == 0 ? le.x : (c == 1 ? le.y : le.z);      // for a missed pixel at any count); the first moment sums the samples
+            double* m = mom + (size_t)pix * 6 + c;                          // so far, the second stays 0 (standard error 0)
+            float acc = 0.0f;
+            for (int k = 0; k < N; k++) acc = (float)((double)acc + x / N);
+            double s1 = k0 > 0 ? m[0] : 0.0;
+            for (int k = 0; k < n; k++) s1 += x;
+            img[(size_t)pix * 3 + c] = (double)acc;
+            m[0] = s1; m[3] = 0.0;
+        } else img[(size_t)pix * 3 + c] = 0.0;
+        return;
+    }
     const double* src = rad + (size_t)s * n * 3 + c;
     double* m = mom + (size_t)pix * 6 + c;
     float acc = k0 > 0 ? (float)img[(size_t)pix * 3 + c] : 0.0f;
@@ -328,6 +351,17 @@ __global__ void __launch_bounds__(256) k_noise_final(const double* __restrict__ 
 // itself (the frame mcpt_render computes); done < N: the fp64 mean s1 / done, which is not the float fold.  Error: sqrt(se2), 0 for
 // done < 2.  One lane per (owned pixel, channel); other pixels are not touched.  PER_PIXEL (adaptive frames): the pixel's own count
 // cnt[pix] in place of `done`.
+// (one lane per (owned pixel, channel): a pixel whose primary ray missed shows its image -- under an environment, the whole frame's fold)
+__global__ void k_missed_image(const int32_t* __restrict__ pixels, long long n_pixels, const uint8_t* __restrict__ hit, const double* __restrict__ img,
+                               double* __restrict__ est)
+{
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= n_pixels * 3) return;
+    const int pix = pixels ? pixels[gid / 3] : (int)(gid / 3);
+    const size_t i = (size_t)pix * 3 + (int)(gid % 3);
+    if (!hit[pix]) est[i] = img[i];
+}
+
 template <bool PER_PIXEL>
 __global__ void k_progressive_image(const int32_t* __restrict__ pixels, long long n_pixels, const double* __restrict__ img,
                                     const double* __restrict__ mom, int done, const int32_t* __restrict__ cnt, int N, double* __restrict__ est,
@@ -528,27 +562,34 @@ void launch_shade_samples(const DScene& S, unsigned long long seed, const double
 {
     const long long n = (long long)n_slots * spp;
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_shade_samples, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
+    if (env_on(S.env)) hipLaunchKernelGGL(k_shade_samples<true>, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
+    else hipLaunchKernelGGL(k_shade_samples<false>, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
 }
 void launch_sample_radiance(const DScene& S, unsigned long long seed, const double* d_dirs, const int32_t* d_pix, const int32_t* d_k,
                             long long n, double* d_rgb, DCounters* ctr, hipStream_t st)
 {
     if (n <= 0) return;
-    hipLaunchKernelGGL(k_sample_radiance, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
+    if (env_on(S.env)) hipLaunchKernelGGL(k_sample_radiance<true>, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
+    else hipLaunchKernelGGL(k_sample_radiance<false>, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
 }
 void launch_fold_samples(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int spp,
-                         double* d_img, hipStream_t st)
+                         double* d_img, const DEnv& env, const double* d_dirs, hipStream_t st)
 {
     if (n_slots <= 0) return;
-    hipLaunchKernelGGL(k_fold_samples, dim3(blocks_for((long long)n_slots * 3, 256)), dim3(256), 0, st, d_rad, d_pixels, d_hits, first_slot, n_slots, spp, d_img);
+    if (env_on(env)) hipLaunchKernelGGL(k_fold_samples<true>, dim3(blocks_for((long long)n_slots * 3, 256)), dim3(256), 0, st, d_rad, d_pixels, d_hits, first_slot, n_slots, spp, d_img, env, d_dirs);
+    else hipLaunchKernelGGL(k_fold_samples<false>, dim3(blocks_for((long long)n_slots * 3, 256)), dim3(256), 0, st, d_rad, d_pixels, d_hits, first_slot, n_slots, spp, d_img, env, d_dirs);
 }
 
 void launch_fold_progressive(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int n, int k0, int N,
-                             double* d_img, double* d_mom, uint8_t* d_hit, hipStream_t st)
+                             double* d_img, double* d_mom, uint8_t* d_hit, const DEnv& env, const double* d_dirs, hipStream_t st)
 {
     if (n_slots <= 0) return;
-    hipLaunchKernelGGL(k_fold_progressive, dim3(blocks_for((long long)n_slots * 3, 256)), dim3(256), 0, st, d_rad, d_pixels, d_hits, first_slot, n_slots, n, k0, N,
-                       d_img, d_mom, d_hit);
+    if (env_on(env))
+        hipLaunchKernelGGL(k_fold_progressive<true>, dim3(blocks_for((long long)n_slots * 3, 256)), dim3(256), 0, st, d_rad, d_pixels, d_hits, first_slot, n_slots, n,
+                           k0, N, d_img, d_mom, d_hit, env, d_dirs);
+    else
+        hipLaunchKernelGGL(k_fold_progressive<false>, dim3(blocks_for((long long)n_slots * 3, 256)), dim3(256), 0, st, d_rad, d_pixels, d_hits, first_slot, n_slots, n,
+                           k0, N, d_img, d_mom, d_hit, env, d_dirs);
 }
 int noise_ranges(long long n_pixels) { return (int)std::min<long long>(kNoiseRanges, std::max<long long>(1, (n_pixels + 255) / 256)); }
 void launch_noise_reduce(const int32_t* d_pixels, long long n_pixels, const double* d_mom, const uint8_t* d_hit, int done, const int32_t* d_cnt,
@@ -561,12 +602,13 @@ void launch_noise_reduce(const int32_t* d_pixels, long long n_pixels, const doub
     hipLaunchKernelGGL(k_noise_final, dim3(1), dim3(256), 0, st, d_partials, ranges, d_out);
 }
 void launch_progressive_image(const int32_t* d_pixels, long long n_pixels, const double* d_img, const double* d_mom, int done, const int32_t* d_cnt,
-                              int N, double* d_est, double* d_err, hipStream_t st)
+                              int N, double* d_est, double* d_err, const uint8_t* d_missed_hit, hipStream_t st)
 {
     if (n_pixels <= 0) return;
     const dim3 grid(blocks_for(n_pixels * 3, 256));
     if (d_cnt) hipLaunchKernelGGL(k_progressive_image<true>, grid, dim3(256), 0, st, d_pixels, n_pixels, d_img, d_mom, done, d_cnt, N, d_est, d_err);
     else hipLaunchKernelGGL(k_progressive_image<false>, grid, dim3(256), 0, st, d_pixels, n_pixels, d_img, d_mom, done, d_cnt, N, d_est, d_err);
+    if (d_missed_hit && d_est) hipLaunchKernelGGL(k_missed_image, grid, dim3(256), 0, st, d_pixels, n_pixels, d_missed_hit, d_img, d_est);
 }
 int adaptive_blocks(int n) { return (n + 255) / 256; }
 void launch_adaptive_select(const int32_t* d_list, int n, const double* d_mom, const uint8_t* d_hit, int k, int min_spp, double rel2, double abs2,

@@ -23,6 +23,8 @@ struct LaunchCfg {
     int cus = 0;
     unsigned logic_first = 0, logic_rest = 0;       // k_wf_logic<true> / <false>
     int trace_grid = 0, trace_grid_short = 0, finish_grid = 0;   // k_wf_trace (deep / short stack), k_wf_finish
+    unsigned logic_first_env = 0, logic_rest_env = 0;   // ... their instantiations under an environment (fewer waves may be resident)
+    int finish_grid_env = 0;
     int array_grid = 0, primary_grid = 0;           // k_trace_persistent<ArrayRaySource> / <PrimaryRaySource>, deep stack
     int array_grid_short = 0, primary_grid_short = 0;   // ... short stack
     long long trace_block_rays = 2048;              // MCPT_TRACE_BLOCK_RAYS: a block of k_wf_trace is started per this many rays
@@ -47,8 +49,9 @@ void launch_shade_samples(const DScene& S, unsigned long long seed, const double
                           const PrimaryHit* d_hits, int first_slot, int n_slots, int spp, int sample_base, double* d_rad, DCounters* ctr, hipStream_t st);
 void launch_sample_radiance(const DScene& S, unsigned long long seed, const double* d_dirs, const int32_t* d_pix, const int32_t* d_k,
                             long long n, double* d_rgb, DCounters* ctr, hipStream_t st);
+// env (active: env_on): a pixel whose primary ray missed folds Le(d_dirs[pixel]) for each sample
 void launch_fold_samples(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int spp,
-                         double* d_img, hipStream_t st);
+                         double* d_img, const DEnv& env, const double* d_dirs, hipStream_t st);
 // ---- lenses (camera.hip).  d_pos: the W*H image-plane points of the camera (DLens::pos).  d_flags[slot * spp + k] (chunk-local): 1 when
 // the camera ray of that sample hit something.
 void launch_primary_pos(const DCamera& cam, double* d_pos, hipStream_t st);
@@ -59,19 +62,26 @@ void launch_sample_radiance_lens(const DScene& S, const DLens& lens, unsigned lo
                                  double* d_rgb, DCounters* ctr, hipStream_t st);
 // the folds of k_fold_samples / k_fold_progressive for the per-sample route (a camera ray that missed has radiance 0: it adds nothing);
 // progressive: d_hitcnt[pix] += the hits of the pass, d_hit[pix] = d_hitcnt[pix] > 0
+// (env active: a camera ray that missed has radiance Le, and every sample is folded)
 void launch_fold_lens(const double* d_rad, const uint8_t* d_flags, const int32_t* d_pixels, int first_slot, int n_slots, int n, int k0, int N,
-                      double* d_img, double* d_mom, uint8_t* d_hit, int32_t* d_hitcnt, hipStream_t st);
+                      double* d_img, double* d_mom, uint8_t* d_hit, int32_t* d_hitcnt, bool env, hipStream_t st);
+// ---- the environment's test seams (env.hip): rgb[n*3] = Le(dirs[i]); out7[n*7] = direction, pdf, radiance of the block-(nl + 2) draw
+void launch_env_eval(const DEnv& E, const double* d_dirs, long long n, double* d_rgb, hipStream_t st);
+void launch_env_sample(const DEnv& E, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, int depth, int nl, long long n, double* d_out7,
+                       hipStream_t st);
 // progressive frames: fold of samples [k0, k0 + n) of a frame of N into d_img, moments into d_mom ([W*H][2][3]), primary hit flags into d_hit
 void launch_fold_progressive(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int n, int k0, int N,
-                             double* d_img, double* d_mom, uint8_t* d_hit, hipStream_t st);
+                             double* d_img, double* d_mom, uint8_t* d_hit, const DEnv& env, const double* d_dirs, hipStream_t st);
 // frame summary after `done` samples (done >= 2): d_out[0..3] = sum se2, sum mean^2, hit pixels, 0; d_partials holds noise_ranges() x 3 doubles
 constexpr int kNoiseRanges = 1024;
 int noise_ranges(long long n_pixels);
 // d_cnt == null: every pixel holds `done` samples; otherwise pixel p holds d_cnt[p] (adaptive frames)
 void launch_noise_reduce(const int32_t* d_pixels, long long n_pixels, const double* d_mom, const uint8_t* d_hit, int done, const int32_t* d_cnt,
                          double* d_partials, double* d_out, hipStream_t st);
+// d_missed_hit (the per-pixel route under an environment, else null): a pixel with d_missed_hit[pix] == 0 shows d_img -- the whole frame's
+// fold of Le, the same at every count
 void launch_progressive_image(const int32_t* d_pixels, long long n_pixels, const double* d_img, const double* d_mom, int done, const int32_t* d_cnt,
-                              int N, double* d_est, double* d_err, hipStream_t st);
+                              int N, double* d_est, double* d_err, const uint8_t* d_missed_hit, hipStream_t st);
 // adaptive frames: after a pass of k samples over d_list[0..n), d_cnt[p] = k for every listed p, and the pixels that continue go to d_out
 // in list order, their number to *d_total.  d_masks holds 4 * adaptive_blocks(n) words, d_block_counts / d_block_offsets adaptive_blocks(n).
 int adaptive_blocks(int n);

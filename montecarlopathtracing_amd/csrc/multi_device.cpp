@@ -198,6 +198,20 @@ int mcpt_multi_set_lens(mcpt_multi* m, const mcpt_lens* lens)
     return MCPT_OK;
 }
 
+// the same environment on every GPU of the group (each device copies the texels; the first refusal clears it on every device)
+int mcpt_multi_set_environment(mcpt_multi* m, const mcpt_environment* e)
+{
+    if (!m) return mcpt_device_set_environment(nullptr, e);   // the device entry point's checks and refusal of a null handle
+    for (Rank& r : m->ranks) {
+        const int rc = mcpt_device_set_environment(r.dev, e);
+        if (rc) {
+            for (Rank& q : m->ranks) (void)mcpt_device_set_environment(q.dev, nullptr);
+            return rc;
+        }
+    }
+    return MCPT_OK;
+}
+
 int mcpt_multi_create(const mcpt_scene* scene, const int32_t* devices, int32_t num_devices, int32_t build_mode, int32_t gather, mcpt_multi** out)
 {
     if (!scene || !out) return fail(MCPT_ERR_ARG, "null argument");

@@ -61,6 +61,7 @@ struct mcpt_progressive {
     DevBuf<DenoiseGuide> guide;
     DevBuf<DenoisePix> dn_buf[2];      // the denoiser's ping-pong buffers (W*H each), allocated on its first call
     mcpt_lens lens{};                  // the device's lens when the handle was created
+    std::shared_ptr<const EnvData> env;   // ... and its environment (null: none)
     DevBuf<int32_t> hitcnt;            // W*H, under an active lens: the samples so far whose camera ray hit (hit = hitcnt > 0)
 };
 
@@ -89,6 +90,7 @@ static int progressive_create(mcpt_device* d, const mcpt_render_params* p, const
     h->d = d; d->refs.fetch_add(1);
     h->p = *p;
     h->lens = d->lens;
+    h->env = d->env;
     h->n_pixels = int64_t(v.size());
     HIP_TRY(h->pixels.upload(v));
     HIP_TRY(alloc_zeroed(h->img, px * 3 * sizeof(double)));
@@ -154,7 +156,7 @@ int mcpt_progressive_step(mcpt_progressive* h, int32_t n, mcpt_stats* stats)
     if (stats) std::memset(stats, 0, sizeof *stats);
     mcpt_render_params q = h->p;
     q.spp = std::min(n, h->p.spp - h->done);
-    const SampleRange r{h->done, q.spp, h->p.spp, h->mom.get(), h->hit.get(), &h->lens, h->hitcnt.get()};
+    const SampleRange r{h->done, q.spp, h->p.spp, h->mom.get(), h->hit.get(), &h->lens, h->hitcnt.get(), h->env.get()};
     const PixelList L = h->adaptive ? PixelList{h->active[h->cur].get(), h->n_active} : PixelList{h->pixels.get(), h->n_pixels};
     const size_t ev_used0 = d->ev_used;
     int slot_used = -1;
@@ -230,7 +232,10 @@ int mcpt_progressive_image_device(mcpt_progressive* h, double* d_img, double* d_
 {
     if (!h || (!d_img && !d_stderr)) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->d->ordinal));
-    launch_progressive_image(h->pixels.get(), h->n_pixels, h->img.get(), h->mom.get(), h->done, h->cnt.get(), h->p.spp, d_img, d_stderr, static_cast<hipStream_t>(stream));
+    // (the per-pixel route under an environment: a missed pixel's image already is the frame's fold of Le)
+    const bool sky = h->env && env_on(h->env->denv) && !lens_active(h->lens);
+    launch_progressive_image(h->pixels.get(), h->n_pixels, h->img.get(), h->mom.get(), h->done, h->cnt.get(), h->p.spp, d_img, d_stderr,
+                             sky ? h->hit.get() : nullptr, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
     return MCPT_OK;
 }

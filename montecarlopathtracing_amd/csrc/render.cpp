@@ -174,16 +174,18 @@ static int prepare_partition(mcpt_device* d, const mcpt_render_params* p, hipStr
     return MCPT_OK;
 }
 
-static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, int first, int n_slots, double* d_img, bool lensed, hipStream_t st)
+// (S.env active: a missed pixel -- or camera ray -- folds the environment's radiance; d_dirs: the pinhole's primary directions)
+static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, int first, int n_slots, double* d_img, bool lensed, const DScene& S,
+                       const double* d_dirs, hipStream_t st)
 {
-    if (lensed) launch_fold_lens(f.rad.get(), f.cam_hit.get(), L.pixels, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, r.hitcnt, st);
-    else if (r.mom) launch_fold_progressive(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, st);
-    else launch_fold_samples(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, d_img, st);
+    if (lensed) launch_fold_lens(f.rad.get(), f.cam_hit.get(), L.pixels, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, r.hitcnt, env_on(S.env), st);
+    else if (r.mom) launch_fold_progressive(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, S.env, d_dirs, st);
+    else launch_fold_samples(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, d_img, S.env, d_dirs, st);
 }
 
 // megakernel path: one lane per camera sample, the whole path in one kernel (kept for A/B runs and as a second
 // implementation the wavefront path is checked against)
-static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, const mcpt_render_params* p,
+static int render_megakernel(mcpt_device* d, const DScene& S, mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, const mcpt_render_params* p,
                              double* d_img, bool timed, const DLens* lens, hipStream_t st, double& ms_trace, int& launches)
 {
     const int64_t npx = L.n;
@@ -196,8 +198,8 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const Sa
     for (int64_t first = 0; first < npx; first += chunk) {
         const int n_slots = int(std::min<int64_t>(chunk, npx - first));
         if (timed) HIP_TRY(hipEventRecord(d->ev[2].get(), st));
-        if (lens) launch_shade_samples_lens(d->ds, *lens, p->seed, L.pixels, int(first), n_slots, spp, r.k0, f.rad.get(), f.cam_hit.get(), f.ctr.get(), st);
-        else launch_shade_samples(d->ds, p->seed, d->dirs.get(), L.pixels, f.hits.get(), int(first), n_slots, spp, r.k0, f.rad.get(), f.ctr.get(), st);
+        if (lens) launch_shade_samples_lens(S, *lens, p->seed, L.pixels, int(first), n_slots, spp, r.k0, f.rad.get(), f.cam_hit.get(), f.ctr.get(), st);
+        else launch_shade_samples(S, p->seed, d->dirs.get(), L.pixels, f.hits.get(), int(first), n_slots, spp, r.k0, f.rad.get(), f.ctr.get(), st);
         HIP_TRY(hipGetLastError());
         if (timed) {
             HIP_TRY(hipEventRecord(d->ev[3].get(), st));
@@ -207,7 +209,7 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const Sa
             ms_trace += ms;
         }
         launches++;
-        fold_range(f, r, L, int(first), n_slots, d_img, lens != nullptr, st);
+        fold_range(f, r, L, int(first), n_slots, d_img, lens != nullptr, S, d->dirs.get(), st);
         HIP_TRY(hipGetLastError());
     }
     return MCPT_OK;
@@ -218,12 +220,13 @@ static int render_megakernel(mcpt_device* d, mcpt_device::FrameSlot& f, const Sa
 // and left in d->ev_pool for mcpt_device_collect_stats -- the frame ends without the host waiting for it.
 // lens (non-null: an active lens): the per-sample route -- per chunk a camera pass (the camera as vertex -1 of every sample) and a trace
 // launch of its rays, then the logic passes from depth 0 on, every vertex in the path state (WfArgs::hits == null)
-static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, const mcpt_render_params* p,
+static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, const mcpt_render_params* p,
                             double* d_img, bool timed, bool keep, const DLens* lens, hipStream_t st, double& ms_trace, int& launches)
 {
     const int64_t npx = L.n;
     const int spp = r.n;
-    const int nl = d->ds.num_lights;
+    // WfArgs::nl: shadow planes -- one per light and one for an active environment (its draws use Philox block num_lights + 2)
+    const int nl = S.num_lights + (env_on(S.env) ? 1 : 0);
     const bool fast = d->trace_mode == MCPT_TRACE_FAST;
     const size_t bpp = wf_bytes_per_path(nl);
     // chunk: as many pixels as the workspace budget holds paths for (every pixel may hit)
@@ -262,6 +265,13 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
     WfArgs a{};
     WfState A, B;
     if (!wf_carve(f.wf_ws.get(), f.wf_ws.bytes(), cap, nl, A, B, a.rays)) return fail(MCPT_ERR_NOMEM, "wavefront workspace too small");
+    // the pool form of the finishing pass keeps nl + 1 rays per path: its area was sized for the scene's lights when the device was made
+    char* path_area = f.path_area.get();
+    if (nl != S.num_lights && d->cfg.finish_pool) {
+        const size_t need = finish_pool_bytes(d->cfg.cus, nl);
+        if (!need) path_area = nullptr;
+        else { HIP_TRY(f.path_area.grow_bytes(need)); path_area = f.path_area.get(); }
+    }
     a.cap = cap; a.nl = nl; a.spp = spp; a.sample_base = r.k0; a.seed = p->seed; a.pixels = L.pixels; a.hit_slots = f.hit_slots.get(); a.surf = f.surf.get(); a.alive_base = f.alive_base.get();
     a.hits = f.hits.get(); a.dirs = d->dirs.get(); a.rad = f.rad.get(); a.counts = f.wf_counts.get(); a.ctr = f.ctr.get(); a.tris = d->tris.get();
     a.materials = d->materials.get(); a.queue = fast ? f.queue.get() : nullptr;
@@ -288,7 +298,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
             ac.nl = 0;          // the trace launch sees the bounce slot only (l == nl): no empty shadow-ray slots to walk past
             EventPair* pr = nullptr;
             if (timed || keep) { if ((rc = next_pair(d->ev_pool, d->ev_used, pr))) return rc; HIP_TRY(hipEventRecord(pr->first.get(), st)); }
-            launch_wf_trace(d->ds, ac, n_upper, fast, f.queue.get(), f.slow_list.get(), d->slow_cap, st, d->cfg);
+            launch_wf_trace(S, ac, n_upper, fast, f.queue.get(), f.slow_list.get(), d->slow_cap, st, d->cfg);
             HIP_TRY(hipGetLastError());
             if (timed || keep) HIP_TRY(hipEventRecord(pr->second.get(), st));
             launches++;
@@ -296,7 +306,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
         } else {
             launch_hit_slots(f.hits.get(), int(first), n_slots, f.hit_slots.get(), &f.wf_counts[0].n_next, st);
             HIP_TRY(hipGetLastError());
-            launch_primary_surface(d->ds, a, f.surf.get(), f.alive_base.get(), &f.wf_counts[0].pad[2], n_slots, st);      // what the samples of a pixel share at their first vertex
+            launch_primary_surface(S, a, f.surf.get(), f.alive_base.get(), &f.wf_counts[0].pad[2], n_slots, st);      // what the samples of a pixel share at their first vertex
             HIP_TRY(hipGetLastError());
         }
         for (int depth = 0; depth < MCPT_MAX_DEPTH && n_upper > 0; depth++) {
@@ -307,9 +317,9 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
             // the per-sample route's depth 0 resolves the camera rays: nothing went to the finishing kernel before it, and its pool form
             // (which reads a pixel's PrimaryHit at depth 0) does not adopt its paths
             const bool cam0 = lens && depth == 0;
-            char* const area = cam0 ? nullptr : f.path_area.get();
-            if (cam0) { WfArgs al = a; al.finish_below = 0u; launch_wf_logic(d->ds, al, n_launch, false, st, d->cfg); }
-            else launch_wf_logic(d->ds, a, n_launch, depth == 0, st, d->cfg);
+            char* const area = cam0 ? nullptr : path_area;
+            if (cam0) { WfArgs al = a; al.finish_below = 0u; launch_wf_logic(S, al, n_launch, false, st, d->cfg); }
+            else launch_wf_logic(S, a, n_launch, depth == 0, st, d->cfg);
             HIP_TRY(hipGetLastError());
             // The host looks at this pass's count every few iterations, and at every iteration once the hand-over to the finishing
             // kernel is near.  The look waits for this logic pass only (event + side stream): when it finds the hand-over, the
@@ -322,7 +332,7 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
                 HIP_TRY(hipStreamSynchronize(d->look_stream.get()));
                 const unsigned int n_now = d->h_look[0];
                 if (n_now <= a.finish_below) {
-                    if (n_now > 0) { launch_wf_finish(d->ds, a, (long long)n_now, st, d->cfg, area, f.slow_list.get(), d->slow_cap); HIP_TRY(hipGetLastError()); }
+                    if (n_now > 0) { launch_wf_finish(S, a, (long long)n_now, st, d->cfg, area, f.slow_list.get(), d->slow_cap); HIP_TRY(hipGetLastError()); }
                     n_upper = 0;
                     break;
                 }
@@ -330,13 +340,13 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
                 n_grid = double(n_now);
             } else if (a.finish_below) {
                 // few paths left (decided on the device from this pass's count): one lane per path runs them to the end
-                launch_wf_finish(d->ds, a, std::min<long long>(n_launch, (long long)a.finish_below), st, d->cfg, area, f.slow_list.get(), d->slow_cap);
+                launch_wf_finish(S, a, std::min<long long>(n_launch, (long long)a.finish_below), st, d->cfg, area, f.slow_list.get(), d->slow_cap);
                 HIP_TRY(hipGetLastError());
             }
             const long long n_trace = look ? (long long)n_grid : n_launch;
             EventPair* pr = nullptr;
             if (timed || keep) { if ((rc = next_pair(d->ev_pool, d->ev_used, pr))) return rc; HIP_TRY(hipEventRecord(pr->first.get(), st)); }
-            launch_wf_trace(d->ds, a, n_trace, fast, f.queue.get(), f.slow_list.get(), d->slow_cap, st, d->cfg);
+            launch_wf_trace(S, a, n_trace, fast, f.queue.get(), f.slow_list.get(), d->slow_cap, st, d->cfg);
             HIP_TRY(hipGetLastError());
             if (timed || keep) HIP_TRY(hipEventRecord(pr->second.get(), st));
             launches++;
@@ -347,10 +357,10 @@ static int render_wavefront(mcpt_device* d, mcpt_device::FrameSlot& f, const Sam
         if (n_upper > 0) {
             a.depth = MCPT_MAX_DEPTH;
             a.counts_in = &f.wf_counts[MCPT_MAX_DEPTH]; a.count_mul = 1u; a.counts = &f.wf_counts[MCPT_MAX_DEPTH + 1];
-            launch_wf_logic(d->ds, a, n_upper, false, st, d->cfg);
+            launch_wf_logic(S, a, n_upper, false, st, d->cfg);
             HIP_TRY(hipGetLastError());
         }
-        fold_range(f, r, L, int(first), n_slots, d_img, lens != nullptr, st);
+        fold_range(f, r, L, int(first), n_slots, d_img, lens != nullptr, S, d->dirs.get(), st);
         HIP_TRY(hipGetLastError());
     }
     if (timed && !keep) {
@@ -385,6 +395,8 @@ int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelList& L,
     const bool lensed = r.lens && lens_active(*r.lens);
     if (lensed && (rc = ensure_pos(d, st))) return rc;
     const DLens dl = lensed ? lens_for(d, *r.lens) : DLens{};
+    DScene S = d->ds;                                   // the scene with the environment of the call
+    S.env = r.env ? r.env->denv : DEnv{};
     const int64_t npx = L.n;
     if (npx == 0) return MCPT_OK;
     const uint64_t primary_rays = uint64_t(npx) * (lensed ? uint64_t(r.n) : 1u);
@@ -402,8 +414,8 @@ int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelList& L,
     }
     double ms_trace = 0;
     int launches = 0;
-    if (p->flags & MCPT_RENDER_MEGAKERNEL) rc = render_megakernel(d, f, r, L, p, d_img, timed, lensed ? &dl : nullptr, st, ms_trace, launches);
-    else rc = render_wavefront(d, f, r, L, p, d_img, timed, keep, lensed ? &dl : nullptr, st, ms_trace, launches);
+    if (p->flags & MCPT_RENDER_MEGAKERNEL) rc = render_megakernel(d, S, f, r, L, p, d_img, timed, lensed ? &dl : nullptr, st, ms_trace, launches);
+    else rc = render_wavefront(d, S, f, r, L, p, d_img, timed, keep, lensed ? &dl : nullptr, st, ms_trace, launches);
     if (rc) return rc;
     if (keep) {
         HIP_TRY(hipEventRecord(fe->second.get(), st));
@@ -464,7 +476,7 @@ int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_im
     // a frame that fails half-way must not leave half-recorded event pairs behind: mcpt_device_collect_stats would trip over them
     const size_t ev_used0 = d->ev_used, frame_ev_used0 = d->frame_ev_used;
     int slot_used = -1;
-    const SampleRange whole{0, p->spp, p->spp, nullptr, nullptr, &d->lens, nullptr};
+    const SampleRange whole{0, p->spp, p->spp, nullptr, nullptr, &d->lens, nullptr, d->env.get()};
     int rc = prepare_partition(d, p, static_cast<hipStream_t>(stream));
     if (rc == MCPT_OK) rc = render_device_impl(d, whole, PixelList{d->pixels.get(), d->n_pixels}, p, d_img, stats, static_cast<hipStream_t>(stream), slot_used);
     if (rc != MCPT_OK) {

@@ -110,15 +110,22 @@ static uint64_t scene_tag(const Scene& s)
 
 // The identity of a frame rendered under a lens: the scene's tag with the lens mixed in -- only when the lens is active, so that a pinhole
 // frame keeps its tag (and existing checkpoint files stay valid) and the two never resume from each other's files.
-static uint64_t frame_tag(const Scene& s, const mcpt_lens* l)
+// An active environment (env: the device's, null or inactive: none) is mixed in the same way, after the lens: its size, scale and texels.
+static uint64_t frame_tag(const Scene& s, const mcpt_lens* l, const EnvData* env)
 {
     uint64_t h = scene_tag(s);
-    if (!l || !lens_active(*l)) return h;
     auto mix = [&](const void* p, size_t n) { const unsigned char* b = static_cast<const unsigned char*>(p); for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; } };
-    const char tag[] = "lens";
-    const int64_t flags = l->flags;
-    const double focus = l->focus_distance > 0.0 ? l->focus_distance : 0.0;     // (every F <= 0 is the same lens)
-    mix(tag, 4); mix(&flags, sizeof flags); mix(&l->aperture, sizeof(double)); mix(&focus, sizeof focus);
+    if (l && lens_active(*l)) {
+        const char tag[] = "lens";
+        const int64_t flags = l->flags;
+        const double focus = l->focus_distance > 0.0 ? l->focus_distance : 0.0;     // (every F <= 0 is the same lens)
+        mix(tag, 4); mix(&flags, sizeof flags); mix(&l->aperture, sizeof(double)); mix(&focus, sizeof focus);
+    }
+    if (env && env->Z > 0.0) {
+        const char tag[] = "envm";
+        const int64_t wh[2] = {env->W, env->H};
+        mix(tag, 4); mix(wh, sizeof wh); mix(&env->scale, sizeof(double)); mix(env->rgb.data(), env->rgb.size() * sizeof(float));
+    }
     return h;
 }
 
@@ -247,8 +254,25 @@ int mcpt_render_scene_opts(const char* path, const char* filename, int32_t spp, 
 int mcpt_render_scene_lens(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
                            const mcpt_lens* lens, mcpt_stats* stats)
 {
+    return mcpt_render_scene_env(path, filename, spp, opt, opt_bytes, lens, nullptr, 1.0, stats);
+}
+
+int mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
+                          const mcpt_lens* lens, const char* environment_pfm, double environment_scale, mcpt_stats* stats)
+{
     if (!path || !filename || spp <= 0 || opt_bytes < 0 || (opt_bytes > 0 && !opt)) return fail(MCPT_ERR_ARG, "bad argument");
     if (int lrc = lens_check(lens)) return lrc;
+    // the environment map is read and checked before anything else is read or written
+    std::vector<float> env_rgb;
+    mcpt_environment env{};
+    if (environment_pfm) {
+        int32_t ew = 0, eh = 0;
+        if (int erc = mcpt_read_pfm(environment_pfm, &ew, &eh, nullptr, 0)) return erc;
+        env_rgb.resize(size_t(ew) * size_t(eh) * 3);
+        if (int erc = mcpt_read_pfm(environment_pfm, &ew, &eh, env_rgb.data(), int64_t(env_rgb.size()))) return erc;
+        env.width = ew; env.height = eh; env.rgb = env_rgb.data(); env.scale = environment_scale;
+        if (int erc = env_check(&env)) return erc;
+    }
     mcpt_render_scene_options o{};
     if (opt) std::memcpy(&o, opt, std::min<size_t>(size_t(opt_bytes), sizeof o));
     const bool talk = !o.quiet;
@@ -282,6 +306,7 @@ int mcpt_render_scene_lens(const char* path, const char* filename, int32_t spp, 
     if (many) rc = mcpt_multi_create(sc, o.num_devices > 0 ? o.devices : nullptr, o.num_devices > 0 ? o.num_devices : 0, MCPT_BUILD_HOST, o.gather, &multi);
     else rc = mcpt_device_create(sc, o.device, &dev);
     if (rc == MCPT_OK && lens) rc = many ? mcpt_multi_set_lens(multi, lens) : mcpt_device_set_lens(dev, lens);
+    if (rc == MCPT_OK && environment_pfm) rc = many ? mcpt_multi_set_environment(multi, &env) : mcpt_device_set_environment(dev, &env);
     if (rc) { if (dev) mcpt_device_free(dev); if (multi) mcpt_multi_free(multi); mcpt_scene_free(sc); return rc; }
     if (talk && many) std::printf("rendering on %d GPUs\n", mcpt_multi_num_devices(multi));
     if (many && o.checkpoint) {
@@ -309,7 +334,7 @@ int mcpt_render_scene_lens(const char* path, const char* filename, int32_t spp, 
         // the frame in `parts` tile partitions, saved after each; partitions a matching checkpoint already holds are skipped
         const int parts = o.checkpoint_parts > 0 ? o.checkpoint_parts : 8;
         std::vector<uint8_t> done(size_t(parts), 0);
-        const uint64_t tag = frame_tag(s, lens);
+        const uint64_t tag = frame_tag(s, lens, dev->env.get());
         std::string cerr;
         const int lrc = checkpoint_load(o.checkpoint, img.data(), s.width, s.height, spp, o.seed, tag, parts, done.data(), cerr);
         if (lrc != MCPT_OK) { std::fill(img.begin(), img.end(), 0.0); std::fill(done.begin(), done.end(), uint8_t(0)); }

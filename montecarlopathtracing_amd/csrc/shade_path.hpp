@@ -4,6 +4,7 @@
 #include "shade_common.hpp"
 #include "trace_fast.hpp"
 #include "kernels.hpp"
+#include "env.hpp"
 
 namespace mcpt {
 
@@ -11,8 +12,10 @@ namespace mcpt {
 // (one bounce per vertex), so L = sum_d T_d * Ldir_d with T_{d+1} = T_d * w_d / 0.6.
 // Resumable: starts at vertex `depth0` with throughput T, gathered radiance L, arrival direction dir and arrival ray type
 // in_type (depth0 = 0, T = 1, L = 0, in_type = TRANSMISSION for a fresh camera sample).  FAST selects the walk
-// (trace_lane_fast with this lane's LDS stack, or the reference-shaped trace_closest); both give the same hits.
-template <bool FAST>
+// (trace_lane_fast with this lane's LDS stack, or the reference-shaped trace_closest); both give the same hits.  ENV: S.env is active
+// (env.hpp) -- one more shadow ray per vertex after the lights', and a SPECULAR / TRANSMISSION bounce ray that leaves the scene adds
+// T' * Le; without it the code is what it was before environments existed.
+template <bool FAST, bool ENV = false>
 __device__ void shade_path_from(const DScene& S, const RngKey& key, uint32_t depth0, V3 T, V3 L, V3 dir, int in_type, Hit hit, double out[3],
                                 LaneStats& ls, int* lds_stack, int stride)
 {
@@ -90,6 +93,18 @@ __device__ void shade_path_from(const DScene& S, const RngKey& key, uint32_t dep
                 }
             }
         }
+        if constexpr (ENV) {                                                    // the environment: Philox block nl + 2
+            V3 direction, c;
+            if (env_light_sample(S.env, key, depth, nl, pn, kd, direction, c) != -2) {
+                Ray rl; rl.o = hit.p + direction * 0.01; rl.d = direction;
+                Hit inter;
+                const bool vis = !trace(rl, inter);
+                ls.shadow++;
+                L_dir.x += vis ? c.x : c.x * 0.0;
+                L_dir.y += vis ? c.y : c.y * 0.0;
+                L_dir.z += vis ? c.z : c.z * 0.0;
+            }
+        }
         L = L + mk(T.x * L_dir.x, T.y * L_dir.y, T.z * L_dir.z);
 
         // indirect illumination, :234-263
@@ -134,9 +149,16 @@ __device__ void shade_path_from(const DScene& S, const RngKey& key, uint32_t dep
         }
         Hit next;
         ls.bounce++;
-        if (!trace(nr, next)) break;
-        const V3 wgt = type == RT_DIFFUSE ? kd : (type == RT_SPECULAR ? ks : mk(1, 1, 1));
-        T = mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR);
+        if constexpr (ENV) {
+            const V3 wgt = type == RT_DIFFUSE ? kd : (type == RT_SPECULAR ? ks : mk(1, 1, 1));
+            const V3 Tn = mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR);
+            if (!trace(nr, next)) { L = env_escape(S.env, L, Tn, type, nr.d); break; }
+            T = Tn;
+        } else {
+            if (!trace(nr, next)) break;
+            const V3 wgt = type == RT_DIFFUSE ? kd : (type == RT_SPECULAR ? ks : mk(1, 1, 1));
+            T = mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR);
+        }
         hit = next; dir = neg(nr.d); in_type = type;
     }
     ls.nodes += w.nodes; ls.tris += w.tris;
@@ -144,9 +166,17 @@ __device__ void shade_path_from(const DScene& S, const RngKey& key, uint32_t dep
 }
 
 // a fresh camera sample through the reference-shaped walk (megakernel pipeline)
+template <bool ENV = false>
 __device__ __forceinline__ void shade_path(const DScene& S, const RngKey& key, V3 view_dir, Hit hit, double out[3], LaneStats& ls)
 {
-    shade_path_from<false>(S, key, 0u, mk(1, 1, 1), mk(0, 0, 0), neg(view_dir), RT_TRANSMISSION, hit, out, ls, nullptr, 0);
+    shade_path_from<false, ENV>(S, key, 0u, mk(1, 1, 1), mk(0, 0, 0), neg(view_dir), RT_TRANSMISSION, hit, out, ls, nullptr, 0);
+}
+
+// a camera ray that left the scene: Le of its direction, unweighted (as an emitter at depth 0)
+__device__ __forceinline__ void env_camera_miss(const DScene& S, const V3& d, double out[3])
+{
+    const V3 le = env_eval(S.env, d);
+    out[0] = le.x; out[1] = le.y; out[2] = le.z;
 }
 
 }  // namespace mcpt

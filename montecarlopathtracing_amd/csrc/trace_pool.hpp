@@ -34,6 +34,7 @@
 // SHADE), and every path advances at its own pace: the one-lane-per-path finishing kernel this replaces ran 64 paths in lock-step, a
 // step as long as its slowest walk.
 #pragma once
+#include "env.hpp"
 #include "trace_persistent.hpp"
 #include "vertex.hpp"
 
@@ -603,6 +604,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 // (vertex.hpp), operation for operation; a path's record lives in this block's part of a global area, [field][path slot][lane].
                 const WfArgs& a = pp.a;
                 const int nl = pp.nl;
+                const int nlights = PP::kEnv ? nl - 1 : nl;              // (nl: shadow planes; an environment's is the last)
                 const bool folded = nl == 1;                             // see k_wf_logic
                 const long long cap = a.cap;
                 const int s0 = k * R;
@@ -649,6 +651,10 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                         const double t = dot(v1 - ro, n) / dot(n, bd);
                         p = ro + bd * t; dir = neg(bd); in_type = bt & 7; depth++; leaf = hl;
                         at_vertex = true;
+                    } else if (PP::kEnv && bt >= 0) {                       // the bounce ray left the scene
+                        const V3 Tn = (mode == P_ADOPTED && folded) ? T : [&] { const V3 wgt = ldp(RD_W); return mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR); }();
+                        const PoolOzDx b1 = pool_ld16(&L.ozdx[bidx]); const PoolDyz b2 = pool_ld16(&L.dyz[bidx]);
+                        Lr = env_escape(S.env, Lr, Tn, bt, mk(b1.dx, b2.dy, b2.dz));
                     }
                 }
                 bool ended = have && mode != P_FREE && !at_vertex;       // no bounce ray, or it left the scene
@@ -690,15 +696,21 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                     const int slot = a.first_slot + id / a.spp;
                     key.pixel = (uint32_t)(a.pixels ? a.pixels[slot] : slot); key.sample = (uint32_t)(a.sample_base + id % a.spp);
                     int sample_mat = -1;
-                    for (int l = 0; l < nl; l++) {
+                    for (int l = 0; l < nlights; l++) {
                         V3 direction, cc;
                         const int expect = light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, cc);
                         ri[(size_t)(RI_EXPECT + l) * plane] = expect;
                         if (expect != -2) { stp(RD_C + 3 * l, cc); emit(s0 + l, p + direction * 0.01, direction); n_shadow++; }
                         else n_skipped++;
                     }
+                    if constexpr (PP::kEnv) {
+                        V3 direction, cc;
+                        const int expect = env_light_sample(S.env, key, depth, (uint32_t)nlights, pn, kd, direction, cc);
+                        ri[(size_t)(RI_EXPECT + nlights) * plane] = expect;
+                        if (expect != -2) { stp(RD_C + 3 * nlights, cc); emit(s0 + nlights, p + direction * 0.01, direction); n_shadow++; }
+                    }
                     V3 nd = mk(0, 0, 0), wgt = mk(1, 1, 1);
-                    const int bt = bounce_sample(key, depth, nl, m, dir, pn, kd, nd, wgt);
+                    const int bt = bounce_sample(key, depth, nlights, m, dir, pn, kd, nd, wgt);
                     ri[RI_BT * plane] = bt;
                     if (bt >= 0) { stp(RD_W, wgt); emit(s0 + nl, (bt & MCPT_BT_NO_OFFSET) ? p : p + nd * 0.01, nd); n_bounce++; }
                     ri[RI_DEPTH * plane] = (int)depth;

@@ -9,6 +9,7 @@
 
 #include "accel_build.hpp"
 #include "dev_common.hpp"
+#include "env.hpp"
 #include "shade_common.hpp"
 #include "trace_persistent.hpp"
 #include "trace_pool.hpp"
@@ -51,13 +52,15 @@ __device__ __forceinline__ void sstc(double* __restrict__ a, long long cap, long
 // What is known goes out at once and the bounce is sampled before the lights (every uniform has its own counter: the order of
 // evaluation is free): L, p and the sample id are stored before anything is computed, the incoming direction dies with
 // bounce_sample -- the later passes' values that are alive at the same time, and with them the registers the compiler had to
-// park in scratch memory (39 at 4 waves per SIMD), are what this order is about.
-template <bool FIRST>
+// park in scratch memory (39 at 4 waves per SIMD), are what this order is about.  ENV: an active environment, shadow plane nl - 1 after
+// the scene's nl - 1 lights (WfArgs::nl counts planes; the Philox block base is the lights' count).
+template <bool FIRST, bool ENV>
 __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a, long long j, int id, int leaf, const V3& p, const V3& dir, const V3& T, const V3& L,
                                                 int mat_first, int pix_first, const V3& pn_first, const V3& kd_first, LaneStats& ls)
 {
     const long long cap = a.cap;
     const int nl = a.nl;
+    const int nlights = ENV ? nl - 1 : nl;
     const bool folded = nl == 1;
     const uint32_t depth = (uint32_t)a.depth;
     sst(a.out.id + j, id);
@@ -74,7 +77,7 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
 
     {
         V3 nd = mk(0, 0, 0), wgt = mk(1, 1, 1);
-        const int btype = bounce_sample(key, depth, nl, m, dir, pn, kd, nd, wgt);
+        const int btype = bounce_sample(key, depth, nlights, m, dir, pn, kd, nd, wgt);
         if (btype >= 0) { sstc(a.out.bdir, cap, j, nd); ls.bounce++; }
         sst(a.out.btype + j, btype);
         if (folded) sstc(a.out.T, cap, j, mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR));
@@ -82,7 +85,7 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
     }
 
     int sample_mat = -1;
-    for (int l = 0; l < nl; l++) {
+    for (int l = 0; l < nlights; l++) {
         V3 direction, c;
         const int expect = light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, c);
         if (expect != -2) {
@@ -91,6 +94,16 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
             ls.shadow++;
         } else ls.skipped++;
         sst(a.out.expect + ((long long)l * cap + j), expect);
+    }
+    if constexpr (ENV) {                                                       // the environment's plane: expect -1 (the ray must leave)
+        V3 direction, c;
+        const int expect = env_light_sample(S.env, key, depth, (uint32_t)nlights, pn, kd, direction, c);
+        if (expect != -2) {
+            sstc(a.out.c + (long long)nlights * 3 * cap, cap, j, folded ? mk(T.x * c.x, T.y * c.y, T.z * c.z) : c);
+            sstc(a.rays.d + (long long)nlights * 3 * cap, cap, j, direction);
+            ls.shadow++;
+        }
+        sst(a.out.expect + ((long long)nlights * cap + j), expect);
     }
 }
 
@@ -112,7 +125,9 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
 // block-wide prefix), one per shade round (ring and output base visible); a block's output positions are one atomic per shade round.
 // Ring slots are written after the barrier of a resolve round, which every wave reaches only after its reads of the shade round
 // before: no slot is overwritten while it is read.
-template <bool FIRST>
+//
+// ENV: an active environment (wf_shade_vertex's last shadow plane; a bounce ray that left the scene adds T' * Le, a camera ray Le).
+template <bool FIRST, bool ENV>
 __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOGIC_WAVES) k_wf_logic(DScene S, WfArgs a)
 {
     const long long n_prev = (long long)a.counts_in->n_next * a.count_mul;
@@ -169,7 +184,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 continue;
             }
             MCPT_LSTAMP(0)
-            wf_shade_vertex<true>(S, a, j, id, leaf, p, dir, mk(1, 1, 1), mk(0, 0, 0), mat_first, pix_first, pn_first, kd_first, ls);
+            wf_shade_vertex<true, ENV>(S, a, j, id, leaf, p, dir, mk(1, 1, 1), mk(0, 0, 0), mat_first, pix_first, pn_first, kd_first, ls);
             MCPT_LSTAMP(2)
         }
     } else {
@@ -241,6 +256,15 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                                 }
                             } else alive[u] = true;
                         }
+                        if (ENV && bt[u] >= 0 && hl[u] < 0) {                           // the bounce ray left the scene
+                            const V3 bd = sldc(a.in.bdir, cap, pos[u]);
+                            if (depth == 0) L[u] = env_eval(S.env, bd);                 // a camera ray (per-sample route): unweighted
+                            else {
+                                const V3 Tn = folded ? sldc(a.in.T, cap, pos[u])
+                                                     : mk(T[u].x * wgt[u].x * MCPT_INV_P_RR, T[u].y * wgt[u].y * MCPT_INV_P_RR, T[u].z * wgt[u].z * MCPT_INV_P_RR);
+                                L[u] = env_escape(S.env, L[u], Tn, bt[u], bd);
+                            }
+                        }
                         if (depth == 0 && a.cam_hit) a.cam_hit[id[u]] = hl[u] >= 0 ? 1 : 0;
                         if (!alive[u]) { sst(a.rad + (size_t)id[u] * 3, L[u].x); sst(a.rad + (size_t)id[u] * 3 + 1, L[u].y); sst(a.rad + (size_t)id[u] * 3 + 2, L[u].z); }
                     }
@@ -304,7 +328,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 const V3 v1 = ld3(tr->v1), n = ld3(tr->n);
                 const double t = dot(v1 - ro, n) / dot(n, bd);
                 const V3 p = ro + bd * t;
-                wf_shade_vertex<false>(S, a, j, id, leaf, p, neg(bd), T, L, 0, 0, mk(0, 0, 0), mk(0, 0, 0), ls);
+                wf_shade_vertex<false, ENV>(S, a, j, id, leaf, p, neg(bd), T, L, 0, 0, mk(0, 0, 0), mk(0, 0, 0), ls);
             }
             head = (head + m_round) & (kRing - 1u);
             count -= m_round;
@@ -324,7 +348,8 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
 // resolve, trace the bounce ray, shade the next vertex (vertex.hpp: the arithmetic of k_wf_logic).  Lanes whose path has ended
 // take the next unclaimed path (one atomic per refill on the pass's own count slot), so a wave is as long as its share of
 // the work, not as its longest path.  A lane that has just adopted a path finds the rays of its first step in the wavefront
-// state instead of computing them; from the second step on everything lives in registers.
+// state instead of computing them; from the second step on everything lives in registers.  ENV: as k_wf_logic.
+template <bool ENV>
 __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, WfArgs a)
 {
     __shared__ int lds_stack[MCPT_FAST_STACK * 256];
@@ -332,6 +357,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
     if (n == 0 || n > (long long)a.finish_below) return;               // nothing left, or still wavefront work
     const long long cap = a.cap;
     const int nl = a.nl;
+    const int nlights = ENV ? nl - 1 : nl;                             // (nl: shadow planes)
     const bool folded = nl == 1;                                       // see k_wf_logic
     const int lane = threadIdx.x & 63;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -407,8 +433,13 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
             V3 c = mk(0, 0, 0);
             Ray r; r.o = p; r.d = mk(1, 1, 1);
             if (mode == M_VERTEX && !ended) {
-                expect = light_sample(S, key, depth, l, p, pn, kd, sample_mat, r.d, c);
-                if (expect != -2) ls.shadow++; else ls.skipped++;
+                if (ENV && l == nlights) {
+                    expect = env_light_sample(S.env, key, depth, (uint32_t)nlights, pn, kd, r.d, c);
+                    if (expect != -2) ls.shadow++;
+                } else {
+                    expect = light_sample(S, key, depth, l, p, pn, kd, sample_mat, r.d, c);
+                    if (expect != -2) ls.shadow++; else ls.skipped++;
+                }
             } else if (mode == M_ADOPTED) {
                 expect = a.out.expect[(long long)l * cap + j];
                 if (expect != -2) { c = ldc(a.out.c + (long long)l * 3 * cap, cap, j); r.d = ldc(a.rays.d + (long long)l * 3 * cap, cap, j); }
@@ -428,7 +459,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
         V3 wgt = mk(1, 1, 1);
         Ray br; br.o = p; br.d = mk(1, 1, 1);
         if (mode == M_VERTEX && !ended) {
-            bt = bounce_sample(key, depth, nl, m, dir, pn, kd, br.d, wgt);
+            bt = bounce_sample(key, depth, nlights, m, dir, pn, kd, br.d, wgt);
             if (bt >= 0) ls.bounce++;
         } else if (mode == M_ADOPTED) {
             bt = a.out.btype[j];
@@ -485,6 +516,9 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
             if (!(mode == M_ADOPTED && folded)) T = mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR);
             leaf = b_hit.leaf; p = b_hit.p; dir = neg(br.d); in_type = bt & 7; depth++;
             goes_on = true;
+        } else if (ENV && bt >= 0 && mode != M_IDLE) {                   // the bounce ray left the scene
+            const V3 Tn = (mode == M_ADOPTED && folded) ? T : mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR);
+            L = env_escape(S.env, L, Tn, bt, br.d);
         }
         if (mode != M_IDLE) {
             if (goes_on) mode = M_VERTEX;
@@ -510,8 +544,10 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
 #ifndef MCPT_POOL_NPC
 #define MCPT_POOL_NPC (MCPT_POOL_KT / 2)           /* path slots per lane the record planes are laid out for (one light: KT / 2 paths) */
 #endif
+template <bool ENV>
 struct WfPaths {
     static constexpr bool kPaths = true;
+    static constexpr bool kEnv = ENV;           // an active environment: the last of the nl shadow planes (see k_wf_logic)
     WfArgs a;
     long long n;                // paths handed over (positions 0 .. n-1 of the wavefront state a.out)
     int nl, npc;
@@ -532,21 +568,21 @@ size_t finish_pool_bytes(int cus, int nl)
     return blocks * (size_t(9 + 3 * nl) * plane * sizeof(double) + size_t(3 + nl) * plane * sizeof(int) + size_t(MCPT_POOL_WAVES) * 64 * MCPT_FAST_STACK * sizeof(int));
 }
 
-template <int NW, int KT, int SCAP>
+template <int NW, int KT, int SCAP, bool ENV>
 __global__ void __launch_bounds__(NW * 64, 1) k_wf_finish_pool(DScene S, WfArgs a, char* area, int* spill)
 {
     const long long n = a.counts->n_next;
     if (n == 0 || n > (long long)a.finish_below) return;               // nothing left, or still wavefront work
     __shared__ PoolLds<NW, KT, SCAP> L;
     const size_t blocks = gridDim.x, plane = size_t(MCPT_POOL_NPC) * 64;
-    WfPaths pp;
+    WfPaths<ENV> pp;
     pp.a = a; pp.n = n; pp.nl = a.nl; pp.npc = MCPT_POOL_NPC; pp.inv_r = 1.0f / (float)(a.nl + 1);
     pp.recd = reinterpret_cast<double*>(area);
     pp.reci = reinterpret_cast<int*>(pp.recd + blocks * size_t(9 + 3 * a.nl) * plane);
     pp.gstack = pp.reci + blocks * size_t(3 + a.nl) * plane;
     WfRaySource src; src.a = a; src.n_paths = n;                       // (path mode never fetches or stores through it)
     Work w = {0, 0};
-    trace_pool<WfRaySource, NW, KT, SCAP, WfPaths>(S, src, nullptr, nullptr, 0u, 64, L, w, spill, pp);
+    trace_pool<WfRaySource, NW, KT, SCAP, WfPaths<ENV>>(S, src, nullptr, nullptr, 0u, 64, L, w, spill, pp);
     LaneStats ls;
     ls.nodes = w.nodes; ls.tris = w.tris;
     __syncthreads();
@@ -657,9 +693,15 @@ void launch_wf_logic(const DScene& S, const WfArgs& a, long long n_upper, bool f
 {
     if (n_upper <= 0) return;
     // small inputs get small grids (>= 1024 paths per block): every wave that starts costs a few atomics on shared counters
-    unsigned g = grid_for(n_upper, 1024, first ? cfg.logic_first : cfg.logic_rest);
-    if (first) hipLaunchKernelGGL(k_wf_logic<true>, dim3(g), dim3(256), 0, st, S, a);
-    else hipLaunchKernelGGL(k_wf_logic<false>, dim3(g), dim3(256), 0, st, S, a);
+    const bool env = env_on(S.env);
+    unsigned g = grid_for(n_upper, 1024, first ? (env ? cfg.logic_first_env : cfg.logic_first) : (env ? cfg.logic_rest_env : cfg.logic_rest));
+    if (first) {
+        if (env) hipLaunchKernelGGL((k_wf_logic<true, true>), dim3(g), dim3(256), 0, st, S, a);
+        else hipLaunchKernelGGL((k_wf_logic<true, false>), dim3(g), dim3(256), 0, st, S, a);
+    } else {
+        if (env) hipLaunchKernelGGL((k_wf_logic<false, true>), dim3(g), dim3(256), 0, st, S, a);
+        else hipLaunchKernelGGL((k_wf_logic<false, false>), dim3(g), dim3(256), 0, st, S, a);
+    }
 }
 
 void launch_wf_finish(const DScene& S, const WfArgs& a, long long n_upper, hipStream_t st, const LaunchCfg& cfg, char* path_area, long long* slow_list,
@@ -671,11 +713,16 @@ void launch_wf_finish(const DScene& S, const WfArgs& a, long long n_upper, hipSt
         const long long per_block = 64ll * (MCPT_POOL_KT / (a.nl + 1));
         const long long nb = (n_upper + per_block - 1) / per_block;
         const int g = (int)(nb < cfg.cus ? nb : cfg.cus);
-        hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK>), dim3(g), dim3(MCPT_POOL_WAVES * 64), 0, st, S, a, path_area,
-                           reinterpret_cast<int*>(slow_list + slow_cap));
+        if (env_on(S.env))
+            hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, true>), dim3(g), dim3(MCPT_POOL_WAVES * 64), 0, st, S, a, path_area,
+                               reinterpret_cast<int*>(slow_list + slow_cap));
+        else
+            hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, false>), dim3(g), dim3(MCPT_POOL_WAVES * 64), 0, st, S, a, path_area,
+                               reinterpret_cast<int*>(slow_list + slow_cap));
         return;
     }
-    hipLaunchKernelGGL(k_wf_finish, dim3(grid_for(n_upper, 256, unsigned(cfg.finish_grid))), dim3(256), 0, st, S, a);
+    if (env_on(S.env)) hipLaunchKernelGGL(k_wf_finish<true>, dim3(grid_for(n_upper, 256, unsigned(cfg.finish_grid_env))), dim3(256), 0, st, S, a);
+    else hipLaunchKernelGGL(k_wf_finish<false>, dim3(grid_for(n_upper, 256, unsigned(cfg.finish_grid))), dim3(256), 0, st, S, a);
 }
 
 void launch_hit_slots(const PrimaryHit* hits, int first_slot, int n_slots, int32_t* hit_slots, unsigned int* count, hipStream_t st)
@@ -692,9 +739,12 @@ void launch_zero_rad(double* rad, long long n, hipStream_t st)
 
 void init_launch_cfg_logic(LaunchCfg& cfg, unsigned forced_grid)
 {
-    cfg.logic_first = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true>), cfg.cus));
-    cfg.logic_rest = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false>), cfg.cus));
-    cfg.finish_grid = persistent_grid(reinterpret_cast<const void*>(k_wf_finish), cfg.cus);
+    cfg.logic_first = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, false>), cfg.cus));
+    cfg.logic_rest = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, false>), cfg.cus));
+    cfg.finish_grid = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<false>), cfg.cus);
+    cfg.logic_first_env = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, true>), cfg.cus));
+    cfg.logic_rest_env = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, true>), cfg.cus));
+    cfg.finish_grid_env = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<true>), cfg.cus);
 }
 
 }  // namespace mcpt
