@@ -95,6 +95,7 @@ struct orc_scene {
     Node* nodes;
     double area0;            /* total area of light 0: the frozen range of the static u1 (Q1) */
     int walk_mode;           /* ORC_TRACE_* the integrator's rays are walked with (same hits; ALIAS = the reference's visit counts) */
+    struct orc_env* env;     /* the environment light (extension): NULL = none or inactive */
 };
 
 /* ------------------------------------------------------------------ RNG seam (D1) */
@@ -536,6 +537,7 @@ void orc_scene_free(orc_scene* s)
     for (int i = 0; i < s->nm; i++) { free(s->m[i].faces); free(s->m[i].bgr); }
     for (int i = 0; i < s->nl; i++) free(s->l[i].cdf);
     free(s->v); free(s->vn); free(s->vt); free(s->f); free(s->order); free(s->m); free(s->l); free(s->nodes);
+    orc_scene_set_environment(s, NULL, 0, 0, 1.0);
     free(s);
 }
 
@@ -761,6 +763,124 @@ void orc_trace_closest(const orc_scene* s, const double* rays, int64_t n, int mo
     if (st) { st->box_tests += tb; st->tri_tests += tt; }
 }
 
+/* ------------------------------------------------------------------ environment light (extension)
+ * include/mcpt.h "environment light", restated from its text (not from the product's code): fp64 tables built on the host in the
+ * header's operation order, the nearest-texel lookup, a draw in proportion to luminance x solid angle. */
+#define ORC_ENV_PI     3.141592653589793
+#define ORC_ENV_TWO_PI 6.283185307179586
+
+typedef struct orc_env {
+    int W, H;
+    double scale, Z;
+    float* rgb;              /* H x W x 3, top row first */
+    double* c;               /* H + 1 row borders in cos(theta) */
+    double* lum;             /* H x W */
+    double* cond;            /* H x W: running sums of lum * omega along each row */
+    double* marg;            /* H: running sums of the rows' last entries */
+} Env;
+
+static void env_free(Env* e)
+{
+    if (!e) return;
+    free(e->rgb); free(e->c); free(e->lum); free(e->cond); free(e->marg); free(e);
+}
+
+double orc_scene_set_environment(orc_scene* s, const float* rgb, int W, int H, double scale)
+{
+    if (!rgb) { env_free(s->env); s->env = NULL; return 0.0; }
+    if (W < 1 || H < 1 || !(scale > 0) || !isfinite(scale)) return -1.0;
+    const size_t n = (size_t)W * (size_t)H;
+    for (size_t k = 0; k < 3 * n; k++)
+        if (!isfinite(rgb[k]) || rgb[k] < 0) return -1.0;
+    Env* e = (Env*)calloc(1, sizeof *e);
+    e->W = W; e->H = H; e->scale = scale;
+    e->rgb = (float*)malloc(sizeof(float) * 3 * n);
+    memcpy(e->rgb, rgb, sizeof(float) * 3 * n);
+    e->c = (double*)malloc(sizeof(double) * (H + 1));
+    e->lum = (double*)malloc(sizeof(double) * n);
+    e->cond = (double*)malloc(sizeof(double) * n);
+    e->marg = (double*)malloc(sizeof(double) * H);
+    for (int i = 0; i <= H; i++) e->c[i] = cos(ORC_ENV_PI * (double)i / (double)H);
+    e->c[0] = 1.0; e->c[H] = -1.0;
+    double total = 0.0;
+    for (int i = 0; i < H; i++) {
+        const double omega = ((e->c[i] - e->c[i + 1]) * ORC_ENV_TWO_PI) / (double)W;
+        double row = 0.0;
+        for (int j = 0; j < W; j++) {
+            const size_t t = (size_t)i * W + j;
+            const double r = (double)rgb[3 * t], g = (double)rgb[3 * t + 1], b = (double)rgb[3 * t + 2];
+            e->lum[t] = (0.2126 * r + 0.7152 * g) + 0.0722 * b;
+            row += e->lum[t] * omega;
+            e->cond[t] = row;
+        }
+        total += row;
+        e->marg[i] = total;
+    }
+    e->Z = total;
+    env_free(s->env); s->env = NULL;
+    if (!(e->Z > 0)) { env_free(e); return 0.0; }
+    s->env = e;
+    return e->Z;
+}
+
+static vec3 env_texel(const Env* e, int i, int j)
+{
+    const float* t = e->rgb + ((size_t)i * e->W + j) * 3;
+    return v3(e->scale * (double)t[0], e->scale * (double)t[1], e->scale * (double)t[2]);
+}
+
+/* the first k of [0, n) with x < a[k] for a non-decreasing a; n - 1 if there is none */
+static int first_above(const double* a, int n, double x)
+{
+    int lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (x < a[mid]) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
+/* Le(d): phi = atan2(z, x) in [0, 2 pi), column floor(phi W / 2 pi) clamped; row i with c[i+1] < y <= c[i] (the last row takes y = -1) */
+static vec3 env_lookup(const Env* e, vec3 d)
+{
+    double phi = atan2(d.z, d.x);
+    if (phi < 0) phi += ORC_ENV_TWO_PI;
+    const double col = floor((phi * (double)e->W) / ORC_ENV_TWO_PI);
+    const int j = col < 0 ? 0 : (col > e->W - 1 ? e->W - 1 : (int)col);
+    const double y = d.y < -1.0 ? -1.0 : (d.y > 1.0 ? 1.0 : d.y);
+    int lo = 0, hi = e->H - 1;                  /* c decreases: the first i with c[i+1] < y */
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (e->c[mid + 1] < y) hi = mid; else lo = mid + 1;
+    }
+    return env_texel(e, lo, j);
+}
+
+/* the draw from u0..u3: direction d, pdf per unit solid angle, the drawn texel's radiance */
+static void env_draw(const Env* e, double u0, double u1, double u2, double u3, vec3* d, double* pdf, vec3* le)
+{
+    const int i = first_above(e->marg, e->H, u0 * e->Z);
+    const double* cond = e->cond + (size_t)i * e->W;
+    const int j = first_above(cond, e->W, u1 * cond[e->W - 1]);
+    const double ct = e->c[i] + (e->c[i + 1] - e->c[i]) * u2;
+    const double one_minus = 1.0 - ct * ct;
+    const double st = sqrt(one_minus > 0.0 ? one_minus : 0.0);
+    const double phi = (ORC_ENV_TWO_PI * ((double)j + u3)) / (double)e->W;
+    *d = v3(st * cos(phi), ct, st * sin(phi));
+    *pdf = e->lum[(size_t)i * e->W + j] / e->Z;
+    *le = env_texel(e, i, j);
+}
+
+int orc_env_eval(const orc_scene* s, const double* dirs, int64_t n, double* rgb)
+{
+    if (!s->env) return -1;
+    for (int64_t i = 0; i < n; i++) {
+        const vec3 le = env_lookup(s->env, v3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]));
+        rgb[3 * i] = le.x; rgb[3 * i + 1] = le.y; rgb[3 * i + 2] = le.z;
+    }
+    return 0;
+}
+
 /* ------------------------------------------------------------------ integrator */
 enum { RT_DIFFUSE = 0, RT_SPECULAR = 1, RT_TRANSMISSION = 2 };   /* sceneManagement.h:203-205 */
 
@@ -769,6 +889,7 @@ typedef struct {
     uint64_t seed; uint32_t pixel, sample;
     int faithful_cost;
     orc_stats* st; Cnt c;
+    const Env* env;          /* the environment the path sees (NULL: none) */
 } Ctx;
 
 /* slot table per path vertex: light i -> 4i..4i+3, then RR, FRESNEL, LOBE, PHI, THETA */
@@ -781,6 +902,27 @@ typedef struct {
 static inline double U(const Ctx* c, int depth, uint32_t slot)
 {
     return orc_uniform(c->seed, c->pixel, c->sample, (uint32_t)depth, slot);
+}
+
+/* the environment's draw at vertex `depth`: slots 4(nl+2) .. 4(nl+2)+3, after the lights (4i..4i+3) and RR..THETA (4nl..4nl+4) */
+static void env_draw_at(const Ctx* c, int depth, vec3* d, double* pdf, vec3* le)
+{
+    const uint32_t b = 4u * ((uint32_t)c->s->nl + 2u);
+    env_draw(c->env, U(c, depth, b), U(c, depth, b + 1u), U(c, depth, b + 2u), U(c, depth, b + 3u), d, pdf, le);
+}
+
+int orc_env_sample(const orc_scene* s, uint64_t seed, const int32_t* pix, const int32_t* k, int depth, int64_t n, double* dirs, double* pdf,
+                   double* rgb)
+{
+    if (!s->env || depth < 0) return -1;
+    for (int64_t i = 0; i < n; i++) {
+        const Ctx c = { s, seed, (uint32_t)pix[i], (uint32_t)k[i], 0, NULL, { 0, 0 }, s->env };
+        vec3 d, le;
+        env_draw_at(&c, depth, &d, &pdf[i], &le);
+        dirs[3 * i] = d.x; dirs[3 * i + 1] = d.y; dirs[3 * i + 2] = d.z;
+        rgb[3 * i] = le.x; rgb[3 * i + 1] = le.y; rgb[3 * i + 2] = le.z;
+    }
+    return 0;
 }
 
 /* Refract, MTPC/pathTracing.cpp:13-27 (float cosi / cost2) */
@@ -932,6 +1074,24 @@ static vec3 shade(Ctx* c, const Hit* p, vec3 dir, int depth)
             }
         }
     }
+    if (c->env) {                        /* the environment's light sample (extension): a shadow ray that must leave the scene */
+        vec3 d, le; double pdf;
+        env_draw_at(c, depth, &d, &pdf, &le);
+        const double k = vdot(d, p->pn);
+        if (k > 0) {
+            RayT rl = { vadd(p->p, vmul(d, 0.01)), d };
+            Hit inter;
+            ray_intersect(s, &rl, &inter, s->walk_mode, &c->c);
+            if (c->st) { c->st->rays_shadow++; c->st->env_shadow++; }
+            if (!inter.hit) {
+                const double g = ((k / vnorm(p->pn)) / ORC_ENV_PI) / pdf;
+                if (c->st) c->st->env_shadow_clear++;
+                L_dir.x += (kd.x * le.x) * g;
+                L_dir.y += (kd.y * le.y) * g;
+                L_dir.z += (kd.z * le.z) * g;
+            }
+        }
+    }
 
     /* indirect illumination, :234-263 */
     vec3 L_indir = v3(0, 0, 0);
@@ -955,6 +1115,17 @@ static vec3 shade(Ctx* c, const Hit* p, vec3 dir, int depth)
                 L_indir.y += m->ks.y * intensity.y;
                 L_indir.z += m->ks.z * intensity.z;
             } else {
+                L_indir = vadd(L_indir, intensity);
+            }
+        } else if (c->env && r.type != RT_DIFFUSE) {      /* left the scene: Le as the radiance it brings back (T' * Le, recursively) */
+            const vec3 intensity = vdiv(env_lookup(c->env, r.d), P_RR);
+            if (r.type == RT_SPECULAR) {
+                if (c->st) c->st->env_escape_specular++;
+                L_indir.x += m->ks.x * intensity.x;
+                L_indir.y += m->ks.y * intensity.y;
+                L_indir.z += m->ks.z * intensity.z;
+            } else {
+                if (c->st) c->st->env_escape_transmission++;
                 L_indir = vadd(L_indir, intensity);
             }
         }
@@ -1022,7 +1193,11 @@ static vec3 sample_radiance(Ctx* c, const RayT* ray, const Hit* primary, int hav
     if (have_primary) h = *primary;
     else { if (c->st) c->st->rays_primary++; ray_intersect(c->s, ray, &h, c->s->walk_mode, &c->c); }
     if (c->st) c->st->samples++;
-    if (!h.hit) return v3(0, 0, 0);
+    if (!h.hit) {
+        if (!c->env) return v3(0, 0, 0);
+        if (c->st) c->st->camera_miss++;
+        return env_lookup(c->env, ray->d);      /* a camera ray that misses brings Le(d), unweighted */
+    }
     return shade(c, &h, vneg(ray->d), 0);
 }
 
@@ -1031,7 +1206,7 @@ void orc_sample_radiance(const orc_scene* s, uint64_t seed, int row, int col, in
     CamFrame cf = cam_frame(s);
     vec3 pos = pixel_pos(&cf, row, col);
     RayT ray = { cf.eye, vnormalize(vsub(pos, cf.eye)) };
-    Ctx c = { s, seed, (uint32_t)(row * s->width + col), (uint32_t)k, 0, st, { 0, 0 } };
+    Ctx c = { s, seed, (uint32_t)(row * s->width + col), (uint32_t)k, 0, st, { 0, 0 }, s->env };
     vec3 r = sample_radiance(&c, &ray, NULL, 0);
     if (st) { st->box_tests += c.c.box; st->tri_tests += c.c.tri; }
     rgb[0] = r.x; rgb[1] = r.y; rgb[2] = r.z;
@@ -1043,11 +1218,14 @@ static void stats_add(orc_stats* a, const orc_stats* b)
     a->box_tests += b->box_tests; a->tri_tests += b->tri_tests; a->shade_calls += b->shade_calls; a->samples += b->samples;
     if (b->max_depth > a->max_depth) a->max_depth = b->max_depth;
     a->rays_on_surface += b->rays_on_surface;
+    a->env_shadow += b->env_shadow; a->env_shadow_clear += b->env_shadow_clear;
+    a->env_escape_specular += b->env_escape_specular; a->env_escape_transmission += b->env_escape_transmission;
+    a->camera_miss += b->camera_miss;
 }
 
-/* generateImg, MTPC/pathTracing.cpp:274-331 (D1, D3) */
-void orc_render(const orc_scene* s, int spp, uint64_t seed, int row0, int row1, int col0, int col1,
-                int faithful_cost, int nthreads, double* img, orc_stats* st)
+/* generateImg, MTPC/pathTracing.cpp:274-331 (D1, D3), under the environment env (NULL: none) */
+static void render_block(const orc_scene* s, const Env* env, int spp, uint64_t seed, int row0, int row1, int col0, int col1,
+                         int faithful_cost, int nthreads, double* img, orc_stats* st)
 {
     CamFrame cf = cam_frame(s);
     const int W = s->width;
@@ -1065,7 +1243,7 @@ void orc_render(const orc_scene* s, int spp, uint64_t seed, int row0, int row1, 
                 if (j >= col0) {
                     float cr = 0, cg = 0, cb = 0;                      /* glm::vec3 current_radiance :301 */
                     RayT ray = { cf.eye, vnormalize(vsub(pos, cf.eye)) };
-                    Ctx c = { s, seed, (uint32_t)(i * W + j), 0, faithful_cost, &local, { 0, 0 } };
+                    Ctx c = { s, seed, (uint32_t)(i * W + j), 0, faithful_cost, &local, { 0, 0 }, env };
                     Hit primary; int have = 0;
                     if (!faithful_cost) {                              /* identical for every k: trace once */
                         local.rays_primary++;
@@ -1074,7 +1252,16 @@ void orc_render(const orc_scene* s, int spp, uint64_t seed, int row0, int row1, 
                     }
                     for (int k = 0; k < spp; k++) {
                         c.sample = (uint32_t)k;
-                        if (have && !primary.hit) { local.samples++; continue; }
+                        if (have && !primary.hit) {
+                            local.samples++;
+                            if (!env) continue;
+                            local.camera_miss++;                       /* a missed pixel folds Le(d) / spp for each sample */
+                            const vec3 le = env_lookup(env, ray.d);
+                            cr += le.x / spp;
+                            cg += le.y / spp;
+                            cb += le.z / spp;
+                            continue;
+                        }
                         vec3 radiance = sample_radiance(&c, &ray, &primary, have);
                         if (!have) {
                             /* faithful: only hits accumulate (:311-319); a miss adds nothing */
@@ -1095,6 +1282,12 @@ void orc_render(const orc_scene* s, int spp, uint64_t seed, int row0, int row1, 
         stats_add(&total, &local);
     }
     if (st) stats_add(st, &total);
+}
+
+void orc_render(const orc_scene* s, int spp, uint64_t seed, int row0, int row1, int col0, int col1,
+                int faithful_cost, int nthreads, double* img, orc_stats* st)
+{
+    render_block(s, s->env, spp, seed, row0, row1, col0, col1, faithful_cost, nthreads, img, st);
 }
 
 /* The reference's own parallel structure, for timing (MTPC/pathTracing.cpp:300-320): the samples of ONE pixel at a time on
@@ -1123,7 +1316,7 @@ void orc_render_reference_style(const orc_scene* s, int spp, uint64_t seed, int 
                     uint64_t box = 0, tri = 0;
 #pragma omp for schedule(static)
                     for (int k = 0; k < spp; k++) {
-                        Ctx c = { s, seed, (uint32_t)(i * W + j), (uint32_t)k, 1, &local, { 0, 0 } };
+                        Ctx c = { s, seed, (uint32_t)(i * W + j), (uint32_t)k, 1, &local, { 0, 0 }, NULL };   /* (no environment) */
                         RayT r = ray;
                         Hit primary;
                         rad[k] = sample_radiance(&c, &r, &primary, 0);
@@ -1220,7 +1413,7 @@ void orc_render_strided(const orc_scene* s, int spp, uint64_t seed, int row_stri
         for (int w = 0; w < nrows * ncb; w++) {
             const int r = (w / ncb) * row_stride, c0 = (w % ncb) * cb;
             const int c1 = c0 + cb < s->width ? c0 + cb : s->width;
-            orc_render(s, spp, seed, r, r + 1, c0, c1, faithful_cost, -1, img, &local);
+            render_block(s, NULL, spp, seed, r, r + 1, c0, c1, faithful_cost, -1, img, &local);   /* (no environment) */
         }
 #pragma omp critical
         stats_add(&total, &local);

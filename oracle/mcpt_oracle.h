@@ -41,6 +41,10 @@
  *   D6  recursion depth of shade() is capped at ORC_MAX_DEPTH (reference: unbounded).
  *   D7  texture row/col are clamped to the raster (reference: possible 1-past read).
  *   D8  Ns/Ni default to 1 when absent from the .mtl (reference: uninitialised).
+ *
+ * Extension (not in the reference): the environment light of include/mcpt.h, restated from that header's text (orc_scene_set_environment
+ * below); pinned by tests/test_env_cpu.py (tables and draws against tests/env_ref.py, closed forms) and held against the GPU by
+ * tests/test_gpu_env_oracle.py.  Without an environment every answer and every count is what it was before.
  */
 #ifndef MCPT_ORACLE_H
 #define MCPT_ORACLE_H
@@ -66,6 +70,10 @@ typedef struct {
     uint64_t box_tests, tri_tests, shade_calls, samples;
     int max_depth;
     uint64_t rays_on_surface;   /* bounce rays that start on the surface itself: refraction / total reflection (pathTracing.cpp:102,109) */
+    /* the environment (extension; all 0 without one).  env_shadow is also counted in rays_shadow. */
+    uint64_t env_shadow, env_shadow_clear;                  /* environment shadow rays traced; those that hit nothing */
+    uint64_t env_escape_specular, env_escape_transmission;  /* SPECULAR / TRANSMISSION bounce rays that left the scene */
+    uint64_t camera_miss;                                   /* camera samples whose primary ray left the scene */
 } orc_stats;
 
 /* ---- RNG seam (D1) ---- */
@@ -132,6 +140,20 @@ void orc_render_strided(const orc_scene*, int spp, uint64_t seed, int row_stride
 /* the reference's own parallel structure (one pixel at a time, min(spp, 8) threads over its samples, fork/join per pixel:
  * MTPC/pathTracing.cpp:300-320), faithful cost, on the pixels (k * row_stride, m * col_stride): the reference-style timing */
 void orc_render_reference_style(const orc_scene*, int spp, uint64_t seed, int row_stride, int col_stride, double* img, orc_stats* st);
+
+/* ---- environment light (extension, not in the reference): include/mcpt.h "environment light", restated from its text ----
+ * rgb = W x H x 3 floats, top row first; the fp64 tables are built in the header's operation order (row borders through the C library's
+ * cos; pi = 3.141592653589793 there, in phi and in the light sample's "/ pi" -- not ORC_PI).  Returns Z.  Z == 0 (an all-black map, or
+ * rgb NULL) leaves the scene WITHOUT an environment, as the header's "inactive"; -1: bad arguments (the previous environment is kept).
+ * With one, orc_sample_radiance and orc_render (either cost) follow the header: a light sample from slots 4(nl+2)..4(nl+2)+3 after the
+ * lights' loop, escapes of SPECULAR and TRANSMISSION bounce rays, camera misses (a missed pixel folds Le / spp for every sample).
+ * orc_render_strided and orc_render_reference_style IGNORE the environment: they render as without one (the CPU baseline). */
+double orc_scene_set_environment(orc_scene*, const float* rgb, int W, int H, double scale);
+/* Le(dirs[i]) -> rgb[n*3]; the draw of vertex `depth` of camera samples (pix[i] = row*W+col, k[i]) -> dirs[n*3], pdf[n], rgb[n*3] (the drawn
+ * texel's radiance): the functions the paths use.  0, or -1 without an active environment. */
+int orc_env_eval(const orc_scene*, const double* dirs, int64_t n, double* rgb);
+int orc_env_sample(const orc_scene*, uint64_t seed, const int32_t* pix, const int32_t* k, int depth, int64_t n, double* dirs, double* pdf,
+                   double* rgb);
 
 /* ---- output: MTPC/MTPC.cpp:10-33, MTPC/svpng.inc:77-107 ---- */
 void orc_quantize(const double* img, int64_t n, uint8_t* rgb8);

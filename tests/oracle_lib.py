@@ -23,7 +23,8 @@ class BvhInfo(C.Structure):
 
 class Stats(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("rays_primary", "rays_shadow", "rays_bounce", "box_tests",
-                                           "tri_tests", "shade_calls", "samples")] + [("max_depth", C.c_int), ("rays_on_surface", C.c_uint64)]
+                                           "tri_tests", "shade_calls", "samples")] + [("max_depth", C.c_int), ("rays_on_surface", C.c_uint64)] + [
+        (n, C.c_uint64) for n in ("env_shadow", "env_shadow_clear", "env_escape_specular", "env_escape_transmission", "camera_miss")]
 
     @property
     def rays(self):
@@ -86,6 +87,11 @@ def lib():
         L.orc_philox4x32_10.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.orc_morton_code.restype = C.c_uint32
         L.orc_morton_code.argtypes = [C.c_float, C.c_float, C.c_float]
+        L.orc_scene_set_environment.restype = C.c_double
+        L.orc_scene_set_environment.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_double]
+        L.orc_env_eval.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double)]
+        L.orc_env_sample.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int64,
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -207,6 +213,40 @@ class OracleScene:
         lib().orc_render(self.h, spp, seed, r0, r1, c0, c1, int(faithful_cost), nthreads, _ptr(img, C.c_double),
                          C.byref(stats) if stats is not None else None)
         return img
+
+    def set_environment(self, rgb=None, scale=1.0):
+        """The environment light (an extension of the oracle, include/mcpt.h): rgb = an (H, W, 3) map, top row first, or an (r, g, b)
+        constant sky, taken as float32 as the product takes it; None clears it.  Returns Z (0: inactive -- the scene has none)."""
+        if rgb is None:
+            return lib().orc_scene_set_environment(self.h, None, 0, 0, 1.0)
+        a = np.asarray(rgb, dtype=np.float64)
+        if a.ndim == 1:
+            a = a.reshape(1, 1, 3)
+        self._env_tex = np.ascontiguousarray(a, dtype=np.float32)
+        z = lib().orc_scene_set_environment(self.h, _ptr(self._env_tex, C.c_float), self._env_tex.shape[1], self._env_tex.shape[0],
+                                            float(scale))
+        if z < 0:
+            raise ValueError("oracle: bad environment")
+        return z
+
+    def env_eval(self, dirs):
+        """Le(dirs[i]) under the scene's environment: (n, 3)"""
+        dirs = np.ascontiguousarray(dirs, dtype=np.float64).reshape(-1, 3)
+        rgb = np.zeros((dirs.shape[0], 3))
+        if lib().orc_env_eval(self.h, _ptr(dirs, C.c_double), dirs.shape[0], _ptr(rgb, C.c_double)) != 0:
+            raise ValueError("oracle: no active environment")
+        return rgb
+
+    def env_sample(self, seed, pix, k, depth):
+        """the environment's draw at vertex `depth` of camera samples (pix[i], k[i]): directions (n, 3), pdf (n,), radiance (n, 3)"""
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        n = pix.shape[0]
+        dirs, pdf, rgb = np.zeros((n, 3)), np.zeros(n), np.zeros((n, 3))
+        if lib().orc_env_sample(self.h, seed, _ptr(pix, C.c_int32), _ptr(k, C.c_int32), int(depth), n, _ptr(dirs, C.c_double),
+                                _ptr(pdf, C.c_double), _ptr(rgb, C.c_double)) != 0:
+            raise ValueError("oracle: no active environment")
+        return dirs, pdf, rgb
 
 
 def _render_strided(self, spp, seed, row_stride, faithful_cost=True, nthreads=0, stats=None, img=None):

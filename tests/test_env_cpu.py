@@ -1,6 +1,11 @@
 """Not gpu: the C-ABI surface of the environment light -- symbols, the mcpt_environment layout against the C compiler, argument errors with a
 null device, the PFM reader against mcpt_write_pfm, render_scene's refusals of a bad map -- and the numpy restatement (env_ref) of maps
-loaded through mcpt_read_pfm: its pdf integrates to 1, a 1x1 map is the uniform sphere, and its draws follow its pdf (chi-square)."""
+loaded through mcpt_read_pfm: its pdf integrates to 1, a 1x1 map is the uniform sphere, and its draws follow its pdf (chi-square).
+
+The oracle's environment mode (an extension of oracle/mcpt_oracle.c, restated from include/mcpt.h), held to something outside itself: its
+tables and draws are env_ref's bit for bit on the edge maps (tests/env_scenes.py) and test_gpu_env.py's map, at two light counts; its
+frames meet the closed forms of a diffuse floor under a constant sky and under a band, and of a Phong plate under a constant sky; a frame
+whose camera rays all miss is the float fold of Le; without an environment, or with an inactive one, nothing changes."""
 import ctypes as C
 import os
 import shutil
@@ -10,6 +15,7 @@ import numpy as np
 import pytest
 
 import env_ref
+import env_scenes
 from conftest import ROOT, SCENES
 
 ERR_IO, ERR_PARSE, ERR_ARG, ERR_NO_DEVICE = -1, -2, -3, -4
@@ -202,3 +208,169 @@ def test_render_scene_refuses_a_bad_map_before_writing(mcpt, tmp_path):
     for scale in (0.0, -1.0, float("nan"), float("inf")):
         assert L.mcpt_render_scene_env(*args, ok.encode(), scale, None) == ERR_ARG
     assert not os.path.exists(prefix + "-SPP1.png")
+
+
+# ---------------------------------------------------------------------------------------------------------------- the oracle's environment
+ORACLE_MAPS = dict(env_scenes.EDGE_MAPS, **{"sky-map": env_scenes.SKIES["map"]})
+OW, OH = 48, 27
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def _off_column_borders(d, W):
+    phi = np.mod(np.arctan2(d[:, 2], d[:, 0]), 2 * np.pi) * W / (2 * np.pi)
+    return np.abs(phi - np.round(phi)) * (2 * np.pi / W) >= 1e-12
+
+
+@pytest.fixture(scope="module")
+def env_dir(tmp_path_factory):
+    d = str(tmp_path_factory.mktemp("env_scenes")) + os.sep
+    env_scenes.open_scene(d, "open_nl0", 0, OW, OH)
+    env_scenes.open_scene(d, "open_nl1", 1, OW, OH)
+    return d
+
+
+@pytest.mark.parametrize("scene", ["open_nl0", "open_nl1"])
+@pytest.mark.parametrize("name", sorted(ORACLE_MAPS))
+def test_oracle_tables_and_draws_are_the_restatement(oracle, env_dir, scene, name):
+    rgb, scale = ORACLE_MAPS[name]
+    osc = oracle.OracleScene(env_dir + scene)
+    assert osc.num_lights == int(scene[-1])
+    ref = env_ref.EnvRef(rgb, scale)
+    assert ref.Z > 0
+    assert osc.set_environment(rgb, scale) == ref.Z
+    rng = np.random.default_rng(len(name))
+    n = 2000
+    pix = rng.integers(0, OW * OH, size=n).astype(np.int32)
+    ks = rng.integers(0, 1000, size=n).astype(np.int32)
+    dirs = [rng.normal(size=(2000, 3)), [[0, 1, 0], [0, -1, 0], [1, 0, 0], [0, 0, 1], [-1, 0, 0], [0, 0, -1], [1, 0, -1e-9]]]
+    for depth in (0, 5):
+        d, pdf, le = osc.env_sample(9, pix, ks, depth)
+        i, j, dr, pr, lr = ref.sample_u(*env_ref.vertex_uniforms(9, pix, ks, depth, osc.num_lights))
+        assert np.array_equal(_bits(pdf), _bits(pr)) and np.array_equal(_bits(le), _bits(lr))
+        assert np.abs(d - dr).max() <= 1e-15
+        assert np.all(ref.lum[i, j] > 0) and np.all(np.isfinite(pdf) & (pdf > 0)) and np.isfinite(le).all()
+        dirs.append(d)
+    dirs = np.concatenate(dirs)
+    dirs /= np.linalg.norm(dirs, axis=1)[:, None]
+    keep = _off_column_borders(dirs, ref.W)
+    assert np.array_equal(_bits(osc.env_eval(dirs)[keep]), _bits(ref.eval(dirs)[keep]))
+    osc.close()
+
+
+def test_oracle_without_an_environment_is_unchanged(oracle):
+    osc = oracle.OracleScene(SCENES + "cornell-box", texture_dir=SCENES, width=32, height=18)
+    st0 = oracle.Stats()
+    ref = osc.render(2, seed=3, stats=st0)
+    strided = osc.render_strided(2, 3, 4, faithful_cost=False)
+    sample = osc.sample_radiance(3, 9, 16, 1)
+    fields = [f for f, _ in oracle.Stats._fields_]
+    assert st0.env_shadow == st0.env_shadow_clear == st0.env_escape_specular == st0.env_escape_transmission == st0.camera_miss == 0
+    with pytest.raises(ValueError):
+        osc.env_eval(np.array([[0.0, 1.0, 0.0]]))
+    # an inactive (all-black) map is no environment; a cleared one neither
+    assert osc.set_environment(np.zeros((4, 8, 3))) == 0.0
+    st1 = oracle.Stats()
+    assert np.array_equal(_bits(osc.render(2, seed=3, stats=st1)), _bits(ref))
+    assert [getattr(st1, f) for f in fields] == [getattr(st0, f) for f in fields]
+    assert osc.set_environment(*env_scenes.SKIES["map"]) > 0
+    lit = osc.render(2, seed=3)
+    assert not np.array_equal(_bits(lit), _bits(ref))
+    # the CPU baseline's entry points ignore the environment
+    assert np.array_equal(_bits(osc.render_strided(2, 3, 4, faithful_cost=False)), _bits(strided))
+    assert osc.set_environment(None) == 0.0
+    st2 = oracle.Stats()
+    assert np.array_equal(_bits(osc.render(2, seed=3, stats=st2)), _bits(ref))
+    assert [getattr(st2, f) for f in fields] == [getattr(st0, f) for f in fields]
+    assert np.array_equal(_bits(osc.sample_radiance(3, 9, 16, 1)), _bits(sample))
+    with pytest.raises(ValueError):
+        osc.set_environment(np.full((2, 2, 3), -1.0))
+    osc.close()
+
+
+def _z(img, expect):
+    x = img.reshape(-1, 3)
+    m = x.mean(axis=0)
+    s = x.std(axis=0, ddof=1) / np.sqrt(x.shape[0])
+    return np.abs(m - expect) / np.maximum(s, 1e-300)
+
+
+def test_oracle_diffuse_floor_under_a_constant_sky(oracle, tmp_path):
+    rho, L = 0.5, np.array([1.0, 2.0, 0.5])
+    env_scenes.floor_scene(str(tmp_path), "floor", (rho, rho, rho))
+    osc = oracle.OracleScene(str(tmp_path / "floor"))
+    assert osc.num_lights == 0
+    assert np.all(osc.render(4, seed=1) == 0.0)                            # no lights, no sky: black
+    osc.set_environment(L)
+    st = oracle.Stats()
+    img = osc.render(256, seed=2, stats=st)
+    z = _z(img, rho * L)
+    assert np.all(z < 5.0), z
+    # every shadow ray sees the sky; nothing escapes but diffuse bounces (which add nothing); every camera ray hits the floor
+    assert st.env_shadow > 0.4 * st.samples and st.env_shadow_clear == st.env_shadow == st.rays_shadow
+    assert st.env_escape_specular == st.env_escape_transmission == st.camera_miss == 0
+    osc.close()
+
+
+def test_oracle_diffuse_floor_under_a_band(oracle, tmp_path):
+    """test_gpu_env.py::test_diffuse_floor_under_a_band on the oracle"""
+    rho = 0.8
+    W_, H_ = 16, 8
+    m = np.zeros((H_, W_, 3))
+    m[1, 3:6] = [[4.0, 2.0, 1.0], [1.0, 1.0, 1.0], [0.5, 3.0, 2.0]]
+    env_scenes.floor_scene(str(tmp_path), "floor", (rho, rho, rho))
+    osc = oracle.OracleScene(str(tmp_path / "floor"))
+    osc.set_environment(m)
+    img = osc.render(512, seed=3)
+    t0, t1 = np.pi * 1 / H_, np.pi * 2 / H_
+    dphi = 2 * np.pi / W_
+    expect = rho / np.pi * m[1, 3:6].sum(axis=0) * dphi * (np.sin(t1) ** 2 - np.sin(t0) ** 2) / 2
+    z = _z(img, expect)
+    assert np.all(z < 5.0), (z, img.reshape(-1, 3).mean(axis=0), expect)
+    osc.close()
+
+
+def test_oracle_phong_plate_under_a_constant_sky(oracle, tmp_path):
+    """Kd = 0, Ks = 0.5: the light sample adds nothing and every bounce is SPECULAR; a bounce ray leaves the scene whichever way it goes
+    and brings Ks * L / 0.6 with probability 0.6 -- Ks * L"""
+    ks, L = 0.5, np.array([1.0, 2.0, 0.5])
+    env_scenes.floor_scene(str(tmp_path), "plate", (0, 0, 0), ks=(ks, ks, ks), ns=20)
+    osc = oracle.OracleScene(str(tmp_path / "plate"))
+    osc.set_environment(L)
+    st = oracle.Stats()
+    img = osc.render(256, seed=4, stats=st)
+    z = _z(img, ks * L)
+    assert np.all(z < 5.0), (z, img.reshape(-1, 3).mean(axis=0))
+    assert st.env_escape_specular == st.rays_bounce > 0.5 * st.samples
+    assert st.env_escape_transmission == st.camera_miss == 0
+    osc.close()
+
+
+def _fold(x, n):
+    acc = np.float32(0.0)
+    for _ in range(n):
+        acc = np.float32(np.float64(acc) + x / n)
+    return np.float64(acc)
+
+
+def test_oracle_camera_misses_are_the_folded_sky(oracle, tmp_path):
+    W_, H_, N_ = 48, 27, 8
+    env_scenes.floor_scene(str(tmp_path), "up", (0.5, 0.5, 0.5), width=W_, height=H_, look_up=True)
+    osc = oracle.OracleScene(str(tmp_path / "up"))
+    rgb, scale = env_scenes.SKIES["map"]
+    osc.set_environment(rgb, scale)
+    rays = osc.primary_rays()
+    face = osc.trace_closest(rays)[0]
+    assert np.all(face < 0)
+    le = osc.env_eval(rays[:, 3:])
+    assert np.array_equal(_bits(le), _bits(env_ref.EnvRef(rgb, scale).eval(rays[:, 3:])))
+    want = np.array([[_fold(x, N_) for x in row] for row in le]).reshape(H_, W_, 3)
+    for faithful in (False, True):
+        st = oracle.Stats()
+        img = osc.render(N_, seed=4, faithful_cost=faithful, stats=st)
+        assert np.array_equal(_bits(img), _bits(want)), faithful
+        assert st.camera_miss == st.samples == W_ * H_ * N_ and st.shade_calls == 0
+    assert np.array_equal(_bits(osc.sample_radiance(4, 5, 7, 3)), _bits(le[5 * W_ + 7]))
+    osc.close()
