@@ -567,6 +567,52 @@ int  mcpt_render_scene_lens(const char* path, const char* filename, int32_t spp,
 int  mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, int64_t options_bytes,
                            const mcpt_lens*, const char* environment_pfm, double environment_scale, mcpt_stats* stats);
 
+/* ---- geometry and camera updates (since the update change): a second frame of a scene in which something moved, without a new scene ---- */
+/* mcpt_device_update_vertices replaces the positions of every face on a live device: v = [num_faces][9] doubles (v1 v2 v3 of every face,
+ * .obj order).  Only positions change: face count, materials, vn, vt, the lights' materials and radiances and the resolution stay;
+ * Face::norm is derived again as the loader derives it.  After the call the device behaves, in every observable result (closest hits,
+ * frames, mcpt_sample_radiance, AOVs, mcpt_device_get_bvh_nodes, mcpt_device_get_leaf_order), exactly as a device created with the same
+ * build mode from a mcpt_scene_create of the same description with v in place of the old vertices; only the work counters (node_visits,
+ * tri_tests, dom_*) may differ after a refit.  The reference's structures (Morton keys, sort, leaf records, level unions) are built again
+ * on the GPU; the key domain is the fixed cube, or for a scene loaded with MCPT_LOAD_MORTON_BOUNDS the bounds of the new vertices.
+ *   MCPT_UPDATE_REFIT   : the culling hierarchy keeps its topology (child references, triangle slots); every box is recomputed bottom up
+ *                         from the new triangles and quantised again with the builders' rule, the smallest grid exponent that fits.
+ *                         The culling hierarchy only culls, so the frame is that of a fresh build bit for bit, at more or fewer visits.
+ *   MCPT_UPDATE_REBUILD : the hierarchy is built again by the builder the device was created with.
+ * The pre-test records and the light tables (areas, CDFs, the area of lights[0]) follow.  The scene handle is not touched: the device owns
+ * the geometry and camera it changes.  The call is synchronous: it waits for every frame of the device in flight (they finish on the old
+ * geometry) and returns when the device holds the new one.  MCPT_ERR_ARG while a progressive or adaptive handle of the device is alive.
+ * Coordinates are vetted as at creation: NaN, infinities or magnitudes outside [1e-150, 1e150] switch the fast walk off
+ * (fast_enabled = 0, the reference-shaped walk answers); coming back into range switches it on again.  A failure midway leaves the device
+ * refusing to trace or render (MCPT_ERR_ARG, "geometry update failed") until an update succeeds.  The first update makes the faces
+ * resident in .obj order (216 bytes per face) and the first refit of a hierarchy its schedule and exact boxes (52 bytes per node).
+ * cost_before / cost_after: sum over the non-empty child slots of (area of the slot's stored box x (1 for a node, the triangle count for a
+ * leaf)) / the area of the root's box (the union of node 0's stored child boxes), from the decoded planes: the figure to watch to decide
+ * when refits have degraded the hierarchy enough to rebuild.
+ * _device: v is a device pointer; `stream` (may be NULL) is waited for before v is read.  mcpt_device_get_vertices: what the device holds.
+ * mcpt_device_set_camera replaces the camera (width and height stay) for every later frame; the same refusal while a progressive handle
+ * lives.  mcpt_multi_*: the same on every device of the group in turn (info: of devices[0]); the first failure is returned. */
+#define MCPT_UPDATE_REFIT    0   /* keep the culling hierarchy's topology, recompute its boxes on the GPU */
+#define MCPT_UPDATE_REBUILD  1   /* build the culling hierarchy again with the builder the device was created with */
+typedef struct {
+    int32_t mode;            /* what was done: MCPT_UPDATE_* */
+    int32_t fast_enabled;    /* mcpt_fast_info.enabled after the update */
+    int32_t leaves_moved;    /* faces whose reference leaf index changed */
+    int32_t reserved;
+    double  ms_reference;    /* staging, Morton keys, sort, leaf records, level unions */
+    double  ms_hierarchy;    /* refit or rebuild, triangle gather, pre-test records */
+    double  ms_tables;       /* light triangles, areas, CDFs */
+    double  ms_total;
+    double  cost_before, cost_after;
+} mcpt_update_info;
+int mcpt_device_update_vertices(mcpt_device*, const double* v, int32_t mode, mcpt_update_info* info /* may be NULL */);
+int mcpt_device_update_vertices_device(mcpt_device*, const double* d_v, int32_t mode, mcpt_update_info* info, void* stream);
+int mcpt_device_get_vertices(mcpt_device*, double* v);
+int mcpt_device_set_camera(mcpt_device*, const double eye[3], const double look_at[3], const double up[3], double fovy);
+int mcpt_device_get_camera(const mcpt_device*, double eye[3], double look_at[3], double up[3], double* fovy);
+int mcpt_multi_update_vertices(mcpt_multi*, const double* v, int32_t mode, mcpt_update_info* info /* of devices[0]; may be NULL */);
+int mcpt_multi_set_camera(mcpt_multi*, const double eye[3], const double look_at[3], const double up[3], double fovy);
+
 #ifdef __cplusplus
 }
 #endif

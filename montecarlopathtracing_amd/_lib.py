@@ -92,6 +92,16 @@ class FastInfo(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_tris", "enabled", "cw_stack_need", "max_depth", "builder", "clusters", "reserved")]
 
 
+class UpdateInfo(C.Structure):
+    """mcpt_update_info: what a geometry update did and what it took (mcpt_device_update_vertices)"""
+    _fields_ = [("mode", C.c_int32), ("fast_enabled", C.c_int32), ("leaves_moved", C.c_int32), ("reserved", C.c_int32),
+                ("ms_reference", C.c_double), ("ms_hierarchy", C.c_double), ("ms_tables", C.c_double), ("ms_total", C.c_double),
+                ("cost_before", C.c_double), ("cost_after", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class Noise(C.Structure):
     """mcpt_noise: the frame summary of a progressive frame after `done` of `spp` samples"""
     _fields_ = [("done", C.c_int32), ("spp", C.c_int32), ("pixels", C.c_int64), ("rel_error", C.c_double), ("abs_rms", C.c_double),
@@ -124,6 +134,8 @@ EXPORTS = [
     "mcpt_device_set_lens", "mcpt_device_get_lens", "mcpt_camera_rays", "mcpt_multi_set_lens", "mcpt_render_scene_lens",
     "mcpt_device_set_environment", "mcpt_device_get_environment", "mcpt_environment_eval", "mcpt_environment_sample", "mcpt_read_pfm",
     "mcpt_multi_set_environment", "mcpt_render_scene_env",
+    "mcpt_device_update_vertices", "mcpt_device_update_vertices_device", "mcpt_device_get_vertices", "mcpt_device_set_camera",
+    "mcpt_device_get_camera", "mcpt_multi_update_vertices", "mcpt_multi_set_camera",
 ]
 
 
@@ -249,6 +261,13 @@ def lib():
     L.mcpt_multi_set_environment.argtypes = [P, C.POINTER(Environment)]
     L.mcpt_render_scene_env.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens), C.c_char_p,
                                         C.c_double, C.POINTER(Stats)]
+    L.mcpt_device_update_vertices.argtypes = [P, D, C.c_int32, C.POINTER(UpdateInfo)]
+    L.mcpt_device_update_vertices_device.argtypes = [P, P, C.c_int32, C.POINTER(UpdateInfo), P]
+    L.mcpt_device_get_vertices.argtypes = [P, D]
+    L.mcpt_device_set_camera.argtypes = [P, D, D, D, C.c_double]
+    L.mcpt_device_get_camera.argtypes = [P, D, D, D, D]
+    L.mcpt_multi_update_vertices.argtypes = [P, D, C.c_int32, C.POINTER(UpdateInfo)]
+    L.mcpt_multi_set_camera.argtypes = [P, D, D, D, C.c_double]
     _lib = L
     return L
 

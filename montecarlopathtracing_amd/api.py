@@ -1,11 +1,12 @@
 """Python face of libmcpt's C ABI, named after the reference's own functions and types
 (render_scene / scene_data / BVH / ray_intersect / generateImg / imshow)."""
 import ctypes as C
+import numbers
 
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, DenoiseParams, Environment, FastInfo, Lens, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, check, lib
+from ._lib import AdaptiveParams, DenoiseParams, Environment, FastInfo, Lens, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -14,6 +15,7 @@ RENDER_KEEP_STATS, RENDER_PIPELINE = 4, 8
 LOAD_STANDARD_OBJ, LOAD_MTLLIB, LOAD_MORTON_BOUNDS = 1, 2, 4
 OUT_PNG_DEFLATE, OUT_PFM, OUT_ERROR_PFM, OUT_SPP_PFM, OUT_DENOISED, OUT_AOV_PFM = 1, 2, 4, 8, 16, 32
 BUILD_HOST, BUILD_DEVICE, BUILD_DEVICE_FAST, BUILD_DEVICE_SAH = 0, 1, 2, 3
+UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 # mcpt_fast_info.builder: which builder made the culling hierarchy a device walks
 FAST_BUILT_HOST, FAST_BUILT_DEVICE_FAST, FAST_BUILT_DEVICE_PLOC, FAST_BUILT_PLOC_FELL_BACK = 0, 1, 2, 3
 SCENE_DEFER_BUILD = 1
@@ -229,6 +231,32 @@ class Scene:
         return out
 
 
+def _update_mode(mode):
+    if mode in ("refit", UPDATE_REFIT):
+        return UPDATE_REFIT
+    if mode in ("rebuild", UPDATE_REBUILD):
+        return UPDATE_REBUILD
+    raise ValueError("mode must be 'refit' or 'rebuild'")
+
+
+def _host_vertices(v, n_faces):
+    """v as the [n_faces, 9] float64 array mcpt_device_update_vertices reads"""
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if v.size != n_faces * 9:
+        raise ValueError("vertices: %d numbers given, the scene's %d faces need %d" % (v.size, n_faces, n_faces * 9))
+    return v.reshape(n_faces, 9)
+
+
+def _camera_args(eye, look_at, up):
+    out = []
+    for q in (eye, look_at, up):
+        a = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+        if a.shape[0] != 3:
+            raise ValueError("eye, look_at and up are 3-vectors")
+        out.append(a)
+    return out
+
+
 class Device:
     """One MI355X holding a resident copy of a Scene."""
 
@@ -374,6 +402,45 @@ class Device:
         check(lib().mcpt_environment_sample(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), int(depth), n, _p(dirs, C.c_double),
                                             _p(pdf, C.c_double), _p(rgb, C.c_double)))
         return dirs, pdf, rgb
+
+    def update_vertices(self, v, mode="refit", stream=None):
+        """New positions for every face, in place (mcpt_device_update_vertices): v = [num_faces, 9] (v1 v2 v3 of every face, .obj order) as
+        a numpy array, a torch tensor on this GPU (float64, contiguous) or a raw device pointer (int); mode "refit" keeps the culling
+        hierarchy's topology and recomputes its boxes, "rebuild" builds it again.  The frame afterwards is that of a fresh device on the
+        moved scene, bit for bit.  Returns the mcpt_update_info record as a dict."""
+        n = self.scene.info.num_faces
+        info = UpdateInfo()
+        m = _update_mode(mode)
+        if isinstance(v, numbers.Integral):
+            v = int(v)
+            check(lib().mcpt_device_update_vertices_device(self._h, C.c_void_p(v), m, C.byref(info), C.c_void_p(stream) if stream else None))
+        elif hasattr(v, "data_ptr") and getattr(v, "is_cuda", False):
+            if v.numel() != n * 9 or not v.is_contiguous() or str(v.dtype) != "torch.float64":
+                raise ValueError("a device tensor of vertices must be contiguous float64 with %d elements" % (n * 9))
+            check(lib().mcpt_device_update_vertices_device(self._h, C.c_void_p(v.data_ptr()), m, C.byref(info), C.c_void_p(stream) if stream else None))
+        else:
+            if hasattr(v, "detach"):
+                v = v.detach().cpu().numpy()
+            v = _host_vertices(v, n)
+            check(lib().mcpt_device_update_vertices(self._h, _p(v, C.c_double), m, C.byref(info)))
+        return info.as_dict()
+
+    def vertices(self):
+        """the positions the device holds now, [num_faces, 9] in .obj order (mcpt_device_get_vertices)"""
+        v = np.zeros((self.scene.info.num_faces, 9))
+        check(lib().mcpt_device_get_vertices(self._h, _p(v, C.c_double)))
+        return v
+
+    def set_camera(self, eye, look_at, up, fovy):
+        """The camera of every later frame (mcpt_device_set_camera); width and height stay."""
+        e, l, u = _camera_args(eye, look_at, up)
+        check(lib().mcpt_device_set_camera(self._h, _p(e, C.c_double), _p(l, C.c_double), _p(u, C.c_double), float(fovy)))
+
+    def camera(self):
+        """the device's camera as a dict of eye, look_at, up (arrays) and fovy"""
+        e, l, u, f = np.zeros(3), np.zeros(3), np.zeros(3), C.c_double()
+        check(lib().mcpt_device_get_camera(self._h, _p(e, C.c_double), _p(l, C.c_double), _p(u, C.c_double), C.byref(f)))
+        return {"eye": e, "look_at": l, "up": u, "fovy": f.value}
 
     def progressive(self, spp, seed=0, rank=0, world=1, tile_w=0, tile_h=0, flags=0):
         """A frame of `spp` samples per pixel rendered in passes (mcpt_progressive_*): see Progressive."""
@@ -522,6 +589,18 @@ class MultiDevice:
         e, tex = make_environment(rgb, scale)
         check(lib().mcpt_multi_set_environment(self._h, C.byref(e)))
         del tex
+
+    def update_vertices(self, v, mode="refit"):
+        """new positions on every device of the group (Device.update_vertices, host arrays); the info record of devices[0]"""
+        v = _host_vertices(v, self.scene.info.num_faces)
+        info = UpdateInfo()
+        check(lib().mcpt_multi_update_vertices(self._h, _p(v, C.c_double), _update_mode(mode), C.byref(info)))
+        return info.as_dict()
+
+    def set_camera(self, eye, look_at, up, fovy):
+        """the same camera on every device of the group (Device.set_camera)"""
+        e, l, u = _camera_args(eye, look_at, up)
+        check(lib().mcpt_multi_set_camera(self._h, _p(e, C.c_double), _p(l, C.c_double), _p(u, C.c_double), float(fovy)))
 
     def generateImg(self, spp, seed=0, tile_w=0, tile_h=0, flags=0, stats=None):
         img = np.zeros((self.height, self.width, 3))

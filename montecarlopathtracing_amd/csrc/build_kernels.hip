@@ -133,6 +133,22 @@ __global__ void k_fast_keys(const DTri* __restrict__ tris, int t, FastDomain dom
     keys[k] = key; idx[k] = k;
 }
 
+// the wave's largest value into the scene's absmax word (non-negative doubles order like integers); every lane of the wave calls it
+__device__ __forceinline__ void absmax_commit(double am, unsigned long long* __restrict__ absmax_bits)
+{
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) am = fmax(am, __shfl_down(am, off, 64));
+    if ((threadIdx.x & 63) == 0 && am > 0.0) atomicMax(absmax_bits, (unsigned long long)__double_as_longlong(am));
+}
+// largest finite |coordinate| of a triangle on axis a, folded into am; *lo / *hi = its extent
+__device__ __forceinline__ double absmax_axis(const DTri* tr, int a, double am, double* lo, double* hi)
+{
+    *lo = fmin(fmin(tr->v1[a], tr->v2[a]), tr->v3[a]); *hi = fmax(fmax(tr->v1[a], tr->v2[a]), tr->v3[a]);
+    if (isfinite(*lo)) am = fmax(am, fabs(*lo));
+    if (isfinite(*hi)) am = fmax(am, fabs(*hi));
+    return am;
+}
+
 // box of fast leaf g = triangles 4g .. 4g+3 of the sorted copy (each triangle's own box is the reference's, BVH.cpp:87-97)
 __global__ void k_fast_leaf_boxes(const DTri* __restrict__ tris, int t, int per_leaf, int groups, FBox* __restrict__ boxes, unsigned long long* __restrict__ absmax_bits)
 {
@@ -145,17 +161,14 @@ __global__ void k_fast_leaf_boxes(const DTri* __restrict__ tris, int t, int per_
         for (int k = first; k < end; k++) {
             const DTri* tr = tris + k;
             for (int a = 0; a < 3; a++) {
-                const double lo = fmin(fmin(tr->v1[a], tr->v2[a]), tr->v3[a]), hi = fmax(fmax(tr->v1[a], tr->v2[a]), tr->v3[a]);
+                double lo, hi;
+                am = absmax_axis(tr, a, am, &lo, &hi);
                 b.lo[a] = fmin(b.lo[a], lo); b.hi[a] = fmax(b.hi[a], hi);
-                if (isfinite(lo)) am = fmax(am, fabs(lo));
-                if (isfinite(hi)) am = fmax(am, fabs(hi));
             }
         }
         boxes[g] = b;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) am = fmax(am, __shfl_down(am, off, 64));
-    if ((threadIdx.x & 63) == 0 && am > 0.0) atomicMax(absmax_bits, (unsigned long long)__double_as_longlong(am));   // non-negative doubles order like integers
+    absmax_commit(am, absmax_bits);
 }
 
 // One level: node i takes children 4i .. 4i+3 of the level below (nodes, or fast leaves when leaf_level), stores its own exact
@@ -744,6 +757,303 @@ hipError_t device_gather_tris(const DTri* tris, const int32_t* d_slots, int n, D
 {
     if (n > 0) hipLaunchKernelGGL(k_gather_tris, dim3((n + 255) / 256), dim3(256), 0, st, tris, d_slots, n, out);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------- geometry updates (mcpt_device_update_vertices)
+// Face::norm of every face from its new vertices, in the loader's operation order (scene_loader.cpp: push_face)
+__global__ void k_face_normals(const double* __restrict__ v9, int t, double* __restrict__ nrm3)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= t) return;
+    const double* p = v9 + (size_t)i * 9;
+    const V3 v0 = ld3(p), v1 = ld3(p + 3), v2 = ld3(p + 6);
+    const V3 n = normalized(cross(v0 - v1, v2 - v0));
+    nrm3[(size_t)i * 3] = n.x; nrm3[(size_t)i * 3 + 1] = n.y; nrm3[(size_t)i * 3 + 2] = n.z;
+}
+
+hipError_t device_face_normals(const double* v9, int t, double* nrm3, hipStream_t st)
+{
+    if (t > 0) hipLaunchKernelGGL(k_face_normals, dim3((t + 255) / 256), dim3(256), 0, st, v9, t, nrm3);
+    return hipGetLastError();
+}
+
+__global__ void k_tri_faces(const DTri* __restrict__ fast_tris, int n, int32_t* __restrict__ tri_faces)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) tri_faces[i] = fast_tris[i].face;
+}
+hipError_t device_tri_faces(const DTri* fast_tris, int n, int32_t* tri_faces, hipStream_t st)
+{
+    if (n > 0) hipLaunchKernelGGL(k_tri_faces, dim3((n + 255) / 256), dim3(256), 0, st, fast_tris, n, tri_faces);
+    return hipGetLastError();
+}
+
+__global__ void k_leaf_of_face(const int32_t* __restrict__ order, int t, int32_t* __restrict__ leaf_of_face)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= t) return;
+    const int f = order[k];
+    if (f >= 0 && f < t) leaf_of_face[f] = k;
+}
+__global__ void k_refit_slots(const int32_t* __restrict__ tri_faces, int n, int t, const int32_t* __restrict__ leaf_of_face, int32_t* __restrict__ slots)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int f = tri_faces[i];
+    slots[i] = (f >= 0 && f < t) ? leaf_of_face[f] : 0;
+}
+// slots[i] = the reference leaf that now holds the face of triangle slot i (the topology keeps tri_faces; the Morton order has moved)
+hipError_t device_refit_slots(const int32_t* d_order, int t, const int32_t* tri_faces, int n, int32_t* leaf_of_face, int32_t* slots, hipStream_t st)
+{
+    if (t <= 0 || n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_leaf_of_face, dim3((t + 255) / 256), dim3(256), 0, st, d_order, t, leaf_of_face);
+    hipLaunchKernelGGL(k_refit_slots, dim3((n + 255) / 256), dim3(256), 0, st, tri_faces, n, t, leaf_of_face, slots);
+    return hipGetLastError();
+}
+
+// Vetting and bounds of new vertices, as device creation takes them on the host: *bad is set when a coordinate is neither zero nor
+// within [1e-150, 1e150] in magnitude (NaN and infinities are not); lo / hi per axis start at +-1e300 and a NaN passes neither
+// comparison.  Doubles are reduced through keys that order like the numbers (sign bit flipped; negative numbers inverted).
+__device__ __forceinline__ unsigned long long order_key(double x)
+{
+    const unsigned long long b = (unsigned long long)__double_as_longlong(x);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__global__ void k_vet_bounds(const double* __restrict__ v9, int t, unsigned long long* __restrict__ lohi /* [6] keys */, int32_t* __restrict__ bad)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    int b = 0;
+    if (i < t) {
+        const double* p = v9 + (size_t)i * 9;
+        for (int k = 0; k < 9; k++) {
+            const double q = p[k], m = fabs(q);
+            const int a = k % 3;
+            if (!(m == 0.0 || (m >= 1e-150 && m <= 1e150))) b = 1;
+            if (q < lo[a]) lo[a] = q;
+            if (q > hi[a]) hi[a] = q;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        b |= __shfl_down(b, off, 64);
+        for (int a = 0; a < 3; a++) {
+            const double l = __shfl_down(lo[a], off, 64), h = __shfl_down(hi[a], off, 64);
+            if (l < lo[a]) lo[a] = l;
+            if (h > hi[a]) hi[a] = h;
+        }
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (b) atomicOr(bad, 1);
+        for (int a = 0; a < 3; a++) { atomicMin(lohi + a, order_key(lo[a])); atomicMax(lohi + 3 + a, order_key(hi[a])); }
+    }
+}
+hipError_t device_vet_bounds(const double* v9, int t, bool* coords_ok, double lo[3], double hi[3], hipStream_t st)
+{
+    auto key = [](double x) { unsigned long long b; std::memcpy(&b, &x, 8); return (b >> 63) ? ~b : (b | 0x8000000000000000ull); };
+    auto unkey = [](unsigned long long k) { const unsigned long long b = (k >> 63) ? (k & 0x7fffffffffffffffull) : ~k; double x; std::memcpy(&x, &b, 8); return x; };
+    unsigned long long h[7];
+    for (int a = 0; a < 3; a++) { h[a] = key(1e300); h[3 + a] = key(-1e300); }
+    h[6] = 0;                                                               // the flag word
+    DevBuf<unsigned long long> w;
+    BK_TRY(w.alloc(7));
+    BK_TRY(hipMemcpy(w.get(), h, sizeof h, hipMemcpyHostToDevice));
+    if (t > 0) hipLaunchKernelGGL(k_vet_bounds, dim3((t + 255) / 256), dim3(256), 0, st, v9, t, w.get(), reinterpret_cast<int32_t*>(w.get() + 6));
+    BK_TRY(hipGetLastError());
+    BK_TRY(hipStreamSynchronize(st));
+    BK_TRY(hipMemcpy(h, w.get(), sizeof h, hipMemcpyDeviceToHost));
+    for (int a = 0; a < 3; a++) { lo[a] = unkey(h[a]); hi[a] = unkey(h[3 + a]); }
+    *coords_ok = (h[6] & 0xffffffffull) == 0;
+    return hipSuccess;
+}
+
+// out[i][9] = the vertices of face faces[i] (the emitter faces, for the light tables)
+__global__ void k_gather_faces(const double* __restrict__ v9, int t, const int32_t* __restrict__ faces, int n, double* __restrict__ out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int f = faces[i];
+    for (int k = 0; k < 9; k++) out[(size_t)i * 9 + k] = (f >= 0 && f < t) ? v9[(size_t)f * 9 + k] : 0.0;
+}
+hipError_t device_gather_faces(const double* v9, int t, const int32_t* faces, int n, double* out, hipStream_t st)
+{
+    if (n > 0) hipLaunchKernelGGL(k_gather_faces, dim3((n + 255) / 256), dim3(256), 0, st, v9, t, faces, n, out);
+    return hipGetLastError();
+}
+
+// wave sums of a flag into one counter (a count: the order of the additions cannot change it)
+__global__ void k_count_differing(const int32_t* __restrict__ a, const int32_t* __restrict__ b, int n, int32_t* __restrict__ count)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    int c = (i < n && a[i] != b[i]) ? 1 : 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(count, c);
+}
+hipError_t device_count_differing(const int32_t* a, const int32_t* b, int n, int32_t* d_count, hipStream_t st)
+{
+    BK_TRY(hipMemsetAsync(d_count, 0, sizeof(int32_t), st));
+    if (n > 0) hipLaunchKernelGGL(k_count_differing, dim3((n + 255) / 256), dim3(256), 0, st, a, b, n, d_count);
+    return hipGetLastError();
+}
+
+// One level of a refit, one thread per node, deepest level first (a child is always one level below its parent, so every inner
+// child's exact box is in `box` from the launch before).  The node keeps child[] and nchild; a leaf slot's box is the exact union of
+// its triangles' boxes, an inner slot's the child node's own exact box; the node's own box goes to `box` for the level above, and its
+// planes are quantised again with the builders' rule (k_fast_level).  The exponent search starts below any exponent that can pass
+// (255 * 2^e >= ext needs e > ilogb(ext) - 9) and steps up, so the smallest passing exponent is found whatever log2 would round to.
+__global__ void k_refit_level(CwNode* __restrict__ nodes, int n_nodes, const int32_t* __restrict__ sched, int first, int count, const DTri* __restrict__ tris, int n_tris,
+                              FBox* __restrict__ box)
+{
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= count) return;
+    const int i = sched[first + j];
+    if (i < 0 || i >= n_nodes) return;
+    CwNode nd = nodes[i];
+    FBox kid[4];
+    bool has[4];
+    FBox own;
+    for (int a = 0; a < 3; a++) { own.lo[a] = __builtin_inf(); own.hi[a] = -__builtin_inf(); }
+    for (int c = 0; c < 4; c++) {
+        const int32_t r = nd.child[c];
+        has[c] = false;
+        if (r == (int32_t)0x80000000) continue;                                // MCPT_FAST_EMPTY
+        FBox b;
+        if (r >= 0) {
+            if (r >= n_nodes) continue;
+            b = box[r];
+        } else {
+            const int ref = -1 - r;
+            int k0 = ref >> 4, k1 = k0 + (ref & 15) + 1;
+            if (k0 < 0 || k0 >= n_tris) continue;
+            k1 = k1 < n_tris ? k1 : n_tris;
+            for (int a = 0; a < 3; a++) { b.lo[a] = __builtin_inf(); b.hi[a] = -__builtin_inf(); }
+            for (int k = k0; k < k1; k++) {
+                const DTri* tr = tris + k;
+                for (int a = 0; a < 3; a++) {
+                    b.lo[a] = fmin(b.lo[a], fmin(fmin(tr->v1[a], tr->v2[a]), tr->v3[a]));
+                    b.hi[a] = fmax(b.hi[a], fmax(fmax(tr->v1[a], tr->v2[a]), tr->v3[a]));
+                }
+            }
+        }
+        kid[c] = b; has[c] = true;
+        for (int a = 0; a < 3; a++) { own.lo[a] = fmin(own.lo[a], b.lo[a]); own.hi[a] = fmax(own.hi[a], b.hi[a]); }
+    }
+    box[i] = own;
+    for (int a = 0; a < 3; a++) {
+        const float pf = __double2float_rd(own.lo[a]);
+        const double p = (double)pf;
+        int e = -126;
+        const double ext = own.hi[a] - p;
+        if (ext > 0) { const int lowest = ilogb(ext); e = lowest > 127 + 9 ? 127 : (lowest - 9 > -126 ? lowest - 9 : -126); }
+        uint32_t wlo = 0, whi = 0;
+        for (;; e++) {
+            const double sc = ldexp(1.0, e);
+            bool ok = p + 255.0 * sc >= own.hi[a];
+            wlo = 0; whi = 0;
+            for (int c = 0; ok && c < 4; c++) {
+                if (!has[c]) continue;
+                double ql = floor((kid[c].lo[a] - p) / sc), qh = ceil((kid[c].hi[a] - p) / sc);
+                ql = fmin(fmax(ql, 0.0), 255.0); qh = fmin(fmax(qh, 0.0), 255.0);
+                while (ql > 0 && p + ql * sc > kid[c].lo[a]) ql -= 1;
+                while (qh < 255 && p + qh * sc < kid[c].hi[a]) qh += 1;
+                if (p + ql * sc > kid[c].lo[a] || p + qh * sc < kid[c].hi[a]) ok = false;
+                wlo |= (uint32_t)ql << (8 * c); whi |= (uint32_t)qh << (8 * c);
+            }
+            if (ok || e >= 127) break;          // (non-finite boxes: the fast walk is off for such a scene)
+        }
+        nd.p[a] = pf; nd.e[a] = (int8_t)e; nd.qlo[a] = wlo; nd.qhi[a] = whi;
+    }
+    nodes[i] = nd;
+}
+
+hipError_t device_refit_levels(CwNode* nodes, int n_nodes, const int32_t* sched, const int* level_first, int n_levels, const DTri* fast_tris, int n_tris, double* node_box,
+                               hipStream_t st)
+{
+    static_assert(sizeof(FBox) == 6 * sizeof(double), "the side array is six doubles per node");
+    for (int l = n_levels - 1; l >= 0; l--) {
+        const int first = level_first[l], count = level_first[l + 1] - first;
+        if (count > 0)
+            hipLaunchKernelGGL(k_refit_level, dim3((count + 127) / 128), dim3(128), 0, st, nodes, n_nodes, sched, first, count, fast_tris, n_tris,
+                               reinterpret_cast<FBox*>(node_box));
+    }
+    return hipGetLastError();
+}
+
+// largest finite |coordinate| of the triangle slots: k_fast_leaf_boxes' reduction without the boxes
+__global__ void k_tris_absmax(const DTri* __restrict__ tris, int n, unsigned long long* __restrict__ absmax_bits)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    double am = 0.0;
+    if (k < n) {
+        const DTri* tr = tris + k;
+        double lo, hi;
+        for (int a = 0; a < 3; a++) am = absmax_axis(tr, a, am, &lo, &hi);
+    }
+    absmax_commit(am, absmax_bits);
+}
+hipError_t device_tris_absmax(const DTri* fast_tris, int n, double* absmax, hipStream_t st)
+{
+    *absmax = 0;
+    DevBuf<unsigned long long> am;
+    BK_TRY(am.alloc(1));
+    BK_TRY(hipMemsetAsync(am.get(), 0, sizeof(unsigned long long), st));
+    if (n > 0) hipLaunchKernelGGL(k_tris_absmax, dim3((n + 255) / 256), dim3(256), 0, st, fast_tris, n, am.get());
+    BK_TRY(hipGetLastError());
+    BK_TRY(hipStreamSynchronize(st));
+    unsigned long long bits = 0;
+    BK_TRY(hipMemcpy(&bits, am.get(), sizeof bits, hipMemcpyDeviceToHost));
+    std::memcpy(absmax, &bits, sizeof bits);
+    return hipSuccess;
+}
+
+// The cost figure's numerator: over every non-empty child slot, the stored box's area dx dy + dy dz + dz dx from the decoded planes
+// p + q 2^e (evaluated in fp64) times 1 for a node and the triangle count for a leaf.  One partial sum per block, folded in a fixed
+// order; the host adds the partials in order.
+__global__ void k_cost_partials(const CwNode* __restrict__ nodes, int n, double* __restrict__ partial)
+{
+    __shared__ double sh[256];
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    double s = 0.0;
+    if (i < n) {
+        const CwNode nd = nodes[i];
+        for (int c = 0; c < 4; c++) {
+            const int32_t r = nd.child[c];
+            if (r == (int32_t)0x80000000) continue;
+            double d[3];
+            for (int a = 0; a < 3; a++) {
+                const double p = (double)nd.p[a], sc = ldexp(1.0, (int)nd.e[a]);
+                const double lo = p + (double)((nd.qlo[a] >> (8 * c)) & 255u) * sc, hi = p + (double)((nd.qhi[a] >> (8 * c)) & 255u) * sc;
+                d[a] = hi - lo;
+            }
+            const double area = d[0] * d[1] + d[1] * d[2] + d[2] * d[0];
+            s += area * (r >= 0 ? 1.0 : (double)(((-1 - r) & 15) + 1));
+        }
+    }
+    sh[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) sh[threadIdx.x] += sh[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = sh[0];
+}
+hipError_t device_cost_sum(const CwNode* nodes, int n_nodes, double* sum, hipStream_t st)
+{
+    *sum = 0;
+    if (n_nodes <= 0) return hipSuccess;
+    const int blocks = (n_nodes + 255) / 256;
+    DevBuf<double> part;
+    BK_TRY(part.alloc(size_t(blocks)));
+    hipLaunchKernelGGL(k_cost_partials, dim3(blocks), dim3(256), 0, st, nodes, n_nodes, part.get());
+    BK_TRY(hipGetLastError());
+    BK_TRY(hipStreamSynchronize(st));
+    std::vector<double> h(static_cast<size_t>(blocks));
+    BK_TRY(hipMemcpy(h.data(), part.get(), size_t(blocks) * sizeof(double), hipMemcpyDeviceToHost));
+    double s = 0;
+    for (double q : h) s += q;
+    *sum = s;
+    return hipSuccess;
 }
 
 }  // namespace mcpt

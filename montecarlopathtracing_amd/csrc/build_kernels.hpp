@@ -46,4 +46,27 @@ hipError_t device_gather_tris(const DTri* tris, const int32_t* d_slots, int n, D
 // the pre-test's fp32 record of every slot of the fast triangle array (absmax = largest |coordinate| of the scene)
 hipError_t device_build_pre(const DTri* fast_tris, int n, double absmax, DTriPre* out, hipStream_t st);
 
+// ---- geometry updates (update.cpp)
+// nrm3[t][3] = Face::norm of the faces v9[t][9], in the loader's operation order
+hipError_t device_face_normals(const double* v9, int t, double* nrm3, hipStream_t st);
+// tri_faces[i] = .obj face of triangle slot i
+hipError_t device_tri_faces(const DTri* fast_tris, int n, int32_t* tri_faces, hipStream_t st);
+// leaf_of_face[t] scattered from d_order, then slots[i] = leaf_of_face[tri_faces[i]]: what device_gather_tris refills the slots from
+hipError_t device_refit_slots(const int32_t* d_order, int t, const int32_t* tri_faces, int n, int32_t* leaf_of_face, int32_t* slots, hipStream_t st);
+// the vetting and the bounds of the vertices v9[t][9] as device creation takes them (synchronises st)
+hipError_t device_vet_bounds(const double* v9, int t, bool* coords_ok, double lo[3], double hi[3], hipStream_t st);
+// out[n][9] = the vertices of the faces faces[n]
+hipError_t device_gather_faces(const double* v9, int t, const int32_t* faces, int n, double* out, hipStream_t st);
+// *d_count = number of i with a[i] != b[i]
+hipError_t device_count_differing(const int32_t* a, const int32_t* b, int n, int32_t* d_count, hipStream_t st);
+// Refit of the hierarchy over the refilled triangle slots: topology kept, every node's planes quantised again around the exact boxes
+// below it.  sched = the nodes grouped by depth (level l: sched[level_first[l] .. level_first[l+1])), one launch per level from the
+// deepest up; node_box = 6 doubles per node (lo[3], hi[3]), the nodes' own exact boxes.
+hipError_t device_refit_levels(CwNode* nodes, int n_nodes, const int32_t* sched, const int* level_first, int n_levels, const DTri* fast_tris, int n_tris, double* node_box,
+                               hipStream_t st);
+// largest finite |coordinate| of the triangle slots (synchronises st)
+hipError_t device_tris_absmax(const DTri* fast_tris, int n, double* absmax, hipStream_t st);
+// sum over the non-empty child slots of (area of the stored box) x (1 for a node, triangle count for a leaf) (synchronises st)
+hipError_t device_cost_sum(const CwNode* nodes, int n_nodes, double* sum, hipStream_t st);
+
 }  // namespace mcpt

@@ -8,6 +8,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -16,6 +17,11 @@
 #include "handles.hpp"
 
 using namespace mcpt;
+
+int geometry_gate(const mcpt_device* d)
+{
+    return d->geometry_failed ? fail(MCPT_ERR_ARG, "geometry update failed: the device renders again after an update that succeeds") : MCPT_OK;
+}
 
 extern "C" {
 
@@ -33,6 +39,8 @@ int mcpt_device_create(const mcpt_scene* h, int32_t ordinal, mcpt_device** out)
 {
     return mcpt_device_create_ex(h, ordinal, (h && !h->s.accel_built) ? MCPT_BUILD_DEVICE : MCPT_BUILD_HOST, out);
 }
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ device creation, stage by stage
 // Each stage writes into d and returns an MCPT_* code.  Whatever it allocates is in a d-> field by the time it returns, so the
@@ -237,7 +245,38 @@ static int build_hierarchy_on_device(mcpt_device* d, const double lo[3], const d
 }
 
 // The fast walk's culling hierarchy: fills d->cw_nodes, d->fast_tris and d->fast_info; *absmax = largest |coordinate| of the scene
-static int create_hierarchy(mcpt_device* d, const mcpt_scene* h, int32_t build_mode, const std::vector<int32_t>& order, const CreateClock& clock, double* absmax)
+int build_culling_hierarchy(mcpt_device* d, bool coords_ok, const double lo[3], const double hi[3],
+                            const std::function<std::shared_ptr<const FastBvh>()>& host_bvh, bool talk, double* absmax)
+{
+    const CreateClock clock{talk, std::chrono::steady_clock::now()};
+    const int32_t build_mode = d->build_mode;
+    mcpt_fast_info& fi = d->fast_info;
+    if (build_mode == MCPT_BUILD_DEVICE_FAST || build_mode == MCPT_BUILD_DEVICE_SAH) {
+        if (const int rc = build_hierarchy_on_device(d, lo, hi, build_mode == MCPT_BUILD_DEVICE_SAH, clock, absmax)) return rc;
+    } else {
+        // the SAH hierarchy built on the host from the leaf order (accel_build.cpp, shared by every device of the scene), its
+        // permuted triangle copy gathered on the GPU
+        const std::shared_ptr<const FastBvh> fb = host_bvh();
+        if (!fb) return fail(MCPT_ERR_HIP, "culling hierarchy on the host: the faces could not be read");
+        clock.lap("culling hierarchy on the host");
+        DevBuf<int32_t> d_slots;
+        HIP_TRY(d->cw_nodes.upload(fb->cw));
+        HIP_TRY(d_slots.upload(fb->leaf_tris));
+        hipError_t e = d->fast_tris.alloc(fb->leaf_tris.size());
+        if (e == hipSuccess) e = device_gather_tris(d->tris.get(), d_slots.get(), int(fb->leaf_tris.size()), d->fast_tris.get(), d->stream.get());
+        if (e == hipSuccess) e = hipStreamSynchronize(d->stream.get());
+        if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("fast triangle gather: ") + hipGetErrorString(e));
+        fi.builder = MCPT_FAST_BUILT_HOST;
+        fi.n_nodes = int32_t(fb->cw.size()); fi.n_tris = int32_t(fb->leaf_tris.size());
+        fi.max_depth = fb->max_depth; fi.cw_stack_need = fb->cw_stack_need;
+        *absmax = fb->scene_absmax;
+    }
+    fi.enabled = fast_walk_enabled(fi, coords_ok, *absmax) ? 1 : 0;
+    return MCPT_OK;
+}
+
+// ... of the scene the device is created from
+static int create_hierarchy(mcpt_device* d, const mcpt_scene* h, const std::vector<int32_t>& order, const CreateClock& clock, double* absmax)
 {
     // one pass over the faces: the scene's bounds, which the GPU builders sort on (a NaN coordinate passes neither comparison), and
     // whether every coordinate is zero or within [1e-150, 1e150], as the fast walk needs (NaN and infinities are not)
@@ -253,28 +292,7 @@ static int create_hierarchy(mcpt_device* d, const mcpt_scene* h, int32_t build_m
                 if (q[a] > hi[a]) hi[a] = q[a];
             }
         }
-    mcpt_fast_info& fi = d->fast_info;
-    if (build_mode == MCPT_BUILD_DEVICE_FAST || build_mode == MCPT_BUILD_DEVICE_SAH) {
-        if (const int rc = build_hierarchy_on_device(d, lo, hi, build_mode == MCPT_BUILD_DEVICE_SAH, clock, absmax)) return rc;
-    } else {
-        // the SAH hierarchy built on the host from the leaf order (accel_build.cpp, shared by every device of the scene), its
-        // permuted triangle copy gathered on the GPU
-        const std::shared_ptr<const FastBvh> fb = shared_fast_bvh(h, order, d->knobs);
-        clock.lap("culling hierarchy on the host");
-        DevBuf<int32_t> d_slots;
-        HIP_TRY(d->cw_nodes.upload(fb->cw));
-        HIP_TRY(d_slots.upload(fb->leaf_tris));
-        hipError_t e = d->fast_tris.alloc(fb->leaf_tris.size());
-        if (e == hipSuccess) e = device_gather_tris(d->tris.get(), d_slots.get(), int(fb->leaf_tris.size()), d->fast_tris.get(), d->stream.get());
-        if (e == hipSuccess) e = hipStreamSynchronize(d->stream.get());
-        if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("fast triangle gather: ") + hipGetErrorString(e));
-        fi.builder = MCPT_FAST_BUILT_HOST;
-        fi.n_nodes = int32_t(fb->cw.size()); fi.n_tris = int32_t(fb->leaf_tris.size());
-        fi.max_depth = fb->max_depth; fi.cw_stack_need = fb->cw_stack_need;
-        *absmax = fb->scene_absmax;
-    }
-    fi.enabled = (coords_ok && fi.max_depth < kFastMaxDepth && fi.cw_stack_need < kFastMaxDepth && *absmax >= 1e-15 && *absmax <= 1e15) ? 1 : 0;
-    return MCPT_OK;
+    return build_culling_hierarchy(d, coords_ok, lo, hi, [&]() { return shared_fast_bvh(h, order, d->knobs); }, clock.talk, absmax);
 }
 
 // The pre-test pays where the walk is bound by instruction issue, i.e. where nodes and triangles come out of L1 / L2 / the 256-MB
@@ -282,7 +300,7 @@ static int create_hierarchy(mcpt_device* d, const mcpt_scene* h, int32_t build_m
 // 10 M-triangle scene the walk waits for memory, and a second dependent fetch per leaf (48-B record, then the 128-B record of a
 // survivor) costs more than the skipped arithmetic saves: 6.90 vs 6.44 ms per launch.  So: records only for scenes of at most
 // MCPT_PRE_TEST_MAX_TRIS triangles (default 2^20: ~200 B per triangle of nodes, records and triangles stay cache-resident).
-static int create_pre_test(mcpt_device* d, double absmax)
+int create_pre_test(mcpt_device* d, double absmax)
 {
     if (d->bi.t > d->knobs.pre_test_max_tris) return MCPT_OK;
     // fp32 records of the triangle phase's pre-test, one per slot of the fast triangle array
@@ -353,6 +371,7 @@ static int create_dscene(mcpt_device* d, const Scene& s, double absmax)
     // (any prefix of the node array may be mirrored; the host builder puts the top of the tree there)
     S.fast.cached = int32_t(std::min<size_t>(size_t(d->fast_info.n_nodes), size_t(kFastTopNodes)));
     if (K.node_cache >= 0 && K.node_cache < S.fast.cached) S.fast.cached = K.node_cache;
+    d->cam_eye = s.eye; d->cam_look_at = s.look_at; d->cam_up = s.up; d->cam_fovy = s.fovy;
     const CameraFrame cf = camera_frame(s);
     put3(S.cam.eye, cf.eye); put3(S.cam.start_point, cf.start_point); put3(S.cam.pdx, cf.screen_pdx); put3(S.cam.pdy, cf.screen_pdy);
     S.cam.width = s.width; S.cam.height = s.height;
@@ -360,6 +379,8 @@ static int create_dscene(mcpt_device* d, const Scene& s, double absmax)
     HIP_TRY(d->dirs.alloc(size_t(s.width) * s.height * 3));
     return MCPT_OK;
 }
+
+extern "C" {
 
 int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mode, mcpt_device** out)
 {
@@ -376,6 +397,7 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
     HIP_TRY(hipSetDevice(ordinal));
     std::unique_ptr<mcpt_device, void (*)(mcpt_device*)> d(new mcpt_device, mcpt_device_free);
     d->ordinal = ordinal;
+    d->build_mode = build_mode;
     d->knobs = read_knobs();
     HIP_TRY(create(d->stream, hipStreamCreateWithFlags, hipStreamNonBlocking));
     for (auto& e : d->ev) HIP_TRY(create(e, hipEventCreate));
@@ -390,7 +412,7 @@ int mcpt_device_create_ex(const mcpt_scene* h, int32_t ordinal, int32_t build_mo
     double absmax = 0;                              // largest |coordinate| of the scene, as the hierarchy's builder found it
     int rc;
     if ((rc = create_reference(d.get(), s, build_mode, clock, order)) || (rc = create_materials_and_lights(d.get(), s)) ||
-        (rc = create_hierarchy(d.get(), h, build_mode, order, clock, &absmax)) || (rc = create_pre_test(d.get(), absmax)))
+        (rc = create_hierarchy(d.get(), h, order, clock, &absmax)) || (rc = create_pre_test(d.get(), absmax)))
         return rc;
     clock.lap("culling hierarchy in HBM");
     if ((rc = create_workspaces(d.get(), s)) || (rc = create_dscene(d.get(), s, absmax))) return rc;
@@ -463,6 +485,7 @@ int mcpt_trace_closest_device(mcpt_device* d, const double* d_rays, int64_t n, i
     if (!d || (n > 0 && !d_rays) || n < 0) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(d->ordinal));
     if (!d_face || !d_t || !d_p) return fail(MCPT_ERR_ARG, "d_face, d_t and d_p are required by the device form");
+    if (const int rc = geometry_gate(d)) return rc;
     launch_trace_closest(d->ds, d->trace_mode == MCPT_TRACE_FAST, d_rays, n, d_face, d_t, d_p, d_pn, d->aux_ctr.get(), d->aux_queue.get(), d->aux_slow_list.get(), d->slow_cap,
                          static_cast<hipStream_t>(stream), d->cfg);
     HIP_TRY(hipGetLastError());
@@ -473,6 +496,7 @@ int mcpt_trace_closest(mcpt_device* d, const double* rays, int64_t n, int32_t* f
 {
     if (!d || (n > 0 && !rays) || n < 0) return fail(MCPT_ERR_ARG, "bad argument");
     if (stats) std::memset(stats, 0, sizeof *stats);
+    if (const int rc = geometry_gate(d)) return rc;
     if (n == 0) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
     DevBuf<double> d_rays, d_t, d_p, d_pn;

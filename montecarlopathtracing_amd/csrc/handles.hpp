@@ -122,6 +122,29 @@ struct mcpt_device {
     // Shared ownership, as a device holds its scene: the caller's handle and every progressive frame created on the device hold one
     // reference each; the device goes with the last of mcpt_device_free / mcpt_progressive_free.
     std::atomic<int> refs{1};
+    // The camera the device renders from (create_dscene takes the scene's; mcpt_device_set_camera replaces it) and what geometry updates
+    // need (update.cpp).  `upd` is made by the first mcpt_device_update_vertices: a device that is never updated holds none of it.
+    mcpt::Vec3 cam_eye, cam_look_at, cam_up;
+    double cam_fovy = 0;
+    int32_t build_mode = MCPT_BUILD_HOST;
+    struct Update {
+        mcpt::DevBuf<double> v9, vn9, vt6, nrm3;        // the faces in .obj order: 216 B per face with the materials
+        mcpt::DevBuf<int32_t> mat;
+        mcpt::DevBuf<int32_t> leaf_of_face, slots, old_order, moved;
+        // of the current culling hierarchy, made by the first refit of it and dropped by a rebuild:
+        mcpt::DevBuf<int32_t> tri_faces;                // triangle slot -> .obj face
+        mcpt::DevBuf<int32_t> sched;                    // the nodes grouped by depth
+        std::vector<int> level_first;                   // level l = sched[level_first[l] .. level_first[l + 1])
+        mcpt::DevBuf<double> node_box;                  // the nodes' exact boxes, 48 B per node
+        std::vector<double> light_v;                    // the emitter faces' vertices the light tables were last made from
+        mcpt::DevBuf<int32_t> light_faces;              // the emitter faces, light by light in material face order
+        mcpt::DevBuf<double> light_buf;                 // their vertices, gathered on the GPU
+        int n_light_faces = 0;
+        double cost = -1;                               // the hierarchy's cost figure after the last update (< 0: not computed yet)
+        float morton_lo[3], morton_span[3];
+    };
+    std::unique_ptr<Update> upd;
+    bool geometry_failed = false;                   // an update failed midway: nothing is traced or rendered until one succeeds
 };
 
 // The helpers below are the library's own: none of them is exported from libmcpt.so.
@@ -142,6 +165,22 @@ struct TileShape { int tw, th, rank, world; };
 int tile_shape(const mcpt_render_params* p, TileShape& t);
 // the pixels (y * W + x, in scan order) that p's rank owns in a W x H frame; MCPT_ERR_ARG as tile_shape
 int owned_pixels(int W, int H, const mcpt_render_params* p, std::vector<int32_t>& out);
+
+// the host's SAH hierarchy over `faces` in leaf order `order`, private to the caller (MCPT_UPDATE_REBUILD: the scene's cache stays as it is)
+std::shared_ptr<const mcpt::FastBvh> private_fast_bvh(const std::vector<mcpt::FaceRec>& faces, const std::vector<int32_t>& order, const mcpt::Knobs& k);
+
+// ---- device.cpp
+// MCPT_ERR_ARG while the device's last geometry update has failed midway
+int geometry_gate(const mcpt_device* d);
+// The fast walk's culling hierarchy of d's reference structures with d's builder: fills d->cw_nodes, d->fast_tris and d->fast_info.
+// coords_ok / lo / hi: the vetting and the bounds of the coordinates; host_bvh: the host builder's tree (asked for by the host modes only).
+int build_culling_hierarchy(mcpt_device* d, bool coords_ok, const double lo[3], const double hi[3],
+                            const std::function<std::shared_ptr<const mcpt::FastBvh>()>& host_bvh, bool talk, double* absmax);
+int create_pre_test(mcpt_device* d, double absmax);
+inline bool fast_walk_enabled(const mcpt_fast_info& fi, bool coords_ok, double absmax)
+{
+    return coords_ok && fi.max_depth < mcpt::kFastMaxDepth && fi.cw_stack_need < mcpt::kFastMaxDepth && absmax >= 1e-15 && absmax <= 1e15;
+}
 
 // ---- environment.cpp
 int env_check(const mcpt_environment* e);

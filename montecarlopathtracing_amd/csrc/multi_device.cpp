@@ -212,6 +212,23 @@ int mcpt_multi_set_environment(mcpt_multi* m, const mcpt_environment* e)
     return MCPT_OK;
 }
 
+// the same geometry on every GPU of the group, one device after the other (a device that fails refuses to render until an update succeeds)
+int mcpt_multi_update_vertices(mcpt_multi* m, const double* v, int32_t mode, mcpt_update_info* info)
+{
+    if (!m) return mcpt_device_update_vertices(nullptr, v, mode, info);       // the device entry point's refusal of a null handle
+    for (size_t i = 0; i < m->ranks.size(); i++)
+        if (const int rc = mcpt_device_update_vertices(m->ranks[i].dev, v, mode, i == 0 ? info : nullptr)) return rc;
+    return MCPT_OK;
+}
+
+int mcpt_multi_set_camera(mcpt_multi* m, const double eye[3], const double look_at[3], const double up[3], double fovy)
+{
+    if (!m) return mcpt_device_set_camera(nullptr, eye, look_at, up, fovy);
+    for (Rank& r : m->ranks)
+        if (const int rc = mcpt_device_set_camera(r.dev, eye, look_at, up, fovy)) return rc;
+    return MCPT_OK;
+}
+
 int mcpt_multi_create(const mcpt_scene* scene, const int32_t* devices, int32_t num_devices, int32_t build_mode, int32_t gather, mcpt_multi** out)
 {
     if (!scene || !out) return fail(MCPT_ERR_ARG, "null argument");

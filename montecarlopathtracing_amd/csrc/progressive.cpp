@@ -82,6 +82,7 @@ static int progressive_create(mcpt_device* d, const mcpt_render_params* p, const
 {
     if (p->flags & (MCPT_RENDER_PIPELINE | MCPT_RENDER_KEEP_STATS))
         return fail(MCPT_ERR_ARG, "a progressive frame takes neither MCPT_RENDER_PIPELINE nor MCPT_RENDER_KEEP_STATS");
+    if (const int rc = geometry_gate(d)) return rc;
     std::vector<int32_t> v;
     if (const int rc = owned_pixels(d->width, d->height, p, v)) return rc;
     HIP_TRY(hipSetDevice(d->ordinal));

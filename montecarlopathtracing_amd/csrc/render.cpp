@@ -51,8 +51,7 @@ static int ensure_pos(mcpt_device* d, hipStream_t st)
 static DLens lens_for(const mcpt_device* d, const mcpt_lens& l)
 {
     DLens c{};
-    const Scene& s = d->scene->s;
-    const Vec3 up = normalized(s.up), dir = s.look_at - s.eye;
+    const Vec3 up = normalized(d->cam_up), dir = d->cam_look_at - d->cam_eye;
     const Vec3 x = normalized(cross(dir, up));
     const double len = norm(dir);
     const double F = l.focus_distance > 0.0 ? l.focus_distance : len;
@@ -471,6 +470,7 @@ extern "C" {
 int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, void* stream)
 {
     if (!d || !p || !d_img || p->spp <= 0) return fail(MCPT_ERR_ARG, "bad argument");
+    if (const int rc = geometry_gate(d)) return rc;
     HIP_TRY(hipSetDevice(d->ordinal));
     if (stats) std::memset(stats, 0, sizeof *stats);
     // a frame that fails half-way must not leave half-recorded event pairs behind: mcpt_device_collect_stats would trip over them
@@ -537,6 +537,7 @@ int mcpt_render(mcpt_device* d, const mcpt_render_params* p, double* img, mcpt_s
 int mcpt_sample_radiance(mcpt_device* d, uint64_t seed, const int32_t* pix, const int32_t* k, int64_t n, double* rgb)
 {
     if (!d || !pix || !k || !rgb || n < 0) return fail(MCPT_ERR_ARG, "bad argument");
+    if (const int rc = geometry_gate(d)) return rc;
     return pair_call(d, pix, k, n, rgb, 3, ensure_dirs, [&](const int32_t* d_pix, const int32_t* d_k, double* d_rgb, hipStream_t st) {
         if (lens_active(d->lens)) {
             if (const int rc = ensure_pos(d, st)) return rc;

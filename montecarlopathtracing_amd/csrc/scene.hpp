@@ -70,6 +70,7 @@ struct Scene {
     std::vector<int32_t> node_level, node_leaf;
     float morton_lo[3] = {-1.0f, -1.0f, -1.0f};   // Morton domain: the reference's fixed [-1,4]^3 (morton code.h:6-7) unless
     float morton_span[3] = {5.0f, 5.0f, 5.0f};    // the scene was loaded with MCPT_LOAD_MORTON_BOUNDS
+    bool morton_bounds = false;           // loaded with MCPT_LOAD_MORTON_BOUNDS: a geometry update derives the domain again
     double area0 = 0;                     // total area of lights[0] (Q1)
     bool accel_built = false;             // false: Morton sort + BVH are left to the device (mcpt_device_create_ex)
 };

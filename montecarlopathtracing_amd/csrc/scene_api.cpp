@@ -43,6 +43,13 @@ std::shared_ptr<const FastBvh> shared_fast_bvh(const mcpt_scene* h, const std::v
     return h->fast_cached;
 }
 
+std::shared_ptr<const FastBvh> private_fast_bvh(const std::vector<FaceRec>& faces, const std::vector<int32_t>& order, const Knobs& k)
+{
+    auto fb = std::make_shared<FastBvh>();
+    build_fast_bvh(faces, order.data(), int(faces.size()), *fb, stack_limit_for(k), build_opts_for(k));
+    return fb;
+}
+
 void scene_release(const mcpt_scene* s) { if (s && s->refs.fetch_sub(1) == 1) delete s; }
 
 // Engine of the fast walk for a scene of t triangles (include/mcpt.h: mcpt_scene_trace_engine).  Measured on MI355X, frame times pool /

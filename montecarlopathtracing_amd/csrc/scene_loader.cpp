@@ -374,6 +374,7 @@ int load_scene_files(const std::string& path, const std::string& filename, int l
                 const double q[3] = {f.v[k].x, f.v[k].y, f.v[k].z};
                 for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], q[a]); hi[a] = std::max(hi[a], q[a]); }
             }
+        s.morton_bounds = true;
         for (int a = 0; a < 3; a++) {
             s.morton_lo[a] = float(lo[a]);
             const float span = float(hi[a]) - s.morton_lo[a];
