@@ -591,7 +591,8 @@ int  mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, 
  * when refits have degraded the hierarchy enough to rebuild.
  * _device: v is a device pointer; `stream` (may be NULL) is waited for before v is read.  mcpt_device_get_vertices: what the device holds.
  * mcpt_device_set_camera replaces the camera (width and height stay) for every later frame; the same refusal while a progressive handle
- * lives.  mcpt_multi_*: the same on every device of the group in turn (info: of devices[0]); the first failure is returned. */
+ * lives.  mcpt_multi_*: the same on every device of the group in turn (info: of devices[0]); the first failure is returned.
+ * On a device that holds a motion (mcpt_device_set_motion, below) both calls define a new key 0 and CLEAR the motion. */
 #define MCPT_UPDATE_REFIT    0   /* keep the culling hierarchy's topology, recompute its boxes on the GPU */
 #define MCPT_UPDATE_REBUILD  1   /* build the culling hierarchy again with the builder the device was created with */
 typedef struct {
@@ -612,6 +613,79 @@ int mcpt_device_set_camera(mcpt_device*, const double eye[3], const double look_
 int mcpt_device_get_camera(const mcpt_device*, double eye[3], double look_at[3], double up[3], double* fovy);
 int mcpt_multi_update_vertices(mcpt_multi*, const double* v, int32_t mode, mcpt_update_info* info /* of devices[0]; may be NULL */);
 int mcpt_multi_set_camera(mcpt_multi*, const double eye[3], const double look_at[3], const double up[3], double fovy);
+
+/* ---- motion blur (since the motion change): a frame that integrates over the time the shutter is open, between two keyframes of a device ---- */
+/* A device may hold a MOTION.  Key 0 is the geometry and camera the device holds when the motion is set.  Key 1 is the caller's: v_end =
+ * [num_faces][9] doubles in .obj order as mcpt_device_update_vertices takes them (NULL: the geometry does not move) and an end camera
+ * (NULL: the camera does not move).  The shutter {open, close, steps} has 0 <= open <= close <= 1, steps = K >= 1, reserved = 0.
+ *   time   : step j of K is rendered at u_j = open + (close - open) * ((j + 0.5) / K), fp64 without contraction, as written
+ *            (mcpt_shutter_time).
+ *   blend  : every coordinate (the vertices; eye, look_at, up, fovy) is x(u) = (1 - u) * x0 + u * x1, fp64 without contraction -- and x0
+ *            itself, not its rounded blend, where x0 == x1: a coordinate that does not move keeps its bits at every u, so a motion whose key 1
+ *            equals key 0 renders the static frame.  For finite keys u = 0 gives key 0 and u = 1 key 1 exactly.  Face::norm is derived from
+ *            the blended vertices as the loader derives it; vn, vt, materials and radiances stay, as for an update.  The camera at u_j is
+ *            what mcpt_device_set_camera makes of the blended values; a blended camera it would refuse fails the frame with MCPT_ERR_ARG.
+ *   samples: sample k of an N-sample frame belongs to step j = (k * K) / N in 64-bit integer arithmetic (mcpt_shutter_step): the steps are
+ *            contiguous, non-empty sample ranges in ascending order.  K <= N is required at render time (MCPT_ERR_ARG).
+ *   THE FRAME: sample k of pixel p is the radiance mcpt_sample_radiance(seed, p, k) returns on a device created (same build mode, lens,
+ *            environment) from a scene whose vertices are V(u_j) and whose camera is C(u_j); the frame is the ordered float fold of these
+ *            (D3) exactly as for a static frame.  Primary hits, light tables, the Morton order and the vetting of the coordinates follow per
+ *            step, because each step is an MCPT_UPDATE_REFIT of the blended vertices on key 0's topology: the boxes of step j come from
+ *            V(u_j) alone, so neither the order of the steps nor what was rendered before can matter.
+ * mcpt_render / mcpt_render_device on a device with a motion render that frame (MCPT_RENDER_MEGAKERNEL and partitions honoured; the call
+ * returns when the frame is finished: the steps are joined by synchronous updates).  So does a uniform progressive handle created on such a
+ * device: a step(n) that crosses step boundaries is split at them, the float fold and the moments carry across, primary hits are traced
+ * again per step; at done == N the image is the one-shot shutter frame bit for bit, and noise / image keep the same bits for any pass
+ * sizes.  A pixel counts as hit when its primary ray hit in any step so far; the moments take every sample (a missed one as 0, or as the
+ * environment's radiance), so the standard error includes the variation over time, and before done == N every pixel shows sum x / done.
+ * The steps are contiguous sample ranges, so BEFORE done == N A PROGRESSIVE FRAME HOLDS THE EARLIEST PART OF THE SHUTTER ONLY: image, stderr
+ * and noise at done < N describe the steps rendered so far -- a preview of the first (done K) / N of the shutter, not a noisier picture of
+ * the whole of it.  A caller that stops on a noise target inside a motion frame gets that partial shutter (mcpt_render_scene_motion refuses
+ * to).
+ * Everything that is not a motion frame -- mcpt_trace_closest*, mcpt_sample_radiance, mcpt_camera_rays, mcpt_device_get_vertices,
+ * _get_camera, _get_bvh_nodes, _get_leaf_order, _fast_hierarchy -- sees key 0, bit for bit what it saw before the motion was set: the
+ * camera returns to key 0 at the end of every frame or pass, the geometry before the next such call (one refit), so a run of motion frames
+ * does not pay for it between frames.  THE FIRST SUCH CALL AFTER A MOTION FRAME THEREFORE COSTS A REFIT (mcpt_update_info.ms_total of the
+ * scene: under a millisecond on the small scenes, 35 ms at 10 M triangles), waits for the device's frames in flight and writes the device's
+ * geometry arrays -- the read-backs mcpt_device_get_vertices, _get_bvh_nodes, _get_leaf_order and _fast_hierarchy (whose handle is const
+ * for what it reports, not for this) included; so do mcpt_device_set_motion*, _clear_motion, _set_camera and _update_vertices*, the last
+ * so that its cost_before and leaves_moved compare with key 0 and not with a step.  mcpt_device_get_camera, _get_motion and _motion_info
+ * never do.
+ * mcpt_device_update_vertices and mcpt_device_set_camera define a new key 0 and CLEAR the motion -- once they have succeeded: a call that
+ * is refused, or an update that fails midway, leaves the motion in place.  mcpt_device_set_motion* and
+ * mcpt_device_clear_motion are refused (MCPT_ERR_ARG) while a progressive handle of the device lives, like an update.
+ * Refused with MCPT_ERR_ARG on a device with a motion: mcpt_progressive_create_adaptive, MCPT_RENDER_PIPELINE, mcpt_progressive_aovs /
+ * _denoise on a handle created under the motion, and in mcpt_render_scene_motion a checkpoint or several GPUs (a mcpt_multi group has no
+ * motion).  Invalid shutters are MCPT_ERR_ARG before MCPT_ERR_NO_DEVICE, as for the lens.
+ * Memory: both keyframes stay resident in the staging layout when the geometry moves, 72 bytes per face per keyframe on top of the 216 per
+ * face the first update makes resident; a one-shot motion frame keeps 49 bytes per pixel of moments (53 under an active lens).
+ * _device: d_v_end is a device pointer; `stream` (may be NULL) is waited for before it is read.
+ * mcpt_device_get_motion: shutter->steps = 0 when the device holds none; *has_geometry / *has_camera say which of the two moves;
+ * camera_end receives key 1's camera (the device's own when it does not move).  Any pointer may be NULL.
+ * mcpt_device_motion_info: of the last motion frame or progressive pass -- the steps it ran, the milliseconds spent in their updates (the
+ * return to key 0 is not in it) and the largest cost_after of a step / the cost at key 0 (mcpt_update_info; 0 when no geometry moved). */
+typedef struct { double open, close; int32_t steps, reserved; } mcpt_shutter;
+typedef struct { double eye[3], look_at[3], up[3], fovy; } mcpt_camera_key;
+typedef struct { int32_t steps_run, reserved; double ms_updates, max_cost_ratio; } mcpt_motion_info;
+int mcpt_device_set_motion(mcpt_device*, const double* v_end, const mcpt_camera_key* camera_end, const mcpt_shutter*);
+int mcpt_device_set_motion_device(mcpt_device*, const double* d_v_end, const mcpt_camera_key* camera_end, const mcpt_shutter*, void* stream);
+int mcpt_device_clear_motion(mcpt_device*);
+int mcpt_device_get_motion(const mcpt_device*, mcpt_shutter* shutter, int32_t* has_geometry, int32_t* has_camera, mcpt_camera_key* camera_end);
+int mcpt_device_motion_info(const mcpt_device*, mcpt_motion_info* out);
+/* pure functions, usable without a GPU: u_j (NaN for an invalid shutter or j outside [0, steps)) and the step of sample k (-1 for
+ * spp < 1, steps outside [1, spp] or k outside [0, spp)) */
+double  mcpt_shutter_time(double open, double close, int32_t steps, int32_t j);
+int32_t mcpt_shutter_step(int32_t spp, int32_t steps, int32_t k);
+/* mcpt_render_scene_env with a motion: end_obj (NULL: the geometry does not move) is the path of an .obj file read with the scene's load
+ * flags, whose faces -- same count, same per-face materials, otherwise MCPT_ERR_PARSE before anything is written -- give key 1's vertices;
+ * end_camera (NULL: the camera does not move) the path of a .camera file whose eye, look_at, up and fovy give key 1's camera (its resolution
+ * and lights are ignored).  shutter == NULL: mcpt_render_scene_env.  With a checkpoint or num_devices != 0: MCPT_ERR_ARG.  MCPT_OUT_ERROR_PFM
+ * renders the frame through a uniform progressive handle under the motion, all N samples of it.  noise_target and time_budget_s are
+ * refused with MCPT_ERR_ARG: a frame stopped at k < N would hold the first part of the shutter only.  So are adaptive frames,
+ * MCPT_OUT_DENOISED and MCPT_OUT_AOV_PFM. */
+int  mcpt_render_scene_motion(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, int64_t options_bytes,
+                              const mcpt_lens*, const char* environment_pfm, double environment_scale, const char* end_obj,
+                              const char* end_camera, const mcpt_shutter*, mcpt_stats* stats);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,24 @@ class UpdateInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
 
 
+class Shutter(C.Structure):
+    """mcpt_shutter: the interval of a motion that is open, in `steps` time steps (mcpt_device_set_motion)"""
+    _fields_ = [("open", C.c_double), ("close", C.c_double), ("steps", C.c_int32), ("reserved", C.c_int32)]
+
+
+class CameraKey(C.Structure):
+    """mcpt_camera_key: the camera of a motion's key 1"""
+    _fields_ = [("eye", C.c_double * 3), ("look_at", C.c_double * 3), ("up", C.c_double * 3), ("fovy", C.c_double)]
+
+
+class MotionInfo(C.Structure):
+    """mcpt_motion_info: what the last motion frame's steps took (mcpt_device_motion_info)"""
+    _fields_ = [("steps_run", C.c_int32), ("reserved", C.c_int32), ("ms_updates", C.c_double), ("max_cost_ratio", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_ if n != "reserved"}
+
+
 class Noise(C.Structure):
     """mcpt_noise: the frame summary of a progressive frame after `done` of `spp` samples"""
     _fields_ = [("done", C.c_int32), ("spp", C.c_int32), ("pixels", C.c_int64), ("rel_error", C.c_double), ("abs_rms", C.c_double),
@@ -136,6 +154,8 @@ EXPORTS = [
     "mcpt_multi_set_environment", "mcpt_render_scene_env",
     "mcpt_device_update_vertices", "mcpt_device_update_vertices_device", "mcpt_device_get_vertices", "mcpt_device_set_camera",
     "mcpt_device_get_camera", "mcpt_multi_update_vertices", "mcpt_multi_set_camera",
+    "mcpt_device_set_motion", "mcpt_device_set_motion_device", "mcpt_device_clear_motion", "mcpt_device_get_motion", "mcpt_device_motion_info",
+    "mcpt_shutter_time", "mcpt_shutter_step", "mcpt_render_scene_motion",
 ]
 
 
@@ -268,6 +288,17 @@ def lib():
     L.mcpt_device_get_camera.argtypes = [P, D, D, D, D]
     L.mcpt_multi_update_vertices.argtypes = [P, D, C.c_int32, C.POINTER(UpdateInfo)]
     L.mcpt_multi_set_camera.argtypes = [P, D, D, D, C.c_double]
+    L.mcpt_device_set_motion.argtypes = [P, D, C.POINTER(CameraKey), C.POINTER(Shutter)]
+    L.mcpt_device_set_motion_device.argtypes = [P, P, C.POINTER(CameraKey), C.POINTER(Shutter), P]
+    L.mcpt_device_clear_motion.argtypes = [P]
+    L.mcpt_device_get_motion.argtypes = [P, C.POINTER(Shutter), I32, I32, C.POINTER(CameraKey)]
+    L.mcpt_device_motion_info.argtypes = [P, C.POINTER(MotionInfo)]
+    L.mcpt_shutter_time.argtypes = [C.c_double, C.c_double, C.c_int32, C.c_int32]
+    L.mcpt_shutter_time.restype = C.c_double
+    L.mcpt_shutter_step.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.mcpt_shutter_step.restype = C.c_int32
+    L.mcpt_render_scene_motion.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens), C.c_char_p,
+                                           C.c_double, C.c_char_p, C.c_char_p, C.POINTER(Shutter), C.POINTER(Stats)]
     _lib = L
     return L
 

@@ -6,7 +6,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, DenoiseParams, Environment, FastInfo, Lens, McptError, Noise, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, Environment, FastInfo, Lens, McptError, MotionInfo, Noise, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -257,6 +257,20 @@ def _camera_args(eye, look_at, up):
     return out
 
 
+def _shutter(shutter, steps):
+    return Shutter(float(shutter[0]), float(shutter[1]), int(steps), 0)
+
+
+def shutter_time(open, close, steps, j):
+    """u_j of a shutter (mcpt_shutter_time; NaN for invalid arguments)"""
+    return lib().mcpt_shutter_time(float(open), float(close), int(steps), int(j))
+
+
+def shutter_step(spp, steps, k):
+    """the step sample k of an spp-sample frame belongs to (mcpt_shutter_step; -1 for invalid arguments)"""
+    return lib().mcpt_shutter_step(int(spp), int(steps), int(k))
+
+
 class Device:
     """One MI355X holding a resident copy of a Scene."""
 
@@ -441,6 +455,51 @@ class Device:
         e, l, u, f = np.zeros(3), np.zeros(3), np.zeros(3), C.c_double()
         check(lib().mcpt_device_get_camera(self._h, _p(e, C.c_double), _p(l, C.c_double), _p(u, C.c_double), C.byref(f)))
         return {"eye": e, "look_at": l, "up": u, "fovy": f.value}
+
+    def set_motion(self, v_end=None, camera_end=None, shutter=(0.0, 1.0), steps=1, stream=None):
+        """A motion between what the device holds now (key 0) and key 1 (mcpt_device_set_motion): v_end as update_vertices takes the
+        vertices (None: the geometry does not move), camera_end a dict of eye, look_at, up and fovy (None: the camera does not move),
+        shutter = (open, close) within [0, 1] rendered in `steps` time steps.  generateImg, render_device and progressive frames then
+        render the shutter frame; everything else keeps seeing key 0."""
+        n = self.scene.info.num_faces
+        sh = _shutter(shutter, steps)
+        cam = None
+        if camera_end is not None:
+            e, l, u = _camera_args(camera_end["eye"], camera_end["look_at"], camera_end["up"])
+            cam = CameraKey((C.c_double * 3)(*e), (C.c_double * 3)(*l), (C.c_double * 3)(*u), float(camera_end["fovy"]))
+        cam = C.byref(cam) if cam is not None else None
+        if isinstance(v_end, numbers.Integral):
+            check(lib().mcpt_device_set_motion_device(self._h, C.c_void_p(int(v_end)), cam, C.byref(sh), C.c_void_p(stream) if stream else None))
+        elif hasattr(v_end, "data_ptr") and getattr(v_end, "is_cuda", False):
+            if v_end.numel() != n * 9 or not v_end.is_contiguous() or str(v_end.dtype) != "torch.float64":
+                raise ValueError("a device tensor of vertices must be contiguous float64 with %d elements" % (n * 9))
+            check(lib().mcpt_device_set_motion_device(self._h, C.c_void_p(v_end.data_ptr()), cam, C.byref(sh), C.c_void_p(stream) if stream else None))
+        else:
+            if v_end is not None:
+                if hasattr(v_end, "detach"):
+                    v_end = v_end.detach().cpu().numpy()
+                v_end = _host_vertices(v_end, n)
+            check(lib().mcpt_device_set_motion(self._h, _p(v_end, C.c_double) if v_end is not None else None, cam, C.byref(sh)))
+
+    def clear_motion(self):
+        """the device without a motion again, at key 0 (mcpt_device_clear_motion)"""
+        check(lib().mcpt_device_clear_motion(self._h))
+
+    @property
+    def motion(self):
+        """None, or the device's motion as a dict: shutter (open, close), steps, has_geometry, has_camera, camera_end"""
+        sh, g, c, cam = Shutter(), C.c_int32(), C.c_int32(), CameraKey()
+        check(lib().mcpt_device_get_motion(self._h, C.byref(sh), C.byref(g), C.byref(c), C.byref(cam)))
+        if sh.steps == 0:
+            return None
+        return {"shutter": (sh.open, sh.close), "steps": sh.steps, "has_geometry": bool(g.value), "has_camera": bool(c.value),
+                "camera_end": {"eye": np.array(cam.eye), "look_at": np.array(cam.look_at), "up": np.array(cam.up), "fovy": cam.fovy}}
+
+    def motion_info(self):
+        """what the steps of the last motion frame (or progressive pass) took: steps_run, ms_updates, max_cost_ratio"""
+        info = MotionInfo()
+        check(lib().mcpt_device_motion_info(self._h, C.byref(info)))
+        return info.as_dict()
 
     def progressive(self, spp, seed=0, rank=0, world=1, tile_w=0, tile_h=0, flags=0):
         """A frame of `spp` samples per pixel rendered in passes (mcpt_progressive_*): see Progressive."""
@@ -726,14 +785,16 @@ def morton_code(x, y, z):
 
 def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, height=0, quiet=True, output_prefix=None, stats=None,
                  load_flags=0, output_flags=0, checkpoint=None, checkpoint_parts=0, devices=None, gather=GATHER_PEER, noise_target=0.0,
-                 time_budget_s=0.0, adaptive_min_spp=0, abs_target=0.0, lens=None, environment=None, environment_scale=1.0):
+                 time_budget_s=0.0, adaptive_min_spp=0, abs_target=0.0, lens=None, environment=None, environment_scale=1.0, motion=None):
     """render_scene(path, filename, N) of MTPC/MTPC.cpp:35; writes <prefix>-SPP<N>.png (default ../result/<filename>).
     devices: list of GPU ordinals, or -1 for every visible GPU (the frame is then rendered by mcpt_multi_*).
     noise_target / time_budget_s / OUT_ERROR_PFM: a progressive frame that may stop at k < N samples (<prefix>-SPP<k>.png).
     adaptive_min_spp > 0: an adaptive frame, noise_target and abs_target its per-pixel targets (OUT_SPP_PFM: the sample-count map).
     OUT_DENOISED / OUT_AOV_PFM: also the denoised frame (.denoised.png, .denoised.pfm with OUT_PFM) / the first-hit AOVs as .pfm files.
     lens: None (the pinhole), a Lens or a dict of Device.set_lens's arguments; rendered through mcpt_render_scene_lens.
-    environment: None, or the path of a colour PFM lat-long map (environment_scale: its scale); rendered through mcpt_render_scene_env."""
+    environment: None, or the path of a colour PFM lat-long map (environment_scale: its scale); rendered through mcpt_render_scene_env.
+    motion: None, or a dict of end_obj and end_camera (file paths, either may be missing), shutter = (open, close) and steps: the shutter
+    frame between the scene and those files (mcpt_render_scene_motion)."""
     dev_arr, ndev = None, 0
     if devices == -1:
         ndev = -1
@@ -744,7 +805,14 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
                            load_flags, output_flags, checkpoint.encode() if checkpoint else None, checkpoint_parts, 0,
                            ndev, gather, dev_arr, noise_target, time_budget_s, adaptive_min_spp, 0, abs_target)
     st = C.byref(stats) if stats is not None else None
-    if environment is not None:
+    if motion is not None:
+        sh = _shutter(motion.get("shutter", (0.0, 1.0)), motion.get("steps", 1))
+        end_obj, end_camera = motion.get("end_obj"), motion.get("end_camera")
+        check(lib().mcpt_render_scene_motion(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o),
+                                             C.byref(_as_lens(lens)) if lens is not None else None,
+                                             environment.encode() if environment is not None else None, float(environment_scale),
+                                             end_obj.encode() if end_obj else None, end_camera.encode() if end_camera else None, C.byref(sh), st))
+    elif environment is not None:
         check(lib().mcpt_render_scene_env(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o),
                                           C.byref(_as_lens(lens)) if lens is not None else None, environment.encode(), float(environment_scale), st))
     elif lens is None:

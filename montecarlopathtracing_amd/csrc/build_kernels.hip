@@ -777,6 +777,26 @@ hipError_t device_face_normals(const double* v9, int t, double* nrm3, hipStream_
     return hipGetLastError();
 }
 
+// A motion's step (motion.cpp): out = the blend of the two keyframes at time u, x(u) = (1 - u) * x0 + u * x1 in fp64 without contraction
+// (-ffp-contract=off), and x0 itself where x0 == x1 -- a coordinate that does not move keeps its bits.  One thread per pair of
+// coordinates (16-byte loads and stores: the three arrays are allocations of their own), thread 0 also the odd last coordinate.
+__device__ __forceinline__ double blend_key(double a, double b, double u) { return a == b ? a : (1.0 - u) * a + u * b; }
+__global__ void k_blend_keys(const double* __restrict__ v0, const double* __restrict__ v1, long long n, double u, double* __restrict__ out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x, pairs = n >> 1;
+    if (i < pairs) {
+        const double2 a = reinterpret_cast<const double2*>(v0)[i], b = reinterpret_cast<const double2*>(v1)[i];
+        reinterpret_cast<double2*>(out)[i] = make_double2(blend_key(a.x, b.x, u), blend_key(a.y, b.y, u));
+    }
+    if (i == 0 && (n & 1)) out[n - 1] = blend_key(v0[n - 1], v1[n - 1], u);
+}
+hipError_t device_blend_keys(const double* v0, const double* v1, int t, double u, double* out, hipStream_t st)
+{
+    const long long n = (long long)t * 9, threads = n / 2 > 0 ? n / 2 : 1;
+    if (t > 0) hipLaunchKernelGGL(k_blend_keys, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, st, v0, v1, n, u, out);
+    return hipGetLastError();
+}
+
 __global__ void k_tri_faces(const DTri* __restrict__ fast_tris, int n, int32_t* __restrict__ tri_faces)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -49,6 +49,8 @@ hipError_t device_build_pre(const DTri* fast_tris, int n, double absmax, DTriPre
 // ---- geometry updates (update.cpp)
 // nrm3[t][3] = Face::norm of the faces v9[t][9], in the loader's operation order
 hipError_t device_face_normals(const double* v9, int t, double* nrm3, hipStream_t st);
+// out[t][9] = the keyframes v0, v1 blended at time u: (1 - u) * x0 + u * x1 per coordinate, x0 itself where x0 == x1 (three distinct allocations)
+hipError_t device_blend_keys(const double* v0, const double* v1, int t, double u, double* out, hipStream_t st);
 // tri_faces[i] = .obj face of triangle slot i
 hipError_t device_tri_faces(const DTri* fast_tris, int n, int32_t* tri_faces, hipStream_t st);
 // leaf_of_face[t] scattered from d_order, then slots[i] = leaf_of_face[tri_faces[i]]: what device_gather_tris refills the slots from

@@ -166,6 +166,47 @@ __global__ void k_fold_lens(const double* __restrict__ rad, const uint8_t* __res
     m[0] = s1; m[3] = s2;
 }
 
+// k_fold_progressive (kernels.hip: keep the two in step) for a piece of a motion frame (mcpt.h: motion blur; the per-pixel route).  The pieces of one pixel are rendered on
+// different geometries and cameras, so its primary ray may hit in one and miss in another: a missed piece brings samples of +0.0 -- which
+// leave the fold and the moments as they are -- or, ENV, of Le(the piece's primary direction), folded and summed like any other sample.
+// hit[pix]: the primary ray hit in some piece so far.  One lane per (slot, channel).
+template <bool ENV>
+__global__ void k_fold_motion(const double* __restrict__ rad, const int32_t* __restrict__ pixels, const PrimaryHit* __restrict__ hits, int first_slot,
+                              int n_slots, int n, int k0, int N, double* __restrict__ img, double* __restrict__ mom, uint8_t* __restrict__ hit, DEnv env,
+                              const double* __restrict__ dirs)
+{
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)n_slots * 3) return;
+    const int s = (int)(gid / 3), c = (int)(gid % 3);
+    const int slot = first_slot + s;
+    const int pix = pixels ? pixels[slot] : slot;
+    const bool h = hits[slot].leaf >= 0;
+    if (c == 0) hit[pix] = (uint8_t)((k0 > 0 ? hit[pix] : 0) | (h ? 1 : 0));
+    const size_t i = (size_t)pix * 3 + c;
+    double* m = mom + (size_t)pix * 6 + c;
+    double le = 0.0;
+    if (!h) {
+        if (ENV) {
+            const V3 e = env_eval(env, ld3(dirs + (size_t)pix * 3));
+            le = c == 0 ? e.x : (c == 1 ? e.y : e.z);
+        } else {
+            if (k0 == 0) { img[i] = 0.0; m[0] = 0.0; m[3] = 0.0; }
+            return;
+        }
+    }
+    const double* src = rad + (size_t)s * n * 3 + c;
+    float acc = k0 > 0 ? (float)img[i] : 0.0f;
+    double s1 = k0 > 0 ? m[0] : 0.0, s2 = k0 > 0 ? m[3] : 0.0;
+    for (int k = 0; k < n; k++) {
+        const double x = h ? src[(size_t)k * 3] : le;
+        acc = (float)((double)acc + x / N);
+        s1 += x;
+        s2 += x * x;
+    }
+    img[i] = (double)acc;
+    m[0] = s1; m[3] = s2;
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
 static inline unsigned blocks_of(long long n, int block) { return (unsigned)((n + block - 1) / block); }
 
@@ -213,6 +254,15 @@ void launch_fold_lens(const double* d_rad, const uint8_t* d_flags, const int32_t
     }
     if (d_mom) hipLaunchKernelGGL((k_fold_lens<true, false>), grid, dim3(256), 0, st, d_rad, d_flags, d_pixels, first_slot, n_slots, n, k0, N, d_img, d_mom, d_hit, d_hitcnt);
     else hipLaunchKernelGGL((k_fold_lens<false, false>), grid, dim3(256), 0, st, d_rad, d_flags, d_pixels, first_slot, n_slots, n, k0, N, d_img, d_mom, d_hit, d_hitcnt);
+}
+
+void launch_fold_motion(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int n, int k0, int N,
+                        double* d_img, double* d_mom, uint8_t* d_hit, const DEnv& env, const double* d_dirs, hipStream_t st)
+{
+    if (n_slots <= 0) return;
+    const dim3 grid(blocks_of((long long)n_slots * 3, 256));
+    if (env_on(env)) hipLaunchKernelGGL(k_fold_motion<true>, grid, dim3(256), 0, st, d_rad, d_pixels, d_hits, first_slot, n_slots, n, k0, N, d_img, d_mom, d_hit, env, d_dirs);
+    else hipLaunchKernelGGL(k_fold_motion<false>, grid, dim3(256), 0, st, d_rad, d_pixels, d_hits, first_slot, n_slots, n, k0, N, d_img, d_mom, d_hit, env, d_dirs);
 }
 
 }  // namespace mcpt

@@ -428,6 +428,7 @@ int mcpt_device_get_bvh_nodes(mcpt_device* d, double* box6, int32_t* leaf_face)
 {
     if (!d) return fail(MCPT_ERR_ARG, "null device");
     HIP_TRY(hipSetDevice(d->ordinal));
+    if (const int rc = motion_home(d)) return rc;
     const mcpt_bvh_info& bi = d->bi;
     if (box6) {
         std::vector<DNode> nodes(bi.Nr);
@@ -450,6 +451,7 @@ int mcpt_device_get_leaf_order(mcpt_device* d, int32_t* leaf_to_face)
 {
     if (!d || !leaf_to_face) return fail(MCPT_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(d->ordinal));
+    if (const int rc = motion_home(d)) return rc;
     HIP_TRY(hipMemcpy(leaf_to_face, d->d_order.get(), size_t(d->bi.t) * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
@@ -458,6 +460,7 @@ int mcpt_device_fast_hierarchy(const mcpt_device* d, mcpt_fast_info* info, void*
 {
     static_assert(sizeof(CwNode) == 64, "mcpt.h documents 64-byte node records");
     if (!d || !info) return fail(MCPT_ERR_ARG, "null argument");
+    if (const int rc = motion_home(const_cast<mcpt_device*>(d))) return rc;     // (the view is read-only; a motion frame's step is not what it shows)
     *info = d->fast_info;
     if (!nodes && !tri_faces) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
@@ -485,6 +488,7 @@ int mcpt_trace_closest_device(mcpt_device* d, const double* d_rays, int64_t n, i
     if (!d || (n > 0 && !d_rays) || n < 0) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(d->ordinal));
     if (!d_face || !d_t || !d_p) return fail(MCPT_ERR_ARG, "d_face, d_t and d_p are required by the device form");
+    if (const int rc = motion_home(d)) return rc;
     if (const int rc = geometry_gate(d)) return rc;
     launch_trace_closest(d->ds, d->trace_mode == MCPT_TRACE_FAST, d_rays, n, d_face, d_t, d_p, d_pn, d->aux_ctr.get(), d->aux_queue.get(), d->aux_slow_list.get(), d->slow_cap,
                          static_cast<hipStream_t>(stream), d->cfg);
@@ -496,6 +500,7 @@ int mcpt_trace_closest(mcpt_device* d, const double* rays, int64_t n, int32_t* f
 {
     if (!d || (n > 0 && !rays) || n < 0) return fail(MCPT_ERR_ARG, "bad argument");
     if (stats) std::memset(stats, 0, sizeof *stats);
+    if (const int rc = motion_home(d)) return rc;
     if (const int rc = geometry_gate(d)) return rc;
     if (n == 0) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));

@@ -4,6 +4,7 @@
 //   device.cpp        device creation stage by stage, hierarchy queries, closest hit
 //   render.cpp        lenses, the integrator (megakernel and wavefront), mcpt_render*, statistics, (pixel, sample) queries
 //   progressive.cpp   progressive frames, AOVs, the denoiser
+//   motion.cpp        a device's motion: the shutter's steps between two keyframes, the return to key 0
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -144,6 +145,22 @@ struct mcpt_device {
         float morton_lo[3], morton_span[3];
     };
     std::unique_ptr<Update> upd;
+    // A motion (motion.cpp, mcpt_device_set_motion): key 0 is what the device held when it was set.  While a motion frame renders, and
+    // until the next call that is not one, the geometry is a step's (away); the camera is back at key 0 whenever a frame or pass returns.
+    struct Motion {
+        mcpt_shutter shutter{};
+        bool has_geometry = false, has_camera = false;
+        mcpt::DevBuf<double> v0, v1;                    // both keyframes in the staging layout, 72 B per face each (has_geometry)
+        mcpt_camera_key c0{}, c1{};                     // the cameras of key 0 and key 1
+        mcpt::DCamera cam0{};                           // key 0's camera as the kernels read it
+        bool away = false;                              // the geometry is step at_step's, not key 0's
+        int at_step = -1;
+        double cost0 = -1;                              // the culling hierarchy's cost figure at key 0
+        mcpt_motion_info info{};                        // of the last motion frame or pass
+        // what a one-shot motion frame folds through (a progressive handle has its own): moments, hit flags, hit counts under a lens
+        mcpt::DevBuf<double> mom; mcpt::DevBuf<uint8_t> hit; mcpt::DevBuf<int32_t> hitcnt;
+    };
+    std::unique_ptr<Motion> motion;
     bool geometry_failed = false;                   // an update failed midway: nothing is traced or rendered until one succeeds
 };
 
@@ -182,6 +199,25 @@ inline bool fast_walk_enabled(const mcpt_fast_info& fi, bool coords_ok, double a
     return coords_ok && fi.max_depth < mcpt::kFastMaxDepth && fi.cw_stack_need < mcpt::kFastMaxDepth && absmax >= 1e-15 && absmax <= 1e15;
 }
 
+// ---- update.cpp
+int wait_for_frames(mcpt_device* d);                // nothing of the device is in flight afterwards
+int stage_faces(mcpt_device* d);                    // the faces in .obj order become resident (d->upd), once
+// MCPT_UPDATE_REFIT to the vertices d_v (device pointer, [t][9]) without the entry point's checks: the caller has waited for the frames
+int refit_geometry(mcpt_device* d, const double* d_v, mcpt_update_info* info);
+int camera_check(const double eye[3], const double look_at[3], const double up[3], double fovy);    // MCPT_ERR_ARG: not a camera
+void camera_apply(mcpt_device* d, const double eye[3], const double look_at[3], const double up[3], double fovy);   // (checked, nothing in flight)
+
+// ---- motion.cpp
+int shutter_check(const mcpt_shutter* s);
+// The geometry back at key 0 (one refit) when a motion frame has left it at a step: called by every entry point that is not a motion frame
+// before it reads the device.  A device without a motion: nothing.
+int motion_home(mcpt_device* d);
+void motion_clear(mcpt_device* d);                  // drops the motion as it stands (the caller replaces what it left)
+// Samples [k0, k0 + n) of an N-sample frame under d's motion, cut at the shutter's step boundaries: for every piece the device goes to the
+// piece's step (blend, refit, camera) once st and the device's frames are idle, then run(first sample, count) renders it on st.  Returns
+// with st idle, the camera at key 0 and d->motion->info describing the pieces.
+int motion_passes(mcpt_device* d, int k0, int n, int N, hipStream_t st, const std::function<int(int, int)>& run);
+
 // ---- environment.cpp
 int env_check(const mcpt_environment* e);
 int env_make(const mcpt_environment* e, std::shared_ptr<mcpt::EnvData>& out);   // tables + upload on the current device (e valid)
@@ -209,6 +245,7 @@ struct SampleRange {
     const mcpt_lens* lens;      // the lens of the call (the device's, or the one a progressive handle took); null: the pinhole
     int32_t* hitcnt;            // progressive passes under an active lens: per pixel, the samples whose camera ray hit
     const mcpt::EnvData* env;   // the environment of the call (the device's, or the one a progressive handle took); null: none
+    bool motion = false;        // a piece of a motion frame (mom != null): a pixel's primary ray may hit in one step and miss in another
 };
 
 // The pixels a render call covers, on the device: the partition's owned list (mcpt_render*, uniform progressive passes) or an adaptive

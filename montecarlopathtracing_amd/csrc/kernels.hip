@@ -256,6 +256,8 @@ __global__ void k_fold_samples(const double* __restrict__ rad, const int32_t* __
 // first and second moments of the radiance, in fp64 in k order: mom[pix][0][c] = sum x, mom[pix][1][c] = sum x*x (no contraction:
 // the library is built with -ffp-contract=off).  hit[pix] records whether the pixel's primary ray hit (k_noise_reduce counts only those).
 // One lane per (slot, channel).  ENV: a missed pixel's image continues the fold of Le(primary direction), its first moment the sum.
+// (A pixel is hit or missed for the whole frame here.  The pieces of a motion frame, where that changes from step to step, fold through
+// k_fold_motion in camera.hip: the same fold and moments, a change to either belongs in both.)
 template <bool ENV>
 __global__ void k_fold_progressive(const double* __restrict__ rad, const int32_t* __restrict__ pixels, const PrimaryHit* __restrict__ hits,
                                    int first_slot, int n_slots, int n, int k0, int N, double* __restrict__ img, double* __restrict__ mom,

@@ -65,6 +65,10 @@ void launch_sample_radiance_lens(const DScene& S, const DLens& lens, unsigned lo
 // (env active: a camera ray that missed has radiance Le, and every sample is folded)
 void launch_fold_lens(const double* d_rad, const uint8_t* d_flags, const int32_t* d_pixels, int first_slot, int n_slots, int n, int k0, int N,
                       double* d_img, double* d_mom, uint8_t* d_hit, int32_t* d_hitcnt, bool env, hipStream_t st);
+// launch_fold_progressive for a piece of a motion frame (camera.hip): a pixel's primary ray may hit in one piece and miss in another, so a
+// missed piece's samples (0, or Le under an environment) continue the fold and the moments; d_hit[pix] = hit in some piece so far
+void launch_fold_motion(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int n, int k0, int N,
+                        double* d_img, double* d_mom, uint8_t* d_hit, const DEnv& env, const double* d_dirs, hipStream_t st);
 // ---- the environment's test seams (env.hip): rgb[n*3] = Le(dirs[i]); out7[n*7] = direction, pdf, radiance of the block-(nl + 2) draw
 void launch_env_eval(const DEnv& E, const double* d_dirs, long long n, double* d_rgb, hipStream_t st);
 void launch_env_sample(const DEnv& E, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, int depth, int nl, long long n, double* d_out7,

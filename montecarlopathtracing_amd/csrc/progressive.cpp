@@ -63,6 +63,7 @@ struct mcpt_progressive {
     mcpt_lens lens{};                  // the device's lens when the handle was created
     std::shared_ptr<const EnvData> env;   // ... and its environment (null: none)
     DevBuf<int32_t> hitcnt;            // W*H, under an active lens: the samples so far whose camera ray hit (hit = hitcnt > 0)
+    bool motion = false;               // created on a device with a motion (which stays while the handle lives): passes are cut at its steps
 };
 
 extern "C" {
@@ -83,6 +84,8 @@ static int progressive_create(mcpt_device* d, const mcpt_render_params* p, const
     if (p->flags & (MCPT_RENDER_PIPELINE | MCPT_RENDER_KEEP_STATS))
         return fail(MCPT_ERR_ARG, "a progressive frame takes neither MCPT_RENDER_PIPELINE nor MCPT_RENDER_KEEP_STATS");
     if (const int rc = geometry_gate(d)) return rc;
+    if (d->motion && ap) return fail(MCPT_ERR_ARG, "the device holds a motion: adaptive frames under a motion are not supported");
+    if (d->motion && d->motion->shutter.steps > p->spp) return fail(MCPT_ERR_ARG, "the shutter has more steps than the frame has samples per pixel");
     std::vector<int32_t> v;
     if (const int rc = owned_pixels(d->width, d->height, p, v)) return rc;
     HIP_TRY(hipSetDevice(d->ordinal));
@@ -92,6 +95,7 @@ static int progressive_create(mcpt_device* d, const mcpt_render_params* p, const
     h->p = *p;
     h->lens = d->lens;
     h->env = d->env;
+    h->motion = d->motion != nullptr;
     h->n_pixels = int64_t(v.size());
     HIP_TRY(h->pixels.upload(v));
     HIP_TRY(alloc_zeroed(h->img, px * 3 * sizeof(double)));
@@ -157,11 +161,25 @@ int mcpt_progressive_step(mcpt_progressive* h, int32_t n, mcpt_stats* stats)
     if (stats) std::memset(stats, 0, sizeof *stats);
     mcpt_render_params q = h->p;
     q.spp = std::min(n, h->p.spp - h->done);
-    const SampleRange r{h->done, q.spp, h->p.spp, h->mom.get(), h->hit.get(), &h->lens, h->hitcnt.get(), h->env.get()};
     const PixelList L = h->adaptive ? PixelList{h->active[h->cur].get(), h->n_active} : PixelList{h->pixels.get(), h->n_pixels};
     const size_t ev_used0 = d->ev_used;
     int slot_used = -1;
-    int rc = render_device_impl(d, r, L, &q, h->img.get(), stats, d->stream.get(), slot_used);
+    // one sample range on the device's geometry and camera -- or, under a motion, one per step of the shutter the pass touches
+    const auto pass = [&](int k0, int n, mcpt_stats* out) {
+        mcpt_render_params piece = q;
+        piece.spp = n;
+        const SampleRange r{k0, n, h->p.spp, h->mom.get(), h->hit.get(), &h->lens, h->hitcnt.get(), h->env.get(), h->motion};
+        return render_device_impl(d, r, L, &piece, h->img.get(), out, d->stream.get(), slot_used);
+    };
+    int rc;
+    if (h->motion)
+        rc = motion_passes(d, h->done, q.spp, h->p.spp, d->stream.get(), [&](int k0, int n) {
+            mcpt_stats piece{};
+            const int prc = pass(k0, n, stats ? &piece : nullptr);
+            if (prc == MCPT_OK && stats) { add_counts(*stats, piece); stats->ms_trace += piece.ms_trace; stats->ms_total += piece.ms_total; }
+            return prc;
+        });
+    else rc = pass(h->done, q.spp, stats);
     if (rc == MCPT_OK && h->adaptive) {
         // which pixels continue: decided on the device; the host reads back the new list's length only
         launch_adaptive_select(L.pixels, int(L.n), h->mom.get(), h->hit.get(), h->done + q.spp, h->min_spp, h->rel2, h->abs2, h->cnt.get(), h->masks.get(),
@@ -234,7 +252,8 @@ int mcpt_progressive_image_device(mcpt_progressive* h, double* d_img, double* d_
     if (!h || (!d_img && !d_stderr)) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->d->ordinal));
     // (the per-pixel route under an environment: a missed pixel's image already is the frame's fold of Le)
-    const bool sky = h->env && env_on(h->env->denv) && !lens_active(h->lens);
+    // (... unless the handle renders a motion: its missed pixels see another sky in every step and show their mean like any other)
+    const bool sky = h->env && env_on(h->env->denv) && !lens_active(h->lens) && !h->motion;
     launch_progressive_image(h->pixels.get(), h->n_pixels, h->img.get(), h->mom.get(), h->done, h->cnt.get(), h->p.spp, d_img, d_stderr,
                              sky ? h->hit.get() : nullptr, static_cast<hipStream_t>(stream));
     HIP_TRY(hipGetLastError());
@@ -288,6 +307,7 @@ static int ensure_aovs(mcpt_progressive* h)
 int mcpt_progressive_aovs(mcpt_progressive* h, int32_t* material, double* depth, double* normal, double* albedo)
 {
     if (!h) return fail(MCPT_ERR_ARG, "null handle");
+    if (h->motion) return fail(MCPT_ERR_ARG, "the frame renders a motion: first-hit AOVs under a motion are not supported");
     HIP_TRY(hipSetDevice(h->d->ordinal));
     int rc = ensure_aovs(h);
     if (rc) return rc;
@@ -309,6 +329,7 @@ int mcpt_progressive_aovs(mcpt_progressive* h, int32_t* material, double* depth,
 static int denoise_args(const mcpt_progressive* h, const mcpt_denoise_params* dp, int& iterations, double& sigma_l, double& sigma_z)
 {
     if (!h) return fail(MCPT_ERR_ARG, "null handle");
+    if (h->motion) return fail(MCPT_ERR_ARG, "the frame renders a motion: denoising under a motion is not supported");
     const mcpt_denoise_params z{};
     const mcpt_denoise_params& q = dp ? *dp : z;
     if (q.reserved != 0) return fail(MCPT_ERR_ARG, "mcpt_denoise_params.reserved must be 0");

@@ -177,7 +177,8 @@ static int prepare_partition(mcpt_device* d, const mcpt_render_params* p, hipStr
 static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, int first, int n_slots, double* d_img, bool lensed, const DScene& S,
                        const double* d_dirs, hipStream_t st)
 {
-    if (lensed) launch_fold_lens(f.rad.get(), f.cam_hit.get(), L.pixels, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, r.hitcnt, env_on(S.env), st);
+    if (r.motion && !lensed) launch_fold_motion(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, S.env, d_dirs, st);
+    else if (lensed) launch_fold_lens(f.rad.get(), f.cam_hit.get(), L.pixels, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, r.hitcnt, env_on(S.env), st);
     else if (r.mom) launch_fold_progressive(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, S.env, d_dirs, st);
     else launch_fold_samples(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, d_img, S.env, d_dirs, st);
 }
@@ -465,6 +466,33 @@ static int pair_call(mcpt_device* d, const int32_t* pix, const int32_t* k, int64
     return MCPT_OK;
 }
 
+// The shutter frame of a device with a motion (mcpt.h: motion blur): the frame's samples in the shutter's steps, each piece a progressive
+// pass on the step's geometry and camera that continues the fold in d_img; the moments it needs beside are the motion's own.
+static int render_motion_frame(mcpt_device* d, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, hipStream_t st)
+{
+    mcpt_device::Motion& m = *d->motion;
+    if (p->flags & MCPT_RENDER_PIPELINE) return fail(MCPT_ERR_ARG, "a motion frame takes no MCPT_RENDER_PIPELINE: its steps are joined by synchronous updates");
+    if (m.shutter.steps > p->spp) return fail(MCPT_ERR_ARG, "the shutter has more steps than the frame has samples per pixel");
+    const size_t px = size_t(d->width) * d->height;
+    const bool lensed = lens_active(d->lens);
+    if (!m.mom) HIP_TRY(m.mom.alloc(std::max<size_t>(px * 6, 1)));
+    if (!m.hit) HIP_TRY(m.hit.alloc(std::max<size_t>(px, 8)));
+    if (lensed && !m.hitcnt) HIP_TRY(m.hitcnt.alloc(std::max<size_t>(px, 2)));
+    if (const int rc = prepare_partition(d, p, st)) return rc;
+    const size_t ev_used0 = d->ev_used, frame_ev_used0 = d->frame_ev_used;
+    int slot_used = -1;
+    const int rc = motion_passes(d, 0, p->spp, p->spp, st, [&](int lo, int cnt) {
+        const SampleRange r{lo, cnt, p->spp, m.mom.get(), m.hit.get(), &d->lens, lensed ? m.hitcnt.get() : nullptr, d->env.get(), true};
+        mcpt_stats piece{};
+        const int prc = render_device_impl(d, r, PixelList{d->pixels.get(), d->n_pixels}, p, d_img, stats ? &piece : nullptr, st, slot_used);
+        if (prc != MCPT_OK && slot_used >= 0) d->slot[slot_used].keeping = false;      // its counters hold part of a frame
+        if (prc == MCPT_OK && stats) { add_counts(*stats, piece); stats->ms_trace += piece.ms_trace; stats->ms_total += piece.ms_total; }
+        return prc;
+    });
+    if (rc != MCPT_OK) { d->ev_used = ev_used0; d->frame_ev_used = frame_ev_used0; }
+    return rc;
+}
+
 extern "C" {
 
 int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_img, mcpt_stats* stats, void* stream)
@@ -473,6 +501,7 @@ int mcpt_render_device(mcpt_device* d, const mcpt_render_params* p, double* d_im
     if (const int rc = geometry_gate(d)) return rc;
     HIP_TRY(hipSetDevice(d->ordinal));
     if (stats) std::memset(stats, 0, sizeof *stats);
+    if (d->motion) return render_motion_frame(d, p, d_img, stats, static_cast<hipStream_t>(stream));
     // a frame that fails half-way must not leave half-recorded event pairs behind: mcpt_device_collect_stats would trip over them
     const size_t ev_used0 = d->ev_used, frame_ev_used0 = d->frame_ev_used;
     int slot_used = -1;
@@ -537,6 +566,7 @@ int mcpt_render(mcpt_device* d, const mcpt_render_params* p, double* img, mcpt_s
 int mcpt_sample_radiance(mcpt_device* d, uint64_t seed, const int32_t* pix, const int32_t* k, int64_t n, double* rgb)
 {
     if (!d || !pix || !k || !rgb || n < 0) return fail(MCPT_ERR_ARG, "bad argument");
+    if (const int rc = motion_home(d)) return rc;
     if (const int rc = geometry_gate(d)) return rc;
     return pair_call(d, pix, k, n, rgb, 3, ensure_dirs, [&](const int32_t* d_pix, const int32_t* d_k, double* d_rgb, hipStream_t st) {
         if (lens_active(d->lens)) {

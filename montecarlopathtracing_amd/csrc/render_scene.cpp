@@ -260,8 +260,18 @@ int mcpt_render_scene_lens(const char* path, const char* filename, int32_t spp, 
 int mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
                           const mcpt_lens* lens, const char* environment_pfm, double environment_scale, mcpt_stats* stats)
 {
+    return mcpt_render_scene_motion(path, filename, spp, opt, opt_bytes, lens, environment_pfm, environment_scale, nullptr, nullptr, nullptr, stats);
+}
+
+int mcpt_render_scene_motion(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
+                             const mcpt_lens* lens, const char* environment_pfm, double environment_scale, const char* end_obj,
+                             const char* end_camera, const mcpt_shutter* shutter, mcpt_stats* stats)
+{
     if (!path || !filename || spp <= 0 || opt_bytes < 0 || (opt_bytes > 0 && !opt)) return fail(MCPT_ERR_ARG, "bad argument");
     if (int lrc = lens_check(lens)) return lrc;
+    if (shutter) { if (int src = shutter_check(shutter)) return src; }
+    if (!shutter && (end_obj || end_camera)) return fail(MCPT_ERR_ARG, "an end .obj or .camera needs a shutter");
+    if (shutter && shutter->steps > spp) return fail(MCPT_ERR_ARG, "the shutter has more steps than the frame has samples per pixel");
     // the environment map is read and checked before anything else is read or written
     std::vector<float> env_rgb;
     mcpt_environment env{};
@@ -288,6 +298,11 @@ int mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, c
         return fail(MCPT_ERR_ARG, "a noise target, a time budget, an adaptive frame, MCPT_OUT_ERROR_PFM, MCPT_OUT_DENOISED or MCPT_OUT_AOV_PFM renders "
                                   "on one GPU without a checkpoint");
     if ((o.output_flags & MCPT_OUT_DENOISED) && spp < 2) return fail(MCPT_ERR_ARG, "MCPT_OUT_DENOISED needs N >= 2 (a variance estimate)");
+    if (shutter && (o.checkpoint || o.num_devices != 0 || adaptive || (o.output_flags & (MCPT_OUT_DENOISED | MCPT_OUT_AOV_PFM))))
+        return fail(MCPT_ERR_ARG, "a motion frame renders on one GPU without a checkpoint, and neither adaptively nor with MCPT_OUT_DENOISED or MCPT_OUT_AOV_PFM");
+    // (the steps are contiguous sample ranges: a frame stopped at k < N would show the first part of the shutter only)
+    if (shutter && (o.noise_target > 0 || o.time_budget_s > 0))
+        return fail(MCPT_ERR_ARG, "a motion frame renders all its samples: a noise target or a time budget would stop it inside the shutter");
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     mcpt_scene* sc = nullptr;
@@ -295,6 +310,15 @@ int mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, c
     if (rc) return rc;
     if (o.width > 0 && o.height > 0) mcpt_scene_set_resolution(sc, o.width, o.height);
     const Scene& s = sc->s;
+    // key 1 of the motion is read and compared with the scene before a device is made or anything is written
+    std::vector<double> v_end;
+    mcpt_camera_key cam_end{};
+    if (shutter) {
+        std::string merr;
+        if (end_obj) rc = load_end_positions(s, end_obj, o.load_flags, v_end, merr);
+        if (rc == MCPT_OK && end_camera) rc = load_end_camera(end_camera, cam_end, merr);
+        if (rc) { mcpt_scene_free(sc); return fail(rc, merr); }
+    }
     if (talk) {
         std::printf("%s%s.obj\nnumber of materials = %zu\nnumber of vertices = %zu\nnumber of faces = %zu\n", path, filename,
                     s.materials.size(), s.v.size(), s.faces.size());
@@ -307,6 +331,7 @@ int mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, c
     else rc = mcpt_device_create(sc, o.device, &dev);
     if (rc == MCPT_OK && lens) rc = many ? mcpt_multi_set_lens(multi, lens) : mcpt_device_set_lens(dev, lens);
     if (rc == MCPT_OK && environment_pfm) rc = many ? mcpt_multi_set_environment(multi, &env) : mcpt_device_set_environment(dev, &env);
+    if (rc == MCPT_OK && shutter) rc = mcpt_device_set_motion(dev, end_obj ? v_end.data() : nullptr, end_camera ? &cam_end : nullptr, shutter);
     if (rc) { if (dev) mcpt_device_free(dev); if (multi) mcpt_multi_free(multi); mcpt_scene_free(sc); return rc; }
     if (talk && many) std::printf("rendering on %d GPUs\n", mcpt_multi_num_devices(multi));
     if (many && o.checkpoint) {

@@ -79,6 +79,8 @@ struct Scene {
 int load_scene_files(const std::string& path, const std::string& filename, int load_flags, Scene& out, std::string& err);
 int finish_scene(Scene& s, const std::string& what, std::string& err);
 int find_material(const Scene& s, const std::string& name);
+int load_end_positions(const Scene& base, const std::string& obj_file, int load_flags, std::vector<double>& v9, std::string& err);
+int load_end_camera(const std::string& file, mcpt_camera_key& out, std::string& err);
 // bvh_build.cpp
 uint32_t morton_code(float x, float y, float z);
 uint32_t morton_code_in(float x, float y, float z, const float lo[3], const float span[3]);

@@ -388,6 +388,38 @@ int load_scene_files(const std::string& path, const std::string& filename, int l
     return finish_scene(s, base, err);
 }
 
+// Key 1 of a motion (mcpt_render_scene_motion): the positions of the faces of obj_file, read as base's own .obj was (same flags, its
+// materials by name) -- the same faces moved, or MCPT_ERR_PARSE.
+int load_end_positions(const Scene& base, const std::string& obj_file, int load_flags, std::vector<double>& v9, std::string& err)
+{
+    Scene end;
+    end.materials.resize(base.materials.size());
+    for (size_t i = 0; i < base.materials.size(); i++) end.materials[i].name = base.materials[i].name;
+    if (const int rc = read_obj(obj_file, load_flags, end, err)) return rc;
+    if (end.faces.size() != base.faces.size()) {
+        err = obj_file + " has " + std::to_string(end.faces.size()) + " faces, the scene " + std::to_string(base.faces.size());
+        return MCPT_ERR_PARSE;
+    }
+    v9.resize(end.faces.size() * 9);
+    for (size_t i = 0; i < end.faces.size(); i++) {
+        if (end.faces[i].material != base.faces[i].material) { err = obj_file + ": face " + std::to_string(i) + " has another material than the scene's"; return MCPT_ERR_PARSE; }
+        for (int c = 0; c < 3; c++) { v9[i * 9 + c * 3] = end.faces[i].v[c].x; v9[i * 9 + c * 3 + 1] = end.faces[i].v[c].y; v9[i * 9 + c * 3 + 2] = end.faces[i].v[c].z; }
+    }
+    return MCPT_OK;
+}
+
+// ... and its camera: eye, lookat, up and fovy of a .camera file
+int load_end_camera(const std::string& file, mcpt_camera_key& out, std::string& err)
+{
+    Scene c;
+    if (const int rc = read_camera(file, c, err)) return rc;
+    const Vec3 src[3] = {c.eye, c.look_at, c.up};
+    double* dst[3] = {out.eye, out.look_at, out.up};
+    for (int i = 0; i < 3; i++) { dst[i][0] = src[i].x; dst[i][1] = src[i].y; dst[i][2] = src[i].z; }
+    out.fovy = c.fovy;
+    return MCPT_OK;
+}
+
 // what read_scene leaves behind once the three files are in: sanity checks, lights -> materials, light area tables
 int finish_scene(Scene& s, const std::string& what, std::string& err)
 {

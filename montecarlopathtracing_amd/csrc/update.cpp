@@ -31,9 +31,12 @@ void light_vertices(const Scene& s, const double* v, std::vector<double>& out)
         for (int32_t f : s.materials[l.material].faces) out.insert(out.end(), v + size_t(f) * 9, v + size_t(f) * 9 + 9);
 }
 
+}  // namespace
+
 // First update: the faces in .obj order become resident (device creation frees its staging copy, and a host-built device never had one)
 int stage_faces(mcpt_device* d)
 {
+    if (d->upd) return MCPT_OK;
     const Scene& s = d->scene->s;
     const int t = d->bi.t;
     std::unique_ptr<Update> u(new Update);
@@ -68,6 +71,8 @@ int stage_faces(mcpt_device* d)
     d->upd = std::move(u);
     return MCPT_OK;
 }
+
+namespace {
 
 // The refit's bottom-up schedule, once per hierarchy: the nodes in breadth-first order from the root are grouped by depth, and a child is
 // one level below its parent.  With it the slot -> face table and the side array of exact boxes.
@@ -272,6 +277,8 @@ int update_geometry(mcpt_device* d, const double* d_v, int32_t mode, mcpt_update
     return MCPT_OK;
 }
 
+}  // namespace
+
 // nothing of the device is in flight afterwards: both frame slots (a pipelined frame ends on the old geometry), the library's streams
 int wait_for_frames(mcpt_device* d)
 {
@@ -282,6 +289,39 @@ int wait_for_frames(mcpt_device* d)
     return MCPT_OK;
 }
 
+int refit_geometry(mcpt_device* d, const double* d_v, mcpt_update_info* info)
+{
+    return update_geometry(d, d_v, MCPT_UPDATE_REFIT, info, std::chrono::steady_clock::now());
+}
+
+// a camera the frame cannot be formed from is refused, not rendered as NaN
+int camera_check(const double eye[3], const double look_at[3], const double up[3], double fovy)
+{
+    const Vec3 e{eye[0], eye[1], eye[2]}, l{look_at[0], look_at[1], look_at[2]}, w{up[0], up[1], up[2]};
+    const Vec3 dir = l - e, side = cross(dir, w);
+    const double all = e.x + e.y + e.z + l.x + l.y + l.z + w.x + w.y + w.z + fovy;
+    if (!std::isfinite(all) || !(fovy > 0.0 && fovy < 180.0) || !(norm(dir) > 0.0) || !(norm(w) > 0.0) || !(norm(side) > 0.0))
+        return fail(MCPT_ERR_ARG, "camera: finite numbers, 0 < fovy < 180, eye != look_at and up not along the view direction");
+    return MCPT_OK;
+}
+
+void camera_apply(mcpt_device* d, const double eye[3], const double look_at[3], const double up[3], double fovy)
+{
+    Scene c;                                        // camera_frame reads the camera and the frame size
+    c.eye = Vec3{eye[0], eye[1], eye[2]}; c.look_at = Vec3{look_at[0], look_at[1], look_at[2]}; c.up = Vec3{up[0], up[1], up[2]};
+    c.fovy = fovy; c.width = d->width; c.height = d->height;
+    const CameraFrame cf = camera_frame(c);
+    DCamera& cam = d->ds.cam;
+    const Vec3 src[4] = {cf.eye, cf.start_point, cf.screen_pdx, cf.screen_pdy};
+    double* dst[4] = {cam.eye, cam.start_point, cam.pdx, cam.pdy};
+    for (int i = 0; i < 4; i++) { dst[i][0] = src[i].x; dst[i][1] = src[i].y; dst[i][2] = src[i].z; }
+    d->cam_eye = c.eye; d->cam_look_at = c.look_at; d->cam_up = c.up; d->cam_fovy = fovy;
+    d->dirs_ready = false;
+    d->pos.reset();
+}
+
+namespace {
+
 // what both forms check before anything is touched
 int update_checks(mcpt_device* d, const double* v, int32_t mode)
 {
@@ -290,7 +330,8 @@ int update_checks(mcpt_device* d, const double* v, int32_t mode)
     if (const int rc = require_device()) return rc;
     if (d->refs.load() > 1) return fail(MCPT_ERR_ARG, "a progressive frame of the device is alive: it is defined over one geometry and camera");
     if (const int rc = wait_for_frames(d)) return rc;
-    if (!d->upd) { if (const int rc = stage_faces(d)) return rc; }
+    if (const int rc = stage_faces(d)) return rc;
+    if (const int rc = motion_home(d)) return rc;   // new vertices are a new key 0: the update's info compares with the old one
     return MCPT_OK;
 }
 
@@ -303,7 +344,9 @@ int mcpt_device_update_vertices_device(mcpt_device* d, const double* d_v, int32_
     const auto t0 = std::chrono::steady_clock::now();
     if (const int rc = update_checks(d, d_v, mode)) return rc;
     if (stream) HIP_TRY(hipStreamSynchronize(static_cast<hipStream_t>(stream)));
-    return update_geometry(d, d_v, mode, info, t0);
+    const int rc = update_geometry(d, d_v, mode, info, t0);
+    if (rc == MCPT_OK) motion_clear(d);             // the update has succeeded: a new key 0
+    return rc;
 }
 
 // an upload into the staging array, then the device form
@@ -313,13 +356,16 @@ int mcpt_device_update_vertices(mcpt_device* d, const double* v, int32_t mode, m
     if (const int rc = update_checks(d, v, mode)) return rc;
     d->geometry_failed = true;                      // (the staging array is what mcpt_device_get_vertices reports)
     HIP_TRY(hipMemcpy(d->upd->v9.get(), v, size_t(d->bi.t) * 9 * sizeof(double), hipMemcpyHostToDevice));
-    return update_geometry(d, d->upd->v9.get(), mode, info, t0);
+    const int rc = update_geometry(d, d->upd->v9.get(), mode, info, t0);
+    if (rc == MCPT_OK) motion_clear(d);             // the update has succeeded: a new key 0
+    return rc;
 }
 
 int mcpt_device_get_vertices(mcpt_device* d, double* v)
 {
     if (!d || !v) return fail(MCPT_ERR_ARG, "null argument");
     if (const int rc = require_device()) return rc;
+    if (const int rc = motion_home(d)) return rc;
     const size_t t = size_t(d->bi.t);
     if (d->upd) {
         HIP_TRY(hipSetDevice(d->ordinal));
@@ -337,25 +383,11 @@ int mcpt_device_set_camera(mcpt_device* d, const double eye[3], const double loo
     if (!d || !eye || !look_at || !up) return fail(MCPT_ERR_ARG, "null argument");
     if (const int rc = require_device()) return rc;
     if (d->refs.load() > 1) return fail(MCPT_ERR_ARG, "a progressive frame of the device is alive: it is defined over one geometry and camera");
-    {   // a camera the frame cannot be formed from is refused, not rendered as NaN
-        const Vec3 e{eye[0], eye[1], eye[2]}, l{look_at[0], look_at[1], look_at[2]}, w{up[0], up[1], up[2]};
-        const Vec3 dir = l - e, side = cross(dir, w);
-        const double all = e.x + e.y + e.z + l.x + l.y + l.z + w.x + w.y + w.z + fovy;
-        if (!std::isfinite(all) || !(fovy > 0.0 && fovy < 180.0) || !(norm(dir) > 0.0) || !(norm(w) > 0.0) || !(norm(side) > 0.0))
-            return fail(MCPT_ERR_ARG, "camera: finite numbers, 0 < fovy < 180, eye != look_at and up not along the view direction");
-    }
+    if (const int rc = camera_check(eye, look_at, up, fovy)) return rc;
     if (const int rc = wait_for_frames(d)) return rc;       // a frame in flight still reads the primary directions
-    Scene c;                                        // camera_frame reads the camera and the frame size
-    c.eye = Vec3{eye[0], eye[1], eye[2]}; c.look_at = Vec3{look_at[0], look_at[1], look_at[2]}; c.up = Vec3{up[0], up[1], up[2]};
-    c.fovy = fovy; c.width = d->width; c.height = d->height;
-    const CameraFrame cf = camera_frame(c);
-    DCamera& cam = d->ds.cam;
-    const Vec3 src[4] = {cf.eye, cf.start_point, cf.screen_pdx, cf.screen_pdy};
-    double* dst[4] = {cam.eye, cam.start_point, cam.pdx, cam.pdy};
-    for (int i = 0; i < 4; i++) { dst[i][0] = src[i].x; dst[i][1] = src[i].y; dst[i][2] = src[i].z; }
-    d->cam_eye = c.eye; d->cam_look_at = c.look_at; d->cam_up = c.up; d->cam_fovy = fovy;
-    d->dirs_ready = false;
-    d->pos.reset();
+    if (const int rc = motion_home(d)) return rc;           // a new camera is a new key 0: the geometry returns to the old one's first
+    motion_clear(d);
+    camera_apply(d, eye, look_at, up, fovy);
     return MCPT_OK;
 }
 
