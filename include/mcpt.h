@@ -434,6 +434,40 @@ int mcpt_environment_sample(mcpt_device*, uint64_t seed, const int32_t* pix, con
  * floats rgb holds; too few: MCPT_ERR_ARG).  MCPT_ERR_IO: no file; MCPT_ERR_PARSE: not a colour PFM. */
 int mcpt_read_pfm(const char* file, int32_t* width, int32_t* height, float* rgb, int64_t cap);
 
+/* ---- light sampling: one shadow ray per vertex from a weighted light pick (no reference counterpart) ---- */
+/* MCPT_VERSION stays 105 with this block, as it did with the environment, update and motion blocks: a binder detects these entry points by
+ * symbol (dlsym of mcpt_device_set_light_sampling), not by the version number. */
+/* MCPT_LIGHTS_ALL, the default and the reference's loop: every vertex samples every light of the scene, one shadow ray each.
+ * MCPT_LIGHTS_ONE: every vertex picks ONE light l with probability p_l, samples it as MCPT_LIGHTS_ALL samples light l (the same Philox
+ * block l, area range and visibility rule; no light before it to inherit a material from) and scales the contribution by 1 / p_l.  The
+ * bounce draws do not depend on the lights, so the paths -- geometry, throughput, emitter hits -- are the same in both modes, sample for
+ * sample; only the direct light at the vertices differs, with the same expectation.  An active environment keeps its own shadow ray.
+ *   table (host, fp64): weights w_l >= 0; cdf[l] = the running sum w_0 + ... + w_l, left to right; Z = cdf[nl-1]; pdf[l] = w_l / Z; the
+ *     kernels scale by the quotient 1.0 / pdf[l], formed on the host.  Default weights: w_l = lum(radiance_l) * total_area_l,
+ *     lum = (0.2126 r + 0.7152 g) + 0.0722 b; if every one of them is 0 (or not finite), w_l = 1.  A device whose emitters an update moves
+ *     makes its default weights again from the new areas.
+ *   the caller's weights: one per light of the scene, finite and >= 0, not all 0 (else MCPT_ERR_ARG).  A light of weight 0 is never
+ *     picked: the estimator then leaves that light's direct light out, and keeping it unbiased is the caller's business.
+ *   pick at vertex `depth` of a camera sample: u = slot 0 of Philox block nl + 3 of that depth (nl = the scene's lights; the lights use
+ *     blocks 0..nl-1, the bounce nl and nl+1, the environment nl+2: every other draw keeps its value); x = u * Z; l = the smallest l with
+ *     x < cdf[l], by binary search, clamped to the last light of non-zero weight.
+ * A scene with no light or one light renders the same bits in both modes.  The setting is device state: every frame, progressive or
+ * adaptive pass, motion frame and (pixel, sample) query that follows uses it (a progressive frame should not see it change between its
+ * passes).  The megakernel counts a picked light behind the surface as shadow_skipped and traces no ray for it. */
+#define MCPT_LIGHTS_ALL 0
+#define MCPT_LIGHTS_ONE 1
+typedef struct { int32_t mode, num_weights; const double* weights; } mcpt_light_sampling;   /* num_weights 0 / weights NULL: the default weights */
+/* NULL means MCPT_LIGHTS_ALL.  MCPT_ERR_ARG: an unknown mode, num_weights != 0 that is not the scene's light count, bad weights. */
+int mcpt_device_set_light_sampling(mcpt_device*, const mcpt_light_sampling*);
+/* *mode and pdf[num_lights] (each may be NULL): the table's probabilities; 1 for every light under MCPT_LIGHTS_ALL */
+int mcpt_device_get_light_sampling(const mcpt_device*, int32_t* mode, double* pdf);
+/* host only (no GPU needed): the table of the scene's lights under `weights` (NULL: the default weights) -> cdf[num_lights], pdf[num_lights].
+ * MCPT_ERR_ARG: a scene without lights, bad weights. */
+int mcpt_scene_light_pick_table(const mcpt_scene*, const double* weights_or_null, double* cdf, double* pdf);
+/* test seam: the pick at vertex `depth` of camera samples (pix[i], k[i]) -> light[n], pdf[n].  MCPT_ERR_ARG unless the device picks
+ * (MCPT_LIGHTS_ONE on a scene of two or more lights). */
+int mcpt_light_pick(mcpt_device*, uint64_t seed, const int32_t* pix, const int32_t* k, int32_t depth, int64_t n, int32_t* light, double* pdf);
+
 /* ---- integrator over several GPUs of one node (no reference counterpart: generateImg is single-process OpenMP) ---- */
 /* The frame is cut into tiles dealt to the GPUs exactly as mcpt_render_params.rank/world describe (rank r = devices[r]); the scene
  * is resident on every GPU; one host thread per GPU renders its tiles; at the end of the frame every rank's pixels travel as one
@@ -461,6 +495,7 @@ int  mcpt_multi_last_timing(const mcpt_multi*, double* render_ms, double* gather
 void mcpt_multi_free(mcpt_multi*);
 int  mcpt_multi_set_lens(mcpt_multi*, const mcpt_lens*);     /* every device of the group (NULL: the pinhole) */
 int  mcpt_multi_set_environment(mcpt_multi*, const mcpt_environment*);   /* every device of the group (NULL: none) */
+int  mcpt_multi_set_light_sampling(mcpt_multi*, const mcpt_light_sampling*);   /* every device of the group (NULL: MCPT_LIGHTS_ALL); a refused argument changes no device */
 
 /* ---- one process per GPU (since 105; no reference counterpart) ---- */
 /* The same exchange between the PROCESSES of a launch: every rank is a process that drives one GPU through mcpt_device_* (params->rank /
@@ -566,6 +601,14 @@ int  mcpt_render_scene_lens(const char* path, const char* filename, int32_t spp,
  * without it nor the reverse, and a frame without one (or with an inactive one) keeps the identity it had before environments existed. */
 int  mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, int64_t options_bytes,
                            const mcpt_lens*, const char* environment_pfm, double environment_scale, mcpt_stats* stats);
+/* mcpt_render_scene_env under a light sampling (NULL: MCPT_LIGHTS_ALL, = mcpt_render_scene_env), set on the device or on every GPU of the
+ * options; an invalid one is refused (MCPT_ERR_ARG) before anything is read or written, a weight count that is not the scene's light
+ * count once the scene is read.  A checkpoint's frame identity includes the mode and the table's probabilities when the device picks
+ * (MCPT_LIGHTS_ONE on a scene of two or more lights): such a frame never resumes from a checkpoint written under another setting, and a
+ * frame that does not pick keeps the identity it had before. */
+int  mcpt_render_scene_lights(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, int64_t options_bytes,
+                              const mcpt_lens*, const char* environment_pfm, double environment_scale, const mcpt_light_sampling*,
+                              mcpt_stats* stats);
 
 /* ---- geometry and camera updates (since the update change): a second frame of a scene in which something moved, without a new scene ---- */
 /* mcpt_device_update_vertices replaces the positions of every face on a live device: v = [num_faces][9] doubles (v1 v2 v3 of every face,

@@ -87,6 +87,11 @@ class Environment(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class LightSampling(C.Structure):
+    """mcpt_light_sampling (mcpt.h: light sampling)"""
+    _fields_ = [("mode", C.c_int32), ("num_weights", C.c_int32), ("weights", C.POINTER(C.c_double))]
+
+
 class FastInfo(C.Structure):
     """mcpt_fast_info: shape and origin of the culling hierarchy a device's fast walk walks (mcpt_device_fast_hierarchy)"""
     _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_tris", "enabled", "cw_stack_need", "max_depth", "builder", "clusters", "reserved")]
@@ -156,6 +161,8 @@ EXPORTS = [
     "mcpt_device_get_camera", "mcpt_multi_update_vertices", "mcpt_multi_set_camera",
     "mcpt_device_set_motion", "mcpt_device_set_motion_device", "mcpt_device_clear_motion", "mcpt_device_get_motion", "mcpt_device_motion_info",
     "mcpt_shutter_time", "mcpt_shutter_step", "mcpt_render_scene_motion",
+    "mcpt_device_set_light_sampling", "mcpt_device_get_light_sampling", "mcpt_multi_set_light_sampling", "mcpt_scene_light_pick_table",
+    "mcpt_light_pick", "mcpt_render_scene_lights",
 ]
 
 
@@ -299,6 +306,13 @@ def lib():
     L.mcpt_shutter_step.restype = C.c_int32
     L.mcpt_render_scene_motion.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens), C.c_char_p,
                                            C.c_double, C.c_char_p, C.c_char_p, C.POINTER(Shutter), C.POINTER(Stats)]
+    L.mcpt_device_set_light_sampling.argtypes = [P, C.POINTER(LightSampling)]
+    L.mcpt_device_get_light_sampling.argtypes = [P, I32, D]
+    L.mcpt_multi_set_light_sampling.argtypes = [P, C.POINTER(LightSampling)]
+    L.mcpt_scene_light_pick_table.argtypes = [P, D, D, D]
+    L.mcpt_light_pick.argtypes = [P, C.c_uint64, I32, I32, C.c_int32, C.c_int64, I32, D]
+    L.mcpt_render_scene_lights.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens), C.c_char_p,
+                                           C.c_double, C.POINTER(LightSampling), C.POINTER(Stats)]
     _lib = L
     return L
 

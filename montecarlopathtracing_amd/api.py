@@ -6,7 +6,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, Environment, FastInfo, Lens, McptError, MotionInfo, Noise, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -95,6 +95,26 @@ def allow_runtime_mismatch(allow=True):
 
 def device_count():
     return lib().mcpt_device_count()
+
+
+LIGHTS_ALL, LIGHTS_ONE = 0, 1
+
+
+def make_light_sampling(mode="all", weights=None):
+    """An mcpt_light_sampling and the float64 weights it points to (keep both alive while it is used); (None, None) for "all" / None.
+    mode: "all", "one", None, or a dict of these two arguments."""
+    if isinstance(mode, dict):
+        mode, weights = mode.get("mode", "one"), mode.get("weights")
+    if mode is None or mode == "all":
+        if weights is not None:
+            raise ValueError('weights go with mode "one"')
+        return None, None
+    if mode != "one":
+        raise ValueError('light sampling mode must be "all" or "one"')
+    if weights is None:
+        return LightSampling(LIGHTS_ONE, 0, None), None
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    return LightSampling(LIGHTS_ONE, w.shape[0], _p(w, C.c_double)), w
 
 
 class Scene:
@@ -208,6 +228,22 @@ class Scene:
         a = np.zeros(1)
         check(lib().mcpt_scene_get_light(self._h, i, name, _p(rad, C.c_double), _p(m, C.c_int32), _p(a, C.c_double)))
         return name.value.decode(), rad, int(m[0]), float(a[0])
+
+    def light_pick_table(self, weights=None):
+        """The pick table of MCPT_LIGHTS_ONE for this scene's lights (mcpt_scene_light_pick_table; host only): the running sums cdf, the
+        probabilities pdf and the factors 1.0 / pdf (0 for a light of weight 0) the kernels scale by.  weights: None (luminance x area) or
+        one non-negative weight per light."""
+        n = self.info.num_lights
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if w.shape[0] != n:
+                raise ValueError("one weight per light of the scene")
+        cdf, pdf = np.zeros(n), np.zeros(n)
+        check(lib().mcpt_scene_light_pick_table(self._h, _p(w, C.c_double) if w is not None else None, _p(cdf, C.c_double), _p(pdf, C.c_double)))
+        inv = np.zeros(n)
+        np.divide(1.0, pdf, out=inv, where=pdf > 0)
+        return cdf, pdf, inv
 
     def trace_engine(self):
         """'pool' or 'vote': the closest-hit engine a device created for this scene now would run (mcpt_scene_trace_engine)"""
@@ -416,6 +452,30 @@ class Device:
         check(lib().mcpt_environment_sample(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), int(depth), n, _p(dirs, C.c_double),
                                             _p(pdf, C.c_double), _p(rgb, C.c_double)))
         return dirs, pdf, rgb
+
+    def set_light_sampling(self, mode="all", weights=None):
+        """How every later frame, pass and sample_radiance samples the scene's lights (mcpt_device_set_light_sampling): "all" (or None) --
+        every light at every vertex, the reference's loop -- or "one": one light per vertex, picked with probability weight / sum and
+        divided by it.  weights: None (luminance x area) or one non-negative weight per light; a light of weight 0 is never picked."""
+        ls, keep = make_light_sampling(mode, weights)
+        check(lib().mcpt_device_set_light_sampling(self._h, C.byref(ls) if ls is not None else None))
+        del keep
+
+    def light_sampling(self):
+        """the device's light sampling: (mode, pdf) with mode "all" or "one" and pdf the pick probability of every light (1 under "all")"""
+        m = C.c_int32()
+        pdf = np.zeros(self.scene.info.num_lights)
+        check(lib().mcpt_device_get_light_sampling(self._h, C.byref(m), _p(pdf, C.c_double) if pdf.size else None))
+        return ("one" if m.value == LIGHTS_ONE else "all"), pdf
+
+    def light_pick(self, seed, pix, k, depth):
+        """the light "one" picks at vertex `depth` of camera samples (pix[i], k[i]): indices (n,) int32, their probabilities (n,)"""
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        n = pix.shape[0]
+        light, pdf = np.zeros(n, dtype=np.int32), np.zeros(n)
+        check(lib().mcpt_light_pick(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), int(depth), n, _p(light, C.c_int32), _p(pdf, C.c_double)))
+        return light, pdf
 
     def update_vertices(self, v, mode="refit", stream=None):
         """New positions for every face, in place (mcpt_device_update_vertices): v = [num_faces, 9] (v1 v2 v3 of every face, .obj order) as
@@ -649,6 +709,12 @@ class MultiDevice:
         check(lib().mcpt_multi_set_environment(self._h, C.byref(e)))
         del tex
 
+    def set_light_sampling(self, mode="all", weights=None):
+        """the same light sampling on every device of the group (Device.set_light_sampling)"""
+        ls, keep = make_light_sampling(mode, weights)
+        check(lib().mcpt_multi_set_light_sampling(self._h, C.byref(ls) if ls is not None else None))
+        del keep
+
     def update_vertices(self, v, mode="refit"):
         """new positions on every device of the group (Device.update_vertices, host arrays); the info record of devices[0]"""
         v = _host_vertices(v, self.scene.info.num_faces)
@@ -785,7 +851,8 @@ def morton_code(x, y, z):
 
 def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, height=0, quiet=True, output_prefix=None, stats=None,
                  load_flags=0, output_flags=0, checkpoint=None, checkpoint_parts=0, devices=None, gather=GATHER_PEER, noise_target=0.0,
-                 time_budget_s=0.0, adaptive_min_spp=0, abs_target=0.0, lens=None, environment=None, environment_scale=1.0, motion=None):
+                 time_budget_s=0.0, adaptive_min_spp=0, abs_target=0.0, lens=None, environment=None, environment_scale=1.0, motion=None,
+                 light_sampling=None):
     """render_scene(path, filename, N) of MTPC/MTPC.cpp:35; writes <prefix>-SPP<N>.png (default ../result/<filename>).
     devices: list of GPU ordinals, or -1 for every visible GPU (the frame is then rendered by mcpt_multi_*).
     noise_target / time_budget_s / OUT_ERROR_PFM: a progressive frame that may stop at k < N samples (<prefix>-SPP<k>.png).
@@ -794,7 +861,9 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
     lens: None (the pinhole), a Lens or a dict of Device.set_lens's arguments; rendered through mcpt_render_scene_lens.
     environment: None, or the path of a colour PFM lat-long map (environment_scale: its scale); rendered through mcpt_render_scene_env.
     motion: None, or a dict of end_obj and end_camera (file paths, either may be missing), shutter = (open, close) and steps: the shutter
-    frame between the scene and those files (mcpt_render_scene_motion)."""
+    frame between the scene and those files (mcpt_render_scene_motion).
+    light_sampling: None / "all", "one", or a dict of Device.set_light_sampling's arguments; rendered through mcpt_render_scene_lights (not
+    together with motion)."""
     dev_arr, ndev = None, 0
     if devices == -1:
         ndev = -1
@@ -805,7 +874,15 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
                            load_flags, output_flags, checkpoint.encode() if checkpoint else None, checkpoint_parts, 0,
                            ndev, gather, dev_arr, noise_target, time_budget_s, adaptive_min_spp, 0, abs_target)
     st = C.byref(stats) if stats is not None else None
-    if motion is not None:
+    ls, keep_w = make_light_sampling(light_sampling)
+    if ls is not None:
+        if motion is not None:
+            raise ValueError("light_sampling and motion do not go together in render_scene")
+        check(lib().mcpt_render_scene_lights(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o),
+                                             C.byref(_as_lens(lens)) if lens is not None else None,
+                                             environment.encode() if environment is not None else None, float(environment_scale), C.byref(ls), st))
+        del keep_w
+    elif motion is not None:
         sh = _shutter(motion.get("shutter", (0.0, 1.0)), motion.get("steps", 1))
         end_obj, end_camera = motion.get("end_obj"), motion.get("end_camera")
         check(lib().mcpt_render_scene_motion(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o),

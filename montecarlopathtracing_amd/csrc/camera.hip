@@ -40,8 +40,8 @@ __global__ void __launch_bounds__(256) k_camera_rays(DLens lens, unsigned long l
 
 // The megakernel with a lens: one lane per camera sample traces its own camera ray (reference-shaped walk) and shades the path from its
 // hit, as k_shade_samples does from the pixel's shared one.  Lane (slot, k) -> rad[(slot*spp + k)*3], flags[slot*spp + k].  ENV: an active
-// environment (a camera ray that misses gives Le of its direction).
-template <bool ENV>
+// environment (a camera ray that misses gives Le of its direction).  ONE: S.pick is active (MCPT_LIGHTS_ONE).
+template <bool ENV, bool ONE>
 __global__ void __launch_bounds__(256) k_shade_samples_lens(DScene S, DLens lens, unsigned long long seed, const int32_t* __restrict__ pixels,
                                                             int first_slot, long long n_samples, int spp, int sample_base, double* __restrict__ rad,
                                                             uint8_t* __restrict__ flags, DCounters* ctr)
@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(256) k_shade_samples_lens(DScene S, DLens lens
         double out[3] = {0, 0, 0};
         if (ok) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix; key.sample = (uint32_t)k;
-            shade_path<ENV>(S, key, r.d, h, out, ls);
+            shade_path<ENV, ONE>(S, key, r.d, h, out, ls);
         } else if (ENV) env_camera_miss(S, r.d, out);
         rad[gid * 3] = out[0]; rad[gid * 3 + 1] = out[1]; rad[gid * 3 + 2] = out[2];
         flags[gid] = ok ? 1 : 0;
@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(256) k_shade_samples_lens(DScene S, DLens lens
 }
 
 // mcpt_sample_radiance with a lens: arbitrary (pixel, k) pairs
-template <bool ENV>
+template <bool ENV, bool ONE>
 __global__ void __launch_bounds__(256) k_sample_radiance_lens(DScene S, DLens lens, unsigned long long seed, const int32_t* __restrict__ pix,
                                                               const int32_t* __restrict__ ks, long long n, double* __restrict__ rgb, DCounters* ctr)
 {
@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(256) k_sample_radiance_lens(DScene S, DLens le
         ls.primary = 1; ls.samples = 1;
         if (trace_closest(S, r, h, w)) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix[gid]; key.sample = (uint32_t)ks[gid];
-            shade_path<ENV>(S, key, r.d, h, out, ls);
+            shade_path<ENV, ONE>(S, key, r.d, h, out, ls);
         } else if (ENV) env_camera_miss(S, r.d, out);
         ls.nodes += w.nodes; ls.tris += w.tris;
         rgb[gid * 3] = out[0]; rgb[gid * 3 + 1] = out[1]; rgb[gid * 3 + 2] = out[2];
@@ -224,19 +224,25 @@ void launch_shade_samples_lens(const DScene& S, const DLens& lens, unsigned long
 {
     const long long n = (long long)n_slots * spp;
     if (n <= 0) return;
-    if (env_on(S.env))
-        hipLaunchKernelGGL(k_shade_samples_lens<true>, dim3(blocks_of(n, 256)), dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad,
-                           d_flags, ctr);
+    const dim3 grid(blocks_of(n, 256));
+    if (pick_on(S.pick)) {
+        if (env_on(S.env)) hipLaunchKernelGGL((k_shade_samples_lens<true, true>), grid, dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad, d_flags, ctr);
+        else hipLaunchKernelGGL((k_shade_samples_lens<false, true>), grid, dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad, d_flags, ctr);
+    } else if (env_on(S.env))
+        hipLaunchKernelGGL((k_shade_samples_lens<true, false>), grid, dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad, d_flags, ctr);
     else
-        hipLaunchKernelGGL(k_shade_samples_lens<false>, dim3(blocks_of(n, 256)), dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad,
-                           d_flags, ctr);
+        hipLaunchKernelGGL((k_shade_samples_lens<false, false>), grid, dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad, d_flags, ctr);
 }
 void launch_sample_radiance_lens(const DScene& S, const DLens& lens, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, long long n,
                                  double* d_rgb, DCounters* ctr, hipStream_t st)
 {
     if (n <= 0) return;
-    if (env_on(S.env)) hipLaunchKernelGGL(k_sample_radiance_lens<true>, dim3(blocks_of(n, 256)), dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr);
-    else hipLaunchKernelGGL(k_sample_radiance_lens<false>, dim3(blocks_of(n, 256)), dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr);
+    const dim3 grid(blocks_of(n, 256));
+    if (pick_on(S.pick)) {
+        if (env_on(S.env)) hipLaunchKernelGGL((k_sample_radiance_lens<true, true>), grid, dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr);
+        else hipLaunchKernelGGL((k_sample_radiance_lens<false, true>), grid, dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr);
+    } else if (env_on(S.env)) hipLaunchKernelGGL((k_sample_radiance_lens<true, false>), grid, dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr);
+    else hipLaunchKernelGGL((k_sample_radiance_lens<false, false>), grid, dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr);
 }
 void launch_camera_pass(const DLens& lens, const WfArgs& a, long long n_samples, hipStream_t st)
 {

@@ -126,6 +126,15 @@ struct DEnv {
     double scale, Z;
 };
 
+// The light pick of MCPT_LIGHTS_ONE (vertex.hpp: light_pick; the table is built on the host by light_sampling.cpp).  All zero: every light
+// at every vertex, and the kernels are the instantiations without it.
+struct DLightPick {
+    const double* cdf;          // [num_lights] running sums of the lights' weights, left to right
+    const double* inv_pdf;      // [num_lights] 1 / p_l as the host formed it (a light of weight 0: 0, never read)
+    double Z;                   // cdf[num_lights - 1]
+    int32_t last, pad;          // the last light of non-zero weight
+};
+
 struct DScene {
     const DNode* nodes;
     const DTri* tris;
@@ -140,12 +149,17 @@ struct DScene {
     double area0;                                  // range of the frozen static u1 (Q1)
     DCamera cam;
     DEnv env;                                      // rgb == null: no (active) environment
+    DLightPick pick;                               // cdf == null: MCPT_LIGHTS_ALL (or a scene of fewer than two lights)
 };
 
 #if defined(__HIPCC__)
 __host__ __device__
 #endif
 inline bool env_on(const DEnv& e) { return e.rgb != nullptr; }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool pick_on(const DLightPick& p) { return p.cdf != nullptr; }
 
 // device-side counters (one cache line)
 struct DCounters {

@@ -4,6 +4,7 @@
 //   device.cpp        device creation stage by stage, hierarchy queries, closest hit
 //   render.cpp        lenses, the integrator (megakernel and wavefront), mcpt_render*, statistics, (pixel, sample) queries
 //   progressive.cpp   progressive frames, AOVs, the denoiser
+//   light_sampling.cpp  MCPT_LIGHTS_ONE: the pick table, its upload, the pick's test seam
 //   motion.cpp        a device's motion: the shutter's steps between two keyframes, the return to key 0
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
@@ -54,6 +55,16 @@ struct EnvData {
     DevBuf<double> d_c, d_marg, d_cond;
     DEnv denv{};
 };
+// A device's light sampling when it is not MCPT_LIGHTS_ALL (light_sampling.cpp): the pick table on the host and on the GPU.  dpick is all
+// zero when the mode changes nothing (a scene of fewer than two lights).
+struct LightPickData {
+    int32_t mode = MCPT_LIGHTS_ALL;
+    bool own_weights = false;               // the caller's weights; else luminance x area, made again when an update moves an emitter
+    std::vector<double> weights;            // the caller's
+    std::vector<double> cdf, pdf;           // the table (the checkpoint identity mixes pdf in)
+    DevBuf<double> d_cdf, d_inv;
+    DLightPick dpick{};
+};
 }  // namespace mcpt
 
 struct mcpt_device {
@@ -76,6 +87,7 @@ struct mcpt_device {
     mcpt_lens lens{};                      // mcpt_device_set_lens (all zero: the reference's pinhole)
     mcpt::DevBuf<double> pos;              // W*H*3 image-plane points pos(i,j), made on the first frame under an active lens
     std::shared_ptr<const mcpt::EnvData> env;   // mcpt_device_set_environment (null: none); ds.env is its denv
+    std::shared_ptr<mcpt::LightPickData> pick;  // mcpt_device_set_light_sampling (null: MCPT_LIGHTS_ALL); ds.pick is its dpick
     // render workspace
     mcpt::DevBuf<int32_t> pixels; int64_t n_pixels = 0; int part_key[4] = {-1, -1, -1, -1};
     mcpt::Event ev[4];
@@ -221,6 +233,12 @@ int motion_passes(mcpt_device* d, int k0, int n, int N, hipStream_t st, const st
 // ---- environment.cpp
 int env_check(const mcpt_environment* e);
 int env_make(const mcpt_environment* e, std::shared_ptr<mcpt::EnvData>& out);   // tables + upload on the current device (e valid)
+
+// ---- light_sampling.cpp
+int light_sampling_check(const mcpt_light_sampling* ls);
+int light_weights_check(const mcpt_light_sampling* ls, size_t num_lights);   // the weights' count and values (MCPT_ERR_ARG)
+// the emitters' areas have changed (areas[num_lights], the device's light records as they are now): default weights are made again
+int light_pick_refresh(mcpt_device* d, const double* areas);
 
 // ---- render.cpp
 inline bool lens_active(const mcpt_lens& l) { return l.flags != 0 || l.aperture > 0.0; }

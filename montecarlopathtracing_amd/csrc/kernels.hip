@@ -179,7 +179,8 @@ __global__ void __launch_bounds__(256) k_primary_hits_reference(DScene S, const 
 // One lane per camera sample.  Samples of one pixel are consecutive lanes, so a wave starts from one shared
 // primary hit (coherent first vertex and shadow rays).  Radiance goes to rad[(slot*spp + k)*3]; lane k of a slot renders camera
 // sample sample_base + k (a whole frame: 0).  ENV: S.env is active (a pixel whose primary ray missed is folded from Le, not from rad).
-template <bool ENV>
+// ONE: S.pick is active (MCPT_LIGHTS_ONE: shade_path.hpp).
+template <bool ENV, bool ONE>
 __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long long seed, const double* __restrict__ dirs,
                                                        const int32_t* __restrict__ pixels, const PrimaryHit* __restrict__ hits,
                                                        int first_slot, long long n_samples, int spp, int sample_base, double* __restrict__ rad, DCounters* ctr)
@@ -196,7 +197,7 @@ __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long l
         if (ph.leaf >= 0) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix; key.sample = (uint32_t)(sample_base + k);
             Hit h; h.leaf = ph.leaf; h.t = ph.t; h.p = mk(ph.p[0], ph.p[1], ph.p[2]);
-            shade_path<ENV>(S, key, ld3(dirs + (size_t)pix * 3), h, r, ls);
+            shade_path<ENV, ONE>(S, key, ld3(dirs + (size_t)pix * 3), h, r, ls);
         }
         rad[gid * 3] = r[0]; rad[gid * 3 + 1] = r[1]; rad[gid * 3 + 2] = r[2];
     }
@@ -204,7 +205,7 @@ __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long l
 }
 
 // mcpt_sample_radiance: arbitrary (pixel, k) pairs, primary ray traced per sample.
-template <bool ENV>
+template <bool ENV, bool ONE>
 __global__ void __launch_bounds__(256) k_sample_radiance(DScene S, unsigned long long seed, const double* __restrict__ dirs,
                                                          const int32_t* __restrict__ pix, const int32_t* __restrict__ ks, long long n,
                                                          double* __restrict__ rgb, DCounters* ctr)
@@ -218,12 +219,23 @@ __global__ void __launch_bounds__(256) k_sample_radiance(DScene S, unsigned long
         ls.primary = 1; ls.samples = 1;
         if (trace_closest(S, r, h, w)) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix[gid]; key.sample = (uint32_t)ks[gid];
-            shade_path<ENV>(S, key, r.d, h, out, ls);
+            shade_path<ENV, ONE>(S, key, r.d, h, out, ls);
         } else if (ENV) env_camera_miss(S, r.d, out);
         ls.nodes += w.nodes; ls.tris += w.tris;
         rgb[gid * 3] = out[0]; rgb[gid * 3 + 1] = out[1]; rgb[gid * 3 + 2] = out[2];
     }
     flush_stats(ctr, ls);
+}
+
+// mcpt_light_pick: the light MCPT_LIGHTS_ONE picks at vertex `depth` of camera samples (pix[i], ks[i])
+__global__ void __launch_bounds__(256) k_light_pick(DLightPick pick, int nl, unsigned long long seed, const int32_t* __restrict__ pix, const int32_t* __restrict__ ks,
+                                                    int depth, long long n, int32_t* __restrict__ light)
+{
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= n) return;
+    RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix[gid]; key.sample = (uint32_t)ks[gid];
+    double inv_p;
+    light[gid] = light_pick(pick, key, (uint32_t)depth, (uint32_t)nl, inv_p);
 }
 
 // Per pixel: acc(float) += radiance/N for k = 0..N-1 in order (pathTracing.cpp:301,316-318 with D3), widened
@@ -564,15 +576,28 @@ void launch_shade_samples(const DScene& S, unsigned long long seed, const double
 {
     const long long n = (long long)n_slots * spp;
     if (n <= 0) return;
-    if (env_on(S.env)) hipLaunchKernelGGL(k_shade_samples<true>, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
-    else hipLaunchKernelGGL(k_shade_samples<false>, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
+    const dim3 grid(blocks_for(n, 256));
+    if (pick_on(S.pick)) {
+        if (env_on(S.env)) hipLaunchKernelGGL((k_shade_samples<true, true>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
+        else hipLaunchKernelGGL((k_shade_samples<false, true>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
+    } else if (env_on(S.env)) hipLaunchKernelGGL((k_shade_samples<true, false>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
+    else hipLaunchKernelGGL((k_shade_samples<false, false>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
 }
 void launch_sample_radiance(const DScene& S, unsigned long long seed, const double* d_dirs, const int32_t* d_pix, const int32_t* d_k,
                             long long n, double* d_rgb, DCounters* ctr, hipStream_t st)
 {
     if (n <= 0) return;
-    if (env_on(S.env)) hipLaunchKernelGGL(k_sample_radiance<true>, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
-    else hipLaunchKernelGGL(k_sample_radiance<false>, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
+    const dim3 grid(blocks_for(n, 256));
+    if (pick_on(S.pick)) {
+        if (env_on(S.env)) hipLaunchKernelGGL((k_sample_radiance<true, true>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
+        else hipLaunchKernelGGL((k_sample_radiance<false, true>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
+    } else if (env_on(S.env)) hipLaunchKernelGGL((k_sample_radiance<true, false>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
+    else hipLaunchKernelGGL((k_sample_radiance<false, false>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
+}
+void launch_light_pick(const DScene& S, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, int depth, long long n, int32_t* d_light, hipStream_t st)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_light_pick, dim3(blocks_for(n, 256)), dim3(256), 0, st, S.pick, S.num_lights, seed, d_pix, d_k, depth, n, d_light);
 }
 void launch_fold_samples(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int spp,
                          double* d_img, const DEnv& env, const double* d_dirs, hipStream_t st)

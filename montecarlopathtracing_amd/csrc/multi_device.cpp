@@ -212,6 +212,23 @@ int mcpt_multi_set_environment(mcpt_multi* m, const mcpt_environment* e)
     return MCPT_OK;
 }
 
+// the same light sampling on every GPU of the group.  The argument is checked against the scene before any device is touched: a call that
+// is refused for its argument leaves every device as it was (a device that fails afterwards is a HIP error: the group goes back to ALL)
+int mcpt_multi_set_light_sampling(mcpt_multi* m, const mcpt_light_sampling* ls)
+{
+    if (!m || m->ranks.empty()) return mcpt_device_set_light_sampling(nullptr, ls);   // the device entry point's checks and refusal of a null handle
+    if (const int rc = light_sampling_check(ls)) return rc;
+    if (const int rc = light_weights_check(ls, m->ranks[0].dev->scene->s.lights.size())) return rc;
+    for (Rank& r : m->ranks) {
+        const int rc = mcpt_device_set_light_sampling(r.dev, ls);
+        if (rc) {
+            for (Rank& q : m->ranks) (void)mcpt_device_set_light_sampling(q.dev, nullptr);
+            return rc;
+        }
+    }
+    return MCPT_OK;
+}
+
 // the same geometry on every GPU of the group, one device after the other (a device that fails refuses to render until an update succeeds)
 int mcpt_multi_update_vertices(mcpt_multi* m, const double* v, int32_t mode, mcpt_update_info* info)
 {

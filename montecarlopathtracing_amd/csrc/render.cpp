@@ -226,7 +226,8 @@ static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameS
     const int64_t npx = L.n;
     const int spp = r.n;
     // WfArgs::nl: shadow planes -- one per light and one for an active environment (its draws use Philox block num_lights + 2)
-    const int nl = S.num_lights + (env_on(S.env) ? 1 : 0);
+    // (MCPT_LIGHTS_ONE: one plane for the picked light, whatever the scene's count -- which stays the Philox block base, S.num_lights)
+    const int nl = (pick_on(S.pick) ? 1 : S.num_lights) + (env_on(S.env) ? 1 : 0);
     const bool fast = d->trace_mode == MCPT_TRACE_FAST;
     const size_t bpp = wf_bytes_per_path(nl);
     // chunk: as many pixels as the workspace budget holds paths for (every pixel may hit)

@@ -111,7 +111,9 @@ static uint64_t scene_tag(const Scene& s)
 // The identity of a frame rendered under a lens: the scene's tag with the lens mixed in -- only when the lens is active, so that a pinhole
 // frame keeps its tag (and existing checkpoint files stay valid) and the two never resume from each other's files.
 // An active environment (env: the device's, null or inactive: none) is mixed in the same way, after the lens: its size, scale and texels.
-static uint64_t frame_tag(const Scene& s, const mcpt_lens* l, const EnvData* env)
+// So is light sampling that picks (pick: the device's; null, or a scene of fewer than two lights, where the mode changes no bit: nothing),
+// last: the mode and the table's probabilities.
+static uint64_t frame_tag(const Scene& s, const mcpt_lens* l, const EnvData* env, const LightPickData* pick)
 {
     uint64_t h = scene_tag(s);
     auto mix = [&](const void* p, size_t n) { const unsigned char* b = static_cast<const unsigned char*>(p); for (size_t i = 0; i < n; i++) { h ^= b[i]; h *= 1099511628211ull; } };
@@ -125,6 +127,11 @@ static uint64_t frame_tag(const Scene& s, const mcpt_lens* l, const EnvData* env
         const char tag[] = "envm";
         const int64_t wh[2] = {env->W, env->H};
         mix(tag, 4); mix(wh, sizeof wh); mix(&env->scale, sizeof(double)); mix(env->rgb.data(), env->rgb.size() * sizeof(float));
+    }
+    if (pick && pick_on(pick->dpick)) {
+        const char tag[] = "lpck";
+        const int64_t mode = pick->mode;
+        mix(tag, 4); mix(&mode, sizeof mode); mix(pick->pdf.data(), pick->pdf.size() * sizeof(double));
     }
     return h;
 }
@@ -263,12 +270,32 @@ int mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, c
     return mcpt_render_scene_motion(path, filename, spp, opt, opt_bytes, lens, environment_pfm, environment_scale, nullptr, nullptr, nullptr, stats);
 }
 
+// every render_scene entry point ends here (light_sampling == null: MCPT_LIGHTS_ALL)
+static int render_scene_impl(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
+                             const mcpt_lens* lens, const char* environment_pfm, double environment_scale, const char* end_obj,
+                             const char* end_camera, const mcpt_shutter* shutter, const mcpt_light_sampling* light_sampling, mcpt_stats* stats);
+
 int mcpt_render_scene_motion(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
                              const mcpt_lens* lens, const char* environment_pfm, double environment_scale, const char* end_obj,
                              const char* end_camera, const mcpt_shutter* shutter, mcpt_stats* stats)
 {
+    return render_scene_impl(path, filename, spp, opt, opt_bytes, lens, environment_pfm, environment_scale, end_obj, end_camera, shutter, nullptr, stats);
+}
+
+int mcpt_render_scene_lights(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
+                             const mcpt_lens* lens, const char* environment_pfm, double environment_scale, const mcpt_light_sampling* light_sampling,
+                             mcpt_stats* stats)
+{
+    return render_scene_impl(path, filename, spp, opt, opt_bytes, lens, environment_pfm, environment_scale, nullptr, nullptr, nullptr, light_sampling, stats);
+}
+
+static int render_scene_impl(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
+                             const mcpt_lens* lens, const char* environment_pfm, double environment_scale, const char* end_obj,
+                             const char* end_camera, const mcpt_shutter* shutter, const mcpt_light_sampling* light_sampling, mcpt_stats* stats)
+{
     if (!path || !filename || spp <= 0 || opt_bytes < 0 || (opt_bytes > 0 && !opt)) return fail(MCPT_ERR_ARG, "bad argument");
     if (int lrc = lens_check(lens)) return lrc;
+    if (int src = light_sampling_check(light_sampling)) return src;
     if (shutter) { if (int src = shutter_check(shutter)) return src; }
     if (!shutter && (end_obj || end_camera)) return fail(MCPT_ERR_ARG, "an end .obj or .camera needs a shutter");
     if (shutter && shutter->steps > spp) return fail(MCPT_ERR_ARG, "the shutter has more steps than the frame has samples per pixel");
@@ -331,6 +358,7 @@ int mcpt_render_scene_motion(const char* path, const char* filename, int32_t spp
     else rc = mcpt_device_create(sc, o.device, &dev);
     if (rc == MCPT_OK && lens) rc = many ? mcpt_multi_set_lens(multi, lens) : mcpt_device_set_lens(dev, lens);
     if (rc == MCPT_OK && environment_pfm) rc = many ? mcpt_multi_set_environment(multi, &env) : mcpt_device_set_environment(dev, &env);
+    if (rc == MCPT_OK && light_sampling) rc = many ? mcpt_multi_set_light_sampling(multi, light_sampling) : mcpt_device_set_light_sampling(dev, light_sampling);
     if (rc == MCPT_OK && shutter) rc = mcpt_device_set_motion(dev, end_obj ? v_end.data() : nullptr, end_camera ? &cam_end : nullptr, shutter);
     if (rc) { if (dev) mcpt_device_free(dev); if (multi) mcpt_multi_free(multi); mcpt_scene_free(sc); return rc; }
     if (talk && many) std::printf("rendering on %d GPUs\n", mcpt_multi_num_devices(multi));
@@ -359,7 +387,7 @@ int mcpt_render_scene_motion(const char* path, const char* filename, int32_t spp
         // the frame in `parts` tile partitions, saved after each; partitions a matching checkpoint already holds are skipped
         const int parts = o.checkpoint_parts > 0 ? o.checkpoint_parts : 8;
         std::vector<uint8_t> done(size_t(parts), 0);
-        const uint64_t tag = frame_tag(s, lens, dev->env.get());
+        const uint64_t tag = frame_tag(s, lens, dev->env.get(), dev->pick.get());
         std::string cerr;
         const int lrc = checkpoint_load(o.checkpoint, img.data(), s.width, s.height, spp, o.seed, tag, parts, done.data(), cerr);
         if (lrc != MCPT_OK) { std::fill(img.begin(), img.end(), 0.0); std::fill(done.begin(), done.end(), uint8_t(0)); }

@@ -604,7 +604,8 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 // (vertex.hpp), operation for operation; a path's record lives in this block's part of a global area, [field][path slot][lane].
                 const WfArgs& a = pp.a;
                 const int nl = pp.nl;
-                const int nlights = PP::kEnv ? nl - 1 : nl;              // (nl: shadow planes; an environment's is the last)
+                const int nplanes = PP::kEnv ? nl - 1 : nl;              // (nl: shadow planes; an environment's is the last, these are the lights')
+                const int nlights = PP::kOne ? S.num_lights : nplanes;   // the Philox block base (MCPT_LIGHTS_ONE: one plane for the picked light)
                 const bool folded = nl == 1;                             // see k_wf_logic
                 const long long cap = a.cap;
                 const int s0 = k * R;
@@ -696,9 +697,9 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                     const int slot = a.first_slot + id / a.spp;
                     key.pixel = (uint32_t)(a.pixels ? a.pixels[slot] : slot); key.sample = (uint32_t)(a.sample_base + id % a.spp);
                     int sample_mat = -1;
-                    for (int l = 0; l < nlights; l++) {
+                    for (int l = 0; l < nplanes; l++) {
                         V3 direction, cc;
-                        const int expect = light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, cc);
+                        const int expect = PP::kOne ? light_sample_one(S, key, depth, p, pn, kd, direction, cc) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, cc);
                         ri[(size_t)(RI_EXPECT + l) * plane] = expect;
                         if (expect != -2) { stp(RD_C + 3 * l, cc); emit(s0 + l, p + direction * 0.01, direction); n_shadow++; }
                         else n_skipped++;
@@ -706,8 +707,8 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                     if constexpr (PP::kEnv) {
                         V3 direction, cc;
                         const int expect = env_light_sample(S.env, key, depth, (uint32_t)nlights, pn, kd, direction, cc);
-                        ri[(size_t)(RI_EXPECT + nlights) * plane] = expect;
-                        if (expect != -2) { stp(RD_C + 3 * nlights, cc); emit(s0 + nlights, p + direction * 0.01, direction); n_shadow++; }
+                        ri[(size_t)(RI_EXPECT + nplanes) * plane] = expect;
+                        if (expect != -2) { stp(RD_C + 3 * nplanes, cc); emit(s0 + nplanes, p + direction * 0.01, direction); n_shadow++; }
                     }
                     V3 nd = mk(0, 0, 0), wgt = mk(1, 1, 1);
                     const int bt = bounce_sample(key, depth, nlights, m, dir, pn, kd, nd, wgt);

@@ -186,6 +186,11 @@ int update_lights(mcpt_device* d)
     }
     d->ds.area0 = lights[0].total_area;
     u.light_v.swap(lv);
+    if (d->pick) {                                  // MCPT_LIGHTS_ONE with default weights: luminance x the new areas
+        std::vector<double> areas;
+        for (const DLight& l : lights) areas.push_back(l.total_area);
+        if (const int rc = light_pick_refresh(d, areas.data())) return rc;
+    }
     return MCPT_OK;
 }
 

@@ -60,6 +60,30 @@ __device__ __forceinline__ int light_sample(const DScene& S, const RngKey& key, 
     return sample_mat;
 }
 
+// MCPT_LIGHTS_ONE: the light picked at vertex `depth` of a camera sample, from slot 0 of Philox block nl + 3 (nl = the scene's lights; the
+// lights' draws use blocks 0 .. nl-1, the bounce nl and nl + 1, the environment nl + 2).  The smallest l with u * Z < cdf[l], by binary
+// search over 0 .. last: a light of weight 0 (cdf[l] == cdf[l-1]) is never picked.  inv_p = 1 / p_l, the host's quotient.
+__device__ __forceinline__ int light_pick(const DLightPick& P, const RngKey& key, uint32_t depth, uint32_t nl, double& inv_p)
+{
+    const double x = uniform1(key, depth, nl + 3u) * P.Z;
+    int lo = 0, hi = P.last;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (x < P.cdf[mid]) hi = mid; else lo = mid + 1; }
+    inv_p = P.inv_pdf[lo];
+    return lo;
+}
+
+// MCPT_LIGHTS_ONE: the one light sample of the vertex -- light_sample of the picked light (its own Philox block, no light before it
+// to inherit a material from), c scaled by 1 / p_l.  Returns as light_sample does.
+__device__ __forceinline__ int light_sample_one(const DScene& S, const RngKey& key, uint32_t depth, const V3& p, const V3& pn, const V3& kd, V3& direction, V3& c)
+{
+    double inv_p;
+    const int l = light_pick(S.pick, key, depth, (uint32_t)S.num_lights, inv_p);
+    int sample_mat = -1;
+    const int expect = light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, c);
+    if (expect != -2) c = mk(c.x * inv_p, c.y * inv_p, c.z * inv_p);
+    return expect;
+}
+
 #define MCPT_BT_NO_OFFSET 8         /* flag in a bounce type: the ray starts at the vertex itself (refraction, total reflection) */
 
 // Russian roulette and nextRay (:3-11, :66-134, :234-263) at a vertex reached along -dir.  Returns -1 when the path ends here,

@@ -53,14 +53,16 @@ __device__ __forceinline__ void sstc(double* __restrict__ a, long long cap, long
 // evaluation is free): L, p and the sample id are stored before anything is computed, the incoming direction dies with
 // bounce_sample -- the later passes' values that are alive at the same time, and with them the registers the compiler had to
 // park in scratch memory (39 at 4 waves per SIMD), are what this order is about.  ENV: an active environment, shadow plane nl - 1 after
-// the scene's nl - 1 lights (WfArgs::nl counts planes; the Philox block base is the lights' count).
-template <bool FIRST, bool ENV>
+// the scene's nl - 1 lights (WfArgs::nl counts planes; the Philox block base is the lights' count).  ONE: S.pick is active (MCPT_LIGHTS_ONE) --
+// the lights have one plane, plane 0, for the light vertex.hpp's light_pick draws; the block base is S.num_lights, whatever nl says.
+template <bool FIRST, bool ENV, bool ONE>
 __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a, long long j, int id, int leaf, const V3& p, const V3& dir, const V3& T, const V3& L,
                                                 int mat_first, int pix_first, const V3& pn_first, const V3& kd_first, LaneStats& ls)
 {
     const long long cap = a.cap;
     const int nl = a.nl;
-    const int nlights = ENV ? nl - 1 : nl;
+    const int nplanes = ENV ? nl - 1 : nl;                                     // the lights' shadow planes
+    const int nlights = ONE ? S.num_lights : nplanes;
     const bool folded = nl == 1;
     const uint32_t depth = (uint32_t)a.depth;
     sst(a.out.id + j, id);
@@ -85,9 +87,9 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
     }
 
     int sample_mat = -1;
-    for (int l = 0; l < nlights; l++) {
+    for (int l = 0; l < nplanes; l++) {
         V3 direction, c;
-        const int expect = light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, c);
+        const int expect = ONE ? light_sample_one(S, key, depth, p, pn, kd, direction, c) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, c);
         if (expect != -2) {
             sstc(a.out.c + (long long)l * 3 * cap, cap, j, folded ? mk(T.x * c.x, T.y * c.y, T.z * c.z) : c);
             sstc(a.rays.d + (long long)l * 3 * cap, cap, j, direction);       // origin p + direction * 0.01: WfRaySource
@@ -99,11 +101,11 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
         V3 direction, c;
         const int expect = env_light_sample(S.env, key, depth, (uint32_t)nlights, pn, kd, direction, c);
         if (expect != -2) {
-            sstc(a.out.c + (long long)nlights * 3 * cap, cap, j, folded ? mk(T.x * c.x, T.y * c.y, T.z * c.z) : c);
-            sstc(a.rays.d + (long long)nlights * 3 * cap, cap, j, direction);
+            sstc(a.out.c + (long long)nplanes * 3 * cap, cap, j, folded ? mk(T.x * c.x, T.y * c.y, T.z * c.z) : c);
+            sstc(a.rays.d + (long long)nplanes * 3 * cap, cap, j, direction);
             ls.shadow++;
         }
-        sst(a.out.expect + ((long long)nlights * cap + j), expect);
+        sst(a.out.expect + ((long long)nplanes * cap + j), expect);
     }
 }
 
@@ -127,7 +129,8 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
 // before: no slot is overwritten while it is read.
 //
 // ENV: an active environment (wf_shade_vertex's last shadow plane; a bounce ray that left the scene adds T' * Le, a camera ray Le).
-template <bool FIRST, bool ENV>
+// ONE: MCPT_LIGHTS_ONE (wf_shade_vertex; the resolve sees planes only and is the same code).
+template <bool FIRST, bool ENV, bool ONE>
 __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOGIC_WAVES) k_wf_logic(DScene S, WfArgs a)
 {
     const long long n_prev = (long long)a.counts_in->n_next * a.count_mul;
@@ -184,7 +187,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 continue;
             }
             MCPT_LSTAMP(0)
-            wf_shade_vertex<true, ENV>(S, a, j, id, leaf, p, dir, mk(1, 1, 1), mk(0, 0, 0), mat_first, pix_first, pn_first, kd_first, ls);
+            wf_shade_vertex<true, ENV, ONE>(S, a, j, id, leaf, p, dir, mk(1, 1, 1), mk(0, 0, 0), mat_first, pix_first, pn_first, kd_first, ls);
             MCPT_LSTAMP(2)
         }
     } else {
@@ -328,7 +331,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 const V3 v1 = ld3(tr->v1), n = ld3(tr->n);
                 const double t = dot(v1 - ro, n) / dot(n, bd);
                 const V3 p = ro + bd * t;
-                wf_shade_vertex<false, ENV>(S, a, j, id, leaf, p, neg(bd), T, L, 0, 0, mk(0, 0, 0), mk(0, 0, 0), ls);
+                wf_shade_vertex<false, ENV, ONE>(S, a, j, id, leaf, p, neg(bd), T, L, 0, 0, mk(0, 0, 0), mk(0, 0, 0), ls);
             }
             head = (head + m_round) & (kRing - 1u);
             count -= m_round;
@@ -348,8 +351,8 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
 // resolve, trace the bounce ray, shade the next vertex (vertex.hpp: the arithmetic of k_wf_logic).  Lanes whose path has ended
 // take the next unclaimed path (one atomic per refill on the pass's own count slot), so a wave is as long as its share of
 // the work, not as its longest path.  A lane that has just adopted a path finds the rays of its first step in the wavefront
-// state instead of computing them; from the second step on everything lives in registers.  ENV: as k_wf_logic.
-template <bool ENV>
+// state instead of computing them; from the second step on everything lives in registers.  ENV, ONE: as k_wf_logic.
+template <bool ENV, bool ONE>
 __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, WfArgs a)
 {
     __shared__ int lds_stack[MCPT_FAST_STACK * 256];
@@ -357,7 +360,8 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
     if (n == 0 || n > (long long)a.finish_below) return;               // nothing left, or still wavefront work
     const long long cap = a.cap;
     const int nl = a.nl;
-    const int nlights = ENV ? nl - 1 : nl;                             // (nl: shadow planes)
+    const int nplanes = ENV ? nl - 1 : nl;                             // (nl: shadow planes; these are the lights')
+    const int nlights = ONE ? S.num_lights : nplanes;                  // the Philox block base
     const bool folded = nl == 1;                                       // see k_wf_logic
     const int lane = threadIdx.x & 63;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
@@ -433,11 +437,11 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
             V3 c = mk(0, 0, 0);
             Ray r; r.o = p; r.d = mk(1, 1, 1);
             if (mode == M_VERTEX && !ended) {
-                if (ENV && l == nlights) {
+                if (ENV && l == nplanes) {
                     expect = env_light_sample(S.env, key, depth, (uint32_t)nlights, pn, kd, r.d, c);
                     if (expect != -2) ls.shadow++;
                 } else {
-                    expect = light_sample(S, key, depth, l, p, pn, kd, sample_mat, r.d, c);
+                    expect = ONE ? light_sample_one(S, key, depth, p, pn, kd, r.d, c) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, r.d, c);
                     if (expect != -2) ls.shadow++; else ls.skipped++;
                 }
             } else if (mode == M_ADOPTED) {
@@ -544,10 +548,11 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
 #ifndef MCPT_POOL_NPC
 #define MCPT_POOL_NPC (MCPT_POOL_KT / 2)           /* path slots per lane the record planes are laid out for (one light: KT / 2 paths) */
 #endif
-template <bool ENV>
+template <bool ENV, bool ONE>
 struct WfPaths {
     static constexpr bool kPaths = true;
     static constexpr bool kEnv = ENV;           // an active environment: the last of the nl shadow planes (see k_wf_logic)
+    static constexpr bool kOne = ONE;           // MCPT_LIGHTS_ONE: the lights' one plane holds the picked light's sample
     WfArgs a;
     long long n;                // paths handed over (positions 0 .. n-1 of the wavefront state a.out)
     int nl, npc;
@@ -568,21 +573,21 @@ size_t finish_pool_bytes(int cus, int nl)
     return blocks * (size_t(9 + 3 * nl) * plane * sizeof(double) + size_t(3 + nl) * plane * sizeof(int) + size_t(MCPT_POOL_WAVES) * 64 * MCPT_FAST_STACK * sizeof(int));
 }
 
-template <int NW, int KT, int SCAP, bool ENV>
+template <int NW, int KT, int SCAP, bool ENV, bool ONE>
 __global__ void __launch_bounds__(NW * 64, 1) k_wf_finish_pool(DScene S, WfArgs a, char* area, int* spill)
 {
     const long long n = a.counts->n_next;
     if (n == 0 || n > (long long)a.finish_below) return;               // nothing left, or still wavefront work
     __shared__ PoolLds<NW, KT, SCAP> L;
     const size_t blocks = gridDim.x, plane = size_t(MCPT_POOL_NPC) * 64;
-    WfPaths<ENV> pp;
+    WfPaths<ENV, ONE> pp;
     pp.a = a; pp.n = n; pp.nl = a.nl; pp.npc = MCPT_POOL_NPC; pp.inv_r = 1.0f / (float)(a.nl + 1);
     pp.recd = reinterpret_cast<double*>(area);
     pp.reci = reinterpret_cast<int*>(pp.recd + blocks * size_t(9 + 3 * a.nl) * plane);
     pp.gstack = pp.reci + blocks * size_t(3 + a.nl) * plane;
     WfRaySource src; src.a = a; src.n_paths = n;                       // (path mode never fetches or stores through it)
     Work w = {0, 0};
-    trace_pool<WfRaySource, NW, KT, SCAP, WfPaths<ENV>>(S, src, nullptr, nullptr, 0u, 64, L, w, spill, pp);
+    trace_pool<WfRaySource, NW, KT, SCAP, WfPaths<ENV, ONE>>(S, src, nullptr, nullptr, 0u, 64, L, w, spill, pp);
     LaneStats ls;
     ls.nodes = w.nodes; ls.tris = w.tris;
     __syncthreads();
@@ -694,13 +699,24 @@ void launch_wf_logic(const DScene& S, const WfArgs& a, long long n_upper, bool f
     if (n_upper <= 0) return;
     // small inputs get small grids (>= 1024 paths per block): every wave that starts costs a few atomics on shared counters
     const bool env = env_on(S.env);
+    if (pick_on(S.pick)) {
+        const unsigned g = grid_for(n_upper, 1024, first ? cfg.logic_first_one[env] : cfg.logic_rest_one[env]);
+        if (first) {
+            if (env) hipLaunchKernelGGL((k_wf_logic<true, true, true>), dim3(g), dim3(256), 0, st, S, a);
+            else hipLaunchKernelGGL((k_wf_logic<true, false, true>), dim3(g), dim3(256), 0, st, S, a);
+        } else {
+            if (env) hipLaunchKernelGGL((k_wf_logic<false, true, true>), dim3(g), dim3(256), 0, st, S, a);
+            else hipLaunchKernelGGL((k_wf_logic<false, false, true>), dim3(g), dim3(256), 0, st, S, a);
+        }
+        return;
+    }
     unsigned g = grid_for(n_upper, 1024, first ? (env ? cfg.logic_first_env : cfg.logic_first) : (env ? cfg.logic_rest_env : cfg.logic_rest));
     if (first) {
-        if (env) hipLaunchKernelGGL((k_wf_logic<true, true>), dim3(g), dim3(256), 0, st, S, a);
-        else hipLaunchKernelGGL((k_wf_logic<true, false>), dim3(g), dim3(256), 0, st, S, a);
+        if (env) hipLaunchKernelGGL((k_wf_logic<true, true, false>), dim3(g), dim3(256), 0, st, S, a);
+        else hipLaunchKernelGGL((k_wf_logic<true, false, false>), dim3(g), dim3(256), 0, st, S, a);
     } else {
-        if (env) hipLaunchKernelGGL((k_wf_logic<false, true>), dim3(g), dim3(256), 0, st, S, a);
-        else hipLaunchKernelGGL((k_wf_logic<false, false>), dim3(g), dim3(256), 0, st, S, a);
+        if (env) hipLaunchKernelGGL((k_wf_logic<false, true, false>), dim3(g), dim3(256), 0, st, S, a);
+        else hipLaunchKernelGGL((k_wf_logic<false, false, false>), dim3(g), dim3(256), 0, st, S, a);
     }
 }
 
@@ -713,16 +729,23 @@ void launch_wf_finish(const DScene& S, const WfArgs& a, long long n_upper, hipSt
         const long long per_block = 64ll * (MCPT_POOL_KT / (a.nl + 1));
         const long long nb = (n_upper + per_block - 1) / per_block;
         const int g = (int)(nb < cfg.cus ? nb : cfg.cus);
-        if (env_on(S.env))
-            hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, true>), dim3(g), dim3(MCPT_POOL_WAVES * 64), 0, st, S, a, path_area,
-                               reinterpret_cast<int*>(slow_list + slow_cap));
+        int* const spill = reinterpret_cast<int*>(slow_list + slow_cap);
+        const dim3 block(MCPT_POOL_WAVES * 64);
+        if (pick_on(S.pick)) {
+            if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, true, true>), dim3(g), block, 0, st, S, a, path_area, spill);
+            else hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, false, true>), dim3(g), block, 0, st, S, a, path_area, spill);
+        } else if (env_on(S.env))
+            hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, true, false>), dim3(g), block, 0, st, S, a, path_area, spill);
         else
-            hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, false>), dim3(g), dim3(MCPT_POOL_WAVES * 64), 0, st, S, a, path_area,
-                               reinterpret_cast<int*>(slow_list + slow_cap));
+            hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, false, false>), dim3(g), block, 0, st, S, a, path_area, spill);
         return;
     }
-    if (env_on(S.env)) hipLaunchKernelGGL(k_wf_finish<true>, dim3(grid_for(n_upper, 256, unsigned(cfg.finish_grid_env))), dim3(256), 0, st, S, a);
-    else hipLaunchKernelGGL(k_wf_finish<false>, dim3(grid_for(n_upper, 256, unsigned(cfg.finish_grid))), dim3(256), 0, st, S, a);
+    if (pick_on(S.pick)) {
+        const unsigned g = grid_for(n_upper, 256, unsigned(cfg.finish_grid_one[env_on(S.env)]));
+        if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish<true, true>), dim3(g), dim3(256), 0, st, S, a);
+        else hipLaunchKernelGGL((k_wf_finish<false, true>), dim3(g), dim3(256), 0, st, S, a);
+    } else if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish<true, false>), dim3(grid_for(n_upper, 256, unsigned(cfg.finish_grid_env))), dim3(256), 0, st, S, a);
+    else hipLaunchKernelGGL((k_wf_finish<false, false>), dim3(grid_for(n_upper, 256, unsigned(cfg.finish_grid))), dim3(256), 0, st, S, a);
 }
 
 void launch_hit_slots(const PrimaryHit* hits, int first_slot, int n_slots, int32_t* hit_slots, unsigned int* count, hipStream_t st)
@@ -739,12 +762,19 @@ void launch_zero_rad(double* rad, long long n, hipStream_t st)
 
 void init_launch_cfg_logic(LaunchCfg& cfg, unsigned forced_grid)
 {
-    cfg.logic_first = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, false>), cfg.cus));
-    cfg.logic_rest = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, false>), cfg.cus));
-    cfg.finish_grid = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<false>), cfg.cus);
-    cfg.logic_first_env = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, true>), cfg.cus));
-    cfg.logic_rest_env = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, true>), cfg.cus));
-    cfg.finish_grid_env = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<true>), cfg.cus);
+    cfg.logic_first = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, false, false>), cfg.cus));
+    cfg.logic_rest = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, false, false>), cfg.cus));
+    cfg.finish_grid = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<false, false>), cfg.cus);
+    cfg.logic_first_env = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, true, false>), cfg.cus));
+    cfg.logic_rest_env = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, true, false>), cfg.cus));
+    cfg.finish_grid_env = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<true, false>), cfg.cus);
+    // MCPT_LIGHTS_ONE, [0] without and [1] under an environment: each instantiation's own occupancy
+    cfg.logic_first_one[0] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, false, true>), cfg.cus));
+    cfg.logic_first_one[1] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, true, true>), cfg.cus));
+    cfg.logic_rest_one[0] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, false, true>), cfg.cus));
+    cfg.logic_rest_one[1] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, true, true>), cfg.cus));
+    cfg.finish_grid_one[0] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<false, true>), cfg.cus);
+    cfg.finish_grid_one[1] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<true, true>), cfg.cus);
 }
 
 }  // namespace mcpt
