@@ -454,12 +454,33 @@ int mcpt_read_pfm(const char* file, int32_t* width, int32_t* height, float* rgb,
  * A scene with no light or one light renders the same bits in both modes.  The setting is device state: every frame, progressive or
  * adaptive pass, motion frame and (pixel, sample) query that follows uses it (a progressive frame should not see it change between its
  * passes).  The megakernel counts a picked light behind the surface as shadow_skipped and traces no ray for it. */
+/* MCPT_LIGHTS_TREE: as MCPT_LIGHTS_ONE -- one light per vertex, the same draw (slot 0 of block nl + 3), the same sample of the picked light,
+ * scaled by 1 / p -- but the probability depends on the vertex (p, pn): a binary tree over the lights is descended from the root, and at
+ * every node the two children are weighed by distance and horizon.
+ *   tree (host, fp64): a leaf per light, its box the exact min / max of the light's triangle vertices, its weight the table's w_l (the same
+ *     defaults, the same caller's weights, the same refusals).  Inner nodes top-down: the node's lights are ordered by box centre
+ *     (lo + hi) * 0.5 along the widest axis of those centres' bounds (the lowest axis among equals), ties by light index; the first
+ *     ceil(n / 2) go left.  An inner node's box is the union of its children's, its weight W_left + W_right.  Nodes are numbered in
+ *     preorder (root 0, the left subtree right after its parent).  Record, 64 bytes: double lo[3], hi[3], w; int32 left, right (inner
+ *     node: the children's indices; leaf: both ~light).  A device whose emitters an update or a motion step moves makes the tree again.
+ *   importance of a node seen from (p, pn), with c = (lo + hi) * 0.5, h = (hi - lo) * 0.5:  0 if s = (c - p) . pn + h . |pn| is below
+ *     -1e-9 * (|pn.x| + |pn.y| + |pn.z|) * (|p|inf + |c|inf + |h|inf) (the whole box lies below the vertex's horizon), else
+ *     W / max(1, |c - p|^2, |h|^2).  Only + - * / and comparisons, sums left to right: host and device give the same bits.
+ *   descent: at a node with children L, R: both importances 0 -> their weights stand in; I_R == 0 -> left, I_L == 0 -> right, with
+ *     probability 1; else pL = I_L / (I_L + I_R), u < pL ? (left, u = u / pL, pdf *= pL) : (right, u = (u - pL) / (1 - pL), pdf *= 1 - pL).
+ *     At the leaf the contribution is scaled by 1.0 / pdf.  A light of weight 0 is never picked; a light that can contribute has s above
+ *     the margin at every ancestor, hence a positive probability: the estimator is unbiased as MCPT_LIGHTS_ONE's is.
+ * A scene of fewer than two lights holds no tree and renders the MCPT_LIGHTS_ALL bits.  Under MCPT_LIGHTS_TREE mcpt_device_get_light_sampling
+ * reports the ROOT's distribution w_l / Z (the table's); the per-vertex probabilities come from mcpt_scene_light_tree_pdf (host) and
+ * mcpt_light_pick_at (device), and mcpt_light_pick, which has no vertex, is refused (MCPT_ERR_ARG). */
 #define MCPT_LIGHTS_ALL 0
 #define MCPT_LIGHTS_ONE 1
+#define MCPT_LIGHTS_TREE 2
 typedef struct { int32_t mode, num_weights; const double* weights; } mcpt_light_sampling;   /* num_weights 0 / weights NULL: the default weights */
-/* NULL means MCPT_LIGHTS_ALL.  MCPT_ERR_ARG: an unknown mode, num_weights != 0 that is not the scene's light count, bad weights. */
+/* NULL means MCPT_LIGHTS_ALL.  mode: MCPT_LIGHTS_ALL, MCPT_LIGHTS_ONE or MCPT_LIGHTS_TREE.  MCPT_ERR_ARG: an unknown mode, num_weights != 0 that is not the scene's light count, bad weights. */
 int mcpt_device_set_light_sampling(mcpt_device*, const mcpt_light_sampling*);
-/* *mode and pdf[num_lights] (each may be NULL): the table's probabilities; 1 for every light under MCPT_LIGHTS_ALL */
+/* *mode and pdf[num_lights] (each may be NULL): the table's probabilities; 1 for every light under MCPT_LIGHTS_ALL; under MCPT_LIGHTS_TREE
+ * the root's distribution w_l / Z -- what a vertex really uses comes from mcpt_scene_light_tree_pdf and mcpt_light_pick_at */
 int mcpt_device_get_light_sampling(const mcpt_device*, int32_t* mode, double* pdf);
 /* host only (no GPU needed): the table of the scene's lights under `weights` (NULL: the default weights) -> cdf[num_lights], pdf[num_lights].
  * MCPT_ERR_ARG: a scene without lights, bad weights. */
@@ -467,6 +488,16 @@ int mcpt_scene_light_pick_table(const mcpt_scene*, const double* weights_or_null
 /* test seam: the pick at vertex `depth` of camera samples (pix[i], k[i]) -> light[n], pdf[n].  MCPT_ERR_ARG unless the device picks
  * (MCPT_LIGHTS_ONE on a scene of two or more lights). */
 int mcpt_light_pick(mcpt_device*, uint64_t seed, const int32_t* pix, const int32_t* k, int32_t depth, int64_t n, int32_t* light, double* pdf);
+/* host only (no GPU needed): the light tree of the scene under `weights` (NULL: the default weights), exactly as a device uploads it ->
+ * *n_nodes (2 * num_lights - 1) and, unless NULL, nodes[*n_nodes] 64-byte records.  MCPT_ERR_ARG: fewer than two lights, bad weights. */
+int mcpt_scene_light_tree(const mcpt_scene*, const double* weights_or_null, int32_t* n_nodes, void* nodes);
+/* host only: the probability of every light at n vertices p[n][3] with normals pn[n][3] -> pdf[n][num_lights]; the host walks the same
+ * tree with the same arithmetic as the device.  MCPT_ERR_ARG as above. */
+int mcpt_scene_light_tree_pdf(const mcpt_scene*, const double* weights_or_null, const double* p, const double* pn, int64_t n, double* pdf);
+/* test seam: the light the path kernels pick at the vertex (p[i], pn[i]) at `depth` of camera sample (pix[i], k[i]), and its probability
+ * -> light[n], pdf[n].  MCPT_ERR_ARG unless the device picks by tree (MCPT_LIGHTS_TREE on a scene of two or more lights). */
+int mcpt_light_pick_at(mcpt_device*, uint64_t seed, const int32_t* pix, const int32_t* k, int32_t depth, const double* p, const double* pn, int64_t n,
+                       int32_t* light, double* pdf);
 
 /* ---- integrator over several GPUs of one node (no reference counterpart: generateImg is single-process OpenMP) ---- */
 /* The frame is cut into tiles dealt to the GPUs exactly as mcpt_render_params.rank/world describe (rank r = devices[r]); the scene
@@ -604,7 +635,7 @@ int  mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, 
 /* mcpt_render_scene_env under a light sampling (NULL: MCPT_LIGHTS_ALL, = mcpt_render_scene_env), set on the device or on every GPU of the
  * options; an invalid one is refused (MCPT_ERR_ARG) before anything is read or written, a weight count that is not the scene's light
  * count once the scene is read.  A checkpoint's frame identity includes the mode and the table's probabilities when the device picks
- * (MCPT_LIGHTS_ONE on a scene of two or more lights): such a frame never resumes from a checkpoint written under another setting, and a
+ * (MCPT_LIGHTS_ONE or MCPT_LIGHTS_TREE on a scene of two or more lights; under MCPT_LIGHTS_TREE the tree's node bytes too): such a frame never resumes from a checkpoint written under another setting, and a
  * frame that does not pick keeps the identity it had before. */
 int  mcpt_render_scene_lights(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, int64_t options_bytes,
                               const mcpt_lens*, const char* environment_pfm, double environment_scale, const mcpt_light_sampling*,

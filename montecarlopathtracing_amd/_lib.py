@@ -163,6 +163,7 @@ EXPORTS = [
     "mcpt_shutter_time", "mcpt_shutter_step", "mcpt_render_scene_motion",
     "mcpt_device_set_light_sampling", "mcpt_device_get_light_sampling", "mcpt_multi_set_light_sampling", "mcpt_scene_light_pick_table",
     "mcpt_light_pick", "mcpt_render_scene_lights",
+    "mcpt_scene_light_tree", "mcpt_scene_light_tree_pdf", "mcpt_light_pick_at",
 ]
 
 
@@ -311,6 +312,9 @@ def lib():
     L.mcpt_multi_set_light_sampling.argtypes = [P, C.POINTER(LightSampling)]
     L.mcpt_scene_light_pick_table.argtypes = [P, D, D, D]
     L.mcpt_light_pick.argtypes = [P, C.c_uint64, I32, I32, C.c_int32, C.c_int64, I32, D]
+    L.mcpt_scene_light_tree.argtypes = [P, D, I32, C.c_void_p]
+    L.mcpt_scene_light_tree_pdf.argtypes = [P, D, D, D, C.c_int64, D]
+    L.mcpt_light_pick_at.argtypes = [P, C.c_uint64, I32, I32, C.c_int32, D, D, C.c_int64, I32, D]
     L.mcpt_render_scene_lights.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens), C.c_char_p,
                                            C.c_double, C.POINTER(LightSampling), C.POINTER(Stats)]
     _lib = L

@@ -97,24 +97,27 @@ def device_count():
     return lib().mcpt_device_count()
 
 
-LIGHTS_ALL, LIGHTS_ONE = 0, 1
+LIGHTS_ALL, LIGHTS_ONE, LIGHTS_TREE = 0, 1, 2
+# one node of the light tree of MCPT_LIGHTS_TREE (mcpt.h), 64 bytes; a leaf has left == right == ~light
+LIGHT_NODE = np.dtype([("lo", "<f8", 3), ("hi", "<f8", 3), ("w", "<f8"), ("left", "<i4"), ("right", "<i4")])
 
 
 def make_light_sampling(mode="all", weights=None):
     """An mcpt_light_sampling and the float64 weights it points to (keep both alive while it is used); (None, None) for "all" / None.
-    mode: "all", "one", None, or a dict of these two arguments."""
+    mode: "all", "one", "tree", None, or a dict of these two arguments."""
     if isinstance(mode, dict):
         mode, weights = mode.get("mode", "one"), mode.get("weights")
     if mode is None or mode == "all":
         if weights is not None:
-            raise ValueError('weights go with mode "one"')
+            raise ValueError('weights go with mode "one" or "tree"')
         return None, None
-    if mode != "one":
-        raise ValueError('light sampling mode must be "all" or "one"')
+    if mode not in ("one", "tree"):
+        raise ValueError('light sampling mode must be "all", "one" or "tree"')
+    m = LIGHTS_TREE if mode == "tree" else LIGHTS_ONE
     if weights is None:
-        return LightSampling(LIGHTS_ONE, 0, None), None
+        return LightSampling(m, 0, None), None
     w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
-    return LightSampling(LIGHTS_ONE, w.shape[0], _p(w, C.c_double)), w
+    return LightSampling(m, w.shape[0], _p(w, C.c_double)), w
 
 
 class Scene:
@@ -244,6 +247,38 @@ class Scene:
         inv = np.zeros(n)
         np.divide(1.0, pdf, out=inv, where=pdf > 0)
         return cdf, pdf, inv
+
+    def _light_weights(self, weights):
+        if weights is None:
+            return None
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if w.shape[0] != self.info.num_lights:
+            raise ValueError("one weight per light of the scene")
+        return w
+
+    def light_tree(self, weights=None):
+        """The light tree of MCPT_LIGHTS_TREE for this scene's lights, exactly as a device uploads it (mcpt_scene_light_tree; host only): a
+        structured array of LIGHT_NODE records, root first.  weights: as light_pick_table."""
+        w = self._light_weights(weights)
+        wp = _p(w, C.c_double) if w is not None else None
+        n = C.c_int32()
+        check(lib().mcpt_scene_light_tree(self._h, wp, C.byref(n), None))
+        nodes = np.zeros(n.value, dtype=LIGHT_NODE)
+        check(lib().mcpt_scene_light_tree(self._h, wp, C.byref(n), nodes.ctypes.data_as(C.c_void_p)))
+        return nodes
+
+    def light_tree_pdf(self, p, pn, weights=None):
+        """The probability with which MCPT_LIGHTS_TREE picks every light at the vertices p (n, 3) with normals pn (n, 3): (n, num_lights)
+        (mcpt_scene_light_tree_pdf; host only, the device's arithmetic)."""
+        w = self._light_weights(weights)
+        p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3)
+        pn = np.ascontiguousarray(pn, dtype=np.float64).reshape(-1, 3)
+        if p.shape != pn.shape:
+            raise ValueError("one normal per vertex")
+        pdf = np.zeros((p.shape[0], self.info.num_lights))
+        check(lib().mcpt_scene_light_tree_pdf(self._h, _p(w, C.c_double) if w is not None else None, _p(p, C.c_double), _p(pn, C.c_double),
+                                              p.shape[0], _p(pdf, C.c_double)))
+        return pdf
 
     def trace_engine(self):
         """'pool' or 'vote': the closest-hit engine a device created for this scene now would run (mcpt_scene_trace_engine)"""
@@ -456,17 +491,20 @@ class Device:
     def set_light_sampling(self, mode="all", weights=None):
         """How every later frame, pass and sample_radiance samples the scene's lights (mcpt_device_set_light_sampling): "all" (or None) --
         every light at every vertex, the reference's loop -- or "one": one light per vertex, picked with probability weight / sum and
-        divided by it.  weights: None (luminance x area) or one non-negative weight per light; a light of weight 0 is never picked."""
+        divided by it -- or "tree": one light per vertex, picked by a descent of the light tree that weighs every node by its distance from
+        the vertex and culls what lies below the vertex's horizon.  weights: None (luminance x area) or one non-negative weight per light;
+        a light of weight 0 is never picked."""
         ls, keep = make_light_sampling(mode, weights)
         check(lib().mcpt_device_set_light_sampling(self._h, C.byref(ls) if ls is not None else None))
         del keep
 
     def light_sampling(self):
-        """the device's light sampling: (mode, pdf) with mode "all" or "one" and pdf the pick probability of every light (1 under "all")"""
+        """the device's light sampling: (mode, pdf) with mode "all", "one" or "tree" and pdf the pick probability of every light (1 under
+        "all"; under "tree" the root's distribution -- a vertex's own comes from Scene.light_tree_pdf and light_pick_at)"""
         m = C.c_int32()
         pdf = np.zeros(self.scene.info.num_lights)
         check(lib().mcpt_device_get_light_sampling(self._h, C.byref(m), _p(pdf, C.c_double) if pdf.size else None))
-        return ("one" if m.value == LIGHTS_ONE else "all"), pdf
+        return {LIGHTS_ONE: "one", LIGHTS_TREE: "tree"}.get(m.value, "all"), pdf
 
     def light_pick(self, seed, pix, k, depth):
         """the light "one" picks at vertex `depth` of camera samples (pix[i], k[i]): indices (n,) int32, their probabilities (n,)"""
@@ -475,6 +513,21 @@ class Device:
         n = pix.shape[0]
         light, pdf = np.zeros(n, dtype=np.int32), np.zeros(n)
         check(lib().mcpt_light_pick(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), int(depth), n, _p(light, C.c_int32), _p(pdf, C.c_double)))
+        return light, pdf
+
+    def light_pick_at(self, seed, pix, k, depth, p, pn):
+        """the light "tree" picks at the vertices p[i] with normals pn[i] at `depth` of camera samples (pix[i], k[i]): indices (n,) int32 and
+        the probabilities they were picked with (n,) (mcpt_light_pick_at: the path kernels' own device function)"""
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        p = np.ascontiguousarray(p, dtype=np.float64).reshape(-1, 3)
+        pn = np.ascontiguousarray(pn, dtype=np.float64).reshape(-1, 3)
+        n = pix.shape[0]
+        if k.shape[0] != n or p.shape[0] != n or pn.shape[0] != n:
+            raise ValueError("one (pixel, sample, vertex, normal) per pick")
+        light, pdf = np.zeros(n, dtype=np.int32), np.zeros(n)
+        check(lib().mcpt_light_pick_at(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), int(depth), _p(p, C.c_double), _p(pn, C.c_double), n,
+                                       _p(light, C.c_int32), _p(pdf, C.c_double)))
         return light, pdf
 
     def update_vertices(self, v, mode="refit", stream=None):
@@ -862,7 +915,7 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
     environment: None, or the path of a colour PFM lat-long map (environment_scale: its scale); rendered through mcpt_render_scene_env.
     motion: None, or a dict of end_obj and end_camera (file paths, either may be missing), shutter = (open, close) and steps: the shutter
     frame between the scene and those files (mcpt_render_scene_motion).
-    light_sampling: None / "all", "one", or a dict of Device.set_light_sampling's arguments; rendered through mcpt_render_scene_lights (not
+    light_sampling: None / "all", "one", "tree", or a dict of Device.set_light_sampling's arguments; rendered through mcpt_render_scene_lights (not
     together with motion)."""
     dev_arr, ndev = None, 0
     if devices == -1:

@@ -4,6 +4,7 @@
 // geometry, shading attributes, materials, light tables and textures live in separate arrays so that a step
 // only pulls the bytes it needs).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 namespace mcpt {
@@ -126,6 +127,8 @@ struct DEnv {
     double scale, Z;
 };
 
+struct DLightNode;
+
 // The light pick of MCPT_LIGHTS_ONE (vertex.hpp: light_pick; the table is built on the host by light_sampling.cpp).  All zero: every light
 // at every vertex, and the kernels are the instantiations without it.
 struct DLightPick {
@@ -133,7 +136,19 @@ struct DLightPick {
     const double* inv_pdf;      // [num_lights] 1 / p_l as the host formed it (a light of weight 0: 0, never read)
     double Z;                   // cdf[num_lights - 1]
     int32_t last, pad;          // the last light of non-zero weight
+    const DLightNode* nodes;      // MCPT_LIGHTS_TREE: the light tree, root = 0 (null: the table alone picks, MCPT_LIGHTS_ONE)
 };
+
+// One node of the light tree of MCPT_LIGHTS_TREE, one 64-byte segment (built by light_sampling.cpp, walked by vertex.hpp: light_pick_at).
+// A leaf is one light of the scene: its box the exact min / max of its DLightTri vertices, its weight the pick table's w_l.  An inner node:
+// the exact union of its children's boxes, w = w_left + w_right.
+struct alignas(64) DLightNode {
+    double lo[3], hi[3];        // the box
+    double w;
+    int32_t left, right;        // inner node: its children's indices (> 0); leaf: both ~light (< 0)
+};
+static_assert(sizeof(DLightNode) == 64 && offsetof(DLightNode, hi) == 24 && offsetof(DLightNode, w) == 48 && offsetof(DLightNode, left) == 56 &&
+              offsetof(DLightNode, right) == 60, "six fp64 planes, the weight, two 32-bit references: one 64-byte segment");
 
 struct DScene {
     const DNode* nodes;
@@ -149,7 +164,7 @@ struct DScene {
     double area0;                                  // range of the frozen static u1 (Q1)
     DCamera cam;
     DEnv env;                                      // rgb == null: no (active) environment
-    DLightPick pick;                               // cdf == null: MCPT_LIGHTS_ALL (or a scene of fewer than two lights)
+    DLightPick pick;                               // cdf == null: MCPT_LIGHTS_ALL (or a scene of fewer than two lights); nodes: MCPT_LIGHTS_TREE
 };
 
 #if defined(__HIPCC__)
@@ -160,6 +175,12 @@ inline bool env_on(const DEnv& e) { return e.rgb != nullptr; }
 __host__ __device__
 #endif
 inline bool pick_on(const DLightPick& p) { return p.cdf != nullptr; }
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline bool tree_on(const DLightPick& p) { return p.nodes != nullptr; }
+// the kernels' compile-time pick mode of a scene: 0 (MCPT_LIGHTS_ALL), 1 (MCPT_LIGHTS_ONE), 2 (MCPT_LIGHTS_TREE)
+inline int pick_mode(const DLightPick& p) { return tree_on(p) ? 2 : (pick_on(p) ? 1 : 0); }
 
 // device-side counters (one cache line)
 struct DCounters {

@@ -4,7 +4,7 @@
 //   device.cpp        device creation stage by stage, hierarchy queries, closest hit
 //   render.cpp        lenses, the integrator (megakernel and wavefront), mcpt_render*, statistics, (pixel, sample) queries
 //   progressive.cpp   progressive frames, AOVs, the denoiser
-//   light_sampling.cpp  MCPT_LIGHTS_ONE: the pick table, its upload, the pick's test seam
+//   light_sampling.cpp  MCPT_LIGHTS_ONE and MCPT_LIGHTS_TREE: the pick table, the light tree, their upload, the picks' test seams
 //   motion.cpp        a device's motion: the shutter's steps between two keyframes, the return to key 0
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
@@ -63,6 +63,8 @@ struct LightPickData {
     std::vector<double> weights;            // the caller's
     std::vector<double> cdf, pdf;           // the table (the checkpoint identity mixes pdf in)
     DevBuf<double> d_cdf, d_inv;
+    std::vector<DLightNode> nodes;          // MCPT_LIGHTS_TREE: the tree as uploaded (the checkpoint identity mixes its bytes in)
+    DevBuf<DLightNode> d_nodes;
     DLightPick dpick{};
 };
 }  // namespace mcpt
@@ -237,7 +239,8 @@ int env_make(const mcpt_environment* e, std::shared_ptr<mcpt::EnvData>& out);   
 // ---- light_sampling.cpp
 int light_sampling_check(const mcpt_light_sampling* ls);
 int light_weights_check(const mcpt_light_sampling* ls, size_t num_lights);   // the weights' count and values (MCPT_ERR_ARG)
-// the emitters' areas have changed (areas[num_lights], the device's light records as they are now): default weights are made again
+// the emitters have moved (areas[num_lights], the device's light records as they are now; d->upd->light_v, their vertices): default weights
+// are made again, and so is the light tree of MCPT_LIGHTS_TREE
 int light_pick_refresh(mcpt_device* d, const double* areas);
 
 // ---- render.cpp

@@ -179,8 +179,8 @@ __global__ void __launch_bounds__(256) k_primary_hits_reference(DScene S, const 
 // One lane per camera sample.  Samples of one pixel are consecutive lanes, so a wave starts from one shared
 // primary hit (coherent first vertex and shadow rays).  Radiance goes to rad[(slot*spp + k)*3]; lane k of a slot renders camera
 // sample sample_base + k (a whole frame: 0).  ENV: S.env is active (a pixel whose primary ray missed is folded from Le, not from rad).
-// ONE: S.pick is active (MCPT_LIGHTS_ONE: shade_path.hpp).
-template <bool ENV, bool ONE>
+// ONE: the pick mode of S.pick, 0 (none), 1 (MCPT_LIGHTS_ONE) or 2 (MCPT_LIGHTS_TREE): shade_path.hpp.
+template <bool ENV, int ONE>
 __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long long seed, const double* __restrict__ dirs,
                                                        const int32_t* __restrict__ pixels, const PrimaryHit* __restrict__ hits,
                                                        int first_slot, long long n_samples, int spp, int sample_base, double* __restrict__ rad, DCounters* ctr)
@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long l
 }
 
 // mcpt_sample_radiance: arbitrary (pixel, k) pairs, primary ray traced per sample.
-template <bool ENV, bool ONE>
+template <bool ENV, int ONE>
 __global__ void __launch_bounds__(256) k_sample_radiance(DScene S, unsigned long long seed, const double* __restrict__ dirs,
                                                          const int32_t* __restrict__ pix, const int32_t* __restrict__ ks, long long n,
                                                          double* __restrict__ rgb, DCounters* ctr)
@@ -236,6 +236,19 @@ __global__ void __launch_bounds__(256) k_light_pick(DLightPick pick, int nl, uns
     RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix[gid]; key.sample = (uint32_t)ks[gid];
     double inv_p;
     light[gid] = light_pick(pick, key, (uint32_t)depth, (uint32_t)nl, inv_p);
+}
+
+// mcpt_light_pick_at: the light MCPT_LIGHTS_TREE picks at the vertices (p[i], pn[i]) at `depth` of camera samples (pix[i], ks[i]), and its probability
+__global__ void __launch_bounds__(256) k_light_pick_at(DLightPick pick, int nl, unsigned long long seed, const int32_t* __restrict__ pix, const int32_t* __restrict__ ks,
+                                                       int depth, const double* __restrict__ p, const double* __restrict__ pn, long long n,
+                                                       int32_t* __restrict__ light, double* __restrict__ pdf)
+{
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= n) return;
+    RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix[gid]; key.sample = (uint32_t)ks[gid];
+    double q;
+    light[gid] = light_pick_at(pick, key, (uint32_t)depth, (uint32_t)nl, ld3(p + gid * 3), ld3(pn + gid * 3), q);
+    pdf[gid] = q;
 }
 
 // Per pixel: acc(float) += radiance/N for k = 0..N-1 in order (pathTracing.cpp:301,316-318 with D3), widened
@@ -577,27 +590,39 @@ void launch_shade_samples(const DScene& S, unsigned long long seed, const double
     const long long n = (long long)n_slots * spp;
     if (n <= 0) return;
     const dim3 grid(blocks_for(n, 256));
-    if (pick_on(S.pick)) {
-        if (env_on(S.env)) hipLaunchKernelGGL((k_shade_samples<true, true>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
-        else hipLaunchKernelGGL((k_shade_samples<false, true>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
-    } else if (env_on(S.env)) hipLaunchKernelGGL((k_shade_samples<true, false>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
-    else hipLaunchKernelGGL((k_shade_samples<false, false>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
+#define MCPT_SHADE(ENV, PICK) hipLaunchKernelGGL((k_shade_samples<ENV, PICK>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr)
+    const bool env = env_on(S.env);
+    switch (pick_mode(S.pick)) {
+    case 2: if (env) MCPT_SHADE(true, 2); else MCPT_SHADE(false, 2); break;
+    case 1: if (env) MCPT_SHADE(true, 1); else MCPT_SHADE(false, 1); break;
+    default: if (env) MCPT_SHADE(true, 0); else MCPT_SHADE(false, 0);
+    }
+#undef MCPT_SHADE
 }
 void launch_sample_radiance(const DScene& S, unsigned long long seed, const double* d_dirs, const int32_t* d_pix, const int32_t* d_k,
                             long long n, double* d_rgb, DCounters* ctr, hipStream_t st)
 {
     if (n <= 0) return;
     const dim3 grid(blocks_for(n, 256));
-    if (pick_on(S.pick)) {
-        if (env_on(S.env)) hipLaunchKernelGGL((k_sample_radiance<true, true>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
-        else hipLaunchKernelGGL((k_sample_radiance<false, true>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
-    } else if (env_on(S.env)) hipLaunchKernelGGL((k_sample_radiance<true, false>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
-    else hipLaunchKernelGGL((k_sample_radiance<false, false>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
+#define MCPT_RADIANCE(ENV, PICK) hipLaunchKernelGGL((k_sample_radiance<ENV, PICK>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr)
+    const bool env = env_on(S.env);
+    switch (pick_mode(S.pick)) {
+    case 2: if (env) MCPT_RADIANCE(true, 2); else MCPT_RADIANCE(false, 2); break;
+    case 1: if (env) MCPT_RADIANCE(true, 1); else MCPT_RADIANCE(false, 1); break;
+    default: if (env) MCPT_RADIANCE(true, 0); else MCPT_RADIANCE(false, 0);
+    }
+#undef MCPT_RADIANCE
 }
 void launch_light_pick(const DScene& S, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, int depth, long long n, int32_t* d_light, hipStream_t st)
 {
     if (n <= 0) return;
     hipLaunchKernelGGL(k_light_pick, dim3(blocks_for(n, 256)), dim3(256), 0, st, S.pick, S.num_lights, seed, d_pix, d_k, depth, n, d_light);
+}
+void launch_light_pick_at(const DScene& S, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, int depth, const double* d_p, const double* d_pn,
+                          long long n, int32_t* d_light, double* d_pdf, hipStream_t st)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_light_pick_at, dim3(blocks_for(n, 256)), dim3(256), 0, st, S.pick, S.num_lights, seed, d_pix, d_k, depth, d_p, d_pn, n, d_light, d_pdf);
 }
 void launch_fold_samples(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int spp,
                          double* d_img, const DEnv& env, const double* d_dirs, hipStream_t st)

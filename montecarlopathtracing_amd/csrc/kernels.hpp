@@ -27,6 +27,8 @@ struct LaunchCfg {
     int finish_grid_env = 0;
     unsigned logic_first_one[2] = {0, 0}, logic_rest_one[2] = {0, 0};   // ... under MCPT_LIGHTS_ONE ([1]: and an environment)
     int finish_grid_one[2] = {0, 0};
+    unsigned logic_first_tree[2] = {0, 0}, logic_rest_tree[2] = {0, 0};   // ... under MCPT_LIGHTS_TREE
+    int finish_grid_tree[2] = {0, 0};
     int array_grid = 0, primary_grid = 0;           // k_trace_persistent<ArrayRaySource> / <PrimaryRaySource>, deep stack
     int array_grid_short = 0, primary_grid_short = 0;   // ... short stack
     long long trace_block_rays = 2048;              // MCPT_TRACE_BLOCK_RAYS: a block of k_wf_trace is started per this many rays
@@ -77,6 +79,9 @@ void launch_env_sample(const DEnv& E, unsigned long long seed, const int32_t* d_
                        hipStream_t st);
 // MCPT_LIGHTS_ONE's test seam (kernels.hip): d_light[i] = the light S.pick draws at vertex `depth` of camera sample (pix[i], k[i])
 void launch_light_pick(const DScene& S, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, int depth, long long n, int32_t* d_light, hipStream_t st);
+// MCPT_LIGHTS_TREE's test seam: the light S.pick's tree gives the vertex (p[i], pn[i]) at `depth` of camera sample (pix[i], k[i]), and its probability
+void launch_light_pick_at(const DScene& S, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, int depth, const double* d_p, const double* d_pn,
+                          long long n, int32_t* d_light, double* d_pdf, hipStream_t st);
 // progressive frames: fold of samples [k0, k0 + n) of a frame of N into d_img, moments into d_mom ([W*H][2][3]), primary hit flags into d_hit
 void launch_fold_progressive(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int n, int k0, int N,
                              double* d_img, double* d_mom, uint8_t* d_hit, const DEnv& env, const double* d_dirs, hipStream_t st);

@@ -1,24 +1,28 @@
-// C ABI, light sampling (include/mcpt.h: mcpt_device_set_light_sampling ... mcpt_light_pick): validation, the pick table in fp64, its
-// upload and the test seam.  The kernels that use it are in vertex.hpp (light_pick, light_sample_one).
+// C ABI, light sampling (include/mcpt.h: mcpt_device_set_light_sampling ... mcpt_light_pick_at): validation, the pick table and the light
+// tree in fp64, their upload and the test seams.  The kernels that use them are in vertex.hpp (light_pick, light_pick_at, light_sample_one).
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
 #include "handles.hpp"
+#include "light_tree.hpp"
 
 using namespace mcpt;
 
 int light_sampling_check(const mcpt_light_sampling* ls)
 {
     if (!ls) return MCPT_OK;
-    if (ls->mode != MCPT_LIGHTS_ALL && ls->mode != MCPT_LIGHTS_ONE) return fail(MCPT_ERR_ARG, "mcpt_light_sampling.mode must be MCPT_LIGHTS_ALL or MCPT_LIGHTS_ONE");
+    if (ls->mode != MCPT_LIGHTS_ALL && ls->mode != MCPT_LIGHTS_ONE && ls->mode != MCPT_LIGHTS_TREE)
+        return fail(MCPT_ERR_ARG, "mcpt_light_sampling.mode must be MCPT_LIGHTS_ALL, MCPT_LIGHTS_ONE or MCPT_LIGHTS_TREE");
     if (ls->num_weights < 0 || (ls->num_weights > 0) != (ls->weights != nullptr)) return fail(MCPT_ERR_ARG, "mcpt_light_sampling: num_weights and weights must go together");
     return MCPT_OK;
 }
 
 // The table of mcpt.h from the lights' radiances and areas (or the caller's weights), sequential sums left to right.  false: a weight
 // is negative or not finite, or the caller's weights are all zero.
-static bool pick_table(const std::vector<LightRec>& lights, const double* areas, const double* weights, std::vector<double>& cdf, std::vector<double>& pdf, int& last)
+static bool pick_table(const std::vector<LightRec>& lights, const double* areas, const double* weights, std::vector<double>& cdf, std::vector<double>& pdf, int& last,
+                       std::vector<double>* w_out = nullptr)
 {
     const size_t n = lights.size();
     std::vector<double> w(n);
@@ -48,7 +52,87 @@ static bool pick_table(const std::vector<LightRec>& lights, const double* areas,
     }
     if (last < 0 || !std::isfinite(run)) return false;
     for (size_t l = 0; l < n; l++) pdf[l] = w[l] / run;
+    if (w_out) w_out->swap(w);
     return true;
+}
+
+// ---- the light tree of MCPT_LIGHTS_TREE
+// box[l] = lo.xyz, hi.xyz: the exact min / max of the vertices of light l's triangles.  light_v: the emitter faces' vertices, light by light
+// in material face order (an updated device's: mcpt_device::Update::light_v), or null for the scene's own.
+static void light_boxes(const Scene& s, const double* light_v, std::vector<double>& box)
+{
+    box.assign(s.lights.size() * 6, 0.0);
+    size_t at = 0;
+    for (size_t l = 0; l < s.lights.size(); l++) {
+        double* b = box.data() + l * 6;
+        for (int a = 0; a < 3; a++) { b[a] = INFINITY; b[3 + a] = -INFINITY; }
+        for (int32_t f : s.materials[s.lights[l].material].faces)
+            for (int c = 0; c < 3; c++) {
+                double q[3];
+                if (light_v) { for (int a = 0; a < 3; a++) q[a] = light_v[at + size_t(c) * 3 + a]; }
+                else { const Vec3& v = s.faces[size_t(f)].v[c]; q[0] = v.x; q[1] = v.y; q[2] = v.z; }
+                for (int a = 0; a < 3; a++) { if (q[a] < b[a]) b[a] = q[a]; if (q[a] > b[3 + a]) b[3 + a] = q[a]; }
+                if (c == 2) at += 9;
+            }
+    }
+}
+
+// Top-down, nodes in preorder (root 0, a node's left subtree right behind it): the lights of a node are split at the median of their box
+// centres along the widest axis of those centres' bounds (the lowest axis among equals); ties are broken by light index; the left side
+// gets the larger half.  The depth is ceil(log2 nl).
+static int tree_node(const std::vector<double>& box, const std::vector<double>& w, std::vector<int>& idx, size_t b, size_t e, std::vector<DLightNode>& nodes)
+{
+    const int me = int(nodes.size());
+    nodes.emplace_back();
+    if (e - b == 1) {
+        const int l = idx[b];
+        DLightNode n{};
+        for (int a = 0; a < 3; a++) { n.lo[a] = box[size_t(l) * 6 + a]; n.hi[a] = box[size_t(l) * 6 + 3 + a]; }
+        n.w = w[size_t(l)]; n.left = n.right = ~l;
+        nodes[size_t(me)] = n;
+        return me;
+    }
+    auto centre = [&](int l, int a) { return (box[size_t(l) * 6 + a] + box[size_t(l) * 6 + 3 + a]) * 0.5; };
+    int axis = 0;
+    double widest = -1.0;
+    for (int a = 0; a < 3; a++) {
+        double lo = INFINITY, hi = -INFINITY;
+        for (size_t i = b; i < e; i++) { const double c = centre(idx[i], a); if (c < lo) lo = c; if (c > hi) hi = c; }
+        if (hi - lo > widest) { widest = hi - lo; axis = a; }
+    }
+    std::sort(idx.begin() + long(b), idx.begin() + long(e), [&](int x, int y) { const double cx = centre(x, axis), cy = centre(y, axis); return cx < cy || (cx == cy && x < y); });
+    const size_t mid = b + (e - b + 1) / 2;
+    const int left = tree_node(box, w, idx, b, mid, nodes), right = tree_node(box, w, idx, mid, e, nodes);
+    DLightNode n{};
+    const DLightNode &L = nodes[size_t(left)], &R = nodes[size_t(right)];
+    for (int a = 0; a < 3; a++) { n.lo[a] = L.lo[a] < R.lo[a] ? L.lo[a] : R.lo[a]; n.hi[a] = L.hi[a] > R.hi[a] ? L.hi[a] : R.hi[a]; }
+    n.w = L.w + R.w; n.left = left; n.right = right;
+    nodes[size_t(me)] = n;
+    return me;
+}
+
+static void tree_build(const std::vector<double>& box, const std::vector<double>& w, std::vector<DLightNode>& nodes)
+{
+    nodes.clear();
+    std::vector<int> idx(w.size());
+    for (size_t l = 0; l < idx.size(); l++) idx[l] = int(l);
+    nodes.reserve(2 * w.size());
+    tree_node(box, w, idx, 0, idx.size(), nodes);
+}
+
+// the probability of every light at the vertex (p, pn): the products light_pick_at forms on its way down, for every leaf
+static void tree_pdf(const std::vector<DLightNode>& nodes, const double* p, const double* pn, double* pdf)
+{
+    std::vector<std::pair<int, double>> todo{{0, 1.0}};
+    while (!todo.empty()) {
+        const auto [n, q] = todo.back();
+        todo.pop_back();
+        const DLightNode& nd = nodes[size_t(n)];
+        if (nd.left < 0) { pdf[~nd.left] = q; continue; }
+        const double pL = light_tree_left(nodes[size_t(nd.left)], nodes[size_t(nd.right)], p[0], p[1], p[2], pn[0], pn[1], pn[2]);
+        if (pL >= 1.0) { todo.push_back({nd.left, q}); todo.push_back({nd.right, 0.0}); }
+        else { todo.push_back({nd.left, q * pL}); todo.push_back({nd.right, q * (1.0 - pL)}); }
+    }
 }
 
 // d's table from its state (the caller's weights, or the lights' current areas: null = the scene's), copied into the device's two arrays
@@ -57,15 +141,25 @@ static int pick_upload(mcpt_device* d, LightPickData& k, const double* areas)
 {
     const std::vector<LightRec>& lights = d->scene->s.lights;
     int last = -1;
-    if (!pick_table(lights, areas, k.own_weights ? k.weights.data() : nullptr, k.cdf, k.pdf, last)) return fail(MCPT_ERR_ARG, "light weights: negative, not finite or all zero");
+    std::vector<double> w;
+    if (!pick_table(lights, areas, k.own_weights ? k.weights.data() : nullptr, k.cdf, k.pdf, last, &w)) return fail(MCPT_ERR_ARG, "light weights: negative, not finite or all zero");
     std::vector<double> inv(k.pdf.size());
     for (size_t l = 0; l < inv.size(); l++) inv[l] = k.pdf[l] > 0.0 ? 1.0 / k.pdf[l] : 0.0;
     if (!k.d_cdf) { HIP_TRY(k.d_cdf.alloc(k.cdf.size())); HIP_TRY(k.d_inv.alloc(inv.size())); }
     HIP_TRY(hipMemcpy(k.d_cdf.get(), k.cdf.data(), k.cdf.size() * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(k.d_inv.get(), inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice));
     k.dpick = DLightPick{};
-    if (k.mode == MCPT_LIGHTS_ONE && lights.size() >= 2) {          // (none or one light: the mode changes nothing)
+    k.nodes.clear();
+    if (k.mode != MCPT_LIGHTS_ALL && lights.size() >= 2) {          // (none or one light: the mode changes nothing)
         k.dpick.cdf = k.d_cdf.get(); k.dpick.inv_pdf = k.d_inv.get(); k.dpick.Z = k.cdf.back(); k.dpick.last = last;
+        if (k.mode == MCPT_LIGHTS_TREE) {                           // boxes from the light triangles as they are now
+            std::vector<double> box;
+            light_boxes(d->scene->s, d->upd ? d->upd->light_v.data() : nullptr, box);
+            tree_build(box, w, k.nodes);
+            if (!k.d_nodes) HIP_TRY(k.d_nodes.alloc(k.nodes.size()));
+            HIP_TRY(hipMemcpy(k.d_nodes.get(), k.nodes.data(), k.nodes.size() * sizeof(DLightNode), hipMemcpyHostToDevice));
+            k.dpick.nodes = k.d_nodes.get();
+        }
     }
     return MCPT_OK;
 }
@@ -85,7 +179,7 @@ int light_weights_check(const mcpt_light_sampling* ls, size_t nl)
 
 int light_pick_refresh(mcpt_device* d, const double* areas)
 {
-    if (!d->pick || d->pick->own_weights) return MCPT_OK;
+    if (!d->pick || (d->pick->own_weights && d->pick->mode != MCPT_LIGHTS_TREE)) return MCPT_OK;   // (the tree's boxes follow the emitters whatever the weights)
     if (const int rc = pick_upload(d, *d->pick, areas)) return rc;
     d->ds.pick = d->pick->dpick;
     return MCPT_OK;
@@ -102,6 +196,39 @@ int mcpt_scene_light_pick_table(const mcpt_scene* h, const double* weights, doub
     if (!pick_table(h->s.lights, nullptr, weights, c, p, last)) return fail(MCPT_ERR_ARG, "light weights: negative, not finite or all zero");
     std::memcpy(cdf, c.data(), c.size() * sizeof(double));
     std::memcpy(pdf, p.data(), p.size() * sizeof(double));
+    return MCPT_OK;
+}
+
+// the tree of the scene's own lights under `weights` (null: the default ones); MCPT_ERR_ARG as mcpt_scene_light_pick_table, or fewer than two lights
+static int scene_tree(const mcpt_scene* h, const double* weights, std::vector<DLightNode>& nodes)
+{
+    if (!h) return fail(MCPT_ERR_ARG, "null argument");
+    if (h->s.lights.size() < 2) return fail(MCPT_ERR_ARG, "a scene of fewer than two lights holds no light tree");
+    std::vector<double> c, p, w, box;
+    int last = -1;
+    if (!pick_table(h->s.lights, nullptr, weights, c, p, last, &w)) return fail(MCPT_ERR_ARG, "light weights: negative, not finite or all zero");
+    light_boxes(h->s, nullptr, box);
+    tree_build(box, w, nodes);
+    return MCPT_OK;
+}
+
+int mcpt_scene_light_tree(const mcpt_scene* h, const double* weights, int32_t* n_nodes, void* out)
+{
+    if (!n_nodes) return fail(MCPT_ERR_ARG, "null argument");
+    std::vector<DLightNode> nodes;
+    if (const int rc = scene_tree(h, weights, nodes)) return rc;
+    *n_nodes = int32_t(nodes.size());
+    if (out) std::memcpy(out, nodes.data(), nodes.size() * sizeof(DLightNode));
+    return MCPT_OK;
+}
+
+int mcpt_scene_light_tree_pdf(const mcpt_scene* h, const double* weights, const double* p, const double* pn, int64_t n, double* pdf)
+{
+    if (n < 0 || (n > 0 && (!p || !pn || !pdf))) return fail(MCPT_ERR_ARG, "bad argument");
+    std::vector<DLightNode> nodes;
+    if (const int rc = scene_tree(h, weights, nodes)) return rc;
+    const size_t nl = h->s.lights.size();
+    for (int64_t i = 0; i < n; i++) tree_pdf(nodes, p + i * 3, pn + i * 3, pdf + size_t(i) * nl);
     return MCPT_OK;
 }
 
@@ -156,6 +283,7 @@ int mcpt_light_pick(mcpt_device* d, uint64_t seed, const int32_t* pix, const int
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
     if (!pick_on(d->ds.pick)) return fail(MCPT_ERR_ARG, "the device does not pick lights (MCPT_LIGHTS_ALL, or a scene of fewer than two lights)");
+    if (tree_on(d->ds.pick)) return fail(MCPT_ERR_ARG, "under MCPT_LIGHTS_TREE the pick depends on the vertex: mcpt_light_pick_at");
     if (n == 0) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
     DevBuf<int32_t> d_pix, d_k, d_light;
@@ -169,6 +297,35 @@ int mcpt_light_pick(mcpt_device* d, uint64_t seed, const int32_t* pix, const int
     HIP_TRY(hipStreamSynchronize(d->stream.get()));
     HIP_TRY(hipMemcpy(light, d_light.get(), size_t(n) * 4, hipMemcpyDeviceToHost));
     for (int64_t i = 0; i < n; i++) pdf[i] = d->pick->pdf[size_t(light[i])];
+    return MCPT_OK;
+}
+
+int mcpt_light_pick_at(mcpt_device* d, uint64_t seed, const int32_t* pix, const int32_t* k, int32_t depth, const double* p, const double* pn, int64_t n,
+                       int32_t* light, double* pdf)
+{
+    if (!pix || !k || !p || !pn || !light || !pdf || n < 0 || depth < 0 || depth >= MCPT_MAX_DEPTH) return fail(MCPT_ERR_ARG, "bad argument");
+    if (const int rc = require_device()) return rc;
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (!tree_on(d->ds.pick)) return fail(MCPT_ERR_ARG, "the device does not pick lights by tree (MCPT_LIGHTS_TREE on a scene of two or more lights)");
+    if (n == 0) return MCPT_OK;
+    HIP_TRY(hipSetDevice(d->ordinal));
+    DevBuf<int32_t> d_pix, d_k, d_light;
+    DevBuf<double> d_p, d_pn, d_pdf;
+    HIP_TRY(d_pix.alloc(size_t(n)));
+    HIP_TRY(d_k.alloc(size_t(n)));
+    HIP_TRY(d_light.alloc(size_t(n)));
+    HIP_TRY(d_p.alloc(size_t(n) * 3));
+    HIP_TRY(d_pn.alloc(size_t(n) * 3));
+    HIP_TRY(d_pdf.alloc(size_t(n)));
+    HIP_TRY(hipMemcpy(d_pix.get(), pix, size_t(n) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_k.get(), k, size_t(n) * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_p.get(), p, size_t(n) * 24, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_pn.get(), pn, size_t(n) * 24, hipMemcpyHostToDevice));
+    launch_light_pick_at(d->ds, seed, d_pix.get(), d_k.get(), depth, d_p.get(), d_pn.get(), n, d_light.get(), d_pdf.get(), d->stream.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(d->stream.get()));
+    HIP_TRY(hipMemcpy(light, d_light.get(), size_t(n) * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pdf, d_pdf.get(), size_t(n) * 8, hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
 

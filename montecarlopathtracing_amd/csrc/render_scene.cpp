@@ -132,6 +132,7 @@ static uint64_t frame_tag(const Scene& s, const mcpt_lens* l, const EnvData* env
         const char tag[] = "lpck";
         const int64_t mode = pick->mode;
         mix(tag, 4); mix(&mode, sizeof mode); mix(pick->pdf.data(), pick->pdf.size() * sizeof(double));
+        if (tree_on(pick->dpick)) mix(pick->nodes.data(), pick->nodes.size() * sizeof(DLightNode));      // MCPT_LIGHTS_TREE: the node bytes too
     }
     return h;
 }

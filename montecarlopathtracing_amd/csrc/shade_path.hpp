@@ -15,9 +15,9 @@ namespace mcpt {
 // in_type (depth0 = 0, T = 1, L = 0, in_type = TRANSMISSION for a fresh camera sample).  FAST selects the walk
 // (trace_lane_fast with this lane's LDS stack, or the reference-shaped trace_closest); both give the same hits.  ENV: S.env is active
 // (env.hpp) -- one more shadow ray per vertex after the lights', and a SPECULAR / TRANSMISSION bounce ray that leaves the scene adds
-// T' * Le; without it the code is what it was before environments existed.  ONE: S.pick is active (MCPT_LIGHTS_ONE) -- one shadow ray for the
-// light vertex.hpp's light_pick draws instead of one per light; a light behind the surface is counted as skipped and not traced.
-template <bool FAST, bool ENV = false, bool ONE = false>
+// T' * Le; without it the code is what it was before environments existed.  ONE: the pick mode (1: MCPT_LIGHTS_ONE, 2: MCPT_LIGHTS_TREE) -- one shadow ray for the
+// light vertex.hpp's light_pick or light_pick_at draws instead of one per light; a light behind the surface is counted as skipped and not traced.
+template <bool FAST, bool ENV = false, int ONE = 0>
 __device__ void shade_path_from(const DScene& S, const RngKey& key, uint32_t depth0, V3 T, V3 L, V3 dir, int in_type, Hit hit, double out[3],
                                 LaneStats& ls, int* lds_stack, int stride)
 {
@@ -59,7 +59,7 @@ __device__ void shade_path_from(const DScene& S, const RngKey& key, uint32_t dep
         int sample_mat = -1;
         if constexpr (ONE) {
             V3 direction, c;
-            const int expect = light_sample_one(S, key, depth, hit.p, pn, kd, direction, c);
+            const int expect = light_sample_one<ONE>(S, key, depth, hit.p, pn, kd, direction, c);
             if (expect != -2) {
                 Ray rl; rl.o = hit.p + direction * 0.01; rl.d = direction;
                 Hit inter;
@@ -182,7 +182,7 @@ __device__ void shade_path_from(const DScene& S, const RngKey& key, uint32_t dep
 }
 
 // a fresh camera sample through the reference-shaped walk (megakernel pipeline)
-template <bool ENV = false, bool ONE = false>
+template <bool ENV = false, int ONE = 0>
 __device__ __forceinline__ void shade_path(const DScene& S, const RngKey& key, V3 view_dir, Hit hit, double out[3], LaneStats& ls)
 {
     shade_path_from<false, ENV, ONE>(S, key, 0u, mk(1, 1, 1), mk(0, 0, 0), neg(view_dir), RT_TRANSMISSION, hit, out, ls, nullptr, 0);

@@ -699,7 +699,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                     int sample_mat = -1;
                     for (int l = 0; l < nplanes; l++) {
                         V3 direction, cc;
-                        const int expect = PP::kOne ? light_sample_one(S, key, depth, p, pn, kd, direction, cc) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, cc);
+                        const int expect = PP::kOne ? light_sample_one<PP::kOne>(S, key, depth, p, pn, kd, direction, cc) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, cc);
                         ri[(size_t)(RI_EXPECT + l) * plane] = expect;
                         if (expect != -2) { stp(RD_C + 3 * l, cc); emit(s0 + l, p + direction * 0.01, direction); n_shadow++; }
                         else n_skipped++;

@@ -4,6 +4,7 @@
 #pragma once
 #include "dev_common.hpp"
 #include "shade_common.hpp"
+#include "light_tree.hpp"
 
 namespace mcpt {
 
@@ -72,12 +73,38 @@ __device__ __forceinline__ int light_pick(const DLightPick& P, const RngKey& key
     return lo;
 }
 
-// MCPT_LIGHTS_ONE: the one light sample of the vertex -- light_sample of the picked light (its own Philox block, no light before it
-// to inherit a material from), c scaled by 1 / p_l.  Returns as light_sample does.
+// MCPT_LIGHTS_TREE: the light picked at the vertex (p, pn) at `depth` of a camera sample, and the probability it was picked with.  The draw is
+// light_pick's (slot 0 of Philox block nl + 3), so every other draw keeps its value.  From the root, at every inner node the left child is
+// taken with probability pL (light_tree.hpp: importance by distance and horizon) and the draw is stretched over the side taken; the tree is
+// a median split, ceil(log2 nl) levels deep, and the descent keeps no stack.  pL is 1.0 (or 0.0) exactly where a side is culled or has
+// weight 0: u / 1.0, pdf * 1.0 and (u - 0.0) / (1.0 - 0.0) change no bit, so those cases need no code of their own.
+__device__ __forceinline__ int light_pick_at(const DLightPick& P, const RngKey& key, uint32_t depth, uint32_t nl, const V3& p, const V3& pn, double& pdf)
+{
+    double u = uniform1(key, depth, nl + 3u);
+    pdf = 1.0;
+    int n = 0, l;
+    while ((l = P.nodes[n].left) >= 0) {
+        const int r = P.nodes[n].right;
+        const double pL = light_tree_left(P.nodes[l], P.nodes[r], p.x, p.y, p.z, pn.x, pn.y, pn.z);
+        if (pL >= 1.0) n = l;
+        else if (u < pL) { n = l; u = u / pL; pdf *= pL; }
+        else { n = r; u = (u - pL) / (1.0 - pL); pdf *= (1.0 - pL); }
+    }
+    return ~l;
+}
+
+// MCPT_LIGHTS_ONE (MODE 1) and MCPT_LIGHTS_TREE (MODE 2): the one light sample of the vertex -- light_sample of the picked light (its own
+// Philox block, no light before it to inherit a material from), c scaled by 1 / p_l.  Returns as light_sample does.
+template <int MODE>
 __device__ __forceinline__ int light_sample_one(const DScene& S, const RngKey& key, uint32_t depth, const V3& p, const V3& pn, const V3& kd, V3& direction, V3& c)
 {
     double inv_p;
-    const int l = light_pick(S.pick, key, depth, (uint32_t)S.num_lights, inv_p);
+    int l;
+    if constexpr (MODE == 2) {
+        double pdf;
+        l = light_pick_at(S.pick, key, depth, (uint32_t)S.num_lights, p, pn, pdf);
+        inv_p = 1.0 / pdf;
+    } else l = light_pick(S.pick, key, depth, (uint32_t)S.num_lights, inv_p);
     int sample_mat = -1;
     const int expect = light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, c);
     if (expect != -2) c = mk(c.x * inv_p, c.y * inv_p, c.z * inv_p);

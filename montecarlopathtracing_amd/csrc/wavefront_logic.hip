@@ -53,9 +53,9 @@ __device__ __forceinline__ void sstc(double* __restrict__ a, long long cap, long
 // evaluation is free): L, p and the sample id are stored before anything is computed, the incoming direction dies with
 // bounce_sample -- the later passes' values that are alive at the same time, and with them the registers the compiler had to
 // park in scratch memory (39 at 4 waves per SIMD), are what this order is about.  ENV: an active environment, shadow plane nl - 1 after
-// the scene's nl - 1 lights (WfArgs::nl counts planes; the Philox block base is the lights' count).  ONE: S.pick is active (MCPT_LIGHTS_ONE) --
+// the scene's nl - 1 lights (WfArgs::nl counts planes; the Philox block base is the lights' count).  ONE: the pick mode of S.pick (1: MCPT_LIGHTS_ONE, 2: MCPT_LIGHTS_TREE) --
 // the lights have one plane, plane 0, for the light vertex.hpp's light_pick draws; the block base is S.num_lights, whatever nl says.
-template <bool FIRST, bool ENV, bool ONE>
+template <bool FIRST, bool ENV, int ONE>
 __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a, long long j, int id, int leaf, const V3& p, const V3& dir, const V3& T, const V3& L,
                                                 int mat_first, int pix_first, const V3& pn_first, const V3& kd_first, LaneStats& ls)
 {
@@ -89,7 +89,7 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
     int sample_mat = -1;
     for (int l = 0; l < nplanes; l++) {
         V3 direction, c;
-        const int expect = ONE ? light_sample_one(S, key, depth, p, pn, kd, direction, c) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, c);
+        const int expect = ONE ? light_sample_one<ONE>(S, key, depth, p, pn, kd, direction, c) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, c);
         if (expect != -2) {
             sstc(a.out.c + (long long)l * 3 * cap, cap, j, folded ? mk(T.x * c.x, T.y * c.y, T.z * c.z) : c);
             sstc(a.rays.d + (long long)l * 3 * cap, cap, j, direction);       // origin p + direction * 0.01: WfRaySource
@@ -129,8 +129,8 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
 // before: no slot is overwritten while it is read.
 //
 // ENV: an active environment (wf_shade_vertex's last shadow plane; a bounce ray that left the scene adds T' * Le, a camera ray Le).
-// ONE: MCPT_LIGHTS_ONE (wf_shade_vertex; the resolve sees planes only and is the same code).
-template <bool FIRST, bool ENV, bool ONE>
+// ONE: the pick mode, 1 (MCPT_LIGHTS_ONE) or 2 (MCPT_LIGHTS_TREE) (wf_shade_vertex; the resolve sees planes only and is the same code).
+template <bool FIRST, bool ENV, int ONE>
 __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOGIC_WAVES) k_wf_logic(DScene S, WfArgs a)
 {
     const long long n_prev = (long long)a.counts_in->n_next * a.count_mul;
@@ -352,7 +352,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
 // take the next unclaimed path (one atomic per refill on the pass's own count slot), so a wave is as long as its share of
 // the work, not as its longest path.  A lane that has just adopted a path finds the rays of its first step in the wavefront
 // state instead of computing them; from the second step on everything lives in registers.  ENV, ONE: as k_wf_logic.
-template <bool ENV, bool ONE>
+template <bool ENV, int ONE>
 __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, WfArgs a)
 {
     __shared__ int lds_stack[MCPT_FAST_STACK * 256];
@@ -441,7 +441,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
                     expect = env_light_sample(S.env, key, depth, (uint32_t)nlights, pn, kd, r.d, c);
                     if (expect != -2) ls.shadow++;
                 } else {
-                    expect = ONE ? light_sample_one(S, key, depth, p, pn, kd, r.d, c) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, r.d, c);
+                    expect = ONE ? light_sample_one<ONE>(S, key, depth, p, pn, kd, r.d, c) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, r.d, c);
                     if (expect != -2) ls.shadow++; else ls.skipped++;
                 }
             } else if (mode == M_ADOPTED) {
@@ -548,11 +548,11 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
 #ifndef MCPT_POOL_NPC
 #define MCPT_POOL_NPC (MCPT_POOL_KT / 2)           /* path slots per lane the record planes are laid out for (one light: KT / 2 paths) */
 #endif
-template <bool ENV, bool ONE>
+template <bool ENV, int ONE>
 struct WfPaths {
     static constexpr bool kPaths = true;
     static constexpr bool kEnv = ENV;           // an active environment: the last of the nl shadow planes (see k_wf_logic)
-    static constexpr bool kOne = ONE;           // MCPT_LIGHTS_ONE: the lights' one plane holds the picked light's sample
+    static constexpr int kOne = ONE;            // MCPT_LIGHTS_ONE (1) or MCPT_LIGHTS_TREE (2): the lights' one plane holds the picked light's sample
     WfArgs a;
     long long n;                // paths handed over (positions 0 .. n-1 of the wavefront state a.out)
     int nl, npc;
@@ -573,7 +573,7 @@ size_t finish_pool_bytes(int cus, int nl)
     return blocks * (size_t(9 + 3 * nl) * plane * sizeof(double) + size_t(3 + nl) * plane * sizeof(int) + size_t(MCPT_POOL_WAVES) * 64 * MCPT_FAST_STACK * sizeof(int));
 }
 
-template <int NW, int KT, int SCAP, bool ENV, bool ONE>
+template <int NW, int KT, int SCAP, bool ENV, int ONE>
 __global__ void __launch_bounds__(NW * 64, 1) k_wf_finish_pool(DScene S, WfArgs a, char* area, int* spill)
 {
     const long long n = a.counts->n_next;
@@ -699,6 +699,17 @@ void launch_wf_logic(const DScene& S, const WfArgs& a, long long n_upper, bool f
     if (n_upper <= 0) return;
     // small inputs get small grids (>= 1024 paths per block): every wave that starts costs a few atomics on shared counters
     const bool env = env_on(S.env);
+    if (tree_on(S.pick)) {
+        const unsigned g = grid_for(n_upper, 1024, first ? cfg.logic_first_tree[env] : cfg.logic_rest_tree[env]);
+        if (first) {
+            if (env) hipLaunchKernelGGL((k_wf_logic<true, true, 2>), dim3(g), dim3(256), 0, st, S, a);
+            else hipLaunchKernelGGL((k_wf_logic<true, false, 2>), dim3(g), dim3(256), 0, st, S, a);
+        } else {
+            if (env) hipLaunchKernelGGL((k_wf_logic<false, true, 2>), dim3(g), dim3(256), 0, st, S, a);
+            else hipLaunchKernelGGL((k_wf_logic<false, false, 2>), dim3(g), dim3(256), 0, st, S, a);
+        }
+        return;
+    }
     if (pick_on(S.pick)) {
         const unsigned g = grid_for(n_upper, 1024, first ? cfg.logic_first_one[env] : cfg.logic_rest_one[env]);
         if (first) {
@@ -731,7 +742,10 @@ void launch_wf_finish(const DScene& S, const WfArgs& a, long long n_upper, hipSt
         const int g = (int)(nb < cfg.cus ? nb : cfg.cus);
         int* const spill = reinterpret_cast<int*>(slow_list + slow_cap);
         const dim3 block(MCPT_POOL_WAVES * 64);
-        if (pick_on(S.pick)) {
+        if (tree_on(S.pick)) {
+            if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, true, 2>), dim3(g), block, 0, st, S, a, path_area, spill);
+            else hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, false, 2>), dim3(g), block, 0, st, S, a, path_area, spill);
+        } else if (pick_on(S.pick)) {
             if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, true, true>), dim3(g), block, 0, st, S, a, path_area, spill);
             else hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, false, true>), dim3(g), block, 0, st, S, a, path_area, spill);
         } else if (env_on(S.env))
@@ -740,7 +754,11 @@ void launch_wf_finish(const DScene& S, const WfArgs& a, long long n_upper, hipSt
             hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, false, false>), dim3(g), block, 0, st, S, a, path_area, spill);
         return;
     }
-    if (pick_on(S.pick)) {
+    if (tree_on(S.pick)) {
+        const unsigned g = grid_for(n_upper, 256, unsigned(cfg.finish_grid_tree[env_on(S.env)]));
+        if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish<true, 2>), dim3(g), dim3(256), 0, st, S, a);
+        else hipLaunchKernelGGL((k_wf_finish<false, 2>), dim3(g), dim3(256), 0, st, S, a);
+    } else if (pick_on(S.pick)) {
         const unsigned g = grid_for(n_upper, 256, unsigned(cfg.finish_grid_one[env_on(S.env)]));
         if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish<true, true>), dim3(g), dim3(256), 0, st, S, a);
         else hipLaunchKernelGGL((k_wf_finish<false, true>), dim3(g), dim3(256), 0, st, S, a);
@@ -775,6 +793,13 @@ void init_launch_cfg_logic(LaunchCfg& cfg, unsigned forced_grid)
     cfg.logic_rest_one[1] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, true, true>), cfg.cus));
     cfg.finish_grid_one[0] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<false, true>), cfg.cus);
     cfg.finish_grid_one[1] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<true, true>), cfg.cus);
+    // MCPT_LIGHTS_TREE likewise
+    cfg.logic_first_tree[0] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, false, 2>), cfg.cus));
+    cfg.logic_first_tree[1] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, true, 2>), cfg.cus));
+    cfg.logic_rest_tree[0] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, false, 2>), cfg.cus));
+    cfg.logic_rest_tree[1] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, true, 2>), cfg.cus));
+    cfg.finish_grid_tree[0] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<false, 2>), cfg.cus);
+    cfg.finish_grid_tree[1] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<true, 2>), cfg.cus);
 }
 
 }  // namespace mcpt

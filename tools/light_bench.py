@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Diagnostic: what MCPT_LIGHTS_ONE buys on a room of many lights (tests/light_scenes.py).  The 10- and 40-light rooms at 1280x720, SPP 256
-by default, on one GPU under "all" (every light at every vertex) and "one" (one picked light per vertex), the two modes alternated in one
+"""Diagnostic: what MCPT_LIGHTS_ONE and MCPT_LIGHTS_TREE buy on a room of many lights (tests/light_scenes.py).  The 10- and 40-light rooms at
+1280x720, SPP 256 by default, on one GPU under "all" (every light at every vertex), "one" (one light per vertex from the global table) and
+"tree" (one light per vertex from the light tree: distance and horizon), the modes alternated in one
 process so that they see the same clocks and the same caches; three frames of each by default, after one warm-up frame of each.
 
     python tools/light_bench.py [--lights 10,40] [--width 1280 --height 720] [--spp 256] [--frames 3] [--seed 0]
@@ -10,7 +11,8 @@ Prints one JSON line per frame (mode, device ms of the frame = mcpt_stats.ms_tot
 of each mode, the shadow rays, the bytes of wavefront state per path (wavefront.hip: wf_bytes_per_path, restated here) and the chunks a
 frame of that many paths takes in the library's default workspace (half of the free HBM; an estimate from hipMemGetInfo, null without torch).
 --rmse-lights N (0: skip): on the N-light room, the RMSE against an "all" frame of --rmse-ref-spp samples of "all" at --rmse-spp and of
-"one" at the sample count that takes the same measured time (the ratio of the two modes' median ms per sample, measured at --rmse-spp)."""
+"one" and of "tree", each at the sample count that takes the same measured time (the ratio of the modes' median ms per sample, measured at
+--rmse-spp)."""
 import argparse
 import json
 import os
@@ -53,8 +55,9 @@ def frames(M, dev, modes, spp, n, seed, label):
                 continue
             times[m].append(st.ms_total)
             shadow[m] = st.rays_shadow
+            shadow[m + "_skipped"] = st.shadow_skipped
             print(json.dumps(dict(label, mode=m, frame=i, spp=spp, ms_total=round(st.ms_total, 3), ms_trace=round(st.ms_trace, 3),
-                                  rays_shadow=st.rays_shadow, rays_bounce=st.rays_bounce, launches=st.launches)), flush=True)
+                                  rays_shadow=st.rays_shadow, shadow_skipped=st.shadow_skipped, rays_bounce=st.rays_bounce, launches=st.launches)), flush=True)
     dev.set_light_sampling(None)
     return {m: statistics.median(v) for m, v in times.items()}, shadow
 
@@ -81,11 +84,12 @@ def main():
         light_scenes.write(d, name, nl, args.width, args.height)
         sc = M.Scene(d, name, width=args.width, height=args.height)
         dev = M.Device(sc, 0)
-        med, shadow = frames(M, dev, ("all", "one"), args.spp, args.frames, args.seed, {"lights": nl})
+        med, shadow = frames(M, dev, ("all", "one", "tree"), args.spp, args.frames, args.seed, {"lights": nl})
         paths = args.width * args.height * args.spp
-        bpp = {"all": bytes_per_path(nl), "one": bytes_per_path(1)}
+        bpp = {"all": bytes_per_path(nl), "one": bytes_per_path(1), "tree": bytes_per_path(1)}
         print(json.dumps({"lights": nl, "width": args.width, "height": args.height, "spp": args.spp, "build_id": M.build_id(),
                           "median_ms": {k: round(v, 3) for k, v in med.items()}, "all_over_one": round(med["all"] / med["one"], 3),
+                          "tree_over_one": round(med["tree"] / med["one"], 3),
                           "rays_shadow": shadow, "bytes_per_path": bpp, "chunks": {k: chunks(paths, v) for k, v in bpp.items()}}), flush=True)
         dev.close()
         sc.close()
@@ -96,24 +100,27 @@ def main():
         sc = M.Scene(d, name, width=w, height=h)
         dev = M.Device(sc, 0)
         ref = dev.generateImg(args.rmse_ref_spp, seed=args.seed + 1000)
-        med, _ = frames(M, dev, ("all", "one"), args.rmse_spp, args.frames, args.seed, {"lights": nl, "rmse": True})
-        spp_one = max(1, int(round(args.rmse_spp * med["all"] / med["one"])))
-        dev.set_light_sampling("one")
-        st = M.Stats()
-        dev.generateImg(spp_one, seed=args.seed, stats=st)            # (sizes the buffers for this count)
-        one_ms = []
-        for _ in range(args.frames):
-            st = M.Stats()
-            one = dev.generateImg(spp_one, seed=args.seed, stats=st)
-            one_ms.append(st.ms_total)
-        dev.set_light_sampling(None)
-        full = dev.generateImg(args.rmse_spp, seed=args.seed)
+        med, _ = frames(M, dev, ("all", "one", "tree"), args.rmse_spp, args.frames, args.seed, {"lights": nl, "rmse": True})
 
         def rmse(a):
             return float(np.sqrt(np.mean((a - ref) ** 2)))
-        print(json.dumps({"lights": nl, "width": w, "height": h, "ref_spp": args.rmse_ref_spp, "all_spp": args.rmse_spp, "all_ms": round(med["all"], 3),
-                          "all_rmse": round(rmse(full), 6), "one_spp": spp_one, "one_ms": round(statistics.median(one_ms), 3),
-                          "one_rmse": round(rmse(one), 6), "ref_mean": round(float(ref.mean()), 6)}), flush=True)
+        out = {"lights": nl, "width": w, "height": h, "ref_spp": args.rmse_ref_spp, "all_spp": args.rmse_spp, "all_ms": round(med["all"], 3)}
+        for mode in ("one", "tree"):
+            spp_m = max(1, int(round(args.rmse_spp * med["all"] / med[mode])))
+            dev.set_light_sampling(mode)
+            dev.generateImg(spp_m, seed=args.seed)                        # (sizes the buffers for this count)
+            ms = []
+            for _ in range(args.frames):
+                st = M.Stats()
+                img = dev.generateImg(spp_m, seed=args.seed, stats=st)
+                ms.append(st.ms_total)
+            out.update({mode + "_spp": spp_m, mode + "_ms": round(statistics.median(ms), 3), mode + "_rmse": round(rmse(img), 6)})
+            img = dev.generateImg(args.rmse_spp, seed=args.seed)
+            out[mode + "_rmse_at_all_spp"] = round(rmse(img), 6)
+        dev.set_light_sampling(None)
+        full = dev.generateImg(args.rmse_spp, seed=args.seed)
+        out.update({"all_rmse": round(rmse(full), 6), "ref_mean": round(float(ref.mean()), 6)})
+        print(json.dumps(out), flush=True)
         dev.close()
         sc.close()
 
