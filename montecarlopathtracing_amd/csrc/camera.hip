@@ -40,8 +40,8 @@ __global__ void __launch_bounds__(256) k_camera_rays(DLens lens, unsigned long l
 
 // The megakernel with a lens: one lane per camera sample traces its own camera ray (reference-shaped walk) and shades the path from its
 // hit, as k_shade_samples does from the pixel's shared one.  Lane (slot, k) -> rad[(slot*spp + k)*3], flags[slot*spp + k].  ENV: an active
-// environment (a camera ray that misses gives Le of its direction).  ONE: the pick mode (1: MCPT_LIGHTS_ONE, 2: MCPT_LIGHTS_TREE).
-template <bool ENV, int ONE>
+// environment (a camera ray that misses gives Le of its direction).  PICK: the pick mode (1: MCPT_LIGHTS_ONE, 2: MCPT_LIGHTS_TREE).
+template <bool ENV, int PICK>
 __global__ void __launch_bounds__(256) k_shade_samples_lens(DScene S, DLens lens, unsigned long long seed, const int32_t* __restrict__ pixels,
                                                             int first_slot, long long n_samples, int spp, int sample_base, double* __restrict__ rad,
                                                             uint8_t* __restrict__ flags, DCounters* ctr)
@@ -60,7 +60,7 @@ __global__ void __launch_bounds__(256) k_shade_samples_lens(DScene S, DLens lens
         double out[3] = {0, 0, 0};
         if (ok) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix; key.sample = (uint32_t)k;
-            shade_path<ENV, ONE>(S, key, r.d, h, out, ls);
+            shade_path<ENV, PICK>(S, key, r.d, h, out, ls);
         } else if (ENV) env_camera_miss(S, r.d, out);
         rad[gid * 3] = out[0]; rad[gid * 3 + 1] = out[1]; rad[gid * 3 + 2] = out[2];
         flags[gid] = ok ? 1 : 0;
@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(256) k_shade_samples_lens(DScene S, DLens lens
 }
 
 // mcpt_sample_radiance with a lens: arbitrary (pixel, k) pairs
-template <bool ENV, int ONE>
+template <bool ENV, int PICK>
 __global__ void __launch_bounds__(256) k_sample_radiance_lens(DScene S, DLens lens, unsigned long long seed, const int32_t* __restrict__ pix,
                                                               const int32_t* __restrict__ ks, long long n, double* __restrict__ rgb, DCounters* ctr)
 {
@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(256) k_sample_radiance_lens(DScene S, DLens le
         ls.primary = 1; ls.samples = 1;
         if (trace_closest(S, r, h, w)) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix[gid]; key.sample = (uint32_t)ks[gid];
-            shade_path<ENV, ONE>(S, key, r.d, h, out, ls);
+            shade_path<ENV, PICK>(S, key, r.d, h, out, ls);
         } else if (ENV) env_camera_miss(S, r.d, out);
         ls.nodes += w.nodes; ls.tris += w.tris;
         rgb[gid * 3] = out[0]; rgb[gid * 3 + 1] = out[1]; rgb[gid * 3 + 2] = out[2];
@@ -225,28 +225,18 @@ void launch_shade_samples_lens(const DScene& S, const DLens& lens, unsigned long
     const long long n = (long long)n_slots * spp;
     if (n <= 0) return;
     const dim3 grid(blocks_of(n, 256));
-#define MCPT_SHADE_LENS(ENV, PICK) hipLaunchKernelGGL((k_shade_samples_lens<ENV, PICK>), grid, dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad, d_flags, ctr)
-    const bool env = env_on(S.env);
-    switch (pick_mode(S.pick)) {
-    case 2: if (env) MCPT_SHADE_LENS(true, 2); else MCPT_SHADE_LENS(false, 2); break;
-    case 1: if (env) MCPT_SHADE_LENS(true, 1); else MCPT_SHADE_LENS(false, 1); break;
-    default: if (env) MCPT_SHADE_LENS(true, 0); else MCPT_SHADE_LENS(false, 0);
-    }
-#undef MCPT_SHADE_LENS
+    with_path_variant(S, [&](auto env, auto pick) {
+        hipLaunchKernelGGL((k_shade_samples_lens<env(), pick()>), grid, dim3(256), 0, st, S, lens, seed, d_pixels, first_slot, n, spp, sample_base, d_rad, d_flags, ctr);
+    });
 }
 void launch_sample_radiance_lens(const DScene& S, const DLens& lens, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, long long n,
                                  double* d_rgb, DCounters* ctr, hipStream_t st)
 {
     if (n <= 0) return;
     const dim3 grid(blocks_of(n, 256));
-#define MCPT_RADIANCE_LENS(ENV, PICK) hipLaunchKernelGGL((k_sample_radiance_lens<ENV, PICK>), grid, dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr)
-    const bool env = env_on(S.env);
-    switch (pick_mode(S.pick)) {
-    case 2: if (env) MCPT_RADIANCE_LENS(true, 2); else MCPT_RADIANCE_LENS(false, 2); break;
-    case 1: if (env) MCPT_RADIANCE_LENS(true, 1); else MCPT_RADIANCE_LENS(false, 1); break;
-    default: if (env) MCPT_RADIANCE_LENS(true, 0); else MCPT_RADIANCE_LENS(false, 0);
-    }
-#undef MCPT_RADIANCE_LENS
+    with_path_variant(S, [&](auto env, auto pick) {
+        hipLaunchKernelGGL((k_sample_radiance_lens<env(), pick()>), grid, dim3(256), 0, st, S, lens, seed, d_pix, d_k, n, d_rgb, ctr);
+    });
 }
 void launch_camera_pass(const DLens& lens, const WfArgs& a, long long n_samples, hipStream_t st)
 {

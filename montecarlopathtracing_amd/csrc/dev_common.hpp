@@ -19,6 +19,7 @@ __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return mk(a.x + b.x, a.y +
 __device__ __forceinline__ V3 operator-(V3 a, V3 b) { return mk(a.x - b.x, a.y - b.y, a.z - b.z); }
 __device__ __forceinline__ V3 operator*(V3 a, double t) { return mk(a.x * t, a.y * t, a.z * t); }
 __device__ __forceinline__ V3 operator/(V3 a, double m) { return mk(a.x / m, a.y / m, a.z / m); }
+__device__ __forceinline__ V3 mul(V3 a, V3 b) { return mk(a.x * b.x, a.y * b.y, a.z * b.z); }      // component-wise (a throughput times a colour)
 __device__ __forceinline__ V3 neg(V3 a) { return mk(-a.x, -a.y, -a.z); }
 __device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 // Vertex::cross, sceneManagement.h:68-74

@@ -89,7 +89,7 @@ __device__ __forceinline__ V3 env_escape(const DEnv& E, const V3& L, const V3& T
 {
     if ((type & 7) == RT_DIFFUSE) return L;
     const V3 le = env_eval(E, d);
-    return L + mk(Tn.x * le.x, Tn.y * le.y, Tn.z * le.z);
+    return L + mul(Tn, le);
 }
 
 }  // namespace mcpt

@@ -179,8 +179,8 @@ __global__ void __launch_bounds__(256) k_primary_hits_reference(DScene S, const 
 // One lane per camera sample.  Samples of one pixel are consecutive lanes, so a wave starts from one shared
 // primary hit (coherent first vertex and shadow rays).  Radiance goes to rad[(slot*spp + k)*3]; lane k of a slot renders camera
 // sample sample_base + k (a whole frame: 0).  ENV: S.env is active (a pixel whose primary ray missed is folded from Le, not from rad).
-// ONE: the pick mode of S.pick, 0 (none), 1 (MCPT_LIGHTS_ONE) or 2 (MCPT_LIGHTS_TREE): shade_path.hpp.
-template <bool ENV, int ONE>
+// PICK: the pick mode of S.pick, 0 (none), 1 (MCPT_LIGHTS_ONE) or 2 (MCPT_LIGHTS_TREE): shade_path.hpp.
+template <bool ENV, int PICK>
 __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long long seed, const double* __restrict__ dirs,
                                                        const int32_t* __restrict__ pixels, const PrimaryHit* __restrict__ hits,
                                                        int first_slot, long long n_samples, int spp, int sample_base, double* __restrict__ rad, DCounters* ctr)
@@ -197,7 +197,7 @@ __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long l
         if (ph.leaf >= 0) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix; key.sample = (uint32_t)(sample_base + k);
             Hit h; h.leaf = ph.leaf; h.t = ph.t; h.p = mk(ph.p[0], ph.p[1], ph.p[2]);
-            shade_path<ENV, ONE>(S, key, ld3(dirs + (size_t)pix * 3), h, r, ls);
+            shade_path<ENV, PICK>(S, key, ld3(dirs + (size_t)pix * 3), h, r, ls);
         }
         rad[gid * 3] = r[0]; rad[gid * 3 + 1] = r[1]; rad[gid * 3 + 2] = r[2];
     }
@@ -205,7 +205,7 @@ __global__ void __launch_bounds__(256) k_shade_samples(DScene S, unsigned long l
 }
 
 // mcpt_sample_radiance: arbitrary (pixel, k) pairs, primary ray traced per sample.
-template <bool ENV, int ONE>
+template <bool ENV, int PICK>
 __global__ void __launch_bounds__(256) k_sample_radiance(DScene S, unsigned long long seed, const double* __restrict__ dirs,
                                                          const int32_t* __restrict__ pix, const int32_t* __restrict__ ks, long long n,
                                                          double* __restrict__ rgb, DCounters* ctr)
@@ -219,7 +219,7 @@ __global__ void __launch_bounds__(256) k_sample_radiance(DScene S, unsigned long
         ls.primary = 1; ls.samples = 1;
         if (trace_closest(S, r, h, w)) {
             RngKey key; key.k0 = (uint32_t)seed; key.k1 = (uint32_t)(seed >> 32); key.pixel = (uint32_t)pix[gid]; key.sample = (uint32_t)ks[gid];
-            shade_path<ENV, ONE>(S, key, r.d, h, out, ls);
+            shade_path<ENV, PICK>(S, key, r.d, h, out, ls);
         } else if (ENV) env_camera_miss(S, r.d, out);
         ls.nodes += w.nodes; ls.tris += w.tris;
         rgb[gid * 3] = out[0]; rgb[gid * 3 + 1] = out[1]; rgb[gid * 3 + 2] = out[2];
@@ -590,28 +590,18 @@ void launch_shade_samples(const DScene& S, unsigned long long seed, const double
     const long long n = (long long)n_slots * spp;
     if (n <= 0) return;
     const dim3 grid(blocks_for(n, 256));
-#define MCPT_SHADE(ENV, PICK) hipLaunchKernelGGL((k_shade_samples<ENV, PICK>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr)
-    const bool env = env_on(S.env);
-    switch (pick_mode(S.pick)) {
-    case 2: if (env) MCPT_SHADE(true, 2); else MCPT_SHADE(false, 2); break;
-    case 1: if (env) MCPT_SHADE(true, 1); else MCPT_SHADE(false, 1); break;
-    default: if (env) MCPT_SHADE(true, 0); else MCPT_SHADE(false, 0);
-    }
-#undef MCPT_SHADE
+    with_path_variant(S, [&](auto env, auto pick) {
+        hipLaunchKernelGGL((k_shade_samples<env(), pick()>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pixels, d_hits, first_slot, n, spp, sample_base, d_rad, ctr);
+    });
 }
 void launch_sample_radiance(const DScene& S, unsigned long long seed, const double* d_dirs, const int32_t* d_pix, const int32_t* d_k,
                             long long n, double* d_rgb, DCounters* ctr, hipStream_t st)
 {
     if (n <= 0) return;
     const dim3 grid(blocks_for(n, 256));
-#define MCPT_RADIANCE(ENV, PICK) hipLaunchKernelGGL((k_sample_radiance<ENV, PICK>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr)
-    const bool env = env_on(S.env);
-    switch (pick_mode(S.pick)) {
-    case 2: if (env) MCPT_RADIANCE(true, 2); else MCPT_RADIANCE(false, 2); break;
-    case 1: if (env) MCPT_RADIANCE(true, 1); else MCPT_RADIANCE(false, 1); break;
-    default: if (env) MCPT_RADIANCE(true, 0); else MCPT_RADIANCE(false, 0);
-    }
-#undef MCPT_RADIANCE
+    with_path_variant(S, [&](auto env, auto pick) {
+        hipLaunchKernelGGL((k_sample_radiance<env(), pick()>), grid, dim3(256), 0, st, S, seed, d_dirs, d_pix, d_k, n, d_rgb, ctr);
+    });
 }
 void launch_light_pick(const DScene& S, unsigned long long seed, const int32_t* d_pix, const int32_t* d_k, int depth, long long n, int32_t* d_light, hipStream_t st)
 {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include "device_scene.hpp"
+#include "path_variant.hpp"
 
 namespace mcpt {
 
@@ -21,14 +22,11 @@ struct TraceQueue;
 // several GPUs from several threads.
 struct LaunchCfg {
     int cus = 0;
-    unsigned logic_first = 0, logic_rest = 0;       // k_wf_logic<true> / <false>
-    int trace_grid = 0, trace_grid_short = 0, finish_grid = 0;   // k_wf_trace (deep / short stack), k_wf_finish
-    unsigned logic_first_env = 0, logic_rest_env = 0;   // ... their instantiations under an environment (fewer waves may be resident)
-    int finish_grid_env = 0;
-    unsigned logic_first_one[2] = {0, 0}, logic_rest_one[2] = {0, 0};   // ... under MCPT_LIGHTS_ONE ([1]: and an environment)
-    int finish_grid_one[2] = {0, 0};
-    unsigned logic_first_tree[2] = {0, 0}, logic_rest_tree[2] = {0, 0};   // ... under MCPT_LIGHTS_TREE
-    int finish_grid_tree[2] = {0, 0};
+    // k_wf_logic<true> / <false> and k_wf_finish, one entry per path variant (path_variant.hpp: variant_index(env, pick)) -- every
+    // instantiation has its own occupancy, so fewer waves of one may be resident than of another
+    unsigned logic_first[kPathVariants] = {}, logic_rest[kPathVariants] = {};
+    int finish_grid[kPathVariants] = {};
+    int trace_grid = 0, trace_grid_short = 0;       // k_wf_trace (deep / short stack)
     int array_grid = 0, primary_grid = 0;           // k_trace_persistent<ArrayRaySource> / <PrimaryRaySource>, deep stack
     int array_grid_short = 0, primary_grid_short = 0;   // ... short stack
     long long trace_block_rays = 2048;              // MCPT_TRACE_BLOCK_RAYS: a block of k_wf_trace is started per this many rays

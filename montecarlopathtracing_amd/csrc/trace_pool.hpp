@@ -604,9 +604,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 // (vertex.hpp), operation for operation; a path's record lives in this block's part of a global area, [field][path slot][lane].
                 const WfArgs& a = pp.a;
                 const int nl = pp.nl;
-                const int nplanes = PP::kEnv ? nl - 1 : nl;              // (nl: shadow planes; an environment's is the last, these are the lights')
-                const int nlights = PP::kOne ? S.num_lights : nplanes;   // the Philox block base (MCPT_LIGHTS_ONE: one plane for the picked light)
-                const bool folded = nl == 1;                             // see k_wf_logic
+                const auto [nplanes, nlights, folded] = path_lights<PP::kEnv, PP::kPick>(S, nl);
                 const long long cap = a.cap;
                 const int s0 = k * R;
                 const size_t plane = (size_t)pp.npc * 64;
@@ -632,18 +630,15 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                         const int expect = ri[(size_t)(RI_EXPECT + l) * plane];
                         if (expect == -2) continue;
                         const V3 cc = ldp(RD_C + 3 * l);
-                        const bool vis = L.cur[(s0 + l) * 64 + lane] == expect;
-                        L_dir.x += vis ? cc.x : cc.x * 0.0;
-                        L_dir.y += vis ? cc.y : cc.y * 0.0;
-                        L_dir.z += vis ? cc.z : cc.z * 0.0;
+                        add_if_visible(L_dir, cc, L.cur[(s0 + l) * 64 + lane] == expect);
                     }
                     if (mode == P_ADOPTED && folded) Lr = Lr + L_dir;            // its c was stored as T * c
-                    else Lr = Lr + mk(T.x * L_dir.x, T.y * L_dir.y, T.z * L_dir.z);
+                    else Lr = Lr + mul(T, L_dir);
                     const int bidx = (s0 + nl) * 64 + lane;
                     const int hl = bt >= 0 ? L.best_leaf[bidx] : -1;
                     if (hl >= 0) {
                         // an adopted path with one light already holds the throughput after its bounce
-                        if (!(mode == P_ADOPTED && folded)) { const V3 wgt = ldp(RD_W); T = mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR); }
+                        if (!(mode == P_ADOPTED && folded)) T = after_bounce(T, ldp(RD_W));
                         // the hit point: the first two lines of the reference's triangle test on the ray that is still in its slot
                         const PoolOxy b0 = pool_ld16(&L.oxy[bidx]); const PoolOzDx b1 = pool_ld16(&L.ozdx[bidx]); const PoolDyz b2 = pool_ld16(&L.dyz[bidx]);
                         const V3 ro = mk(b0.ox, b0.oy, b1.oz), bd = mk(b1.dx, b2.dy, b2.dz);
@@ -653,7 +648,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                         p = ro + bd * t; dir = neg(bd); in_type = bt & 7; depth++; leaf = hl;
                         at_vertex = true;
                     } else if (PP::kEnv && bt >= 0) {                       // the bounce ray left the scene
-                        const V3 Tn = (mode == P_ADOPTED && folded) ? T : [&] { const V3 wgt = ldp(RD_W); return mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR); }();
+                        const V3 Tn = (mode == P_ADOPTED && folded) ? T : after_bounce(T, ldp(RD_W));
                         const PoolOzDx b1 = pool_ld16(&L.ozdx[bidx]); const PoolDyz b2 = pool_ld16(&L.dyz[bidx]);
                         Lr = env_escape(S.env, Lr, Tn, bt, mk(b1.dx, b2.dy, b2.dz));
                     }
@@ -669,7 +664,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                     if (m->light >= 0) {
                         const V3 rad = ld3(S.lights[m->light].radiance);
                         if (depth == 0) Lr = rad;
-                        else if (in_type != RT_DIFFUSE) Lr = Lr + mk(T.x * rad.x, T.y * rad.y, T.z * rad.z);
+                        else if (in_type != RT_DIFFUSE) Lr = Lr + mul(T, rad);
                         ended = true; at_vertex = false;
                     } else vertex_surface(S, leaf, p, m, pn, kd);
                 }
@@ -692,14 +687,11 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 };
                 int n_shadow = 0, n_skipped = 0, n_bounce = 0;
                 if (at_vertex) {
-                    RngKey key;
-                    key.k0 = (uint32_t)a.seed; key.k1 = (uint32_t)(a.seed >> 32);
-                    const int slot = a.first_slot + id / a.spp;
-                    key.pixel = (uint32_t)(a.pixels ? a.pixels[slot] : slot); key.sample = (uint32_t)(a.sample_base + id % a.spp);
+                    const RngKey key = sample_key(a, id);
                     int sample_mat = -1;
                     for (int l = 0; l < nplanes; l++) {
                         V3 direction, cc;
-                        const int expect = PP::kOne ? light_sample_one<PP::kOne>(S, key, depth, p, pn, kd, direction, cc) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, cc);
+                        const int expect = PP::kPick ? light_sample_one<PP::kPick>(S, key, depth, p, pn, kd, direction, cc) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, cc);
                         ri[(size_t)(RI_EXPECT + l) * plane] = expect;
                         if (expect != -2) { stp(RD_C + 3 * l, cc); emit(s0 + l, p + direction * 0.01, direction); n_shadow++; }
                         else n_skipped++;

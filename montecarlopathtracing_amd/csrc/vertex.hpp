@@ -1,12 +1,55 @@
-// The three pieces of shade() a path vertex is made of (MTPC/pathTracing.cpp:137-266), in the form the wavefront kernels use
-// them: what the surface looks like at the hit, one light sample, and Russian roulette + nextRay.  Same arithmetic, operation
-// for operation, as shade_path_from() (shade_path.hpp); tests compare the two pipelines bit for bit.
+// The three pieces of shade() a path vertex is made of (MTPC/pathTracing.cpp:137-266): what the surface looks like at the hit, one
+// light sample, and Russian roulette + nextRay -- and the few expressions that join them into a path.  The megakernel (shade_path.hpp),
+// the logic and finishing kernels (wavefront_logic.hip) and the pool engine's path mode (trace_pool.hpp) all shade with these, each in
+// its own order and with its own way of tracing the rays.  One copy remains: shade_path's loop over every light spells light_sample out
+// (it says why); tests hold the two equal bit for bit.
 #pragma once
 #include "dev_common.hpp"
 #include "shade_common.hpp"
 #include "light_tree.hpp"
+#include "wavefront.hpp"
 
 namespace mcpt {
+
+// ---- what joins the pieces
+// the throughput after a bounce of weight wgt that survived Russian roulette: T * wgt / P_RR
+__device__ __forceinline__ V3 after_bounce(const V3& T, const V3& wgt)
+{
+    return mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR);
+}
+// L_dir += visibility * c as the reference forms it: a hidden light adds c * 0.0 (a zero of c's sign, NaN for an infinite c), not nothing
+__device__ __forceinline__ void add_if_visible(V3& L_dir, const V3& c, bool vis)
+{
+    L_dir.x += vis ? c.x : c.x * 0.0;
+    L_dir.y += vis ? c.y : c.y * 0.0;
+    L_dir.z += vis ? c.z : c.z * 0.0;
+}
+// What a vertex's light samples are counted in, from nl = the shadow rays (planes) of a vertex: nplanes of them are the lights' -- ENV: an
+// active environment has the last plane, PICK (1: MCPT_LIGHTS_ONE, 2: MCPT_LIGHTS_TREE): the lights share one plane, for the picked light;
+// nlights = the Philox block base (dev_common.hpp), the scene's lights whatever nl says; folded: with one plane T * c and T * w / P_RR are
+// formed when the vertex is shaded instead of when it is resolved (k_wf_logic).
+struct PathLights { int nplanes, nlights; bool folded; };
+template <bool ENV, int PICK>
+__device__ __forceinline__ PathLights path_lights(const DScene& S, int nl)
+{
+    const int nplanes = ENV ? nl - 1 : nl;
+    return {nplanes, PICK ? S.num_lights : nplanes, nl == 1};
+}
+// The RNG key of chunk-local sample id of a wavefront pass (WfState::id): its camera sample from the pass's base, its pixel through
+// the slot list -- or given, where the caller has it at hand (the first logic pass: the pixel's record).
+__device__ __forceinline__ RngKey sample_key(const WfArgs& a, int id, int pixel)
+{
+    RngKey key;
+    key.k0 = (uint32_t)a.seed; key.k1 = (uint32_t)(a.seed >> 32);
+    key.pixel = (uint32_t)pixel;
+    key.sample = (uint32_t)(a.sample_base + id % a.spp);
+    return key;
+}
+__device__ __forceinline__ RngKey sample_key(const WfArgs& a, int id)
+{
+    const int slot = a.first_slot + id / a.spp;
+    return sample_key(a, id, a.pixels ? a.pixels[slot] : slot);
+}
 
 // interpolated normal and diffuse colour at p on leaf `leaf` (:147-160, texture lookup Q9 / D7)
 __device__ __forceinline__ void vertex_surface(const DScene& S, int leaf, const V3& p, const DMaterial* m, V3& pn, V3& kd)
@@ -93,14 +136,14 @@ __device__ __forceinline__ int light_pick_at(const DLightPick& P, const RngKey& 
     return ~l;
 }
 
-// MCPT_LIGHTS_ONE (MODE 1) and MCPT_LIGHTS_TREE (MODE 2): the one light sample of the vertex -- light_sample of the picked light (its own
+// MCPT_LIGHTS_ONE (PICK 1) and MCPT_LIGHTS_TREE (PICK 2): the one light sample of the vertex -- light_sample of the picked light (its own
 // Philox block, no light before it to inherit a material from), c scaled by 1 / p_l.  Returns as light_sample does.
-template <int MODE>
+template <int PICK>
 __device__ __forceinline__ int light_sample_one(const DScene& S, const RngKey& key, uint32_t depth, const V3& p, const V3& pn, const V3& kd, V3& direction, V3& c)
 {
     double inv_p;
     int l;
-    if constexpr (MODE == 2) {
+    if constexpr (PICK == 2) {
         double pdf;
         l = light_pick_at(S.pick, key, depth, (uint32_t)S.num_lights, p, pn, pdf);
         inv_p = 1.0 / pdf;

@@ -120,7 +120,7 @@ void launch_wf_finish(const DScene& S, const WfArgs& a, long long n_upper, hipSt
                       unsigned int slow_cap);
 size_t finish_pool_bytes(int cus, int nl);
 int persistent_grid(const void* kernel, int cus);   // blocks of 256 threads of `kernel` resident on the current device
-void init_launch_cfg_logic(LaunchCfg& cfg, unsigned forced_grid);   // wavefront_logic.hip: logic_first / logic_rest / finish_grid of cfg
+void init_launch_cfg_logic(LaunchCfg& cfg, unsigned forced_grid);   // wavefront_logic.hip: logic_first / logic_rest / finish_grid of cfg, for every path variant
 long long persistent_chunk(long long total, int grid_blocks);
 
 void launch_primary_surface(const DScene& S, const WfArgs& a, PrimarySurface* surf, unsigned int* alive_count, unsigned int* alive_total, int n_slots_upper,

@@ -53,17 +53,14 @@ __device__ __forceinline__ void sstc(double* __restrict__ a, long long cap, long
 // evaluation is free): L, p and the sample id are stored before anything is computed, the incoming direction dies with
 // bounce_sample -- the later passes' values that are alive at the same time, and with them the registers the compiler had to
 // park in scratch memory (39 at 4 waves per SIMD), are what this order is about.  ENV: an active environment, shadow plane nl - 1 after
-// the scene's nl - 1 lights (WfArgs::nl counts planes; the Philox block base is the lights' count).  ONE: the pick mode of S.pick (1: MCPT_LIGHTS_ONE, 2: MCPT_LIGHTS_TREE) --
-// the lights have one plane, plane 0, for the light vertex.hpp's light_pick draws; the block base is S.num_lights, whatever nl says.
-template <bool FIRST, bool ENV, int ONE>
+// the scene's nl - 1 lights (WfArgs::nl counts planes; the Philox block base is the lights' count).  PICK: the pick mode of S.pick (1: MCPT_LIGHTS_ONE, 2: MCPT_LIGHTS_TREE) --
+// the lights have one plane, plane 0, for the light vertex.hpp's light_pick draws; the block base is S.num_lights, whatever nl says (path_lights).
+template <bool FIRST, bool ENV, int PICK>
 __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a, long long j, int id, int leaf, const V3& p, const V3& dir, const V3& T, const V3& L,
                                                 int mat_first, int pix_first, const V3& pn_first, const V3& kd_first, LaneStats& ls)
 {
     const long long cap = a.cap;
-    const int nl = a.nl;
-    const int nplanes = ENV ? nl - 1 : nl;                                     // the lights' shadow planes
-    const int nlights = ONE ? S.num_lights : nplanes;
-    const bool folded = nl == 1;
+    const auto [nplanes, nlights, folded] = path_lights<ENV, PICK>(S, a.nl);
     const uint32_t depth = (uint32_t)a.depth;
     sst(a.out.id + j, id);
     if (!FIRST) { sstc(a.out.L, cap, j, L); sstc(a.out.p, cap, j, p); }       // first pass: L = 0; p is the pixel's primary hit (a.hits)
@@ -71,27 +68,23 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
     V3 pn = pn_first, kd = kd_first;
     if (!FIRST) vertex_surface(S, leaf, p, m, pn, kd);
 
-    RngKey key;
-    key.k0 = (uint32_t)a.seed; key.k1 = (uint32_t)(a.seed >> 32);
-    if (FIRST) key.pixel = (uint32_t)pix_first;
-    else { const int slot = a.first_slot + id / a.spp; key.pixel = (uint32_t)(a.pixels ? a.pixels[slot] : slot); }
-    key.sample = (uint32_t)(a.sample_base + id % a.spp);
+    const RngKey key = FIRST ? sample_key(a, id, pix_first) : sample_key(a, id);
 
     {
         V3 nd = mk(0, 0, 0), wgt = mk(1, 1, 1);
         const int btype = bounce_sample(key, depth, nlights, m, dir, pn, kd, nd, wgt);
         if (btype >= 0) { sstc(a.out.bdir, cap, j, nd); ls.bounce++; }
         sst(a.out.btype + j, btype);
-        if (folded) sstc(a.out.T, cap, j, mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR));
+        if (folded) sstc(a.out.T, cap, j, after_bounce(T, wgt));
         else { sstc(a.out.w, cap, j, wgt); if (!FIRST) sstc(a.out.T, cap, j, T); }
     }
 
     int sample_mat = -1;
     for (int l = 0; l < nplanes; l++) {
         V3 direction, c;
-        const int expect = ONE ? light_sample_one<ONE>(S, key, depth, p, pn, kd, direction, c) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, c);
+        const int expect = PICK ? light_sample_one<PICK>(S, key, depth, p, pn, kd, direction, c) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, direction, c);
         if (expect != -2) {
-            sstc(a.out.c + (long long)l * 3 * cap, cap, j, folded ? mk(T.x * c.x, T.y * c.y, T.z * c.z) : c);
+            sstc(a.out.c + (long long)l * 3 * cap, cap, j, folded ? mul(T, c) : c);
             sstc(a.rays.d + (long long)l * 3 * cap, cap, j, direction);       // origin p + direction * 0.01: WfRaySource
             ls.shadow++;
         } else ls.skipped++;
@@ -101,7 +94,7 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
         V3 direction, c;
         const int expect = env_light_sample(S.env, key, depth, (uint32_t)nlights, pn, kd, direction, c);
         if (expect != -2) {
-            sstc(a.out.c + (long long)nplanes * 3 * cap, cap, j, folded ? mk(T.x * c.x, T.y * c.y, T.z * c.z) : c);
+            sstc(a.out.c + (long long)nplanes * 3 * cap, cap, j, folded ? mul(T, c) : c);
             sstc(a.rays.d + (long long)nplanes * 3 * cap, cap, j, direction);
             ls.shadow++;
         }
@@ -129,8 +122,8 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
 // before: no slot is overwritten while it is read.
 //
 // ENV: an active environment (wf_shade_vertex's last shadow plane; a bounce ray that left the scene adds T' * Le, a camera ray Le).
-// ONE: the pick mode, 1 (MCPT_LIGHTS_ONE) or 2 (MCPT_LIGHTS_TREE) (wf_shade_vertex; the resolve sees planes only and is the same code).
-template <bool FIRST, bool ENV, int ONE>
+// PICK: the pick mode, 1 (MCPT_LIGHTS_ONE) or 2 (MCPT_LIGHTS_TREE) (wf_shade_vertex; the resolve sees planes only and is the same code).
+template <bool FIRST, bool ENV, int PICK>
 __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOGIC_WAVES) k_wf_logic(DScene S, WfArgs a)
 {
     const long long n_prev = (long long)a.counts_in->n_next * a.count_mul;
@@ -187,7 +180,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 continue;
             }
             MCPT_LSTAMP(0)
-            wf_shade_vertex<true, ENV, ONE>(S, a, j, id, leaf, p, dir, mk(1, 1, 1), mk(0, 0, 0), mat_first, pix_first, pn_first, kd_first, ls);
+            wf_shade_vertex<true, ENV, PICK>(S, a, j, id, leaf, p, dir, mk(1, 1, 1), mk(0, 0, 0), mat_first, pix_first, pn_first, kd_first, ls);
             MCPT_LSTAMP(2)
         }
     } else {
@@ -229,10 +222,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                         const int hm = sld(a.in.hit_mat + ((long long)l * cap + i));
                         const V3 c = sldc(a.in.c + (long long)l * 3 * cap, cap, i);
                         if (expect == -2) continue;
-                        const bool vis = hm == expect;
-                        L_dir[u].x += vis ? c.x : c.x * 0.0;
-                        L_dir[u].y += vis ? c.y : c.y * 0.0;
-                        L_dir[u].z += vis ? c.z : c.z * 0.0;
+                        add_if_visible(L_dir[u], c, hm == expect);
                     }
                 }
 #pragma unroll
@@ -242,8 +232,8 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                         const bool have_vertex = bt[u] >= 0 && hl[u] >= 0;
                         if (folded) L[u] = L[u] + L_dir[u];
                         else {
-                            L[u] = L[u] + mk(T[u].x * L_dir[u].x, T[u].y * L_dir[u].y, T[u].z * L_dir[u].z);
-                            if (have_vertex) T[u] = mk(T[u].x * wgt[u].x * MCPT_INV_P_RR, T[u].y * wgt[u].y * MCPT_INV_P_RR, T[u].z * wgt[u].z * MCPT_INV_P_RR);
+                            L[u] = L[u] + mul(T[u], L_dir[u]);
+                            if (have_vertex) T[u] = after_bounce(T[u], wgt[u]);
                         }
                         if (have_vertex) {
                             ls.shades++;
@@ -255,7 +245,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                                     const DMaterial* m = S.materials + S.tris[hl[u] & MCPT_HIT_LEAF_MASK].material;
                                     if (folded) T[u] = sldc(a.in.T, cap, pos[u]);
                                     const V3 rad = ld3(S.lights[m->light].radiance);
-                                    L[u] = L[u] + mk(T[u].x * rad.x, T[u].y * rad.y, T[u].z * rad.z);
+                                    L[u] = L[u] + mul(T[u], rad);
                                 }
                             } else alive[u] = true;
                         }
@@ -263,8 +253,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                             const V3 bd = sldc(a.in.bdir, cap, pos[u]);
                             if (depth == 0) L[u] = env_eval(S.env, bd);                 // a camera ray (per-sample route): unweighted
                             else {
-                                const V3 Tn = folded ? sldc(a.in.T, cap, pos[u])
-                                                     : mk(T[u].x * wgt[u].x * MCPT_INV_P_RR, T[u].y * wgt[u].y * MCPT_INV_P_RR, T[u].z * wgt[u].z * MCPT_INV_P_RR);
+                                const V3 Tn = folded ? sldc(a.in.T, cap, pos[u]) : after_bounce(T[u], wgt[u]);
                                 L[u] = env_escape(S.env, L[u], Tn, bt[u], bd);
                             }
                         }
@@ -317,7 +306,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 const int bt = sld(a.in.btype + i);
                 V3 T = mk(1, 1, 1);
                 if (depth > 1 || (folded && depth > 0)) T = sldc(a.in.T, cap, i);      // (depth 0, the per-sample route: a camera ray, T = 1)
-                if (!folded && depth > 0) { const V3 wgt = sldc(a.in.w, cap, i); T = mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR); }
+                if (!folded && depth > 0) T = after_bounce(T, sldc(a.in.w, cap, i));
                 const V3 bd = sldc(a.in.bdir, cap, i);
                 // the vertex the bounce ray left from: the pixel's primary hit after the first pass, in.p afterwards (and always in the
                 // per-sample route of a lens, hits == null: depth 0 resolves the camera rays, left from the lens points in in.p)
@@ -331,7 +320,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 const V3 v1 = ld3(tr->v1), n = ld3(tr->n);
                 const double t = dot(v1 - ro, n) / dot(n, bd);
                 const V3 p = ro + bd * t;
-                wf_shade_vertex<false, ENV, ONE>(S, a, j, id, leaf, p, neg(bd), T, L, 0, 0, mk(0, 0, 0), mk(0, 0, 0), ls);
+                wf_shade_vertex<false, ENV, PICK>(S, a, j, id, leaf, p, neg(bd), T, L, 0, 0, mk(0, 0, 0), mk(0, 0, 0), ls);
             }
             head = (head + m_round) & (kRing - 1u);
             count -= m_round;
@@ -351,8 +340,8 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
 // resolve, trace the bounce ray, shade the next vertex (vertex.hpp: the arithmetic of k_wf_logic).  Lanes whose path has ended
 // take the next unclaimed path (one atomic per refill on the pass's own count slot), so a wave is as long as its share of
 // the work, not as its longest path.  A lane that has just adopted a path finds the rays of its first step in the wavefront
-// state instead of computing them; from the second step on everything lives in registers.  ENV, ONE: as k_wf_logic.
-template <bool ENV, int ONE>
+// state instead of computing them; from the second step on everything lives in registers.  ENV, PICK: as k_wf_logic.
+template <bool ENV, int PICK>
 __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, WfArgs a)
 {
     __shared__ int lds_stack[MCPT_FAST_STACK * 256];
@@ -360,9 +349,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
     if (n == 0 || n > (long long)a.finish_below) return;               // nothing left, or still wavefront work
     const long long cap = a.cap;
     const int nl = a.nl;
-    const int nplanes = ENV ? nl - 1 : nl;                             // (nl: shadow planes; these are the lights')
-    const int nlights = ONE ? S.num_lights : nplanes;                  // the Philox block base
-    const bool folded = nl == 1;                                       // see k_wf_logic
+    const auto [nplanes, nlights, folded] = path_lights<ENV, PICK>(S, nl);
     const int lane = threadIdx.x & 63;
     const unsigned long long lt_mask = (1ull << lane) - 1ull;
     LaneStats ls;
@@ -402,8 +389,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
                 if (a.depth > 0 || folded) T = ldc(a.out.T, cap, j);
                 if (a.depth > 0) L = ldc(a.out.L, cap, j);
                 p = src.vertex(j);
-                const int slot = a.first_slot + id / a.spp;
-                key.pixel = (uint32_t)(a.pixels ? a.pixels[slot] : slot); key.sample = (uint32_t)(a.sample_base + id % a.spp);
+                key = sample_key(a, id);
             }
         }
         if (!__ballot(mode != M_IDLE)) {
@@ -422,7 +408,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
             if (m->light >= 0) {
                 const V3 rad = ld3(S.lights[m->light].radiance);
                 if (depth == 0) L = rad;
-                else if (in_type != RT_DIFFUSE) L = L + mk(T.x * rad.x, T.y * rad.y, T.z * rad.z);
+                else if (in_type != RT_DIFFUSE) L = L + mul(T, rad);
                 ended = true;
             } else vertex_surface(S, leaf, p, m, pn, kd);
         }
@@ -441,7 +427,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
                     expect = env_light_sample(S.env, key, depth, (uint32_t)nlights, pn, kd, r.d, c);
                     if (expect != -2) ls.shadow++;
                 } else {
-                    expect = ONE ? light_sample_one<ONE>(S, key, depth, p, pn, kd, r.d, c) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, r.d, c);
+                    expect = PICK ? light_sample_one<PICK>(S, key, depth, p, pn, kd, r.d, c) : light_sample(S, key, depth, l, p, pn, kd, sample_mat, r.d, c);
                     if (expect != -2) ls.shadow++; else ls.skipped++;
                 }
             } else if (mode == M_ADOPTED) {
@@ -453,10 +439,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
             if (expect != -2) {
                 Hit h;
                 const bool ok = trace_lane_fast(S, r, h, w, stack, 256);
-                const bool vis = (ok ? S.tris[h.leaf].material : -1) == expect;
-                L_dir.x += vis ? c.x : c.x * 0.0;
-                L_dir.y += vis ? c.y : c.y * 0.0;
-                L_dir.z += vis ? c.z : c.z * 0.0;
+                add_if_visible(L_dir, c, (ok ? S.tris[h.leaf].material : -1) == expect);
             }
         }
         int bt = -1;
@@ -498,12 +481,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
             if (kind >= 0) ok1 = trace_lane_fast(S, r1, h1, w, stack, 256);
             const int mat1 = (kind == 0 || kind == 2) ? (ok1 ? S.tris[h1.leaf].material : -1) : -1;
             const int mat_helped = __shfl(mat1, partner, 64);
-            if (have_s) {
-                const bool vis = (give ? mat_helped : mat1) == expect0;
-                L_dir.x += vis ? c0.x : c0.x * 0.0;
-                L_dir.y += vis ? c0.y : c0.y * 0.0;
-                L_dir.z += vis ? c0.z : c0.z * 0.0;
-            }
+            if (have_s) add_if_visible(L_dir, c0, (give ? mat_helped : mat1) == expect0);
             if (kind == 1) { b_ok = ok1; b_hit = h1; }
             const bool second = have_b && kind == 0;
             if (__ballot(second)) { if (second) b_ok = trace_lane_fast(S, br, b_hit, w, stack, 256); }
@@ -512,16 +490,16 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
         fin_t_trace += __builtin_amdgcn_s_memtime() - fin_ta;
 #endif
         if (mode == M_ADOPTED && folded) L = L + L_dir;                 // its c was stored as T * c
-        else L = L + mk(T.x * L_dir.x, T.y * L_dir.y, T.z * L_dir.z);
+        else L = L + mul(T, L_dir);
 
         bool goes_on = false;
         if (bt >= 0 && b_ok) {
             // an adopted path with one light already holds the throughput after its bounce
-            if (!(mode == M_ADOPTED && folded)) T = mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR);
+            if (!(mode == M_ADOPTED && folded)) T = after_bounce(T, wgt);
             leaf = b_hit.leaf; p = b_hit.p; dir = neg(br.d); in_type = bt & 7; depth++;
             goes_on = true;
         } else if (ENV && bt >= 0 && mode != M_IDLE) {                   // the bounce ray left the scene
-            const V3 Tn = (mode == M_ADOPTED && folded) ? T : mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR);
+            const V3 Tn = (mode == M_ADOPTED && folded) ? T : after_bounce(T, wgt);
             L = env_escape(S.env, L, Tn, bt, br.d);
         }
         if (mode != M_IDLE) {
@@ -548,11 +526,11 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
 #ifndef MCPT_POOL_NPC
 #define MCPT_POOL_NPC (MCPT_POOL_KT / 2)           /* path slots per lane the record planes are laid out for (one light: KT / 2 paths) */
 #endif
-template <bool ENV, int ONE>
+template <bool ENV, int PICK>
 struct WfPaths {
     static constexpr bool kPaths = true;
     static constexpr bool kEnv = ENV;           // an active environment: the last of the nl shadow planes (see k_wf_logic)
-    static constexpr int kOne = ONE;            // MCPT_LIGHTS_ONE (1) or MCPT_LIGHTS_TREE (2): the lights' one plane holds the picked light's sample
+    static constexpr int kPick = PICK;          // MCPT_LIGHTS_ONE (1) or MCPT_LIGHTS_TREE (2): the lights' one plane holds the picked light's sample
     WfArgs a;
     long long n;                // paths handed over (positions 0 .. n-1 of the wavefront state a.out)
     int nl, npc;
@@ -573,21 +551,21 @@ size_t finish_pool_bytes(int cus, int nl)
     return blocks * (size_t(9 + 3 * nl) * plane * sizeof(double) + size_t(3 + nl) * plane * sizeof(int) + size_t(MCPT_POOL_WAVES) * 64 * MCPT_FAST_STACK * sizeof(int));
 }
 
-template <int NW, int KT, int SCAP, bool ENV, int ONE>
+template <int NW, int KT, int SCAP, bool ENV, int PICK>
 __global__ void __launch_bounds__(NW * 64, 1) k_wf_finish_pool(DScene S, WfArgs a, char* area, int* spill)
 {
     const long long n = a.counts->n_next;
     if (n == 0 || n > (long long)a.finish_below) return;               // nothing left, or still wavefront work
     __shared__ PoolLds<NW, KT, SCAP> L;
     const size_t blocks = gridDim.x, plane = size_t(MCPT_POOL_NPC) * 64;
-    WfPaths<ENV, ONE> pp;
+    WfPaths<ENV, PICK> pp;
     pp.a = a; pp.n = n; pp.nl = a.nl; pp.npc = MCPT_POOL_NPC; pp.inv_r = 1.0f / (float)(a.nl + 1);
     pp.recd = reinterpret_cast<double*>(area);
     pp.reci = reinterpret_cast<int*>(pp.recd + blocks * size_t(9 + 3 * a.nl) * plane);
     pp.gstack = pp.reci + blocks * size_t(3 + a.nl) * plane;
     WfRaySource src; src.a = a; src.n_paths = n;                       // (path mode never fetches or stores through it)
     Work w = {0, 0};
-    trace_pool<WfRaySource, NW, KT, SCAP, WfPaths<ENV, ONE>>(S, src, nullptr, nullptr, 0u, 64, L, w, spill, pp);
+    trace_pool<WfRaySource, NW, KT, SCAP, WfPaths<ENV, PICK>>(S, src, nullptr, nullptr, 0u, 64, L, w, spill, pp);
     LaneStats ls;
     ls.nodes = w.nodes; ls.tris = w.tris;
     __syncthreads();
@@ -697,38 +675,13 @@ void launch_primary_surface(const DScene& S, const WfArgs& a, PrimarySurface* su
 void launch_wf_logic(const DScene& S, const WfArgs& a, long long n_upper, bool first, hipStream_t st, const LaunchCfg& cfg)
 {
     if (n_upper <= 0) return;
-    // small inputs get small grids (>= 1024 paths per block): every wave that starts costs a few atomics on shared counters
-    const bool env = env_on(S.env);
-    if (tree_on(S.pick)) {
-        const unsigned g = grid_for(n_upper, 1024, first ? cfg.logic_first_tree[env] : cfg.logic_rest_tree[env]);
-        if (first) {
-            if (env) hipLaunchKernelGGL((k_wf_logic<true, true, 2>), dim3(g), dim3(256), 0, st, S, a);
-            else hipLaunchKernelGGL((k_wf_logic<true, false, 2>), dim3(g), dim3(256), 0, st, S, a);
-        } else {
-            if (env) hipLaunchKernelGGL((k_wf_logic<false, true, 2>), dim3(g), dim3(256), 0, st, S, a);
-            else hipLaunchKernelGGL((k_wf_logic<false, false, 2>), dim3(g), dim3(256), 0, st, S, a);
-        }
-        return;
-    }
-    if (pick_on(S.pick)) {
-        const unsigned g = grid_for(n_upper, 1024, first ? cfg.logic_first_one[env] : cfg.logic_rest_one[env]);
-        if (first) {
-            if (env) hipLaunchKernelGGL((k_wf_logic<true, true, true>), dim3(g), dim3(256), 0, st, S, a);
-            else hipLaunchKernelGGL((k_wf_logic<true, false, true>), dim3(g), dim3(256), 0, st, S, a);
-        } else {
-            if (env) hipLaunchKernelGGL((k_wf_logic<false, true, true>), dim3(g), dim3(256), 0, st, S, a);
-            else hipLaunchKernelGGL((k_wf_logic<false, false, true>), dim3(g), dim3(256), 0, st, S, a);
-        }
-        return;
-    }
-    unsigned g = grid_for(n_upper, 1024, first ? (env ? cfg.logic_first_env : cfg.logic_first) : (env ? cfg.logic_rest_env : cfg.logic_rest));
-    if (first) {
-        if (env) hipLaunchKernelGGL((k_wf_logic<true, true, false>), dim3(g), dim3(256), 0, st, S, a);
-        else hipLaunchKernelGGL((k_wf_logic<true, false, false>), dim3(g), dim3(256), 0, st, S, a);
-    } else {
-        if (env) hipLaunchKernelGGL((k_wf_logic<false, true, false>), dim3(g), dim3(256), 0, st, S, a);
-        else hipLaunchKernelGGL((k_wf_logic<false, false, false>), dim3(g), dim3(256), 0, st, S, a);
-    }
+    with_path_variant(S, [&](auto env, auto pick) {
+        // small inputs get small grids (>= 1024 paths per block): every wave that starts costs a few atomics on shared counters
+        constexpr int v = variant_index(env(), pick());
+        const unsigned g = grid_for(n_upper, 1024, first ? cfg.logic_first[v] : cfg.logic_rest[v]);
+        if (first) hipLaunchKernelGGL((k_wf_logic<true, env(), pick()>), dim3(g), dim3(256), 0, st, S, a);
+        else hipLaunchKernelGGL((k_wf_logic<false, env(), pick()>), dim3(g), dim3(256), 0, st, S, a);
+    });
 }
 
 void launch_wf_finish(const DScene& S, const WfArgs& a, long long n_upper, hipStream_t st, const LaunchCfg& cfg, char* path_area, long long* slow_list,
@@ -741,29 +694,15 @@ void launch_wf_finish(const DScene& S, const WfArgs& a, long long n_upper, hipSt
         const long long nb = (n_upper + per_block - 1) / per_block;
         const int g = (int)(nb < cfg.cus ? nb : cfg.cus);
         int* const spill = reinterpret_cast<int*>(slow_list + slow_cap);
-        const dim3 block(MCPT_POOL_WAVES * 64);
-        if (tree_on(S.pick)) {
-            if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, true, 2>), dim3(g), block, 0, st, S, a, path_area, spill);
-            else hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, false, 2>), dim3(g), block, 0, st, S, a, path_area, spill);
-        } else if (pick_on(S.pick)) {
-            if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, true, true>), dim3(g), block, 0, st, S, a, path_area, spill);
-            else hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, false, true>), dim3(g), block, 0, st, S, a, path_area, spill);
-        } else if (env_on(S.env))
-            hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, true, false>), dim3(g), block, 0, st, S, a, path_area, spill);
-        else
-            hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, false, false>), dim3(g), block, 0, st, S, a, path_area, spill);
+        with_path_variant(S, [&](auto env, auto pick) {
+            hipLaunchKernelGGL((k_wf_finish_pool<MCPT_POOL_WAVES, MCPT_POOL_KT, MCPT_POOL_STACK, env(), pick()>), dim3(g), dim3(MCPT_POOL_WAVES * 64), 0, st, S, a, path_area, spill);
+        });
         return;
     }
-    if (tree_on(S.pick)) {
-        const unsigned g = grid_for(n_upper, 256, unsigned(cfg.finish_grid_tree[env_on(S.env)]));
-        if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish<true, 2>), dim3(g), dim3(256), 0, st, S, a);
-        else hipLaunchKernelGGL((k_wf_finish<false, 2>), dim3(g), dim3(256), 0, st, S, a);
-    } else if (pick_on(S.pick)) {
-        const unsigned g = grid_for(n_upper, 256, unsigned(cfg.finish_grid_one[env_on(S.env)]));
-        if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish<true, true>), dim3(g), dim3(256), 0, st, S, a);
-        else hipLaunchKernelGGL((k_wf_finish<false, true>), dim3(g), dim3(256), 0, st, S, a);
-    } else if (env_on(S.env)) hipLaunchKernelGGL((k_wf_finish<true, false>), dim3(grid_for(n_upper, 256, unsigned(cfg.finish_grid_env))), dim3(256), 0, st, S, a);
-    else hipLaunchKernelGGL((k_wf_finish<false, false>), dim3(grid_for(n_upper, 256, unsigned(cfg.finish_grid))), dim3(256), 0, st, S, a);
+    with_path_variant(S, [&](auto env, auto pick) {
+        const unsigned g = grid_for(n_upper, 256, unsigned(cfg.finish_grid[variant_index(env(), pick())]));
+        hipLaunchKernelGGL((k_wf_finish<env(), pick()>), dim3(g), dim3(256), 0, st, S, a);
+    });
 }
 
 void launch_hit_slots(const PrimaryHit* hits, int first_slot, int n_slots, int32_t* hit_slots, unsigned int* count, hipStream_t st)
@@ -780,26 +719,13 @@ void launch_zero_rad(double* rad, long long n, hipStream_t st)
 
 void init_launch_cfg_logic(LaunchCfg& cfg, unsigned forced_grid)
 {
-    cfg.logic_first = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, false, false>), cfg.cus));
-    cfg.logic_rest = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, false, false>), cfg.cus));
-    cfg.finish_grid = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<false, false>), cfg.cus);
-    cfg.logic_first_env = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, true, false>), cfg.cus));
-    cfg.logic_rest_env = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, true, false>), cfg.cus));
-    cfg.finish_grid_env = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<true, false>), cfg.cus);
-    // MCPT_LIGHTS_ONE, [0] without and [1] under an environment: each instantiation's own occupancy
-    cfg.logic_first_one[0] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, false, true>), cfg.cus));
-    cfg.logic_first_one[1] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, true, true>), cfg.cus));
-    cfg.logic_rest_one[0] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, false, true>), cfg.cus));
-    cfg.logic_rest_one[1] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, true, true>), cfg.cus));
-    cfg.finish_grid_one[0] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<false, true>), cfg.cus);
-    cfg.finish_grid_one[1] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<true, true>), cfg.cus);
-    // MCPT_LIGHTS_TREE likewise
-    cfg.logic_first_tree[0] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, false, 2>), cfg.cus));
-    cfg.logic_first_tree[1] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, true, 2>), cfg.cus));
-    cfg.logic_rest_tree[0] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, false, 2>), cfg.cus));
-    cfg.logic_rest_tree[1] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, true, 2>), cfg.cus));
-    cfg.finish_grid_tree[0] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<false, 2>), cfg.cus);
-    cfg.finish_grid_tree[1] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<true, 2>), cfg.cus);
+    // every instantiation's own occupancy; forced_grid overrides the logic grids only
+    for_each_path_variant([&](auto env, auto pick) {
+        constexpr int v = variant_index(env(), pick());
+        cfg.logic_first[v] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<true, env(), pick()>), cfg.cus));
+        cfg.logic_rest[v] = forced_grid ? forced_grid : unsigned(persistent_grid(reinterpret_cast<const void*>(k_wf_logic<false, env(), pick()>), cfg.cus));
+        cfg.finish_grid[v] = persistent_grid(reinterpret_cast<const void*>(k_wf_finish<env(), pick()>), cfg.cus);
+    });
 }
 
 }  // namespace mcpt

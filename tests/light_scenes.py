@@ -89,8 +89,10 @@ def _texture(size, rng):
     return (np.clip(img, 0, 1) * 255).astype(np.uint8)
 
 
-def write(directory, name, n_lights, width, height, variant="finite", seed=1):
-    """Write <directory>/<name>.{obj,mtl,camera} and its texture; returns the light materials' names in light order."""
+def write(directory, name, n_lights, width, height, variant="finite", seed=1, sunk=()):
+    """Write <directory>/<name>.{obj,mtl,camera} and its texture; returns the light materials' names in light order.
+    sunk: indices of lights that go 0.25 below the floor instead, facing up -- below the horizon of the floor and of every other
+    surface that faces up, and hidden from the whole room."""
     assert variant in ("finite", "nan")
     slots = _slots()
     assert 1 <= n_lights <= len(slots), "at most %d lights" % len(slots)
@@ -141,6 +143,8 @@ def write(directory, name, n_lights, width, height, variant="finite", seed=1):
             else:
                 assert got < a0
         c, U, V, N = slots[order[i]]
+        if i in sunk:
+            c, N = (c[0], y0 - 0.25, c[2]), (0.0, 1.0, 0.0)
         c, U, V = np.array(c), np.array(U), np.array(V)
         tris3 = [tuple(tuple(c + a * U + b * V) for a, b in t) for t in tris2]
         mat = "Lamp%02d" % i

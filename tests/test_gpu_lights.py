@@ -212,6 +212,43 @@ def test_image_matches_oracle(cases, oracle, mcpt, key, engine):
         assert np.isnan(ref).any() and np.isfinite(ref).any()
 
 
+def test_megakernel_traces_lights_behind_the_surface(oracle, mcpt, scene_dir):
+    """Without a light pick the reference traces a shadow ray to every light, also to one behind the surface, whose answer it does not
+    use.  The megakernel does the same and counts it in rays_shadow; the wavefront leaves such a ray out and counts it as skipped.  Two
+    lights, one sunk below the floor: behind the floor at every vertex there."""
+    name, w, h, spp = "lights_sunk", 16, 16, 4
+    light_scenes.write(scene_dir, name, 2, w, h, sunk=(1,))
+    osc = oracle.OracleScene(scene_dir + name, texture_dir=scene_dir, width=w, height=h)
+    sc = mcpt.Scene(scene_dir, name, width=w, height=h)
+    dev = mcpt.Device(sc, 0)
+    try:
+        ost, wst, mst = oracle.Stats(), mcpt.Stats(), mcpt.Stats()
+        ref = osc.render(spp, seed=3, stats=ost)
+        wf = dev.generateImg(spp, seed=3, stats=wst)
+        mk = dev.generateImg(spp, seed=3, stats=mst, flags=mcpt.RENDER_MEGAKERNEL)
+        # with the primary rays on the reference-shaped walk too, every ray of the frame is walked as the oracle walks it: the same work
+        rst = mcpt.Stats()
+        dev.set_trace_mode(mcpt.TRACE_REFERENCE)
+        mk_ref = dev.generateImg(spp, seed=3, stats=rst, flags=mcpt.RENDER_MEGAKERNEL)
+    finally:
+        dev.close()
+        sc.close()
+        osc.close()
+    print("shadow rays: oracle %d, megakernel %d (+ %d skipped), wavefront %d (+ %d skipped)"
+          % (ost.rays_shadow, mst.rays_shadow, mst.shadow_skipped, wst.rays_shadow, wst.shadow_skipped))
+    assert ost.rays_on_surface == 0
+    assert ost.rays_shadow > wst.rays_shadow > 0                    # the scene really has lights behind surfaces
+    assert wst.rays_shadow + wst.shadow_skipped == ost.rays_shadow
+    assert (mst.rays_shadow, mst.shadow_skipped) == (ost.rays_shadow, 0)
+    assert (mst.rays_bounce, mst.shade_calls, mst.samples) == (ost.rays_bounce, ost.shade_calls, ost.samples)
+    assert int((_bits(mk) != _bits(wf)).sum()) == 0
+    print("work: oracle %d box tests, %d triangle tests; megakernel %d node visits, %d triangle tests"
+          % (ost.box_tests, ost.tri_tests, rst.node_visits, rst.tri_tests))
+    assert (rst.node_visits, rst.tri_tests) == (ost.box_tests, ost.tri_tests)       # the rays behind the surface included
+    assert (rst.rays_shadow, rst.shadow_skipped) == (ost.rays_shadow, 0) and int((_bits(mk_ref) != _bits(mk)).sum()) == 0
+    _check_image(mk, ref, spp, oracle, mcpt)
+
+
 # ---------------------------------------------------------------------------------------------- (b) and (d): every route
 @pytest.mark.parametrize("key", list(CASES))
 def test_every_route_gives_the_same_frame(cases, mcpt, key):
