@@ -430,8 +430,9 @@ void build_fast_upper(const double* boxes6, int n, int lower_need, FastBvh& out,
     out.cw_stack_need += lower_need;
 }
 
-// The trace engines mirror the first nodes of the array in LDS (trace_fast.hpp: NodeCache): relabel so that these are the top of the
-// tree, breadth first -- the nodes nearly every ray steps on.  The others keep their relative order.  A walk does not depend on node
+// Relabel the nodes so that the first ones of the array are the top of the tree, breadth first -- the nodes nearly every ray steps on,
+// next to each other in memory.  (An LDS mirror of them was measured and not kept: DESIGN.md section 6; the order stays, every recorded
+// profile and counter was taken with it.)  The others keep their relative order.  A walk does not depend on node
 // numbers (children are ordered by entry distance, pushed by slot): same visits, same results.
 static void cw_top_first(std::vector<CwNode>& cw, int n_top)
 {

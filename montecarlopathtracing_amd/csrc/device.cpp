@@ -368,9 +368,6 @@ static int create_dscene(mcpt_device* d, const Scene& s, double absmax)
     S.fast.stack_limit = K.short_kernel ? kFastShortStack : kFastMaxDepth;
     S.fast.stack_cap = S.fast.stack_limit;
     if (K.test_stack_cap >= 4 && K.test_stack_cap < S.fast.stack_cap) S.fast.stack_cap = K.test_stack_cap;
-    // (any prefix of the node array may be mirrored; the host builder puts the top of the tree there)
-    S.fast.cached = int32_t(std::min<size_t>(size_t(d->fast_info.n_nodes), size_t(kFastTopNodes)));
-    if (K.node_cache >= 0 && K.node_cache < S.fast.cached) S.fast.cached = K.node_cache;
     d->cam_eye = s.eye; d->cam_look_at = s.look_at; d->cam_up = s.up; d->cam_fovy = s.fovy;
     const CameraFrame cf = camera_frame(s);
     put3(S.cam.eye, cf.eye); put3(S.cam.start_point, cf.start_point); put3(S.cam.pdx, cf.screen_pdx); put3(S.cam.pdy, cf.screen_pdy);

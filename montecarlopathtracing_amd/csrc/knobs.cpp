@@ -44,7 +44,6 @@ const Row kRows[] = {
     {"MCPT_FAST_LEAF", "4", "most triangles in a leaf of the host-built hierarchy (1..8)"},
     {"MCPT_FAST_CT", "1.6", "SAH cost of a leaf triangle relative to a node"},
     {"MCPT_BUILD_SERIAL", "0", "1: the host SAH builder on one thread (the threaded build gives the same tree)"},
-    {"MCPT_NODE_CACHE", "engine default", "nodes of the top of the tree the engines may mirror in LDS; no effect unless compiled with MCPT_POOL_CACHE_N > 0"},
     {"MCPT_CLUSTER_LEAF", "1", "MCPT_BUILD_DEVICE_FAST: triangles per leaf of a Morton cluster (1..8)"},
     {"MCPT_CLUSTER_LEVELS", "1", "MCPT_BUILD_DEVICE_FAST: levels of 4-wide nodes built on the GPU (1..5)"},
     {"MCPT_PLOC_CLUSTER", "4096", "MCPT_BUILD_DEVICE_SAH: most triangles in a cluster grown on the GPU"},
@@ -89,7 +88,6 @@ Knobs read_knobs()
     k.fast_leaf = (int)env_ll("MCPT_FAST_LEAF", 0, 1, 1 << 20);
     k.fast_ct = env_d("MCPT_FAST_CT", 0.0, 1e-9, 1e9);
     k.build_serial = env("MCPT_BUILD_SERIAL") != nullptr;
-    k.node_cache = (int)env_ll("MCPT_NODE_CACHE", -1, 0, 1 << 20);
     k.cluster_leaf = (int)env_ll("MCPT_CLUSTER_LEAF", 1, 1, 8);
     k.cluster_levels = (int)env_ll("MCPT_CLUSTER_LEVELS", 1, 1, 5);
     k.ploc_cluster = (int)env_ll("MCPT_PLOC_CLUSTER", 4096, 4, 65536);

@@ -26,7 +26,6 @@ struct Knobs {
     int fast_leaf = 0;                  // MCPT_FAST_LEAF (0: default leaf size)
     double fast_ct = 0;                 // MCPT_FAST_CT (0: default SAH cost of a triangle)
     int build_serial = 0;               // MCPT_BUILD_SERIAL
-    int node_cache = -1;                // MCPT_NODE_CACHE (-1: the engines' own prefix of the top of the tree)
     // ---- culling hierarchy (device builders)
     int cluster_leaf = 1, cluster_levels = 1;   // MCPT_CLUSTER_LEAF / MCPT_CLUSTER_LEVELS (MCPT_BUILD_DEVICE_FAST)
     int ploc_cluster = 4096, ploc_height = 0, ploc_radius = 8, ploc_leaf = 0, ploc_budget = 0;   // MCPT_PLOC_* (MCPT_BUILD_DEVICE_SAH)

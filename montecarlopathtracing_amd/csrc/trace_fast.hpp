@@ -115,6 +115,15 @@ __device__ __forceinline__ bool better_candidate(const DTri* __restrict__ tr, co
     return t > 0 && (!found || t < best.t || (t == best.t && k < best.leaf));
 }
 
+// The hit point of a ray that hit triangle tr: the first two lines of intersect(Ray&, Face&, Vertex&) again -- the same operations on
+// the same operands give the same bits as when the triangle was tested, so an engine carries the triangle, not the point.
+__device__ __forceinline__ V3 hit_point(const DTri* __restrict__ tr, const Ray& r)
+{
+    const V3 v1 = ld3(tr->v1), n = ld3(tr->n);
+    const double t = dot(v1 - r.o, n) / dot(n, r.d);
+    return r.o + r.d * t;
+}
+
 // Rays the fast walk may take.  fp64 side (exact decisions at the leaves): no under/overflow in (b-o)*(1/d);
 // fp32 side (conservative culling on compressed nodes): every product stays finite and above the denormal range.
 __device__ __forceinline__ bool fast_path_ok(const DFast& F, const Ray& r)
@@ -230,46 +239,14 @@ __device__ __forceinline__ bool tri_pre_reject(const DTriPre* __restrict__ q, co
     return clear && rej;
 }
 
-#ifndef MCPT_PARTIAL_SORT
-#define MCPT_PARTIAL_SORT 0
-#endif
-#ifndef MCPT_CW_PACKED
-#define MCPT_CW_PACKED 0          /* near and far plane of an axis as one v_pk_fma_f32: 12 packed instead of 24 scalar fmas per node, 9 instructions fewer after
-                                     the moves it needs -- and 0.6 % slower on three scenes (measured twice): not kept */
-#endif
 struct CwHits { float key[4]; int ref[4]; };
 
 // One step on a compressed node: which children may contain a candidate, sorted by lower bound of entry distance
 // (absent / culled children get key = +inf, ref = EMPTY).
-__device__ __forceinline__ CwHits cw_step_words(const uint4& w0, const uint4& w1, const uint4& w2, const uint4& w3, const RayF& f, float limit_f);
 __device__ __forceinline__ CwHits cw_step(const CwNode* __restrict__ nd, const RayF& f, float limit_f)
 {
     const uint4* q = reinterpret_cast<const uint4*>(nd);
     const uint4 w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3];
-    return cw_step_words(w0, w1, w2, w3, f, limit_f);
-}
-
-// The top of the tree mirrored in LDS (the block copies nodes [0, n) there when it starts): nearly every ray steps on these nodes, and a
-// node fetch is four 16-byte gathers per lane through the vector memory path, which the walk keeps as busy as the ALUs.
-#ifndef MCPT_NODE_CACHE_N
-#define MCPT_NODE_CACHE_N 96         /* nodes of it the engines hold (6 KB per block) */
-#endif
-struct NodeCache { const uint4* lds; int n; };
-__device__ __forceinline__ void fill_node_cache(uint4* lds, const CwNode* __restrict__ nodes, int n)
-{
-    const uint4* g = reinterpret_cast<const uint4*>(nodes);
-    for (int i = threadIdx.x; i < n * 4; i += blockDim.x) lds[i] = g[i];
-    __syncthreads();
-}
-__device__ __forceinline__ CwHits cw_step(const CwNode* __restrict__ nodes, int cur, const NodeCache& nc, const RayF& f, float limit_f)
-{
-    uint4 w0, w1, w2, w3;
-    if (cur < nc.n) { const uint4* q = nc.lds + cur * 4; w0 = q[0]; w1 = q[1]; w2 = q[2]; w3 = q[3]; }
-    else { const uint4* q = reinterpret_cast<const uint4*>(nodes + cur); w0 = q[0]; w1 = q[1]; w2 = q[2]; w3 = q[3]; }
-    return cw_step_words(w0, w1, w2, w3, f, limit_f);
-}
-__device__ __forceinline__ CwHits cw_step_words(const uint4& w0, const uint4& w1, const uint4& w2, const uint4& w3, const RayF& f, float limit_f)
-{
     const float p[3] = {__uint_as_float(w0.x), __uint_as_float(w0.y), __uint_as_float(w0.z)};
     const int e[3] = {(int)(signed char)(w0.w & 255u), (int)(signed char)((w0.w >> 8) & 255u), (int)(signed char)((w0.w >> 16) & 255u)};
     const unsigned qlo[3] = {w1.x, w1.y, w1.z}, qhi[3] = {w1.w, w2.x, w2.y};
@@ -288,47 +265,20 @@ __device__ __forceinline__ CwHits cw_step_words(const uint4& w0, const uint4& w1
         farw[a] = pos ? qhi[a] : qlo[a];
     }
     CwHits h;
-#if MCPT_CW_PACKED
-    typedef float cw_f2 __attribute__((ext_vector_type(2)));
-    cw_f2 sr2[3], pr2[3];
-#pragma unroll
-    for (int a = 0; a < 3; a++) { sr2[a] = cw_f2{sr[a], sr[a]}; pr2[a] = cw_f2{prlo[a], prhi[a]}; }
-#endif
 #pragma unroll
     for (int c = 0; c < 4; c++) {
-#if MCPT_CW_PACKED
-        // near and far plane of an axis as one packed fma (v_pk_fma_f32: the same two roundings as two fmaf)
-        const cw_f2 tx = __builtin_elementwise_fma(cw_f2{(float)((nearw[0] >> (8 * c)) & 255u), (float)((farw[0] >> (8 * c)) & 255u)}, sr2[0], pr2[0]);
-        const cw_f2 ty = __builtin_elementwise_fma(cw_f2{(float)((nearw[1] >> (8 * c)) & 255u), (float)((farw[1] >> (8 * c)) & 255u)}, sr2[1], pr2[1]);
-        const cw_f2 tz = __builtin_elementwise_fma(cw_f2{(float)((nearw[2] >> (8 * c)) & 255u), (float)((farw[2] >> (8 * c)) & 255u)}, sr2[2], pr2[2]);
-        const float tnx = tx.x, tfx = tx.y, tny = ty.x, tfy = ty.y, tnz = tz.x, tfz = tz.y;
-#else
         const float tnx = fmaf((float)((nearw[0] >> (8 * c)) & 255u), sr[0], prlo[0]);
         const float tny = fmaf((float)((nearw[1] >> (8 * c)) & 255u), sr[1], prlo[1]);
         const float tnz = fmaf((float)((nearw[2] >> (8 * c)) & 255u), sr[2], prlo[2]);
         const float tfx = fmaf((float)((farw[0] >> (8 * c)) & 255u), sr[0], prhi[0]);
         const float tfy = fmaf((float)((farw[1] >> (8 * c)) & 255u), sr[1], prhi[1]);
         const float tfz = fmaf((float)((farw[2] >> (8 * c)) & 255u), sr[2], prhi[2]);
-#endif
         const float entry = fmaxf(fmaxf(tnx, tny), tnz);
         const float exit = fminf(fminf(tfx, tfy), tfz);
         const bool hit = child[c] != MCPT_FAST_EMPTY && exit >= 0.0f && entry <= exit && entry <= limit_f;
         h.key[c] = hit ? entry : __builtin_inff();
         h.ref[c] = hit ? child[c] : MCPT_FAST_EMPTY;
     }
-#if MCPT_PARTIAL_SORT
-    // only the nearest child is brought to the front (three conditional swaps); the other hits keep their slot order
-#define MCPT_CSWAP(i, j)                                                                        \
-    {                                                                                           \
-        const bool sw = h.key[j] < h.key[i];                                                    \
-        const float ka = sw ? h.key[j] : h.key[i], kb = sw ? h.key[i] : h.key[j];               \
-        const int ra = sw ? h.ref[j] : h.ref[i], rb = sw ? h.ref[i] : h.ref[j];                 \
-        h.key[i] = ka; h.key[j] = kb; h.ref[i] = ra; h.ref[j] = rb;                             \
-    }
-    MCPT_CSWAP(0, 1) MCPT_CSWAP(2, 3) MCPT_CSWAP(0, 2)
-#undef MCPT_CSWAP
-    return h;
-#endif
     // sorting network for 4 keys
 #define MCPT_CSWAP(i, j)                                                                        \
     {                                                                                           \
@@ -342,9 +292,6 @@ __device__ __forceinline__ CwHits cw_step_words(const uint4& w0, const uint4& w1
     return h;
 }
 
-#ifndef MCPT_LANE_PRE_TEST
-#define MCPT_LANE_PRE_TEST 0           /* the pre-test in the one-lane walk too: measured, no difference (the finishing kernel is bound by its chain of dependent steps, 15.51 vs 15.52 ms per 1/8 frame) */
-#endif
 // One ray per lane, start to finish (while-while over the compressed hierarchy): the same decisions, in the same order
 // per candidate, as the persistent engine -- used where only a few thousand rays remain and a launch per bounce would
 // cost more than the rays themselves.  stack: this lane's LDS words, stack[i * stride].
@@ -354,6 +301,9 @@ __device__ __forceinline__ bool trace_lane_fast(const DScene& S, const Ray& r, H
     if (!fast_path_ok(F, r)) return trace_closest(S, r, best, w);
     const CwNode* __restrict__ nodes = F.cw;
     const DTri* __restrict__ tris = F.tris;
+    // (The culling constants here and in the voting engine's refill, and the push-and-step below and in its inner phase, stay spelled
+    // out at both sites: shared definitions were measured and cost 8 bytes of scratch in k_trace_persistent's short-stack form and in
+    // one k_wf_finish_pool.)
     const V3 rcp = mk(fast_rcp(r.d.x), fast_rcp(r.d.y), fast_rcp(r.d.z));
     const double rmax = fmax(fmax(fabs(rcp.x), fabs(rcp.y)), fabs(rcp.z));
     const double scale = fmax(fmax(F.absmax, fabs(r.o.x)), fmax(fabs(r.o.y), fabs(r.o.z)));
@@ -377,23 +327,7 @@ __device__ __forceinline__ bool trace_lane_fast(const DScene& S, const Ray& r, H
         if (cur == MCPT_FAST_EMPTY) break;
         const int ref = -1 - cur;
         const int first = ref >> 4, count = (ref & 7) + 1;
-        // the leaf's triangles through the conservative fp32 pre-test first (tri_pre_reject: their records are requested together,
-        // one memory latency for the whole leaf), the reference's test for the survivors only
-        unsigned int surv = 0;
-#if MCPT_LANE_PRE_TEST
-        if (!F.pre) surv = (1u << count) - 1u;
-        else {
-            const PreRay pr = make_pre_ray(F, r, rf.o, __double2float_ru(margin));
-#pragma unroll
-            for (int i = 0; i < 4; i++) {        // (a slot past the leaf's last is the next leaf's or the array's padding: tested, not used)
-                const bool rej = tri_pre_reject(F.pre + first + i, pr, limit_f);
-                if (i < count && !rej) surv |= 1u << i;
-            }
-            for (int i = 4; i < count; i++) if (!tri_pre_reject(F.pre + first + i, pr, limit_f)) surv |= 1u << i;
-        }
-#else
-        surv = (1u << count) - 1u;
-#endif
+        unsigned int surv = (1u << count) - 1u;
         w.tris += count;
         while (surv) {
             const int i = __ffs(surv) - 1;

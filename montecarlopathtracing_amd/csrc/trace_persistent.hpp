@@ -36,29 +36,17 @@ namespace mcpt {
 #ifndef MCPT_TAIL_CHUNK
 #define MCPT_TAIL_CHUNK 256         /* slots per claim in the last eighth of a launch */
 #endif
-// Phase vote: the phase with the largest weight x (lanes waiting for it) runs.
+// Phase vote: the vote knows two classes -- lanes at a node, lanes at a leaf (pre-test or exact stage); the class with the largest
+// weight x (lanes waiting for it) runs.  A leaf iteration runs the pre-test for the lanes that enter a leaf and then one exact test for
+// every lane that holds a survivor (its own fresh ones included).
 #ifndef MCPT_W_INNER
 #define MCPT_W_INNER 4
 #endif
 #ifndef MCPT_W_TRI
 #define MCPT_W_TRI 3
 #endif
-#ifndef MCPT_W_EXACT
-#define MCPT_W_EXACT 3
-#endif
-#ifndef MCPT_LEAF_CLASS
-#define MCPT_LEAF_CLASS 1           /* 1: the vote knows two classes -- lanes at a node, lanes at a leaf; a leaf iteration runs the pre-test
-                                       for the lanes that enter a leaf and then one exact test for every lane that holds a survivor (its own
-                                       fresh ones included).  0: three classes, the exact test as a phase of its own. */
-#endif
-#ifndef MCPT_EXACT_MIN
-#define MCPT_EXACT_MIN 1            /* MCPT_LEAF_CLASS: lanes holding a survivor before a leaf iteration runs its exact block */
-#endif
 #ifndef MCPT_PRE_UNROLL
 #define MCPT_PRE_UNROLL 2           /* triangles per round of the pre-test (their records are requested together) */
-#endif
-#ifndef MCPT_PRE_TEST
-#define MCPT_PRE_TEST 1             /* 0: every visited triangle survives the pre-test (A/B runs; same results) */
 #endif
 
 // Src must provide:  long long total() const;
@@ -71,6 +59,91 @@ namespace mcpt {
 #define MCPT_RAYBUF_DOUBLES 6
 #define MCPT_RAYBUF_BYTES (64 * (MCPT_RAYBUF_DOUBLES * 8 + 4))      /* per wave: 64 rays and their flags */
 
+// ---- steps the two queue-fed engines (this one and trace_pool.hpp) share: each keeps its own state layout, the arithmetic and the
+// decisions are here once.
+
+// The claim schedule.  The queue head counts tickets: ticket k < big_tickets covers slots [k * chunk, (k + 1) * chunk) -- the first seven
+// eighths of the launch -- and every later ticket MCPT_TAIL_CHUNK slots (tests/test_trace_schedule_cpu.py restates it).
+struct TicketSchedule { long long total, chunk, small, big_tickets; };
+__device__ __forceinline__ TicketSchedule make_ticket_schedule(long long total, long long chunk)
+{
+    TicketSchedule ts;
+    ts.total = total; ts.chunk = chunk;
+    ts.small = chunk < MCPT_TAIL_CHUNK ? chunk : MCPT_TAIL_CHUNK;
+    ts.big_tickets = (total - total / 8) / chunk;
+    return ts;
+}
+// the slots of a ticket: [next, range_end); false: the ticket lies past the last slot (the queue is empty)
+__device__ __forceinline__ bool ticket_range(const TicketSchedule& ts, long long ticket, long long& next, long long& range_end)
+{
+    const long long size = ticket < ts.big_tickets ? ts.chunk : ts.small;
+    next = ticket < ts.big_tickets ? ticket * ts.chunk : ts.big_tickets * ts.chunk + (ticket - ts.big_tickets) * ts.small;
+    range_end = next + size < ts.total ? next + size : ts.total;
+    return next < ts.total;
+}
+
+// A slot goes to the deferred list, which the second pass walks one lane per ray.  undecided: the fast walk took the ray and could not
+// decide it (stack overflow, leader's own box fails), so if the list is full the second pass has to re-walk every slot; a ray the fast
+// walk may not take at all is recognised again by fast_path_ok() when the second pass scans the slots.
+__device__ __forceinline__ void defer_ray(TraceQueue* queue, long long* __restrict__ slow_list, unsigned int slow_cap, long long slot, bool undecided)
+{
+    const unsigned int at = atomicAdd(&queue->slow_count, 1u);
+    if (at < slow_cap) slow_list[at] = slot;
+    else if (undecided) queue->redo_all = 1u;
+}
+
+// A leaf's triangles [first, first + count) through the fp32 pre-test; bit k of the result: triangle first + k goes on to the exact test.
+// MCPT_PRE_UNROLL triangles per round: their records are requested together, so a round costs one memory latency.
+__device__ __forceinline__ unsigned int leaf_survivors(const DTriPre* __restrict__ pre, int first, int count, const PreRay& pr, float limit_f)
+{
+    unsigned int surv = 0;
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+    for (int k0 = 0; k0 < count; k0 += MCPT_PRE_UNROLL) {
+#pragma unroll
+        for (int j = 0; j < MCPT_PRE_UNROLL; j++) {
+            const int k = k0 + j;
+            // (a slot past the leaf's last is a triangle of the next leaf or the array's padding: tested, not used)
+            const bool rej = tri_pre_reject(pre + first + k, pr, limit_f);
+            if (k < count && !rej) surv |= 1u << k;
+        }
+    }
+    return surv;
+}
+#ifdef MCPT_PRE_CHECK
+// self-check build: every REJECTED triangle through the exact test as well; one that passes it with a positive t_k not behind the
+// leader should have survived.  Returns the mask of those (the caller counts them and makes them survive).
+__device__ __forceinline__ unsigned int leaf_wrongly_rejected(const DTri* __restrict__ tris, int first, int count, unsigned int surv, const Ray& r,
+                                                              bool found, double best_t)
+{
+    unsigned int wrong = 0;
+    for (int k = 0; k < count; k++) {
+        if ((surv >> k) & 1u) continue;
+        V3 pc;
+        if (tri_hit(tris + first + k, r, pc)) {
+            const double tc = (pc.x - r.o.x) / r.d.x;
+            if (tc > 0.0 && (!found || tc <= best_t * (1.0 + 0x1p-40))) wrong |= 1u << k;
+        }
+    }
+    return wrong;
+}
+#endif
+
+// Ranking a triangle whose test passed against the leader.  With ta = (p.x - o.x) * (1 / d.x) > 0, t_k = (p.x - o.x) / d.x is within
+// 2^-50 (relative) of this product and has its sign: two candidates whose products differ by more than band = best_t * 2^-47 are ranked
+// like their t_k -- ta < best_t - band leads, ta > best_t + band is behind.  (Both engines spell these two comparisons out: as a shared
+// function returning lead / tie / behind they were measured and changed the pool kernels' VGPR count.)  In between the two are closer
+// than the products resolve (a shared edge, a face listed twice, two sides of a sheet), and tie_prefers_new() decides:
+// the reference's own order of two candidates, (t_k, k), from their hit points' x with true divisions (pathTracing.cpp:347).  Whether
+// either is a candidate at all (its own box) is not looked at here -- a non-candidate that takes or keeps the lead can only be displaced
+// by something closer still, and if it is still leading when the ray is finished the own-box test sends the ray to the exact walk.
+__device__ __forceinline__ bool tie_prefers_new(const Ray& r, double px_new, double px_old, const DTri* __restrict__ tr_new, const DTri* __restrict__ tr_old)
+{
+    const double t_new = (px_new - r.o.x) / r.d.x, t_old = (px_old - r.o.x) / r.d.x;
+    return t_new < t_old || (t_new == t_old && tr_new->leaf < tr_old->leaf);
+}
+// the walk's limit once ta leads: upper bound (rounded up) of the leader's product x (1 + 2^-47) + margin
+__device__ __forceinline__ float lead_limit(double ta, float margin_f) { return __double2float_ru((ta + ta * 0x1p-47) + (double)margin_f); }
+
 template <class Src>
 __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src, TraceQueue* queue, long long* __restrict__ slow_list,
                                                  unsigned int slow_cap, long long chunk, int* __restrict__ stack, int stride,
@@ -81,10 +154,7 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
     const CwNode* __restrict__ nodes = F.cw;
     const DTri* __restrict__ tris = F.tris;
     const DTriPre* __restrict__ pre = F.pre;
-    const long long total = src.total();
-    // ticket k < big_tickets: slots [k * chunk, (k + 1) * chunk); later tickets: MCPT_TAIL_CHUNK slots each
-    const long long small = chunk < MCPT_TAIL_CHUNK ? chunk : MCPT_TAIL_CHUNK;
-    const long long big_tickets = (total - total / 8) / chunk;
+    const TicketSchedule ts = make_ticket_schedule(src.total(), chunk);
     const int lane = threadIdx.x & 63;
     // work counters that are the same for every lane of a phase: wave-uniform, in scalar registers (per-lane they would cost three
     // VGPRs the walk does not have); wctr: a few LDS words behind the rays for the rare per-lane corrections
@@ -131,19 +201,10 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
             h.leaf = tr->leaf;
             h.mat = tr->material;
             h.t = (best_px - r.o.x) / r.d.x;                    // pathTracing.cpp:347
-            // the hit point, for sources that store it: the first two lines of intersect(Ray&, Face&, Vertex&) again -- the same
-            // operations on the same operands give the same bits as when the triangle was tested
-            if constexpr (Src::kWantsPoint) {
-                const V3 v1 = ld3(tr->v1), n = ld3(tr->n);
-                const double t = dot(v1 - r.o, n) / dot(n, r.d);
-                h.p = r.o + r.d * t;
-            }
+            if constexpr (Src::kWantsPoint) h.p = hit_point(tr, r);     // for sources that store it
         }
-        if (ambiguous) {
-            const unsigned int at = atomicAdd(&queue->slow_count, 1u);
-            if (at < slow_cap) slow_list[at] = slot;
-            else queue->redo_all = 1u;                          // list full: the second pass re-walks every slot
-        } else src.store(slot, found, h);
+        if (ambiguous) defer_ray(queue, slow_list, slow_cap, slot, true);
+        else src.store(slot, found, h);
     };
 
     // claim the next <= 64 slots
@@ -154,11 +215,7 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
             unsigned long long got = 0;
             if (lane == 0) got = atomicAdd(&queue->head, 1ull);
             got = __shfl(got, 0, 64);
-            const long long ticket = (long long)got;
-            const long long size = ticket < big_tickets ? chunk : small;
-            next = ticket < big_tickets ? ticket * chunk : big_tickets * chunk + (ticket - big_tickets) * small;
-            range_end = next + size < total ? next + size : total;
-            if (next >= total) { queue_empty = true; return; }
+            if (!ticket_range(ts, (long long)got, next, range_end)) { queue_empty = true; return; }
         }
         const long long avail = range_end - next;
         reg_count = avail < 64 ? (int)avail : 64;
@@ -226,6 +283,7 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
                         const long long q = lds_base + e;
                         if (fast_path_ok(F, nr)) {
                             slot = q; r = nr;
+                            // (the culling constants of trace_lane_fast, spelled out: see there)
                             const V3 rcp = mk(fast_rcp(r.d.x), fast_rcp(r.d.y), fast_rcp(r.d.z));
                             const double rmax = fmax(fmax(fabs(rcp.x), fabs(rcp.y)), fabs(rcp.z));     // = 1 / min|d_k|
                             const double scale = fmax(fmax(F.absmax, fabs(r.o.x)), fmax(fabs(r.o.y), fabs(r.o.z)));
@@ -236,10 +294,7 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
                             ambiguous = false;
                             sp = 0; cur = 0; state = ST_INNER;
                             started = true;
-                        } else {
-                            const unsigned int at = atomicAdd(&queue->slow_count, 1u);
-                            if (at < slow_cap) slow_list[at] = q;    // list full: the second pass scans every slot instead
-                        }
+                        } else defer_ray(queue, slow_list, slow_cap, q, false);
                     }
                 }
                 lds_taken += give;
@@ -254,21 +309,14 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
             if (lds_taken >= lds_count && reg_count == 0) break;      // no walking lane and no ray left to hand out
             continue;
         }
-#if MCPT_LEAF_CLASS
         // two classes: lanes at a node, lanes at a leaf (pre-test or exact stage); the leaf phase runs both of its blocks
         const int phase = (MCPT_W_INNER * n_inner >= MCPT_W_TRI * (n_tri + n_exact)) ? ST_INNER : ST_TRI;
-#else
-        const int s_inner = MCPT_W_INNER * n_inner, s_tri = MCPT_W_TRI * n_tri, s_exact = MCPT_W_EXACT * n_exact;
-        const int phase = (s_inner >= s_tri && s_inner >= s_exact) ? ST_INNER : (s_tri >= s_exact ? ST_TRI : ST_EXACT);
-#endif
 #ifdef MCPT_TRACE_DIAG
         if (lane == 0) {
             const int k = phase - 1;                                   // 0 inner, 1 tri, 2 exact
             w.diag[2 * k] += 1; w.diag[2 * k + 1] += phase == ST_INNER ? n_inner : (phase == ST_TRI ? n_tri : n_exact);
             w.diag[6] += 64 - n_inner - n_tri - n_exact;
-#if MCPT_LEAF_CLASS
             if (phase == ST_TRI) { w.diag[4] += 1; w.diag[5] += n_exact; }      // exact-stage lanes at the start of a leaf iteration
-#endif
         }
 #endif
         MCPT_STAMP(phase)
@@ -294,71 +342,41 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
                 }
             }
         }
-#if MCPT_LEAF_CLASS
         if (phase == ST_TRI && n_tri) {
-#else
-        else if (phase == ST_TRI) {
-#endif
             // -------------------------------------------------------------- the triangles of a leaf through the fp32 pre-test
             if (state == ST_TRI) {
                 unsigned int surv = 0;
-#if MCPT_PRE_TEST
                 w.tris += tri_m;
                 if (!pre) surv = (1u << tri_m) - 1u;       // scenes for which the pre-test is switched off (device.cpp: too large for the caches)
                 else {
-                const PreRay pr = make_pre_ray(F, r, rf.o, margin_f);
-                // MCPT_PRE_UNROLL triangles per round: their records are requested together, so a round costs one memory latency
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-                for (int k0 = 0; k0 < tri_m; k0 += MCPT_PRE_UNROLL) {
-#pragma unroll
-                    for (int j = 0; j < MCPT_PRE_UNROLL; j++) {
-                        const int k = k0 + j;
-                        // (a slot past the leaf's last is a triangle of the next leaf or the array's padding: tested, not used)
-                        const bool rej = tri_pre_reject(pre + cur + k, pr, limit_f);
-                        if (k < tri_m && !rej) surv |= 1u << k;
-                    }
-                }
+                    const PreRay pr = make_pre_ray(F, r, rf.o, margin_f);
+                    surv = leaf_survivors(pre, cur, tri_m, pr, limit_f);
 #ifdef MCPT_PRE_CHECK
-                // self-check build: every REJECTED triangle through the exact test as well; one that passes it with a positive t_k not
-                // behind the leader should have survived (counted, and made to survive)
-                for (int k = 0; k < tri_m; k++) {
-                    if ((surv >> k) & 1u) continue;
-                    V3 pc;
-                    if (tri_hit(tris + cur + k, r, pc)) {
-                        const double tc = (pc.x - r.o.x) / r.d.x;
-                        if (tc > 0.0 && (!found || tc <= best_t * (1.0 + 0x1p-40))) {
-                            atomicAdd(&wctr[3], 1u); surv |= 1u << k;
-                            if (w.dbg && atomicCAS(w.dbg, 0ull, 1ull) == 0ull) {      // the first one: what the pre-test saw
-                                float h[8];
-                                (void)tri_pre_reject(pre + cur + k, pr, limit_f, h);
-                                double* o = reinterpret_cast<double*>(w.dbg);
-                                for (int i = 0; i < 8; i++) o[1 + i] = h[i];
-                                o[9] = tc; o[10] = found ? best_t : -1.0; o[11] = limit_f; o[12] = pr.margin; o[13] = pr.eta4; o[14] = cur + k; o[15] = tri_m;
-                                o[16] = r.o.x; o[17] = r.o.y; o[18] = r.o.z; o[19] = r.d.x; o[20] = r.d.y; o[21] = r.d.z;
-                            }
+                    const unsigned int wrong = leaf_wrongly_rejected(tris, cur, tri_m, surv, r, found, best_t);
+                    if (wrong) {
+                        atomicAdd(&wctr[3], (unsigned int)__popc(wrong)); surv |= wrong;
+                        if (w.dbg && atomicCAS(w.dbg, 0ull, 1ull) == 0ull) {      // the first one: what the pre-test saw
+                            const int k = __ffs((int)wrong) - 1;
+                            float h[8];
+                            (void)tri_pre_reject(pre + cur + k, pr, limit_f, h);
+                            V3 pc;
+                            (void)tri_hit(tris + cur + k, r, pc);
+                            double* o = reinterpret_cast<double*>(w.dbg);
+                            for (int i = 0; i < 8; i++) o[1 + i] = h[i];
+                            o[9] = (pc.x - r.o.x) / r.d.x; o[10] = found ? best_t : -1.0; o[11] = limit_f; o[12] = pr.margin; o[13] = pr.eta4; o[14] = cur + k; o[15] = tri_m;
+                            o[16] = r.o.x; o[17] = r.o.y; o[18] = r.o.z; o[19] = r.d.x; o[20] = r.d.y; o[21] = r.d.z;
                         }
                     }
-                }
 #endif
                 }
-#else
-                w.tris += tri_m;
-                surv = (1u << tri_m) - 1u;
-#endif
                 if (surv) { tri_m = (int)surv; state = ST_EXACT; }
                 else pop_next();
             }
         }
-#if MCPT_LEAF_CLASS
-        // the exact block runs once enough lanes hold a survivor (or nothing else is waiting at a leaf): below that they wait, as
-        // members of the leaf class, for the next leaf iteration
+        // the exact block of a leaf iteration runs as soon as one lane holds a survivor
         const int n_hold = phase == ST_TRI ? __popcll(__ballot(state == ST_EXACT)) : 0;
-        if (n_hold >= MCPT_EXACT_MIN || (n_hold && (!n_tri || n_hold >= n_tri + n_exact))) {
+        if (n_hold) {
             c_exact += (unsigned int)n_hold;
-#else
-        else if (phase == ST_EXACT) {
-            c_exact += (unsigned int)n_exact;
-#endif
             // -------------------------------------------------------------- one surviving triangle through the reference's test
             if (state == ST_EXACT) {
                 const int k = __ffs(tri_m) - 1;
@@ -369,24 +387,14 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
                 // order of evaluation is free: the triangle test goes first, the own box is looked at once per ray (finish_ray).
                 V3 p;
                 if (tri_hit(tr, r, p)) {
-                    // t_k = (p.x - o.x) / d.x is within 2^-50 (relative) of this product and has its sign: two candidates whose
-                    // products differ by more than 2^-47 are ranked like their t_k
                     const double ta = (p.x - r.o.x) * fast_rcp(r.d.x);
                     if (ta > 0.0) {
                         const double band = best_t * 0x1p-47;
                         if (!found || ta < best_t - band) {
                             found = true; best_leaf = ti; best_t = ta; best_px = p.x;
-                            limit_f = __double2float_ru((ta + ta * 0x1p-47) + (double)margin_f);
-                        } else if (!(ta > best_t + band)) {
-                            // closer to the leader than the products resolve (a shared edge, a face listed twice, two sides of
-                            // a sheet): the reference's own order of the two, (t_k, k).  Whether either is a candidate at all (its
-                            // own box) is not looked at here -- a non-candidate that takes or keeps the lead here can only be
-                            // displaced by something closer still, and if it is still leading when the ray is finished the own-box
-                            // test there sends the ray to the exact walk
-                            const double t_new = (p.x - r.o.x) / r.d.x, t_old = (best_px - r.o.x) / r.d.x;
-                            if (t_new < t_old || (t_new == t_old && tr->leaf < tris[best_leaf].leaf)) {
-                                best_leaf = ti; best_t = ta; best_px = p.x;
-                            }
+                            limit_f = lead_limit(ta, margin_f);
+                        } else if (!(ta > best_t + band) && tie_prefers_new(r, p.x, best_px, tr, tris + best_leaf)) {
+                            best_leaf = ti; best_t = ta; best_px = p.x;
                         }
                     }
                 }

@@ -17,7 +17,7 @@
 //     floats, limit, leader, eight stack entries): every slot more per lane is worth one to two lanes per step.
 //   * Ordering between the wave that leaves a slot and the wave that takes it: the OR that files the slot is a release, the AND that
 //     claims it an acquire (workgroup scope) -- everything the step wrote, in LDS or in the global spill area, happens-before
-//     everything the next step reads (MCPT_POOL_ORDER).
+//     everything the next step reads.
 //   * Only the first MCPT_POOL_STACK entries of a slot's traversal stack are in LDS; the deeper ones (a tenth of the rays get there)
 //     live in a global spill area behind the launch's deferred-ray list, [block][entry][slot].  A ray that would pass the walk's
 //     stack_cap goes to the deferred list (one-lane walk), like in the persistent engine.
@@ -52,58 +52,16 @@ struct NoPaths { static constexpr bool kPaths = false; };
 #define MCPT_POOL_STACK 8           /* stack entries per slot in LDS */
 #endif
 #define MCPT_POOL_SPILL (MCPT_FAST_STACK - MCPT_POOL_STACK)      /* ... and beyond them in global memory (few rays go that deep) */
-// vote: the class with the largest weight x (lanes that can claim a slot of it) runs; ties go downstream (finish > exact > leaf > node)
 #ifndef MCPT_POOL_CLAIMS
 #define MCPT_POOL_CLAIMS 2             /* attempts of a lane to claim a slot in one step */
 #endif
 /* (a claim that takes every slot of the class the word shows and hands back all but one was measured in round 3: 85.0 vs 81.7 ms, the
    hidden slots starve the other waves) */
-#ifndef MCPT_POOL_PREFETCH
-#define MCPT_POOL_PREFETCH 0
-#endif
-#ifndef MCPT_POOL_CACHE_N
-#define MCPT_POOL_CACHE_N 0         /* nodes of the top of the tree held in LDS; 52 is what the 160 KB leave beside the ray slots -- measured: 7.11 ms per trace
-                                       launch with them, 7.07 without (round 4: the kernel is bound by vector instruction issue, not by its gathers) */
-#endif
-#ifndef MCPT_POOL_STICKY
-#define MCPT_POOL_STICKY 0          /* a lane whose slot stays at a node keeps it for the wave's next node step (no filing, no claim) */
-#endif
-#ifndef MCPT_POOL_PREF
-#define MCPT_POOL_PREF 0            /* > 0: every wave has a class it prefers (its score counts (4 + PREF) / 4): simultaneous voters spread out */
-#endif
 // Hand-over of a slot from one wave to another.  What a step writes (LDS state, and stack entries beyond the eighth: plain stores to
-// the global spill area) must be visible to the wave that claims the slot next.  1 (default): the filing OR is a RELEASE and the claiming
-// AND an ACQUIRE at workgroup scope -- the memory model's own guarantee, for LDS and for the spill area alike.  0: relaxed atomics
-// between compiler barriers, which leans on the LDS unit executing a wave's instructions in order and says nothing about the spill
-// stores (they travel through the vector memory path, counted by vmcnt, not lgkmcnt) -- what rounds 3 ran; kept for A/B runs.
-#ifndef MCPT_POOL_ORDER
-#define MCPT_POOL_ORDER 1
-#endif
-#if MCPT_POOL_ORDER
+// the global spill area) must be visible to the wave that claims the slot next: the filing OR is a RELEASE and the claiming AND an
+// ACQUIRE at workgroup scope -- the memory model's own guarantee, for LDS and for the spill area alike.
 #define MCPT_POOL_CLAIM_ORDER __ATOMIC_ACQUIRE
 #define MCPT_POOL_FILE_ORDER __ATOMIC_RELEASE
-#else
-#define MCPT_POOL_CLAIM_ORDER __ATOMIC_RELAXED
-#define MCPT_POOL_FILE_ORDER __ATOMIC_RELAXED
-#endif
-#ifndef MCPT_POOL_FASTPUSH
-#define MCPT_POOL_FASTPUSH 1        /* 0: a branch per pushed child (A/B runs) */
-#endif
-#ifndef MCPT_PW_INNER
-#define MCPT_PW_INNER 4
-#endif
-#ifndef MCPT_PW_LEAF
-#define MCPT_PW_LEAF 4
-#endif
-#ifndef MCPT_PW_EXACT
-#define MCPT_PW_EXACT 4
-#endif
-#ifndef MCPT_PW_FIN
-#define MCPT_PW_FIN 4
-#endif
-#ifndef MCPT_PW_SHADE
-#define MCPT_PW_SHADE 4             /* path mode: weight of the paths waiting for their next vertex */
-#endif
 
 struct alignas(16) PoolOxy { double ox, oy; };
 struct alignas(16) PoolOzDx { double oz, dx; };
@@ -144,7 +102,6 @@ struct PoolLds {
     unsigned int cls[5 * 64];               // [class][lane]: bit k = slot k * 64 + lane waits for a step of that class (class 4, path mode: bit k = PATH slot k waits for its next vertex)
     unsigned int busy[64];                  // path mode: bit k = ray slot k of this lane is still walking
     int tbl[NW * 64];                       // refill: rank among the fetched rays -> lane that holds it
-    uint4 nodes[MCPT_POOL_CACHE_N ? MCPT_POOL_CACHE_N * 5 : 1];     // the top of the tree, 80 bytes apart (64 of node, 16 unused: lanes on eight consecutive nodes read without a bank conflict)
     unsigned int stat[8];                   // path mode: shade calls, shadow rays, bounce rays, shadow rays skipped, deepest vertex (flushed by the kernel)
     unsigned int live;                      // slots that may still carry a ray (path mode: path slots that may still carry a path)
     unsigned int dry;                       // waves whose supply of source slots has run out
@@ -172,9 +129,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
     const CwNode* __restrict__ nodes = F.cw;
     const DTri* __restrict__ tris = F.tris;
     const DTriPre* __restrict__ pre = F.pre;
-    const long long total = src.total();
-    const long long small = chunk < MCPT_TAIL_CHUNK ? chunk : MCPT_TAIL_CHUNK;
-    const long long big_tickets = (total - total / 8) / chunk;
+    const TicketSchedule ts = make_ticket_schedule(src.total(), chunk);
     const int lane = threadIdx.x & 63, wave = uni((int)(threadIdx.x >> 6));      // (wave: the same in every lane, and the compiler is told so)
     const int stack_max = spill ? SCAP + MCPT_POOL_SPILL : SCAP;
     const int stack_cap = F.stack_cap < stack_max ? F.stack_cap : stack_max;
@@ -191,10 +146,6 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
     // every slot starts in the finish class without a ray: the first steps of every wave are refills
     // (path mode: every path slot starts free in the SHADE class -- the first steps are adoptions -- and no ray slot is filed)
     for (int k = wave; k < KT; k += NW) { L.spf[k * 64 + lane] = 0; if constexpr (PP::kPaths) L.q[k * 64 + lane] = 0u; }
-    // More than half of all node steps are on the top three levels of the tree: MCPT_POOL_CACHE_N > 0 reads those nodes from LDS.  Two
-    // explicit address spaces and a branch between them -- one pointer that may be either is a flat load, which goes down BOTH paths.
-    const int n_cached = F.cached < MCPT_POOL_CACHE_N ? F.cached : MCPT_POOL_CACHE_N;
-    { const uint4* g = reinterpret_cast<const uint4*>(nodes); for (int i = threadIdx.x; i < n_cached * 4; i += NW * 64) L.nodes[(i >> 2) * 5 + (i & 3)] = g[i]; }
     // path mode: R ray slots per path (one per light and the bounce ray), NP path slots per lane
     int R = 1, NP = KT;
     if constexpr (PP::kPaths) { R = pp.nl + 1; NP = KT / R; }
@@ -222,30 +173,6 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
     // every pair of waves with a stride of its own (11, 13, 17, 19: odd, and coprime to the 20 slots), so that two waves after the same
     // class do not keep looking at the same slot first (-0.5 % of the kernel against a common stride of 1)
     const int rot_stride = (int)((0x13110d0bu >> (8 * ((wave >> 1) & 3))) & 255u) % KT | 1;
-    bool keep = false;                          // MCPT_POOL_STICKY: this lane still owns slot keep_k, which waits for a node step
-    int keep_k = 0;
-#if MCPT_POOL_PREF
-    // nine waves of sixteen lean to the node step, three to the pre-test, two each to the exact test and the refill (their shares of the steps)
-    const int pref_slot = (wave * 16 / NW) & 15;
-    const int pref = pref_slot < 9 ? C_INNER : (pref_slot < 12 ? C_LEAF : (pref_slot < 14 ? C_EXACT : C_FIN));
-#endif
-
-    // What the slot's next step will read from memory is requested now -- by whichever wave runs that step, from the CU's L1 instead of
-    // from L2.  The loaded word is not looked at; it is folded into `junk` behind a later load of this wave (loads return in order), so
-    // nothing ever waits for it.
-    unsigned int pf = 0, junk = 0;
-#if MCPT_POOL_PREFETCH
-#define MCPT_TOUCH(ptr) pf += *reinterpret_cast<const volatile unsigned int*>(ptr)
-#else
-#define MCPT_TOUCH(ptr)
-#endif
-    auto touch_next = [&](bool node, int first, int cnt) __attribute__((always_inline)) {
-#if MCPT_POOL_PREFETCH
-        if (node) MCPT_TOUCH(nodes + first);
-        else if (pre) { MCPT_TOUCH(pre + first); if (cnt > 2) MCPT_TOUCH(pre + first + cnt - 1); }
-#endif
-    };
-
     // Culling pads and pruning margin are recomputed from the floats a step has at hand instead of being carried in the slot (16 bytes
     // of 184): in fp32, rounded so that they are never below the values make_rayf / the voting engine use (those have a factor 2.6 of
     // slack over the error they cover) -- a larger pad or margin only culls less; the decisions at the leaves are untouched.
@@ -261,18 +188,13 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
         int sp = spf & 255;
         if (sp == 0) return C_FIN;
         sp--;
-#if MCPT_POOL_FASTPUSH
         int nxt;
         // (the empty asm keeps the compiler from merging the two reads into one flat load through a selected address)
         if (!__ballot(sp >= SCAP)) { nxt = L.stack[(sp * KT + k) * 64 + lane]; __asm__ volatile("" : "+v"(nxt)); }
         else nxt = st_get(sp, k);
-#else
-        const int nxt = st_get(sp, k);
-#endif
         const bool node = nxt >= 0;
         const int ref = -1 - nxt;
         const int first = node ? nxt : ref >> 4, cnt = (ref & 7) + 1;
-        touch_next(node, first, cnt);
         L.cur[idx] = first;
         L.spf[idx] = (spf & 0xff00) | sp | (node ? 0 : cnt << 16);
         return node ? C_INNER : C_LEAF;
@@ -283,7 +205,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
         const unsigned int m_leaf = __hip_atomic_load(&L.cls[C_LEAF * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         const unsigned int m_exact = __hip_atomic_load(&L.cls[C_EXACT * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         const unsigned int m_fin = __hip_atomic_load(&L.cls[C_FIN * 64 + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        const int n_inner = __popcll(__ballot(keep || m_inner != 0u));
+        const int n_inner = __popcll(__ballot(m_inner != 0u));
         const int n_leaf = __popcll(__ballot(m_leaf != 0u));
         const int n_exact = __popcll(__ballot(m_exact != 0u));
         // A wave's claim on source slots is private (a chunk per ticket): once the tickets are gone, a wave without a chunk leaves the
@@ -297,7 +219,6 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
             n_shade = __popcll(__ballot(m_shade != 0u));
         }
         if (!(n_inner | n_leaf | n_exact | n_fin | n_shade)) {
-            // (no lane keeps a slot here: n_inner counts them)
             if (uni((int)__hip_atomic_load(&L.live, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0) break;
             __builtin_amdgcn_s_sleep(4);         // the other waves hold what is left
 #ifdef MCPT_POOL_DEBUG
@@ -305,34 +226,19 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
 #endif
             continue;
         }
-        int c = C_FIN, best_score = MCPT_PW_FIN * n_fin;
-        if (MCPT_PW_EXACT * n_exact > best_score) { c = C_EXACT; best_score = MCPT_PW_EXACT * n_exact; }
-        if (MCPT_PW_LEAF * n_leaf > best_score) { c = C_LEAF; best_score = MCPT_PW_LEAF * n_leaf; }
-        if (MCPT_PW_INNER * n_inner > best_score) { c = C_INNER; best_score = MCPT_PW_INNER * n_inner; }
+        // vote: the class with the most lanes that can claim a slot of it runs; ties go downstream (finish > exact > leaf > node)
+        int c = C_FIN, best_score = n_fin;
+        if (n_exact > best_score) { c = C_EXACT; best_score = n_exact; }
+        if (n_leaf > best_score) { c = C_LEAF; best_score = n_leaf; }
+        if (n_inner > best_score) { c = C_INNER; best_score = n_inner; }
         // (a waiting path keeps up to R ray slots idle: the SHADE class goes first on a tie)
-        if (PP::kPaths && MCPT_PW_SHADE * n_shade >= best_score && n_shade) { c = C_SHADE; best_score = MCPT_PW_SHADE * n_shade; }
-#if MCPT_POOL_PREF
-        {
-            const int s0 = MCPT_PW_INNER * n_inner * (pref == C_INNER ? 4 + MCPT_POOL_PREF : 4), s1 = MCPT_PW_LEAF * n_leaf * (pref == C_LEAF ? 4 + MCPT_POOL_PREF : 4);
-            const int s2 = MCPT_PW_EXACT * n_exact * (pref == C_EXACT ? 4 + MCPT_POOL_PREF : 4), s3 = MCPT_PW_FIN * n_fin * (pref == C_FIN ? 4 + MCPT_POOL_PREF : 4);
-            c = C_FIN; best_score = s3;
-            if (s2 > best_score) { c = C_EXACT; best_score = s2; }
-            if (s1 > best_score) { c = C_LEAF; best_score = s1; }
-            if (s0 > best_score) { c = C_INNER; best_score = s0; }
-        }
-#endif
+        if (PP::kPaths && n_shade >= best_score && n_shade) { c = C_SHADE; best_score = n_shade; }
         c = uni(c);
-        // slots kept for a node step that is not the next step after all are filed now
-        if (c != C_INNER && __ballot(keep)) {
-            if (keep) __hip_atomic_fetch_or(&L.cls[C_INNER * 64 + lane], 1u << keep_k, MCPT_POOL_FILE_ORDER, __HIP_MEMORY_SCOPE_WORKGROUP);
-            keep = false;
-        }
 
         // Claim: another wave's lane of the same index may be after the same slot (it read the same mask a moment ago).  Odd waves look
         // from the top, even ones from the bottom, and a lane that lost tries once more on what the atomic returned (the fresh mask).
-        bool have = keep;
-        int k = keep_k;
-        keep = false;
+        bool have = false;
+        int k = 0;
         unsigned int cm = c == C_INNER ? m_inner : (c == C_LEAF ? m_leaf : (c == C_EXACT ? m_exact : (c == C_FIN ? m_fin : m_shade)));
         unsigned int* const cword = &L.cls[c * 64 + lane];
         // (rot and the wave's parity are scalars: the two masks are too, and the choice between them is a scalar branch)
@@ -385,32 +291,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 if (sp > stack_cap - 3) {        // three pushes must fit: the ray goes to the one-lane walk
                     L.spf[idx] = spf | F_AMBIG; nc = C_FIN; refused = true;
                 } else {
-#if MCPT_POOL_CACHE_N
-                    // (the LDS side first: the memory side's loads go into the same registers and would otherwise be waited for before the
-                    // LDS reads may even be issued)
-                    typedef unsigned int pool_u4 __attribute__((ext_vector_type(4)));
-                    pool_u4 v0 = 0u, v1 = 0u, v2 = 0u, v3 = 0u;
-                    const bool in_lds = cur < n_cached;
-                    if (in_lds) {
-                        typedef const pool_u4 __attribute__((address_space(3)))* lds_words;
-                        const lds_words q = (lds_words)&L.nodes[cur * 5];
-                        v0 = q[0]; v1 = q[1]; v2 = q[2]; v3 = q[3];
-                    }
-                    __asm__ volatile("" ::: "memory");
-                    if (!in_lds) {
-                        typedef const pool_u4 __attribute__((address_space(1)))* mem_words;
-                        const mem_words q = (mem_words)(nodes + cur);
-                        v0 = q[0]; v1 = q[1]; v2 = q[2]; v3 = q[3];
-                    }
-                    const uint4 w0 = make_uint4(v0.x, v0.y, v0.z, v0.w), w1 = make_uint4(v1.x, v1.y, v1.z, v1.w), w2 = make_uint4(v2.x, v2.y, v2.z, v2.w),
-                                w3 = make_uint4(v3.x, v3.y, v3.z, v3.w);
-                    const CwHits h = cw_step_words(w0, w1, w2, w3, rf, limit);
-#else
-                    const CwHits h = cw_step(nodes + cur, rf, limit);        // (a global load: a pointer that may be LDS or memory is a flat one)
-#endif
-
-                    junk += pf; pf = 0;
-#if MCPT_POOL_FASTPUSH
+                    const CwHits h = cw_step(nodes + cur, rf, limit);
                     // The children come back sorted with the culled ones last: n hits, the n - 1 farther ones go on the stack, farthest
                     // first.  When every lane's pushes stay in the LDS part of its stack (nine steps in ten) they are three predicated
                     // stores at computed positions -- no branch per push, none between LDS and the spill area.
@@ -426,26 +307,17 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                         if (h.ref[2] != MCPT_FAST_EMPTY) { st_put(sp, k, h.ref[2]); sp++; }
                         if (h.ref[1] != MCPT_FAST_EMPTY) { st_put(sp, k, h.ref[1]); sp++; }
                     }
-#else
-                    if (h.ref[3] != MCPT_FAST_EMPTY) { st_put(sp, k, h.ref[3]); sp++; }
-                    if (h.ref[2] != MCPT_FAST_EMPTY) { st_put(sp, k, h.ref[2]); sp++; }
-                    if (h.ref[1] != MCPT_FAST_EMPTY) { st_put(sp, k, h.ref[1]); sp++; }
-#endif
                     int nxt = h.ref[0];
-#if MCPT_POOL_FASTPUSH
                     {
                         const bool pop = nxt == MCPT_FAST_EMPTY && sp > 0;
                         if (pop) sp--;
                         if (!__ballot(pop && sp >= SCAP)) { if (pop) { nxt = L.stack[(sp * KT + k) * 64 + lane]; __asm__ volatile("" : "+v"(nxt)); } }      // (an LDS read, not a flat one)
                         else if (pop) nxt = st_get(sp, k);
                     }
-#else
-                    if (nxt == MCPT_FAST_EMPTY && sp > 0) { sp--; nxt = st_get(sp, k); }
-#endif
                     const bool node = nxt >= 0, none = nxt == MCPT_FAST_EMPTY;
                     const int ref = -1 - nxt;
                     const int first = node ? nxt : ref >> 4, cnt = (ref & 7) + 1;
-                    if (!none) { touch_next(node, first, cnt); L.cur[idx] = first; }
+                    if (!none) L.cur[idx] = first;
                     spf = (spf & 0xff00) | sp | ((!node && !none) ? cnt << 16 : 0);
                     L.spf[idx] = spf;
                     nc = node ? C_INNER : (none ? C_FIN : C_LEAF);
@@ -463,43 +335,17 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 const float limit = a4.limit, margin = margin_of(of, a4);
                 unsigned int surv = 0;
                 w.tris += cnt;
-#if MCPT_PRE_TEST
                 if (!pre) surv = (1u << cnt) - 1u;
                 else {
                     Ray r; r.o = mk(a0.ox, a0.oy, a1.oz); r.d = mk(a1.dx, a2.dy, a2.dz);
                     const PreRay pr = make_pre_ray(F, r, of, margin);
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-                    for (int k0 = 0; k0 < cnt; k0 += MCPT_PRE_UNROLL) {
-#pragma unroll
-                        for (int j = 0; j < MCPT_PRE_UNROLL; j++) {
-                            const int kk = k0 + j;
-                            const bool rej = tri_pre_reject(pre + cur + kk, pr, limit);
-                            if (kk < cnt && !rej) surv |= 1u << kk;
-                        }
-                    }
-                    junk += pf; pf = 0;
+                    surv = leaf_survivors(pre, cur, cnt, pr, limit);
 #ifdef MCPT_PRE_CHECK
-                    const double bt = L.best_t[idx];
-                    const bool found = (spf0 & F_FOUND) != 0;
-                    for (int kk = 0; kk < cnt; kk++) {
-                        if ((surv >> kk) & 1u) continue;
-                        V3 pc;
-                        if (tri_hit(tris + cur + kk, r, pc)) {
-                            const double tc = (pc.x - r.o.x) / r.d.x;
-                            if (tc > 0.0 && (!found || tc <= bt * (1.0 + 0x1p-40))) { w.pre_wrong++; surv |= 1u << kk; }
-                        }
-                    }
+                    const unsigned int wrong = leaf_wrongly_rejected(tris, cur, cnt, surv, r, (spf0 & F_FOUND) != 0, L.best_t[idx]);
+                    w.pre_wrong += (unsigned int)__popc(wrong); surv |= wrong;
 #endif
                 }
-#else
-                surv = (1u << cnt) - 1u;
-#endif
-                if (surv) {
-#if MCPT_POOL_PREFETCH
-                    { const DTri* tn = tris + cur + (__ffs((int)surv) - 1); MCPT_TOUCH(tn); MCPT_TOUCH(reinterpret_cast<const char*>(tn) + 64); }
-#endif
-                    L.spf[idx] = (spf0 & 0xffff) | ((int)surv << 16); nc = C_EXACT;
-                }
+                if (surv) { L.spf[idx] = (spf0 & 0xffff) | ((int)surv << 16); nc = C_EXACT; }
                 else nc = pop_next(idx, k, spf0);
             }
         } else if (c == C_EXACT) {
@@ -519,7 +365,6 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 const bool found = (spf & F_FOUND) != 0;
                 V3 p;
                 const bool hit = tri_hit(tr, r, p);
-                junk += pf; pf = 0;
                 if (hit) {
                     const double ta = (p.x - r.o.x) * fast_rcp(r.d.x);
                     if (ta > 0.0) {
@@ -531,17 +376,12 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                             const PoolRcp a4 = L.rcp[idx];
                             const float of[3] = {(float)a0.ox, (float)a0.oy, (float)a1.oz};
                             L.best_t[idx] = ta; L.best_leaf[idx] = ti;
-                            L.rcp[idx].limit = __double2float_ru((ta + ta * 0x1p-47) + (double)margin_of(of, a4));
+                            L.rcp[idx].limit = lead_limit(ta, margin_of(of, a4));
                             const bool own = own_box_hit(tr, r, mk(fast_rcp(r.d.x), fast_rcp(r.d.y), fast_rcp(r.d.z)));
                             spf = (spf & ~F_OWNFAIL) | F_FOUND | (own ? 0 : F_OWNFAIL);
                         } else if (!(ta > best_t + band)) {
-                            // (the leader's hit point again: the first two lines of the reference's test on its triangle, same operands, same bits)
                             const DTri* lt = tris + L.best_leaf[idx];
-                            const V3 lv1 = ld3(lt->v1), ln = ld3(lt->n);
-                            const double tl = dot(lv1 - r.o, ln) / dot(ln, r.d);
-                            const double old_px = (r.o + r.d * tl).x;
-                            const double t_new = (p.x - r.o.x) / r.d.x, t_old = (old_px - r.o.x) / r.d.x;
-                            if (t_new < t_old || (t_new == t_old && tr->leaf < lt->leaf)) {
+                            if (tie_prefers_new(r, p.x, hit_point(lt, r).x, tr, lt)) {      // (the leader's hit point is formed again)
                                 L.best_t[idx] = ta; L.best_leaf[idx] = ti;
                                 const bool own = own_box_hit(tr, r, mk(fast_rcp(r.d.x), fast_rcp(r.d.y), fast_rcp(r.d.z)));
                                 spf = (spf & ~F_OWNFAIL) | (own ? 0 : F_OWNFAIL);
@@ -550,9 +390,6 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                     }
                 }
                 if (surv) {
-#if MCPT_POOL_PREFETCH
-                    { const DTri* tn = tris + cur + (__ffs(surv) - 1); MCPT_TOUCH(tn); MCPT_TOUCH(reinterpret_cast<const char*>(tn) + 64); }
-#endif
                     spf = (spf & 0xffff) | (surv << 16);
                     L.spf[idx] = spf; nc = C_EXACT;
                 }
@@ -641,11 +478,8 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                         if (!(mode == P_ADOPTED && folded)) T = after_bounce(T, ldp(RD_W));
                         // the hit point: the first two lines of the reference's triangle test on the ray that is still in its slot
                         const PoolOxy b0 = pool_ld16(&L.oxy[bidx]); const PoolOzDx b1 = pool_ld16(&L.ozdx[bidx]); const PoolDyz b2 = pool_ld16(&L.dyz[bidx]);
-                        const V3 ro = mk(b0.ox, b0.oy, b1.oz), bd = mk(b1.dx, b2.dy, b2.dz);
-                        const DTri* tr = S.tris + hl;
-                        const V3 v1 = ld3(tr->v1), n = ld3(tr->n);
-                        const double t = dot(v1 - ro, n) / dot(n, bd);
-                        p = ro + bd * t; dir = neg(bd); in_type = bt & 7; depth++; leaf = hl;
+                        Ray br; br.o = mk(b0.ox, b0.oy, b1.oz); br.d = mk(b1.dx, b2.dy, b2.dz);
+                        p = hit_point(S.tris + hl, br); dir = neg(br.d); in_type = bt & 7; depth++; leaf = hl;
                         at_vertex = true;
                     } else if (PP::kEnv && bt >= 0) {                       // the bounce ray left the scene
                         const V3 Tn = (mode == P_ADOPTED && folded) ? T : after_bounce(T, ldp(RD_W));
@@ -796,18 +630,11 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                         if (spf & F_OWNFAIL) ambiguous = true;              // (tested when the triangle became the leader)
                         h.leaf = tr->leaf;
                         h.mat = tr->material;
-                        // the hit point: the first two lines of intersect(Ray&, Face&, Vertex&) again -- same operands, same bits as when the
-                        // triangle was tested; t_k is divided out of its x (pathTracing.cpp:347)
-                        const V3 v1 = ld3(tr->v1), n = ld3(tr->n);
-                        const double t = dot(v1 - r.o, n) / dot(n, r.d);
-                        h.p = r.o + r.d * t;
+                        h.p = hit_point(tr, r);                             // t_k is divided out of its x (pathTracing.cpp:347)
                         h.t = (h.p.x - r.o.x) / r.d.x;
                     }
-                    if (ambiguous) {
-                        const unsigned int at = atomicAdd(&queue->slow_count, 1u);
-                        if (at < slow_cap) slow_list[at] = slot;
-                        else queue->redo_all = 1u;
-                    } else src.store(slot, found, h);
+                    if (ambiguous) defer_ray(queue, slow_list, slow_cap, slot, true);
+                    else src.store(slot, found, h);
                 }
             }
             bool got = false;
@@ -815,14 +642,11 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
             if (!queue_empty && next >= range_end) {
                 unsigned long long tk = 0;
                 if (lane == 0) tk = atomicAdd(&queue->head, 1ull);
-                const long long ticket = uni((long long)tk);
-                const long long size = ticket < big_tickets ? chunk : small;
-                next = ticket < big_tickets ? ticket * chunk : big_tickets * chunk + (ticket - big_tickets) * small;
-                range_end = next + size < total ? next + size : total;
+                const bool in_range = ticket_range(ts, uni((long long)tk), next, range_end);
 #ifdef MCPT_POOL_DEBUG
                 d_tickets++;
 #endif
-                if (next >= total) {
+                if (!in_range) {
                     queue_empty = true;
                     unsigned int before = 0;
                     if (lane == 0) before = __hip_atomic_fetch_add(&L.dry, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -836,17 +660,13 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 Ray nr; nr.o = mk(0, 0, 0); nr.d = mk(1, 1, 1);
                 const bool valid = lane < avail && src.fetch(next + lane, nr);
                 const bool ok = valid && fast_path_ok(F, nr);
-                junk += pf; pf = 0;
                 const unsigned long long V = __ballot(ok);
                 const int n_ok = __popcll(V);
                 const int rank_ok = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(V >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)V, 0u));
                 int used = avail;                // source slots consumed by this step
                 if (n_ok > n_have) used = __ffsll((long long)__ballot(ok && rank_ok == n_have - 1));
                 used = uni(used);
-                if (valid && !ok && lane < used) {      // a ray the fast walk may not take
-                    const unsigned int at = atomicAdd(&queue->slow_count, 1u);
-                    if (at < slow_cap) slow_list[at] = next + lane;
-                }
+                if (valid && !ok && lane < used) defer_ray(queue, slow_list, slow_cap, next + lane, false);      // a ray the fast walk may not take
                 if (ok && rank_ok < n_have) L.tbl[wave * 64 + rank_ok] = lane;
                 const int rank_need = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(hv >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)hv, 0u));
                 got = have && rank_need < n_ok;
@@ -865,7 +685,6 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                     L.best_t[idx] = 0;
                     L.cur[idx] = 0; L.best_leaf[idx] = -1; L.spf[idx] = F_RAY;
                     L.q[idx] = (unsigned int)(next + from);
-                    MCPT_TOUCH(nodes);
                     nc = C_INNER;
                 }
                 next += used;
@@ -888,15 +707,10 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
 #ifdef MCPT_POOL_DEBUG
         { const unsigned long long tn = __builtin_amdgcn_s_memtime(); d_cyc[c] += tn - d_t; d_t = tn; }
 #endif
-#if MCPT_POOL_STICKY
-        if (have && c == C_INNER && nc == C_INNER) { keep = true; keep_k = k; nc = C_DEAD; }      // (not filed: it stays with this lane)
-#endif
         if (have && nc != C_DEAD)
             __hip_atomic_fetch_or(&L.cls[nc * 64 + lane], 1u << k, MCPT_POOL_FILE_ORDER, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
-#undef MCPT_TOUCH
-    junk += pf;
-    if (lane == 0) { w.nodes += c_nodes + (junk == 0x9e3779b9u ? 1u : 0u); w.rays += c_rays; w.exact += c_exact; }
+    if (lane == 0) { w.nodes += c_nodes; w.rays += c_rays; w.exact += c_exact; }
 #ifdef MCPT_POOL_DEBUG
     if constexpr (PP::kPaths) {
         if (lane == 0 && pp.a.ctr) {
@@ -917,7 +731,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
         atomicAdd(&w.dbg[7], (unsigned long long)c_rays);
         for (int i = 0; i < 4; i++) { atomicAdd(&w.dbg[8 + i], d_cs[i]); atomicAdd(&w.dbg[12 + i], d_cl[i]); atomicAdd(&w.dbg[16 + i], d_want[i]); }
         atomicAdd(&w.dbg[20], d_sleep); atomicAdd(&w.dbg[21], d_miss);
-        if (threadIdx.x == 0 && blockIdx.x == 0) { atomicAdd(&w.dbg[4], (unsigned long long)total); atomicAdd(&w.dbg[5], 1ull); }
+        if (threadIdx.x == 0 && blockIdx.x == 0) { atomicAdd(&w.dbg[4], (unsigned long long)ts.total); atomicAdd(&w.dbg[5], 1ull); }
     }
 #endif
 }

@@ -266,8 +266,6 @@ int update_geometry(mcpt_device* d, const double* d_v, int32_t mode, mcpt_update
     DScene& S = d->ds;
     S.fast.cw = d->cw_nodes.get(); S.fast.tris = d->fast_tris.get(); S.fast.pre = d->fast_pre.get();
     S.fast.absmax = absmax; S.fast.enabled = fi.enabled;
-    S.fast.cached = int32_t(std::min<size_t>(size_t(fi.n_nodes), size_t(kFastTopNodes)));
-    if (d->knobs.node_cache >= 0 && d->knobs.node_cache < S.fast.cached) S.fast.cached = d->knobs.node_cache;
     out.ms_hierarchy = ms_since(t0) - out.ms_reference;
 
     // ---- light tables

@@ -45,10 +45,8 @@ bool wf_carve(void* base, size_t bytes, long long cap, int nl, WfState& A, WfSta
 }
 
 // ---------------------------------------------------------------------------------------------- trace kernels
-#ifndef MCPT_KARG_SOURCE
-#define MCPT_KARG_SOURCE 1          /* the trace kernels read WfArgs from the kernarg segment where they need it (wf_ray_source.hpp: WfRaySourceK); 0: held in registers */
-#endif
-// where the second kernel parameter (WfArgs a) of k_wf_trace / k_wf_trace_pool lies in the kernarg segment: explicit arguments are laid
+// The trace kernels read WfArgs from the kernarg segment where they need it (wf_ray_source.hpp: WfRaySourceK) instead of holding it in
+// registers.  Where the second kernel parameter (WfArgs a) of k_wf_trace / k_wf_trace_pool lies in the kernarg segment: explicit arguments are laid
 // out in order at their natural alignment, DScene first
 __device__ __forceinline__ WfArgsKernarg wf_kernarg_args()
 {
@@ -93,11 +91,7 @@ __global__ void __launch_bounds__(256, WAVES) k_wf_trace(DScene S, WfArgs a, Tra
     const long long chunk = wf_chunk(n_paths * (a.nl + 1), min_chunk, max_chunk);
     __shared__ int lds_stack[STACK * 256];
     __shared__ double lds_rays[4 * MCPT_RAYBUF_BYTES / 8];
-#if MCPT_KARG_SOURCE
     WfRaySourceK src; src.ap = wf_kernarg_args(); src.n_paths = n_paths; src.nl = a.nl;
-#else
-    WfRaySource src; src.a = a; src.n_paths = n_paths;
-#endif
     LaneStats ls;
     Work w = {0, 0};
 #ifdef MCPT_PRE_CHECK
@@ -128,13 +122,8 @@ __global__ void __launch_bounds__(NW * 64, 1) k_wf_trace_pool(DScene S, WfArgs a
     if (n_paths <= (long long)a.finish_below) return;
     const long long chunk = wf_chunk(n_paths * (a.nl + 1), min_chunk, max_chunk);
     __shared__ PoolLds<NW, KT, SCAP> L;
-#if MCPT_KARG_SOURCE
     typedef WfRaySourceK Src;
     Src src; src.ap = wf_kernarg_args(); src.n_paths = n_paths; src.nl = a.nl;
-#else
-    typedef WfRaySource Src;
-    Src src; src.a = a; src.n_paths = n_paths;
-#endif
     LaneStats ls;
     Work w = {0, 0};
 #ifdef MCPT_POOL_DEBUG

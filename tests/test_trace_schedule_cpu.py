@@ -3,12 +3,13 @@
 A wave of either engine takes a ticket from the queue head; ticket k < big_tickets is the slot range [k * chunk, (k + 1) * chunk), every
 later ticket MCPT_TAIL_CHUNK slots (or chunk, if smaller), and a wave whose range starts at or past the total stops claiming.  Within its
 range the wave fetches 64 slots at a time.  Restated here:
-- the ticket -> [next, range_end) mapping and the 64-slot batches: csrc/trace_persistent.hpp:85-87 and 150-166 (request), the same
-  in csrc/trace_pool.hpp:175-176 and 809-816;
-- the chunk each launch passes in: wf_chunk (csrc/wavefront.hip:77-83, k_wf_trace and k_wf_trace_pool), persistent_chunk
-  (csrc/wavefront.hip:246-254, the voting engine's closest-hit and primary launches) and the pool engine's closest-hit formula
+- the ticket -> [next, range_end) mapping and the 64-slot batches: make_ticket_schedule and ticket_range
+  (csrc/trace_persistent.hpp:67-83), called from request (csrc/trace_persistent.hpp:217-230) and from the pool engine's refill
+  (csrc/trace_pool.hpp:132 and 640-665);
+- the chunk each launch passes in: wf_chunk (csrc/wavefront.hip:75-81, k_wf_trace and k_wf_trace_pool), persistent_chunk
+  (csrc/wavefront.hip:235-243, the voting engine's closest-hit and primary launches) and the pool engine's closest-hit formula
   (csrc/kernels.hip:457-460);
-- the chunk knobs: csrc/knobs.cpp:84-86 and init_launch_cfg (csrc/wavefront.hip:239-241).
+- the chunk knobs: csrc/knobs.cpp:83-85 and init_launch_cfg (csrc/wavefront.hip:228-230).
 Asserted: the tickets issued until a wave sees next >= total cover [0, total) exactly once and in order, for every total and chunk where
 the mapping has an edge (1..300 slots, around 512, 4096 and 2^20, either side of seven eighths of a multiple of the chunk), and each
 chunk formula stays a multiple of 64 within its bounds.  The GPU side of the same schedule (non-default chunk knobs, one block or many,
@@ -27,7 +28,7 @@ def _c_div(a, b):
 
 
 def ticket_range(ticket, total, chunk):
-    """[next, range_end) of one ticket (trace_persistent.hpp:153-161 / trace_pool.hpp:811-817)"""
+    """[next, range_end) of one ticket (ticket_range, trace_persistent.hpp:77-83)"""
     small = chunk if chunk < TAIL_CHUNK else TAIL_CHUNK
     big_tickets = _c_div(total - _c_div(total, 8), chunk)
     size = chunk if ticket < big_tickets else small
@@ -77,7 +78,7 @@ def pool_closest_chunk(total, gp, min_chunk, max_chunk):
 
 
 def chunk_knobs(min_env, max_env):
-    """knobs.cpp:84-86 (env_ll: outside 64..2^24 the default) then init_launch_cfg's rounding"""
+    """knobs.cpp:83-85 (env_ll: outside 64..2^24 the default) then init_launch_cfg's rounding"""
     def env_ll(v, dflt):
         return dflt if v is None or v < 64 or v > (1 << 24) else v
     lo = env_ll(min_env, 256) // 64 * 64
