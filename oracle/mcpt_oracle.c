@@ -96,6 +96,7 @@ struct orc_scene {
     double area0;            /* total area of light 0: the frozen range of the static u1 (Q1) */
     int walk_mode;           /* ORC_TRACE_* the integrator's rays are walked with (same hits; ALIAS = the reference's visit counts) */
     struct orc_env* env;     /* the environment light (extension): NULL = none or inactive */
+    struct orc_pick* pick;   /* the light pick (extension): NULL = every light at every vertex */
 };
 
 /* ------------------------------------------------------------------ RNG seam (D1) */
@@ -538,6 +539,7 @@ void orc_scene_free(orc_scene* s)
     for (int i = 0; i < s->nl; i++) free(s->l[i].cdf);
     free(s->v); free(s->vn); free(s->vt); free(s->f); free(s->order); free(s->m); free(s->l); free(s->nodes);
     orc_scene_set_environment(s, NULL, 0, 0, 1.0);
+    orc_scene_set_light_pick(s, 0, NULL, NULL, 0, 0, 0.0, NULL, 0);
     free(s);
 }
 
@@ -925,6 +927,143 @@ int orc_env_sample(const orc_scene* s, uint64_t seed, const int32_t* pix, const 
     return 0;
 }
 
+/* ------------------------------------------------------------------ light pick (extension)
+ * include/mcpt.h "light sampling", restated from its text and from the numpy restatements the tests hold the library to
+ * (tests/light_pick_ref.py, tests/light_tree_ref.py) -- not from the product's code.  The table and the tree are GIVEN (those tests
+ * hold them to the library's bit for bit); what is restated here is the draw, the search, the descent and what shade() does with them. */
+typedef struct { double lo[3], hi[3], w; int32_t left, right; } LNode;      /* 64 bytes: light_tree_ref.NODE */
+
+typedef struct orc_pick {
+    int mode;                /* 1: the weighted table, 2: the tree */
+    int n, last; double Z;
+    double *cdf, *inv_pdf;   /* mode 1 */
+    LNode* nodes; int n_nodes;   /* mode 2 */
+    int wrong;               /* 0; 1, 2: deliberately wrong answers for the tests' power checks (orc_scene_set_light_pick_wrong) */
+} Pick;
+
+static void pick_free(Pick* k)
+{
+    if (!k) return;
+    free(k->cdf); free(k->inv_pdf); free(k->nodes); free(k);
+}
+
+int orc_scene_set_light_pick(orc_scene* s, int mode, const double* cdf, const double* inv_pdf, int n, int last, double Z,
+                             const void* nodes, int n_nodes)
+{
+    if (mode == 0) { pick_free(s->pick); s->pick = NULL; return 0; }
+    if (mode == 1) {
+        if (!cdf || !inv_pdf || n != s->nl || n < 1 || last < 0 || last >= n || !(Z > 0)) return -1;
+    } else if (mode == 2) {
+        if (!nodes || s->nl < 1 || n_nodes != 2 * s->nl - 1) return -1;
+        const LNode* q = (const LNode*)nodes;
+        for (int i = 0; i < n_nodes; i++) {          /* children inside the array, leaves name a light */
+            if (q[i].left >= 0 ? (q[i].left >= n_nodes || q[i].right < 0 || q[i].right >= n_nodes) : (~q[i].left >= s->nl)) return -1;
+        }
+    } else return -1;
+    Pick* k = (Pick*)calloc(1, sizeof *k);
+    k->mode = mode;
+    if (mode == 1) {
+        k->n = n; k->last = last; k->Z = Z;
+        k->cdf = (double*)malloc(sizeof(double) * n);
+        k->inv_pdf = (double*)malloc(sizeof(double) * n);
+        memcpy(k->cdf, cdf, sizeof(double) * n);
+        memcpy(k->inv_pdf, inv_pdf, sizeof(double) * n);
+    } else {
+        k->n_nodes = n_nodes;
+        k->nodes = (LNode*)malloc(sizeof(LNode) * n_nodes);
+        memcpy(k->nodes, nodes, sizeof(LNode) * n_nodes);
+    }
+    pick_free(s->pick);
+    s->pick = k;
+    return 0;
+}
+
+int orc_scene_set_light_pick_wrong(orc_scene* s, int wrong)
+{
+    if (!s->pick || wrong < 0 || wrong > 2) return -1;
+    s->pick->wrong = wrong;
+    return 0;
+}
+
+static inline double np_max(double a, double b) { return (a > b) ? a : b; }      /* np.maximum on numbers */
+
+/* light_tree_ref.importance: W / max(1, |c - p|^2, |h|^2), or 0 when the whole box is below the vertex's horizon by more than the margin */
+static double lnode_importance(const LNode* n, vec3 p, vec3 pn)
+{
+    const vec3 c = v3((n->lo[0] + n->hi[0]) * 0.5, (n->lo[1] + n->hi[1]) * 0.5, (n->lo[2] + n->hi[2]) * 0.5);
+    const vec3 h = v3((n->hi[0] - n->lo[0]) * 0.5, (n->hi[1] - n->lo[1]) * 0.5, (n->hi[2] - n->lo[2]) * 0.5);
+    const vec3 d = vsub(c, p);
+    const vec3 a = v3(fabs(pn.x), fabs(pn.y), fabs(pn.z));
+    const double s = ((d.x * pn.x + d.y * pn.y) + d.z * pn.z) + ((h.x * a.x + h.y * a.y) + h.z * a.z);
+    const double pinf = np_max(np_max(fabs(p.x), fabs(p.y)), fabs(p.z));
+    const double cinf = np_max(np_max(fabs(c.x), fabs(c.y)), fabs(c.z));
+    const double hinf = np_max(np_max(h.x, h.y), h.z);
+    const double margin = (1e-9 * ((a.x + a.y) + a.z)) * ((pinf + cinf) + hinf);
+    const double d2 = (d.x * d.x + d.y * d.y) + d.z * d.z;
+    const double h2 = (h.x * h.x + h.y * h.y) + h.z * h.z;
+    const double D = np_max(1.0, np_max(d2, h2));
+    return (s < -margin) ? 0.0 : n->w / D;
+}
+
+/* light_tree_ref.TreeRef.descend for one draw u at the vertex (p, pn): the light, and the probability it was reached with */
+static int tree_descend(const Pick* k, double u, vec3 p, vec3 pn, double* pdf_out)
+{
+    int n = 0;
+    double pdf = 1.0;
+    while (k->nodes[n].left >= 0) {
+        const int l = k->nodes[n].left, r = k->nodes[n].right;
+        double iL = lnode_importance(&k->nodes[l], p, pn), iR = lnode_importance(&k->nodes[r], p, pn);
+        if (iL == 0.0 && iR == 0.0) { iL = k->nodes[l].w; iR = k->nodes[r].w; }     /* both culled: the weights stand in */
+        int left;
+        if (iR == 0.0) left = 1;                      /* forced: the draw and the probability stay as they are */
+        else if (iL == 0.0) left = 0;
+        else {
+            const double pL = iL / (iL + iR);
+            left = u < pL;
+            if (left) { u = u / pL; pdf = pdf * pL; }
+            else { u = (u - pL) / (1.0 - pL); pdf = pdf * (1.0 - pL); }
+        }
+        n = left ? l : r;
+    }
+    *pdf_out = pdf;
+    return ~k->nodes[n].left;
+}
+
+/* the light of the vertex (p, pn) at `depth` of camera sample (pixel, sample), from u = slot 0 of Philox block nl + 3, and the factor
+ * 1 / p its contribution is scaled by: mode 1 the smallest l <= last with u * Z < cdf[l] and the table's quotient, mode 2 the descent */
+static int pick_light(const Pick* k, int nl, uint64_t seed, uint32_t pixel, uint32_t sample, int depth, vec3 p, vec3 pn, double* inv, double* pdf_out)
+{
+    const double u = orc_uniform(seed, pixel, sample, (uint32_t)depth, 4u * ((uint32_t)nl + 3u));
+    if (k->mode == 1) {
+        const double x = u * k->Z;
+        int l = 0;
+        while (l < k->last && !(x < k->cdf[l])) l++;
+        *inv = k->inv_pdf[l];
+        if (pdf_out) *pdf_out = 1.0 / *inv;          /* (the table holds the factors only) */
+        return l;
+    }
+    double pdf;
+    const int l = tree_descend(k, u, p, pn, &pdf);
+    *inv = 1.0 / pdf;
+    if (pdf_out) *pdf_out = pdf;
+    return l;
+}
+
+int orc_light_pick(const orc_scene* s, uint64_t seed, const int32_t* pix, const int32_t* k, int depth, const double* p, const double* pn,
+                   int64_t n, int32_t* out_l, double* out_pdf, double* out_inv)
+{
+    if (!s->pick || depth < 0 || (s->pick->mode == 2 && (!p || !pn))) return -1;
+    for (int64_t i = 0; i < n; i++) {
+        const vec3 P = p ? v3(p[3 * i], p[3 * i + 1], p[3 * i + 2]) : v3(0, 0, 0);
+        const vec3 N = pn ? v3(pn[3 * i], pn[3 * i + 1], pn[3 * i + 2]) : v3(0, 0, 0);
+        double inv, pdf;
+        out_l[i] = pick_light(s->pick, s->nl, seed, (uint32_t)pix[i], (uint32_t)k[i], depth, P, N, &inv, &pdf);
+        if (out_pdf) out_pdf[i] = pdf;
+        if (out_inv) out_inv[i] = inv;
+    }
+    return 0;
+}
+
 /* Refract, MTPC/pathTracing.cpp:13-27 (float cosi / cost2) */
 static int refract_dir(vec3 i, vec3 n, double eta, vec3* out)
 {
@@ -1001,6 +1140,60 @@ static NextRay next_ray(const Ctx* c, int depth, const Hit* p, const Material* m
 }
 
 
+/* One light of shade()'s direct illumination, MTPC/pathTracing.cpp:166-232 (the body of its loop over the lights): light i seen from p,
+ * its four draws from Philox block blk (the reference's loop: blk == i).  sample_mat carries over from call to call as the reference's
+ * sample_face does (a light whose area draw finds no triangle keeps the material of the light before).  Returns 1 and the term the
+ * reference adds to L_dir, or 0 where it adds nothing (the light is behind the surface); one shadow ray either way. */
+static int light_term(Ctx* c, const Hit* p, vec3 kd, int depth, int i, uint32_t blk, int* sample_mat, vec3* out)
+{
+    const orc_scene* s = c->s;
+    const Light* L = &s->l[i];
+    const Material* lm = &s->m[L->material];
+    vec3 xl = v3(0, 0, 0), vn = v3(0, 0, 0);
+    double total_aera; const double* cdf = L->cdf; double* tmp = NULL;
+    if (c->faithful_cost) {          /* rebuild the CDF per call like :177-184 (same values) */
+        tmp = (double*)malloc(sizeof(double) * (lm->nf ? lm->nf : 1));
+        double tot = 0;
+        for (int j = 0; j < lm->nf; j++) { tot += face_area(&s->f[lm->faces[j]]); tmp[j] = tot; }
+        total_aera = tot; cdf = tmp;
+    } else total_aera = L->total_area;
+    /* static u1(0, total_aera of the FIRST light ever processed) -- Q1 */
+    double rnd = U(c, depth, 4u * blk + 0u) * s->area0;
+    for (int j = 0; j < lm->nf; j++) {
+        if (rnd < cdf[j]) {
+            const Face* sf = &s->f[lm->faces[j]];
+            *sample_mat = sf->material;
+            double rnd1 = U(c, depth, 4u * blk + 1u), rnd2 = U(c, depth, 4u * blk + 2u), rnd3 = U(c, depth, 4u * blk + 3u);
+            double p1 = rnd1 / (rnd1 + rnd2 + rnd3), p2 = rnd2 / (rnd1 + rnd2 + rnd3), p3 = rnd3 / (rnd1 + rnd2 + rnd3);
+            xl = vadd(vadd(vmul(sf->v1, p1), vmul(sf->v2, p2)), vmul(sf->v3, p3));
+            vn = vadd(vadd(vmul(sf->vn1, p1), vmul(sf->vn2, p2)), vmul(sf->vn3, p3));
+            break;
+        }
+    }
+    free(tmp);
+    vec3 direction = vnormalize(vsub(xl, p->p));
+    double visibility = 1;
+    RayT rl = { vadd(p->p, vmul(direction, 0.01)), direction };
+    Hit inter;
+    ray_intersect(s, &rl, &inter, s->walk_mode, &c->c);
+    if (c->st) c->st->rays_shadow++;
+    int inter_mat = inter.hit ? s->f[s->order[inter.leaf]].material : -1;
+    if (inter_mat != *sample_mat) visibility = 0;                           /* :213 */
+    if (vdot(direction, p->pn) > 0) {
+        double pdf_light = (double)1 / total_aera;
+        double cos_theta = fabs(vdot(direction, vn) / vnorm(direction) / vnorm(vn));
+        double cos_theta_hat = fabs(vdot(direction, p->pn) / vnorm(direction) / vnorm(p->pn));
+        double dist = std_max(1.0, vnorm(vsub(xl, p->p)));
+        vec3 intensity = vmul(vdiv(vdiv(vmul(vmul(L->radiance, cos_theta), cos_theta_hat), pow(dist, 2)), pdf_light), visibility);
+        double kd_dots = vdot(direction, p->pn);
+        if (kd_dots > 0) {
+            *out = v3(kd.x * intensity.x * kd_dots / ORC_PI, kd.y * intensity.y * kd_dots / ORC_PI, kd.z * intensity.z * kd_dots / ORC_PI);
+            return 1;
+        }
+    }
+    return 0;
+}
+
 /* shade, MTPC/pathTracing.cpp:137-266.  p->leaf identifies p.f. */
 static vec3 shade(Ctx* c, const Hit* p, vec3 dir, int depth)
 {
@@ -1026,52 +1219,20 @@ static vec3 shade(Ctx* c, const Hit* p, vec3 dir, int depth)
 
     /* direct illumination, :166-232 */
     vec3 L_dir = v3(0, 0, 0);
-    int sample_mat = -1;                 /* Face sample_face; (material "" until a triangle is chosen) */
-    for (int i = 0; i < nl; i++) {
-        const Light* L = &s->l[i];
-        const Material* lm = &s->m[L->material];
-        vec3 xl = v3(0, 0, 0), vn = v3(0, 0, 0);
-        double total_aera; const double* cdf = L->cdf; double* tmp = NULL;
-        if (c->faithful_cost) {          /* rebuild the CDF per call like :177-184 (same values) */
-            tmp = (double*)malloc(sizeof(double) * (lm->nf ? lm->nf : 1));
-            double tot = 0;
-            for (int j = 0; j < lm->nf; j++) { tot += face_area(&s->f[lm->faces[j]]); tmp[j] = tot; }
-            total_aera = tot; cdf = tmp;
-        } else total_aera = L->total_area;
-        /* static u1(0, total_aera of the FIRST light ever processed) -- Q1 */
-        double rnd = U(c, depth, 4u * i + 0u) * s->area0;
-        for (int j = 0; j < lm->nf; j++) {
-            if (rnd < cdf[j]) {
-                const Face* sf = &s->f[lm->faces[j]];
-                sample_mat = sf->material;
-                double rnd1 = U(c, depth, 4u * i + 1u), rnd2 = U(c, depth, 4u * i + 2u), rnd3 = U(c, depth, 4u * i + 3u);
-                double p1 = rnd1 / (rnd1 + rnd2 + rnd3), p2 = rnd2 / (rnd1 + rnd2 + rnd3), p3 = rnd3 / (rnd1 + rnd2 + rnd3);
-                xl = vadd(vadd(vmul(sf->v1, p1), vmul(sf->v2, p2)), vmul(sf->v3, p3));
-                vn = vadd(vadd(vmul(sf->vn1, p1), vmul(sf->vn2, p2)), vmul(sf->vn3, p3));
-                break;
-            }
+    if (!s->pick) {                      /* the reference's loop: every light */
+        int sample_mat = -1;             /* Face sample_face; (material "" until a triangle is chosen) */
+        for (int i = 0; i < nl; i++) {
+            vec3 t;
+            if (light_term(c, p, kd, depth, i, (uint32_t)i, &sample_mat, &t)) { L_dir.x += t.x; L_dir.y += t.y; L_dir.z += t.z; }
         }
-        free(tmp);
-        vec3 direction = vnormalize(vsub(xl, p->p));
-        double visibility = 1;
-        RayT rl = { vadd(p->p, vmul(direction, 0.01)), direction };
-        Hit inter;
-        ray_intersect(s, &rl, &inter, s->walk_mode, &c->c);
-        if (c->st) c->st->rays_shadow++;
-        int inter_mat = inter.hit ? s->f[s->order[inter.leaf]].material : -1;
-        if (inter_mat != sample_mat) visibility = 0;                           /* :213 */
-        if (vdot(direction, p->pn) > 0) {
-            double pdf_light = (double)1 / total_aera;
-            double cos_theta = fabs(vdot(direction, vn) / vnorm(direction) / vnorm(vn));
-            double cos_theta_hat = fabs(vdot(direction, p->pn) / vnorm(direction) / vnorm(p->pn));
-            double dist = std_max(1.0, vnorm(vsub(xl, p->p)));
-            vec3 intensity = vmul(vdiv(vdiv(vmul(vmul(L->radiance, cos_theta), cos_theta_hat), pow(dist, 2)), pdf_light), visibility);
-            double kd_dots = vdot(direction, p->pn);
-            if (kd_dots > 0) {
-                L_dir.x += kd.x * intensity.x * kd_dots / ORC_PI;
-                L_dir.y += kd.y * intensity.y * kd_dots / ORC_PI;
-                L_dir.z += kd.z * intensity.z * kd_dots / ORC_PI;
-            }
+    } else if (nl > 0) {                 /* one picked light (extension): its own block, no light before it, its term over its probability */
+        double inv;
+        const int l = pick_light(s->pick, nl, c->seed, c->pixel, c->sample, depth, p->p, p->pn, &inv, NULL);
+        int sample_mat = -1;
+        vec3 t;
+        if (s->pick->wrong == 1 && depth > 0) inv = 1.0;
+        if (light_term(c, p, kd, depth, l, s->pick->wrong == 2 ? 0u : (uint32_t)l, &sample_mat, &t)) {
+            L_dir.x += t.x * inv; L_dir.y += t.y * inv; L_dir.z += t.z * inv;
         }
     }
     if (c->env) {                        /* the environment's light sample (extension): a shadow ray that must leave the scene */

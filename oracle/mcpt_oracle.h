@@ -45,6 +45,10 @@
  * Extension (not in the reference): the environment light of include/mcpt.h, restated from that header's text (orc_scene_set_environment
  * below); pinned by tests/test_env_cpu.py (tables and draws against tests/env_ref.py, closed forms) and held against the GPU by
  * tests/test_gpu_env_oracle.py.  Without an environment every answer and every count is what it was before.
+ * Extension (not in the reference): the light pick of include/mcpt.h (MCPT_LIGHTS_ONE, MCPT_LIGHTS_TREE), restated from that header's
+ * text and tests/light_pick_ref.py / tests/light_tree_ref.py (orc_scene_set_light_pick below); pinned by
+ * tests/test_light_pick_oracle_cpu.py and held against the GPU by tests/test_gpu_light_pick_oracle.py.  Without a pick (the default)
+ * every answer and every count is what it was before.
  */
 #ifndef MCPT_ORACLE_H
 #define MCPT_ORACLE_H
@@ -154,6 +158,28 @@ double orc_scene_set_environment(orc_scene*, const float* rgb, int W, int H, dou
 int orc_env_eval(const orc_scene*, const double* dirs, int64_t n, double* rgb);
 int orc_env_sample(const orc_scene*, uint64_t seed, const int32_t* pix, const int32_t* k, int depth, int64_t n, double* dirs, double* pdf,
                    double* rgb);
+
+/* ---- light pick (extension, not in the reference): include/mcpt.h "light sampling" ----
+ * mode 0 (the default): every light at every vertex, the reference's loop.  mode 1 (MCPT_LIGHTS_ONE): one light per vertex from the
+ * table cdf[n], inv_pdf[n] (1.0 / pdf, 0 for a light of weight 0), last (the last light of non-zero weight), Z (the weights' sum) --
+ * tests/light_pick_ref.PickRef.  mode 2 (MCPT_LIGHTS_TREE): one light per vertex by the descent of the n_nodes = 2 nl - 1 64-byte nodes of
+ * tests/light_tree_ref.TreeRef (lo[3], hi[3], w as doubles, left, right as int32; a leaf holds ~light in both).  The arrays are copied; the
+ * oracle builds neither (tests hold both to the library's own, bit for bit).  Arguments a mode does not use may be NULL / 0.  In modes 1
+ * and 2 orc_sample_radiance and orc_render shade a vertex with ONE light l in place of the loop: u = slot 0 of Philox block nl + 3 at the
+ * vertex's depth; mode 1 the smallest l <= last with u * Z < cdf[l]; mode 2 the descent at the vertex's own (p, pn); the loop's body for
+ * that light alone -- its draws from block l, no light before it to inherit a material from, one shadow ray -- and its term times 1 / p_l.
+ * The environment's sample and the bounce are untouched (the paths are mode 0's).  orc_render_strided / _reference_style are for scenes
+ * without a pick.  0, or -1 on bad arguments (the previous setting is kept). */
+int orc_scene_set_light_pick(orc_scene*, int mode, const double* cdf, const double* inv_pdf, int n, int last, double Z,
+                             const void* nodes, int n_nodes);
+/* FOR THE TESTS' POWER CHECKS ONLY: makes the picking modes answer wrongly -- 1: the factor 1 / p is applied at depth 0 only, 2: the picked
+ * light's four draws come from block 0.  0 (what every orc_scene_set_light_pick leaves) is right.  0, or -1 without a pick. */
+int orc_scene_set_light_pick_wrong(orc_scene*, int wrong);
+/* the pick alone, at vertex `depth` of camera samples (pix[i], k[i]): out_l[n] the light, out_inv[n] the factor shade() scales by, out_pdf[n]
+ * the probability (mode 2: the descent's own, the factor is 1.0 / it; mode 1: 1.0 / the factor -- the table holds no probabilities).  p, pn (n x 3):
+ * the vertices, mode 2 only.  out_pdf / out_inv may be NULL.  0, or -1 without a pick. */
+int orc_light_pick(const orc_scene*, uint64_t seed, const int32_t* pix, const int32_t* k, int depth, const double* p, const double* pn,
+                   int64_t n, int32_t* out_l, double* out_pdf, double* out_inv);
 
 /* ---- output: MTPC/MTPC.cpp:10-33, MTPC/svpng.inc:77-107 ---- */
 void orc_quantize(const double* img, int64_t n, uint8_t* rgb8);

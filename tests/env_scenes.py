@@ -3,7 +3,9 @@ of both the product (mcpt.Scene) and the oracle (oracle_lib.OracleScene), in the
 
 open_scene: an open scene under the sky -- a diffuse floor whose vertex normals are not of unit length and differ per vertex (so the
 interpolated normal is not of unit length either), a Phong plate (Ks 0.8, Ns 200) tilted towards the camera, a glass box (Ni 1.5) and,
-with n_lights = 1, one small emitter facing down.  The upper part of the frame and the rays past the floor's far edge see the sky.  Every
+with n_lights >= 1, one small emitter facing down; n_lights = 2 and 3 add a larger emitter facing down over the left of the floor and a
+larger one standing to the right of the box, facing it -- each its own material and radiance, none smaller than the first (the reference draws
+every light's point over the first light's area: every draw finds a triangle, nothing goes NaN).  The upper part of the frame and the rays past the floor's far edge see the sky.  Every
 kind of environment path is reached: shadow rays that leave the scene and shadow rays that the plate, the box or the emitter block,
 SPECULAR escapes off the plate and the box, TRANSMISSION escapes out of the box, camera rays that miss.
 
@@ -111,8 +113,8 @@ def _write(directory, name, parts, mats, camera, lights=()):
 
 
 def open_scene(directory, name, n_lights, width, height):
-    """Write <directory>/<name>.{obj,mtl,camera}: the open scene with 0 or 1 lights."""
-    assert n_lights in (0, 1)
+    """Write <directory>/<name>.{obj,mtl,camera}: the open scene with 0 to 3 lights."""
+    assert n_lights in (0, 1, 2, 3)
     # the floor: vertex normals of lengths 1.3 .. 2.2, tilted a little each its own way
     floor_n = [(0.1, 1.6, -0.05), (-0.08, 2.2, 0.1), (0.05, 1.3, 0.12), (-0.1, 1.9, -0.07)]
     parts = [("Floor", _quad((-3, 0, 3), (3, 0, 3), (3, 0, -3), (-3, 0, -3), floor_n))]
@@ -128,6 +130,14 @@ def open_scene(directory, name, n_lights, width, height):
         parts.append(("Lamp", _quad((-0.3, 2.2, -0.3), (0.3, 2.2, -0.3), (0.3, 2.2, 0.3), (-0.3, 2.2, 0.3), [(0, -1, 0)] * 4)))
         mats["Lamp"] = ((0, 0, 0), (0, 0, 0), 1, 1)
         lights.append(("Lamp", (6.0, 6.0, 5.0)))
+    if n_lights >= 2:                  # 0.75 x 0.75 (the first lamp is 0.6 x 0.6), lower and to the left
+        parts.append(("Lamp1", _quad((-1.75, 1.9, 0.5), (-1.0, 1.9, 0.5), (-1.0, 1.9, 1.25), (-1.75, 1.9, 1.25), [(0, -1, 0)] * 4)))
+        mats["Lamp1"] = ((0, 0, 0), (0, 0, 0), 1, 1)
+        lights.append(("Lamp1", (1.5, 2.5, 4.0)))
+    if n_lights >= 3:                  # 0.75 x 1.0, upright at x = 2.25, facing -x: the box's right side and the floor under it
+        parts.append(("Lamp2", _quad((2.25, 0.25, -0.5), (2.25, 0.25, 0.5), (2.25, 1.0, 0.5), (2.25, 1.0, -0.5), [(-1, 0, 0)] * 4)))
+        mats["Lamp2"] = ((0, 0, 0), (0, 0, 0), 1, 1)
+        lights.append(("Lamp2", (9.0, 4.0, 1.0)))
     _write(directory, name, parts, mats, ((0, 1.6, 3.6), (0, 0.35, -0.3), (0, 1, 0), 55, width, height), lights)
 
 

@@ -92,6 +92,11 @@ def lib():
         L.orc_env_eval.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_double)]
         L.orc_env_sample.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.c_int64,
                                      C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.orc_scene_set_light_pick.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double,
+                                               C.c_void_p, C.c_int]
+        L.orc_scene_set_light_pick_wrong.argtypes = [C.c_void_p, C.c_int]
+        L.orc_light_pick.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -247,6 +252,47 @@ class OracleScene:
                                 _ptr(pdf, C.c_double), _ptr(rgb, C.c_double)) != 0:
             raise ValueError("oracle: no active environment")
         return dirs, pdf, rgb
+
+    def set_light_pick(self, mode, pick_ref=None, tree_ref=None, wrong=0):
+        """The light pick (an extension of the oracle, include/mcpt.h): mode 0 / None / "all" -- every light at every vertex, the default;
+        1 / "one" -- one light per vertex from the table of pick_ref (light_pick_ref.PickRef); 2 / "tree" -- one light per vertex by the
+        descent of tree_ref's nodes (light_tree_ref.TreeRef).  The oracle builds neither: it takes them as the tests hold them to the library.
+        wrong: 1 or 2 make the oracle's answer WRONG on purpose (1: the factor 1 / p at depth 0 only, 2: the light's draws from block 0), for
+        tests that show a comparison against it has the power to fail; never set otherwise."""
+        mode = {None: 0, "all": 0, "one": 1, "tree": 2}.get(mode, mode)
+        L = lib()
+        if mode == 0:
+            rc = L.orc_scene_set_light_pick(self.h, 0, None, None, 0, 0, 0.0, None, 0)
+        elif mode == 1:
+            cdf = np.ascontiguousarray(pick_ref.cdf, dtype=np.float64)
+            inv = np.ascontiguousarray(pick_ref.inv, dtype=np.float64)
+            rc = L.orc_scene_set_light_pick(self.h, 1, _ptr(cdf, C.c_double), _ptr(inv, C.c_double), cdf.shape[0], int(pick_ref.last),
+                                            float(pick_ref.Z), None, 0)
+        elif mode == 2:
+            nodes = np.ascontiguousarray(tree_ref.nodes)
+            assert nodes.dtype.itemsize == 64
+            rc = L.orc_scene_set_light_pick(self.h, 2, None, None, 0, 0, 0.0, nodes.ctypes.data_as(C.c_void_p), nodes.shape[0])
+        else:
+            raise ValueError("oracle: light pick mode 0, 1 or 2")
+        if rc != 0:
+            raise ValueError("oracle: bad light pick")
+        if wrong and L.orc_scene_set_light_pick_wrong(self.h, int(wrong)) != 0:
+            raise ValueError("oracle: wrong = 1 or 2 goes with a picking mode")
+
+    def light_pick(self, seed, pix, k, depth, p=None, pn=None):
+        """the oracle's pick alone at vertex `depth` of camera samples (pix[i], k[i]) -- at the vertices (p[i], pn[i]) under the tree:
+        lights (n,) int32, probabilities (n,), the factors 1 / p the shading scales by (n,)"""
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        n = pix.shape[0]
+        if p is not None:
+            p = np.ascontiguousarray(p, dtype=np.float64).reshape(n, 3)
+            pn = np.ascontiguousarray(pn, dtype=np.float64).reshape(n, 3)
+        light, pdf, inv = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n)
+        if lib().orc_light_pick(self.h, seed, _ptr(pix, C.c_int32), _ptr(k, C.c_int32), int(depth), _ptr(p, C.c_double), _ptr(pn, C.c_double),
+                                n, _ptr(light, C.c_int32), _ptr(pdf, C.c_double), _ptr(inv, C.c_double)) != 0:
+            raise ValueError("oracle: the scene does not pick (or the tree needs vertices)")
+        return light, pdf, inv
 
 
 def _render_strided(self, spp, seed, row_stride, faithful_cost=True, nthreads=0, stats=None, img=None):
