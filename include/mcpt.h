@@ -364,6 +364,44 @@ int mcpt_progressive_aovs(mcpt_progressive*, int32_t* material, double* depth, d
 int mcpt_progressive_denoise(mcpt_progressive*, const mcpt_denoise_params*, double* img);
 int mcpt_progressive_denoise_device(mcpt_progressive*, const mcpt_denoise_params*, double* d_img, void* stream);
 
+/* ---- sample AOVs and the filter they guide (since the guided-denoising change): guides averaged over each pixel's camera samples ---- */
+/* Under an active lens the first-hit AOVs above show a picture the frame does not: one hard surface per pixel where the frame mixes two at
+ * an antialiased silhouette, razor-sharp edges inside the blur of what is out of focus, a miss where most of a pixel's samples hit.
+ * mcpt_progressive_sample_aovs: for G camera samples per owned pixel (samples = G, 1 <= G <= the handle's spp; 0: min(spp,
+ * MCPT_GUIDE_SAMPLES)) sample k = 0 .. G-1 gets the frame's own camera ray of (pixel, k) -- the handle's lens and seed, what mcpt_camera_rays
+ * returns -- traced for its closest hit on the device's current walk and engine.  A sample is a MISS, an EMITTER hit (the hit material is a
+ * light) or a SURFACE hit; a surface hit contributes its t, the diffuse colour kd and the shading normal pn of the first-hit AOVs, pn divided
+ * by its length sqrt((x x + y y) + z z) (a zero normal contributes 0).  Per pixel, summed in k order in fp64 without contraction by one GPU
+ * lane (no atomics):
+ *   counts : 3 int32 per pixel, ns (surface), ne (emitter), nm (miss); ns + ne + nm = G.
+ *   depth  : sum t / ns;   albedo : sum kd / ns per channel;   normal : sum pn^ / ns per component, not renormalised.  All 0 when ns == 0.
+ * W*H*3 int32 / W*H / W*H*3 / W*H*3 doubles, each pointer may be NULL; pixels not owned keep the caller's values.  Kept with the handle per
+ * G: a call with another G computes them again.  They depend on the lens, the seed and G, not on the samples rendered.  Without an active
+ * lens the G rays of a pixel coincide and the AOVs are the first-hit ones (counts (G,0,0), (0,G,0) or (0,0,G)).
+ * mcpt_progressive_denoise_guided: the filter of mcpt_progressive_denoise guided by them.  The first struct is that call's, with its rules
+ * and defaults; mcpt_guide_params adds G and sigma_a (NULL or all 0: the defaults).  MCPT_ERR_ARG: samples outside 0..spp, reserved != 0,
+ * sigma_a negative or not finite, whatever mcpt_progressive_denoise refuses (done < 2 among it), a handle under a motion (both calls).
+ * Biased like that filter; reads the handle and never writes what the other calls return.  In fp64 without contraction, sums in the
+ * order written:
+ *   filtered : p is a FILTERED pixel when it is owned, ns_p > 0 and ne_p == 0.  Every other owned pixel is output bit for bit as the
+ *              estimate and is never a neighbour; pixels not owned are not written.
+ *   demodulate: cov = ns / G; m_c = max(cov * albedo_c, 0.01); e_c = c_c / m_c; v_p = sum_c ((w_c * w_c) * se2_c) / (m_c * m_c); c, se2,
+ *              w and lum as in mcpt_progressive_denoise.
+ *   n^_p     : the normal AOV divided by its length sqrt((n_x n_x + n_y n_y) + n_z n_z); a zero normal stays 0.  t_p: the depth AOV.
+ *   iteration i = 0 .. K-1, step s = 2^i: g_p, the taps, h, b, N_pq, D_pq, L_pq, e'_p and v'_p as in mcpt_progressive_denoise, except
+ *     that a window entry or tap counts when q is inside the frame and a filtered pixel (no material is compared), and
+ *     w_pq = ((h[dx] h[dy]) N_pq) exp((-D_pq - L_pq) - A_pq),
+ *     A_pq = ((|m_q0 - m_p0| + |m_q1 - m_p1|) + |m_q2 - m_p2|) / sigma_a, 0 at the centre tap.
+ *   output   : m_c e_c after K iterations; K = 0: the estimate itself, bit for bit.
+ * Defaults: G = min(spp, MCPT_GUIDE_SAMPLES), sigma_a = MCPT_DENOISE_SIGMA_A.  The same bits on any MI355X, on every call, for any pass
+ * schedule that reaches the same state, under every trace engine. */
+#define MCPT_GUIDE_SAMPLES     16
+#define MCPT_DENOISE_SIGMA_A   0.2
+typedef struct { int32_t samples, reserved; double sigma_a; } mcpt_guide_params;   /* 0 = default; reserved must be 0 */
+int mcpt_progressive_sample_aovs(mcpt_progressive*, int32_t samples, int32_t* counts3, double* depth, double* normal, double* albedo);
+int mcpt_progressive_denoise_guided(mcpt_progressive*, const mcpt_denoise_params*, const mcpt_guide_params*, double* img);
+int mcpt_progressive_denoise_guided_device(mcpt_progressive*, const mcpt_denoise_params*, const mcpt_guide_params*, double* d_img, void* stream);
+
 /* ---- camera lens (since the lens change; the reference has a pinhole and one primary ray per pixel) ---- */
 /* The reference traces one primary ray per pixel, through the pixel's corner, and gives it to all N samples (pathTracing.cpp:297-308), so
  * every frame is aliased and nothing is out of focus.  A lens set on a device gives every camera sample (pixel, k) a camera ray of its own.
@@ -384,8 +422,9 @@ int mcpt_progressive_denoise_device(mcpt_progressive*, const mcpt_denoise_params
  * mcpt_sample_radiance, mcpt_multi_* and progressive / adaptive handles trace a camera ray per sample, and rays_primary counts those rays.
  * A progressive handle takes the device's lens when it is created (a later set_lens leaves it as it is).  Per pixel the handle counts the
  * samples whose camera ray hit something; "the pixel's primary ray missed" (noise sums, the adaptive rule's immediate stop, the zero pixels
- * of the fold) then means: that count is 0.  With a pinhole the count is 0 or `done`, which is the rule above.  AOVs stay those of the
- * pixel's unjittered pinhole ray, and the denoiser's pass-through rule is unchanged (guides for depth of field are not modelled).
+ * of the fold) then means: that count is 0.  With a pinhole the count is 0 or `done`, which is the rule above.  The first-hit calls
+ * (mcpt_progressive_aovs, mcpt_progressive_denoise) keep the guides of the pixel's unjittered pinhole ray and their pass-through rule; guides
+ * that follow the lens are the sample AOVs above (mcpt_progressive_sample_aovs, mcpt_progressive_denoise_guided).
  * MCPT_LENS_PER_SAMPLE alone traces a camera ray per sample although all rays of a pixel coincide: the same frame, bit for bit, through the
  * per-sample route (an A/B and test seam).  Errors (MCPT_ERR_ARG): unknown flag bits, reserved != 0, aperture negative or not finite,
  * focus_distance not finite.  With a NULL device and valid arguments: MCPT_ERR_NO_DEVICE without a GPU, as the other entry points. */
@@ -577,6 +616,10 @@ int  mcpt_render_scene(const char* path, const char* filename, int32_t spp);
                                         with the defaults; needs N >= 2 */
 #define MCPT_OUT_AOV_PFM     32      /* also write <prefix>-SPP<N>.albedo.pfm, .normal.pfm, .depth.pfm and .material.pfm (mcpt_progressive_aovs;
                                         depth and material -- as a float, -1 for a miss -- in all three channels) as fp32 */
+#define MCPT_OUT_DENOISED_SAMPLES 64  /* also write <prefix>-SPP<N>.denoised-samples.png (and .denoised-samples.pfm with MCPT_OUT_PFM):
+                                        mcpt_progressive_denoise_guided with all defaults; needs N >= 2 */
+#define MCPT_OUT_SAMPLE_AOV_PFM  128  /* also write <prefix>-SPP<N>.s-albedo.pfm, .s-normal.pfm, .s-depth.pfm (in all three channels) and
+                                        .coverage.pfm (ns/G, ne/G, nm/G): mcpt_progressive_sample_aovs with the default G, as fp32 */
 typedef struct {
     uint64_t seed;
     int32_t  device;            /* HIP ordinal */
@@ -600,7 +643,8 @@ typedef struct {
      * or at N.  A frame stopped at k < N samples is written as <prefix>-SPP<k>.png (the estimate of mcpt_progressive_image); at N it is
      * the plain call's frame, byte for byte.  With a checkpoint or num_devices != 0 these return MCPT_ERR_ARG.  MCPT_OUT_DENOISED and
      * MCPT_OUT_AOV_PFM (since the denoising change) also make the frame progressive, under the same conditions; the plain .png stays
-     * byte for byte what it is without them. */
+     * byte for byte what it is without them.  So do MCPT_OUT_DENOISED_SAMPLES and MCPT_OUT_SAMPLE_AOV_PFM (since the guided-denoising
+     * change), with the same refusals; MCPT_OUT_DENOISED keeps writing the first-hit-guided frame, lens or not. */
     double   noise_target;      /* 0 = none */
     double   time_budget_s;     /* 0 = none */
     /* since the adaptive-sampling change (mcpt_render_scene_opts only).  adaptive_min_spp > 0: an adaptive frame

@@ -76,6 +76,11 @@ class DenoiseParams(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("reserved", C.c_int32), ("sigma_l", C.c_double), ("sigma_z", C.c_double)]
 
 
+class GuideParams(C.Structure):
+    """mcpt_guide_params: the sample AOVs' count and the albedo sigma of mcpt_progressive_denoise_guided (0 = the default)"""
+    _fields_ = [("samples", C.c_int32), ("reserved", C.c_int32), ("sigma_a", C.c_double)]
+
+
 class Lens(C.Structure):
     """mcpt_lens: pixel-area jitter and a thin-lens aperture (mcpt_device_set_lens); all zero = the reference's pinhole"""
     _fields_ = [("flags", C.c_int32), ("reserved", C.c_int32), ("aperture", C.c_double), ("focus_distance", C.c_double)]
@@ -151,6 +156,7 @@ EXPORTS = [
     "mcpt_progressive_image_device", "mcpt_progressive_next_pass", "mcpt_progressive_free",
     "mcpt_progressive_create_adaptive", "mcpt_progressive_active", "mcpt_progressive_active_pixels", "mcpt_progressive_sample_counts",
     "mcpt_progressive_aovs", "mcpt_progressive_denoise", "mcpt_progressive_denoise_device",
+    "mcpt_progressive_sample_aovs", "mcpt_progressive_denoise_guided", "mcpt_progressive_denoise_guided_device",
     "mcpt_multi_create", "mcpt_multi_num_devices", "mcpt_multi_render", "mcpt_multi_render_device", "mcpt_multi_last_timing", "mcpt_multi_collect_stats", "mcpt_multi_free",
     "mcpt_comm_unique_id", "mcpt_comm_create", "mcpt_comm_size", "mcpt_comm_gather_frame", "mcpt_comm_allreduce", "mcpt_comm_free",
     "mcpt_render_scene", "mcpt_render_scene_ex", "mcpt_render_scene_opts",
@@ -256,6 +262,9 @@ def lib():
     L.mcpt_progressive_aovs.argtypes = [P, I32, D, D, D]
     L.mcpt_progressive_denoise.argtypes = [P, C.POINTER(DenoiseParams), D]
     L.mcpt_progressive_denoise_device.argtypes = [P, C.POINTER(DenoiseParams), P, P]
+    L.mcpt_progressive_sample_aovs.argtypes = [P, C.c_int32, I32, D, D, D]
+    L.mcpt_progressive_denoise_guided.argtypes = [P, C.POINTER(DenoiseParams), C.POINTER(GuideParams), D]
+    L.mcpt_progressive_denoise_guided_device.argtypes = [P, C.POINTER(DenoiseParams), C.POINTER(GuideParams), P, P]
     L.mcpt_multi_create.argtypes = [P, I32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(P)]
     L.mcpt_multi_num_devices.argtypes = [P]
     L.mcpt_multi_render.argtypes = [P, C.POINTER(RenderParams), D, C.POINTER(Stats)]

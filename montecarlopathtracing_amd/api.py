@@ -6,7 +6,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -14,6 +14,7 @@ RENDER_DEFAULT, RENDER_MEGAKERNEL = 0, 2
 RENDER_KEEP_STATS, RENDER_PIPELINE = 4, 8
 LOAD_STANDARD_OBJ, LOAD_MTLLIB, LOAD_MORTON_BOUNDS = 1, 2, 4
 OUT_PNG_DEFLATE, OUT_PFM, OUT_ERROR_PFM, OUT_SPP_PFM, OUT_DENOISED, OUT_AOV_PFM = 1, 2, 4, 8, 16, 32
+OUT_DENOISED_SAMPLES, OUT_SAMPLE_AOV_PFM = 64, 128
 BUILD_HOST, BUILD_DEVICE, BUILD_DEVICE_FAST, BUILD_DEVICE_SAH = 0, 1, 2, 3
 UPDATE_REFIT, UPDATE_REBUILD = 0, 1
 # mcpt_fast_info.builder: which builder made the culling hierarchy a device walks
@@ -712,6 +713,27 @@ class Progressive:
         check(lib().mcpt_progressive_denoise(self._h, C.byref(dp), _p(img, C.c_double)))
         return img
 
+    def sample_aovs(self, samples=0):
+        """the AOVs averaged over `samples` camera samples of every owned pixel under the handle's lens (mcpt_progressive_sample_aovs; 0:
+        min(spp, 16)): a dict of numpy arrays, counts [H,W,3] int32 (surface, emitter and miss samples), depth [H,W], normal [H,W,3] (the
+        mean unit normal, not renormalised) and albedo [H,W,3] float64.  Pixels not owned: 0."""
+        h, w = self.device.height, self.device.width
+        out = {"counts": np.zeros((h, w, 3), dtype=np.int32), "depth": np.zeros((h, w)), "normal": np.zeros((h, w, 3)),
+               "albedo": np.zeros((h, w, 3))}
+        check(lib().mcpt_progressive_sample_aovs(self._h, samples, _p(out["counts"], C.c_int32), _p(out["depth"], C.c_double),
+                                                 _p(out["normal"], C.c_double), _p(out["albedo"], C.c_double)))
+        return out
+
+    def denoise_guided(self, iterations=0, sigma_l=0.0, sigma_z=0.0, samples=0, sigma_a=0.0, img=None):
+        """denoise() guided by sample_aovs(samples) instead of the first-hit AOVs (mcpt_progressive_denoise_guided): the filter for frames
+        under a lens.  iterations, sigma_l and sigma_z as in denoise(); samples and sigma_a of 0 are their defaults."""
+        if img is None:
+            img = np.zeros((self.device.height, self.device.width, 3))
+        dp = DenoiseParams(iterations, 0, sigma_l, sigma_z)
+        gp = GuideParams(samples, 0, sigma_a)
+        check(lib().mcpt_progressive_denoise_guided(self._h, C.byref(dp), C.byref(gp), _p(img, C.c_double)))
+        return img
+
     def close(self):
         if getattr(self, "_h", None):
             lib().mcpt_progressive_free(self._h)
@@ -911,6 +933,8 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
     noise_target / time_budget_s / OUT_ERROR_PFM: a progressive frame that may stop at k < N samples (<prefix>-SPP<k>.png).
     adaptive_min_spp > 0: an adaptive frame, noise_target and abs_target its per-pixel targets (OUT_SPP_PFM: the sample-count map).
     OUT_DENOISED / OUT_AOV_PFM: also the denoised frame (.denoised.png, .denoised.pfm with OUT_PFM) / the first-hit AOVs as .pfm files.
+    OUT_DENOISED_SAMPLES / OUT_SAMPLE_AOV_PFM: the frame denoised under the sample AOVs' guidance (.denoised-samples.*) / the sample AOVs
+    (.s-albedo.pfm, .s-normal.pfm, .s-depth.pfm, .coverage.pfm): the guides that follow a lens.
     lens: None (the pinhole), a Lens or a dict of Device.set_lens's arguments; rendered through mcpt_render_scene_lens.
     environment: None, or the path of a colour PFM lat-long map (environment_scale: its scale); rendered through mcpt_render_scene_env.
     motion: None, or a dict of end_obj and end_camera (file paths, either may be missing), shutter = (open, close) and steps: the shutter

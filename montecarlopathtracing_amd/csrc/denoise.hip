@@ -53,11 +53,19 @@ __device__ __forceinline__ double demod_albedo(double a) { return a > 0.01 ? a :
 // ---- prepare: one lane per owned pixel.  The estimate is mcpt_progressive_image's (the float fold at k == N, else the fp64 mean), the
 // squared standard error its progressive_se2 (0 below two samples).  A surface pixel, when the filter iterates, is demodulated into
 // buf: e = c / a, v = sum_c (w_c^2 se2_c / a_c^2) in channel order.  Every other owned pixel -- and every one when there are no
-// iterations -- is the output now, as the estimate.
+// iterations -- is the output now, as the estimate.  SAMPLES (mcpt_progressive_denoise_guided): the guide is the sample AOVs' record, a
+// filtered pixel is demodulated by its m = max(cov * albedo, 0.01) and `albedo` is not read.
+template <bool SAMPLES> struct GuideOf { using type = DenoiseGuide; };
+template <> struct GuideOf<true> { using type = SampleGuide; };
+__device__ __forceinline__ bool filtered(const DenoiseGuide& g) { return g.material >= 0; }
+__device__ __forceinline__ bool filtered(const SampleGuide& g) { return g.filtered != 0; }
+
+template <bool SAMPLES>
 __global__ void __launch_bounds__(256) k_denoise_prepare(const int32_t* __restrict__ pixels, long long n, const double* __restrict__ img,
                                                          const double* __restrict__ mom, int done, const int32_t* __restrict__ cnt, int N,
-                                                         const double* __restrict__ albedo, const DenoiseGuide* __restrict__ guide,
-                                                         int iterations, DenoisePix* __restrict__ buf, double* __restrict__ out)
+                                                         const double* __restrict__ albedo,
+                                                         const typename GuideOf<SAMPLES>::type* __restrict__ guide, int iterations,
+                                                         DenoisePix* __restrict__ buf, double* __restrict__ out)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -66,7 +74,7 @@ __global__ void __launch_bounds__(256) k_denoise_prepare(const int32_t* __restri
     const double* m = mom + (size_t)pix * 6;
     double c[3];
     for (int ch = 0; ch < 3; ch++) c[ch] = k == N ? img[(size_t)pix * 3 + ch] : (k > 0 ? m[ch] / k : 0.0);
-    if (iterations == 0 || guide[pix].material < 0) {
+    if (iterations == 0 || !filtered(guide[pix])) {
         for (int ch = 0; ch < 3; ch++) out[(size_t)pix * 3 + ch] = c[ch];
         return;
     }
@@ -74,7 +82,9 @@ __global__ void __launch_bounds__(256) k_denoise_prepare(const int32_t* __restri
     DenoisePix r;
     double v = 0.0;
     for (int ch = 0; ch < 3; ch++) {
-        const double a = demod_albedo(albedo[(size_t)pix * 3 + ch]);
+        double a;
+        if constexpr (SAMPLES) a = guide[pix].m[ch];
+        else a = demod_albedo(albedo[(size_t)pix * 3 + ch]);
         const double se2 = k >= 2 ? progressive_se2(m[ch], m[3 + ch], k) : 0.0;
         r.e[ch] = c[ch] / a;
         v += ((w[ch] * w[ch]) * se2) / (a * a);
@@ -90,15 +100,20 @@ __global__ void __launch_bounds__(256) k_denoise_prepare(const int32_t* __restri
 //     D = |t_q - t_p| / (sigma_z t_p s max(|dx|, |dy|)) (0 at the centre),   L = |lum(e_q) - lum(e_p)| / (sigma_l sqrt(g) + 1e-10),
 //     e' = sum w e_q / sum w,   v' = sum w^2 v_q / (sum w)^2.
 // The last iteration writes max(albedo, 0.01) * e' to out instead of dst.
-__global__ void __launch_bounds__(256) k_denoise_atrous(int width, int height, int s, const DenoiseGuide* __restrict__ guide,
+// SAMPLES: a window entry or tap counts when it is a filtered pixel inside the frame, whatever its material, and the weight is
+//     w = h[dx] h[dy] * N * exp((-D - L) - A),   A = ((|m_q0 - m_p0| + |m_q1 - m_p1|) + |m_q2 - m_p2|) / sigma_a (0 at the centre);
+// the last iteration writes m * e'.
+template <bool SAMPLES>
+__global__ void __launch_bounds__(256) k_denoise_atrous(int width, int height, int s, const typename GuideOf<SAMPLES>::type* __restrict__ guide,
                                                         const DenoisePix* __restrict__ src, DenoisePix* __restrict__ dst, double sigma_l,
-                                                        double sigma_z, const double* __restrict__ albedo, double* __restrict__ out)
+                                                        double sigma_z, const double* __restrict__ albedo, double* __restrict__ out, double sigma_a)
 {
     const int x = blockIdx.x * 16 + threadIdx.x, y = blockIdx.y * 16 + threadIdx.y;
     if (x >= width || y >= height) return;
     const size_t pix = (size_t)y * width + x;
-    const DenoiseGuide gp = guide[pix];
-    if (gp.material < 0) return;
+    using Guide = typename GuideOf<SAMPLES>::type;
+    const Guide gp = guide[pix];
+    if (!filtered(gp)) return;
     const double k3[3] = {0.25, 0.5, 0.25};
     double sv = 0.0, sk = 0.0;
     for (int dy = -1; dy <= 1; dy++) {
@@ -108,7 +123,8 @@ __global__ void __launch_bounds__(256) k_denoise_atrous(int width, int height, i
             const int qx = x + dx;
             if (qx < 0 || qx >= width) continue;
             const size_t q = (size_t)qy * width + qx;
-            if (guide[q].material != gp.material) continue;
+            if constexpr (SAMPLES) { if (guide[q].filtered == 0) continue; }
+            else { if (guide[q].material != gp.material) continue; }
             const double kw = k3[dx + 1] * k3[dy + 1];
             sv += kw * src[q].v;
             sk += kw;
@@ -127,27 +143,34 @@ __global__ void __launch_bounds__(256) k_denoise_atrous(int width, int height, i
             const int qx = x + s * dx;
             if (qx < 0 || qx >= width) continue;
             const size_t q = (size_t)qy * width + qx;
-            const DenoiseGuide gq = guide[q];
-            if (gq.material != gp.material) continue;
+            const Guide gq = guide[q];
+            if constexpr (SAMPLES) { if (gq.filtered == 0) continue; }
+            else { if (gq.material != gp.material) continue; }
             const DenoisePix cq = src[q];
-            double nw = 1.0, dz = 0.0;
+            double nw = 1.0, dz = 0.0, da = 0.0;
             if (dx != 0 || dy != 0) {
                 const double d = (gp.n[0] * gq.n[0] + gp.n[1] * gq.n[1]) + gp.n[2] * gq.n[2];
                 nw = d > 0.0 ? d : 0.0;
                 for (int j = 0; j < 7; j++) nw = nw * nw;
                 const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
                 dz = fabs(gq.t - gp.t) / (((sigma_z * gp.t) * (double)s) * (double)(ax > ay ? ax : ay));
+                if constexpr (SAMPLES) da = ((fabs(gq.m[0] - gp.m[0]) + fabs(gq.m[1] - gp.m[1])) + fabs(gq.m[2] - gp.m[2])) / sigma_a;
             }
             const double lq = luminance(cq.e[0], cq.e[1], cq.e[2]);
             const double dl = fabs(lq - lp) / lden;
-            const double w = ((h5[dx + 2] * h5[dy + 2]) * nw) * exp(-dz - dl);
+            double w;
+            if constexpr (SAMPLES) w = ((h5[dx + 2] * h5[dy + 2]) * nw) * exp((-dz - dl) - da);
+            else w = ((h5[dx + 2] * h5[dy + 2]) * nw) * exp(-dz - dl);
             sw += w;
             for (int ch = 0; ch < 3; ch++) se[ch] += w * cq.e[ch];
             svv += (w * w) * cq.v;
         }
     }
     if (out) {
-        for (int ch = 0; ch < 3; ch++) out[pix * 3 + ch] = demod_albedo(albedo[pix * 3 + ch]) * (se[ch] / sw);
+        for (int ch = 0; ch < 3; ch++) {
+            if constexpr (SAMPLES) out[pix * 3 + ch] = gp.m[ch] * (se[ch] / sw);
+            else out[pix * 3 + ch] = demod_albedo(albedo[pix * 3 + ch]) * (se[ch] / sw);
+        }
         return;
     }
     DenoisePix r;
@@ -171,14 +194,31 @@ void launch_denoise(const int32_t* d_pixels, long long n_pixels, int width, int 
                     double sigma_z, DenoisePix* d_buf0, DenoisePix* d_buf1, double* d_out, hipStream_t st)
 {
     if (n_pixels <= 0) return;
-    hipLaunchKernelGGL(k_denoise_prepare, dim3(blocks_of(n_pixels, 256)), dim3(256), 0, st, d_pixels, n_pixels, d_img, d_mom, done, d_cnt, N,
+    hipLaunchKernelGGL(k_denoise_prepare<false>, dim3(blocks_of(n_pixels, 256)), dim3(256), 0, st, d_pixels, n_pixels, d_img, d_mom, done, d_cnt, N,
                        d_albedo, d_guide, iterations, d_buf0, d_out);
     const dim3 grid(blocks_of(width, 16), blocks_of(height, 16));
     DenoisePix* buf[2] = {d_buf0, d_buf1};
     for (int i = 0; i < iterations; i++) {
         const bool last = i + 1 == iterations;
-        hipLaunchKernelGGL(k_denoise_atrous, grid, dim3(16, 16), 0, st, width, height, 1 << i, d_guide, buf[i & 1], buf[(i + 1) & 1], sigma_l,
-                           sigma_z, d_albedo, last ? d_out : nullptr);
+        hipLaunchKernelGGL(k_denoise_atrous<false>, grid, dim3(16, 16), 0, st, width, height, 1 << i, d_guide, buf[i & 1], buf[(i + 1) & 1], sigma_l,
+                           sigma_z, d_albedo, last ? d_out : nullptr, 0.0);
+    }
+}
+
+void launch_denoise_guided(const int32_t* d_pixels, long long n_pixels, int width, int height, const double* d_img, const double* d_mom, int done,
+                           const int32_t* d_cnt, int N, const SampleGuide* d_guide, int iterations, double sigma_l, double sigma_z, double sigma_a,
+                           DenoisePix* d_buf0, DenoisePix* d_buf1, double* d_out, hipStream_t st)
+{
+    if (n_pixels <= 0) return;
+    const double* no_albedo = nullptr;
+    hipLaunchKernelGGL(k_denoise_prepare<true>, dim3(blocks_of(n_pixels, 256)), dim3(256), 0, st, d_pixels, n_pixels, d_img, d_mom, done, d_cnt, N,
+                       no_albedo, d_guide, iterations, d_buf0, d_out);
+    const dim3 grid(blocks_of(width, 16), blocks_of(height, 16));
+    DenoisePix* buf[2] = {d_buf0, d_buf1};
+    for (int i = 0; i < iterations; i++) {
+        const bool last = i + 1 == iterations;
+        hipLaunchKernelGGL(k_denoise_atrous<true>, grid, dim3(16, 16), 0, st, width, height, 1 << i, d_guide, buf[i & 1], buf[(i + 1) & 1], sigma_l,
+                           sigma_z, no_albedo, last ? d_out : nullptr, sigma_a);
     }
 }
 

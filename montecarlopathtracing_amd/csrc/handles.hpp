@@ -247,6 +247,8 @@ int light_pick_refresh(mcpt_device* d, const double* areas);
 inline bool lens_active(const mcpt_lens& l) { return l.flags != 0 || l.aperture > 0.0; }
 int lens_check(const mcpt_lens* l);
 int ensure_dirs(mcpt_device* d, hipStream_t st);    // the primary directions, made on first use
+int ensure_pos(mcpt_device* d, hipStream_t st);     // the image-plane points camera_ray starts from (d->pos), made on first use
+mcpt::DLens lens_for(const mcpt_device* d, const mcpt_lens& l);   // lens l on d's camera as the kernels read it (after ensure_pos)
 void counters_to_stats(const mcpt::DCounters& c, mcpt_stats* s, bool print_diag);
 // a += b for every counter of b (max_depth: the larger); ms_trace and ms_total are the caller's to combine
 void add_counts(mcpt_stats& a, const mcpt_stats& b);

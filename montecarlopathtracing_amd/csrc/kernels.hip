@@ -17,7 +17,9 @@
 namespace mcpt {
 
 // ------------------------------------------------------------------------------------------------ kernels
-// mcpt_trace_closest with the reference-shaped walk: one lane per ray.
+// mcpt_trace_closest with the reference-shaped walk: one lane per ray.  LEAF: face receives the leaf index, not the .obj face (the
+// caller shades at the hit: launch_trace_closest_leaf), and no normal is formed.
+template <bool LEAF>
 __global__ void __launch_bounds__(256) k_trace_closest_reference(DScene S, const double* __restrict__ rays, long long n,
                                                        int32_t* __restrict__ face, double* __restrict__ t_out,
                                                        double* __restrict__ p_out, double* __restrict__ pn_out, DCounters* ctr)
@@ -31,8 +33,8 @@ __global__ void __launch_bounds__(256) k_trace_closest_reference(DScene S, const
         const bool ok = trace_closest(S, r, h, w);
         ls.nodes = w.nodes; ls.tris = w.tris; ls.primary = 1;
         V3 pn = mk(0, 0, 0);
-        if (ok) pn = hit_normal(S, h);
-        if (face) face[gid] = ok ? S.tris[h.leaf].face : -1;
+        if (ok && !LEAF) pn = hit_normal(S, h);
+        if (face) face[gid] = ok ? (LEAF ? h.leaf : S.tris[h.leaf].face) : -1;
         if (t_out) t_out[gid] = ok ? h.t : 0.0;
         if (p_out) { p_out[gid * 3] = h.p.x; p_out[gid * 3 + 1] = h.p.y; p_out[gid * 3 + 2] = h.p.z; }
         if (pn_out) { pn_out[gid * 3] = pn.x; pn_out[gid * 3 + 1] = pn.y; pn_out[gid * 3 + 2] = pn.z; }
@@ -551,12 +553,25 @@ void launch_trace_closest(const DScene& S, bool fast, const double* d_rays, long
 {
     if (n <= 0) return;
     if (!fast) {
-        hipLaunchKernelGGL(k_trace_closest_reference, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, d_rays, n, d_face, d_t, d_p, d_pn, ctr);
+        hipLaunchKernelGGL(k_trace_closest_reference<false>, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, d_rays, n, d_face, d_t, d_p, d_pn, ctr);
         return;
     }
     ArrayRaySource src; src.rays = d_rays; src.n = n; src.leaf_out = d_face; src.t_out = d_t; src.p_out = d_p;
     launch_persistent(S, src, n, queue, slow_list, slow_cap, ctr, st, cfg.array_grid, cfg.array_grid_short, cfg);
     hipLaunchKernelGGL(k_finish_hits, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, n, d_face, d_p, d_pn, ctr);
+}
+// The same launch, handing back the leaf of every hit (-1: a miss) instead of its .obj face: what vertex_surface needs.  The walks, and so
+// t and p, are launch_trace_closest's; only the last step (leaf -> face, the hit's normal) is left out.
+void launch_trace_closest_leaf(const DScene& S, bool fast, const double* d_rays, long long n, int32_t* d_leaf, double* d_t, double* d_p,
+                               DCounters* ctr, TraceQueue* queue, long long* slow_list, unsigned int slow_cap, hipStream_t st, const LaunchCfg& cfg)
+{
+    if (n <= 0) return;
+    if (!fast) {
+        hipLaunchKernelGGL(k_trace_closest_reference<true>, dim3(blocks_for(n, 256)), dim3(256), 0, st, S, d_rays, n, d_leaf, d_t, d_p, (double*)nullptr, ctr);
+        return;
+    }
+    ArrayRaySource src; src.rays = d_rays; src.n = n; src.leaf_out = d_leaf; src.t_out = d_t; src.p_out = d_p;
+    launch_persistent(S, src, n, queue, slow_list, slow_cap, ctr, st, cfg.array_grid, cfg.array_grid_short, cfg);
 }
 void launch_pack_pixels(const double* d_frame, const int32_t* d_pixels, long long n_pixels, double* d_out, hipStream_t st)
 {

@@ -42,6 +42,9 @@ void init_launch_cfg_closest(LaunchCfg& cfg);
 void launch_trace_closest(const DScene& S, bool fast, const double* d_rays, long long n, int32_t* d_face, double* d_t, double* d_p,
                           double* d_pn, DCounters* ctr, TraceQueue* queue, long long* slow_list, unsigned int slow_cap, hipStream_t st,
                           const LaunchCfg& cfg);
+// ... with the leaf of every hit in d_leaf (-1: a miss) instead of the .obj face, and no normal: the same walks, t and p
+void launch_trace_closest_leaf(const DScene& S, bool fast, const double* d_rays, long long n, int32_t* d_leaf, double* d_t, double* d_p,
+                               DCounters* ctr, TraceQueue* queue, long long* slow_list, unsigned int slow_cap, hipStream_t st, const LaunchCfg& cfg);
 void launch_pack_pixels(const double* d_frame, const int32_t* d_pixels, long long n_pixels, double* d_out, hipStream_t st);
 void launch_unpack_pixels(const double* d_in, const int32_t* d_pixels, long long n_pixels, double* d_frame, hipStream_t st);
 void launch_primary_dirs(const DCamera& cam, double* d_dirs, hipStream_t st);

@@ -1,5 +1,5 @@
 // C ABI, progressive frames (include/mcpt.h: mcpt_progressive_*): a frame of N samples per pixel in passes, its noise estimate, adaptive
-// frames that stop each pixel on its own error, first-hit AOVs and the denoiser.
+// frames that stop each pixel on its own error, first-hit AOVs, sample AOVs and the denoiser in both its forms.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -63,6 +63,11 @@ struct mcpt_progressive {
     mcpt_lens lens{};                  // the device's lens when the handle was created
     std::shared_ptr<const EnvData> env;   // ... and its environment (null: none)
     DevBuf<int32_t> hitcnt;            // W*H, under an active lens: the samples so far whose camera ray hit (hit = hitcnt > 0)
+    // sample AOVs (mcpt_progressive_sample_aovs: W*H[*3], owned pixels written) of guide_G camera samples per pixel (0: none yet) and the
+    // guide record mcpt_progressive_denoise_guided's taps read; made again when a call asks for another G
+    int guide_G = 0;
+    DevBuf<int32_t> saov_counts; DevBuf<double> saov_depth, saov_normal, saov_albedo;
+    DevBuf<SampleGuide> sguide;
     bool motion = false;               // created on a device with a motion (which stays while the handle lives): passes are cut at its steps
 };
 
@@ -373,6 +378,129 @@ int mcpt_progressive_denoise(mcpt_progressive* h, const mcpt_denoise_params* dp,
     // pageable host buffer: blocking copies either side; pixels this rank does not own keep the caller's values
     return with_device_frames(h->d->stream.get(), size_t(h->d->width) * h->d->height * 3 * sizeof(double), img, nullptr,
                               [&](double* d_out, double*) { return mcpt_progressive_denoise_device(h, dp, d_out, h->d->stream.get()); });
+}
+
+// ---- sample AOVs and the filter they guide (mcpt.h: mcpt_progressive_sample_aovs, mcpt_progressive_denoise_guided)
+static constexpr long long kGuideChunkRays = 1ll << 20;
+
+// samples: the caller's G (0: the default) -> G, or MCPT_ERR_ARG
+static int guide_samples(const mcpt_progressive* h, int32_t samples, int& G)
+{
+    if (samples < 0 || samples > h->p.spp) return fail(MCPT_ERR_ARG, "guide samples outside 0..spp");
+    G = samples > 0 ? samples : std::min<int>(h->p.spp, MCPT_GUIDE_SAMPLES);
+    return MCPT_OK;
+}
+
+// The sample AOVs of G camera samples per owned pixel, in chunks of whole pixels of at most 2^20 rays: the frame's own camera rays
+// (launch_guide_rays), their closest hits on the device's stream and closest-hit workspace, the fold.  Kept per G.
+static int ensure_sample_aovs(mcpt_progressive* h, int G)
+{
+    if (h->guide_G == G) return MCPT_OK;
+    mcpt_device* d = h->d;
+    hipStream_t st = d->stream.get();
+    if (const int rc = ensure_pos(d, st)) return rc;
+    const size_t px = size_t(d->width) * d->height;
+    const int per_chunk = int(std::max<long long>(1, std::min<long long>(kGuideChunkRays / G, std::max<int64_t>(h->n_pixels, 1))));
+    const size_t rays = size_t(per_chunk) * size_t(G);
+    h->guide_G = 0;                                   // what the buffers hold is overwritten from here on
+    DevBuf<double> rays6, t, p;
+    DevBuf<int32_t> leaf;
+    hipError_t e = alloc_once(rays6, rays * 6 * sizeof(double));
+    if (e == hipSuccess) e = alloc_once(t, rays * sizeof(double));
+    if (e == hipSuccess) e = alloc_once(p, rays * 3 * sizeof(double));
+    if (e == hipSuccess) e = alloc_once(leaf, rays * sizeof(int32_t));
+    if (e == hipSuccess) e = alloc_once(h->saov_counts, px * 3 * sizeof(int32_t));
+    if (e == hipSuccess) e = alloc_once(h->saov_depth, px * sizeof(double));
+    if (e == hipSuccess) e = alloc_once(h->saov_normal, px * 3 * sizeof(double));
+    if (e == hipSuccess) e = alloc_once(h->saov_albedo, px * 3 * sizeof(double));
+    if (e == hipSuccess) e = alloc_once(h->sguide, px * sizeof(SampleGuide));
+    // pixels not owned: filtered == 0 in the guide, so that no tap reads them
+    if (e == hipSuccess) e = hipMemsetAsync(h->sguide.get(), 0, px * sizeof(SampleGuide), st);
+    const DLens lens = lens_for(d, h->lens);
+    for (int64_t first = 0; first < h->n_pixels && e == hipSuccess; first += per_chunk) {
+        const int n = int(std::min<int64_t>(per_chunk, h->n_pixels - first));
+        launch_guide_rays(lens, h->p.seed, h->pixels.get(), int(first), n, G, rays6.get(), st);
+        launch_trace_closest_leaf(d->ds, d->trace_mode == MCPT_TRACE_FAST, rays6.get(), (long long)n * G, leaf.get(), t.get(), p.get(), d->aux_ctr.get(),
+                                  d->aux_queue.get(), d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
+        launch_guide_fold(d->ds, h->pixels.get(), int(first), n, G, leaf.get(), t.get(), p.get(), h->saov_counts.get(), h->saov_depth.get(),
+                          h->saov_normal.get(), h->saov_albedo.get(), h->sguide.get(), st);
+        e = hipGetLastError();
+    }
+    const hipError_t es = hipStreamSynchronize(st);   // the chunk buffers go with this call
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return fail(MCPT_ERR_HIP, std::string("sample AOVs: ") + hipGetErrorString(e));
+    h->guide_G = G;
+    return MCPT_OK;
+}
+
+int mcpt_progressive_sample_aovs(mcpt_progressive* h, int32_t samples, int32_t* counts3, double* depth, double* normal, double* albedo)
+{
+    if (!h) return fail(MCPT_ERR_ARG, "null handle");
+    if (h->motion) return fail(MCPT_ERR_ARG, "the frame renders a motion: sample AOVs under a motion are not supported");
+    int G = 0;
+    int rc = guide_samples(h, samples, G);
+    if (rc) return rc;
+    if ((rc = geometry_gate(h->d))) return rc;
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    if ((rc = ensure_sample_aovs(h, G))) return rc;
+    const size_t px = size_t(h->d->width) * h->d->height;
+    // the device arrays whole, then the owned pixels into the caller's (pixels not owned keep the caller's values)
+    auto fetch = [&](const void* src, void* dst, size_t per_pixel) -> int {
+        if (!dst) return MCPT_OK;
+        std::vector<uint8_t> all(px * per_pixel);
+        HIP_TRY(hipMemcpy(all.data(), src, all.size(), hipMemcpyDeviceToHost));
+        for (int32_t pix : h->owned) std::memcpy(static_cast<uint8_t*>(dst) + size_t(pix) * per_pixel, all.data() + size_t(pix) * per_pixel, per_pixel);
+        return MCPT_OK;
+    };
+    if ((rc = fetch(h->saov_counts.get(), counts3, 3 * sizeof(int32_t)))) return rc;
+    if ((rc = fetch(h->saov_depth.get(), depth, sizeof(double)))) return rc;
+    if ((rc = fetch(h->saov_normal.get(), normal, 3 * sizeof(double)))) return rc;
+    return fetch(h->saov_albedo.get(), albedo, 3 * sizeof(double));
+}
+
+static int guided_args(const mcpt_progressive* h, const mcpt_denoise_params* dp, const mcpt_guide_params* gp, int& iterations, double& sigma_l,
+                       double& sigma_z, int& G, double& sigma_a)
+{
+    if (!h) return fail(MCPT_ERR_ARG, "null handle");
+    const mcpt_guide_params z{};
+    const mcpt_guide_params& q = gp ? *gp : z;
+    if (q.reserved != 0) return fail(MCPT_ERR_ARG, "mcpt_guide_params.reserved must be 0");
+    if (!(std::isfinite(q.sigma_a) && q.sigma_a >= 0.0)) return fail(MCPT_ERR_ARG, "sigma_a must be finite and >= 0 (0: the default)");
+    if (const int rc = guide_samples(h, q.samples, G)) return rc;
+    sigma_a = q.sigma_a > 0.0 ? q.sigma_a : MCPT_DENOISE_SIGMA_A;
+    return denoise_args(h, dp, iterations, sigma_l, sigma_z);
+}
+
+int mcpt_progressive_denoise_guided_device(mcpt_progressive* h, const mcpt_denoise_params* dp, const mcpt_guide_params* gp, double* d_img, void* stream)
+{
+    int iterations = 0, G = 0;
+    double sigma_l = 0.0, sigma_z = 0.0, sigma_a = 0.0;
+    int rc = guided_args(h, dp, gp, iterations, sigma_l, sigma_z, G, sigma_a);
+    if (rc) return rc;
+    if (!d_img) return fail(MCPT_ERR_ARG, "null image");
+    if ((rc = geometry_gate(h->d))) return rc;
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    if ((rc = ensure_sample_aovs(h, G))) return rc;
+    const size_t px = size_t(h->d->width) * h->d->height;
+    for (auto& b : h->dn_buf)
+        if (!b) HIP_TRY(b.alloc(px));
+    launch_denoise_guided(h->pixels.get(), h->n_pixels, h->d->width, h->d->height, h->img.get(), h->mom.get(), h->done, h->cnt.get(), h->p.spp, h->sguide.get(),
+                          iterations, sigma_l, sigma_z, sigma_a, h->dn_buf[0].get(), h->dn_buf[1].get(), d_img, static_cast<hipStream_t>(stream));
+    HIP_TRY(hipGetLastError());
+    return MCPT_OK;
+}
+
+int mcpt_progressive_denoise_guided(mcpt_progressive* h, const mcpt_denoise_params* dp, const mcpt_guide_params* gp, double* img)
+{
+    int iterations = 0, G = 0;
+    double sigma_l = 0.0, sigma_z = 0.0, sigma_a = 0.0;
+    int rc = guided_args(h, dp, gp, iterations, sigma_l, sigma_z, G, sigma_a);
+    if (rc) return rc;
+    if (!img) return fail(MCPT_ERR_ARG, "null image");
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    // pageable host buffer: blocking copies either side; pixels this rank does not own keep the caller's values
+    return with_device_frames(h->d->stream.get(), size_t(h->d->width) * h->d->height * 3 * sizeof(double), img, nullptr,
+                              [&](double* d_out, double*) { return mcpt_progressive_denoise_guided_device(h, dp, gp, d_out, h->d->stream.get()); });
 }
 
 int mcpt_progressive_next_pass(int32_t spp, int32_t done, double remaining_s, double s_per_sample)

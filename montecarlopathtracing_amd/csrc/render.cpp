@@ -36,7 +36,7 @@ int lens_check(const mcpt_lens* l)
     if (!std::isfinite(l->focus_distance)) return fail(MCPT_ERR_ARG, "the focus distance must be finite");
     return MCPT_OK;
 }
-static int ensure_pos(mcpt_device* d, hipStream_t st)
+int ensure_pos(mcpt_device* d, hipStream_t st)
 {
     if (!d->pos) {
         HIP_TRY(d->pos.alloc_bytes(std::max<size_t>(size_t(d->width) * d->height * 3 * sizeof(double), 8)));
@@ -48,7 +48,7 @@ static int ensure_pos(mcpt_device* d, hipStream_t st)
 }
 // what the kernels need of a lens: the device's camera frame (device.cpp: create_dscene), x^ = screen_x_dir and y^ = the normalised up as
 // camera_frame forms them, F / l
-static DLens lens_for(const mcpt_device* d, const mcpt_lens& l)
+DLens lens_for(const mcpt_device* d, const mcpt_lens& l)
 {
     DLens c{};
     const Vec3 up = normalized(d->cam_up), dir = d->cam_look_at - d->cam_eye;

@@ -181,10 +181,13 @@ int mcpt_decode_jpeg(const char* file, int32_t* width, int32_t* height, uint8_t*
 // time budget scales the last pass's seconds per sample by the share of pixels the next pass renders (the fixed cost of a pass is not
 // modelled).  counts (may be null) receives the samples of every pixel; denoised (may be null) mcpt_progressive_denoise's image with the
 // defaults; aovs (may be null) the AOV images, every one as W*H*3 doubles (albedo, normal, depth, material: the scalars in all channels).
+// guided (may be null) receives mcpt_progressive_denoise_guided's image with all defaults; saovs (may be null) the sample AOVs of the default G
+// (depth in all channels; coverage: ns/G, ne/G, nm/G).
 struct SceneAovs { std::vector<double> albedo, normal, depth, material; };
+struct SceneSampleAovs { std::vector<double> albedo, normal, depth, coverage; };
 static int render_scene_progressive(mcpt_device* dev, const mcpt_render_params& rp, const mcpt_render_scene_options& o, bool talk, std::vector<double>& img,
                                     std::vector<double>* err, std::vector<int32_t>* counts, std::vector<double>* denoised, SceneAovs* aovs,
-                                    int& rendered, mcpt_stats& local)
+                                    std::vector<double>* guided, SceneSampleAovs* saovs, int& rendered, mcpt_stats& local)
 {
     using clk = std::chrono::steady_clock;
     const bool adaptive = o.adaptive_min_spp > 0;
@@ -242,6 +245,23 @@ static int render_scene_progressive(mcpt_device* dev, const mcpt_render_params& 
         aovs->material.resize(img.size());
         for (size_t i = 0; i < px; i++)
             for (size_t c = 0; c < 3; c++) { aovs->depth[3 * i + c] = depth[i]; aovs->material[3 * i + c] = double(mat[i]); }
+    }
+    if (rc == MCPT_OK && guided) {
+        guided->assign(img.size(), 0.0);
+        rc = mcpt_progressive_denoise_guided(pr, nullptr, nullptr, guided->data());
+    }
+    if (rc == MCPT_OK && saovs) {
+        const size_t px = img.size() / 3;
+        std::vector<int32_t> cnt(px * 3, 0);
+        std::vector<double> depth(px, 0.0);
+        saovs->albedo.assign(img.size(), 0.0);
+        saovs->normal.assign(img.size(), 0.0);
+        rc = mcpt_progressive_sample_aovs(pr, 0, cnt.data(), depth.data(), saovs->normal.data(), saovs->albedo.data());
+        saovs->depth.resize(img.size());
+        saovs->coverage.resize(img.size());
+        const double G = double(std::min<int>(rp.spp, MCPT_GUIDE_SAMPLES));
+        for (size_t i = 0; i < px; i++)
+            for (size_t c = 0; c < 3; c++) { saovs->depth[3 * i + c] = depth[i]; saovs->coverage[3 * i + c] = double(cnt[3 * i + c]) / G; }
     }
     if (rc == MCPT_OK && talk) std::printf("progressive: %d of %d samples per pixel, relative error %.4g\n", mcpt_progressive_done(pr), rp.spp, nz.rel_error);
     mcpt_progressive_free(pr);
@@ -316,18 +336,21 @@ static int render_scene_impl(const char* path, const char* filename, int32_t spp
     const bool talk = !o.quiet;
     // a noise target, a time budget or the error image: the frame goes through a progressive handle (one GPU, no checkpoint)
     const bool adaptive = o.adaptive_min_spp > 0;
-    const bool progressive = o.noise_target > 0 || o.time_budget_s > 0 || (o.output_flags & (MCPT_OUT_ERROR_PFM | MCPT_OUT_DENOISED | MCPT_OUT_AOV_PFM)) ||
+    const bool progressive = o.noise_target > 0 || o.time_budget_s > 0 || (o.output_flags & (MCPT_OUT_ERROR_PFM | MCPT_OUT_DENOISED | MCPT_OUT_AOV_PFM | MCPT_OUT_DENOISED_SAMPLES | MCPT_OUT_SAMPLE_AOV_PFM)) ||
                              adaptive;
     if (o.noise_target < 0 || o.time_budget_s < 0 || std::isnan(o.noise_target) || std::isnan(o.time_budget_s))
         return fail(MCPT_ERR_ARG, "noise_target and time_budget_s must be >= 0");
     if (o.adaptive_min_spp < 0 || o.adaptive_min_spp == 1 || (adaptive && (!(std::isfinite(o.abs_target) && o.abs_target >= 0.0) || std::isinf(o.noise_target))))
         return fail(MCPT_ERR_ARG, "adaptive_min_spp must be 0 or >= 2, the targets finite and >= 0");
     if (progressive && (o.checkpoint || o.num_devices != 0))
-        return fail(MCPT_ERR_ARG, "a noise target, a time budget, an adaptive frame, MCPT_OUT_ERROR_PFM, MCPT_OUT_DENOISED or MCPT_OUT_AOV_PFM renders "
-                                  "on one GPU without a checkpoint");
-    if ((o.output_flags & MCPT_OUT_DENOISED) && spp < 2) return fail(MCPT_ERR_ARG, "MCPT_OUT_DENOISED needs N >= 2 (a variance estimate)");
-    if (shutter && (o.checkpoint || o.num_devices != 0 || adaptive || (o.output_flags & (MCPT_OUT_DENOISED | MCPT_OUT_AOV_PFM))))
-        return fail(MCPT_ERR_ARG, "a motion frame renders on one GPU without a checkpoint, and neither adaptively nor with MCPT_OUT_DENOISED or MCPT_OUT_AOV_PFM");
+        return fail(MCPT_ERR_ARG, "a noise target, a time budget, an adaptive frame, MCPT_OUT_ERROR_PFM, MCPT_OUT_DENOISED, MCPT_OUT_AOV_PFM, "
+                                  "MCPT_OUT_DENOISED_SAMPLES or MCPT_OUT_SAMPLE_AOV_PFM renders on one GPU without a checkpoint");
+    if ((o.output_flags & (MCPT_OUT_DENOISED | MCPT_OUT_DENOISED_SAMPLES)) && spp < 2)
+        return fail(MCPT_ERR_ARG, "MCPT_OUT_DENOISED and MCPT_OUT_DENOISED_SAMPLES need N >= 2 (a variance estimate)");
+    if (shutter && (o.checkpoint || o.num_devices != 0 || adaptive ||
+                    (o.output_flags & (MCPT_OUT_DENOISED | MCPT_OUT_AOV_PFM | MCPT_OUT_DENOISED_SAMPLES | MCPT_OUT_SAMPLE_AOV_PFM))))
+        return fail(MCPT_ERR_ARG, "a motion frame renders on one GPU without a checkpoint, and neither adaptively nor with MCPT_OUT_DENOISED, MCPT_OUT_AOV_PFM or "
+                                  "their sample-guided forms");
     // (the steps are contiguous sample ranges: a frame stopped at k < N would show the first part of the shutter only)
     if (shutter && (o.noise_target > 0 || o.time_budget_s > 0))
         return fail(MCPT_ERR_ARG, "a motion frame renders all its samples: a noise target or a time budget would stop it inside the shutter");
@@ -378,10 +401,13 @@ static int render_scene_impl(const char* path, const char* filename, int32_t spp
     std::vector<int32_t> counts;                         // adaptive frames: the samples of every pixel
     std::vector<double> denoised;
     SceneAovs aovs;
+    std::vector<double> guided;
+    SceneSampleAovs saovs;
     if (progressive) {
         rc = render_scene_progressive(dev, rp, o, talk, img, (o.output_flags & MCPT_OUT_ERROR_PFM) ? &err_img : nullptr, adaptive ? &counts : nullptr,
                                       (o.output_flags & MCPT_OUT_DENOISED) ? &denoised : nullptr, (o.output_flags & MCPT_OUT_AOV_PFM) ? &aovs : nullptr,
-                                      rendered, local);
+                                      (o.output_flags & MCPT_OUT_DENOISED_SAMPLES) ? &guided : nullptr,
+                                      (o.output_flags & MCPT_OUT_SAMPLE_AOV_PFM) ? &saovs : nullptr, rendered, local);
     } else if (!o.checkpoint) {
         rc = many ? mcpt_multi_render(multi, &rp, img.data(), &local) : mcpt_render(dev, &rp, img.data(), &local);
     } else {
@@ -438,6 +464,19 @@ static int render_scene_impl(const char* path, const char* filename, int32_t spp
         if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_AOV_PFM)) {
             const std::pair<const char*, const std::vector<double>*> files[] = {
                 {".albedo.pfm", &aovs.albedo}, {".normal.pfm", &aovs.normal}, {".depth.pfm", &aovs.depth}, {".material.pfm", &aovs.material}};
+            for (const auto& f : files)
+                if (rc == MCPT_OK) rc = mcpt_write_pfm((stem + f.first).c_str(), f.second->data(), s.width, s.height);
+        }
+        if (rc == MCPT_OK && !guided.empty()) {
+            mcpt_quantize_rgb8(guided.data(), int64_t(guided.size()), rgb.data());
+            const std::string dn = stem + ".denoised-samples";
+            rc = (o.output_flags & MCPT_OUT_PNG_DEFLATE) ? mcpt_write_png_deflate((dn + ".png").c_str(), rgb.data(), s.width, s.height)
+                                                          : mcpt_write_png((dn + ".png").c_str(), rgb.data(), s.width, s.height);
+            if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_PFM)) rc = mcpt_write_pfm((dn + ".pfm").c_str(), guided.data(), s.width, s.height);
+        }
+        if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_SAMPLE_AOV_PFM)) {
+            const std::pair<const char*, const std::vector<double>*> files[] = {
+                {".s-albedo.pfm", &saovs.albedo}, {".s-normal.pfm", &saovs.normal}, {".s-depth.pfm", &saovs.depth}, {".coverage.pfm", &saovs.coverage}};
             for (const auto& f : files)
                 if (rc == MCPT_OK) rc = mcpt_write_pfm((stem + f.first).c_str(), f.second->data(), s.width, s.height);
         }

@@ -1,0 +1,194 @@
+"""Not gpu: the C-ABI surface of the sample AOVs and the guided denoiser (symbols, struct layout, argument errors without a device,
+render_scene's refusals) and their numpy restatement (tests/guide_ref.py) against denoise_ref and hand computations."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import denoise_ref as R
+import guide_ref as GR
+from conftest import ROOT, SCENES
+from test_adaptive_cpu import _offsets
+
+ERR_ARG = -3
+NAMES = ["mcpt_progressive_sample_aovs", "mcpt_progressive_denoise_guided", "mcpt_progressive_denoise_guided_device"]
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+# ---- the interface
+def test_guided_symbols_are_declared_and_exported(mcpt):
+    from montecarlopathtracing_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "mcpt.h")).read()
+    L = C.CDLL(_lib.LIB_PATH)
+    for sym in NAMES:
+        assert (sym + "(") in hdr and sym in _lib.EXPORTS and hasattr(L, sym), sym
+    assert "MCPT_OUT_DENOISED_SAMPLES 64" in hdr and mcpt.OUT_DENOISED_SAMPLES == 64
+    assert "MCPT_OUT_SAMPLE_AOV_PFM  128" in hdr and mcpt.OUT_SAMPLE_AOV_PFM == 128
+    assert "#define MCPT_GUIDE_SAMPLES     %d\n" % GR.GUIDE_SAMPLES in hdr
+    assert "#define MCPT_DENOISE_SIGMA_A   %s\n" % GR.SIGMA_A in hdr
+    assert "#define MCPT_VERSION 105" in hdr and L.mcpt_version() == 105
+    assert "not modelled)" not in hdr.split("camera lens (since")[1].split("environment light (since")[0]
+
+
+def test_guide_params_layout_matches_the_header(mcpt, tmp_path):
+    from montecarlopathtracing_amd import _lib
+    _offsets(tmp_path, "mcpt_guide_params", [n for n, _ in _lib.GuideParams._fields_], _lib.GuideParams)
+    assert C.sizeof(_lib.GuideParams) == 16
+    assert C.sizeof(_lib.DenoiseParams) == 24                      # the first-hit filter's struct is as it was
+
+
+def test_null_handle_is_refused(mcpt):
+    L = mcpt.lib()
+    img = np.zeros(12)
+    ptr = img.ctypes.data_as(C.POINTER(C.c_double))
+    gp = C.byref(mcpt.GuideParams(0, 0, 0.0))
+    assert L.mcpt_progressive_sample_aovs(None, 0, None, None, None, None) == ERR_ARG
+    assert L.mcpt_progressive_denoise_guided(None, None, gp, ptr) == ERR_ARG
+    assert L.mcpt_progressive_denoise_guided(None, None, None, None) == ERR_ARG
+    assert L.mcpt_progressive_denoise_guided_device(None, None, gp, None, None) == ERR_ARG
+
+
+@pytest.mark.parametrize("kw", [dict(output_flags=64, checkpoint="x.ckpt"), dict(output_flags=128, devices=-1),
+                                dict(output_flags=64 | 128, devices=[0]), dict(output_flags=128, checkpoint="y.ckpt")])
+def test_render_scene_refuses_guided_combinations(mcpt, tmp_path, kw):
+    """the new flags make the frame progressive: checkpoints and several GPUs are refused before anything is loaded or written"""
+    with pytest.raises(mcpt.McptError) as e:
+        mcpt.render_scene(SCENES, "cornell-box", 16, output_prefix=str(tmp_path / "x"), **kw)
+    assert e.value.code == ERR_ARG
+    assert os.listdir(tmp_path) == []
+
+
+def test_render_scene_refuses_guided_denoising_of_one_sample(mcpt, tmp_path):
+    with pytest.raises(mcpt.McptError) as e:
+        mcpt.render_scene(SCENES, "cornell-box", 1, output_prefix=str(tmp_path / "x"), output_flags=64)
+    assert e.value.code == ERR_ARG
+    assert os.listdir(tmp_path) == []
+
+
+def test_the_self_check_variant_links_every_kernel_file():
+    """build() also makes csrc/variants/libmcpt_chk.so from the same sources: it must resolve the new launch functions too"""
+    from montecarlopathtracing_amd import _lib
+    chk = os.path.join(os.path.dirname(_lib.LIB_PATH), "variants", "libmcpt_chk.so")
+    assert os.path.exists(chk)
+    L = C.CDLL(chk)
+    for sym in NAMES:
+        assert hasattr(L, sym), sym
+
+
+# ---- the fold
+def test_fold_of_identical_samples_is_the_sample():
+    rng = np.random.default_rng(1)
+    t = rng.random(7) + 0.5
+    kd = rng.random((7, 3))
+    n = GR.unit(rng.normal(size=(7, 3)))
+    for G in (1, 2):
+        kind = np.full((G, 7), GR.SURFACE)
+        counts, depth, normal, albedo = GR.fold(kind, np.stack([t] * G), np.stack([kd] * G), np.stack([n] * G))
+        assert np.array_equal(counts, np.broadcast_to([G, 0, 0], (7, 3)))
+        assert np.array_equal(_bits(depth), _bits(t)) and np.array_equal(_bits(albedo), _bits(kd)) and np.array_equal(_bits(normal), _bits(n))
+
+
+def test_fold_counts_kinds_and_sums_the_surface_samples_in_order():
+    kind = np.array([[GR.SURFACE, GR.MISS, GR.EMITTER], [GR.MISS, GR.MISS, GR.SURFACE], [GR.SURFACE, GR.MISS, GR.SURFACE]])
+    t = np.array([[0.1, 9.0, 9.0], [9.0, 9.0, 0.7], [0.2, 9.0, 1e-17]])
+    kd = np.repeat(t[..., None], 3, axis=2)
+    nh = np.zeros((3, 3, 3))
+    nh[..., 1] = 1.0
+    nh[2, 0] = (0.0, 0.0, 0.0)                                     # a zero normal contributes 0
+    counts, depth, normal, albedo = GR.fold(kind, t, kd, nh)
+    assert counts.dtype == np.int32 and counts.tolist() == [[2, 0, 1], [0, 0, 3], [2, 1, 0]]
+    assert depth[0] == (0.1 + 0.2) / 2.0 and depth[1] == 0.0 and depth[2] == (0.7 + 1e-17) / 2.0
+    assert np.array_equal(albedo[0], [depth[0]] * 3) and np.all(albedo[1] == 0.0) and np.all(normal[1] == 0.0)
+    assert normal[0].tolist() == [0.0, 0.5, 0.0] and normal[2].tolist() == [0.0, 1.0, 0.0]
+
+
+# ---- the filter
+def _frame(h, w, rng, G=4):
+    est = rng.random((h, w, 3))
+    se2 = rng.random((h, w, 3)) * 1e-3
+    normal = rng.normal(size=(h, w, 3)) * 0.05
+    normal[..., 2] += 1.0
+    depth = 3.0 + 0.1 * rng.random((h, w))
+    albedo = 0.2 + 0.6 * rng.random((h, w, 3))
+    counts = np.zeros((h, w, 3), dtype=np.int32)
+    counts[..., 0] = G
+    return est, se2, counts, normal, depth, albedo
+
+
+@pytest.mark.parametrize("K", [0, 1, 5])
+def test_full_coverage_and_no_albedo_term_is_the_first_hit_filter_bit_for_bit(K):
+    """cov = 1, one material everywhere, sigma_a = +inf (A = 0), no emitter samples: mcpt_progressive_denoise's filter"""
+    h, w, G = 23, 37, 4
+    est, se2, counts, normal, depth, albedo = _frame(h, w, np.random.default_rng(11), G)
+    owned = np.ones((h, w), dtype=bool)
+    got = GR.denoise(est, se2, owned, counts, normal, depth, albedo, G, iterations=K, sigma_a=np.inf)
+    want = R.denoise(est, se2, np.zeros((h, w), dtype=np.int64), normal, depth, albedo, iterations=K)
+    assert np.array_equal(_bits(got), _bits(want))
+    if K:
+        assert not np.array_equal(_bits(got), _bits(est))
+        assert not np.array_equal(_bits(got), _bits(GR.denoise(est, se2, owned, counts, normal, depth, albedo, G, iterations=K, sigma_a=0.05)))
+
+
+def test_emitter_and_empty_pixels_pass_through_and_are_not_neighbours():
+    h, w, G = 16, 16, 4
+    est, se2, counts, normal, depth, albedo = _frame(h, w, np.random.default_rng(12), G)
+    counts[5, 7] = (3, 1, 0)                                       # ne > 0
+    counts[9, 2] = (0, 0, 4)                                       # ns == 0
+    counts[0, :] = (0, 4, 0)
+    owned = np.ones((h, w), dtype=bool)
+    owned[12, 12] = False
+    filt = GR.filtered_pixels(counts, owned)
+    assert not filt[5, 7] and not filt[9, 2] and not filt[0].any() and not filt[12, 12] and filt.sum() == h * w - 19
+    out = GR.denoise(est, se2, owned, counts, normal, depth, albedo, G, iterations=3)
+    assert np.array_equal(_bits(out[~filt]), _bits(est[~filt]))
+    assert not np.array_equal(out[filt], est[filt])
+    est2 = est.copy()
+    est2[~filt] = 1e9
+    out2 = GR.denoise(est2, se2, owned, counts, normal, depth, albedo, G, iterations=3)
+    assert np.array_equal(_bits(out2[filt]), _bits(out[filt]))
+
+
+def test_partial_coverage_demodulates_by_cov_times_albedo():
+    counts = np.array([[[2, 0, 2], [4, 0, 0], [1, 0, 3]]], dtype=np.int32)
+    albedo = np.array([[[0.5, 0.5, 0.5], [0.5, 0.004, 1.0], [0.02, 0.5, 0.5]]])
+    m = GR.demodulation(counts, albedo, 4)
+    assert m.tolist() == [[[0.25, 0.25, 0.25], [0.5, 0.01, 1.0], [0.01, 0.125, 0.125]]]
+
+
+def test_taps_outside_the_frame_and_the_centre_tap_by_hand():
+    """a constant demodulated colour (L = 0), equal normals, depths and m (D = A = 0): every tap inside the frame weighs h[dx] h[dy] and
+    the centre tap exactly h[0] h[0] whatever sigma_a is; at a corner only the 3 x 3 inside the frame counts"""
+    h, w, G = 5, 5, 2
+    rng = np.random.default_rng(13)
+    est = np.full((h, w, 3), 0.4)
+    se2 = rng.random((h, w, 3)) * 1e-3
+    counts = np.zeros((h, w, 3), dtype=np.int32)
+    counts[..., 0] = G
+    normal = np.zeros((h, w, 3))
+    normal[..., 2] = 0.5                                           # not unit: the filter normalises
+    depth = np.full((h, w), 3.0)
+    albedo = np.full((h, w, 3), 0.5)
+    owned = np.ones((h, w), dtype=bool)
+    filt = GR.filtered_pixels(counts, owned)
+    m = GR.demodulation(counts, albedo, G)
+    e = est / m
+    v0 = sum(((R.LUM[c] * R.LUM[c]) * se2[..., c]) / (m[..., c] * m[..., c]) for c in range(3))
+    e1, v1 = GR.atrous(e, v0, filt, GR.unit(normal), depth, m, 1, 2.0, 0.05, 1e-3)
+    hh = R.H5
+    centre = sum((hh[dx + 2] * hh[dy + 2]) ** 2 * v0[2 + dy, 2 + dx] for dy in range(-2, 3) for dx in range(-2, 3))
+    assert v1[2, 2] == pytest.approx(centre, rel=1e-15)
+    sw = sum(hh[dx + 2] * hh[dy + 2] for dy in range(0, 3) for dx in range(0, 3))
+    corner = sum((hh[dx + 2] * hh[dy + 2]) ** 2 * v0[dy, dx] for dy in range(0, 3) for dx in range(0, 3)) / (sw * sw)
+    assert v1[0, 0] == pytest.approx(corner, rel=1e-15)
+    assert np.allclose(e1, 0.8, rtol=4e-16, atol=0.0)
+    # a pixel whose m differs by far more than sigma_a keeps its own value: only its centre tap (A = 0) has weight
+    albedo[2, 2] = 1.0
+    est[2, 2] = 0.9
+    m = GR.demodulation(counts, albedo, G)
+    e = est / m
+    e1, _ = GR.atrous(e, v0, filt, GR.unit(normal), depth, m, 1, 1e6, 0.05, 1e-3)
+    assert e1[2, 2] == pytest.approx(e[2, 2], rel=1e-12)

@@ -13,7 +13,10 @@ base="-O3 -std=c++17 -fPIC -ffp-contract=off -pthread -Wall -Wno-unused-function
 logic_flags="${LOGIC_FLAGS--mllvm -disable-machine-licm}"      # as the Makefile's LOGICFLAGS (LOGIC_FLAGS= in the environment: none)
 rm -f variants/obj_$name/*.o                                     # (objects of files that are gone must not be linked)
 pids=()
-for f in kernels wavefront build_kernels denoise camera env; do
+# every kernel file of the library (the Makefile's .hip objects); wavefront_logic takes its own flags below
+for src in *.hip; do
+  f=${src%.hip}
+  [ $f = wavefront_logic ] && continue
   $HIPCC $base $hip_only --offload-arch=gfx950 -c -o variants/obj_$name/$f.o $f.hip & pids+=($!)
 done
 $HIPCC $base $hip_only $logic_flags --offload-arch=gfx950 -c -o variants/obj_$name/wavefront_logic.o wavefront_logic.hip & pids+=($!)
