@@ -12,9 +12,6 @@
 
 namespace mcpt {
 
-#ifndef MCPT_FAST_STACK
-#define MCPT_FAST_STACK 36
-#endif
 constexpr int kFastMaxDepth = MCPT_FAST_STACK;          // inner levels; bounds the per-lane LDS stack of the deep-stack kernels
 // The trace engine exists in two shapes (wavefront.hip): a 27-entry stack leaves LDS and registers for 4 waves per SIMD, the 36-entry
 // one for 3.  Hierarchies are built for the deep stack; the short-stack engine hands a ray that would overflow to the one-lane walk.

@@ -7,6 +7,13 @@
 #include <cstddef>
 #include <cstdint>
 
+// Per-lane traversal stack entries of the deep-stack trace kernels, in LDS (36 KB per block of 256 lanes).  The one definition: the kernels
+// size their stacks by it and the builder (accel_build.hpp: kFastMaxDepth) keeps every hierarchy below it: 35 = 3 x 11 levels of the
+// device-built 4-wide tree (16.7 M triangles) + slack.
+#ifndef MCPT_FAST_STACK
+#define MCPT_FAST_STACK 36
+#endif
+
 namespace mcpt {
 
 // One real BVH node, compact level order (index = BVH::findIndex).  48 bytes of box padded to one 64-B segment.
@@ -181,19 +188,83 @@ inline bool tree_on(const DLightPick& p) { return p.nodes != nullptr; }
 // the kernels' compile-time pick mode of a scene: 0 (MCPT_LIGHTS_ALL), 1 (MCPT_LIGHTS_ONE), 2 (MCPT_LIGHTS_TREE)
 inline int pick_mode(const DLightPick& p) { return tree_on(p) ? 2 : (pick_on(p) ? 1 : 0); }
 
-// device-side counters (one cache line)
+// ---- device-side counters and diagnostic words.  The kernels add to them by name; stats.cpp turns them into mcpt_stats and the MCPT_PRINT_DIAG
+// text.  The layout is fixed (680 bytes of 64-bit words, asserted below): mcpt_device_collect_stats sums two of them word by word.
+
+// MCPT_TRACE_DIAG builds: what the waves of the persistent trace engine did, word by word (a wave counts in Work::diag, k_wf_trace adds that to
+// DCounters::diag).  Phases: 0 inner, 1 pre-test, 2 exact; stages of the wave's time: 0 refill, then the phases.
+enum TraceDiagWord {
+    TD_ITERS = 0,           // + 2 * phase: iterations of the phase
+    TD_LANES = 1,           // + 2 * phase: lanes that waited for it
+    TD_IDLE_LANES = 6,
+    TD_CYCLES = 8,          // + stage: wave cycles
+    TD_WORDS = 12
+};
+// MCPT_PRE_CHECK builds: what the pre-test saw of the first triangle it should not have rejected (the wave that turns `claimed` from 0 to 1 writes it)
+struct PreCheckRecord {
+    unsigned long long claimed;
+    double seen[8];                                          // tri_pre_reject's margins: beta, gamma, alpha, behind, beyond, clear; t32, |det|
+    double t_k, leader, limit_f, margin, eta4, slot, count;
+    double o[3], d[3];                                       // the ray
+    unsigned long long spare[2];
+};
+// MCPT_POOL_DEBUG builds: the refill account of the pool engine's trace launches (trace_pool.hpp)
+struct PoolDebug {
+    unsigned long long used, ok, refills, retired, slots, launches, tickets, started;
+    unsigned long long class_steps[4], class_lanes[4], class_want[4];
+    unsigned long long sleeps, missed;
+    unsigned long long spare[2];
+};
+// MCPT_POOL_DEBUG builds: the pool scheduler's account per class (node, leaf, exact, result, shade), of the finishing pass and of the trace launches
+struct PoolAccount {
+    unsigned long long steps[5], lanes[5];                   // steps per class, lanes that claimed
+    unsigned long long sleeps, missed;                       // ... steps that claimed nothing
+    unsigned long long cycles[5];                            // wave cycles per class
+    unsigned long long overhead, life, waves;                // cycles voting / claiming / sleeping, wave lifetimes, waves
+    unsigned long long spare[4];
+};
+// What a trace engine's Work::dbg points to.  The two debug builds share the first 24 words: a library is compiled with at most one of them.
+struct DebugWords {
+    union { PreCheckRecord pre; PoolDebug pool; };
+    PoolAccount account;
+};
+#if defined(MCPT_PRE_CHECK) && defined(MCPT_POOL_DEBUG)
+#error "MCPT_PRE_CHECK and MCPT_POOL_DEBUG share DebugWords: build one or the other (chk is the first alone, diag the second with MCPT_TRACE_DIAG)"
+#endif
+
 struct DCounters {
     unsigned long long rays_primary, rays_shadow, rays_bounce, node_visits, tri_tests, shade_calls, samples, max_depth;
     unsigned long long shadow_skipped;   // shadow rays the reference traces although their result is never used (light behind the surface)
     unsigned long long trace_rays, trace_nodes, trace_tris;   // work done inside the dominant kernel (k_wf_trace) only
     unsigned long long trace_exact;                           // ... triangles of those that survived the pre-test (exact fp64 tests)
-    unsigned long long dbg[24];   // MCPT_PRE_CHECK builds: what the pre-test saw of the first triangle it should not have rejected
-    unsigned long long pp[24];    // MCPT_POOL_DEBUG builds, pool form of the finishing pass: [0..4] steps per class (node, leaf, exact, result, shade),
-                                  // [5..9] lanes that claimed, [10] sleeps, [11] steps that claimed nothing, [12..16] wave cycles per class,
-                                  // [17] cycles voting / claiming / sleeping, [18] wave lifetimes, [19] waves
-    unsigned long long pad[24];   // diagnostics: [0..11] trace engine (MCPT_TRACE_DIAG builds), [12] rays k_wf_trace handed to the exact walk,
-                                  // [13..15] finishing kernel, [16..19] logic kernel,
-                                  // [20] pre-test self-check, [21..22] kernarg self-check (MCPT_PRE_CHECK: trace launches whose kernarg WfArgs differ / checked)
+    DebugWords dbg;
+    unsigned long long diag[TD_WORDS];
+    unsigned long long deferred_rays;                         // rays k_wf_trace handed to the exact walk
+    unsigned long long finish_steps, finish_life, finish_trace;   // finishing kernel: longest wave in steps, in ticks alive, in ticks inside the ray walks (maxima)
+    unsigned long long logic_cycles[3], logic_waves;          // logic kernel, later passes: cycles in resolve / compaction / shade, waves
+    unsigned long long pre_wrong;                             // pre-test self-check: rejected triangles that are candidates by the exact test (must stay 0)
+    unsigned long long kernarg_differ, kernarg_checked;       // MCPT_PRE_CHECK: trace launches whose kernarg WfArgs differ / that were checked
+    unsigned long long spare;
 };
+// The layout, word by word: the debug words at byte 104, the pool account at 296, the diagnostics at 488.  Recorded profiles and both sides of
+// the host / kernel boundary rely on it; a member that moves fails here, not on the GPU.
+#define MCPT_WORD(member, base, index) static_assert(offsetof(DCounters, member) == (base) + 8 * (index), #member)
+static_assert(sizeof(DCounters) == 680 && sizeof(DCounters) % sizeof(unsigned long long) == 0 && alignof(DCounters) == alignof(unsigned long long),
+              "85 64-bit words and nothing else: summed word by word");
+static_assert(sizeof(PreCheckRecord) == 192 && sizeof(PoolDebug) == 192 && sizeof(PoolAccount) == 192, "24 words each");
+MCPT_WORD(dbg, 104, 0); MCPT_WORD(dbg.account, 296, 0); MCPT_WORD(diag, 488, 0);
+MCPT_WORD(dbg.pre.claimed, 104, 0); MCPT_WORD(dbg.pre.seen, 104, 1); MCPT_WORD(dbg.pre.t_k, 104, 9); MCPT_WORD(dbg.pre.leader, 104, 10);
+MCPT_WORD(dbg.pre.limit_f, 104, 11); MCPT_WORD(dbg.pre.margin, 104, 12); MCPT_WORD(dbg.pre.eta4, 104, 13); MCPT_WORD(dbg.pre.slot, 104, 14);
+MCPT_WORD(dbg.pre.count, 104, 15); MCPT_WORD(dbg.pre.o, 104, 16); MCPT_WORD(dbg.pre.d, 104, 19);
+MCPT_WORD(dbg.pool.used, 104, 0); MCPT_WORD(dbg.pool.ok, 104, 1); MCPT_WORD(dbg.pool.refills, 104, 2); MCPT_WORD(dbg.pool.retired, 104, 3);
+MCPT_WORD(dbg.pool.slots, 104, 4); MCPT_WORD(dbg.pool.launches, 104, 5); MCPT_WORD(dbg.pool.tickets, 104, 6); MCPT_WORD(dbg.pool.started, 104, 7);
+MCPT_WORD(dbg.pool.class_steps, 104, 8); MCPT_WORD(dbg.pool.class_lanes, 104, 12); MCPT_WORD(dbg.pool.class_want, 104, 16);
+MCPT_WORD(dbg.pool.sleeps, 104, 20); MCPT_WORD(dbg.pool.missed, 104, 21);
+MCPT_WORD(dbg.account.steps, 296, 0); MCPT_WORD(dbg.account.lanes, 296, 5); MCPT_WORD(dbg.account.sleeps, 296, 10); MCPT_WORD(dbg.account.missed, 296, 11);
+MCPT_WORD(dbg.account.cycles, 296, 12); MCPT_WORD(dbg.account.overhead, 296, 17); MCPT_WORD(dbg.account.life, 296, 18); MCPT_WORD(dbg.account.waves, 296, 19);
+MCPT_WORD(deferred_rays, 488, 12); MCPT_WORD(finish_steps, 488, 13); MCPT_WORD(finish_life, 488, 14); MCPT_WORD(finish_trace, 488, 15);
+MCPT_WORD(logic_cycles, 488, 16); MCPT_WORD(logic_waves, 488, 19); MCPT_WORD(pre_wrong, 488, 20); MCPT_WORD(kernarg_differ, 488, 21);
+MCPT_WORD(kernarg_checked, 488, 22); MCPT_WORD(spare, 488, 23);
+#undef MCPT_WORD
 
 }  // namespace mcpt

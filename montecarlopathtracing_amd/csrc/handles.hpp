@@ -23,7 +23,10 @@
 #include "kernels.hpp"
 #include "knobs.hpp"
 #include "scene.hpp"
+#include "stats.hpp"
 #include "wavefront.hpp"
+
+static_assert(MCPT_MAX_DEPTH_DEV == MCPT_MAX_DEPTH, "the kernels' path depth (kernels.hpp) is the C API's (mcpt.h)");
 
 struct mcpt_scene {
     mcpt::Scene s;
@@ -249,9 +252,6 @@ int lens_check(const mcpt_lens* l);
 int ensure_dirs(mcpt_device* d, hipStream_t st);    // the primary directions, made on first use
 int ensure_pos(mcpt_device* d, hipStream_t st);     // the image-plane points camera_ray starts from (d->pos), made on first use
 mcpt::DLens lens_for(const mcpt_device* d, const mcpt_lens& l);   // lens l on d's camera as the kernels read it (after ensure_pos)
-void counters_to_stats(const mcpt::DCounters& c, mcpt_stats* s, bool print_diag);
-// a += b for every counter of b (max_depth: the larger); ms_trace and ms_total are the caller's to combine
-void add_counts(mcpt_stats& a, const mcpt_stats& b);
 // Runs run(d_img, d_img2) on device copies of the caller's pageable host frames (`bytes` each; a null frame stays null): each is copied
 // in first, so that pixels the call does not write keep the caller's values, and out again on success.  The stream is synchronised
 // in between, on failure as well: nothing enqueued may still use a copy when it goes.

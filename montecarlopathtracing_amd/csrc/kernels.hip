@@ -93,7 +93,7 @@ __global__ void __launch_bounds__(256, WAVES) k_trace_persistent(DScene S, Src s
     Work w = {0, 0};
     trace_persistent(S, src, queue, slow_list, slow_cap, chunk, lds_stack + threadIdx.x, 256, lds_rays + (threadIdx.x >> 6) * (MCPT_RAYBUF_BYTES / 8), w, S.fast.stack_cap < STACK ? S.fast.stack_cap : STACK);
     ls.nodes = w.nodes; ls.tris = w.tris;
-    { const unsigned long long tw = wave_sum(w.pre_wrong); if ((threadIdx.x & 63) == 0 && tw && ctr) atomicAdd(&ctr->pad[20], tw); }
+    { const unsigned long long tw = wave_sum(w.pre_wrong); if ((threadIdx.x & 63) == 0 && tw && ctr) atomicAdd(&ctr->pre_wrong, tw); }
     flush_stats(ctr, ls);
 }
 
@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(NW * 64, 1) k_trace_pool(DScene S, Src src, Tr
     Work w = {0, 0};
     trace_pool<Src, NW, KT, SCAP>(S, src, queue, slow_list, slow_cap, chunk, L, w, reinterpret_cast<int*>(slow_list + slow_cap));
     ls.nodes = w.nodes; ls.tris = w.tris;
-    { const unsigned long long tw = wave_sum(w.pre_wrong); if ((threadIdx.x & 63) == 0 && tw && ctr) atomicAdd(&ctr->pad[20], tw); }
+    { const unsigned long long tw = wave_sum(w.pre_wrong); if ((threadIdx.x & 63) == 0 && tw && ctr) atomicAdd(&ctr->pre_wrong, tw); }
     flush_stats(ctr, ls);
 }
 

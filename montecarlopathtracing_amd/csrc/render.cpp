@@ -65,67 +65,6 @@ DLens lens_for(const mcpt_device* d, const mcpt_lens& l)
     return c;
 }
 
-void counters_to_stats(const DCounters& c, mcpt_stats* s, bool print_diag)
-{
-    s->rays_primary = c.rays_primary; s->rays_shadow = c.rays_shadow; s->rays_bounce = c.rays_bounce;
-    s->node_visits = c.node_visits; s->tri_tests = c.tri_tests; s->shade_calls = c.shade_calls; s->samples = c.samples;
-    s->shadow_skipped = c.shadow_skipped;
-    s->dom_rays = c.trace_rays; s->dom_node_visits = c.trace_nodes; s->dom_tri_tests = c.trace_tris;
-    if (print_diag) {
-        const double tot = double(c.pad[8] + c.pad[9] + c.pad[10] + c.pad[11]);
-        const double iters = double(c.pad[0] + c.pad[2] + c.pad[4]);
-        auto per = [](unsigned long long a, unsigned long long b) { return b ? double(a) / double(b) : 0.0; };
-        std::fprintf(stderr, "trace diag: inner iters %llu lanes %.1f/64 | pre-test iters %llu lanes %.1f/64 | exact iters %llu lanes %.1f/64 | idle lanes/iter %.1f | "
-                             "wave time: refill %.1f%% inner %.1f%% pre-test %.1f%% exact %.1f%% | cycles per iter: inner %.0f pre-test %.0f exact %.0f\n",
-                     c.pad[0], per(c.pad[1], c.pad[0]), c.pad[2], per(c.pad[3], c.pad[2]), c.pad[4], per(c.pad[5], c.pad[4]), iters ? double(c.pad[6]) / iters : 0.0,
-                     tot ? 100.0 * c.pad[8] / tot : 0.0, tot ? 100.0 * c.pad[9] / tot : 0.0, tot ? 100.0 * c.pad[10] / tot : 0.0, tot ? 100.0 * c.pad[11] / tot : 0.0,
-                     per(c.pad[9], c.pad[0]), per(c.pad[10], c.pad[2]), per(c.pad[11], c.pad[4]));
-        std::fprintf(stderr, "k_wf_trace: %llu rays, %.3f nodes, %.3f triangles visited, %.3f exact tests per ray (%.1f %% of the visited triangles survive the pre-test)\n",
-                     c.trace_rays, per(c.trace_nodes, c.trace_rays), per(c.trace_tris, c.trace_rays), per(c.trace_exact, c.trace_rays), 100.0 * per(c.trace_exact, c.trace_tris));
-        std::fprintf(stderr, "rays deferred to the exact walk by k_wf_trace: %llu of %llu\n", c.pad[12], c.trace_rays);
-#ifdef MCPT_POOL_DEBUG
-        if (c.pp[19]) {
-            static const char* nm[5] = {"node", "leaf", "exact", "result", "shade"};
-            const double life = double(c.pp[18]);
-            for (int i = 0; i < 5; i++)
-                std::fprintf(stderr, "pool %-6s: %10llu steps, %5.1f lanes per step, %7.0f cycles per step, %5.1f %% of wave time\n", nm[i], c.pp[i],
-                             c.pp[i] ? double(c.pp[5 + i]) / c.pp[i] : 0.0, c.pp[i] ? double(c.pp[12 + i]) / c.pp[i] : 0.0, life ? 100.0 * c.pp[12 + i] / life : 0.0);
-            std::fprintf(stderr, "pool: %llu waves, %.0f cycles per wave, vote + claim + sleep %.1f %% of wave time, %llu sleeps, %llu steps that claimed nothing\n", c.pp[19],
-                         life / c.pp[19], life ? 100.0 * c.pp[17] / life : 0.0, c.pp[10], c.pp[11]);
-        }
-        for (int i = 0; i < 4; i++) std::fprintf(stderr, "pool class %d: %llu steps, %.1f lanes per step (%.1f could before the claim)\n", i, c.dbg[8 + i], c.dbg[8 + i] ? double(c.dbg[12 + i]) / c.dbg[8 + i] : 0.0, c.dbg[8 + i] ? double(c.dbg[16 + i]) / c.dbg[8 + i] : 0.0);
-        std::fprintf(stderr, "pool: %llu sleeps, %llu steps that claimed nothing\n", c.dbg[20], c.dbg[21]);
-        std::fprintf(stderr, "pool debug: %llu launches, %llu slots in all, %llu consumed in %llu refill steps, %llu rays among them, %llu started, %llu slots retired, %llu tickets\n", c.dbg[5], c.dbg[4], c.dbg[0], c.dbg[2], c.dbg[1], c.dbg[7], c.dbg[3], c.dbg[6]);
-#endif
-        if (c.pad[20]) {
-            std::fprintf(stderr, "PRE-TEST SELF-CHECK: %llu rejected triangles are candidates by the exact test\n", c.pad[20]);
-            double g[24]; std::memcpy(g, c.dbg, sizeof g);
-            std::fprintf(stderr, "  first: margins beta %.6g gamma %.6g alpha %.6g behind %.6g beyond %.6g clear %.6g | t32 %.9g |det| %.6g | t_k %.17g leader %.17g limit_f %.9g margin %.6g eta4 %.6g slot %.0f of %.0f\n"
-                                 "  ray o %.17g %.17g %.17g d %.17g %.17g %.17g\n",
-                         g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13], g[14], g[15], g[16], g[17], g[18], g[19], g[20], g[21]);
-        }
-#ifdef MCPT_PRE_CHECK
-        std::fprintf(stderr, "KERNARG CHECK: %llu of %llu trace launches read another WfArgs through the kernarg segment\n", c.pad[21], c.pad[22]);
-#endif
-        if (c.pad[13]) std::fprintf(stderr, "finish diag: longest wave %llu steps, %.0f us alive, %.0f us of it in the ray walks (100 MHz ticks; maxima over waves and launches)\n",
-                                    c.pad[13], double(c.pad[14]) / 100.0, double(c.pad[15]) / 100.0);
-        const double lt = double(c.pad[16] + c.pad[17] + c.pad[18]);
-        std::fprintf(stderr, "logic diag: resolve %.1f%% compaction %.1f%% shade %.1f%% | cycles per wave: %.0f / %.0f / %.0f (waves %llu)\n",
-                     lt ? 100.0 * c.pad[16] / lt : 0.0, lt ? 100.0 * c.pad[17] / lt : 0.0, lt ? 100.0 * c.pad[18] / lt : 0.0,
-                     c.pad[19] ? double(c.pad[16]) / c.pad[19] : 0.0, c.pad[19] ? double(c.pad[17]) / c.pad[19] : 0.0, c.pad[19] ? double(c.pad[18]) / c.pad[19] : 0.0, c.pad[19]);
-    }
-}
-
-void add_counts(mcpt_stats& a, const mcpt_stats& b)
-{
-    a.rays_primary += b.rays_primary; a.rays_shadow += b.rays_shadow; a.rays_bounce += b.rays_bounce;
-    a.node_visits += b.node_visits; a.tri_tests += b.tri_tests; a.shade_calls += b.shade_calls;
-    a.samples += b.samples; a.shadow_skipped += b.shadow_skipped;
-    a.dom_rays += b.dom_rays; a.dom_node_visits += b.dom_node_visits; a.dom_tri_tests += b.dom_tri_tests;
-    a.launches += b.launches;
-    a.max_depth = std::max(a.max_depth, b.max_depth);
-}
-
 int with_device_frames(hipStream_t st, size_t bytes, double* img, double* img2, const std::function<int(double*, double*)>& run)
 {
     double* const host[2] = {img, img2};
@@ -307,7 +246,7 @@ static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameS
         } else {
             launch_hit_slots(f.hits.get(), int(first), n_slots, f.hit_slots.get(), &f.wf_counts[0].n_next, st);
             HIP_TRY(hipGetLastError());
-            launch_primary_surface(S, a, f.surf.get(), f.alive_base.get(), &f.wf_counts[0].pad[2], n_slots, st);      // what the samples of a pixel share at their first vertex
+            launch_primary_surface(S, a, f.surf.get(), f.alive_base.get(), &f.wf_counts[0].shaded_pixels, n_slots, st);      // what the samples of a pixel share at their first vertex
             HIP_TRY(hipGetLastError());
         }
         for (int depth = 0; depth < MCPT_MAX_DEPTH && n_upper > 0; depth++) {

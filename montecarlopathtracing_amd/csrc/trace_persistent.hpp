@@ -242,7 +242,7 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
 #ifdef MCPT_TRACE_DIAG
     unsigned long long t_prev = __builtin_amdgcn_s_memtime();
     int last_phase = 0;
-#define MCPT_STAMP(ph) { const unsigned long long t_now = __builtin_amdgcn_s_memtime(); if (lane == 0) w.diag[8 + last_phase] += t_now - t_prev; t_prev = t_now; last_phase = ph; }
+#define MCPT_STAMP(ph) { const unsigned long long t_now = __builtin_amdgcn_s_memtime(); if (lane == 0) w.diag[TD_CYCLES + last_phase] += t_now - t_prev; t_prev = t_now; last_phase = ph; }
 #else
 #define MCPT_STAMP(ph)
 #endif
@@ -314,9 +314,9 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
 #ifdef MCPT_TRACE_DIAG
         if (lane == 0) {
             const int k = phase - 1;                                   // 0 inner, 1 tri, 2 exact
-            w.diag[2 * k] += 1; w.diag[2 * k + 1] += phase == ST_INNER ? n_inner : (phase == ST_TRI ? n_tri : n_exact);
-            w.diag[6] += 64 - n_inner - n_tri - n_exact;
-            if (phase == ST_TRI) { w.diag[4] += 1; w.diag[5] += n_exact; }      // exact-stage lanes at the start of a leaf iteration
+            w.diag[TD_ITERS + 2 * k] += 1; w.diag[TD_LANES + 2 * k] += phase == ST_INNER ? n_inner : (phase == ST_TRI ? n_tri : n_exact);
+            w.diag[TD_IDLE_LANES] += 64 - n_inner - n_tri - n_exact;
+            if (phase == ST_TRI) { w.diag[TD_ITERS + 2 * 2] += 1; w.diag[TD_LANES + 2 * 2] += n_exact; }      // exact-stage lanes at the start of a leaf iteration
         }
 #endif
         MCPT_STAMP(phase)
@@ -355,16 +355,16 @@ __device__ __forceinline__ void trace_persistent(const DScene& S, const Src& src
                     const unsigned int wrong = leaf_wrongly_rejected(tris, cur, tri_m, surv, r, found, best_t);
                     if (wrong) {
                         atomicAdd(&wctr[3], (unsigned int)__popc(wrong)); surv |= wrong;
-                        if (w.dbg && atomicCAS(w.dbg, 0ull, 1ull) == 0ull) {      // the first one: what the pre-test saw
+                        if (w.dbg && atomicCAS(&w.dbg->pre.claimed, 0ull, 1ull) == 0ull) {      // the first one: what the pre-test saw
                             const int k = __ffs((int)wrong) - 1;
                             float h[8];
                             (void)tri_pre_reject(pre + cur + k, pr, limit_f, h);
                             V3 pc;
                             (void)tri_hit(tris + cur + k, r, pc);
-                            double* o = reinterpret_cast<double*>(w.dbg);
-                            for (int i = 0; i < 8; i++) o[1 + i] = h[i];
-                            o[9] = (pc.x - r.o.x) / r.d.x; o[10] = found ? best_t : -1.0; o[11] = limit_f; o[12] = pr.margin; o[13] = pr.eta4; o[14] = cur + k; o[15] = tri_m;
-                            o[16] = r.o.x; o[17] = r.o.y; o[18] = r.o.z; o[19] = r.d.x; o[20] = r.d.y; o[21] = r.d.z;
+                            PreCheckRecord& o = w.dbg->pre;
+                            for (int i = 0; i < 8; i++) o.seen[i] = h[i];
+                            o.t_k = (pc.x - r.o.x) / r.d.x; o.leader = found ? best_t : -1.0; o.limit_f = limit_f; o.margin = pr.margin; o.eta4 = pr.eta4; o.slot = cur + k; o.count = tri_m;
+                            o.o[0] = r.o.x; o.o[1] = r.o.y; o.o[2] = r.o.z; o.d[0] = r.d.x; o.d[1] = r.d.y; o.d[2] = r.d.z;
                         }
                     }
 #endif

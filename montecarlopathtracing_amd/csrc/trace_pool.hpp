@@ -553,7 +553,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                     if (!queue_empty) {
                         const unsigned int want = (unsigned int)__popcll(wb);
                         unsigned int got = 0;
-                        if (lane == 0) got = atomicAdd(&a.counts->pad[0], want);
+                        if (lane == 0) got = atomicAdd(&a.counts->finish_claimed, want);
                         got = (unsigned int)uni((int)got);
                         if ((long long)got + want >= pp.n) queue_empty = true;
                         mine = (long long)got + (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(wb >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)wb, 0u));
@@ -714,24 +714,25 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
 #ifdef MCPT_POOL_DEBUG
     if constexpr (PP::kPaths) {
         if (lane == 0 && pp.a.ctr) {
-            unsigned long long* o = pp.a.ctr->pp;
-            for (int i = 0; i < 5; i++) { atomicAdd(&o[i], d_cs[i]); atomicAdd(&o[5 + i], d_cl[i]); atomicAdd(&o[12 + i], d_cyc[i]); }
-            atomicAdd(&o[10], d_sleep); atomicAdd(&o[11], d_miss); atomicAdd(&o[17], d_cyc[5]);
-            atomicAdd(&o[18], __builtin_amdgcn_s_memtime() - d_t0); atomicAdd(&o[19], 1ull);
+            PoolAccount& o = pp.a.ctr->dbg.account;
+            for (int i = 0; i < 5; i++) { atomicAdd(&o.steps[i], d_cs[i]); atomicAdd(&o.lanes[i], d_cl[i]); atomicAdd(&o.cycles[i], d_cyc[i]); }
+            atomicAdd(&o.sleeps, d_sleep); atomicAdd(&o.missed, d_miss); atomicAdd(&o.overhead, d_cyc[5]);
+            atomicAdd(&o.life, __builtin_amdgcn_s_memtime() - d_t0); atomicAdd(&o.waves, 1ull);
         }
     } else
     if (lane == 0 && w.dbg) {
-        {   // (the same account for the trace launches: DCounters::pp follows DCounters::dbg)
-            unsigned long long* o = w.dbg + 24;
-            for (int i = 0; i < 4; i++) { atomicAdd(&o[i], d_cs[i]); atomicAdd(&o[5 + i], d_cl[i]); atomicAdd(&o[12 + i], d_cyc[i]); }
-            atomicAdd(&o[10], d_sleep); atomicAdd(&o[11], d_miss); atomicAdd(&o[17], d_cyc[5]);
-            atomicAdd(&o[18], __builtin_amdgcn_s_memtime() - d_t0); atomicAdd(&o[19], 1ull);
+        {   // (the same account for the trace launches)
+            PoolAccount& o = w.dbg->account;
+            for (int i = 0; i < 4; i++) { atomicAdd(&o.steps[i], d_cs[i]); atomicAdd(&o.lanes[i], d_cl[i]); atomicAdd(&o.cycles[i], d_cyc[i]); }
+            atomicAdd(&o.sleeps, d_sleep); atomicAdd(&o.missed, d_miss); atomicAdd(&o.overhead, d_cyc[5]);
+            atomicAdd(&o.life, __builtin_amdgcn_s_memtime() - d_t0); atomicAdd(&o.waves, 1ull);
         }
-        atomicAdd(&w.dbg[0], d_used); atomicAdd(&w.dbg[1], d_okc); atomicAdd(&w.dbg[2], d_steps); atomicAdd(&w.dbg[3], d_kill); atomicAdd(&w.dbg[6], d_tickets);
-        atomicAdd(&w.dbg[7], (unsigned long long)c_rays);
-        for (int i = 0; i < 4; i++) { atomicAdd(&w.dbg[8 + i], d_cs[i]); atomicAdd(&w.dbg[12 + i], d_cl[i]); atomicAdd(&w.dbg[16 + i], d_want[i]); }
-        atomicAdd(&w.dbg[20], d_sleep); atomicAdd(&w.dbg[21], d_miss);
-        if (threadIdx.x == 0 && blockIdx.x == 0) { atomicAdd(&w.dbg[4], (unsigned long long)ts.total); atomicAdd(&w.dbg[5], 1ull); }
+        PoolDebug& g = w.dbg->pool;
+        atomicAdd(&g.used, d_used); atomicAdd(&g.ok, d_okc); atomicAdd(&g.refills, d_steps); atomicAdd(&g.retired, d_kill); atomicAdd(&g.tickets, d_tickets);
+        atomicAdd(&g.started, (unsigned long long)c_rays);
+        for (int i = 0; i < 4; i++) { atomicAdd(&g.class_steps[i], d_cs[i]); atomicAdd(&g.class_lanes[i], d_cl[i]); atomicAdd(&g.class_want[i], d_want[i]); }
+        atomicAdd(&g.sleeps, d_sleep); atomicAdd(&g.missed, d_miss);
+        if (threadIdx.x == 0 && blockIdx.x == 0) { atomicAdd(&g.slots, (unsigned long long)ts.total); atomicAdd(&g.launches, 1ull); }
     }
 #endif
 }

@@ -56,15 +56,15 @@ __device__ __forceinline__ WfArgsKernarg wf_kernarg_args()
 }
 
 // MCPT_PRE_CHECK builds: the kernarg segment seen through wf_kernarg_args() must hold the launch's own WfArgs.  One lane per launch compares
-// a few fields with the by-value copy and counts the launches checked (DCounters::pad[22]) and those that differ (pad[21], must stay 0) --
+// a few fields with the by-value copy and counts the launches checked (DCounters::kernarg_checked) and those that differ (kernarg_differ, must stay 0) --
 // a counter, not a trap: the frame goes on and the host reports the count.
 __device__ __forceinline__ void wf_kernarg_check(const WfArgs& a)
 {
 #ifdef MCPT_PRE_CHECK
     if (blockIdx.x == 0 && threadIdx.x == 0 && a.ctr) {
         const WfArgsKernarg k = wf_kernarg_args();
-        if (k->cap != a.cap || k->spp != a.spp || k->sample_base != a.sample_base) atomicAdd(&a.ctr->pad[21], 1ull);
-        atomicAdd(&a.ctr->pad[22], 1ull);
+        if (k->cap != a.cap || k->spp != a.spp || k->sample_base != a.sample_base) atomicAdd(&a.ctr->kernarg_differ, 1ull);
+        atomicAdd(&a.ctr->kernarg_checked, 1ull);
     }
 #else
     (void)a;
@@ -95,7 +95,7 @@ __global__ void __launch_bounds__(256, WAVES) k_wf_trace(DScene S, WfArgs a, Tra
     LaneStats ls;
     Work w = {0, 0};
 #ifdef MCPT_PRE_CHECK
-    if (a.ctr) w.dbg = a.ctr->dbg;
+    if (a.ctr) w.dbg = &a.ctr->dbg;
 #endif
     trace_persistent(S, src, queue, slow_list, slow_cap, chunk, lds_stack + threadIdx.x, 256, lds_rays + (threadIdx.x >> 6) * (MCPT_RAYBUF_BYTES / 8), w, S.fast.stack_cap < STACK ? S.fast.stack_cap : STACK);
     ls.nodes = w.nodes; ls.tris = w.tris;
@@ -105,10 +105,10 @@ __global__ void __launch_bounds__(256, WAVES) k_wf_trace(DScene S, WfArgs a, Tra
             atomicAdd(&a.ctr->trace_nodes, tn); atomicAdd(&a.ctr->trace_tris, tt); atomicAdd(&a.ctr->trace_rays, tr); atomicAdd(&a.ctr->trace_exact, te);
         }
         const unsigned long long tw = wave_sum(w.pre_wrong);
-        if ((threadIdx.x & 63) == 0 && tw) atomicAdd(&a.ctr->pad[20], tw);
+        if ((threadIdx.x & 63) == 0 && tw) atomicAdd(&a.ctr->pre_wrong, tw);
     }
 #ifdef MCPT_TRACE_DIAG
-    if ((threadIdx.x & 63) == 0 && a.ctr) for (int i = 0; i < 12; i++) atomicAdd(&a.ctr->pad[i], w.diag[i]);
+    if ((threadIdx.x & 63) == 0 && a.ctr) for (int i = 0; i < TD_WORDS; i++) atomicAdd(&a.ctr->diag[i], w.diag[i]);
 #endif
     flush_stats(a.ctr, ls);
 }
@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(NW * 64, 1) k_wf_trace_pool(DScene S, WfArgs a
     LaneStats ls;
     Work w = {0, 0};
 #ifdef MCPT_POOL_DEBUG
-    if (a.ctr) w.dbg = a.ctr->dbg;
+    if (a.ctr) w.dbg = &a.ctr->dbg;
 #endif
     trace_pool<Src, NW, KT, SCAP>(S, src, queue, slow_list, slow_cap, chunk, L, w, reinterpret_cast<int*>(slow_list + slow_cap));
     ls.nodes = w.nodes; ls.tris = w.tris;
@@ -137,7 +137,7 @@ __global__ void __launch_bounds__(NW * 64, 1) k_wf_trace_pool(DScene S, WfArgs a
             atomicAdd(&a.ctr->trace_nodes, tn); atomicAdd(&a.ctr->trace_tris, tt); atomicAdd(&a.ctr->trace_rays, tr); atomicAdd(&a.ctr->trace_exact, te);
         }
         const unsigned long long tw = wave_sum(w.pre_wrong);
-        if ((threadIdx.x & 63) == 0 && tw) atomicAdd(&a.ctr->pad[20], tw);
+        if ((threadIdx.x & 63) == 0 && tw) atomicAdd(&a.ctr->pre_wrong, tw);
     }
     flush_stats(a.ctr, ls);
 }
@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(256) k_wf_trace_slow(DScene S, WfArgs a, const
 {
     const long long n_paths = a.counts->n_next;
     if (n_paths <= (long long)a.finish_below || queue->slow_count == 0) return;
-    if (a.ctr && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&a.ctr->pad[12], (unsigned long long)queue->slow_count);   // diagnostics
+    if (a.ctr && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&a.ctr->deferred_rays, (unsigned long long)queue->slow_count);   // diagnostics
     __shared__ int lds_stack[MCPT_FAST_STACK * 256];
     WfRaySource src; src.a = a; src.n_paths = n_paths;
     LaneStats ls;

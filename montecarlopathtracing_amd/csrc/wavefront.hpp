@@ -68,8 +68,12 @@ struct TraceQueue {                 // persistent trace kernels; device words, z
 
 struct WfCounts {           // one per iteration, on the device: slot 0 = hit pixels of the chunk, slot d+1 = paths alive after
     unsigned int n_next;    // logic(d).  Kernels read their input count from the previous slot, so the host need not know it.
-    unsigned int pad[15];
+    unsigned int finish_claimed;    // the finishing kernels' live claim ticket: paths of this slot handed out so far
+    unsigned int pad1;
+    unsigned int shaded_pixels;     // slot 0: the chunk's hit pixels that are shaded (not emitters), counted by k_primary_surface
+    unsigned int pad[12];
 };
+static_assert(sizeof(WfCounts) == 64 && offsetof(WfCounts, finish_claimed) == 4 && offsetof(WfCounts, shaded_pixels) == 12, "one 64-byte segment; the words the kernels share");
 #define MCPT_WF_COUNT_SLOTS 72
 
 struct WfArgs {

@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
     if constexpr (FIRST) {
         // ---- first pass: no resolve and no compaction -- a pixel's samples live or die together, so k_primary_surface has numbered the
         // shaded pixels and sample k of pixel number n sits at n * spp + k (no ballot, no atomic, no barrier)
-        if (blockIdx.x == 0 && threadIdx.x == 0) a.counts->n_next = a.counts_in->pad[2] * (unsigned int)a.spp;   // shaded pixels x samples
+        if (blockIdx.x == 0 && threadIdx.x == 0) a.counts->n_next = a.counts_in->shaded_pixels * (unsigned int)a.spp;   // shaded pixels x samples
         for (long long base = (long long)blockIdx.x * 256; base < n_round; base += (long long)gridDim.x * 256) {
             const long long i = base + threadIdx.x;
             if (i >= n_prev) continue;
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
             // the block-wise compaction used to leave.  One eighth of the frame, ms per frame by window: none (slot order) 18.8,
             // 2^7 17.3, 2^10 16.5, 2^12 18.0, 2^14 18.7, 2^16 18.8; the whole frame is within 0.5 % for all of them.
             unsigned int an = a.alive_base[(i / a.spp) >> 6] + (unsigned int)ps->alive_index;
-            const unsigned int n_alive = a.counts_in->pad[2];
+            const unsigned int n_alive = a.counts_in->shaded_pixels;
 #ifndef MCPT_SHUFFLE_LOG2
 #define MCPT_SHUFFLE_LOG2 10
 #endif
@@ -328,7 +328,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
         }
     }
 #ifdef MCPT_TRACE_DIAG
-    if (!FIRST && (threadIdx.x & 63) == 0 && a.ctr) { for (int k = 0; k < 3; k++) atomicAdd(&a.ctr->pad[16 + k], dg[k]); atomicAdd(&a.ctr->pad[19], 1ull); }     // (the later passes' account)
+    if (!FIRST && (threadIdx.x & 63) == 0 && a.ctr) { for (int k = 0; k < 3; k++) atomicAdd(&a.ctr->logic_cycles[k], dg[k]); atomicAdd(&a.ctr->logic_waves, 1ull); }     // (the later passes' account)
 #endif
     flush_stats(a.ctr, ls);
 }
@@ -377,7 +377,7 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
         if (idle && !queue_empty && (__popcll(idle) >= 16 || idle == ~0ull)) {
             const unsigned int want = (unsigned int)__popcll(idle);
             unsigned int got = 0;
-            if (lane == 0) got = atomicAdd(&a.counts->pad[0], want);
+            if (lane == 0) got = atomicAdd(&a.counts->finish_claimed, want);
             got = __shfl(got, 0, 64);
             if ((long long)got + want >= n) queue_empty = true;
             const long long mine = (long long)got + __popcll(idle & lt_mask);
@@ -510,9 +510,9 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
 #ifdef MCPT_TRACE_DIAG
     if (lane == 0 && a.ctr) {
         const unsigned long long life = __builtin_amdgcn_s_memtime() - fin_t0;
-        atomicMax(&a.ctr->pad[13], fin_iters);
-        atomicMax(&a.ctr->pad[14], life);
-        atomicMax(&a.ctr->pad[15], fin_t_trace);
+        atomicMax(&a.ctr->finish_steps, fin_iters);
+        atomicMax(&a.ctr->finish_life, life);
+        atomicMax(&a.ctr->finish_trace, fin_t_trace);
     }
 #endif
     ls.nodes += w.nodes; ls.tris += w.tris;

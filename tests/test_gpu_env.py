@@ -3,14 +3,12 @@ pipeline and hand-over path renders the same frame under a constant sky and a va
 missed pixel; diffuse surfaces under known skies converge to their closed forms; an environment that is cleared or inactive changes
 nothing; progressive, adaptive and several-device frames agree with the one-shot frame; the kernarg self-check holds."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import env_ref
+import selfcheck
 from conftest import ROOT, SCENES, extra_scene_dir
 
 pytestmark = pytest.mark.gpu
@@ -405,9 +403,6 @@ def test_render_scene_environment_png_and_checkpoints(mcpt, tmp_path):
 
 # ---------------------------------------------------------------------------------------------------------------- 8. kernarg self-check
 def test_kernarg_self_check_with_an_environment():
-    lib = os.path.join(ROOT, "montecarlopathtracing_amd", "csrc", "variants", "libmcpt_chk.so")
-    if not os.path.exists(lib):
-        subprocess.check_call(["bash", os.path.join(ROOT, "tools", "build_variant.sh"), "chk", "-DMCPT_PRE_CHECK"], stdout=subprocess.DEVNULL)
     code = r'''
 import os, sys
 sys.path.insert(0, %r)
@@ -421,9 +416,8 @@ for engine in ("pool", "vote"):
     dev.close()
 print("done")
 ''' % (ROOT, SCENES)
-    env = dict(os.environ, MCPT_LIB=lib, MCPT_PRINT_DIAG="1", MCPT_FINISH_PATHS="0")
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env)
+    out = selfcheck.run(code, timeout=900)
     assert out.returncode == 0 and "done" in out.stdout, out.stderr[-3000:]
-    found = [(int(a), int(b)) for a, b in re.findall(r"KERNARG CHECK: (\d+) of (\d+) trace launches", out.stderr)]
+    found = selfcheck.kernarg_checks(out.stderr)
     assert len(found) == 2, found
     assert all(a == 0 for a, _ in found) and all(b > 0 for _, b in found), found

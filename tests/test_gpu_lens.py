@@ -3,14 +3,12 @@ the wavefront and the megakernel agree under a real lens, the camera rays are th
 and antialiasing meet their exact geometric answers, and partitions, several devices, pipelined frames, render_scene's checkpoints and the
 kernarg self-check hold under a lens."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import lens_ref
+import selfcheck
 from conftest import ROOT, SCENES, extra_scene_dir
 
 pytestmark = pytest.mark.gpu
@@ -365,9 +363,6 @@ def test_render_scene_lens_png_and_checkpoints(mcpt, tmp_path):
 
 
 def test_kernarg_self_check_with_a_lens(tmp_path):
-    lib = os.path.join(ROOT, "montecarlopathtracing_amd", "csrc", "variants", "libmcpt_chk.so")
-    if not os.path.exists(lib):
-        subprocess.check_call(["bash", os.path.join(ROOT, "tools", "build_variant.sh"), "chk", "-DMCPT_PRE_CHECK"], stdout=subprocess.DEVNULL)
     code = r'''
 import os, sys
 sys.path.insert(0, %r)
@@ -385,9 +380,8 @@ for engine in ("pool", "vote"):
     dev.close()
 print("done")
 ''' % (ROOT, SCENES)
-    env = dict(os.environ, MCPT_LIB=lib, MCPT_PRINT_DIAG="1", MCPT_FINISH_PATHS="0")
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env)
+    out = selfcheck.run(code, timeout=900)
     assert out.returncode == 0 and "done" in out.stdout, out.stderr[-3000:]
-    found = [(int(a), int(b)) for a, b in re.findall(r"KERNARG CHECK: (\d+) of (\d+) trace launches", out.stderr)]
+    found = selfcheck.kernarg_checks(out.stderr)
     assert len(found) == 8, found
     assert all(a == 0 for a, _ in found) and all(b > 0 for _, b in found), found

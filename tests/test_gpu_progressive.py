@@ -2,13 +2,11 @@
 the one-shot frame bit for bit under every engine and chunking; the moments, the standard error and the frame summary are exact and
 deterministic; the error estimate behaves like one."""
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+import selfcheck
 from conftest import ROOT, SCENES, extra_scene_dir
 
 pytestmark = pytest.mark.gpu
@@ -212,9 +210,6 @@ def test_render_scene_progressive(mcpt, tmp_path):
 def test_kernarg_self_check_counts_no_mismatch(tmp_path):
     """The -DMCPT_PRE_CHECK build compares the WfArgs the trace kernels read through the kernarg segment (wf_kernarg_args) with their
     by-value copy at entry, over the passes of a progressive frame (sample_base != 0) and a plain one: no mismatch, and checks made."""
-    lib = os.path.join(ROOT, "montecarlopathtracing_amd", "csrc", "variants", "libmcpt_chk.so")
-    if not os.path.exists(lib):
-        subprocess.check_call(["bash", os.path.join(ROOT, "tools", "build_variant.sh"), "chk", "-DMCPT_PRE_CHECK"], stdout=subprocess.DEVNULL)
     code = r'''
 import sys
 sys.path.insert(0, %r)
@@ -232,9 +227,8 @@ for engine in ("pool", "vote"):
     dev.close()
 print("done")
 ''' % (ROOT, SCENES)
-    env = dict(os.environ, MCPT_LIB=lib, MCPT_PRINT_DIAG="1", MCPT_FINISH_PATHS="0")
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=900, env=env)
+    out = selfcheck.run(code, timeout=900)
     assert out.returncode == 0 and "done" in out.stdout, out.stderr[-3000:]
-    found = [(int(a), int(b)) for a, b in re.findall(r"KERNARG CHECK: (\d+) of (\d+) trace launches", out.stderr)]
+    found = selfcheck.kernarg_checks(out.stderr)
     assert len(found) == 8, found
     assert all(a == 0 for a, _ in found) and all(b > 0 for _, b in found), found

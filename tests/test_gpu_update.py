@@ -485,11 +485,8 @@ def test_multi_device(mcpt, tmp_path_factory):
 
 def test_pre_test_rejects_no_candidate_after_a_refit(tmp_path):
     """the pre-test self-check build (csrc/variants/libmcpt_chk.so) renders a refitted scene and counts no rejected candidate"""
-    import subprocess
-    import sys
-    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib = os.path.join(ROOT, "montecarlopathtracing_amd", "csrc", "variants", "libmcpt_chk.so")
-    assert os.path.exists(lib), "build() makes the self-check build"
+    import selfcheck
+    ROOT = selfcheck.ROOT
     code = r'''
 import sys
 sys.path.insert(0, %r); sys.path.insert(0, %r)
@@ -507,8 +504,7 @@ for build in (M.BUILD_HOST, M.BUILD_DEVICE_FAST):
     dev.close()
 print("done")
 ''' % (ROOT, os.path.join(ROOT, "tests"), SCENES)
-    env = dict(os.environ, MCPT_LIB=lib, MCPT_PRINT_DIAG="1", MCPT_FINISH_PATHS="0")
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env)
+    out = selfcheck.run(code, timeout=600)
     assert out.returncode == 0 and "done" in out.stdout, out.stderr[-3000:]
     assert "PRE-TEST SELF-CHECK" not in out.stderr, out.stderr[-3000:]
     assert "exact tests per ray" in out.stderr

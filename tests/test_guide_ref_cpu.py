@@ -71,8 +71,8 @@ def test_render_scene_refuses_guided_denoising_of_one_sample(mcpt, tmp_path):
 
 def test_the_self_check_variant_links_every_kernel_file():
     """build() also makes csrc/variants/libmcpt_chk.so from the same sources: it must resolve the new launch functions too"""
-    from montecarlopathtracing_amd import _lib
-    chk = os.path.join(os.path.dirname(_lib.LIB_PATH), "variants", "libmcpt_chk.so")
+    import selfcheck
+    chk = selfcheck.variant_lib()
     assert os.path.exists(chk)
     L = C.CDLL(chk)
     for sym in NAMES:
