@@ -321,8 +321,9 @@ int     mcpt_progressive_sample_counts(mcpt_progressive*, int32_t* counts);
  * call (the primary rays of the owned pixels traced on the device's stream), kept with the handle and freed with it.
  *   material : the material of the hit triangle, -1 for a miss.
  *   depth    : the hit's ray parameter t (the primary direction is a unit vector); 0 on a miss.
- *   normal   : the interpolated shading normal exactly as the integrator forms it at a vertex (barycentric blend of the vertex normals),
- *              not normalised; 0 on a miss and on an emitter.
+ *   normal   : the interpolated normal of the hit, the barycentric blend of the vertex normals exactly as the closest hit forms it (the pn
+ *              of mcpt_trace_closest: findGarCor's three quotients; shading's own blend multiplies by a reciprocal and may differ from it
+ *              in the last bit), not normalised; 0 on a miss and on an emitter.
  *   albedo   : the diffuse colour Kd exactly as shading forms it, the texel / 255 (the .mtl's map_Kd) included; 0 on a miss and an emitter.
  * mcpt_progressive_denoise: an edge-avoiding a-trous wavelet filter (the spatial filter of SVGF) of the estimate, guided by the AOVs and
  * the per-pixel variance.  Host: W*H*3 doubles, pixels not owned keep the caller's values; _device: into a device buffer on `stream`,
@@ -370,7 +371,7 @@ int mcpt_progressive_denoise_device(mcpt_progressive*, const mcpt_denoise_params
  * mcpt_progressive_sample_aovs: for G camera samples per owned pixel (samples = G, 1 <= G <= the handle's spp; 0: min(spp,
  * MCPT_GUIDE_SAMPLES)) sample k = 0 .. G-1 gets the frame's own camera ray of (pixel, k) -- the handle's lens and seed, what mcpt_camera_rays
  * returns -- traced for its closest hit on the device's current walk and engine.  A sample is a MISS, an EMITTER hit (the hit material is a
- * light) or a SURFACE hit; a surface hit contributes its t, the diffuse colour kd and the shading normal pn of the first-hit AOVs, pn divided
+ * light) or a SURFACE hit; a surface hit contributes its t, the diffuse colour kd and the normal pn of the first-hit AOVs, pn divided
  * by its length sqrt((x x + y y) + z z) (a zero normal contributes 0).  Per pixel, summed in k order in fp64 without contraction by one GPU
  * lane (no atomics):
  *   counts : 3 int32 per pixel, ns (surface), ne (emitter), nm (miss); ns + ne + nm = G.

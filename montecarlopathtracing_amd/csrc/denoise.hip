@@ -11,8 +11,9 @@
 
 namespace mcpt {
 
-// ---- AOVs: one lane per owned pixel.  The surface at the hit is vertex_surface's (what shading sees), formed only where shading forms
-// it: on a hit of a non-emitting material.  A miss: material -1, everything else 0; an emitter: its material and depth, normal and
+// ---- AOVs: one lane per owned pixel.  The albedo at the hit is vertex_surface's (what shading sees), the normal the closest hit's
+// (hit_normal: the pn of mcpt_trace_closest, the oracle's bits), both formed only where shading forms a surface: on a hit of a
+// non-emitting material.  A miss: material -1, everything else 0; an emitter: its material and depth, normal and
 // albedo 0.  The guide record of a surface pixel carries the normal divided by its length (0 for a zero normal).
 __global__ void __launch_bounds__(256) k_primary_aov(DScene S, const int32_t* __restrict__ pixels, int n, const PrimaryHit* __restrict__ hits,
                                                      int32_t* __restrict__ mat, double* __restrict__ depth, double* __restrict__ normal,
@@ -30,7 +31,13 @@ __global__ void __launch_bounds__(256) k_primary_aov(DScene S, const int32_t* __
         material = S.tris[ph.leaf].material;
         t = ph.t;
         const DMaterial* m = S.materials + material;
-        if (m->light < 0) { vertex_surface(S, ph.leaf, mk(ph.p[0], ph.p[1], ph.p[2]), m, pn, kd); surface = true; }
+        if (m->light < 0) {
+            Hit h;
+            h.leaf = ph.leaf; h.t = ph.t; h.p = mk(ph.p[0], ph.p[1], ph.p[2]);
+            vertex_surface(S, ph.leaf, h.p, m, pn, kd);
+            pn = hit_normal(S, h);
+            surface = true;
+        }
     }
     mat[pix] = material;
     depth[pix] = t;

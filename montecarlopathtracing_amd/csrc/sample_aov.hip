@@ -25,8 +25,9 @@ __global__ void __launch_bounds__(256) k_guide_rays(DLens lens, unsigned long lo
     r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
 }
 
-// A sample is a miss, an emitter hit (material.light >= 0) or a surface hit; a surface hit adds t, vertex_surface's kd and its pn divided
-// by its length (a zero normal adds 0).  depth, albedo, normal = the sums / ns (0 when ns == 0).  The guide record: n^ = normal / |normal|,
+// A sample is a miss, an emitter hit (material.light >= 0) or a surface hit; a surface hit adds t, vertex_surface's kd and the closest hit's
+// normal (hit_normal: findGarCor's quotients, the pn of mcpt_trace_closest, so the fold is checkable against the fp64 oracle bit for bit)
+// divided by its length (a zero normal adds 0).  depth, albedo, normal = the sums / ns (0 when ns == 0).  The guide record: n^ = normal / |normal|,
 // t = depth, m = max((ns / G) * albedo, 0.01), filtered = ns > 0 and ne == 0.
 __global__ void __launch_bounds__(256) k_guide_fold(DScene S, const int32_t* __restrict__ pixels, int first, int n, int G, const int32_t* __restrict__ leaf,
                                                     const double* __restrict__ t, const double* __restrict__ p, int32_t* __restrict__ counts,
@@ -47,7 +48,10 @@ __global__ void __launch_bounds__(256) k_guide_fold(DScene S, const int32_t* __r
         if (m->light >= 0) { ne++; continue; }
         ns++;
         V3 pn, kd;
-        vertex_surface(S, lf, ld3(p + j * 3), m, pn, kd);
+        Hit h;
+        h.leaf = lf; h.t = t[j]; h.p = ld3(p + j * 3);
+        vertex_surface(S, lf, h.p, m, pn, kd);
+        pn = hit_normal(S, h);
         const double len = sqrt((pn.x * pn.x + pn.y * pn.y) + pn.z * pn.z);
         st += t[j];
         sk.x += kd.x; sk.y += kd.y; sk.z += kd.z;

@@ -97,6 +97,9 @@ struct orc_scene {
     int walk_mode;           /* ORC_TRACE_* the integrator's rays are walked with (same hits; ALIAS = the reference's visit counts) */
     struct orc_env* env;     /* the environment light (extension): NULL = none or inactive */
     struct orc_pick* pick;   /* the light pick (extension): NULL = every light at every vertex */
+    /* the camera lens (extension): all 0 = the reference's pinhole, one primary ray per pixel */
+    int lens_flags; double lens_aperture, lens_focus;
+    int lens_wrong;          /* 0; 1, 2: deliberately wrong answers for the tests' power checks (orc_scene_set_lens_wrong) */
 };
 
 /* ------------------------------------------------------------------ RNG seam (D1) */
@@ -1295,7 +1298,7 @@ static vec3 shade(Ctx* c, const Hit* p, vec3 dir, int depth)
 }
 
 /* camera frame of generateImg, MTPC/pathTracing.cpp:276-294 */
-typedef struct { vec3 eye, start_point, screen_pdx, screen_pdy; } CamFrame;
+typedef struct { vec3 eye, start_point, screen_pdx, screen_pdy; vec3 xhat, yhat; double l; } CamFrame;   /* xhat, yhat, l: the lens's (extension) */
 
 static CamFrame cam_frame(const orc_scene* s)
 {
@@ -1313,6 +1316,7 @@ static CamFrame cam_frame(const orc_scene* s)
     cf.screen_pdx = vmul(screen_x_dir, pdx);
     cf.start_point = vadd(vsub(screen_center, vmul(screen_x_dir, dx)), vmul(up, dy));
     cf.eye = s->eye;
+    cf.xhat = screen_x_dir; cf.yhat = up; cf.l = l;
     return cf;
 }
 
@@ -1348,6 +1352,71 @@ void orc_primary_rays(const orc_scene* s, int row0, int row1, double* rays6)
     }
 }
 
+
+/* ------------------------------------------------------------------ camera lens (extension)
+ * include/mcpt.h "camera lens", restated from its text (not from the product's code): every camera sample (pixel, k) gets a camera ray of
+ * its own from u0..u3 = the Philox block (pixel, k, 0xFFFF << 16, 'MCPT'), i.e. orc_uniform at depth 0xFFFF, slots 0..3. */
+#define ORC_LENS_JITTER     1
+#define ORC_LENS_PER_SAMPLE 2
+#define ORC_LENS_DEPTH      0xFFFFu
+#define ORC_LENS_TWO_PI     6.283185307179586      /* 2 pi with the full-precision pi (not ORC_PI) */
+
+static inline int lens_active(const orc_scene* s) { return s->lens_flags != 0 || s->lens_aperture > 0; }
+
+int orc_scene_set_lens(orc_scene* s, int flags, double aperture, double focus_distance)
+{
+    if ((flags & ~(ORC_LENS_JITTER | ORC_LENS_PER_SAMPLE)) != 0) return -1;
+    if (!isfinite(aperture) || aperture < 0 || !isfinite(focus_distance)) return -1;
+    s->lens_flags = flags; s->lens_aperture = aperture; s->lens_focus = focus_distance;
+    s->lens_wrong = 0;
+    return 0;
+}
+
+int orc_scene_set_lens_wrong(orc_scene* s, int wrong)
+{
+    if (!lens_active(s) || wrong < 0 || wrong > 2) return -1;
+    s->lens_wrong = wrong;
+    return 0;
+}
+
+/* the camera ray of sample k of pixel (row, col) under the scene's lens, in the header's operation order */
+static RayT camera_ray(const orc_scene* s, const CamFrame* cf, uint64_t seed, int row, int col, uint32_t k)
+{
+    const uint32_t pixel = (uint32_t)(row * s->width + col);
+    vec3 q = pixel_pos(cf, row, col);
+    if (s->lens_flags & ORC_LENS_JITTER) {
+        const double u0 = orc_uniform(seed, pixel, k, ORC_LENS_DEPTH, 0), u1 = orc_uniform(seed, pixel, k, ORC_LENS_DEPTH, 1);
+        q = vsub(vadd(q, vmul(cf->screen_pdx, u0)), vmul(cf->screen_pdy, u1));
+    }
+    RayT ray;
+    if (!(s->lens_aperture > 0)) {               /* the pinhole */
+        ray.o = cf->eye;
+        ray.d = vnormalize(vsub(q, cf->eye));
+        return ray;
+    }
+    const double u2 = orc_uniform(seed, pixel, k, ORC_LENS_DEPTH, 2), u3 = orc_uniform(seed, pixel, k, ORC_LENS_DEPTH, 3);
+    const double F = s->lens_focus > 0 ? s->lens_focus : cf->l;
+    const vec3 f = vadd(cf->eye, vmul(vsub(q, cf->eye), F / cf->l));
+    const double r = s->lens_aperture * sqrt(u2);
+    const double phi = ORC_LENS_TWO_PI * u3;
+    ray.o = vadd(vadd(cf->eye, vmul(cf->xhat, r * cos(phi))), vmul(cf->yhat, r * sin(phi)));
+    ray.d = vnormalize(vsub(f, ray.o));
+    return ray;
+}
+
+int orc_camera_rays(const orc_scene* s, uint64_t seed, const int32_t* pix, const int32_t* k, int64_t n, double* rays6)
+{
+    const CamFrame cf = cam_frame(s);
+    const int64_t npix = (int64_t)s->width * s->height;
+    for (int64_t i = 0; i < n; i++) if (pix[i] < 0 || pix[i] >= npix || k[i] < 0) return -1;
+    for (int64_t i = 0; i < n; i++) {
+        const RayT r = camera_ray(s, &cf, seed, pix[i] / s->width, pix[i] % s->width, (uint32_t)k[i]);
+        double* o = rays6 + i * 6;
+        o[0] = r.o.x; o[1] = r.o.y; o[2] = r.o.z; o[3] = r.d.x; o[4] = r.d.y; o[5] = r.d.z;
+    }
+    return 0;
+}
+
 static vec3 sample_radiance(Ctx* c, const RayT* ray, const Hit* primary, int have_primary)
 {
     Hit h;
@@ -1362,13 +1431,33 @@ static vec3 sample_radiance(Ctx* c, const RayT* ray, const Hit* primary, int hav
     return shade(c, &h, vneg(ray->d), 0);
 }
 
+/* one camera sample under an active lens: its own ray traced and counted, shaded from ITS hit with wo = -d of ITS ray; a miss is 0, or
+ * Le(its d) under an environment.  pin_d: the direction of the pixel's unjittered pinhole ray, used by the wrong modes only. */
+static vec3 lens_sample_radiance(Ctx* c, const RayT* ray, vec3 pin_d)
+{
+    Hit h;
+    if (c->st) c->st->rays_primary++;
+    ray_intersect(c->s, ray, &h, c->s->walk_mode, &c->c);
+    if (c->st) c->st->samples++;
+    if (!h.hit) {
+        if (!c->env) return v3(0, 0, 0);
+        if (c->st) c->st->camera_miss++;
+        return env_lookup(c->env, c->s->lens_wrong == 2 ? pin_d : ray->d);
+    }
+    return shade(c, &h, vneg(c->s->lens_wrong == 1 ? pin_d : ray->d), 0);
+}
+
 void orc_sample_radiance(const orc_scene* s, uint64_t seed, int row, int col, int k, double rgb[3], orc_stats* st)
 {
     CamFrame cf = cam_frame(s);
     vec3 pos = pixel_pos(&cf, row, col);
     RayT ray = { cf.eye, vnormalize(vsub(pos, cf.eye)) };
     Ctx c = { s, seed, (uint32_t)(row * s->width + col), (uint32_t)k, 0, st, { 0, 0 }, s->env };
-    vec3 r = sample_radiance(&c, &ray, NULL, 0);
+    vec3 r;
+    if (lens_active(s)) {
+        const RayT own = camera_ray(s, &cf, seed, row, col, (uint32_t)k);
+        r = lens_sample_radiance(&c, &own, ray.d);
+    } else r = sample_radiance(&c, &ray, NULL, 0);
     if (st) { st->box_tests += c.c.box; st->tri_tests += c.c.tri; }
     rgb[0] = r.x; rgb[1] = r.y; rgb[2] = r.z;
 }
@@ -1384,8 +1473,9 @@ static void stats_add(orc_stats* a, const orc_stats* b)
     a->camera_miss += b->camera_miss;
 }
 
-/* generateImg, MTPC/pathTracing.cpp:274-331 (D1, D3), under the environment env (NULL: none) */
-static void render_block(const orc_scene* s, const Env* env, int spp, uint64_t seed, int row0, int row1, int col0, int col1,
+/* generateImg, MTPC/pathTracing.cpp:274-331 (D1, D3), under the environment env (NULL: none); lens != 0: under the scene's lens, a camera ray
+ * per sample and the same float accumulation in k order, missed samples included */
+static void render_block(const orc_scene* s, const Env* env, int lens, int spp, uint64_t seed, int row0, int row1, int col0, int col1,
                          int faithful_cost, int nthreads, double* img, orc_stats* st)
 {
     CamFrame cf = cam_frame(s);
@@ -1406,13 +1496,21 @@ static void render_block(const orc_scene* s, const Env* env, int spp, uint64_t s
                     RayT ray = { cf.eye, vnormalize(vsub(pos, cf.eye)) };
                     Ctx c = { s, seed, (uint32_t)(i * W + j), 0, faithful_cost, &local, { 0, 0 }, env };
                     Hit primary; int have = 0;
-                    if (!faithful_cost) {                              /* identical for every k: trace once */
+                    if (!faithful_cost && !lens) {                     /* identical for every k: trace once */
                         local.rays_primary++;
                         ray_intersect(s, &ray, &primary, s->walk_mode, &c.c);
                         have = 1;
                     }
                     for (int k = 0; k < spp; k++) {
                         c.sample = (uint32_t)k;
+                        if (lens) {                                    /* a camera ray per sample; a missed one adds its 0 (or Le) too */
+                            const RayT own = camera_ray(s, &cf, seed, i, j, (uint32_t)k);
+                            const vec3 x = lens_sample_radiance(&c, &own, ray.d);
+                            cr += x.x / spp;
+                            cg += x.y / spp;
+                            cb += x.z / spp;
+                            continue;
+                        }
                         if (have && !primary.hit) {
                             local.samples++;
                             if (!env) continue;
@@ -1448,7 +1546,7 @@ static void render_block(const orc_scene* s, const Env* env, int spp, uint64_t s
 void orc_render(const orc_scene* s, int spp, uint64_t seed, int row0, int row1, int col0, int col1,
                 int faithful_cost, int nthreads, double* img, orc_stats* st)
 {
-    render_block(s, s->env, spp, seed, row0, row1, col0, col1, faithful_cost, nthreads, img, st);
+    render_block(s, s->env, lens_active(s), spp, seed, row0, row1, col0, col1, faithful_cost, nthreads, img, st);
 }
 
 /* The reference's own parallel structure, for timing (MTPC/pathTracing.cpp:300-320): the samples of ONE pixel at a time on
@@ -1477,7 +1575,7 @@ void orc_render_reference_style(const orc_scene* s, int spp, uint64_t seed, int 
                     uint64_t box = 0, tri = 0;
 #pragma omp for schedule(static)
                     for (int k = 0; k < spp; k++) {
-                        Ctx c = { s, seed, (uint32_t)(i * W + j), (uint32_t)k, 1, &local, { 0, 0 }, NULL };   /* (no environment) */
+                        Ctx c = { s, seed, (uint32_t)(i * W + j), (uint32_t)k, 1, &local, { 0, 0 }, NULL };   /* (no environment; the pixel's pinhole ray: no lens) */
                         RayT r = ray;
                         Hit primary;
                         rad[k] = sample_radiance(&c, &r, &primary, 0);
@@ -1574,7 +1672,7 @@ void orc_render_strided(const orc_scene* s, int spp, uint64_t seed, int row_stri
         for (int w = 0; w < nrows * ncb; w++) {
             const int r = (w / ncb) * row_stride, c0 = (w % ncb) * cb;
             const int c1 = c0 + cb < s->width ? c0 + cb : s->width;
-            render_block(s, NULL, spp, seed, r, r + 1, c0, c1, faithful_cost, -1, img, &local);   /* (no environment) */
+            render_block(s, NULL, 0, spp, seed, r, r + 1, c0, c1, faithful_cost, -1, img, &local);   /* (no environment, no lens) */
         }
 #pragma omp critical
         stats_add(&total, &local);

@@ -49,6 +49,10 @@
  * text and tests/light_pick_ref.py / tests/light_tree_ref.py (orc_scene_set_light_pick below); pinned by
  * tests/test_light_pick_oracle_cpu.py and held against the GPU by tests/test_gpu_light_pick_oracle.py.  Without a pick (the default)
  * every answer and every count is what it was before.
+ * Extension (not in the reference): the camera lens of include/mcpt.h (MCPT_LENS_JITTER, MCPT_LENS_PER_SAMPLE, the thin lens), restated from
+ * that header's "camera lens" paragraph (orc_scene_set_lens below); pinned by tests/test_lens_oracle_cpu.py (the rays against
+ * tests/lens_ref.py, the per-sample route against the pinhole's, the frame against the fold of its samples) and held against the GPU by
+ * tests/test_gpu_lens_oracle.py.  Without a lens (the default) every answer and every count is what it was before.
  */
 #ifndef MCPT_ORACLE_H
 #define MCPT_ORACLE_H
@@ -180,6 +184,26 @@ int orc_scene_set_light_pick_wrong(orc_scene*, int wrong);
  * the vertices, mode 2 only.  out_pdf / out_inv may be NULL.  0, or -1 without a pick. */
 int orc_light_pick(const orc_scene*, uint64_t seed, const int32_t* pix, const int32_t* k, int depth, const double* p, const double* pn,
                    int64_t n, int32_t* out_l, double* out_pdf, double* out_inv);
+
+/* ---- camera lens (extension, not in the reference): include/mcpt.h "camera lens", restated from its text ----
+ * flags: MCPT_LENS_JITTER (1) | MCPT_LENS_PER_SAMPLE (2); aperture >= 0; focus_distance (<= 0: |look_at - eye|).  All zero: the pinhole, and
+ * every answer and count is the reference's.  A lens is ACTIVE when it has a flag or aperture > 0; then orc_sample_radiance and orc_render
+ * (either cost) give every camera sample (pixel, k) a camera ray of its own -- u0..u3 = orc_uniform(seed, pixel, k, depth 0xFFFF, slot 0..3),
+ * q = the running-sum corner, jittered as (q + pdx*u0) - pdy*u1, the pinhole's or the thin lens's ray in the header's operation order, phi with
+ * pi = 3.141592653589793 (not ORC_PI) -- trace it (rays_primary counts each one), shade from THAT sample's hit with wo = -d of THAT sample; a
+ * sample that misses is 0, or Le(its own d) under an environment (camera_miss counts it), and the frame folds every sample, missed ones
+ * included, by the same float accumulation in k order.  MCPT_LENS_PER_SAMPLE alone: the pinhole's answers bit for bit, through this route.
+ * orc_render_strided and orc_render_reference_style IGNORE the lens, as they ignore the environment: the pixel's pinhole ray (the CPU
+ * baseline).  0, or -1 on what the header calls MCPT_ERR_ARG (unknown flag bits, aperture negative or not finite, focus_distance not
+ * finite): the previous lens is kept. */
+int orc_scene_set_lens(orc_scene*, int flags, double aperture, double focus_distance);
+/* the camera rays of samples (pix[i] = row*W+col, k[i]) under the scene's lens, active or not -> rays6[n*6] = origin xyz, direction xyz.
+ * 0, or -1 for a pixel outside the frame or a negative k (nothing is written). */
+int orc_camera_rays(const orc_scene*, uint64_t seed, const int32_t* pix, const int32_t* k, int64_t n, double* rays6);
+/* FOR THE TESTS' POWER CHECKS ONLY: makes the lens route answer wrongly -- 1: the first vertex is shaded with wo of the pixel's unjittered
+ * pinhole ray, 2: a missed sample under an environment takes Le of the pixel's pinhole direction.  0 (what every orc_scene_set_lens leaves) is
+ * right.  0, or -1 without an active lens. */
+int orc_scene_set_lens_wrong(orc_scene*, int wrong);
 
 /* ---- output: MTPC/MTPC.cpp:10-33, MTPC/svpng.inc:77-107 ---- */
 void orc_quantize(const double* img, int64_t n, uint8_t* rgb8);

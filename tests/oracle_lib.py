@@ -15,6 +15,7 @@ SCENES = os.path.join(ROOT, "scenes")
 
 TRACE_REAL_ONLY, TRACE_ALIAS, TRACE_FLAT = 0, 1, 2
 ORDER_STABLE, ORDER_LIBSTDCXX = 0, 1
+LENS_JITTER, LENS_PER_SAMPLE = 1, 2       # include/mcpt.h: MCPT_LENS_*
 
 
 class BvhInfo(C.Structure):
@@ -97,6 +98,9 @@ def lib():
         L.orc_scene_set_light_pick_wrong.argtypes = [C.c_void_p, C.c_int]
         L.orc_light_pick.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double),
                                      C.POINTER(C.c_double), C.c_int64, C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.orc_scene_set_lens.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
+        L.orc_scene_set_lens_wrong.argtypes = [C.c_void_p, C.c_int]
+        L.orc_camera_rays.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -293,6 +297,26 @@ class OracleScene:
                                 n, _ptr(light, C.c_int32), _ptr(pdf, C.c_double), _ptr(inv, C.c_double)) != 0:
             raise ValueError("oracle: the scene does not pick (or the tree needs vertices)")
         return light, pdf, inv
+
+    def set_lens(self, aperture=0.0, focus_distance=0.0, jitter=False, per_sample=False, wrong=0):
+        """The camera lens (an extension of the oracle, include/mcpt.h), with the arguments of the product's Device.set_lens; no arguments:
+        the reference's pinhole.  wrong: 1 or 2 make the oracle's answer WRONG on purpose (1: the first vertex is shaded with wo of the
+        pixel's pinhole ray, 2: a missed sample takes Le of the pixel's pinhole direction), for tests that show a comparison against it has
+        the power to fail; never set otherwise.  A refused lens (ValueError) leaves the previous one in place."""
+        flags = (LENS_JITTER if jitter else 0) | (LENS_PER_SAMPLE if per_sample else 0)
+        if lib().orc_scene_set_lens(self.h, flags, float(aperture), float(focus_distance)) != 0:
+            raise ValueError("oracle: bad lens")
+        if wrong and lib().orc_scene_set_lens_wrong(self.h, int(wrong)) != 0:
+            raise ValueError("oracle: wrong = 1 or 2 goes with an active lens")
+
+    def camera_rays(self, seed, pix, k):
+        """camera rays of samples (pix[i], k[i]) under the scene's lens, active or not: (n, 6) = origin, direction"""
+        pix = np.ascontiguousarray(pix, dtype=np.int32)
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        rays = np.zeros((pix.shape[0], 6))
+        if lib().orc_camera_rays(self.h, seed, _ptr(pix, C.c_int32), _ptr(k, C.c_int32), pix.shape[0], _ptr(rays, C.c_double)) != 0:
+            raise ValueError("oracle: a pixel outside the frame or a negative sample index")
+        return rays
 
 
 def _render_strided(self, spp, seed, row_stride, faithful_cost=True, nthreads=0, stats=None, img=None):
