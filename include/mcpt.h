@@ -806,6 +806,77 @@ int  mcpt_render_scene_motion(const char* path, const char* filename, int32_t sp
                               const mcpt_lens*, const char* environment_pfm, double environment_scale, const char* end_obj,
                               const char* end_camera, const mcpt_shutter*, mcpt_stats* stats);
 
+/* ---- display transform (since the display change): a linear fp64 frame becomes 8-bit pixels, on the GPU ---- */
+/* Off by default: without display parameters every byte the library writes is mcpt_quantize_rgb8's.  A frame is n_pixels x 3 doubles,
+ * the picture n_pixels x 3 bytes (x 4 with MCPT_DISPLAY_RGBA: alpha 255).  Everything is fp64 without contraction, in the order written.
+ *   HISTOGRAM of the luminance Y = (0.2126 r + 0.7152 g) + 0.0722 b of the raw frame, MCPT_DISPLAY_SLOTS int64 counts.  With `bits` the 64
+ *            bits of Y, b = (((bits >> 52) - 1023 + 24) * 8) + ((bits >> 49) & 7): MCPT_DISPLAY_BINS bins over 2^-24 .. 2^24, 8 per stop,
+ *            taken from the exponent and the top three mantissa bits -- never from a logarithm, so no rounding moves a pixel across an edge
+ *            and the counts are exact on every device.  slot 0: skipped pixels (Y not finite or Y <= 0, NaN included); slot 1: b < 0
+ *            (denormals included); slots 2 .. 385: bins 0 .. 383; slot 386: b > 383.
+ *   EXPOSURE from the slots (mcpt_display_exposure, host only): counted = the sum of slots 1 .. 386;
+ *            log_average = exp2(sum n_b log2(centre_b) / counted), summed in slot order, centre_b = ldexp(1 + ((b & 7) + 0.5) / 8, (b >> 3) - 24),
+ *            the under slot counted at bin 0's centre and the over slot at bin 383's;
+ *            l_percentile = the upper edge ldexp(1 + ((b & 7) + 1) / 8, (b >> 3) - 24) of the first bin at which the running count (the
+ *            under slot first) reaches ceil(p counted); p == 0 is 0.99.  counted == 0: both are 0.
+ *   PARAMETERS  e = exposure (0: 1.0); with auto_key > 0 and log_average > 0, e = e * (auto_key / log_average).  REINHARD's white
+ *            w = white, or max(1, e * l_percentile) when white == 0 (1 when nothing was counted).  The histogram is taken only when
+ *            auto_key > 0 or REINHARD is asked with white == 0; otherwise info reports log_average = l_percentile = counted = skipped = 0.
+ *   MAP      per pixel and channel c, with IEEE division:
+ *            x = e * c;  x = x > 0 ? x : 0 (NaN and negatives: 0);  x = x < 2^64 ? x : 2^64;
+ *            MCPT_CURVE_CLAMP    y = x
+ *            MCPT_CURVE_REINHARD Yx = (0.2126 x_r + 0.7152 x_g) + 0.0722 x_b;  y_c = x_c * ((1 + Yx / (w * w)) / (1 + Yx)), 0 when Yx == 0
+ *            MCPT_CURVE_FILMIC   y = (x * (2.51 * x + 0.03)) / (x * (2.43 * x + 0.59) + 0.14)
+ *            y = y < 1 ? y : 1;
+ *            MCPT_TRANSFER_LINEAR  the byte is y * 255 truncated, as mcpt_quantize_rgb8 truncates
+ *            MCPT_TRANSFER_SRGB    y = y <= 0.0031308 ? 12.92 * y : 1.055 * pow(y, 1 / 2.4) - 0.055;  the byte is floor(y * 255 + 0.5)
+ *            (pow is the one step in which two math libraries may differ by an ulp: a byte may then differ where y * 255 + 0.5 is within
+ *            that ulp of an integer).
+ * NULL or all-zero parameters give mcpt_quantize_rgb8's bytes bit for bit.  MCPT_ERR_ARG: reserved != 0, an unknown curve, transfer or
+ * flag, a negative or non-finite exposure, auto_key, percentile or white, a percentile above 1.
+ * _device forms take device pointers and enqueue on `stream`; a call that takes the histogram waits for the stream (the slots come back
+ * to the host: 3 KB).  The device map writes four pixels per lane with 4-byte (RGBA: 16-byte) stores when d_out is aligned to that and
+ * d_img to 16 bytes, and single bytes otherwise: the bytes are the same.  mcpt_display_host is the same arithmetic on the CPU, usable
+ * without a GPU: it is what mcpt_render_scene_display writes its pictures through.
+ * mcpt_progressive_display: the picture of a progressive handle's estimate (MCPT_DISPLAY_ESTIMATE: mcpt_progressive_image), of its denoised
+ * frame (_DENOISED: mcpt_progressive_denoise) or of the sample-guided one (_DENOISED_GUIDED: mcpt_progressive_denoise_guided), the filters
+ * with all defaults and their own refusals.  Histogram and map run over the handle's owned pixels only: the bytes of every other pixel of
+ * rgb8 (W x H x 3 or 4 bytes) stay as they are.  The frame never leaves the GPU; the handle keeps one fp64 scratch frame from the first
+ * call on.  The handle's image, moments and counts are not changed.
+ * mcpt_render_scene_display: mcpt_render_scene_lights whose .png, .denoised.png and .denoised-samples.png go through the display (each
+ * picture with its own histogram); the PFMs stay linear.  display == NULL: mcpt_render_scene_lights, byte for byte.  MCPT_DISPLAY_RGBA is
+ * refused there (the PNGs are RGB). */
+#define MCPT_DISPLAY_BINS   384
+#define MCPT_DISPLAY_SLOTS  387
+#define MCPT_CURVE_CLAMP      0
+#define MCPT_CURVE_REINHARD   1
+#define MCPT_CURVE_FILMIC     2
+#define MCPT_TRANSFER_LINEAR  0
+#define MCPT_TRANSFER_SRGB    1
+#define MCPT_DISPLAY_RGBA     1   /* flags: four bytes per pixel, alpha 255 */
+#define MCPT_DISPLAY_ESTIMATE         0
+#define MCPT_DISPLAY_DENOISED         1
+#define MCPT_DISPLAY_DENOISED_GUIDED  2
+typedef struct { double exposure;    /* 0: 1.0; with auto_key > 0 a compensation factor */
+                 double auto_key;    /* > 0: exposure *= auto_key / log_average (0.18 is the usual key) */
+                 double percentile;  /* 0: 0.99 */
+                 double white;       /* REINHARD's w; 0: max(1, exposure * l_percentile) */
+                 int32_t curve, transfer, flags, reserved; } mcpt_display_params;
+typedef struct { double exposure, white, log_average, l_percentile; int64_t counted, skipped; } mcpt_display_info;
+int mcpt_display_histogram_device(mcpt_device*, const double* d_img, int64_t n_pixels, int64_t slots[MCPT_DISPLAY_SLOTS], void* stream);
+int mcpt_display_histogram(mcpt_device*, const double* img, int64_t n_pixels, int64_t slots[MCPT_DISPLAY_SLOTS]);
+int mcpt_display_exposure(const int64_t slots[MCPT_DISPLAY_SLOTS], double percentile, double* log_average, double* l_percentile);
+int mcpt_display_device(mcpt_device*, const double* d_img, int64_t n_pixels, const mcpt_display_params*, uint8_t* d_out,
+                        mcpt_display_info* info /* may be NULL */, void* stream);
+int mcpt_display(mcpt_device*, const double* img, int64_t n_pixels, const mcpt_display_params*, uint8_t* out, mcpt_display_info* info);
+int mcpt_display_host(const double* img, int64_t n_pixels, const mcpt_display_params*, uint8_t* out, mcpt_display_info* info);
+int mcpt_progressive_display(mcpt_progressive*, int32_t source, const mcpt_display_params*, uint8_t* rgb8, mcpt_display_info* info);
+int mcpt_progressive_display_device(mcpt_progressive*, int32_t source, const mcpt_display_params*, uint8_t* d_rgb8, mcpt_display_info* info,
+                                    void* stream);
+int mcpt_render_scene_display(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options*, int64_t options_bytes,
+                              const mcpt_lens*, const char* environment_pfm, double environment_scale, const mcpt_light_sampling*,
+                              const mcpt_display_params* display, mcpt_stats* stats);
+
 #ifdef __cplusplus
 }
 #endif

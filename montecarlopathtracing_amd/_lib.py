@@ -139,6 +139,21 @@ class Noise(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class DisplayParams(C.Structure):
+    """mcpt_display_params: exposure, tone curve and transfer of the display transform (all zero: imshow's bytes)"""
+    _fields_ = [("exposure", C.c_double), ("auto_key", C.c_double), ("percentile", C.c_double), ("white", C.c_double),
+                ("curve", C.c_int32), ("transfer", C.c_int32), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DisplayInfo(C.Structure):
+    """mcpt_display_info: what a display call used (exposure, white) and what its histogram held"""
+    _fields_ = [("exposure", C.c_double), ("white", C.c_double), ("log_average", C.c_double), ("l_percentile", C.c_double),
+                ("counted", C.c_int64), ("skipped", C.c_int64)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -170,6 +185,8 @@ EXPORTS = [
     "mcpt_device_set_light_sampling", "mcpt_device_get_light_sampling", "mcpt_multi_set_light_sampling", "mcpt_scene_light_pick_table",
     "mcpt_light_pick", "mcpt_render_scene_lights",
     "mcpt_scene_light_tree", "mcpt_scene_light_tree_pdf", "mcpt_light_pick_at",
+    "mcpt_display_histogram_device", "mcpt_display_histogram", "mcpt_display_exposure", "mcpt_display_device", "mcpt_display",
+    "mcpt_display_host", "mcpt_progressive_display", "mcpt_progressive_display_device", "mcpt_render_scene_display",
 ]
 
 
@@ -326,6 +343,18 @@ def lib():
     L.mcpt_light_pick_at.argtypes = [P, C.c_uint64, I32, I32, C.c_int32, D, D, C.c_int64, I32, D]
     L.mcpt_render_scene_lights.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens), C.c_char_p,
                                            C.c_double, C.POINTER(LightSampling), C.POINTER(Stats)]
+    I64 = C.POINTER(C.c_int64)
+    DP, DI = C.POINTER(DisplayParams), C.POINTER(DisplayInfo)
+    L.mcpt_display_histogram_device.argtypes = [P, P, C.c_int64, I64, P]
+    L.mcpt_display_histogram.argtypes = [P, D, C.c_int64, I64]
+    L.mcpt_display_exposure.argtypes = [I64, C.c_double, D, D]
+    L.mcpt_display_device.argtypes = [P, P, C.c_int64, DP, P, DI, P]
+    L.mcpt_display.argtypes = [P, D, C.c_int64, DP, U8, DI]
+    L.mcpt_display_host.argtypes = [D, C.c_int64, DP, U8, DI]
+    L.mcpt_progressive_display.argtypes = [P, C.c_int32, DP, U8, DI]
+    L.mcpt_progressive_display_device.argtypes = [P, C.c_int32, DP, P, DI, P]
+    L.mcpt_render_scene_display.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens), C.c_char_p,
+                                            C.c_double, C.POINTER(LightSampling), DP, C.POINTER(Stats)]
     _lib = L
     return L
 

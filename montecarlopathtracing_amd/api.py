@@ -6,7 +6,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -45,6 +45,59 @@ def make_environment(rgb, scale=1.0):
     tex = np.ascontiguousarray(a, dtype=np.float32)
     e = Environment(tex.shape[1], tex.shape[0], _p(tex, C.c_float), float(scale), 0, 0)
     return e, tex
+
+
+CURVE_CLAMP, CURVE_REINHARD, CURVE_FILMIC = 0, 1, 2
+TRANSFER_LINEAR, TRANSFER_SRGB = 0, 1
+DISPLAY_RGBA = 1
+DISPLAY_BINS, DISPLAY_SLOTS = 384, 387
+DISPLAY_ESTIMATE, DISPLAY_DENOISED, DISPLAY_DENOISED_GUIDED = 0, 1, 2
+_CURVES = {"clamp": CURVE_CLAMP, "reinhard": CURVE_REINHARD, "filmic": CURVE_FILMIC}
+_TRANSFERS = {"linear": TRANSFER_LINEAR, "srgb": TRANSFER_SRGB}
+_SOURCES = {"estimate": DISPLAY_ESTIMATE, "denoised": DISPLAY_DENOISED, "denoised_guided": DISPLAY_DENOISED_GUIDED}
+
+
+def make_display(exposure=0, auto_key=0, percentile=0, white=0, curve="clamp", transfer="linear", rgba=False):
+    """An mcpt_display_params (mcpt.h: display transform).  exposure: a factor (0: 1.0); auto_key > 0: the exposure is scaled so that the
+    frame's log-average luminance lands on that key (0.18 is the usual one); percentile (0: 0.99) picks the luminance that REINHARD's
+    white (0: automatic) is taken from; curve "clamp", "reinhard" or "filmic"; transfer "linear" or "srgb"; rgba: four bytes per pixel,
+    alpha 255.  Curve and transfer may be given as their MCPT_* numbers.  All defaults: imshow's bytes."""
+    c = _CURVES[curve] if isinstance(curve, str) else int(curve)
+    t = _TRANSFERS[transfer] if isinstance(transfer, str) else int(transfer)
+    return DisplayParams(float(exposure), float(auto_key), float(percentile), float(white), c, t, DISPLAY_RGBA if rgba else 0, 0)
+
+
+def _as_display(display):
+    if display is None or isinstance(display, DisplayParams):
+        return display
+    return make_display(**display)
+
+
+def _frame_pixels(img):
+    img = np.ascontiguousarray(img, dtype=np.float64)
+    if img.ndim < 1 or img.shape[-1] != 3:
+        raise ValueError("a frame is an array of RGB triples")
+    return img, img.size // 3
+
+
+def display_host(img, **kw):
+    """The display transform on the CPU (mcpt_display_host; usable without a GPU): img [..., 3] float64 and make_display's arguments ->
+    (uint8 array [..., 3] or [..., 4], info dict)."""
+    img, n = _frame_pixels(img)
+    dp, info = make_display(**kw), DisplayInfo()
+    out = np.zeros(img.shape[:-1] + (4 if dp.flags & DISPLAY_RGBA else 3,), dtype=np.uint8)
+    check(lib().mcpt_display_host(_p(img, C.c_double), n, C.byref(dp), _p(out, C.c_uint8), C.byref(info)))
+    return out, info.as_dict()
+
+
+def display_exposure(slots, percentile=0.0):
+    """(log_average, l_percentile) of a luminance histogram's 387 slots (mcpt_display_exposure; host only)"""
+    slots = np.ascontiguousarray(slots, dtype=np.int64).reshape(-1)
+    if slots.shape[0] != DISPLAY_SLOTS:
+        raise ValueError("a luminance histogram has %d slots" % DISPLAY_SLOTS)
+    la, lp = C.c_double(), C.c_double()
+    check(lib().mcpt_display_exposure(slots.ctypes.data_as(C.POINTER(C.c_int64)), float(percentile), C.byref(la), C.byref(lp)))
+    return la.value, lp.value
 
 
 def _as_lens(lens):
@@ -615,6 +668,29 @@ class Device:
         check(lib().mcpt_device_motion_info(self._h, C.byref(info)))
         return info.as_dict()
 
+    def display(self, img, **kw):
+        """The display transform of a frame on this GPU (mcpt_display): img [..., 3] float64 and make_display's arguments -> (uint8 array
+        [..., 3] or [..., 4], info dict of the exposure and white used and of the histogram, when one was taken)."""
+        img, n = _frame_pixels(img)
+        dp, info = make_display(**kw), DisplayInfo()
+        out = np.zeros(img.shape[:-1] + (4 if dp.flags & DISPLAY_RGBA else 3,), dtype=np.uint8)
+        check(lib().mcpt_display(self._h, _p(img, C.c_double), n, C.byref(dp), _p(out, C.c_uint8), C.byref(info)))
+        return out, info.as_dict()
+
+    def display_device(self, d_img_ptr, n_pixels, d_out_ptr, stream=None, **kw):
+        """The same between caller-owned device buffers (e.g. torch tensors' data_ptr()) on `stream` (mcpt_display_device): the info dict."""
+        dp, info = make_display(**kw), DisplayInfo()
+        check(lib().mcpt_display_device(self._h, C.c_void_p(d_img_ptr), int(n_pixels), C.byref(dp), C.c_void_p(d_out_ptr), C.byref(info),
+                                        C.c_void_p(stream) if stream else None))
+        return info.as_dict()
+
+    def luminance_histogram(self, img):
+        """the 387 slots of a frame's luminance histogram, counted on this GPU (mcpt_display_histogram): int64"""
+        img, n = _frame_pixels(img)
+        slots = np.zeros(DISPLAY_SLOTS, dtype=np.int64)
+        check(lib().mcpt_display_histogram(self._h, _p(img, C.c_double), n, slots.ctypes.data_as(C.POINTER(C.c_int64))))
+        return slots
+
     def progressive(self, spp, seed=0, rank=0, world=1, tile_w=0, tile_h=0, flags=0):
         """A frame of `spp` samples per pixel rendered in passes (mcpt_progressive_*): see Progressive."""
         return Progressive(self, spp, seed, rank, world, tile_w, tile_h, flags)
@@ -733,6 +809,20 @@ class Progressive:
         gp = GuideParams(samples, 0, sigma_a)
         check(lib().mcpt_progressive_denoise_guided(self._h, C.byref(dp), C.byref(gp), _p(img, C.c_double)))
         return img
+
+    def display(self, source="estimate", out=None, **kw):
+        """The frame's picture without the frame leaving the GPU (mcpt_progressive_display): source "estimate" (image()), "denoised"
+        (denoise()) or "denoised_guided" (denoise_guided()), the filters with their defaults; make_display's arguments -> (uint8 [H,W,3] or
+        [H,W,4], info dict).  Pixels not owned: left as in out, else 0."""
+        dp, info = make_display(**kw), DisplayInfo()
+        shape = (self.device.height, self.device.width, 4 if dp.flags & DISPLAY_RGBA else 3)
+        if out is None:
+            out = np.zeros(shape, dtype=np.uint8)
+        if out.dtype != np.uint8 or out.shape != shape or not out.flags["C_CONTIGUOUS"]:
+            raise ValueError("out must be a contiguous uint8 array of shape %r" % (shape,))
+        check(lib().mcpt_progressive_display(self._h, _SOURCES[source] if isinstance(source, str) else int(source), C.byref(dp),
+                                             _p(out, C.c_uint8), C.byref(info)))
+        return out, info.as_dict()
 
     def close(self):
         if getattr(self, "_h", None):
@@ -927,7 +1017,7 @@ def morton_code(x, y, z):
 def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, height=0, quiet=True, output_prefix=None, stats=None,
                  load_flags=0, output_flags=0, checkpoint=None, checkpoint_parts=0, devices=None, gather=GATHER_PEER, noise_target=0.0,
                  time_budget_s=0.0, adaptive_min_spp=0, abs_target=0.0, lens=None, environment=None, environment_scale=1.0, motion=None,
-                 light_sampling=None):
+                 light_sampling=None, display=None):
     """render_scene(path, filename, N) of MTPC/MTPC.cpp:35; writes <prefix>-SPP<N>.png (default ../result/<filename>).
     devices: list of GPU ordinals, or -1 for every visible GPU (the frame is then rendered by mcpt_multi_*).
     noise_target / time_budget_s / OUT_ERROR_PFM: a progressive frame that may stop at k < N samples (<prefix>-SPP<k>.png).
@@ -940,7 +1030,9 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
     motion: None, or a dict of end_obj and end_camera (file paths, either may be missing), shutter = (open, close) and steps: the shutter
     frame between the scene and those files (mcpt_render_scene_motion).
     light_sampling: None / "all", "one", "tree", or a dict of Device.set_light_sampling's arguments; rendered through mcpt_render_scene_lights (not
-    together with motion)."""
+    together with motion).
+    display: None (imshow's bytes), a DisplayParams or a dict of make_display's arguments: the .png and .denoised*.png go through the display
+    transform, the PFMs stay linear; rendered through mcpt_render_scene_display (not together with motion)."""
     dev_arr, ndev = None, 0
     if devices == -1:
         ndev = -1
@@ -952,7 +1044,16 @@ def render_scene(path, filename, N_ray_per_pixel, seed=0, device=0, width=0, hei
                            ndev, gather, dev_arr, noise_target, time_budget_s, adaptive_min_spp, 0, abs_target)
     st = C.byref(stats) if stats is not None else None
     ls, keep_w = make_light_sampling(light_sampling)
-    if ls is not None:
+    dp = _as_display(display)
+    if dp is not None:
+        if motion is not None:
+            raise ValueError("display and motion do not go together in render_scene")
+        check(lib().mcpt_render_scene_display(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o),
+                                              C.byref(_as_lens(lens)) if lens is not None else None,
+                                              environment.encode() if environment is not None else None, float(environment_scale),
+                                              C.byref(ls) if ls is not None else None, C.byref(dp), st))
+        del keep_w
+    elif ls is not None:
         if motion is not None:
             raise ValueError("light_sampling and motion do not go together in render_scene")
         check(lib().mcpt_render_scene_lights(path.encode(), filename.encode(), N_ray_per_pixel, C.byref(o), C.sizeof(o),

@@ -6,6 +6,7 @@
 //   progressive.cpp   progressive frames, AOVs, the denoiser
 //   light_sampling.cpp  MCPT_LIGHTS_ONE and MCPT_LIGHTS_TREE: the pick table, the light tree, their upload, the picks' test seams
 //   motion.cpp        a device's motion: the shutter's steps between two keyframes, the return to key 0
+//   display_api.cpp   the display transform: histogram, exposure, the map to 8-bit pixels on the GPU and on the host
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -179,6 +180,8 @@ struct mcpt_device {
     };
     std::unique_ptr<Motion> motion;
     bool geometry_failed = false;                   // an update failed midway: nothing is traced or rendered until one succeeds
+    // display transform (display_api.cpp): the luminance histogram's slots and their pinned copy, made on the first call that takes one
+    mcpt::DevBuf<unsigned long long> disp_slots; mcpt::HostBuf<int64_t> h_disp_slots;
 };
 
 // The helpers below are the library's own: none of them is exported from libmcpt.so.
@@ -245,6 +248,14 @@ int light_weights_check(const mcpt_light_sampling* ls, size_t num_lights);   // 
 // the emitters have moved (areas[num_lights], the device's light records as they are now; d->upd->light_v, their vertices): default weights
 // are made again, and so is the light tree of MCPT_LIGHTS_TREE
 int light_pick_refresh(mcpt_device* d, const double* areas);
+
+// ---- display_api.cpp
+int display_check(const mcpt_display_params* p);    // MCPT_ERR_ARG: not display parameters (null: the defaults)
+// The picture of pixels d_pixels[0 .. n) (null: pixels 0 .. n) of the frame d_img under p (checked), 3 or 4 bytes per pixel at each pixel's
+// own place in d_out, on st: the histogram over the same pixels when p needs one (st is then waited for), and the map.
+int display_frame_device(mcpt_device* d, const double* d_img, const int32_t* d_pixels, int64_t n, const mcpt_display_params* p, uint8_t* d_out,
+                         mcpt_display_info* info, hipStream_t st);
+int display_histogram_device(mcpt_device* d, const double* d_img, const int32_t* d_pixels, int64_t n, int64_t* slots, hipStream_t st);
 
 // ---- render.cpp
 inline bool lens_active(const mcpt_lens& l) { return l.flags != 0 || l.aperture > 0.0; }

@@ -1,5 +1,5 @@
 // C ABI, progressive frames (include/mcpt.h: mcpt_progressive_*): a frame of N samples per pixel in passes, its noise estimate, adaptive
-// frames that stop each pixel on its own error, first-hit AOVs, sample AOVs and the denoiser in both its forms.
+// frames that stop each pixel on its own error, first-hit AOVs, sample AOVs, the denoiser in both its forms and the frame's picture.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -69,6 +69,7 @@ struct mcpt_progressive {
     DevBuf<int32_t> saov_counts; DevBuf<double> saov_depth, saov_normal, saov_albedo;
     DevBuf<SampleGuide> sguide;
     bool motion = false;               // created on a device with a motion (which stays while the handle lives): passes are cut at its steps
+    DevBuf<double> disp_frame;         // W*H*3: the frame mcpt_progressive_display maps (allocated on its first call)
 };
 
 extern "C" {
@@ -501,6 +502,51 @@ int mcpt_progressive_denoise_guided(mcpt_progressive* h, const mcpt_denoise_para
     // pageable host buffer: blocking copies either side; pixels this rank does not own keep the caller's values
     return with_device_frames(h->d->stream.get(), size_t(h->d->width) * h->d->height * 3 * sizeof(double), img, nullptr,
                               [&](double* d_out, double*) { return mcpt_progressive_denoise_guided_device(h, dp, gp, d_out, h->d->stream.get()); });
+}
+
+// ---- the picture of the frame (mcpt.h: display transform): the source frame into the handle's scratch, then histogram and map over the
+// owned pixels -- the whole frame when the handle owns all of it
+int mcpt_progressive_display_device(mcpt_progressive* h, int32_t source, const mcpt_display_params* p, uint8_t* d_rgb8, mcpt_display_info* info,
+                                    void* stream)
+{
+    if (const int rc = display_check(p)) return rc;
+    if (!h || !d_rgb8) return fail(MCPT_ERR_ARG, "null argument");
+    if (source != MCPT_DISPLAY_ESTIMATE && source != MCPT_DISPLAY_DENOISED && source != MCPT_DISPLAY_DENOISED_GUIDED)
+        return fail(MCPT_ERR_ARG, "unknown display source");
+    mcpt_device* d = h->d;
+    HIP_TRY(hipSetDevice(d->ordinal));
+    const size_t px = size_t(d->width) * d->height;
+    if (!h->disp_frame) {
+        // cleared on the caller's stream, ahead of the kernels that write it (pixels not owned are never read)
+        HIP_TRY(alloc_once(h->disp_frame, px * 3 * sizeof(double)));
+        HIP_TRY(hipMemsetAsync(h->disp_frame.get(), 0, px * 3 * sizeof(double), static_cast<hipStream_t>(stream)));
+    }
+    double* frame = h->disp_frame.get();
+    int rc;
+    if (source == MCPT_DISPLAY_ESTIMATE) rc = mcpt_progressive_image_device(h, frame, nullptr, stream);
+    else if (source == MCPT_DISPLAY_DENOISED) rc = mcpt_progressive_denoise_device(h, nullptr, frame, stream);
+    else rc = mcpt_progressive_denoise_guided_device(h, nullptr, nullptr, frame, stream);
+    if (rc) return rc;
+    const bool whole = h->n_pixels == int64_t(px);
+    return display_frame_device(d, frame, whole ? nullptr : h->pixels.get(), h->n_pixels, p, d_rgb8, info, static_cast<hipStream_t>(stream));
+}
+
+int mcpt_progressive_display(mcpt_progressive* h, int32_t source, const mcpt_display_params* p, uint8_t* rgb8, mcpt_display_info* info)
+{
+    if (const int rc = display_check(p)) return rc;
+    if (!h || !rgb8) return fail(MCPT_ERR_ARG, "null argument");
+    HIP_TRY(hipSetDevice(h->d->ordinal));
+    // pageable host buffer: blocking copies either side; pixels this rank does not own keep the caller's bytes
+    const size_t bytes = size_t(h->d->width) * h->d->height * ((p && (p->flags & MCPT_DISPLAY_RGBA)) ? 4 : 3);
+    DevBuf<uint8_t> d_out;
+    HIP_TRY(d_out.alloc_bytes(std::max<size_t>(bytes, 16)));
+    HIP_TRY(hipMemcpy(d_out.get(), rgb8, bytes, hipMemcpyHostToDevice));
+    hipStream_t st = h->d->stream.get();
+    int rc = mcpt_progressive_display_device(h, source, p, d_out.get(), info, st);
+    const hipError_t e = hipStreamSynchronize(st);        // also on failure: nothing enqueued may still use the copy when it goes
+    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    if (rc == MCPT_OK) HIP_TRY(hipMemcpy(rgb8, d_out.get(), bytes, hipMemcpyDeviceToHost));
+    return rc;
 }
 
 int mcpt_progressive_next_pass(int32_t spp, int32_t done, double remaining_s, double s_per_sample)

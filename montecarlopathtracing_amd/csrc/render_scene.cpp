@@ -294,27 +294,39 @@ int mcpt_render_scene_env(const char* path, const char* filename, int32_t spp, c
 // every render_scene entry point ends here (light_sampling == null: MCPT_LIGHTS_ALL)
 static int render_scene_impl(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
                              const mcpt_lens* lens, const char* environment_pfm, double environment_scale, const char* end_obj,
-                             const char* end_camera, const mcpt_shutter* shutter, const mcpt_light_sampling* light_sampling, mcpt_stats* stats);
+                             const char* end_camera, const mcpt_shutter* shutter, const mcpt_light_sampling* light_sampling,
+                             const mcpt_display_params* display, mcpt_stats* stats);
 
 int mcpt_render_scene_motion(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
                              const mcpt_lens* lens, const char* environment_pfm, double environment_scale, const char* end_obj,
                              const char* end_camera, const mcpt_shutter* shutter, mcpt_stats* stats)
 {
-    return render_scene_impl(path, filename, spp, opt, opt_bytes, lens, environment_pfm, environment_scale, end_obj, end_camera, shutter, nullptr, stats);
+    return render_scene_impl(path, filename, spp, opt, opt_bytes, lens, environment_pfm, environment_scale, end_obj, end_camera, shutter, nullptr, nullptr, stats);
 }
 
 int mcpt_render_scene_lights(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
                              const mcpt_lens* lens, const char* environment_pfm, double environment_scale, const mcpt_light_sampling* light_sampling,
                              mcpt_stats* stats)
 {
-    return render_scene_impl(path, filename, spp, opt, opt_bytes, lens, environment_pfm, environment_scale, nullptr, nullptr, nullptr, light_sampling, stats);
+    return mcpt_render_scene_display(path, filename, spp, opt, opt_bytes, lens, environment_pfm, environment_scale, light_sampling, nullptr, stats);
+}
+
+int mcpt_render_scene_display(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
+                              const mcpt_lens* lens, const char* environment_pfm, double environment_scale, const mcpt_light_sampling* light_sampling,
+                              const mcpt_display_params* display, mcpt_stats* stats)
+{
+    return render_scene_impl(path, filename, spp, opt, opt_bytes, lens, environment_pfm, environment_scale, nullptr, nullptr, nullptr, light_sampling,
+                             display, stats);
 }
 
 static int render_scene_impl(const char* path, const char* filename, int32_t spp, const mcpt_render_scene_options* opt, int64_t opt_bytes,
                              const mcpt_lens* lens, const char* environment_pfm, double environment_scale, const char* end_obj,
-                             const char* end_camera, const mcpt_shutter* shutter, const mcpt_light_sampling* light_sampling, mcpt_stats* stats)
+                             const char* end_camera, const mcpt_shutter* shutter, const mcpt_light_sampling* light_sampling,
+                             const mcpt_display_params* display, mcpt_stats* stats)
 {
     if (!path || !filename || spp <= 0 || opt_bytes < 0 || (opt_bytes > 0 && !opt)) return fail(MCPT_ERR_ARG, "bad argument");
+    if (int drc = display_check(display)) return drc;
+    if (display && (display->flags & MCPT_DISPLAY_RGBA)) return fail(MCPT_ERR_ARG, "render_scene writes RGB pictures: MCPT_DISPLAY_RGBA is refused");
     if (int lrc = lens_check(lens)) return lrc;
     if (int src = light_sampling_check(light_sampling)) return src;
     if (shutter) { if (int src = shutter_check(shutter)) return src; }
@@ -441,11 +453,17 @@ static int render_scene_impl(const char* path, const char* filename, int32_t spp
     if (rc == MCPT_OK) {
         if (talk) std::printf("Phase 2(ray tracing) = %.3f ms\n", std::chrono::duration<double, std::milli>(t2 - t1).count());
         std::vector<uint8_t> rgb(img.size());
-        mcpt_quantize_rgb8(img.data(), int64_t(img.size()), rgb.data());
+        // a frame's picture: imshow's bytes, or -- with display parameters -- the display transform's (the frame is on the host by now)
+        const auto picture = [&](const std::vector<double>& frame) {
+            return display ? mcpt_display_host(frame.data(), int64_t(frame.size() / 3), display, rgb.data(), nullptr)
+                           : mcpt_quantize_rgb8(frame.data(), int64_t(frame.size()), rgb.data());
+        };
+        rc = picture(img);
         const std::string prefix = o.output_prefix ? std::string(o.output_prefix) : std::string("../result/") + filename;
         const std::string stem = prefix + "-SPP" + std::to_string(rendered);            // imshow, MTPC.cpp:17-20 (a progressive frame stopped early: its own count)
-        rc = (o.output_flags & MCPT_OUT_PNG_DEFLATE) ? mcpt_write_png_deflate((stem + ".png").c_str(), rgb.data(), s.width, s.height)
-                                                      : mcpt_write_png((stem + ".png").c_str(), rgb.data(), s.width, s.height);
+        if (rc == MCPT_OK)
+            rc = (o.output_flags & MCPT_OUT_PNG_DEFLATE) ? mcpt_write_png_deflate((stem + ".png").c_str(), rgb.data(), s.width, s.height)
+                                                          : mcpt_write_png((stem + ".png").c_str(), rgb.data(), s.width, s.height);
         if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_PFM)) rc = mcpt_write_pfm((stem + ".pfm").c_str(), img.data(), s.width, s.height);
         if (rc == MCPT_OK && !err_img.empty()) rc = mcpt_write_pfm((stem + ".err.pfm").c_str(), err_img.data(), s.width, s.height);
         if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_SPP_PFM)) {
@@ -455,9 +473,9 @@ static int render_scene_impl(const char* path, const char* filename, int32_t spp
             rc = mcpt_write_pfm((stem + ".spp.pfm").c_str(), spp_img.data(), s.width, s.height);
         }
         if (rc == MCPT_OK && !denoised.empty()) {
-            mcpt_quantize_rgb8(denoised.data(), int64_t(denoised.size()), rgb.data());
+            rc = picture(denoised);
             const std::string dn = stem + ".denoised";
-            rc = (o.output_flags & MCPT_OUT_PNG_DEFLATE) ? mcpt_write_png_deflate((dn + ".png").c_str(), rgb.data(), s.width, s.height)
+            if (rc == MCPT_OK) rc = (o.output_flags & MCPT_OUT_PNG_DEFLATE) ? mcpt_write_png_deflate((dn + ".png").c_str(), rgb.data(), s.width, s.height)
                                                           : mcpt_write_png((dn + ".png").c_str(), rgb.data(), s.width, s.height);
             if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_PFM)) rc = mcpt_write_pfm((dn + ".pfm").c_str(), denoised.data(), s.width, s.height);
         }
@@ -468,9 +486,9 @@ static int render_scene_impl(const char* path, const char* filename, int32_t spp
                 if (rc == MCPT_OK) rc = mcpt_write_pfm((stem + f.first).c_str(), f.second->data(), s.width, s.height);
         }
         if (rc == MCPT_OK && !guided.empty()) {
-            mcpt_quantize_rgb8(guided.data(), int64_t(guided.size()), rgb.data());
+            rc = picture(guided);
             const std::string dn = stem + ".denoised-samples";
-            rc = (o.output_flags & MCPT_OUT_PNG_DEFLATE) ? mcpt_write_png_deflate((dn + ".png").c_str(), rgb.data(), s.width, s.height)
+            if (rc == MCPT_OK) rc = (o.output_flags & MCPT_OUT_PNG_DEFLATE) ? mcpt_write_png_deflate((dn + ".png").c_str(), rgb.data(), s.width, s.height)
                                                           : mcpt_write_png((dn + ".png").c_str(), rgb.data(), s.width, s.height);
             if (rc == MCPT_OK && (o.output_flags & MCPT_OUT_PFM)) rc = mcpt_write_pfm((dn + ".pfm").c_str(), guided.data(), s.width, s.height);
         }
