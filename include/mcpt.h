@@ -877,6 +877,53 @@ int mcpt_render_scene_display(const char* path, const char* filename, int32_t sp
                               const mcpt_lens*, const char* environment_pfm, double environment_scale, const mcpt_light_sampling*,
                               const mcpt_display_params* display, mcpt_stats* stats);
 
+/* ---- radiance queries (since the query change; the reference reaches its path tracer through the scene's camera only) ---- */
+/* A QUERY LIST gives the path tracer n rays, or n surface points, of the caller's: light probes and lightmaps, reflection probes, a
+ * projection the .camera file cannot express, the radiance along a few rays.  Every query gets spp path samples and its answer is their
+ * mean, the standard error of that mean and the number of samples whose ray hit anything.  MCPT_VERSION stays 105: detect the block by
+ * symbol.  fp64, no contraction, sums in the order written.
+ *   keys     : query i has id ids[i], or i when ids == NULL; ids are >= 0.  Its sample j = 0 .. spp-1 is sample index k = sample_base + j,
+ *              and the path of (i, k) uses the RNG key (seed, pixel = id, sample = k) -- the key of camera sample (pixel, k).  Nothing else of
+ *              a frame enters: the scene's width, height and camera and the device's lens do not affect a query.  A query whose rays are
+ *              a frame's camera rays and whose ids are their pixels computes that frame's samples, bit for bit.
+ *   MCPT_QUERY_RAY        : q = origin o, direction d.  Every sample traces the ray (o, d) as given, from o itself (the camera rays'
+ *              convention, no offset).  d must have unit length: the host-pointer form refuses a component that is not finite and
+ *              | |d|^2 - 1 | > 1e-9, |d|^2 = (dx dx + dy dy) + dz dz; the device form does not look.
+ *   MCPT_QUERY_HEMISPHERE : q = position a, normal b of any non-zero finite length.  n^ = b / sqrt((bx bx + by by) + bz bz); e = the
+ *              coordinate axis on which |n^| is smallest, the lowest axis among equals; t = normalize(cross(e, n^)), s = cross(n^, t),
+ *              cross(p, q) = (py qz - qy pz, qx pz - px qz, px qy - qx py); u0, u1 = words 0 and 1 of the camera-uniform block
+ *              uniform(seed, id, k, depth 0xFFFF, slot 0..3) the lens draws from (a query has no lens: nothing collides);
+ *              r = sqrt(u0), phi = (2 pi) * u1 with the full-precision pi, z = sqrt(max(0, 1 - u0));
+ *              d = normalize((t * (r cos phi) + s * (r sin phi)) + n^ * z), o = a + d * 0.01 (the shadow rays' offset).
+ *              d is cosine-weighted about n^, so the mean is the cosine-weighted mean of the incoming radiance: THE IRRADIANCE IS
+ *              pi TIMES THE MEAN (and its standard error pi times the standard error).
+ *   shading  : the ray is a camera ray of the per-sample route (camera lens above).  Its first hit is shaded at depth 0 under the unchanged
+ *              rules and draws; a ray that reaches an emitter returns the light's radiance unweighted; a ray that leaves the scene gives
+ *              +0.0, or Le(d) under an active environment.  Environment, light sampling and trace mode are the device's.  A device that
+ *              holds a motion answers from key 0, as every call that is not a frame.
+ *   fold     : per query and channel, in k order: s1 += x, s2 += x * x; mean = s1 / spp; stderr = 0 when spp < 2, else
+ *              sqrt(max((s2 - s1 * s1 / spp) / (spp - 1), 0) / spp) -- the expressions of a progressive frame's estimate and error.
+ *              hits[i] = the samples of query i whose ray hit anything.  mean3 is required; stderr3 and hits may be NULL.
+ *   stats    : rays_primary = samples = n * spp; the other counters as for a frame under a lens.
+ *   flags    : 0, the wavefront pipeline, or MCPT_RENDER_MEGAKERNEL.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE): spp < 1, sample_base < 0, sample_base + spp > 2^31 - 1, n < 0 or n > 2^31 - 1, an
+ * unknown kind or flag, reserved != 0, NULL q6 or mean3 with n > 0 and, in the host-pointer forms, a negative id, a component that is not
+ * finite, a direction that is not unit, a normal of length zero or not finite.  n == 0: MCPT_OK, nothing is launched.
+ * The host-pointer form is synchronous.  The device form (device pointers throughout) enqueues on `stream` and returns without waiting
+ * when stats == NULL.  Both use the device's frame slot 0 and first wait for the device's frames still in flight (MCPT_RENDER_PIPELINE /
+ * KEEP_STATS).  Queries are allowed while progressive handles of the device live: they touch none of a handle's state.
+ * Not covered: the multi-device group, render_scene, per-query sample counts, adaptive stopping of queries. */
+#define MCPT_QUERY_RAY        0   /* q = origin xyz, direction xyz */
+#define MCPT_QUERY_HEMISPHERE 1   /* q = position xyz, normal xyz  */
+typedef struct { int32_t spp, sample_base; uint64_t seed; int32_t kind, flags, reserved[2]; } mcpt_query_params;
+int mcpt_query_radiance(mcpt_device*, const double* q6, const int32_t* ids, int64_t n, const mcpt_query_params*,
+                        double* mean3, double* stderr3, int32_t* hits, mcpt_stats*);
+int mcpt_query_radiance_device(mcpt_device*, const double* d_q6, const int32_t* d_ids, int64_t n, const mcpt_query_params*,
+                               double* d_mean3, double* d_stderr3, int32_t* d_hits, mcpt_stats*, void* stream);
+/* test seam: the ray of sample k[i] of query i -> rays6[n*6] = origin xyz, direction xyz (k[i] >= 0) */
+int mcpt_query_rays(mcpt_device*, const double* q6, const int32_t* ids, int64_t n, uint64_t seed, int32_t kind,
+                    const int32_t* k, double* rays6);
+
 #ifdef __cplusplus
 }
 #endif

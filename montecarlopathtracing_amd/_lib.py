@@ -154,6 +154,12 @@ class DisplayInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class QueryParams(C.Structure):
+    """mcpt_query_params: samples per query, first sample index, seed, kind and flags of a radiance query"""
+    _fields_ = [("spp", C.c_int32), ("sample_base", C.c_int32), ("seed", C.c_uint64), ("kind", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -187,6 +193,7 @@ EXPORTS = [
     "mcpt_scene_light_tree", "mcpt_scene_light_tree_pdf", "mcpt_light_pick_at",
     "mcpt_display_histogram_device", "mcpt_display_histogram", "mcpt_display_exposure", "mcpt_display_device", "mcpt_display",
     "mcpt_display_host", "mcpt_progressive_display", "mcpt_progressive_display_device", "mcpt_render_scene_display",
+    "mcpt_query_radiance", "mcpt_query_radiance_device", "mcpt_query_rays",
 ]
 
 
@@ -355,6 +362,10 @@ def lib():
     L.mcpt_progressive_display_device.argtypes = [P, C.c_int32, DP, P, DI, P]
     L.mcpt_render_scene_display.argtypes = [C.c_char_p, C.c_char_p, C.c_int32, C.POINTER(RenderSceneOptions), C.c_int64, C.POINTER(Lens), C.c_char_p,
                                             C.c_double, C.POINTER(LightSampling), DP, C.POINTER(Stats)]
+    QP = C.POINTER(QueryParams)
+    L.mcpt_query_radiance.argtypes = [P, D, I32, C.c_int64, QP, D, D, I32, C.POINTER(Stats)]
+    L.mcpt_query_radiance_device.argtypes = [P, P, P, C.c_int64, QP, P, P, P, C.POINTER(Stats), P]
+    L.mcpt_query_rays.argtypes = [P, D, I32, C.c_int64, C.c_uint64, C.c_int32, I32, D]
     _lib = L
     return L
 

@@ -1,12 +1,13 @@
 """Python face of libmcpt's C ABI, named after the reference's own functions and types
 (render_scene / scene_data / BVH / ray_intersect / generateImg / imshow)."""
 import ctypes as C
+import math
 import numbers
 
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -22,6 +23,8 @@ FAST_BUILT_HOST, FAST_BUILT_DEVICE_FAST, FAST_BUILT_DEVICE_PLOC, FAST_BUILT_PLOC
 SCENE_DEFER_BUILD = 1
 GATHER_PEER, GATHER_RCCL = 0, 1
 LENS_JITTER, LENS_PER_SAMPLE = 1, 2
+QUERY_RAY, QUERY_HEMISPHERE = 0, 1
+_QUERY_KINDS = {"ray": QUERY_RAY, "hemisphere": QUERY_HEMISPHERE}
 
 
 def _p(a, t):
@@ -504,6 +507,63 @@ class Device:
         k = np.ascontiguousarray(k, dtype=np.int32)
         rays = np.zeros((pix.shape[0], 6))
         check(lib().mcpt_camera_rays(self._h, seed, _p(pix, C.c_int32), _p(k, C.c_int32), pix.shape[0], _p(rays, C.c_double)))
+        return rays
+
+    @staticmethod
+    def _query_list(q, ids, what="rays"):
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        if q.ndim != 2 or q.shape[1] != 6:
+            raise ValueError("%s must have shape (n, 6), not %r" % (what, q.shape))
+        if ids is not None:
+            ids = np.asarray(ids)
+            if ids.dtype.kind not in "iu" or ids.shape != (q.shape[0],):
+                raise ValueError("ids must be %d integers" % q.shape[0])
+            if ids.size and (int(ids.min()) < -2 ** 31 or int(ids.max()) >= 2 ** 31):
+                raise ValueError("ids must fit 32 bits")
+            ids = np.ascontiguousarray(ids, dtype=np.int32)
+        return q, ids
+
+    def _query(self, q, ids, spp, seed, sample_base, kind, flags, stats):
+        for name, v in (("spp", spp), ("sample_base", sample_base), ("flags", flags)):
+            if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError("%s must be a 32-bit integer" % name)
+        n = q.shape[0]
+        mean, err, hits = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros(n, dtype=np.int32)
+        qp = QueryParams(int(spp), int(sample_base), int(seed), kind, int(flags), (C.c_int32 * 2)(0, 0))
+        check(lib().mcpt_query_radiance(self._h, _p(q, C.c_double), _p(ids, C.c_int32), n, C.byref(qp), _p(mean, C.c_double),
+                                        _p(err, C.c_double), _p(hits, C.c_int32), C.byref(stats) if stats is not None else None))
+        return mean, err, hits
+
+    def radiance(self, rays, spp, seed=0, ids=None, sample_base=0, flags=0, stats=None):
+        """Path-traced radiance along the caller's rays (mcpt_query_radiance, MCPT_QUERY_RAY): rays (n, 6) = origin, unit direction;
+        query i takes samples sample_base .. sample_base + spp - 1 under the RNG key (seed, ids[i] or i, sample).  Returns
+        (mean [n,3], stderr [n,3], hits [n])."""
+        q, ids = self._query_list(rays, ids)
+        return self._query(q, ids, spp, seed, sample_base, QUERY_RAY, flags, stats)
+
+    def irradiance(self, points, normals, spp, seed=0, ids=None, sample_base=0, flags=0, stats=None):
+        """Irradiance at surface points (mcpt_query_radiance, MCPT_QUERY_HEMISPHERE): cosine-weighted directions about each normal, from
+        0.01 off the point; E = pi * mean.  Returns (E [n,3], E_stderr [n,3], hits [n])."""
+        points = np.asarray(points, dtype=np.float64)
+        normals = np.asarray(normals, dtype=np.float64)
+        if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+            raise ValueError("points and normals must both have shape (n, 3)")
+        q, ids = self._query_list(np.concatenate([points, normals], axis=1), ids, "points and normals")
+        mean, err, hits = self._query(q, ids, spp, seed, sample_base, QUERY_HEMISPHERE, flags, stats)
+        return math.pi * mean, math.pi * err, hits
+
+    def query_rays(self, q, seed, k, kind="ray", ids=None):
+        """test seam (mcpt_query_rays): the ray of sample k[i] of query i, (n, 6) = origin, direction; kind is "ray" or "hemisphere" """
+        if kind not in _QUERY_KINDS:
+            raise ValueError('kind must be "ray" or "hemisphere"')
+        q, ids = self._query_list(q, ids, "q")
+        k = np.asarray(k)
+        if k.dtype.kind not in "iu" or k.shape != (q.shape[0],):
+            raise ValueError("k must be %d integers" % q.shape[0])
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        rays = np.zeros((q.shape[0], 6))
+        check(lib().mcpt_query_rays(self._h, _p(q, C.c_double), _p(ids, C.c_int32), q.shape[0], int(seed), _QUERY_KINDS[kind], _p(k, C.c_int32),
+                                    _p(rays, C.c_double)))
         return rays
 
     def set_environment(self, rgb=None, scale=1.0):

@@ -122,6 +122,16 @@ struct DLens {
     int32_t flags, pad;
 };
 
+// A query list on the device and where its fold goes (mcpt_query_radiance; query.hpp: query_ray): entry i of q6 is query i, slot i of the
+// call; its id is the call's slot list's, or i.
+struct DQuery {
+    const double* q6;           // [n][6] origin + direction (MCPT_QUERY_RAY), or position + normal (MCPT_QUERY_HEMISPHERE)
+    int kind;
+    double* mean3;              // [n][3]
+    double* stderr3;            // [n][3] or null
+    int32_t* hits;              // [n] or null
+};
+
 // The environment light of a frame (env.hpp; tables built by environment.cpp).  All zero: none -- or an inactive one, Z == 0 -- and the
 // kernels are the instantiations without it.
 struct DEnv {

@@ -3,6 +3,7 @@
 //   scene_api.cpp     scene handles, the tile partition, the trace engine of a scene, the shared culling hierarchy
 //   device.cpp        device creation stage by stage, hierarchy queries, closest hit
 //   render.cpp        lenses, the integrator (megakernel and wavefront), mcpt_render*, statistics, (pixel, sample) queries
+//   query_api.cpp     radiance queries: the integrator behind a caller's rays and surface points
 //   progressive.cpp   progressive frames, AOVs, the denoiser
 //   light_sampling.cpp  MCPT_LIGHTS_ONE and MCPT_LIGHTS_TREE: the pick table, the light tree, their upload, the picks' test seams
 //   motion.cpp        a device's motion: the shutter's steps between two keyframes, the return to key 0
@@ -280,6 +281,10 @@ struct SampleRange {
     int32_t* hitcnt;            // progressive passes under an active lens: per pixel, the samples whose camera ray hit
     const mcpt::EnvData* env;   // the environment of the call (the device's, or the one a progressive handle took); null: none
     bool motion = false;        // a piece of a motion frame (mom != null): a pixel's primary ray may hit in one step and miss in another
+    // A radiance query (query_api.cpp): the call's slots are the entries of this list, not pixels -- sample k of slot s traces the list's
+    // ray through the per-sample route and is folded into the list's own outputs (d_img, mom, hit, lens and hitcnt are not read; the
+    // PixelList holds the ids, or null for the slot itself).  Null: a frame or a pass.
+    const mcpt::DQuery* query = nullptr;
 };
 
 // The pixels a render call covers, on the device: the partition's owned list (mcpt_render*, uniform progressive passes) or an adaptive

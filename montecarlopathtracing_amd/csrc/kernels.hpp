@@ -70,6 +70,15 @@ void launch_sample_radiance_lens(const DScene& S, const DLens& lens, unsigned lo
 // (env active: a camera ray that missed has radiance Le, and every sample is folded)
 void launch_fold_lens(const double* d_rad, const uint8_t* d_flags, const int32_t* d_pixels, int first_slot, int n_slots, int n, int k0, int N,
                       double* d_img, double* d_mom, uint8_t* d_hit, int32_t* d_hitcnt, bool env, hipStream_t st);
+// ---- radiance queries (query.hip)
+// the megakernel form of a query list: lane (slot, j) -> d_rad[(s*spp + j)*3], d_flags[s*spp + j], s = the slot within the chunk
+void launch_query_samples(const DScene& S, const DQuery& q, unsigned long long seed, const int32_t* d_ids, int first_slot, int n_slots, int spp,
+                          int sample_base, double* d_rad, uint8_t* d_flags, DCounters* ctr, hipStream_t st);
+// the fold of a chunk's n samples per slot into q's outputs at slots first_slot .. first_slot + n_slots; env: a missed ray's radiance is
+// Le of its direction (else +0.0)
+void launch_query_fold(const DQuery& q, const double* d_rad, const uint8_t* d_flags, int first_slot, int n_slots, int n, bool env, hipStream_t st);
+// test seam: the ray of sample d_k[i] of query i
+void launch_query_rays(const DQuery& q, unsigned long long seed, const int32_t* d_ids, const int32_t* d_k, long long n, double* d_rays6, hipStream_t st);
 // launch_fold_progressive for a piece of a motion frame (camera.hip): a pixel's primary ray may hit in one piece and miss in another, so a
 // missed piece's samples (0, or Le under an environment) continue the fold and the moments; d_hit[pix] = hit in some piece so far
 void launch_fold_motion(const double* d_rad, const int32_t* d_pixels, const PrimaryHit* d_hits, int first_slot, int n_slots, int n, int k0, int N,

@@ -1,0 +1,151 @@
+// C ABI, radiance queries (include/mcpt.h: mcpt_query_radiance*, mcpt_query_rays): the integrator behind a caller's list of rays or
+// surface points.  The list is the sample source of an ordinary render call (render.cpp: the per-sample route with a query pass for the
+// camera pass and the query fold for the frame's), so chunking, engines, hand-over and statistics are the frame's own.
+#include <hip/hip_runtime_api.h>
+
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <string>
+
+#include "handles.hpp"
+
+using namespace mcpt;
+
+static constexpr int64_t kInt32Max = std::numeric_limits<int32_t>::max();
+
+static int kind_check(int32_t kind)
+{
+    return kind == MCPT_QUERY_RAY || kind == MCPT_QUERY_HEMISPHERE ? MCPT_OK : fail(MCPT_ERR_ARG, "unknown query kind");
+}
+static int count_check(int64_t n)
+{
+    return n >= 0 && n <= kInt32Max ? MCPT_OK : fail(MCPT_ERR_ARG, "the number of queries must be in 0 .. 2^31 - 1");
+}
+
+// what both forms of mcpt_query_radiance refuse without looking at the list
+static int params_check(const mcpt_query_params* p, int64_t n, const void* q6, const void* mean3)
+{
+    if (!p) return fail(MCPT_ERR_ARG, "null query parameters");
+    if (p->spp < 1) return fail(MCPT_ERR_ARG, "spp must be >= 1");
+    if (p->sample_base < 0) return fail(MCPT_ERR_ARG, "sample_base must be >= 0");
+    if (int64_t(p->sample_base) + int64_t(p->spp) > kInt32Max) return fail(MCPT_ERR_ARG, "sample_base + spp must not exceed 2^31 - 1");
+    if (const int rc = count_check(n)) return rc;
+    if (const int rc = kind_check(p->kind)) return rc;
+    if (p->flags != 0 && p->flags != MCPT_RENDER_MEGAKERNEL) return fail(MCPT_ERR_ARG, "unknown query flag (0 or MCPT_RENDER_MEGAKERNEL)");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(MCPT_ERR_ARG, "mcpt_query_params.reserved must be 0");
+    if (n > 0 && (!q6 || !mean3)) return fail(MCPT_ERR_ARG, "null query list or mean");
+    return MCPT_OK;
+}
+
+// what the host-pointer forms refuse of the list itself
+static int list_check(const double* q6, const int32_t* ids, int64_t n, int32_t kind)
+{
+    for (int64_t i = 0; i < n; i++) {
+        if (ids && ids[i] < 0) return fail(MCPT_ERR_ARG, "query " + std::to_string(i) + ": negative id");
+        const double* q = q6 + i * 6;
+        for (int c = 0; c < 6; c++)
+            if (!std::isfinite(q[c])) return fail(MCPT_ERR_ARG, "query " + std::to_string(i) + ": component that is not finite");
+        const double l2 = (q[3] * q[3] + q[4] * q[4]) + q[5] * q[5];
+        if (kind == MCPT_QUERY_RAY) {
+            if (!(std::fabs(l2 - 1.0) <= 1e-9)) return fail(MCPT_ERR_ARG, "query " + std::to_string(i) + ": the direction must have unit length");
+        } else {
+            const double l = std::sqrt(l2);
+            if (!(std::isfinite(l) && l > 0.0)) return fail(MCPT_ERR_ARG, "query " + std::to_string(i) + ": the normal must have a non-zero finite length");
+        }
+    }
+    return MCPT_OK;
+}
+
+extern "C" {
+
+int mcpt_query_radiance_device(mcpt_device* d, const double* d_q6, const int32_t* d_ids, int64_t n, const mcpt_query_params* p, double* d_mean3,
+                               double* d_stderr3, int32_t* d_hits, mcpt_stats* stats, void* stream)
+{
+    if (const int rc = params_check(p, n, d_q6, d_mean3)) return rc;
+    if (const int rc = require_device()) return rc;
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return MCPT_OK;
+    if (const int rc = motion_home(d)) return rc;           // a device that holds a motion answers from key 0
+    if (const int rc = geometry_gate(d)) return rc;
+    if (const int rc = wait_for_frames(d)) return rc;       // the call uses frame slot 0 and the device's look stream
+    mcpt_render_params rp{};
+    rp.spp = p->spp; rp.seed = p->seed; rp.world = 1; rp.flags = p->flags;
+    const DQuery q{d_q6, p->kind, d_mean3, d_stderr3, d_hits};
+    SampleRange r{p->sample_base, p->spp, p->spp, nullptr, nullptr, nullptr, nullptr, d->env.get()};
+    r.query = &q;
+    // a call that fails half-way must not leave half-recorded event pairs behind (render.cpp: mcpt_render_device)
+    const size_t ev_used0 = d->ev_used;
+    int slot_used = -1;
+    const int rc = render_device_impl(d, r, PixelList{d_ids, n}, &rp, nullptr, stats, static_cast<hipStream_t>(stream), slot_used);
+    if (rc != MCPT_OK) d->ev_used = ev_used0;
+    return rc;
+}
+
+int mcpt_query_radiance(mcpt_device* d, const double* q6, const int32_t* ids, int64_t n, const mcpt_query_params* p, double* mean3, double* stderr3,
+                        int32_t* hits, mcpt_stats* stats)
+{
+    if (const int rc = params_check(p, n, q6, mean3)) return rc;
+    if (const int rc = list_check(q6, ids, n, p->kind)) return rc;
+    if (const int rc = require_device()) return rc;
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    if (n == 0) return MCPT_OK;
+    HIP_TRY(hipSetDevice(d->ordinal));
+    // the caller's arrays are pageable host memory: blocking copies on either side of the call, which itself is ordered on d->stream
+    DevBuf<double> d_q, d_mean, d_err;
+    DevBuf<int32_t> d_ids, d_hits;
+    const size_t sn = size_t(n);
+    HIP_TRY(d_q.alloc(sn * 6));
+    HIP_TRY(d_mean.alloc(sn * 3));
+    if (stderr3) HIP_TRY(d_err.alloc(sn * 3));
+    if (hits) HIP_TRY(d_hits.alloc(sn));
+    if (ids) HIP_TRY(d_ids.alloc(sn));
+    HIP_TRY(hipMemcpy(d_q.get(), q6, sn * 6 * sizeof(double), hipMemcpyHostToDevice));
+    if (ids) HIP_TRY(hipMemcpy(d_ids.get(), ids, sn * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipStream_t st = d->stream.get();
+    int rc = mcpt_query_radiance_device(d, d_q.get(), ids ? d_ids.get() : nullptr, n, p, d_mean.get(), stderr3 ? d_err.get() : nullptr,
+                                        hits ? d_hits.get() : nullptr, stats, st);
+    const hipError_t e = hipStreamSynchronize(st);          // also on failure: nothing enqueued may still use a copy when it goes
+    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    if (rc != MCPT_OK) return rc;
+    HIP_TRY(hipMemcpy(mean3, d_mean.get(), sn * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (stderr3) HIP_TRY(hipMemcpy(stderr3, d_err.get(), sn * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (hits) HIP_TRY(hipMemcpy(hits, d_hits.get(), sn * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
+
+int mcpt_query_rays(mcpt_device* d, const double* q6, const int32_t* ids, int64_t n, uint64_t seed, int32_t kind, const int32_t* k, double* rays6)
+{
+    if (const int rc = count_check(n)) return rc;
+    if (const int rc = kind_check(kind)) return rc;
+    if (n > 0 && (!q6 || !k || !rays6)) return fail(MCPT_ERR_ARG, "null argument");
+    for (int64_t i = 0; i < n; i++)
+        if (k[i] < 0) return fail(MCPT_ERR_ARG, "query " + std::to_string(i) + ": negative sample index");
+    if (const int rc = list_check(q6, ids, n, kind)) return rc;
+    if (const int rc = require_device()) return rc;
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (n == 0) return MCPT_OK;
+    HIP_TRY(hipSetDevice(d->ordinal));
+    DevBuf<double> d_q, d_rays;
+    DevBuf<int32_t> d_ids, d_k;
+    const size_t sn = size_t(n);
+    HIP_TRY(d_q.alloc(sn * 6));
+    HIP_TRY(d_rays.alloc(sn * 6));
+    HIP_TRY(d_k.alloc(sn));
+    if (ids) HIP_TRY(d_ids.alloc(sn));
+    HIP_TRY(hipMemcpy(d_q.get(), q6, sn * 6 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_k.get(), k, sn * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (ids) HIP_TRY(hipMemcpy(d_ids.get(), ids, sn * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipStream_t st = d->stream.get();
+    launch_query_rays(DQuery{d_q.get(), kind, nullptr, nullptr, nullptr}, seed, ids ? d_ids.get() : nullptr, d_k.get(), n, d_rays.get(), st);
+    hipError_t e = hipGetLastError();
+    const hipError_t es = hipStreamSynchronize(st);
+    if (e == hipSuccess) e = es;
+    if (e == hipSuccess) e = hipMemcpy(rays6, d_rays.get(), sn * 6 * sizeof(double), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    return MCPT_OK;
+}
+
+}  // extern "C"

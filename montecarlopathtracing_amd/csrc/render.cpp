@@ -112,11 +112,21 @@ static int prepare_partition(mcpt_device* d, const mcpt_render_params* p, hipStr
     return MCPT_OK;
 }
 
+// Where the camera samples of a render call come from.  The per-pixel route: neither (the pixel's shared primary hit).  The per-sample
+// route: an active lens (a camera ray per sample, camera.hip) or a query list (the caller's ray per sample, query.hip) -- one source
+// pass, the same trace and logic launches after it, and the source's own fold.
+struct SampleSource {
+    const DLens* lens = nullptr;
+    const DQuery* query = nullptr;
+    bool per_sample() const { return lens || query; }
+};
+
 // (S.env active: a missed pixel -- or camera ray -- folds the environment's radiance; d_dirs: the pinhole's primary directions)
 static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, int first, int n_slots, double* d_img, bool lensed, const DScene& S,
                        const double* d_dirs, hipStream_t st)
 {
-    if (r.motion && !lensed) launch_fold_motion(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, S.env, d_dirs, st);
+    if (r.query) launch_query_fold(*r.query, f.rad.get(), f.cam_hit.get(), first, n_slots, r.n, env_on(S.env), st);
+    else if (r.motion && !lensed) launch_fold_motion(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, S.env, d_dirs, st);
     else if (lensed) launch_fold_lens(f.rad.get(), f.cam_hit.get(), L.pixels, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, r.hitcnt, env_on(S.env), st);
     else if (r.mom) launch_fold_progressive(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, S.env, d_dirs, st);
     else launch_fold_samples(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, d_img, S.env, d_dirs, st);
@@ -125,19 +135,21 @@ static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const Pi
 // megakernel path: one lane per camera sample, the whole path in one kernel (kept for A/B runs and as a second
 // implementation the wavefront path is checked against)
 static int render_megakernel(mcpt_device* d, const DScene& S, mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, const mcpt_render_params* p,
-                             double* d_img, bool timed, const DLens* lens, hipStream_t st, double& ms_trace, int& launches)
+                             double* d_img, bool timed, const SampleSource& src, hipStream_t st, double& ms_trace, int& launches)
 {
     const int64_t npx = L.n;
     const int spp = r.n;
-    const size_t per_pixel = size_t(spp) * 3 * sizeof(double) + (lens ? size_t(spp) : 0);   // (+ the hit flag of every sample under a lens)
+    const bool per_sample = src.per_sample();
+    const size_t per_pixel = size_t(spp) * 3 * sizeof(double) + (per_sample ? size_t(spp) : 0);   // (+ the hit flag of every sample under a lens)
     int64_t chunk = int64_t(std::max<size_t>(d->sample_budget_bytes / per_pixel, 64));
     chunk = std::min<int64_t>(chunk, npx);
     HIP_TRY(f.rad.grow_bytes(size_t(chunk) * per_pixel));
-    if (lens) HIP_TRY(f.cam_hit.grow(size_t(chunk * spp)));
+    if (per_sample) HIP_TRY(f.cam_hit.grow(size_t(chunk * spp)));
     for (int64_t first = 0; first < npx; first += chunk) {
         const int n_slots = int(std::min<int64_t>(chunk, npx - first));
         if (timed) HIP_TRY(hipEventRecord(d->ev[2].get(), st));
-        if (lens) launch_shade_samples_lens(S, *lens, p->seed, L.pixels, int(first), n_slots, spp, r.k0, f.rad.get(), f.cam_hit.get(), f.ctr.get(), st);
+        if (src.query) launch_query_samples(S, *src.query, p->seed, L.pixels, int(first), n_slots, spp, r.k0, f.rad.get(), f.cam_hit.get(), f.ctr.get(), st);
+        else if (per_sample) launch_shade_samples_lens(S, *src.lens, p->seed, L.pixels, int(first), n_slots, spp, r.k0, f.rad.get(), f.cam_hit.get(), f.ctr.get(), st);
         else launch_shade_samples(S, p->seed, d->dirs.get(), L.pixels, f.hits.get(), int(first), n_slots, spp, r.k0, f.rad.get(), f.ctr.get(), st);
         HIP_TRY(hipGetLastError());
         if (timed) {
@@ -148,7 +160,7 @@ static int render_megakernel(mcpt_device* d, const DScene& S, mcpt_device::Frame
             ms_trace += ms;
         }
         launches++;
-        fold_range(f, r, L, int(first), n_slots, d_img, lens != nullptr, S, d->dirs.get(), st);
+        fold_range(f, r, L, int(first), n_slots, d_img, per_sample, S, d->dirs.get(), st);
         HIP_TRY(hipGetLastError());
     }
     return MCPT_OK;
@@ -157,13 +169,14 @@ static int render_megakernel(mcpt_device* d, const DScene& S, mcpt_device::Frame
 // wavefront path (wavefront.hpp): per chunk, lockstep iterations of logic + trace over compacted path state in HBM.
 // timed: event pairs around the trace launches, summed here (one stream synchronisation at the end); keep: the pairs are recorded
 // and left in d->ev_pool for mcpt_device_collect_stats -- the frame ends without the host waiting for it.
-// lens (non-null: an active lens): the per-sample route -- per chunk a camera pass (the camera as vertex -1 of every sample) and a trace
-// launch of its rays, then the logic passes from depth 0 on, every vertex in the path state (WfArgs::hits == null)
+// src (a lens or a query list): the per-sample route -- per chunk a source pass (the camera, or the caller's ray, as vertex -1 of every
+// sample) and a trace launch of its rays, then the logic passes from depth 0 on, every vertex in the path state (WfArgs::hits == null)
 static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, const mcpt_render_params* p,
-                            double* d_img, bool timed, bool keep, const DLens* lens, hipStream_t st, double& ms_trace, int& launches)
+                            double* d_img, bool timed, bool keep, const SampleSource& src, hipStream_t st, double& ms_trace, int& launches)
 {
     const int64_t npx = L.n;
     const int spp = r.n;
+    const bool per_sample = src.per_sample();
     // WfArgs::nl: shadow planes -- one per light and one for an active environment (its draws use Philox block num_lights + 2)
     // (MCPT_LIGHTS_ONE: one plane for the picked light, whatever the scene's count -- which stays the Philox block base, S.num_lights)
     const int nl = (pick_on(S.pick) ? 1 : S.num_lights) + (env_on(S.env) ? 1 : 0);
@@ -185,7 +198,7 @@ static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameS
         }
         budget = d->wf_auto_budget;
     }
-    int64_t cap = int64_t((budget - overhead) / (bpp + 24 + (lens ? 1 : 0)));      // + 24 B radiance per sample (+ its hit flag under a lens)
+    int64_t cap = int64_t((budget - overhead) / (bpp + 24 + (per_sample ? 1 : 0)));      // + 24 B radiance per sample (+ its hit flag under a lens)
     cap = std::min<int64_t>(cap, npx * int64_t(spp));
     cap = std::min<int64_t>(cap, (int64_t(1) << 31) - 4096);                 // 32-bit compaction counter / sample ids
     int64_t chunk_slots = std::max<int64_t>(cap / spp, 1);
@@ -194,7 +207,7 @@ static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameS
     const size_t ws_need = size_t(cap) * bpp + overhead;
     HIP_TRY(f.wf_ws.grow_bytes(ws_need));
     HIP_TRY(f.rad.grow_bytes(size_t(cap) * 3 * sizeof(double)));
-    if (lens) {
+    if (per_sample) {
         HIP_TRY(f.cam_hit.grow(size_t(cap)));
     } else {
         HIP_TRY(f.hit_slots.grow(size_t(chunk_slots)));
@@ -216,7 +229,7 @@ static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameS
     a.hits = f.hits.get(); a.dirs = d->dirs.get(); a.rad = f.rad.get(); a.counts = f.wf_counts.get(); a.ctr = f.ctr.get(); a.tris = d->tris.get();
     a.materials = d->materials.get(); a.queue = fast ? f.queue.get() : nullptr;
     a.finish_below = fast ? unsigned(std::min<long long>(std::max<long long>(d->finish_threshold, 0), 1ll << 30)) : 0u;
-    if (lens) { a.hits = nullptr; a.cam_hit = f.cam_hit.get(); }
+    if (per_sample) { a.hits = nullptr; a.cam_hit = f.cam_hit.get(); }
     // Iterations are enqueued without waiting for their counts: every kernel reads its input count from the device slot the
     // previous one wrote.  The host looks at a count only every few iterations (to stop, and to size the next grids).
     const size_t ev_first = d->ev_used;
@@ -229,11 +242,12 @@ static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameS
         a.first_slot = int(first);
         a.in = A; a.out = B;
         a.counts_in = &f.wf_counts[0];
-        if (lens) {
+        if (per_sample) {
             // the camera as vertex -1: its state into a.out, the count into slot 0, its rays traced as a bounce (depth -1: from a.out.p)
             WfArgs ac = a;
             ac.depth = -1; ac.counts = &f.wf_counts[0]; ac.count_mul = 1u; ac.finish_below = 0u;
-            launch_camera_pass(*lens, ac, n_upper, st);
+            if (src.query) launch_query_pass(*src.query, ac, n_upper, st);
+            else launch_camera_pass(*src.lens, ac, n_upper, st);
             HIP_TRY(hipGetLastError());
             ac.nl = 0;          // the trace launch sees the bounce slot only (l == nl): no empty shadow-ray slots to walk past
             EventPair* pr = nullptr;
@@ -251,12 +265,12 @@ static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameS
         }
         for (int depth = 0; depth < MCPT_MAX_DEPTH && n_upper > 0; depth++) {
             a.depth = depth;
-            a.counts_in = &f.wf_counts[depth]; a.count_mul = depth == 0 && !lens ? unsigned(spp) : 1u;
+            a.counts_in = &f.wf_counts[depth]; a.count_mul = depth == 0 && !per_sample ? unsigned(spp) : 1u;
             a.counts = &f.wf_counts[depth + 1];
             const long long n_launch = std::max<long long>(1, (long long)n_grid);
             // the per-sample route's depth 0 resolves the camera rays: nothing went to the finishing kernel before it, and its pool form
             // (which reads a pixel's PrimaryHit at depth 0) does not adopt its paths
-            const bool cam0 = lens && depth == 0;
+            const bool cam0 = per_sample && depth == 0;
             char* const area = cam0 ? nullptr : path_area;
             if (cam0) { WfArgs al = a; al.finish_below = 0u; launch_wf_logic(S, al, n_launch, false, st, d->cfg); }
             else launch_wf_logic(S, a, n_launch, depth == 0, st, d->cfg);
@@ -300,7 +314,7 @@ static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameS
             launch_wf_logic(S, a, n_upper, false, st, d->cfg);
             HIP_TRY(hipGetLastError());
         }
-        fold_range(f, r, L, int(first), n_slots, d_img, lens != nullptr, S, d->dirs.get(), st);
+        fold_range(f, r, L, int(first), n_slots, d_img, per_sample, S, d->dirs.get(), st);
         HIP_TRY(hipGetLastError());
     }
     if (timed && !keep) {
@@ -330,17 +344,19 @@ int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelList& L,
     slot_used = si;
     mcpt_device::FrameSlot& f = d->slot[si];
     if (f.used) HIP_TRY(hipStreamWaitEvent(st, f.done.get(), 0));
-    int rc = ensure_dirs(d, st);
+    int rc = r.query ? MCPT_OK : ensure_dirs(d, st);        // (nothing of the frame enters a query)
     if (rc) return rc;
-    const bool lensed = r.lens && lens_active(*r.lens);
-    if (lensed && (rc = ensure_pos(d, st))) return rc;
-    const DLens dl = lensed ? lens_for(d, *r.lens) : DLens{};
+    const bool with_lens = !r.query && r.lens && lens_active(*r.lens);
+    const bool lensed = with_lens || r.query;           // the per-sample route
+    if (with_lens && (rc = ensure_pos(d, st))) return rc;
+    const DLens dl = with_lens ? lens_for(d, *r.lens) : DLens{};
+    const SampleSource src{with_lens ? &dl : nullptr, r.query};
     DScene S = d->ds;                                   // the scene with the environment of the call
     S.env = r.env ? r.env->denv : DEnv{};
     const int64_t npx = L.n;
     if (npx == 0) return MCPT_OK;
     const uint64_t primary_rays = uint64_t(npx) * (lensed ? uint64_t(r.n) : 1u);
-    HIP_TRY(f.hits.grow(size_t(npx)));
+    if (!r.query) HIP_TRY(f.hits.grow(size_t(npx)));        // (a query's slots are no pixels: nothing of it has a primary hit record)
     if (!keep || !f.keeping) HIP_TRY(hipMemsetAsync(f.ctr.get(), 0, sizeof(DCounters), st));    // kept statistics accumulate until they are collected
     f.keeping = keep;
     EventPair* fe = nullptr;
@@ -354,8 +370,8 @@ int render_device_impl(mcpt_device* d, const SampleRange& r, const PixelList& L,
     }
     double ms_trace = 0;
     int launches = 0;
-    if (p->flags & MCPT_RENDER_MEGAKERNEL) rc = render_megakernel(d, S, f, r, L, p, d_img, timed, lensed ? &dl : nullptr, st, ms_trace, launches);
-    else rc = render_wavefront(d, S, f, r, L, p, d_img, timed, keep, lensed ? &dl : nullptr, st, ms_trace, launches);
+    if (p->flags & MCPT_RENDER_MEGAKERNEL) rc = render_megakernel(d, S, f, r, L, p, d_img, timed, src, st, ms_trace, launches);
+    else rc = render_wavefront(d, S, f, r, L, p, d_img, timed, keep, src, st, ms_trace, launches);
     if (rc) return rc;
     if (keep) {
         HIP_TRY(hipEventRecord(fe->second.get(), st));

@@ -135,5 +135,8 @@ void launch_zero_rad(double* rad, long long n_doubles, hipStream_t st);
 // (from the lens point, MCPT_BT_NO_OFFSET), T = 1, no shadow rays; a.out receives the state, a.counts->n_next = n_samples.  The trace
 // launch that follows reads it with a.depth = -1; the logic pass of depth 0 then forms every sample's first vertex from its own hit.
 void launch_camera_pass(const DLens& lens, const WfArgs& a, long long n_samples, hipStream_t st);
+// The same for a query list (query.hip): the caller's ray as vertex -1 of every (slot, j); a.pixels is the id list (null: the slot itself),
+// a.sample_base the first sample index.
+void launch_query_pass(const DQuery& q, const WfArgs& a, long long n_samples, hipStream_t st);
 
 }  // namespace mcpt
