@@ -1473,6 +1473,33 @@ static void stats_add(orc_stats* a, const orc_stats* b)
     a->camera_miss += b->camera_miss;
 }
 
+/* ------------------------------------------------------------------ ray-keyed entry (extension)
+ * include/mcpt.h "radiance queries", its "shading" and "keys" paragraphs: sample i is sample_radiance on the caller's ray as given -- traced
+ * from its origin, no offset, under the scene's walk mode, shaded at depth 0 with wo = -d -- keyed (seed, pixel = ids[i] or i, sample = k[i]).
+ * The scene's environment and light pick apply; its lens, camera and resolution are never looked at.  wrong (the power checks only): 1 the
+ * ray leaves o + d * 0.01, 2 the pixel word is the list position. */
+void orc_ray_radiance(const orc_scene* s, uint64_t seed, const int32_t* ids, const int32_t* k, const double* rays6, int64_t n, int wrong,
+                      double* rgb, uint8_t* hit, uint8_t* on_surface, orc_stats* st)
+{
+#pragma omp parallel for schedule(dynamic, 32)
+    for (int64_t i = 0; i < n; i++) {
+        const double* q = rays6 + i * 6;
+        RayT ray = { v3(q[0], q[1], q[2]), v3(q[3], q[4], q[5]) };
+        if (wrong == 1) ray.o = vadd(ray.o, vmul(ray.d, 0.01));
+        orc_stats one; memset(&one, 0, sizeof one);
+        Ctx c = { s, seed, (ids && wrong != 2) ? (uint32_t)ids[i] : (uint32_t)i, (uint32_t)k[i], 0, &one, { 0, 0 }, s->env };
+        const vec3 r = sample_radiance(&c, &ray, NULL, 0);
+        one.box_tests += c.c.box; one.tri_tests += c.c.tri;
+        rgb[3 * i] = r.x; rgb[3 * i + 1] = r.y; rgb[3 * i + 2] = r.z;
+        if (hit) hit[i] = one.shade_calls > 0;                  /* shade() runs exactly when the ray hit */
+        if (on_surface) on_surface[i] = one.rays_on_surface > 0;
+        if (st) {
+#pragma omp critical(orc_ray_radiance_stats)
+            stats_add(st, &one);
+        }
+    }
+}
+
 /* generateImg, MTPC/pathTracing.cpp:274-331 (D1, D3), under the environment env (NULL: none); lens != 0: under the scene's lens, a camera ray
  * per sample and the same float accumulation in k order, missed samples included */
 static void render_block(const orc_scene* s, const Env* env, int lens, int spp, uint64_t seed, int row0, int row1, int col0, int col1,

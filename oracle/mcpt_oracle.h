@@ -53,6 +53,10 @@
  * that header's "camera lens" paragraph (orc_scene_set_lens below); pinned by tests/test_lens_oracle_cpu.py (the rays against
  * tests/lens_ref.py, the per-sample route against the pinhole's, the frame against the fold of its samples) and held against the GPU by
  * tests/test_gpu_lens_oracle.py.  Without a lens (the default) every answer and every count is what it was before.
+ * Extension (not in the reference): a ray-keyed entry to the integrator (orc_ray_radiance below), for the radiance queries of include/mcpt.h,
+ * whose rays no camera sends: the caller's ray as given, shaded at depth 0 under the key (seed, id, k).  It adds no arithmetic -- it calls what
+ * orc_sample_radiance calls -- and is pinned by tests/test_query_oracle_cpu.py (the camera's rays keyed by pixel give orc_sample_radiance bit
+ * for bit, under every lens, sky and pick) and held against the GPU by tests/test_gpu_query_oracle.py.  No other function changed with it.
  */
 #ifndef MCPT_ORACLE_H
 #define MCPT_ORACLE_H
@@ -204,6 +208,19 @@ int orc_camera_rays(const orc_scene*, uint64_t seed, const int32_t* pix, const i
  * pinhole ray, 2: a missed sample under an environment takes Le of the pixel's pinhole direction.  0 (what every orc_scene_set_lens leaves) is
  * right.  0, or -1 without an active lens. */
 int orc_scene_set_lens_wrong(orc_scene*, int wrong);
+
+/* ---- ray-keyed entry (extension, not in the reference): include/mcpt.h "radiance queries", its "keys" and "shading" paragraphs ----
+ * Sample i traces rays6[i] (origin xyz, unit direction xyz) as given -- from its origin, no offset, under the scene's walk mode -- and shades
+ * the hit at depth 0 with wo = -d under the RNG key (seed, pixel = ids[i], or i when ids == NULL, sample = k[i]); a miss is +0.0, or Le(d)
+ * under an environment (camera_miss counts it).  The scene's environment and light pick apply; its lens, camera and resolution do not.  It is
+ * the integrator orc_sample_radiance runs, entered by ray: on the rays of orc_camera_rays with ids = the pixels it gives that function's
+ * answers and counts bit for bit, under any lens.  rgb[n*3]; hit[i] (may be NULL): whether the ray hit anything; on_surface[i] (may be
+ * NULL): whether the path traced a bounce ray that starts on the surface it leaves (rays_on_surface); st (may be NULL): summed over the
+ * samples (max_depth: the largest).  Samples run on OpenMP threads; every answer is its own.
+ * wrong -- FOR THE TESTS' POWER CHECKS ONLY: 0 is right; 1: the ray leaves o + d * 0.01 instead of o; 2: the pixel word of the key is the list
+ * position instead of the id.  Nothing of it stays in the scene. */
+void orc_ray_radiance(const orc_scene*, uint64_t seed, const int32_t* ids, const int32_t* k, const double* rays6, int64_t n, int wrong,
+                      double* rgb, uint8_t* hit, uint8_t* on_surface, orc_stats* st);
 
 /* ---- output: MTPC/MTPC.cpp:10-33, MTPC/svpng.inc:77-107 ---- */
 void orc_quantize(const double* img, int64_t n, uint8_t* rgb8);

@@ -101,6 +101,9 @@ def lib():
         L.orc_scene_set_lens.argtypes = [C.c_void_p, C.c_int, C.c_double, C.c_double]
         L.orc_scene_set_lens_wrong.argtypes = [C.c_void_p, C.c_int]
         L.orc_camera_rays.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int64, C.POINTER(C.c_double)]
+        L.orc_ray_radiance.restype = None
+        L.orc_ray_radiance.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int64, C.c_int,
+                                       C.POINTER(C.c_double), C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), C.POINTER(Stats)]
         _lib = L
     return _lib
 
@@ -317,6 +320,27 @@ class OracleScene:
         if lib().orc_camera_rays(self.h, seed, _ptr(pix, C.c_int32), _ptr(k, C.c_int32), pix.shape[0], _ptr(rays, C.c_double)) != 0:
             raise ValueError("oracle: a pixel outside the frame or a negative sample index")
         return rays
+
+    def ray_radiance(self, seed, rays, k, ids=None, wrong=0, stats=None):
+        """The integrator entered by ray (orc_ray_radiance; the radiance queries of include/mcpt.h): sample i traces rays[i] = origin, unit
+        direction as given and is keyed (seed, ids[i] or i, k[i]).  The scene's environment and light pick apply, its lens and camera do not.
+        Returns radiance (n, 3), hit (n,) bool, on_surface (n,) bool -- whether the path traced a ray that starts on the surface it leaves.
+        wrong: 1 or 2 make the answer WRONG on purpose (1: the ray leaves o + d * 0.01, 2: the key's pixel word is the list position), for
+        tests that show a comparison against it has the power to fail; never set otherwise."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        k = np.ascontiguousarray(np.broadcast_to(np.asarray(k), (n,)), dtype=np.int32)
+        if ids is not None:
+            ids = np.ascontiguousarray(ids, dtype=np.int32)
+            if ids.shape != (n,):
+                raise ValueError("oracle: one id per ray")
+        if wrong not in (0, 1, 2):
+            raise ValueError("oracle: wrong = 0, 1 or 2")
+        rgb, hit, on_surface = np.zeros((n, 3)), np.zeros(n, dtype=np.uint8), np.zeros(n, dtype=np.uint8)
+        lib().orc_ray_radiance(self.h, seed, _ptr(ids, C.c_int32), _ptr(k, C.c_int32), _ptr(rays, C.c_double), n, int(wrong),
+                               _ptr(rgb, C.c_double), _ptr(hit, C.c_uint8), _ptr(on_surface, C.c_uint8),
+                               C.byref(stats) if stats is not None else None)
+        return rgb, hit.astype(bool), on_surface.astype(bool)
 
 
 def _render_strided(self, spp, seed, row_stride, faithful_cost=True, nthreads=0, stats=None, img=None):
