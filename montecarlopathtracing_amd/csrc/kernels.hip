@@ -78,7 +78,7 @@ struct PrimaryRaySource {
     __device__ __forceinline__ void store(long long q, bool ok, const Hit& h) const
     {
         PrimaryHit ph;
-        ph.leaf = ok ? h.leaf : -1; ph.pad = 0; ph.t = h.t; ph.p[0] = h.p.x; ph.p[1] = h.p.y; ph.p[2] = h.p.z;
+        ph.leaf = ok ? h.leaf : -1; ph.surf = 0; ph.t = h.t; ph.p[0] = h.p.x; ph.p[1] = h.p.y; ph.p[2] = h.p.z;
         hits[q] = ph;
     }
 };
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(256) k_primary_hits_reference(DScene S, const 
         const bool ok = trace_closest(S, r, h, w);
         ls.nodes = w.nodes; ls.tris = w.tris; ls.primary = 1;
         PrimaryHit ph;
-        ph.leaf = ok ? h.leaf : -1; ph.pad = 0; ph.t = h.t; ph.p[0] = h.p.x; ph.p[1] = h.p.y; ph.p[2] = h.p.z;
+        ph.leaf = ok ? h.leaf : -1; ph.surf = 0; ph.t = h.t; ph.p[0] = h.p.x; ph.p[1] = h.p.y; ph.p[2] = h.p.z;
         hits[gid] = ph;
     }
     flush_stats(ctr, ls);

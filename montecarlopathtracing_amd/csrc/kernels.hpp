@@ -10,7 +10,8 @@ namespace mcpt {
 #define MCPT_MAX_DEPTH_DEV 64      /* == MCPT_MAX_DEPTH in mcpt.h (D6) */
 
 struct PrimaryHit {                 // closest hit of a pixel's (sample-independent) primary ray
-    int32_t leaf, pad;
+    int32_t leaf;
+    int32_t surf;                   // wavefront frames: the pixel's PrimarySurface within its chunk (wavefront.hpp), set by k_primary_surface; else 0
     double t;
     double p[3];
 };

@@ -564,7 +564,9 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                             id = a.out.id[j];
                             depth = (uint32_t)a.depth;
                             T = mk(1, 1, 1); Lr = mk(0, 0, 0);
-                            if (a.depth > 0 || folded) T = ldc(a.out.T, cap, j);
+                            // (one light: T is in the state where there is a bounce ray; the first pass stored none -- vertex.hpp)
+                            if (folded && a.depth == 0) { const int b0 = a.out.btype[j]; if (b0 >= 0) T = first_vertex_throughput(S, a, id, b0); }
+                            else if (a.depth > 0 || folded) T = ldc(a.out.T, cap, j);
                             if (a.depth > 0) Lr = ldc(a.out.L, cap, j);
                             if (a.depth == 0) { const PrimaryHit* ph = a.hits + (a.first_slot + id / a.spp); p = mk(ph->p[0], ph->p[1], ph->p[2]); }
                             else p = ldc(a.out.p, cap, j);

@@ -17,6 +17,18 @@ __device__ __forceinline__ V3 after_bounce(const V3& T, const V3& wgt)
 {
     return mk(T.x * wgt.x * MCPT_INV_P_RR, T.y * wgt.y * MCPT_INV_P_RR, T.z * wgt.z * MCPT_INV_P_RR);
 }
+// The throughput after the bounce of a pixel's primary hit -- the first vertex of the per-pixel route, shaded by k_wf_logic<true> with
+// T = 1 -- for a sample whose bounce ray there has type bt: after_bounce((1, 1, 1), wgt) with bounce_sample's wgt (kd / ks / 1: the pixel's
+// kd from its PrimarySurface, its material's ks).  The same expression on the same operands as when the vertex was shaded, hence the same
+// bits; with one light the first pass therefore does not store T, and whoever reads the T of such a vertex (the depth-1 logic pass, the
+// finishing kernels when they adopt at depth 0) calls this instead.
+__device__ __forceinline__ V3 first_vertex_throughput(const DScene& S, const WfArgs& a, int id, int bt)
+{
+    const PrimarySurface* ps = a.surf + a.hits[a.first_slot + id / a.spp].surf;
+    const int type = bt & 7;
+    const V3 wgt = type == RT_DIFFUSE ? ld3(ps->kd) : (type == RT_SPECULAR ? ld3(S.materials[ps->material].ks) : mk(1, 1, 1));
+    return after_bounce(mk(1, 1, 1), wgt);
+}
 // L_dir += visibility * c as the reference forms it: a hidden light adds c * 0.0 (a zero of c's sign, NaN for an infinite c), not nothing
 __device__ __forceinline__ void add_if_visible(V3& L_dir, const V3& c, bool vis)
 {

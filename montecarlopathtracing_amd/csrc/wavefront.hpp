@@ -17,14 +17,18 @@ namespace mcpt {
 
 struct WfState {            // one side of the double buffer; every array has `cap` entries per component
     int32_t* id;            // chunk-local sample id = (slot - first_slot) * spp + k
-    double* T;              // [3][cap] throughput at the vertex that was just shaded (one light: after its bounce, and
-                            //          c = T * c); several lights: not stored by the first pass (T = 1)
+    double* T;              // [3][cap] throughput at the vertex that was just shaded.  One light: after its bounce (and c = T * c), stored
+                            //          only where there is a bounce ray, and not at all by the first pass -- its vertices are the pixels'
+                            //          primary hits, and a pixel's samples have one of three values there (kd, ks or 1, over P_RR: vertex.hpp
+                            //          first_vertex_throughput forms it again from PrimarySurface wherever it is read).  Several lights:
+                            //          before the bounce; not stored by the first pass (T = 1)
     double* L;              // [3][cap] radiance gathered before that vertex; not stored by the first pass (L = 0)
     // what shade(d) leaves for resolve(d):
     double* c;              // [nl][3][cap] direct-light contribution of light l if visible
     int32_t* expect;        // [nl][cap] material the shadow ray must hit to be visible; -2 = no shadow ray
     double* w;              // [3][cap] weight of the bounce (kd / ks / 1); with one light it is folded into T and c instead
-    double* bdir;           // [3][cap] direction of the bounce ray
+    double* bdir;           // [3][cap] direction of the bounce ray, stored only where there is one.  A wave writes its vertices with a bounce
+                            //          ray first (wave_rank.hpp), so the lines at the end of its 64 positions are not touched in bdir and T
     int32_t* btype;         // [cap] ray_type of the bounce ray (| MCPT_BT_NO_OFFSET: it starts at the vertex itself), -1 = none
     // what trace(d) adds:
     int32_t* hit_mat;       // [nl][cap] material of the shadow ray's closest hit, -1 = miss
@@ -86,7 +90,7 @@ struct WfArgs {
     const int32_t* hit_slots;   // first pass: compacted list of slots whose primary ray hit something
     const PrimarySurface* surf; // first pass: one record per entry of hit_slots
     const unsigned int* alive_base;   // first pass: shaded pixels before each group of 64 entries of hit_slots (k_alive_scan)
-    const PrimaryHit* hits;     // first pass: primary hit per slot
+    PrimaryHit* hits;           // first pass: primary hit per slot (k_primary_surface sets its index into surf)
     const double* dirs;         // primary directions per pixel
     int first_slot;
     double* rad;                // [chunk samples][3] finished radiance

@@ -14,6 +14,7 @@
 #include "trace_persistent.hpp"
 #include "trace_pool.hpp"
 #include "vertex.hpp"
+#include "wave_rank.hpp"
 #include "wavefront.hpp"
 #include "wf_ray_source.hpp"
 
@@ -48,34 +49,41 @@ __device__ __forceinline__ void sstc(double* __restrict__ a, long long cap, long
 #endif
 
 // ---------------------------------------------------------------------------------------------- logic kernel
-// Shade vertex `depth` of sample `id` at path position j (pathTracing.cpp:147-241; the pieces are in vertex.hpp).
-// What is known goes out at once and the bounce is sampled before the lights (every uniform has its own counter: the order of
-// evaluation is free): L, p and the sample id are stored before anything is computed, the incoming direction dies with
-// bounce_sample -- the later passes' values that are alive at the same time, and with them the registers the compiler had to
+// Shade vertex `depth` of sample `id` (pathTracing.cpp:147-241; the pieces are in vertex.hpp).
+// The bounce is sampled first (every uniform has its own counter: the order of evaluation is free): the incoming direction dies with
+// bounce_sample, and the path position j can depend on whether there is a bounce ray.  RANKED: j_lane is the position lane order would
+// give -- the wave's first position + lane -- and the wave's vertices go out ranked instead, bounce rays first (wave_rank.hpp; every lane
+// of the wave that shades is here, none under a branch of its own).  Then what is known goes out at once: the sample id, L (load_L()
+// fetches it only now: the later passes take it off the ring a second time instead of holding it across bounce_sample) and p, before
+// the lights are sampled -- the later passes' values that are alive at the same time, and with them the registers the compiler had to
 // park in scratch memory (39 at 4 waves per SIMD), are what this order is about.  ENV: an active environment, shadow plane nl - 1 after
 // the scene's nl - 1 lights (WfArgs::nl counts planes; the Philox block base is the lights' count).  PICK: the pick mode of S.pick (1: MCPT_LIGHTS_ONE, 2: MCPT_LIGHTS_TREE) --
 // the lights have one plane, plane 0, for the light vertex.hpp's light_pick draws; the block base is S.num_lights, whatever nl says (path_lights).
-template <bool FIRST, bool ENV, int PICK>
-__device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a, long long j, int id, int leaf, const V3& p, const V3& dir, const V3& T, const V3& L,
-                                                int mat_first, int pix_first, const V3& pn_first, const V3& kd_first, LaneStats& ls)
+template <bool FIRST, bool ENV, int PICK, class LoadL>
+__device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a, long long j_lane, bool ranked, int id, int leaf, const V3& p, const V3& dir, const V3& T,
+                                                LoadL load_L, int mat_first, int pix_first, const V3& pn_first, const V3& kd_first, LaneStats& ls)
 {
     const long long cap = a.cap;
     const auto [nplanes, nlights, folded] = path_lights<ENV, PICK>(S, a.nl);
     const uint32_t depth = (uint32_t)a.depth;
-    sst(a.out.id + j, id);
-    if (!FIRST) { sstc(a.out.L, cap, j, L); sstc(a.out.p, cap, j, p); }       // first pass: L = 0; p is the pixel's primary hit (a.hits)
     const DMaterial* m = S.materials + (FIRST ? mat_first : S.tris[leaf].material);
     V3 pn = pn_first, kd = kd_first;
     if (!FIRST) vertex_surface(S, leaf, p, m, pn, kd);
 
     const RngKey key = FIRST ? sample_key(a, id, pix_first) : sample_key(a, id);
 
+    long long j = j_lane;
     {
         V3 nd = mk(0, 0, 0), wgt = mk(1, 1, 1);
         const int btype = bounce_sample(key, depth, nlights, m, dir, pn, kd, nd, wgt);
+        if (ranked) { const int lane = threadIdx.x & 63; j = j_lane - lane + (long long)bounce_first_rank(__ballot(btype >= 0), lane); }
+        sst(a.out.id + j, id);
+        if (!FIRST) { sstc(a.out.L, cap, j, load_L()); sstc(a.out.p, cap, j, p); }       // first pass: L = 0; p is the pixel's primary hit (a.hits)
         if (btype >= 0) { sstc(a.out.bdir, cap, j, nd); ls.bounce++; }
         sst(a.out.btype + j, btype);
-        if (folded) sstc(a.out.T, cap, j, after_bounce(T, wgt));
+        // one light: the throughput after the bounce, where there is one (nothing reads it elsewhere); the first pass's is formed again
+        // by its readers (first_vertex_throughput)
+        if (folded) { if (!FIRST && btype >= 0) sstc(a.out.T, cap, j, after_bounce(T, wgt)); }
         else { sstc(a.out.w, cap, j, wgt); if (!FIRST) sstc(a.out.T, cap, j, T); }
     }
 
@@ -115,7 +123,8 @@ __device__ __forceinline__ void wf_shade_vertex(const DScene& S, const WfArgs& a
 // lead to a surface that is not an emitter -- and parks the survivors in a ring in LDS: position, leaf, radiance (32 bytes).  It SHADES
 // in rounds of 256 vertices taken off the ring, every wave full, as soon as 256 are there (and what is left at the end): the words the
 // next vertex is made of (sample id, throughput, the bounce ray it was reached by) are read from the position then -- for the
-// survivors only (the bytes moved stay what they were: a survivor's words share their 128-byte lines with the dead positions').  One
+// survivors only (a survivor's words share their 128-byte lines with the dead positions': what keeps whole lines of the bounce ray's
+// words out of the stream is the order a wave writes its 64 positions in, bounce rays first -- wf_shade_vertex, wave_rank.hpp).  One
 // barrier per resolve round (the
 // block-wide prefix), one per shade round (ring and output base visible); a block's output positions are one atomic per shade round.
 // Ring slots are written after the barrier of a resolve round, which every wave reaches only after its reads of the shade round
@@ -180,7 +189,8 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 continue;
             }
             MCPT_LSTAMP(0)
-            wf_shade_vertex<true, ENV, PICK>(S, a, j, id, leaf, p, dir, mk(1, 1, 1), mk(0, 0, 0), mat_first, pix_first, pn_first, kd_first, ls);
+            // (a run of spp positions that is a whole number of waves: this wave's 64 samples are one pixel's, positions j - lane .. + 63)
+            wf_shade_vertex<true, ENV, PICK>(S, a, j, (a.spp & 63) == 0, id, leaf, p, dir, mk(1, 1, 1), [] { return mk(0, 0, 0); }, mat_first, pix_first, pn_first, kd_first, ls);
             MCPT_LSTAMP(2)
         }
     } else {
@@ -243,7 +253,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                                 if (depth == 0) L[u] = ld3(S.lights[S.materials[S.tris[hl[u] & MCPT_HIT_LEAF_MASK].material].light].radiance);   // a camera ray (per-sample route): unweighted
                                 else if ((bt[u] & 7) != RT_DIFFUSE) {
                                     const DMaterial* m = S.materials + S.tris[hl[u] & MCPT_HIT_LEAF_MASK].material;
-                                    if (folded) T[u] = sldc(a.in.T, cap, pos[u]);
+                                    if (folded) T[u] = depth == 1 && a.hits ? first_vertex_throughput(S, a, id[u], bt[u]) : sldc(a.in.T, cap, pos[u]);
                                     const V3 rad = ld3(S.lights[m->light].radiance);
                                     L[u] = L[u] + mul(T[u], rad);
                                 }
@@ -253,7 +263,7 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                             const V3 bd = sldc(a.in.bdir, cap, pos[u]);
                             if (depth == 0) L[u] = env_eval(S.env, bd);                 // a camera ray (per-sample route): unweighted
                             else {
-                                const V3 Tn = folded ? sldc(a.in.T, cap, pos[u]) : after_bounce(T[u], wgt[u]);
+                                const V3 Tn = !folded ? after_bounce(T[u], wgt[u]) : depth == 1 && a.hits ? first_vertex_throughput(S, a, id[u], bt[u]) : sldc(a.in.T, cap, pos[u]);
                                 L[u] = env_escape(S.env, L[u], Tn, bt[u], bd);
                             }
                         }
@@ -299,13 +309,14 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 const unsigned int s = (head + threadIdx.x) & (kRing - 1u);
                 const long long i = ring_pos[s];
                 const int leaf = ring_leaf[s];
-                const V3 L = mk(ring_L[0][s], ring_L[1][s], ring_L[2][s]);
-                const long long j = (long long)block_base[bturn] + threadIdx.x;
+                const long long j = (long long)block_base[bturn] + threadIdx.x;     // (in lane order; wf_shade_vertex ranks the wave's 64)
                 // the sample, its throughput and the bounce ray that reached this vertex, from the position
                 const int id = sld(a.in.id + i);
                 const int bt = sld(a.in.btype + i);
+                // (depth 0, the per-sample route: a camera ray, T = 1; one light, depth 1 of the per-pixel route: the first pass stored none)
                 V3 T = mk(1, 1, 1);
-                if (depth > 1 || (folded && depth > 0)) T = sldc(a.in.T, cap, i);      // (depth 0, the per-sample route: a camera ray, T = 1)
+                if (folded && depth == 1 && a.hits) T = first_vertex_throughput(S, a, id, bt);
+                else if (depth > 1 || (folded && depth > 0)) T = sldc(a.in.T, cap, i);
                 if (!folded && depth > 0) T = after_bounce(T, sldc(a.in.w, cap, i));
                 const V3 bd = sldc(a.in.bdir, cap, i);
                 // the vertex the bounce ray left from: the pixel's primary hit after the first pass, in.p afterwards (and always in the
@@ -320,7 +331,8 @@ __global__ void __launch_bounds__(256, FIRST ? MCPT_LOGIC_WAVES_FIRST : MCPT_LOG
                 const V3 v1 = ld3(tr->v1), n = ld3(tr->n);
                 const double t = dot(v1 - ro, n) / dot(n, bd);
                 const V3 p = ro + bd * t;
-                wf_shade_vertex<false, ENV, PICK>(S, a, j, id, leaf, p, neg(bd), T, L, 0, 0, mk(0, 0, 0), mk(0, 0, 0), ls);
+                wf_shade_vertex<false, ENV, PICK>(S, a, j, true, id, leaf, p, neg(bd), T, [&] { return mk(ring_L[0][s], ring_L[1][s], ring_L[2][s]); }, 0, 0, mk(0, 0, 0),
+                                                  mk(0, 0, 0), ls);
             }
             head = (head + m_round) & (kRing - 1u);
             count -= m_round;
@@ -386,7 +398,9 @@ __global__ void __launch_bounds__(256, MCPT_FINISH_WAVES) k_wf_finish(DScene S, 
                 id = a.out.id[j];
                 depth = (uint32_t)a.depth;
                 T = mk(1, 1, 1); L = mk(0, 0, 0);
-                if (a.depth > 0 || folded) T = ldc(a.out.T, cap, j);
+                // (one light: T is in the state where there is a bounce ray, and nothing uses it elsewhere; the first pass stored none)
+                if (folded && a.depth == 0 && a.hits) { const int b0 = a.out.btype[j]; if (b0 >= 0) T = first_vertex_throughput(S, a, id, b0); }
+                else if (a.depth > 0 || folded) T = ldc(a.out.T, cap, j);
                 if (a.depth > 0) L = ldc(a.out.L, cap, j);
                 p = src.vertex(j);
                 key = sample_key(a, id);
@@ -600,6 +614,7 @@ __global__ void k_primary_surface(DScene S, WfArgs a, PrimarySurface* __restrict
         if (m->light < 0) { vertex_surface(S, ph.leaf, p, m, pn, kd); shaded = true; }
         r.pn[0] = pn.x; r.pn[1] = pn.y; r.pn[2] = pn.z; r.kd[0] = kd.x; r.kd[1] = kd.y; r.kd[2] = kd.z;
         r.pad[0] = r.pad[1] = r.pad[2] = 0;
+        a.hits[slot].surf = (int32_t)h;         // the way back from a sample to this record (first_vertex_throughput)
         }
         // the shaded pixels of the chunk are numbered in slot order (paths in another order trace measurably slower on a rank's
         // share of a frame): here the rank within the wave and the wave's count, k_alive_scan turns the counts into offsets
