@@ -912,7 +912,8 @@ int mcpt_render_scene_display(const char* path, const char* filename, int32_t sp
  * The host-pointer form is synchronous.  The device form (device pointers throughout) enqueues on `stream` and returns without waiting
  * when stats == NULL.  Both use the device's frame slot 0 and first wait for the device's frames still in flight (MCPT_RENDER_PIPELINE /
  * KEEP_STATS).  Queries are allowed while progressive handles of the device live: they touch none of a handle's state.
- * Not covered: the multi-device group, render_scene, per-query sample counts, adaptive stopping of queries. */
+ * Not covered: the multi-device group, render_scene, per-query sample counts, adaptive stopping of queries.  The radiance of the whole
+ * sphere about a point, for any normal afterwards, is a light probe's (below), not a kind of this call. */
 #define MCPT_QUERY_RAY        0   /* q = origin xyz, direction xyz */
 #define MCPT_QUERY_HEMISPHERE 1   /* q = position xyz, normal xyz  */
 typedef struct { int32_t spp, sample_base; uint64_t seed; int32_t kind, flags, reserved[2]; } mcpt_query_params;
@@ -923,6 +924,52 @@ int mcpt_query_radiance_device(mcpt_device*, const double* d_q6, const int32_t* 
 /* test seam: the ray of sample k[i] of query i -> rays6[n*6] = origin xyz, direction xyz (k[i] >= 0) */
 int mcpt_query_rays(mcpt_device*, const double* q6, const int32_t* ids, int64_t n, uint64_t seed, int32_t kind,
                     const int32_t* k, double* rays6);
+
+/* ---- light probes (since the probe change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* A LIGHT PROBE is a point in free space that stores the incoming radiance of the whole sphere about it as nine real spherical-harmonic
+ * coefficients (bands 0..2) per colour channel; a receiver then looks up diffuse lighting for any normal without tracing again.
+ * mcpt_query_sh is mcpt_query_radiance over a list of n positions p3[n*3] with a third source draw and a fold of its own; keys, shading,
+ * sample ranges, flags, statistics (rays_primary = samples = n * spp), concurrency and the motion rule are that call's, word for word.
+ * fp64, no contraction, sums in the order written.
+ *   draw     : u0, u1 = words 0 and 1 of the camera-uniform block uniform(seed, id, k, depth 0xFFFF, slot 0..3), the hemisphere kind's;
+ *              z = 1.0 - 2.0 * u0, r = sqrt(max(0, 1.0 - z * z)), phi = 6.283185307179586 * u1,
+ *              d = normalize((r cos phi, r sin phi, z)) in world axes, o = p: the probe point itself, no offset (MCPT_QUERY_RAY's
+ *              convention).  A PROBE IS MEANT TO SIT IN FREE SPACE; a caller who puts one on a surface lifts it off first.
+ *              The draw is an internal third kind: mcpt_query_radiance and mcpt_query_rays refuse kind 2 as before.
+ *   basis    : for a unit direction (x, y, z), in this index order and operation order:
+ *                Y0 = 0.28209479177387814
+ *                Y1 = 0.4886025119029199 * y      Y2 = 0.4886025119029199 * z      Y3 = 0.4886025119029199 * x
+ *                Y4 = 1.0925484305920792 * (x * y)    Y5 = 1.0925484305920792 * (y * z)
+ *                Y6 = 0.31539156525252005 * (3.0 * (z * z) - 1.0)
+ *                Y7 = 1.0925484305920792 * (x * z)    Y8 = 0.5462742152960396 * (x * x - y * y)
+ *              (1/(2 sqrt(pi)), sqrt(3/(4 pi)), sqrt(15/(4 pi)), sqrt(5/(16 pi)), sqrt(15/(16 pi)): orthonormal over the sphere)
+ *   fold     : per probe s, coefficient i and channel c, in k order, with x_k the sample's radiance (a missed ray: +0.0, or Le(d) under an
+ *              environment, summed like any other) and d_k bitwise the direction its ray was given:
+ *              v = x_k[c] * Y_i(d_k), s1 += v, s2 += v * v;
+ *              sh[s][i][c] = 12.566370614359172 * (s1 / spp)                                          (4 pi: 1 / the draw's density)
+ *              err[s][i][c] = 0 when spp < 2, else 12.566370614359172 * sqrt(max((s2 - s1 * s1 / spp) / (spp - 1), 0) / spp)
+ *              hits[s] = the samples of probe s whose ray hit anything.  sh27 [n][9][3] is required; stderr27 and hits may be NULL.
+ *   use      : mcpt_sh_radiance: L(d) = sum_i sh[i] * Y_i(d), in index order from 0.0.  mcpt_sh_irradiance, probe i with normal i of any
+ *              non-zero finite length: n^ = n / sqrt((nx nx + ny ny) + nz nz), E_c = sum_i (A_l(i) * Y_i(n^)) * sh[i][c] in index
+ *              order from 0.0, A0 = 3.141592653589793 (i = 0), A1 = 2.0943951023931953 (i = 1..3), A2 = 0.7853981633974483 (i = 4..8):
+ *              the order-2 approximation of the irradiance mcpt_query_radiance's hemisphere kind estimates for one normal.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE), in mcpt_query_radiance's order: NULL parameters, spp < 1, sample_base < 0,
+ * sample_base + spp > 2^31 - 1, n < 0 or n > 2^31 - 1, a flag other than 0 or MCPT_RENDER_MEGAKERNEL, reserved != 0, NULL p3 or sh27 with
+ * n > 0 and, in the host-pointer forms, a negative id or a position that is not finite.  n == 0: MCPT_OK, nothing is launched.  The device
+ * form takes device pointers throughout (p3 as n*3 device doubles), enqueues on `stream` and returns without waiting when stats == NULL.
+ * The host helpers need no device; they refuse a NULL pointer, n < 0, a component that is not finite and, mcpt_sh_irradiance, a normal of
+ * zero, underflowing or overflowing length.
+ * Not covered: the multi-device group, render_scene, interpolation between the probes of a grid, bands above 2, adaptive stopping. */
+typedef struct { int32_t spp, sample_base; uint64_t seed; int32_t flags, reserved[3]; } mcpt_sh_params;
+int mcpt_query_sh(mcpt_device*, const double* p3, const int32_t* ids, int64_t n, const mcpt_sh_params*,
+                  double* sh27, double* stderr27, int32_t* hits, mcpt_stats*);
+int mcpt_query_sh_device(mcpt_device*, const double* d_p3, const int32_t* d_ids, int64_t n, const mcpt_sh_params*,
+                         double* d_sh27, double* d_stderr27, int32_t* d_hits, mcpt_stats*, void* stream);
+/* test seam: the ray of sample k[i] of probe i -> rays6[n*6] = origin xyz, direction xyz (k[i] >= 0) */
+int mcpt_query_sh_rays(mcpt_device*, const double* p3, const int32_t* ids, int64_t n, uint64_t seed, const int32_t* k, double* rays6);
+int mcpt_sh_basis(const double* d3, int64_t n, double* y9);                                     /* y9[n*9] = Y_0..8(d_i) */
+int mcpt_sh_radiance(const double* sh27, const double* d3, int64_t n, double* rgb3);           /* probe i along direction i */
+int mcpt_sh_irradiance(const double* sh27, const double* n3, int64_t n, double* e3);           /* probe i under normal i */
 
 #ifdef __cplusplus
 }

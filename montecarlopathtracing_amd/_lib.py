@@ -160,6 +160,11 @@ class QueryParams(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class ShParams(C.Structure):
+    """mcpt_sh_params: samples per probe, first sample index, seed and flags of a light-probe call"""
+    _fields_ = [("spp", C.c_int32), ("sample_base", C.c_int32), ("seed", C.c_uint64), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -194,6 +199,7 @@ EXPORTS = [
     "mcpt_display_histogram_device", "mcpt_display_histogram", "mcpt_display_exposure", "mcpt_display_device", "mcpt_display",
     "mcpt_display_host", "mcpt_progressive_display", "mcpt_progressive_display_device", "mcpt_render_scene_display",
     "mcpt_query_radiance", "mcpt_query_radiance_device", "mcpt_query_rays",
+    "mcpt_query_sh", "mcpt_query_sh_device", "mcpt_query_sh_rays", "mcpt_sh_basis", "mcpt_sh_radiance", "mcpt_sh_irradiance",
 ]
 
 
@@ -366,6 +372,13 @@ def lib():
     L.mcpt_query_radiance.argtypes = [P, D, I32, C.c_int64, QP, D, D, I32, C.POINTER(Stats)]
     L.mcpt_query_radiance_device.argtypes = [P, P, P, C.c_int64, QP, P, P, P, C.POINTER(Stats), P]
     L.mcpt_query_rays.argtypes = [P, D, I32, C.c_int64, C.c_uint64, C.c_int32, I32, D]
+    SP = C.POINTER(ShParams)
+    L.mcpt_query_sh.argtypes = [P, D, I32, C.c_int64, SP, D, D, I32, C.POINTER(Stats)]
+    L.mcpt_query_sh_device.argtypes = [P, P, P, C.c_int64, SP, P, P, P, C.POINTER(Stats), P]
+    L.mcpt_query_sh_rays.argtypes = [P, D, I32, C.c_int64, C.c_uint64, I32, D]
+    L.mcpt_sh_basis.argtypes = [D, C.c_int64, D]
+    L.mcpt_sh_radiance.argtypes = [D, D, C.c_int64, D]
+    L.mcpt_sh_irradiance.argtypes = [D, D, C.c_int64, D]
     _lib = L
     return L
 

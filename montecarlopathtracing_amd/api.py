@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -101,6 +101,41 @@ def display_exposure(slots, percentile=0.0):
     la, lp = C.c_double(), C.c_double()
     check(lib().mcpt_display_exposure(slots.ctypes.data_as(C.POINTER(C.c_int64)), float(percentile), C.byref(la), C.byref(lp)))
     return la.value, lp.value
+
+
+def _sh_args(sh, v, what):
+    v = np.ascontiguousarray(v, dtype=np.float64)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("%s must have shape (n, 3), not %r" % (what, v.shape))
+    if sh is not None:
+        sh = np.ascontiguousarray(sh, dtype=np.float64)
+        if sh.shape != (v.shape[0], 9, 3):
+            raise ValueError("sh must have shape (%d, 9, 3), not %r" % (v.shape[0], sh.shape))
+    return sh, v
+
+
+def sh_basis(dirs):
+    """Y_0..8 of unit directions (n, 3), in mcpt.h's index order (mcpt_sh_basis): (n, 9)"""
+    _, d = _sh_args(None, dirs, "dirs")
+    y = np.zeros((d.shape[0], 9))
+    check(lib().mcpt_sh_basis(_p(d, C.c_double), d.shape[0], _p(y, C.c_double)))
+    return y
+
+
+def sh_radiance(sh, dirs):
+    """the radiance probe i's coefficients sh[i] (9, 3) give along the unit direction dirs[i] (mcpt_sh_radiance): (n, 3)"""
+    sh, d = _sh_args(sh, dirs, "dirs")
+    rgb = np.zeros((d.shape[0], 3))
+    check(lib().mcpt_sh_radiance(_p(sh, C.c_double), _p(d, C.c_double), d.shape[0], _p(rgb, C.c_double)))
+    return rgb
+
+
+def sh_irradiance(sh, normals):
+    """the irradiance probe i's coefficients sh[i] (9, 3) give a receiver of normal normals[i], any non-zero length (mcpt_sh_irradiance): (n, 3)"""
+    sh, nrm = _sh_args(sh, normals, "normals")
+    e = np.zeros((nrm.shape[0], 3))
+    check(lib().mcpt_sh_irradiance(_p(sh, C.c_double), _p(nrm, C.c_double), nrm.shape[0], _p(e, C.c_double)))
+    return e
 
 
 def _as_lens(lens):
@@ -564,6 +599,46 @@ class Device:
         rays = np.zeros((q.shape[0], 6))
         check(lib().mcpt_query_rays(self._h, _p(q, C.c_double), _p(ids, C.c_int32), q.shape[0], int(seed), _QUERY_KINDS[kind], _p(k, C.c_int32),
                                     _p(rays, C.c_double)))
+        return rays
+
+    @staticmethod
+    def _probe_list(points, ids):
+        p = np.ascontiguousarray(points, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("points must have shape (n, 3), not %r" % (p.shape,))
+        if ids is not None:
+            ids = np.asarray(ids)
+            if ids.dtype.kind not in "iu" or ids.shape != (p.shape[0],):
+                raise ValueError("ids must be %d integers" % p.shape[0])
+            if ids.size and (int(ids.min()) < -2 ** 31 or int(ids.max()) >= 2 ** 31):
+                raise ValueError("ids must fit 32 bits")
+            ids = np.ascontiguousarray(ids, dtype=np.int32)
+        return p, ids
+
+    def sh_probes(self, points, spp, seed=0, ids=None, sample_base=0, flags=0, stats=None):
+        """Light probes (mcpt_query_sh): the incoming radiance of the whole sphere about each of points (n, 3), in free space, as nine
+        spherical-harmonic coefficients per channel; probe i takes samples sample_base .. sample_base + spp - 1 under the RNG key
+        (seed, ids[i] or i, sample).  Returns (sh [n,9,3], stderr [n,9,3], hits [n]); sh_radiance and sh_irradiance evaluate sh."""
+        p, ids = self._probe_list(points, ids)
+        for name, v in (("spp", spp), ("sample_base", sample_base), ("flags", flags)):
+            if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError("%s must be a 32-bit integer" % name)
+        n = p.shape[0]
+        sh, err, hits = np.zeros((n, 9, 3)), np.zeros((n, 9, 3)), np.zeros(n, dtype=np.int32)
+        sp = ShParams(int(spp), int(sample_base), int(seed), int(flags), (C.c_int32 * 3)(0, 0, 0))
+        check(lib().mcpt_query_sh(self._h, _p(p, C.c_double), _p(ids, C.c_int32), n, C.byref(sp), _p(sh, C.c_double), _p(err, C.c_double),
+                                  _p(hits, C.c_int32), C.byref(stats) if stats is not None else None))
+        return sh, err, hits
+
+    def sh_probe_rays(self, points, seed, k, ids=None):
+        """test seam (mcpt_query_sh_rays): the ray of sample k[i] of probe i, (n, 6) = origin (the point itself), direction"""
+        p, ids = self._probe_list(points, ids)
+        k = np.asarray(k)
+        if k.dtype.kind not in "iu" or k.shape != (p.shape[0],):
+            raise ValueError("k must be %d integers" % p.shape[0])
+        k = np.ascontiguousarray(k, dtype=np.int32)
+        rays = np.zeros((p.shape[0], 6))
+        check(lib().mcpt_query_sh_rays(self._h, _p(p, C.c_double), _p(ids, C.c_int32), p.shape[0], int(seed), _p(k, C.c_int32), _p(rays, C.c_double)))
         return rays
 
     def set_environment(self, rgb=None, scale=1.0):

@@ -123,12 +123,14 @@ struct DLens {
 };
 
 // A query list on the device and where its fold goes (mcpt_query_radiance; query.hpp: query_ray): entry i of q6 is query i, slot i of the
-// call; its id is the call's slot list's, or i.
+// call; its id is the call's slot list's, or i.  A probe list (mcpt_query_sh; kind 2, internal) holds positions alone, 3 doubles per entry,
+// and its fold writes nine coefficients per channel.
+#define MCPT_QUERY_KIND_SPHERE 2
 struct DQuery {
-    const double* q6;           // [n][6] origin + direction (MCPT_QUERY_RAY), or position + normal (MCPT_QUERY_HEMISPHERE)
+    const double* q6;           // [n][6] origin + direction (MCPT_QUERY_RAY), or position + normal (MCPT_QUERY_HEMISPHERE); a probe list: [n][3]
     int kind;
-    double* mean3;              // [n][3]
-    double* stderr3;            // [n][3] or null
+    double* mean3;              // [n][3]; a probe list: [n][9][3]
+    double* stderr3;            // [n][3] or null; a probe list: [n][9][3] or null
     int32_t* hits;              // [n] or null
 };
 

@@ -3,7 +3,8 @@
 //   scene_api.cpp     scene handles, the tile partition, the trace engine of a scene, the shared culling hierarchy
 //   device.cpp        device creation stage by stage, hierarchy queries, closest hit
 //   render.cpp        lenses, the integrator (megakernel and wavefront), mcpt_render*, statistics, (pixel, sample) queries
-//   query_api.cpp     radiance queries: the integrator behind a caller's rays and surface points
+//   query_api.cpp     radiance queries: the integrator behind a caller's rays, surface points and light probes
+//   sh_api.cpp        light probes on the host: the spherical-harmonic basis, radiance and irradiance from a probe's coefficients
 //   progressive.cpp   progressive frames, AOVs, the denoiser
 //   light_sampling.cpp  MCPT_LIGHTS_ONE and MCPT_LIGHTS_TREE: the pick table, the light tree, their upload, the picks' test seams
 //   motion.cpp        a device's motion: the shutter's steps between two keyframes, the return to key 0

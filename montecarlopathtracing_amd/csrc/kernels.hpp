@@ -78,6 +78,10 @@ void launch_query_samples(const DScene& S, const DQuery& q, unsigned long long s
 // the fold of a chunk's n samples per slot into q's outputs at slots first_slot .. first_slot + n_slots; env: a missed ray's radiance is
 // Le of its direction (else +0.0)
 void launch_query_fold(const DQuery& q, const double* d_rad, const uint8_t* d_flags, int first_slot, int n_slots, int n, bool env, hipStream_t st);
+// the same for a probe list (q.kind == MCPT_QUERY_KIND_SPHERE): every sample times the nine basis functions of its own direction, drawn
+// again from (seed, d_ids[slot] or slot, sample_base + j); q.mean3 and q.stderr3 are [n][9][3]
+void launch_query_fold_sh(const DQuery& q, unsigned long long seed, const int32_t* d_ids, const double* d_rad, const uint8_t* d_flags, int first_slot,
+                          int n_slots, int n, int sample_base, bool env, hipStream_t st);
 // test seam: the ray of sample d_k[i] of query i
 void launch_query_rays(const DQuery& q, unsigned long long seed, const int32_t* d_ids, const int32_t* d_k, long long n, double* d_rays6, hipStream_t st);
 // launch_fold_progressive for a piece of a motion frame (camera.hip): a pixel's primary ray may hit in one piece and miss in another, so a

@@ -1,5 +1,7 @@
 // Radiance queries (mcpt_query_radiance): the source pass that puts a caller's rays where the camera pass puts the lens's, the megakernel
-// form, the fold into per-query mean, standard error and hit count, and the mcpt_query_rays seam.  -ffp-contract=off (Makefile).
+// form, the fold into per-query mean, standard error and hit count, and the mcpt_query_rays seam; for a list of light probes
+// (mcpt_query_sh) the same pass and megakernel form over the sphere draw, and the fold into spherical-harmonic coefficients.
+// -ffp-contract=off (Makefile).
 #include <hip/hip_runtime.h>
 
 #include "dev_common.hpp"
@@ -7,6 +9,7 @@
 #include "path_variant.hpp"
 #include "query.hpp"
 #include "shade_common.hpp"
+#include "sh_math.hpp"
 #include "shade_path.hpp"
 #include "vertex.hpp"
 #include "wavefront.hpp"
@@ -19,7 +22,7 @@ __global__ void __launch_bounds__(256) k_query_rays(DQuery q, unsigned long long
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (gid >= n) return;
     V3 o, d;
-    query_ray(q.kind, q.q6 + gid * 6, seed, ids ? ids[gid] : (int)gid, ks[gid], o, d);
+    query_ray(q.kind, q.q6 + gid * query_stride(q.kind), seed, ids ? ids[gid] : (int)gid, ks[gid], o, d);
     double* r = rays6 + gid * 6;
     r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
 }
@@ -38,7 +41,7 @@ __global__ void __launch_bounds__(256) k_query_samples(DScene S, DQuery q, unsig
         const int k = sample_base + (int)(gid % spp);
         const int id = ids ? ids[slot] : slot;
         Ray r;
-        query_ray(q.kind, q.q6 + (size_t)slot * 6, seed, id, k, r.o, r.d);
+        query_ray(q.kind, q.q6 + (size_t)slot * query_stride(q.kind), seed, id, k, r.o, r.d);
         Hit h; Work w = {0, 0};
         const bool ok = trace_closest(S, r, h, w);
         ls.nodes = w.nodes; ls.tris = w.tris; ls.primary = 1; ls.samples = 1;
@@ -73,7 +76,7 @@ __global__ void __launch_bounds__(256) k_query_pass(DQuery q, WfArgs a, long lon
     const int k = a.sample_base + (int)(j % a.spp);
     const int id = a.pixels ? a.pixels[slot] : slot;
     V3 o, d;
-    query_ray(KIND, q.q6 + (size_t)slot * 6, a.seed, id, k, o, d);
+    query_ray(KIND, q.q6 + (size_t)slot * query_stride(KIND), a.seed, id, k, o, d);
     a.out.id[j] = (int32_t)j;
     stc(a.out.p, cap, j, o);
     stc(a.out.bdir, cap, j, d);
@@ -110,6 +113,53 @@ __global__ void __launch_bounds__(256) k_query_fold(DQuery q, const double* __re
     if (c == 0 && q.hits) q.hits[first_slot + s] = h;
 }
 
+// The fold of a probe list (mcpt_query_sh): k_query_fold's lanes and walk -- one lane per (slot, channel), the slot's hit flags, then its
+// n samples in k order, no atomics -- with every sample weighted by the nine basis functions of its own direction: v = x * Y_i(d_k),
+// s1[i] += v, s2[i] += v * v.  The path state's direction is gone by now, so d_k is drawn again from the key (query_ray: bitwise the
+// direction the sample's ray was given).  The three lanes of a slot repeat that draw; a lane per slot would not, but holds 54
+// accumulators and reads 24-byte pieces a sample stride apart, and a lane per (slot, coefficient) repeats it nine times.  q.mean3 and
+// q.stderr3 are [n][9][3] here.  A slot none of whose rays hit is not read without an environment: x = +0.0 throughout, so is every sum.
+template <bool ENV>
+__global__ void __launch_bounds__(256) k_query_fold_sh(DQuery q, unsigned long long seed, const int32_t* __restrict__ ids, const double* __restrict__ rad,
+                                                       const uint8_t* __restrict__ flags, int first_slot, int n_slots, int n, int sample_base)
+{
+    const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (gid >= (long long)n_slots * 3) return;
+    const int s = (int)(gid / 3), c = (int)(gid % 3);
+    const double* src = rad + (size_t)s * n * 3 + c;
+    const uint8_t* f = flags + (size_t)s * n;
+    int h = 0;
+    for (int k = 0; k < n; k++) h += f[k];
+    double s1[MCPT_SH_N], s2[MCPT_SH_N];
+#pragma unroll
+    for (int i = 0; i < MCPT_SH_N; i++) { s1[i] = 0.0; s2[i] = 0.0; }
+    const int slot = first_slot + s;
+    if (h > 0 || ENV) {
+        const int id = ids ? ids[slot] : slot;
+        const double* p = q.q6 + (size_t)slot * 3;
+        for (int k = 0; k < n; k++) {
+            const double x = src[(size_t)k * 3];
+            V3 o, d;
+            query_ray(MCPT_QUERY_KIND_SPHERE, p, seed, id, sample_base + k, o, d);
+            double Y[MCPT_SH_N];
+            sh_basis9(d.x, d.y, d.z, Y);
+#pragma unroll
+            for (int i = 0; i < MCPT_SH_N; i++) {
+                const double v = x * Y[i];
+                s1[i] += v;
+                s2[i] += v * v;
+            }
+        }
+    }
+    const size_t o27 = (size_t)slot * (MCPT_SH_N * 3) + c;
+#pragma unroll
+    for (int i = 0; i < MCPT_SH_N; i++) {
+        q.mean3[o27 + i * 3] = 12.566370614359172 * (s1[i] / n);
+        if (q.stderr3) q.stderr3[o27 + i * 3] = n >= 2 ? 12.566370614359172 * sqrt(progressive_se2(s1[i], s2[i], n)) : 0.0;
+    }
+    if (c == 0 && q.hits) q.hits[slot] = h;
+}
+
 // ------------------------------------------------------------------------------------------------ launchers
 static inline unsigned blocks_of(long long n, int block) { return (unsigned)((n + block - 1) / block); }
 
@@ -132,6 +182,7 @@ void launch_query_pass(const DQuery& q, const WfArgs& a, long long n_samples, hi
 {
     const dim3 grid(blocks_of(n_samples > 0 ? n_samples : 1, 256));
     if (q.kind == MCPT_QUERY_KIND_RAY) hipLaunchKernelGGL(k_query_pass<MCPT_QUERY_KIND_RAY>, grid, dim3(256), 0, st, q, a, n_samples);
+    else if (q.kind == MCPT_QUERY_KIND_SPHERE) hipLaunchKernelGGL(k_query_pass<MCPT_QUERY_KIND_SPHERE>, grid, dim3(256), 0, st, q, a, n_samples);
     else hipLaunchKernelGGL(k_query_pass<MCPT_QUERY_KIND_HEMISPHERE>, grid, dim3(256), 0, st, q, a, n_samples);
 }
 void launch_query_fold(const DQuery& q, const double* d_rad, const uint8_t* d_flags, int first_slot, int n_slots, int n, bool env, hipStream_t st)
@@ -140,6 +191,14 @@ void launch_query_fold(const DQuery& q, const double* d_rad, const uint8_t* d_fl
     const dim3 grid(blocks_of((long long)n_slots * 3, 256));
     if (env) hipLaunchKernelGGL(k_query_fold<true>, grid, dim3(256), 0, st, q, d_rad, d_flags, first_slot, n_slots, n);
     else hipLaunchKernelGGL(k_query_fold<false>, grid, dim3(256), 0, st, q, d_rad, d_flags, first_slot, n_slots, n);
+}
+void launch_query_fold_sh(const DQuery& q, unsigned long long seed, const int32_t* d_ids, const double* d_rad, const uint8_t* d_flags, int first_slot,
+                          int n_slots, int n, int sample_base, bool env, hipStream_t st)
+{
+    if (n_slots <= 0) return;
+    const dim3 grid(blocks_of((long long)n_slots * 3, 256));
+    if (env) hipLaunchKernelGGL(k_query_fold_sh<true>, grid, dim3(256), 0, st, q, seed, d_ids, d_rad, d_flags, first_slot, n_slots, n, sample_base);
+    else hipLaunchKernelGGL(k_query_fold_sh<false>, grid, dim3(256), 0, st, q, seed, d_ids, d_rad, d_flags, first_slot, n_slots, n, sample_base);
 }
 
 }  // namespace mcpt

@@ -23,18 +23,39 @@ static int count_check(int64_t n)
     return n >= 0 && n <= kInt32Max ? MCPT_OK : fail(MCPT_ERR_ARG, "the number of queries must be in 0 .. 2^31 - 1");
 }
 
+// what every query call refuses of its sample range and count, and of its flags: the pieces of params_check and sh_params_check, which
+// refuse the same things in the same order
+static int range_check(int32_t spp, int32_t sample_base, int64_t n)
+{
+    if (spp < 1) return fail(MCPT_ERR_ARG, "spp must be >= 1");
+    if (sample_base < 0) return fail(MCPT_ERR_ARG, "sample_base must be >= 0");
+    if (int64_t(sample_base) + int64_t(spp) > kInt32Max) return fail(MCPT_ERR_ARG, "sample_base + spp must not exceed 2^31 - 1");
+    return count_check(n);
+}
+static int flags_check(int32_t flags)
+{
+    return flags == 0 || flags == MCPT_RENDER_MEGAKERNEL ? MCPT_OK : fail(MCPT_ERR_ARG, "unknown query flag (0 or MCPT_RENDER_MEGAKERNEL)");
+}
+
 // what both forms of mcpt_query_radiance refuse without looking at the list
 static int params_check(const mcpt_query_params* p, int64_t n, const void* q6, const void* mean3)
 {
     if (!p) return fail(MCPT_ERR_ARG, "null query parameters");
-    if (p->spp < 1) return fail(MCPT_ERR_ARG, "spp must be >= 1");
-    if (p->sample_base < 0) return fail(MCPT_ERR_ARG, "sample_base must be >= 0");
-    if (int64_t(p->sample_base) + int64_t(p->spp) > kInt32Max) return fail(MCPT_ERR_ARG, "sample_base + spp must not exceed 2^31 - 1");
-    if (const int rc = count_check(n)) return rc;
+    if (const int rc = range_check(p->spp, p->sample_base, n)) return rc;
     if (const int rc = kind_check(p->kind)) return rc;
-    if (p->flags != 0 && p->flags != MCPT_RENDER_MEGAKERNEL) return fail(MCPT_ERR_ARG, "unknown query flag (0 or MCPT_RENDER_MEGAKERNEL)");
+    if (const int rc = flags_check(p->flags)) return rc;
     if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(MCPT_ERR_ARG, "mcpt_query_params.reserved must be 0");
     if (n > 0 && (!q6 || !mean3)) return fail(MCPT_ERR_ARG, "null query list or mean");
+    return MCPT_OK;
+}
+// ... and both forms of mcpt_query_sh
+static int sh_params_check(const mcpt_sh_params* p, int64_t n, const void* p3, const void* sh27)
+{
+    if (!p) return fail(MCPT_ERR_ARG, "null probe parameters");
+    if (const int rc = range_check(p->spp, p->sample_base, n)) return rc;
+    if (const int rc = flags_check(p->flags)) return rc;
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0) return fail(MCPT_ERR_ARG, "mcpt_sh_params.reserved must be 0");
+    if (n > 0 && (!p3 || !sh27)) return fail(MCPT_ERR_ARG, "null probe list or coefficients");
     return MCPT_OK;
 }
 
@@ -57,12 +78,21 @@ static int list_check(const double* q6, const int32_t* ids, int64_t n, int32_t k
     return MCPT_OK;
 }
 
-extern "C" {
-
-int mcpt_query_radiance_device(mcpt_device* d, const double* d_q6, const int32_t* d_ids, int64_t n, const mcpt_query_params* p, double* d_mean3,
-                               double* d_stderr3, int32_t* d_hits, mcpt_stats* stats, void* stream)
+// ... and of a probe list
+static int probe_list_check(const double* p3, const int32_t* ids, int64_t n)
 {
-    if (const int rc = params_check(p, n, d_q6, d_mean3)) return rc;
+    for (int64_t i = 0; i < n; i++) {
+        if (ids && ids[i] < 0) return fail(MCPT_ERR_ARG, "probe " + std::to_string(i) + ": negative id");
+        for (int c = 0; c < 3; c++)
+            if (!std::isfinite(p3[i * 3 + c])) return fail(MCPT_ERR_ARG, "probe " + std::to_string(i) + ": component that is not finite");
+    }
+    return MCPT_OK;
+}
+
+// The call itself, after the refusals: q's list, of q.kind, as the sample source of a render call on `stream`.
+static int query_device(mcpt_device* d, const DQuery& q, const int32_t* d_ids, int64_t n, int32_t spp, int32_t sample_base, uint64_t seed, int32_t flags,
+                        mcpt_stats* stats, void* stream)
+{
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
     if (stats) std::memset(stats, 0, sizeof *stats);
@@ -71,9 +101,8 @@ int mcpt_query_radiance_device(mcpt_device* d, const double* d_q6, const int32_t
     if (const int rc = geometry_gate(d)) return rc;
     if (const int rc = wait_for_frames(d)) return rc;       // the call uses frame slot 0 and the device's look stream
     mcpt_render_params rp{};
-    rp.spp = p->spp; rp.seed = p->seed; rp.world = 1; rp.flags = p->flags;
-    const DQuery q{d_q6, p->kind, d_mean3, d_stderr3, d_hits};
-    SampleRange r{p->sample_base, p->spp, p->spp, nullptr, nullptr, nullptr, nullptr, d->env.get()};
+    rp.spp = spp; rp.seed = seed; rp.world = 1; rp.flags = flags;
+    SampleRange r{sample_base, spp, spp, nullptr, nullptr, nullptr, nullptr, d->env.get()};
     r.query = &q;
     // a call that fails half-way must not leave half-recorded event pairs behind (render.cpp: mcpt_render_device)
     const size_t ev_used0 = d->ev_used;
@@ -83,47 +112,41 @@ int mcpt_query_radiance_device(mcpt_device* d, const double* d_q6, const int32_t
     return rc;
 }
 
-int mcpt_query_radiance(mcpt_device* d, const double* q6, const int32_t* ids, int64_t n, const mcpt_query_params* p, double* mean3, double* stderr3,
-                        int32_t* hits, mcpt_stats* stats)
+// The host-pointer form of a call whose list, of `kind`, has `in` doubles per entry and whose answers have `out`: the caller's arrays are pageable host
+// memory, so blocking copies on either side of the device form, which itself is ordered on d->stream.
+static int query_host(mcpt_device* d, int kind, int in, int out, const double* list, const int32_t* ids, int64_t n, int32_t spp,
+                      int32_t sample_base, uint64_t seed, int32_t flags, double* mean, double* err, int32_t* hits, mcpt_stats* stats)
 {
-    if (const int rc = params_check(p, n, q6, mean3)) return rc;
-    if (const int rc = list_check(q6, ids, n, p->kind)) return rc;
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n == 0) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
-    // the caller's arrays are pageable host memory: blocking copies on either side of the call, which itself is ordered on d->stream
     DevBuf<double> d_q, d_mean, d_err;
     DevBuf<int32_t> d_ids, d_hits;
     const size_t sn = size_t(n);
-    HIP_TRY(d_q.alloc(sn * 6));
-    HIP_TRY(d_mean.alloc(sn * 3));
-    if (stderr3) HIP_TRY(d_err.alloc(sn * 3));
+    HIP_TRY(d_q.alloc(sn * in));
+    HIP_TRY(d_mean.alloc(sn * out));
+    if (err) HIP_TRY(d_err.alloc(sn * out));
     if (hits) HIP_TRY(d_hits.alloc(sn));
     if (ids) HIP_TRY(d_ids.alloc(sn));
-    HIP_TRY(hipMemcpy(d_q.get(), q6, sn * 6 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_q.get(), list, sn * in * sizeof(double), hipMemcpyHostToDevice));
     if (ids) HIP_TRY(hipMemcpy(d_ids.get(), ids, sn * sizeof(int32_t), hipMemcpyHostToDevice));
     hipStream_t st = d->stream.get();
-    int rc = mcpt_query_radiance_device(d, d_q.get(), ids ? d_ids.get() : nullptr, n, p, d_mean.get(), stderr3 ? d_err.get() : nullptr,
-                                        hits ? d_hits.get() : nullptr, stats, st);
+    const DQuery q{d_q.get(), kind, d_mean.get(), err ? d_err.get() : nullptr, hits ? d_hits.get() : nullptr};
+    int rc = query_device(d, q, ids ? d_ids.get() : nullptr, n, spp, sample_base, seed, flags, stats, st);
     const hipError_t e = hipStreamSynchronize(st);          // also on failure: nothing enqueued may still use a copy when it goes
     if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
     if (rc != MCPT_OK) return rc;
-    HIP_TRY(hipMemcpy(mean3, d_mean.get(), sn * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (stderr3) HIP_TRY(hipMemcpy(stderr3, d_err.get(), sn * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(mean, d_mean.get(), sn * out * sizeof(double), hipMemcpyDeviceToHost));
+    if (err) HIP_TRY(hipMemcpy(err, d_err.get(), sn * out * sizeof(double), hipMemcpyDeviceToHost));
     if (hits) HIP_TRY(hipMemcpy(hits, d_hits.get(), sn * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MCPT_OK;
 }
 
-int mcpt_query_rays(mcpt_device* d, const double* q6, const int32_t* ids, int64_t n, uint64_t seed, int32_t kind, const int32_t* k, double* rays6)
+// the rays of a list on the host: the body of mcpt_query_rays and mcpt_query_sh_rays after their refusals (`in` doubles per entry)
+static int rays_host(mcpt_device* d, int kind, int in, const double* list, const int32_t* ids, int64_t n, uint64_t seed, const int32_t* k, double* rays6)
 {
-    if (const int rc = count_check(n)) return rc;
-    if (const int rc = kind_check(kind)) return rc;
-    if (n > 0 && (!q6 || !k || !rays6)) return fail(MCPT_ERR_ARG, "null argument");
-    for (int64_t i = 0; i < n; i++)
-        if (k[i] < 0) return fail(MCPT_ERR_ARG, "query " + std::to_string(i) + ": negative sample index");
-    if (const int rc = list_check(q6, ids, n, kind)) return rc;
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
     if (n == 0) return MCPT_OK;
@@ -131,11 +154,11 @@ int mcpt_query_rays(mcpt_device* d, const double* q6, const int32_t* ids, int64_
     DevBuf<double> d_q, d_rays;
     DevBuf<int32_t> d_ids, d_k;
     const size_t sn = size_t(n);
-    HIP_TRY(d_q.alloc(sn * 6));
+    HIP_TRY(d_q.alloc(sn * in));
     HIP_TRY(d_rays.alloc(sn * 6));
     HIP_TRY(d_k.alloc(sn));
     if (ids) HIP_TRY(d_ids.alloc(sn));
-    HIP_TRY(hipMemcpy(d_q.get(), q6, sn * 6 * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_q.get(), list, sn * in * sizeof(double), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_k.get(), k, sn * sizeof(int32_t), hipMemcpyHostToDevice));
     if (ids) HIP_TRY(hipMemcpy(d_ids.get(), ids, sn * sizeof(int32_t), hipMemcpyHostToDevice));
     hipStream_t st = d->stream.get();
@@ -146,6 +169,64 @@ int mcpt_query_rays(mcpt_device* d, const double* q6, const int32_t* ids, int64_
     if (e == hipSuccess) e = hipMemcpy(rays6, d_rays.get(), sn * 6 * sizeof(double), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
     return MCPT_OK;
+}
+
+extern "C" {
+
+int mcpt_query_radiance_device(mcpt_device* d, const double* d_q6, const int32_t* d_ids, int64_t n, const mcpt_query_params* p, double* d_mean3,
+                               double* d_stderr3, int32_t* d_hits, mcpt_stats* stats, void* stream)
+{
+    if (const int rc = params_check(p, n, d_q6, d_mean3)) return rc;
+    return query_device(d, DQuery{d_q6, p->kind, d_mean3, d_stderr3, d_hits}, d_ids, n, p->spp, p->sample_base, p->seed, p->flags, stats, stream);
+}
+
+int mcpt_query_radiance(mcpt_device* d, const double* q6, const int32_t* ids, int64_t n, const mcpt_query_params* p, double* mean3, double* stderr3,
+                        int32_t* hits, mcpt_stats* stats)
+{
+    if (const int rc = params_check(p, n, q6, mean3)) return rc;
+    if (const int rc = list_check(q6, ids, n, p->kind)) return rc;
+    return query_host(d, p->kind, 6, 3, q6, ids, n, p->spp, p->sample_base, p->seed, p->flags, mean3, stderr3,
+                      hits, stats);
+}
+
+int mcpt_query_rays(mcpt_device* d, const double* q6, const int32_t* ids, int64_t n, uint64_t seed, int32_t kind, const int32_t* k, double* rays6)
+{
+    if (const int rc = count_check(n)) return rc;
+    if (const int rc = kind_check(kind)) return rc;
+    if (n > 0 && (!q6 || !k || !rays6)) return fail(MCPT_ERR_ARG, "null argument");
+    for (int64_t i = 0; i < n; i++)
+        if (k[i] < 0) return fail(MCPT_ERR_ARG, "query " + std::to_string(i) + ": negative sample index");
+    if (const int rc = list_check(q6, ids, n, kind)) return rc;
+    return rays_host(d, kind, 6, q6, ids, n, seed, k, rays6);
+}
+
+// ---- light probes: the same calls over a list of positions, whose samples leave uniformly over the sphere (query.hpp) and fold into nine
+// spherical-harmonic coefficients per channel (query.hip: k_query_fold_sh)
+int mcpt_query_sh_device(mcpt_device* d, const double* d_p3, const int32_t* d_ids, int64_t n, const mcpt_sh_params* p, double* d_sh27, double* d_stderr27,
+                         int32_t* d_hits, mcpt_stats* stats, void* stream)
+{
+    if (const int rc = sh_params_check(p, n, d_p3, d_sh27)) return rc;
+    return query_device(d, DQuery{d_p3, MCPT_QUERY_KIND_SPHERE, d_sh27, d_stderr27, d_hits}, d_ids, n, p->spp, p->sample_base, p->seed, p->flags, stats,
+                        stream);
+}
+
+int mcpt_query_sh(mcpt_device* d, const double* p3, const int32_t* ids, int64_t n, const mcpt_sh_params* p, double* sh27, double* stderr27, int32_t* hits,
+                  mcpt_stats* stats)
+{
+    if (const int rc = sh_params_check(p, n, p3, sh27)) return rc;
+    if (const int rc = probe_list_check(p3, ids, n)) return rc;
+    return query_host(d, MCPT_QUERY_KIND_SPHERE, 3, 27, p3, ids, n, p->spp, p->sample_base, p->seed, p->flags,
+                      sh27, stderr27, hits, stats);
+}
+
+int mcpt_query_sh_rays(mcpt_device* d, const double* p3, const int32_t* ids, int64_t n, uint64_t seed, const int32_t* k, double* rays6)
+{
+    if (const int rc = count_check(n)) return rc;
+    if (n > 0 && (!p3 || !k || !rays6)) return fail(MCPT_ERR_ARG, "null argument");
+    for (int64_t i = 0; i < n; i++)
+        if (k[i] < 0) return fail(MCPT_ERR_ARG, "probe " + std::to_string(i) + ": negative sample index");
+    if (const int rc = probe_list_check(p3, ids, n)) return rc;
+    return rays_host(d, MCPT_QUERY_KIND_SPHERE, 3, p3, ids, n, seed, k, rays6);
 }
 
 }  // extern "C"

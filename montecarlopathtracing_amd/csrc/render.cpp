@@ -121,11 +121,14 @@ struct SampleSource {
     bool per_sample() const { return lens || query; }
 };
 
-// (S.env active: a missed pixel -- or camera ray -- folds the environment's radiance; d_dirs: the pinhole's primary directions)
+// (S.env active: a missed pixel -- or camera ray -- folds the environment's radiance; d_dirs: the pinhole's primary directions; seed: the
+// call's, from which a probe list's fold draws its samples' directions again)
 static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const PixelList& L, int first, int n_slots, double* d_img, bool lensed, const DScene& S,
-                       const double* d_dirs, hipStream_t st)
+                       const double* d_dirs, unsigned long long seed, hipStream_t st)
 {
-    if (r.query) launch_query_fold(*r.query, f.rad.get(), f.cam_hit.get(), first, n_slots, r.n, env_on(S.env), st);
+    if (r.query && r.query->kind == MCPT_QUERY_KIND_SPHERE)
+        launch_query_fold_sh(*r.query, seed, L.pixels, f.rad.get(), f.cam_hit.get(), first, n_slots, r.n, r.k0, env_on(S.env), st);
+    else if (r.query) launch_query_fold(*r.query, f.rad.get(), f.cam_hit.get(), first, n_slots, r.n, env_on(S.env), st);
     else if (r.motion && !lensed) launch_fold_motion(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, S.env, d_dirs, st);
     else if (lensed) launch_fold_lens(f.rad.get(), f.cam_hit.get(), L.pixels, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, r.hitcnt, env_on(S.env), st);
     else if (r.mom) launch_fold_progressive(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, S.env, d_dirs, st);
@@ -160,7 +163,7 @@ static int render_megakernel(mcpt_device* d, const DScene& S, mcpt_device::Frame
             ms_trace += ms;
         }
         launches++;
-        fold_range(f, r, L, int(first), n_slots, d_img, per_sample, S, d->dirs.get(), st);
+        fold_range(f, r, L, int(first), n_slots, d_img, per_sample, S, d->dirs.get(), p->seed, st);
         HIP_TRY(hipGetLastError());
     }
     return MCPT_OK;
@@ -314,7 +317,7 @@ static int render_wavefront(mcpt_device* d, const DScene& S, mcpt_device::FrameS
             launch_wf_logic(S, a, n_upper, false, st, d->cfg);
             HIP_TRY(hipGetLastError());
         }
-        fold_range(f, r, L, int(first), n_slots, d_img, per_sample, S, d->dirs.get(), st);
+        fold_range(f, r, L, int(first), n_slots, d_img, per_sample, S, d->dirs.get(), p->seed, st);
         HIP_TRY(hipGetLastError());
     }
     if (timed && !keep) {
