@@ -971,6 +971,74 @@ int mcpt_sh_basis(const double* d3, int64_t n, double* y9);                     
 int mcpt_sh_radiance(const double* sh27, const double* d3, int64_t n, double* rgb3);           /* probe i along direction i */
 int mcpt_sh_irradiance(const double* sh27, const double* n3, int64_t n, double* e3);           /* probe i under normal i */
 
+/* ---- lightmaps (since the lightmap change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* A LIGHTMAP is the irradiance at the surface points a UV chart maps its texels to.  The baker rasterises the chart, lists the covered
+ * texels with their positions and normals, asks mcpt_query_radiance's hemisphere kind for that list and puts the answers back: A LIGHTMAP
+ * IS, BIT FOR BIT, THE HEMISPHERE QUERY OF ITS OWN TEXEL LIST.  fp64, no contraction, IEEE division, every expression in the order written.
+ *   chart    : uv6[num_faces][6] = (au, av, bu, bv, cu, cv) of every face in .obj order; NULL: the scene's own vt1 vt2 vt3 (all zero in a
+ *              scene created without vt: nothing is covered, which is not an error).  The map is width x height texels, each size in
+ *              1 .. 16384.  Texel (x, y) has index T = y * width + x and centre pu = (x + 0.5) / width, pv = (y + 0.5) / height; row 0 is
+ *              the row nearest v = 0: no flip, no wrap.  UVs outside [0, 1] are allowed; only texels of the map count.
+ *   coverage : for face f with chart corners a, b, c and a centre p
+ *                area2 = (bu - au) * (cv - av) - (bv - av) * (cu - au)
+ *                e_a   = (bu - pu) * (cv - pv) - (bv - pv) * (cu - pu)
+ *                e_b   = (cu - pu) * (av - pv) - (cv - pv) * (au - pu)
+ *                e_c   = (au - pu) * (bv - pv) - (av - pv) * (bu - pu)
+ *              f COVERS the texel when area2 > 0 and e_a, e_b, e_c >= 0, or area2 < 0 and all three <= 0.  A face is skipped altogether
+ *              when area2 is 0 or not finite, or when its geometric normal n (Face::norm) has a length that is zero or not finite:
+ *              (nx nx + ny ny) + nz nz is 0, NaN or infinite.  owner[T] = the LOWEST .obj face index that covers T, or -1.  A centre
+ *              exactly on a shared edge or vertex is claimed by every face that touches it and the lowest wins: there is no top-left rule,
+ *              and the answer does not depend on how the work is spread.  Only the texels of a face's box are tested against it: those
+ *              whose centre lies between the smallest and the largest of its three u and of its three v, and one texel more on every side
+ *              (in exact arithmetic no centre outside the corners' box passes the three inequalities; a sliver thinner than fp64's
+ *              rounding does not get texels outside it from rounding either).
+ *   list     : the covered texels in ascending T.  For entry i with texel T and owner f:
+ *                w_a = e_a / area2, w_b = e_b / area2, w_c = e_c / area2;
+ *                position = (v1 * w_a + v2 * w_b) + v3 * w_c per component, from the device's current vertices (after
+ *                mcpt_device_update_vertices the updated ones; under a motion key 0's);
+ *                normal = the same blend of vn1, vn2, vn3 -- Face::norm instead when its squared length (x x + y y) + z z is 0 or not finite;
+ *                q6[i] = (position, normal), texels[i] = T.
+ *              The id of a texel's query is T, so its samples depend neither on which other texels are covered nor on the list's order.
+ *   bake     : mcpt_query_radiance_device over (q6, ids = texels) with kind MCPT_QUERY_HEMISPHERE and the caller's spp, sample_base, seed
+ *              and flags (0 or MCPT_RENDER_MEGAKERNEL); environment, light sampling, trace mode and engine are the device's.  Chunking,
+ *              statistics (rays_primary = samples = covered texels * spp), concurrency and the motion rule are that call's, word for word.
+ *   scatter  : irradiance3[T] = 3.141592653589793 * mean, stderr3[T] = 3.141592653589793 * stderr, hits[T] = the query's hit count.
+ *              Every texel that is not covered gets +0.0, +0.0 and 0.
+ *   dilation : dilate = R rounds, 0 .. 64, on irradiance3 only.  A texel is VALID before round 1 when it is covered.  In round r = 1 .. R
+ *              every texel not valid after round r - 1 looks at its 8 neighbours (y + dy, x + dx), dy and dx in -1 .. 1, row-major, inside
+ *              the map; if c >= 1 of them were valid after round r - 1, its irradiance becomes s / c per channel, s = 0.0 plus their values
+ *              of round r - 1 in that order, it becomes valid and its owner becomes -1 - r: a filled texel reads -2, -3, ..., -1 was
+ *              never filled and >= 0 is a face.  stderr3 and hits of filled texels stay 0.  Every round reads the frame of the round
+ *              before and writes another, so the result does not depend on scheduling.
+ * mcpt_lightmap_raster_host is the coverage rule alone for a caller's chart, on the CPU: no device, no scene, hence never the skip by a
+ * face's normal.  mcpt_lightmap_texels is coverage and list on the device; it returns the number of covered texels (< 0: MCPT_ERR_*);
+ * owner[W*H], texels[cap] and q6[cap*6] may each be NULL; more covered texels than cap while a list is asked for: MCPT_ERR_ARG.
+ * mcpt_bake_lightmap is all five steps: irradiance3[W*H*3] is required, stderr3[W*H*3], hits[W*H] and owner[W*H] may be NULL.  The host
+ * form is synchronous.  The _device form takes device pointers throughout (d_uv6 as num_faces * 6 device doubles) and enqueues on `stream`;
+ * IT WAITS ONCE FOR THE STREAM, for the number of covered texels (4 bytes come back to the host, as the display histogram's slots do),
+ * and otherwise returns without waiting when stats == NULL.  No texel covered: MCPT_OK, no query is launched, the maps are all zero and
+ * owner all -1.  A device keeps the baker's workspace from its first bake on (about 4 bytes per texel of the largest map so far, up to 104 per
+ * covered texel, 8 per face, and with dilation 28 more per texel); a bake first waits for the device's previous bake.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE, in this order): NULL parameters, a size outside 1 .. 16384, spp < 1, sample_base < 0,
+ * sample_base + spp > 2^31 - 1, a flag other than 0 or MCPT_RENDER_MEGAKERNEL, dilate outside 0 .. 64, reserved != 0, NULL irradiance3;
+ * mcpt_lightmap_texels: a size outside 1 .. 16384, cap < 0; mcpt_lightmap_raster_host: num_faces < 0, a size outside 1 .. 16384, NULL uv6
+ * or owner.  In the host-pointer forms a chart component that is not finite is MCPT_ERR_ARG as well -- on a device, after the missing
+ * device and the NULL device, because the chart's length is the device's face count.  The device form does not look: a face whose area2
+ * is not finite is skipped.
+ * Not covered: UV unwrapping and packing; supersampling or conservative coverage (a sliver that contains no texel centre gets no texel:
+ * dilation is the remedy); rejecting texels whose point lies inside other geometry; directional or SH lightmaps; the multi-device group
+ * and render_scene; the use of a lightmap in shading. */
+typedef struct { int32_t width, height, spp, sample_base; uint64_t seed;
+                 int32_t flags, dilate, reserved[2]; } mcpt_lightmap_params;
+int     mcpt_lightmap_raster_host(const double* uv6, int64_t num_faces, int32_t width, int32_t height, int32_t* owner);
+int64_t mcpt_lightmap_texels(mcpt_device*, const double* uv6, int32_t width, int32_t height,
+                             int32_t* owner, int32_t* texels, double* q6, int64_t cap);
+int mcpt_bake_lightmap(mcpt_device*, const double* uv6, const mcpt_lightmap_params*,
+                       double* irradiance3, double* stderr3, int32_t* hits, int32_t* owner, mcpt_stats*);
+int mcpt_bake_lightmap_device(mcpt_device*, const double* d_uv6, const mcpt_lightmap_params*,
+                              double* d_irradiance3, double* d_stderr3, int32_t* d_hits, int32_t* d_owner,
+                              mcpt_stats*, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,12 @@ class ShParams(C.Structure):
     _fields_ = [("spp", C.c_int32), ("sample_base", C.c_int32), ("seed", C.c_uint64), ("flags", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class LightmapParams(C.Structure):
+    """mcpt_lightmap_params: a lightmap's size, samples per texel, first sample index, seed, flags and dilation rounds"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("spp", C.c_int32), ("sample_base", C.c_int32), ("seed", C.c_uint64),
+                ("flags", C.c_int32), ("dilate", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -200,6 +206,7 @@ EXPORTS = [
     "mcpt_display_host", "mcpt_progressive_display", "mcpt_progressive_display_device", "mcpt_render_scene_display",
     "mcpt_query_radiance", "mcpt_query_radiance_device", "mcpt_query_rays",
     "mcpt_query_sh", "mcpt_query_sh_device", "mcpt_query_sh_rays", "mcpt_sh_basis", "mcpt_sh_radiance", "mcpt_sh_irradiance",
+    "mcpt_lightmap_raster_host", "mcpt_lightmap_texels", "mcpt_bake_lightmap", "mcpt_bake_lightmap_device",
 ]
 
 
@@ -379,6 +386,12 @@ def lib():
     L.mcpt_sh_basis.argtypes = [D, C.c_int64, D]
     L.mcpt_sh_radiance.argtypes = [D, D, C.c_int64, D]
     L.mcpt_sh_irradiance.argtypes = [D, D, C.c_int64, D]
+    LP = C.POINTER(LightmapParams)
+    L.mcpt_lightmap_raster_host.argtypes = [D, C.c_int64, C.c_int32, C.c_int32, I32]
+    L.mcpt_lightmap_texels.argtypes = [P, D, C.c_int32, C.c_int32, I32, I32, D, C.c_int64]
+    L.mcpt_lightmap_texels.restype = C.c_int64
+    L.mcpt_bake_lightmap.argtypes = [P, D, LP, D, D, I32, I32, C.POINTER(Stats)]
+    L.mcpt_bake_lightmap_device.argtypes = [P, P, LP, P, P, P, P, C.POINTER(Stats), P]
     _lib = L
     return L
 

@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -136,6 +136,51 @@ def sh_irradiance(sh, normals):
     e = np.zeros((nrm.shape[0], 3))
     check(lib().mcpt_sh_irradiance(_p(sh, C.c_double), _p(nrm, C.c_double), nrm.shape[0], _p(e, C.c_double)))
     return e
+
+
+def _chart(uv, num_faces=None):
+    """a UV chart as (num_faces, 6) float64 = (au, av, bu, bv, cu, cv) per face in .obj order"""
+    uv = np.ascontiguousarray(uv, dtype=np.float64)
+    if uv.ndim != 2 or uv.shape[1] != 6 or (num_faces is not None and uv.shape[0] != num_faces):
+        raise ValueError("a chart must have shape (%s, 6), not %r" % ("num_faces" if num_faces is None else num_faces, uv.shape))
+    return uv
+
+
+def _map_size(width, height):
+    for name, v in (("width", width), ("height", height)):
+        if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("%s must be a 32-bit integer" % name)
+    return int(width), int(height)
+
+
+def lightmap_raster(uv, width, height):
+    """Coverage of a width x height lightmap by a UV chart, on the CPU (mcpt_lightmap_raster_host; no device, no scene): uv (num_faces, 6)
+    -> owner [height, width] int32, the lowest face whose chart triangle covers the texel's centre, or -1."""
+    uv = _chart(uv)
+    width, height = _map_size(width, height)
+    owner = np.zeros((max(height, 0), max(width, 0)), dtype=np.int32)
+    check(lib().mcpt_lightmap_raster_host(_p(uv, C.c_double), uv.shape[0], width, height, _p(owner, C.c_int32)))
+    return owner
+
+
+def grid_atlas(num_faces, width, height, pad=1):
+    """A trivial chart for a scene that has none, so that it can be baked: the map is cut into C x C square cells of s = min(width, height)
+    // C texels, C = ceil(sqrt(num_faces)); face f gets the cell at column f % C, row f // C, and its corners in texel units are
+    (x0 + pad, y0 + pad), (x0 + s - pad, y0 + pad), (x0 + pad, y0 + s - pad), divided by (width, height).  Not an unwrapper: every face
+    is a right triangle in its own cell, whatever its shape.  ValueError when s < 2 * pad + 2.  Returns (num_faces, 6)."""
+    num_faces, pad = int(num_faces), int(pad)
+    if num_faces < 1 or pad < 0:
+        raise ValueError("grid_atlas needs at least one face and pad >= 0")
+    cells = math.isqrt(num_faces - 1) + 1                       # ceil(sqrt(num_faces)), in integers
+    s = min(int(width), int(height)) // cells
+    if s < 2 * pad + 2:
+        raise ValueError("a %d x %d map gives %d faces cells of %d texels: at least %d are needed" % (width, height, num_faces, s, 2 * pad + 2))
+    f = np.arange(num_faces)
+    x0, y0 = (f % cells) * s, (f // cells) * s
+    uv = np.stack([x0 + pad, y0 + pad, x0 + s - pad, y0 + pad, x0 + pad, y0 + s - pad], axis=1).astype(np.float64)
+    uv[:, 0::2] /= float(width)
+    uv[:, 1::2] /= float(height)
+    return uv
 
 
 def _as_lens(lens):
@@ -640,6 +685,40 @@ class Device:
         rays = np.zeros((p.shape[0], 6))
         check(lib().mcpt_query_sh_rays(self._h, _p(p, C.c_double), _p(ids, C.c_int32), p.shape[0], int(seed), _p(k, C.c_int32), _p(rays, C.c_double)))
         return rays
+
+    def lightmap_texels(self, width, height, uv=None):
+        """Coverage and texel list of a width x height lightmap on the device (mcpt_lightmap_texels): uv (num_faces, 6) or None for the
+        scene's own vt.  Returns (owner [height, width], texels [n] ascending, q6 [n, 6] = position, normal of every covered texel)."""
+        width, height = _map_size(width, height)
+        uv = _chart(uv, self.scene.info.num_faces) if uv is not None else None
+        owner = np.zeros((max(height, 0), max(width, 0)), dtype=np.int32)
+        n = lib().mcpt_lightmap_texels(self._h, _p(uv, C.c_double), width, height, _p(owner, C.c_int32), None, None, 0)
+        if n < 0:
+            check(n)
+        texels, q6 = np.zeros(n, dtype=np.int32), np.zeros((n, 6))
+        if n > 0:
+            got = lib().mcpt_lightmap_texels(self._h, _p(uv, C.c_double), width, height, None, _p(texels, C.c_int32), _p(q6, C.c_double), n)
+            if got < 0:
+                check(got)
+        return owner, texels, q6
+
+    def bake_lightmap(self, width, height, spp, uv=None, seed=0, sample_base=0, dilate=0, flags=0, stats=None):
+        """A lightmap (mcpt_bake_lightmap): the irradiance at the surface points a chart maps its texels to -- uv (num_faces, 6), or None
+        for the scene's own vt -- from spp hemisphere samples per covered texel, keyed (seed, texel index, sample); dilate rounds fill
+        the gutters.  Returns (E [height, width, 3], E_stderr [height, width, 3], hits [height, width], owner [height, width]); owner is
+        the face of a covered texel, -1 - r for a texel filled in round r, -1 otherwise."""
+        width, height = _map_size(width, height)
+        for name, v in (("spp", spp), ("sample_base", sample_base), ("flags", flags), ("dilate", dilate)):
+            if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError("%s must be a 32-bit integer" % name)
+        uv = _chart(uv, self.scene.info.num_faces) if uv is not None else None
+        shape = (max(height, 0), max(width, 0))
+        E, err = np.zeros(shape + (3,)), np.zeros(shape + (3,))
+        hits, owner = np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int32)
+        lp = LightmapParams(width, height, int(spp), int(sample_base), int(seed), int(flags), int(dilate), (C.c_int32 * 2)(0, 0))
+        check(lib().mcpt_bake_lightmap(self._h, _p(uv, C.c_double), C.byref(lp), _p(E, C.c_double), _p(err, C.c_double), _p(hits, C.c_int32),
+                                       _p(owner, C.c_int32), C.byref(stats) if stats is not None else None))
+        return E, err, hits, owner
 
     def set_environment(self, rgb=None, scale=1.0):
         """The environment light of every later frame, sample_radiance and progressive handle created after it (mcpt_device_set_environment):

@@ -9,6 +9,7 @@
 //   light_sampling.cpp  MCPT_LIGHTS_ONE and MCPT_LIGHTS_TREE: the pick table, the light tree, their upload, the picks' test seams
 //   motion.cpp        a device's motion: the shutter's steps between two keyframes, the return to key 0
 //   display_api.cpp   the display transform: histogram, exposure, the map to 8-bit pixels on the GPU and on the host
+//   lightmap_api.cpp  lightmap baking: a UV chart's coverage, its texel list, the hemisphere query of that list, scatter and dilation
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -184,6 +185,20 @@ struct mcpt_device {
     bool geometry_failed = false;                   // an update failed midway: nothing is traced or rendered until one succeeds
     // display transform (display_api.cpp): the luminance histogram's slots and their pinned copy, made on the first call that takes one
     mcpt::DevBuf<unsigned long long> disp_slots; mcpt::HostBuf<int64_t> h_disp_slots;
+    // lightmap baking (lightmap_api.cpp): what a bake keeps between its kernels, made by the first one and grown to the largest map so far.
+    // A device-form bake may return with its kernels still enqueued, so none of this is a local of the call; `done` is recorded behind a
+    // bake's last kernel and waited for before the next one writes here.
+    struct Lightmap {
+        mcpt::DevBuf<int32_t> owner[2], slot_of_face, big, block_counts, block_offsets, total;
+        mcpt::DevBuf<unsigned int> n_big;
+        mcpt::DevBuf<unsigned long long> masks;
+        mcpt::DevBuf<int32_t> texels, hits;             // the covered texels' list and the query's answers, by list entry
+        mcpt::DevBuf<double> q6, mean, err;
+        mcpt::DevBuf<double> irr;                       // the dilation's second frame
+        mcpt::HostBuf<int32_t> h_total;                 // pinned word the covered count lands in
+        mcpt::Event done;
+    };
+    std::unique_ptr<Lightmap> lm;
 };
 
 // The helpers below are the library's own: none of them is exported from libmcpt.so.
@@ -258,6 +273,15 @@ int display_check(const mcpt_display_params* p);    // MCPT_ERR_ARG: not display
 int display_frame_device(mcpt_device* d, const double* d_img, const int32_t* d_pixels, int64_t n, const mcpt_display_params* p, uint8_t* d_out,
                          mcpt_display_info* info, hipStream_t st);
 int display_histogram_device(mcpt_device* d, const double* d_img, const int32_t* d_pixels, int64_t n, int64_t* slots, hipStream_t st);
+
+// ---- query_api.cpp
+// what every query call refuses of its sample range and count, and of its flags (MCPT_ERR_ARG)
+int range_check(int32_t spp, int32_t sample_base, int64_t n);
+int flags_check(int32_t flags);
+// The query call itself, after the refusals: q's list, of q.kind, as the sample source of a render call on `stream` (device pointers
+// throughout; d_ids null: entry i has id i).  stats (may be null) is cleared first; n == 0 launches nothing.
+int query_device(mcpt_device* d, const mcpt::DQuery& q, const int32_t* d_ids, int64_t n, int32_t spp, int32_t sample_base, uint64_t seed, int32_t flags,
+                 mcpt_stats* stats, void* stream);
 
 // ---- render.cpp
 inline bool lens_active(const mcpt_lens& l) { return l.flags != 0 || l.aperture > 0.0; }

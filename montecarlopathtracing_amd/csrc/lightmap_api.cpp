@@ -1,0 +1,245 @@
+// C ABI, lightmap baking (include/mcpt.h: mcpt_lightmap_*, mcpt_bake_lightmap*): a UV chart is rasterised into a map of texels, the
+// covered texels become a list of surface points, mcpt_query_radiance's hemisphere kind answers that list (query_api.cpp: query_device,
+// unchanged), and the answers go back into the map, whose gutters are dilated.  Everything but the host rasteriser runs on the GPU
+// (lightmap.hip); the host waits once per call, for the number of covered texels.
+#include <hip/hip_runtime_api.h>
+
+#include <cmath>
+#include <cstring>
+#include <string>
+
+#include "handles.hpp"
+#include "lightmap.hpp"
+
+using namespace mcpt;
+
+static int size_check(int32_t width, int32_t height)
+{
+    return width >= 1 && width <= kLightmapMaxSize && height >= 1 && height <= kLightmapMaxSize
+               ? MCPT_OK
+               : fail(MCPT_ERR_ARG, "a lightmap's width and height must be in 1 .. 16384");
+}
+
+static int chart_check(const double* uv6, int64_t num_faces)
+{
+    for (int64_t i = 0; i < num_faces * 6; i++)
+        if (!std::isfinite(uv6[i])) return fail(MCPT_ERR_ARG, "chart of face " + std::to_string(i / 6) + ": component that is not finite");
+    return MCPT_OK;
+}
+
+// what both forms of mcpt_bake_lightmap refuse without looking at the chart
+static int params_check(const mcpt_lightmap_params* p, const void* irradiance3)
+{
+    if (!p) return fail(MCPT_ERR_ARG, "null lightmap parameters");
+    if (const int rc = size_check(p->width, p->height)) return rc;
+    if (const int rc = range_check(p->spp, p->sample_base, int64_t(p->width) * p->height)) return rc;
+    if (const int rc = flags_check(p->flags)) return rc;
+    if (p->dilate < 0 || p->dilate > kLightmapMaxDilate) return fail(MCPT_ERR_ARG, "dilate must be in 0 .. 64");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(MCPT_ERR_ARG, "mcpt_lightmap_params.reserved must be 0");
+    if (!irradiance3) return fail(MCPT_ERR_ARG, "null irradiance map");
+    return MCPT_OK;
+}
+
+// what every call on a device does before it reads the device's triangles: the device itself, key 0 of a motion, a geometry that stands
+static int device_gate(mcpt_device* d)
+{
+    if (const int rc = require_device()) return rc;
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    HIP_TRY(hipSetDevice(d->ordinal));
+    if (const int rc = motion_home(d)) return rc;
+    return geometry_gate(d);
+}
+
+// the workspace of a W x H map on d, once the bake before this one has left it
+static int ensure_work(mcpt_device* d, int W, int H, LightmapWork& w)
+{
+    if (!d->lm) {
+        d->lm = std::make_unique<mcpt_device::Lightmap>();
+        HIP_TRY(create(d->lm->done, hipEventCreateWithFlags, hipEventDisableTiming));
+        HIP_TRY(d->lm->h_total.alloc(1));
+        HIP_TRY(d->lm->total.alloc(1));
+        HIP_TRY(d->lm->n_big.alloc(1));
+    }
+    mcpt_device::Lightmap& m = *d->lm;
+    HIP_TRY(hipEventSynchronize(m.done.get()));
+    const size_t n = size_t(W) * H, t = size_t(d->ds.t > 0 ? d->ds.t : 1), blocks = size_t(lightmap_blocks((long long)n));
+    HIP_TRY(m.owner[0].grow(n));
+    HIP_TRY(m.slot_of_face.grow(t));
+    HIP_TRY(m.big.grow(t));
+    HIP_TRY(m.masks.grow(blocks * 4));
+    HIP_TRY(m.block_counts.grow(blocks));
+    HIP_TRY(m.block_offsets.grow(blocks));
+    w = LightmapWork{m.owner[0].get(), m.slot_of_face.get(), m.big.get(), m.n_big.get(), m.masks.get(), m.block_counts.get(), m.block_offsets.get(),
+                     m.total.get()};
+    return MCPT_OK;
+}
+
+// Step 1 on st and the number of covered texels, which the host waits for: 4 bytes back.
+static int raster_device(mcpt_device* d, const double* d_uv6, int W, int H, const LightmapWork& w, hipStream_t st, int32_t& covered)
+{
+    launch_lightmap_raster(d->ds, d_uv6, W, H, w, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(d->lm->h_total.get(), w.total, sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    covered = d->lm->h_total[0];
+    return MCPT_OK;
+}
+
+// Steps 1 to 5 on st, after the refusals; device pointers throughout.
+static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_params& p, double* d_irr, double* d_err, int32_t* d_hits, int32_t* d_owner,
+                       mcpt_stats* stats, hipStream_t st)
+{
+    if (const int rc = device_gate(d)) return rc;
+    if (stats) std::memset(stats, 0, sizeof *stats);
+    const int W = p.width, H = p.height, R = p.dilate;
+    const size_t n = size_t(W) * H;
+    LightmapWork w{};
+    if (const int rc = ensure_work(d, W, H, w)) return rc;
+    mcpt_device::Lightmap& m = *d->lm;
+    if (R > 0) {
+        HIP_TRY(m.owner[1].grow(n));
+        HIP_TRY(m.irr.grow(n * 3));
+    }
+    int32_t covered = 0;
+    if (const int rc = raster_device(d, d_uv6, W, H, w, st, covered)) return rc;
+    // the rounds alternate between the caller's frame and the baker's own: the scatter starts where R rounds end in the caller's
+    double* frame[2] = {d_irr, m.irr.get()};
+    int at = R & 1;
+    HIP_TRY(hipMemsetAsync(frame[at], 0, n * 3 * sizeof(double), st));
+    if (d_err) HIP_TRY(hipMemsetAsync(d_err, 0, n * 3 * sizeof(double), st));
+    if (d_hits) HIP_TRY(hipMemsetAsync(d_hits, 0, n * sizeof(int32_t), st));
+    if (covered > 0) {
+        const size_t c = size_t(covered);
+        HIP_TRY(m.texels.grow(c));
+        HIP_TRY(m.q6.grow(c * 6));
+        HIP_TRY(m.mean.grow(c * 3));
+        if (d_err) HIP_TRY(m.err.grow(c * 3));
+        if (d_hits) HIP_TRY(m.hits.grow(c));
+        launch_lightmap_texels(d->ds, d_uv6, W, H, w, m.texels.get(), m.q6.get(), st);
+        HIP_TRY(hipGetLastError());
+        const DQuery q{m.q6.get(), MCPT_QUERY_HEMISPHERE, m.mean.get(), d_err ? m.err.get() : nullptr, d_hits ? m.hits.get() : nullptr};
+        if (const int rc = query_device(d, q, m.texels.get(), covered, p.spp, p.sample_base, p.seed, p.flags, stats, st)) return rc;
+        launch_lightmap_scatter(m.texels.get(), covered, q.mean3, q.stderr3, q.hits, frame[at], d_err, d_hits, st);
+        HIP_TRY(hipGetLastError());
+    }
+    int32_t* own[2] = {m.owner[0].get(), m.owner[1].get()};
+    for (int r = 1; r <= R; r++) {
+        launch_lightmap_dilate(frame[at], own[(r - 1) & 1], W, H, r, frame[at ^ 1], own[r & 1], st);
+        at ^= 1;
+    }
+    HIP_TRY(hipGetLastError());
+    if (d_owner) HIP_TRY(hipMemcpyAsync(d_owner, own[R & 1], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipEventRecord(m.done.get(), st));
+    return MCPT_OK;
+}
+
+// a chart of the caller's on the device (null stays null: the scene's own vt)
+static int upload_chart(const mcpt_device* d, const double* uv6, DevBuf<double>& d_uv)
+{
+    if (!uv6) return MCPT_OK;
+    const size_t c = size_t(d->ds.t) * 6;
+    HIP_TRY(d_uv.alloc(c));
+    if (c > 0) HIP_TRY(hipMemcpy(d_uv.get(), uv6, c * sizeof(double), hipMemcpyHostToDevice));
+    return MCPT_OK;
+}
+
+extern "C" {
+
+int mcpt_lightmap_raster_host(const double* uv6, int64_t num_faces, int32_t width, int32_t height, int32_t* owner)
+{
+    if (num_faces < 0 || num_faces > 0x7ffffffe) return fail(MCPT_ERR_ARG, "the number of faces must be in 0 .. 2^31 - 2");
+    if (const int rc = size_check(width, height)) return rc;
+    if (!owner || (num_faces > 0 && !uv6)) return fail(MCPT_ERR_ARG, "null argument");
+    if (const int rc = chart_check(uv6, num_faces)) return rc;
+    const size_t n = size_t(width) * height;
+    for (size_t i = 0; i < n; i++) owner[i] = -1;
+    // faces in descending order, so that the lowest face that covers a texel is the last to write it
+    for (int64_t f = num_faces - 1; f >= 0; f--) {
+        const double* uv = uv6 + f * 6;
+        const double area2 = lightmap_area2(uv);
+        if (!lightmap_area_ok(area2)) continue;
+        int x0, x1, y0, y1;
+        if (!lightmap_box(uv, width, height, x0, x1, y0, y1)) continue;
+        for (int y = y0; y <= y1; y++) {
+            const double pv = lightmap_centre(y, height);
+            for (int x = x0; x <= x1; x++) {
+                double e[3];
+                lightmap_edges(uv, lightmap_centre(x, width), pv, e);
+                if (lightmap_covers(area2, e)) owner[size_t(y) * width + x] = int32_t(f);
+            }
+        }
+    }
+    return MCPT_OK;
+}
+
+int64_t mcpt_lightmap_texels(mcpt_device* d, const double* uv6, int32_t width, int32_t height, int32_t* owner, int32_t* texels, double* q6, int64_t cap)
+{
+    if (const int rc = size_check(width, height)) return rc;
+    if (cap < 0) return fail(MCPT_ERR_ARG, "cap must be >= 0");
+    if (const int rc = require_device()) return rc;
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (uv6)
+        if (const int rc = chart_check(uv6, d->ds.t)) return rc;
+    if (const int rc = device_gate(d)) return rc;
+    DevBuf<double> d_uv, d_q6;
+    DevBuf<int32_t> d_texels;
+    if (const int rc = upload_chart(d, uv6, d_uv)) return rc;
+    LightmapWork w{};
+    if (const int rc = ensure_work(d, width, height, w)) return rc;
+    hipStream_t st = d->stream.get();
+    int32_t covered = 0;
+    if (const int rc = raster_device(d, d_uv.get(), width, height, w, st, covered)) return rc;
+    const size_t n = size_t(width) * height, c = size_t(covered);
+    if ((texels || q6) && covered > cap) return fail(MCPT_ERR_ARG, "more texels are covered (" + std::to_string(covered) + ") than the list holds");
+    if (owner) HIP_TRY(hipMemcpy(owner, w.owner, n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if ((texels || q6) && covered > 0) {
+        if (texels) HIP_TRY(d_texels.alloc(c));
+        if (q6) HIP_TRY(d_q6.alloc(c * 6));
+        launch_lightmap_texels(d->ds, d_uv.get(), width, height, w, d_texels.get(), d_q6.get(), st);
+        hipError_t e = hipGetLastError();
+        const hipError_t es = hipStreamSynchronize(st);        // also on failure: nothing enqueued may still use the lists when they go
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
+        if (texels) HIP_TRY(hipMemcpy(texels, d_texels.get(), c * sizeof(int32_t), hipMemcpyDeviceToHost));
+        if (q6) HIP_TRY(hipMemcpy(q6, d_q6.get(), c * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return covered;
+}
+
+int mcpt_bake_lightmap_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_params* p, double* d_irradiance3, double* d_stderr3,
+                              int32_t* d_hits, int32_t* d_owner, mcpt_stats* stats, void* stream)
+{
+    if (const int rc = params_check(p, d_irradiance3)) return rc;
+    return bake_device(d, d_uv6, *p, d_irradiance3, d_stderr3, d_hits, d_owner, stats, static_cast<hipStream_t>(stream));
+}
+
+int mcpt_bake_lightmap(mcpt_device* d, const double* uv6, const mcpt_lightmap_params* p, double* irradiance3, double* stderr3, int32_t* hits,
+                       int32_t* owner, mcpt_stats* stats)
+{
+    if (const int rc = params_check(p, irradiance3)) return rc;
+    if (const int rc = require_device()) return rc;
+    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (uv6)
+        if (const int rc = chart_check(uv6, d->ds.t)) return rc;
+    HIP_TRY(hipSetDevice(d->ordinal));
+    const size_t n = size_t(p->width) * p->height;
+    DevBuf<double> d_uv, d_irr, d_err;
+    DevBuf<int32_t> d_hits, d_owner;
+    if (const int rc = upload_chart(d, uv6, d_uv)) return rc;
+    HIP_TRY(d_irr.alloc(n * 3));
+    if (stderr3) HIP_TRY(d_err.alloc(n * 3));
+    if (hits) HIP_TRY(d_hits.alloc(n));
+    if (owner) HIP_TRY(d_owner.alloc(n));
+    hipStream_t st = d->stream.get();
+    int rc = bake_device(d, d_uv.get(), *p, d_irr.get(), d_err.get(), d_hits.get(), d_owner.get(), stats, st);
+    const hipError_t e = hipStreamSynchronize(st);              // also on failure: nothing enqueued may still use a copy when it goes
+    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
+    if (rc != MCPT_OK) return rc;
+    HIP_TRY(hipMemcpy(irradiance3, d_irr.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (stderr3) HIP_TRY(hipMemcpy(stderr3, d_err.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost));
+    if (hits) HIP_TRY(hipMemcpy(hits, d_hits.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (owner) HIP_TRY(hipMemcpy(owner, d_owner.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return MCPT_OK;
+}
+
+}  // extern "C"

@@ -24,15 +24,15 @@ static int count_check(int64_t n)
 }
 
 // what every query call refuses of its sample range and count, and of its flags: the pieces of params_check and sh_params_check, which
-// refuse the same things in the same order
-static int range_check(int32_t spp, int32_t sample_base, int64_t n)
+// refuse the same things in the same order (lightmap_api.cpp shares them: handles.hpp)
+int range_check(int32_t spp, int32_t sample_base, int64_t n)
 {
     if (spp < 1) return fail(MCPT_ERR_ARG, "spp must be >= 1");
     if (sample_base < 0) return fail(MCPT_ERR_ARG, "sample_base must be >= 0");
     if (int64_t(sample_base) + int64_t(spp) > kInt32Max) return fail(MCPT_ERR_ARG, "sample_base + spp must not exceed 2^31 - 1");
     return count_check(n);
 }
-static int flags_check(int32_t flags)
+int flags_check(int32_t flags)
 {
     return flags == 0 || flags == MCPT_RENDER_MEGAKERNEL ? MCPT_OK : fail(MCPT_ERR_ARG, "unknown query flag (0 or MCPT_RENDER_MEGAKERNEL)");
 }
@@ -90,8 +90,8 @@ static int probe_list_check(const double* p3, const int32_t* ids, int64_t n)
 }
 
 // The call itself, after the refusals: q's list, of q.kind, as the sample source of a render call on `stream`.
-static int query_device(mcpt_device* d, const DQuery& q, const int32_t* d_ids, int64_t n, int32_t spp, int32_t sample_base, uint64_t seed, int32_t flags,
-                        mcpt_stats* stats, void* stream)
+int query_device(mcpt_device* d, const DQuery& q, const int32_t* d_ids, int64_t n, int32_t spp, int32_t sample_base, uint64_t seed, int32_t flags,
+                 mcpt_stats* stats, void* stream)
 {
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
