@@ -912,8 +912,9 @@ int mcpt_render_scene_display(const char* path, const char* filename, int32_t sp
  * The host-pointer form is synchronous.  The device form (device pointers throughout) enqueues on `stream` and returns without waiting
  * when stats == NULL.  Both use the device's frame slot 0 and first wait for the device's frames still in flight (MCPT_RENDER_PIPELINE /
  * KEEP_STATS).  Queries are allowed while progressive handles of the device live: they touch none of a handle's state.
- * Not covered: the multi-device group, render_scene, per-query sample counts, adaptive stopping of queries.  The radiance of the whole
- * sphere about a point, for any normal afterwards, is a light probe's (below), not a kind of this call. */
+ * Not covered: the multi-device group, render_scene, sample counts given per query by the caller.  Queries that stop on their own error
+ * estimate are the adaptive queries' block below.  The radiance of the whole sphere about a point, for any normal afterwards, is a light
+ * probe's (below), not a kind of this call. */
 #define MCPT_QUERY_RAY        0   /* q = origin xyz, direction xyz */
 #define MCPT_QUERY_HEMISPHERE 1   /* q = position xyz, normal xyz  */
 typedef struct { int32_t spp, sample_base; uint64_t seed; int32_t kind, flags, reserved[2]; } mcpt_query_params;
@@ -1027,7 +1028,8 @@ int mcpt_sh_irradiance(const double* sh27, const double* n3, int64_t n, double* 
  * is not finite is skipped.
  * Not covered: UV unwrapping and packing; supersampling or conservative coverage (a sliver that contains no texel centre gets no texel:
  * dilation is the remedy); rejecting texels whose point lies inside other geometry; directional or SH lightmaps; the multi-device group
- * and render_scene; the use of a lightmap in shading. */
+ * and render_scene; the use of a lightmap in shading.  Texels that stop on their own error estimate are mcpt_bake_lightmap_adaptive's
+ * (adaptive queries, below). */
 typedef struct { int32_t width, height, spp, sample_base; uint64_t seed;
                  int32_t flags, dilate, reserved[2]; } mcpt_lightmap_params;
 int     mcpt_lightmap_raster_host(const double* uv6, int64_t num_faces, int32_t width, int32_t height, int32_t* owner);
@@ -1038,6 +1040,61 @@ int mcpt_bake_lightmap(mcpt_device*, const double* uv6, const mcpt_lightmap_para
 int mcpt_bake_lightmap_device(mcpt_device*, const double* d_uv6, const mcpt_lightmap_params*,
                               double* d_irradiance3, double* d_stderr3, int32_t* d_hits, int32_t* d_owner,
                               mcpt_stats*, void* stream);
+
+/* ---- adaptive queries and lightmaps (since the adaptive-query change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* AN ADAPTIVE QUERY CALL is mcpt_query_radiance in passes: every query stops on its own error estimate, as a pixel of an adaptive frame
+ * does, and the active list is compacted on the GPU without atomics.  It takes a list, a mcpt_query_params -- whose spp is now the LARGEST
+ * count a query may get -- and a mcpt_adaptive_params (rel_target, abs_target, min_spp, as for frames).  Keys, kinds (MCPT_QUERY_RAY and
+ * MCPT_QUERY_HEMISPHERE), shading, flags, environment, light sampling, trace mode and the motion rule are mcpt_query_radiance's.
+ *   passes   : boundaries b_0 = min(min_spp, spp), b_{j+1} = min(2 * b_j, spp), computed in 64 bits; the last boundary is spp.  A min_spp
+ *              above spp is taken as spp: one pass, the one-shot call.  Pass j renders samples [sample_base + b_{j-1}, sample_base + b_j)
+ *              of the active queries only, with b_{-1} = 0.  Queries only leave the list, so all active queries share the count.
+ *              mcpt_query_pass_boundaries writes the boundaries of (spp >= 1, min_spp >= 2) to bounds[cap] (may be NULL) and returns
+ *              their number; more boundaries than cap while a list is asked for, or cap < 0: MCPT_ERR_ARG.  Host only, no device.
+ *   stopping : after the pass that ends at k = b_j < spp, query i stops when
+ *                  se2 < rel2 * m2 + abs2
+ *              with se2, m2, rel2 and abs2 exactly as in mcpt_progressive_create_adaptive's text above: fp64 without contraction, the
+ *              channels summed in order 0, 1, 2, from query i's own s1_c and s2_c, the fold's sums, added in k order.  k >= min_spp holds
+ *              at every boundary by construction.  THERE IS NO MISS RULE: a query has no pixel whose value is known to be +0.0 for every
+ *              count, and under an environment a missed ray carries Le(d).  A query whose samples are all +0.0 has se2 = m2 = 0, so it
+ *              stops only when abs_target > 0 (with abs_target = 0 it runs to spp).  A query that is still active at spp keeps count spp.
+ *   answers  : with c_i the count of query i: mean = s1 / c_i; stderr = sqrt(se2_c(c_i)), and 0 when c_i < 2; hits = the number of those
+ *              c_i samples whose ray hit; counts[i] = c_i -- mcpt_query_radiance's fold expressions.  Hence
+ *              QUERY i OF AN ADAPTIVE CALL IS, BIT FOR BIT, QUERY i OF mcpt_query_radiance WITH spp = counts[i], the same id, seed and
+ *              sample_base.  With both targets 0 every count is spp and the whole call is the one-shot call, bit for bit.  The sums
+ *              continue across passes exactly: they start from +0.0 and add every sample of a pass in k order, and a stored fp64 sum
+ *              reloaded is the same sum.  Stopping on a query's own variance estimate biases its estimate slightly, as for a frame.
+ *              mean3 is required; stderr3, hits and counts may be NULL.
+ *   stats    : rays_primary = samples = the sum of counts, added up over the passes; the other counters likewise, ms_trace and ms_total
+ *              the passes' sums.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE): first mcpt_query_radiance's own, in its order (the host-pointer form's look at the
+ * list included); then NULL adaptive parameters, targets that are not finite or are negative, min_spp < 2, reserved != 0.  n == 0:
+ * MCPT_OK, nothing is launched.
+ * The host-pointer form is synchronous.  The _device form takes device pointers throughout and enqueues on `stream`; AFTER EVERY PASS BUT
+ * THE LAST IT WAITS FOR THE STREAM, for the length of the next list (4 bytes come back to the host through a pinned word, as an adaptive
+ * frame's step and the baker's texel count do), and stops early when that list is empty; after the last pass it enqueues the finishing
+ * kernel and returns without waiting when stats == NULL.  Both forms use the device's frame slot 0 and first wait for the device's frames
+ * in flight; live progressive handles are untouched.  A device keeps the call's workspace from its first adaptive call on (117 bytes per
+ * query of the longest list so far); a call first waits for the device's previous adaptive call.
+ * AN ADAPTIVE LIGHTMAP IS, BIT FOR BIT, THE ADAPTIVE HEMISPHERE QUERY OF ITS OWN TEXEL LIST (ids = the texel indices), scattered as a
+ * lightmap's: coverage, list, scatter, dilation, refusals and waiting are mcpt_bake_lightmap's with the adaptive call in the query's place
+ * (so the _device form waits for the texel count and then as above); the adaptive parameters are refused after the lightmap's own.
+ * counts[T] (W*H, may be NULL) is the texel's count, and 0 where the texel is not covered or was only dilated.  The targets apply to the
+ * query's mean, which is the irradiance over pi: rel_target does not care about the scale, ABS_TARGET DOES -- an absolute error e of the
+ * irradiance is abs_target = e / pi.
+ * Not covered: adaptive light probes, sample counts given per query by the caller, a caller-chosen pass schedule, the multi-device group,
+ * render_scene. */
+int mcpt_query_pass_boundaries(int32_t spp, int32_t min_spp, int32_t* bounds, int32_t cap);
+int mcpt_query_radiance_adaptive(mcpt_device*, const double* q6, const int32_t* ids, int64_t n, const mcpt_query_params*,
+                                 const mcpt_adaptive_params*, double* mean3, double* stderr3, int32_t* hits, int32_t* counts, mcpt_stats*);
+int mcpt_query_radiance_adaptive_device(mcpt_device*, const double* d_q6, const int32_t* d_ids, int64_t n, const mcpt_query_params*,
+                                        const mcpt_adaptive_params*, double* d_mean3, double* d_stderr3, int32_t* d_hits, int32_t* d_counts,
+                                        mcpt_stats*, void* stream);
+int mcpt_bake_lightmap_adaptive(mcpt_device*, const double* uv6, const mcpt_lightmap_params*, const mcpt_adaptive_params*,
+                                double* irradiance3, double* stderr3, int32_t* hits, int32_t* owner, int32_t* counts, mcpt_stats*);
+int mcpt_bake_lightmap_adaptive_device(mcpt_device*, const double* d_uv6, const mcpt_lightmap_params*, const mcpt_adaptive_params*,
+                                       double* d_irradiance3, double* d_stderr3, int32_t* d_hits, int32_t* d_owner, int32_t* d_counts,
+                                       mcpt_stats*, void* stream);
 
 #ifdef __cplusplus
 }

@@ -207,6 +207,8 @@ EXPORTS = [
     "mcpt_query_radiance", "mcpt_query_radiance_device", "mcpt_query_rays",
     "mcpt_query_sh", "mcpt_query_sh_device", "mcpt_query_sh_rays", "mcpt_sh_basis", "mcpt_sh_radiance", "mcpt_sh_irradiance",
     "mcpt_lightmap_raster_host", "mcpt_lightmap_texels", "mcpt_bake_lightmap", "mcpt_bake_lightmap_device",
+    "mcpt_query_pass_boundaries", "mcpt_query_radiance_adaptive", "mcpt_query_radiance_adaptive_device",
+    "mcpt_bake_lightmap_adaptive", "mcpt_bake_lightmap_adaptive_device",
 ]
 
 
@@ -392,6 +394,12 @@ def lib():
     L.mcpt_lightmap_texels.restype = C.c_int64
     L.mcpt_bake_lightmap.argtypes = [P, D, LP, D, D, I32, I32, C.POINTER(Stats)]
     L.mcpt_bake_lightmap_device.argtypes = [P, P, LP, P, P, P, P, C.POINTER(Stats), P]
+    AP = C.POINTER(AdaptiveParams)
+    L.mcpt_query_pass_boundaries.argtypes = [C.c_int32, C.c_int32, I32, C.c_int32]
+    L.mcpt_query_radiance_adaptive.argtypes = [P, D, I32, C.c_int64, QP, AP, D, D, I32, I32, C.POINTER(Stats)]
+    L.mcpt_query_radiance_adaptive_device.argtypes = [P, P, P, C.c_int64, QP, AP, P, P, P, P, C.POINTER(Stats), P]
+    L.mcpt_bake_lightmap_adaptive.argtypes = [P, D, LP, AP, D, D, I32, I32, I32, C.POINTER(Stats)]
+    L.mcpt_bake_lightmap_adaptive_device.argtypes = [P, P, LP, AP, P, P, P, P, P, C.POINTER(Stats), P]
     _lib = L
     return L
 

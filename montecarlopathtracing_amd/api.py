@@ -138,6 +138,29 @@ def sh_irradiance(sh, normals):
     return e
 
 
+def _adaptive_params(rel_target, abs_target, min_spp):
+    """mcpt_adaptive_params of the adaptive query calls: the targets as floats, min_spp a 32-bit integer (the library judges their values)"""
+    if not isinstance(min_spp, numbers.Integral) or not -2 ** 31 <= min_spp < 2 ** 31:
+        raise ValueError("min_spp must be a 32-bit integer")
+    return AdaptiveParams(float(rel_target), float(abs_target), int(min_spp), 0)
+
+
+def query_pass_boundaries(spp, min_spp):
+    """The pass boundaries of an adaptive query call (mcpt_query_pass_boundaries): b_0 = min(min_spp, spp), doubling up to spp itself.
+    Returns them as an int32 array; no device is needed."""
+    for name, v in (("spp", spp), ("min_spp", min_spp)):
+        if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("%s must be a 32-bit integer" % name)
+    n = lib().mcpt_query_pass_boundaries(int(spp), int(min_spp), None, 0)
+    if n < 0:
+        check(n)
+    b = np.zeros(n, dtype=np.int32)
+    got = lib().mcpt_query_pass_boundaries(int(spp), int(min_spp), _p(b, C.c_int32), n)
+    if got < 0:
+        check(got)
+    return b
+
+
 def _chart(uv, num_faces=None):
     """a UV chart as (num_faces, 6) float64 = (au, av, bu, bv, cu, cv) per face in .obj order"""
     uv = np.ascontiguousarray(uv, dtype=np.float64)
@@ -632,6 +655,38 @@ class Device:
         mean, err, hits = self._query(q, ids, spp, seed, sample_base, QUERY_HEMISPHERE, flags, stats)
         return math.pi * mean, math.pi * err, hits
 
+    def _query_adaptive(self, q, ids, spp, rel_target, abs_target, min_spp, seed, sample_base, kind, flags, stats):
+        for name, v in (("spp", spp), ("sample_base", sample_base), ("flags", flags)):
+            if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError("%s must be a 32-bit integer" % name)
+        ap = _adaptive_params(rel_target, abs_target, min_spp)
+        n = q.shape[0]
+        mean, err = np.zeros((n, 3)), np.zeros((n, 3))
+        hits, counts = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        qp = QueryParams(int(spp), int(sample_base), int(seed), kind, int(flags), (C.c_int32 * 2)(0, 0))
+        check(lib().mcpt_query_radiance_adaptive(self._h, _p(q, C.c_double), _p(ids, C.c_int32), n, C.byref(qp), C.byref(ap), _p(mean, C.c_double),
+                                                 _p(err, C.c_double), _p(hits, C.c_int32), _p(counts, C.c_int32),
+                                                 C.byref(stats) if stats is not None else None))
+        return mean, err, hits, counts
+
+    def radiance_adaptive(self, rays, spp, rel_target, abs_target=0.0, min_spp=16, seed=0, ids=None, sample_base=0, flags=0, stats=None):
+        """radiance() in passes (mcpt_query_radiance_adaptive): spp is the largest count a query may get; after each pass, whose boundaries
+        double from min_spp (query_pass_boundaries), a query stops once its own error estimate meets the targets.  Query i is radiance()'s
+        with spp = counts[i], bit for bit.  Returns (mean [n,3], stderr [n,3], hits [n], counts [n])."""
+        q, ids = self._query_list(rays, ids)
+        return self._query_adaptive(q, ids, spp, rel_target, abs_target, min_spp, seed, sample_base, QUERY_RAY, flags, stats)
+
+    def irradiance_adaptive(self, points, normals, spp, rel_target, abs_target=0.0, min_spp=16, seed=0, ids=None, sample_base=0, flags=0, stats=None):
+        """irradiance() in passes (mcpt_query_radiance_adaptive, MCPT_QUERY_HEMISPHERE); the targets apply to the query's mean, E / pi.
+        Returns (E [n,3], E_stderr [n,3], hits [n], counts [n])."""
+        points = np.asarray(points, dtype=np.float64)
+        normals = np.asarray(normals, dtype=np.float64)
+        if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+            raise ValueError("points and normals must both have shape (n, 3)")
+        q, ids = self._query_list(np.concatenate([points, normals], axis=1), ids, "points and normals")
+        mean, err, hits, counts = self._query_adaptive(q, ids, spp, rel_target, abs_target, min_spp, seed, sample_base, QUERY_HEMISPHERE, flags, stats)
+        return math.pi * mean, math.pi * err, hits, counts
+
     def query_rays(self, q, seed, k, kind="ray", ids=None):
         """test seam (mcpt_query_rays): the ray of sample k[i] of query i, (n, 6) = origin, direction; kind is "ray" or "hemisphere" """
         if kind not in _QUERY_KINDS:
@@ -719,6 +774,26 @@ class Device:
         check(lib().mcpt_bake_lightmap(self._h, _p(uv, C.c_double), C.byref(lp), _p(E, C.c_double), _p(err, C.c_double), _p(hits, C.c_int32),
                                        _p(owner, C.c_int32), C.byref(stats) if stats is not None else None))
         return E, err, hits, owner
+
+    def bake_lightmap_adaptive(self, width, height, spp, rel_target, abs_target=0.0, min_spp=16, uv=None, seed=0, sample_base=0, dilate=0, flags=0,
+                               stats=None):
+        """bake_lightmap() whose texels stop on their own error estimate (mcpt_bake_lightmap_adaptive): the adaptive hemisphere query of
+        the map's own texel list; spp is the largest count a texel may get and the targets apply to E / pi.  Returns (E, E_stderr, hits,
+        owner, counts), each [height, width(, 3)]; counts is 0 where a texel is not covered or was only dilated."""
+        width, height = _map_size(width, height)
+        for name, v in (("spp", spp), ("sample_base", sample_base), ("flags", flags), ("dilate", dilate)):
+            if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError("%s must be a 32-bit integer" % name)
+        ap = _adaptive_params(rel_target, abs_target, min_spp)
+        uv = _chart(uv, self.scene.info.num_faces) if uv is not None else None
+        shape = (max(height, 0), max(width, 0))
+        E, err = np.zeros(shape + (3,)), np.zeros(shape + (3,))
+        hits, owner, counts = np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int32)
+        lp = LightmapParams(width, height, int(spp), int(sample_base), int(seed), int(flags), int(dilate), (C.c_int32 * 2)(0, 0))
+        check(lib().mcpt_bake_lightmap_adaptive(self._h, _p(uv, C.c_double), C.byref(lp), C.byref(ap), _p(E, C.c_double), _p(err, C.c_double),
+                                                _p(hits, C.c_int32), _p(owner, C.c_int32), _p(counts, C.c_int32),
+                                                C.byref(stats) if stats is not None else None))
+        return E, err, hits, owner, counts
 
     def set_environment(self, rgb=None, scale=1.0):
         """The environment light of every later frame, sample_radiance and progressive handle created after it (mcpt_device_set_environment):

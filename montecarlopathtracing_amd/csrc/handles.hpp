@@ -10,6 +10,7 @@
 //   motion.cpp        a device's motion: the shutter's steps between two keyframes, the return to key 0
 //   display_api.cpp   the display transform: histogram, exposure, the map to 8-bit pixels on the GPU and on the host
 //   lightmap_api.cpp  lightmap baking: a UV chart's coverage, its texel list, the hemisphere query of that list, scatter and dilation
+//   adaptive_query_api.cpp  adaptive queries: the query call in passes, every query stopping on its own error estimate
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -23,6 +24,7 @@
 #include <vector>
 
 #include "accel_build.hpp"
+#include "adaptive_query.hpp"
 #include "hip_owned.hpp"
 #include "kernels.hpp"
 #include "knobs.hpp"
@@ -193,12 +195,29 @@ struct mcpt_device {
         mcpt::DevBuf<unsigned int> n_big;
         mcpt::DevBuf<unsigned long long> masks;
         mcpt::DevBuf<int32_t> texels, hits;             // the covered texels' list and the query's answers, by list entry
+        mcpt::DevBuf<int32_t> counts;                   // an adaptive bake: the queries' own sample counts, by list entry
         mcpt::DevBuf<double> q6, mean, err;
         mcpt::DevBuf<double> irr;                       // the dilation's second frame
         mcpt::HostBuf<int32_t> h_total;                 // pinned word the covered count lands in
         mcpt::Event done;
     };
     std::unique_ptr<Lightmap> lm;
+    // adaptive queries (adaptive_query_api.cpp): what a call keeps between its passes, made by the first one and grown to the longest
+    // list so far.  A device-form call returns with its finishing kernel enqueued, so none of this is a local of the call; `done` is
+    // recorded behind a call's last kernel and waited for before the next one writes here.
+    struct AdaptiveQuery {
+        mcpt::DevBuf<double> mom;                       // [n][2][3] the queries' moments, by position in the caller's list
+        mcpt::DevBuf<int32_t> hitcnt, cnt;              // [n] hit counts and sample counts
+        mcpt::DevBuf<int32_t> sel[2];                   // the active list (positions, ascending) and the next one
+        mcpt::DevBuf<uint8_t> ones;                     // [n] the selection's hit bytes: a query has no miss rule
+        mcpt::DevBuf<double> cq6;                       // the compact list of a pass
+        mcpt::DevBuf<int32_t> cids;
+        mcpt::DevBuf<unsigned long long> masks;
+        mcpt::DevBuf<int32_t> block_counts, block_offsets, total;
+        mcpt::HostBuf<int32_t> h_total;                 // pinned word the next list's length lands in
+        mcpt::Event done;
+    };
+    std::unique_ptr<AdaptiveQuery> aq;
 };
 
 // The helpers below are the library's own: none of them is exported from libmcpt.so.
@@ -283,6 +302,18 @@ int flags_check(int32_t flags);
 int query_device(mcpt_device* d, const mcpt::DQuery& q, const int32_t* d_ids, int64_t n, int32_t spp, int32_t sample_base, uint64_t seed, int32_t flags,
                  mcpt_stats* stats, void* stream);
 
+// the refusals of mcpt_query_radiance's two forms, shared with the adaptive call (adaptive_query_api.cpp): the parameters, and the list itself
+int query_params_check(const mcpt_query_params* p, int64_t n, const void* q6, const void* mean3);
+int query_list_check(const double* q6, const int32_t* ids, int64_t n, int32_t kind);
+
+// ---- adaptive_query_api.cpp
+// what the adaptive calls refuse of their adaptive parameters (MCPT_ERR_ARG)
+int adaptive_params_check(const mcpt_adaptive_params* ap);
+// The adaptive query call after the refusals, device pointers throughout: q's list in passes on `stream`, d_counts (may be null) the
+// queries' own counts.  stats (may be null) is cleared first; n == 0 launches nothing.
+int adaptive_query_device(mcpt_device* d, const mcpt::DQuery& q, const int32_t* d_ids, int64_t n, int32_t spp, int32_t sample_base, uint64_t seed,
+                          int32_t flags, const mcpt_adaptive_params& ap, int32_t* d_counts, mcpt_stats* stats, void* stream);
+
 // ---- render.cpp
 inline bool lens_active(const mcpt_lens& l) { return l.flags != 0 || l.aperture > 0.0; }
 int lens_check(const mcpt_lens* l);
@@ -310,6 +341,10 @@ struct SampleRange {
     // ray through the per-sample route and is folded into the list's own outputs (d_img, mom, hit, lens and hitcnt are not read; the
     // PixelList holds the ids, or null for the slot itself).  Null: a frame or a pass.
     const mcpt::DQuery* query = nullptr;
+    // A pass of an adaptive query call (adaptive_query_api.cpp; host side, the pointers are the device's): `query` is the compact list of
+    // the active queries and answers nothing itself -- the fold continues the moments and hit counts of the caller's positions
+    // (k_query_fold_moments).  Null: a query call folds into its own outputs.
+    const mcpt::QueryMoments* moments = nullptr;
 };
 
 // The pixels a render call covers, on the device: the partition's owned list (mcpt_render*, uniform progressive passes) or an adaptive

@@ -85,9 +85,10 @@ static int raster_device(mcpt_device* d, const double* d_uv6, int W, int H, cons
     return MCPT_OK;
 }
 
-// Steps 1 to 5 on st, after the refusals; device pointers throughout.
-static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_params& p, double* d_irr, double* d_err, int32_t* d_hits, int32_t* d_owner,
-                       mcpt_stats* stats, hipStream_t st)
+// Steps 1 to 5 on st, after the refusals; device pointers throughout.  ap: an adaptive bake (mcpt_bake_lightmap_adaptive) -- step 3 is the
+// adaptive query call (adaptive_query_api.cpp) and d_counts (may be null) the map of the texels' own sample counts; null: a uniform bake.
+static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_params& p, const mcpt_adaptive_params* ap, double* d_irr, double* d_err,
+                       int32_t* d_hits, int32_t* d_owner, int32_t* d_counts, mcpt_stats* stats, hipStream_t st)
 {
     if (const int rc = device_gate(d)) return rc;
     if (stats) std::memset(stats, 0, sizeof *stats);
@@ -108,6 +109,7 @@ static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_
     HIP_TRY(hipMemsetAsync(frame[at], 0, n * 3 * sizeof(double), st));
     if (d_err) HIP_TRY(hipMemsetAsync(d_err, 0, n * 3 * sizeof(double), st));
     if (d_hits) HIP_TRY(hipMemsetAsync(d_hits, 0, n * sizeof(int32_t), st));
+    if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, n * sizeof(int32_t), st));
     if (covered > 0) {
         const size_t c = size_t(covered);
         HIP_TRY(m.texels.grow(c));
@@ -115,10 +117,16 @@ static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_
         HIP_TRY(m.mean.grow(c * 3));
         if (d_err) HIP_TRY(m.err.grow(c * 3));
         if (d_hits) HIP_TRY(m.hits.grow(c));
+        if (d_counts) HIP_TRY(m.counts.grow(c));
         launch_lightmap_texels(d->ds, d_uv6, W, H, w, m.texels.get(), m.q6.get(), st);
         HIP_TRY(hipGetLastError());
         const DQuery q{m.q6.get(), MCPT_QUERY_HEMISPHERE, m.mean.get(), d_err ? m.err.get() : nullptr, d_hits ? m.hits.get() : nullptr};
-        if (const int rc = query_device(d, q, m.texels.get(), covered, p.spp, p.sample_base, p.seed, p.flags, stats, st)) return rc;
+        if (ap) {
+            if (const int rc = adaptive_query_device(d, q, m.texels.get(), covered, p.spp, p.sample_base, p.seed, p.flags, *ap,
+                                                     d_counts ? m.counts.get() : nullptr, stats, st))
+                return rc;
+            if (d_counts) launch_aq_scatter_counts(m.texels.get(), covered, m.counts.get(), d_counts, st);
+        } else if (const int rc = query_device(d, q, m.texels.get(), covered, p.spp, p.sample_base, p.seed, p.flags, stats, st)) return rc;
         launch_lightmap_scatter(m.texels.get(), covered, q.mean3, q.stderr3, q.hits, frame[at], d_err, d_hits, st);
         HIP_TRY(hipGetLastError());
     }
@@ -210,13 +218,15 @@ int mcpt_bake_lightmap_device(mcpt_device* d, const double* d_uv6, const mcpt_li
                               int32_t* d_hits, int32_t* d_owner, mcpt_stats* stats, void* stream)
 {
     if (const int rc = params_check(p, d_irradiance3)) return rc;
-    return bake_device(d, d_uv6, *p, d_irradiance3, d_stderr3, d_hits, d_owner, stats, static_cast<hipStream_t>(stream));
+    return bake_device(d, d_uv6, *p, nullptr, d_irradiance3, d_stderr3, d_hits, d_owner, nullptr, stats, static_cast<hipStream_t>(stream));
 }
 
-int mcpt_bake_lightmap(mcpt_device* d, const double* uv6, const mcpt_lightmap_params* p, double* irradiance3, double* stderr3, int32_t* hits,
-                       int32_t* owner, mcpt_stats* stats)
+}  // extern "C"
+
+// the host-pointer form of both bakes, after their refusals (ap null: the uniform one)
+static int bake_host(mcpt_device* d, const double* uv6, const mcpt_lightmap_params* p, const mcpt_adaptive_params* ap, double* irradiance3, double* stderr3,
+                     int32_t* hits, int32_t* owner, int32_t* counts, mcpt_stats* stats)
 {
-    if (const int rc = params_check(p, irradiance3)) return rc;
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
     if (uv6)
@@ -224,14 +234,15 @@ int mcpt_bake_lightmap(mcpt_device* d, const double* uv6, const mcpt_lightmap_pa
     HIP_TRY(hipSetDevice(d->ordinal));
     const size_t n = size_t(p->width) * p->height;
     DevBuf<double> d_uv, d_irr, d_err;
-    DevBuf<int32_t> d_hits, d_owner;
+    DevBuf<int32_t> d_hits, d_owner, d_counts;
     if (const int rc = upload_chart(d, uv6, d_uv)) return rc;
     HIP_TRY(d_irr.alloc(n * 3));
+    if (counts) HIP_TRY(d_counts.alloc(n));
     if (stderr3) HIP_TRY(d_err.alloc(n * 3));
     if (hits) HIP_TRY(d_hits.alloc(n));
     if (owner) HIP_TRY(d_owner.alloc(n));
     hipStream_t st = d->stream.get();
-    int rc = bake_device(d, d_uv.get(), *p, d_irr.get(), d_err.get(), d_hits.get(), d_owner.get(), stats, st);
+    int rc = bake_device(d, d_uv.get(), *p, ap, d_irr.get(), d_err.get(), d_hits.get(), d_owner.get(), d_counts.get(), stats, st);
     const hipError_t e = hipStreamSynchronize(st);              // also on failure: nothing enqueued may still use a copy when it goes
     if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
     if (rc != MCPT_OK) return rc;
@@ -239,7 +250,34 @@ int mcpt_bake_lightmap(mcpt_device* d, const double* uv6, const mcpt_lightmap_pa
     if (stderr3) HIP_TRY(hipMemcpy(stderr3, d_err.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost));
     if (hits) HIP_TRY(hipMemcpy(hits, d_hits.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if (owner) HIP_TRY(hipMemcpy(owner, d_owner.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (counts) HIP_TRY(hipMemcpy(counts, d_counts.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MCPT_OK;
+}
+
+extern "C" {
+
+int mcpt_bake_lightmap(mcpt_device* d, const double* uv6, const mcpt_lightmap_params* p, double* irradiance3, double* stderr3, int32_t* hits,
+                       int32_t* owner, mcpt_stats* stats)
+{
+    if (const int rc = params_check(p, irradiance3)) return rc;
+    return bake_host(d, uv6, p, nullptr, irradiance3, stderr3, hits, owner, nullptr, stats);
+}
+
+int mcpt_bake_lightmap_adaptive_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_params* p, const mcpt_adaptive_params* ap,
+                                       double* d_irradiance3, double* d_stderr3, int32_t* d_hits, int32_t* d_owner, int32_t* d_counts, mcpt_stats* stats,
+                                       void* stream)
+{
+    if (const int rc = params_check(p, d_irradiance3)) return rc;
+    if (const int rc = adaptive_params_check(ap)) return rc;
+    return bake_device(d, d_uv6, *p, ap, d_irradiance3, d_stderr3, d_hits, d_owner, d_counts, stats, static_cast<hipStream_t>(stream));
+}
+
+int mcpt_bake_lightmap_adaptive(mcpt_device* d, const double* uv6, const mcpt_lightmap_params* p, const mcpt_adaptive_params* ap, double* irradiance3,
+                                double* stderr3, int32_t* hits, int32_t* owner, int32_t* counts, mcpt_stats* stats)
+{
+    if (const int rc = params_check(p, irradiance3)) return rc;
+    if (const int rc = adaptive_params_check(ap)) return rc;
+    return bake_host(d, uv6, p, ap, irradiance3, stderr3, hits, owner, counts, stats);
 }
 
 }  // extern "C"

@@ -23,7 +23,7 @@ static int count_check(int64_t n)
     return n >= 0 && n <= kInt32Max ? MCPT_OK : fail(MCPT_ERR_ARG, "the number of queries must be in 0 .. 2^31 - 1");
 }
 
-// what every query call refuses of its sample range and count, and of its flags: the pieces of params_check and sh_params_check, which
+// what every query call refuses of its sample range and count, and of its flags: the pieces of query_params_check and sh_params_check, which
 // refuse the same things in the same order (lightmap_api.cpp shares them: handles.hpp)
 int range_check(int32_t spp, int32_t sample_base, int64_t n)
 {
@@ -38,7 +38,7 @@ int flags_check(int32_t flags)
 }
 
 // what both forms of mcpt_query_radiance refuse without looking at the list
-static int params_check(const mcpt_query_params* p, int64_t n, const void* q6, const void* mean3)
+int query_params_check(const mcpt_query_params* p, int64_t n, const void* q6, const void* mean3)
 {
     if (!p) return fail(MCPT_ERR_ARG, "null query parameters");
     if (const int rc = range_check(p->spp, p->sample_base, n)) return rc;
@@ -60,7 +60,7 @@ static int sh_params_check(const mcpt_sh_params* p, int64_t n, const void* p3, c
 }
 
 // what the host-pointer forms refuse of the list itself
-static int list_check(const double* q6, const int32_t* ids, int64_t n, int32_t kind)
+int query_list_check(const double* q6, const int32_t* ids, int64_t n, int32_t kind)
 {
     for (int64_t i = 0; i < n; i++) {
         if (ids && ids[i] < 0) return fail(MCPT_ERR_ARG, "query " + std::to_string(i) + ": negative id");
@@ -176,15 +176,15 @@ extern "C" {
 int mcpt_query_radiance_device(mcpt_device* d, const double* d_q6, const int32_t* d_ids, int64_t n, const mcpt_query_params* p, double* d_mean3,
                                double* d_stderr3, int32_t* d_hits, mcpt_stats* stats, void* stream)
 {
-    if (const int rc = params_check(p, n, d_q6, d_mean3)) return rc;
+    if (const int rc = query_params_check(p, n, d_q6, d_mean3)) return rc;
     return query_device(d, DQuery{d_q6, p->kind, d_mean3, d_stderr3, d_hits}, d_ids, n, p->spp, p->sample_base, p->seed, p->flags, stats, stream);
 }
 
 int mcpt_query_radiance(mcpt_device* d, const double* q6, const int32_t* ids, int64_t n, const mcpt_query_params* p, double* mean3, double* stderr3,
                         int32_t* hits, mcpt_stats* stats)
 {
-    if (const int rc = params_check(p, n, q6, mean3)) return rc;
-    if (const int rc = list_check(q6, ids, n, p->kind)) return rc;
+    if (const int rc = query_params_check(p, n, q6, mean3)) return rc;
+    if (const int rc = query_list_check(q6, ids, n, p->kind)) return rc;
     return query_host(d, p->kind, 6, 3, q6, ids, n, p->spp, p->sample_base, p->seed, p->flags, mean3, stderr3,
                       hits, stats);
 }
@@ -196,7 +196,7 @@ int mcpt_query_rays(mcpt_device* d, const double* q6, const int32_t* ids, int64_
     if (n > 0 && (!q6 || !k || !rays6)) return fail(MCPT_ERR_ARG, "null argument");
     for (int64_t i = 0; i < n; i++)
         if (k[i] < 0) return fail(MCPT_ERR_ARG, "query " + std::to_string(i) + ": negative sample index");
-    if (const int rc = list_check(q6, ids, n, kind)) return rc;
+    if (const int rc = query_list_check(q6, ids, n, kind)) return rc;
     return rays_host(d, kind, 6, q6, ids, n, seed, k, rays6);
 }
 

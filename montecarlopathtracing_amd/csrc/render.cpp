@@ -128,6 +128,7 @@ static void fold_range(mcpt_device::FrameSlot& f, const SampleRange& r, const Pi
 {
     if (r.query && r.query->kind == MCPT_QUERY_KIND_SPHERE)
         launch_query_fold_sh(*r.query, seed, L.pixels, f.rad.get(), f.cam_hit.get(), first, n_slots, r.n, r.k0, env_on(S.env), st);
+    else if (r.query && r.moments) launch_query_fold_moments(*r.moments, f.rad.get(), f.cam_hit.get(), first, n_slots, r.n, env_on(S.env), st);
     else if (r.query) launch_query_fold(*r.query, f.rad.get(), f.cam_hit.get(), first, n_slots, r.n, env_on(S.env), st);
     else if (r.motion && !lensed) launch_fold_motion(f.rad.get(), L.pixels, f.hits.get(), first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, S.env, d_dirs, st);
     else if (lensed) launch_fold_lens(f.rad.get(), f.cam_hit.get(), L.pixels, first, n_slots, r.n, r.k0, r.N, d_img, r.mom, r.hit, r.hitcnt, env_on(S.env), st);
