@@ -1096,6 +1096,69 @@ int mcpt_bake_lightmap_adaptive_device(mcpt_device*, const double* d_uv6, const 
                                        double* d_irradiance3, double* d_stderr3, int32_t* d_hits, int32_t* d_owner, int32_t* d_counts,
                                        mcpt_stats*, void* stream);
 
+/* ---- lightmap denoising (since the lightmap-denoise change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* mcpt_lightmap_denoise: an edge-avoiding a-trous wavelet filter of an irradiance map in UV space, guided by the world position, the
+ * normal and the world footprint of every covered texel and by the map's own standard error.  A frame's filter (mcpt_progressive_denoise)
+ * cannot be pointed at a lightmap: neighbours in the map need not be neighbours in the world, there is no depth, material or albedo, and
+ * gutter texels carry no data.  The call takes maps, not a bake, so it serves mcpt_bake_lightmap, mcpt_bake_lightmap_adaptive and maps
+ * the caller has accumulated: irradiance3[W*H*3] and stderr3[W*H*3] as a bake writes them, out3[W*H*3], owner[W*H] (may be NULL).  out3 may
+ * be the same buffer as irradiance3: every input is read before anything is written.  BAKE WITH dilate = 0 AND LET THIS CALL DILATE: it
+ * dilates after it filters, and never reads a texel that is not covered.
+ * THE DENOISED MAP IS BIASED: it trades variance for a bias towards the neighbours' values.  A MAP WHOSE stderr3 IS 0 COMES BACK
+ * ESSENTIALLY UNFILTERED (the luminance stop is closed: only taps of exactly the same luminance count) -- a bake with spp = 1 is such a map.
+ * The struct carries the map's size, so there is no all-zero-means-defaults rule: iterations is K as given, 0 .. 10 (0: no filtering), a
+ * sigma of 0 is its default, dilate = R rounds, 0 .. 64.  The filter, in fp64 without contraction, every sum in the order written:
+ *   coverage : mcpt_bake_lightmap's step 1 on the same chart (uv6 as there; NULL: the scene's own vt) gives owner[T].  T is COVERED when
+ *              owner[T] >= 0.  Only covered texels are read from irradiance3 and stderr3: anything may stand at the others, NaN and the
+ *              results of an earlier dilation included.
+ *   guides   : of a covered texel T with owner f.  Position p and normal n are the q6 of T's entry of mcpt_lightmap_texels, bit for bit.
+ *              n^ = n divided by its length sqrt((n_x n_x + n_y n_y) + n_z n_z); a zero normal stays 0.  The footprint h is the world
+ *              length of a texel's side on f: e1 = v2 - v1, e2 = v3 - v1 from the device's current vertices,
+ *              c = e1 x e2 = (e1_y e2_z - e1_z e2_y, e1_z e2_x - e1_x e2_z, e1_x e2_y - e1_y e2_x), A2 = sqrt((c_x c_x + c_y c_y) + c_z c_z),
+ *              h = sqrt(A2 / (|area2_f| * (double(W) * double(H)))), area2_f the chart's of coverage.
+ *   input    : e = irradiance3[T]; lum(e) = (0.2126 e_0 + 0.7152 e_1) + 0.0722 e_2; v = sum_c (w_c * w_c) * (se_c * se_c) from 0.0,
+ *              se = stderr3[T], w = (0.2126, 0.7152, 0.0722), channels in order.  There is no demodulation: irradiance carries no albedo.
+ *   iteration i = 0 .. K-1, step s = 2^i, from (e, v) to (e', v'):
+ *     g_p  = sum k_q v_q / sum k_q over the 3 x 3 window q = p + (dx, dy), dx, dy in -1..1 row-major, q inside the map and covered;
+ *            k_q = b[dx] b[dy], b = (1/4, 1/2, 1/4).
+ *     taps : q = p + s (dx, dy) for dy, dx in -2..2, row-major; a tap counts when q is inside the map and covered.
+ *     w_pq = ((h[dx] h[dy]) N_pq) exp(-D_pq - L_pq),   h = (1/16, 1/4, 3/8, 1/4, 1/16),
+ *            N_pq = max(0, (n^_p.x n^_q.x + n^_p.y n^_q.y) + n^_p.z n^_q.z)^128 by seven squarings, 1 at the centre tap,
+ *            L_pq = |lum(e_q) - lum(e_p)| / (sigma_l sqrt(g_p) + 1e-10),
+ *            D_pq = max(0, t_pq) / sigma_p (t_pq > 0 ? t_pq : 0: a NaN counts as 0), 0 at the centre tap,
+ *            t_pq = r_pq / ((h_p s) len) - 1, r_pq = sqrt((x x + y y) + z z) of (x, y, z) = p_q - p_p, len = sqrt(double(dx dx + dy dy)).
+ *            D is the excess of the world distance over what a continuous, isotropic chart gives at that tap: 0 inside a well-behaved
+ *            chart, growing with stretch, enormous across an atlas seam -- which is what keeps unrelated charts apart.
+ *     e'_p = (sum w_pq e_q) / sum w_pq per channel,  v'_p = (sum (w_pq w_pq) v_q) / (sum w_pq * sum w_pq).
+ *   output   : a covered texel gets e after K iterations (K = 0: its input, bit for bit), every other texel +0.0.  Then R rounds of
+ *              mcpt_bake_lightmap's dilation run on out3, word for word: valid means covered, filled texels read -1 - r in owner.
+ * Defaults: MCPT_LIGHTMAP_DENOISE_ITERATIONS for the Python face (the C struct's K is taken as given), sigma_l =
+ * MCPT_LIGHTMAP_DENOISE_SIGMA_L, sigma_p = MCPT_LIGHTMAP_DENOISE_SIGMA_P.  Every output is one GPU lane's fixed-order sum: the same bits
+ * on any MI355X, on every call.
+ * The host form is synchronous.  The _device form takes device pointers throughout, enqueues on `stream` and DOES NOT WAIT FOR ANYTHING
+ * it enqueues: it runs map-wide and needs no texel count back.  Like a bake, a call first waits for the event behind the device's previous
+ * bake or denoise, and it keeps its workspace in the device: about 128 bytes per texel of the largest map so far (a 64-byte guide record
+ * and two 32-byte (e, v) records), beside the baker's 4 bytes per texel and 8 per face, and with dilation 28 more per texel.  A map for
+ * which that cannot be allocated returns MCPT_ERR_NOMEM and leaves the device usable.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE, in this order): NULL parameters, a size outside 1 .. 16384, iterations outside 0 .. 10,
+ * dilate outside 0 .. 64, a sigma that is negative or not finite, reserved != 0, NULL irradiance3, stderr3 or out3.  In the host form a
+ * chart component that is not finite is refused where mcpt_bake_lightmap refuses it; the call meets a motion as a bake does.
+ * Not covered: stitching across seams (filtering between charts that are adjacent in the world but apart in the atlas); temporal or
+ * multi-bake accumulation; a denoise option inside mcpt_bake_lightmap*; SH or directional lightmaps; the multi-device group and
+ * render_scene; the use of a lightmap in shading. */
+#define MCPT_LIGHTMAP_DENOISE_ITERATIONS      5
+#define MCPT_LIGHTMAP_DENOISE_MAX_ITERATIONS  10
+#define MCPT_LIGHTMAP_DENOISE_SIGMA_L         2.0
+#define MCPT_LIGHTMAP_DENOISE_SIGMA_P         1.0
+typedef struct { int32_t width, height, iterations, dilate;
+                 double sigma_l, sigma_p;          /* 0 = the default */
+                 int32_t reserved[2]; } mcpt_lightmap_denoise_params;
+int mcpt_lightmap_denoise(mcpt_device*, const double* uv6, const mcpt_lightmap_denoise_params*,
+                          const double* irradiance3, const double* stderr3, double* out3, int32_t* owner);
+int mcpt_lightmap_denoise_device(mcpt_device*, const double* d_uv6, const mcpt_lightmap_denoise_params*,
+                                 const double* d_irradiance3, const double* d_stderr3, double* d_out3, int32_t* d_owner,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

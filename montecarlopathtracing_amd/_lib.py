@@ -171,6 +171,12 @@ class LightmapParams(C.Structure):
                 ("flags", C.c_int32), ("dilate", C.c_int32), ("reserved", C.c_int32 * 2)]
 
 
+class LightmapDenoiseParams(C.Structure):
+    """mcpt_lightmap_denoise_params: the map's size, the filter's iterations, the dilation rounds and the two sigmas (0: the default)"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("dilate", C.c_int32),
+                ("sigma_l", C.c_double), ("sigma_p", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -209,6 +215,7 @@ EXPORTS = [
     "mcpt_lightmap_raster_host", "mcpt_lightmap_texels", "mcpt_bake_lightmap", "mcpt_bake_lightmap_device",
     "mcpt_query_pass_boundaries", "mcpt_query_radiance_adaptive", "mcpt_query_radiance_adaptive_device",
     "mcpt_bake_lightmap_adaptive", "mcpt_bake_lightmap_adaptive_device",
+    "mcpt_lightmap_denoise", "mcpt_lightmap_denoise_device",
 ]
 
 
@@ -400,6 +407,9 @@ def lib():
     L.mcpt_query_radiance_adaptive_device.argtypes = [P, P, P, C.c_int64, QP, AP, P, P, P, P, C.POINTER(Stats), P]
     L.mcpt_bake_lightmap_adaptive.argtypes = [P, D, LP, AP, D, D, I32, I32, I32, C.POINTER(Stats)]
     L.mcpt_bake_lightmap_adaptive_device.argtypes = [P, P, LP, AP, P, P, P, P, P, C.POINTER(Stats), P]
+    LDP = C.POINTER(LightmapDenoiseParams)
+    L.mcpt_lightmap_denoise.argtypes = [P, D, LDP, D, D, D, I32]
+    L.mcpt_lightmap_denoise_device.argtypes = [P, P, LDP, P, P, P, P, P]
     _lib = L
     return L
 

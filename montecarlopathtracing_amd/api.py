@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -25,6 +25,9 @@ GATHER_PEER, GATHER_RCCL = 0, 1
 LENS_JITTER, LENS_PER_SAMPLE = 1, 2
 QUERY_RAY, QUERY_HEMISPHERE = 0, 1
 _QUERY_KINDS = {"ray": QUERY_RAY, "hemisphere": QUERY_HEMISPHERE}
+# mcpt.h: MCPT_LIGHTMAP_DENOISE_*
+LIGHTMAP_DENOISE_ITERATIONS, LIGHTMAP_DENOISE_MAX_ITERATIONS = 5, 10
+LIGHTMAP_DENOISE_SIGMA_L, LIGHTMAP_DENOISE_SIGMA_P = 2.0, 1.0
 
 
 def _p(a, t):
@@ -794,6 +797,29 @@ class Device:
                                                 _p(hits, C.c_int32), _p(owner, C.c_int32), _p(counts, C.c_int32),
                                                 C.byref(stats) if stats is not None else None))
         return E, err, hits, owner, counts
+
+    def denoise_lightmap(self, E, E_stderr, uv=None, iterations=LIGHTMAP_DENOISE_ITERATIONS, sigma_l=0.0, sigma_p=0.0, dilate=0):
+        """A lightmap denoised (mcpt_lightmap_denoise): an edge-avoiding a-trous filter in UV space over the texels the chart covers -- uv
+        (num_faces, 6), or None for the scene's own vt -- guided by every texel's world position, normal and footprint and by E_stderr;
+        the size is E's, [height, width, 3].  iterations 0 .. 10 (0: no filtering), a sigma of 0 is its default, dilate rounds fill the
+        gutters afterwards.  Returns (E_denoised [height, width, 3], owner [height, width]).  The result is biased towards the neighbours'
+        values; a map whose E_stderr is 0 (spp = 1) comes back essentially unfiltered.  Bake the map passed here with dilate=0: the
+        denoiser dilates after it filters, from the filtered texels, and never reads a texel that is not covered -- values an earlier
+        dilation put there would only be overwritten."""
+        E = np.ascontiguousarray(E, dtype=np.float64)
+        E_stderr = np.ascontiguousarray(E_stderr, dtype=np.float64)
+        if E.ndim != 3 or E.shape[2] != 3 or E_stderr.shape != E.shape:
+            raise ValueError("E and E_stderr must both have shape (height, width, 3), not %r and %r" % (E.shape, E_stderr.shape))
+        for name, v in (("iterations", iterations), ("dilate", dilate)):
+            if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError("%s must be a 32-bit integer" % name)
+        height, width = E.shape[:2]
+        uv = _chart(uv, self.scene.info.num_faces) if uv is not None else None
+        out, owner = np.zeros((height, width, 3)), np.zeros((height, width), dtype=np.int32)
+        dp = LightmapDenoiseParams(width, height, int(iterations), int(dilate), float(sigma_l), float(sigma_p), (C.c_int32 * 2)(0, 0))
+        check(lib().mcpt_lightmap_denoise(self._h, _p(uv, C.c_double), C.byref(dp), _p(E, C.c_double), _p(E_stderr, C.c_double),
+                                          _p(out, C.c_double), _p(owner, C.c_int32)))
+        return out, owner
 
     def set_environment(self, rgb=None, scale=1.0):
         """The environment light of every later frame, sample_radiance and progressive handle created after it (mcpt_device_set_environment):

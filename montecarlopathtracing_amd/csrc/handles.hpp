@@ -11,6 +11,7 @@
 //   display_api.cpp   the display transform: histogram, exposure, the map to 8-bit pixels on the GPU and on the host
 //   lightmap_api.cpp  lightmap baking: a UV chart's coverage, its texel list, the hemisphere query of that list, scatter and dilation
 //   adaptive_query_api.cpp  adaptive queries: the query call in passes, every query stopping on its own error estimate
+//   lightmap_denoise_api.cpp  the lightmap denoiser: a chart-aware a-trous filter of an irradiance map, then the baker's dilation
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -200,6 +201,9 @@ struct mcpt_device {
         mcpt::DevBuf<double> irr;                       // the dilation's second frame
         mcpt::HostBuf<int32_t> h_total;                 // pinned word the covered count lands in
         mcpt::Event done;
+        // the denoiser (lightmap_denoise_api.cpp) shares owner[], irr and `done` with the bakes and keeps, per texel of the largest map it
+        // has seen, a 64-byte guide record and two 32-byte (e, v) records: 128 bytes
+        mcpt::DevBuf<char> dn_guide, dn_buf[2];
     };
     std::unique_ptr<Lightmap> lm;
     // adaptive queries (adaptive_query_api.cpp): what a call keeps between its passes, made by the first one and grown to the longest
@@ -305,6 +309,17 @@ int query_device(mcpt_device* d, const mcpt::DQuery& q, const int32_t* d_ids, in
 // the refusals of mcpt_query_radiance's two forms, shared with the adaptive call (adaptive_query_api.cpp): the parameters, and the list itself
 int query_params_check(const mcpt_query_params* p, int64_t n, const void* q6, const void* mean3);
 int query_list_check(const double* q6, const int32_t* ids, int64_t n, int32_t kind);
+
+// ---- lightmap_api.cpp
+namespace mcpt { struct LightmapWork; }
+int lightmap_size_check(int32_t width, int32_t height);             // MCPT_ERR_ARG: a size outside 1 .. 16384
+int lightmap_chart_check(const double* uv6, int64_t num_faces);     // MCPT_ERR_ARG: a chart component that is not finite
+// what every lightmap call on a device does before it reads the device's triangles: the device itself, key 0 of a motion, a geometry that stands
+int lightmap_device_gate(mcpt_device* d);
+// the baker's workspace of a W x H map on d (d->lm), once the bake or denoise before this one has left it
+int lightmap_ensure_work(mcpt_device* d, int W, int H, mcpt::LightmapWork& w);
+// a chart of the caller's on the device (null stays null: the scene's own vt)
+int lightmap_upload_chart(const mcpt_device* d, const double* uv6, mcpt::DevBuf<double>& d_uv);
 
 // ---- adaptive_query_api.cpp
 // what the adaptive calls refuse of their adaptive parameters (MCPT_ERR_ARG)

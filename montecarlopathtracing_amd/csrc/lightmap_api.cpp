@@ -13,14 +13,14 @@
 
 using namespace mcpt;
 
-static int size_check(int32_t width, int32_t height)
+int lightmap_size_check(int32_t width, int32_t height)
 {
     return width >= 1 && width <= kLightmapMaxSize && height >= 1 && height <= kLightmapMaxSize
                ? MCPT_OK
                : fail(MCPT_ERR_ARG, "a lightmap's width and height must be in 1 .. 16384");
 }
 
-static int chart_check(const double* uv6, int64_t num_faces)
+int lightmap_chart_check(const double* uv6, int64_t num_faces)
 {
     for (int64_t i = 0; i < num_faces * 6; i++)
         if (!std::isfinite(uv6[i])) return fail(MCPT_ERR_ARG, "chart of face " + std::to_string(i / 6) + ": component that is not finite");
@@ -31,7 +31,7 @@ static int chart_check(const double* uv6, int64_t num_faces)
 static int params_check(const mcpt_lightmap_params* p, const void* irradiance3)
 {
     if (!p) return fail(MCPT_ERR_ARG, "null lightmap parameters");
-    if (const int rc = size_check(p->width, p->height)) return rc;
+    if (const int rc = lightmap_size_check(p->width, p->height)) return rc;
     if (const int rc = range_check(p->spp, p->sample_base, int64_t(p->width) * p->height)) return rc;
     if (const int rc = flags_check(p->flags)) return rc;
     if (p->dilate < 0 || p->dilate > kLightmapMaxDilate) return fail(MCPT_ERR_ARG, "dilate must be in 0 .. 64");
@@ -41,7 +41,7 @@ static int params_check(const mcpt_lightmap_params* p, const void* irradiance3)
 }
 
 // what every call on a device does before it reads the device's triangles: the device itself, key 0 of a motion, a geometry that stands
-static int device_gate(mcpt_device* d)
+int lightmap_device_gate(mcpt_device* d)
 {
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
@@ -51,7 +51,7 @@ static int device_gate(mcpt_device* d)
 }
 
 // the workspace of a W x H map on d, once the bake before this one has left it
-static int ensure_work(mcpt_device* d, int W, int H, LightmapWork& w)
+int lightmap_ensure_work(mcpt_device* d, int W, int H, LightmapWork& w)
 {
     if (!d->lm) {
         d->lm = std::make_unique<mcpt_device::Lightmap>();
@@ -90,12 +90,12 @@ static int raster_device(mcpt_device* d, const double* d_uv6, int W, int H, cons
 static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_params& p, const mcpt_adaptive_params* ap, double* d_irr, double* d_err,
                        int32_t* d_hits, int32_t* d_owner, int32_t* d_counts, mcpt_stats* stats, hipStream_t st)
 {
-    if (const int rc = device_gate(d)) return rc;
+    if (const int rc = lightmap_device_gate(d)) return rc;
     if (stats) std::memset(stats, 0, sizeof *stats);
     const int W = p.width, H = p.height, R = p.dilate;
     const size_t n = size_t(W) * H;
     LightmapWork w{};
-    if (const int rc = ensure_work(d, W, H, w)) return rc;
+    if (const int rc = lightmap_ensure_work(d, W, H, w)) return rc;
     mcpt_device::Lightmap& m = *d->lm;
     if (R > 0) {
         HIP_TRY(m.owner[1].grow(n));
@@ -142,7 +142,7 @@ static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_
 }
 
 // a chart of the caller's on the device (null stays null: the scene's own vt)
-static int upload_chart(const mcpt_device* d, const double* uv6, DevBuf<double>& d_uv)
+int lightmap_upload_chart(const mcpt_device* d, const double* uv6, DevBuf<double>& d_uv)
 {
     if (!uv6) return MCPT_OK;
     const size_t c = size_t(d->ds.t) * 6;
@@ -156,9 +156,9 @@ extern "C" {
 int mcpt_lightmap_raster_host(const double* uv6, int64_t num_faces, int32_t width, int32_t height, int32_t* owner)
 {
     if (num_faces < 0 || num_faces > 0x7ffffffe) return fail(MCPT_ERR_ARG, "the number of faces must be in 0 .. 2^31 - 2");
-    if (const int rc = size_check(width, height)) return rc;
+    if (const int rc = lightmap_size_check(width, height)) return rc;
     if (!owner || (num_faces > 0 && !uv6)) return fail(MCPT_ERR_ARG, "null argument");
-    if (const int rc = chart_check(uv6, num_faces)) return rc;
+    if (const int rc = lightmap_chart_check(uv6, num_faces)) return rc;
     const size_t n = size_t(width) * height;
     for (size_t i = 0; i < n; i++) owner[i] = -1;
     // faces in descending order, so that the lowest face that covers a texel is the last to write it
@@ -182,18 +182,18 @@ int mcpt_lightmap_raster_host(const double* uv6, int64_t num_faces, int32_t widt
 
 int64_t mcpt_lightmap_texels(mcpt_device* d, const double* uv6, int32_t width, int32_t height, int32_t* owner, int32_t* texels, double* q6, int64_t cap)
 {
-    if (const int rc = size_check(width, height)) return rc;
+    if (const int rc = lightmap_size_check(width, height)) return rc;
     if (cap < 0) return fail(MCPT_ERR_ARG, "cap must be >= 0");
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
     if (uv6)
-        if (const int rc = chart_check(uv6, d->ds.t)) return rc;
-    if (const int rc = device_gate(d)) return rc;
+        if (const int rc = lightmap_chart_check(uv6, d->ds.t)) return rc;
+    if (const int rc = lightmap_device_gate(d)) return rc;
     DevBuf<double> d_uv, d_q6;
     DevBuf<int32_t> d_texels;
-    if (const int rc = upload_chart(d, uv6, d_uv)) return rc;
+    if (const int rc = lightmap_upload_chart(d, uv6, d_uv)) return rc;
     LightmapWork w{};
-    if (const int rc = ensure_work(d, width, height, w)) return rc;
+    if (const int rc = lightmap_ensure_work(d, width, height, w)) return rc;
     hipStream_t st = d->stream.get();
     int32_t covered = 0;
     if (const int rc = raster_device(d, d_uv.get(), width, height, w, st, covered)) return rc;
@@ -230,12 +230,12 @@ static int bake_host(mcpt_device* d, const double* uv6, const mcpt_lightmap_para
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
     if (uv6)
-        if (const int rc = chart_check(uv6, d->ds.t)) return rc;
+        if (const int rc = lightmap_chart_check(uv6, d->ds.t)) return rc;
     HIP_TRY(hipSetDevice(d->ordinal));
     const size_t n = size_t(p->width) * p->height;
     DevBuf<double> d_uv, d_irr, d_err;
     DevBuf<int32_t> d_hits, d_owner, d_counts;
-    if (const int rc = upload_chart(d, uv6, d_uv)) return rc;
+    if (const int rc = lightmap_upload_chart(d, uv6, d_uv)) return rc;
     HIP_TRY(d_irr.alloc(n * 3));
     if (counts) HIP_TRY(d_counts.alloc(n));
     if (stderr3) HIP_TRY(d_err.alloc(n * 3));
