@@ -960,7 +960,8 @@ int mcpt_query_rays(mcpt_device*, const double* q6, const int32_t* ids, int64_t 
  * form takes device pointers throughout (p3 as n*3 device doubles), enqueues on `stream` and returns without waiting when stats == NULL.
  * The host helpers need no device; they refuse a NULL pointer, n < 0, a component that is not finite and, mcpt_sh_irradiance, a normal of
  * zero, underflowing or overflowing length.
- * Not covered: the multi-device group, render_scene, interpolation between the probes of a grid, bands above 2, adaptive stopping. */
+ * Not covered: the multi-device group, render_scene, interpolation between the probes of a grid (that is the irradiance volumes' block
+ * below), bands above 2, adaptive stopping. */
 typedef struct { int32_t spp, sample_base; uint64_t seed; int32_t flags, reserved[3]; } mcpt_sh_params;
 int mcpt_query_sh(mcpt_device*, const double* p3, const int32_t* ids, int64_t n, const mcpt_sh_params*,
                   double* sh27, double* stderr27, int32_t* hits, mcpt_stats*);
@@ -1158,6 +1159,65 @@ int mcpt_lightmap_denoise(mcpt_device*, const double* uv6, const mcpt_lightmap_d
 int mcpt_lightmap_denoise_device(mcpt_device*, const double* d_uv6, const mcpt_lightmap_denoise_params*,
                                  const double* d_irradiance3, const double* d_stderr3, double* d_out3, int32_t* d_owner,
                                  void* stream);
+
+/* ---- irradiance volumes (since the volume change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* AN IRRADIANCE VOLUME is a regular grid of light probes and a lookup that answers "the irradiance at this point for this normal" by
+ * blending the eight probes around the point trilinearly and evaluating the blend as mcpt_sh_irradiance evaluates one probe.  It lights
+ * moving objects and surfaces without a chart, and it is a cheap stand-in for a lightmap.  fp64, no contraction, IEEE division, every
+ * sum in the order written.
+ *   grid     : nx * ny * nz probes.  Probe (ix, iy, iz) has index P = (iz * ny + iy) * nx + ix and, on axis a, the coordinate
+ *              origin[a] + double(i_a) * spacing[a].  A valid grid: origin finite; spacing finite and > 0 on every axis, also where the
+ *              count is 1; every count >= 1 and nx * ny * nz <= 2^31 - 1 (in 64 bits); flags 0 or MCPT_VOLUME_CLAMP_ZERO; reserved 0.
+ *              mcpt_volume_points writes the positions, p3[nprobes * 3], on the host: no device.
+ *   bake     : A BAKE IS, BIT FOR BIT, mcpt_query_sh OVER mcpt_volume_points OF THE GRID WITH ids == NULL: the RNG key id of probe P is
+ *              P; sh27 [nprobes][9][3] is required, stderr27 and hits [nprobes] may be NULL; stats->rays_primary = samples = nprobes *
+ *              spp.  The positions are written on the GPU into a list the device keeps (24 bytes per probe of the largest grid so far);
+ *              keys, shading, sample ranges, flags, chunking, concurrency and the motion rule are mcpt_query_sh's, word for word.
+ *   lookup   : receiver r is q6[r] = position x, normal b of any non-zero finite length -- the hemisphere query's list format, so
+ *              mcpt_lightmap_texels' q6 goes in unchanged.  Per axis a with n probes:
+ *                g = (x_a - origin_a) / spacing_a, g = g > 0.0 ? g : 0.0, g = g < double(n - 1) ? g : double(n - 1): a point outside
+ *                the grid takes the border's value;
+ *                n == 1: i0 = i1 = 0, f = 0.0;   n >= 2: i0 = min(int(floor(g)), n - 2), i1 = i0 + 1, f = g - double(i0) (1.0 on the
+ *                far border); then THE SNAP: f = 0.0 when x_a == origin_a + double(i0) * spacing_a, else f = 1.0 when x_a == origin_a +
+ *                double(i1) * spacing_a -- a coordinate that is a probe's own, bit for bit, belongs to that probe alone (g does not
+ *                give a probe's index back exactly unless origin and spacing are dyadic: (0.1 + 0.3 - 0.1) / 0.3 is 1 + 2^-52);
+ *                w0 = 1.0 - f, w1 = f.
+ *              Corner j = dz * 4 + dy * 2 + dx, j = 0 .. 7, is probe P_j = (i_dz * ny + i_dy) * nx + i_dx with weight
+ *              w_j = (wx_dx * wy_dy) * wz_dz.
+ *   mask     : valid is NULL or one byte per probe.  With a mask, w_j = 0.0 where valid[P_j] == 0; W = sum_j w_j in j order from 0.0;
+ *              W > 0: w_j = w_j / W; otherwise every output of the receiver is +0.0.  Without a mask nothing is divided.
+ *              corners[r] (may be NULL) = the number of j with w_j > 0 after masking.
+ *   value    : c[i][ch] = sum_j w_j * sh[P_j][i][ch] in j order from 0.0; n^ and A_l as in mcpt_sh_irradiance;
+ *              E_ch = sum_i (A_l(i) * Y_i(n^)) * c[i][ch] in i order from 0.0; under MCPT_VOLUME_CLAMP_ZERO, last,
+ *              E_ch = E_ch > 0.0 ? E_ch : 0.0 (order-2 ringing can go negative).  Hence A RECEIVER EXACTLY ON PROBE P GETS
+ *              mcpt_sh_irradiance(sh[P], b), BIT FOR BIT, with or without a mask that keeps P: weights of exactly 1 and 0 give exact
+ *              sums when the coefficients are finite.  Every output is one lane's fixed-order sum: the same bits on the host and on the GPU.
+ * The lookup takes coefficient arrays, not a bake: accumulated, edited or loaded volumes go through it.  mcpt_volume_irradiance_host runs
+ * on the CPU and needs no device.  The host-pointer forms are synchronous and copy in and out around the device form.  The _device forms
+ * take device pointers throughout and enqueue on `stream`: the bake returns without waiting when stats == NULL, after first waiting for
+ * the event behind the device's previous bake; the lookup never waits and allocates nothing.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE, in this order): a NULL grid or NULL parameters; an invalid grid, in the field order
+ * above; the bake: mcpt_query_sh's refusals in its order; the lookup: n < 0 or n > 2^31 - 1, then NULL sh27, q6 or e3 with n > 0.  The
+ * host-pointer forms of the lookup also refuse a coefficient or a position that is not finite and a normal mcpt_sh_irradiance would
+ * refuse; THE DEVICE FORM DOES NOT LOOK, and its result for such input is unspecified (it still reads no probe outside the grid).
+ * n == 0: MCPT_OK, nothing is launched.  A probe list or a copy that cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable.
+ * Not covered: a standard error of the lookup (the coefficients of one probe share their samples: a sum of squares would be wrong);
+ * finding invalid probes (the query does not report back-face hits: the mask is the caller's); visibility-weighted interpolation;
+ * radiance (glossy) lookup and returning the blended coefficients; adaptive probes; the multi-device group and render_scene; lighting a
+ * frame from the volume. */
+#define MCPT_VOLUME_CLAMP_ZERO 1   /* E_c = max(E_c, 0.0): order-2 ringing can go negative */
+typedef struct { double origin[3], spacing[3]; int32_t nx, ny, nz, flags; int32_t reserved[4]; } mcpt_volume_grid;
+int mcpt_volume_points(const mcpt_volume_grid*, double* p3);
+int mcpt_bake_volume(mcpt_device*, const mcpt_volume_grid*, const mcpt_sh_params*,
+                     double* sh27, double* stderr27, int32_t* hits, mcpt_stats*);
+int mcpt_bake_volume_device(mcpt_device*, const mcpt_volume_grid*, const mcpt_sh_params*,
+                            double* d_sh27, double* d_stderr27, int32_t* d_hits, mcpt_stats*, void* stream);
+int mcpt_volume_irradiance_host(const mcpt_volume_grid*, const double* sh27, const uint8_t* valid,
+                                const double* q6, int64_t n, double* e3, int32_t* corners);
+int mcpt_volume_irradiance(mcpt_device*, const mcpt_volume_grid*, const double* sh27, const uint8_t* valid,
+                           const double* q6, int64_t n, double* e3, int32_t* corners);
+int mcpt_volume_irradiance_device(mcpt_device*, const mcpt_volume_grid*, const double* d_sh27, const uint8_t* d_valid,
+                                  const double* d_q6, int64_t n, double* d_e3, int32_t* d_corners, void* stream);
 
 #ifdef __cplusplus
 }

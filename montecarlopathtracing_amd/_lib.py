@@ -177,6 +177,16 @@ class LightmapDenoiseParams(C.Structure):
                 ("sigma_l", C.c_double), ("sigma_p", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
+class VolumeGrid(C.Structure):
+    """mcpt_volume_grid: origin, spacing and probe counts of an irradiance volume's grid, and its flags (api.volume_grid makes one)"""
+    _fields_ = [("origin", C.c_double * 3), ("spacing", C.c_double * 3), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32 * 4)]
+
+    @property
+    def num_probes(self):
+        return self.nx * self.ny * self.nz
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -216,6 +226,8 @@ EXPORTS = [
     "mcpt_query_pass_boundaries", "mcpt_query_radiance_adaptive", "mcpt_query_radiance_adaptive_device",
     "mcpt_bake_lightmap_adaptive", "mcpt_bake_lightmap_adaptive_device",
     "mcpt_lightmap_denoise", "mcpt_lightmap_denoise_device",
+    "mcpt_volume_points", "mcpt_bake_volume", "mcpt_bake_volume_device",
+    "mcpt_volume_irradiance_host", "mcpt_volume_irradiance", "mcpt_volume_irradiance_device",
 ]
 
 
@@ -410,6 +422,13 @@ def lib():
     LDP = C.POINTER(LightmapDenoiseParams)
     L.mcpt_lightmap_denoise.argtypes = [P, D, LDP, D, D, D, I32]
     L.mcpt_lightmap_denoise_device.argtypes = [P, P, LDP, P, P, P, P, P]
+    VG = C.POINTER(VolumeGrid)
+    L.mcpt_volume_points.argtypes = [VG, D]
+    L.mcpt_bake_volume.argtypes = [P, VG, SP, D, D, I32, C.POINTER(Stats)]
+    L.mcpt_bake_volume_device.argtypes = [P, VG, SP, P, P, P, C.POINTER(Stats), P]
+    L.mcpt_volume_irradiance_host.argtypes = [VG, D, U8, D, C.c_int64, D, I32]
+    L.mcpt_volume_irradiance.argtypes = [P, VG, D, U8, D, C.c_int64, D, I32]
+    L.mcpt_volume_irradiance_device.argtypes = [P, VG, P, P, P, C.c_int64, P, P, P]
     _lib = L
     return L
 

@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -28,6 +28,7 @@ _QUERY_KINDS = {"ray": QUERY_RAY, "hemisphere": QUERY_HEMISPHERE}
 # mcpt.h: MCPT_LIGHTMAP_DENOISE_*
 LIGHTMAP_DENOISE_ITERATIONS, LIGHTMAP_DENOISE_MAX_ITERATIONS = 5, 10
 LIGHTMAP_DENOISE_SIGMA_L, LIGHTMAP_DENOISE_SIGMA_P = 2.0, 1.0
+VOLUME_CLAMP_ZERO = 1
 
 
 def _p(a, t):
@@ -139,6 +140,68 @@ def sh_irradiance(sh, normals):
     e = np.zeros((nrm.shape[0], 3))
     check(lib().mcpt_sh_irradiance(_p(sh, C.c_double), _p(nrm, C.c_double), nrm.shape[0], _p(e, C.c_double)))
     return e
+
+
+def volume_grid(origin, spacing, counts, clamp_zero=False):
+    """An mcpt_volume_grid (mcpt.h: irradiance volumes): probe (ix, iy, iz) sits at origin + (ix, iy, iz) * spacing; counts = (nx, ny, nz);
+    spacing is a triple or one number for all axes; clamp_zero: the lookup returns max(E, 0).  The library judges the values."""
+    origin = np.asarray(origin, dtype=np.float64).reshape(-1)
+    spacing = np.asarray(spacing, dtype=np.float64).reshape(-1)
+    if spacing.shape[0] == 1:
+        spacing = np.repeat(spacing, 3)
+    counts = tuple(counts)
+    if origin.shape[0] != 3 or spacing.shape[0] != 3 or len(counts) != 3:
+        raise ValueError("origin, spacing and counts are triples")
+    for v in counts:
+        if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("counts must be 32-bit integers")
+    return VolumeGrid((C.c_double * 3)(*origin), (C.c_double * 3)(*spacing), int(counts[0]), int(counts[1]), int(counts[2]),
+                      VOLUME_CLAMP_ZERO if clamp_zero else 0, (C.c_int32 * 4)(0, 0, 0, 0))
+
+
+def _grid_probes(grid):
+    """the number of probes the arrays of `grid` must hold (0 for counts the library will refuse)"""
+    if not isinstance(grid, VolumeGrid):
+        raise ValueError("grid must be a VolumeGrid (volume_grid makes one)")
+    n = max(grid.nx, 0) * max(grid.ny, 0) * max(grid.nz, 0)
+    return n if n < 2 ** 31 else 0
+
+
+def volume_points(grid):
+    """The probe positions of a grid (mcpt_volume_points; no device): (nz * ny * nx, 3), probe (ix, iy, iz) at row (iz * ny + iy) * nx + ix"""
+    p = np.zeros((_grid_probes(grid), 3))
+    check(lib().mcpt_volume_points(C.byref(grid), _p(p, C.c_double)))
+    return p
+
+
+def _volume_args(grid, sh, points, normals, valid):
+    probes = _grid_probes(grid)
+    sh = np.ascontiguousarray(sh, dtype=np.float64)
+    if sh.shape[-2:] != (9, 3) or sh.size != probes * 27:
+        raise ValueError("sh must hold (9, 3) coefficients for each of the grid's %d probes, not %r" % (probes, sh.shape))
+    points = np.asarray(points, dtype=np.float64)
+    normals = np.asarray(normals, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+        raise ValueError("points and normals must both have shape (n, 3)")
+    if valid is not None:
+        valid = np.ascontiguousarray(valid)
+        if valid.dtype.kind not in "biu" or valid.size != probes:
+            raise ValueError("valid must hold one flag for each of the grid's %d probes" % probes)
+        valid = np.ascontiguousarray(valid != 0, dtype=np.uint8)
+    return sh, np.ascontiguousarray(np.concatenate([points, normals], axis=1)), valid
+
+
+def volume_irradiance_host(grid, sh, points, normals, valid=None):
+    """The irradiance volume's lookup on the CPU (mcpt_volume_irradiance_host; no device): sh [nz, ny, nx, 9, 3] (or [nprobes, 9, 3]) the
+    probes' coefficients, receiver i at points[i] with normal normals[i] of any non-zero length, valid one flag per probe or None.
+    Returns (E [n, 3], corners [n]): the trilinear blend of the eight probes around each point under the cosine lobe of its normal, and
+    how many of the eight took part."""
+    sh, q, valid = _volume_args(grid, sh, points, normals, valid)
+    n = q.shape[0]
+    E, corners = np.zeros((n, 3)), np.zeros(n, dtype=np.int32)
+    check(lib().mcpt_volume_irradiance_host(C.byref(grid), _p(sh, C.c_double), _p(valid, C.c_uint8), _p(q, C.c_double), n, _p(E, C.c_double),
+                                            _p(corners, C.c_int32)))
+    return E, corners
 
 
 def _adaptive_params(rel_target, abs_target, min_spp):
@@ -820,6 +883,30 @@ class Device:
         check(lib().mcpt_lightmap_denoise(self._h, _p(uv, C.c_double), C.byref(dp), _p(E, C.c_double), _p(E_stderr, C.c_double),
                                           _p(out, C.c_double), _p(owner, C.c_int32)))
         return out, owner
+
+    def bake_volume(self, grid, spp, seed=0, sample_base=0, flags=0, stats=None):
+        """An irradiance volume (mcpt_bake_volume): sh_probes() of volume_points(grid), bit for bit, with the positions made on the GPU;
+        probe P's RNG key id is P.  Returns (sh [nz, ny, nx, 9, 3], stderr [nz, ny, nx, 9, 3], hits [nz, ny, nx]); volume_irradiance
+        looks the coefficients up."""
+        for name, v in (("spp", spp), ("sample_base", sample_base), ("flags", flags)):
+            if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+                raise ValueError("%s must be a 32-bit integer" % name)
+        shape = (max(grid.nz, 0), max(grid.ny, 0), max(grid.nx, 0)) if _grid_probes(grid) else (0, 0, 0)
+        sh, err, hits = np.zeros(shape + (9, 3)), np.zeros(shape + (9, 3)), np.zeros(shape, dtype=np.int32)
+        sp = ShParams(int(spp), int(sample_base), int(seed), int(flags), (C.c_int32 * 3)(0, 0, 0))
+        check(lib().mcpt_bake_volume(self._h, C.byref(grid), C.byref(sp), _p(sh, C.c_double), _p(err, C.c_double), _p(hits, C.c_int32),
+                                     C.byref(stats) if stats is not None else None))
+        return sh, err, hits
+
+    def volume_irradiance(self, grid, sh, points, normals, valid=None):
+        """The irradiance volume's lookup on the GPU (mcpt_volume_irradiance): volume_irradiance_host's arguments and answers, bit for
+        bit.  Returns (E [n, 3], corners [n])."""
+        sh, q, valid = _volume_args(grid, sh, points, normals, valid)
+        n = q.shape[0]
+        E, corners = np.zeros((n, 3)), np.zeros(n, dtype=np.int32)
+        check(lib().mcpt_volume_irradiance(self._h, C.byref(grid), _p(sh, C.c_double), _p(valid, C.c_uint8), _p(q, C.c_double), n,
+                                           _p(E, C.c_double), _p(corners, C.c_int32)))
+        return E, corners
 
     def set_environment(self, rgb=None, scale=1.0):
         """The environment light of every later frame, sample_radiance and progressive handle created after it (mcpt_device_set_environment):

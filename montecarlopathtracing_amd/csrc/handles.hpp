@@ -12,6 +12,7 @@
 //   lightmap_api.cpp  lightmap baking: a UV chart's coverage, its texel list, the hemisphere query of that list, scatter and dilation
 //   adaptive_query_api.cpp  adaptive queries: the query call in passes, every query stopping on its own error estimate
 //   lightmap_denoise_api.cpp  the lightmap denoiser: a chart-aware a-trous filter of an irradiance map, then the baker's dilation
+//   volume_api.cpp    irradiance volumes: a probe grid's points, its bake through the probe query, the lookup between its probes
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -222,6 +223,14 @@ struct mcpt_device {
         mcpt::Event done;
     };
     std::unique_ptr<AdaptiveQuery> aq;
+    // irradiance volumes (volume_api.cpp): the positions of the grid a bake answers, made by the first bake and grown to the largest grid
+    // so far.  A device-form bake returns with its query enqueued, so the list is not a local of the call; `done` is recorded behind a
+    // bake's last kernel and waited for before the next one writes here.
+    struct Volume {
+        mcpt::DevBuf<double> p3;                        // [nprobes][3]
+        mcpt::Event done;
+    };
+    std::unique_ptr<Volume> vol;
 };
 
 // The helpers below are the library's own: none of them is exported from libmcpt.so.
@@ -309,6 +318,8 @@ int query_device(mcpt_device* d, const mcpt::DQuery& q, const int32_t* d_ids, in
 // the refusals of mcpt_query_radiance's two forms, shared with the adaptive call (adaptive_query_api.cpp): the parameters, and the list itself
 int query_params_check(const mcpt_query_params* p, int64_t n, const void* q6, const void* mean3);
 int query_list_check(const double* q6, const int32_t* ids, int64_t n, int32_t kind);
+// the refusals of mcpt_query_sh's two forms, shared with the volume bake (volume_api.cpp)
+int sh_params_check(const mcpt_sh_params* p, int64_t n, const void* p3, const void* sh27);
 
 // ---- lightmap_api.cpp
 namespace mcpt { struct LightmapWork; }

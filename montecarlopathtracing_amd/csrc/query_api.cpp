@@ -49,7 +49,7 @@ int query_params_check(const mcpt_query_params* p, int64_t n, const void* q6, co
     return MCPT_OK;
 }
 // ... and both forms of mcpt_query_sh
-static int sh_params_check(const mcpt_sh_params* p, int64_t n, const void* p3, const void* sh27)
+int sh_params_check(const mcpt_sh_params* p, int64_t n, const void* p3, const void* sh27)
 {
     if (!p) return fail(MCPT_ERR_ARG, "null probe parameters");
     if (const int rc = range_check(p->spp, p->sample_base, n)) return rc;
