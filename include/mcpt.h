@@ -1202,8 +1202,8 @@ int mcpt_lightmap_denoise_device(mcpt_device*, const double* d_uv6, const mcpt_l
  * refuse; THE DEVICE FORM DOES NOT LOOK, and its result for such input is unspecified (it still reads no probe outside the grid).
  * n == 0: MCPT_OK, nothing is launched.  A probe list or a copy that cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable.
  * Not covered: a standard error of the lookup (the coefficients of one probe share their samples: a sum of squares would be wrong);
- * finding invalid probes (the query does not report back-face hits: the mask is the caller's); visibility-weighted interpolation;
- * radiance (glossy) lookup and returning the blended coefficients; adaptive probes; the multi-device group and render_scene; lighting a
+ * finding invalid probes and visibility-weighted interpolation here (both are the probe visibility block's below: its bake fills the
+ * mask, its lookup weighs every corner by what the probe sees); radiance (glossy) lookup and returning the blended coefficients; adaptive probes; the multi-device group and render_scene; lighting a
  * frame from the volume. */
 #define MCPT_VOLUME_CLAMP_ZERO 1   /* E_c = max(E_c, 0.0): order-2 ringing can go negative */
 typedef struct { double origin[3], spacing[3]; int32_t nx, ny, nz, flags; int32_t reserved[4]; } mcpt_volume_grid;
@@ -1218,6 +1218,89 @@ int mcpt_volume_irradiance(mcpt_device*, const mcpt_volume_grid*, const double* 
                            const double* q6, int64_t n, double* e3, int32_t* corners);
 int mcpt_volume_irradiance_device(mcpt_device*, const mcpt_volume_grid*, const double* d_sh27, const uint8_t* d_valid,
                                   const double* d_q6, int64_t n, double* d_e3, int32_t* d_corners, void* stream);
+
+/* ---- probe visibility (since the visibility change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* PROBE VISIBILITY is what a probe sees of its surroundings: per probe an R x R octahedral map of the mean and mean square of the distance
+ * to the nearest surface, and the number of its rays that hit a surface from behind.  The second finds the probes that sit inside
+ * geometry (the mask of the irradiance volumes' lookup); the first lets a lookup take away the weight of a probe that cannot see the
+ * receiver, so that light no longer leaks through walls.  fp64, no contraction, IEEE division, every expression and sum in the order
+ * written.
+ *   bin      : mcpt_visibility_bin, bin[i] of direction d3[i] = (x, y, z) in a map of res = R in 1 .. 16 (host, no device):
+ *                l = (|x| + |y|) + |z|, u = x / l, v = y / l;
+ *                z < 0.0: (u, v) = ((1.0 - |v|) * (u >= 0.0 ? 1.0 : -1.0), (1.0 - |u|) * (v >= 0.0 ? 1.0 : -1.0)), from the old u and v;
+ *                bx = int(floor((u * 0.5 + 0.5) * double(R))) clamped to 0 .. R - 1, by likewise from v; bin = by * R + bx.
+ *              The helper refuses a direction that is not finite or whose l is 0 or overflows; the kernels put such a direction into
+ *              bin 0 and never outside the table.
+ *   rays     : sample j of probe i is the ray mcpt_query_sh gives it: the sphere draw of (seed, ids[i] or i, sample_base + j) from the
+ *              point itself.  A PROBE'S VISIBILITY RAYS ARE ITS RADIANCE RAYS, BIT FOR BIT, for the same seed, id and sample range.
+ *   trace    : the closest hit mcpt_trace_closest_device answers (the device's trace mode and engine, key 0 of a motion, a geometry
+ *              that stands), through the same walks; the rays are drawn on the GPU into a workspace the device keeps.
+ *   fold     : per probe, in j order, with d the ray's direction, t the hit's distance and n the hit triangle's stored face normal
+ *              (mcpt_scene_get_faces: geom27[24..26]):
+ *                hit = the ray hit anything; hits += hit; back += hit && ((d.x n.x + d.y n.y) + d.z n.z) > 0.0;
+ *                r = hit ? (t < max_distance ? t : max_distance) : max_distance;
+ *                b = bin(d, R); c[b] += 1, s1[b] += r, s2[b] += r * r.
+ *              The stored normal is normalize(cross(v1 - v2, v3 - v1)) of the face's vertices, the library's rule everywhere: `back`
+ *              means what it says in a scene whose faces wind so that this normal points into free space.  A scene wound the other way
+ *              (cornell-box is) reports every hit as a back-face hit: its caller takes the mask from hits - back instead.
+ *   outputs  : moments[i][b] = (s1 / c, s2 / c), [n][R * R][2]; a bin with c == 0 holds (-1.0, 0.0): "no data".  hits[i], back[i];
+ *              valid[i] = double(back) <= max_back_fraction * double(spp) ? 1 : 0.  moments is required; hits, back and valid may be NULL.
+ *              stats->rays_primary = samples = n * spp, launches = the number of chunks; the other fields are 0.
+ *   chunks   : the call works in chunks of whole probes: at most workspace_rays rays and at least one probe each; 0 selects 4 194 304
+ *              rays.  The workspace holds 84 bytes per ray of the largest chunk so far.  THE RESULT DOES NOT DEPEND ON THE CHUNKING:
+ *              every sum belongs to one probe and is added in j order.
+ *   grid form: A VOLUME VISIBILITY BAKE IS, BIT FOR BIT, mcpt_query_visibility OVER mcpt_volume_points OF THE GRID WITH ids == NULL;
+ *              the points are written on the GPU into the volume's own list.
+ *   lookup   : mcpt_volume_irradiance with one factor per corner.  P_j and the trilinear w_j are that call's, the snap included.
+ *              valid == NULL is a mask of ones; w_j = 0.0 where valid[P_j] == 0.  With n^ the receiver's unit normal (b / sqrt((bx bx
+ *              + by by) + bz bz)), x' = x + n^ * normal_bias per component, (vx, vy, vz) = x' - c_j with c_j the probe's position,
+ *              dist = sqrt((vx vx + vy vy) + vz vz):
+ *                dist == 0.0: f = 1.0.  Otherwise b = bin(v / dist, R), (mu, m2) = moments[P_j][b];
+ *                mu < 0.0: f = 1.0.  Otherwise dc = dist < max_distance ? dist : max_distance;
+ *                dc <= mu: f = 1.0.  Otherwise var = m2 - mu * mu, var = var > 0.0 ? var : 0.0, delta = dc - mu,
+ *                ch = var / (var + delta * delta), f = (ch * ch) * ch                                    (Chebyshev's bound, cubed);
+ *                last, f = f > min_visibility ? f : min_visibility.
+ *              w_j = w_j * f_j; W = sum_j w_j in j order from 0.0; W > 0: w_j = w_j / W, otherwise every output of the receiver is
+ *              +0.0 and corners[r] = 0.  The value and the clamp are mcpt_volume_irradiance's; corners[r] = the number of w_j > 0.
+ *              Hence (a) WITH EVERY FACTOR 1 (moments all (-1, 0)) THE CALL IS mcpt_volume_irradiance UNDER THE SAME MASK (all ones
+ *              where NULL), BIT FOR BIT, and (b) with normal_bias == 0 A RECEIVER EXACTLY ON A VALID PROBE P GETS
+ *              mcpt_sh_irradiance(sh[P], b), BIT FOR BIT.  mcpt_volume_irradiance_visible_host runs on the CPU and needs no device.
+ * The host-pointer forms are synchronous and copy in and out around the device forms.  The _device forms take device pointers throughout
+ * and enqueue on `stream`.  The bakes return without waiting when stats == NULL, after first waiting for the event behind the device's
+ * previous visibility bake (and, the grid form, its previous volume bake); they use the counters and queue words of
+ * mcpt_trace_closest_device and, like it, must not overlap another closest-hit call of the same device on another stream.  The lookup
+ * never waits and allocates nothing; IT DOES NOT LOOK AT ITS ARRAYS and reads no probe or bin outside its tables.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE, in this order).  The bakes: NULL parameters (the grid form: a NULL grid or NULL
+ * parameters, then an invalid grid in its field order); spp < 1; sample_base < 0; sample_base + spp > 2^31 - 1; res outside 1 .. 16;
+ * max_distance not finite or <= 0; max_back_fraction not finite or outside [0, 1]; workspace_rays < 0; reserved0 or reserved != 0;
+ * n < 0 or n > 2^31 - 1; NULL p3 or moments with n > 0; the host-pointer list form: a negative id or a position that is not finite.
+ * The lookups: the grid's errors; a NULL mcpt_volume_visibility; res outside 1 .. 16; flags != 0; max_distance not finite or <= 0;
+ * normal_bias not finite or < 0; min_visibility not finite or outside [0, 1]; reserved != 0; n < 0 or n > 2^31 - 1; NULL sh27, moments,
+ * q6 or e3 with n > 0; the host-pointer forms: mcpt_volume_irradiance's array checks, then a moment that is neither finite with a mean
+ * >= 0 nor exactly (-1.0, 0.0).  mcpt_visibility_bin: n < 0, NULL d3 or bin with n > 0, res outside 1 .. 16, then the directions.
+ * n == 0: MCPT_OK, nothing is launched.  A workspace or a copy that cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable.
+ * Not covered: the normal-facing "wrap" weight and the weight crush of DDGI; a view bias; relocating probes; filtered (lobe-blended)
+ * depth maps; fp32 or fp16 moment storage; a ray source inside the engines (the rays go through a workspace); the multi-device group
+ * and render_scene. */
+typedef struct { int32_t spp, sample_base; uint64_t seed; int32_t res, reserved0;
+                 double max_distance, max_back_fraction; int64_t workspace_rays; int32_t reserved[2]; } mcpt_visibility_params;
+typedef struct { int32_t res, flags; double max_distance, normal_bias, min_visibility; int32_t reserved[4]; } mcpt_volume_visibility;
+int mcpt_visibility_bin(const double* d3, int64_t n, int32_t res, int32_t* bin);
+int mcpt_query_visibility(mcpt_device*, const double* p3, const int32_t* ids, int64_t n, const mcpt_visibility_params*,
+                          double* moments, int32_t* hits, int32_t* back, uint8_t* valid, mcpt_stats*);
+int mcpt_query_visibility_device(mcpt_device*, const double* d_p3, const int32_t* d_ids, int64_t n, const mcpt_visibility_params*,
+                                 double* d_moments, int32_t* d_hits, int32_t* d_back, uint8_t* d_valid, mcpt_stats*, void* stream);
+int mcpt_bake_volume_visibility(mcpt_device*, const mcpt_volume_grid*, const mcpt_visibility_params*,
+                                double* moments, int32_t* hits, int32_t* back, uint8_t* valid, mcpt_stats*);
+int mcpt_bake_volume_visibility_device(mcpt_device*, const mcpt_volume_grid*, const mcpt_visibility_params*,
+                                       double* d_moments, int32_t* d_hits, int32_t* d_back, uint8_t* d_valid, mcpt_stats*, void* stream);
+int mcpt_volume_irradiance_visible_host(const mcpt_volume_grid*, const double* sh27, const double* moments, const uint8_t* valid,
+                                        const mcpt_volume_visibility*, const double* q6, int64_t n, double* e3, int32_t* corners);
+int mcpt_volume_irradiance_visible(mcpt_device*, const mcpt_volume_grid*, const double* sh27, const double* moments, const uint8_t* valid,
+                                   const mcpt_volume_visibility*, const double* q6, int64_t n, double* e3, int32_t* corners);
+int mcpt_volume_irradiance_visible_device(mcpt_device*, const mcpt_volume_grid*, const double* d_sh27, const double* d_moments,
+                                          const uint8_t* d_valid, const mcpt_volume_visibility*, const double* d_q6, int64_t n,
+                                          double* d_e3, int32_t* d_corners, void* stream);
 
 #ifdef __cplusplus
 }

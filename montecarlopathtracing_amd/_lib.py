@@ -187,6 +187,20 @@ class VolumeGrid(C.Structure):
         return self.nx * self.ny * self.nz
 
 
+class VisibilityParams(C.Structure):
+    """mcpt_visibility_params: samples per probe, first sample index, seed, the octahedral map's resolution, the depth clamp, the share of
+    back-face hits a valid probe may have, and the workspace's size in rays (0: the default)"""
+    _fields_ = [("spp", C.c_int32), ("sample_base", C.c_int32), ("seed", C.c_uint64), ("res", C.c_int32), ("reserved0", C.c_int32),
+                ("max_distance", C.c_double), ("max_back_fraction", C.c_double), ("workspace_rays", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
+class VolumeVisibility(C.Structure):
+    """mcpt_volume_visibility: what the visibility-weighted lookup needs of a bake (res, max_distance) and its own knobs (normal_bias,
+    min_visibility); api.volume_visibility makes one"""
+    _fields_ = [("res", C.c_int32), ("flags", C.c_int32), ("max_distance", C.c_double), ("normal_bias", C.c_double),
+                ("min_visibility", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -228,6 +242,9 @@ EXPORTS = [
     "mcpt_lightmap_denoise", "mcpt_lightmap_denoise_device",
     "mcpt_volume_points", "mcpt_bake_volume", "mcpt_bake_volume_device",
     "mcpt_volume_irradiance_host", "mcpt_volume_irradiance", "mcpt_volume_irradiance_device",
+    "mcpt_visibility_bin", "mcpt_query_visibility", "mcpt_query_visibility_device",
+    "mcpt_bake_volume_visibility", "mcpt_bake_volume_visibility_device",
+    "mcpt_volume_irradiance_visible_host", "mcpt_volume_irradiance_visible", "mcpt_volume_irradiance_visible_device",
 ]
 
 
@@ -429,6 +446,15 @@ def lib():
     L.mcpt_volume_irradiance_host.argtypes = [VG, D, U8, D, C.c_int64, D, I32]
     L.mcpt_volume_irradiance.argtypes = [P, VG, D, U8, D, C.c_int64, D, I32]
     L.mcpt_volume_irradiance_device.argtypes = [P, VG, P, P, P, C.c_int64, P, P, P]
+    VP, VV = C.POINTER(VisibilityParams), C.POINTER(VolumeVisibility)
+    L.mcpt_visibility_bin.argtypes = [D, C.c_int64, C.c_int32, I32]
+    L.mcpt_query_visibility.argtypes = [P, D, I32, C.c_int64, VP, D, I32, I32, U8, C.POINTER(Stats)]
+    L.mcpt_query_visibility_device.argtypes = [P, P, P, C.c_int64, VP, P, P, P, P, C.POINTER(Stats), P]
+    L.mcpt_bake_volume_visibility.argtypes = [P, VG, VP, D, I32, I32, U8, C.POINTER(Stats)]
+    L.mcpt_bake_volume_visibility_device.argtypes = [P, VG, VP, P, P, P, P, C.POINTER(Stats), P]
+    L.mcpt_volume_irradiance_visible_host.argtypes = [VG, D, D, U8, VV, D, C.c_int64, D, I32]
+    L.mcpt_volume_irradiance_visible.argtypes = [P, VG, D, D, U8, VV, D, C.c_int64, D, I32]
+    L.mcpt_volume_irradiance_visible_device.argtypes = [P, VG, P, P, P, VV, P, C.c_int64, P, P, P]
     _lib = L
     return L
 

@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -202,6 +202,61 @@ def volume_irradiance_host(grid, sh, points, normals, valid=None):
     check(lib().mcpt_volume_irradiance_host(C.byref(grid), _p(sh, C.c_double), _p(valid, C.c_uint8), _p(q, C.c_double), n, _p(E, C.c_double),
                                             _p(corners, C.c_int32)))
     return E, corners
+
+
+def visibility_bin(dirs, res):
+    """The octahedral bin of each direction dirs (n, 3), of any non-zero finite length, in a res x res map (mcpt_visibility_bin; no
+    device): (n,) int32 in 0 .. res * res - 1, bin = by * res + bx."""
+    d = np.ascontiguousarray(dirs, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != 3:
+        raise ValueError("dirs must have shape (n, 3)")
+    if not isinstance(res, numbers.Integral) or not -2 ** 31 <= res < 2 ** 31:
+        raise ValueError("res must be a 32-bit integer")
+    out = np.zeros(d.shape[0], dtype=np.int32)
+    check(lib().mcpt_visibility_bin(_p(d, C.c_double), d.shape[0], int(res), _p(out, C.c_int32)))
+    return out
+
+
+def volume_visibility(res=8, max_distance=1.0, normal_bias=0.0, min_visibility=0.0):
+    """An mcpt_volume_visibility (mcpt.h: probe visibility) for volume_irradiance_visible: res and max_distance are the bake's;
+    normal_bias lifts a receiver off its surface along its normal before the probes' maps are asked; min_visibility is the factor's
+    floor.  The library judges the values."""
+    if not isinstance(res, numbers.Integral) or not -2 ** 31 <= res < 2 ** 31:
+        raise ValueError("res must be a 32-bit integer")
+    return VolumeVisibility(int(res), 0, float(max_distance), float(normal_bias), float(min_visibility), (C.c_int32 * 4)(0, 0, 0, 0))
+
+
+def _visibility_moments(grid, vis, moments):
+    if not isinstance(vis, VolumeVisibility):
+        raise ValueError("vis must be a VolumeVisibility (volume_visibility makes one)")
+    probes, bins = _grid_probes(grid), vis.res ** 2 if 1 <= vis.res <= 16 else 0
+    moments = np.ascontiguousarray(moments, dtype=np.float64)
+    if moments.shape[-1:] != (2,) or moments.size != probes * bins * 2:
+        raise ValueError("moments must hold (%d, 2) values for each of the grid's %d probes, not %r" % (bins, probes, moments.shape))
+    return moments
+
+
+def volume_irradiance_visible_host(grid, sh, moments, points, normals, vis, valid=None):
+    """The visibility-weighted lookup on the CPU (mcpt_volume_irradiance_visible_host; no device): volume_irradiance_host with every
+    corner's weight multiplied by what its probe sees of the receiver -- moments [nz, ny, nx, res * res, 2] (or [nprobes, res * res, 2])
+    from bake_volume_visibility, vis from volume_visibility.  Returns (E [n, 3], corners [n])."""
+    sh, q, valid = _volume_args(grid, sh, points, normals, valid)
+    moments = _visibility_moments(grid, vis, moments)
+    n = q.shape[0]
+    E, corners = np.zeros((n, 3)), np.zeros(n, dtype=np.int32)
+    check(lib().mcpt_volume_irradiance_visible_host(C.byref(grid), _p(sh, C.c_double), _p(moments, C.c_double), _p(valid, C.c_uint8), C.byref(vis),
+                                                    _p(q, C.c_double), n, _p(E, C.c_double), _p(corners, C.c_int32)))
+    return E, corners
+
+
+def _visibility_params(spp, res, max_distance, max_back_fraction, seed, sample_base, workspace_rays):
+    for name, v in (("spp", spp), ("sample_base", sample_base), ("res", res)):
+        if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("%s must be a 32-bit integer" % name)
+    if not isinstance(workspace_rays, numbers.Integral) or not -2 ** 63 <= workspace_rays < 2 ** 63:
+        raise ValueError("workspace_rays must be a 64-bit integer")
+    return VisibilityParams(int(spp), int(sample_base), int(seed), int(res), 0, float(max_distance), float(max_back_fraction), int(workspace_rays),
+                            (C.c_int32 * 2)(0, 0))
 
 
 def _adaptive_params(rel_target, abs_target, min_spp):
@@ -906,6 +961,50 @@ class Device:
         E, corners = np.zeros((n, 3)), np.zeros(n, dtype=np.int32)
         check(lib().mcpt_volume_irradiance(self._h, C.byref(grid), _p(sh, C.c_double), _p(valid, C.c_uint8), _p(q, C.c_double), n,
                                            _p(E, C.c_double), _p(corners, C.c_int32)))
+        return E, corners
+
+    def probe_visibility(self, points, spp, res=8, max_distance=1.0, max_back_fraction=0.25, seed=0, ids=None, sample_base=0, workspace_rays=0,
+                         stats=None):
+        """What each of points (n, 3) sees (mcpt_query_visibility): the rays sh_probes() traces for the same seed, ids and sample range,
+        folded into a res x res octahedral map of the mean and mean square of the distance to the nearest surface, clamped at
+        max_distance, and into the count of hits from behind.  Returns (moments [n, res * res, 2] -- a bin without samples holds
+        (-1, 0) --, hits [n], back [n], valid [n]); valid is 0 where more than max_back_fraction of the spp rays hit a back face: the
+        probe sits inside geometry.  workspace_rays bounds the rays in flight (0: the library's default); it does not change the result."""
+        p, ids = self._probe_list(points, ids)
+        vp = _visibility_params(spp, res, max_distance, max_back_fraction, seed, sample_base, workspace_rays)
+        n, bins = p.shape[0], int(res) ** 2 if 1 <= res <= 16 else 0      # (the library refuses any other res)
+        moments, hits, back = np.zeros((n, bins, 2)), np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        valid = np.zeros(n, dtype=np.uint8)
+        check(lib().mcpt_query_visibility(self._h, _p(p, C.c_double), _p(ids, C.c_int32), n, C.byref(vp), _p(moments, C.c_double), _p(hits, C.c_int32),
+                                          _p(back, C.c_int32), _p(valid, C.c_uint8), C.byref(stats) if stats is not None else None))
+        return moments, hits, back, valid
+
+    def bake_volume_visibility(self, grid, spp, res=8, max_distance=None, max_back_fraction=0.25, seed=0, sample_base=0, workspace_rays=0, stats=None):
+        """probe_visibility() of volume_points(grid), bit for bit, with the positions made on the GPU (mcpt_bake_volume_visibility); probe
+        P's RNG key id is P, so the rays are bake_volume()'s.  max_distance defaults to 1.5 x the cell diagonal.  Returns (moments
+        [nz, ny, nx, res * res, 2], hits [nz, ny, nx], back [nz, ny, nx], valid [nz, ny, nx]): valid is volume_irradiance's mask, and
+        volume_irradiance_visible takes the moments."""
+        probes = _grid_probes(grid)
+        if max_distance is None:
+            max_distance = 1.5 * float(np.sqrt(sum(float(s) ** 2 for s in grid.spacing)))
+        vp = _visibility_params(spp, res, max_distance, max_back_fraction, seed, sample_base, workspace_rays)
+        shape = (max(grid.nz, 0), max(grid.ny, 0), max(grid.nx, 0)) if probes else (0, 0, 0)
+        bins = int(res) ** 2 if 1 <= res <= 16 else 0
+        moments, hits, back = np.zeros(shape + (bins, 2)), np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int32)
+        valid = np.zeros(shape, dtype=np.uint8)
+        check(lib().mcpt_bake_volume_visibility(self._h, C.byref(grid), C.byref(vp), _p(moments, C.c_double), _p(hits, C.c_int32), _p(back, C.c_int32),
+                                                _p(valid, C.c_uint8), C.byref(stats) if stats is not None else None))
+        return moments, hits, back, valid
+
+    def volume_irradiance_visible(self, grid, sh, moments, points, normals, vis, valid=None):
+        """The visibility-weighted lookup on the GPU (mcpt_volume_irradiance_visible): volume_irradiance_visible_host's arguments and
+        answers, bit for bit.  Returns (E [n, 3], corners [n])."""
+        sh, q, valid = _volume_args(grid, sh, points, normals, valid)
+        moments = _visibility_moments(grid, vis, moments)
+        n = q.shape[0]
+        E, corners = np.zeros((n, 3)), np.zeros(n, dtype=np.int32)
+        check(lib().mcpt_volume_irradiance_visible(self._h, C.byref(grid), _p(sh, C.c_double), _p(moments, C.c_double), _p(valid, C.c_uint8), C.byref(vis),
+                                                   _p(q, C.c_double), n, _p(E, C.c_double), _p(corners, C.c_int32)))
         return E, corners
 
     def set_environment(self, rgb=None, scale=1.0):

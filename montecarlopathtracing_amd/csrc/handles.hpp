@@ -13,6 +13,7 @@
 //   adaptive_query_api.cpp  adaptive queries: the query call in passes, every query stopping on its own error estimate
 //   lightmap_denoise_api.cpp  the lightmap denoiser: a chart-aware a-trous filter of an irradiance map, then the baker's dilation
 //   volume_api.cpp    irradiance volumes: a probe grid's points, its bake through the probe query, the lookup between its probes
+//   visibility_api.cpp  probe visibility: the octahedral bin, the depth-moment bake of a probe list or grid, the visibility-weighted lookup
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -231,6 +232,15 @@ struct mcpt_device {
         mcpt::Event done;
     };
     std::unique_ptr<Volume> vol;
+    // probe visibility (visibility_api.cpp): the rays of a chunk of probes and their closest hits, made by the first bake and grown to the
+    // largest chunk so far, 84 bytes per ray.  A device-form bake returns with its fold enqueued, so the workspace is not a local of the
+    // call; `done` is recorded behind a bake's last kernel and waited for before the next one writes here.
+    struct Visibility {
+        mcpt::DevBuf<double> rays6, t, p;               // [rays][6], [rays], [rays][3]
+        mcpt::DevBuf<int32_t> leaf;                     // [rays]
+        mcpt::Event done;
+    };
+    std::unique_ptr<Visibility> vis;
 };
 
 // The helpers below are the library's own: none of them is exported from libmcpt.so.
@@ -320,6 +330,15 @@ int query_params_check(const mcpt_query_params* p, int64_t n, const void* q6, co
 int query_list_check(const double* q6, const int32_t* ids, int64_t n, int32_t kind);
 // the refusals of mcpt_query_sh's two forms, shared with the volume bake (volume_api.cpp)
 int sh_params_check(const mcpt_sh_params* p, int64_t n, const void* p3, const void* sh27);
+// what the host-pointer forms refuse of a probe list itself, shared with the visibility bake (visibility_api.cpp)
+int probe_list_check(const double* p3, const int32_t* ids, int64_t n);
+
+// ---- volume_api.cpp (shared with visibility_api.cpp)
+int volume_grid_check(const mcpt_volume_grid* g);   // what every call refuses of a grid, in the struct's field order
+// what the host-pointer forms of a lookup refuse of the coefficients and the receivers themselves
+int volume_arrays_check(const mcpt_volume_grid& g, const double* sh27, const double* q6, int64_t n);
+// a failed allocation of a workspace or a copy: MCPT_ERR_NOMEM when the memory is not there, and the device stays usable
+int volume_alloc_result(hipError_t e, const char* what, size_t bytes);
 
 // ---- lightmap_api.cpp
 namespace mcpt { struct LightmapWork; }

@@ -79,7 +79,7 @@ int query_list_check(const double* q6, const int32_t* ids, int64_t n, int32_t ki
 }
 
 // ... and of a probe list
-static int probe_list_check(const double* p3, const int32_t* ids, int64_t n)
+int probe_list_check(const double* p3, const int32_t* ids, int64_t n)
 {
     for (int64_t i = 0; i < n; i++) {
         if (ids && ids[i] < 0) return fail(MCPT_ERR_ARG, "probe " + std::to_string(i) + ": negative id");

@@ -17,7 +17,7 @@ using namespace mcpt;
 static constexpr int64_t kInt32Max = std::numeric_limits<int32_t>::max();
 
 // what every call refuses of a grid, in the struct's field order
-static int grid_check(const mcpt_volume_grid* g)
+int volume_grid_check(const mcpt_volume_grid* g)
 {
     if (!g) return fail(MCPT_ERR_ARG, "null volume grid");
     for (int a = 0; a < 3; a++)
@@ -35,14 +35,14 @@ static int grid_check(const mcpt_volume_grid* g)
 // what every form of the lookup refuses without looking at the arrays
 static int lookup_check(const mcpt_volume_grid* g, const void* sh27, const void* q6, int64_t n, const void* e3)
 {
-    if (const int rc = grid_check(g)) return rc;
+    if (const int rc = volume_grid_check(g)) return rc;
     if (n < 0 || n > kInt32Max) return fail(MCPT_ERR_ARG, "the number of receivers must be in 0 .. 2^31 - 1");
     if (n > 0 && (!sh27 || !q6 || !e3)) return fail(MCPT_ERR_ARG, "null coefficients, receiver list or irradiance");
     return MCPT_OK;
 }
 
 // ... and what the host-pointer forms refuse of the arrays themselves
-static int lookup_arrays_check(const mcpt_volume_grid& g, const double* sh27, const double* q6, int64_t n)
+int volume_arrays_check(const mcpt_volume_grid& g, const double* sh27, const double* q6, int64_t n)
 {
     const int64_t coefficients = volume_probes(g) * (MCPT_SH_N * 3);
     for (int64_t i = 0; i < coefficients; i++)
@@ -58,7 +58,7 @@ static int lookup_arrays_check(const mcpt_volume_grid& g, const double* sh27, co
 }
 
 // a failed allocation of a workspace or a copy: MCPT_ERR_NOMEM when the memory is not there, and the device stays usable
-static int alloc_result(hipError_t e, const char* what, size_t bytes)
+int volume_alloc_result(hipError_t e, const char* what, size_t bytes)
 {
     if (e == hipSuccess) return MCPT_OK;
     (void)hipGetLastError();                                    // the runtime keeps the failure as its last error: it has been reported here
@@ -84,7 +84,7 @@ static int bake_device(mcpt_device* d, const mcpt_volume_grid& g, const mcpt_sh_
     HIP_TRY(hipEventSynchronize(v.done.get()));                 // the bake before this one has read its points
     const int64_t n = volume_probes(g);
     const size_t bytes = size_t(n) * 3 * sizeof(double);
-    if (const int rc = alloc_result(v.p3.grow_bytes(bytes), "the volume's probe positions", bytes)) return rc;
+    if (const int rc = volume_alloc_result(v.p3.grow_bytes(bytes), "the volume's probe positions", bytes)) return rc;
     launch_volume_points(g, v.p3.get(), st);
     HIP_TRY(hipGetLastError());
     const int rc = query_device(d, DQuery{v.p3.get(), MCPT_QUERY_KIND_SPHERE, d_sh, d_err, d_hits}, nullptr, n, p.spp, p.sample_base, p.seed, p.flags,
@@ -110,7 +110,7 @@ extern "C" {
 
 int mcpt_volume_points(const mcpt_volume_grid* g, double* p3)
 {
-    if (const int rc = grid_check(g)) return rc;
+    if (const int rc = volume_grid_check(g)) return rc;
     if (!p3) return fail(MCPT_ERR_ARG, "null positions");
     int64_t P = 0;
     for (int iz = 0; iz < g->nz; iz++)
@@ -127,7 +127,7 @@ int mcpt_bake_volume_device(mcpt_device* d, const mcpt_volume_grid* g, const mcp
                             mcpt_stats* stats, void* stream)
 {
     if (!g || !p) return fail(MCPT_ERR_ARG, "null volume grid or probe parameters");
-    if (const int rc = grid_check(g)) return rc;
+    if (const int rc = volume_grid_check(g)) return rc;
     if (const int rc = sh_params_check(p, volume_probes(*g), g, d_sh27)) return rc;
     return bake_device(d, *g, *p, d_sh27, d_stderr27, d_hits, stats, static_cast<hipStream_t>(stream));
 }
@@ -135,7 +135,7 @@ int mcpt_bake_volume_device(mcpt_device* d, const mcpt_volume_grid* g, const mcp
 int mcpt_bake_volume(mcpt_device* d, const mcpt_volume_grid* g, const mcpt_sh_params* p, double* sh27, double* stderr27, int32_t* hits, mcpt_stats* stats)
 {
     if (!g || !p) return fail(MCPT_ERR_ARG, "null volume grid or probe parameters");
-    if (const int rc = grid_check(g)) return rc;
+    if (const int rc = volume_grid_check(g)) return rc;
     if (const int rc = sh_params_check(p, volume_probes(*g), g, sh27)) return rc;
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
@@ -143,9 +143,9 @@ int mcpt_bake_volume(mcpt_device* d, const mcpt_volume_grid* g, const mcpt_sh_pa
     const size_t n = size_t(volume_probes(*g)), bytes = n * MCPT_SH_N * 3 * sizeof(double);
     DevBuf<double> d_sh, d_err;
     DevBuf<int32_t> d_hits;
-    if (const int rc = alloc_result(d_sh.alloc_bytes(bytes), "the volume's coefficients", bytes)) return rc;
+    if (const int rc = volume_alloc_result(d_sh.alloc_bytes(bytes), "the volume's coefficients", bytes)) return rc;
     if (stderr27)
-        if (const int rc = alloc_result(d_err.alloc_bytes(bytes), "the volume's standard errors", bytes)) return rc;
+        if (const int rc = volume_alloc_result(d_err.alloc_bytes(bytes), "the volume's standard errors", bytes)) return rc;
     if (hits) HIP_TRY(d_hits.alloc(n));
     hipStream_t st = d->stream.get();
     int rc = bake_device(d, *g, *p, d_sh.get(), d_err.get(), d_hits.get(), stats, st);
@@ -163,7 +163,7 @@ int mcpt_volume_irradiance_host(const mcpt_volume_grid* g, const double* sh27, c
 {
     if (const int rc = lookup_check(g, sh27, q6, n, e3)) return rc;
     if (n == 0) return MCPT_OK;
-    if (const int rc = lookup_arrays_check(*g, sh27, q6, n)) return rc;
+    if (const int rc = volume_arrays_check(*g, sh27, q6, n)) return rc;
     const bool clamp = (g->flags & MCPT_VOLUME_CLAMP_ZERO) != 0;
     for (int64_t r = 0; r < n; r++) {
         int32_t P[8];
@@ -188,7 +188,7 @@ int mcpt_volume_irradiance(mcpt_device* d, const mcpt_volume_grid* g, const doub
 {
     if (const int rc = lookup_check(g, sh27, q6, n, e3)) return rc;
     if (n > 0)
-        if (const int rc = lookup_arrays_check(*g, sh27, q6, n)) return rc;
+        if (const int rc = volume_arrays_check(*g, sh27, q6, n)) return rc;
     if (const int rc = require_device()) return rc;
     if (!d) return fail(MCPT_ERR_ARG, "null device");
     if (n == 0) return MCPT_OK;
@@ -197,9 +197,9 @@ int mcpt_volume_irradiance(mcpt_device* d, const mcpt_volume_grid* g, const doub
     DevBuf<double> d_sh, d_q, d_e;
     DevBuf<uint8_t> d_valid;
     DevBuf<int32_t> d_corners;
-    if (const int rc = alloc_result(d_sh.alloc_bytes(sh_bytes), "the volume's coefficients", sh_bytes)) return rc;
-    if (const int rc = alloc_result(d_q.alloc_bytes(sn * 6 * sizeof(double)), "the receiver list", sn * 6 * sizeof(double))) return rc;
-    if (const int rc = alloc_result(d_e.alloc_bytes(sn * 3 * sizeof(double)), "the receivers' irradiance", sn * 3 * sizeof(double))) return rc;
+    if (const int rc = volume_alloc_result(d_sh.alloc_bytes(sh_bytes), "the volume's coefficients", sh_bytes)) return rc;
+    if (const int rc = volume_alloc_result(d_q.alloc_bytes(sn * 6 * sizeof(double)), "the receiver list", sn * 6 * sizeof(double))) return rc;
+    if (const int rc = volume_alloc_result(d_e.alloc_bytes(sn * 3 * sizeof(double)), "the receivers' irradiance", sn * 3 * sizeof(double))) return rc;
     if (valid) HIP_TRY(d_valid.alloc(probes));
     if (corners) HIP_TRY(d_corners.alloc(sn));
     HIP_TRY(hipMemcpy(d_sh.get(), sh27, sh_bytes, hipMemcpyHostToDevice));
