@@ -1029,8 +1029,8 @@ int mcpt_sh_irradiance(const double* sh27, const double* n3, int64_t n, double* 
  * is not finite is skipped.
  * Not covered: UV unwrapping and packing; supersampling or conservative coverage (a sliver that contains no texel centre gets no texel:
  * dilation is the remedy); rejecting texels whose point lies inside other geometry; directional or SH lightmaps; the multi-device group
- * and render_scene; the use of a lightmap in shading.  Texels that stop on their own error estimate are mcpt_bake_lightmap_adaptive's
- * (adaptive queries, below). */
+ * and render_scene.  The use of a lightmap in shading is the baked frames' block's, below.  Texels that stop on their own error
+ * estimate are mcpt_bake_lightmap_adaptive's (adaptive queries, below). */
 typedef struct { int32_t width, height, spp, sample_base; uint64_t seed;
                  int32_t flags, dilate, reserved[2]; } mcpt_lightmap_params;
 int     mcpt_lightmap_raster_host(const double* uv6, int64_t num_faces, int32_t width, int32_t height, int32_t* owner);
@@ -1203,8 +1203,8 @@ int mcpt_lightmap_denoise_device(mcpt_device*, const double* d_uv6, const mcpt_l
  * n == 0: MCPT_OK, nothing is launched.  A probe list or a copy that cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable.
  * Not covered: a standard error of the lookup (the coefficients of one probe share their samples: a sum of squares would be wrong);
  * finding invalid probes and visibility-weighted interpolation here (both are the probe visibility block's below: its bake fills the
- * mask, its lookup weighs every corner by what the probe sees); radiance (glossy) lookup and returning the blended coefficients; adaptive probes; the multi-device group and render_scene; lighting a
- * frame from the volume. */
+ * mask, its lookup weighs every corner by what the probe sees); radiance (glossy) lookup and returning the blended coefficients; adaptive probes; the multi-device group and render_scene.  Lighting a
+ * frame from the volume is the baked frames' block's, below. */
 #define MCPT_VOLUME_CLAMP_ZERO 1   /* E_c = max(E_c, 0.0): order-2 ringing can go negative */
 typedef struct { double origin[3], spacing[3]; int32_t nx, ny, nz, flags; int32_t reserved[4]; } mcpt_volume_grid;
 int mcpt_volume_points(const mcpt_volume_grid*, double* p3);
@@ -1301,6 +1301,103 @@ int mcpt_volume_irradiance_visible(mcpt_device*, const mcpt_volume_grid*, const 
 int mcpt_volume_irradiance_visible_device(mcpt_device*, const mcpt_volume_grid*, const double* d_sh27, const double* d_moments,
                                           const uint8_t* d_valid, const mcpt_volume_visibility*, const double* d_q6, int64_t n,
                                           double* d_e3, int32_t* d_corners, void* stream);
+
+/* ---- baked frames (since the baked-frame change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* A BAKED FRAME shows what a bake holds: every camera ray is traced for its closest hit and the surface there is lit by the irradiance a
+ * lightmap or an irradiance volume stores, L = kd * E / pi -- global illumination from one ray per camera sample.  Three layers, each a
+ * test seam of the next: the lightmap's lookup by chart coordinate, the baked radiance along a caller's rays, the frame.  fp64, no
+ * contraction, IEEE division, every expression and sum in the order written; every output is one lane's fixed-order sum: the same bits on
+ * the host and on the GPU, whatever the launch shape and the chunking.
+ *   lightmap lookup : mcpt_lightmap_irradiance*, the counterpart of mcpt_volume_irradiance*.  A map of width x height texels (each in
+ *              1 .. 16384), irradiance3[W * H * 3], owner[W * H] or NULL, as mcpt_bake_lightmap writes them: texel x has its centre at
+ *              (x + 0.5) / W, row 0 is the row nearest v = 0, no flip, no wrap.  For chart coordinate uv2[i] = (u, v), per axis (u with W,
+ *              v with H):
+ *                s = u * double(W) - 0.5; s = s > 0.0 ? s : 0.0; s = s < double(W - 1) ? s : double(W - 1)  -- THE CLAMP IS IN DOUBLE,
+ *                before any conversion to int: a coordinate of 1e300 takes the border's texel, a NaN lands on texel 0;
+ *                W == 1: i0 = i1 = 0, f = 0.0;   W >= 2: i0 = min(int(floor(s)), W - 2), i1 = i0 + 1, f = s - double(i0);
+ *                w0 = 1.0 - f, w1 = f.
+ *              Tap j = dy * 2 + dx, j = 0 .. 3, is texel T_j = y_dy * W + x_dx with weight w_j = wx_dx * wy_dy.  With an owner map,
+ *              w_j = 0.0 where owner[T_j] == -1 (never covered, never filled by dilation); S = sum_j w_j in j order from 0.0; S > 0:
+ *              w_j = w_j / S; otherwise E = +0.0 and taps = 0.  With owner == NULL nothing is divided.
+ *              E_c = sum_j w_j * irradiance3[T_j][c] in j order from 0.0; taps[i] (may be NULL) = the number of j with w_j > 0.  Hence a
+ *              coordinate whose s comes out a whole number on both axes gets that texel's value, bit for bit (finite maps).
+ *   source   : mcpt_baked_source names what lights the surfaces.  MCPT_BAKED_VOLUME: grid, sh27 and valid (may be NULL) as
+ *              mcpt_volume_irradiance takes them; with moments != NULL also visibility, and the lookup is
+ *              mcpt_volume_irradiance_visible's.  MCPT_BAKED_LIGHTMAP: width, height, irradiance3 and owner (may be NULL) as above, and
+ *              the chart uv6[num_faces][6] in .obj order, NULL: the faces' own vt -- exactly as mcpt_bake_lightmap reads a chart.  The
+ *              fields of the other kind are not read.  In the host-pointer calls every pointer is a host pointer, in the _device calls a
+ *              device pointer (grid and visibility are always host structs).
+ *   baked radiance : mcpt_baked_radiance*, rays6[n][6] = origin, direction as mcpt_trace_closest takes them, answered by its walks (the
+ *              device's trace mode and engine, its current geometry, key 0 of a motion).  With d the ray's direction and p the hit:
+ *                kind = MCPT_BAKED_MISS (0), MCPT_BAKED_EMITTER (1: the hit material is a light) or MCPT_BAKED_SURFACE (2);
+ *                MISS    : L = Le(d) as mcpt_environment_eval gives it when the device has an active environment, else +0.0;
+ *                EMITTER : L = the light's radiance (what a camera sample that hits an emitter shows);
+ *                SURFACE : kd = the diffuse colour shading forms there, texel included (mcpt_progressive_aovs' albedo); n = pn of
+ *                          mcpt_trace_closest, replaced by the face's stored normal when (nx nx + ny ny) + nz nz is 0 or not finite;
+ *                          under MCPT_BAKED_FACE_VIEWER n = -n when ((dx nx + dy ny) + dz nz) > 0.0.
+ *                          Volume: E, lit = the lookup's e3 and corners at q6 = (p, n).
+ *                          Lightmap: g = the barycentrics of p as mcpt_trace_closest forms them for pn (the quotient form);
+ *                          (au .. cv) = the chart row of the hit face; u = (au * g.x + bu * g.y) + cu * g.z, v likewise;
+ *                          E, lit = the lightmap lookup's e3 and taps at (u, v).
+ *                          L_c = (kd_c * E_c) / 3.141592653589793; under MCPT_BAKED_LIGHTING_ONLY L_c = E_c / 3.141592653589793.
+ *              mcpt_baked_outputs, every pointer may be NULL: radiance3[n][3], kind[n], face[n] (the .obj index, -1: a miss), q6[n][6]
+ *              (p and the n that went into the lookup), uv2[n][2] (+0.0 under a volume), kd3[n][3], e3[n][3], lit[n].  For a ray that
+ *              is not a surface hit everything but radiance3, kind and face is +0.0 or 0.  Glass and mirrors show kd * E / pi like any
+ *              other surface.  stats: rays_primary = samples = n, launches = the number of chunks (of at most 4 194 304 rays).
+ *   frame    : mcpt_render_baked*.  For every pixel of the device's frame, sample k = 0 .. samples - 1 is the frame's own camera ray of
+ *              (pixel, k): mcpt_camera_rays of (seed, pixel, k) under the device's lens, shaded as above under `flags`.
+ *              img[pixel][c] = s / double(samples), s = 0.0 + L_0 + ... in k order: mcpt_render's layout, so mcpt_display_device takes
+ *              it as it is.  counts3[pixel] (may be NULL) = (surface, emitter, miss) samples; lit[pixel] (may be NULL) = the surface
+ *              samples whose lookup had lit > 0.  The call works in chunks of whole pixels of at most workspace_rays rays (0: 4 194 304)
+ *              and at least one pixel; stats: rays_primary = samples = pixels * samples, launches = the number of chunks.
+ * mcpt_lightmap_irradiance_host runs on the CPU and needs no device.  The host-pointer forms are synchronous and copy in and out around
+ * the _device forms.  The _device forms take device pointers throughout and enqueue on `stream`.  mcpt_baked_radiance_device and
+ * mcpt_render_baked_device keep a workspace on the device (116 bytes per ray of the largest chunk so far), first wait for the event behind
+ * the device's previous baked call, and return without waiting when stats == NULL (the first frame of a device also makes the lens's
+ * image-plane points and waits for them); they use the counters and queue words of mcpt_trace_closest_device and, like it, must not
+ * overlap another closest-hit call of the same device on another stream.  The lightmap lookup never waits and allocates nothing.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE, in this order).  The lightmap lookup: a size outside 1 .. 16384; n < 0 or n > 2^31 - 1;
+ * NULL irradiance3, uv2 or e3 with n > 0; the host-pointer forms: a coordinate that is not finite.  A source: NULL; kind neither
+ * MCPT_BAKED_VOLUME nor MCPT_BAKED_LIGHTMAP; flags != 0; reserved != 0; a volume: the grid's errors (NULL first), NULL sh27, and with
+ * moments a NULL visibility and then its errors in mcpt_volume_irradiance_visible's order; a lightmap: a size outside 1 .. 16384, NULL
+ * irradiance3.  mcpt_baked_radiance*: the source; a flag other than MCPT_BAKED_FACE_VIEWER | MCPT_BAKED_LIGHTING_ONLY; n < 0 or
+ * n > 2^31 - 1; NULL rays6 with n > 0; NULL outputs; outputs' reserved != 0.  mcpt_render_baked*: the source; NULL parameters; samples
+ * outside 1 .. 65536; a flag other than the two above; workspace_rays < 0; reserved != 0; NULL img.  In the
+ * host-pointer forms a chart component that is not finite is MCPT_ERR_ARG as well -- after the missing device and the NULL device, because
+ * the chart's length is the device's face count.  THE DEVICE FORMS DO NOT LOOK AT THEIR ARRAYS and read no texel or probe outside their
+ * tables.  n == 0: MCPT_OK, nothing is launched.  A workspace or a copy that cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable.
+ * Not covered: direct light or shadows added on top of the bake; specular or glass transport; standard errors of a baked frame;
+ * mip-mapping or anisotropic filtering of the map; chart-aware taps beyond the owner rule; partitions, the multi-device group and
+ * render_scene; a baked source inside the progressive handles. */
+#define MCPT_BAKED_VOLUME    1
+#define MCPT_BAKED_LIGHTMAP  2
+#define MCPT_BAKED_MISS      0
+#define MCPT_BAKED_EMITTER   1
+#define MCPT_BAKED_SURFACE   2
+#define MCPT_BAKED_FACE_VIEWER    1   /* the shading normal faces the ray's origin */
+#define MCPT_BAKED_LIGHTING_ONLY  2   /* L = E / pi: the lighting without the surface's colour */
+typedef struct { int32_t kind, flags;
+                 const mcpt_volume_grid* grid; const double* sh27; const uint8_t* valid;
+                 const double* moments; const mcpt_volume_visibility* visibility;
+                 const double* uv6; int32_t width, height; const double* irradiance3; const int32_t* owner;
+                 int64_t reserved[4]; } mcpt_baked_source;
+typedef struct { double* radiance3; int32_t* kind; int32_t* face; double* q6; double* uv2; double* kd3; double* e3; int32_t* lit;
+                 int64_t reserved[2]; } mcpt_baked_outputs;
+typedef struct { int32_t samples, flags; uint64_t seed; int64_t workspace_rays; int32_t reserved[2]; } mcpt_baked_frame_params;
+int mcpt_lightmap_irradiance_host(int32_t width, int32_t height, const double* irradiance3, const int32_t* owner,
+                                  const double* uv2, int64_t n, double* e3, int32_t* taps);
+int mcpt_lightmap_irradiance(mcpt_device*, int32_t width, int32_t height, const double* irradiance3, const int32_t* owner,
+                             const double* uv2, int64_t n, double* e3, int32_t* taps);
+int mcpt_lightmap_irradiance_device(mcpt_device*, int32_t width, int32_t height, const double* d_irradiance3, const int32_t* d_owner,
+                                    const double* d_uv2, int64_t n, double* d_e3, int32_t* d_taps, void* stream);
+int mcpt_baked_radiance(mcpt_device*, const mcpt_baked_source*, const double* rays6, int64_t n, int32_t flags,
+                        const mcpt_baked_outputs*, mcpt_stats*);
+int mcpt_baked_radiance_device(mcpt_device*, const mcpt_baked_source*, const double* d_rays6, int64_t n, int32_t flags,
+                               const mcpt_baked_outputs*, mcpt_stats*, void* stream);
+int mcpt_render_baked(mcpt_device*, const mcpt_baked_source*, const mcpt_baked_frame_params*,
+                      double* img, int32_t* counts3, int32_t* lit, mcpt_stats*);
+int mcpt_render_baked_device(mcpt_device*, const mcpt_baked_source*, const mcpt_baked_frame_params*,
+                             double* d_img, int32_t* d_counts3, int32_t* d_lit, mcpt_stats*, void* stream);
 
 #ifdef __cplusplus
 }

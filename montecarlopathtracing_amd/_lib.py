@@ -201,6 +201,25 @@ class VolumeVisibility(C.Structure):
                 ("min_visibility", C.c_double), ("reserved", C.c_int32 * 4)]
 
 
+class BakedSource(C.Structure):
+    """mcpt_baked_source: what lights the surfaces of a baked frame -- an irradiance volume (grid, sh27, valid, moments, visibility) or a
+    lightmap (uv6, width, height, irradiance3, owner); api.baked_volume and api.baked_lightmap make the Python-side holders"""
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_int32), ("grid", C.POINTER(VolumeGrid)), ("sh27", C.c_void_p), ("valid", C.c_void_p),
+                ("moments", C.c_void_p), ("visibility", C.POINTER(VolumeVisibility)), ("uv6", C.c_void_p), ("width", C.c_int32),
+                ("height", C.c_int32), ("irradiance3", C.c_void_p), ("owner", C.c_void_p), ("reserved", C.c_int64 * 4)]
+
+
+class BakedOutputs(C.Structure):
+    """mcpt_baked_outputs: where mcpt_baked_radiance puts its answers, ray by ray; every pointer may be null"""
+    _fields_ = [("radiance3", C.c_void_p), ("kind", C.c_void_p), ("face", C.c_void_p), ("q6", C.c_void_p), ("uv2", C.c_void_p),
+                ("kd3", C.c_void_p), ("e3", C.c_void_p), ("lit", C.c_void_p), ("reserved", C.c_int64 * 2)]
+
+
+class BakedFrameParams(C.Structure):
+    """mcpt_baked_frame_params: camera samples per pixel, MCPT_BAKED_* flags, seed, and the workspace's size in rays (0: the default)"""
+    _fields_ = [("samples", C.c_int32), ("flags", C.c_int32), ("seed", C.c_uint64), ("workspace_rays", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -245,6 +264,8 @@ EXPORTS = [
     "mcpt_visibility_bin", "mcpt_query_visibility", "mcpt_query_visibility_device",
     "mcpt_bake_volume_visibility", "mcpt_bake_volume_visibility_device",
     "mcpt_volume_irradiance_visible_host", "mcpt_volume_irradiance_visible", "mcpt_volume_irradiance_visible_device",
+    "mcpt_lightmap_irradiance_host", "mcpt_lightmap_irradiance", "mcpt_lightmap_irradiance_device",
+    "mcpt_baked_radiance", "mcpt_baked_radiance_device", "mcpt_render_baked", "mcpt_render_baked_device",
 ]
 
 
@@ -455,6 +476,14 @@ def lib():
     L.mcpt_volume_irradiance_visible_host.argtypes = [VG, D, D, U8, VV, D, C.c_int64, D, I32]
     L.mcpt_volume_irradiance_visible.argtypes = [P, VG, D, D, U8, VV, D, C.c_int64, D, I32]
     L.mcpt_volume_irradiance_visible_device.argtypes = [P, VG, P, P, P, VV, P, C.c_int64, P, P, P]
+    BS, BO, BF = C.POINTER(BakedSource), C.POINTER(BakedOutputs), C.POINTER(BakedFrameParams)
+    L.mcpt_lightmap_irradiance_host.argtypes = [C.c_int32, C.c_int32, D, I32, D, C.c_int64, D, I32]
+    L.mcpt_lightmap_irradiance.argtypes = [P, C.c_int32, C.c_int32, D, I32, D, C.c_int64, D, I32]
+    L.mcpt_lightmap_irradiance_device.argtypes = [P, C.c_int32, C.c_int32, P, P, P, C.c_int64, P, P, P]
+    L.mcpt_baked_radiance.argtypes = [P, BS, D, C.c_int64, C.c_int32, BO, C.POINTER(Stats)]
+    L.mcpt_baked_radiance_device.argtypes = [P, BS, P, C.c_int64, C.c_int32, BO, C.POINTER(Stats), P]
+    L.mcpt_render_baked.argtypes = [P, BS, BF, D, I32, I32, C.POINTER(Stats)]
+    L.mcpt_render_baked_device.argtypes = [P, BS, BF, P, P, P, C.POINTER(Stats), P]
     _lib = L
     return L
 

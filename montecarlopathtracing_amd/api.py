@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -29,10 +29,21 @@ _QUERY_KINDS = {"ray": QUERY_RAY, "hemisphere": QUERY_HEMISPHERE}
 LIGHTMAP_DENOISE_ITERATIONS, LIGHTMAP_DENOISE_MAX_ITERATIONS = 5, 10
 LIGHTMAP_DENOISE_SIGMA_L, LIGHTMAP_DENOISE_SIGMA_P = 2.0, 1.0
 VOLUME_CLAMP_ZERO = 1
+# mcpt.h: MCPT_BAKED_* -- the kinds of a baked source, the kinds of a sample, the flags of a baked call
+BAKED_VOLUME, BAKED_LIGHTMAP = 1, 2
+BAKED_MISS, BAKED_EMITTER, BAKED_SURFACE = 0, 1, 2
+BAKED_FACE_VIEWER, BAKED_LIGHTING_ONLY = 1, 2
 
 
 def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
+
+
+def _dp(ptr):
+    """a device pointer or stream given as an address (a torch tensor's data_ptr()) or as a ctypes pointer; None or 0: null"""
+    if isinstance(ptr, C.c_void_p):
+        return ptr
+    return C.c_void_p(ptr) if ptr else None
 
 
 def make_lens(aperture=0.0, focus_distance=0.0, jitter=False, per_sample=False):
@@ -247,6 +258,86 @@ def volume_irradiance_visible_host(grid, sh, moments, points, normals, vis, vali
     check(lib().mcpt_volume_irradiance_visible_host(C.byref(grid), _p(sh, C.c_double), _p(moments, C.c_double), _p(valid, C.c_uint8), C.byref(vis),
                                                     _p(q, C.c_double), n, _p(E, C.c_double), _p(corners, C.c_int32)))
     return E, corners
+
+
+def _lightmap_args(E, uv, owner):
+    E = np.ascontiguousarray(E, dtype=np.float64)
+    if E.ndim != 3 or E.shape[2] != 3:
+        raise ValueError("E must have shape (height, width, 3), not %r" % (E.shape,))
+    uv = np.ascontiguousarray(uv, dtype=np.float64)
+    if uv.ndim != 2 or uv.shape[1] != 2:
+        raise ValueError("uv must have shape (n, 2), not %r" % (uv.shape,))
+    if owner is not None:
+        owner = np.ascontiguousarray(owner, dtype=np.int32)
+        if owner.shape != E.shape[:2]:
+            raise ValueError("owner must have shape (height, width) = %r, not %r" % (E.shape[:2], owner.shape))
+    return E, uv, owner
+
+
+def lightmap_irradiance_host(E, uv, owner=None):
+    """A lightmap's lookup by chart coordinate on the CPU (mcpt_lightmap_irradiance_host; no device): E [height, width, 3] and owner
+    [height, width] (or None) as bake_lightmap returns them, uv (n, 2) chart coordinates.  Returns (e [n, 3], taps [n]): the bilinear
+    blend of the four texels around each coordinate -- texel x has its centre at (x + 0.5) / width, no flip, no wrap, the border's texels
+    outside the map -- leaving out texels whose owner is -1, and how many of the four took part."""
+    E, uv, owner = _lightmap_args(E, uv, owner)
+    n = uv.shape[0]
+    e, taps = np.zeros((n, 3)), np.zeros(n, dtype=np.int32)
+    check(lib().mcpt_lightmap_irradiance_host(E.shape[1], E.shape[0], _p(E, C.c_double), _p(owner, C.c_int32), _p(uv, C.c_double), n,
+                                              _p(e, C.c_double), _p(taps, C.c_int32)))
+    return e, taps
+
+
+class _Baked:
+    """What lights the surfaces of a baked frame (mcpt_baked_source) with the arrays it points to; baked_volume and baked_lightmap make one"""
+
+    def __init__(self, kind, **arrays):
+        self.kind = kind
+        self.__dict__.update(arrays)
+
+    def struct(self):
+        """the mcpt_baked_source of host pointers into this object's arrays (which must outlive it)"""
+        s = BakedSource()
+        s.kind = self.kind
+        addr = lambda a: a.ctypes.data if a is not None else None
+        if self.kind == BAKED_VOLUME:
+            s.grid = C.pointer(self.grid)
+            s.sh27, s.valid, s.moments = addr(self.sh), addr(self.valid), addr(self.moments)
+            if self.vis is not None:
+                s.visibility = C.pointer(self.vis)
+        else:
+            s.uv6, s.irradiance3, s.owner = addr(self.uv), addr(self.E), addr(self.owner)
+            s.height, s.width = self.E.shape[:2]
+        return s
+
+
+def baked_volume(grid, sh, valid=None, moments=None, vis=None):
+    """An irradiance volume as the source of Device.baked_radiance and Device.render_baked: grid, sh and valid as volume_irradiance takes
+    them; with moments (and vis, from volume_visibility) the lookup is volume_irradiance_visible's."""
+    probes = _grid_probes(grid)
+    sh = np.ascontiguousarray(sh, dtype=np.float64)
+    if sh.shape[-2:] != (9, 3) or sh.size != probes * 27:
+        raise ValueError("sh must hold (9, 3) coefficients for each of the grid's %d probes, not %r" % (probes, sh.shape))
+    if valid is not None:
+        valid = np.ascontiguousarray(valid)
+        if valid.dtype.kind not in "biu" or valid.size != probes:
+            raise ValueError("valid must hold one flag for each of the grid's %d probes" % probes)
+        valid = np.ascontiguousarray(valid != 0, dtype=np.uint8)
+    if moments is not None:
+        moments = _visibility_moments(grid, vis, moments)
+    elif vis is not None:
+        raise ValueError("vis without moments")
+    return _Baked(BAKED_VOLUME, grid=grid, sh=sh, valid=valid, moments=moments, vis=vis)
+
+
+def baked_lightmap(E, uv=None, owner=None):
+    """A lightmap as the source of Device.baked_radiance and Device.render_baked: E [height, width, 3] and owner [height, width] (or
+    None) as bake_lightmap returns them, uv (num_faces, 6) the chart it was baked under, None: the scene's own vt."""
+    E, _, owner = _lightmap_args(E, np.zeros((0, 2)), owner)
+    return _Baked(BAKED_LIGHTMAP, E=E, uv=_chart(uv) if uv is not None else None, owner=owner)
+
+
+def _baked_flags(face_viewer, lighting_only):
+    return (BAKED_FACE_VIEWER if face_viewer else 0) | (BAKED_LIGHTING_ONLY if lighting_only else 0)
 
 
 def _visibility_params(spp, res, max_distance, max_back_fraction, seed, sample_base, workspace_rays):
@@ -1006,6 +1097,81 @@ class Device:
         check(lib().mcpt_volume_irradiance_visible(self._h, C.byref(grid), _p(sh, C.c_double), _p(moments, C.c_double), _p(valid, C.c_uint8), C.byref(vis),
                                                    _p(q, C.c_double), n, _p(E, C.c_double), _p(corners, C.c_int32)))
         return E, corners
+
+    def lightmap_irradiance(self, E, uv, owner=None):
+        """A lightmap's lookup by chart coordinate on the GPU (mcpt_lightmap_irradiance): lightmap_irradiance_host's arguments and
+        answers, bit for bit.  Returns (e [n, 3], taps [n])."""
+        E, uv, owner = _lightmap_args(E, uv, owner)
+        n = uv.shape[0]
+        e, taps = np.zeros((n, 3)), np.zeros(n, dtype=np.int32)
+        check(lib().mcpt_lightmap_irradiance(self._h, E.shape[1], E.shape[0], _p(E, C.c_double), _p(owner, C.c_int32), _p(uv, C.c_double), n,
+                                             _p(e, C.c_double), _p(taps, C.c_int32)))
+        return e, taps
+
+    def lightmap_irradiance_device(self, width, height, d_E_ptr, d_uv_ptr, n, d_e_ptr, d_owner_ptr=None, d_taps_ptr=None, stream=None):
+        """The same between caller-owned device buffers (e.g. torch tensors' data_ptr()) on `stream` (mcpt_lightmap_irradiance_device)."""
+        check(lib().mcpt_lightmap_irradiance_device(self._h, int(width), int(height), _dp(d_E_ptr), _dp(d_owner_ptr),
+                                                    _dp(d_uv_ptr), int(n), _dp(d_e_ptr), _dp(d_taps_ptr),
+                                                    _dp(stream)))
+
+    def _baked_source(self, source):
+        if not isinstance(source, _Baked):
+            raise ValueError("source must come from baked_volume or baked_lightmap")
+        if source.kind == BAKED_LIGHTMAP and source.uv is not None:
+            _chart(source.uv, self.scene.info.num_faces)
+        return source.struct()
+
+    def baked_radiance(self, rays, source, face_viewer=False, lighting_only=False, stats=None):
+        """What the caller's rays (n, 6) = origin, direction see of a bake (mcpt_baked_radiance): every ray's closest hit, lit by `source`
+        (baked_volume or baked_lightmap) as L = kd * E / pi; a miss shows the environment, an emitter its radiance.  face_viewer turns the
+        shading normal towards the ray's origin; lighting_only leaves kd out.  Returns a dict: radiance [n, 3], kind [n] (BAKED_MISS,
+        BAKED_EMITTER, BAKED_SURFACE), face [n] (.obj index, -1: a miss), q6 [n, 6] (hit point and the normal that went into the lookup),
+        uv [n, 2] (the chart coordinate, lightmap sources), kd [n, 3], e [n, 3] (the irradiance looked up) and lit [n] (the corners or taps
+        that took part).  Everything but radiance, kind and face is 0 where a ray is not a surface hit."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must have shape (n, 6), not %r" % (rays.shape,))
+        n = rays.shape[0]
+        s = self._baked_source(source)
+        out = {"radiance": np.zeros((n, 3)), "kind": np.zeros(n, dtype=np.int32), "face": np.zeros(n, dtype=np.int32), "q6": np.zeros((n, 6)),
+               "uv": np.zeros((n, 2)), "kd": np.zeros((n, 3)), "e": np.zeros((n, 3)), "lit": np.zeros(n, dtype=np.int32)}
+        o = BakedOutputs(*[out[k].ctypes.data for k in ("radiance", "kind", "face", "q6", "uv", "kd", "e", "lit")])
+        check(lib().mcpt_baked_radiance(self._h, C.byref(s), _p(rays, C.c_double), n, _baked_flags(face_viewer, lighting_only), C.byref(o),
+                                        C.byref(stats) if stats is not None else None))
+        return out
+
+    def baked_radiance_device(self, d_rays_ptr, n, source_struct, outputs_struct, face_viewer=False, lighting_only=False, stats=None, stream=None):
+        """The same between caller-owned device buffers on `stream` (mcpt_baked_radiance_device): source_struct a BakedSource and
+        outputs_struct a BakedOutputs of device pointers."""
+        check(lib().mcpt_baked_radiance_device(self._h, C.byref(source_struct), _dp(d_rays_ptr), int(n), _baked_flags(face_viewer, lighting_only),
+                                               C.byref(outputs_struct), C.byref(stats) if stats is not None else None,
+                                               _dp(stream)))
+
+    def render_baked(self, source, samples=1, seed=0, face_viewer=False, lighting_only=False, workspace_rays=0, stats=None):
+        """A frame lit by a bake (mcpt_render_baked): for every pixel, `samples` camera rays of the device's lens -- camera_rays(seed,
+        pixel, k) -- shaded as baked_radiance shades them and averaged in k order.  Returns {"image": [H, W, 3] in generateImg's layout,
+        "counts": [H, W, 3] = (surface, emitter, miss) samples per pixel, "lit": [H, W] surface samples whose lookup found anything}.
+        workspace_rays bounds the rays in flight (0: the library's default); it does not change the result."""
+        if not isinstance(samples, numbers.Integral) or not -2 ** 31 <= samples < 2 ** 31:
+            raise ValueError("samples must be a 32-bit integer")
+        if not isinstance(workspace_rays, numbers.Integral) or not -2 ** 63 <= workspace_rays < 2 ** 63:
+            raise ValueError("workspace_rays must be a 64-bit integer")
+        s = self._baked_source(source)
+        fp = BakedFrameParams(int(samples), _baked_flags(face_viewer, lighting_only), int(seed), int(workspace_rays), (C.c_int32 * 2)(0, 0))
+        img = np.zeros((self.height, self.width, 3))
+        counts, lit = np.zeros((self.height, self.width, 3), dtype=np.int32), np.zeros((self.height, self.width), dtype=np.int32)
+        check(lib().mcpt_render_baked(self._h, C.byref(s), C.byref(fp), _p(img, C.c_double), _p(counts, C.c_int32), _p(lit, C.c_int32),
+                                      C.byref(stats) if stats is not None else None))
+        return {"image": img, "counts": counts, "lit": lit}
+
+    def render_baked_device(self, source_struct, d_img_ptr, samples=1, seed=0, face_viewer=False, lighting_only=False, workspace_rays=0,
+                            d_counts_ptr=None, d_lit_ptr=None, stats=None, stream=None):
+        """The same into a caller-owned device buffer on `stream` (mcpt_render_baked_device): source_struct a BakedSource of device
+        pointers.  Returns without waiting when stats is None."""
+        fp = BakedFrameParams(int(samples), _baked_flags(face_viewer, lighting_only), int(seed), int(workspace_rays), (C.c_int32 * 2)(0, 0))
+        check(lib().mcpt_render_baked_device(self._h, C.byref(source_struct), C.byref(fp), _dp(d_img_ptr),
+                                             _dp(d_counts_ptr), _dp(d_lit_ptr),
+                                             C.byref(stats) if stats is not None else None, _dp(stream)))
 
     def set_environment(self, rgb=None, scale=1.0):
         """The environment light of every later frame, sample_radiance and progressive handle created after it (mcpt_device_set_environment):

@@ -14,6 +14,7 @@
 //   lightmap_denoise_api.cpp  the lightmap denoiser: a chart-aware a-trous filter of an irradiance map, then the baker's dilation
 //   volume_api.cpp    irradiance volumes: a probe grid's points, its bake through the probe query, the lookup between its probes
 //   visibility_api.cpp  probe visibility: the octahedral bin, the depth-moment bake of a probe list or grid, the visibility-weighted lookup
+//   baked_api.cpp     baked frames: the lightmap's lookup by chart coordinate, baked radiance along a caller's rays, frames lit by a bake
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -241,6 +242,15 @@ struct mcpt_device {
         mcpt::Event done;
     };
     std::unique_ptr<Visibility> vis;
+    // baked frames (baked_api.cpp): the rays of a chunk, their closest hits and the chunk's shaded samples, made by the first call and grown
+    // to the largest chunk so far, 116 bytes per ray.  A device-form call returns with its fold enqueued, so the workspace is not a local
+    // of the call; `done` is recorded behind a call's last kernel and waited for before the next one writes here.
+    struct Baked {
+        mcpt::DevBuf<double> rays6, t, p, rad;          // [rays][6], [rays], [rays][3], [rays][3]
+        mcpt::DevBuf<int32_t> leaf, kind, lit;          // [rays]
+        mcpt::Event done;
+    };
+    std::unique_ptr<Baked> baked;
 };
 
 // The helpers below are the library's own: none of them is exported from libmcpt.so.
@@ -339,6 +349,9 @@ int volume_grid_check(const mcpt_volume_grid* g);   // what every call refuses o
 int volume_arrays_check(const mcpt_volume_grid& g, const double* sh27, const double* q6, int64_t n);
 // a failed allocation of a workspace or a copy: MCPT_ERR_NOMEM when the memory is not there, and the device stays usable
 int volume_alloc_result(hipError_t e, const char* what, size_t bytes);
+
+// ---- visibility_api.cpp (shared with baked_api.cpp)
+int volume_visibility_check(const mcpt_volume_visibility* v);   // what every visibility-weighted lookup refuses of its knobs, in the struct's field order
 
 // ---- lightmap_api.cpp
 namespace mcpt { struct LightmapWork; }

@@ -37,11 +37,9 @@ static int bake_check(const mcpt_visibility_params* p, int64_t n, const void* p3
     return MCPT_OK;
 }
 
-// what every form of the lookup refuses without looking at the arrays
-static int lookup_check(const mcpt_volume_grid* g, const mcpt_volume_visibility* v, const void* sh27, const void* moments, const void* q6, int64_t n,
-                        const void* e3)
+// what every visibility-weighted lookup refuses of its knobs, in the struct's field order
+int volume_visibility_check(const mcpt_volume_visibility* v)
 {
-    if (const int rc = volume_grid_check(g)) return rc;
     if (!v) return fail(MCPT_ERR_ARG, "null volume visibility");
     if (v->res < 1 || v->res > 16) return fail(MCPT_ERR_ARG, "res must be in 1 .. 16");
     if (v->flags != 0) return fail(MCPT_ERR_ARG, "mcpt_volume_visibility.flags must be 0");
@@ -51,6 +49,15 @@ static int lookup_check(const mcpt_volume_grid* g, const mcpt_volume_visibility*
         return fail(MCPT_ERR_ARG, "min_visibility must be in [0, 1]");
     for (int i = 0; i < 4; i++)
         if (v->reserved[i] != 0) return fail(MCPT_ERR_ARG, "mcpt_volume_visibility.reserved must be 0");
+    return MCPT_OK;
+}
+
+// what every form of the lookup refuses without looking at the arrays
+static int lookup_check(const mcpt_volume_grid* g, const mcpt_volume_visibility* v, const void* sh27, const void* moments, const void* q6, int64_t n,
+                        const void* e3)
+{
+    if (const int rc = volume_grid_check(g)) return rc;
+    if (const int rc = volume_visibility_check(v)) return rc;
     if (n < 0 || n > kInt32Max) return fail(MCPT_ERR_ARG, "the number of receivers must be in 0 .. 2^31 - 1");
     if (n > 0 && (!sh27 || !moments || !q6 || !e3)) return fail(MCPT_ERR_ARG, "null coefficients, moments, receiver list or irradiance");
     return MCPT_OK;
