@@ -1399,6 +1399,103 @@ int mcpt_render_baked(mcpt_device*, const mcpt_baked_source*, const mcpt_baked_f
 int mcpt_render_baked_device(mcpt_device*, const mcpt_baked_source*, const mcpt_baked_frame_params*,
                              double* d_img, int32_t* d_counts3, int32_t* d_lit, mcpt_stats*, void* stream);
 
+/* ---- reflection probes (since the reflection-probe change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* A REFLECTION PROBE is a point in free space that holds an R x R octahedral map of the radiance arriving there.  A CHAIN is 1 to 8 maps
+ * filtered from it with Phong lobes cos^ns of chosen integer exponents -- the lobe RT_SPECULAR draws from, which is radially symmetric
+ * about the mirror direction, so the filtered map is exactly what a glossy surface of that exponent sees; there is no split-sum
+ * approximation.  A LOOKUP answers "the radiance from direction d for a lobe of exponent x".  fp64, no contraction, IEEE division, every
+ * expression and sum in the order written; every output is one lane's fixed-order sum: the same bits on the host and on the GPU, whatever
+ * the launch shape and the chunking.
+ *   encode   : direction (x, y, z) of any non-zero finite length -> (s, t) in [0, 1]^2, mcpt_visibility_bin's map continued:
+ *                l = (|x| + |y|) + |z|, u = x / l, v = y / l;
+ *                z < 0.0: (u, v) = ((1.0 - |v|) * (u >= 0.0 ? 1.0 : -1.0), (1.0 - |u|) * (v >= 0.0 ? 1.0 : -1.0)), from the old u and v;
+ *                s = u * 0.5 + 0.5, t = v * 0.5 + 0.5.
+ *   decode   : (s, t) -> d: u = 2.0 * s - 1.0, v = 2.0 * t - 1.0, z = (1.0 - |u|) - |v|; z < 0.0: the same fold of (u, v);
+ *                d = (u, v, z) / sqrt((u u + v v) + z z).
+ *   texels   : texel b = y * R + x has its centre at ((x + 0.5) / R, (y + 0.5) / R); d_b = decode(centre);
+ *                w_b = ((2.0 / R) * (2.0 / R)) / (n2 * sqrt(n2)), n2 = (u u + v v) + z z of the centre's folded, unnormalised (u, v, z): the
+ *                midpoint-rule solid angle du dv / |p|^3.  mcpt_reflection_texels(res, d3, w) gives both for res in 1 .. 256 (host, no
+ *                device; either pointer may be NULL).  mcpt_visibility_bin(d_b, R) == b for R in 1 .. 16.
+ *   wrap     : a tap (x, y) with x, y in -1 .. R: (1) if x < 0 or x >= R: x = x < 0 ? -1 - x : 2R - 1 - x and y = R - 1 - y; (2) then the
+ *                same test on y, with x = R - 1 - x.  All four edges of the square are seams of the lower hemisphere, all four corners
+ *                the direction (0, 0, -1).
+ *   ipow     : ipow(c, n), integer n >= 0, by binary squaring: r = 1.0, b = c; while n > 0: if n & 1: r = r * b; n >>= 1; if n: b = b * b.
+ *                There is no pow.
+ *   bake     : mcpt_bake_reflection*, n probes p3[n][3], S = spp samples per texel.  Sample j of texel b of probe i is entry
+ *                e = (i * R * R + b) * S + j.  Its RNG id is id_base[i] + b * S + j (id_base == NULL: i * R * R * S) and its sample index
+ *                k = sample_base for every entry; u0, u1 = words 0 and 1 of the camera-uniform block uniform(seed, id, k, depth 0xFFFF,
+ *                slot 0..3), which MCPT_QUERY_HEMISPHERE draws from and MCPT_QUERY_RAY does not: nothing collides;
+ *                d = decode((x + u0) / R, (y + u1) / R), o = p_i itself, no offset (a probe sits in free space).
+ *                A BAKE IS, BIT FOR BIT, mcpt_query_radiance_device OVER THESE RAYS -- kind MCPT_QUERY_RAY, spp = 1, ids = the entries' ids,
+ *                the same sample_base, seed and flags -- FOLDED PER TEXEL in j order with the query's own expressions: s1 += x,
+ *                s2 += x * x, radiance = s1 / S, stderr = 0 when S < 2, else sqrt(max((s2 - s1 * s1 / S) / (S - 1), 0) / S); hits[b] = the
+ *                samples whose ray hit anything.  (An id per sample keeps the paths of a texel's samples independent; a ray-kind query
+ *                with spp > 1 would retrace one ray.)  Environment, light sampling, trace mode, motion (key 0) and concurrency are the
+ *                query's rules, word for word.  radiance [n][R * R][3] is required; stderr [n][R * R][3] and hits [n][R * R] may be NULL.
+ *                stats: rays_primary = samples = n * R * R * S; the other counters are the queries', summed over the chunks.
+ *   chunks   : the bake works in chunks of whole texels: at most workspace_rays rays and at least one texel each; 0 selects 4 194 304
+ *                rays.  The workspace holds 80 bytes per ray of the largest chunk so far.  THE RESULT DOES NOT DEPEND ON THE CHUNKING.
+ *   test seam: mcpt_reflection_rays gives rays6[m][6] and ids[m] of the listed entries entry[m] (host pointers), made by the bake's own
+ *                device function.
+ *   chain    : mcpt_reflection_chain: res = the source map's R; num_levels in 1 .. 8; level_res[l] in 1 .. 256; level_ns[l] in
+ *                0 .. 65535, strictly descending; unused slots 0.  Storage chain[n][T][3], T = sum of level_res[l]^2; level l starts at
+ *                texel sum_{m < l} level_res[m]^2.
+ *   prefilter: mcpt_reflection_prefilter*.  For output texel o of level l with centre direction r and ns = level_ns[l], over the source
+ *                texels b in ascending order: c = (r.x d_b.x + r.y d_b.y) + r.z d_b.z; a texel with c > 0.0 contributes
+ *                g = w_b * ipow(c, ns), W += g, A_ch += g * L_b[ch]; the others contribute nothing.  out = W > 0.0 ? A / W : +0.0.
+ *                W == 0 happens: a 1 x 1 source lies in the upper hemisphere, and cos^65535 underflows between coarse texels.
+ *   lookup   : mcpt_reflection_lookup*.  Receiver q has a probe index probe[q], a direction d3[q] of any non-zero finite length and an
+ *                exponent x[q], finite and >= 0.  With wt(a) = 1.0 / sqrt(a + 1.0): one level, or x >= ns[0]: level 0 alone;
+ *                x <= ns[L - 1]: the last level alone; otherwise l with ns[l] >= x > ns[l + 1],
+ *                a = (wt(x) - wt(ns[l])) / (wt(ns[l + 1]) - wt(ns[l])); a == 0.0: level l alone, otherwise
+ *                value = (1.0 - a) * v_l + a * v_{l+1} per channel.  Hence AN x EQUAL TO A LEVEL'S EXPONENT READS THAT LEVEL ALONE.
+ *                Inside a level of size R: (s, t) = encode(d), a = s * R - 0.5, b = t * R - 0.5, each clamped to [-1, R - 0.5] IN DOUBLE
+ *                before any conversion to int (a = a > -1.0 ? a : -1.0, then a = a < R - 0.5 ? a : R - 0.5: a NaN takes -1).  A direction
+ *                a caller may give has a in [-0.5, R - 0.5] already: half a texel beyond a border the tap across the seam weighs as
+ *                much as the border's own, at all four borders alike, which is what makes the lookup continuous across the seams.
+ *                x0 = floor(a), fx = a - x0, y0 and fy likewise; the taps (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1) go
+ *                through the wrap; v = ((w00 m00 + w10 m10) + w01 m01) + w11 m11 with w00 = (1 - fx)(1 - fy), w10 = fx (1 - fy),
+ *                w01 = (1 - fx) fy, w11 = fx fy.  In the device form a probe[q] outside 0 .. n - 1 gives +0.0.
+ * mcpt_reflection_texels, mcpt_reflection_prefilter_host and mcpt_reflection_lookup_host run on the CPU and need no device.  The
+ * host-pointer forms are synchronous and copy in and out around the _device forms.  The _device forms take device pointers throughout
+ * (parameters and chain are always host structs) and enqueue on `stream`.  mcpt_bake_reflection_device first waits for the event behind
+ * the device's previous reflection bake and returns without waiting when stats == NULL; otherwise it is a query call: it uses the
+ * device's frame slot 0 and first waits for the device's frames in flight.  The prefilter and the lookup never wait and allocate
+ * nothing; THEY DO NOT LOOK AT THEIR ARRAYS and read nothing outside their tables.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE, in this order).  The bake and mcpt_reflection_rays: NULL parameters; spp < 1;
+ * sample_base < 0; res outside 1 .. 256; a flag other than 0 or MCPT_RENDER_MEGAKERNEL; workspace_rays < 0; reserved != 0; n < 0;
+ * n * R * R * S > 2^31 - 1; the bake: NULL p3 or radiance with n > 0; the seam: m outside 0 .. 2^31 - 1, a NULL array with m > 0, an
+ * entry outside 0 .. n * R * R * S - 1; the host-pointer forms: a position that is not finite, a negative id_base[i],
+ * id_base[i] + R * R * S - 1 > 2^31 - 1 (the device form cannot look at id_base: its caller keeps every id within 0 .. 2^31 - 1).
+ * A chain: NULL; res outside 1 .. 256; num_levels outside 1 .. 8; a level_res outside 1 .. 256 or an unused slot != 0; a level_ns
+ * outside 0 .. 65535, not strictly descending, or an unused slot != 0; reserved != 0.  The prefilter: the chain; n < 0 or n > 2^31 - 1;
+ * NULL radiance or chain with n > 0; the host-pointer forms: a radiance that is not finite.  The lookup: the chain; n, then m, outside
+ * 0 .. 2^31 - 1; a NULL array with m > 0; the host-pointer forms: a chain value that is not finite, then per receiver a direction
+ * that is zero, not finite or whose l overflows, a probe index outside 0 .. n - 1, an x that is not finite or < 0.
+ * mcpt_reflection_texels: res outside 1 .. 256.  n == 0 (the lookup: m == 0): MCPT_OK, nothing is launched.  A workspace or a copy
+ * that cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable.
+ * Not covered: a specular term in baked frames; choosing or blending probes by position; parallax correction; GGX or other lobes, and
+ * real-valued level exponents; fp32 or fp16 storage; adaptive stopping; the multi-device group and render_scene. */
+typedef struct { int32_t spp, sample_base; uint64_t seed; int32_t res, flags; int64_t workspace_rays; int32_t reserved[4]; } mcpt_reflection_params;
+typedef struct { int32_t res, num_levels; int32_t level_res[8], level_ns[8]; int32_t reserved[4]; } mcpt_reflection_chain;
+int mcpt_reflection_texels(int32_t res, double* d3, double* w);
+int mcpt_bake_reflection(mcpt_device*, const double* p3, const int32_t* id_base, int64_t n, const mcpt_reflection_params*,
+                         double* radiance, double* stderr3, int32_t* hits, mcpt_stats*);
+int mcpt_bake_reflection_device(mcpt_device*, const double* d_p3, const int32_t* d_id_base, int64_t n, const mcpt_reflection_params*,
+                                double* d_radiance, double* d_stderr3, int32_t* d_hits, mcpt_stats*, void* stream);
+int mcpt_reflection_rays(mcpt_device*, const double* p3, const int32_t* id_base, int64_t n, const mcpt_reflection_params*,
+                         const int64_t* entry, int64_t m, double* rays6, int32_t* ids);
+int mcpt_reflection_prefilter_host(const mcpt_reflection_chain*, const double* radiance, int64_t n, double* chain);
+int mcpt_reflection_prefilter(mcpt_device*, const mcpt_reflection_chain*, const double* radiance, int64_t n, double* chain);
+int mcpt_reflection_prefilter_device(mcpt_device*, const mcpt_reflection_chain*, const double* d_radiance, int64_t n, double* d_chain,
+                                     void* stream);
+int mcpt_reflection_lookup_host(const mcpt_reflection_chain*, const double* chain, int64_t n, const int32_t* probe, const double* d3,
+                                const double* x, int64_t m, double* out3);
+int mcpt_reflection_lookup(mcpt_device*, const mcpt_reflection_chain*, const double* chain, int64_t n, const int32_t* probe,
+                           const double* d3, const double* x, int64_t m, double* out3);
+int mcpt_reflection_lookup_device(mcpt_device*, const mcpt_reflection_chain*, const double* d_chain, int64_t n, const int32_t* d_probe,
+                                  const double* d_d3, const double* d_x, int64_t m, double* d_out3, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

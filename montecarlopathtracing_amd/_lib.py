@@ -220,6 +220,24 @@ class BakedFrameParams(C.Structure):
     _fields_ = [("samples", C.c_int32), ("flags", C.c_int32), ("seed", C.c_uint64), ("workspace_rays", C.c_int64), ("reserved", C.c_int32 * 2)]
 
 
+class ReflectionParams(C.Structure):
+    """mcpt_reflection_params: samples per texel, the sample index, seed, the octahedral map's resolution, flags, and the workspace's size
+    in rays (0: the default)"""
+    _fields_ = [("spp", C.c_int32), ("sample_base", C.c_int32), ("seed", C.c_uint64), ("res", C.c_int32), ("flags", C.c_int32),
+                ("workspace_rays", C.c_int64), ("reserved", C.c_int32 * 4)]
+
+
+class ReflectionChain(C.Structure):
+    """mcpt_reflection_chain: the source map's resolution and the resolution and Phong exponent of each of 1 .. 8 prefiltered levels
+    (api.reflection_chain makes one)"""
+    _fields_ = [("res", C.c_int32), ("num_levels", C.c_int32), ("level_res", C.c_int32 * 8), ("level_ns", C.c_int32 * 8),
+                ("reserved", C.c_int32 * 4)]
+
+    @property
+    def num_texels(self):
+        return sum(self.level_res[l] ** 2 for l in range(max(0, min(self.num_levels, 8))))
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -266,6 +284,9 @@ EXPORTS = [
     "mcpt_volume_irradiance_visible_host", "mcpt_volume_irradiance_visible", "mcpt_volume_irradiance_visible_device",
     "mcpt_lightmap_irradiance_host", "mcpt_lightmap_irradiance", "mcpt_lightmap_irradiance_device",
     "mcpt_baked_radiance", "mcpt_baked_radiance_device", "mcpt_render_baked", "mcpt_render_baked_device",
+    "mcpt_reflection_texels", "mcpt_bake_reflection", "mcpt_bake_reflection_device", "mcpt_reflection_rays",
+    "mcpt_reflection_prefilter_host", "mcpt_reflection_prefilter", "mcpt_reflection_prefilter_device",
+    "mcpt_reflection_lookup_host", "mcpt_reflection_lookup", "mcpt_reflection_lookup_device",
 ]
 
 
@@ -484,6 +505,17 @@ def lib():
     L.mcpt_baked_radiance_device.argtypes = [P, BS, P, C.c_int64, C.c_int32, BO, C.POINTER(Stats), P]
     L.mcpt_render_baked.argtypes = [P, BS, BF, D, I32, I32, C.POINTER(Stats)]
     L.mcpt_render_baked_device.argtypes = [P, BS, BF, P, P, P, C.POINTER(Stats), P]
+    RP, RC = C.POINTER(ReflectionParams), C.POINTER(ReflectionChain)
+    L.mcpt_reflection_texels.argtypes = [C.c_int32, D, D]
+    L.mcpt_bake_reflection.argtypes = [P, D, I32, C.c_int64, RP, D, D, I32, C.POINTER(Stats)]
+    L.mcpt_bake_reflection_device.argtypes = [P, P, P, C.c_int64, RP, P, P, P, C.POINTER(Stats), P]
+    L.mcpt_reflection_rays.argtypes = [P, D, I32, C.c_int64, RP, I64, C.c_int64, D, I32]
+    L.mcpt_reflection_prefilter_host.argtypes = [RC, D, C.c_int64, D]
+    L.mcpt_reflection_prefilter.argtypes = [P, RC, D, C.c_int64, D]
+    L.mcpt_reflection_prefilter_device.argtypes = [P, RC, P, C.c_int64, P, P]
+    L.mcpt_reflection_lookup_host.argtypes = [RC, D, C.c_int64, I32, D, D, C.c_int64, D]
+    L.mcpt_reflection_lookup.argtypes = [P, RC, D, C.c_int64, I32, D, D, C.c_int64, D]
+    L.mcpt_reflection_lookup_device.argtypes = [P, RC, P, C.c_int64, P, P, P, C.c_int64, P, P]
     _lib = L
     return L
 

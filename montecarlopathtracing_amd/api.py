@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, ReflectionParams, ReflectionChain, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -334,6 +334,87 @@ def baked_lightmap(E, uv=None, owner=None):
     None) as bake_lightmap returns them, uv (num_faces, 6) the chart it was baked under, None: the scene's own vt."""
     E, _, owner = _lightmap_args(E, np.zeros((0, 2)), owner)
     return _Baked(BAKED_LIGHTMAP, E=E, uv=_chart(uv) if uv is not None else None, owner=owner)
+
+
+def _int32(**values):
+    for name, v in values.items():
+        if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("%s must be a 32-bit integer" % name)
+
+
+def reflection_chain(res, levels):
+    """An mcpt_reflection_chain (mcpt.h: reflection probes) for prefilter_reflection and reflection_lookup: res is the source map's
+    resolution, levels 1 to 8 pairs (level_res, ns) -- the level's resolution and the integer exponent of its Phong lobe, exponents
+    strictly descending.  The library judges the values."""
+    levels = [tuple(l) for l in levels]
+    if len(levels) > 8 or any(len(l) != 2 for l in levels):
+        raise ValueError("levels must be at most 8 pairs (level_res, ns)")
+    _int32(res=res, **{"%s of level %d" % (name, i): v for i, l in enumerate(levels) for name, v in zip(("level_res", "ns"), l)})
+    c = ReflectionChain()
+    c.res, c.num_levels = int(res), len(levels)
+    for i, (r, ns) in enumerate(levels):
+        c.level_res[i], c.level_ns[i] = int(r), int(ns)
+    return c
+
+
+def reflection_texels(res):
+    """The texels of a res x res octahedral map (mcpt_reflection_texels; no device): (d [res * res, 3], w [res * res]), the centre
+    directions and the midpoint-rule solid angles, texel b = y * res + x."""
+    _int32(res=res)
+    n = int(res) ** 2 if 1 <= res <= 256 else 0             # (the library refuses any other res)
+    d, w = np.zeros((n, 3)), np.zeros(n)
+    check(lib().mcpt_reflection_texels(int(res), _p(d, C.c_double), _p(w, C.c_double)))
+    return d, w
+
+
+def _reflection_maps(chain_desc, radiance):
+    if not isinstance(chain_desc, ReflectionChain):
+        raise ValueError("the chain must be a ReflectionChain (reflection_chain makes one)")
+    texels = chain_desc.res ** 2 if 1 <= chain_desc.res <= 256 else 0
+    radiance = np.ascontiguousarray(radiance, dtype=np.float64)
+    if radiance.ndim != 3 or radiance.shape[1:] != (texels, 3):
+        raise ValueError("radiance must have shape (n, %d, 3), not %r" % (texels, radiance.shape))
+    return radiance
+
+
+def _reflection_receivers(chain_desc, chain, probe, dirs, ns):
+    if not isinstance(chain_desc, ReflectionChain):
+        raise ValueError("the chain must be a ReflectionChain (reflection_chain makes one)")
+    chain = np.ascontiguousarray(chain, dtype=np.float64)
+    if chain.ndim != 3 or chain.shape[1:] != (chain_desc.num_texels, 3):
+        raise ValueError("chain must have shape (n, %d, 3), not %r" % (chain_desc.num_texels, chain.shape))
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64)
+    if dirs.ndim != 2 or dirs.shape[1] != 3:
+        raise ValueError("dirs must have shape (m, 3), not %r" % (dirs.shape,))
+    m = dirs.shape[0]
+    probe = np.asarray(probe)
+    if probe.dtype.kind not in "iu" or probe.shape != (m,):
+        raise ValueError("probe must be %d integers" % m)
+    if probe.size and (int(probe.min()) < -2 ** 31 or int(probe.max()) >= 2 ** 31):
+        raise ValueError("probe indices must fit 32 bits")
+    ns = np.ascontiguousarray(np.broadcast_to(np.asarray(ns, dtype=np.float64), (m,)))
+    return chain, np.ascontiguousarray(probe, dtype=np.int32), dirs, ns
+
+
+def reflection_prefilter_host(chain_desc, radiance):
+    """The prefilter on the CPU (mcpt_reflection_prefilter_host; no device): radiance [n, res * res, 3] as bake_reflection_probes
+    returns it -> chain [n, T, 3], every level the map convolved with the level's Phong lobe, level l at texels
+    sum(level_res[:l] ** 2) onwards."""
+    radiance = _reflection_maps(chain_desc, radiance)
+    chain = np.zeros((radiance.shape[0], chain_desc.num_texels, 3))
+    check(lib().mcpt_reflection_prefilter_host(C.byref(chain_desc), _p(radiance, C.c_double), radiance.shape[0], _p(chain, C.c_double)))
+    return chain
+
+
+def reflection_lookup_host(chain_desc, chain, probe, dirs, ns):
+    """The lookup on the CPU (mcpt_reflection_lookup_host; no device): for receiver q the radiance chain[probe[q]] holds for direction
+    dirs[q] (any non-zero length) under a lobe of exponent ns[q] (a number or an array, finite and >= 0) -- bilinear inside a level
+    across the octahedral seams, blended between the two levels whose exponents enclose ns[q].  Returns [m, 3]."""
+    chain, probe, dirs, ns = _reflection_receivers(chain_desc, chain, probe, dirs, ns)
+    out = np.zeros((dirs.shape[0], 3))
+    check(lib().mcpt_reflection_lookup_host(C.byref(chain_desc), _p(chain, C.c_double), chain.shape[0], _p(probe, C.c_int32), _p(dirs, C.c_double),
+                                            _p(ns, C.c_double), dirs.shape[0], _p(out, C.c_double)))
+    return out
 
 
 def _baked_flags(face_viewer, lighting_only):
@@ -1172,6 +1253,90 @@ class Device:
         check(lib().mcpt_render_baked_device(self._h, C.byref(source_struct), C.byref(fp), _dp(d_img_ptr),
                                              _dp(d_counts_ptr), _dp(d_lit_ptr),
                                              C.byref(stats) if stats is not None else None, _dp(stream)))
+
+    @staticmethod
+    def _reflection_params(res, spp, seed, sample_base, workspace_rays, flags):
+        _int32(res=res, spp=spp, sample_base=sample_base, flags=flags)
+        if not isinstance(workspace_rays, numbers.Integral) or not -2 ** 63 <= workspace_rays < 2 ** 63:
+            raise ValueError("workspace_rays must be a 64-bit integer")
+        return ReflectionParams(int(spp), int(sample_base), int(seed), int(res), int(flags), int(workspace_rays), (C.c_int32 * 4)(0, 0, 0, 0))
+
+    @staticmethod
+    def _id_base(id_base, n):
+        if id_base is None:
+            return None
+        id_base = np.asarray(id_base)
+        if id_base.dtype.kind not in "iu" or id_base.shape != (n,):
+            raise ValueError("id_base must be %d integers" % n)
+        if id_base.size and (int(id_base.min()) < -2 ** 31 or int(id_base.max()) >= 2 ** 31):
+            raise ValueError("id_base must fit 32 bits")
+        return np.ascontiguousarray(id_base, dtype=np.int32)
+
+    def bake_reflection_probes(self, points, res, spp, seed=0, sample_base=0, id_base=None, workspace_rays=0, flags=0, stats=None):
+        """Reflection probes (mcpt_bake_reflection): for each of points (n, 3) a res x res octahedral map of the path-traced radiance
+        arriving there, spp jittered rays per texel -- radiance() with spp = 1 over reflection_rays(), folded per texel, bit for bit.
+        Sample j of texel b of probe i has the RNG id id_base[i] + b * spp + j (id_base None: i * res * res * spp) and the sample index
+        sample_base.  Returns (radiance [n, res * res, 3], stderr [n, res * res, 3], hits [n, res * res]); prefilter_reflection takes
+        the first.  workspace_rays bounds the rays in flight (0: the library's default); it does not change the result."""
+        p, _ = self._probe_list(points, None)
+        rp = self._reflection_params(res, spp, seed, sample_base, workspace_rays, flags)
+        n, texels = p.shape[0], int(res) ** 2 if 1 <= res <= 256 else 0      # (the library refuses any other res)
+        id_base = self._id_base(id_base, n)
+        rad, err, hits = np.zeros((n, texels, 3)), np.zeros((n, texels, 3)), np.zeros((n, texels), dtype=np.int32)
+        check(lib().mcpt_bake_reflection(self._h, _p(p, C.c_double), _p(id_base, C.c_int32), n, C.byref(rp), _p(rad, C.c_double), _p(err, C.c_double),
+                                         _p(hits, C.c_int32), C.byref(stats) if stats is not None else None))
+        return rad, err, hits
+
+    def bake_reflection_probes_device(self, d_points_ptr, n, d_radiance_ptr, res, spp, seed=0, sample_base=0, d_id_base_ptr=None, workspace_rays=0, flags=0,
+                                      d_stderr_ptr=None, d_hits_ptr=None, stats=None, stream=None):
+        """The same between caller-owned device buffers on `stream` (mcpt_bake_reflection_device).  Returns without waiting when stats
+        is None."""
+        rp = self._reflection_params(res, spp, seed, sample_base, workspace_rays, flags)
+        check(lib().mcpt_bake_reflection_device(self._h, _dp(d_points_ptr), _dp(d_id_base_ptr), int(n), C.byref(rp), _dp(d_radiance_ptr), _dp(d_stderr_ptr),
+                                                _dp(d_hits_ptr), C.byref(stats) if stats is not None else None, _dp(stream)))
+
+    def reflection_rays(self, points, res, spp, entries, seed=0, sample_base=0, id_base=None):
+        """test seam (mcpt_reflection_rays): (rays [m, 6] = origin, direction, ids [m]) of the listed entries of
+        bake_reflection_probes(points, res, spp, ...); entry (i * res * res + b) * spp + j is sample j of texel b of probe i."""
+        p, _ = self._probe_list(points, None)
+        rp = self._reflection_params(res, spp, seed, sample_base, 0, 0)
+        id_base = self._id_base(id_base, p.shape[0])
+        e = np.asarray(entries)
+        if e.dtype.kind not in "iu" or e.ndim != 1:
+            raise ValueError("entries must be a list of integers")
+        e = np.ascontiguousarray(e, dtype=np.int64)
+        rays, ids = np.zeros((e.shape[0], 6)), np.zeros(e.shape[0], dtype=np.int32)
+        check(lib().mcpt_reflection_rays(self._h, _p(p, C.c_double), _p(id_base, C.c_int32), p.shape[0], C.byref(rp), _p(e, C.c_int64), e.shape[0],
+                                         _p(rays, C.c_double), _p(ids, C.c_int32)))
+        return rays, ids
+
+    def prefilter_reflection(self, radiance, res, levels):
+        """The prefilter on the GPU (mcpt_reflection_prefilter): radiance [n, res * res, 3] convolved with the Phong lobe of every
+        (level_res, ns) of levels -- reflection_prefilter_host's answer, bit for bit.  Returns (chain_desc, chain [n, T, 3]) for
+        reflection_lookup."""
+        c = reflection_chain(res, levels)
+        radiance = _reflection_maps(c, radiance)
+        chain = np.zeros((radiance.shape[0], c.num_texels, 3))
+        check(lib().mcpt_reflection_prefilter(self._h, C.byref(c), _p(radiance, C.c_double), radiance.shape[0], _p(chain, C.c_double)))
+        return c, chain
+
+    def prefilter_reflection_device(self, chain_desc, d_radiance_ptr, n, d_chain_ptr, stream=None):
+        """The same between caller-owned device buffers on `stream` (mcpt_reflection_prefilter_device); never waits."""
+        check(lib().mcpt_reflection_prefilter_device(self._h, C.byref(chain_desc), _dp(d_radiance_ptr), int(n), _dp(d_chain_ptr), _dp(stream)))
+
+    def reflection_lookup(self, chain_desc, chain, probe, dirs, ns):
+        """The lookup on the GPU (mcpt_reflection_lookup): reflection_lookup_host's arguments and answer, bit for bit."""
+        chain, probe, dirs, ns = _reflection_receivers(chain_desc, chain, probe, dirs, ns)
+        out = np.zeros((dirs.shape[0], 3))
+        check(lib().mcpt_reflection_lookup(self._h, C.byref(chain_desc), _p(chain, C.c_double), chain.shape[0], _p(probe, C.c_int32), _p(dirs, C.c_double),
+                                           _p(ns, C.c_double), dirs.shape[0], _p(out, C.c_double)))
+        return out
+
+    def reflection_lookup_device(self, chain_desc, d_chain_ptr, n, d_probe_ptr, d_dirs_ptr, d_ns_ptr, m, d_out_ptr, stream=None):
+        """The same between caller-owned device buffers on `stream` (mcpt_reflection_lookup_device); never waits.  A probe index outside
+        0 .. n - 1 gives +0.0."""
+        check(lib().mcpt_reflection_lookup_device(self._h, C.byref(chain_desc), _dp(d_chain_ptr), int(n), _dp(d_probe_ptr), _dp(d_dirs_ptr), _dp(d_ns_ptr),
+                                                  int(m), _dp(d_out_ptr), _dp(stream)))
 
     def set_environment(self, rgb=None, scale=1.0):
         """The environment light of every later frame, sample_radiance and progressive handle created after it (mcpt_device_set_environment):

@@ -15,6 +15,7 @@
 //   volume_api.cpp    irradiance volumes: a probe grid's points, its bake through the probe query, the lookup between its probes
 //   visibility_api.cpp  probe visibility: the octahedral bin, the depth-moment bake of a probe list or grid, the visibility-weighted lookup
 //   baked_api.cpp     baked frames: the lightmap's lookup by chart coordinate, baked radiance along a caller's rays, frames lit by a bake
+//   reflection_api.cpp  reflection probes: an octahedral radiance map per probe through the ray query, its Phong prefilter, the chain's lookup
 //   render_scene.cpp  output writers, checkpoints, render_scene
 #pragma once
 #include <hip/hip_runtime_api.h>
@@ -251,6 +252,15 @@ struct mcpt_device {
         mcpt::Event done;
     };
     std::unique_ptr<Baked> baked;
+    // reflection probes (reflection_api.cpp): the rays of a chunk of texels with their ids, and the query's answers to them, made by the
+    // first bake and grown to the largest chunk so far, 80 bytes per ray.  A device-form bake returns with its fold enqueued, so the
+    // workspace is not a local of the call; `done` is recorded behind a bake's last kernel and waited for before the next one writes here.
+    struct Reflection {
+        mcpt::DevBuf<double> rays6, mean;               // [rays][6], [rays][3]
+        mcpt::DevBuf<int32_t> ids, hits;                // [rays]
+        mcpt::Event done;
+    };
+    std::unique_ptr<Reflection> refl;
 };
 
 // The helpers below are the library's own: none of them is exported from libmcpt.so.
