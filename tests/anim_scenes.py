@@ -29,6 +29,22 @@ def rigid(v, faces, degrees=30.0, shift=(0.05, 0.0, -0.04)):
     return out
 
 
+def mirror(v, faces):
+    """the faces `faces` reflected in the plane x = c through their centroid: the body keeps its place, and as every face keeps the order
+    of its vertices its winding turns inside out (a reflection turns (v1 - v2) x (v3 - v1) into minus its own mirror image)"""
+    out = v.copy()
+    p = out[faces].reshape(-1, 3)
+    c = p.mean(axis=0)
+    p[:, 0] = 2.0 * c[0] - p[:, 0]
+    out[faces] = p.reshape(-1, 9)
+    return out
+
+
+def face_normals(v):
+    """the faces' geometric normals as the loader and an update form them, (v1 - v2) x (v3 - v1), not normalised"""
+    return np.cross(v[:, 0:3] - v[:, 3:6], v[:, 6:9] - v[:, 0:3])
+
+
 def sine_field(v, amplitude=0.05, phase=0.0):
     """every vertex displaced by a sine field of `amplitude` x the scene's diagonal (a function of position: shared vertices stay shared)"""
     p = v.reshape(-1, 3)

@@ -180,6 +180,24 @@ def test_prefilter_is_the_host_form_bit_for_bit(mcpt, cornell, case):
         assert (~(got != 0).any(axis=2)).sum() > 0                  # the empty lobes of a 1 x 1 source: +0.0 from the kernel too
 
 
+def test_prefilter_past_one_launch_of_probes(mcpt, cornell):
+    """launch_reflection_prefilter cuts the probes into launches of 65 535 (blockIdx.y's limit) and offsets both pointers for the next
+    launch: 65 537 probes of a 1 x 1 source under levels of 2 x 2 and 1 x 1 texels -- 5 chain texels a probe, 7.9 MB -- leave two probes to
+    the second launch.  Every probe has a radiance of its own, so a probe read or written at another probe's place shows."""
+    n, R, levels = 65537, 1, [(2, 1), (1, 0)]
+    i = np.arange(n, dtype=np.float64)
+    L = np.stack([0.25 + i, 0.5 + 3.0 * i, 1.0 / (1.0 + i)], axis=1).reshape(n, 1, 3)
+    assert np.unique(L.reshape(n, 3), axis=0).shape[0] == n
+    c, got = cornell.prefilter_reflection(L, R, levels)
+    want = mcpt.reflection_prefilter_host(c, L)
+    assert got.shape == want.shape == (n, 5, 3) and got.nbytes < 8 * 2 ** 20
+    assert _same(got, want), int((_bits(got) != _bits(want)).sum())
+    for p in (n - 2, n - 1, 65534):                                 # the second launch's two probes, and the first launch's last
+        assert _same(got[p], want[p]) and (got[p, 4] > 0).all(), p
+    assert not _same(got[n - 1], got[1]) and not _same(got[n - 2], got[0])      # (not the first launch's probes once more)
+    assert len({tuple(r) for r in got[:, 4].tolist()}) == n                      # every probe's 1 x 1 level is its own
+
+
 # ---- lookup
 
 @pytest.mark.parametrize("case", range(len(LOOKUP_CASES)))

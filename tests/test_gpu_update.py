@@ -47,12 +47,12 @@ def source(name, tmp_factory):
     return (extra_scene_dir() if name == "glassroom" else SCENES), name
 
 
-def base(mcpt, name, tmp_factory):
-    """the scene, its vertices [n, 9], the faces' materials and the light materials"""
-    key = ("base", name)
+def base(mcpt, name, tmp_factory, size=(W, H)):
+    """the scene (at this file's frame size unless another is asked for), its vertices [n, 9], the faces' materials and the light materials"""
+    key = ("base", name) if size == (W, H) else ("base", name, size)
     if key not in _cache:
         d, f = source(name, tmp_factory)
-        sc = mcpt.Scene(d, f, width=W, height=H)
+        sc = mcpt.Scene(d, f, width=size[0], height=size[1])
         g, m, _ = sc.faces()
         lights = [sc.light(i)[2] for i in range(sc.info.num_lights)]
         _cache[key] = (sc, np.ascontiguousarray(g[:, :9]), m, lights)
@@ -73,6 +73,10 @@ def deform(mcpt, name, what, tmp_factory):
         for l in lights:
             counts[l] = 0
         return A.rigid(v, np.nonzero(m == int(np.argmax(counts)))[0])
+    if what == "mirror":
+        # the same object turned inside out where it stands
+        names = [sc.material(i)[0] for i in range(sc.info.num_materials)]
+        return A.mirror(v, np.nonzero(m == names.index("Table"))[0])
     if what == "sine":
         return A.sine_field(v, 0.05)
     if what == "lights":
@@ -93,9 +97,9 @@ def moved_files(mcpt, name, what, tmp_factory):
     return _cache[key], source(name, tmp_factory)[1]
 
 
-def fresh(mcpt, name, what, build, tmp_factory):
+def fresh(mcpt, name, what, build, tmp_factory, size=(W, H)):
     d, f = moved_files(mcpt, name, what, tmp_factory)
-    sc = mcpt.Scene(d, f, width=W, height=H)
+    sc = mcpt.Scene(d, f, width=size[0], height=size[1])
     return sc, mcpt.Device(sc, 0, build=build)
 
 

@@ -76,6 +76,37 @@ def test_exponent_is_minimal():
         assert ref[1] >= e and (ref[1] > e or (ref[2], ref[3]) == (ql, qh))
 
 
+def test_mirror_turns_a_body_inside_out(mcpt):
+    """anim_scenes.mirror on cornell-box's "Table" and on random triangles: for every mirrored face the sign of n . (face centroid - c), c the
+    body's centroid, is the opposite of the original's, where n = (v1 - v2) x (v3 - v1) is the normal the loader and an update store; the
+    body keeps its centroid and its extent; every other face keeps its bits"""
+    import anim_scenes as A
+    from conftest import SCENES
+    sc = mcpt.Scene(SCENES, "cornell-box", width=64, height=36)
+    g, m, _ = sc.faces()
+    names = [sc.material(i)[0] for i in range(sc.info.num_materials)]
+    table = np.nonzero(m == names.index("Table"))[0]
+    rng = np.random.default_rng(6)
+    soup = rng.normal(size=(300, 9))
+    for v, faces in ((np.ascontiguousarray(g[:, :9]), table), (soup, np.arange(0, 300, 3))):
+        w = A.mirror(v, faces)
+        rest = np.setdiff1d(np.arange(v.shape[0]), faces)
+        assert np.array_equal(w[rest].view(np.uint64), v[rest].view(np.uint64)) and not np.array_equal(w[faces], v[faces])
+        c = v[faces].reshape(-1, 3).mean(axis=0)
+        assert np.abs(w[faces].reshape(-1, 3).mean(axis=0) - c).max() <= 1e-12 * np.abs(v[faces]).max()
+        lo, hi = v[faces].reshape(-1, 3).min(axis=0), v[faces].reshape(-1, 3).max(axis=0)
+        wl, wh = w[faces].reshape(-1, 3).min(axis=0), w[faces].reshape(-1, 3).max(axis=0)
+        assert np.array_equal(wl[1:], lo[1:]) and np.array_equal(wh[1:], hi[1:])      # y and z untouched; x in [2c - hi, 2c - lo]
+        assert wl[0] == 2.0 * c[0] - hi[0] and wh[0] == 2.0 * c[0] - lo[0]
+        side = lambda x: (A.face_normals(x[faces]) * (x[faces].reshape(-1, 3, 3).mean(axis=1) - c)).sum(axis=1)
+        a, b = side(v), side(w)
+        decided = np.abs(a) > 1e-9 * np.abs(a).max()          # (a face whose plane holds c faces neither way)
+        assert decided.sum() > 0.9 * faces.size
+        assert np.array_equal(np.sign(b[decided]), -np.sign(a[decided]))
+        assert np.abs(a + b).max() <= 1e-9 * np.abs(a).max()
+    sc.close()
+
+
 def test_new_symbols_and_null_handles(mcpt):
     from montecarlopathtracing_amd import _lib
     L = mcpt.lib()
