@@ -37,29 +37,27 @@ int adaptive_params_check(const mcpt_adaptive_params* ap)
     return MCPT_OK;
 }
 
-// the workspace of a list of n queries on d, once the call before this one has left it
-static int ensure_work(mcpt_device* d, size_t n)
+// the workspace of a list of n queries on d for a call on st, once the call before this one has left it
+static int ensure_work(mcpt_device* d, size_t n, hipStream_t st, Lease& l)
 {
-    if (!d->aq) {
-        auto w = std::make_unique<mcpt_device::AdaptiveQuery>();
-        HIP_TRY(create(w->done, hipEventCreateWithFlags, hipEventDisableTiming));
-        HIP_TRY(w->h_total.alloc(1));
-        HIP_TRY(w->total.alloc(1));
-        d->aq = std::move(w);
-    }
+    const auto words = [](mcpt_device::AdaptiveQuery& w) -> int {
+        HIP_TRY(w.h_total.alloc(1));
+        HIP_TRY(w.total.alloc(1));
+        return MCPT_OK;
+    };
+    if (const int rc = lease(d->aq, st, l, words)) return rc;
     mcpt_device::AdaptiveQuery& w = *d->aq;
-    HIP_TRY(hipEventSynchronize(w.done.get()));
     const size_t blocks = size_t((n + 255) / 256);
-    HIP_TRY(w.mom.grow(n * 6));
-    HIP_TRY(w.hitcnt.grow(n));
-    HIP_TRY(w.cnt.grow(n));
-    HIP_TRY(w.sel[0].grow(n));
-    HIP_TRY(w.sel[1].grow(n));
-    HIP_TRY(w.ones.grow(n));
-    HIP_TRY(w.masks.grow(blocks * 4));
-    HIP_TRY(w.block_counts.grow(blocks));
-    HIP_TRY(w.block_offsets.grow(blocks));
-    return MCPT_OK;
+    const char* what = "the adaptive query's workspace";
+    if (const int rc = grow(w.mom, n * 6, what)) return rc;
+    if (const int rc = grow(w.hitcnt, n, what)) return rc;
+    if (const int rc = grow(w.cnt, n, what)) return rc;
+    if (const int rc = grow(w.sel[0], n, what)) return rc;
+    if (const int rc = grow(w.sel[1], n, what)) return rc;
+    if (const int rc = grow(w.ones, n, what)) return rc;
+    if (const int rc = grow(w.masks, blocks * 4, what)) return rc;
+    if (const int rc = grow(w.block_counts, blocks, what)) return rc;
+    return grow(w.block_offsets, blocks, what);
 }
 
 // the passes and the finishing kernel on st; the gates have been passed and the workspace is the call's
@@ -87,8 +85,8 @@ static int run_passes(mcpt_device* d, const DQuery& q, const int32_t* d_ids, int
         const double* pq6 = q.q6;
         const int32_t* pids = d_ids;
         if (j > 0) {
-            HIP_TRY(w.cq6.grow(size_t(active) * 6));
-            HIP_TRY(w.cids.grow(size_t(active)));
+            if (const int rc = grow(w.cq6, size_t(active) * 6, "the adaptive query's compact list")) return rc;
+            if (const int rc = grow(w.cids, size_t(active), "the adaptive query's compact list")) return rc;
             launch_aq_gather(q.q6, d_ids, w.sel[cur].get(), active, w.cq6.get(), w.cids.get(), st);
             HIP_TRY(hipGetLastError());
             pq6 = w.cq6.get(); pids = w.cids.get();
@@ -100,7 +98,7 @@ static int run_passes(mcpt_device* d, const DQuery& q, const int32_t* d_ids, int
         rp.spp = cnt;
         mcpt_stats piece{};
         if (const int rc = render_device_impl(d, r, PixelList{pids, active}, &rp, nullptr, stats ? &piece : nullptr, st, slot_used)) return rc;
-        if (stats) { add_counts(*stats, piece); stats->ms_trace += piece.ms_trace; stats->ms_total += piece.ms_total; }
+        if (stats) add_piece(*stats, piece);
         // which queries continue, and every active query's count: decided on the device over list positions (no miss rule: the hit bytes are ones)
         launch_adaptive_select(w.sel[cur].get(), int(active), w.mom.get(), w.ones.get(), k, min_spp, rel2, abs2, w.cnt.get(), w.masks.get(),
                                w.block_counts.get(), w.block_offsets.get(), w.total.get(), w.sel[cur ^ 1].get(), st);
@@ -121,24 +119,20 @@ static int run_passes(mcpt_device* d, const DQuery& q, const int32_t* d_ids, int
 int adaptive_query_device(mcpt_device* d, const DQuery& q, const int32_t* d_ids, int64_t n, int32_t spp, int32_t sample_base, uint64_t seed, int32_t flags,
                           const mcpt_adaptive_params& ap, int32_t* d_counts, mcpt_stats* stats, void* stream)
 {
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (const int rc = device_gate(d)) return rc;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n == 0) return MCPT_OK;
-    HIP_TRY(hipSetDevice(d->ordinal));
     if (const int rc = motion_home(d)) return rc;           // a device that holds a motion answers from key 0
     if (const int rc = geometry_gate(d)) return rc;
     if (const int rc = wait_for_frames(d)) return rc;       // the passes use frame slot 0 and the device's look stream
-    if (const int rc = ensure_work(d, size_t(n))) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
+    Lease l;
+    if (const int rc = ensure_work(d, size_t(n), st, l)) return rc;
     // a call that fails half-way must not leave half-recorded event pairs behind (render.cpp: mcpt_render_device)
     const size_t ev_used0 = d->ev_used;
     const int rc = run_passes(d, q, d_ids, n, spp, sample_base, seed, flags, ap, d_counts, stats, st);
     if (rc != MCPT_OK) d->ev_used = ev_used0;
-    // (also on failure: what was enqueued may still use the workspace)
-    const hipError_t e = hipEventRecord(d->aq->done.get(), st);
-    if (rc == MCPT_OK && e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    return rc;
+    return l.end(rc);
 }
 
 extern "C" {
@@ -172,34 +166,21 @@ int mcpt_query_radiance_adaptive(mcpt_device* d, const double* q6, const int32_t
     if (const int rc = query_params_check(p, n, q6, mean3)) return rc;
     if (const int rc = query_list_check(q6, ids, n, p->kind)) return rc;
     if (const int rc = adaptive_params_check(ap)) return rc;
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (const int rc = device_gate(d)) return rc;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n == 0) return MCPT_OK;
-    // the caller's arrays are pageable host memory: blocking copies on either side of the device form, which is ordered on d->stream
-    HIP_TRY(hipSetDevice(d->ordinal));
-    DevBuf<double> d_q, d_mean, d_err;
-    DevBuf<int32_t> d_ids, d_hits, d_counts;
     const size_t sn = size_t(n);
-    HIP_TRY(d_q.alloc(sn * 6));
-    HIP_TRY(d_mean.alloc(sn * 3));
-    if (stderr3) HIP_TRY(d_err.alloc(sn * 3));
-    if (hits) HIP_TRY(d_hits.alloc(sn));
-    if (counts) HIP_TRY(d_counts.alloc(sn));
-    if (ids) HIP_TRY(d_ids.alloc(sn));
-    HIP_TRY(hipMemcpy(d_q.get(), q6, sn * 6 * sizeof(double), hipMemcpyHostToDevice));
-    if (ids) HIP_TRY(hipMemcpy(d_ids.get(), ids, sn * sizeof(int32_t), hipMemcpyHostToDevice));
-    hipStream_t st = d->stream.get();
-    const DQuery q{d_q.get(), p->kind, d_mean.get(), d_err.get(), d_hits.get()};
-    int rc = adaptive_query_device(d, q, d_ids.get(), n, p->spp, p->sample_base, p->seed, p->flags, *ap, d_counts.get(), stats, st);
-    const hipError_t e = hipStreamSynchronize(st);          // also on failure: nothing enqueued may still use a copy when it goes
-    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    if (rc != MCPT_OK) return rc;
-    HIP_TRY(hipMemcpy(mean3, d_mean.get(), sn * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (stderr3) HIP_TRY(hipMemcpy(stderr3, d_err.get(), sn * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (hits) HIP_TRY(hipMemcpy(hits, d_hits.get(), sn * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (counts) HIP_TRY(hipMemcpy(counts, d_counts.get(), sn * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    Staging S(d->stream.get());
+    const int32_t* d_ids = nullptr;
+    int32_t* d_counts = nullptr;
+    DQuery q{nullptr, p->kind, nullptr, nullptr, nullptr};
+    if (const int rc = S.in(q6, sn * 6, "the query list", q.q6)) return rc;
+    if (const int rc = S.in(ids, sn, "the queries' ids", d_ids)) return rc;
+    if (const int rc = S.out(mean3, sn * 3, "the queries' answers", q.mean3)) return rc;
+    if (const int rc = S.out(stderr3, sn * 3, "the queries' standard errors", q.stderr3)) return rc;
+    if (const int rc = S.out(hits, sn, "the queries' hits", q.hits)) return rc;
+    if (const int rc = S.out(counts, sn, "the queries' sample counts", d_counts)) return rc;
+    return S.finish(adaptive_query_device(d, q, d_ids, n, p->spp, p->sample_base, p->seed, p->flags, *ap, d_counts, stats, d->stream.get()));
 }
 
 }  // extern "C"

@@ -154,10 +154,10 @@ int mcpt_display_histogram(mcpt_device* d, const double* img, int64_t n_pixels, 
 {
     if (!d || !slots || n_pixels < 0 || (n_pixels > 0 && !img)) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(d->ordinal));
-    DevBuf<double> d_img;
-    HIP_TRY(d_img.alloc(size_t(n_pixels) * 3));
-    if (n_pixels > 0) HIP_TRY(hipMemcpy(d_img.get(), img, size_t(n_pixels) * 3 * sizeof(double), hipMemcpyHostToDevice));
-    return display_histogram_device(d, d_img.get(), nullptr, n_pixels, slots, d->stream.get());      // (returns with the stream idle)
+    Staging S(d->stream.get());
+    const double* d_img = nullptr;
+    if (const int rc = S.in(img, size_t(n_pixels) * 3, "the frame", d_img)) return rc;
+    return display_histogram_device(d, d_img, nullptr, n_pixels, slots, d->stream.get());            // (returns with the stream idle)
 }
 
 int mcpt_display_device(mcpt_device* d, const double* d_img, int64_t n_pixels, const mcpt_display_params* p, uint8_t* d_out, mcpt_display_info* info,
@@ -175,17 +175,12 @@ int mcpt_display(mcpt_device* d, const double* img, int64_t n_pixels, const mcpt
     if (!d || n_pixels < 0 || (n_pixels > 0 && (!img || !out))) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(d->ordinal));
     const size_t bytes = size_t(n_pixels) * ((p && (p->flags & MCPT_DISPLAY_RGBA)) ? 4 : 3);
-    DevBuf<double> d_img;
-    DevBuf<uint8_t> d_out;
-    HIP_TRY(d_img.alloc(size_t(n_pixels) * 3));
-    HIP_TRY(d_out.alloc(bytes));
-    if (n_pixels > 0) HIP_TRY(hipMemcpy(d_img.get(), img, size_t(n_pixels) * 3 * sizeof(double), hipMemcpyHostToDevice));
-    hipStream_t st = d->stream.get();
-    int rc = display_frame_device(d, d_img.get(), nullptr, n_pixels, p, d_out.get(), info, st);
-    const hipError_t e = hipStreamSynchronize(st);        // also on failure: nothing enqueued may still use the copies when they go
-    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    if (rc == MCPT_OK && n_pixels > 0) HIP_TRY(hipMemcpy(out, d_out.get(), bytes, hipMemcpyDeviceToHost));
-    return rc;
+    Staging S(d->stream.get());
+    const double* d_img = nullptr;
+    uint8_t* d_out = nullptr;
+    if (const int rc = S.in(img, size_t(n_pixels) * 3, "the frame", d_img)) return rc;
+    if (const int rc = S.out(out, bytes, "the picture", d_out)) return rc;
+    return S.finish(display_frame_device(d, d_img, nullptr, n_pixels, p, d_out, info, d->stream.get()));
 }
 
 }  // extern "C"

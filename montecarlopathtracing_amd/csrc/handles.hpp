@@ -17,6 +17,8 @@
 //   baked_api.cpp     baked frames: the lightmap's lookup by chart coordinate, baked radiance along a caller's rays, frames lit by a bake
 //   reflection_api.cpp  reflection probes: an octahedral radiance map per probe through the ray query, its Phong prefilter, the chain's lookup
 //   render_scene.cpp  output writers, checkpoints, render_scene
+//   staging.cpp       what the query family's files share (staging.hpp): the device gate, the allocation mapping, a host-pointer call's
+//                     device copies, the lease of a per-device workspace; chunks.hpp: how a workspace budget cuts a list into chunks
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -34,6 +36,7 @@
 #include "kernels.hpp"
 #include "knobs.hpp"
 #include "scene.hpp"
+#include "staging.hpp"
 #include "stats.hpp"
 #include "wavefront.hpp"
 
@@ -192,9 +195,8 @@ struct mcpt_device {
     bool geometry_failed = false;                   // an update failed midway: nothing is traced or rendered until one succeeds
     // display transform (display_api.cpp): the luminance histogram's slots and their pinned copy, made on the first call that takes one
     mcpt::DevBuf<unsigned long long> disp_slots; mcpt::HostBuf<int64_t> h_disp_slots;
-    // lightmap baking (lightmap_api.cpp): what a bake keeps between its kernels, made by the first one and grown to the largest map so far.
-    // A device-form bake may return with its kernels still enqueued, so none of this is a local of the call; `done` is recorded behind a
-    // bake's last kernel and waited for before the next one writes here.
+    // The six workspaces below are kept between calls; a call holds one through its `done` event, by staging.hpp's lease.
+    // lightmap baking (lightmap_api.cpp): what a bake keeps between its kernels, made by the first one and grown to the largest map so far
     struct Lightmap {
         mcpt::DevBuf<int32_t> owner[2], slot_of_face, big, block_counts, block_offsets, total;
         mcpt::DevBuf<unsigned int> n_big;
@@ -211,8 +213,7 @@ struct mcpt_device {
     };
     std::unique_ptr<Lightmap> lm;
     // adaptive queries (adaptive_query_api.cpp): what a call keeps between its passes, made by the first one and grown to the longest
-    // list so far.  A device-form call returns with its finishing kernel enqueued, so none of this is a local of the call; `done` is
-    // recorded behind a call's last kernel and waited for before the next one writes here.
+    // list so far
     struct AdaptiveQuery {
         mcpt::DevBuf<double> mom;                       // [n][2][3] the queries' moments, by position in the caller's list
         mcpt::DevBuf<int32_t> hitcnt, cnt;              // [n] hit counts and sample counts
@@ -226,17 +227,15 @@ struct mcpt_device {
         mcpt::Event done;
     };
     std::unique_ptr<AdaptiveQuery> aq;
-    // irradiance volumes (volume_api.cpp): the positions of the grid a bake answers, made by the first bake and grown to the largest grid
-    // so far.  A device-form bake returns with its query enqueued, so the list is not a local of the call; `done` is recorded behind a
-    // bake's last kernel and waited for before the next one writes here.
+    // irradiance volumes (volume_api.cpp: volume_points_device, shared with the visibility grid bake): the positions of the grid a bake
+    // answers, made by the first bake and grown to the largest grid so far
     struct Volume {
         mcpt::DevBuf<double> p3;                        // [nprobes][3]
         mcpt::Event done;
     };
     std::unique_ptr<Volume> vol;
     // probe visibility (visibility_api.cpp): the rays of a chunk of probes and their closest hits, made by the first bake and grown to the
-    // largest chunk so far, 84 bytes per ray.  A device-form bake returns with its fold enqueued, so the workspace is not a local of the
-    // call; `done` is recorded behind a bake's last kernel and waited for before the next one writes here.
+    // largest chunk so far, 84 bytes per ray
     struct Visibility {
         mcpt::DevBuf<double> rays6, t, p;               // [rays][6], [rays], [rays][3]
         mcpt::DevBuf<int32_t> leaf;                     // [rays]
@@ -244,8 +243,7 @@ struct mcpt_device {
     };
     std::unique_ptr<Visibility> vis;
     // baked frames (baked_api.cpp): the rays of a chunk, their closest hits and the chunk's shaded samples, made by the first call and grown
-    // to the largest chunk so far, 116 bytes per ray.  A device-form call returns with its fold enqueued, so the workspace is not a local
-    // of the call; `done` is recorded behind a call's last kernel and waited for before the next one writes here.
+    // to the largest chunk so far, 116 bytes per ray
     struct Baked {
         mcpt::DevBuf<double> rays6, t, p, rad;          // [rays][6], [rays], [rays][3], [rays][3]
         mcpt::DevBuf<int32_t> leaf, kind, lit;          // [rays]
@@ -253,8 +251,7 @@ struct mcpt_device {
     };
     std::unique_ptr<Baked> baked;
     // reflection probes (reflection_api.cpp): the rays of a chunk of texels with their ids, and the query's answers to them, made by the
-    // first bake and grown to the largest chunk so far, 80 bytes per ray.  A device-form bake returns with its fold enqueued, so the
-    // workspace is not a local of the call; `done` is recorded behind a bake's last kernel and waited for before the next one writes here.
+    // first bake and grown to the largest chunk so far, 80 bytes per ray
     struct Reflection {
         mcpt::DevBuf<double> rays6, mean;               // [rays][6], [rays][3]
         mcpt::DevBuf<int32_t> ids, hits;                // [rays]
@@ -357,8 +354,8 @@ int probe_list_check(const double* p3, const int32_t* ids, int64_t n);
 int volume_grid_check(const mcpt_volume_grid* g);   // what every call refuses of a grid, in the struct's field order
 // what the host-pointer forms of a lookup refuse of the coefficients and the receivers themselves
 int volume_arrays_check(const mcpt_volume_grid& g, const double* sh27, const double* q6, int64_t n);
-// a failed allocation of a workspace or a copy: MCPT_ERR_NOMEM when the memory is not there, and the device stays usable
-int volume_alloc_result(hipError_t e, const char* what, size_t bytes);
+// The grid's positions into the volume's own list (d->vol->p3) on st, for the bake that answers them: the list is the caller's until l ends
+int volume_points_device(mcpt_device* d, const mcpt_volume_grid& g, hipStream_t st, Lease& l);
 
 // ---- visibility_api.cpp (shared with baked_api.cpp)
 int volume_visibility_check(const mcpt_volume_visibility* v);   // what every visibility-weighted lookup refuses of its knobs, in the struct's field order
@@ -369,10 +366,8 @@ int lightmap_size_check(int32_t width, int32_t height);             // MCPT_ERR_
 int lightmap_chart_check(const double* uv6, int64_t num_faces);     // MCPT_ERR_ARG: a chart component that is not finite
 // what every lightmap call on a device does before it reads the device's triangles: the device itself, key 0 of a motion, a geometry that stands
 int lightmap_device_gate(mcpt_device* d);
-// the baker's workspace of a W x H map on d (d->lm), once the bake or denoise before this one has left it
-int lightmap_ensure_work(mcpt_device* d, int W, int H, mcpt::LightmapWork& w);
-// a chart of the caller's on the device (null stays null: the scene's own vt)
-int lightmap_upload_chart(const mcpt_device* d, const double* uv6, mcpt::DevBuf<double>& d_uv);
+// the baker's workspace of a W x H map on d (d->lm) for a call on st, once the bake or denoise before this one has left it
+int lightmap_ensure_work(mcpt_device* d, int W, int H, mcpt::LightmapWork& w, hipStream_t st, Lease& l);
 
 // ---- adaptive_query_api.cpp
 // what the adaptive calls refuse of their adaptive parameters (MCPT_ERR_ARG)

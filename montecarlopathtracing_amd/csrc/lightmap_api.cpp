@@ -13,6 +13,8 @@
 
 using namespace mcpt;
 
+static const char* const kWork = "the lightmap baker's workspace";
+
 int lightmap_size_check(int32_t width, int32_t height)
 {
     return width >= 1 && width <= kLightmapMaxSize && height >= 1 && height <= kLightmapMaxSize
@@ -43,32 +45,29 @@ static int params_check(const mcpt_lightmap_params* p, const void* irradiance3)
 // what every call on a device does before it reads the device's triangles: the device itself, key 0 of a motion, a geometry that stands
 int lightmap_device_gate(mcpt_device* d)
 {
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
-    HIP_TRY(hipSetDevice(d->ordinal));
+    if (const int rc = device_gate(d)) return rc;
     if (const int rc = motion_home(d)) return rc;
     return geometry_gate(d);
 }
 
-// the workspace of a W x H map on d, once the bake before this one has left it
-int lightmap_ensure_work(mcpt_device* d, int W, int H, LightmapWork& w)
+// the workspace of a W x H map on d for a call on st, once the bake or denoise before this one has left it
+int lightmap_ensure_work(mcpt_device* d, int W, int H, LightmapWork& w, hipStream_t st, Lease& l)
 {
-    if (!d->lm) {
-        d->lm = std::make_unique<mcpt_device::Lightmap>();
-        HIP_TRY(create(d->lm->done, hipEventCreateWithFlags, hipEventDisableTiming));
-        HIP_TRY(d->lm->h_total.alloc(1));
-        HIP_TRY(d->lm->total.alloc(1));
-        HIP_TRY(d->lm->n_big.alloc(1));
-    }
+    const auto words = [](mcpt_device::Lightmap& m) -> int {
+        HIP_TRY(m.h_total.alloc(1));
+        HIP_TRY(m.total.alloc(1));
+        HIP_TRY(m.n_big.alloc(1));
+        return MCPT_OK;
+    };
+    if (const int rc = lease(d->lm, st, l, words)) return rc;
     mcpt_device::Lightmap& m = *d->lm;
-    HIP_TRY(hipEventSynchronize(m.done.get()));
     const size_t n = size_t(W) * H, t = size_t(d->ds.t > 0 ? d->ds.t : 1), blocks = size_t(lightmap_blocks((long long)n));
-    HIP_TRY(m.owner[0].grow(n));
-    HIP_TRY(m.slot_of_face.grow(t));
-    HIP_TRY(m.big.grow(t));
-    HIP_TRY(m.masks.grow(blocks * 4));
-    HIP_TRY(m.block_counts.grow(blocks));
-    HIP_TRY(m.block_offsets.grow(blocks));
+    if (const int rc = grow(m.owner[0], n, kWork)) return rc;
+    if (const int rc = grow(m.slot_of_face, t, kWork)) return rc;
+    if (const int rc = grow(m.big, t, kWork)) return rc;
+    if (const int rc = grow(m.masks, blocks * 4, kWork)) return rc;
+    if (const int rc = grow(m.block_counts, blocks, kWork)) return rc;
+    if (const int rc = grow(m.block_offsets, blocks, kWork)) return rc;
     w = LightmapWork{m.owner[0].get(), m.slot_of_face.get(), m.big.get(), m.n_big.get(), m.masks.get(), m.block_counts.get(), m.block_offsets.get(),
                      m.total.get()};
     return MCPT_OK;
@@ -95,11 +94,12 @@ static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_
     const int W = p.width, H = p.height, R = p.dilate;
     const size_t n = size_t(W) * H;
     LightmapWork w{};
-    if (const int rc = lightmap_ensure_work(d, W, H, w)) return rc;
+    Lease l;                                                // (d->lm's: the adaptive query call below holds its own)
+    if (const int rc = lightmap_ensure_work(d, W, H, w, st, l)) return rc;
     mcpt_device::Lightmap& m = *d->lm;
     if (R > 0) {
-        HIP_TRY(m.owner[1].grow(n));
-        HIP_TRY(m.irr.grow(n * 3));
+        if (const int rc = grow(m.owner[1], n, kWork)) return rc;
+        if (const int rc = grow(m.irr, n * 3, kWork)) return rc;
     }
     int32_t covered = 0;
     if (const int rc = raster_device(d, d_uv6, W, H, w, st, covered)) return rc;
@@ -112,12 +112,15 @@ static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_
     if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, n * sizeof(int32_t), st));
     if (covered > 0) {
         const size_t c = size_t(covered);
-        HIP_TRY(m.texels.grow(c));
-        HIP_TRY(m.q6.grow(c * 6));
-        HIP_TRY(m.mean.grow(c * 3));
-        if (d_err) HIP_TRY(m.err.grow(c * 3));
-        if (d_hits) HIP_TRY(m.hits.grow(c));
-        if (d_counts) HIP_TRY(m.counts.grow(c));
+        if (const int rc = grow(m.texels, c, kWork)) return rc;
+        if (const int rc = grow(m.q6, c * 6, kWork)) return rc;
+        if (const int rc = grow(m.mean, c * 3, kWork)) return rc;
+        if (d_err)
+            if (const int rc = grow(m.err, c * 3, kWork)) return rc;
+        if (d_hits)
+            if (const int rc = grow(m.hits, c, kWork)) return rc;
+        if (d_counts)
+            if (const int rc = grow(m.counts, c, kWork)) return rc;
         launch_lightmap_texels(d->ds, d_uv6, W, H, w, m.texels.get(), m.q6.get(), st);
         HIP_TRY(hipGetLastError());
         const DQuery q{m.q6.get(), MCPT_QUERY_HEMISPHERE, m.mean.get(), d_err ? m.err.get() : nullptr, d_hits ? m.hits.get() : nullptr};
@@ -137,18 +140,7 @@ static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_
     }
     HIP_TRY(hipGetLastError());
     if (d_owner) HIP_TRY(hipMemcpyAsync(d_owner, own[R & 1], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipEventRecord(m.done.get(), st));
-    return MCPT_OK;
-}
-
-// a chart of the caller's on the device (null stays null: the scene's own vt)
-int lightmap_upload_chart(const mcpt_device* d, const double* uv6, DevBuf<double>& d_uv)
-{
-    if (!uv6) return MCPT_OK;
-    const size_t c = size_t(d->ds.t) * 6;
-    HIP_TRY(d_uv.alloc(c));
-    if (c > 0) HIP_TRY(hipMemcpy(d_uv.get(), uv6, c * sizeof(double), hipMemcpyHostToDevice));
-    return MCPT_OK;
+    return l.end(MCPT_OK);
 }
 
 extern "C" {
@@ -184,32 +176,30 @@ int64_t mcpt_lightmap_texels(mcpt_device* d, const double* uv6, int32_t width, i
 {
     if (const int rc = lightmap_size_check(width, height)) return rc;
     if (cap < 0) return fail(MCPT_ERR_ARG, "cap must be >= 0");
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (const int rc = device_gate(d)) return rc;
     if (uv6)
         if (const int rc = lightmap_chart_check(uv6, d->ds.t)) return rc;
-    if (const int rc = lightmap_device_gate(d)) return rc;
-    DevBuf<double> d_uv, d_q6;
-    DevBuf<int32_t> d_texels;
-    if (const int rc = lightmap_upload_chart(d, uv6, d_uv)) return rc;
-    LightmapWork w{};
-    if (const int rc = lightmap_ensure_work(d, width, height, w)) return rc;
+    if (const int rc = motion_home(d)) return rc;
+    if (const int rc = geometry_gate(d)) return rc;
     hipStream_t st = d->stream.get();
+    Staging S(st);
+    const double* d_uv = nullptr;                           // (null stays null: the scene's own vt)
+    if (const int rc = S.in(uv6, size_t(d->ds.t) * 6, "the chart", d_uv)) return rc;
+    LightmapWork w{};
+    Lease l;
+    if (const int rc = lightmap_ensure_work(d, width, height, w, st, l)) return rc;
     int32_t covered = 0;
-    if (const int rc = raster_device(d, d_uv.get(), width, height, w, st, covered)) return rc;
+    if (const int rc = raster_device(d, d_uv, width, height, w, st, covered)) return rc;
     const size_t n = size_t(width) * height, c = size_t(covered);
     if ((texels || q6) && covered > cap) return fail(MCPT_ERR_ARG, "more texels are covered (" + std::to_string(covered) + ") than the list holds");
     if (owner) HIP_TRY(hipMemcpy(owner, w.owner, n * sizeof(int32_t), hipMemcpyDeviceToHost));
     if ((texels || q6) && covered > 0) {
-        if (texels) HIP_TRY(d_texels.alloc(c));
-        if (q6) HIP_TRY(d_q6.alloc(c * 6));
-        launch_lightmap_texels(d->ds, d_uv.get(), width, height, w, d_texels.get(), d_q6.get(), st);
-        hipError_t e = hipGetLastError();
-        const hipError_t es = hipStreamSynchronize(st);        // also on failure: nothing enqueued may still use the lists when they go
-        if (e == hipSuccess) e = es;
-        if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
-        if (texels) HIP_TRY(hipMemcpy(texels, d_texels.get(), c * sizeof(int32_t), hipMemcpyDeviceToHost));
-        if (q6) HIP_TRY(hipMemcpy(q6, d_q6.get(), c * 6 * sizeof(double), hipMemcpyDeviceToHost));
+        int32_t* d_texels = nullptr;
+        double* d_q6 = nullptr;
+        if (const int rc = S.out(texels, c, "the texel list", d_texels)) return rc;
+        if (const int rc = S.out(q6, c * 6, "the texels' surface points", d_q6)) return rc;
+        launch_lightmap_texels(d->ds, d_uv, width, height, w, d_texels, d_q6, st);
+        if (const int rc = S.finish(launch_result())) return rc;
     }
     return covered;
 }
@@ -227,31 +217,21 @@ int mcpt_bake_lightmap_device(mcpt_device* d, const double* d_uv6, const mcpt_li
 static int bake_host(mcpt_device* d, const double* uv6, const mcpt_lightmap_params* p, const mcpt_adaptive_params* ap, double* irradiance3, double* stderr3,
                      int32_t* hits, int32_t* owner, int32_t* counts, mcpt_stats* stats)
 {
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (const int rc = device_gate(d)) return rc;
     if (uv6)
         if (const int rc = lightmap_chart_check(uv6, d->ds.t)) return rc;
-    HIP_TRY(hipSetDevice(d->ordinal));
     const size_t n = size_t(p->width) * p->height;
-    DevBuf<double> d_uv, d_irr, d_err;
-    DevBuf<int32_t> d_hits, d_owner, d_counts;
-    if (const int rc = lightmap_upload_chart(d, uv6, d_uv)) return rc;
-    HIP_TRY(d_irr.alloc(n * 3));
-    if (counts) HIP_TRY(d_counts.alloc(n));
-    if (stderr3) HIP_TRY(d_err.alloc(n * 3));
-    if (hits) HIP_TRY(d_hits.alloc(n));
-    if (owner) HIP_TRY(d_owner.alloc(n));
-    hipStream_t st = d->stream.get();
-    int rc = bake_device(d, d_uv.get(), *p, ap, d_irr.get(), d_err.get(), d_hits.get(), d_owner.get(), d_counts.get(), stats, st);
-    const hipError_t e = hipStreamSynchronize(st);              // also on failure: nothing enqueued may still use a copy when it goes
-    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    if (rc != MCPT_OK) return rc;
-    HIP_TRY(hipMemcpy(irradiance3, d_irr.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (stderr3) HIP_TRY(hipMemcpy(stderr3, d_err.get(), n * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (hits) HIP_TRY(hipMemcpy(hits, d_hits.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (owner) HIP_TRY(hipMemcpy(owner, d_owner.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (counts) HIP_TRY(hipMemcpy(counts, d_counts.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    Staging S(d->stream.get());
+    const double* d_uv = nullptr;                           // (null stays null: the scene's own vt)
+    double *d_irr = nullptr, *d_err = nullptr;
+    int32_t *d_hits = nullptr, *d_owner = nullptr, *d_counts = nullptr;
+    if (const int rc = S.in(uv6, size_t(d->ds.t) * 6, "the chart", d_uv)) return rc;
+    if (const int rc = S.out(irradiance3, n * 3, "the irradiance map", d_irr)) return rc;
+    if (const int rc = S.out(stderr3, n * 3, "the standard error map", d_err)) return rc;
+    if (const int rc = S.out(hits, n, "the hit map", d_hits)) return rc;
+    if (const int rc = S.out(owner, n, "the owner map", d_owner)) return rc;
+    if (const int rc = S.out(counts, n, "the sample count map", d_counts)) return rc;
+    return S.finish(bake_device(d, d_uv, *p, ap, d_irr, d_err, d_hits, d_owner, d_counts, stats, d->stream.get()));
 }
 
 extern "C" {

@@ -28,16 +28,8 @@ static int params_check(const mcpt_lightmap_denoise_params* p, const void* irrad
     return MCPT_OK;
 }
 
-// a workspace buffer of the denoiser's: a map too large for the memory that is left is MCPT_ERR_NOMEM, and the device stays usable
-static int grow_work(DevBuf<char>& b, size_t bytes)
-{
-    const hipError_t e = b.grow_bytes(bytes);
-    if (e == hipSuccess) return MCPT_OK;
-    (void)hipGetLastError();                                    // the runtime keeps the failure as its last error: it has been reported here
-    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation)
-        return fail(MCPT_ERR_NOMEM, "the lightmap denoiser's workspace (" + std::to_string(bytes) + " bytes) cannot be allocated");
-    return fail(MCPT_ERR_HIP, std::string("lightmap denoise workspace: ") + hipGetErrorString(e));
-}
+// (a map too large for the memory that is left is MCPT_ERR_NOMEM, and the device stays usable)
+static const char* const kWork = "the lightmap denoiser's workspace";
 
 // The whole call on st, after the refusals; device pointers throughout.  Nothing here waits for st.
 static int denoise_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_denoise_params& p, const double* d_irr, const double* d_err,
@@ -49,16 +41,17 @@ static int denoise_device(mcpt_device* d, const double* d_uv6, const mcpt_lightm
     const double sigma_l = p.sigma_l > 0.0 ? p.sigma_l : MCPT_LIGHTMAP_DENOISE_SIGMA_L;
     const double sigma_p = p.sigma_p > 0.0 ? p.sigma_p : MCPT_LIGHTMAP_DENOISE_SIGMA_P;
     LightmapWork w{};
-    if (const int rc = lightmap_ensure_work(d, W, H, w)) return rc;
+    Lease l;
+    if (const int rc = lightmap_ensure_work(d, W, H, w, st, l)) return rc;
     mcpt_device::Lightmap& m = *d->lm;
-    if (const int rc = grow_work(m.dn_guide, n * sizeof(LightmapGuide))) return rc;
+    if (const int rc = grow(m.dn_guide, n * sizeof(LightmapGuide), kWork)) return rc;
     if (K > 0) {
-        if (const int rc = grow_work(m.dn_buf[0], n * sizeof(LightmapPix))) return rc;
-        if (const int rc = grow_work(m.dn_buf[1], n * sizeof(LightmapPix))) return rc;
+        if (const int rc = grow(m.dn_buf[0], n * sizeof(LightmapPix), kWork)) return rc;
+        if (const int rc = grow(m.dn_buf[1], n * sizeof(LightmapPix), kWork)) return rc;
     }
     if (R > 0) {
-        HIP_TRY(m.owner[1].grow(n));
-        HIP_TRY(m.irr.grow(n * 3));
+        if (const int rc = grow(m.owner[1], n, kWork)) return rc;
+        if (const int rc = grow(m.irr, n * 3, kWork)) return rc;
     }
     launch_lightmap_raster(d->ds, d_uv6, W, H, w, st);
     HIP_TRY(hipGetLastError());
@@ -75,8 +68,7 @@ static int denoise_device(mcpt_device* d, const double* d_uv6, const mcpt_lightm
     }
     HIP_TRY(hipGetLastError());
     if (d_owner) HIP_TRY(hipMemcpyAsync(d_owner, own[R & 1], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipEventRecord(m.done.get(), st));
-    return MCPT_OK;
+    return l.end(MCPT_OK);
 }
 
 extern "C" {
@@ -92,29 +84,20 @@ int mcpt_lightmap_denoise(mcpt_device* d, const double* uv6, const mcpt_lightmap
                           double* out3, int32_t* owner)
 {
     if (const int rc = params_check(p, irradiance3, stderr3, out3)) return rc;
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (const int rc = device_gate(d)) return rc;
     if (uv6)
         if (const int rc = lightmap_chart_check(uv6, d->ds.t)) return rc;
-    HIP_TRY(hipSetDevice(d->ordinal));
-    const size_t n = size_t(p->width) * p->height, bytes = n * 3 * sizeof(double);
-    DevBuf<double> d_uv, d_irr, d_err, d_out;
-    DevBuf<int32_t> d_owner;
-    if (const int rc = lightmap_upload_chart(d, uv6, d_uv)) return rc;
-    HIP_TRY(d_irr.alloc(n * 3));
-    HIP_TRY(d_err.alloc(n * 3));
-    HIP_TRY(d_out.alloc(n * 3));
-    if (owner) HIP_TRY(d_owner.alloc(n));
-    HIP_TRY(hipMemcpy(d_irr.get(), irradiance3, bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_err.get(), stderr3, bytes, hipMemcpyHostToDevice));
-    hipStream_t st = d->stream.get();
-    int rc = denoise_device(d, d_uv.get(), *p, d_irr.get(), d_err.get(), d_out.get(), d_owner.get(), st);
-    const hipError_t e = hipStreamSynchronize(st);              // also on failure: nothing enqueued may still use a copy when it goes
-    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    if (rc != MCPT_OK) return rc;
-    HIP_TRY(hipMemcpy(out3, d_out.get(), bytes, hipMemcpyDeviceToHost));
-    if (owner) HIP_TRY(hipMemcpy(owner, d_owner.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    const size_t n = size_t(p->width) * p->height;
+    Staging S(d->stream.get());
+    const double *d_uv = nullptr, *d_irr = nullptr, *d_err = nullptr;    // (a null chart stays null: the scene's own vt)
+    double* d_out = nullptr;
+    int32_t* d_owner = nullptr;
+    if (const int rc = S.in(uv6, size_t(d->ds.t) * 6, "the chart", d_uv)) return rc;
+    if (const int rc = S.in(irradiance3, n * 3, "the irradiance map", d_irr)) return rc;
+    if (const int rc = S.in(stderr3, n * 3, "the standard error map", d_err)) return rc;
+    if (const int rc = S.out(out3, n * 3, "the denoised map", d_out)) return rc;
+    if (const int rc = S.out(owner, n, "the owner map", d_owner)) return rc;
+    return S.finish(denoise_device(d, d_uv, *p, d_irr, d_err, d_out, d_owner, d->stream.get()));
 }
 
 }  // extern "C"

@@ -182,7 +182,7 @@ int mcpt_progressive_step(mcpt_progressive* h, int32_t n, mcpt_stats* stats)
         rc = motion_passes(d, h->done, q.spp, h->p.spp, d->stream.get(), [&](int k0, int n) {
             mcpt_stats piece{};
             const int prc = pass(k0, n, stats ? &piece : nullptr);
-            if (prc == MCPT_OK && stats) { add_counts(*stats, piece); stats->ms_trace += piece.ms_trace; stats->ms_total += piece.ms_total; }
+            if (prc == MCPT_OK && stats) add_piece(*stats, piece);
             return prc;
         });
     else rc = pass(h->done, q.spp, stats);

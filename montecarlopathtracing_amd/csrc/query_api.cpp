@@ -5,22 +5,15 @@
 
 #include <cmath>
 #include <cstring>
-#include <limits>
 #include <string>
 
 #include "handles.hpp"
 
 using namespace mcpt;
 
-static constexpr int64_t kInt32Max = std::numeric_limits<int32_t>::max();
-
 static int kind_check(int32_t kind)
 {
     return kind == MCPT_QUERY_RAY || kind == MCPT_QUERY_HEMISPHERE ? MCPT_OK : fail(MCPT_ERR_ARG, "unknown query kind");
-}
-static int count_check(int64_t n)
-{
-    return n >= 0 && n <= kInt32Max ? MCPT_OK : fail(MCPT_ERR_ARG, "the number of queries must be in 0 .. 2^31 - 1");
 }
 
 // what every query call refuses of its sample range and count, and of its flags: the pieces of query_params_check and sh_params_check, which
@@ -30,7 +23,7 @@ int range_check(int32_t spp, int32_t sample_base, int64_t n)
     if (spp < 1) return fail(MCPT_ERR_ARG, "spp must be >= 1");
     if (sample_base < 0) return fail(MCPT_ERR_ARG, "sample_base must be >= 0");
     if (int64_t(sample_base) + int64_t(spp) > kInt32Max) return fail(MCPT_ERR_ARG, "sample_base + spp must not exceed 2^31 - 1");
-    return count_check(n);
+    return count_check(n, "queries");
 }
 int flags_check(int32_t flags)
 {
@@ -93,8 +86,7 @@ int probe_list_check(const double* p3, const int32_t* ids, int64_t n)
 int query_device(mcpt_device* d, const DQuery& q, const int32_t* d_ids, int64_t n, int32_t spp, int32_t sample_base, uint64_t seed, int32_t flags,
                  mcpt_stats* stats, void* stream)
 {
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (const int rc = device_gate(d)) return rc;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n == 0) return MCPT_OK;
     if (const int rc = motion_home(d)) return rc;           // a device that holds a motion answers from key 0
@@ -117,58 +109,37 @@ int query_device(mcpt_device* d, const DQuery& q, const int32_t* d_ids, int64_t 
 static int query_host(mcpt_device* d, int kind, int in, int out, const double* list, const int32_t* ids, int64_t n, int32_t spp,
                       int32_t sample_base, uint64_t seed, int32_t flags, double* mean, double* err, int32_t* hits, mcpt_stats* stats)
 {
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (const int rc = device_gate(d)) return rc;
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n == 0) return MCPT_OK;
-    HIP_TRY(hipSetDevice(d->ordinal));
-    DevBuf<double> d_q, d_mean, d_err;
-    DevBuf<int32_t> d_ids, d_hits;
     const size_t sn = size_t(n);
-    HIP_TRY(d_q.alloc(sn * in));
-    HIP_TRY(d_mean.alloc(sn * out));
-    if (err) HIP_TRY(d_err.alloc(sn * out));
-    if (hits) HIP_TRY(d_hits.alloc(sn));
-    if (ids) HIP_TRY(d_ids.alloc(sn));
-    HIP_TRY(hipMemcpy(d_q.get(), list, sn * in * sizeof(double), hipMemcpyHostToDevice));
-    if (ids) HIP_TRY(hipMemcpy(d_ids.get(), ids, sn * sizeof(int32_t), hipMemcpyHostToDevice));
-    hipStream_t st = d->stream.get();
-    const DQuery q{d_q.get(), kind, d_mean.get(), err ? d_err.get() : nullptr, hits ? d_hits.get() : nullptr};
-    int rc = query_device(d, q, ids ? d_ids.get() : nullptr, n, spp, sample_base, seed, flags, stats, st);
-    const hipError_t e = hipStreamSynchronize(st);          // also on failure: nothing enqueued may still use a copy when it goes
-    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    if (rc != MCPT_OK) return rc;
-    HIP_TRY(hipMemcpy(mean, d_mean.get(), sn * out * sizeof(double), hipMemcpyDeviceToHost));
-    if (err) HIP_TRY(hipMemcpy(err, d_err.get(), sn * out * sizeof(double), hipMemcpyDeviceToHost));
-    if (hits) HIP_TRY(hipMemcpy(hits, d_hits.get(), sn * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    Staging S(d->stream.get());
+    const int32_t* d_ids = nullptr;
+    DQuery q{nullptr, kind, nullptr, nullptr, nullptr};
+    if (const int rc = S.in(list, sn * in, "the query list", q.q6)) return rc;
+    if (const int rc = S.in(ids, sn, "the queries' ids", d_ids)) return rc;
+    if (const int rc = S.out(mean, sn * out, "the queries' answers", q.mean3)) return rc;
+    if (const int rc = S.out(err, sn * out, "the queries' standard errors", q.stderr3)) return rc;
+    if (const int rc = S.out(hits, sn, "the queries' hits", q.hits)) return rc;
+    return S.finish(query_device(d, q, d_ids, n, spp, sample_base, seed, flags, stats, d->stream.get()));
 }
 
 // the rays of a list on the host: the body of mcpt_query_rays and mcpt_query_sh_rays after their refusals (`in` doubles per entry)
 static int rays_host(mcpt_device* d, int kind, int in, const double* list, const int32_t* ids, int64_t n, uint64_t seed, const int32_t* k, double* rays6)
 {
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (const int rc = device_gate(d)) return rc;
     if (n == 0) return MCPT_OK;
-    HIP_TRY(hipSetDevice(d->ordinal));
-    DevBuf<double> d_q, d_rays;
-    DevBuf<int32_t> d_ids, d_k;
     const size_t sn = size_t(n);
-    HIP_TRY(d_q.alloc(sn * in));
-    HIP_TRY(d_rays.alloc(sn * 6));
-    HIP_TRY(d_k.alloc(sn));
-    if (ids) HIP_TRY(d_ids.alloc(sn));
-    HIP_TRY(hipMemcpy(d_q.get(), list, sn * in * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_k.get(), k, sn * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (ids) HIP_TRY(hipMemcpy(d_ids.get(), ids, sn * sizeof(int32_t), hipMemcpyHostToDevice));
-    hipStream_t st = d->stream.get();
-    launch_query_rays(DQuery{d_q.get(), kind, nullptr, nullptr, nullptr}, seed, ids ? d_ids.get() : nullptr, d_k.get(), n, d_rays.get(), st);
-    hipError_t e = hipGetLastError();
-    const hipError_t es = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = es;
-    if (e == hipSuccess) e = hipMemcpy(rays6, d_rays.get(), sn * 6 * sizeof(double), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    return MCPT_OK;
+    Staging S(d->stream.get());
+    const int32_t *d_ids = nullptr, *d_k = nullptr;
+    DQuery q{nullptr, kind, nullptr, nullptr, nullptr};
+    double* d_rays = nullptr;
+    if (const int rc = S.in(list, sn * in, "the query list", q.q6)) return rc;
+    if (const int rc = S.in(k, sn, "the queries' sample indices", d_k)) return rc;
+    if (const int rc = S.in(ids, sn, "the queries' ids", d_ids)) return rc;
+    if (const int rc = S.out(rays6, sn * 6, "the queries' rays", d_rays)) return rc;
+    launch_query_rays(q, seed, d_ids, d_k, n, d_rays, d->stream.get());
+    return S.finish(launch_result());
 }
 
 extern "C" {
@@ -191,7 +162,7 @@ int mcpt_query_radiance(mcpt_device* d, const double* q6, const int32_t* ids, in
 
 int mcpt_query_rays(mcpt_device* d, const double* q6, const int32_t* ids, int64_t n, uint64_t seed, int32_t kind, const int32_t* k, double* rays6)
 {
-    if (const int rc = count_check(n)) return rc;
+    if (const int rc = count_check(n, "queries")) return rc;
     if (const int rc = kind_check(kind)) return rc;
     if (n > 0 && (!q6 || !k || !rays6)) return fail(MCPT_ERR_ARG, "null argument");
     for (int64_t i = 0; i < n; i++)
@@ -221,7 +192,7 @@ int mcpt_query_sh(mcpt_device* d, const double* p3, const int32_t* ids, int64_t 
 
 int mcpt_query_sh_rays(mcpt_device* d, const double* p3, const int32_t* ids, int64_t n, uint64_t seed, const int32_t* k, double* rays6)
 {
-    if (const int rc = count_check(n)) return rc;
+    if (const int rc = count_check(n, "queries")) return rc;
     if (n > 0 && (!p3 || !k || !rays6)) return fail(MCPT_ERR_ARG, "null argument");
     for (int64_t i = 0; i < n; i++)
         if (k[i] < 0) return fail(MCPT_ERR_ARG, "probe " + std::to_string(i) + ": negative sample index");

@@ -7,19 +7,17 @@
 
 #include <cmath>
 #include <cstring>
-#include <limits>
 #include <string>
 #include <vector>
 
+#include "chunks.hpp"
 #include "handles.hpp"
 #include "reflection.hpp"
 
 using namespace mcpt;
 
-static constexpr int64_t kInt32Max = std::numeric_limits<int32_t>::max();
-static constexpr int64_t kDefaultWorkspaceRays = int64_t(1) << 22;  // 320 MB of workspace
 static constexpr size_t kRayBytes = (6 + 3) * sizeof(double) + 2 * sizeof(int32_t);
-static_assert(kRayBytes == 80, "mcpt.h states the workspace's bytes per ray");
+static_assert(kRayBytes == 80, "mcpt.h states the workspace's bytes per ray");    // (the default workspace of 2^22 rays: 320 MB)
 
 static int res_check(int32_t res)
 {
@@ -90,7 +88,7 @@ static int chain_check(const mcpt_reflection_chain* c)
 static int prefilter_check(const mcpt_reflection_chain* c, const void* radiance, int64_t n, const void* chain)
 {
     if (const int rc = chain_check(c)) return rc;
-    if (n < 0 || n > kInt32Max) return fail(MCPT_ERR_ARG, "the number of probes must be in 0 .. 2^31 - 1");
+    if (const int rc = count_check(n, "probes")) return rc;
     if (n > 0 && (!radiance || !chain)) return fail(MCPT_ERR_ARG, "null radiance or chain");
     return MCPT_OK;
 }
@@ -98,8 +96,8 @@ static int prefilter_check(const mcpt_reflection_chain* c, const void* radiance,
 static int lookup_check(const mcpt_reflection_chain* c, const void* chain, int64_t n, const void* probe, const void* d3, const void* x, int64_t m, const void* out3)
 {
     if (const int rc = chain_check(c)) return rc;
-    if (n < 0 || n > kInt32Max) return fail(MCPT_ERR_ARG, "the number of probes must be in 0 .. 2^31 - 1");
-    if (m < 0 || m > kInt32Max) return fail(MCPT_ERR_ARG, "the number of receivers must be in 0 .. 2^31 - 1");
+    if (const int rc = count_check(n, "probes")) return rc;
+    if (const int rc = count_check(m, "receivers")) return rc;
     if (m > 0 && (!chain || !probe || !d3 || !x || !out3)) return fail(MCPT_ERR_ARG, "null chain, probe indices, directions, exponents or radiance");
     return MCPT_OK;
 }
@@ -125,33 +123,8 @@ static int lookup_arrays_check(const mcpt_reflection_chain& c, const double* cha
     return MCPT_OK;
 }
 
-// what every call on a device asks before it touches one
-static int device_gate(mcpt_device* d)
-{
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
-    HIP_TRY(hipSetDevice(d->ordinal));
-    return MCPT_OK;
-}
-
-template <class T>
-static int upload(DevBuf<T>& b, const T* host, size_t count, const char* what)
-{
-    const size_t bytes = (count > 0 ? count : 1) * sizeof(T);
-    if (const int rc = volume_alloc_result(b.alloc_bytes(bytes), what, bytes)) return rc;
-    if (count > 0) HIP_TRY(hipMemcpy(b.get(), host, count * sizeof(T), hipMemcpyHostToDevice));
-    return MCPT_OK;
-}
-
-// the end of a host-pointer call: the stream is waited for, on failure as well -- nothing enqueued may still use a copy when it goes
-static int finish(int rc, hipStream_t st)
-{
-    const hipError_t e = hipStreamSynchronize(st);
-    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    return rc;
-}
-
-// the counters of one chunk's query added to the call's
+// the counters of one chunk's query added to the call's (not stats.cpp's add_piece: rays_primary and samples are the bake's own, set after
+// its loop, and stay 0 in the statistics of a bake that fails)
 static void add_stats(mcpt_stats& s, const mcpt_stats& q)
 {
     s.rays_shadow += q.rays_shadow; s.rays_bounce += q.rays_bounce; s.node_visits += q.node_visits; s.tri_tests += q.tri_tests;
@@ -169,43 +142,34 @@ static int bake_device(mcpt_device* d, const double* d_p3, const int32_t* d_id_b
     if (n == 0) return MCPT_OK;
     if (const int rc = motion_home(d)) return rc;           // a device that holds a motion answers from key 0
     if (const int rc = geometry_gate(d)) return rc;
-    if (!d->refl) {
-        auto r = std::make_unique<mcpt_device::Reflection>();
-        HIP_TRY(create(r->done, hipEventCreateWithFlags, hipEventDisableTiming));
-        d->refl = std::move(r);
-    }
+    Lease l;
+    if (const int rc = lease(d->refl, st, l)) return rc;    // the bake before this one has left the workspace
     mcpt_device::Reflection& w = *d->refl;
-    HIP_TRY(hipEventSynchronize(w.done.get()));             // the bake before this one has left the workspace
     const int64_t texels = n * rp.res * rp.res;             // <= 2^31 - 1 with spp
-    const int64_t budget = rp.workspace_rays > 0 ? rp.workspace_rays : kDefaultWorkspaceRays;
-    int64_t per_chunk = budget / rp.spp;                    // whole texels, at least one
-    per_chunk = per_chunk < 1 ? 1 : (per_chunk > texels ? texels : per_chunk);
+    const int64_t per_chunk = chunk_plan(rp.workspace_rays, rp.spp, texels);    // whole texels
     const size_t sr = size_t(per_chunk) * size_t(rp.spp);   // <= 2^31 - 1
-    if (const int rc = volume_alloc_result(w.rays6.grow_bytes(sr * 6 * sizeof(double)), "the reflection rays", sr * 6 * sizeof(double))) return rc;
-    if (const int rc = volume_alloc_result(w.mean.grow_bytes(sr * 3 * sizeof(double)), "the reflection samples' radiance", sr * 3 * sizeof(double))) return rc;
-    if (const int rc = volume_alloc_result(w.ids.grow_bytes(sr * sizeof(int32_t)), "the reflection rays' ids", sr * sizeof(int32_t))) return rc;
-    if (const int rc = volume_alloc_result(w.hits.grow_bytes(sr * sizeof(int32_t)), "the reflection samples' hits", sr * sizeof(int32_t))) return rc;
+    if (const int rc = grow(w.rays6, sr * 6, "the reflection rays")) return rc;
+    if (const int rc = grow(w.mean, sr * 3, "the reflection samples' radiance")) return rc;
+    if (const int rc = grow(w.ids, sr, "the reflection rays' ids")) return rc;
+    if (const int rc = grow(w.hits, sr, "the reflection samples' hits")) return rc;
     int rc = MCPT_OK;
     for (int64_t first = 0; first < texels && rc == MCPT_OK; first += per_chunk) {
         ReflChunk c{};
         c.p3 = d_p3; c.id_base = d_id_base; c.R = rp.res; c.S = rp.spp; c.sample_base = rp.sample_base; c.seed = rp.seed;
-        c.first_texel = first; c.texels = texels - first < per_chunk ? texels - first : per_chunk;
+        c.first_texel = first; c.texels = chunk_count(per_chunk, texels, first);
         c.rays6 = w.rays6.get(); c.ids = w.ids.get(); c.mean3 = w.mean.get(); c.hits = w.hits.get();
         const int64_t rays = c.texels * c.S;
         launch_reflection_rays(c, nullptr, rays, st);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) { rc = fail(MCPT_ERR_HIP, hipGetErrorString(e)); break; }
+        if ((rc = launch_result()) != MCPT_OK) break;
         mcpt_stats qs;
         rc = query_device(d, DQuery{w.rays6.get(), MCPT_QUERY_RAY, w.mean.get(), nullptr, w.hits.get()}, w.ids.get(), rays, 1, rp.sample_base, rp.seed,
                           rp.flags, stats ? &qs : nullptr, st);
         if (rc != MCPT_OK) break;
         if (stats) add_stats(*stats, qs);
         launch_reflection_fold(c, d_radiance, d_stderr, d_hits, st);
-        e = hipGetLastError();
-        if (e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
+        rc = launch_result();
     }
-    HIP_TRY(hipEventRecord(w.done.get(), st));              // also after a failure: kernels may be enqueued
-    if (rc != MCPT_OK) return rc;
+    if ((rc = l.end(rc)) != MCPT_OK) return rc;
     if (stats) {
         HIP_TRY(hipStreamSynchronize(st));
         stats->rays_primary = stats->samples = uint64_t(texels) * uint64_t(rp.spp);
@@ -244,31 +208,24 @@ int mcpt_bake_reflection(mcpt_device* d, const double* p3, const int32_t* id_bas
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n == 0) return MCPT_OK;
     const size_t sn = size_t(n), texels = sn * size_t(p->res) * size_t(p->res);
-    DevBuf<double> d_p, d_rad, d_err;
-    DevBuf<int32_t> d_base, d_hits;
-    if (const int rc = upload(d_p, p3, sn * 3, "the probe list")) return rc;
-    if (id_base)
-        if (const int rc = upload(d_base, id_base, sn, "the probes' id bases")) return rc;
-    if (const int rc = volume_alloc_result(d_rad.alloc_bytes(texels * 3 * sizeof(double)), "the probes' radiance", texels * 3 * sizeof(double))) return rc;
-    if (stderr3)
-        if (const int rc = volume_alloc_result(d_err.alloc_bytes(texels * 3 * sizeof(double)), "the probes' standard errors", texels * 3 * sizeof(double))) return rc;
-    if (hits)
-        if (const int rc = volume_alloc_result(d_hits.alloc_bytes(texels * sizeof(int32_t)), "the probes' hits", texels * sizeof(int32_t))) return rc;
-    hipStream_t st = d->stream.get();
-    if (const int rc = finish(bake_device(d, d_p.get(), id_base ? d_base.get() : nullptr, n, *p, d_rad.get(), stderr3 ? d_err.get() : nullptr,
-                                          hits ? d_hits.get() : nullptr, stats, st), st))
-        return rc;
-    HIP_TRY(hipMemcpy(radiance, d_rad.get(), texels * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (stderr3) HIP_TRY(hipMemcpy(stderr3, d_err.get(), texels * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (hits) HIP_TRY(hipMemcpy(hits, d_hits.get(), texels * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    Staging S(d->stream.get());
+    const double* d_p = nullptr;
+    const int32_t* d_base = nullptr;
+    double *d_rad = nullptr, *d_err = nullptr;
+    int32_t* d_hits = nullptr;
+    if (const int rc = S.in(p3, sn * 3, "the probe list", d_p)) return rc;
+    if (const int rc = S.in(id_base, sn, "the probes' id bases", d_base)) return rc;
+    if (const int rc = S.out(radiance, texels * 3, "the probes' radiance", d_rad)) return rc;
+    if (const int rc = S.out(stderr3, texels * 3, "the probes' standard errors", d_err)) return rc;
+    if (const int rc = S.out(hits, texels, "the probes' hits", d_hits)) return rc;
+    return S.finish(bake_device(d, d_p, d_base, n, *p, d_rad, d_err, d_hits, stats, d->stream.get()));
 }
 
 int mcpt_reflection_rays(mcpt_device* d, const double* p3, const int32_t* id_base, int64_t n, const mcpt_reflection_params* p, const int64_t* entry, int64_t m,
                          double* rays6, int32_t* ids)
 {
     if (const int rc = params_check(p, n)) return rc;
-    if (m < 0 || m > kInt32Max) return fail(MCPT_ERR_ARG, "the number of entries must be in 0 .. 2^31 - 1");
+    if (const int rc = count_check(m, "entries")) return rc;
     if (m > 0 && (!p3 || !entry || !rays6 || !ids)) return fail(MCPT_ERR_ARG, "null argument");
     const int64_t entries = n * p->res * p->res * p->spp;
     for (int64_t i = 0; i < m; i++)
@@ -278,26 +235,18 @@ int mcpt_reflection_rays(mcpt_device* d, const double* p3, const int32_t* id_bas
     if (const int rc = device_gate(d)) return rc;
     if (m == 0) return MCPT_OK;
     const size_t sn = size_t(n), sm = size_t(m);
-    DevBuf<double> d_p, d_rays;
-    DevBuf<int32_t> d_base, d_ids;
-    DevBuf<long long> d_entry;
-    static_assert(sizeof(long long) == sizeof(int64_t), "the entry list is int64");
-    if (const int rc = upload(d_p, p3, sn * 3, "the probe list")) return rc;
-    if (id_base)
-        if (const int rc = upload(d_base, id_base, sn, "the probes' id bases")) return rc;
-    if (const int rc = upload(d_entry, reinterpret_cast<const long long*>(entry), sm, "the entries")) return rc;
-    if (const int rc = volume_alloc_result(d_rays.alloc_bytes(sm * 6 * sizeof(double)), "the entries' rays", sm * 6 * sizeof(double))) return rc;
-    if (const int rc = volume_alloc_result(d_ids.alloc_bytes(sm * sizeof(int32_t)), "the entries' ids", sm * sizeof(int32_t))) return rc;
+    Staging S(d->stream.get());
     ReflChunk c{};
-    c.p3 = d_p.get(); c.id_base = id_base ? d_base.get() : nullptr; c.R = p->res; c.S = p->spp; c.sample_base = p->sample_base; c.seed = p->seed;
-    c.rays6 = d_rays.get(); c.ids = d_ids.get();
-    hipStream_t st = d->stream.get();
-    launch_reflection_rays(c, d_entry.get(), m, st);
-    const hipError_t el = hipGetLastError();
-    if (const int rc = finish(el == hipSuccess ? MCPT_OK : fail(MCPT_ERR_HIP, hipGetErrorString(el)), st)) return rc;
-    HIP_TRY(hipMemcpy(rays6, d_rays.get(), sm * 6 * sizeof(double), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ids, d_ids.get(), sm * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    const long long* d_entry = nullptr;
+    static_assert(sizeof(long long) == sizeof(int64_t), "the entry list is int64");
+    if (const int rc = S.in(p3, sn * 3, "the probe list", c.p3)) return rc;
+    if (const int rc = S.in(id_base, sn, "the probes' id bases", c.id_base)) return rc;
+    if (const int rc = S.in(reinterpret_cast<const long long*>(entry), sm, "the entries", d_entry)) return rc;
+    if (const int rc = S.out(rays6, sm * 6, "the entries' rays", c.rays6)) return rc;
+    if (const int rc = S.out(ids, sm, "the entries' ids", c.ids)) return rc;
+    c.R = p->res; c.S = p->spp; c.sample_base = p->sample_base; c.seed = p->seed;
+    launch_reflection_rays(c, d_entry, m, d->stream.get());
+    return S.finish(launch_result());
 }
 
 int mcpt_reflection_prefilter_host(const mcpt_reflection_chain* c, const double* radiance, int64_t n, double* chain)
@@ -324,8 +273,7 @@ int mcpt_reflection_prefilter_device(mcpt_device* d, const mcpt_reflection_chain
     if (const int rc = device_gate(d)) return rc;
     if (n == 0) return MCPT_OK;
     launch_reflection_prefilter(*c, d_radiance, n, d_chain, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MCPT_OK;
+    return launch_result();
 }
 
 int mcpt_reflection_prefilter(mcpt_device* d, const mcpt_reflection_chain* c, const double* radiance, int64_t n, double* chain)
@@ -336,15 +284,13 @@ int mcpt_reflection_prefilter(mcpt_device* d, const mcpt_reflection_chain* c, co
     if (const int rc = device_gate(d)) return rc;
     if (n == 0) return MCPT_OK;
     const size_t in = size_t(n) * size_t(c->res) * size_t(c->res) * 3, out = size_t(n) * size_t(reflection_chain_texels(*c)) * 3;
-    DevBuf<double> d_rad, d_chain;
-    if (const int rc = upload(d_rad, radiance, in, "the probes' radiance")) return rc;
-    if (const int rc = volume_alloc_result(d_chain.alloc_bytes(out * sizeof(double)), "the probes' chains", out * sizeof(double))) return rc;
-    hipStream_t st = d->stream.get();
-    launch_reflection_prefilter(*c, d_rad.get(), n, d_chain.get(), st);
-    const hipError_t el = hipGetLastError();
-    if (const int rc = finish(el == hipSuccess ? MCPT_OK : fail(MCPT_ERR_HIP, hipGetErrorString(el)), st)) return rc;
-    HIP_TRY(hipMemcpy(chain, d_chain.get(), out * sizeof(double), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    Staging S(d->stream.get());
+    const double* d_rad = nullptr;
+    double* d_chain = nullptr;
+    if (const int rc = S.in(radiance, in, "the probes' radiance", d_rad)) return rc;
+    if (const int rc = S.out(chain, out, "the probes' chains", d_chain)) return rc;
+    launch_reflection_prefilter(*c, d_rad, n, d_chain, d->stream.get());
+    return S.finish(launch_result());
 }
 
 int mcpt_reflection_lookup_host(const mcpt_reflection_chain* c, const double* chain, int64_t n, const int32_t* probe, const double* d3, const double* x,
@@ -365,8 +311,7 @@ int mcpt_reflection_lookup_device(mcpt_device* d, const mcpt_reflection_chain* c
     if (const int rc = device_gate(d)) return rc;
     if (m == 0) return MCPT_OK;
     launch_reflection_lookup(*c, d_chain, n, d_probe, d_d3, d_x, m, d_out3, static_cast<hipStream_t>(stream));
-    HIP_TRY(hipGetLastError());
-    return MCPT_OK;
+    return launch_result();
 }
 
 int mcpt_reflection_lookup(mcpt_device* d, const mcpt_reflection_chain* c, const double* chain, int64_t n, const int32_t* probe, const double* d3,
@@ -378,19 +323,17 @@ int mcpt_reflection_lookup(mcpt_device* d, const mcpt_reflection_chain* c, const
     if (const int rc = device_gate(d)) return rc;
     if (m == 0) return MCPT_OK;
     const size_t sm = size_t(m), texels = size_t(n) * size_t(reflection_chain_texels(*c));
-    DevBuf<double> d_chain, d_d, d_x, d_out;
-    DevBuf<int32_t> d_probe;
-    if (const int rc = upload(d_chain, chain, texels * 3, "the probes' chains")) return rc;
-    if (const int rc = upload(d_probe, probe, sm, "the receivers' probes")) return rc;
-    if (const int rc = upload(d_d, d3, sm * 3, "the receivers' directions")) return rc;
-    if (const int rc = upload(d_x, x, sm, "the receivers' exponents")) return rc;
-    if (const int rc = volume_alloc_result(d_out.alloc_bytes(sm * 3 * sizeof(double)), "the receivers' radiance", sm * 3 * sizeof(double))) return rc;
-    hipStream_t st = d->stream.get();
-    launch_reflection_lookup(*c, d_chain.get(), n, d_probe.get(), d_d.get(), d_x.get(), m, d_out.get(), st);
-    const hipError_t el = hipGetLastError();
-    if (const int rc = finish(el == hipSuccess ? MCPT_OK : fail(MCPT_ERR_HIP, hipGetErrorString(el)), st)) return rc;
-    HIP_TRY(hipMemcpy(out3, d_out.get(), sm * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    Staging S(d->stream.get());
+    const double *d_chain = nullptr, *d_d = nullptr, *d_x = nullptr;
+    const int32_t* d_probe = nullptr;
+    double* d_out = nullptr;
+    if (const int rc = S.in(chain, texels * 3, "the probes' chains", d_chain)) return rc;
+    if (const int rc = S.in(probe, sm, "the receivers' probes", d_probe)) return rc;
+    if (const int rc = S.in(d3, sm * 3, "the receivers' directions", d_d)) return rc;
+    if (const int rc = S.in(x, sm, "the receivers' exponents", d_x)) return rc;
+    if (const int rc = S.out(out3, sm * 3, "the receivers' radiance", d_out)) return rc;
+    launch_reflection_lookup(*c, d_chain, n, d_probe, d_d, d_x, m, d_out, d->stream.get());
+    return S.finish(launch_result());
 }
 
 }  // extern "C"

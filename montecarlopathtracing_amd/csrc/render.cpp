@@ -446,7 +446,7 @@ static int render_motion_frame(mcpt_device* d, const mcpt_render_params* p, doub
         mcpt_stats piece{};
         const int prc = render_device_impl(d, r, PixelList{d->pixels.get(), d->n_pixels}, p, d_img, stats ? &piece : nullptr, st, slot_used);
         if (prc != MCPT_OK && slot_used >= 0) d->slot[slot_used].keeping = false;      // its counters hold part of a frame
-        if (prc == MCPT_OK && stats) { add_counts(*stats, piece); stats->ms_trace += piece.ms_trace; stats->ms_total += piece.ms_total; }
+        if (prc == MCPT_OK && stats) add_piece(*stats, piece);
         return prc;
     });
     if (rc != MCPT_OK) { d->ev_used = ev_used0; d->frame_ev_used = frame_ev_used0; }

@@ -70,3 +70,10 @@ void add_counts(mcpt_stats& a, const mcpt_stats& b)
     a.launches += b.launches;
     a.max_depth = std::max(a.max_depth, b.max_depth);
 }
+
+void add_piece(mcpt_stats& a, const mcpt_stats& piece)
+{
+    add_counts(a, piece);
+    a.ms_trace += piece.ms_trace;
+    a.ms_total += piece.ms_total;
+}

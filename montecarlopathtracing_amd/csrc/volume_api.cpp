@@ -6,15 +6,12 @@
 
 #include <cmath>
 #include <cstring>
-#include <limits>
 #include <string>
 
 #include "handles.hpp"
 #include "volume.hpp"
 
 using namespace mcpt;
-
-static constexpr int64_t kInt32Max = std::numeric_limits<int32_t>::max();
 
 // what every call refuses of a grid, in the struct's field order
 int volume_grid_check(const mcpt_volume_grid* g)
@@ -36,7 +33,7 @@ int volume_grid_check(const mcpt_volume_grid* g)
 static int lookup_check(const mcpt_volume_grid* g, const void* sh27, const void* q6, int64_t n, const void* e3)
 {
     if (const int rc = volume_grid_check(g)) return rc;
-    if (n < 0 || n > kInt32Max) return fail(MCPT_ERR_ARG, "the number of receivers must be in 0 .. 2^31 - 1");
+    if (const int rc = count_check(n, "receivers")) return rc;
     if (n > 0 && (!sh27 || !q6 || !e3)) return fail(MCPT_ERR_ARG, "null coefficients, receiver list or irradiance");
     return MCPT_OK;
 }
@@ -57,53 +54,34 @@ int volume_arrays_check(const mcpt_volume_grid& g, const double* sh27, const dou
     return MCPT_OK;
 }
 
-// a failed allocation of a workspace or a copy: MCPT_ERR_NOMEM when the memory is not there, and the device stays usable
-int volume_alloc_result(hipError_t e, const char* what, size_t bytes)
+int volume_points_device(mcpt_device* d, const mcpt_volume_grid& g, hipStream_t st, Lease& l)
 {
-    if (e == hipSuccess) return MCPT_OK;
-    (void)hipGetLastError();                                    // the runtime keeps the failure as its last error: it has been reported here
-    if (e == hipErrorOutOfMemory || e == hipErrorMemoryAllocation)
-        return fail(MCPT_ERR_NOMEM, std::string(what) + " (" + std::to_string(bytes) + " bytes) cannot be allocated");
-    return fail(MCPT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    if (const int rc = lease(d->vol, st, l)) return rc;    // the bake before this one has read its points
+    if (const int rc = grow(d->vol->p3, size_t(volume_probes(g)) * 3, "the volume's probe positions")) return rc;
+    launch_volume_points(g, d->vol->p3.get(), st);
+    return launch_result();
 }
 
 // The bake on st, after the refusals; device pointers throughout.  Nothing here waits for st but the query itself, as mcpt_query_sh_device does.
 static int bake_device(mcpt_device* d, const mcpt_volume_grid& g, const mcpt_sh_params& p, double* d_sh, double* d_err, int32_t* d_hits, mcpt_stats* stats,
                        hipStream_t st)
 {
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
-    HIP_TRY(hipSetDevice(d->ordinal));
+    if (const int rc = device_gate(d)) return rc;
     if (stats) std::memset(stats, 0, sizeof *stats);
-    if (!d->vol) {
-        auto v = std::make_unique<mcpt_device::Volume>();
-        HIP_TRY(create(v->done, hipEventCreateWithFlags, hipEventDisableTiming));
-        d->vol = std::move(v);
-    }
-    mcpt_device::Volume& v = *d->vol;
-    HIP_TRY(hipEventSynchronize(v.done.get()));                 // the bake before this one has read its points
-    const int64_t n = volume_probes(g);
-    const size_t bytes = size_t(n) * 3 * sizeof(double);
-    if (const int rc = volume_alloc_result(v.p3.grow_bytes(bytes), "the volume's probe positions", bytes)) return rc;
-    launch_volume_points(g, v.p3.get(), st);
-    HIP_TRY(hipGetLastError());
-    const int rc = query_device(d, DQuery{v.p3.get(), MCPT_QUERY_KIND_SPHERE, d_sh, d_err, d_hits}, nullptr, n, p.spp, p.sample_base, p.seed, p.flags,
-                                stats, st);
-    HIP_TRY(hipEventRecord(v.done.get(), st));                  // also after a failure: k_vol_points is enqueued
-    return rc;
+    Lease l;
+    if (const int rc = volume_points_device(d, g, st, l)) return rc;
+    return l.end(query_device(d, DQuery{d->vol->p3.get(), MCPT_QUERY_KIND_SPHERE, d_sh, d_err, d_hits}, nullptr, volume_probes(g), p.spp, p.sample_base,
+                              p.seed, p.flags, stats, st));
 }
 
 // the lookup on st, after the refusals: it allocates nothing and never waits
 static int lookup_device(mcpt_device* d, const mcpt_volume_grid& g, const double* d_sh, const uint8_t* d_valid, const double* d_q6, int64_t n, double* d_e3,
                          int32_t* d_corners, hipStream_t st)
 {
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (const int rc = device_gate(d)) return rc;
     if (n == 0) return MCPT_OK;
-    HIP_TRY(hipSetDevice(d->ordinal));
     launch_volume_irradiance(g, d_sh, d_valid, d_q6, n, d_e3, d_corners, st);
-    HIP_TRY(hipGetLastError());
-    return MCPT_OK;
+    return launch_result();
 }
 
 extern "C" {
@@ -137,25 +115,15 @@ int mcpt_bake_volume(mcpt_device* d, const mcpt_volume_grid* g, const mcpt_sh_pa
     if (!g || !p) return fail(MCPT_ERR_ARG, "null volume grid or probe parameters");
     if (const int rc = volume_grid_check(g)) return rc;
     if (const int rc = sh_params_check(p, volume_probes(*g), g, sh27)) return rc;
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
-    HIP_TRY(hipSetDevice(d->ordinal));
-    const size_t n = size_t(volume_probes(*g)), bytes = n * MCPT_SH_N * 3 * sizeof(double);
-    DevBuf<double> d_sh, d_err;
-    DevBuf<int32_t> d_hits;
-    if (const int rc = volume_alloc_result(d_sh.alloc_bytes(bytes), "the volume's coefficients", bytes)) return rc;
-    if (stderr27)
-        if (const int rc = volume_alloc_result(d_err.alloc_bytes(bytes), "the volume's standard errors", bytes)) return rc;
-    if (hits) HIP_TRY(d_hits.alloc(n));
-    hipStream_t st = d->stream.get();
-    int rc = bake_device(d, *g, *p, d_sh.get(), d_err.get(), d_hits.get(), stats, st);
-    const hipError_t e = hipStreamSynchronize(st);              // also on failure: nothing enqueued may still use a copy when it goes
-    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    if (rc != MCPT_OK) return rc;
-    HIP_TRY(hipMemcpy(sh27, d_sh.get(), bytes, hipMemcpyDeviceToHost));
-    if (stderr27) HIP_TRY(hipMemcpy(stderr27, d_err.get(), bytes, hipMemcpyDeviceToHost));
-    if (hits) HIP_TRY(hipMemcpy(hits, d_hits.get(), n * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    if (const int rc = device_gate(d)) return rc;
+    const size_t n = size_t(volume_probes(*g));
+    Staging S(d->stream.get());
+    double *d_sh = nullptr, *d_err = nullptr;
+    int32_t* d_hits = nullptr;
+    if (const int rc = S.out(sh27, n * MCPT_SH_N * 3, "the volume's coefficients", d_sh)) return rc;
+    if (const int rc = S.out(stderr27, n * MCPT_SH_N * 3, "the volume's standard errors", d_err)) return rc;
+    if (const int rc = S.out(hits, n, "the volume's hits", d_hits)) return rc;
+    return S.finish(bake_device(d, *g, *p, d_sh, d_err, d_hits, stats, d->stream.get()));
 }
 
 int mcpt_volume_irradiance_host(const mcpt_volume_grid* g, const double* sh27, const uint8_t* valid, const double* q6, int64_t n, double* e3,
@@ -189,30 +157,20 @@ int mcpt_volume_irradiance(mcpt_device* d, const mcpt_volume_grid* g, const doub
     if (const int rc = lookup_check(g, sh27, q6, n, e3)) return rc;
     if (n > 0)
         if (const int rc = volume_arrays_check(*g, sh27, q6, n)) return rc;
-    if (const int rc = require_device()) return rc;
-    if (!d) return fail(MCPT_ERR_ARG, "null device");
+    if (const int rc = device_gate(d)) return rc;
     if (n == 0) return MCPT_OK;
-    HIP_TRY(hipSetDevice(d->ordinal));
-    const size_t probes = size_t(volume_probes(*g)), sn = size_t(n), sh_bytes = probes * MCPT_SH_N * 3 * sizeof(double);
-    DevBuf<double> d_sh, d_q, d_e;
-    DevBuf<uint8_t> d_valid;
-    DevBuf<int32_t> d_corners;
-    if (const int rc = volume_alloc_result(d_sh.alloc_bytes(sh_bytes), "the volume's coefficients", sh_bytes)) return rc;
-    if (const int rc = volume_alloc_result(d_q.alloc_bytes(sn * 6 * sizeof(double)), "the receiver list", sn * 6 * sizeof(double))) return rc;
-    if (const int rc = volume_alloc_result(d_e.alloc_bytes(sn * 3 * sizeof(double)), "the receivers' irradiance", sn * 3 * sizeof(double))) return rc;
-    if (valid) HIP_TRY(d_valid.alloc(probes));
-    if (corners) HIP_TRY(d_corners.alloc(sn));
-    HIP_TRY(hipMemcpy(d_sh.get(), sh27, sh_bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_q.get(), q6, sn * 6 * sizeof(double), hipMemcpyHostToDevice));
-    if (valid) HIP_TRY(hipMemcpy(d_valid.get(), valid, probes, hipMemcpyHostToDevice));
-    hipStream_t st = d->stream.get();
-    int rc = lookup_device(d, *g, d_sh.get(), d_valid.get(), d_q.get(), n, d_e.get(), d_corners.get(), st);
-    const hipError_t e = hipStreamSynchronize(st);              // also on failure: nothing enqueued may still use a copy when it goes
-    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    if (rc != MCPT_OK) return rc;
-    HIP_TRY(hipMemcpy(e3, d_e.get(), sn * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (corners) HIP_TRY(hipMemcpy(corners, d_corners.get(), sn * sizeof(int32_t), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    const size_t probes = size_t(volume_probes(*g)), sn = size_t(n);
+    Staging S(d->stream.get());
+    const double *d_sh = nullptr, *d_q = nullptr;
+    const uint8_t* d_valid = nullptr;
+    double* d_e = nullptr;
+    int32_t* d_corners = nullptr;
+    if (const int rc = S.in(sh27, probes * MCPT_SH_N * 3, "the volume's coefficients", d_sh)) return rc;
+    if (const int rc = S.in(q6, sn * 6, "the receiver list", d_q)) return rc;
+    if (const int rc = S.in(valid, probes, "the volume's mask", d_valid)) return rc;
+    if (const int rc = S.out(e3, sn * 3, "the receivers' irradiance", d_e)) return rc;
+    if (const int rc = S.out(corners, sn, "the receivers' corners", d_corners)) return rc;
+    return S.finish(lookup_device(d, *g, d_sh, d_valid, d_q, n, d_e, d_corners, d->stream.get()));
 }
 
 }  // extern "C"
