@@ -239,10 +239,11 @@ struct CwHits { float key[4]; int ref[4]; };
 
 // One step on a compressed node: which children may contain a candidate, sorted by lower bound of entry distance
 // (absent / culled children get key = +inf, ref = EMPTY).
-__device__ __forceinline__ CwHits cw_step(const CwNode* __restrict__ nd, const RayF& f, float limit_f)
+// The step on the node's 16 words.  kLimit = false: a ray without a leader (limit = +inf) -- the comparison with the limit decides
+// nothing there (an entry that is NaN already fails entry <= exit), so the decisions are those of kLimit = true at limit_f = +inf.
+template <bool kLimit>
+__device__ __forceinline__ CwHits cw_step_words(const uint4& w0, const uint4& w1, const uint4& w2, const uint4& w3, const RayF& f, float limit_f)
 {
-    const uint4* q = reinterpret_cast<const uint4*>(nd);
-    const uint4 w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3];
     const float p[3] = {__uint_as_float(w0.x), __uint_as_float(w0.y), __uint_as_float(w0.z)};
     const int e[3] = {(int)(signed char)(w0.w & 255u), (int)(signed char)((w0.w >> 8) & 255u), (int)(signed char)((w0.w >> 16) & 255u)};
     const unsigned qlo[3] = {w1.x, w1.y, w1.z}, qhi[3] = {w1.w, w2.x, w2.y};
@@ -271,7 +272,7 @@ __device__ __forceinline__ CwHits cw_step(const CwNode* __restrict__ nd, const R
         const float tfz = fmaf((float)((farw[2] >> (8 * c)) & 255u), sr[2], prhi[2]);
         const float entry = fmaxf(fmaxf(tnx, tny), tnz);
         const float exit = fminf(fminf(tfx, tfy), tfz);
-        const bool hit = child[c] != MCPT_FAST_EMPTY && exit >= 0.0f && entry <= exit && entry <= limit_f;
+        const bool hit = child[c] != MCPT_FAST_EMPTY && exit >= 0.0f && entry <= exit && (!kLimit || entry <= limit_f);
         h.key[c] = hit ? entry : __builtin_inff();
         h.ref[c] = hit ? child[c] : MCPT_FAST_EMPTY;
     }
@@ -286,6 +287,22 @@ __device__ __forceinline__ CwHits cw_step(const CwNode* __restrict__ nd, const R
     MCPT_CSWAP(0, 1) MCPT_CSWAP(2, 3) MCPT_CSWAP(0, 2) MCPT_CSWAP(1, 3) MCPT_CSWAP(1, 2)
 #undef MCPT_CSWAP
     return h;
+}
+__device__ __forceinline__ CwHits cw_step(const CwNode* __restrict__ nd, const RayF& f, float limit_f)
+{
+    const uint4* q = reinterpret_cast<const uint4*>(nd);
+    return cw_step_words<true>(q[0], q[1], q[2], q[3], f, limit_f);
+}
+// The same step on a node every lane of the wave is on (the root, for rays that start their walk) and without a limit: the node's words
+// come by scalar loads through the constant address space, and what only depends on them -- exponents, child words -- is scalar work.
+// The nodes are only rewritten between launches (refit), and the scalar cache is invalidated when a kernel starts.
+typedef unsigned int cw_u4 __attribute__((ext_vector_type(4)));
+typedef const cw_u4 __attribute__((address_space(4)))* CwNodeWords;
+__device__ __forceinline__ CwHits cw_step_uniform(CwNodeWords q, const RayF& f)
+{
+    const cw_u4 v0 = q[0], v1 = q[1], v2 = q[2], v3 = q[3];
+    return cw_step_words<false>(make_uint4(v0.x, v0.y, v0.z, v0.w), make_uint4(v1.x, v1.y, v1.z, v1.w), make_uint4(v2.x, v2.y, v2.z, v2.w),
+                                make_uint4(v3.x, v3.y, v3.z, v3.w), f, __builtin_inff());
 }
 
 // One ray per lane, start to finish (while-while over the compressed hierarchy): the same decisions, in the same order

@@ -21,6 +21,10 @@
 //   * Only the first MCPT_POOL_STACK entries of a slot's traversal stack are in LDS; the deeper ones (a tenth of the rays get there)
 //     live in a global spill area behind the launch's deferred-ray list, [block][entry][slot].  A ray that would pass the walk's
 //     stack_cap goes to the deferred list (one-lane walk), like in the persistent engine.
+//   * A ray's first two node steps -- on the root, the same node in every lane, and on its nearest child where that is an inner node --
+//     are taken by the refill step that loads the ray, while it is in registers: every lane that got a ray takes part, where a node
+//     step of the pool runs with the lanes that happen to wait for one.  (Path mode files its rays at the root: the SHADE step runs
+//     at 24 lanes and holds the vertex code's registers.)
 // The decisions are the persistent engine's, test for test (same cw_step, tri_pre_reject, tri_hit, ranking, own-box check at the end),
 // so results are bit-identical to it and to the reference-shaped walk.
 //
@@ -123,6 +127,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                                            const PP& pp = PP())
 {
     static_assert(KT <= 32, "one 32-bit set per class");
+    static_assert(SCAP >= 6, "the pushes of a ray's first two steps land in LDS");
     enum { C_INNER = 0, C_LEAF = 1, C_EXACT = 2, C_FIN = 3, C_SHADE = 4, C_DEAD = 5 };
     enum { F_FOUND = 256, F_AMBIG = 512, F_RAY = 1024, F_OWNFAIL = 2048 /* the leader's own box does not pass the reference's box test */ };
     const DFast& F = S.fast;
@@ -276,7 +281,8 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
         if (c == C_INNER) {
             // ---------------------------------------------------------------- one step on a compressed node
             // (a lane that stays on nodes taking its next node step at once -- no filing, vote, claim and reload in between, at the lanes
-            // that happen to go on -- was measured in round 4: no difference at two, three or four steps in a row)
+            // that happen to go on -- was measured in round 4: no difference at two, three or four steps in a row.  The steps every ray
+            // takes with nearly all its lanes, on the root and on its nearest child, are taken in the refill below.)
             bool refused = false;
             if (have) {
                 const int cur = L.cur[idx];
@@ -674,9 +680,14 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 got = have && rank_need < n_ok;
                 __asm__ volatile("" ::: "memory");
                 const int from = got ? L.tbl[wave * 64 + rank_need] : lane;
+                // The root's words, for the first step below: scalar loads, issued here where rays are fetched (a refill that finds the
+                // queue dry loads nothing) and, like the launch's arguments (wf_ray_source.hpp), not held in registers across the walk loop.
+                CwNodeWords root = (CwNodeWords)nodes;
+                __asm__ volatile("" : "+s"(root));
                 Ray r;
                 r.o.x = __shfl(nr.o.x, from, 64); r.o.y = __shfl(nr.o.y, from, 64); r.o.z = __shfl(nr.o.z, from, 64);
                 r.d.x = __shfl(nr.d.x, from, 64); r.d.y = __shfl(nr.d.y, from, 64); r.d.z = __shfl(nr.d.z, from, 64);
+                bool second = false;                    // this lane's ray also took a step on its nearest root child
                 if (got) {
                     const V3 rcp = mk(fast_rcp(r.d.x), fast_rcp(r.d.y), fast_rcp(r.d.z));
                     PoolOxy b0; b0.ox = r.o.x; b0.oy = r.o.y;
@@ -685,15 +696,50 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                     PoolRcp b4; b4.rx = (float)rcp.x; b4.ry = (float)rcp.y; b4.rz = (float)rcp.z; b4.limit = __builtin_inff();
                     L.oxy[idx] = b0; L.ozdx[idx] = b1; L.dyz[idx] = b2; L.rcp[idx] = b4;
                     L.best_t[idx] = 0;
-                    L.cur[idx] = 0; L.best_leaf[idx] = -1; L.spf[idx] = F_RAY;
+                    L.best_leaf[idx] = -1;
                     L.q[idx] = (unsigned int)(next + from);
-                    nc = C_INNER;
+                    // Every walk starts on node 0, so the ray takes that step here, where it is in registers and every lane that got a
+                    // ray takes part: no filing, vote, claim and reload for it, and a node that is the same in all lanes (cw_step_uniform).
+                    // A ray whose nearest root child is an inner node takes that step too, at once (the ordinary cw_step: most lanes go on,
+                    // the top of a tree is inner nodes).  The floats are formed by the node step's own expressions; the pushes, the pop,
+                    // the refusal and the decode are its own, so the walk goes on exactly as if the slot had been filed at the root.
+                    // sp <= 3 before the second step: the pushes of both land in the LDS part of the stack, and the root step cannot be
+                    // refused (sp = 0, a device's stack_cap is at least 4).  A third step could pass the LDS part: not taken here.
+                    {
+                        RayF rf;
+                        rf.o[0] = (float)b0.ox; rf.o[1] = (float)b0.oy; rf.o[2] = (float)b1.oz;
+                        rf.r[0] = b4.rx; rf.r[1] = b4.ry; rf.r[2] = b4.rz;
+                        rf.pad[0] = pad_of(rf.o[0], b4.rx); rf.pad[1] = pad_of(rf.o[1], b4.ry); rf.pad[2] = pad_of(rf.o[2], b4.rz);
+                        int* const col = &L.stack[k * 64 + lane];
+                        int sp = 0;
+                        // (the node step's three predicated stores and its pop)
+                        auto push_hits = [&](const CwHits& h) __attribute__((always_inline)) -> int {
+                            const int n_hit = (h.ref[0] != MCPT_FAST_EMPTY) + (h.ref[1] != MCPT_FAST_EMPTY) + (h.ref[2] != MCPT_FAST_EMPTY) + (h.ref[3] != MCPT_FAST_EMPTY);
+                            if (n_hit >= 4) col[sp * (KT * 64)] = h.ref[3];
+                            if (n_hit >= 3) col[(sp + n_hit - 3) * (KT * 64)] = h.ref[2];
+                            if (n_hit >= 2) col[(sp + n_hit - 2) * (KT * 64)] = h.ref[1];
+                            sp += n_hit > 1 ? n_hit - 1 : 0;
+                            int nx = h.ref[0];
+                            if (nx == MCPT_FAST_EMPTY && sp > 0) { sp--; nx = col[sp * (KT * 64)]; }
+                            return nx;
+                        };
+                        int nxt = push_hits(cw_step_uniform(root, rf));
+                        second = nxt >= 0 && !(sp > stack_cap - 3);       // (a ray the node step would refuse is filed as it is: it refuses)
+                        if (second) nxt = push_hits(cw_step(nodes + nxt, rf, __builtin_inff()));
+                        const bool node = nxt >= 0, none = nxt == MCPT_FAST_EMPTY;
+                        const int ref = -1 - nxt;
+                        L.cur[idx] = none ? 0 : (node ? nxt : ref >> 4);
+                        L.spf[idx] = F_RAY | sp | ((!node && !none) ? ((ref & 7) + 1) << 16 : 0);
+                        nc = node ? C_INNER : (none ? C_FIN : C_LEAF);       // (no child hit: the next result step stores the miss)
+                    }
                 }
                 next += used;
 #ifdef MCPT_POOL_DEBUG
                 d_used += used; d_okc += __popcll(__ballot(ok && lane < used)); d_steps++;
 #endif
-                c_rays += (unsigned int)__popcll(__ballot(got));
+                const unsigned int n_got = (unsigned int)__popcll(__ballot(got));
+                c_rays += n_got;
+                c_nodes += n_got + (unsigned int)__popcll(__ballot(got && second));
             }
             if (have && !got) {
                 if (queue_empty && all_dry) nc = C_DEAD;           // no ray left for this slot, in any wave
