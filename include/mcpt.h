@@ -1343,7 +1343,7 @@ int mcpt_volume_irradiance_visible_device(mcpt_device*, const mcpt_volume_grid*,
  *              mcpt_baked_outputs, every pointer may be NULL: radiance3[n][3], kind[n], face[n] (the .obj index, -1: a miss), q6[n][6]
  *              (p and the n that went into the lookup), uv2[n][2] (+0.0 under a volume), kd3[n][3], e3[n][3], lit[n].  For a ray that
  *              is not a surface hit everything but radiance3, kind and face is +0.0 or 0.  Glass and mirrors show kd * E / pi like any
- *              other surface.  stats: rays_primary = samples = n, launches = the number of chunks (of at most 4 194 304 rays).
+ *              other surface here; mcpt_baked_radiance_specular (baked specular, below) adds their ks * R.  stats: rays_primary = samples = n, launches = the number of chunks (of at most 4 194 304 rays).
  *   frame    : mcpt_render_baked*.  For every pixel of the device's frame, sample k = 0 .. samples - 1 is the frame's own camera ray of
  *              (pixel, k): mcpt_camera_rays of (seed, pixel, k) under the device's lens, shaded as above under `flags`.
  *              img[pixel][c] = s / double(samples), s = 0.0 + L_0 + ... in k order: mcpt_render's layout, so mcpt_display_device takes
@@ -1366,7 +1366,7 @@ int mcpt_volume_irradiance_visible_device(mcpt_device*, const mcpt_volume_grid*,
  * host-pointer forms a chart component that is not finite is MCPT_ERR_ARG as well -- after the missing device and the NULL device, because
  * the chart's length is the device's face count.  THE DEVICE FORMS DO NOT LOOK AT THEIR ARRAYS and read no texel or probe outside their
  * tables.  n == 0: MCPT_OK, nothing is launched.  A workspace or a copy that cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable.
- * Not covered: direct light or shadows added on top of the bake; specular or glass transport; standard errors of a baked frame;
+ * Not covered: direct light or shadows added on top of the bake; glass transport (refraction); standard errors of a baked frame;
  * mip-mapping or anisotropic filtering of the map; chart-aware taps beyond the owner rule; partitions, the multi-device group and
  * render_scene; a baked source inside the progressive handles. */
 #define MCPT_BAKED_VOLUME    1
@@ -1474,8 +1474,9 @@ int mcpt_render_baked_device(mcpt_device*, const mcpt_baked_source*, const mcpt_
  * that is zero, not finite or whose l overflows, a probe index outside 0 .. n - 1, an x that is not finite or < 0.
  * mcpt_reflection_texels: res outside 1 .. 256.  n == 0 (the lookup: m == 0): MCPT_OK, nothing is launched.  A workspace or a copy
  * that cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable.
- * Not covered: a specular term in baked frames; choosing or blending probes by position; parallax correction; GGX or other lobes, and
- * real-valued level exponents; fp32 or fp16 storage; adaptive stopping; the multi-device group and render_scene. */
+ * Not covered: parallax correction; nearest-probe choice and irregular probe sets; GGX or other lobes, and real-valued level exponents;
+ * fp32 or fp16 storage; adaptive stopping; the multi-device group and render_scene.  (A specular term in baked frames and choosing or
+ * blending probes by position stood here; the baked specular block below adds both, for probes on a volume grid.) */
 typedef struct { int32_t spp, sample_base; uint64_t seed; int32_t res, flags; int64_t workspace_rays; int32_t reserved[4]; } mcpt_reflection_params;
 typedef struct { int32_t res, num_levels; int32_t level_res[8], level_ns[8]; int32_t reserved[4]; } mcpt_reflection_chain;
 int mcpt_reflection_texels(int32_t res, double* d3, double* w);
@@ -1495,6 +1496,89 @@ int mcpt_reflection_lookup(mcpt_device*, const mcpt_reflection_chain*, const dou
                            const double* d3, const double* x, int64_t m, double* out3);
 int mcpt_reflection_lookup_device(mcpt_device*, const mcpt_reflection_chain*, const double* d_chain, int64_t n, const int32_t* d_probe,
                                   const double* d_d3, const double* d_x, int64_t m, double* d_out3, void* stream);
+
+/* ---- baked specular (since the baked-specular change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* A REFLECTION VOLUME is a chain of reflection probes on every probe of an mcpt_volume_grid; it is looked up by position with the corners
+ * and weights of the irradiance volume, and BAKED SPECULAR adds what it holds along the mirror direction to the surface samples of baked
+ * radiance and baked frames: L = kd * E / pi + ks * R(reflect(d, n), Ns).  Three layers, each a test seam of the next: the reflection
+ * volume's lookup, the baked radiance with a specular term, the frame.  fp64, no contraction, IEEE division, every expression and sum in
+ * the order written; every output is one lane's fixed-order sum: the same bits on the host and on the GPU, whatever the launch shape and
+ * the chunking.
+ *   reflection volume lookup : mcpt_reflection_volume_lookup*.  grid as mcpt_volume_irradiance takes it (its flags are not read), a chain
+ *              description as mcpt_reflection_lookup takes it, chain[nprobes][T][3] with the probes' rows in mcpt_volume_points' order,
+ *              valid[nprobes] or NULL, moments (with visibility) or NULL.  Receiver i has q6[i] = (position, normal), a direction d3[i] of
+ *              any non-zero finite length and an exponent x[i], finite and >= 0.
+ *                P_j, w_j, j = 0 .. 7 = the corners and weights mcpt_volume_irradiance forms at q6[i] -- the snap, the mask and its
+ *                renormalisation -- and with moments != NULL those of mcpt_volume_irradiance_visible, normal_bias included;
+ *                v_j = mcpt_reflection_lookup's value for the chain of probe P_j, direction d3[i] and exponent x[i];
+ *                out_c = sum_j w_j * v_j,c in j order from 0.0, where a corner with w_j == 0.0 contributes nothing and is not read;
+ *                corners[i] (may be NULL) = the number of j with w_j > 0; with none out = +0.0.
+ *              Hence a receiver on a probe reads that probe's mcpt_reflection_lookup, bit for bit.  (The level or levels of x, the blend
+ *              factor a and each level's four wrapped taps and weights depend on d3[i] and x[i] alone: they are formed once per receiver
+ *              and serve all eight corners; v_j is mcpt_reflection_lookup's expression tap by tap, with (1.0 - a) formed once.)
+ *   specular source : mcpt_baked_specular: flags 0 (pad is not read); grid, chain, chain_data, valid (may be NULL), moments (may be NULL)
+ *              and visibility (with moments) as above.  In the host-pointer calls chain_data, valid and moments are host pointers, in the
+ *              _device calls device pointers (grid, chain and visibility are always host structs).
+ *   baked radiance : mcpt_baked_radiance_specular*.  The rays, the closest hit, kind, face, q6, uv2, kd3, e3 and lit are
+ *              mcpt_baked_radiance's under the same source and flags, bit for bit; D = its radiance.  For a SURFACE hit whose material
+ *              has a ks component != 0.0, with d the ray's direction and n = q6[3..5] -- the normal that went into the diffuse lookup,
+ *              after the fallback to the face's normal and after MCPT_BAKED_FACE_VIEWER:
+ *                dn = (dx nx + dy ny) + dz nz;  nn = (nx nx + ny ny) + nz nz;
+ *                r_c = d_c * nn - n_c * (2.0 * dn)   -- the mirror direction scaled by |n|^2: no division, the same for n and -n;
+ *                l = (|rx| + |ry|) + |rz|; unless l > 0.0 and l is finite there is no specular term;
+ *                x = Ns >= 0.0 ? Ns : 0.0;   R, slit = the reflection volume lookup's out and corners at (q6, r, x);
+ *                L_c = D_c + ks_c * R_c; under MCPT_BAKED_LIGHTING_ONLY L_c = D_c + R_c.
+ *              Everywhere else L = D.  Materials with Ni > 1 (glass) are treated by their ks like any other.
+ *              mcpt_baked_specular_outputs (may be NULL, and so may every pointer of it): spec3[n][3] = R, ks3[n][3], r3[n][3], ns[n] =
+ *              the material's Ns, slit[n]; +0.0 or 0 for every ray without a specular term.  stats and chunks: mcpt_baked_radiance's.
+ *   frame    : mcpt_render_baked_specular*: mcpt_render_baked with every sample shaded as above; img, counts3 and lit as there;
+ *              slit[pixel] (may be NULL) = the samples whose specular lookup had slit > 0.
+ * mcpt_reflection_volume_lookup_host runs on the CPU and needs no device.  The host-pointer forms are synchronous and copy in and out
+ * around the _device forms.  The _device forms take device pointers throughout and enqueue on `stream`.
+ * mcpt_baked_radiance_specular_device and mcpt_render_baked_specular_device keep a workspace on the device (the baked calls' own: 116
+ * bytes per ray of the largest chunk so far, 120 for a frame that asks for slit), first wait for the event behind the device's previous
+ * baked call, and return without waiting when stats == NULL (the first frame of a device also makes the lens's image-plane points and
+ * waits for them); they use the counters and queue words of mcpt_trace_closest_device and, like it, must not overlap another closest-hit
+ * call of the same device on another stream.  The reflection volume lookup never waits and allocates nothing.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE, in this order).  The lookup: the grid's errors (NULL first); the chain's errors in
+ * mcpt_reflection_lookup's order; with moments a NULL visibility and then its errors; m < 0 or m > 2^31 - 1; NULL chain, q6, d3, x or
+ * out3 with m > 0; the host-pointer forms: a chain value that is not finite, then per receiver a component of q6 that is not finite, a
+ * normal of zero or non-finite length, a direction that is zero, not finite or whose l overflows, an x that is not finite or < 0.
+ * The baked calls: the diffuse source's errors as in the plain calls; the specular source: NULL; flags != 0; reserved != 0; the grid's
+ * errors (NULL first); the chain's errors; NULL chain_data; with moments a NULL visibility and then its errors; then the call's own
+ * errors as in the plain calls (mcpt_baked_radiance*: flags, n, NULL rays6, NULL outputs, outputs' reserved; mcpt_render_baked*: NULL
+ * parameters, samples, flags, workspace_rays, reserved, NULL img); last mcpt_baked_specular_outputs' reserved != 0.  A chart component
+ * that is not finite: as in the plain calls.  THE DEVICE FORMS DO NOT LOOK AT THEIR ARRAYS and read no texel, bin or probe outside their
+ * tables.  n == 0 (the lookup: m == 0): MCPT_OK, nothing is launched.  A workspace or a copy that cannot be allocated: MCPT_ERR_NOMEM,
+ * and the device stays usable.
+ * Not covered: parallax correction; refraction and glass transport; nearest-probe choice and irregular probe sets; weighting the two
+ * lobes by the path tracer's lobe-pick probability; a specular source inside the progressive handles; partitions, the multi-device group
+ * and render_scene. */
+typedef struct { int32_t flags, pad;
+                 const mcpt_volume_grid* grid; const mcpt_reflection_chain* chain; const double* chain_data;
+                 const uint8_t* valid; const double* moments; const mcpt_volume_visibility* visibility;
+                 int64_t reserved[4]; } mcpt_baked_specular;
+typedef struct { double* spec3; double* ks3; double* r3; double* ns; int32_t* slit; int64_t reserved[2]; } mcpt_baked_specular_outputs;
+int mcpt_reflection_volume_lookup_host(const mcpt_volume_grid*, const mcpt_reflection_chain*, const double* chain, const uint8_t* valid,
+                                       const double* moments, const mcpt_volume_visibility*, const double* q6, const double* d3,
+                                       const double* x, int64_t m, double* out3, int32_t* corners);
+int mcpt_reflection_volume_lookup(mcpt_device*, const mcpt_volume_grid*, const mcpt_reflection_chain*, const double* chain,
+                                  const uint8_t* valid, const double* moments, const mcpt_volume_visibility*, const double* q6,
+                                  const double* d3, const double* x, int64_t m, double* out3, int32_t* corners);
+int mcpt_reflection_volume_lookup_device(mcpt_device*, const mcpt_volume_grid*, const mcpt_reflection_chain*, const double* d_chain,
+                                         const uint8_t* d_valid, const double* d_moments, const mcpt_volume_visibility*,
+                                         const double* d_q6, const double* d_d3, const double* d_x, int64_t m, double* d_out3,
+                                         int32_t* d_corners, void* stream);
+int mcpt_baked_radiance_specular(mcpt_device*, const mcpt_baked_source*, const mcpt_baked_specular*, const double* rays6, int64_t n,
+                                 int32_t flags, const mcpt_baked_outputs*, const mcpt_baked_specular_outputs*, mcpt_stats*);
+int mcpt_baked_radiance_specular_device(mcpt_device*, const mcpt_baked_source*, const mcpt_baked_specular*, const double* d_rays6,
+                                        int64_t n, int32_t flags, const mcpt_baked_outputs*, const mcpt_baked_specular_outputs*,
+                                        mcpt_stats*, void* stream);
+int mcpt_render_baked_specular(mcpt_device*, const mcpt_baked_source*, const mcpt_baked_specular*, const mcpt_baked_frame_params*,
+                               double* img, int32_t* counts3, int32_t* lit, int32_t* slit, mcpt_stats*);
+int mcpt_render_baked_specular_device(mcpt_device*, const mcpt_baked_source*, const mcpt_baked_specular*,
+                                      const mcpt_baked_frame_params*, double* d_img, int32_t* d_counts3, int32_t* d_lit,
+                                      int32_t* d_slit, mcpt_stats*, void* stream);
 
 #ifdef __cplusplus
 }

@@ -238,6 +238,20 @@ class ReflectionChain(C.Structure):
         return sum(self.level_res[l] ** 2 for l in range(max(0, min(self.num_levels, 8))))
 
 
+class BakedSpecular(C.Structure):
+    """mcpt_baked_specular: the reflection volume a baked call adds ks * R from -- grid, chain description, chain data, valid, moments
+    and visibility; api.baked_reflection makes the Python-side holder"""
+    _fields_ = [("flags", C.c_int32), ("pad", C.c_int32), ("grid", C.POINTER(VolumeGrid)), ("chain", C.POINTER(ReflectionChain)),
+                ("chain_data", C.c_void_p), ("valid", C.c_void_p), ("moments", C.c_void_p), ("visibility", C.POINTER(VolumeVisibility)),
+                ("reserved", C.c_int64 * 4)]
+
+
+class BakedSpecularOutputs(C.Structure):
+    """mcpt_baked_specular_outputs: where mcpt_baked_radiance_specular puts the specular term's parts, ray by ray; every pointer may be null"""
+    _fields_ = [("spec3", C.c_void_p), ("ks3", C.c_void_p), ("r3", C.c_void_p), ("ns", C.c_void_p), ("slit", C.c_void_p),
+                ("reserved", C.c_int64 * 2)]
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -287,6 +301,8 @@ EXPORTS = [
     "mcpt_reflection_texels", "mcpt_bake_reflection", "mcpt_bake_reflection_device", "mcpt_reflection_rays",
     "mcpt_reflection_prefilter_host", "mcpt_reflection_prefilter", "mcpt_reflection_prefilter_device",
     "mcpt_reflection_lookup_host", "mcpt_reflection_lookup", "mcpt_reflection_lookup_device",
+    "mcpt_reflection_volume_lookup_host", "mcpt_reflection_volume_lookup", "mcpt_reflection_volume_lookup_device",
+    "mcpt_baked_radiance_specular", "mcpt_baked_radiance_specular_device", "mcpt_render_baked_specular", "mcpt_render_baked_specular_device",
 ]
 
 
@@ -516,6 +532,15 @@ def lib():
     L.mcpt_reflection_lookup_host.argtypes = [RC, D, C.c_int64, I32, D, D, C.c_int64, D]
     L.mcpt_reflection_lookup.argtypes = [P, RC, D, C.c_int64, I32, D, D, C.c_int64, D]
     L.mcpt_reflection_lookup_device.argtypes = [P, RC, P, C.c_int64, P, P, P, C.c_int64, P, P]
+    VG, VV = C.POINTER(VolumeGrid), C.POINTER(VolumeVisibility)
+    SP, SO = C.POINTER(BakedSpecular), C.POINTER(BakedSpecularOutputs)
+    L.mcpt_reflection_volume_lookup_host.argtypes = [VG, RC, D, U8, D, VV, D, D, D, C.c_int64, D, I32]
+    L.mcpt_reflection_volume_lookup.argtypes = [P, VG, RC, D, U8, D, VV, D, D, D, C.c_int64, D, I32]
+    L.mcpt_reflection_volume_lookup_device.argtypes = [P, VG, RC, P, P, P, VV, P, P, P, C.c_int64, P, P, P]
+    L.mcpt_baked_radiance_specular.argtypes = [P, BS, SP, D, C.c_int64, C.c_int32, BO, SO, C.POINTER(Stats)]
+    L.mcpt_baked_radiance_specular_device.argtypes = [P, BS, SP, P, C.c_int64, C.c_int32, BO, SO, C.POINTER(Stats), P]
+    L.mcpt_render_baked_specular.argtypes = [P, BS, SP, BF, D, I32, I32, I32, C.POINTER(Stats)]
+    L.mcpt_render_baked_specular_device.argtypes = [P, BS, SP, BF, P, P, P, P, C.POINTER(Stats), P]
     _lib = L
     return L
 

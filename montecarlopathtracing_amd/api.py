@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, ReflectionParams, ReflectionChain, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, BakedSpecular, BakedSpecularOutputs, ReflectionParams, ReflectionChain, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -415,6 +415,72 @@ def reflection_lookup_host(chain_desc, chain, probe, dirs, ns):
     check(lib().mcpt_reflection_lookup_host(C.byref(chain_desc), _p(chain, C.c_double), chain.shape[0], _p(probe, C.c_int32), _p(dirs, C.c_double),
                                             _p(ns, C.c_double), dirs.shape[0], _p(out, C.c_double)))
     return out
+
+
+class _BakedReflection:
+    """A reflection volume (mcpt_baked_specular) with the arrays it points to; baked_reflection makes one"""
+
+    def __init__(self, grid, chain_desc, chain, valid, moments, vis):
+        self.grid, self.chain_desc, self.chain, self.valid, self.moments, self.vis = grid, chain_desc, chain, valid, moments, vis
+
+    def struct(self):
+        """the mcpt_baked_specular of host pointers into this object's arrays (which must outlive it)"""
+        s = BakedSpecular()
+        s.grid, s.chain = C.pointer(self.grid), C.pointer(self.chain_desc)
+        addr = lambda a: a.ctypes.data if a is not None else None
+        s.chain_data, s.valid, s.moments = addr(self.chain), addr(self.valid), addr(self.moments)
+        if self.vis is not None:
+            s.visibility = C.pointer(self.vis)
+        return s
+
+
+def baked_reflection(grid, chain_desc, chain, valid=None, moments=None, vis=None):
+    """A reflection volume -- the specular source of Device.baked_radiance_specular and Device.render_baked_specular, and what
+    reflection_volume_lookup looks up: grid from volume_grid, chain_desc from reflection_chain (or prefilter_reflection), chain
+    [nz, ny, nx, T, 3] (or [nprobes, T, 3]) the probes' chains in volume_points' order, valid one flag per probe or None; with moments
+    (and vis, from volume_visibility) the corners are volume_irradiance_visible's."""
+    probes = _grid_probes(grid)
+    if not isinstance(chain_desc, ReflectionChain):
+        raise ValueError("the chain must be a ReflectionChain (reflection_chain makes one)")
+    chain = np.ascontiguousarray(chain, dtype=np.float64)
+    if chain.shape[-2:] != (chain_desc.num_texels, 3) or chain.size != probes * chain_desc.num_texels * 3:
+        raise ValueError("chain must hold (%d, 3) texels for each of the grid's %d probes, not %r" % (chain_desc.num_texels, probes, chain.shape))
+    if valid is not None:
+        valid = np.ascontiguousarray(valid)
+        if valid.dtype.kind not in "biu" or valid.size != probes:
+            raise ValueError("valid must hold one flag for each of the grid's %d probes" % probes)
+        valid = np.ascontiguousarray(valid != 0, dtype=np.uint8)
+    if moments is not None:
+        moments = _visibility_moments(grid, vis, moments)
+    elif vis is not None:
+        raise ValueError("vis without moments")
+    return _BakedReflection(grid, chain_desc, chain, valid, moments, vis)
+
+
+def _volume_receivers(volume, points, normals, dirs, ns):
+    if not isinstance(volume, _BakedReflection):
+        raise ValueError("volume must come from baked_reflection")
+    points, normals = np.asarray(points, dtype=np.float64), np.asarray(normals, dtype=np.float64)
+    dirs = np.ascontiguousarray(dirs, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape or dirs.shape != points.shape:
+        raise ValueError("points, normals and dirs must all have shape (m, 3)")
+    ns = np.ascontiguousarray(np.broadcast_to(np.asarray(ns, dtype=np.float64), (points.shape[0],)))
+    return np.ascontiguousarray(np.concatenate([points, normals], axis=1)), dirs, ns
+
+
+def reflection_volume_lookup_host(volume, points, normals, dirs, ns):
+    """A reflection volume's lookup on the CPU (mcpt_reflection_volume_lookup_host; no device): for receiver i at points[i] with normal
+    normals[i] the radiance volume (from baked_reflection) holds for direction dirs[i] (any non-zero length) under a lobe of exponent
+    ns[i] (a number or an array, finite and >= 0) -- reflection_lookup_host of each of the eight probes around the point, blended with
+    volume_irradiance's weights (volume_irradiance_visible's when the volume has moments).  Returns (radiance [m, 3], corners [m])."""
+    q, dirs, ns = _volume_receivers(volume, points, normals, dirs, ns)
+    m = q.shape[0]
+    out, corners = np.zeros((m, 3)), np.zeros(m, dtype=np.int32)
+    v = volume
+    check(lib().mcpt_reflection_volume_lookup_host(C.byref(v.grid), C.byref(v.chain_desc), _p(v.chain, C.c_double), _p(v.valid, C.c_uint8),
+                                                   _p(v.moments, C.c_double), C.byref(v.vis) if v.vis is not None else None, _p(q, C.c_double),
+                                                   _p(dirs, C.c_double), _p(ns, C.c_double), m, _p(out, C.c_double), _p(corners, C.c_int32)))
+    return out, corners
 
 
 def _baked_flags(face_viewer, lighting_only):
@@ -1253,6 +1319,96 @@ class Device:
         check(lib().mcpt_render_baked_device(self._h, C.byref(source_struct), C.byref(fp), _dp(d_img_ptr),
                                              _dp(d_counts_ptr), _dp(d_lit_ptr),
                                              C.byref(stats) if stats is not None else None, _dp(stream)))
+
+    def reflection_volume_lookup(self, volume, points, normals, dirs, ns):
+        """A reflection volume's lookup on the GPU (mcpt_reflection_volume_lookup): reflection_volume_lookup_host's arguments and
+        answers, bit for bit.  Returns (radiance [m, 3], corners [m])."""
+        q, dirs, ns = _volume_receivers(volume, points, normals, dirs, ns)
+        m = q.shape[0]
+        out, corners = np.zeros((m, 3)), np.zeros(m, dtype=np.int32)
+        v = volume
+        check(lib().mcpt_reflection_volume_lookup(self._h, C.byref(v.grid), C.byref(v.chain_desc), _p(v.chain, C.c_double), _p(v.valid, C.c_uint8),
+                                                  _p(v.moments, C.c_double), C.byref(v.vis) if v.vis is not None else None, _p(q, C.c_double),
+                                                  _p(dirs, C.c_double), _p(ns, C.c_double), m, _p(out, C.c_double), _p(corners, C.c_int32)))
+        return out, corners
+
+    def reflection_volume_lookup_device(self, specular_struct, d_q6_ptr, d_dirs_ptr, d_ns_ptr, m, d_out_ptr, d_corners_ptr=None, stream=None):
+        """The same between caller-owned device buffers on `stream` (mcpt_reflection_volume_lookup_device); never waits.  specular_struct: a
+        BakedSpecular whose chain_data, valid and moments are device pointers."""
+        s = specular_struct
+        check(lib().mcpt_reflection_volume_lookup_device(self._h, s.grid, s.chain, _dp(s.chain_data), _dp(s.valid), _dp(s.moments), s.visibility,
+                                                         _dp(d_q6_ptr), _dp(d_dirs_ptr), _dp(d_ns_ptr), int(m), _dp(d_out_ptr), _dp(d_corners_ptr),
+                                                         _dp(stream)))
+
+    @staticmethod
+    def _baked_specular(specular):
+        if not isinstance(specular, _BakedReflection):
+            raise ValueError("specular must come from baked_reflection")
+        return specular.struct()
+
+    def baked_radiance_specular(self, rays, source, specular, face_viewer=False, lighting_only=False, stats=None):
+        """baked_radiance with a specular term (mcpt_baked_radiance_specular): a surface hit whose material has a non-zero ks also shows
+        ks * R, R the radiance the reflection volume `specular` (baked_reflection) holds at the hit along the mirror direction under the
+        material's exponent Ns (R alone under lighting_only).  Returns baked_radiance's dict -- everything but radiance is the plain
+        call's, bit for bit -- with spec [n, 3] = R, ks [n, 3], r [n, 3] (the mirror direction scaled by |n|^2), ns [n] and slit [n] (the
+        probes that took part), all 0 where a ray has no specular term."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        if rays.ndim != 2 or rays.shape[1] != 6:
+            raise ValueError("rays must have shape (n, 6), not %r" % (rays.shape,))
+        n = rays.shape[0]
+        s, sp = self._baked_source(source), self._baked_specular(specular)
+        out = {"radiance": np.zeros((n, 3)), "kind": np.zeros(n, dtype=np.int32), "face": np.zeros(n, dtype=np.int32), "q6": np.zeros((n, 6)),
+               "uv": np.zeros((n, 2)), "kd": np.zeros((n, 3)), "e": np.zeros((n, 3)), "lit": np.zeros(n, dtype=np.int32),
+               "spec": np.zeros((n, 3)), "ks": np.zeros((n, 3)), "r": np.zeros((n, 3)), "ns": np.zeros(n), "slit": np.zeros(n, dtype=np.int32)}
+        o = BakedOutputs(*[out[k].ctypes.data for k in ("radiance", "kind", "face", "q6", "uv", "kd", "e", "lit")])
+        so = BakedSpecularOutputs(*[out[k].ctypes.data for k in ("spec", "ks", "r", "ns", "slit")])
+        check(lib().mcpt_baked_radiance_specular(self._h, C.byref(s), C.byref(sp), _p(rays, C.c_double), n, _baked_flags(face_viewer, lighting_only),
+                                                 C.byref(o), C.byref(so), C.byref(stats) if stats is not None else None))
+        return out
+
+    def baked_radiance_specular_device(self, d_rays_ptr, n, source_struct, specular_struct, outputs_struct, specular_outputs_struct=None, face_viewer=False,
+                                       lighting_only=False, stats=None, stream=None):
+        """The same between caller-owned device buffers on `stream` (mcpt_baked_radiance_specular_device): source_struct a BakedSource,
+        specular_struct a BakedSpecular, outputs_struct a BakedOutputs and specular_outputs_struct a BakedSpecularOutputs (or None) of
+        device pointers."""
+        check(lib().mcpt_baked_radiance_specular_device(self._h, C.byref(source_struct), C.byref(specular_struct), _dp(d_rays_ptr), int(n),
+                                                        _baked_flags(face_viewer, lighting_only), C.byref(outputs_struct),
+                                                        C.byref(specular_outputs_struct) if specular_outputs_struct is not None else None,
+                                                        C.byref(stats) if stats is not None else None, _dp(stream)))
+
+    def render_baked_specular(self, source, specular, samples=1, seed=0, face_viewer=False, lighting_only=False, workspace_rays=0, stats=None):
+        """render_baked with every sample shaded as baked_radiance_specular shades it (mcpt_render_baked_specular).  Returns render_baked's
+        dict with "slit": [H, W] the samples whose specular lookup found a probe."""
+        if not isinstance(samples, numbers.Integral) or not -2 ** 31 <= samples < 2 ** 31:
+            raise ValueError("samples must be a 32-bit integer")
+        if not isinstance(workspace_rays, numbers.Integral) or not -2 ** 63 <= workspace_rays < 2 ** 63:
+            raise ValueError("workspace_rays must be a 64-bit integer")
+        s, sp = self._baked_source(source), self._baked_specular(specular)
+        fp = BakedFrameParams(int(samples), _baked_flags(face_viewer, lighting_only), int(seed), int(workspace_rays), (C.c_int32 * 2)(0, 0))
+        img = np.zeros((self.height, self.width, 3))
+        counts, lit = np.zeros((self.height, self.width, 3), dtype=np.int32), np.zeros((self.height, self.width), dtype=np.int32)
+        slit = np.zeros((self.height, self.width), dtype=np.int32)
+        check(lib().mcpt_render_baked_specular(self._h, C.byref(s), C.byref(sp), C.byref(fp), _p(img, C.c_double), _p(counts, C.c_int32),
+                                               _p(lit, C.c_int32), _p(slit, C.c_int32), C.byref(stats) if stats is not None else None))
+        return {"image": img, "counts": counts, "lit": lit, "slit": slit}
+
+    def render_baked_specular_device(self, source_struct, specular_struct, d_img_ptr, samples=1, seed=0, face_viewer=False, lighting_only=False,
+                                     workspace_rays=0, d_counts_ptr=None, d_lit_ptr=None, d_slit_ptr=None, stats=None, stream=None):
+        """The same into a caller-owned device buffer on `stream` (mcpt_render_baked_specular_device): source_struct a BakedSource and
+        specular_struct a BakedSpecular of device pointers.  Returns without waiting when stats is None."""
+        fp = BakedFrameParams(int(samples), _baked_flags(face_viewer, lighting_only), int(seed), int(workspace_rays), (C.c_int32 * 2)(0, 0))
+        check(lib().mcpt_render_baked_specular_device(self._h, C.byref(source_struct), C.byref(specular_struct), C.byref(fp), _dp(d_img_ptr),
+                                                      _dp(d_counts_ptr), _dp(d_lit_ptr), _dp(d_slit_ptr),
+                                                      C.byref(stats) if stats is not None else None, _dp(stream)))
+
+    def bake_reflection_volume(self, grid, res, spp, seed=0, sample_base=0, workspace_rays=0, flags=0, stats=None):
+        """Reflection probes on every probe of a grid: bake_reflection_probes of volume_points(grid), bit for bit, reshaped.  Returns
+        (radiance [nz, ny, nx, res * res, 3], stderr [nz, ny, nx, res * res, 3], hits [nz, ny, nx, res * res]); prefilter_reflection of
+        the first, flattened to [nprobes, res * res, 3], gives the chain baked_reflection takes."""
+        rad, err, hits = self.bake_reflection_probes(volume_points(grid), res, spp, seed=seed, sample_base=sample_base, workspace_rays=workspace_rays,
+                                                     flags=flags, stats=stats)
+        shape = (grid.nz, grid.ny, grid.nx)
+        return rad.reshape(shape + rad.shape[1:]), err.reshape(shape + err.shape[1:]), hits.reshape(shape + hits.shape[1:])
 
     @staticmethod
     def _reflection_params(res, spp, seed, sample_base, workspace_rays, flags):

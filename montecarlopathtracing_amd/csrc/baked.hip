@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "baked.hpp"
+#include "baked_surface.hpp"
 #include "camera.hpp"
 #include "dev_common.hpp"
 #include "env.hpp"
@@ -82,10 +83,7 @@ __device__ __forceinline__ void baked_sample(const DScene& S, const BakedSource&
     h.leaf = lf; h.t = t; h.p = p;
     pn = hit_normal(S, h);
     double n[3] = {pn.x, pn.y, pn.z};
-    if (baked_normal_bad(n))
-        for (int c = 0; c < 3; c++) n[c] = tr->n[c];
-    const double dd[3] = {d.x, d.y, d.z};
-    if (flags & MCPT_BAKED_FACE_VIEWER) baked_face_viewer(dd, n);
+    baked_normal_rule(tr, d, flags, n);
     r.kd[0] = kd.x; r.kd[1] = kd.y; r.kd[2] = kd.z;
     r.q[0] = p.x; r.q[1] = p.y; r.q[2] = p.z;
     for (int c = 0; c < 3; c++) r.q[3 + c] = n[c];

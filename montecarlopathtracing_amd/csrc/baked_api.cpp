@@ -10,6 +10,7 @@
 #include <string>
 
 #include "baked.hpp"
+#include "baked_specular.hpp"
 #include "chunks.hpp"
 #include "handles.hpp"
 
@@ -37,7 +38,7 @@ static int lookup_uv_check(const double* uv2, int64_t n)
 }
 
 // what every call refuses of its source, in the header's order
-static int source_check(const mcpt_baked_source* s)
+int baked_source_check(const mcpt_baked_source* s)
 {
     if (!s) return fail(MCPT_ERR_ARG, "null baked source");
     if (s->kind != MCPT_BAKED_VOLUME && s->kind != MCPT_BAKED_LIGHTMAP) return fail(MCPT_ERR_ARG, "a baked source is MCPT_BAKED_VOLUME or MCPT_BAKED_LIGHTMAP");
@@ -56,9 +57,9 @@ static int source_check(const mcpt_baked_source* s)
     return MCPT_OK;
 }
 
-static int radiance_check(const mcpt_baked_source* s, const void* rays6, int64_t n, int32_t flags, const mcpt_baked_outputs* o)
+// what a baked radiance call refuses of its own arguments, after its source
+int baked_radiance_args_check(const void* rays6, int64_t n, int32_t flags, const mcpt_baked_outputs* o)
 {
-    if (const int rc = source_check(s)) return rc;
     if (flags & ~(MCPT_BAKED_FACE_VIEWER | MCPT_BAKED_LIGHTING_ONLY)) return fail(MCPT_ERR_ARG, "unknown baked flag");
     if (const int rc = count_check(n, "rays")) return rc;
     if (n > 0 && !rays6) return fail(MCPT_ERR_ARG, "null rays");
@@ -67,9 +68,15 @@ static int radiance_check(const mcpt_baked_source* s, const void* rays6, int64_t
     return MCPT_OK;
 }
 
-static int frame_check(const mcpt_baked_source* s, const mcpt_baked_frame_params* p, const void* img)
+static int radiance_check(const mcpt_baked_source* s, const void* rays6, int64_t n, int32_t flags, const mcpt_baked_outputs* o)
 {
-    if (const int rc = source_check(s)) return rc;
+    if (const int rc = baked_source_check(s)) return rc;
+    return baked_radiance_args_check(rays6, n, flags, o);
+}
+
+// what a baked frame call refuses of its own arguments, after its source
+int baked_frame_args_check(const mcpt_baked_frame_params* p, const void* img)
+{
     if (!p) return fail(MCPT_ERR_ARG, "null baked frame parameters");
     if (p->samples < 1 || p->samples > kMaxSamples) return fail(MCPT_ERR_ARG, "samples must be in 1 .. 65536");
     if (p->flags & ~(MCPT_BAKED_FACE_VIEWER | MCPT_BAKED_LIGHTING_ONLY)) return fail(MCPT_ERR_ARG, "unknown baked flag");
@@ -77,6 +84,12 @@ static int frame_check(const mcpt_baked_source* s, const mcpt_baked_frame_params
     if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(MCPT_ERR_ARG, "mcpt_baked_frame_params.reserved must be 0");
     if (!img) return fail(MCPT_ERR_ARG, "null image");
     return MCPT_OK;
+}
+
+static int frame_check(const mcpt_baked_source* s, const mcpt_baked_frame_params* p, const void* img)
+{
+    if (const int rc = baked_source_check(s)) return rc;
+    return baked_frame_args_check(p, img);
 }
 
 // a checked source whose pointers are the device's, as the kernels read it
@@ -95,7 +108,7 @@ static BakedSource device_source(const mcpt_baked_source& s)
 }
 
 // the device copies of a host-pointer source among the call's: `dev` is s with the device's pointers
-static int source_upload(const mcpt_device* d, const mcpt_baked_source& s, Staging& S, mcpt_baked_source& dev)
+int baked_source_upload(const mcpt_device* d, const mcpt_baked_source& s, Staging& S, mcpt_baked_source& dev)
 {
     dev = s;
     if (s.kind == MCPT_BAKED_VOLUME) {
@@ -115,8 +128,8 @@ static int source_upload(const mcpt_device* d, const mcpt_baked_source& s, Stagi
     return MCPT_OK;
 }
 
-// the workspace for chunks of `rays` rays of a call on st, once the call before this one has left it
-static int baked_workspace(mcpt_device* d, int64_t rays, bool own_rays, bool samples, hipStream_t st, Lease& l)
+// the workspace for chunks of `rays` rays of a call on st, once the call before this one has left it (spec: a specular frame's word per ray)
+static int baked_workspace(mcpt_device* d, int64_t rays, bool own_rays, bool samples, bool spec, hipStream_t st, Lease& l)
 {
     if (const int rc = lease(d->baked, st, l)) return rc;
     mcpt_device::Baked& w = *d->baked;
@@ -132,6 +145,8 @@ static int baked_workspace(mcpt_device* d, int64_t rays, bool own_rays, bool sam
         if (const int rc = grow(w.kind, sr, "the baked samples' kinds")) return rc;
         if (const int rc = grow(w.lit, sr, "the baked samples' lookups")) return rc;
     }
+    if (spec)
+        if (const int rc = grow(w.slit, sr, "the baked samples' specular lookups")) return rc;
     return MCPT_OK;
 }
 
@@ -140,6 +155,18 @@ static inline void trace_chunk(mcpt_device* d, const double* d_rays6, int64_t n,
     mcpt_device::Baked& w = *d->baked;
     launch_trace_closest_leaf(d->ds, d->trace_mode == MCPT_TRACE_FAST, d_rays6, n, w.leaf.get(), w.t.get(), w.p.get(), d->aux_ctr.get(), d->aux_queue.get(),
                               d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
+}
+
+// the specular outputs of rays first .. of a call
+static BakedSpecOut spec_outputs_at(const BakedSpecOut& o, int64_t first)
+{
+    BakedSpecOut r{};
+    r.spec3 = o.spec3 ? o.spec3 + first * 3 : nullptr;
+    r.ks3 = o.ks3 ? o.ks3 + first * 3 : nullptr;
+    r.r3 = o.r3 ? o.r3 + first * 3 : nullptr;
+    r.ns = o.ns ? o.ns + first : nullptr;
+    r.slit = o.slit ? o.slit + first : nullptr;
+    return r;
 }
 
 // the outputs of rays first .. of a call
@@ -158,9 +185,10 @@ static BakedOut outputs_at(const mcpt_baked_outputs& o, int64_t first)
 }
 
 // Baked radiance on st, after the refusals and the gate; device pointers throughout.  Nothing here waits for st unless the caller asks for
-// statistics.
-static int radiance_device(mcpt_device* d, const mcpt_baked_source& s, const double* d_rays6, int64_t n, int32_t flags, const mcpt_baked_outputs& o,
-                           mcpt_stats* stats, hipStream_t st)
+// statistics.  spec (may be null): the specular pass after every chunk's shading (mcpt.h: baked specular); without it the launches are the
+// plain call's.
+int baked_radiance_device(mcpt_device* d, const mcpt_baked_source& s, const double* d_rays6, int64_t n, int32_t flags, const mcpt_baked_outputs& o,
+                          const BakedSpecular* spec, mcpt_stats* stats, hipStream_t st)
 {
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (n == 0) return MCPT_OK;
@@ -168,7 +196,7 @@ static int radiance_device(mcpt_device* d, const mcpt_baked_source& s, const dou
     if (const int rc = geometry_gate(d)) return rc;
     const int64_t per_chunk = chunk_plan(0, 1, n);          // the workspace of a caller's rays is the default
     Lease l;
-    if (const int rc = baked_workspace(d, per_chunk, false, false, st, l)) return rc;
+    if (const int rc = baked_workspace(d, per_chunk, false, false, false, st, l)) return rc;
     mcpt_device::Baked& w = *d->baked;
     const BakedSource B = device_source(s);
     int chunks = 0;
@@ -177,7 +205,10 @@ static int radiance_device(mcpt_device* d, const mcpt_baked_source& s, const dou
         const int64_t count = chunk_count(per_chunk, n, first);
         const double* rays = d_rays6 + first * 6;
         trace_chunk(d, rays, count, st);
-        launch_baked_shade(d->ds, B, flags, rays, w.leaf.get(), w.t.get(), w.p.get(), count, outputs_at(o, first), st);
+        const BakedOut at = outputs_at(o, first);
+        launch_baked_shade(d->ds, B, flags, rays, w.leaf.get(), w.t.get(), w.p.get(), count, at, st);
+        if (spec)
+            launch_baked_specular(d->ds, spec->V, flags, rays, w.leaf.get(), w.t.get(), w.p.get(), count, at.radiance3, spec_outputs_at(spec->rays, first), st);
         rc = launch_result();
     }
     if ((rc = l.end(rc)) != MCPT_OK) return rc;
@@ -189,9 +220,10 @@ static int radiance_device(mcpt_device* d, const mcpt_baked_source& s, const dou
     return MCPT_OK;
 }
 
-// A baked frame on st, after the refusals and the gate; device pointers throughout.
-static int frame_device(mcpt_device* d, const mcpt_baked_source& s, const mcpt_baked_frame_params& fp, double* d_img, int32_t* d_counts3, int32_t* d_lit,
-                        mcpt_stats* stats, hipStream_t st)
+// A baked frame on st, after the refusals and the gate; device pointers throughout.  spec (may be null): the specular pass between every
+// chunk's shading and its fold; without it the launches are the plain call's.
+int baked_frame_device(mcpt_device* d, const mcpt_baked_source& s, const mcpt_baked_frame_params& fp, double* d_img, int32_t* d_counts3, int32_t* d_lit,
+                       const BakedSpecular* spec, mcpt_stats* stats, hipStream_t st)
 {
     if (stats) std::memset(stats, 0, sizeof *stats);
     if (const int rc = motion_home(d)) return rc;
@@ -203,7 +235,7 @@ static int frame_device(mcpt_device* d, const mcpt_baked_source& s, const mcpt_b
     const int flags = fp.flags;
     const int64_t per_chunk = chunk_plan(fp.workspace_rays, G, pixels);     // whole pixels
     Lease l;
-    if (const int rc = baked_workspace(d, per_chunk * G, true, true, st, l)) return rc;
+    if (const int rc = baked_workspace(d, per_chunk * G, true, true, spec && spec->pixel_slit, st, l)) return rc;
     mcpt_device::Baked& w = *d->baked;
     const BakedSource B = device_source(s);
     const DLens lens = lens_for(d, d->lens);
@@ -219,6 +251,12 @@ static int frame_device(mcpt_device* d, const mcpt_baked_source& s, const mcpt_b
         BakedOut o{};
         o.radiance3 = w.rad.get(); o.kind = w.kind.get(); o.lit = w.lit.get();
         launch_baked_shade(d->ds, B, flags, c.rays6, c.leaf, c.t, c.p, rays, o, st);
+        if (spec) {
+            BakedSpecOut so{};
+            so.slit = spec->pixel_slit ? w.slit.get() : nullptr;
+            launch_baked_specular(d->ds, spec->V, flags, c.rays6, c.leaf, c.t, c.p, rays, w.rad.get(), so, st);
+            if (spec->pixel_slit) launch_baked_specular_count(c, w.slit.get(), spec->pixel_slit, st);
+        }
         launch_baked_fold(c, w.rad.get(), w.kind.get(), w.lit.get(), d_img, d_counts3, d_lit, st);
         rc = launch_result();
     }
@@ -282,7 +320,7 @@ int mcpt_baked_radiance_device(mcpt_device* d, const mcpt_baked_source* s, const
 {
     if (const int rc = radiance_check(s, d_rays6, n, flags, o)) return rc;
     if (const int rc = device_gate(d)) return rc;
-    return radiance_device(d, *s, d_rays6, n, flags, *o, stats, static_cast<hipStream_t>(stream));
+    return baked_radiance_device(d, *s, d_rays6, n, flags, *o, nullptr, stats, static_cast<hipStream_t>(stream));
 }
 
 int mcpt_baked_radiance(mcpt_device* d, const mcpt_baked_source* s, const double* rays6, int64_t n, int32_t flags, const mcpt_baked_outputs* o,
@@ -293,7 +331,7 @@ int mcpt_baked_radiance(mcpt_device* d, const mcpt_baked_source* s, const double
     if (stats) std::memset(stats, 0, sizeof *stats);
     Staging S(d->stream.get());
     mcpt_baked_source src;
-    if (const int rc = source_upload(d, *s, S, src)) return rc;
+    if (const int rc = baked_source_upload(d, *s, S, src)) return rc;
     if (n == 0) return MCPT_OK;
     const size_t sn = size_t(n);
     const double* d_rays = nullptr;
@@ -308,7 +346,7 @@ int mcpt_baked_radiance(mcpt_device* d, const mcpt_baked_source* s, const double
     if (const int rc = S.out(o->kd3, sn * 3, "a baked output", dev.kd3)) return rc;
     if (const int rc = S.out(o->e3, sn * 3, "a baked output", dev.e3)) return rc;
     if (const int rc = S.out(o->lit, sn, "a baked output", dev.lit)) return rc;
-    return S.finish(radiance_device(d, src, d_rays, n, flags, dev, stats, d->stream.get()));
+    return S.finish(baked_radiance_device(d, src, d_rays, n, flags, dev, nullptr, stats, d->stream.get()));
 }
 
 int mcpt_render_baked_device(mcpt_device* d, const mcpt_baked_source* s, const mcpt_baked_frame_params* p, double* d_img, int32_t* d_counts3, int32_t* d_lit,
@@ -316,7 +354,7 @@ int mcpt_render_baked_device(mcpt_device* d, const mcpt_baked_source* s, const m
 {
     if (const int rc = frame_check(s, p, d_img)) return rc;
     if (const int rc = device_gate(d)) return rc;
-    return frame_device(d, *s, *p, d_img, d_counts3, d_lit, stats, static_cast<hipStream_t>(stream));
+    return baked_frame_device(d, *s, *p, d_img, d_counts3, d_lit, nullptr, stats, static_cast<hipStream_t>(stream));
 }
 
 int mcpt_render_baked(mcpt_device* d, const mcpt_baked_source* s, const mcpt_baked_frame_params* p, double* img, int32_t* counts3, int32_t* lit,
@@ -327,7 +365,7 @@ int mcpt_render_baked(mcpt_device* d, const mcpt_baked_source* s, const mcpt_bak
     if (stats) std::memset(stats, 0, sizeof *stats);
     Staging S(d->stream.get());
     mcpt_baked_source src;
-    if (const int rc = source_upload(d, *s, S, src)) return rc;
+    if (const int rc = baked_source_upload(d, *s, S, src)) return rc;
     const size_t px = size_t(d->width) * size_t(d->height);
     if (px == 0) return MCPT_OK;
     double* d_img = nullptr;
@@ -335,7 +373,7 @@ int mcpt_render_baked(mcpt_device* d, const mcpt_baked_source* s, const mcpt_bak
     if (const int rc = S.out(img, px * 3, "the frame", d_img)) return rc;
     if (const int rc = S.out(counts3, px * 3, "the frame's counts", d_counts)) return rc;
     if (const int rc = S.out(lit, px, "the frame's lookups", d_lit)) return rc;
-    return S.finish(frame_device(d, src, *p, d_img, d_counts, d_lit, stats, d->stream.get()));
+    return S.finish(baked_frame_device(d, src, *p, d_img, d_counts, d_lit, nullptr, stats, d->stream.get()));
 }
 
 }  // extern "C"

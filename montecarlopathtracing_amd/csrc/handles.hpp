@@ -247,6 +247,7 @@ struct mcpt_device {
     struct Baked {
         mcpt::DevBuf<double> rays6, t, p, rad;          // [rays][6], [rays], [rays][3], [rays][3]
         mcpt::DevBuf<int32_t> leaf, kind, lit;          // [rays]
+        mcpt::DevBuf<int32_t> slit;                     // [rays] a specular frame's lookups: 4 bytes per ray more, grown by those calls alone
         mcpt::Event done;
     };
     std::unique_ptr<Baked> baked;
@@ -359,6 +360,23 @@ int volume_points_device(mcpt_device* d, const mcpt_volume_grid& g, hipStream_t 
 
 // ---- visibility_api.cpp (shared with baked_api.cpp)
 int volume_visibility_check(const mcpt_volume_visibility* v);   // what every visibility-weighted lookup refuses of its knobs, in the struct's field order
+
+// ---- reflection_api.cpp (shared with baked_specular_api.cpp)
+int reflection_chain_check(const mcpt_reflection_chain* c);    // what every call refuses of a chain, in the struct's field order
+int reflection_finite_check(const double* a, size_t count, const char* what);   // MCPT_ERR_ARG: a value of a[0 .. count) that is not finite
+
+// ---- baked_api.cpp (shared with baked_specular_api.cpp)
+namespace mcpt { struct BakedSpecular; }
+int baked_source_check(const mcpt_baked_source* s);  // what every baked call refuses of its source, in the header's order
+int baked_radiance_args_check(const void* rays6, int64_t n, int32_t flags, const mcpt_baked_outputs* o);
+int baked_frame_args_check(const mcpt_baked_frame_params* p, const void* img);
+// the device copies of a host-pointer source among the call's: `dev` is s with the device's pointers
+int baked_source_upload(const mcpt_device* d, const mcpt_baked_source& s, Staging& S, mcpt_baked_source& dev);
+// the baked radiance call and the baked frame on `st` after the refusals and the gate (device pointers throughout); spec null: the plain calls
+int baked_radiance_device(mcpt_device* d, const mcpt_baked_source& s, const double* d_rays6, int64_t n, int32_t flags, const mcpt_baked_outputs& o,
+                          const mcpt::BakedSpecular* spec, mcpt_stats* stats, hipStream_t st);
+int baked_frame_device(mcpt_device* d, const mcpt_baked_source& s, const mcpt_baked_frame_params& fp, double* d_img, int32_t* d_counts3, int32_t* d_lit,
+                       const mcpt::BakedSpecular* spec, mcpt_stats* stats, hipStream_t st);
 
 // ---- lightmap_api.cpp
 namespace mcpt { struct LightmapWork; }

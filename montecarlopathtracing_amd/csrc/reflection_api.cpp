@@ -65,7 +65,7 @@ static int list_check(const mcpt_reflection_params& p, const double* p3, const i
 }
 
 // what every call refuses of a chain, in the struct's field order
-static int chain_check(const mcpt_reflection_chain* c)
+int reflection_chain_check(const mcpt_reflection_chain* c)
 {
     if (!c) return fail(MCPT_ERR_ARG, "null reflection chain");
     if (const int rc = res_check(c->res)) return rc;
@@ -87,7 +87,7 @@ static int chain_check(const mcpt_reflection_chain* c)
 
 static int prefilter_check(const mcpt_reflection_chain* c, const void* radiance, int64_t n, const void* chain)
 {
-    if (const int rc = chain_check(c)) return rc;
+    if (const int rc = reflection_chain_check(c)) return rc;
     if (const int rc = count_check(n, "probes")) return rc;
     if (n > 0 && (!radiance || !chain)) return fail(MCPT_ERR_ARG, "null radiance or chain");
     return MCPT_OK;
@@ -95,14 +95,14 @@ static int prefilter_check(const mcpt_reflection_chain* c, const void* radiance,
 
 static int lookup_check(const mcpt_reflection_chain* c, const void* chain, int64_t n, const void* probe, const void* d3, const void* x, int64_t m, const void* out3)
 {
-    if (const int rc = chain_check(c)) return rc;
+    if (const int rc = reflection_chain_check(c)) return rc;
     if (const int rc = count_check(n, "probes")) return rc;
     if (const int rc = count_check(m, "receivers")) return rc;
     if (m > 0 && (!chain || !probe || !d3 || !x || !out3)) return fail(MCPT_ERR_ARG, "null chain, probe indices, directions, exponents or radiance");
     return MCPT_OK;
 }
 
-static int finite_check(const double* a, size_t count, const char* what)
+int reflection_finite_check(const double* a, size_t count, const char* what)
 {
     for (size_t i = 0; i < count; i++)
         if (!std::isfinite(a[i])) return fail(MCPT_ERR_ARG, std::string(what) + ": value " + std::to_string(i) + " is not finite");
@@ -112,7 +112,7 @@ static int finite_check(const double* a, size_t count, const char* what)
 // ... and what the host-pointer forms of the lookup refuse of the arrays themselves
 static int lookup_arrays_check(const mcpt_reflection_chain& c, const double* chain, int64_t n, const int32_t* probe, const double* d3, const double* x, int64_t m)
 {
-    if (const int rc = finite_check(chain, size_t(n) * size_t(reflection_chain_texels(c)) * 3, "the chain")) return rc;
+    if (const int rc = reflection_finite_check(chain, size_t(n) * size_t(reflection_chain_texels(c)) * 3, "the chain")) return rc;
     for (int64_t q = 0; q < m; q++) {
         const double* d = d3 + q * 3;
         const double l = (std::fabs(d[0]) + std::fabs(d[1])) + std::fabs(d[2]);
@@ -254,7 +254,7 @@ int mcpt_reflection_prefilter_host(const mcpt_reflection_chain* c, const double*
     if (const int rc = prefilter_check(c, radiance, n, chain)) return rc;
     if (n == 0) return MCPT_OK;
     const int src = c->res * c->res, T = reflection_chain_texels(*c);
-    if (const int rc = finite_check(radiance, size_t(n) * size_t(src) * 3, "the radiance")) return rc;
+    if (const int rc = reflection_finite_check(radiance, size_t(n) * size_t(src) * 3, "the radiance")) return rc;
     std::vector<double> dw(size_t(src) * 4);                // the source texels' directions and solid angles, as the kernel's records hold them
     for (int b = 0; b < src; b++) reflection_texel(c->res, b, &dw[size_t(b) * 4], dw[size_t(b) * 4 + 3]);
     for (int l = 0, first = 0; l < c->num_levels; first += c->level_res[l] * c->level_res[l], l++)
@@ -280,7 +280,7 @@ int mcpt_reflection_prefilter(mcpt_device* d, const mcpt_reflection_chain* c, co
 {
     if (const int rc = prefilter_check(c, radiance, n, chain)) return rc;
     if (n > 0)
-        if (const int rc = finite_check(radiance, size_t(n) * size_t(c->res) * size_t(c->res) * 3, "the radiance")) return rc;
+        if (const int rc = reflection_finite_check(radiance, size_t(n) * size_t(c->res) * size_t(c->res) * 3, "the radiance")) return rc;
     if (const int rc = device_gate(d)) return rc;
     if (n == 0) return MCPT_OK;
     const size_t in = size_t(n) * size_t(c->res) * size_t(c->res) * 3, out = size_t(n) * size_t(reflection_chain_texels(*c)) * 3;

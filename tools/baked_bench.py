@@ -3,6 +3,7 @@
 
     python tools/baked_bench.py frame  [--width 1280 --height 720 --samples 1 --grid 64 --size 2048 --calls 5]
     python tools/baked_bench.py approx [--width 320 --height 180 --samples 16 --ref-spp 4096 --size 1024 --spp 256]
+    python tools/baked_bench.py specular [--scene glassroom --width 1280 --height 720 --samples 1 --probe-grid 8 --probe-res 64 --calls 5]
 
 frame : cornell-box at --width x --height.  The sources are synthetic (what a kernel costs does not depend on what the numbers mean): a
         --grid^3 volume over the scene's bounds, plain and with moments, and a --size^2 lightmap under grid_atlas, all in device buffers.
@@ -17,6 +18,12 @@ approx: cornell-box and glassroom at --width x --height: frames lit by a lightma
         grid_atlas, glassroom under its own chart), and by volumes of 16^3 and 32^3 probes baked at --spp with their visibility, against
         the path-traced frame at --ref-spp: relative RMS difference and the ratio of the means over the pixels whose samples are all
         surface hits.  The two are not expected to agree (DESIGN 6s says why).
+specular: --scene (glassroom under its sky, or veach-mis) at --width x --height.  The diffuse source is a synthetic 8^3 volume, the
+        specular source a synthetic --probe-grid^3 reflection volume of --probe-res^2 probes in five levels (each half the size of the one
+        before), plain and with moments, all in device buffers.  One warm-up call and --calls timed calls of mcpt_render_baked_device and
+        of mcpt_render_baked_specular_device per source, between two HIP events on one stream, taken in turn.  Medians.  The specular
+        kernel's traffic floor: 84 bytes read and 24 read and written again per ray (the direction's ray record, the hit and the
+        radiance), at 8 TB/s; under rocprofv3 --kernel-trace --stats (a run of its own) k_baked_specular is the kernel's own time.
 One process; --time-limit seconds after its start the process ends itself.  One JSON line per result."""
 import argparse
 import ctypes as C
@@ -40,7 +47,10 @@ def grid_over(M, dev, n, inset=0.02):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["frame", "approx"])
+    ap.add_argument("mode", choices=["frame", "approx", "specular"])
+    ap.add_argument("--scene", choices=["glassroom", "veach-mis"], default="glassroom")
+    ap.add_argument("--probe-grid", type=int, default=8)
+    ap.add_argument("--probe-res", type=int, default=64)
     ap.add_argument("--width", type=int, default=None)
     ap.add_argument("--height", type=int, default=None)
     ap.add_argument("--samples", type=int, default=None)
@@ -103,8 +113,16 @@ def main():
     hip.hipEventSynchronize.argtypes = [C.c_void_p]
     hip.hipEventElapsedTime.argtypes = [C.POINTER(C.c_float), C.c_void_p, C.c_void_p]
     Wd, Ht, G, size = a.width or 1280, a.height or 720, a.samples or 1, a.size or 2048
-    sc = M.Scene(scenes, "cornell-box", width=Wd, height=Ht)
-    dev = M.Device(sc, 0)
+    if a.mode == "specular":
+        from conftest import extra_scene_dir
+        import env_scenes
+        sc = M.Scene(extra_scene_dir() if a.scene == "glassroom" else scenes, a.scene, width=Wd, height=Ht)
+        dev = M.Device(sc, 0)
+        if a.scene == "glassroom":
+            dev.set_environment(*env_scenes.SKIES["map"])
+    else:
+        sc = M.Scene(scenes, "cornell-box", width=Wd, height=Ht)
+        dev = M.Device(sc, 0)
     hip_rt.set_device(0)
     st = hip_rt.Stream()
     e0, e1 = C.c_void_p(), C.c_void_p()
@@ -128,6 +146,45 @@ def main():
         return buf
 
     rng = np.random.default_rng(a.seed)
+    if a.mode == "specular":
+        px = Wd * Ht
+        gd, gs = grid_over(M, dev, 8), grid_over(M, dev, a.probe_grid)
+        probes = a.probe_grid ** 3
+        levels = [(max(a.probe_res >> l, 1), ns) for l, ns in enumerate((4096, 512, 64, 8, 0))]
+        desc = M.reflection_chain(a.probe_res, levels)
+        maxd = 1.5 * float(np.sqrt(sum(float(v) ** 2 for v in gs.spacing)))
+        vis = M.volume_visibility(R, maxd, 0.0, 0.0)
+        d_sh = upload(rng.normal(size=(512, 9, 3)))
+        d_chain = upload(rng.uniform(0.5, 1.5, size=(probes, desc.num_texels, 3)))
+        mu = rng.uniform(0.0, maxd, size=(probes, R * R))
+        d_m = upload(np.stack([mu, mu * mu + rng.uniform(0.0, 0.1 * maxd * maxd, size=mu.shape)], axis=2))
+        d_img, d_slit = hip_rt.DeviceBuffer(px * 24), hip_rt.DeviceBuffer(px * 4)
+        src = _lib.BakedSource()
+        src.kind, src.grid, src.sh27 = M.BAKED_VOLUME, C.pointer(gd), d_sh.ptr
+        fp = _lib.BakedFrameParams(G, M.BAKED_FACE_VIEWER, a.seed, 0, (C.c_int32 * 2)(0, 0))
+        calls = {"plain": lambda: L.mcpt_render_baked_device(dev._h, C.byref(src), C.byref(fp), d_img.ptr, None, None, None, st.h)}
+        keep = []
+        for kind in ("specular", "specular visible"):
+            sp = _lib.BakedSpecular()
+            sp.grid, sp.chain, sp.chain_data = C.pointer(gs), C.pointer(desc), d_chain.ptr
+            if kind == "specular visible":
+                sp.moments, sp.visibility = d_m.ptr, C.pointer(vis)
+            keep.append(sp)
+            calls[kind] = lambda sp=sp: L.mcpt_render_baked_specular_device(dev._h, C.byref(src), C.byref(sp), C.byref(fp), d_img.ptr, None, None, d_slit.ptr, None, st.h)
+        ms = {k: [] for k in calls}
+        for i in range(a.calls + 1):
+            for k, call in calls.items():
+                ms[k].append(once(call))
+        slit = np.zeros(px, dtype=np.int32)
+        d_slit.to_host_async(slit, st.h)
+        st.synchronize()
+        floor_ms = px * G * (84 + 2 * 24) / HBM_BYTES_PER_S * 1e3
+        for k, v in ms.items():
+            print(json.dumps(dict(base, what="mcpt_render_baked_specular_device" if k != "plain" else "mcpt_render_baked_device", source=k, scene=a.scene,
+                                  width=Wd, height=Ht, samples=G, probes=probes, probe_res=a.probe_res, chain_mb=round(probes * desc.num_texels * 24 / 1e6, 1),
+                                  ms=round(float(np.median(v[1:])), 4), calls_ms=[round(t, 4) for t in v[1:]], specular_floor_ms=round(floor_ms, 4),
+                                  specular_pixels=int((slit > 0).sum()))), flush=True)
+        return
     n = a.grid
     probes = n ** 3
     g = grid_over(M, dev, n)
