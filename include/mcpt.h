@@ -1029,7 +1029,8 @@ int mcpt_sh_irradiance(const double* sh27, const double* n3, int64_t n, double* 
  * is not finite is skipped.
  * Not covered: UV unwrapping and packing; supersampling or conservative coverage (a sliver that contains no texel centre gets no texel:
  * dilation is the remedy); rejecting texels whose point lies inside other geometry; directional or SH lightmaps; the multi-device group
- * and render_scene.  The use of a lightmap in shading is the baked frames' block's, below.  Texels that stop on their own error
+ * and render_scene.  (The ambient occlusion block's map counts, per texel, the rays that met a face from behind: that finds the
+ * texels inside other geometry.)  The use of a lightmap in shading is the baked frames' block's, below.  Texels that stop on their own error
  * estimate are mcpt_bake_lightmap_adaptive's (adaptive queries, below). */
 typedef struct { int32_t width, height, spp, sample_base; uint64_t seed;
                  int32_t flags, dilate, reserved[2]; } mcpt_lightmap_params;
@@ -1579,6 +1580,81 @@ int mcpt_render_baked_specular(mcpt_device*, const mcpt_baked_source*, const mcp
 int mcpt_render_baked_specular_device(mcpt_device*, const mcpt_baked_source*, const mcpt_baked_specular*,
                                       const mcpt_baked_frame_params*, double* d_img, int32_t* d_counts3, int32_t* d_lit,
                                       int32_t* d_slit, mcpt_stats*, void* stream);
+
+/* ---- ambient occlusion (since the occlusion change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* AMBIENT OCCLUSION is the share of a surface point's cosine-weighted hemisphere that nothing nearby closes, and the BENT NORMAL the mean
+ * open direction.  A query takes a list of surface points, traces the irradiance query's own rays for their closest hit and folds
+ * distances instead of radiance: no shading at all.  A map is that query over a lightmap's texel list.  The bent normal and ao repair
+ * a coarse irradiance volume at contacts (E_volume(bent) * ao); the back-face count tells the texels whose point lies inside other
+ * geometry.  fp64, no contraction, IEEE division, every expression and sum in the order written.
+ *   list     : n entries, q6 = (position a, normal b of any non-zero finite length), ids[i] or i: MCPT_QUERY_HEMISPHERE's list and keys.
+ *   rays     : sample j of entry i is the ray mcpt_query_radiance's hemisphere kind gives it: the draw of (seed, id, sample_base + j), from
+ *              0.01 off the point.  AN ENTRY'S OCCLUSION RAYS ARE ITS IRRADIANCE RAYS, BIT FOR BIT, for the same seed, id and sample range;
+ *              mcpt_query_rays with MCPT_QUERY_HEMISPHERE is the test seam.
+ *   trace    : the closest hit mcpt_trace_closest_device answers (the device's trace mode and engine, key 0 of a motion, a geometry that
+ *              stands), through the same walks; the rays are drawn on the GPU into the workspace the visibility bakes keep.
+ *   fold     : per entry, in j order, with d the ray's direction, t the hit's distance (measured from the ray's origin, 0.01 off the
+ *              point) and n the hit triangle's stored face normal (mcpt_scene_get_faces: geom27[24..26]):
+ *                hit = the ray hit anything; near = hit && t < max_distance; x = t / max_distance;
+ *                v = 1.0 when not near, otherwise 0.0 (MCPT_OCCLUSION_HARD), x (_LINEAR) or x * x (_SQUARE);
+ *                s1 += v; s2 += v * v; bx += d.x * v, by += d.y * v, bz += d.z * v;
+ *                hits += near; back += near && ((d.x n.x + d.y n.y) + d.z n.z) > 0.0.
+ *              The stored normal is normalize(cross(v1 - v2, v3 - v1)) of the face's vertices, the library's rule everywhere: `back`
+ *              means what it says in a scene whose faces wind so that this normal points into free space.  A scene wound the other way
+ *              (cornell-box is) reports every near hit as a back-face hit: its caller reads hits - back instead.
+ *   outputs  : ao[i] = s1 / spp; stderr1[i] = 0 when spp < 2, else sqrt(max((s2 - s1 * s1 / spp) / (spp - 1), 0) / spp), the radiance
+ *              query's expression; bent3[i] = (bx, by, bz) / l with l = sqrt((bx bx + by by) + bz bz) when l is finite and > 0, otherwise
+ *              the hemisphere rule's n^ = b / sqrt((bx bx + by by) + bz bz) of the entry's own normal b; hits[i], back[i].  ao [n] is
+ *              required; stderr1 [n], bent3 [n][3], hits [n] and back [n] may be NULL.
+ *              stats->rays_primary = samples = n * spp, launches = the number of chunks; the other fields are 0.
+ *   chunks   : the call works in chunks of whole entries: at most workspace_rays rays and at least one entry each; 0 selects 4 194 304
+ *              rays.  The workspace is the visibility bakes' own, 84 bytes per ray of the largest chunk so far.  THE RESULT DOES NOT
+ *              DEPEND ON THE CHUNKING: every sum belongs to one entry and is added in j order.
+ *   host fold: mcpt_occlusion_fold_host is the fold alone, on the CPU and without a device, over rays the caller traced: rays6 [n * spp][6]
+ *              (origin, direction; the origin is not read), hit [n * spp] (non-zero: the ray hit), t [n * spp], n3 [n * spp][3] the hit
+ *              faces' normals (read for near samples only); sample j of entry i sits at i * spp + j.  It does not look at the values.
+ *   map      : mcpt_bake_occlusion_lightmap takes everything but the fold from the lightmap baker: the chart, coverage, texel list and
+ *              owner of mcpt_lightmap_texels for a width x height map, unchanged.  AN OCCLUSION MAP IS, BIT FOR BIT, mcpt_query_occlusion
+ *              OVER mcpt_lightmap_texels' LIST WITH ids = texels.  scatter: ao[T], stderr1[T], bent3[T], hits[T], back[T] = the answers
+ *              of the entry of texel T; every texel that is not covered gets +0.0 and 0.  dilation: `dilate` rounds, 0 .. 64, of the
+ *              lightmap's rule on ao alone -- the same neighbour order, s / c from s = 0.0, owner = -1 - r; stderr1, bent3, hits and back
+ *              of filled texels stay 0.  ao [W*H] is required; stderr1 [W*H], bent3 [W*H*3], hits, back and owner [W*H] may be NULL.
+ *              stats are the query's over the covered texels.  No texel covered: MCPT_OK, no query is launched.
+ * The host-pointer forms are synchronous and copy in and out around the device forms.  The _device forms take device pointers throughout
+ * and enqueue on `stream`.  The query returns without waiting when stats == NULL, after first waiting for the event behind the device's
+ * previous visibility or occlusion call; it uses the counters and queue words of mcpt_trace_closest_device and, like it, must not
+ * overlap another closest-hit call of the same device on another stream.  THE MAP'S DEVICE FORM WAITS ONCE FOR THE STREAM, for the number
+ * of covered texels, as mcpt_bake_lightmap_device does, and first waits for the device's previous bake; besides the baker's raster and
+ * list it keeps 48 bytes per covered texel and, with dilation, 12 per texel.  Calls are allowed while progressive handles of the device
+ * live: they touch none of a handle's state.
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE, in this order): NULL parameters; spp < 1; sample_base < 0; sample_base + spp > 2^31 - 1;
+ * an unknown falloff; flags != 0; max_distance not finite or <= 0; workspace_rays < 0; reserved != 0; n < 0 or n > 2^31 - 1; NULL q6 or
+ * ao with n > 0; mcpt_query_occlusion: the list checks of the hemisphere kind (a negative id, a component that is not finite, a normal of
+ * length zero or not finite); mcpt_occlusion_fold_host: NULL rays6, hit, t or n3 with n > 0.  The map: a NULL mcpt_occlusion_map; a size
+ * outside 1 .. 16384; dilate outside 0 .. 64; its reserved != 0; then the parameters' errors as above; NULL ao; in the host-pointer form
+ * a chart component that is not finite, after the missing device, as in mcpt_bake_lightmap.  n == 0: MCPT_OK, nothing is launched.  A
+ * workspace or a copy that cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable.
+ * Not covered: adaptive occlusion queries; denoising occlusion maps; occlusion as an input of mcpt_render_baked; two-sided or
+ * per-material occlusion; a ray source inside the trace engines (the rays go through a workspace); detecting a scene's winding; the
+ * multi-device group (mcpt_multi_*) and render_scene. */
+#define MCPT_OCCLUSION_HARD   0   /* a near hit closes its direction */
+#define MCPT_OCCLUSION_LINEAR 1   /* ... leaves t / max_distance of it open */
+#define MCPT_OCCLUSION_SQUARE 2   /* ... leaves (t / max_distance)^2 of it open */
+typedef struct { int32_t spp, sample_base; uint64_t seed; int32_t falloff, flags; double max_distance;
+                 int64_t workspace_rays; int32_t reserved[2]; } mcpt_occlusion_params;          /* 48 bytes */
+typedef struct { int32_t width, height, dilate, reserved; } mcpt_occlusion_map;                  /* 16 bytes */
+int mcpt_query_occlusion(mcpt_device*, const double* q6, const int32_t* ids, int64_t n, const mcpt_occlusion_params*,
+                         double* ao, double* stderr1, double* bent3, int32_t* hits, int32_t* back, mcpt_stats*);
+int mcpt_query_occlusion_device(mcpt_device*, const double* d_q6, const int32_t* d_ids, int64_t n, const mcpt_occlusion_params*,
+                                double* d_ao, double* d_stderr1, double* d_bent3, int32_t* d_hits, int32_t* d_back, mcpt_stats*,
+                                void* stream);
+int mcpt_occlusion_fold_host(const double* q6, const double* rays6, const int32_t* hit, const double* t, const double* n3, int64_t n,
+                             const mcpt_occlusion_params*, double* ao, double* stderr1, double* bent3, int32_t* hits, int32_t* back);
+int mcpt_bake_occlusion_lightmap(mcpt_device*, const double* uv6, const mcpt_occlusion_map*, const mcpt_occlusion_params*,
+                                 double* ao, double* stderr1, double* bent3, int32_t* hits, int32_t* back, int32_t* owner, mcpt_stats*);
+int mcpt_bake_occlusion_lightmap_device(mcpt_device*, const double* d_uv6, const mcpt_occlusion_map*, const mcpt_occlusion_params*,
+                                        double* d_ao, double* d_stderr1, double* d_bent3, int32_t* d_hits, int32_t* d_back,
+                                        int32_t* d_owner, mcpt_stats*, void* stream);
 
 #ifdef __cplusplus
 }

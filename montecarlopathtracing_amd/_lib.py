@@ -252,6 +252,18 @@ class BakedSpecularOutputs(C.Structure):
                 ("reserved", C.c_int64 * 2)]
 
 
+class OcclusionParams(C.Structure):
+    """mcpt_occlusion_params: samples per entry, first sample index, seed, the falloff (MCPT_OCCLUSION_*), flags (0), the distance beyond
+    which a hit no longer occludes, and the workspace's size in rays (0: the default)"""
+    _fields_ = [("spp", C.c_int32), ("sample_base", C.c_int32), ("seed", C.c_uint64), ("falloff", C.c_int32), ("flags", C.c_int32),
+                ("max_distance", C.c_double), ("workspace_rays", C.c_int64), ("reserved", C.c_int32 * 2)]
+
+
+class OcclusionMap(C.Structure):
+    """mcpt_occlusion_map: an occlusion map's size and dilation rounds"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("dilate", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -303,6 +315,8 @@ EXPORTS = [
     "mcpt_reflection_lookup_host", "mcpt_reflection_lookup", "mcpt_reflection_lookup_device",
     "mcpt_reflection_volume_lookup_host", "mcpt_reflection_volume_lookup", "mcpt_reflection_volume_lookup_device",
     "mcpt_baked_radiance_specular", "mcpt_baked_radiance_specular_device", "mcpt_render_baked_specular", "mcpt_render_baked_specular_device",
+    "mcpt_query_occlusion", "mcpt_query_occlusion_device", "mcpt_occlusion_fold_host",
+    "mcpt_bake_occlusion_lightmap", "mcpt_bake_occlusion_lightmap_device",
 ]
 
 
@@ -541,6 +555,12 @@ def lib():
     L.mcpt_baked_radiance_specular_device.argtypes = [P, BS, SP, P, C.c_int64, C.c_int32, BO, SO, C.POINTER(Stats), P]
     L.mcpt_render_baked_specular.argtypes = [P, BS, SP, BF, D, I32, I32, I32, C.POINTER(Stats)]
     L.mcpt_render_baked_specular_device.argtypes = [P, BS, SP, BF, P, P, P, P, C.POINTER(Stats), P]
+    OP, OM = C.POINTER(OcclusionParams), C.POINTER(OcclusionMap)
+    L.mcpt_query_occlusion.argtypes = [P, D, I32, C.c_int64, OP, D, D, D, I32, I32, C.POINTER(Stats)]
+    L.mcpt_query_occlusion_device.argtypes = [P, P, P, C.c_int64, OP, P, P, P, P, P, C.POINTER(Stats), P]
+    L.mcpt_occlusion_fold_host.argtypes = [D, D, I32, D, D, C.c_int64, OP, D, D, D, I32, I32]
+    L.mcpt_bake_occlusion_lightmap.argtypes = [P, D, OM, OP, D, D, D, I32, I32, I32, C.POINTER(Stats)]
+    L.mcpt_bake_occlusion_lightmap_device.argtypes = [P, P, OM, OP, P, P, P, P, P, P, C.POINTER(Stats), P]
     _lib = L
     return L
 

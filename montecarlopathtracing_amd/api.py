@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, BakedSpecular, BakedSpecularOutputs, ReflectionParams, ReflectionChain, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, BakedSpecular, BakedSpecularOutputs, ReflectionParams, ReflectionChain, OcclusionParams, OcclusionMap, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -495,6 +495,52 @@ def _visibility_params(spp, res, max_distance, max_back_fraction, seed, sample_b
         raise ValueError("workspace_rays must be a 64-bit integer")
     return VisibilityParams(int(spp), int(sample_base), int(seed), int(res), 0, float(max_distance), float(max_back_fraction), int(workspace_rays),
                             (C.c_int32 * 2)(0, 0))
+
+
+OCCLUSION_HARD, OCCLUSION_LINEAR, OCCLUSION_SQUARE = 0, 1, 2
+_FALLOFFS = {"hard": OCCLUSION_HARD, "linear": OCCLUSION_LINEAR, "square": OCCLUSION_SQUARE}
+
+
+def _occlusion_params(spp, max_distance, falloff, seed, sample_base, workspace_rays):
+    """mcpt_occlusion_params: falloff by name ("hard", "linear", "square") or by its MCPT_OCCLUSION_* number (the library judges a number)"""
+    for name, v in (("spp", spp), ("sample_base", sample_base)):
+        if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("%s must be a 32-bit integer" % name)
+    if not isinstance(workspace_rays, numbers.Integral) or not -2 ** 63 <= workspace_rays < 2 ** 63:
+        raise ValueError("workspace_rays must be a 64-bit integer")
+    if isinstance(falloff, str):
+        if falloff not in _FALLOFFS:
+            raise ValueError('falloff must be "hard", "linear" or "square"')
+        falloff = _FALLOFFS[falloff]
+    elif not isinstance(falloff, numbers.Integral) or not -2 ** 31 <= falloff < 2 ** 31:
+        raise ValueError('falloff must be "hard", "linear", "square" or a 32-bit integer')
+    return OcclusionParams(int(spp), int(sample_base), int(seed), int(falloff), 0, float(max_distance), int(workspace_rays), (C.c_int32 * 2)(0, 0))
+
+
+def occlusion_fold_host(points, normals, rays, hit, t, face_normals, spp, max_distance, falloff="hard"):
+    """The occlusion fold alone, on the CPU (mcpt_occlusion_fold_host; no device): points and normals (n, 3), and for the n * spp rays the
+    caller traced -- sample j of entry i at i * spp + j -- rays (n * spp, 6), hit flags, distances t and the hit faces' normals
+    (n * spp, 3).  Returns a dict: ao [n], stderr [n], bent [n, 3], hits [n], back [n]."""
+    points = np.asarray(points, dtype=np.float64)
+    normals = np.asarray(normals, dtype=np.float64)
+    if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+        raise ValueError("points and normals must both have shape (n, 3)")
+    op = _occlusion_params(spp, max_distance, falloff, 0, 0, 0)
+    n = points.shape[0]
+    m = n * max(int(spp), 0)
+    q = np.ascontiguousarray(np.concatenate([points, normals], axis=1))
+    rays = np.ascontiguousarray(rays, dtype=np.float64)
+    t = np.ascontiguousarray(t, dtype=np.float64)
+    face_normals = np.ascontiguousarray(face_normals, dtype=np.float64)
+    hit = np.ascontiguousarray(np.asarray(hit) != 0, dtype=np.int32)
+    if rays.shape != (m, 6) or t.shape != (m,) or hit.shape != (m,) or face_normals.shape != (m, 3):
+        raise ValueError("rays, hit, t and face_normals must have shapes (%d, 6), (%d,), (%d,) and (%d, 3)" % (m, m, m, m))
+    ao, err, bent = np.zeros(n), np.zeros(n), np.zeros((n, 3))
+    hits, back = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+    check(lib().mcpt_occlusion_fold_host(_p(q, C.c_double), _p(rays, C.c_double), _p(hit, C.c_int32), _p(t, C.c_double), _p(face_normals, C.c_double),
+                                         n, C.byref(op), _p(ao, C.c_double), _p(err, C.c_double), _p(bent, C.c_double), _p(hits, C.c_int32),
+                                         _p(back, C.c_int32)))
+    return {"ao": ao, "stderr": err, "bent": bent, "hits": hits, "back": back}
 
 
 def _adaptive_params(rel_target, abs_target, min_spp):
@@ -1244,6 +1290,45 @@ class Device:
         check(lib().mcpt_volume_irradiance_visible(self._h, C.byref(grid), _p(sh, C.c_double), _p(moments, C.c_double), _p(valid, C.c_uint8), C.byref(vis),
                                                    _p(q, C.c_double), n, _p(E, C.c_double), _p(corners, C.c_int32)))
         return E, corners
+
+    def occlusion(self, points, normals, spp, max_distance, falloff="hard", seed=0, ids=None, sample_base=0, workspace_rays=0, stats=None):
+        """Ambient occlusion at surface points (mcpt_query_occlusion): the rays irradiance() traces for the same seed, ids and sample
+        range, answered by their closest hit alone.  A hit nearer than max_distance closes its direction -- altogether ("hard"), or
+        leaving t / max_distance ("linear") or its square ("square") open.  Returns a dict: ao [n] the open share of the cosine-weighted
+        hemisphere, stderr [n], bent [n, 3] the unit mean open direction (the unit normal where nothing is open), hits [n] the near
+        hits and back [n] those from behind a face.  workspace_rays bounds the rays in flight (0: the library's default); it does not
+        change the result."""
+        points = np.asarray(points, dtype=np.float64)
+        normals = np.asarray(normals, dtype=np.float64)
+        if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+            raise ValueError("points and normals must both have shape (n, 3)")
+        q, ids = self._query_list(np.concatenate([points, normals], axis=1), ids, "points and normals")
+        op = _occlusion_params(spp, max_distance, falloff, seed, sample_base, workspace_rays)
+        n = q.shape[0]
+        ao, err, bent = np.zeros(n), np.zeros(n), np.zeros((n, 3))
+        hits, back = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.int32)
+        check(lib().mcpt_query_occlusion(self._h, _p(q, C.c_double), _p(ids, C.c_int32), n, C.byref(op), _p(ao, C.c_double), _p(err, C.c_double),
+                                         _p(bent, C.c_double), _p(hits, C.c_int32), _p(back, C.c_int32), C.byref(stats) if stats is not None else None))
+        return {"ao": ao, "stderr": err, "bent": bent, "hits": hits, "back": back}
+
+    def bake_occlusion_lightmap(self, width, height, spp, max_distance, uv=None, falloff="hard", seed=0, sample_base=0, dilate=0, workspace_rays=0,
+                                stats=None):
+        """An occlusion map (mcpt_bake_occlusion_lightmap): occlusion() of lightmap_texels()' list with ids = texels, bit for bit, put
+        back into the map; dilate rounds of the lightmap's rule fill the gutters of ao alone.  Returns a dict: ao [height, width],
+        stderr [height, width], bent [height, width, 3], hits, back and owner [height, width]; owner is bake_lightmap()'s."""
+        width, height = _map_size(width, height)
+        if not isinstance(dilate, numbers.Integral) or not -2 ** 31 <= dilate < 2 ** 31:
+            raise ValueError("dilate must be a 32-bit integer")
+        op = _occlusion_params(spp, max_distance, falloff, seed, sample_base, workspace_rays)
+        uv = _chart(uv, self.scene.info.num_faces) if uv is not None else None
+        shape = (max(height, 0), max(width, 0))
+        ao, err, bent = np.zeros(shape), np.zeros(shape), np.zeros(shape + (3,))
+        hits, back, owner = np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int32), np.zeros(shape, dtype=np.int32)
+        om = OcclusionMap(width, height, int(dilate), 0)
+        check(lib().mcpt_bake_occlusion_lightmap(self._h, _p(uv, C.c_double), C.byref(om), C.byref(op), _p(ao, C.c_double), _p(err, C.c_double),
+                                                 _p(bent, C.c_double), _p(hits, C.c_int32), _p(back, C.c_int32), _p(owner, C.c_int32),
+                                                 C.byref(stats) if stats is not None else None))
+        return {"ao": ao, "stderr": err, "bent": bent, "hits": hits, "back": back, "owner": owner}
 
     def lightmap_irradiance(self, E, uv, owner=None):
         """A lightmap's lookup by chart coordinate on the GPU (mcpt_lightmap_irradiance): lightmap_irradiance_host's arguments and

@@ -14,6 +14,7 @@
 //   lightmap_denoise_api.cpp  the lightmap denoiser: a chart-aware a-trous filter of an irradiance map, then the baker's dilation
 //   volume_api.cpp    irradiance volumes: a probe grid's points, its bake through the probe query, the lookup between its probes
 //   visibility_api.cpp  probe visibility: the octahedral bin, the depth-moment bake of a probe list or grid, the visibility-weighted lookup
+//   occlusion_api.cpp  ambient occlusion: the hemisphere rays of a point list folded into occlusion and bent normals, and that query as a map
 //   baked_api.cpp     baked frames: the lightmap's lookup by chart coordinate, baked radiance along a caller's rays, frames lit by a bake
 //   reflection_api.cpp  reflection probes: an octahedral radiance map per probe through the ray query, its Phong prefilter, the chain's lookup
 //   render_scene.cpp  output writers, checkpoints, render_scene
@@ -205,6 +206,10 @@ struct mcpt_device {
         mcpt::DevBuf<int32_t> counts;                   // an adaptive bake: the queries' own sample counts, by list entry
         mcpt::DevBuf<double> q6, mean, err;
         mcpt::DevBuf<double> irr;                       // the dilation's second frame
+        // an occlusion map (occlusion_api.cpp) shares the raster, the list, irr and `done` with the bakes and keeps its query's answers
+        // by list entry, 48 bytes per covered texel: ao [c], stderr [c], bent [c][3]; hits [c], back [c]
+        mcpt::DevBuf<double> occ;
+        mcpt::DevBuf<int32_t> occ_cnt;
         mcpt::HostBuf<int32_t> h_total;                 // pinned word the covered count lands in
         mcpt::Event done;
         // the denoiser (lightmap_denoise_api.cpp) shares owner[], irr and `done` with the bakes and keeps, per texel of the largest map it
@@ -235,7 +240,7 @@ struct mcpt_device {
     };
     std::unique_ptr<Volume> vol;
     // probe visibility (visibility_api.cpp): the rays of a chunk of probes and their closest hits, made by the first bake and grown to the
-    // largest chunk so far, 84 bytes per ray
+    // largest chunk so far, 84 bytes per ray; an occlusion query (occlusion_api.cpp) draws its rays into the same workspace under the same lease
     struct Visibility {
         mcpt::DevBuf<double> rays6, t, p;               // [rays][6], [rays], [rays][3]
         mcpt::DevBuf<int32_t> leaf;                     // [rays]
