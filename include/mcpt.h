@@ -21,6 +21,15 @@
  * with the documented seams D1..D8 of DESIGN.md (counter-based RNG instead of time(NULL) engines, stable
  * Morton sort, serial sample accumulation, CRLF stripping, no virtual-child aliasing, depth cap, texture
  * clamp, Ns/Ni defaults).
+ *
+ * Device pointers.  Every d_* argument (and every device pointer in a struct a _device form takes) need only be aligned to its element
+ * type: 8 bytes for doubles, 4 for int32, 1 for bytes -- what a sub-allocator hands out.  The library reads exactly the documented extent
+ * of each input and writes no input.  It writes exactly the documented extent of each output, in every word of it unless the entry says
+ * otherwise (pixels a partition does not own, for instance), and nothing before or after it.  No answer depends on what an output held
+ * before the call.  Where wider accesses are faster (the display map's four pixels per lane) the launcher takes them only when the
+ * pointers allow it and a slower path otherwise; an entry point that truly needed more would refuse with MCPT_ERR_ARG and say so in its
+ * block below, never misbehave silently.  tests/test_gpu_extents.py holds every device-pointer entry point to this, with each buffer
+ * inside a larger allocation between two bands of a fill byte.
  */
 #ifndef MCPT_H
 #define MCPT_H

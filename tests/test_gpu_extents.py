@@ -1,0 +1,870 @@
+"""Every entry point of include/mcpt.h that reads or writes the caller's own device memory, held to its buffers' exact extents.
+
+The other GPU suites hold the device forms to the host forms through tests/hip_rt.py's DeviceBuffer: an allocation of the payload's own
+size, zeroed, at hipMalloc's alignment.  Here every input and every output of a call sits in a tests/guarded.py Guarded buffer -- inside a
+larger allocation, between two 64 KiB bands of a fill byte, holding that fill, optionally one element off 16-byte alignment -- and for
+every case:
+  (a) each output payload equals, in every word, what the HOST form of the same call answers; where the header documents words the call
+      leaves alone (pixels a partition does not own) exactly those words still hold the fill: the mask is computed here from the header's
+      rule, never from the output;
+  (b) every band of every buffer still holds the fill and every input still holds what was uploaded;
+  (c) the outputs are the same bits under the fills 0xFF and 0xA5 and at both alignments, so no answer depends on what an output held
+      before the call or on a byte outside an input.
+List calls run at n = 1, 65 and B + 1 = 257 (all four (fill, skew) pairs at 257; 0xFF unskewed at the smaller sizes), with odd per-item
+counts and, where a call takes workspace_rays (visibility, occlusion, the reflection bake, the baked frames), a workspace that cuts 257
+items into chunks of 100, 100 and 57; the radiance, SH and adaptive queries size their chunks from the device's path-state budget, which
+no parameter of a call sets: test_list_in_chunks runs them at 257 queries of 301 samples on a device whose budget holds 118 (or 83)
+such queries a chunk.  The calls go through the C ABI, on a side stream, with every optional output present and
+stats == NULL.
+
+Coverage: symbol | case | sizes | block constant the sizes come from
+  mcpt_trace_closest_device             | test_list[trace_closest]       | n 1, 65, 257                          | 256: k_wf_trace / k_query_* launches (query.hip, dim3(256))
+  mcpt_query_radiance_device            | test_list[radiance], test_list_in_chunks | n 1, 65, 257; spp 3 and 301                  | 256: query.hip __launch_bounds__(256)
+  mcpt_query_radiance_adaptive_device   | test_list[adaptive], test_list_in_chunks | n 1, 65, 257; spp 5 and 301, min 2           | 256: adaptive_query.hip __launch_bounds__(256)
+  mcpt_query_sh_device                  | test_list[sh], test_list_in_chunks | n 1, 65, 257; spp 3 and 301                  | 256: query.hip k_query_fold_sh
+  mcpt_query_visibility_device          | test_list[visibility]          | n 1, 65, 257; spp 5, res 4            | 256: visibility.hip kVisBlock
+  mcpt_query_occlusion_device           | test_list[occlusion]           | n 1, 65, 257; spp 5                   | 256: occlusion.hip kOccBlock
+  mcpt_bake_reflection_device           | test_list[reflection_bake]     | n 1, 65, 257; res 5, spp 3            | 256: reflection.hip kReflBlock
+  mcpt_reflection_prefilter_device      | test_list[reflection_prefilter]| n 1, 65, 257; res 5 -> levels 4, 2    | 256: reflection.hip kReflBlock
+  mcpt_reflection_lookup_device         | test_list[reflection_lookup]   | m 1, 65, 257; 3 probes                | 256: reflection.hip kReflBlock
+  mcpt_reflection_volume_lookup_device  | test_list[reflection_volume]   | m 1, 65, 257; grid 3 x 2 x 2          | 256: baked_specular.hip kSpecBlock
+  mcpt_volume_irradiance_device         | test_list[volume_lookup]       | n 1, 65, 257; grid 3 x 2 x 2          | 256: volume.hip kVolBlock
+  mcpt_volume_irradiance_visible_device | test_list[volume_lookup_visible]| n 1, 65, 257; grid 3 x 2 x 2         | 256: visibility.hip kVisBlock
+  mcpt_lightmap_irradiance_device       | test_list[lightmap_lookup]     | n 1, 65, 257; map 16 x 16             | 256: baked.hip kBakedBlock
+  mcpt_baked_radiance_device            | test_list[baked-volume], [baked-lightmap] | n 1, 65, 257                | 256: baked.hip kBakedBlock
+  mcpt_baked_radiance_specular_device   | test_list[baked_specular]      | n 1, 65, 257                          | 256: baked_specular.hip kSpecBlock
+  mcpt_bake_lightmap_device             | test_map[lightmap-*]           | 33 x 17 dilate 0 and 2, 1 x 1; chart null and guarded | 256: lightmap.hip kLmBlock
+  mcpt_bake_lightmap_adaptive_device    | test_map[adaptive-*]           | 33 x 17 dilate 0 and 2, 1 x 1; chart null and guarded | 256: lightmap.hip kLmBlock
+  mcpt_bake_occlusion_lightmap_device   | test_map[occlusion-*]          | 33 x 17 dilate 0 and 2, 1 x 1; chart null and guarded | 256: occlusion.hip kOccBlock, lightmap.hip kLmBlock
+  mcpt_lightmap_denoise_device          | test_map[denoise-*]            | 33 x 17 dilate 0 and 2, 1 x 1; chart null and guarded | 256: lightmap_denoise.hip kLmdBlock
+  mcpt_bake_volume_device               | test_grid[volume-*]            | grids 3 x 2 x 2 and 1 x 1 x 1; spp 33 | 256: volume.hip kVolBlock
+  mcpt_bake_volume_visibility_device    | test_grid[visibility-*]        | grids 3 x 2 x 2 and 1 x 1 x 1; res 8  | 256: visibility.hip kVisBlock
+  mcpt_render_device                    | test_frame_render             | 33 x 17 and 1 x 1; world 2, ranks 0 and 1, tiles 32 x 8 and 5 x 3 | 256: wavefront.hip fold
+  mcpt_render_baked_device              | test_frame_baked[baked-*]      | 33 x 17 and 1 x 1; 3 samples          | 256: baked.hip kBakedBlock
+  mcpt_render_baked_specular_device     | test_frame_baked[baked_specular-*] | 33 x 17 and 1 x 1; 3 samples          | 256: baked_specular.hip kSpecBlock
+  mcpt_progressive_image_device         | test_frame_progressive[image-*]            | 33 x 17 rank 1 of 2, and 1 x 1        | 256: kernels.hip
+  mcpt_progressive_denoise_device       | test_frame_progressive[denoise-*]          | 33 x 17 rank 1 of 2, and 1 x 1        | 256: denoise.hip
+  mcpt_progressive_denoise_guided_device| test_frame_progressive[guided-*]           | 33 x 17 rank 1 of 2, and 1 x 1        | 256: denoise.hip
+  mcpt_progressive_display_device       | test_frame_progressive[display-*]          | 33 x 17 rank 1 of 2, and 1 x 1; RGB and RGBA | 256: display.hip kDisplayBlock
+  mcpt_display_device                   | test_display                   | n_pixels 1, 5, 1023; RGB and RGBA     | 256: display.hip kDisplayBlock, four pixels per lane
+  mcpt_display_histogram_device         | test_display                   | n_pixels 1, 5, 1023 (input only)      | 256: display.hip kDisplayBlock
+  mcpt_device_update_vertices_device    | test_update[refit], [rebuild]  | the scene's faces x 9 (input only)    | 256: build_kernels.hip
+  mcpt_device_set_motion_device         | test_update[motion]            | the scene's faces x 9 (input only)    | 256: build_kernels.hip
+  mcpt_multi_render_device              | test_multi_frame               | 64 x 36; *d_img is the handle's own, so it cannot be guarded: held to mcpt_multi_render | 256: wavefront.hip fold
+  mcpt_comm_gather_frame                | NOT COVERED here               | needs an RCCL communicator of several processes, one GPU each (tests/test_gpu_parity.py drives it through procs.py) | none
+
+112 cases; the whole file takes 2.0 s of wall time on an MI355X (pytest's own figure, devices and bakes included).
+"""
+import ctypes as C
+import os
+import types
+
+import numpy as np
+import pytest
+
+import query_family as QF
+from conftest import SCENES
+from guarded import FILLS, G, Guarded, fill_value
+from hip_rt import Stream
+from montecarlopathtracing_amd._lib import check
+from montecarlopathtracing_amd.api import _adaptive_params, _p, _visibility_params
+
+pytestmark = pytest.mark.gpu
+
+KNOBS = ("MCPT_TRACE_ENGINE", "MCPT_FINISH_ENGINE", "MCPT_FINISH_PATHS", "MCPT_WORKSPACE_GB")
+F64, I32, U8 = np.dtype(np.float64), np.dtype(np.int32), np.dtype(np.uint8)
+CT = {F64: C.c_double, I32: C.c_int32, U8: C.c_uint8}
+B = 256                                         # the block size of every kernel behind these calls (the table names each source's constant)
+SIZES = (1, 65, B + 1)
+ALL = tuple((f, s) for f in FILLS for s in (False, True))
+ONE = ((0xFF, False),)
+CHUNK = 100                                     # items per chunk: 257 = 100 + 100 + 57
+SPP, VIS_SPP, OCC_SPP = 3, 5, 5
+SMALL = ((33, 17), (1, 1))
+
+
+# ---- the buffers of a call and its two forms
+
+class In:
+    def __init__(self, a, dtype=None):
+        self.a = np.ascontiguousarray(a, dtype=dtype)
+        self.dtype, self.shape = self.a.dtype, self.a.shape
+
+
+class Out:
+    def __init__(self, shape, dtype, keep=None):
+        """keep: the elements the header says the call leaves as they were (a boolean array of `shape`), or None: every word is written"""
+        self.shape, self.dtype, self.keep = tuple(shape), np.dtype(dtype), keep
+
+
+class Case:
+    """bufs: {name: In | Out | None}; call(device, p, stream) -> the entry point's return code, p(buf) the pointer argument of a buffer in
+    the form that is called and p.addr(buf) its address for a struct field"""
+
+    def __init__(self, name, bufs, call):
+        self.name, self.bufs, self.call = name, {k: v for k, v in bufs.items() if v is not None}, call
+
+
+class HostP:
+    def __init__(self, fill):
+        self.fill, self.arrays = fill, {}
+
+    def arr(self, b):
+        if isinstance(b, In):
+            return b.a
+        if id(b) not in self.arrays:
+            self.arrays[id(b)] = np.full(b.shape, fill_value(b.dtype, self.fill), b.dtype)
+        return self.arrays[id(b)]
+
+    def __call__(self, b):
+        return None if b is None else _p(self.arr(b), CT[b.dtype])
+
+    def addr(self, b):
+        return None if b is None else self.arr(b).ctypes.data
+
+
+class DevP:
+    def __init__(self, fill, skewed):
+        self.fill, self.skewed, self.g = fill, skewed, {}
+
+    def buf(self, b):
+        if id(b) not in self.g:
+            self.g[id(b)] = Guarded(b.a if isinstance(b, In) else int(np.prod(b.shape)) * b.dtype.itemsize, b.dtype, self.fill,
+                                    b.dtype.itemsize if self.skewed else 0)
+        return self.g[id(b)]
+
+    def __call__(self, b):
+        return None if b is None else self.buf(b).ptr
+
+    addr = __call__
+
+    def free(self):
+        for g in self.g.values():
+            g.free()
+
+
+def bits(a):
+    return QF.bits(a).reshape(-1)
+
+
+def host(w, case, fill=0xFF):
+    """the host form's answer: {name: array}, every output array holding `fill` before the call"""
+    p = HostP(fill)
+    rc = case.call(False, p, None)
+    assert rc == 0, (case.name, rc, w.lib.mcpt_last_error())
+    return {k: p.arr(b) for k, b in case.bufs.items() if isinstance(b, Out)}
+
+
+def device(w, case, fill, skewed):
+    """the device form on the side stream with every buffer guarded: the output payloads, after (b) held for every buffer"""
+    p = DevP(fill, skewed)
+    try:
+        rc = case.call(True, p, w.stream.h)
+        assert rc == 0, (case.name, rc, w.lib.mcpt_last_error())
+        w.stream.synchronize()
+        got = {k: p.buf(b).payload().reshape(b.shape) for k, b in case.bufs.items() if isinstance(b, Out)}
+        for k, b in case.bufs.items():
+            p.buf(b).check("%s: %s" % (case.name, k))                                                   # (b)
+        return got
+    finally:
+        p.free()
+
+
+def hold(w, case, configs):
+    want = host(w, case)
+    first = None
+    for fill, skewed in configs:
+        got = device(w, case, fill, skewed)
+        for k, b in case.bufs.items():
+            if not isinstance(b, Out):
+                continue
+            what = "%s: %s under fill 0x%02X%s" % (case.name, k, fill, ", skewed" if skewed else "")
+            g, h = bits(got[k]), bits(want[k])
+            live = np.ones(g.shape, bool) if b.keep is None else ~np.ascontiguousarray(b.keep).reshape(-1)
+            bad = np.flatnonzero((g != h) & live)
+            assert bad.size == 0, "%s: %d of %d words differ from the host form's, the first at word %d" % (what, bad.size, int(live.sum()), bad[0])   # (a)
+            if b.keep is not None:
+                f = bits(np.array([fill_value(b.dtype, fill)]))[0]
+                bad = np.flatnonzero((g != f) & ~live)
+                assert bad.size == 0, "%s: %d of the %d words the header leaves alone were written, the first word %d" % (what, bad.size, int((~live).sum()), bad[0])
+                assert (h[~live] == bits(np.array([fill_value(b.dtype, 0xFF)]))[0]).all(), "%s: the host form wrote words the header leaves alone" % what
+            if first is not None:
+                assert np.array_equal(g[live], bits(first[k])[live]), what + ": differs from the first run's"   # (c)
+        first = first or got
+    return want
+
+
+# ---- one device of cornell-box at query_family's size, and what the lookups and baked calls read
+
+@pytest.fixture(autouse=True)
+def _clean_env(monkeypatch):
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+
+
+def take(a, n):
+    """n entries of a query list, around again where the list is shorter"""
+    return np.ascontiguousarray(a[np.arange(n) % len(a)])
+
+
+@pytest.fixture(scope="module")
+def w(mcpt):
+    saved = {k: os.environ.pop(k) for k in KNOBS if k in os.environ}
+    try:
+        sc = mcpt.Scene(SCENES, "cornell-box", width=QF.W, height=QF.H)
+        dev = mcpt.Device(sc, 0)
+    finally:
+        os.environ.update(saved)
+    geom = sc.faces()[0]
+    w = types.SimpleNamespace(mcpt=mcpt, lib=mcpt.lib(), sc=sc, dev=dev, h=dev._h, geom=geom, q=QF.lists(mcpt, geom[:, :9]), stream=Stream(),
+                              small={}, cache={})
+    w.recv = np.ascontiguousarray(np.concatenate([w.q["points"], w.q["normals"]], axis=1))
+    w.chart = np.ascontiguousarray(0.05 + 0.9 * geom[:, 18:24])          # a chart of the caller's own: the scene's, shrunk into the map
+    yield w
+    if "tight" in w.cache:
+        w.cache["tight"].close()
+    for sc2, dev2 in w.small.values():
+        dev2.close()
+        sc2.close()
+    w.stream.destroy()
+    dev.close()
+    sc.close()
+
+
+def small(w, size):
+    """a device of the same scene with a width x height camera"""
+    if size not in w.small:
+        sc = w.mcpt.Scene(SCENES, "cornell-box", width=size[0], height=size[1])
+        w.small[size] = (sc, w.mcpt.Device(sc, 0))
+    return w.small[size]
+
+
+def sh_params(w, spp):
+    return w.mcpt.ShParams(spp, 0, QF.SEED, 0, (C.c_int32 * 3)(0, 0, 0))
+
+
+def bake_volume_case(w, g, name="bake_volume"):
+    shape = (g.nz, g.ny, g.nx)
+    sp = sh_params(w, QF.VOLUME_SPP)
+    o = dict(sh27=Out(shape + (9, 3), F64), stderr27=Out(shape + (9, 3), F64), hits=Out(shape, I32))
+
+    def call(dv, p, st):
+        if dv:
+            return w.lib.mcpt_bake_volume_device(w.h, C.byref(g), C.byref(sp), p(o["sh27"]), p(o["stderr27"]), p(o["hits"]), None, st)
+        return w.lib.mcpt_bake_volume(w.h, C.byref(g), C.byref(sp), p(o["sh27"]), p(o["stderr27"]), p(o["hits"]), None)
+    return Case(name, o, call)
+
+
+def bake_visibility_case(w, g, name="bake_volume_visibility"):
+    shape, res = (g.nz, g.ny, g.nx), QF.GRID_VIS_RES
+    vp = _visibility_params(QF.GRID_VIS_SPP, res, w.q["grid_distance"], QF.BACK_FRACTION, QF.SEED, 0, 0)
+    o = dict(moments=Out(shape + (res * res, 2), F64), hits=Out(shape, I32), back=Out(shape, I32), valid=Out(shape, U8))
+
+    def call(dv, p, st):
+        a = (w.h, C.byref(g), C.byref(vp), p(o["moments"]), p(o["hits"]), p(o["back"]), p(o["valid"]), None)
+        return w.lib.mcpt_bake_volume_visibility_device(*a, st) if dv else w.lib.mcpt_bake_volume_visibility(*a)
+    return Case(name, o, call)
+
+
+def lightmap_case(w, kind, width, height, dilate, chart, E=None, err=None):
+    """kind: lightmap, adaptive, occlusion or denoise (which reads E and err, a bake of the same size and chart)"""
+    uv = In(w.chart) if chart else None
+    px = (height, width)
+    if kind == "denoise":
+        dp = w.mcpt.LightmapDenoiseParams(width, height, 3, dilate, 0.0, 0.0, (C.c_int32 * 2)(0, 0))
+        b = dict(uv6=uv, irradiance3=In(E), stderr3=In(err), out3=Out(px + (3,), F64), owner=Out(px, I32))
+
+        def call(dv, p, st):
+            a = (w.h, p(uv), C.byref(dp), p(b["irradiance3"]), p(b["stderr3"]), p(b["out3"]), p(b["owner"]))
+            return w.lib.mcpt_lightmap_denoise_device(*a, st) if dv else w.lib.mcpt_lightmap_denoise(*a)
+    elif kind == "occlusion":
+        om = w.mcpt.OcclusionMap(width, height, dilate, 0)
+        op = w.mcpt.OcclusionParams(OCC_SPP, 0, QF.SEED, 1, 0, w.q["vis_distance"], CHUNK * OCC_SPP, (C.c_int32 * 2)(0, 0))
+        b = dict(uv6=uv, ao=Out(px, F64), stderr1=Out(px, F64), bent3=Out(px + (3,), F64), hits=Out(px, I32), back=Out(px, I32), owner=Out(px, I32))
+
+        def call(dv, p, st):
+            a = (w.h, p(uv), C.byref(om), C.byref(op)) + tuple(p(b[k]) for k in ("ao", "stderr1", "bent3", "hits", "back", "owner")) + (None,)
+            return w.lib.mcpt_bake_occlusion_lightmap_device(*a, st) if dv else w.lib.mcpt_bake_occlusion_lightmap(*a)
+    else:
+        adaptive = kind == "adaptive"
+        lp = w.mcpt.LightmapParams(width, height, 5 if adaptive else SPP, 0, QF.SEED, 0, dilate, (C.c_int32 * 2)(0, 0))
+        ap = _adaptive_params(QF.ADAPTIVE_REL, 0.0, 2)
+        b = dict(uv6=uv, irradiance3=Out(px + (3,), F64), stderr3=Out(px + (3,), F64), hits=Out(px, I32), owner=Out(px, I32),
+                 counts=Out(px, I32) if adaptive else None)
+
+        def call(dv, p, st):
+            outs = tuple(p(b[k]) for k in ("irradiance3", "stderr3", "hits", "owner"))
+            if adaptive:
+                a = (w.h, p(uv), C.byref(lp), C.byref(ap)) + outs + (p(b["counts"]), None)
+                return w.lib.mcpt_bake_lightmap_adaptive_device(*a, st) if dv else w.lib.mcpt_bake_lightmap_adaptive(*a)
+            a = (w.h, p(uv), C.byref(lp)) + outs + (None,)
+            return w.lib.mcpt_bake_lightmap_device(*a, st) if dv else w.lib.mcpt_bake_lightmap(*a)
+    return Case("%s %dx%d dilate %d %s chart" % (kind, width, height, dilate, "guarded" if chart else "null"), b, call)
+
+
+def baked(w):
+    """what the lookups and the baked calls read, made once by the host forms: the volume, its visibility, a lightmap, a reflection volume"""
+    if "baked" not in w.cache:
+        m, g = w.mcpt, w.q["grid"]
+        d = types.SimpleNamespace(grid=g)
+        d.sh = host(w, bake_volume_case(w, g))["sh27"]
+        v = host(w, bake_visibility_case(w, g))
+        d.moments, d.valid = v["moments"], v["valid"]
+        d.vis = m.volume_visibility(QF.GRID_VIS_RES, w.q["grid_distance"], normal_bias=0.01 * w.q["grid_distance"])
+        lm = host(w, lightmap_case(w, "lightmap", QF.MAP, QF.MAP, 2, False))
+        d.E, d.owner = lm["irradiance3"], lm["owner"]
+        d.chain_desc = m.reflection_chain(QF.REFL_RES, [(4, 64), (2, 4)])
+        pts = np.zeros((g.num_probes, 3))
+        check(w.lib.mcpt_volume_points(C.byref(g), _p(pts, C.c_double)))
+        rad = host(w, reflection_bake_case(w, pts, np.arange(g.num_probes, dtype=np.int32) * 1000))["radiance"]
+        d.chain = host(w, prefilter_case(w, d.chain_desc, rad))["chain"]
+        w.cache["baked"] = d
+    return w.cache["baked"]
+
+
+# ---- the list calls
+
+def radiance_case(w, n, adaptive=False, h=None, spp=None):
+    h = h or w.h
+    q, ids = In(take(w.q["rays"], n)), In(take(w.q["ids"], n))
+    qp = w.mcpt.QueryParams(spp or (5 if adaptive else SPP), QF.RAY_BASE, QF.SEED, w.mcpt.QUERY_RAY, 0, (C.c_int32 * 2)(0, 0))
+    ap = _adaptive_params(QF.ADAPTIVE_REL, 0.0, 2)
+    b = dict(q6=q, ids=ids, mean3=Out((n, 3), F64), stderr3=Out((n, 3), F64), hits=Out((n,), I32), counts=Out((n,), I32) if adaptive else None)
+
+    def call(dv, p, st):
+        outs = (p(b["mean3"]), p(b["stderr3"]), p(b["hits"]))
+        if adaptive:
+            a = (h, p(q), p(ids), n, C.byref(qp), C.byref(ap)) + outs + (p(b["counts"]), None)
+            return w.lib.mcpt_query_radiance_adaptive_device(*a, st) if dv else w.lib.mcpt_query_radiance_adaptive(*a)
+        a = (h, p(q), p(ids), n, C.byref(qp)) + outs + (None,)
+        return w.lib.mcpt_query_radiance_device(*a, st) if dv else w.lib.mcpt_query_radiance(*a)
+    return Case("adaptive" if adaptive else "radiance", b, call)
+
+
+def sh_case(w, n, h=None, spp=None):
+    h = h or w.h
+    sp = sh_params(w, spp or SPP)
+    b = dict(p3=In(take(w.q["probes"], n)), ids=In(take(w.q["ids"], n)), sh27=Out((n, 9, 3), F64), stderr27=Out((n, 9, 3), F64), hits=Out((n,), I32))
+
+    def call(dv, p, st):
+        a = (h, p(b["p3"]), p(b["ids"]), n, C.byref(sp), p(b["sh27"]), p(b["stderr27"]), p(b["hits"]), None)
+        return w.lib.mcpt_query_sh_device(*a, st) if dv else w.lib.mcpt_query_sh(*a)
+    return Case("sh", b, call)
+
+
+def visibility_case(w, n):
+    res = QF.VIS_RES
+    vp = _visibility_params(VIS_SPP, res, w.q["vis_distance"], QF.BACK_FRACTION, QF.SEED, 0, CHUNK * VIS_SPP)
+    b = dict(p3=In(take(w.q["vis_probes"], n)), ids=In(take(w.q["ids"], n)), moments=Out((n, res * res, 2), F64), hits=Out((n,), I32),
+             back=Out((n,), I32), valid=Out((n,), U8))
+
+    def call(dv, p, st):
+        a = (w.h, p(b["p3"]), p(b["ids"]), n, C.byref(vp), p(b["moments"]), p(b["hits"]), p(b["back"]), p(b["valid"]), None)
+        return w.lib.mcpt_query_visibility_device(*a, st) if dv else w.lib.mcpt_query_visibility(*a)
+    return Case("visibility", b, call)
+
+
+def occlusion_case(w, n):
+    op = w.mcpt.OcclusionParams(OCC_SPP, 0, QF.SEED, 1, 0, w.q["vis_distance"], CHUNK * OCC_SPP, (C.c_int32 * 2)(0, 0))
+    b = dict(q6=In(take(w.recv, n)), ids=In(take(w.q["point_ids"], n)), ao=Out((n,), F64), stderr1=Out((n,), F64), bent3=Out((n, 3), F64),
+             hits=Out((n,), I32), back=Out((n,), I32))
+
+    def call(dv, p, st):
+        a = (w.h, p(b["q6"]), p(b["ids"]), n, C.byref(op)) + tuple(p(b[k]) for k in ("ao", "stderr1", "bent3", "hits", "back")) + (None,)
+        return w.lib.mcpt_query_occlusion_device(*a, st) if dv else w.lib.mcpt_query_occlusion(*a)
+    return Case("occlusion", b, call)
+
+
+def trace_case(w, n):
+    b = dict(rays=In(take(w.q["rays"], n)), face=Out((n,), I32), t=Out((n,), F64), p=Out((n, 3), F64), pn=Out((n, 3), F64))
+
+    def call(dv, p, st):
+        a = (w.h, p(b["rays"]), n, p(b["face"]), p(b["t"]), p(b["p"]), p(b["pn"]))
+        return w.lib.mcpt_trace_closest_device(*a, st) if dv else w.lib.mcpt_trace_closest(*a, None)
+    return Case("trace_closest", b, call)
+
+
+def reflection_bake_case(w, points, base):
+    n, R = len(points), QF.REFL_RES
+    rp = w.mcpt.ReflectionParams(SPP, 0, QF.SEED, R, 0, CHUNK * R * R * SPP, (C.c_int32 * 4)(0, 0, 0, 0))
+    b = dict(p3=In(points), id_base=In(base, np.int32), radiance=Out((n, R * R, 3), F64), stderr3=Out((n, R * R, 3), F64), hits=Out((n, R * R), I32))
+
+    def call(dv, p, st):
+        a = (w.h, p(b["p3"]), p(b["id_base"]), n, C.byref(rp), p(b["radiance"]), p(b["stderr3"]), p(b["hits"]), None)
+        return w.lib.mcpt_bake_reflection_device(*a, st) if dv else w.lib.mcpt_bake_reflection(*a)
+    return Case("reflection_bake", b, call)
+
+
+def prefilter_case(w, c, rad):
+    n = len(rad)
+    b = dict(radiance=In(rad), chain=Out((n, c.num_texels, 3), F64))
+
+    def call(dv, p, st):
+        a = (w.h, C.byref(c), p(b["radiance"]), n, p(b["chain"]))
+        return w.lib.mcpt_reflection_prefilter_device(*a, st) if dv else w.lib.mcpt_reflection_prefilter(*a)
+    return Case("reflection_prefilter", b, call)
+
+
+def directions(m, seed):
+    rng = np.random.default_rng(seed)
+    return np.ascontiguousarray(rng.normal(size=(m, 3))), np.ascontiguousarray(rng.random(m) * 80.0)
+
+
+def reflection_lookup_case(w, m):
+    d = baked(w)
+    n = 3
+    d3, x = directions(m, 9)
+    b = dict(chain=In(d.chain.reshape(-1, d.chain_desc.num_texels, 3)[:n]), probe=In((np.arange(m) % n).astype(np.int32)), d3=In(d3), x=In(x),
+             out3=Out((m, 3), F64))
+
+    def call(dv, p, st):
+        a = (w.h, C.byref(d.chain_desc), p(b["chain"]), n, p(b["probe"]), p(b["d3"]), p(b["x"]), m, p(b["out3"]))
+        return w.lib.mcpt_reflection_lookup_device(*a, st) if dv else w.lib.mcpt_reflection_lookup(*a)
+    return Case("reflection_lookup", b, call)
+
+
+def reflection_volume_case(w, m):
+    d = baked(w)
+    d3, x = directions(m, 10)
+    b = dict(chain=In(d.chain), valid=In(d.valid), moments=In(d.moments), q6=In(take(w.recv, m)), d3=In(d3), x=In(x), out3=Out((m, 3), F64),
+             corners=Out((m,), I32))
+
+    def call(dv, p, st):
+        a = (w.h, C.byref(d.grid), C.byref(d.chain_desc), p(b["chain"]), p(b["valid"]), p(b["moments"]), C.byref(d.vis), p(b["q6"]), p(b["d3"]),
+             p(b["x"]), m, p(b["out3"]), p(b["corners"]))
+        return w.lib.mcpt_reflection_volume_lookup_device(*a, st) if dv else w.lib.mcpt_reflection_volume_lookup(*a)
+    return Case("reflection_volume", b, call)
+
+
+def volume_lookup_case(w, n, visible):
+    d = baked(w)
+    b = dict(sh27=In(d.sh), moments=In(d.moments) if visible else None, valid=In(d.valid), q6=In(take(w.recv, n)), e3=Out((n, 3), F64),
+             corners=Out((n,), I32))
+
+    def call(dv, p, st):
+        if visible:
+            a = (w.h, C.byref(d.grid), p(b["sh27"]), p(b["moments"]), p(b["valid"]), C.byref(d.vis), p(b["q6"]), n, p(b["e3"]), p(b["corners"]))
+            return w.lib.mcpt_volume_irradiance_visible_device(*a, st) if dv else w.lib.mcpt_volume_irradiance_visible(*a)
+        a = (w.h, C.byref(d.grid), p(b["sh27"]), p(b["valid"]), p(b["q6"]), n, p(b["e3"]), p(b["corners"]))
+        return w.lib.mcpt_volume_irradiance_device(*a, st) if dv else w.lib.mcpt_volume_irradiance(*a)
+    return Case("volume_lookup_visible" if visible else "volume_lookup", b, call)
+
+
+def lightmap_lookup_case(w, n):
+    d = baked(w)
+    uv = np.ascontiguousarray(np.random.default_rng(5).random((n, 2)))
+    b = dict(irradiance3=In(d.E), owner=In(d.owner), uv2=In(uv), e3=Out((n, 3), F64), taps=Out((n,), I32))
+
+    def call(dv, p, st):
+        a = (w.h, QF.MAP, QF.MAP, p(b["irradiance3"]), p(b["owner"]), p(b["uv2"]), n, p(b["e3"]), p(b["taps"]))
+        return w.lib.mcpt_lightmap_irradiance_device(*a, st) if dv else w.lib.mcpt_lightmap_irradiance(*a)
+    return Case("lightmap_lookup", b, call)
+
+
+def source_bufs(w, kind):
+    d = baked(w)
+    if kind == "volume":
+        return dict(src_sh27=In(d.sh), src_valid=In(d.valid), src_moments=In(d.moments))
+    return dict(src_uv6=In(w.geom[:, 18:24]), src_irradiance3=In(d.E), src_owner=In(d.owner))
+
+
+def source_struct(w, kind, b, p):
+    """the mcpt_baked_source of a form's own pointers"""
+    d, m = baked(w), w.mcpt
+    s = m.BakedSource()
+    if kind == "volume":
+        s.kind = m.BAKED_VOLUME
+        s.grid, s.visibility = C.pointer(d.grid), C.pointer(d.vis)
+        s.sh27, s.valid, s.moments = p.addr(b["src_sh27"]), p.addr(b["src_valid"]), p.addr(b["src_moments"])
+    else:
+        s.kind = m.BAKED_LIGHTMAP
+        s.uv6, s.irradiance3, s.owner = p.addr(b["src_uv6"]), p.addr(b["src_irradiance3"]), p.addr(b["src_owner"])
+        s.height, s.width = d.E.shape[:2]
+    return s
+
+
+def specular_bufs(w):
+    d = baked(w)
+    return dict(spec_chain=In(d.chain), spec_valid=In(d.valid), spec_moments=In(d.moments))
+
+
+def specular_struct(w, b, p):
+    d = baked(w)
+    s = w.mcpt.BakedSpecular()
+    s.grid, s.chain, s.visibility = C.pointer(d.grid), C.pointer(d.chain_desc), C.pointer(d.vis)
+    s.chain_data, s.valid, s.moments = p.addr(b["spec_chain"]), p.addr(b["spec_valid"]), p.addr(b["spec_moments"])
+    return s
+
+
+BAKED_OUT = (("radiance", 3, F64), ("kind", 0, I32), ("face", 0, I32), ("q6", 6, F64), ("uv", 2, F64), ("kd", 3, F64), ("e", 3, F64), ("lit", 0, I32))
+SPEC_OUT = (("spec3", 3, F64), ("ks3", 3, F64), ("r3", 3, F64), ("ns", 0, F64), ("slit", 0, I32))
+
+
+def baked_radiance_case(w, n, kind, specular=False):
+    b = dict(rays6=In(take(w.q["rays"], n)), **source_bufs(w, kind))
+    b.update({k: Out((n, c) if c else (n,), t) for k, c, t in BAKED_OUT})
+    if specular:
+        b.update(specular_bufs(w))
+        b.update({k: Out((n, c) if c else (n,), t) for k, c, t in SPEC_OUT})
+
+    def call(dv, p, st):
+        s = source_struct(w, kind, b, p)
+        o = w.mcpt.BakedOutputs(*[p.addr(b[k]) for k, _, _ in BAKED_OUT])
+        tail = (None, st) if dv else (None,)
+        if specular:
+            sp = specular_struct(w, b, p)
+            so = w.mcpt.BakedSpecularOutputs(*[p.addr(b[k]) for k, _, _ in SPEC_OUT])
+            f = w.lib.mcpt_baked_radiance_specular_device if dv else w.lib.mcpt_baked_radiance_specular
+            return f(w.h, C.byref(s), C.byref(sp), p(b["rays6"]), n, 1, C.byref(o), C.byref(so), *tail)
+        f = w.lib.mcpt_baked_radiance_device if dv else w.lib.mcpt_baked_radiance
+        return f(w.h, C.byref(s), p(b["rays6"]), n, 1, C.byref(o), *tail)
+    return Case("baked_specular" if specular else "baked-" + kind, b, call)
+
+
+def list_case(w, call, n):
+    if call == "radiance":
+        return radiance_case(w, n)
+    if call == "adaptive":
+        return radiance_case(w, n, adaptive=True)
+    if call == "reflection_bake":
+        return reflection_bake_case(w, take(w.q["refl_probes"], n), np.arange(n, dtype=np.int32) * (QF.REFL_RES ** 2 * SPP))
+    if call == "reflection_prefilter":
+        return prefilter_case(w, w.mcpt.reflection_chain(QF.REFL_RES, [(4, 64), (2, 4)]), np.random.default_rng(12).random((n, QF.REFL_RES ** 2, 3)))
+    if call in ("baked-volume", "baked-lightmap"):
+        return baked_radiance_case(w, n, call[6:])
+    if call == "baked_specular":
+        return baked_radiance_case(w, n, "volume", specular=True)
+    if call in ("volume_lookup", "volume_lookup_visible"):
+        return volume_lookup_case(w, n, call.endswith("visible"))
+    return {"sh": sh_case, "visibility": visibility_case, "occlusion": occlusion_case, "trace_closest": trace_case,
+            "reflection_lookup": reflection_lookup_case, "reflection_volume": reflection_volume_case, "lightmap_lookup": lightmap_lookup_case}[call](w, n)
+
+
+LIST_CALLS = ("trace_closest", "radiance", "adaptive", "sh", "visibility", "occlusion", "reflection_bake", "reflection_prefilter", "reflection_lookup",
+              "reflection_volume", "volume_lookup", "volume_lookup_visible", "lightmap_lookup", "baked-volume", "baked-lightmap", "baked_specular")
+
+
+# n: 1, 65 and B + 1 = 257 with B = 256, the block size of every kernel of these calls (the docstring's table names each constant); all four
+# (fill, skew) pairs at 257, fill 0xFF unskewed below
+@pytest.mark.parametrize("n", SIZES)
+@pytest.mark.parametrize("call", LIST_CALLS)
+def test_list(w, call, n):
+    want = hold(w, list_case(w, call, n), ALL if n == B + 1 else ONE)
+    if n == B + 1:
+        assert any(np.abs(np.nan_to_num(a.astype(np.float64))).max() > 0 for a in want.values()), "the case answers nothing but zeros"
+
+
+# The radiance, SH and adaptive queries take no workspace_rays: their chunks are what the device's path-state budget holds (render.cpp,
+# render_wavefront: (budget - 64 KiB) / (wf_bytes_per_path(nl) + 25) samples, whole queries).  On a device created under
+# MCPT_WORKSPACE_GB=0.011 that is 35 701 samples with one shadow plane (304 + 25 bytes a sample) and 25 259 with two (440 + 25): at 301
+# samples a query, 118 or 83 queries a chunk, so 257 queries are 118 + 118 + 21 or 83 + 83 + 83 + 8.
+CHUNKED_SPP = 301
+
+
+def tight(w):
+    """a second device of the scene whose frame slot holds a few ten thousand paths"""
+    if "tight" not in w.cache:
+        saved = os.environ.get("MCPT_WORKSPACE_GB")
+        os.environ["MCPT_WORKSPACE_GB"] = "0.011"
+        try:
+            w.cache["tight"] = w.mcpt.Device(w.sc, 0)
+        finally:
+            if saved is None:
+                del os.environ["MCPT_WORKSPACE_GB"]
+            else:
+                os.environ["MCPT_WORKSPACE_GB"] = saved
+    return w.cache["tight"]._h
+
+
+@pytest.mark.parametrize("call", ["radiance", "adaptive", "sh"])
+def test_list_in_chunks(w, call):
+    n = B + 1
+    if call == "sh":
+        case = sh_case(w, n, tight(w), CHUNKED_SPP)
+    else:
+        case = radiance_case(w, n, call == "adaptive", tight(w), CHUNKED_SPP)
+    want = hold(w, case, ALL)
+    assert any(np.abs(a.astype(np.float64)).max() > 0 for a in want.values())
+
+
+# ---- maps: 33 x 17 (neither a multiple of a block nor of a row of one) at dilate 0 and 2, and 1 x 1; the scene's chart and a guarded one
+
+MAPS = ((33, 17, 0), (33, 17, 2), (1, 1, 0))
+
+
+@pytest.mark.parametrize("chart", [False, True], ids=["own", "guarded"])
+@pytest.mark.parametrize("width, height, dilate", MAPS, ids=["33x17-d0", "33x17-d2", "1x1"])
+@pytest.mark.parametrize("kind", ["lightmap", "adaptive", "occlusion", "denoise"])
+def test_map(w, kind, width, height, dilate, chart):
+    E = err = None
+    if kind == "denoise":
+        src = host(w, lightmap_case(w, "lightmap", width, height, 0, chart))
+        E, err = src["irradiance3"], src["stderr3"]
+    want = hold(w, lightmap_case(w, kind, width, height, dilate, chart, E, err), ALL)
+    if width > 1:
+        # covered texels everywhere; the scene's own chart covers the whole map, the shrunk one leaves a border no face covers
+        assert (want["owner"] >= 0).any() and (want["owner"] < 0).any() == chart
+
+
+# ---- grids: query_family's 3 x 2 x 2 and the smallest a call accepts, one probe
+
+@pytest.mark.parametrize("counts", [QF.COUNTS, (1, 1, 1)], ids=["3x2x2", "1x1x1"])
+@pytest.mark.parametrize("kind", ["volume", "visibility"])
+def test_grid(w, kind, counts):
+    g0 = w.q["grid"]
+    g = w.mcpt.volume_grid(tuple(g0.origin), tuple(g0.spacing), counts)
+    want = hold(w, (bake_volume_case if kind == "volume" else bake_visibility_case)(w, g), ALL)
+    assert want["hits"].max() > 0
+
+
+# ---- frames
+
+def not_owned(width, height, rank, world, tile_w, tile_h, channels):
+    """mcpt.h, mcpt_render_params: tile (tx, ty) belongs to rank (tx + shift * ty) mod world, shift the first integer >= world / 2 coprime
+    with world; tile_w / tile_h <= 0: 32 x 8.  True where the pixel is another rank's."""
+    tw, th = (tile_w, tile_h) if tile_w > 0 and tile_h > 0 else (32, 8)
+    shift = next(s for s in range((world + 1) // 2, 2 * world + 2) if np.gcd(s, world) == 1) if world > 1 else 0
+    ty, tx = np.divmod(np.arange(height), th)[0][:, None], np.divmod(np.arange(width), tw)[0][None, :]
+    other = (tx + shift * ty) % max(world, 1) != rank
+    return np.ascontiguousarray(np.broadcast_to(other[:, :, None], (height, width, channels))) if channels else other
+
+
+def render_case(w, size, rank, tile):
+    sc, dev = small(w, size)
+    W, H = size
+    world = 2
+    rp = w.mcpt.RenderParams(SPP, QF.SEED, rank, world, tile[0], tile[1], 0)
+    b = dict(img=Out((H, W, 3), F64, keep=not_owned(W, H, rank, world, tile[0], tile[1], 3)))
+
+    def call(dv, p, st):
+        return w.lib.mcpt_render_device(dev._h, C.byref(rp), p(b["img"]), None, st) if dv else w.lib.mcpt_render(dev._h, C.byref(rp), p(b["img"]), None)
+    return Case("render %dx%d rank %d of 2, tiles %s" % (W, H, rank, tile), b, call)
+
+
+@pytest.mark.parametrize("tile", [(0, 0), (5, 3)], ids=["tiles32x8", "tiles5x3"])
+@pytest.mark.parametrize("rank", [0, 1])
+@pytest.mark.parametrize("size", SMALL, ids=["33x17", "1x1"])
+def test_frame_render(w, size, rank, tile):
+    case = render_case(w, size, rank, tile)
+    want = hold(w, case, ALL)
+    keep = case.bufs["img"].keep
+    if size == (1, 1):
+        assert keep.all() == (rank == 1)                    # (the one pixel is rank 0's: rank 1 writes nothing at all)
+    else:
+        assert keep.any() and not keep.all() and np.nan_to_num(want["img"][~keep]).max() > 0
+
+
+def baked_frame_case(w, size, specular):
+    sc, dev = small(w, size)
+    W, H = size
+    fp = w.mcpt.BakedFrameParams(3, 1, QF.SEED, CHUNK * 3, (C.c_int32 * 2)(0, 0))
+    b = dict(img=Out((H, W, 3), F64), counts3=Out((H, W, 3), I32), lit=Out((H, W), I32), slit=Out((H, W), I32) if specular else None,
+             **source_bufs(w, "volume"))
+    if specular:
+        b.update(specular_bufs(w))
+
+    def call(dv, p, st):
+        s = source_struct(w, "volume", b, p)
+        outs = (p(b["img"]), p(b["counts3"]), p(b["lit"]))
+        tail = (None, st) if dv else (None,)
+        if specular:
+            sp = specular_struct(w, b, p)
+            f = w.lib.mcpt_render_baked_specular_device if dv else w.lib.mcpt_render_baked_specular
+            return f(dev._h, C.byref(s), C.byref(sp), C.byref(fp), *outs, p(b["slit"]), *tail)
+        f = w.lib.mcpt_render_baked_device if dv else w.lib.mcpt_render_baked
+        return f(dev._h, C.byref(s), C.byref(fp), *outs, *tail)
+    return Case("render_baked%s %dx%d" % ("_specular" if specular else "", W, H), b, call)
+
+
+@pytest.mark.parametrize("size", SMALL, ids=["33x17", "1x1"])
+@pytest.mark.parametrize("specular", [False, True], ids=["baked", "baked_specular"])
+def test_frame_baked(w, specular, size):
+    want = hold(w, baked_frame_case(w, size, specular), ALL)
+    assert (want["counts3"].sum(axis=2) == 3).all()
+
+
+@pytest.fixture(scope="module")
+def handles(w):
+    """a progressive handle per small device after 3 of 5 samples: rank 1 of 2 on the 33 x 17 one, the whole frame on the 1 x 1 one"""
+    made = {}
+    for size in SMALL:
+        sc, dev = small(w, size)
+        part = (1, 2, 8, 4) if size != (1, 1) else (0, 1, 0, 0)
+        rp = w.mcpt.RenderParams(5, QF.SEED, part[0], part[1], part[2], part[3], 0)
+        h = C.c_void_p()
+        check(w.lib.mcpt_progressive_create(dev._h, C.byref(rp), C.byref(h)))
+        check(w.lib.mcpt_progressive_step(h, 3, None))
+        made[size] = (h, part)
+    yield made
+    for h, _ in made.values():
+        w.lib.mcpt_progressive_free(h)
+
+
+def progressive_case(w, handles, size, what):
+    h, (rank, world, tw, th) = handles[size]
+    W, H = size
+    L = w.lib
+    if what == "image":
+        keep = not_owned(W, H, rank, world, tw, th, 3)
+        b = dict(img=Out((H, W, 3), F64, keep), stderr=Out((H, W, 3), F64, keep))
+        call = lambda dv, p, st: (L.mcpt_progressive_image_device(h, p(b["img"]), p(b["stderr"]), st) if dv else
+                                  L.mcpt_progressive_image(h, p(b["img"]), p(b["stderr"])))
+    elif what == "denoise":
+        b = dict(img=Out((H, W, 3), F64, not_owned(W, H, rank, world, tw, th, 3)))
+        call = lambda dv, p, st: L.mcpt_progressive_denoise_device(h, None, p(b["img"]), st) if dv else L.mcpt_progressive_denoise(h, None, p(b["img"]))
+    elif what == "guided":
+        b = dict(img=Out((H, W, 3), F64, not_owned(W, H, rank, world, tw, th, 3)))
+        call = lambda dv, p, st: (L.mcpt_progressive_denoise_guided_device(h, None, None, p(b["img"]), st) if dv else
+                                  L.mcpt_progressive_denoise_guided(h, None, None, p(b["img"])))
+    else:
+        ch = 4 if what == "display-rgba" else 3
+        dp = w.mcpt.make_display(auto_key=0.18, curve="reinhard", transfer="srgb", rgba=ch == 4)
+        b = dict(rgb8=Out((H, W, ch), U8, not_owned(W, H, rank, world, tw, th, ch)))
+        call = lambda dv, p, st: (L.mcpt_progressive_display_device(h, 0, C.byref(dp), p(b["rgb8"]), None, st) if dv else
+                                  L.mcpt_progressive_display(h, 0, C.byref(dp), p(b["rgb8"]), None))
+    return Case("progressive %s %dx%d" % (what, W, H), b, call)
+
+
+@pytest.mark.parametrize("size", SMALL, ids=["33x17", "1x1"])
+@pytest.mark.parametrize("what", ["image", "denoise", "guided", "display-rgb", "display-rgba"])
+def test_frame_progressive(w, handles, what, size):
+    case = progressive_case(w, handles, size, what)
+    want = hold(w, case, ALL)
+    if size != (1, 1):
+        for k, b in case.bufs.items():
+            assert b.keep.any() and not b.keep.all() and np.nan_to_num(want[k][~b.keep].astype(np.float64)).max() > 0, k
+
+
+# ---- the display transform: 1, 5 and 1023 pixels (four pixels per lane: a tail of 1, of 1 after a full lane, of 3 after 255 lanes)
+
+@pytest.mark.parametrize("n", [1, 5, 1023])
+@pytest.mark.parametrize("rgba", [False, True], ids=["rgb", "rgba"])
+def test_display(w, rgba, n):
+    img = np.ascontiguousarray(np.random.default_rng(3).random((n, 3)) * 2.0)
+    dp = w.mcpt.make_display(auto_key=0.18, curve="reinhard", transfer="srgb", rgba=rgba)
+    b = dict(img=In(img), out=Out((n, 4 if rgba else 3), U8))
+
+    def call(dv, p, st):
+        a = (w.h, p(b["img"]), n, C.byref(dp), p(b["out"]), None)
+        return w.lib.mcpt_display_device(*a, st) if dv else w.lib.mcpt_display(*a)
+    want = hold(w, Case("display %d %s" % (n, "rgba" if rgba else "rgb"), b, call), ALL)
+    assert not rgba or (want["out"][:, 3] == 255).all()
+    # the histogram alone reads d_img and writes the host's slots: the same counts as the host form, the input and its bands intact
+    slots = np.zeros(387, np.int64)
+    check(w.lib.mcpt_display_histogram(w.h, _p(img, C.c_double), n, _p(slots, C.c_int64)))
+    assert slots.sum() == n
+    for fill, skewed in ALL:
+        g = Guarded(img, F64, fill, 8 if skewed else 0)
+        try:
+            got = np.zeros(387, np.int64)
+            check(w.lib.mcpt_display_histogram_device(w.h, g.ptr, n, _p(got, C.c_int64), w.stream.h))
+            w.stream.synchronize()
+            assert np.array_equal(got, slots), (fill, skewed)
+            g.check("display_histogram: img")
+        finally:
+            g.free()
+
+
+# ---- the calls that only read: a geometry update in each mode and a motion, from a guarded d_v
+
+def moved(w):
+    v = np.ascontiguousarray(w.geom[:, :9]).copy()
+    v += 0.02 * np.sin(np.arange(v.size, dtype=np.float64)).reshape(v.shape)
+    return v
+
+
+@pytest.mark.parametrize("what", ["refit", "rebuild", "motion"])
+def test_update(w, what):
+    m, L = w.mcpt, w.lib
+    v = moved(w)
+    rp = m.RenderParams(SPP, QF.SEED, 0, 1, 0, 0, 0)
+    sh = m.Shutter(0.0, 1.0, 3, 0)
+    size = (33, 17)
+
+    def frame(apply):
+        sc = m.Scene(SCENES, "cornell-box", width=size[0], height=size[1])
+        dev = m.Device(sc, 0)
+        try:
+            apply(dev)
+            img = np.zeros((size[1], size[0], 3))
+            check(L.mcpt_render(dev._h, C.byref(rp), _p(img, C.c_double), None))
+            return img
+        finally:
+            dev.close()
+            sc.close()
+
+    def host_form(dev):
+        if what == "motion":
+            check(L.mcpt_device_set_motion(dev._h, _p(v, C.c_double), None, C.byref(sh)))
+        else:
+            check(L.mcpt_device_update_vertices(dev._h, _p(v, C.c_double), what == "rebuild", None))
+    want = frame(host_form)
+    still = frame(lambda dev: None)
+    assert not np.array_equal(QF.bits(want), QF.bits(still))                    # (the update is seen in the frame)
+    for fill, skewed in ALL:
+        g = Guarded(v, F64, fill, 8 if skewed else 0)
+
+        def device_form(dev):
+            if what == "motion":
+                check(L.mcpt_device_set_motion_device(dev._h, g.ptr, None, C.byref(sh), w.stream.h))
+            else:
+                check(L.mcpt_device_update_vertices_device(dev._h, g.ptr, what == "rebuild", None, w.stream.h))
+        try:
+            got = frame(device_form)
+            w.stream.synchronize()
+            g.check("%s: d_v" % what)
+        finally:
+            g.free()
+        assert np.array_equal(QF.bits(got), QF.bits(want)), (what, fill, skewed)
+
+
+# ---- a group of one device: the frame stays in a buffer of the handle's own (*d_img is returned, not taken), so there is nothing of the
+# caller's to guard; it is held to the host form
+
+def test_multi_frame(w):
+    m, L = w.mcpt, w.lib
+    from hip_rt import check as hip_check, hip
+    ordinals = np.zeros(1, np.int32)
+    h = C.c_void_p()
+    check(L.mcpt_multi_create(w.sc._h, _p(ordinals, C.c_int32), 1, m.BUILD_HOST, m.GATHER_PEER, C.byref(h)))
+    try:
+        rp = m.RenderParams(SPP, QF.SEED, 0, 1, 0, 0, 0)
+        want = np.zeros((QF.H, QF.W, 3))
+        check(L.mcpt_multi_render(h, C.byref(rp), _p(want, C.c_double), None))
+        d_img = C.c_void_p()
+        check(L.mcpt_multi_render_device(h, C.byref(rp), C.byref(d_img), None))
+        got = np.full((QF.H, QF.W, 3), np.nan)
+        hip_check(hip().hipMemcpy(got.ctypes.data_as(C.c_void_p), d_img, got.nbytes, 2))
+        assert d_img.value and np.array_equal(QF.bits(got), QF.bits(want)) and want.max() > 0
+    finally:
+        L.mcpt_multi_free(h)
+
+
+# ---- the check has power: one byte in a band, one word in an input
+
+def test_a_damaged_band_and_a_modified_input_are_found(w):
+    from hip_rt import check as hip_check, hip
+    a = np.arange(12, dtype=np.float64)
+    one = np.array([0x5A], np.uint8)
+
+    def poke(g, at, src):
+        hip_check(hip().hipMemcpy(C.c_void_p(g.ptr + at), src.ctypes.data_as(C.c_void_p), src.nbytes, 1))
+    for fill in FILLS:
+        for at, side in ((-8, "front"), (a.nbytes + 3, "back")):
+            g = Guarded(a, F64, fill, skew=8)
+            try:
+                g.check("intact")
+                poke(g, at, one)
+                with pytest.raises(AssertionError, match=r"q6: %s band damaged at byte %s of the payload .*holds 0x5A" % (side, "%+d" % at if at < 0 else r"\+%d" % at)):
+                    g.check("q6")
+            finally:
+                g.free()
+        g = Guarded(a, F64, fill)
+        try:
+            poke(g, 16, np.array([2.0000000000000004]))
+            with pytest.raises(AssertionError, match=r"q6: input payload modified at byte \+16 of 96"):
+                g.check("q6")
+            assert g.payload()[2] != a[2]
+        finally:
+            g.free()
+    assert G == 65536
