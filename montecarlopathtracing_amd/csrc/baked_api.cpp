@@ -1,6 +1,6 @@
 // C ABI, baked frames (include/mcpt.h: mcpt_lightmap_irradiance*, mcpt_baked_radiance*, mcpt_render_baked*): the lightmap's lookup by chart
 // coordinate, and camera or caller's rays shaded from a bake.  A call writes or takes the rays of a chunk, answers them with the unchanged
-// closest-hit launch (kernels.hip: launch_trace_closest_leaf -- mcpt_trace_closest_device's walks, handing back the leaf), shades the hits
+// closest-hit launch (hit_work.hpp: trace_leaf -- mcpt_trace_closest_device's walks, handing back the leaf), shades the hits
 // under the source (baked.hip) and, a frame, folds every pixel's samples.  The workspace is the device's own (mcpt_device::Baked).  The
 // lookup's arithmetic is baked.hpp's, compiled here for the host form.
 #include <hip/hip_runtime_api.h>
@@ -133,13 +133,8 @@ static int baked_workspace(mcpt_device* d, int64_t rays, bool own_rays, bool sam
 {
     if (const int rc = lease(d->baked, st, l)) return rc;
     mcpt_device::Baked& w = *d->baked;
-    if (rays > (int64_t(1) << 40)) return fail(MCPT_ERR_NOMEM, "the baked workspace of " + std::to_string(rays) + " rays cannot be allocated");
+    if (const int rc = hit_work_grow(w, rays, int64_t(1) << 40, "baked", own_rays)) return rc;
     const size_t sr = size_t(rays);
-    if (own_rays)
-        if (const int rc = grow(w.rays6, sr * 6, "the baked rays")) return rc;
-    if (const int rc = grow(w.t, sr, "the baked rays' distances")) return rc;
-    if (const int rc = grow(w.p, sr * 3, "the baked rays' hit points")) return rc;
-    if (const int rc = grow(w.leaf, sr, "the baked rays' hits")) return rc;
     if (samples) {
         if (const int rc = grow(w.rad, sr * 3, "the baked samples' radiance")) return rc;
         if (const int rc = grow(w.kind, sr, "the baked samples' kinds")) return rc;
@@ -148,13 +143,6 @@ static int baked_workspace(mcpt_device* d, int64_t rays, bool own_rays, bool sam
     if (spec)
         if (const int rc = grow(w.slit, sr, "the baked samples' specular lookups")) return rc;
     return MCPT_OK;
-}
-
-static inline void trace_chunk(mcpt_device* d, const double* d_rays6, int64_t n, hipStream_t st)
-{
-    mcpt_device::Baked& w = *d->baked;
-    launch_trace_closest_leaf(d->ds, d->trace_mode == MCPT_TRACE_FAST, d_rays6, n, w.leaf.get(), w.t.get(), w.p.get(), d->aux_ctr.get(), d->aux_queue.get(),
-                              d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
 }
 
 // the specular outputs of rays first .. of a call
@@ -199,25 +187,15 @@ int baked_radiance_device(mcpt_device* d, const mcpt_baked_source& s, const doub
     if (const int rc = baked_workspace(d, per_chunk, false, false, false, st, l)) return rc;
     mcpt_device::Baked& w = *d->baked;
     const BakedSource B = device_source(s);
-    int chunks = 0;
-    int rc = MCPT_OK;
-    for (int64_t first = 0; first < n && rc == MCPT_OK; first += per_chunk, chunks++) {
-        const int64_t count = chunk_count(per_chunk, n, first);
+    return chunk_run(n, per_chunk, 1, l, stats, st, [&](int64_t first, int64_t count) {
         const double* rays = d_rays6 + first * 6;
-        trace_chunk(d, rays, count, st);
+        trace_leaf(d, rays, count, w.leaf.get(), w.t.get(), w.p.get(), st);
         const BakedOut at = outputs_at(o, first);
         launch_baked_shade(d->ds, B, flags, rays, w.leaf.get(), w.t.get(), w.p.get(), count, at, st);
         if (spec)
             launch_baked_specular(d->ds, spec->V, flags, rays, w.leaf.get(), w.t.get(), w.p.get(), count, at.radiance3, spec_outputs_at(spec->rays, first), st);
-        rc = launch_result();
-    }
-    if ((rc = l.end(rc)) != MCPT_OK) return rc;
-    if (stats) {
-        HIP_TRY(hipStreamSynchronize(st));
-        stats->rays_primary = stats->samples = uint64_t(n);
-        stats->launches = chunks;
-    }
-    return MCPT_OK;
+        return launch_result();
+    });
 }
 
 // A baked frame on st, after the refusals and the gate; device pointers throughout.  spec (may be null): the specular pass between every
@@ -239,15 +217,13 @@ int baked_frame_device(mcpt_device* d, const mcpt_baked_source& s, const mcpt_ba
     mcpt_device::Baked& w = *d->baked;
     const BakedSource B = device_source(s);
     const DLens lens = lens_for(d, d->lens);
-    int chunks = 0;
-    int rc = MCPT_OK;
-    for (int64_t first = 0; first < pixels && rc == MCPT_OK; first += per_chunk, chunks++) {
+    return chunk_run(pixels, per_chunk, G, l, stats, st, [&](int64_t first, int64_t count) {
         BakedChunk c{};
-        c.first = int(first); c.n = int(chunk_count(per_chunk, pixels, first)); c.G = G;
+        c.first = int(first); c.n = int(count); c.G = G;
         c.rays6 = w.rays6.get(); c.leaf = w.leaf.get(); c.t = w.t.get(); c.p = w.p.get();
         const long long rays = (long long)c.n * G;
         launch_baked_camera_rays(lens, fp.seed, c, w.rays6.get(), st);
-        trace_chunk(d, c.rays6, rays, st);
+        trace_leaf(d, c.rays6, rays, w.leaf.get(), w.t.get(), w.p.get(), st);
         BakedOut o{};
         o.radiance3 = w.rad.get(); o.kind = w.kind.get(); o.lit = w.lit.get();
         launch_baked_shade(d->ds, B, flags, c.rays6, c.leaf, c.t, c.p, rays, o, st);
@@ -258,15 +234,8 @@ int baked_frame_device(mcpt_device* d, const mcpt_baked_source& s, const mcpt_ba
             if (spec->pixel_slit) launch_baked_specular_count(c, w.slit.get(), spec->pixel_slit, st);
         }
         launch_baked_fold(c, w.rad.get(), w.kind.get(), w.lit.get(), d_img, d_counts3, d_lit, st);
-        rc = launch_result();
-    }
-    if ((rc = l.end(rc)) != MCPT_OK) return rc;
-    if (stats) {
-        HIP_TRY(hipStreamSynchronize(st));
-        stats->rays_primary = stats->samples = uint64_t(pixels) * uint64_t(G);
-        stats->launches = chunks;
-    }
-    return MCPT_OK;
+        return launch_result();
+    });
 }
 
 extern "C" {

@@ -27,4 +27,15 @@ inline int64_t chunk_count(int64_t per_chunk, int64_t n, int64_t first)
     return n - first < per_chunk ? n - first : per_chunk;
 }
 
+// The callers' loop: body(first, count) for every chunk of a list of n items in order, until the list is done or body returns non-zero,
+// which is returned (else 0).  chunks = the calls of body.  first < n <= 2^62 before every step, so first + per_chunk does not overflow.
+template <class Body>
+int chunk_walk(int64_t n, int64_t per_chunk, int& chunks, Body body)
+{
+    int rc = 0;
+    chunks = 0;
+    for (int64_t first = 0; first < n && rc == 0; first += per_chunk, chunks++) rc = body(first, chunk_count(per_chunk, n, first));
+    return rc;
+}
+
 }  // namespace mcpt

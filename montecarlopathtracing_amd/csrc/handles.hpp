@@ -20,6 +20,8 @@
 //   render_scene.cpp  output writers, checkpoints, render_scene
 //   staging.cpp       what the query family's files share (staging.hpp): the device gate, the allocation mapping, a host-pointer call's
 //                     device copies, the lease of a per-device workspace; chunks.hpp: how a workspace budget cuts a list into chunks
+//   hit_work.cpp      what the closest-hit chunk loops share (hit_work.hpp): the workspace of a chunk's rays and hits, the closest-hit
+//                     launch, the loop and its statistics (visibility, occlusion, baked radiance and frames)
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -34,6 +36,7 @@
 #include "accel_build.hpp"
 #include "adaptive_query.hpp"
 #include "hip_owned.hpp"
+#include "hit_work.hpp"
 #include "kernels.hpp"
 #include "knobs.hpp"
 #include "scene.hpp"
@@ -240,18 +243,17 @@ struct mcpt_device {
     };
     std::unique_ptr<Volume> vol;
     // probe visibility (visibility_api.cpp): the rays of a chunk of probes and their closest hits, made by the first bake and grown to the
-    // largest chunk so far, 84 bytes per ray; an occlusion query (occlusion_api.cpp) draws its rays into the same workspace under the same lease
-    struct Visibility {
-        mcpt::DevBuf<double> rays6, t, p;               // [rays][6], [rays], [rays][3]
-        mcpt::DevBuf<int32_t> leaf;                     // [rays]
+    // largest chunk so far (hit_work.hpp), 84 bytes per ray; an occlusion query (occlusion_api.cpp) draws its rays into the same workspace
+    // under the same lease
+    struct Visibility : HitWork {
         mcpt::Event done;
     };
     std::unique_ptr<Visibility> vis;
-    // baked frames (baked_api.cpp): the rays of a chunk, their closest hits and the chunk's shaded samples, made by the first call and grown
-    // to the largest chunk so far, 116 bytes per ray
-    struct Baked {
-        mcpt::DevBuf<double> rays6, t, p, rad;          // [rays][6], [rays], [rays][3], [rays][3]
-        mcpt::DevBuf<int32_t> leaf, kind, lit;          // [rays]
+    // baked frames (baked_api.cpp): the rays of a chunk and their closest hits (hit_work.hpp) and the chunk's shaded samples, made by the
+    // first call and grown to the largest chunk so far, 116 bytes per ray
+    struct Baked : HitWork {
+        mcpt::DevBuf<double> rad;                       // [rays][3]
+        mcpt::DevBuf<int32_t> kind, lit;                // [rays]
         mcpt::DevBuf<int32_t> slit;                     // [rays] a specular frame's lookups: 4 bytes per ray more, grown by those calls alone
         mcpt::Event done;
     };
@@ -391,6 +393,19 @@ int lightmap_chart_check(const double* uv6, int64_t num_faces);     // MCPT_ERR_
 int lightmap_device_gate(mcpt_device* d);
 // the baker's workspace of a W x H map on d (d->lm) for a call on st, once the bake or denoise before this one has left it
 int lightmap_ensure_work(mcpt_device* d, int W, int H, mcpt::LightmapWork& w, hipStream_t st, Lease& l);
+// step 1 on st and the number of covered texels, which the host waits for: 4 bytes back
+int lightmap_raster_device(mcpt_device* d, const double* d_uv6, int W, int H, const mcpt::LightmapWork& w, hipStream_t st, int32_t& covered);
+// Rounds 1 .. R of the dilation of a W x H map of `channels` doubles a texel on st: round r reads frame[at] and own[(r - 1) & 1] and writes
+// the other frame and own[r & 1].  at: the frame round 1 reads, then the one round R wrote.
+void lightmap_dilate_rounds(double* const frame[2], int32_t* const own[2], int W, int H, int R, int channels, int& at, hipStream_t st);
+// A map the caller clears before the texel list is answered into it, and its size; a null map is skipped.
+struct MapClear { void* map; size_t bytes; };
+// The spine every map bake shares, after its refusals, on st: the gate, the baker's workspace, the raster and the covered count, the clear
+// of d_map (channels doubles a texel) and of clears[0 .. n_clears), the covered texels' list, answer(texels, q6, covered, frame_at) -- which
+// answers the list (stats are its to fill) and scatters into frame_at --, `dilate` rounds and the owner map (d_owner may be null).
+using MapAnswer = std::function<int(const int32_t* texels, const double* q6, int32_t covered, double* frame_at)>;
+int map_bake(mcpt_device* d, const double* d_uv6, int W, int H, int dilate, int channels, double* d_map, const MapClear* clears, int n_clears,
+             int32_t* d_owner, mcpt_stats* stats, hipStream_t st, const MapAnswer& answer);
 
 // ---- adaptive_query_api.cpp
 // what the adaptive calls refuse of their adaptive parameters (MCPT_ERR_ARG)

@@ -194,17 +194,21 @@ __global__ void __launch_bounds__(kLmBlock) k_lm_scatter(const int32_t* __restri
 
 // ---- step 5, one round: a texel that is not valid (owner -1) takes the mean of its valid neighbours of the round before, summed in
 // row-major order, and becomes valid with owner -1 - round; every other texel is copied.  Input and output are different buffers.
+// CH channels a texel: 3 (irradiance) or 1 (an occlusion map).
+template <int CH>
 __global__ void __launch_bounds__(kLmBlock) k_lm_dilate(const double* __restrict__ irr_in, const int32_t* __restrict__ owner_in, int W, int H, int round,
                                                         double* __restrict__ irr_out, int32_t* __restrict__ owner_out)
 {
     const int i = blockIdx.x * kLmBlock + threadIdx.x;
     if (i >= W * H) return;
     const int o = owner_in[i];
-    double s[3] = {irr_in[(size_t)i * 3], irr_in[(size_t)i * 3 + 1], irr_in[(size_t)i * 3 + 2]};
+    double s[CH];
+    for (int ch = 0; ch < CH; ch++) s[ch] = irr_in[(size_t)i * CH + ch];
     int out = o;
     if (o == -1) {
         const int x = i % W, y = i / W;
-        double a[3] = {0.0, 0.0, 0.0};
+        double a[CH];
+        for (int ch = 0; ch < CH; ch++) a[ch] = 0.0;
         int c = 0;
         for (int dy = -1; dy <= 1; dy++) {
             for (int dx = -1; dx <= 1; dx++) {
@@ -212,16 +216,16 @@ __global__ void __launch_bounds__(kLmBlock) k_lm_dilate(const double* __restrict
                 if (xx < 0 || xx >= W || yy < 0 || yy >= H) continue;
                 const size_t j = (size_t)yy * W + xx;
                 if (owner_in[j] == -1) continue;                // (the texel itself among them)
-                for (int ch = 0; ch < 3; ch++) a[ch] += irr_in[j * 3 + ch];
+                for (int ch = 0; ch < CH; ch++) a[ch] += irr_in[j * CH + ch];
                 c++;
             }
         }
         if (c > 0) {
-            for (int ch = 0; ch < 3; ch++) s[ch] = a[ch] / double(c);
+            for (int ch = 0; ch < CH; ch++) s[ch] = a[ch] / double(c);
             out = -1 - round;
         }
     }
-    for (int ch = 0; ch < 3; ch++) irr_out[(size_t)i * 3 + ch] = s[ch];
+    for (int ch = 0; ch < CH; ch++) irr_out[(size_t)i * CH + ch] = s[ch];
     owner_out[i] = out;
 }
 
@@ -255,11 +259,14 @@ void launch_lightmap_scatter(const int32_t* d_texels, long long n_list, const do
                        d_hits);
 }
 
-void launch_lightmap_dilate(const double* d_irr_in, const int32_t* d_owner_in, int W, int H, int round, double* d_irr_out, int32_t* d_owner_out,
+void launch_lightmap_dilate(const double* d_in, const int32_t* d_owner_in, int W, int H, int round, double* d_out, int32_t* d_owner_out, int channels,
                             hipStream_t st)
 {
-    hipLaunchKernelGGL(k_lm_dilate, dim3(lightmap_blocks((long long)W * H)), dim3(kLmBlock), 0, st, d_irr_in, d_owner_in, W, H, round, d_irr_out,
-                       d_owner_out);
+    const dim3 grid(lightmap_blocks((long long)W * H));
+    if (channels == 3)
+        hipLaunchKernelGGL(k_lm_dilate<3>, grid, dim3(kLmBlock), 0, st, d_in, d_owner_in, W, H, round, d_out, d_owner_out);
+    else
+        hipLaunchKernelGGL(k_lm_dilate<1>, grid, dim3(kLmBlock), 0, st, d_in, d_owner_in, W, H, round, d_out, d_owner_out);
 }
 
 }  // namespace mcpt

@@ -96,8 +96,8 @@ void launch_lightmap_texels(const DScene& S, const double* d_uv6, int W, int H, 
 // cleared the maps.  d_err / d_hits (and their sources) may be null.
 void launch_lightmap_scatter(const int32_t* d_texels, long long n_list, const double* d_mean, const double* d_stderr, const int32_t* d_hits_in,
                              double* d_irr, double* d_err, int32_t* d_hits, hipStream_t st);
-// Step 5, round r: (irr_in, owner_in) -> (irr_out, owner_out), every texel of the W x H map written.
-void launch_lightmap_dilate(const double* d_irr_in, const int32_t* d_owner_in, int W, int H, int round, double* d_irr_out, int32_t* d_owner_out,
+// Step 5, round r: (in, owner_in) -> (out, owner_out), every texel of the W x H map written; channels a texel: 3, or 1 (an occlusion map).
+void launch_lightmap_dilate(const double* d_in, const int32_t* d_owner_in, int W, int H, int round, double* d_out, int32_t* d_owner_out, int channels,
                             hipStream_t st);
 
 }  // namespace mcpt

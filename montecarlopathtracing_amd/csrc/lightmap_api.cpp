@@ -1,7 +1,8 @@
 // C ABI, lightmap baking (include/mcpt.h: mcpt_lightmap_*, mcpt_bake_lightmap*): a UV chart is rasterised into a map of texels, the
 // covered texels become a list of surface points, mcpt_query_radiance's hemisphere kind answers that list (query_api.cpp: query_device,
 // unchanged), and the answers go back into the map, whose gutters are dilated.  Everything but the host rasteriser runs on the GPU
-// (lightmap.hip); the host waits once per call, for the number of covered texels.
+// (lightmap.hip); the host waits once per call, for the number of covered texels.  The spine of a bake (map_bake) is the occlusion
+// map's as well (occlusion_api.cpp), and the dilation's round loop (lightmap_dilate_rounds) the denoiser's.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -74,7 +75,7 @@ int lightmap_ensure_work(mcpt_device* d, int W, int H, LightmapWork& w, hipStrea
 }
 
 // Step 1 on st and the number of covered texels, which the host waits for: 4 bytes back.
-static int raster_device(mcpt_device* d, const double* d_uv6, int W, int H, const LightmapWork& w, hipStream_t st, int32_t& covered)
+int lightmap_raster_device(mcpt_device* d, const double* d_uv6, int W, int H, const LightmapWork& w, hipStream_t st, int32_t& covered)
 {
     launch_lightmap_raster(d->ds, d_uv6, W, H, w, st);
     HIP_TRY(hipGetLastError());
@@ -84,36 +85,67 @@ static int raster_device(mcpt_device* d, const double* d_uv6, int W, int H, cons
     return MCPT_OK;
 }
 
-// Steps 1 to 5 on st, after the refusals; device pointers throughout.  ap: an adaptive bake (mcpt_bake_lightmap_adaptive) -- step 3 is the
-// adaptive query call (adaptive_query_api.cpp) and d_counts (may be null) the map of the texels' own sample counts; null: a uniform bake.
-static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_params& p, const mcpt_adaptive_params* ap, double* d_irr, double* d_err,
-                       int32_t* d_hits, int32_t* d_owner, int32_t* d_counts, mcpt_stats* stats, hipStream_t st)
+// Step 5, rounds 1 .. R: the one loop of the two bakes, the occlusion map and the denoiser.
+void lightmap_dilate_rounds(double* const frame[2], int32_t* const own[2], int W, int H, int R, int channels, int& at, hipStream_t st)
+{
+    for (int r = 1; r <= R; r++) {
+        launch_lightmap_dilate(frame[at], own[(r - 1) & 1], W, H, r, frame[at ^ 1], own[r & 1], channels, st);
+        at ^= 1;
+    }
+}
+
+// Steps 1 to 5 on st, after the refusals; device pointers throughout.  Step 3, the answers to the texel list, and step 4, their scatter
+// into frame_at, are the caller's `answer`.
+int map_bake(mcpt_device* d, const double* d_uv6, int W, int H, int R, int channels, double* d_map, const MapClear* clears, int n_clears,
+             int32_t* d_owner, mcpt_stats* stats, hipStream_t st, const MapAnswer& answer)
 {
     if (const int rc = lightmap_device_gate(d)) return rc;
     if (stats) std::memset(stats, 0, sizeof *stats);
-    const int W = p.width, H = p.height, R = p.dilate;
-    const size_t n = size_t(W) * H;
+    const size_t n = size_t(W) * H, ch = size_t(channels);
     LightmapWork w{};
-    Lease l;                                                // (d->lm's: the adaptive query call below holds its own)
+    Lease l;                                                // (d->lm's: the query behind `answer` holds its own)
     if (const int rc = lightmap_ensure_work(d, W, H, w, st, l)) return rc;
     mcpt_device::Lightmap& m = *d->lm;
     if (R > 0) {
         if (const int rc = grow(m.owner[1], n, kWork)) return rc;
-        if (const int rc = grow(m.irr, n * 3, kWork)) return rc;
+        if (const int rc = grow(m.irr, n * ch, kWork)) return rc;
     }
     int32_t covered = 0;
-    if (const int rc = raster_device(d, d_uv6, W, H, w, st, covered)) return rc;
+    if (const int rc = lightmap_raster_device(d, d_uv6, W, H, w, st, covered)) return rc;
     // the rounds alternate between the caller's frame and the baker's own: the scatter starts where R rounds end in the caller's
-    double* frame[2] = {d_irr, m.irr.get()};
+    double* const frame[2] = {d_map, m.irr.get()};
     int at = R & 1;
-    HIP_TRY(hipMemsetAsync(frame[at], 0, n * 3 * sizeof(double), st));
-    if (d_err) HIP_TRY(hipMemsetAsync(d_err, 0, n * 3 * sizeof(double), st));
-    if (d_hits) HIP_TRY(hipMemsetAsync(d_hits, 0, n * sizeof(int32_t), st));
-    if (d_counts) HIP_TRY(hipMemsetAsync(d_counts, 0, n * sizeof(int32_t), st));
+    HIP_TRY(hipMemsetAsync(frame[at], 0, n * ch * sizeof(double), st));
+    for (int i = 0; i < n_clears; i++)
+        if (clears[i].map) HIP_TRY(hipMemsetAsync(clears[i].map, 0, clears[i].bytes, st));
     if (covered > 0) {
         const size_t c = size_t(covered);
         if (const int rc = grow(m.texels, c, kWork)) return rc;
         if (const int rc = grow(m.q6, c * 6, kWork)) return rc;
+        launch_lightmap_texels(d->ds, d_uv6, W, H, w, m.texels.get(), m.q6.get(), st);
+        HIP_TRY(hipGetLastError());
+        if (const int rc = answer(m.texels.get(), m.q6.get(), covered, frame[at])) return rc;
+        HIP_TRY(hipGetLastError());
+    }
+    int32_t* const own[2] = {m.owner[0].get(), m.owner[1].get()};
+    lightmap_dilate_rounds(frame, own, W, H, R, channels, at, st);
+    HIP_TRY(hipGetLastError());
+    if (d_owner) HIP_TRY(hipMemcpyAsync(d_owner, own[R & 1], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    return l.end(MCPT_OK);
+}
+
+// Both irradiance bakes on st, after the refusals; device pointers throughout.  ap: an adaptive bake (mcpt_bake_lightmap_adaptive) -- step 3
+// is the adaptive query call (adaptive_query_api.cpp) and d_counts (may be null) the map of the texels' own sample counts; null: a
+// uniform bake, step 3 the query call (query_api.cpp).
+static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_params& p, const mcpt_adaptive_params* ap, double* d_irr, double* d_err,
+                       int32_t* d_hits, int32_t* d_owner, int32_t* d_counts, mcpt_stats* stats, hipStream_t st)
+{
+    const size_t n = size_t(p.width) * p.height;
+    const MapClear clears[] = {{d_err, n * 3 * sizeof(double)}, {d_hits, n * sizeof(int32_t)}, {d_counts, n * sizeof(int32_t)}};
+    return map_bake(d, d_uv6, p.width, p.height, p.dilate, 3, d_irr, clears, 3, d_owner, stats, st,
+                    [&](const int32_t* texels, const double* q6, int32_t covered, double* frame_at) -> int {
+        const size_t c = size_t(covered);
+        mcpt_device::Lightmap& m = *d->lm;
         if (const int rc = grow(m.mean, c * 3, kWork)) return rc;
         if (d_err)
             if (const int rc = grow(m.err, c * 3, kWork)) return rc;
@@ -121,26 +153,16 @@ static int bake_device(mcpt_device* d, const double* d_uv6, const mcpt_lightmap_
             if (const int rc = grow(m.hits, c, kWork)) return rc;
         if (d_counts)
             if (const int rc = grow(m.counts, c, kWork)) return rc;
-        launch_lightmap_texels(d->ds, d_uv6, W, H, w, m.texels.get(), m.q6.get(), st);
-        HIP_TRY(hipGetLastError());
-        const DQuery q{m.q6.get(), MCPT_QUERY_HEMISPHERE, m.mean.get(), d_err ? m.err.get() : nullptr, d_hits ? m.hits.get() : nullptr};
+        const DQuery q{q6, MCPT_QUERY_HEMISPHERE, m.mean.get(), d_err ? m.err.get() : nullptr, d_hits ? m.hits.get() : nullptr};
         if (ap) {
-            if (const int rc = adaptive_query_device(d, q, m.texels.get(), covered, p.spp, p.sample_base, p.seed, p.flags, *ap,
-                                                     d_counts ? m.counts.get() : nullptr, stats, st))
+            if (const int rc = adaptive_query_device(d, q, texels, covered, p.spp, p.sample_base, p.seed, p.flags, *ap, d_counts ? m.counts.get() : nullptr,
+                                                     stats, st))
                 return rc;
-            if (d_counts) launch_aq_scatter_counts(m.texels.get(), covered, m.counts.get(), d_counts, st);
-        } else if (const int rc = query_device(d, q, m.texels.get(), covered, p.spp, p.sample_base, p.seed, p.flags, stats, st)) return rc;
-        launch_lightmap_scatter(m.texels.get(), covered, q.mean3, q.stderr3, q.hits, frame[at], d_err, d_hits, st);
-        HIP_TRY(hipGetLastError());
-    }
-    int32_t* own[2] = {m.owner[0].get(), m.owner[1].get()};
-    for (int r = 1; r <= R; r++) {
-        launch_lightmap_dilate(frame[at], own[(r - 1) & 1], W, H, r, frame[at ^ 1], own[r & 1], st);
-        at ^= 1;
-    }
-    HIP_TRY(hipGetLastError());
-    if (d_owner) HIP_TRY(hipMemcpyAsync(d_owner, own[R & 1], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    return l.end(MCPT_OK);
+            if (d_counts) launch_aq_scatter_counts(texels, covered, m.counts.get(), d_counts, st);
+        } else if (const int rc = query_device(d, q, texels, covered, p.spp, p.sample_base, p.seed, p.flags, stats, st)) return rc;
+        launch_lightmap_scatter(texels, covered, q.mean3, q.stderr3, q.hits, frame_at, d_err, d_hits, st);
+        return MCPT_OK;
+    });
 }
 
 extern "C" {
@@ -189,7 +211,7 @@ int64_t mcpt_lightmap_texels(mcpt_device* d, const double* uv6, int32_t width, i
     Lease l;
     if (const int rc = lightmap_ensure_work(d, width, height, w, st, l)) return rc;
     int32_t covered = 0;
-    if (const int rc = raster_device(d, d_uv, width, height, w, st, covered)) return rc;
+    if (const int rc = lightmap_raster_device(d, d_uv, width, height, w, st, covered)) return rc;
     const size_t n = size_t(width) * height, c = size_t(covered);
     if ((texels || q6) && covered > cap) return fail(MCPT_ERR_ARG, "more texels are covered (" + std::to_string(covered) + ") than the list holds");
     if (owner) HIP_TRY(hipMemcpy(owner, w.owner, n * sizeof(int32_t), hipMemcpyDeviceToHost));

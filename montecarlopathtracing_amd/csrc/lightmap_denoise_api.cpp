@@ -56,16 +56,13 @@ static int denoise_device(mcpt_device* d, const double* d_uv6, const mcpt_lightm
     launch_lightmap_raster(d->ds, d_uv6, W, H, w, st);
     HIP_TRY(hipGetLastError());
     // the dilation's rounds alternate between the caller's frame and the baker's own: the filter writes where R rounds end in the caller's
-    double* frame[2] = {d_out, m.irr.get()};
+    double* const frame[2] = {d_out, m.irr.get()};
     int at = R & 1;
     launch_lightmap_denoise(d->ds, d_uv6, W, H, w, d_irr, d_err, K, sigma_l, sigma_p, reinterpret_cast<LightmapGuide*>(m.dn_guide.get()),
                             reinterpret_cast<LightmapPix*>(m.dn_buf[0].get()), reinterpret_cast<LightmapPix*>(m.dn_buf[1].get()), frame[at], st);
     HIP_TRY(hipGetLastError());
-    int32_t* own[2] = {m.owner[0].get(), m.owner[1].get()};
-    for (int r = 1; r <= R; r++) {
-        launch_lightmap_dilate(frame[at], own[(r - 1) & 1], W, H, r, frame[at ^ 1], own[r & 1], st);
-        at ^= 1;
-    }
+    int32_t* const own[2] = {m.owner[0].get(), m.owner[1].get()};
+    lightmap_dilate_rounds(frame, own, W, H, R, 3, at, st);
     HIP_TRY(hipGetLastError());
     if (d_owner) HIP_TRY(hipMemcpyAsync(d_owner, own[R & 1], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     return l.end(MCPT_OK);

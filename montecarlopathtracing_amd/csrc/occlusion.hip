@@ -1,11 +1,12 @@
 // Ambient occlusion's kernels (mcpt.h: ambient occlusion): the rays of a chunk of entries -- the irradiance query's own draw (query.hpp:
-// query_ray), written into the visibility bake's workspace, which the unchanged closest-hit launch then answers --, the fold of those
-// answers into every entry's occlusion, error, bent normal and hit counts, and, for a map, the scatter of a texel list's answers and the
-// lightmap's dilation on one channel.  The arithmetic is occlusion.hpp's, the copy the host fold compiles.  fp64 throughout, no
-// contraction (-ffp-contract=off).  Every sum is added in sample order; no atomics, no LDS: a result depends neither on the grid of the
-// launch nor on the chunking nor on the device.
+// query_ray; chunk_kernels.hpp: k_chunk_rays), written into the visibility bake's workspace, which the unchanged closest-hit launch then
+// answers --, the fold of those answers into every entry's occlusion, error, bent normal and hit counts, and, for a map, the scatter of
+// a texel list's answers (its dilation is the lightmap's own kernel on one channel: lightmap.hip).  The arithmetic is occlusion.hpp's,
+// the copy the host fold compiles.  fp64 throughout, no contraction (-ffp-contract=off).  Every sum is added in sample order; no
+// atomics, no LDS: a result depends neither on the grid of the launch nor on the chunking nor on the device.
 #include <hip/hip_runtime.h>
 
+#include "chunk_kernels.hpp"
 #include "dev_common.hpp"
 #include "device_scene.hpp"
 #include "occlusion.hpp"
@@ -15,19 +16,6 @@ namespace mcpt {
 
 static constexpr int kOccBlock = 256;
 static constexpr int kOccWaves = kOccBlock / 64;
-
-// ---- rays: one lane per ray of the chunk, six fp64 stores
-__global__ void __launch_bounds__(kOccBlock) k_occ_rays(OccChunk c, long long n)
-{
-    const long long gid = (long long)blockIdx.x * kOccBlock + threadIdx.x;
-    if (gid >= n) return;
-    const long long i = c.first + gid / c.spp;
-    const int j = int(gid % c.spp);
-    V3 o, d;
-    query_ray(MCPT_QUERY_KIND_HEMISPHERE, c.q6 + i * 6, c.seed, c.ids ? c.ids[i] : (int)i, c.sample_base + j, o, d);
-    double* r = c.rays6 + gid * 6;
-    r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
-}
 
 // sample `slot` of the workspace as the fold reads it
 __device__ __forceinline__ OccSample occ_load(const DScene& S, const OccChunk& c, long long slot)
@@ -44,22 +32,13 @@ __device__ __forceinline__ void occ_store(const OccChunk& c, long long P, const 
     ao[P] = a.s1 / c.spp;
     if (err) err[P] = occlusion_stderr(a.s1, a.s2, c.spp);
     if (bent3) {
-        const double nrm[3] = {c.q6[P * 6 + 3], c.q6[P * 6 + 4], c.q6[P * 6 + 5]};
+        const double nrm[3] = {c.list[P * 6 + 3], c.list[P * 6 + 4], c.list[P * 6 + 5]};
         double o[3];
         occlusion_bent(a.b, nrm, o);
         bent3[P * 3] = o[0]; bent3[P * 3 + 1] = o[1]; bent3[P * 3 + 2] = o[2];
     }
     if (hits) hits[P] = a.hits;
     if (back) back[P] = a.back;
-}
-
-// the value lane `src` (the same for the whole wave) holds: a copy of visibility.hip's wave_read(double, int), kept here so that
-// visibility.hip's object stays the bytes it was (one shared copy in dev_common.hpp would change them)
-__device__ __forceinline__ double occ_wave_read(double v, int src)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, src), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), src);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
 // ---- fold: one wave per entry, waves striding over the chunk's entries.  The wave reads 64 samples a step, coalesced, each lane derives
@@ -86,8 +65,8 @@ __global__ void __launch_bounds__(kOccBlock) k_occ_fold(DScene S, OccChunk c, do
             a.back += __popcll(__ballot(s.behind));
             for (int j = 0; j < m; j++) {
                 OccSample r;
-                r.v = occ_wave_read(s.v, j);
-                r.dv[0] = occ_wave_read(s.dv[0], j); r.dv[1] = occ_wave_read(s.dv[1], j); r.dv[2] = occ_wave_read(s.dv[2], j);
+                r.v = wave_read(s.v, j);
+                r.dv[0] = wave_read(s.dv[0], j); r.dv[1] = wave_read(s.dv[1], j); r.dv[2] = wave_read(s.dv[2], j);
                 r.near = false; r.behind = false;       // (counted above)
                 occlusion_add(a, r);
             }
@@ -114,72 +93,21 @@ __global__ void __launch_bounds__(kOccBlock) k_occ_scatter(const int32_t* __rest
     if (back) back[T] = back_in[i];
 }
 
-// ---- a map's dilation, one round of the lightmap's rule (lightmap.hip: k_lm_dilate) on one channel: a texel that is not valid (owner
-// -1) takes the mean of its valid neighbours of the round before, summed in row-major order, and becomes valid with owner -1 - round;
-// every other texel is copied.  Input and output are different buffers.
-__global__ void __launch_bounds__(kOccBlock) k_occ_dilate(const double* __restrict__ ao_in, const int32_t* __restrict__ owner_in, int W, int H, int round,
-                                                          double* __restrict__ ao_out, int32_t* __restrict__ owner_out)
-{
-    const long long i = (long long)blockIdx.x * kOccBlock + threadIdx.x;
-    if (i >= (long long)W * H) return;
-    const int o = owner_in[i];
-    double s = ao_in[i];
-    int out = o;
-    if (o == -1) {
-        const int x = int(i % W), y = int(i / W);
-        double a = 0.0;
-        int c = 0;
-        for (int dy = -1; dy <= 1; dy++) {
-            for (int dx = -1; dx <= 1; dx++) {
-                const int xx = x + dx, yy = y + dy;
-                if (xx < 0 || xx >= W || yy < 0 || yy >= H) continue;
-                const size_t j = (size_t)yy * W + xx;
-                if (owner_in[j] == -1) continue;                // (the texel itself among them)
-                a += ao_in[j];
-                c++;
-            }
-        }
-        if (c > 0) {
-            s = a / double(c);
-            out = -1 - round;
-        }
-    }
-    ao_out[i] = s;
-    owner_out[i] = out;
-}
-
-static inline unsigned occ_blocks(long long n, long long per_block, long long cap)
-{
-    const long long b = (n + per_block - 1) / per_block;
-    return (unsigned)(b < cap ? (b > 0 ? b : 1) : cap);
-}
-
-void launch_occlusion_rays(const OccChunk& c, hipStream_t st)
-{
-    const long long n = c.count * c.spp;
-    hipLaunchKernelGGL(k_occ_rays, dim3(occ_blocks(n, kOccBlock, 0x7fffffffll)), dim3(kOccBlock), 0, st, c, n);
-}
+void launch_occlusion_rays(const OccChunk& c, hipStream_t st) { launch_chunk_rays<MCPT_QUERY_KIND_HEMISPHERE>(c, st); }
 
 void launch_occlusion_fold(const DScene& S, const OccChunk& c, double* d_ao, double* d_stderr1, double* d_bent3, int32_t* d_hits, int32_t* d_back,
                            hipStream_t st)
 {
     // (the fold's waves stride over the entries: a grid beyond a few waves per SIMD of the largest device gains nothing)
-    hipLaunchKernelGGL(k_occ_fold, dim3(occ_blocks(c.count, kOccWaves, 1 << 16)), dim3(kOccBlock), 0, st, S, c, d_ao, d_stderr1, d_bent3, d_hits, d_back);
+    hipLaunchKernelGGL(k_occ_fold, dim3(grid_blocks(c.count, kOccWaves, 1 << 16)), dim3(kOccBlock), 0, st, S, c, d_ao, d_stderr1, d_bent3, d_hits, d_back);
 }
 
 void launch_occlusion_scatter(const int32_t* d_texels, long long n_list, const double* ao, const double* err, const double* bent3, const int32_t* hits,
                               const int32_t* back, double* d_ao, double* d_err, double* d_bent3, int32_t* d_hits, int32_t* d_back, hipStream_t st)
 {
     if (n_list <= 0) return;
-    hipLaunchKernelGGL(k_occ_scatter, dim3(occ_blocks(n_list, kOccBlock, 0x7fffffffll)), dim3(kOccBlock), 0, st, d_texels, n_list, ao, err, bent3, hits, back,
+    hipLaunchKernelGGL(k_occ_scatter, dim3(grid_blocks(n_list, kOccBlock, 0x7fffffffll)), dim3(kOccBlock), 0, st, d_texels, n_list, ao, err, bent3, hits, back,
                        d_ao, d_err, d_bent3, d_hits, d_back);
-}
-
-void launch_occlusion_dilate(const double* d_ao_in, const int32_t* d_owner_in, int W, int H, int round, double* d_ao_out, int32_t* d_owner_out,
-                             hipStream_t st)
-{
-    hipLaunchKernelGGL(k_occ_dilate, dim3(occ_blocks((long long)W * H, kOccBlock, 0x7fffffffll)), dim3(kOccBlock), 0, st, d_ao_in, d_owner_in, W, H, round,
-                       d_ao_out, d_owner_out);
 }
 
 }  // namespace mcpt

@@ -1,7 +1,8 @@
 // Ambient occlusion (mcpt.h: ambient occlusion): the arithmetic of an entry's fold -- the value of one sample under a falloff, the five
 // sums, the standard error, the bent normal and its fallback --, the one copy of it: occlusion.hip compiles it for the GPU,
 // occlusion_api.cpp for mcpt_occlusion_fold_host.  fp64, no contraction (-ffp-contract=off), IEEE division, every expression in the order
-// mcpt.h writes it; tests/occlusion_ref.py restates it in numpy.  The launch interface of the four kernels is at the end.
+// mcpt.h writes it; tests/occlusion_ref.py restates it in numpy.  The launch interface of the three kernels is at the end; a map is dilated
+// by the lightmap's own kernel on one channel (lightmap.hpp: launch_lightmap_dilate).
 #pragma once
 #include <hip/hip_runtime_api.h>
 #include <math.h>
@@ -81,22 +82,14 @@ MCPT_HD void occlusion_bent(const double* b, const double* nrm, double* out)
     out[0] = s[0] / m; out[1] = s[1] / m; out[2] = s[2] / m;
 }
 
-// What a query's kernels share: the entries of one chunk and the workspace their rays live in (mcpt_device::Visibility).  Ray (i, j),
-// sample j of the chunk's entry i, sits at slot i * spp + j of rays6 / leaf / t.
-struct OccChunk {
-    const double* q6;           // [n][6] all the call's entries: position, normal
-    const int32_t* ids;         // [n] or null
-    long long first, count;     // the chunk's entries: first .. first + count - 1
-    int spp, sample_base;
-    unsigned long long seed;
+// What a query's kernels share: a RayChunk (visibility.hpp) whose list is the call's entries, [n][6] position and normal, in the hit
+// workspace the visibility bake uses too (mcpt_device::Visibility), and the two knobs of the fold.
+struct OccChunk : RayChunk {
     int falloff;
     double max_distance;
-    double* rays6;              // [count * spp][6]
-    int32_t* leaf;              // [count * spp] the leaf of the closest hit, -1: a miss
-    double* t;                  // [count * spp]
 };
 
-// rays6[slot] = query_ray(MCPT_QUERY_KIND_HEMISPHERE, ...) of every ray of the chunk, one lane per ray
+// rays6[slot] = query_ray(MCPT_QUERY_KIND_HEMISPHERE, ...) of every ray of the chunk (chunk_kernels.hpp: k_chunk_rays)
 void launch_occlusion_rays(const OccChunk& c, hipStream_t st);
 // the fold of the chunk's traced rays into ao [n] and (each may be null) stderr1 [n], bent3 [n][3], hits, back [n], at the chunk's entries
 void launch_occlusion_fold(const DScene& S, const OccChunk& c, double* d_ao, double* d_stderr1, double* d_bent3, int32_t* d_hits, int32_t* d_back,
@@ -105,8 +98,5 @@ void launch_occlusion_fold(const DScene& S, const OccChunk& c, double* d_ao, dou
 // be null.
 void launch_occlusion_scatter(const int32_t* d_texels, long long n_list, const double* ao, const double* err, const double* bent3, const int32_t* hits,
                               const int32_t* back, double* d_ao, double* d_err, double* d_bent3, int32_t* d_hits, int32_t* d_back, hipStream_t st);
-// the lightmap's dilation rule, round r, on one channel: (ao_in, owner_in) -> (ao_out, owner_out), every texel of the W x H map written
-void launch_occlusion_dilate(const double* d_ao_in, const int32_t* d_owner_in, int W, int H, int round, double* d_ao_out, int32_t* d_owner_out,
-                             hipStream_t st);
 
 }  // namespace mcpt

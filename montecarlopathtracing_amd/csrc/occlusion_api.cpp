@@ -1,8 +1,8 @@
 // C ABI, ambient occlusion (include/mcpt.h: mcpt_query_occlusion*, mcpt_occlusion_fold_host, mcpt_bake_occlusion_lightmap*): per entry of
 // a list of surface points the share of its hemisphere that is open, a bent normal and the counts of near and back-face hits.  A query
 // draws the irradiance query's own rays into the visibility bake's workspace (occlusion.hip), answers them with the unchanged closest-hit
-// launch (kernels.hip: launch_trace_closest_leaf) and folds chunk by chunk; a map is that query over the lightmap baker's texel list
-// (lightmap.hip, unchanged), scattered and dilated on one channel.  The arithmetic is occlusion.hpp's, compiled here for the host fold.
+// launch (hit_work.hpp: trace_leaf) and folds chunk by chunk (chunk_run); a map is that query over the lightmap baker's texel list,
+// scattered and dilated on one channel (lightmap_api.cpp: map_bake).  The arithmetic is occlusion.hpp's, compiled here for the host fold.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -58,91 +58,39 @@ static int occlusion_device(mcpt_device* d, const double* d_q6, const int32_t* d
     if (const int rc = geometry_gate(d)) return rc;
     Lease l;
     if (const int rc = lease(d->vis, st, l)) return rc;     // the visibility or occlusion call before this one has left the workspace
-    mcpt_device::Visibility& w = *d->vis;
+    HitWork& w = *d->vis;
     const int64_t per_chunk = chunk_plan(op.workspace_rays, op.spp, n);     // whole entries
-    const int64_t rays = per_chunk * op.spp;
-    // (2^38 rays are 256 blocks short of the largest grid of k_occ_rays, and 23 TB)
-    if (rays > (int64_t(1) << 38)) return fail(MCPT_ERR_NOMEM, "the occlusion workspace of " + std::to_string(rays) + " rays cannot be allocated");
-    const size_t sr = size_t(rays);
-    if (const int rc = grow(w.rays6, sr * 6, "the occlusion rays")) return rc;
-    if (const int rc = grow(w.t, sr, "the occlusion rays' distances")) return rc;
-    if (const int rc = grow(w.p, sr * 3, "the occlusion rays' hit points")) return rc;
-    if (const int rc = grow(w.leaf, sr, "the occlusion rays' hits")) return rc;
-    int chunks = 0;
-    int rc = MCPT_OK;
-    for (int64_t first = 0; first < n && rc == MCPT_OK; first += per_chunk, chunks++) {
-        OccChunk c{};
-        c.q6 = d_q6; c.ids = d_ids; c.first = first; c.count = chunk_count(per_chunk, n, first);
-        c.spp = op.spp; c.sample_base = op.sample_base; c.seed = op.seed; c.falloff = op.falloff; c.max_distance = op.max_distance;
-        c.rays6 = w.rays6.get(); c.leaf = w.leaf.get(); c.t = w.t.get();
+    // (2^38 rays are 256 blocks short of the largest grid of the rays kernel, and 23 TB)
+    if (const int rc = hit_work_grow(w, per_chunk * op.spp, int64_t(1) << 38, "occlusion", true)) return rc;
+    return chunk_run(n, per_chunk, op.spp, l, stats, st, [&](int64_t first, int64_t count) {
+        const OccChunk c{{d_q6, d_ids, first, count, op.spp, op.sample_base, op.seed, w.rays6.get(), w.leaf.get(), w.t.get()}, op.falloff, op.max_distance};
         launch_occlusion_rays(c, st);
-        launch_trace_closest_leaf(d->ds, d->trace_mode == MCPT_TRACE_FAST, c.rays6, c.count * c.spp, c.leaf, c.t, w.p.get(), d->aux_ctr.get(), d->aux_queue.get(),
-                                  d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
+        trace_leaf(d, c.rays6, c.count * c.spp, c.leaf, c.t, w.p.get(), st);
         launch_occlusion_fold(d->ds, c, d_ao, d_err, d_bent3, d_hits, d_back, st);
-        rc = launch_result();
-    }
-    if ((rc = l.end(rc)) != MCPT_OK) return rc;
-    if (stats) {
-        HIP_TRY(hipStreamSynchronize(st));
-        stats->rays_primary = stats->samples = uint64_t(n) * uint64_t(op.spp);
-        stats->launches = chunks;
-    }
-    return MCPT_OK;
+        return launch_result();
+    });
 }
 
-// The map on st, after the refusals; device pointers throughout.  The host waits once, for the number of covered texels.
+// The map on st, after the refusals; device pointers throughout: the lightmap baker's spine (lightmap_api.cpp: map_bake) on one channel
+// around the query above.  (The map holds d->lm's lease, the query d->vis's.)
 static int map_device(mcpt_device* d, const double* d_uv6, const mcpt_occlusion_map& mp, const mcpt_occlusion_params& op, double* d_ao, double* d_err,
                       double* d_bent3, int32_t* d_hits, int32_t* d_back, int32_t* d_owner, mcpt_stats* stats, hipStream_t st)
 {
-    if (const int rc = lightmap_device_gate(d)) return rc;
-    if (stats) std::memset(stats, 0, sizeof *stats);
-    const int W = mp.width, H = mp.height, R = mp.dilate;
-    const size_t n = size_t(W) * H;
-    LightmapWork w{};
-    Lease l;                                                // (d->lm's: the query below holds d->vis's)
-    if (const int rc = lightmap_ensure_work(d, W, H, w, st, l)) return rc;
-    mcpt_device::Lightmap& m = *d->lm;
-    if (R > 0) {
-        if (const int rc = grow(m.owner[1], n, kWork)) return rc;
-        if (const int rc = grow(m.irr, n, kWork)) return rc;
-    }
-    // the lightmap's raster (lightmap.hip) and the covered count, which the host waits for: 4 bytes back
-    launch_lightmap_raster(d->ds, d_uv6, W, H, w, st);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(m.h_total.get(), w.total, sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    const int32_t covered = m.h_total[0];
-    // the rounds alternate between the caller's frame and the baker's own: the scatter starts where R rounds end in the caller's
-    double* frame[2] = {d_ao, m.irr.get()};
-    int at = R & 1;
-    HIP_TRY(hipMemsetAsync(frame[at], 0, n * sizeof(double), st));
-    if (d_err) HIP_TRY(hipMemsetAsync(d_err, 0, n * sizeof(double), st));
-    if (d_bent3) HIP_TRY(hipMemsetAsync(d_bent3, 0, n * 3 * sizeof(double), st));
-    if (d_hits) HIP_TRY(hipMemsetAsync(d_hits, 0, n * sizeof(int32_t), st));
-    if (d_back) HIP_TRY(hipMemsetAsync(d_back, 0, n * sizeof(int32_t), st));
-    if (covered > 0) {
+    const size_t n = size_t(mp.width) * mp.height;
+    const MapClear clears[] = {{d_err, n * sizeof(double)}, {d_bent3, n * 3 * sizeof(double)}, {d_hits, n * sizeof(int32_t)}, {d_back, n * sizeof(int32_t)}};
+    return map_bake(d, d_uv6, mp.width, mp.height, mp.dilate, 1, d_ao, clears, 4, d_owner, stats, st,
+                    [&](const int32_t* texels, const double* q6, int32_t covered, double* frame_at) -> int {
         const size_t c = size_t(covered);
-        if (const int rc = grow(m.texels, c, kWork)) return rc;
-        if (const int rc = grow(m.q6, c * 6, kWork)) return rc;
+        mcpt_device::Lightmap& m = *d->lm;
         if (const int rc = grow(m.occ, c * 5, kWork)) return rc;
         if (const int rc = grow(m.occ_cnt, c * 2, kWork)) return rc;
-        launch_lightmap_texels(d->ds, d_uv6, W, H, w, m.texels.get(), m.q6.get(), st);
-        HIP_TRY(hipGetLastError());
         // the query's answers by list entry: ao [c], stderr [c], bent [c][3]; hits [c], back [c]
         double *ao = m.occ.get(), *err = d_err ? ao + c : nullptr, *bent = d_bent3 ? ao + 2 * c : nullptr;
         int32_t *hits = d_hits ? m.occ_cnt.get() : nullptr, *back = d_back ? m.occ_cnt.get() + c : nullptr;
-        if (const int rc = occlusion_device(d, m.q6.get(), m.texels.get(), covered, op, ao, err, bent, hits, back, stats, st)) return rc;
-        launch_occlusion_scatter(m.texels.get(), covered, ao, err, bent, hits, back, frame[at], d_err, d_bent3, d_hits, d_back, st);
-        HIP_TRY(hipGetLastError());
-    }
-    int32_t* own[2] = {m.owner[0].get(), m.owner[1].get()};
-    for (int r = 1; r <= R; r++) {
-        launch_occlusion_dilate(frame[at], own[(r - 1) & 1], W, H, r, frame[at ^ 1], own[r & 1], st);
-        at ^= 1;
-    }
-    HIP_TRY(hipGetLastError());
-    if (d_owner) HIP_TRY(hipMemcpyAsync(d_owner, own[R & 1], n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    return l.end(MCPT_OK);
+        if (const int rc = occlusion_device(d, q6, texels, covered, op, ao, err, bent, hits, back, stats, st)) return rc;
+        launch_occlusion_scatter(texels, covered, ao, err, bent, hits, back, frame_at, d_err, d_bent3, d_hits, d_back, st);
+        return MCPT_OK;
+    });
 }
 
 extern "C" {

@@ -421,8 +421,7 @@ static int ensure_sample_aovs(mcpt_progressive* h, int G)
     for (int64_t first = 0; first < h->n_pixels && e == hipSuccess; first += per_chunk) {
         const int n = int(std::min<int64_t>(per_chunk, h->n_pixels - first));
         launch_guide_rays(lens, h->p.seed, h->pixels.get(), int(first), n, G, rays6.get(), st);
-        launch_trace_closest_leaf(d->ds, d->trace_mode == MCPT_TRACE_FAST, rays6.get(), (long long)n * G, leaf.get(), t.get(), p.get(), d->aux_ctr.get(),
-                                  d->aux_queue.get(), d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
+        trace_leaf(d, rays6.get(), (long long)n * G, leaf.get(), t.get(), p.get(), st);
         launch_guide_fold(d->ds, h->pixels.get(), int(first), n, G, leaf.get(), t.get(), p.get(), h->saov_counts.get(), h->saov_depth.get(),
                           h->saov_normal.get(), h->saov_albedo.get(), h->sguide.get(), st);
         e = hipGetLastError();

@@ -1,10 +1,12 @@
 // Probe visibility's kernels (mcpt.h: probe visibility): the rays of a chunk of probes -- the probe query's own draw (query.hpp:
-// query_ray), written into a workspace the unchanged closest-hit launch then answers --, the fold of those answers into every probe's
-// octahedral depth moments and hit counts, and the irradiance volume's lookup with a factor per corner.  The arithmetic is
-// visibility.hpp's, the copy the host forms compile.  fp64 throughout, no contraction (-ffp-contract=off).  Every sum is one lane's, in
-// sample order; no atomics, no LDS: a result depends neither on the grid of the launch nor on the chunking nor on the device.
+// query_ray, in chunk_kernels.hpp's k_chunk_rays), written into a workspace the unchanged closest-hit launch then answers --, the fold
+// of those answers into every probe's octahedral depth moments and hit counts, and the irradiance volume's lookup with a factor per
+// corner.  The arithmetic is visibility.hpp's, the copy the host forms compile.  fp64 throughout, no contraction (-ffp-contract=off).
+// Every sum is one lane's, in sample order; no atomics, no LDS: a result depends neither on the grid of the launch nor on the chunking
+// nor on the device.
 #include <hip/hip_runtime.h>
 
+#include "chunk_kernels.hpp"
 #include "dev_common.hpp"
 #include "device_scene.hpp"
 #include "query.hpp"
@@ -15,35 +17,13 @@ namespace mcpt {
 static constexpr int kVisBlock = 256;
 static constexpr int kVisWaves = kVisBlock / 64;
 
-// ---- rays: one lane per ray of the chunk, six fp64 stores
-__global__ void __launch_bounds__(kVisBlock) k_vis_rays(VisChunk c, long long n)
-{
-    const long long gid = (long long)blockIdx.x * kVisBlock + threadIdx.x;
-    if (gid >= n) return;
-    const long long i = c.first + gid / c.spp;
-    const int j = int(gid % c.spp);
-    V3 o, d;
-    query_ray(MCPT_QUERY_KIND_SPHERE, c.p3 + i * 3, c.seed, c.ids ? c.ids[i] : (int)i, c.sample_base + j, o, d);
-    double* r = c.rays6 + gid * 6;
-    r[0] = o.x; r[1] = o.y; r[2] = o.z; r[3] = d.x; r[4] = d.y; r[5] = d.z;
-}
-
-// the value lane `src` (the same for the whole wave) holds
-__device__ __forceinline__ int wave_read(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
-__device__ __forceinline__ double wave_read(double v, int src)
-{
-    const long long b = __double_as_longlong(v);
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, src), hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), src);
-    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
 // ---- fold: one wave per probe, a lane per bin (NB = 1: R <= 8) or per four bins (NB = 4: lane l holds bins l, l + 64, l + 128, l + 192).
 // The wave reads 64 samples a step, each lane derives its sample's bin and depth, and the 64 (bin, depth) pairs go round the wave in
 // sample order: the lane that holds the bin adds.  So a bin's sums are one lane's, added in j order.  Hits and back-face hits are
 // counted by ballot.  A lane per (probe, bin) that scans all the probe's samples itself derives every sample's bin R * R times over and
 // measured 6.4 times slower (3.47 ms against 0.54 ms for 64^3 probes of 64 samples at R = 8: DESIGN 6r); it was removed.
 template <int NB>
-__global__ void __launch_bounds__(kVisBlock) k_vis_fold(DScene S, VisChunk c, int R, double max_distance, double max_back_fraction, double* __restrict__ moments,
+__global__ void __launch_bounds__(kVisBlock) k_vis_fold(DScene S, RayChunk c, int R, double max_distance, double max_back_fraction, double* __restrict__ moments,
                                                         int32_t* __restrict__ hits, int32_t* __restrict__ back, uint8_t* __restrict__ valid)
 {
     const int lane = threadIdx.x & 63;
@@ -118,23 +98,13 @@ __global__ void __launch_bounds__(kVisBlock) k_vol_irradiance_visible(mcpt_volum
     if (corners) corners[r] = c;
 }
 
-static inline unsigned vis_blocks(long long n, long long per_block, long long cap)
-{
-    const long long b = (n + per_block - 1) / per_block;
-    return (unsigned)(b < cap ? (b > 0 ? b : 1) : cap);
-}
+void launch_visibility_rays(const RayChunk& c, hipStream_t st) { launch_chunk_rays<MCPT_QUERY_KIND_SPHERE>(c, st); }
 
-void launch_visibility_rays(const VisChunk& c, hipStream_t st)
-{
-    const long long n = c.count * c.spp;
-    hipLaunchKernelGGL(k_vis_rays, dim3(vis_blocks(n, kVisBlock, 0x7fffffffll)), dim3(kVisBlock), 0, st, c, n);
-}
-
-void launch_visibility_fold(const DScene& S, const VisChunk& c, const mcpt_visibility_params& vp, double* d_moments, int32_t* d_hits, int32_t* d_back,
+void launch_visibility_fold(const DScene& S, const RayChunk& c, const mcpt_visibility_params& vp, double* d_moments, int32_t* d_hits, int32_t* d_back,
                             uint8_t* d_valid, hipStream_t st)
 {
     // (the fold's waves stride over the probes: a grid beyond a few waves per SIMD of the largest device gains nothing)
-    const dim3 grid(vis_blocks(c.count, kVisWaves, 1 << 16));
+    const dim3 grid(grid_blocks(c.count, kVisWaves, 1 << 16));
     if (vp.res <= 8)
         hipLaunchKernelGGL(k_vis_fold<1>, grid, dim3(kVisBlock), 0, st, S, c, vp.res, vp.max_distance, vp.max_back_fraction, d_moments, d_hits, d_back, d_valid);
     else

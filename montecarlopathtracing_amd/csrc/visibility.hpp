@@ -97,12 +97,13 @@ MCPT_HD int visibility_corners(const mcpt_volume_grid& g, const mcpt_volume_visi
     return n;
 }
 
-// What a bake's kernels share: the probes of one chunk and the workspace their rays live in.  Ray (i, j), sample j of the chunk's probe
-// i, sits at slot i * spp + j of rays6 / leaf / t.
-struct VisChunk {
-    const double* p3;           // [n][3] all the call's probes
+// What the kernels of a call that answers a list chunk by chunk share (a bake here, an occlusion query: occlusion.hpp): the items (probes,
+// entries) of one chunk and the workspace their rays live in (HitWork).  Ray (i, j), sample j of the chunk's item i, sits at slot
+// i * spp + j of rays6 / leaf / t.
+struct RayChunk {
+    const double* list;         // all the call's items: [n][3] positions (sphere) or [n][6] positions and normals (hemisphere)
     const int32_t* ids;         // [n] or null
-    long long first, count;     // the chunk's probes: first .. first + count - 1
+    long long first, count;     // the chunk's items: first .. first + count - 1
     int spp, sample_base;
     unsigned long long seed;
     double* rays6;              // [count * spp][6]
@@ -110,10 +111,10 @@ struct VisChunk {
     double* t;                  // [count * spp]
 };
 
-// rays6[slot] = query_ray(MCPT_QUERY_KIND_SPHERE, ...) of every ray of the chunk, one lane per ray
-void launch_visibility_rays(const VisChunk& c, hipStream_t st);
+// rays6[slot] = query_ray(MCPT_QUERY_KIND_SPHERE, ...) of every ray of the chunk (chunk_kernels.hpp: k_chunk_rays)
+void launch_visibility_rays(const RayChunk& c, hipStream_t st);
 // the fold of the chunk's traced rays into moments [n][R * R][2] and (each may be null) hits, back, valid [n], at the chunk's probes
-void launch_visibility_fold(const DScene& S, const VisChunk& c, const mcpt_visibility_params& vp, double* d_moments, int32_t* d_hits, int32_t* d_back,
+void launch_visibility_fold(const DScene& S, const RayChunk& c, const mcpt_visibility_params& vp, double* d_moments, int32_t* d_hits, int32_t* d_back,
                             uint8_t* d_valid, hipStream_t st);
 // launch_volume_irradiance with visibility_corners for volume_corners
 void launch_volume_irradiance_visible(const mcpt_volume_grid& g, const mcpt_volume_visibility& vp, const double* d_sh27, const double* d_moments,

@@ -1,8 +1,8 @@
 // C ABI, probe visibility (include/mcpt.h: mcpt_visibility_bin, mcpt_query_visibility*, mcpt_bake_volume_visibility*,
 // mcpt_volume_irradiance_visible*): per probe an octahedral map of depth moments and the count of back-face hits, and the irradiance
 // volume's lookup weighted by them.  A bake draws the probe query's own rays into a workspace the device keeps (visibility.hip), answers
-// them with the unchanged closest-hit launch (kernels.hip: launch_trace_closest_leaf -- mcpt_trace_closest_device's walks, handing back the
-// leaf, whose record holds the face normal) and folds chunk by chunk.  The arithmetic is visibility.hpp's, compiled here for the host forms.
+// them with the unchanged closest-hit launch (hit_work.hpp: trace_leaf -- mcpt_trace_closest_device's walks, handing back the leaf, whose
+// record holds the face normal) and folds chunk by chunk (hit_work.hpp: chunk_run).  The arithmetic is visibility.hpp's, compiled here for the host forms.
 #include <hip/hip_runtime_api.h>
 
 #include <cmath>
@@ -86,36 +86,17 @@ static int bake_device(mcpt_device* d, const double* d_p3, const int32_t* d_ids,
     if (const int rc = geometry_gate(d)) return rc;
     Lease l;
     if (const int rc = lease(d->vis, st, l)) return rc;     // the bake before this one has left the workspace
-    mcpt_device::Visibility& w = *d->vis;
+    HitWork& w = *d->vis;
     const int64_t per_chunk = chunk_plan(vp.workspace_rays, vp.spp, n);     // whole probes
-    const int64_t rays = per_chunk * vp.spp;
-    if (rays > (int64_t(1) << 40)) return fail(MCPT_ERR_NOMEM, "the visibility workspace of " + std::to_string(rays) + " rays cannot be allocated");
-    const size_t sr = size_t(rays);
-    if (const int rc = grow(w.rays6, sr * 6, "the visibility rays")) return rc;
-    if (const int rc = grow(w.t, sr, "the visibility rays' distances")) return rc;
-    if (const int rc = grow(w.p, sr * 3, "the visibility rays' hit points")) return rc;
-    if (const int rc = grow(w.leaf, sr, "the visibility rays' hits")) return rc;
+    if (const int rc = hit_work_grow(w, per_chunk * vp.spp, int64_t(1) << 40, "visibility", true)) return rc;
     static_assert(kRayBytes == 84, "mcpt.h states the workspace's bytes per ray");
-    int chunks = 0;
-    int rc = MCPT_OK;
-    for (int64_t first = 0; first < n && rc == MCPT_OK; first += per_chunk, chunks++) {
-        VisChunk c{};
-        c.p3 = d_p3; c.ids = d_ids; c.first = first; c.count = chunk_count(per_chunk, n, first);
-        c.spp = vp.spp; c.sample_base = vp.sample_base; c.seed = vp.seed;
-        c.rays6 = w.rays6.get(); c.leaf = w.leaf.get(); c.t = w.t.get();
+    return chunk_run(n, per_chunk, vp.spp, l, stats, st, [&](int64_t first, int64_t count) {
+        const RayChunk c{d_p3, d_ids, first, count, vp.spp, vp.sample_base, vp.seed, w.rays6.get(), w.leaf.get(), w.t.get()};
         launch_visibility_rays(c, st);
-        launch_trace_closest_leaf(d->ds, d->trace_mode == MCPT_TRACE_FAST, c.rays6, c.count * c.spp, c.leaf, c.t, w.p.get(), d->aux_ctr.get(), d->aux_queue.get(),
-                                  d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
+        trace_leaf(d, c.rays6, c.count * c.spp, c.leaf, c.t, w.p.get(), st);
         launch_visibility_fold(d->ds, c, vp, d_moments, d_hits, d_back, d_valid, st);
-        rc = launch_result();
-    }
-    if ((rc = l.end(rc)) != MCPT_OK) return rc;
-    if (stats) {
-        HIP_TRY(hipStreamSynchronize(st));
-        stats->rays_primary = stats->samples = uint64_t(n) * uint64_t(vp.spp);
-        stats->launches = chunks;
-    }
-    return MCPT_OK;
+        return launch_result();
+    });
 }
 
 // the grid form on st: the grid's positions into the volume's own list (volume_api.cpp), then the list form

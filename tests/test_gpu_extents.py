@@ -22,8 +22,8 @@ Coverage: symbol | case | sizes | block constant the sizes come from
   mcpt_query_radiance_device            | test_list[radiance], test_list_in_chunks | n 1, 65, 257; spp 3 and 301                  | 256: query.hip __launch_bounds__(256)
   mcpt_query_radiance_adaptive_device   | test_list[adaptive], test_list_in_chunks | n 1, 65, 257; spp 5 and 301, min 2           | 256: adaptive_query.hip __launch_bounds__(256)
   mcpt_query_sh_device                  | test_list[sh], test_list_in_chunks | n 1, 65, 257; spp 3 and 301                  | 256: query.hip k_query_fold_sh
-  mcpt_query_visibility_device          | test_list[visibility]          | n 1, 65, 257; spp 5, res 4            | 256: visibility.hip kVisBlock
-  mcpt_query_occlusion_device           | test_list[occlusion]           | n 1, 65, 257; spp 5                   | 256: occlusion.hip kOccBlock
+  mcpt_query_visibility_device          | test_list[visibility]          | n 1, 65, 257; spp 5, res 4            | 256: visibility.hip kVisBlock, chunk_kernels.hpp kChunkBlock
+  mcpt_query_occlusion_device           | test_list[occlusion]           | n 1, 65, 257; spp 5                   | 256: occlusion.hip kOccBlock, chunk_kernels.hpp kChunkBlock
   mcpt_bake_reflection_device           | test_list[reflection_bake]     | n 1, 65, 257; res 5, spp 3            | 256: reflection.hip kReflBlock
   mcpt_reflection_prefilter_device      | test_list[reflection_prefilter]| n 1, 65, 257; res 5 -> levels 4, 2    | 256: reflection.hip kReflBlock
   mcpt_reflection_lookup_device         | test_list[reflection_lookup]   | m 1, 65, 257; 3 probes                | 256: reflection.hip kReflBlock
@@ -35,10 +35,10 @@ Coverage: symbol | case | sizes | block constant the sizes come from
   mcpt_baked_radiance_specular_device   | test_list[baked_specular]      | n 1, 65, 257                          | 256: baked_specular.hip kSpecBlock
   mcpt_bake_lightmap_device             | test_map[lightmap-*]           | 33 x 17 dilate 0 and 2, 1 x 1; chart null and guarded | 256: lightmap.hip kLmBlock
   mcpt_bake_lightmap_adaptive_device    | test_map[adaptive-*]           | 33 x 17 dilate 0 and 2, 1 x 1; chart null and guarded | 256: lightmap.hip kLmBlock
-  mcpt_bake_occlusion_lightmap_device   | test_map[occlusion-*]          | 33 x 17 dilate 0 and 2, 1 x 1; chart null and guarded | 256: occlusion.hip kOccBlock, lightmap.hip kLmBlock
+  mcpt_bake_occlusion_lightmap_device   | test_map[occlusion-*]          | 33 x 17 dilate 0 and 2, 1 x 1; chart null and guarded | 256: occlusion.hip kOccBlock, chunk_kernels.hpp kChunkBlock, lightmap.hip kLmBlock (k_lm_dilate<1>)
   mcpt_lightmap_denoise_device          | test_map[denoise-*]            | 33 x 17 dilate 0 and 2, 1 x 1; chart null and guarded | 256: lightmap_denoise.hip kLmdBlock
   mcpt_bake_volume_device               | test_grid[volume-*]            | grids 3 x 2 x 2 and 1 x 1 x 1; spp 33 | 256: volume.hip kVolBlock
-  mcpt_bake_volume_visibility_device    | test_grid[visibility-*]        | grids 3 x 2 x 2 and 1 x 1 x 1; res 8  | 256: visibility.hip kVisBlock
+  mcpt_bake_volume_visibility_device    | test_grid[visibility-*]        | grids 3 x 2 x 2 and 1 x 1 x 1; res 8  | 256: visibility.hip kVisBlock, chunk_kernels.hpp kChunkBlock
   mcpt_render_device                    | test_frame_render             | 33 x 17 and 1 x 1; world 2, ranks 0 and 1, tiles 32 x 8 and 5 x 3 | 256: wavefront.hip fold
   mcpt_render_baked_device              | test_frame_baked[baked-*]      | 33 x 17 and 1 x 1; 3 samples          | 256: baked.hip kBakedBlock
   mcpt_render_baked_specular_device     | test_frame_baked[baked_specular-*] | 33 x 17 and 1 x 1; 3 samples          | 256: baked_specular.hip kSpecBlock

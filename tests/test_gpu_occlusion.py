@@ -218,7 +218,7 @@ def test_device_forms_on_a_side_stream_are_the_host_forms(mcpt, cornell, surface
 
 # ---- 2. the map
 
-@pytest.mark.parametrize("dilate", [0, 2])
+@pytest.mark.parametrize("dilate", [0, 1, 2, 3])
 @pytest.mark.parametrize("size", [(16, 16), (33, 17)], ids=lambda s: "%dx%d" % s)
 def test_a_map_is_the_query_of_its_texel_list(mcpt, cornell, chart, size, dilate):
     dev = cornell

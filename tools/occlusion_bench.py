@@ -10,7 +10,7 @@ bake  : cornell-box under grid_atlas at --size^2.  One warm-up call and --calls 
         same rays -- and of mcpt_query_visibility_device over the map's texel list at the same sample count (the same number of rays,
         drawn over the sphere), taken in turn.  Medians.  The fold's traffic floor: 36 bytes read per ray (direction, leaf, distance) and
         56 written per entry, at 8 TB/s.  Under rocprofv3 --kernel-trace --stats (a run of its own) the kernels' names give the split:
-        k_occ_rays, the trace engine's kernels, k_occ_fold, k_occ_scatter.  Run from the checkout of a build without the occlusion calls
+        k_chunk_rays<1>, the trace engine's kernels, k_occ_fold, k_occ_scatter.  Run from the checkout of a build without the occlusion calls
         (the parent's), the tool times the lightmap bake alone.
 approx: glassroom's own chart at --size^2: volumes of 8^3, 16^3 and 32^3 probes baked at --spp and the occlusion of the texel list at
         --spp with a reach of 1.5 cell diagonals, against Device.irradiance of the same list at --ref-spp.  The estimates: the plain

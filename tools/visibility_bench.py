@@ -9,7 +9,7 @@ bake  : cornell-box, a --grid^3 volume over the scene's bounds (2 % in from ever
         mcpt_bake_volume_visibility_device, each between two HIP events on one stream, and the same of mcpt_bake_volume_device on the
         same grid -- the yardstick: the radiance bake of the same rays.  Medians.  The fold's traffic floor: 36 bytes read per ray
         (direction, leaf, distance) and 16 written per bin, at 8 TB/s.  Under rocprofv3 --kernel-trace --stats (a run of its own) the
-        kernels' names give the split: k_vis_rays, the trace engine's kernels, k_vis_fold.  MCPT_LIB selects another build of the library.
+        kernels' names give the split: k_chunk_rays<2>, the trace engine's kernels, k_vis_fold.  MCPT_LIB selects another build of the library.
 lookup: that volume baked once (coefficients and moments) into device buffers; the receivers are the texel list of cornell-box under
         grid_atlas at --size^2.  mcpt_volume_irradiance_visible_device and mcpt_volume_irradiance_device timed alternately.
 approx: glassroom's own chart at --size^2: volumes of 8^3, 16^3 and 32^3 probes baked at --spp, looked up plainly, under the baked
