@@ -25,6 +25,11 @@
 //     are taken by the refill step that loads the ray, while it is in registers: every lane that got a ray takes part, where a node
 //     step of the pool runs with the lanes that happen to wait for one.  (Path mode files its rays at the root: the SHADE step runs
 //     at 24 lanes and holds the vertex code's registers.)
+//   * A refill from a sparse source (the wavefront's path state: a quarter of its slots hold no ray) reads the flag words of a window of
+//     up to 128 source slots first, ranks the rays among them (refill_window.hpp) and lets every claiming lane load the one ray it will
+//     walk: no empty slot is fetched, no ray word crosses lanes, and a step hands out rays to all its lanes where 64 slots held 42.
+//     Dense sources (every slot a ray) fetch 64 slots, one per lane, and shuffle the rays to the lanes that need one -- and so does a
+//     wave of a sparse source whose last refill found rays in 7 slots of 8 and more: there the flags' trip to memory buys nothing.
 // The decisions are the persistent engine's, test for test (same cw_step, tri_pre_reject, tri_hit, ranking, own-box check at the end),
 // so results are bit-identical to it and to the reference-shaped walk.
 //
@@ -39,6 +44,7 @@
 // step as long as its slowest walk.
 #pragma once
 #include "env.hpp"
+#include "refill_window.hpp"
 #include "trace_persistent.hpp"
 #include "vertex.hpp"
 
@@ -105,7 +111,7 @@ struct PoolLds {
     int stack[SCAP * KT * 64];              // [entry][k][lane]
     unsigned int cls[5 * 64];               // [class][lane]: bit k = slot k * 64 + lane waits for a step of that class (class 4, path mode: bit k = PATH slot k waits for its next vertex)
     unsigned int busy[64];                  // path mode: bit k = ray slot k of this lane is still walking
-    int tbl[NW * 64];                       // refill: rank among the fetched rays -> lane that holds it
+    int tbl[NW * 64];                       // refill: rank among the rays found -> their offset from the wave's next source slot (a row per wave)
     unsigned int stat[8];                   // path mode: shade calls, shadow rays, bounce rays, shadow rays skipped, deepest vertex (flushed by the kernel)
     unsigned int live;                      // slots that may still carry a ray (path mode: path slots that may still carry a path)
     unsigned int dry;                       // waves whose supply of source slots has run out
@@ -173,6 +179,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
     const unsigned long long d_t0 = d_t;
 #endif
     long long next = 0, range_end = 0;          // unclaimed part of the wave's chunk of source slots
+    [[maybe_unused]] bool window_next = true;   // sparse sources: the wave's next refill reads flags first (the same in every lane)
     bool queue_empty = false;
     int rot = wave % KT;                        // where a lane starts to look for a set bit: rotates, so no slot waits forever --
     // every pair of waves with a stride of its own (11, 13, 17, 19: odd, and coprime to the 20 slots), so that two waves after the same
@@ -662,31 +669,98 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 }
             }
             if (!queue_empty) {
-                // the next <= 64 source slots, one per lane; the rays among them go to the lanes that need one, in order
                 const long long left = range_end - next;
-                const int avail = left < 64 ? (int)left : 64;
-                Ray nr; nr.o = mk(0, 0, 0); nr.d = mk(1, 1, 1);
-                const bool valid = lane < avail && src.fetch(next + lane, nr);
-                const bool ok = valid && fast_path_ok(F, nr);
-                const unsigned long long V = __ballot(ok);
-                const int n_ok = __popcll(V);
-                const int rank_ok = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(V >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)V, 0u));
-                int used = avail;                // source slots consumed by this step
-                if (n_ok > n_have) used = __ffsll((long long)__ballot(ok && rank_ok == n_have - 1));
-                used = uni(used);
-                if (valid && !ok && lane < used) defer_ray(queue, slow_list, slow_cap, next + lane, false);      // a ray the fast walk may not take
-                if (ok && rank_ok < n_have) L.tbl[wave * 64 + rank_ok] = lane;
                 const int rank_need = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(hv >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)hv, 0u));
-                got = have && rank_need < n_ok;
-                __asm__ volatile("" ::: "memory");
-                const int from = got ? L.tbl[wave * 64 + rank_need] : lane;
                 // The root's words, for the first step below: scalar loads, issued here where rays are fetched (a refill that finds the
                 // queue dry loads nothing) and, like the launch's arguments (wf_ray_source.hpp), not held in registers across the walk loop.
                 CwNodeWords root = (CwNodeWords)nodes;
                 __asm__ volatile("" : "+s"(root));
-                Ray r;
-                r.o.x = __shfl(nr.o.x, from, 64); r.o.y = __shfl(nr.o.y, from, 64); r.o.z = __shfl(nr.o.z, from, 64);
-                r.d.x = __shfl(nr.d.x, from, 64); r.d.y = __shfl(nr.d.y, from, 64); r.d.z = __shfl(nr.d.z, from, 64);
+                Ray r; r.o = mk(0, 0, 0); r.d = mk(1, 1, 1);
+                int from = lane;                 // this lane's ray: its offset from `next`
+                int used;                        // source slots consumed by this step
+#ifdef MCPT_POOL_DEBUG
+                int n_okc;                       // rays among them that the fast walk takes
+#endif
+                // A sparse source refills by one of two forms, chosen per wave from what its last refill saw (window_next).  Where a
+                // quarter and more of the slots are empty (a bounce plane after Russian roulette) the window form below hands a ray to
+                // every lane that asks; where nearly every slot holds a ray (shadow planes, scenes of many lights) it finds no more rays
+                // than the 64-slot fetch and its second trip to memory -- flags, then rays -- is all that is left of it: veach-mis, 93 %
+                // of whose slots hold a ray, was 1.1 ms of 120 slower with the window form alone (profiles/r07_window_refill.txt).
+                // Both forms consume `used` slots from `next` and start or defer every ray among them, so they mix freely.
+                bool use_window = false;
+                if constexpr (Src::kSparse) use_window = window_next;
+                if (use_window) {
+                  if constexpr (Src::kSparse) {
+                    // Flags first, then each lane loads its own ray (refill_window.hpp).  The window is the next W <= 128 source slots;
+                    // lane i reads the flag words of offsets i and 64 + i, inside the window only.  The window's rays go, in slot order,
+                    // to the lanes that claimed a slot; a lane fetches the one ray it will walk, and no empty slot is fetched at all.
+                    // The window's first slot is split into (plane, path) once -- `next` is the same in every lane: scalar work -- and
+                    // every lane steps on from there.
+                    const int W = left < (long long)kRefillWindow ? (int)left : (int)kRefillWindow;
+                    int win_l; long long win_j;
+                    src.split(next, win_l, win_j);
+                    win_l = uni(win_l); win_j = uni(win_j);
+                    int flag0 = 0, flag1 = 0;
+                    bool fb0 = false, fb1 = false;
+                    { int l; long long j;
+                      if (lane < W) { src.split_from(win_l, win_j, lane, l, j); flag0 = src.flag(l, j, fb0); }
+                      if (lane + 64 < W) { src.split_from(win_l, win_j, 64 + lane, l, j); flag1 = src.flag(l, j, fb1); } }
+                    const bool v0 = lane < W && Src::flag_has_ray(flag0, fb0);
+                    const bool v1 = lane + 64 < W && Src::flag_has_ray(flag1, fb1);
+                    const unsigned long long V0 = __ballot(v0), V1 = __ballot(v1);
+                    const int n_valid = refill_n_valid(V0, V1);
+                    const int rank0 = refill_rank(V0, 0, (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(V0 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)V0, 0u)));
+                    const int rank1 = refill_rank(V0, 1, (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(V1 >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)V1, 0u)));
+                    // (ordering: rank -> offset goes through this wave's own row of L.tbl, written and read by this wave in this step;
+                    // the compiler barrier keeps the reads behind the writes, the LDS serves a wave's accesses in order)
+                    if (v0 && refill_taken(rank0, n_have)) L.tbl[wave * 64 + rank0] = lane;
+                    if (v1 && refill_taken(rank1, n_have)) L.tbl[wave * 64 + rank1] = 64 + lane;
+                    // Progress: n_have >= 1 here (hv != 0), so used = W when every ray of the window is taken -- an empty window
+                    // included: a plane without a ray drains 128 slots a step, then through tickets like any other -- and otherwise
+                    // the offset of the last ray taken + 1 >= 1.  No loop, no wait: the step ends whatever the flags say.
+                    used = uni(refill_used(__ballot(v0 && refill_last(rank0, n_have)), __ballot(v1 && refill_last(rank1, n_have)), n_valid, n_have, W));
+                    // No slot twice, none skipped: claiming lanes have ranks 0 .. n_have - 1, so ranks below min(n_valid, n_have) are
+                    // taken, each by one lane, and those are exactly the rays below next + used; every one is started or deferred.
+                    const bool take = have && rank_need < n_valid;
+                    __asm__ volatile("" ::: "memory");
+                    if (take) {
+                        from = L.tbl[wave * 64 + rank_need];
+                        int l; long long j;
+                        src.split_from(win_l, win_j, from, l, j);
+                        src.fetch(l, j, r);
+                        got = fast_path_ok(F, r);
+                        if (!got) defer_ray(queue, slow_list, slow_cap, next + from, false);      // a ray the fast walk may not take: this lane asks again
+                    }
+                    // the share of rays among the slots this step consumed: 7 in 8 and more, and the next refill fetches 64 slots whole
+                    window_next = (n_valid < n_have ? n_valid : n_have) * 8 < used * 7;
+#ifdef MCPT_POOL_DEBUG
+                    n_okc = __popcll(__ballot(got));
+#endif
+                  }
+                } else {
+                    // (nearly) every slot holds a ray: the next <= 64 source slots, one per lane; the rays go to the lanes that need one, in order
+                    const int avail = left < 64 ? (int)left : 64;
+                    Ray nr; nr.o = mk(0, 0, 0); nr.d = mk(1, 1, 1);
+                    const bool valid = lane < avail && src.fetch(next + lane, nr);
+                    const bool ok = valid && fast_path_ok(F, nr);
+                    const unsigned long long V = __ballot(ok);
+                    const int n_ok = __popcll(V);
+                    const int rank_ok = (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(V >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)V, 0u));
+                    used = avail;
+                    if (n_ok > n_have) used = __ffsll((long long)__ballot(ok && rank_ok == n_have - 1));
+                    used = uni(used);
+                    if (valid && !ok && lane < used) defer_ray(queue, slow_list, slow_cap, next + lane, false);      // a ray the fast walk may not take
+                    if (ok && rank_ok < n_have) L.tbl[wave * 64 + rank_ok] = lane;
+                    got = have && rank_need < n_ok;
+                    __asm__ volatile("" ::: "memory");
+                    from = got ? L.tbl[wave * 64 + rank_need] : lane;
+                    r.o.x = __shfl(nr.o.x, from, 64); r.o.y = __shfl(nr.o.y, from, 64); r.o.z = __shfl(nr.o.z, from, 64);
+                    r.d.x = __shfl(nr.d.x, from, 64); r.d.y = __shfl(nr.d.y, from, 64); r.d.z = __shfl(nr.d.z, from, 64);
+                    if constexpr (Src::kSparse) window_next = __popcll(__ballot(valid && lane < used)) * 8 < used * 7;
+#ifdef MCPT_POOL_DEBUG
+                    n_okc = __popcll(__ballot(ok && lane < used));
+#endif
+                }
                 bool second = false;                    // this lane's ray also took a step on its nearest root child
                 if (got) {
                     const V3 rcp = mk(fast_rcp(r.d.x), fast_rcp(r.d.y), fast_rcp(r.d.z));
@@ -735,7 +809,7 @@ __device__ __forceinline__ void trace_pool(const DScene& S, const Src& src, Trac
                 }
                 next += used;
 #ifdef MCPT_POOL_DEBUG
-                d_used += used; d_okc += __popcll(__ballot(ok && lane < used)); d_steps++;
+                d_used += used; d_okc += n_okc; d_steps++;
 #endif
                 const unsigned int n_got = (unsigned int)__popcll(__ballot(got));
                 c_rays += n_got;

@@ -242,10 +242,12 @@ long long persistent_chunk(long long total, int grid_blocks)
     return c;
 }
 
-void launch_wf_trace(const DScene& S, const WfArgs& a, long long n_upper, bool fast, TraceQueue* queue, long long* slow_list,
+void launch_wf_trace(const DScene& S, const WfArgs& args, long long n_upper, bool fast, TraceQueue* queue, long long* slow_list,
                      unsigned int slow_cap, hipStream_t st, const LaunchCfg& cfg)
 {
     if (n_upper <= 0) return;
+    WfArgs a = args;
+    { const DivMagic dm = div_magic((unsigned int)(a.spp > 0 ? a.spp : 1)); a.spp_mul = dm.mul; a.spp_shift = dm.shift; }
     const long long total = n_upper * (a.nl + 1);
     if (!fast) {
         hipLaunchKernelGGL(k_wf_trace_reference, dim3(grid_for(total, 256, 1u << 20)), dim3(256), 0, st, S, a);

@@ -112,6 +112,10 @@ struct WfArgs {
     // state (out.p) instead of a pixel's PrimaryHit -- and the first logic pass records here, per chunk-local sample id, whether the
     // sample's camera ray hit something (1) or not (0).  Null in the per-pixel route.
     uint8_t* cam_hit;
+    // id / spp of the trace kernels' first launch (the pixel of a path: its PrimaryHit) as one multiplication and one shift, exactly
+    // (div_magic, refill_window.hpp).  launch_wf_trace fills the two in from spp; behind the older fields like sample_base.
+    unsigned int spp_mul;
+    int spp_shift;
 };
 
 size_t wf_bytes_per_path(int nl);

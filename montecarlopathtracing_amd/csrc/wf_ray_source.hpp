@@ -2,6 +2,7 @@
 // l in [0, nl] (l == nl: the bounce ray of path j), rebuilt from the path state k_wf_logic wrote (wavefront.hpp).
 #pragma once
 #include "dev_common.hpp"
+#include "refill_window.hpp"
 #include "vertex.hpp"
 #include "wavefront.hpp"
 
@@ -10,6 +11,7 @@ namespace mcpt {
 // ray slot q = l*n_paths + j, l in [0, nl] (l == nl: the bounce ray of path j)
 struct WfRaySource {
     static constexpr bool kWantsPoint = false;      // results are a leaf or a material: the hit point is formed again by the next logic pass
+    static constexpr bool kSparse = true;           // many slots hold no ray (Russian roulette, lights behind the surface): has_ray() says which
     WfArgs a;
     long long n_paths;
     __device__ __forceinline__ long long total() const { return n_paths * (a.nl + 1); }
@@ -29,10 +31,37 @@ struct WfRaySource {
         }
         return ldc(a.out.p, a.cap, j);
     }
+    // (l, j) of the slot `off` behind slot (l0, j0): a caller that walks a window of slots splits its first slot once -- a wave's
+    // next slot is the same in every lane, so that is scalar work -- and every lane steps on from there, seldom over a plane's end
+    __device__ __forceinline__ void split_from(int l0, long long j0, int off, int& l, long long& j) const
+    {
+        l = l0; j = j0 + off;
+        while (j >= n_paths) { j -= n_paths; l++; }
+    }
+    // The flag word of slot (l, j) alone, by fetch()'s own rule -- in two halves, so that a caller can request the word early and look
+    // at it late: flag() loads it and says whether it is a bounce slot's, flag_has_ray() judges it.
+    __device__ __forceinline__ int flag(int l, long long j, bool& bounce) const
+    {
+        bounce = l == a.nl;
+        return bounce ? a.out.btype[j] : a.out.expect[(long long)l * a.cap + j];
+    }
+    static __device__ __forceinline__ bool flag_has_ray(int flag, bool bounce) { return bounce ? flag >= 0 : flag != -2; }
+    __device__ __forceinline__ bool has_ray(long long q) const
+    {
+        int l; long long j;
+        split(q, l, j);
+        bool bounce;
+        const int f = flag(l, j, bounce);
+        return flag_has_ray(f, bounce);
+    }
     __device__ __forceinline__ bool fetch(long long q, Ray& r) const
     {
         int l; long long j;
         split(q, l, j);
+        return fetch(l, j, r);
+    }
+    __device__ __forceinline__ bool fetch(int l, long long j, Ray& r) const
+    {
         // branch-free: the ray words are loaded whether or not the slot is in use, so nothing waits on the flag
         const bool bounce = l == a.nl;
         const int flag = bounce ? a.out.btype[j] : a.out.expect[(long long)l * a.cap + j];
@@ -86,6 +115,7 @@ template <class P, class T> __device__ __forceinline__ void wf_sst(P p, T v) { *
 #endif
 struct WfRaySourceK {
     static constexpr bool kWantsPoint = false;
+    static constexpr bool kSparse = true;
     WfArgsKernarg ap;
     long long n_paths;
     int nl;
@@ -96,17 +126,42 @@ struct WfRaySourceK {
         l = 0; j = q;
         while (j >= n_paths) { j -= n_paths; l++; }
     }
+    __device__ __forceinline__ void split_from(int l0, long long j0, int off, int& l, long long& j) const
+    {
+        l = l0; j = j0 + off;
+        while (j >= n_paths) { j -= n_paths; l++; }
+    }
+    __device__ __forceinline__ int flag(int l, long long j, bool& bounce) const
+    {
+        const WfArgsKernarg A = args();
+        bounce = l == nl;
+        return bounce ? wf_sld(wf_glob(A->out.btype) + j) : wf_sld(wf_glob(A->out.expect) + ((long long)l * A->cap + j));
+    }
+    static __device__ __forceinline__ bool flag_has_ray(int flag, bool bounce) { return bounce ? flag >= 0 : flag != -2; }
+    __device__ __forceinline__ bool has_ray(long long q) const
+    {
+        int l; long long j;
+        split(q, l, j);
+        bool bounce;
+        const int f = flag(l, j, bounce);
+        return flag_has_ray(f, bounce);
+    }
     __device__ __forceinline__ bool fetch(long long q, Ray& r) const
     {
         int l; long long j;
         split(q, l, j);
+        return fetch(l, j, r);
+    }
+    __device__ __forceinline__ bool fetch(int l, long long j, Ray& r) const
+    {
         const WfArgsKernarg A = args();
         const long long cap = A->cap;
         const bool bounce = l == nl;
         const int flag = bounce ? wf_sld(wf_glob(A->out.btype) + j) : wf_sld(wf_glob(A->out.expect) + ((long long)l * cap + j));
         V3 p;
         if (A->depth == 0 && A->hits) {
-            const auto* ph = wf_glob(A->hits) + (A->first_slot + wf_glob(A->out.id)[j] / A->spp);
+            // (id / spp without a run-time division: launch_wf_trace passes the multiplier and the shift, refill_window.hpp)
+            const auto* ph = wf_glob(A->hits) + (A->first_slot + (int)div_by_magic((unsigned int)wf_glob(A->out.id)[j], A->spp_mul, A->spp_shift));
             p = mk(ph->p[0], ph->p[1], ph->p[2]);
         } else {
             const auto* g = wf_glob(A->out.p);
