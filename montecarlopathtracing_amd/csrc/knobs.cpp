@@ -58,6 +58,7 @@ const Row kRows[] = {
     {"MCPT_TEST_STACK_CAP", "off", "stack entries the trace engines may use (tests force the hand-over to the one-lane walk)"},
     {"MCPT_PRINT_DIAG", "0", "1: phase times and in-kernel counters on stderr"},
     {"MCPT_ALLOW_RUNTIME_MISMATCH", "0", "1: run on a HIP runtime of another release than the one libmcpt.so was compiled against (mcpt_allow_runtime_mismatch)"},
+    {"MCPT_RCCL_LIBRARY", "unset", "path of the collective library the exchanges load first, before librccl.so.1 (mcpt_comm_*, MCPT_GATHER_RCCL; tests name a stand-in that works within one process)"},
 };
 
 std::string make_table()
@@ -103,6 +104,12 @@ Knobs read_knobs()
     k.print_diag = env("MCPT_PRINT_DIAG") != nullptr;
     k.allow_runtime_mismatch = (int)env_ll("MCPT_ALLOW_RUNTIME_MISMATCH", 0, 0, 1 << 30) != 0;
     return k;
+}
+
+std::string rccl_library()
+{
+    const char* e = env("MCPT_RCCL_LIBRARY");
+    return e ? e : "";
 }
 
 const char* knobs_table()

@@ -5,6 +5,7 @@
 // (mcpt_knobs_describe; INTEGRATION.md section 7 is checked against it by a test); nothing else in the library calls getenv.
 #pragma once
 #include <cstdint>
+#include <string>
 
 namespace mcpt {
 
@@ -39,5 +40,9 @@ struct Knobs {
 
 Knobs read_knobs();                     // the process environment, now
 const char* knobs_table();              // one line per variable: name, default, meaning
+// MCPT_RCCL_LIBRARY: the path rccl_loader.hpp tries before librccl.so.1 (empty: unset).  Not a member of Knobs: it is read when an
+// exchange loads the collective library (mcpt_comm_unique_id / mcpt_comm_create, mcpt_multi_create under MCPT_GATHER_RCCL), and kept
+// nowhere -- the loaded library is what the handle keeps.
+std::string rccl_library();
 
 }  // namespace mcpt

@@ -310,7 +310,7 @@ int mcpt_multi_create(const mcpt_scene* scene, const int32_t* devices, int32_t n
     if (gather == MCPT_GATHER_RCCL) {
         std::string err;
         const auto needed = [](const Rccl& r) { return r.CommInitAll && r.CommDestroy && r.GroupStart && r.GroupEnd && r.Send && r.Recv && r.GetErrorString; };
-        if (!m->rccl.load(err, needed)) return fail(MCPT_ERR_IO, err);
+        if (!m->rccl.load(err, needed, mcpt::rccl_library())) return fail(MCPT_ERR_IO, err);
         m->comms.assign(ord.size(), nullptr);
         std::vector<int> devlist(ord.begin(), ord.end());
         const ncclResult_t r = m->rccl.CommInitAll(m->comms.data(), int(devlist.size()), devlist.data());

@@ -22,8 +22,9 @@ struct mcpt_comm {
     int ordinal = 0, rank = 0, world = 1;
     mcpt::Stream stream;                        // the exchange's own stream
     mcpt::Event ev;
-    // pixel lists of the partition the buffers were made for
-    int key[2] = {-1, -1};
+    // pixel lists of the partition the buffers were made for: frame width and height, tile_w, tile_h as the call gave them (world and rank
+    // are the handle's).  A communicator is bound to no scene: the frame's size comes with every call.  {-1, ...}: no list is valid
+    int key[4] = {-1, -1, -1, -1};
     int64_t n_own = 0;
     DevBuf<int32_t> d_pixels_own;               // this rank's pixels
     DevBuf<double> d_compact;                   // [n_own][3]
@@ -47,14 +48,16 @@ static const auto comm_needs = [](const Rccl& r) {
 static void free_lists(mcpt_comm* c)
 {
     c->d_pixels_own.reset(); c->d_compact.reset(); c->d_pixels_of.clear(); c->d_stage_of.clear(); c->n_of.clear();
-    c->key[0] = c->key[1] = -1; c->n_own = 0;
+    for (int& k : c->key) k = -1;
+    c->n_own = 0;
 }
 
 static int prepare_lists(mcpt_comm* c, const mcpt_scene* scene, const mcpt_render_params* p)
 {
-    const int key[2] = {p->tile_w, p->tile_h};
+    const int key[4] = {scene->s.width, scene->s.height, p->tile_w, p->tile_h};
+    if (key[0] <= 0 || key[1] <= 0) return fail(MCPT_ERR_ARG, "the scene has no frame size");
     if (c->d_pixels_own && std::memcmp(key, c->key, sizeof key) == 0) return MCPT_OK;
-    free_lists(c);
+    free_lists(c);                              // (the key with them: whatever fails below, no list of this handle counts as valid)
     // rank r's pixels (a rank without pixels still gets buffers of one entry)
     auto list_of = [&](int r, std::vector<int32_t>& pix) -> int64_t {
         mcpt_render_params q = *p;
@@ -91,7 +94,7 @@ int mcpt_comm_unique_id(uint8_t* id, int64_t cap)
     if (!id || cap < int64_t(sizeof(ncclUniqueId))) return fail(MCPT_ERR_ARG, "the id buffer needs 128 bytes");
     Rccl r;
     std::string err;
-    if (!r.load(err, comm_needs)) return fail(MCPT_ERR_IO, err);
+    if (!r.load(err, comm_needs, mcpt::rccl_library())) return fail(MCPT_ERR_IO, err);
     ncclUniqueId u;
     const ncclResult_t rc = r.GetUniqueId(&u);
     if (rc != ncclSuccess) return fail(MCPT_ERR_HIP, std::string("ncclGetUniqueId: ") + r.GetErrorString(rc));
@@ -120,7 +123,7 @@ int mcpt_comm_create(int32_t ordinal, int32_t rank, int32_t world, const uint8_t
     std::unique_ptr<mcpt_comm, void (*)(mcpt_comm*)> c(new mcpt_comm, mcpt_comm_free);
     c->ordinal = ordinal; c->rank = rank; c->world = world;
     std::string err;
-    if (!c->rccl.load(err, comm_needs)) return fail(MCPT_ERR_IO, err);
+    if (!c->rccl.load(err, comm_needs, mcpt::rccl_library())) return fail(MCPT_ERR_IO, err);
     HIP_TRY(hipSetDevice(ordinal));
     HIP_TRY(create(c->stream, hipStreamCreateWithFlags, hipStreamNonBlocking));
     HIP_TRY(create(c->ev, hipEventCreateWithFlags, hipEventDisableTiming));

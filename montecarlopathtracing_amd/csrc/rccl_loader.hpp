@@ -24,13 +24,15 @@ struct Rccl {
 
     // Loads the library and binds every entry point above that it has; false (and err) when it cannot be loaded or has_needed(*this),
     // the caller's test of the entry points it uses, fails.  (Callers pass a lambda: no instance of load is exported from libmcpt.so.)
+    // `first` is MCPT_RCCL_LIBRARY (knobs.hpp: mcpt::rccl_library()): where it is not empty it is the first candidate.
     template <class Needed>
-    bool load(std::string& err, Needed has_needed)
+    bool load(std::string& err, Needed has_needed, const std::string& first)
     {
         if (!lib) {
+            if (!first.empty()) lib = dlopen(first.c_str(), RTLD_NOW | RTLD_LOCAL);
             for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) {
-                lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
                 if (lib) break;
+                lib = dlopen(name, RTLD_NOW | RTLD_LOCAL);
             }
             if (!lib) { err = std::string("cannot load librccl: ") + dlerror(); return false; }
             auto sym = [&](const char* n) { return dlsym(lib, n); };

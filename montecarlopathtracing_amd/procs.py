@@ -6,7 +6,9 @@ that the ranks build themselves (mcpt_comm_*, csrc/proc_comm.cpp).  torch is del
 runs libmcpt.so's kernels on the wheel's bundled HIP runtime instead of the release they were compiled against, and the
 library refuses that since version 105.  What the ranks need from a launcher is only their rank, the world size and a way to pass
 RCCL's 128-byte unique id from rank 0 to the others -- a file in the node's temporary directory, named after the launcher's process id
-(all ranks are children of one launcher process) and the rendezvous port, written atomically by rank 0 and polled by the others.
+(all ranks are children of one launcher process) and the rendezvous port, written atomically by rank 0 and polled by the others.  A
+record belongs to one attempt of one launch (exchange_id): ranks that took ids of different launches would wait in ncclCommInitRank
+for each other, and that call has no time limit.
 
 The torch.distributed form of the same partition / gather is dist.py (kept for the gloo rehearsal on CPU and as `--launcher torch`)."""
 import ctypes as C
@@ -33,29 +35,66 @@ def rendezvous_file(tag=None):
     return os.path.join(os.environ.get("MCPT_RDZV_DIR") or tempfile.gettempdir(), "mcpt_rdzv_%s" % tag)
 
 
-def exchange_id(rank, world, make_id, path=None, timeout=120.0, started=None):
-    """rank 0: make_id() -> bytes, published; other ranks: wait for it.  The record carries rank 0's clock so that a file left behind by
-    an earlier launch under the same name is not taken for this one's."""
+def launch_key():
+    """what tells one attempt of a launch from another under the same launcher process: torch.distributed.run's run id and restart
+    count (a --max-restarts respawn keeps the launcher, its process id and the port, and counts up); empty under other launchers"""
+    run, restart = os.environ.get("TORCHELASTIC_RUN_ID"), os.environ.get("TORCHELASTIC_RESTART_COUNT")
+    if run is None and restart is None:
+        return b""
+    return ("%s/%s" % (run or "", restart or "")).encode()
+
+
+def launch_began(pid=None):
+    """when the launcher process (default: this process's parent) started, as time.time() counts, from /proc: field 22 of
+    /proc/<pid>/stat is the start in clock ticks after boot, /proc/uptime the seconds since boot.  Rounded UP by the resolution of the
+    two (a tick, 10 ms) and a little more: a record has to be younger than this to be taken, and no rank writes one within 50 ms of
+    its launcher's start.  None where /proc does not say, or says a time that has not come yet."""
+    try:
+        with open("/proc/%d/stat" % (os.getppid() if pid is None else pid)) as fh:
+            ticks = int(fh.read().rsplit(")", 1)[1].split()[19])           # (the command name may hold blanks: count from its ")")
+        with open("/proc/uptime") as fh:
+            uptime = float(fh.read().split()[0])
+        now = time.time()
+        began = now - (uptime - ticks / os.sysconf("SC_CLK_TCK"))
+        # (a /proc whose uptime is not the clock the ticks count in -- some container file systems rewrite it -- gives a start in the future)
+        return began + 0.05 if began <= now else None
+    except (OSError, ValueError, IndexError):
+        return None
+
+
+def exchange_id(rank, world, make_id, path=None, timeout=120.0, started=None, began=None):
+    """rank 0: make_id() -> bytes, published; other ranks: wait for it.  A record belongs to one attempt of one launch: it carries
+    rank 0's clock and launch_key(), and a reader takes it only if the key is its own and the stamp is not older than `began`, the
+    start of the launcher process (launch_began(); given explicitly by tests).  So a file left behind under the same name -- by a
+    crashed or timed-out launch whose process id and port a container hands out again, or by the previous attempt of a launcher that
+    respawns its ranks -- is never returned, however recent; the reader waits for rank 0 to replace it and raises after `timeout`.
+    The ranks of a launch start at different times, so a rank's own start (`started`) bounds less: a record more than 300 s older
+    than it is not taken either, and where /proc does not give the launcher's start that is the only bound."""
     path = path or rendezvous_file()
     started = time.time() if started is None else started
     if world == 1:
         return make_id()
+    key = launch_key()
     if rank == 0:
         ident = make_id()
         assert len(ident) == ID_BYTES
         tmp = "%s.%d.tmp" % (path, os.getpid())
         with open(tmp, "wb") as fh:
-            fh.write(np.float64(time.time()).tobytes() + ident)
+            fh.write(np.float64(time.time()).tobytes() + ident + key)
         os.replace(tmp, path)                      # atomic: a reader sees nothing or everything
         return ident
+    if began is None:
+        began = launch_began()
+    floor = started - 300.0 if began is None else max(began, started - 300.0)
     deadline = time.time() + timeout
     while time.time() < deadline:
         try:
-            raw = open(path, "rb").read()
+            with open(path, "rb") as fh:
+                raw = fh.read()
         except OSError:
             raw = b""
-        if len(raw) == 8 + ID_BYTES and float(np.frombuffer(raw[:8], dtype=np.float64)[0]) >= started - 300.0:
-            return raw[8:]
+        if len(raw) >= 8 + ID_BYTES and raw[8 + ID_BYTES:] == key and float(np.frombuffer(raw[:8], dtype=np.float64)[0]) >= floor:
+            return raw[8:8 + ID_BYTES]
         time.sleep(0.02)
     raise TimeoutError("rank %d: no unique id from rank 0 under %s within %.0f s" % (rank, path, timeout))
 

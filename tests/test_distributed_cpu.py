@@ -99,3 +99,136 @@ def test_unique_id_rendezvous_between_processes(tmp_path):
         P.exchange_id(1, 2, None, path, timeout=0.3)
     assert P.exchange_id(0, 1, lambda: b"x" * 128, path) == b"x" * 128                            # a launch of one needs no file
     assert P.rendezvous_file("abc").endswith("mcpt_rdzv_abc")
+
+
+# ---- a rendezvous record belongs to one attempt of one launch
+
+def _record(path, stamp, ident, key=b""):
+    with open(path, "wb") as fh:
+        fh.write(np.float64(stamp).tobytes() + ident + key)
+
+
+def _publish_later(path, delay, ident):
+    import threading
+    import time
+    import montecarlopathtracing_amd.procs as P
+
+    def run():
+        time.sleep(delay)
+        P.exchange_id(0, 2, lambda: ident, path)
+    t = threading.Thread(target=run)
+    t.start()
+    return t
+
+
+def test_launcher_start_comes_from_proc():
+    """launch_began(): the start of the parent process as time.time() counts -- before this process's own start, which is before now,
+    and the same figure (to the clock's resolution) whenever it is asked; None for a process /proc does not know."""
+    import time
+    import montecarlopathtracing_amd.procs as P
+    parent, own = P.launch_began(), P.launch_began(os.getpid())
+    assert parent is not None and own is not None
+    assert parent <= own + 0.03 and own <= time.time() + 0.06                   # (each is rounded up by 50 ms; /proc/uptime counts in 10 ms)
+    assert abs(P.launch_began() - parent) < 0.05
+    assert P.launch_began(2 ** 30) is None
+
+
+@pytest.mark.parametrize("monkey_key", [False, True], ids=["plain", "elastic"])
+def test_a_record_from_before_the_launch_is_never_taken(tmp_path, monkeypatch, monkey_key):
+    """A record under the same name stamped ten seconds before the launcher of this "launch" (the parent process: /proc) started is
+    ignored, also though it is far younger than the 300 s the old rule allowed; the reader returns what rank 0 then writes.  With the
+    launcher's start given explicitly the same holds to the second: a record 10 ms older is refused, one stamped at it is taken."""
+    import time
+    import montecarlopathtracing_amd.procs as P
+    for k in ("TORCHELASTIC_RUN_ID", "TORCHELASTIC_RESTART_COUNT"):
+        monkeypatch.delenv(k, raising=False)
+    if monkey_key:
+        monkeypatch.setenv("TORCHELASTIC_RUN_ID", "job 7")
+        monkeypatch.setenv("TORCHELASTIC_RESTART_COUNT", "2")
+    key = P.launch_key()
+    assert key == (b"job 7/2" if monkey_key else b"")
+    path = str(tmp_path / "rdzv")
+    stale, fresh = bytes(128), bytes(range(128))
+    _record(path, P.launch_began() - 10.0, stale, key)
+    with pytest.raises(TimeoutError):
+        P.exchange_id(1, 2, None, path, timeout=0.3)
+    t = _publish_later(path, 0.2, fresh)
+    try:
+        assert P.exchange_id(1, 2, None, path, timeout=30.0) == fresh
+    finally:
+        t.join()
+    now = time.time()
+    _record(path, now - 0.01, stale, key)
+    with pytest.raises(TimeoutError):
+        P.exchange_id(1, 2, None, path, timeout=0.2, began=now)
+    _record(path, now, fresh, key)
+    assert P.exchange_id(1, 2, None, path, timeout=5.0, began=now) == fresh
+    # bench.py's call: its own start as `started` (later than rank 0's write in a real launch) does not refuse a record of this launch
+    assert P.exchange_id(1, 2, None, path, timeout=5.0, started=time.time() + 5.0, began=now) == fresh
+
+
+def test_a_record_of_another_restart_count_is_not_taken(tmp_path, monkeypatch):
+    """torch.distributed.run --max-restarts respawns the ranks under the same launcher process and port: the record of the attempt
+    before (fresh by every clock) is not this attempt's.  Nor is one of another run id, or one written without a key."""
+    import montecarlopathtracing_amd.procs as P
+    path = str(tmp_path / "rdzv")
+    first, second = bytes(range(128)), bytes(range(128, 256))
+    monkeypatch.setenv("TORCHELASTIC_RUN_ID", "none")
+    monkeypatch.setenv("TORCHELASTIC_RESTART_COUNT", "0")
+    assert P.exchange_id(0, 2, lambda: first, path) == first
+    assert P.exchange_id(1, 2, None, path, timeout=5.0) == first
+    monkeypatch.setenv("TORCHELASTIC_RESTART_COUNT", "1")
+    with pytest.raises(TimeoutError):
+        P.exchange_id(1, 2, None, path, timeout=0.3)
+    t = _publish_later(path, 0.2, second)
+    try:
+        assert P.exchange_id(2, 3, None, path, timeout=30.0) == second
+    finally:
+        t.join()
+    monkeypatch.setenv("TORCHELASTIC_RUN_ID", "other")
+    with pytest.raises(TimeoutError):
+        P.exchange_id(1, 2, None, path, timeout=0.3)
+    monkeypatch.delenv("TORCHELASTIC_RUN_ID")
+    monkeypatch.delenv("TORCHELASTIC_RESTART_COUNT")
+    with pytest.raises(TimeoutError):
+        P.exchange_id(1, 2, None, path, timeout=0.3)                            # (a launcher without a key takes no keyed record)
+    P.exchange_id(0, 2, lambda: first, path)
+    monkeypatch.setenv("TORCHELASTIC_RESTART_COUNT", "0")
+    with pytest.raises(TimeoutError):
+        P.exchange_id(1, 2, None, path, timeout=0.3)                            # (nor a keyed one an unkeyed record)
+
+
+def test_the_stand_in_for_librccl_compiles_and_exports_its_entry_points(tmp_path):
+    """tests/fake_rccl.cpp (the collective library of tests/test_gpu_comm_gather.py) against the installed <rccl/rccl.h>: its definitions
+    are held to the header's declarations, so a signature that drifts fails here; it exports what csrc/proc_comm.cpp's comm_needs asks
+    for and ncclCommCount, nothing else; and csrc/rccl_loader.hpp binds no entry point by another name."""
+    import re
+    import fake_rccl
+    so = fake_rccl.build(tmp_path)
+    assert fake_rccl.exported(so) == sorted(fake_rccl.ENTRY_POINTS)
+    csrc = os.path.join(ROOT, "montecarlopathtracing_amd", "csrc")
+    needs = re.search(r"comm_needs = .*?return (.*?);", open(os.path.join(csrc, "proc_comm.cpp")).read(), flags=re.S).group(1)
+    asked = sorted("nccl" + n for n in re.findall(r"r\.(\w+)", needs))
+    assert asked == sorted(set(fake_rccl.ENTRY_POINTS) - {"ncclCommCount"}), asked
+    bound = set(re.findall(r'sym\("(nccl\w+)"\)', open(os.path.join(csrc, "rccl_loader.hpp")).read()))
+    assert set(fake_rccl.ENTRY_POINTS) <= bound
+
+
+def test_the_stand_in_keeps_its_contract_on_the_host_under_sanitizers(tmp_path):
+    """tests/fake_rccl.cpp with the HIP calls it makes defined as host operations (tests/fake_rccl_host_main.cpp), as a stand-alone program
+    under the address and undefined-behaviour sanitizers, the ranks as threads: groups of sends only against groups of receives only, two
+    ids side by side, a ring, count and type mismatches refused on both sides without a copy, every wait for a peer ending at its bound
+    (150 ms here) with an error, the all-reduce's barrier, and every event destroyed with its communicator."""
+    import shutil
+    import subprocess
+    cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    if cxx is None:
+        pytest.skip("no host C++ compiler")
+    import fake_rccl
+    exe = str(tmp_path / "fake_rccl_host")
+    subprocess.check_call([cxx, "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-Wall", "-Wextra", "-Werror",
+                           "-pthread", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(fake_rccl.ROCM, "include"), "-o", exe,
+                           os.path.join(ROOT, "tests", "fake_rccl.cpp"), os.path.join(ROOT, "tests", "fake_rccl_host_main.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stderr == "", out.stderr[-2000:]
+    assert out.stdout.startswith("ok ") and int(out.stdout.split()[1]) > 5000

@@ -51,7 +51,10 @@ Coverage: symbol | case | sizes | block constant the sizes come from
   mcpt_device_update_vertices_device    | test_update[refit], [rebuild]  | the scene's faces x 9 (input only)    | 256: build_kernels.hip
   mcpt_device_set_motion_device         | test_update[motion]            | the scene's faces x 9 (input only)    | 256: build_kernels.hip
   mcpt_multi_render_device              | test_multi_frame               | 64 x 36; *d_img is the handle's own, so it cannot be guarded: held to mcpt_multi_render | 256: wavefront.hip fold
-  mcpt_comm_gather_frame                | NOT COVERED here               | needs an RCCL communicator of several processes, one GPU each (tests/test_gpu_parity.py drives it through procs.py) | none
+  mcpt_comm_gather_frame                | test_gpu_comm_gather.py::test_pattern_frames | 33 x 17 and 1 x 1; worlds 2, 3, 5; tiles 32 x 8 and 5 x 3 (ranks as threads over tests/fake_rccl.cpp) | 256: kernels.hip k_pack_pixels, k_unpack_pixels
+
+mcpt_comm_gather_frame needs several ranks, which RCCL refuses on one GPU: its guarded cases live in tests/test_gpu_comm_gather.py, beside the
+stand-in for librccl they need (rank 0's payload to a restatement of the partition, the other ranks' frames to their inputs, all bands).
 
 112 cases; the whole file takes 2.0 s of wall time on an MI355X (pytest's own figure, devices and bakes included).
 """

@@ -1,7 +1,7 @@
 """tests/guarded.py without a GPU: the offset arithmetic of Guarded (where the payload sits, which bytes are the bands, what the message of a
 damaged band or a modified input says) against host memory standing in for the allocation -- the device sits behind guarded._alloc and
 guarded._copy, which are replaced here.  And the coverage table of tests/test_gpu_extents.py against include/mcpt.h: every entry point
-that takes a d_* argument has a row, so a new device form cannot arrive untested."""
+that takes a d_* argument has a row, none of them NOT COVERED, so a new device form cannot arrive untested."""
 import ctypes as C
 import os
 import re
@@ -135,5 +135,11 @@ def test_every_device_pointer_entry_point_has_a_row_in_the_extents_table():
     for s, row in rows.items():
         cols = [c.strip() for c in row.split("|")]
         assert len(cols) == 3 and all(cols), (s, row)       # the case, its sizes, the block constant
+        elsewhere = re.match(r"(test_gpu_\w+\.py)::(test_\w+)$", cols[0])
+        if elsewhere:                                       # a row that names a test of another file: the call is looked for there
+            other = open(os.path.join(ROOT, "tests", elsewhere.group(1))).read()
+            assert "def %s(" % elsewhere.group(2) in other and "lib.%s(" % s in other, "%s: no call in %s" % (s, elsewhere.group(1))
+            assert "pytestmark = pytest.mark.gpu" in other and "Guarded(" in other
         if not cols[0].startswith("NOT COVERED"):
             assert src.count(s) >= 2, "%s has a row but no call in the file" % s
+    assert not [s for s, row in rows.items() if "NOT COVERED" in row]
