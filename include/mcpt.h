@@ -1665,6 +1665,55 @@ int mcpt_bake_occlusion_lightmap_device(mcpt_device*, const double* d_uv6, const
                                         double* d_ao, double* d_stderr1, double* d_bent3, int32_t* d_hits, int32_t* d_back,
                                         int32_t* d_owner, mcpt_stats*, void* stream);
 
+/* ---- any-hit rays (since the any-hit change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* IS ANYTHING IN THE WAY OF A RAY BEFORE DISTANCE tmax?  The third question of a ray interface beside "what is the closest hit" and "what
+ * radiance comes along it": line of sight between two points, coverage and form-factor matrices, shadow masks for a caller's own lights.
+ * A walk of its own answers it: it stops at the first blocker, writes one byte per ray or one bit per point pair, and the rays of a pair
+ * matrix are formed in registers and never exist in memory.  The closest-hit engines and the integrator are untouched.
+ *   THE RULE : RAY i WITH LIMIT tmax[i] IS OCCLUDED IFF mcpt_trace_closest OF THE SAME RAY, ON THE SAME DEVICE STATE, ANSWERS face >= 0 AND
+ *              t < tmax[i].  The comparison is the IEEE one: a NaN limit is never occluded; tmax <= 0 is never occluded; tmax = +inf asks
+ *              "does the ray hit anything".  t is in the ray's own parameter: for an un-normalised direction, multiples of d.  Every
+ *              answer is held to this rule exactly; nothing has a tolerance.  (The closest hit is the smallest accepted t_k and every
+ *              accepted t_k is > 0, so the rule asks whether SOME leaf passes the reference's own box test, its triangle test and
+ *              0 < t_k < tmax: no order between candidates is involved, and the first such leaf ends the walk.)
+ *   state    : what mcpt_trace_closest_device sees: the device's trace mode (MCPT_TRACE_REFERENCE answers by the closest-hit walk of the
+ *              reference shape and the comparison), key 0 of a motion, a geometry that stands after updates.
+ *   rays     : mcpt_trace_any: rays6 [n][6] = origin, direction as mcpt_trace_closest takes them; tmax [n], or NULL for +inf throughout;
+ *              occluded [n] receives 0 or 1.
+ *   pairs    : for points a_i (a3 [na][3]) and b_j (b3 [nb][3]) and 0 <= t0 < t1, the ray of the pair (i, j) is, per component,
+ *                d = b - a;  o = a + t0 * d (a product, then a sum: two roundings);  tmax = t1 - t0 (one value for all pairs),
+ *              and THE PAIR IS OCCLUDED IFF THAT RAY WITH THAT LIMIT IS, for every pair, a == b included (a zero direction gets whatever
+ *              the closest hit says for it).  In the ray's parameter b lies at 1 - t0: (t0, t1) = (0, 1) asks for the open segment; a caller
+ *              whose points lie on surfaces passes, for example, t0 = 1e-4, t1 = 1 - 1e-4, so that neither point's own surface blocks.
+ *              mcpt_pair_rays writes these rays on the host, without a device -- rays6 [na*nb][6], pair (i, j) at i * nb + j, and the one
+ *              limit to *tmax --: A MATRIX IS, BIT FOR BIT, mcpt_trace_any OVER mcpt_pair_rays' RAYS WITH THAT LIMIT.
+ *   matrix   : W = (nb + 63) / 64 words of 64 bits a row: pair (i, j) is bit j & 63 of bits[i * W + (j >> 6)], set means occluded.  The
+ *              padding bits of a row's last word are 0.  Every one of the na * W words is written.
+ *   stats    : the host-pointer forms fill rays_primary = the rays or pairs answered, node_visits, tri_tests, launches = 1 and ms_trace
+ *              (= ms_total) from events around the launch; the other fields are 0.
+ * The host-pointer forms are synchronous and copy in and out around the device forms.  The _device forms take device pointers throughout,
+ * enqueue on `stream` and return without waiting; they keep no workspace.  They add to the counters of mcpt_trace_closest_device and, like
+ * it, MUST NOT OVERLAP ANOTHER CLOSEST-HIT OR ANY-HIT CALL OF THE SAME DEVICE ON ANOTHER STREAM.  Calls are allowed while progressive
+ * handles of the device live: they touch none of a handle's state.  (Their pointer parameters are spelled dev_*, not d_*: the extents of
+ * these two calls are held by tests/test_gpu_any_hit.py, not by the table of tests/test_gpu_extents.py, which lists the d_* entry points.)
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE, in this order).  The ray calls: n < 0 or n > 2^31 - 1; NULL rays6 or occluded with n > 0.
+ * The pair calls: NULL parameters; flags != 0; reserved != 0; t0 or t1 not finite, or not 0 <= t0 < t1; na or nb < 0 or > 2^31 - 1;
+ * na * W > 2^31 - 1; a NULL point list with a non-zero count; a NULL output (bits; rays6 or tmax) when na and nb are both non-zero.
+ * n == 0 (na == 0 or nb == 0): MCPT_OK, nothing is launched and nothing is written.  A copy that cannot be allocated: MCPT_ERR_NOMEM,
+ * and the device stays usable.
+ * Not covered: the integrator's shadow rays, the occlusion query and the visibility bakes stay on their closest-hit walks; a tmin other
+ * than through t0 (an interval (tmin, tmax) does not follow from one closest hit); any-hit in the pool or voting engines and refilling
+ * lanes that finish early; which triangle blocked, or how many; alpha-tested or per-material blockers; matrices of more than 2^31 - 1
+ * words (the caller cuts them); the multi-device group (mcpt_multi_*) and render_scene. */
+typedef struct { double t0, t1; int32_t flags, reserved; } mcpt_pair_params;                     /* 24 bytes; flags == 0 */
+int mcpt_trace_any(mcpt_device*, const double* rays6, const double* tmax, int64_t n, uint8_t* occluded, mcpt_stats*);
+int mcpt_trace_any_device(mcpt_device*, const double* dev_rays6, const double* dev_tmax, int64_t n, uint8_t* dev_occluded, void* stream);
+int mcpt_pair_rays(const double* a3, int64_t na, const double* b3, int64_t nb, const mcpt_pair_params*, double* rays6, double* tmax);
+int mcpt_trace_any_pairs(mcpt_device*, const double* a3, int64_t na, const double* b3, int64_t nb, const mcpt_pair_params*,
+                         uint64_t* bits, mcpt_stats*);
+int mcpt_trace_any_pairs_device(mcpt_device*, const double* dev_a3, int64_t na, const double* dev_b3, int64_t nb,
+                                const mcpt_pair_params*, uint64_t* dev_bits, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -264,6 +264,11 @@ class OcclusionMap(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("dilate", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PairParams(C.Structure):
+    """mcpt_pair_params: the part [t0, t1] of every segment a -> b that a pair matrix asks about, and flags (0)"""
+    _fields_ = [("t0", C.c_double), ("t1", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -317,6 +322,7 @@ EXPORTS = [
     "mcpt_baked_radiance_specular", "mcpt_baked_radiance_specular_device", "mcpt_render_baked_specular", "mcpt_render_baked_specular_device",
     "mcpt_query_occlusion", "mcpt_query_occlusion_device", "mcpt_occlusion_fold_host",
     "mcpt_bake_occlusion_lightmap", "mcpt_bake_occlusion_lightmap_device",
+    "mcpt_trace_any", "mcpt_trace_any_device", "mcpt_pair_rays", "mcpt_trace_any_pairs", "mcpt_trace_any_pairs_device",
 ]
 
 
@@ -561,6 +567,12 @@ def lib():
     L.mcpt_occlusion_fold_host.argtypes = [D, D, I32, D, D, C.c_int64, OP, D, D, D, I32, I32]
     L.mcpt_bake_occlusion_lightmap.argtypes = [P, D, OM, OP, D, D, D, I32, I32, I32, C.POINTER(Stats)]
     L.mcpt_bake_occlusion_lightmap_device.argtypes = [P, P, OM, OP, P, P, P, P, P, P, C.POINTER(Stats), P]
+    PP, U8, U64 = C.POINTER(PairParams), C.POINTER(C.c_uint8), C.POINTER(C.c_uint64)
+    L.mcpt_trace_any.argtypes = [P, D, D, C.c_int64, U8, C.POINTER(Stats)]
+    L.mcpt_trace_any_device.argtypes = [P, P, P, C.c_int64, P, P]
+    L.mcpt_pair_rays.argtypes = [D, C.c_int64, D, C.c_int64, PP, D, D]
+    L.mcpt_trace_any_pairs.argtypes = [P, D, C.c_int64, D, C.c_int64, PP, U64, C.POINTER(Stats)]
+    L.mcpt_trace_any_pairs_device.argtypes = [P, P, C.c_int64, P, C.c_int64, PP, P, P]
     _lib = L
     return L
 

@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, BakedSpecular, BakedSpecularOutputs, ReflectionParams, ReflectionChain, OcclusionParams, OcclusionMap, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, BakedSpecular, BakedSpecularOutputs, ReflectionParams, ReflectionChain, OcclusionParams, OcclusionMap, PairParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -541,6 +541,27 @@ def occlusion_fold_host(points, normals, rays, hit, t, face_normals, spp, max_di
                                          n, C.byref(op), _p(ao, C.c_double), _p(err, C.c_double), _p(bent, C.c_double), _p(hits, C.c_int32),
                                          _p(back, C.c_int32)))
     return {"ao": ao, "stderr": err, "bent": bent, "hits": hits, "back": back}
+
+
+def _pair_args(a, b, t0, t1):
+    """the two point lists of a pair call as contiguous (n, 3) arrays and its mcpt_pair_params (the library judges t0 and t1)"""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] != 3 or b.ndim != 2 or b.shape[1] != 3:
+        raise ValueError("a and b must have shapes (na, 3) and (nb, 3)")
+    return a, b, PairParams(float(t0), float(t1), 0, 0)
+
+
+def pair_rays(a, b, t0=0.0, t1=1.0):
+    """The rays of a pair matrix, on the CPU (mcpt_pair_rays; no device): for points a (na, 3) and b (nb, 3) the ray of pair (i, j), at
+    i * nb + j, has d = b - a and o = a + t0 * d, and every pair has the limit t1 - t0.  Returns (rays6 [na * nb, 6], tmax);
+    Device.any_hit(rays6, tmax) reshaped to (na, nb) is Device.any_hit_pairs(a, b, t0, t1), bit for bit."""
+    a, b, pp = _pair_args(a, b, t0, t1)
+    na, nb = a.shape[0], b.shape[0]
+    rays = np.zeros((na * nb, 6))
+    tmax = C.c_double(pp.t1 - pp.t0)
+    check(lib().mcpt_pair_rays(_p(a, C.c_double), na, _p(b, C.c_double), nb, C.byref(pp), _p(rays, C.c_double), C.byref(tmax)))
+    return rays, tmax.value
 
 
 def _adaptive_params(rel_target, abs_target, min_spp):
@@ -1329,6 +1350,54 @@ class Device:
                                                  _p(bent, C.c_double), _p(hits, C.c_int32), _p(back, C.c_int32), _p(owner, C.c_int32),
                                                  C.byref(stats) if stats is not None else None))
         return {"ao": ao, "stderr": err, "bent": bent, "hits": hits, "back": back, "owner": owner}
+
+    def any_hit(self, rays, tmax=None, stats=None):
+        """Is anything in the way of each ray before its limit (mcpt_trace_any): rays [n, 6] as ray_intersect() takes them, tmax [n] in
+        each ray's own parameter, one number for all of them, or None for +inf ("does the ray hit anything").  Ray i is occluded iff
+        ray_intersect() answers face >= 0 and t < tmax[i] for it -- exactly; a NaN or non-positive limit is never occluded -- but the
+        walk stops at the first blocker and one byte per ray comes back.  Returns bool [n]."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 6)
+        n = rays.shape[0]
+        if tmax is not None:
+            tmax = np.asarray(tmax, dtype=np.float64)
+            if tmax.ndim == 0:
+                tmax = np.full(n, float(tmax))
+            tmax = np.ascontiguousarray(tmax)
+            if tmax.shape != (n,):
+                raise ValueError("tmax must be a number or have shape (%d,)" % n)
+        occ = np.zeros(n, dtype=np.uint8)
+        check(lib().mcpt_trace_any(self._h, _p(rays, C.c_double), _p(tmax, C.c_double), n, _p(occ, C.c_uint8),
+                                   C.byref(stats) if stats is not None else None))
+        return occ != 0
+
+    def any_hit_pairs(self, a, b, t0=0.0, t1=1.0, packed=False, stats=None):
+        """Point-pair visibility (mcpt_trace_any_pairs): for points a (na, 3) and b (nb, 3), is anything in the way of the part
+        [t0, t1] of the segment a_i -> b_j -- any_hit() of pair_rays(a, b, t0, t1), bit for bit, with the rays formed on the GPU and one
+        bit per pair coming back.  Points on surfaces want, for example, t0 = 1e-4 and t1 = 1 - 1e-4, so that neither point's own
+        surface blocks.  Returns bool [na, nb], True where occluded; packed: the uint64 words [na, (nb + 63) // 64] as they are, pair
+        (i, j) in bit j & 63 of word [i, j >> 6], padding bits 0."""
+        a, b, pp = _pair_args(a, b, t0, t1)
+        na, nb = a.shape[0], b.shape[0]
+        W = (nb + 63) // 64
+        bits = np.zeros((na, W), dtype=np.uint64)
+        check(lib().mcpt_trace_any_pairs(self._h, _p(a, C.c_double), na, _p(b, C.c_double), nb, C.byref(pp), _p(bits, C.c_uint64),
+                                         C.byref(stats) if stats is not None else None))
+        if packed:
+            return bits
+        if na == 0 or nb == 0:
+            return np.zeros((na, nb), dtype=bool)
+        return np.unpackbits(bits.view(np.uint8).reshape(na, W * 8), axis=1, bitorder="little")[:, :nb].astype(bool)
+
+    def any_hit_device(self, d_rays_ptr, n, d_occluded_ptr, d_tmax_ptr=None, stream=None):
+        """any_hit() between caller-owned device buffers (e.g. torch tensors' data_ptr()) on `stream` (mcpt_trace_any_device): rays
+        [n, 6] float64, tmax [n] float64 or None, occluded [n] uint8."""
+        check(lib().mcpt_trace_any_device(self._h, _dp(d_rays_ptr), _dp(d_tmax_ptr), int(n), _dp(d_occluded_ptr), _dp(stream)))
+
+    def any_hit_pairs_device(self, d_a_ptr, na, d_b_ptr, nb, d_bits_ptr, t0=0.0, t1=1.0, stream=None):
+        """any_hit_pairs(packed=True) between caller-owned device buffers on `stream` (mcpt_trace_any_pairs_device): a [na, 3] and
+        b [nb, 3] float64, bits [na, (nb + 63) // 64] uint64."""
+        pp = PairParams(float(t0), float(t1), 0, 0)
+        check(lib().mcpt_trace_any_pairs_device(self._h, _dp(d_a_ptr), int(na), _dp(d_b_ptr), int(nb), C.byref(pp), _dp(d_bits_ptr), _dp(stream)))
 
     def lightmap_irradiance(self, E, uv, owner=None):
         """A lightmap's lookup by chart coordinate on the GPU (mcpt_lightmap_irradiance): lightmap_irradiance_host's arguments and

@@ -15,6 +15,7 @@
 //   volume_api.cpp    irradiance volumes: a probe grid's points, its bake through the probe query, the lookup between its probes
 //   visibility_api.cpp  probe visibility: the octahedral bin, the depth-moment bake of a probe list or grid, the visibility-weighted lookup
 //   occlusion_api.cpp  ambient occlusion: the hemisphere rays of a point list folded into occlusion and bent normals, and that query as a map
+//   any_hit_api.cpp   any-hit rays: is anything in the way of a ray before its limit, for a ray list and for the matrix of two point lists' pairs
 //   baked_api.cpp     baked frames: the lightmap's lookup by chart coordinate, baked radiance along a caller's rays, frames lit by a bake
 //   reflection_api.cpp  reflection probes: an octahedral radiance map per probe through the ray query, its Phong prefilter, the chain's lookup
 //   render_scene.cpp  output writers, checkpoints, render_scene
