@@ -475,7 +475,8 @@ int mcpt_device_set_environment(mcpt_device*, const mcpt_environment*);
 /* width = height = 0 when there is none; Z = 0 when it is inactive.  Any pointer may be NULL. */
 int mcpt_device_get_environment(const mcpt_device*, int32_t* width, int32_t* height, double* scale, double* Z);
 /* test seams: rgb[n*3] = Le(dirs[i]) under the device's environment; the draw of vertex `depth` of camera samples (pix[i], k[i]) ->
- * dirs[n*3], pdf[n], rgb[n*3] (the radiance of the drawn texel).  MCPT_ERR_ARG without an active environment. */
+ * dirs[n*3], pdf[n], rgb[n*3] (the radiance of the drawn texel).  MCPT_ERR_ARG without an active environment.  A copy that cannot be
+ * allocated: MCPT_ERR_NOMEM, and the device stays usable. */
 int mcpt_environment_eval(mcpt_device*, const double* dirs, int64_t n, double* rgb);
 int mcpt_environment_sample(mcpt_device*, uint64_t seed, const int32_t* pix, const int32_t* k, int32_t depth, int64_t n, double* dirs, double* pdf,
                             double* rgb);
@@ -535,7 +536,7 @@ int mcpt_device_get_light_sampling(const mcpt_device*, int32_t* mode, double* pd
  * MCPT_ERR_ARG: a scene without lights, bad weights. */
 int mcpt_scene_light_pick_table(const mcpt_scene*, const double* weights_or_null, double* cdf, double* pdf);
 /* test seam: the pick at vertex `depth` of camera samples (pix[i], k[i]) -> light[n], pdf[n].  MCPT_ERR_ARG unless the device picks
- * (MCPT_LIGHTS_ONE on a scene of two or more lights). */
+ * (MCPT_LIGHTS_ONE on a scene of two or more lights).  A copy that cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable. */
 int mcpt_light_pick(mcpt_device*, uint64_t seed, const int32_t* pix, const int32_t* k, int32_t depth, int64_t n, int32_t* light, double* pdf);
 /* host only (no GPU needed): the light tree of the scene under `weights` (NULL: the default weights), exactly as a device uploads it ->
  * *n_nodes (2 * num_lights - 1) and, unless NULL, nodes[*n_nodes] 64-byte records.  MCPT_ERR_ARG: fewer than two lights, bad weights. */
@@ -544,7 +545,8 @@ int mcpt_scene_light_tree(const mcpt_scene*, const double* weights_or_null, int3
  * tree with the same arithmetic as the device.  MCPT_ERR_ARG as above. */
 int mcpt_scene_light_tree_pdf(const mcpt_scene*, const double* weights_or_null, const double* p, const double* pn, int64_t n, double* pdf);
 /* test seam: the light the path kernels pick at the vertex (p[i], pn[i]) at `depth` of camera sample (pix[i], k[i]), and its probability
- * -> light[n], pdf[n].  MCPT_ERR_ARG unless the device picks by tree (MCPT_LIGHTS_TREE on a scene of two or more lights). */
+ * -> light[n], pdf[n].  MCPT_ERR_ARG unless the device picks by tree (MCPT_LIGHTS_TREE on a scene of two or more lights).  A copy that
+ * cannot be allocated: MCPT_ERR_NOMEM, and the device stays usable. */
 int mcpt_light_pick_at(mcpt_device*, uint64_t seed, const int32_t* pix, const int32_t* k, int32_t depth, const double* p, const double* pn, int64_t n,
                        int32_t* light, double* pdf);
 

@@ -46,28 +46,6 @@ static int any_gate(mcpt_device* d)
 
 static bool fast_walk(const mcpt_device* d) { return d->trace_mode == MCPT_TRACE_FAST && d->ds.fast.enabled != 0; }
 
-// The host forms around their launch: counters cleared and events recorded on the device's stream, then the copies back and the statistics.
-template <class Launch>
-static int host_form(mcpt_device* d, Staging& S, uint64_t answered, mcpt_stats* stats, Launch launch)
-{
-    hipStream_t st = d->stream.get();
-    HIP_TRY(hipMemsetAsync(d->aux_ctr.get(), 0, sizeof(DCounters), st));
-    HIP_TRY(hipEventRecord(d->ev[0].get(), st));
-    launch(st);
-    const int launched = launch_result();
-    if (launched == MCPT_OK) HIP_TRY(hipEventRecord(d->ev[1].get(), st));
-    if (const int rc = S.finish(launched)) return rc;
-    if (!stats) return MCPT_OK;
-    DCounters c{};
-    HIP_TRY(hipMemcpy(&c, d->aux_ctr.get(), sizeof c, hipMemcpyDeviceToHost));
-    counters_to_stats(c, stats, d->knobs.print_diag != 0);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, d->ev[0].get(), d->ev[1].get());
-    stats->rays_primary = answered;
-    stats->ms_trace = ms; stats->ms_total = ms; stats->launches = 1;
-    return MCPT_OK;
-}
-
 extern "C" {
 
 int mcpt_trace_any_device(mcpt_device* d, const double* d_rays6, const double* d_tmax, int64_t n, uint8_t* d_occluded, void* stream)
@@ -92,7 +70,7 @@ int mcpt_trace_any(mcpt_device* d, const double* rays6, const double* tmax, int6
     if (const int rc = S.in(rays6, sn * 6, "the rays", d_rays)) return rc;
     if (const int rc = S.in(tmax, sn, "the rays' limits", d_tmax)) return rc;
     if (const int rc = S.out(occluded, sn, "the rays' answers", d_occ)) return rc;
-    return host_form(d, S, uint64_t(n), stats, [&](hipStream_t st) {
+    return host_form(d, S, n, stats, [&](hipStream_t st) {
         launch_any_rays(d->ds, fast_walk(d), d_rays, d_tmax, n, d_occ, d->aux_ctr.get(), d->cfg.cus, st);
     });
 }
@@ -135,7 +113,7 @@ int mcpt_trace_any_pairs(mcpt_device* d, const double* a3, int64_t na, const dou
     if (const int rc = S.in(a3, size_t(na) * 3, "the first points", d_a)) return rc;
     if (const int rc = S.in(b3, size_t(nb) * 3, "the second points", d_b)) return rc;
     if (const int rc = S.out(bits, size_t(na * pair_row_words(nb)), "the pair matrix", d_bits)) return rc;
-    return host_form(d, S, uint64_t(na) * uint64_t(nb), stats, [&](hipStream_t st) {
+    return host_form(d, S, na * nb, stats, [&](hipStream_t st) {
         launch_any_pairs(d->ds, fast_walk(d), d_a, na, d_b, nb, p->t0, p->t1, reinterpret_cast<unsigned long long*>(d_bits), d->aux_ctr.get(), d->cfg.cus, st);
     });
 }

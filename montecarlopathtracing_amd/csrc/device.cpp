@@ -501,36 +501,21 @@ int mcpt_trace_closest(mcpt_device* d, const double* rays, int64_t n, int32_t* f
     if (const int rc = geometry_gate(d)) return rc;
     if (n == 0) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
-    DevBuf<double> d_rays, d_t, d_p, d_pn;
-    DevBuf<int32_t> d_face;
-    HIP_TRY(d_rays.alloc(size_t(n) * 6));
-    HIP_TRY(d_face.alloc(size_t(n)));
-    HIP_TRY(d_t.alloc(size_t(n)));
-    HIP_TRY(d_p.alloc(size_t(n) * 3));
-    HIP_TRY(d_pn.alloc(size_t(n) * 3));
-    hipStream_t st = d->stream.get();
-    // host buffers are pageable: blocking copies (the runtime stages them), ordered around the kernels by stream synchronisation
-    HIP_TRY(hipMemcpy(d_rays.get(), rays, size_t(n) * 6 * sizeof(double), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemsetAsync(d->aux_ctr.get(), 0, sizeof(DCounters), st));
-    HIP_TRY(hipEventRecord(d->ev[0].get(), st));
-    launch_trace_closest(d->ds, d->trace_mode == MCPT_TRACE_FAST, d_rays.get(), n, d_face.get(), d_t.get(), d_p.get(), d_pn.get(), d->aux_ctr.get(),
-                         d->aux_queue.get(), d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d->ev[1].get(), st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (face) HIP_TRY(hipMemcpy(face, d_face.get(), size_t(n) * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (t) HIP_TRY(hipMemcpy(t, d_t.get(), size_t(n) * sizeof(double), hipMemcpyDeviceToHost));
-    if (p) HIP_TRY(hipMemcpy(p, d_p.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    if (pn) HIP_TRY(hipMemcpy(pn, d_pn.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    DCounters c{};
-    HIP_TRY(hipMemcpy(&c, d->aux_ctr.get(), sizeof c, hipMemcpyDeviceToHost));
-    if (stats) {
-        counters_to_stats(c, stats, d->knobs.print_diag != 0);
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, d->ev[0].get(), d->ev[1].get());
-        stats->ms_trace = ms; stats->ms_total = ms; stats->launches = 1;
-    }
-    return MCPT_OK;
+    const size_t sn = size_t(n);
+    Staging S(d->stream.get());
+    const double* d_rays = nullptr;
+    int32_t* d_face = nullptr;
+    double *d_t = nullptr, *d_p = nullptr, *d_pn = nullptr;
+    // the launch requires d_face, d_t and d_p, so an absent one still gets room; d_pn may be null
+    if (const int rc = S.in(rays, sn * 6, "the rays", d_rays)) return rc;
+    if (const int rc = S.out(face, sn, "the rays' faces", d_face, Staging::kRoom)) return rc;
+    if (const int rc = S.out(t, sn, "the rays' distances", d_t, Staging::kRoom)) return rc;
+    if (const int rc = S.out(p, sn * 3, "the rays' hit points", d_p, Staging::kRoom)) return rc;
+    if (const int rc = S.out(pn, sn * 3, "the rays' normals", d_pn)) return rc;
+    return host_form(d, S, kNotReported, stats, [&](hipStream_t st) {
+        launch_trace_closest(d->ds, d->trace_mode == MCPT_TRACE_FAST, d_rays, n, d_face, d_t, d_p, d_pn, d->aux_ctr.get(), d->aux_queue.get(),
+                             d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
+    });
 }
 
 }  // extern "C"

@@ -100,15 +100,13 @@ int mcpt_environment_eval(mcpt_device* d, const double* dirs, int64_t n, double*
     if (!env_on(d->ds.env)) return fail(MCPT_ERR_ARG, "the device has no active environment");
     if (n == 0) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
-    DevBuf<double> d_dirs, d_rgb;
-    HIP_TRY(d_dirs.alloc(size_t(n) * 3));
-    HIP_TRY(d_rgb.alloc(size_t(n) * 3));
-    HIP_TRY(hipMemcpy(d_dirs.get(), dirs, size_t(n) * 3 * sizeof(double), hipMemcpyHostToDevice));
-    launch_env_eval(d->ds.env, d_dirs.get(), n, d_rgb.get(), d->stream.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(d->stream.get()));
-    HIP_TRY(hipMemcpy(rgb, d_rgb.get(), size_t(n) * 3 * sizeof(double), hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    Staging S(d->stream.get());
+    const double* d_dirs = nullptr;
+    double* d_rgb = nullptr;
+    if (const int rc = S.in(dirs, size_t(n) * 3, "the directions", d_dirs)) return rc;
+    if (const int rc = S.out(rgb, size_t(n) * 3, "the directions' radiance", d_rgb)) return rc;
+    launch_env_eval(d->ds.env, d_dirs, n, d_rgb, d->stream.get());
+    return S.finish(launch_result());
 }
 
 int mcpt_environment_sample(mcpt_device* d, uint64_t seed, const int32_t* pix, const int32_t* k, int32_t depth, int64_t n, double* dirs, double* pdf,
@@ -120,18 +118,15 @@ int mcpt_environment_sample(mcpt_device* d, uint64_t seed, const int32_t* pix, c
     if (!env_on(d->ds.env)) return fail(MCPT_ERR_ARG, "the device has no active environment");
     if (n == 0) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
-    DevBuf<int32_t> d_pix, d_k;
-    DevBuf<double> d_out;
-    HIP_TRY(d_pix.alloc(size_t(n)));
-    HIP_TRY(d_k.alloc(size_t(n)));
-    HIP_TRY(d_out.alloc(size_t(n) * 7));
-    HIP_TRY(hipMemcpy(d_pix.get(), pix, size_t(n) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_k.get(), k, size_t(n) * 4, hipMemcpyHostToDevice));
-    launch_env_sample(d->ds.env, seed, d_pix.get(), d_k.get(), depth, d->ds.num_lights, n, d_out.get(), d->stream.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(d->stream.get()));
-    std::vector<double> o(size_t(n) * 7);
-    HIP_TRY(hipMemcpy(o.data(), d_out.get(), o.size() * sizeof(double), hipMemcpyDeviceToHost));
+    std::vector<double> o(size_t(n) * 7);                   // the kernel's rows: direction, probability, radiance
+    Staging S(d->stream.get());
+    const int32_t *d_pix = nullptr, *d_k = nullptr;
+    double* d_out = nullptr;
+    if (const int rc = S.in(pix, size_t(n), "the pixels", d_pix)) return rc;
+    if (const int rc = S.in(k, size_t(n), "the samples", d_k)) return rc;
+    if (const int rc = S.out(o.data(), o.size(), "the samples' rows", d_out)) return rc;
+    launch_env_sample(d->ds.env, seed, d_pix, d_k, depth, d->ds.num_lights, n, d_out, d->stream.get());
+    if (const int rc = S.finish(launch_result())) return rc;
     for (int64_t i = 0; i < n; i++) {
         const double* r = &o[size_t(i) * 7];
         dirs[i * 3] = r[0]; dirs[i * 3 + 1] = r[1]; dirs[i * 3 + 2] = r[2];

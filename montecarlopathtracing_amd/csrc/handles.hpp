@@ -22,7 +22,8 @@
 //   staging.cpp       what the query family's files share (staging.hpp): the device gate, the allocation mapping, a host-pointer call's
 //                     device copies, the lease of a per-device workspace; chunks.hpp: how a workspace budget cuts a list into chunks
 //   hit_work.cpp      what the closest-hit chunk loops share (hit_work.hpp): the workspace of a chunk's rays and hits, the closest-hit
-//                     launch, the loop and its statistics (visibility, occlusion, baked radiance and frames)
+//                     launch, the loop and its statistics (visibility, occlusion, baked radiance and frames); the host form of a trace
+//                     call around its launch (mcpt_trace_closest, mcpt_trace_any, mcpt_trace_any_pairs)
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -422,10 +423,6 @@ int lens_check(const mcpt_lens* l);
 int ensure_dirs(mcpt_device* d, hipStream_t st);    // the primary directions, made on first use
 int ensure_pos(mcpt_device* d, hipStream_t st);     // the image-plane points camera_ray starts from (d->pos), made on first use
 mcpt::DLens lens_for(const mcpt_device* d, const mcpt_lens& l);   // lens l on d's camera as the kernels read it (after ensure_pos)
-// Runs run(d_img, d_img2) on device copies of the caller's pageable host frames (`bytes` each; a null frame stays null): each is copied
-// in first, so that pixels the call does not write keep the caller's values, and out again on success.  The stream is synchronised
-// in between, on failure as well: nothing enqueued may still use a copy when it goes.
-int with_device_frames(hipStream_t st, size_t bytes, double* img, double* img2, const std::function<int(double*, double*)>& run);
 
 // Which camera samples of every owned pixel a render call covers and where they are folded.  A frame: samples [0, N) through
 // k_fold_samples (mom == null).  A progressive pass (mcpt_progressive_step): samples [k0, k0 + n) of a frame of N through

@@ -25,6 +25,33 @@ void trace_leaf(mcpt_device* d, const double* d_rays6, long long n, int32_t* d_l
                               d->aux_slow_list.get(), d->slow_cap, st, d->cfg);
 }
 
+int host_form_begin(mcpt_device* d, hipStream_t& st)
+{
+    st = d->stream.get();
+    HIP_TRY(hipMemsetAsync(d->aux_ctr.get(), 0, sizeof(DCounters), st));
+    HIP_TRY(hipEventRecord(d->ev[0].get(), st));
+    return MCPT_OK;
+}
+
+int host_form_end(mcpt_device* d, Staging& S, int64_t answered, mcpt_stats* stats)
+{
+    int launched = launch_result();
+    if (launched == MCPT_OK) {
+        const hipError_t e = hipEventRecord(d->ev[1].get(), d->stream.get());
+        if (e != hipSuccess) launched = fail(MCPT_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(e));
+    }
+    if (const int rc = S.finish(launched)) return rc;          // (the stream is waited for whatever came of the launch)
+    if (!stats) return MCPT_OK;
+    DCounters c{};
+    HIP_TRY(hipMemcpy(&c, d->aux_ctr.get(), sizeof c, hipMemcpyDeviceToHost));
+    counters_to_stats(c, stats, d->knobs.print_diag != 0);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, d->ev[0].get(), d->ev[1].get());
+    if (answered != kNotReported) stats->rays_primary = uint64_t(answered);
+    stats->ms_trace = ms; stats->ms_total = ms; stats->launches = 1;
+    return MCPT_OK;
+}
+
 int chunk_stats(mcpt_stats* stats, int64_t n, int64_t rays_per_item, int chunks, hipStream_t st)
 {
     if (!stats) return MCPT_OK;

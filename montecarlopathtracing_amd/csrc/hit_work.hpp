@@ -39,4 +39,20 @@ int chunk_run(int64_t n, int64_t per_chunk, int64_t rays_per_item, Lease& l, mcp
     return chunk_stats(stats, n, rays_per_item, chunks, st);
 }
 
+// The host form of a trace call (mcpt_trace_closest, mcpt_trace_any, mcpt_trace_any_pairs) around its launch on the device's own stream:
+// the auxiliary counters cleared and the first event recorded (host_form_begin hands the stream back), launch(st), then the second event,
+// S.finish and, where asked for, the statistics of one launch (host_form_end).  answered: what rays_primary reports; kNotReported: it is
+// left as it was.
+constexpr int64_t kNotReported = -1;
+int host_form_begin(mcpt_device* d, hipStream_t& st);
+int host_form_end(mcpt_device* d, Staging& S, int64_t answered, mcpt_stats* stats);
+template <class Launch>
+int host_form(mcpt_device* d, Staging& S, int64_t answered, mcpt_stats* stats, Launch launch)
+{
+    hipStream_t st = nullptr;
+    if (const int rc = host_form_begin(d, st)) return rc;
+    launch(st);
+    return host_form_end(d, S, answered, stats);
+}
+
 #pragma GCC visibility pop

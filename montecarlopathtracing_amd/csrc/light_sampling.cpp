@@ -286,16 +286,14 @@ int mcpt_light_pick(mcpt_device* d, uint64_t seed, const int32_t* pix, const int
     if (tree_on(d->ds.pick)) return fail(MCPT_ERR_ARG, "under MCPT_LIGHTS_TREE the pick depends on the vertex: mcpt_light_pick_at");
     if (n == 0) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
-    DevBuf<int32_t> d_pix, d_k, d_light;
-    HIP_TRY(d_pix.alloc(size_t(n)));
-    HIP_TRY(d_k.alloc(size_t(n)));
-    HIP_TRY(d_light.alloc(size_t(n)));
-    HIP_TRY(hipMemcpy(d_pix.get(), pix, size_t(n) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_k.get(), k, size_t(n) * 4, hipMemcpyHostToDevice));
-    launch_light_pick(d->ds, seed, d_pix.get(), d_k.get(), depth, n, d_light.get(), d->stream.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(d->stream.get()));
-    HIP_TRY(hipMemcpy(light, d_light.get(), size_t(n) * 4, hipMemcpyDeviceToHost));
+    Staging S(d->stream.get());
+    const int32_t *d_pix = nullptr, *d_k = nullptr;
+    int32_t* d_light = nullptr;
+    if (const int rc = S.in(pix, size_t(n), "the pixels", d_pix)) return rc;
+    if (const int rc = S.in(k, size_t(n), "the samples", d_k)) return rc;
+    if (const int rc = S.out(light, size_t(n), "the picked lights", d_light)) return rc;
+    launch_light_pick(d->ds, seed, d_pix, d_k, depth, n, d_light, d->stream.get());
+    if (const int rc = S.finish(launch_result())) return rc;
     for (int64_t i = 0; i < n; i++) pdf[i] = d->pick->pdf[size_t(light[i])];
     return MCPT_OK;
 }
@@ -309,24 +307,19 @@ int mcpt_light_pick_at(mcpt_device* d, uint64_t seed, const int32_t* pix, const 
     if (!tree_on(d->ds.pick)) return fail(MCPT_ERR_ARG, "the device does not pick lights by tree (MCPT_LIGHTS_TREE on a scene of two or more lights)");
     if (n == 0) return MCPT_OK;
     HIP_TRY(hipSetDevice(d->ordinal));
-    DevBuf<int32_t> d_pix, d_k, d_light;
-    DevBuf<double> d_p, d_pn, d_pdf;
-    HIP_TRY(d_pix.alloc(size_t(n)));
-    HIP_TRY(d_k.alloc(size_t(n)));
-    HIP_TRY(d_light.alloc(size_t(n)));
-    HIP_TRY(d_p.alloc(size_t(n) * 3));
-    HIP_TRY(d_pn.alloc(size_t(n) * 3));
-    HIP_TRY(d_pdf.alloc(size_t(n)));
-    HIP_TRY(hipMemcpy(d_pix.get(), pix, size_t(n) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_k.get(), k, size_t(n) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_p.get(), p, size_t(n) * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_pn.get(), pn, size_t(n) * 24, hipMemcpyHostToDevice));
-    launch_light_pick_at(d->ds, seed, d_pix.get(), d_k.get(), depth, d_p.get(), d_pn.get(), n, d_light.get(), d_pdf.get(), d->stream.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(d->stream.get()));
-    HIP_TRY(hipMemcpy(light, d_light.get(), size_t(n) * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(pdf, d_pdf.get(), size_t(n) * 8, hipMemcpyDeviceToHost));
-    return MCPT_OK;
+    Staging S(d->stream.get());
+    const int32_t *d_pix = nullptr, *d_k = nullptr;
+    const double *d_p = nullptr, *d_pn = nullptr;
+    int32_t* d_light = nullptr;
+    double* d_pdf = nullptr;
+    if (const int rc = S.in(pix, size_t(n), "the pixels", d_pix)) return rc;
+    if (const int rc = S.in(k, size_t(n), "the samples", d_k)) return rc;
+    if (const int rc = S.in(p, size_t(n) * 3, "the vertices", d_p)) return rc;
+    if (const int rc = S.in(pn, size_t(n) * 3, "the vertices' normals", d_pn)) return rc;
+    if (const int rc = S.out(light, size_t(n), "the picked lights", d_light)) return rc;
+    if (const int rc = S.out(pdf, size_t(n), "the picks' probabilities", d_pdf)) return rc;
+    launch_light_pick_at(d->ds, seed, d_pix, d_k, depth, d_p, d_pn, n, d_light, d_pdf, d->stream.get());
+    return S.finish(launch_result());
 }
 
 }  // extern "C"

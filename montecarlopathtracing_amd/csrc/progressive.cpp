@@ -270,9 +270,13 @@ int mcpt_progressive_image(mcpt_progressive* h, double* img, double* stderr_img)
 {
     if (!h || (!img && !stderr_img)) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->d->ordinal));
-    // pageable host buffers: blocking copies either side; pixels this rank does not own keep the caller's values
-    return with_device_frames(h->d->stream.get(), size_t(h->d->width) * h->d->height * 3 * sizeof(double), img, stderr_img,
-                              [&](double* d_est, double* d_err) { return mcpt_progressive_image_device(h, d_est, d_err, h->d->stream.get()); });
+    // pixels this rank does not own keep the caller's values
+    Staging S(h->d->stream.get());
+    const size_t words = size_t(h->d->width) * h->d->height * 3;
+    double *d_est = nullptr, *d_err = nullptr;
+    if (const int rc = S.inout(img, words, "the image", d_est)) return rc;
+    if (const int rc = S.inout(stderr_img, words, "the standard errors", d_err)) return rc;
+    return S.finish(mcpt_progressive_image_device(h, d_est, d_err, h->d->stream.get()));
 }
 
 // First-hit AOVs of the owned pixels: the primary hits of the owned list traced again on the device's stream and closest-hit workspace
@@ -376,9 +380,11 @@ int mcpt_progressive_denoise(mcpt_progressive* h, const mcpt_denoise_params* dp,
     if (rc) return rc;
     if (!img) return fail(MCPT_ERR_ARG, "null image");
     HIP_TRY(hipSetDevice(h->d->ordinal));
-    // pageable host buffer: blocking copies either side; pixels this rank does not own keep the caller's values
-    return with_device_frames(h->d->stream.get(), size_t(h->d->width) * h->d->height * 3 * sizeof(double), img, nullptr,
-                              [&](double* d_out, double*) { return mcpt_progressive_denoise_device(h, dp, d_out, h->d->stream.get()); });
+    // pixels this rank does not own keep the caller's values
+    Staging S(h->d->stream.get());
+    double* d_out = nullptr;
+    if ((rc = S.inout(img, size_t(h->d->width) * h->d->height * 3, "the image", d_out))) return rc;
+    return S.finish(mcpt_progressive_denoise_device(h, dp, d_out, h->d->stream.get()));
 }
 
 // ---- sample AOVs and the filter they guide (mcpt.h: mcpt_progressive_sample_aovs, mcpt_progressive_denoise_guided)
@@ -498,9 +504,11 @@ int mcpt_progressive_denoise_guided(mcpt_progressive* h, const mcpt_denoise_para
     if (rc) return rc;
     if (!img) return fail(MCPT_ERR_ARG, "null image");
     HIP_TRY(hipSetDevice(h->d->ordinal));
-    // pageable host buffer: blocking copies either side; pixels this rank does not own keep the caller's values
-    return with_device_frames(h->d->stream.get(), size_t(h->d->width) * h->d->height * 3 * sizeof(double), img, nullptr,
-                              [&](double* d_out, double*) { return mcpt_progressive_denoise_guided_device(h, dp, gp, d_out, h->d->stream.get()); });
+    // pixels this rank does not own keep the caller's values
+    Staging S(h->d->stream.get());
+    double* d_out = nullptr;
+    if ((rc = S.inout(img, size_t(h->d->width) * h->d->height * 3, "the image", d_out))) return rc;
+    return S.finish(mcpt_progressive_denoise_guided_device(h, dp, gp, d_out, h->d->stream.get()));
 }
 
 // ---- the picture of the frame (mcpt.h: display transform): the source frame into the handle's scratch, then histogram and map over the
@@ -535,17 +543,12 @@ int mcpt_progressive_display(mcpt_progressive* h, int32_t source, const mcpt_dis
     if (const int rc = display_check(p)) return rc;
     if (!h || !rgb8) return fail(MCPT_ERR_ARG, "null argument");
     HIP_TRY(hipSetDevice(h->d->ordinal));
-    // pageable host buffer: blocking copies either side; pixels this rank does not own keep the caller's bytes
+    // pixels this rank does not own keep the caller's bytes
     const size_t bytes = size_t(h->d->width) * h->d->height * ((p && (p->flags & MCPT_DISPLAY_RGBA)) ? 4 : 3);
-    DevBuf<uint8_t> d_out;
-    HIP_TRY(d_out.alloc_bytes(std::max<size_t>(bytes, 16)));
-    HIP_TRY(hipMemcpy(d_out.get(), rgb8, bytes, hipMemcpyHostToDevice));
-    hipStream_t st = h->d->stream.get();
-    int rc = mcpt_progressive_display_device(h, source, p, d_out.get(), info, st);
-    const hipError_t e = hipStreamSynchronize(st);        // also on failure: nothing enqueued may still use the copy when it goes
-    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    if (rc == MCPT_OK) HIP_TRY(hipMemcpy(rgb8, d_out.get(), bytes, hipMemcpyDeviceToHost));
-    return rc;
+    Staging S(h->d->stream.get());
+    uint8_t* d_out = nullptr;
+    if (const int rc = S.inout(rgb8, bytes, "the picture", d_out)) return rc;
+    return S.finish(mcpt_progressive_display_device(h, source, p, d_out, info, h->d->stream.get()));
 }
 
 int mcpt_progressive_next_pass(int32_t spp, int32_t done, double remaining_s, double s_per_sample)

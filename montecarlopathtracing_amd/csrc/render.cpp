@@ -7,7 +7,6 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <vector>
 
@@ -63,24 +62,6 @@ DLens lens_for(const mcpt_device* d, const mcpt_lens& l)
     c.focus_scale = F / len;
     c.flags = l.flags;
     return c;
-}
-
-int with_device_frames(hipStream_t st, size_t bytes, double* img, double* img2, const std::function<int(double*, double*)>& run)
-{
-    double* const host[2] = {img, img2};
-    DevBuf<double> dev[2];
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; i++)
-        if (host[i]) {
-            e = dev[i].alloc_bytes(bytes);
-            if (e == hipSuccess) e = hipMemcpy(dev[i].get(), host[i], bytes, hipMemcpyHostToDevice);
-        }
-    int rc = e == hipSuccess ? run(dev[0].get(), dev[1].get()) : fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    e = hipStreamSynchronize(st);           // also on failure: nothing of the call may still use a copy when it goes
-    for (int i = 0; i < 2 && rc == MCPT_OK && e == hipSuccess; i++)
-        if (host[i]) e = hipMemcpy(host[i], dev[i].get(), bytes, hipMemcpyDeviceToHost);
-    if (rc == MCPT_OK && e != hipSuccess) rc = fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    return rc;
 }
 
 // the next unused start/stop pair of a pool, created on first use
@@ -407,23 +388,15 @@ static int pair_call(mcpt_device* d, const int32_t* pix, const int32_t* k, int64
         if (pix[i] < 0 || pix[i] >= d->width * d->height) return fail(MCPT_ERR_ARG, "pixel index out of range");
     HIP_TRY(hipSetDevice(d->ordinal));
     hipStream_t st = d->stream.get();
-    int rc = prepare(d, st);
-    if (rc) return rc;
-    DevBuf<int32_t> d_pix, d_k;
-    DevBuf<double> d_out;
-    hipError_t e = d_pix.alloc(size_t(n));
-    if (e == hipSuccess) e = d_k.alloc(size_t(n));
-    if (e == hipSuccess) e = d_out.alloc(size_t(n) * per);
-    if (e == hipSuccess) e = hipMemcpy(d_pix.get(), pix, size_t(n) * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d_k.get(), k, size_t(n) * 4, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        if ((rc = launch(d_pix.get(), d_k.get(), d_out.get(), st))) return rc;
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipMemcpy(out, d_out.get(), size_t(n) * per * sizeof(double), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return fail(MCPT_ERR_HIP, hipGetErrorString(e));
-    return MCPT_OK;
+    if (const int rc = prepare(d, st)) return rc;
+    Staging S(st);
+    const int32_t *d_pix = nullptr, *d_k = nullptr;
+    double* d_out = nullptr;
+    if (const int rc = S.in(pix, size_t(n), "the pixels", d_pix)) return rc;
+    if (const int rc = S.in(k, size_t(n), "the samples", d_k)) return rc;
+    if (const int rc = S.out(out, size_t(n) * per, "the pairs' answers", d_out)) return rc;
+    const int rc = launch(d_pix, d_k, d_out, st);
+    return S.finish(rc == MCPT_OK ? launch_result() : rc);
 }
 
 // The shutter frame of a device with a motion (mcpt.h: motion blur): the frame's samples in the shutter's steps, each piece a progressive
@@ -518,9 +491,11 @@ int mcpt_render(mcpt_device* d, const mcpt_render_params* p, double* img, mcpt_s
 {
     if (!d || !p || !img) return fail(MCPT_ERR_ARG, "bad argument");
     HIP_TRY(hipSetDevice(d->ordinal));
-    // The caller's frame is pageable host memory: blocking copies on either side of the frame, which itself is ordered on d->stream.
-    return with_device_frames(d->stream.get(), size_t(d->width) * d->height * 3 * sizeof(double), img, nullptr,
-                              [&](double* d_img, double*) { return mcpt_render_device(d, p, d_img, stats, d->stream.get()); });
+    // The caller's frame goes in and comes back: pixels this rank does not own keep the caller's values.
+    Staging S(d->stream.get());
+    double* d_img = nullptr;
+    if (const int rc = S.inout(img, size_t(d->width) * d->height * 3, "the frame", d_img)) return rc;
+    return S.finish(mcpt_render_device(d, p, d_img, stats, d->stream.get()));
 }
 
 int mcpt_sample_radiance(mcpt_device* d, uint64_t seed, const int32_t* pix, const int32_t* k, int64_t n, double* rgb)

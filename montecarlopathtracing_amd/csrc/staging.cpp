@@ -36,11 +36,12 @@ int launch_result()
     return e == hipSuccess ? MCPT_OK : fail(MCPT_ERR_HIP, hipGetErrorString(e));
 }
 
-// one array of the call: src (in) is copied to the device now, dst (out) is remembered for finish(); neither: the array is absent
-int Staging::add(const void* src, void* dst, size_t bytes, const char* what, void*& dev)
+// one array of the call: src (in) is copied to the device now, dst (out) is remembered for finish(), both: an in-out array; neither: the
+// array is absent, and gets device room only where `room` asks for it
+int Staging::add(const void* src, void* dst, size_t bytes, const char* what, void*& dev, bool room)
 {
     dev = nullptr;
-    if (!src && !dst) return MCPT_OK;
+    if (!src && !dst && !room) return MCPT_OK;
     DevBuf<char> b;
     if (const int rc = alloc_result(b.alloc(bytes), what, bytes)) return rc;
     dev = b.get();

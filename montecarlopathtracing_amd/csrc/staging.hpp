@@ -49,22 +49,34 @@ public:
         dev = static_cast<T*>(p);
         return rc;
     }
-    // dev = device room for host[0 .. count), which finish() fills from it; a null host leaves dev null
+    // what a null host gets of out(): a null dev, or device room all the same (the launch requires the array), which nobody reads back
+    enum Absent { kNull, kRoom };
+    // dev = device room for host[0 .. count), which finish() fills from it; a null host leaves dev null, or as `absent` says
     template <class T>
-    int out(T* host, size_t count, const char* what, T*& dev)
+    int out(T* host, size_t count, const char* what, T*& dev, Absent absent = kNull)
     {
         void* p = nullptr;
-        const int rc = add(nullptr, host, count * sizeof(T), what, p);
+        const int rc = add(nullptr, host, count * sizeof(T), what, p, absent == kRoom);
+        dev = static_cast<T*>(p);
+        return rc;
+    }
+    // dev = a device copy of host[0 .. count), filled now and copied back by finish() among the out() arrays: what the kernels do not
+    // write comes back as the caller's own bytes; a null host leaves dev null
+    template <class T>
+    int inout(T* host, size_t count, const char* what, T*& dev)
+    {
+        void* p = nullptr;
+        const int rc = add(host, host, count * sizeof(T), what, p);
         dev = static_cast<T*>(p);
         return rc;
     }
     // The end of the call, rc the device form's result: the stream is waited for, on failure as well -- nothing enqueued may still use a
-    // copy when it goes -- and when all is well every out() array is copied back, in the order of the out() calls.
+    // copy when it goes -- and when all is well every out() and inout() array is copied back, in the order of those calls.
     int finish(int rc);
 
 private:
     struct Copy { mcpt::DevBuf<char> dev; void* host; size_t bytes; };      // host: where finish() copies it back to, or null
-    int add(const void* src, void* dst, size_t bytes, const char* what, void*& dev);
+    int add(const void* src, void* dst, size_t bytes, const char* what, void*& dev, bool room = false);
     hipStream_t st_;
     std::vector<Copy> copies_;
 };
