@@ -16,6 +16,7 @@
 // Every other ray takes trace_closest().  The walk itself is in trace_persistent.hpp (per-lane stack: 32 entries in LDS).
 #pragma once
 #include "dev_common.hpp"
+#include "pre_test.hpp"
 
 namespace mcpt {
 
@@ -193,7 +194,7 @@ __device__ __forceinline__ double fast_rcp(double x)
 // Distance: t* = tq/det is the true parameter of the plane hit; a triangle is skipped when t* < -margin (the reference's t_k is then
 // negative: not a candidate) or t* > limit (it cannot beat the leader) -- the same margin and limit, with the same meaning, as the
 // box culling of cw_step.
-struct PreRay { float o[3], d[3], dm, eta4, margin; };
+// (PreRay, PreRec and the arithmetic itself: pre_test.hpp, which the host compiler reads too)
 __device__ __forceinline__ PreRay make_pre_ray(const DFast& F, const Ray& r, const float of[3], float margin_ru)
 {
     PreRay q;
@@ -208,31 +209,16 @@ __device__ __forceinline__ PreRay make_pre_ray(const DFast& F, const Ray& r, con
     q.margin = margin_ru;
     return q;
 }
-__device__ __forceinline__ bool tri_pre_reject(const DTriPre* __restrict__ q, const PreRay& R, float limit_f, float* dbg = nullptr)
+// A triangle's record: three 16-byte loads (all of a round's are requested before any is used: leaf_survivors).
+__device__ __forceinline__ PreRec load_pre_rec(const DTriPre* __restrict__ q)
 {
     const float4* w = reinterpret_cast<const float4*>(q);
     const float4 A = w[0], B = w[1], C = w[2];             // v0 a1 | e1 a2 | e2 -
-    const float a1 = A.w, a2 = B.w;
-    const float tx = R.o[0] - A.x, ty = R.o[1] - A.y, tz = R.o[2] - A.z;
-    const float px = fmaf(R.d[1], C.z, -(R.d[2] * C.y)), py = fmaf(R.d[2], C.x, -(R.d[0] * C.z)), pz = fmaf(R.d[0], C.y, -(R.d[1] * C.x));
-    const float det = fmaf(B.z, pz, fmaf(B.y, py, B.x * px));
-    const float u = fmaf(tz, pz, fmaf(ty, py, tx * px));
-    const float qx = fmaf(ty, B.z, -(tz * B.y)), qy = fmaf(tz, B.x, -(tx * B.z)), qz = fmaf(tx, B.y, -(ty * B.x));
-    const float v = fmaf(R.d[2], qz, fmaf(R.d[1], qy, R.d[0] * qx));
-    const float tq = fmaf(C.z, qz, fmaf(C.y, qy, C.x * qx));
-    const float T = fmaxf(fmaxf(fabsf(tx), fabsf(ty)), fabsf(tz));
-    const float base = fmaf(T, 0x1p-18f, R.eta4);
-    const float da1 = R.dm * a1, da2 = R.dm * a2;
-    const float Eu = da2 * base, Ev = da1 * base, X = da2 * a1, Etq = (a1 * a2) * base;
-    const float Dt = fabsf(det);
-    const bool neg = det < 0.0f;
-    const float U = neg ? -u : u, V = neg ? -v : v, TQ = neg ? -tq : tq;
-    const bool clear = Dt > 0x1p-9f * X;                    // (i); false as well when a1 = +inf or anything is NaN
-    bool rej = U < -Eu || V < -Ev || (U + V) - Dt > (Eu + Ev) + 0x1p-19f * X;
-    rej = rej || TQ + Etq < -((R.margin * Dt) * 1.002f) || TQ - Etq > (limit_f * Dt) * 1.002f;
-    if (dbg) { dbg[0] = U + Eu; dbg[1] = V + Ev; dbg[2] = ((Eu + Ev) + 0x1p-19f * X) - ((U + V) - Dt); dbg[3] = TQ + Etq + (R.margin * Dt) * 1.002f;
-               dbg[4] = (limit_f * Dt) * 1.002f - (TQ - Etq); dbg[5] = Dt - 0x1p-9f * X; dbg[6] = TQ / Dt; dbg[7] = Dt; }
-    return clear && rej;
+    return PreRec{{A.x, A.y, A.z}, A.w, {B.x, B.y, B.z}, B.w, {C.x, C.y, C.z}};
+}
+__device__ __forceinline__ bool tri_pre_reject(const DTriPre* __restrict__ q, const PreRay& R, float limit_f, float* dbg = nullptr)
+{
+    return pre_reject(load_pre_rec(q), R, limit_f, dbg);
 }
 
 struct CwHits { float key[4]; int ref[4]; };

@@ -93,17 +93,21 @@ __device__ __forceinline__ void defer_ray(TraceQueue* queue, long long* __restri
 }
 
 // A leaf's triangles [first, first + count) through the fp32 pre-test; bit k of the result: triangle first + k goes on to the exact test.
-// MCPT_PRE_UNROLL triangles per round: their records are requested together, so a round costs one memory latency.
+// MCPT_PRE_UNROLL triangles per round: their records are loaded into temporaries before any arithmetic on either, and the pre-test has no
+// branch (pre_test.hpp), so a round costs one memory latency.
 __device__ __forceinline__ unsigned int leaf_survivors(const DTriPre* __restrict__ pre, int first, int count, const PreRay& pr, float limit_f)
 {
     unsigned int surv = 0;
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
     for (int k0 = 0; k0 < count; k0 += MCPT_PRE_UNROLL) {
+        // (a slot past the leaf's last is a triangle of the next leaf or the array's padding: tested, not used)
+        PreRec rec[MCPT_PRE_UNROLL];
+#pragma unroll
+        for (int j = 0; j < MCPT_PRE_UNROLL; j++) rec[j] = load_pre_rec(pre + first + k0 + j);
 #pragma unroll
         for (int j = 0; j < MCPT_PRE_UNROLL; j++) {
             const int k = k0 + j;
-            // (a slot past the leaf's last is a triangle of the next leaf or the array's padding: tested, not used)
-            const bool rej = tri_pre_reject(pre + first + k, pr, limit_f);
+            const bool rej = pre_reject(rec[j], pr, limit_f);
             if (k < count && !rej) surv |= 1u << k;
         }
     }
