@@ -1716,6 +1716,114 @@ int mcpt_trace_any_pairs(mcpt_device*, const double* a3, int64_t na, const doubl
 int mcpt_trace_any_pairs_device(mcpt_device*, const double* dev_a3, int64_t na, const double* dev_b3, int64_t nb,
                                 const mcpt_pair_params*, uint64_t* dev_bits, void* stream);
 
+/* ---- direct light (since the direct-light change; MCPT_VERSION stays 105: detect the block by symbol) ---- */
+/* THE IRRADIANCE THAT A CALLER'S OWN LIGHTS SEND TO A LIST OF SURFACE POINTS, past the scene's geometry: point, spot, directional (sun)
+ * and rectangle lights that are not modelled as emitting triangles.  One fused kernel forms every shadow ray in registers, walks it with
+ * the any-hit walk and folds irradiance, its standard error, irradiance by light and a shadow mask by light per receiver; no ray exists in
+ * memory.  A map is that query over a lightmap's texel list.  The closest-hit engines, the integrator and the any-hit kernels are
+ * untouched.  fp64, no contraction, IEEE division and sqrt, every expression and sum in the order written; only + - * / and sqrt enter.
+ *   THE RULE : A DIRECT-LIGHT ANSWER IS, BIT FOR BIT, mcpt_direct_fold_host OVER mcpt_trace_any'S ANSWERS TO THE RAYS AND LIMITS THAT
+ *              mcpt_direct_rays (the test seam) WRITES FOR THE SAME LIST, LIGHTS AND PARAMETERS, on the same device state.
+ *   receiver : entry i of q6 = (position a, normal b of any non-zero finite length), ids[i] or i: MCPT_QUERY_HEMISPHERE's list, ids and
+ *              refusals; n^ = b / sqrt((bx bx + by by) + bz bz), that kind's n^.
+ *   toward y : for a point y (a light's position, or a sample on a rectangle): L = y - a; r2 = (Lx Lx + Ly Ly) + Lz Lz; the slot is
+ *              SKIPPED unless r2 is finite and > 0; r = sqrt(r2); w = L / r per component; cr = (n^x wx + n^y wy) + n^z wz; SKIPPED unless
+ *              cr > 0.
+ *   ray      : o = a + w * bias per component (a product, then a sum), d = w, tmax = r - bias.  THE SLOT IS OCCLUDED EXACTLY WHEN
+ *              mcpt_trace_any'S RULE SAYS SO FOR THAT RAY AND LIMIT: tmax <= 0, a light within bias of the receiver, is never occluded.
+ *   POINT    : SKIPPED when range > 0 && r > range; g = cr / r2.  color is the intensity (irradiance at distance 1, facing the light).
+ *   SPOT     : POINT's rule, then s^ = direction / sqrt((dx dx + dy dy) + dz dz); cs = -((s^x wx + s^y wy) + s^z wz);
+ *              x = (cs - cos_outer) / (cos_inner - cos_outer); SKIPPED unless x > 0; x = min(x, 1.0); f = (x * x) * (3.0 - 2.0 * x);
+ *              g = (cr / r2) * f.
+ *   DIRECTIONAL: direction is the way the light travels: w = -s^; cr as above, SKIPPED unless cr > 0; o = a + w * bias, d = w,
+ *              tmax = +inf; g = cr.  color is the irradiance on a surface facing the light.
+ *   RECT     : corner position, edges u, v; color is the emitted radiance; the light emits toward N = cross(u, v) =
+ *              (uy vz - vy uz, vx uz - ux vz, ux vy - vx uy), the library's cross.  A = sqrt((Nx Nx + Ny Ny) + Nz Nz); N^ = N / A.  Sample j
+ *              has index k = sample_base + j; xi1, xi2 are words 0 and 1 of the Philox block of (seed, pixel = id, sample = k) at depth
+ *              0xFFFE, block l for light index l (a depth no path vertex and no camera draw has; a word w is (w + 0.5) * 2^-32);
+ *              y = (position + u * xi1) + v * xi2; cl = -((N^x wx + N^y wy) + N^z wz), with MCPT_LIGHT_TWO_SIDED cl = fabs(cl); SKIPPED
+ *              unless cl > 0; g = ((cr * cl) / r2) * A.
+ *   g        : last, under every type: THE SLOT IS SKIPPED UNLESS g > 0 (a quotient that underflowed to zero, a NaN out of an overflow),
+ *              so that a slot is skipped exactly when its g is +0.0 and the fold can tell from g alone.
+ *   slots    : lights in order; a delta light (POINT, SPOT, DIRECTIONAL) has 1 slot, evaluated once whatever spp is, a RECT spp slots in
+ *              j order; R = mcpt_direct_slots is their sum; slot s of entry i sits at i * R + s.  mcpt_direct_rays writes, per slot, the
+ *              ray (rays6 [n*R][6]: o, d), tmax [n*R] and g [n*R]; for a skipped slot o = a, d = 0, tmax = 0, g = +0.0.  It runs on the
+ *              device, through the same functions as the query (csrc/direct.hpp).
+ *   fold     : per entry, for l = 0 .. nl - 1 in order: a slot's value is x[c] = color[c] * g when it was not skipped and its ray is not
+ *              occluded, else +0.0; traced_l = the slots of light l not skipped (g > 0), lit_l = those of them not occluded.  Delta light:
+ *              E_l = x, se2_l = 0.  RECT: s1 += x; s2 += x * x over j from +0.0; E_l = s1 / spp; se2_l = 0 when spp < 2, else
+ *              max((s2 - s1 * s1 / spp) / (spp - 1), 0) / spp, the radiance query's expression.  E += E_l; V += se2_l per channel, both
+ *              from +0.0.  irradiance3[i] = E; stderr3[i] = sqrt(V); per_light3[i][l] = E_l; visibility[i][l] = traced_l ?
+ *              (double)lit_l / (double)traced_l : +0.0.  irradiance3 [n][3] is required; stderr3 [n][3], per_light3 [n][nl][3] and
+ *              visibility [n][nl] may be NULL.  nl == 0: every output that is asked for is written with +0.0.
+ *              mcpt_direct_fold_host is this fold alone, on the CPU and without a device, over g [n*R] and occluded [n*R] (non-zero:
+ *              occluded); it reads `traced` from g > 0 and does not otherwise look at the values.
+ *   lights   : a HOST array in every form, like the parameter structs.  The device turns it into a table of its own (a pinned copy and a
+ *              device copy it keeps between calls, 160 bytes a light) before the call returns: THE CALLER MAY FREE OR OVERWRITE lights AS
+ *              SOON AS A _device CALL HAS RETURNED.  A call first waits for the event behind the device's previous direct-light call.
+ *   map      : mcpt_bake_direct_lightmap takes everything but the fold from the lightmap baker: the chart, coverage, texel list and owner of
+ *              mcpt_lightmap_texels for a width x height map, unchanged.  A DIRECT LIGHTMAP IS, BIT FOR BIT, mcpt_query_direct OVER
+ *              mcpt_lightmap_texels' LIST WITH ids = texels.  scatter: the four answers of the entry of texel T go to irradiance3[T],
+ *              stderr3[T], per_light3[T], visibility[T] as they are (irradiance needs no factor pi here); every texel that is not covered
+ *              gets +0.0.  dilation: `dilate` rounds, 0 .. 64, of the lightmap's rule on irradiance3 alone; stderr3, per_light3 and
+ *              visibility of filled texels stay 0.  irradiance3 [W*H*3] is required; stderr3 [W*H*3], per_light3 [W*H*nl*3], visibility
+ *              [W*H*nl] and owner [W*H] may be NULL.  stats are the query's over the covered texels.  No texel covered: MCPT_OK, no query
+ *              is launched.
+ *   state    : what mcpt_trace_any_device sees: the device's trace mode (MCPT_TRACE_REFERENCE answers every ray by the definition), key 0
+ *              of a motion, a geometry that stands after updates.
+ *   stats    : rays_primary = the shadow rays walked, that is, the slots not skipped; node_visits, tri_tests, launches = 1 and ms_trace
+ *              (= ms_total) from events around the launch; the other fields are 0.
+ * The host-pointer forms are synchronous and copy in and out around the device forms.  The _device forms take device pointers throughout
+ * but for the lights and the structs, and enqueue on `stream`; the query returns without waiting, THE MAP'S DEVICE FORM WAITS ONCE FOR THE
+ * STREAM, for the number of covered texels, as mcpt_bake_lightmap_device does (and again when stats are asked for), and first waits for
+ * the device's previous bake; besides the baker's raster and list it keeps 48 + 32 nl bytes per covered texel and, with dilation, 28 per
+ * texel.  They add to the counters of mcpt_trace_closest_device and, like it, MUST NOT OVERLAP ANOTHER CLOSEST-HIT OR ANY-HIT CALL OF THE
+ * SAME DEVICE ON ANOTHER STREAM.  Calls are allowed while progressive handles of the device live: they touch none of a handle's state.
+ * (The pointer parameters are spelled dev_*, not d_*, as the any-hit block's: tests/test_gpu_direct.py holds these calls' extents.)
+ * Errors (MCPT_ERR_ARG, before MCPT_ERR_NO_DEVICE, in this order): NULL parameters; spp < 1; sample_base < 0; sample_base + spp > 2^31 - 1;
+ * bias not finite or < 0; flags != 0; reserved != 0; nl < 0 or nl > 4096 (the Philox block field has 16 bits); NULL lights with nl > 0;
+ * then per light, in index order, looking only at the fields its type reads (POINT: position, color, range; SPOT: those, direction and
+ * the cosines; DIRECTIONAL: direction, color; RECT: position, u, v, color; flags and type of every light): an unknown type; a flag other
+ * than MCPT_LIGHT_TWO_SIDED, or that flag on a light that is not a RECT; a component that is not finite; a direction of zero or
+ * non-finite length; a cross(u, v) of zero or non-finite length; cosines not within -1 <= cos_outer < cos_inner <= 1; range < 0; then
+ * n < 0 or n > 2^31 - 1; n * R > 2^31 - 1; NULL q6 or irradiance3 with n > 0 (mcpt_direct_rays: NULL q6, or NULL rays6, tmax or g with
+ * n * R > 0; mcpt_direct_fold_host: NULL irradiance3, or NULL g or occluded with n * R > 0); the host-pointer forms: the list checks of
+ * the hemisphere kind (a negative id, a component that is not finite, a normal of length zero or not finite).  mcpt_direct_slots: spp < 1,
+ * then the lights' errors; it returns R >= 0 or the negative error code.  The map: a NULL mcpt_direct_map; a size outside 1 .. 16384;
+ * dilate outside 0 .. 64; its reserved != 0; then the parameters' and lights' errors as above; NULL irradiance3; in the host-pointer form
+ * a chart component that is not finite, after the missing device, as in mcpt_bake_lightmap; covered * R > 2^31 - 1, once the raster has
+ * counted the covered texels.  n == 0: MCPT_OK, nothing is launched and nothing is written.  A table, a workspace or a copy that cannot
+ * be allocated: MCPT_ERR_NOMEM, and the device stays usable.
+ * Not covered: light from these lights after its first bounce (nothing here enters the integrator); textured, IES or sphere lights;
+ * stratified rectangle samples; adaptive sampling, and denoising the map; these lights in mcpt_render_baked (the caller adds the map to
+ * an indirect bake: irradiance is linear); any-hit in the engines and refill of lanes that finish early; the multi-device group
+ * (mcpt_multi_*) and render_scene. */
+#define MCPT_LIGHT_POINT       0
+#define MCPT_LIGHT_SPOT        1
+#define MCPT_LIGHT_DIRECTIONAL 2
+#define MCPT_LIGHT_RECT        3
+#define MCPT_LIGHT_TWO_SIDED   1   /* flags; RECT only */
+typedef struct { int32_t type, flags; double position[3], direction[3], u[3], v[3], color[3];
+                 double cos_inner, cos_outer, range; } mcpt_direct_light;                         /* 152 bytes */
+typedef struct { int32_t spp, sample_base; uint64_t seed; double bias; int32_t flags, reserved[3]; } mcpt_direct_params;   /* 40 bytes; flags == 0 */
+typedef struct { int32_t width, height, dilate, reserved; } mcpt_direct_map;                      /* 16 bytes */
+int mcpt_query_direct(mcpt_device*, const double* q6, const int32_t* ids, int64_t n, const mcpt_direct_light* lights, int32_t nl,
+                      const mcpt_direct_params*, double* irradiance3, double* stderr3, double* per_light3, double* visibility, mcpt_stats*);
+int mcpt_query_direct_device(mcpt_device*, const double* dev_q6, const int32_t* dev_ids, int64_t n, const mcpt_direct_light* lights,
+                             int32_t nl, const mcpt_direct_params*, double* dev_irradiance3, double* dev_stderr3, double* dev_per_light3,
+                             double* dev_visibility, void* stream);
+int64_t mcpt_direct_slots(const mcpt_direct_light* lights, int32_t nl, int32_t spp);             /* R: slots per entry; < 0: MCPT_ERR_* */
+int mcpt_direct_rays(mcpt_device*, const double* q6, const int32_t* ids, int64_t n, const mcpt_direct_light* lights, int32_t nl,
+                     const mcpt_direct_params*, double* rays6, double* tmax, double* g);          /* test seam: [n*R][6], [n*R], [n*R] */
+int mcpt_direct_fold_host(const mcpt_direct_light* lights, int32_t nl, const mcpt_direct_params*, const double* g, const uint8_t* occluded,
+                          int64_t n, double* irradiance3, double* stderr3, double* per_light3, double* visibility);   /* no device */
+int mcpt_bake_direct_lightmap(mcpt_device*, const double* uv6, const mcpt_direct_map*, const mcpt_direct_light* lights, int32_t nl,
+                              const mcpt_direct_params*, double* irradiance3, double* stderr3, double* per_light3, double* visibility,
+                              int32_t* owner, mcpt_stats*);
+int mcpt_bake_direct_lightmap_device(mcpt_device*, const double* dev_uv6, const mcpt_direct_map*, const mcpt_direct_light* lights, int32_t nl,
+                                     const mcpt_direct_params*, double* dev_irradiance3, double* dev_stderr3, double* dev_per_light3,
+                                     double* dev_visibility, int32_t* dev_owner, mcpt_stats*, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -269,6 +269,24 @@ class PairParams(C.Structure):
     _fields_ = [("t0", C.c_double), ("t1", C.c_double), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DirectLight(C.Structure):
+    """mcpt_direct_light: one of a caller's own lights -- type (MCPT_LIGHT_*), flags (MCPT_LIGHT_TWO_SIDED on a rectangle), position,
+    direction (the way the light travels), the rectangle's edges u and v, colour, a spot's two cosines and a point or spot light's range"""
+    _fields_ = [("type", C.c_int32), ("flags", C.c_int32), ("position", C.c_double * 3), ("direction", C.c_double * 3), ("u", C.c_double * 3),
+                ("v", C.c_double * 3), ("color", C.c_double * 3), ("cos_inner", C.c_double), ("cos_outer", C.c_double), ("range", C.c_double)]
+
+
+class DirectParams(C.Structure):
+    """mcpt_direct_params: samples per rectangle light, first sample index, seed, the shadow rays' offset along themselves, flags (0)"""
+    _fields_ = [("spp", C.c_int32), ("sample_base", C.c_int32), ("seed", C.c_uint64), ("bias", C.c_double), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class DirectMap(C.Structure):
+    """mcpt_direct_map: a direct lightmap's size and dilation rounds"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("dilate", C.c_int32), ("reserved", C.c_int32)]
+
+
 # every symbol include/mcpt.h declares
 EXPORTS = [
     "mcpt_version", "mcpt_last_error", "mcpt_device_count", "mcpt_build_id",
@@ -323,6 +341,8 @@ EXPORTS = [
     "mcpt_query_occlusion", "mcpt_query_occlusion_device", "mcpt_occlusion_fold_host",
     "mcpt_bake_occlusion_lightmap", "mcpt_bake_occlusion_lightmap_device",
     "mcpt_trace_any", "mcpt_trace_any_device", "mcpt_pair_rays", "mcpt_trace_any_pairs", "mcpt_trace_any_pairs_device",
+    "mcpt_query_direct", "mcpt_query_direct_device", "mcpt_direct_slots", "mcpt_direct_rays", "mcpt_direct_fold_host",
+    "mcpt_bake_direct_lightmap", "mcpt_bake_direct_lightmap_device",
 ]
 
 
@@ -573,6 +593,15 @@ def lib():
     L.mcpt_pair_rays.argtypes = [D, C.c_int64, D, C.c_int64, PP, D, D]
     L.mcpt_trace_any_pairs.argtypes = [P, D, C.c_int64, D, C.c_int64, PP, U64, C.POINTER(Stats)]
     L.mcpt_trace_any_pairs_device.argtypes = [P, P, C.c_int64, P, C.c_int64, PP, P, P]
+    DL, DP, DM = C.POINTER(DirectLight), C.POINTER(DirectParams), C.POINTER(DirectMap)
+    L.mcpt_query_direct.argtypes = [P, D, I32, C.c_int64, DL, C.c_int32, DP, D, D, D, D, C.POINTER(Stats)]
+    L.mcpt_query_direct_device.argtypes = [P, P, P, C.c_int64, DL, C.c_int32, DP, P, P, P, P, P]
+    L.mcpt_direct_slots.argtypes = [DL, C.c_int32, C.c_int32]
+    L.mcpt_direct_slots.restype = C.c_int64
+    L.mcpt_direct_rays.argtypes = [P, D, I32, C.c_int64, DL, C.c_int32, DP, D, D, D]
+    L.mcpt_direct_fold_host.argtypes = [DL, C.c_int32, DP, D, U8, C.c_int64, D, D, D, D]
+    L.mcpt_bake_direct_lightmap.argtypes = [P, D, DM, DL, C.c_int32, DP, D, D, D, D, I32, C.POINTER(Stats)]
+    L.mcpt_bake_direct_lightmap_device.argtypes = [P, P, DM, DL, C.c_int32, DP, P, P, P, P, P, C.POINTER(Stats), P]
     _lib = L
     return L
 

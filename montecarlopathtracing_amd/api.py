@@ -7,7 +7,7 @@ import numbers
 import numpy as np
 
 from . import _lib
-from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, BakedSpecular, BakedSpecularOutputs, ReflectionParams, ReflectionChain, OcclusionParams, OcclusionMap, PairParams, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
+from ._lib import AdaptiveParams, CameraKey, DenoiseParams, DisplayInfo, DisplayParams, GuideParams, Environment, FastInfo, Lens, LightSampling, McptError, MotionInfo, Noise, QueryParams, ShParams, LightmapParams, LightmapDenoiseParams, VolumeGrid, VisibilityParams, VolumeVisibility, BakedSource, BakedOutputs, BakedFrameParams, BakedSpecular, BakedSpecularOutputs, ReflectionParams, ReflectionChain, OcclusionParams, OcclusionMap, PairParams, DirectLight, DirectParams, DirectMap, Shutter, RenderParams, RenderSceneOptions, SceneDesc, SceneInfo, Stats, UpdateInfo, check, lib
 
 
 TRACE_FAST, TRACE_REFERENCE = 0, 1
@@ -562,6 +562,93 @@ def pair_rays(a, b, t0=0.0, t1=1.0):
     tmax = C.c_double(pp.t1 - pp.t0)
     check(lib().mcpt_pair_rays(_p(a, C.c_double), na, _p(b, C.c_double), nb, C.byref(pp), _p(rays, C.c_double), C.byref(tmax)))
     return rays, tmax.value
+
+
+LIGHT_POINT, LIGHT_SPOT, LIGHT_DIRECTIONAL, LIGHT_RECT = 0, 1, 2, 3
+LIGHT_TWO_SIDED = 1
+
+
+def _vec3(v, name):
+    v = np.asarray(v, dtype=np.float64)
+    if v.shape != (3,):
+        raise ValueError("%s must have 3 components" % name)
+    return (C.c_double * 3)(*v.tolist())
+
+
+def _light(type_, flags=0, position=(0, 0, 0), direction=(0, 0, 0), u=(0, 0, 0), v=(0, 0, 0), color=(1, 1, 1), cos_inner=0.0, cos_outer=0.0, range=0.0):
+    return DirectLight(int(type_), int(flags), _vec3(position, "position"), _vec3(direction, "direction"), _vec3(u, "u"), _vec3(v, "v"),
+                       _vec3(color, "color"), float(cos_inner), float(cos_outer), float(range))
+
+
+def point_light(position, color, range=0.0):
+    """A point light for Device.direct_light (mcpt_direct_light, MCPT_LIGHT_POINT): color is its intensity, the irradiance it sends to a
+    surface that faces it at distance 1; range > 0 cuts it off beyond that distance."""
+    return _light(LIGHT_POINT, position=position, color=color, range=range)
+
+
+def spot_light(position, direction, color, inner_degrees, outer_degrees, range=0.0):
+    """A spot light (MCPT_LIGHT_SPOT): a point light that shines along `direction`, in full within inner_degrees of it and not at all
+    beyond outer_degrees, a smoothstep of the cosine between them.  The half-angles become the record's cosines here."""
+    return _light(LIGHT_SPOT, position=position, direction=direction, color=color, cos_inner=math.cos(math.radians(float(inner_degrees))),
+                  cos_outer=math.cos(math.radians(float(outer_degrees))), range=range)
+
+
+def directional_light(direction, color):
+    """A directional light (MCPT_LIGHT_DIRECTIONAL): `direction` is the way the light travels, color the irradiance on a surface that
+    faces it."""
+    return _light(LIGHT_DIRECTIONAL, direction=direction, color=color)
+
+
+def rect_light(corner, u, v, color, two_sided=False):
+    """A rectangle light (MCPT_LIGHT_RECT): the parallelogram corner + s u + t v, 0 <= s, t <= 1, of emitted radiance `color`, shining
+    toward cross(u, v) -- the library's cross -- or, two_sided, both ways."""
+    return _light(LIGHT_RECT, flags=LIGHT_TWO_SIDED if two_sided else 0, position=corner, u=u, v=v, color=color)
+
+
+def _lights(lights):
+    """a sequence of DirectLight records as one contiguous ctypes array (None for an empty one) and its length"""
+    lights = list(lights)
+    for L in lights:
+        if not isinstance(L, DirectLight):
+            raise ValueError("lights must be DirectLight records (point_light, spot_light, directional_light, rect_light)")
+    return ((DirectLight * len(lights))(*lights) if lights else None), len(lights)
+
+
+def _direct_params(spp, bias, seed, sample_base):
+    for name, v in (("spp", spp), ("sample_base", sample_base)):
+        if not isinstance(v, numbers.Integral) or not -2 ** 31 <= v < 2 ** 31:
+            raise ValueError("%s must be a 32-bit integer" % name)
+    return DirectParams(int(spp), int(sample_base), int(seed), float(bias), 0, (C.c_int32 * 3)(0, 0, 0))
+
+
+def direct_slots(lights, spp=1):
+    """R, the shadow-ray slots of one receiver under `lights` (mcpt_direct_slots; no device): 1 per point, spot or directional light,
+    spp per rectangle."""
+    arr, nl = _lights(lights)
+    if not isinstance(spp, numbers.Integral) or not -2 ** 31 <= spp < 2 ** 31:
+        raise ValueError("spp must be a 32-bit integer")
+    R = lib().mcpt_direct_slots(arr, nl, int(spp))
+    if R < 0:
+        check(int(R))
+    return int(R)
+
+
+def direct_fold_host(lights, g, occluded, n, spp=1):
+    """The direct-light fold alone, on the CPU (mcpt_direct_fold_host; no device): g [n * R] the slots' factors as Device.direct_rays
+    writes them (+0.0: a skipped slot) and occluded [n * R] their shadow rays' answers (Device.any_hit of those rays and limits).
+    Returns what Device.direct_light returns, bit for bit."""
+    arr, nl = _lights(lights)
+    dp = _direct_params(spp, 0.0, 0, 0)
+    R = direct_slots(lights, spp)
+    n = int(n)
+    g = np.ascontiguousarray(g, dtype=np.float64)
+    occ = np.ascontiguousarray(np.asarray(occluded) != 0, dtype=np.uint8)
+    if g.shape != (n * R,) or occ.shape != (n * R,):
+        raise ValueError("g and occluded must have shape (%d,)" % (n * R))
+    E, err, pl, vis = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, nl, 3)), np.zeros((n, nl))
+    check(lib().mcpt_direct_fold_host(arr, nl, C.byref(dp), _p(g, C.c_double), _p(occ, C.c_uint8), n, _p(E, C.c_double), _p(err, C.c_double),
+                                      _p(pl, C.c_double), _p(vis, C.c_double)))
+    return {"irradiance": E, "stderr": err, "per_light": pl, "visibility": vis}
 
 
 def _adaptive_params(rel_target, abs_target, min_spp):
@@ -1398,6 +1485,63 @@ class Device:
         b [nb, 3] float64, bits [na, (nb + 63) // 64] uint64."""
         pp = PairParams(float(t0), float(t1), 0, 0)
         check(lib().mcpt_trace_any_pairs_device(self._h, _dp(d_a_ptr), int(na), _dp(d_b_ptr), int(nb), C.byref(pp), _dp(d_bits_ptr), _dp(stream)))
+
+    def _direct_list(self, points, normals, ids):
+        points = np.asarray(points, dtype=np.float64)
+        normals = np.asarray(normals, dtype=np.float64)
+        if points.ndim != 2 or points.shape[1] != 3 or normals.shape != points.shape:
+            raise ValueError("points and normals must both have shape (n, 3)")
+        return self._query_list(np.concatenate([points, normals], axis=1), ids, "points and normals")
+
+    def direct_light(self, points, normals, lights, spp=1, bias=0.01, seed=0, ids=None, sample_base=0, stats=None):
+        """Direct light from the caller's own lights at surface points (mcpt_query_direct): `lights` is a sequence of point_light,
+        spot_light, directional_light and rect_light records; every shadow ray is formed and walked on the GPU and leaves the point by
+        `bias` along itself; a rectangle takes spp samples, drawn from (seed, id, sample_base + j), the other lights one.  Returns a
+        dict: irradiance [n, 3], stderr [n, 3] (the rectangles' sampling error), per_light [n, nl, 3] and visibility [n, nl], the share
+        of a light's shadow rays that reached it (0 where none was shot) -- direct_fold_host() of any_hit() of direct_rays(), bit for
+        bit."""
+        q, ids = self._direct_list(points, normals, ids)
+        arr, nl = _lights(lights)
+        dp = _direct_params(spp, bias, seed, sample_base)
+        n = q.shape[0]
+        E, err, pl, vis = np.zeros((n, 3)), np.zeros((n, 3)), np.zeros((n, nl, 3)), np.zeros((n, nl))
+        check(lib().mcpt_query_direct(self._h, _p(q, C.c_double), _p(ids, C.c_int32), n, arr, nl, C.byref(dp), _p(E, C.c_double), _p(err, C.c_double),
+                                      _p(pl, C.c_double), _p(vis, C.c_double), C.byref(stats) if stats is not None else None))
+        return {"irradiance": E, "stderr": err, "per_light": pl, "visibility": vis}
+
+    def direct_rays(self, points, normals, lights, spp=1, bias=0.01, seed=0, ids=None, sample_base=0):
+        """The shadow rays direct_light() forms, written out (mcpt_direct_rays, the test seam): per entry R = direct_slots(lights, spp)
+        slots, the lights in order and a rectangle's samples in order.  Returns (rays [n * R, 6], tmax [n * R], g [n * R]); a skipped
+        slot has a zero direction, tmax 0 and g +0.0."""
+        q, ids = self._direct_list(points, normals, ids)
+        arr, nl = _lights(lights)
+        dp = _direct_params(spp, bias, seed, sample_base)
+        n = q.shape[0]
+        m = n * direct_slots(lights, spp)
+        rays, tmax, g = np.zeros((m, 6)), np.zeros(m), np.zeros(m)
+        check(lib().mcpt_direct_rays(self._h, _p(q, C.c_double), _p(ids, C.c_int32), n, arr, nl, C.byref(dp), _p(rays, C.c_double), _p(tmax, C.c_double),
+                                     _p(g, C.c_double)))
+        return rays, tmax, g
+
+    def bake_direct_lightmap(self, width, height, lights, spp=1, uv=None, bias=0.01, seed=0, sample_base=0, dilate=0, stats=None):
+        """A direct lightmap (mcpt_bake_direct_lightmap): direct_light() of lightmap_texels()' list with ids = texels, bit for bit, put
+        back into the map; dilate rounds of the lightmap's rule fill the gutters of the irradiance alone.  Returns a dict: irradiance and
+        stderr [height, width, 3], per_light [height, width, nl, 3], visibility [height, width, nl] and owner [height, width], which is
+        bake_lightmap()'s."""
+        width, height = _map_size(width, height)
+        if not isinstance(dilate, numbers.Integral) or not -2 ** 31 <= dilate < 2 ** 31:
+            raise ValueError("dilate must be a 32-bit integer")
+        arr, nl = _lights(lights)
+        dp = _direct_params(spp, bias, seed, sample_base)
+        uv = _chart(uv, self.scene.info.num_faces) if uv is not None else None
+        shape = (max(height, 0), max(width, 0))
+        E, err, pl, vis = np.zeros(shape + (3,)), np.zeros(shape + (3,)), np.zeros(shape + (nl, 3)), np.zeros(shape + (nl,))
+        owner = np.zeros(shape, dtype=np.int32)
+        dm = DirectMap(width, height, int(dilate), 0)
+        check(lib().mcpt_bake_direct_lightmap(self._h, _p(uv, C.c_double), C.byref(dm), arr, nl, C.byref(dp), _p(E, C.c_double), _p(err, C.c_double),
+                                              _p(pl, C.c_double), _p(vis, C.c_double), _p(owner, C.c_int32),
+                                              C.byref(stats) if stats is not None else None))
+        return {"irradiance": E, "stderr": err, "per_light": pl, "visibility": vis, "owner": owner}
 
     def lightmap_irradiance(self, E, uv, owner=None):
         """A lightmap's lookup by chart coordinate on the GPU (mcpt_lightmap_irradiance): lightmap_irradiance_host's arguments and

@@ -16,6 +16,7 @@
 //   visibility_api.cpp  probe visibility: the octahedral bin, the depth-moment bake of a probe list or grid, the visibility-weighted lookup
 //   occlusion_api.cpp  ambient occlusion: the hemisphere rays of a point list folded into occlusion and bent normals, and that query as a map
 //   any_hit_api.cpp   any-hit rays: is anything in the way of a ray before its limit, for a ray list and for the matrix of two point lists' pairs
+//   direct_api.cpp    direct light from a caller's own point, spot, directional and rectangle lights: a fused shadow-ray query, and that query as a map
 //   baked_api.cpp     baked frames: the lightmap's lookup by chart coordinate, baked radiance along a caller's rays, frames lit by a bake
 //   reflection_api.cpp  reflection probes: an octahedral radiance map per probe through the ray query, its Phong prefilter, the chain's lookup
 //   render_scene.cpp  output writers, checkpoints, render_scene
@@ -201,7 +202,7 @@ struct mcpt_device {
     bool geometry_failed = false;                   // an update failed midway: nothing is traced or rendered until one succeeds
     // display transform (display_api.cpp): the luminance histogram's slots and their pinned copy, made on the first call that takes one
     mcpt::DevBuf<unsigned long long> disp_slots; mcpt::HostBuf<int64_t> h_disp_slots;
-    // The six workspaces below are kept between calls; a call holds one through its `done` event, by staging.hpp's lease.
+    // The seven workspaces below are kept between calls; a call holds one through its `done` event, by staging.hpp's lease.
     // lightmap baking (lightmap_api.cpp): what a bake keeps between its kernels, made by the first one and grown to the largest map so far
     struct Lightmap {
         mcpt::DevBuf<int32_t> owner[2], slot_of_face, big, block_counts, block_offsets, total;
@@ -215,6 +216,9 @@ struct mcpt_device {
         // by list entry, 48 bytes per covered texel: ao [c], stderr [c], bent [c][3]; hits [c], back [c]
         mcpt::DevBuf<double> occ;
         mcpt::DevBuf<int32_t> occ_cnt;
+        // a direct-light map (direct_api.cpp) does the same and keeps, by list entry, irradiance [c][3], stderr [c][3], irradiance by
+        // light [c][nl][3] and visibility by light [c][nl]: 48 + 32 nl bytes per covered texel
+        mcpt::DevBuf<double> direct;
         mcpt::HostBuf<int32_t> h_total;                 // pinned word the covered count lands in
         mcpt::Event done;
         // the denoiser (lightmap_denoise_api.cpp) shares owner[], irr and `done` with the bakes and keeps, per texel of the largest map it
@@ -268,6 +272,14 @@ struct mcpt_device {
         mcpt::Event done;
     };
     std::unique_ptr<Reflection> refl;
+    // direct light (direct_api.cpp): the light table of a call (direct.hpp: DirectLight, 160 bytes a light) in a pinned copy, which the
+    // caller's lights are turned into before the call returns, and the device copy the kernels read, grown to the longest table so far
+    struct Direct {
+        mcpt::HostBuf<char> h_lights;
+        mcpt::DevBuf<char> lights;
+        mcpt::Event done;
+    };
+    std::unique_ptr<Direct> direct;
 };
 
 // The helpers below are the library's own: none of them is exported from libmcpt.so.
